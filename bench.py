@@ -11,6 +11,13 @@ gradient + dual average, PSD projection.  Nothing is skipped inside the timed re
     python bench.py --gpus 1 --steps 200 --warmup 20
     python bench.py --config c3                      (configs[2]: the rank ~128 regime)
     python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N ...   (N > 1)
+    python bench.py --full                           (everything below the headline, see --full)
+    python bench.py --dump-outputs bench_outputs     (the last timed step's outputs as bench_outputs/<name>.npy)
+
+A plain run sets the workload up, warms up, times the K steps and prints the headline.  `--full` adds what
+takes runs or checks of its own: the HIP-event roofline and per-kernel breakdown, where the trainer stands
+(LogStep block, the oracle's ROC sweep on the same W), pj-learn's own loop from W = 0 (`reference_run`), the
+other BASELINE configurations (`other_configs`, N > 1: `other_modes`) and the CPU baseline.
 
 The configuration BASELINE quotes is a trainer whose learned rank has settled near 64; from
 the reference's start (W = 0, every pair violates, rank of a few hundred) that takes about 300
@@ -288,6 +295,40 @@ def reference_run(dlco, wl, data_ctx, iters, logstep, kw):
                     "`value` times steady-state steps only, like the reference's Ttime per 100 steps divided out)"}
 
 
+DUMP_SAMPLE = 1 << 21          # elements kept of an output larger than this: a fixed, seeded sample (8 MB in fp32)
+DUMP_W_MAX = 1 << 23           # W is written whole up to this many elements (32 MB; rank ~64 at F = 8192 is 0.5 M)
+
+
+def _fixed_sample(a, n):
+    """`a` itself, or (more than n elements) the elements at n flat positions drawn by numpy's default_rng(0), sorted,
+    duplicates dropped: the same positions in every run of the same shape."""
+    if a.size <= n:
+        return a
+    idx = np.unique(np.random.default_rng(0).integers(0, a.size, n))
+    return a.reshape(-1)[idx]
+
+
+def dump_outputs(ctx, outdir, shard):
+    """--dump-outputs DIR: what the timed path handed its caller after its last timed step, as DIR/<name>.npy (float32;
+    integer outputs as float64, exact): W (rows sqrt(e) v^T), A = W^T W and the dual average (F x F: whole up to
+    DUMP_SAMPLE elements, else `<name>_sample`, a fixed sample), and that step's batch - the sampled row ids, their
+    squared distances and violation counts.  At most ~50 MB in all."""
+    os.makedirs(outdir, exist_ok=True)
+    getters = [("W", ctx.W, DUMP_W_MAX), ("A", ctx.A, DUMP_SAMPLE)]
+    if not shard:                                          # a sharded rank holds a column slab of the dual average only
+        getters.append(("dfavg", ctx.dfavg, DUMP_SAMPLE))
+    outs = {}
+    for name, get, cap in getters:
+        M = get()
+        outs[name if M.size <= cap else name + "_sample"] = _fixed_sample(M, cap)
+    b = ctx.batch()
+    outs.update(batch_pos_rows=b["pos_rows"], batch_neg_rows=b["neg_rows"], batch_pos_dist=b["pd"], batch_neg_dist=b["nd"],
+                batch_rho=b["rho"], batch_kappa=b["kappa"])
+    for name, a in outs.items():
+        a = np.asarray(a)
+        np.save(os.path.join(outdir, name + ".npy"), a.astype(np.float32 if a.dtype == np.float32 else np.float64))
+
+
 def self_launch(args, argv):
     """`python bench.py --gpus N` with N > 1 and no WORLD_SIZE in the environment: this process becomes the launcher.  It
     has not imported torch.cuda, the product library or anything else that touches HIP (and never will): it starts
@@ -345,6 +386,7 @@ def dry_launch(args):
     if rank == 0:
         print(json.dumps({"metric": "pj-learn patch-pairs/sec", "dry_launch": True, "value": 2.0 * 8 * args.steps * world / float(tmax.item()),
                           "unit": "pair-rows/s", "n_gpus": world, "ranks_joined": int(ranks.item()), "steps": args.steps, "warmup": args.warmup,
+                          "ms_per_step": float(tmax.item()) / args.steps * 1e3,
                           "data": "synthetic (CPU oracle, launcher rehearsal: not a measurement)"}), flush=True)
     tr.close()
     dist.destroy_process_group()
@@ -459,7 +501,17 @@ def main():
                     help="rehearse the N-rank launch on the CPU (gloo + the oracle's step on a toy problem): no GPU is touched")
     ap.add_argument("--no-other-configs", action="store_true",
                     help="single GPU, default workload: skip the short configs[2] and configs[4] runs reported as other_configs")
+    ap.add_argument("--full", action="store_true",
+                    help="besides the headline: HIP events around the gradient in the timed steps and a breakdown run after them "
+                         "(roofline, step_roofline, breakdown_ms_per_step), the trainer's state with the oracle's ROC sweep, "
+                         "reference_run, other_configs / other_modes and cpu_baseline (each --no-* / --reference-iters 0 still "
+                         "drops its part); off: set up, warm up, time --steps, print the headline")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps write what the last one computed (W, A, the dual average, the batch) as "
+                         "DIR/<name>.npy; F x F outputs as a fixed seeded sample of %d elements" % DUMP_SAMPLE)
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
 
     # N > 1 without a launcher around us: become the launcher BEFORE anything touches the GPU (see self_launch)
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
@@ -538,8 +590,56 @@ def main():
     dev_name, _, _ = ctx.device_name()
     B = R.Bg
 
+    def headline(dt, rank_now, nsteps):
+        """The fields of the result line that a plain run prints; --full adds to them."""
+        return {
+            "metric": "pj-learn patch-pairs/sec",
+            "value": 2.0 * B * args.steps / dt,
+            "unit": "pair-rows/s",
+            "n_gpus": world,
+            "steps": args.steps,
+            "warmup": args.warmup,
+            "ms_per_step": dt / args.steps * 1e3,
+            "higher_is_better": True,
+            "scaling": R.scaling,
+            "vs_baseline": None,
+            "dtype": "bf16 (gradient MFMA inputs; f32 accumulate, f32 elsewhere)" if args.bf16 else "f32",
+            "data": "synthetic",
+            "config": {
+                "workload": "pj-learn %s: %d pair-rows x PR-dim %d, batch %d+%d per GPU (global %d+%d), mu=%g gamma=%g, %s, rank %d after %d steps"
+                            % (wl["name"], N, F, B // world, B // world, B, B, wl["mu"], wl["gamma"],
+                               "bf16 MFMA + fp32 accumulate in the gradient, projection and statistics GEMMs (configs[4] variant), fp32 elsewhere"
+                               if args.bf16 else "fp32", rank_now, nsteps)
+                            + (" [pair mode: %d patch descriptors + Indices, differences formed in the kernels]" % args.patches
+                               if args.pair_mode else ""),
+                "generator": {k_: wl[k_] for k_ in ("latent", "sigma_pos", "sigma_neg", "noise", "jitter", "seed")},
+                "device": dev_name,
+                "burn_in_steps": args.burn_in,
+                "parallelism": ("dp%d (replicated data, batch slots sharded; dual average sharded by columns: all-gather of the "
+                                "2B distances and of the tracker products' column slabs, no F x F exchange; collectives issued by %s)"
+                                % (world, "the library through RCCL" if getattr(R.trainer, "native", False) else "a torch.distributed callback")) if R.shard else
+                               ("dp%d (replicated data, batch slots sharded, all-gather dists + all-reduce gradient)" % world),
+                "combinations_per_s": float(B) * B * args.steps / dt,
+            },
+        }
+
+    def finish(out):
+        if rank == 0:
+            sys.stdout.flush()
+            os.write(real_stdout, (json.dumps(out) + "\n").encode())
+        R.close()
+        if use_dist:
+            dist.destroy_process_group()
+
     R.run(args.burn_in)
     R.run(args.warmup)
+    if not args.full:
+        # a plain run: between the set-up and the result line nothing but the timed steps (no HIP events inside them)
+        dt = R.timed(args.steps)
+        if args.dump_outputs and rank == 0:
+            dump_outputs(ctx, args.dump_outputs, R.shard)
+        finish(headline(dt, ctx.W().shape[0], args.burn_in + args.warmup + args.steps))
+        return
     # timed region: HIP events around the dominant kernel only (two records per step); the other kernel groups are timed
     # over a second, untimed stretch of steps right after it - every event record costs queue time (all four groups: ~3 %
     # of the step), and `value` should not pay for the breakdown
@@ -551,6 +651,8 @@ def main():
     cn1 = ctx.counters()
     n_syrk, ms_syrk = ctx.profile_read("grad_syrk")
     ctx.profile_enable(0)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(ctx, args.dump_outputs, R.shard)       # before the breakdown steps below move the trainer on
     bsteps = 0 if args.no_profile else max(1, min(args.steps, 100))
     n_prod = n_jac = n_prj = n_ru = 0
     ms_prod = ms_jac = ms_prj = ms_ru = 0.0
@@ -605,36 +707,9 @@ def main():
     flops_pair_row = 2.0 * F * F + 2.0 * F * rank_now
     t_kernel_path = (ms_syrk / max(args.steps, 1) + ms_prj / bdiv) * 1e-3          # P1+P2 + Q1+U1 per step, HIP events
     t_prod = ms_prod / max(n_prod, 1) * 1e-3
-    out = {
-        "metric": "pj-learn patch-pairs/sec",
-        "value": value,
-        "unit": "pair-rows/s",
-        "n_gpus": world,
-        "steps": args.steps,
-        "warmup": args.warmup,
-        "ms_per_step": dt / args.steps * 1e3,
-        "higher_is_better": True,
-        "scaling": R.scaling,
-        "vs_baseline": None,
-        "dtype": "bf16 (gradient MFMA inputs; f32 accumulate, f32 elsewhere)" if args.bf16 else "f32",
-        "data": "synthetic",
-        "config": {
-            "workload": "pj-learn %s: %d pair-rows x PR-dim %d, batch %d+%d per GPU (global %d+%d), mu=%g gamma=%g, %s, rank %d after %d steps"
-                        % (wl["name"], N, F, B // world, B // world, B, B, wl["mu"], wl["gamma"],
-                           "bf16 MFMA + fp32 accumulate in the gradient, projection and statistics GEMMs (configs[4] variant), fp32 elsewhere"
-                           if args.bf16 else "fp32", rank_now, args.burn_in + args.warmup + args.steps + bsteps)
-                        + (" [pair mode: %d patch descriptors + Indices, differences formed in the kernels]" % args.patches
-                           if args.pair_mode else ""),
-            "generator": {k_: wl[k_] for k_ in ("latent", "sigma_pos", "sigma_neg", "noise", "jitter", "seed")},
-            "device": dev_name,
-            "burn_in_steps": args.burn_in,
-            "state_after_run": q,
-            "parallelism": ("dp%d (replicated data, batch slots sharded; dual average sharded by columns: all-gather of the "
-                            "2B distances and of the tracker products' column slabs, no F x F exchange; collectives issued by %s)"
-                            % (world, "the library through RCCL" if getattr(R.trainer, "native", False) else "a torch.distributed callback")) if shard else
-                           ("dp%d (replicated data, batch slots sharded, all-gather dists + all-reduce gradient)" % world),
-            "combinations_per_s": float(B) * B * args.steps / dt,
-        },
+    out = headline(dt, rank_now, args.burn_in + args.warmup + args.steps + bsteps)
+    out["config"]["state_after_run"] = q
+    out.update({
         "roofline": {
             "bound": "mfma",
             "pipe": ("bf16 MFMA (v_mfma_f32_32x32x16_bf16), operands rounded to bf16 once, fp32 accumulation" if args.bf16 else
@@ -719,7 +794,7 @@ def main():
             "eig_rank_update_passes_per_step": (cn1["rank_update_passes"] - cn0["rank_update_passes"]) / args.steps,
             "eig_locked_passes_per_step": (cn1["locked_passes"] - cn0["locked_passes"]) / args.steps,
         },
-    }
+    })
     # ---- N > 1: the other two modes SURVEY 8(d)/(e) and BASELINE configs[3] name, measured after the headline
     if world > 1 and not args.no_other_modes and not args.pair_mode:
         others = {}
@@ -757,11 +832,7 @@ def main():
             out["cpu_baseline"] = cpu_baseline(ctx, wl, args.cpu_rows, args.cpu_steps, args.cpu_t0)
         else:
             out["cpu_baseline"] = None
-        sys.stdout.flush()
-        os.write(real_stdout, (json.dumps(out) + "\n").encode())
-    R.close()
-    if use_dist:
-        dist.destroy_process_group()
+    finish(out)
 
 
 if __name__ == "__main__":

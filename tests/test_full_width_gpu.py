@@ -48,10 +48,24 @@ TOL_GRAD = 5e-6
 TOL_FPR = 1e-3
 
 
+def _host_threads():
+    """Host threads for the oracle's ssyevr: the CPUs this process may use (affinity mask, cgroup quota and
+    DLCO_CPU_THREADS, as bench.ncores counts them), cut to OMP_NUM_THREADS when that is set.  The affinity mask
+    alone can name every core of a large shared host, far more threads than the process is granted and than the
+    OpenBLAS build is made for."""
+    import bench
+    n = bench.ncores()
+    try:
+        n = min(n, int(os.environ.get("OMP_NUM_THREADS", "")))
+    except ValueError:
+        pass
+    return max(1, n)
+
+
 def _oracle_W(ref, dfavg, mu, gamma, t_last):
     """The reference's W for the dual average `dfavg` of iteration t_last (src/pj-learn.cpp:426-490)."""
     A = ref.dual_to_primal(dfavg, mu, gamma, t_last)
-    ref.set_threads(len(os.sched_getaffinity(0)))         # ssyevr at n = 8192: every core (the suite's default is one thread)
+    ref.set_threads(_host_threads())                      # ssyevr at n = 8192: every core we may use (the suite's default is one thread)
     W, ev = ref.psd_factor(A)
     ref.set_threads(1)
     del A

@@ -8,7 +8,7 @@ OUT=$ROOT/gpurun_out/profiles_new
 mkdir -p $OUT
 cd /tmp && export TMPDIR=/tmp
 rocprofv3 --pmc SQ_VALU_MFMA_BUSY_CYCLES SQ_BUSY_CU_CYCLES GRBM_GUI_ACTIVE SQ_WAVE_CYCLES SQ_WAIT_ANY SQ_WAIT_INST_ANY SQ_ACTIVE_INST_ANY \
-  --kernel-trace --output-format csv -d $OUT/pmc_sq -- python3 $ROOT/bench.py --no-cpu-baseline --reference-iters 0 --no-other-configs --steps 20 > $OUT/pmc_sq.json 2> $OUT/pmc_sq.log
+  --kernel-trace --output-format csv -d $OUT/pmc_sq -- python3 $ROOT/bench.py --full --no-cpu-baseline --reference-iters 0 --no-other-configs --steps 20 > $OUT/pmc_sq.json 2> $OUT/pmc_sq.log
 DLCO_ROUND=$R python3 - $OUT/pmc_sq $OUT <<'PY'
 import csv, glob, json, os, sys, collections
 d, out = sys.argv[1:3]
@@ -23,7 +23,7 @@ for r in rows:
         if key in r["Kernel_Name"]:
             agg[name][r["Counter_Name"]].append(float(r["Counter_Value"]))
 js = {"command": "rocprofv3 --pmc SQ_VALU_MFMA_BUSY_CYCLES SQ_BUSY_CU_CYCLES GRBM_GUI_ACTIVE SQ_WAVE_CYCLES SQ_WAIT_ANY SQ_WAIT_INST_ANY SQ_ACTIVE_INST_ANY "
-                 "--kernel-trace -- python3 bench.py --no-cpu-baseline --steps 20 (tools/collect_sq.sh); means over the last 20 launches of each kernel",
+                 "--kernel-trace -- python3 bench.py --full --no-cpu-baseline --steps 20 (tools/collect_sq.sh); means over the last 20 launches of each kernel",
       "note": "GRBM_GUI_ACTIVE is summed over the 8 XCDs (elapsed shader cycles = value / 8); SQ_VALU_MFMA_BUSY_CYCLES is summed over the 1024 SIMDs; "
               "mfma_util = MFMA_BUSY / (elapsed * 1024). SQ_WAVE_CYCLES / SQ_WAIT_* / SQ_ACTIVE_INST_ANY count quad-cycles per wave (MI355X guide, PMC section).",
       "kernels": {}}

@@ -6,10 +6,10 @@ ROOT=${GRAFT_REPO_ROOT:-$(pwd)}
 OUT=$ROOT/gpurun_out/$T
 mkdir -p $OUT
 cd /tmp && export TMPDIR=/tmp
-python3 $ROOT/bench.py --no-cpu-baseline --no-other-configs > $OUT/c2.json 2> $OUT/c2.err || exit 1
-python3 $ROOT/bench.py --no-cpu-baseline --config c3 > $OUT/c3.json 2> $OUT/c3.err || exit 1
-python3 $ROOT/bench.py --no-cpu-baseline --config ref544 > $OUT/ref544.json 2> $OUT/ref544.err || exit 1
-rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/stats -- python3 $ROOT/bench.py --no-cpu-baseline --reference-iters 0 --no-other-configs > $OUT/stats_bench.json 2> $OUT/stats.log || exit 1
+python3 $ROOT/bench.py --full --no-cpu-baseline --no-other-configs > $OUT/c2.json 2> $OUT/c2.err || exit 1
+python3 $ROOT/bench.py --full --no-cpu-baseline --config c3 > $OUT/c3.json 2> $OUT/c3.err || exit 1
+python3 $ROOT/bench.py --full --no-cpu-baseline --config ref544 > $OUT/ref544.json 2> $OUT/ref544.err || exit 1
+rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/stats -- python3 $ROOT/bench.py --full --no-cpu-baseline --reference-iters 0 --no-other-configs > $OUT/stats_bench.json 2> $OUT/stats.log || exit 1
 python3 $ROOT/tools/trace_breakdown.py $OUT/stats 200 $OUT/kernel_stats_timed.csv > $OUT/step_breakdown.txt
 rm -rf $OUT/stats
 python3 - $OUT <<'PY'
