@@ -248,8 +248,8 @@ int dlco_grad_rda(dlco_ctx *ctx, const int32_t *pos_rows_host, const int32_t *ne
 int dlco_psd_project(dlco_ctx *ctx, const float *dfavg_host, uint32_t t,
                      float *W_host, int32_t *r, float *A_host /* may be NULL */);
 /* Building block of E1 (no single reference line: the reference calls LAPACKE_ssyevr, :440):
- * out[rows,F] = X[rows,F] * G[F,F] for a symmetric G, rows <= 128.  mode 0 = fp32 MFMA (k-ordered
- * fmaf chain), mode 1 = two-way split-bf16 MFMA with fp32 accumulation (the Chebyshev filter;
+ * out[rows,F] = X[rows,F] * G[F,F] for a symmetric G, rows <= 128.  mode 0 = the generic fp32 MFMA GEMM (k-ordered
+ * fmaf chains, K slices summed in a fixed order: the tracker's products where no split-bf16 kernel applies), mode 1 = two-way split-bf16 MFMA with fp32 accumulation (the Chebyshev filter;
  * relative error ~1e-5), mode 2 = three-way split-bf16 MFMA (the Rayleigh-Ritz product when
  * F % 512 == 0; error at the level of fp32 rounding, ~1e-7).  Modes 3 / 4 (F == 8192 only) are modes 1 / 2 on the packed
  * upper-tile form of G that a single-rank trainer keeps its dual average in: only the upper triangle of G_host is read,

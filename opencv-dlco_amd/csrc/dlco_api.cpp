@@ -18,6 +18,32 @@ using namespace dlco;
 
 static thread_local std::string g_last_error;
 
+// Every environment variable the library reads (DESIGN.md §5 lists the same).  None is needed in production: each selects
+// a path that production takes elsewhere, is a test hook, or writes a trace that changes no result.  Each is read where
+// it has always been: per context, per tracker, or once per process by a function-local static.
+namespace {
+struct EnvSwitch { const char *name, *purpose; };
+const EnvSwitch kEnvSwitches[] = {
+    {"DLCO_SYRK_FP32", "gradient SYRK as the k-ordered fp32 MFMA chain (syrk_rda_kernel8) instead of split-bf16 planes"},
+    {"DLCO_NO_PACKED", "full F x F dual average where the packed upper-tile form would apply"},
+    {"DLCO_FORCE_SHARD", "column-sharded layout (cfg.shard) on a single rank: the multi-GPU path on one GPU"},
+    {"DLCO_NO_RANK_UPDATE", "first filter term from a product with the dual average, not from the step's rank update"},
+    {"DLCO_NO_LOCKING", "converged top Ritz pairs stay in the Chebyshev filter"},
+    {"DLCO_RANK_UPDATE_CHECK", "also form the product the rank update replaces and count the largest deviation"},
+    {"DLCO_TEST_JMW_TIMEOUT", "test hook: the multi-workgroup Jacobi gives up at its first grid barrier"},
+    {"DLCO_EIG_DEBUG", "trace of every tracker pass on stderr"},
+    {"DLCO_JACOBI_TRACE", "file: sweep time stamps of one single-workgroup Jacobi call"},
+    {"DLCO_SYRK_TRACE", "file: phase time stamps of one SYRK launch"},
+};
+}  // namespace
+
+const char *dlco::env_switch(const char *name)
+{
+    for (const EnvSwitch &s : kEnvSwitches)
+        if (std::strcmp(s.name, name) == 0) return std::getenv(name);
+    throw Error(-2, std::string("not an environment switch of the library: ") + name);
+}
+
 struct dlco_ctx {
     dlco_cfg cfg{};
     // F is the width every device buffer and kernel works at: the caller's FeatDim (Fu, src/pj-learn.cpp:176-179) rounded up
@@ -588,7 +614,6 @@ int dlco_ctx_create(dlco_ctx **out, const dlco_cfg *cfg)
         c = new dlco_ctx();
         c->cfg = *cfg;
         if (c->cfg.eig_tol <= 0.f) c->cfg.eig_tol = 2e-4f;
-        if (const char *e = std::getenv("DLCO_EIG_TOL")) { const float v = (float)std::atof(e); if (v > 0.f) c->cfg.eig_tol = v; }   // developer override
         if (c->cfg.eig_guard <= 0) c->cfg.eig_guard = 32;
         if (c->cfg.eig_max_iter <= 0) c->cfg.eig_max_iter = 40;
         DLCO_HIP(hipGetDeviceProperties(&c->prop, cfg->device));
@@ -597,7 +622,7 @@ int dlco_ctx_create(dlco_ctx **out, const dlco_cfg *cfg)
         c->Fu = cfg->F; c->N = cfg->N; c->B = cfg->B;
         c->Bl = cfg->B / cfg->world; c->lo = cfg->rank * c->Bl;
         // column-sharded dual average (world > 1, or forced for single-rank testing of the path)
-        c->shard = cfg->shard != 0 && (cfg->world > 1 || std::getenv("DLCO_FORCE_SHARD") != nullptr);
+        c->shard = cfg->shard != 0 && (cfg->world > 1 || env_switch("DLCO_FORCE_SHARD") != nullptr);
         // device width: whole 128-column tiles (whole tiles per rank when the columns are sharded)
         {
             const int gran = 128 * (c->shard ? cfg->world : 1);
@@ -635,7 +660,7 @@ int dlco_ctx_create(dlco_ctx **out, const dlco_cfg *cfg)
         c->act_ids.alloc(kcap); c->act_w.alloc(kcap); c->seed_ids.alloc(kcap); c->seed_w.alloc(kcap); c->act_slot.alloc(kcap);
         // one rank, packed dual average, the gradient's default arithmetic (its split planes are what the shortcut reads)
         c->planes_mode = syrk_planes_mode(cfg->grad_bf16 != 0);
-        c->rank_update = c->packed && cfg->world == 1 && c->planes_mode != 0 && std::getenv("DLCO_NO_RANK_UPDATE") == nullptr;
+        c->rank_update = c->packed && cfg->world == 1 && c->planes_mode != 0 && env_switch("DLCO_NO_RANK_UPDATE") == nullptr;
         c->eig->set_emit_guards(c->rank_update);
         c->dist_x.alloc(2 * B); c->pd.alloc(B); c->nd.alloc(B);
         c->xdist = c->dist_x.p; c->xgrad = c->grad.p;
@@ -1228,8 +1253,21 @@ int dlco_sym_product(dlco_ctx *c, const float *X_host, int32_t rows, const float
             ok = skinny_product_bf16x2(X.p, F, rows, G.p, F, F, F, 1.0f, out.p, F, nullptr, 0.f, nullptr, 0.f, hi.p, lo.p, slab.p,
                                        c->stream, 0, mode == 2 ? lo2.p : nullptr);
             sync(c);
-        } else {
-            ok = skinny_product_f32(X.p, F, rows, pad, G.p, F, F, F, 1.0f, out.p, F, nullptr, 0.f, nullptr, 0.f, c->stream);
+        } else {                                                 // the generic fp32 GEMM, K slices summed in order
+            GemmArgs g;
+            g.M = rows; g.N = F; g.K = F;
+            g.A.p = X.p; g.A.ld = F; g.A.kmajor = false;
+            g.B.p = G.p; g.B.ld = F; g.B.kmajor = true;
+            g.C = out.p; g.ldc = F;
+            const int bm = rows <= 64 ? 64 : 128;                // K slices as the tracker's products choose them
+            const long tiles = (long)((rows + bm - 1) / bm) * ((F + 127) / 128);
+            g.split_k = (int)std::max(1L, std::min((1023 + tiles) / tiles, (long)F / 256));
+            DevBuf<float> slab;
+            slab.alloc(gemm_slab_floats(rows, F, g.split_k));
+            g.slab = slab.p;
+            gemm_f32(g, c->stream);
+            sync(c);
+            ok = true;
         }
         DLCO_CHECK(ok, DLCO_ERR_INVALID, "dlco_sym_product: shape not supported by this mode");
         d2h_rows(c, out_host, out.p, (size_t)rows);

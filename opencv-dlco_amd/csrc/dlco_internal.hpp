@@ -36,6 +36,10 @@ struct Error : std::runtime_error {
         if (!(cond)) throw ::dlco::Error((code), std::string(msg));                \
     } while (0)
 
+// The value of one of the library's environment switches, nullptr when it is not set.  The library reads its environment
+// nowhere else: the switches and what each is for are listed beside it (dlco_api.cpp); a name outside that list throws.
+const char *env_switch(const char *name);
+
 // hipFuncSetAttribute(MaxDynamicSharedMemorySize) once per (kernel, device): the attribute is per device, and contexts may
 // be created on several devices and from several threads (cfg.device)
 inline void ensure_dynamic_lds(const void *func, int bytes)
@@ -158,7 +162,7 @@ struct GemmArgs {
 void gemm_f32(const GemmArgs &a, hipStream_t s);
 // Same product on the bf16 matrix cores with split operands (x = hi + lo, three MFMAs per term,
 // fp32 accumulation; ~1e-5 relative error): kernels_bf16x2.hip.  plane_hi/lo are workspaces of
-// bf16x2_plane_bytes(M, K) bytes each.  Returns false for unsupported shapes.
+// bf16x2_plane_bytes(M, K) bytes each.  Returns false for unsupported shapes (the caller then takes gemm_f32).
 size_t bf16x2_plane_bytes(int M, int K);
 size_t bf16x2_slab_floats(int M, int N, int ksplit = 0);
 // plane_lo2 != nullptr selects the three-way split (x = hi + mid + lo, six MFMAs per term): fp32-level accuracy.
@@ -227,10 +231,6 @@ bool skinny_product_sym(const float *X, long ldx, int M, const float *Gpacked, i
                         hipStream_t s, void *plane_lo2 = nullptr, bool planes_ready = false, bool emit_planes = false);
 // planes_ready: plane_hi / plane_lo already hold the two-way planes of X (skip the split); emit_planes: the reduction also
 // writes the two-way planes of the RESULT into plane_hi / plane_lo (the next product of a Chebyshev chain takes it as X)
-// C[M][N] = alpha * X[M][K] * G[K][N] + b1*E1 + b2*E2 for M <= 128 (single launch, K split over
-// the waves of a workgroup, deterministic).  Returns false when the shape is not supported.
-bool skinny_product_f32(const float *X, long ldx, int M, int x_rows_alloc, const float *G, long ldg, int N, int K,
-                        float alpha, float *C, long ldc, const float *E1, float b1, const float *E2, float b2, hipStream_t s);
 size_t gemm_slab_floats(int M, int N, int split_k);
 void splitk_reduce_f32(const float *slab, int split, int M, int N, float *C, long ldc, float alpha, float beta,
                        const float *E1, float b1, const float *E2, float b2, hipStream_t s);

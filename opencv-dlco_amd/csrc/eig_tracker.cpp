@@ -33,9 +33,6 @@ EigTracker::EigTracker(int F, int max_rows, int guard, float tol, int max_iter, 
     srcrow_.alloc(cap_ + 8);
     jwork_.alloc(jacobi_work_floats(cap_));
     dead_.alloc(CHOL_INV_MAX_N);
-    if (const char *e = std::getenv("DLCO_PANEL_AMP")) panel_amp_ = std::max(1.0, std::atof(e));
-    // filter products run on the bf16 matrix cores with split operands unless DLCO_FP32_FILTER is set
-    bf16_filter_ = (F_ % 128 == 0) && std::getenv("DLCO_FP32_FILTER") == nullptr;
     // K slices of a product over a full (unpacked) matrix: a divisor of the tile count, four where it divides
     {
         const int nt = F_ / 128;
@@ -43,12 +40,10 @@ EigTracker::EigTracker(int F, int max_rows, int guard, float tol, int max_iter, 
         for (int d : {4, 2, 8, 7, 6, 5, 3})
             if (nt > 0 && nt % d == 0) { ks_ = d; break; }
     }
-    if (bf16_filter_) {
-        plane_hi_.alloc(bf16x2_plane_bytes(std::min(cap_, 160), F_));
-        plane_lo_.alloc(bf16x2_plane_bytes(std::min(cap_, 160), F_));
-        // the Rayleigh-Ritz product takes the three-way split (fp32-level accuracy) unless DLCO_FP32_RR is set
-        if (std::getenv("DLCO_FP32_RR") == nullptr) plane_lo2_.alloc(bf16x2_plane_bytes(std::min(cap_, 128), F_));
-    }
+    // split-bf16 products (F is whole 128-column tiles): two-way planes for the filter, three-way for the Rayleigh-Ritz product
+    plane_hi_.alloc(bf16x2_plane_bytes(std::min(cap_, 160), F_));
+    plane_lo_.alloc(bf16x2_plane_bytes(std::min(cap_, 160), F_));
+    plane_lo2_.alloc(bf16x2_plane_bytes(std::min(cap_, 128), F_));
     pv_.alloc(F_);
     pw_.alloc(F_);
     slab_floats_ = std::max((size_t)4 * cap_ * F_, (size_t)8 << 20);
@@ -103,7 +98,7 @@ void EigTracker::seed_rows(const float *src, long ld, const int32_t *ids_dev, in
 
 bool EigTracker::rank_coeff_job(RankCoeffJob *job, int kmax)
 {
-    if (wext_rows_ <= 0 || wext_rows_ != m_ || m_ > 160 || !packed_ || !bf16_filter_ || shard_ || kmax % 32 != 0) return false;
+    if (wext_rows_ <= 0 || wext_rows_ != m_ || m_ > 160 || !packed_ || shard_ || kmax % 32 != 0) return false;
     coeff_.alloc(rank_coeff_bytes(cap_ < 160 ? cap_ : 160, kmax));
     job->nw = wext_nw_; job->m = m_; job->MT = (m_ + 31) / 32;
     job->wscale = wscale_.p; job->frag = coeff_.p;
@@ -135,8 +130,8 @@ void EigTracker::product(const float *X, int rows, const float *G, float alpha, 
     // (one HBM-bound pass over G per chunk, still cheaper than the generic fp32 GEMM)
     // (the row-streaming kernel takes 160 rows with the two-way split - a block of rank ~128 plus its guards
     // in ONE pass over G - and 96 with the three-way split; a sharded rank's slab kernel 128)
-    const int one_pass = (approx && !shard_ && bf16_filter_) ? 160 : (packed_ ? 96 : 128);   // (symmetric three-way kernel: 96 rows)
-    if (rows > one_pass && bf16_filter_ && (packed_ || F_ >= 256) && (approx || plane_lo2_.p)) {
+    const int one_pass = (approx && !shard_) ? 160 : (packed_ ? 96 : 128);   // (symmetric three-way kernel: 96 rows)
+    if (rows > one_pass && (packed_ || F_ >= 256)) {
         chain_next_ = false;                                     // row chunks share the plane buffers: no carried planes
         const int step = approx ? (rows <= 2 * one_pass ? (rows / 2 + 31) / 32 * 32 : one_pass) : 96;
         for (int r0 = 0; r0 < rows; r0 += step) {
@@ -169,7 +164,7 @@ void EigTracker::product(const float *X, int rows, const float *G, float alpha, 
         const float *E1s = E1 ? E1 + c0 : nullptr, *E2s = E2 ? E2 + c0 : nullptr;
         if (prof_) prof_->begin(PROF_EIG_PRODUCT);
         bool done = false;
-        if (bf16_filter_ && rows <= 128 && (approx || plane_lo2_.p)) {
+        if (rows <= 128) {
             int ks = ks_;                                            // keep ~256 workgroups in flight
             while (ks < 4 * world && F_ % (128 * ks * 2) == 0 && bf16x2_slab_floats(rows, cw, ks * 2) <= slab_floats_) ks *= 2;
             done = skinny_product_bf16x2(X, F_, rows, G + c0, F_, cw, F_, alpha, out + c0, F_, E1s, b1, E2s, b2, plane_hi_.p,
@@ -195,19 +190,13 @@ void EigTracker::product(const float *X, int rows, const float *G, float alpha, 
         unpack_cols(out, F_, shard_->gather, cw, rows, world, s_);
         return;
     }
-    if (bf16_filter_ && rows <= one_pass && F_ >= 256 && (approx || plane_lo2_.p)) {
+    if (rows <= one_pass && F_ >= 256) {
         // filter products: two-way split (~1e-5); exact products (Rayleigh-Ritz): three-way split (~1e-7)
         if (prof_) prof_->begin(PROF_EIG_PRODUCT);
         const bool ok = skinny_product_bf16x2(X, F_, rows, G, F_, F_, F_, alpha, out, F_, E1, b1, E2, b2, plane_hi_.p,
                                               plane_lo_.p, slab_.p, s_, ks_, approx ? nullptr : plane_lo2_.p);
         if (prof_) prof_->end(PROF_EIG_PRODUCT);
         if (ok) return;
-    }
-    if (rows <= 128 && F_ >= 256) {
-        if (prof_) prof_->begin(PROF_EIG_PRODUCT);
-        skinny_product_f32(X, F_, rows, cap_, G, F_, F_, F_, alpha, out, F_, E1, b1, E2, b2, s_);
-        if (prof_) prof_->end(PROF_EIG_PRODUCT);
-        return;
     }
     GemmArgs g;
     g.M = rows; g.N = F_; g.K = F_;
@@ -401,7 +390,7 @@ int EigTracker::update(const float *G, float mu, float cscale, float *W, double 
     // The caller may have told what changed: G = beta G_prev + alpha X_a^T diag(w) X_a (offer_rank_update).  With Y_ = Q_ H_prev
     // still there from the last Rayleigh-Ritz step and the projections of X_a on exactly these rows, the first filter
     // term needs no pass over G (kernels_rankupd.hip).
-    const bool ru_ok = ru_offered_ && y_ok_ && have_theta_ && packed_ && bf16_filter_ && !shard_ && wext_rows_ == m_ &&
+    const bool ru_ok = ru_offered_ && y_ok_ && have_theta_ && packed_ && !shard_ && wext_rows_ == m_ &&
                        ru_.rows == m_ && m_ >= 1 && m_ <= 160 && m_ < live_ && ru_.proj && ru_.planes;
     ru_offered_ = false;
     const int ru_nw = wext_nw_;
@@ -475,7 +464,7 @@ int EigTracker::update(const float *G, float mu, float cscale, float *W, double 
             // factor the marginal case needs.
             // (It gains a factor 0.5-0.9 on the criterion, measured, and what it must reach is the tolerance of the passes
             // after the first: only a miss within 1.6x of THAT is worth a pass without products.)
-            const bool cheap = it >= 1 && !cheap_done && y_ok_ && cheap_pass_ && last_crit_ <= cheap_margin_ * tol_pass2_ * tol;
+            const bool cheap = it >= 1 && !cheap_done && y_ok_ && last_crit_ <= cheap_margin_ * tol_pass2_ * tol;
             if (cheap) {
                 cheap_done = true;                                   // once per step: if it is not enough, filter properly
                 d = 1;
@@ -590,7 +579,7 @@ int EigTracker::update(const float *G, float mu, float cscale, float *W, double 
         // they decide guards_ok) are rotated but do not prolong the sweeps.  What this may leave unfinished
         // shows up in the residuals below, which decide convergence.
         float lam_cut = -3.0e38f;
-        if (guard_stop_ && have_theta_ && n_ritz == m_) {
+        if (have_theta_ && n_ritz == m_) {
             int nwp = 0;
             while (nwp < m_ && h_theta_[nwp] > mu) nwp++;
             const int ig = nwp + std::max(2, guard_ / 4);
@@ -608,34 +597,27 @@ int EigTracker::update(const float *G, float mu, float cscale, float *W, double 
         rotate(Vm_.p, cap_, m_, m_, Qo, Qn, Yb, Yn);
         Q_ = Qn; Y_ = Yn;
         y_ok_ = true;                                                // Y_ = Q_ H for the current H
-        if (!poll_readback_) residual_norms(Q_, Y_, F_, evals_.p, m_, F_, res_.p, s_);
-        if (poll_readback_) {
-            // the block is written into pinned memory by a kernel that raises a sequence number last; polling it
-            // costs a few microseconds where copy + hipStreamSynchronize cost tens (one read-back per pass)
-            unsigned *flag = reinterpret_cast<unsigned *>(pin_ + pin_floats_ - 16);
-            const unsigned seq = ++publish_seq_;
-            int *extra_host = reinterpret_cast<int *>(pin_ + pin_floats_ - 32);
-            // (the residual kernel's last workgroup publishes: one launch)
-            // (the kernel also writes this pass's rows of W, guard rows and scales included: if the pass is the update's last,
-            // W is already where it belongs)
-            ResidualEmit em;
-            em.W = W; em.ldw = F_; em.mu = mu; em.cscale = cscale; em.wscale = wscale_.p; em.guards = emit_guards_;
-            residual_norms_publish(Q_, Y_, F_, evals_.p, m_, F_, res_.p, reinterpret_cast<unsigned *>(sweeps_dev_ + 4), ritz_block_.p, pin_,
-                                   (int)blk, flag, seq, s_, extra_dev_, extra_host, &em, &w_emitted);
-            const auto t0 = std::chrono::steady_clock::now();
-            bool seen = false;
-            for (long spins = 0;; spins++) {
-                if (__atomic_load_n(flag, __ATOMIC_ACQUIRE) == seq) { seen = true; break; }
-                if ((spins & 1023) == 1023 && std::chrono::steady_clock::now() - t0 > std::chrono::milliseconds(200)) break;
-            }
-            if (!seen) {                                             // slow box or a faulted kernel: let the runtime tell
-                DLCO_HIP(hipStreamSynchronize(s_));
-                DLCO_CHECK(__atomic_load_n(flag, __ATOMIC_ACQUIRE) == seq, -3, "eig tracker: read-back did not arrive");
-            }
-        } else {
-            DLCO_HIP(hipMemcpyAsync(pin_, ritz_block_.p, blk * sizeof(float), hipMemcpyDeviceToHost, s_));
-            if (extra_dev_) DLCO_HIP(hipMemcpyAsync(pin_ + pin_floats_ - 32, extra_dev_, sizeof(int), hipMemcpyDeviceToHost, s_));
+        // the block is written into pinned memory by a kernel that raises a sequence number last; polling it
+        // costs a few microseconds where copy + hipStreamSynchronize cost tens (one read-back per pass)
+        unsigned *flag = reinterpret_cast<unsigned *>(pin_ + pin_floats_ - 16);
+        const unsigned seq = ++publish_seq_;
+        int *extra_host = reinterpret_cast<int *>(pin_ + pin_floats_ - 32);
+        // (the residual kernel's last workgroup publishes: one launch)
+        // (the kernel also writes this pass's rows of W, guard rows and scales included: if the pass is the update's last,
+        // W is already where it belongs)
+        ResidualEmit em;
+        em.W = W; em.ldw = F_; em.mu = mu; em.cscale = cscale; em.wscale = wscale_.p; em.guards = emit_guards_;
+        residual_norms_publish(Q_, Y_, F_, evals_.p, m_, F_, res_.p, reinterpret_cast<unsigned *>(sweeps_dev_ + 4), ritz_block_.p, pin_,
+                               (int)blk, flag, seq, s_, extra_dev_, extra_host, &em, &w_emitted);
+        const auto t0 = std::chrono::steady_clock::now();
+        bool seen = false;
+        for (long spins = 0;; spins++) {
+            if (__atomic_load_n(flag, __ATOMIC_ACQUIRE) == seq) { seen = true; break; }
+            if ((spins & 1023) == 1023 && std::chrono::steady_clock::now() - t0 > std::chrono::milliseconds(200)) break;
+        }
+        if (!seen) {                                             // slow box or a faulted kernel: let the runtime tell
             DLCO_HIP(hipStreamSynchronize(s_));
+            DLCO_CHECK(__atomic_load_n(flag, __ATOMIC_ACQUIRE) == seq, -3, "eig tracker: read-back did not arrive");
         }
         if (extra_dev_) extra_val_ = *reinterpret_cast<int *>(pin_ + pin_floats_ - 32);
         const int sweeps = *reinterpret_cast<int *>(pin_ + 2 * (cap_ + 8));
@@ -667,11 +649,11 @@ int EigTracker::update(const float *G, float mu, float cscale, float *W, double 
         // a pair just above the threshold carries almost no weight in A and its residual counts with
         // that weight.  Pairs well above mu keep the weight 1 of the plain residual test.
         float crit = 0.f;
-        const float bsep = (weighted_crit_ && nw < m_) ? std::min(mu, h_theta_[nw + (m_ - nw) / 2]) : mu;
+        const float bsep = nw < m_ ? std::min(mu, h_theta_[nw + (m_ - nw) / 2]) : mu;
         for (int i = 0; i < nw; i++) {
             float wgt = 1.f;
             const float den = h_theta_[i] - bsep;
-            if (weighted_crit_ && den > 0.f) wgt = std::min(1.f, (h_theta_[i] - mu + h_res_[i]) / den);
+            if (den > 0.f) wgt = std::min(1.f, (h_theta_[i] - mu + h_res_[i]) / den);
             crit = std::max(crit, cscale * h_res_[i] * wgt);
         }
         const float emax = nw > 0 ? cscale * (h_theta_[0] - mu) : 0.f;
@@ -685,7 +667,7 @@ int EigTracker::update(const float *G, float mu, float cscale, float *W, double 
         const float gtol = tol * std::max(emax, cscale * 1e-3f * std::fabs(mu));
         for (int i = nw; i < ng; i++) {
             const float excess = h_theta_[i] + h_res_[i] - mu;
-            const bool below = excess < 0.f || (weighted_crit_ && cscale * excess <= gtol);
+            const bool below = excess < 0.f || cscale * excess <= gtol;
             const bool small = cscale * h_res_[i] <= gtol;
             guards_ok = guards_ok && (below || small);
         }

@@ -11,7 +11,6 @@
 // positive eigenspace does; when it reaches F the method is the dense eigensolver.
 #pragma once
 
-#include <cstdlib>
 #include "dlco_internal.hpp"
 
 #include <functional>
@@ -87,7 +86,7 @@ public:
     bool rank_coeff_job(RankCoeffJob *job, int kmax);
     void set_packed(bool on) { packed_ = on; }
     bool packed() const { return packed_; }
-    static bool packed_supported(int F) { return F % 128 == 0 && F / 128 <= 64 && std::getenv("DLCO_FP32_FILTER") == nullptr && std::getenv("DLCO_FP32_RR") == nullptr && std::getenv("DLCO_NO_PACKED") == nullptr; }
+    static bool packed_supported(int F) { return F % 128 == 0 && F / 128 <= 64 && env_switch("DLCO_NO_PACKED") == nullptr; }
     const EigStats &stats() const { return st_; }
     float last_crit() const { return last_crit_; }
 
@@ -115,7 +114,7 @@ private:
     int wext_rows_ = 0, wext_nw_ = 0;   // W as the last update() left it: rows in all, Ritz rows among them
     RankUpdate ru_;
     bool ru_offered_ = false;
-    bool ru_check_ = std::getenv("DLCO_RANK_UPDATE_CHECK") != nullptr;
+    bool ru_check_ = env_switch("DLCO_RANK_UPDATE_CHECK") != nullptr;
     DevBuf<float> wscale_;
     DevBuf<char> coeff_;
     const float *chain_planes_of_ = nullptr;   // the matrix whose two-way planes sit in plane_hi_/plane_lo_ (emitted by a reduction)
@@ -134,15 +133,12 @@ private:
     int deg0_ = 4;                   // filter degree of the first pass of a step (adapted)
     int last_deg_ = 0;               // degree actually used by the last filter (after the amplification cap)
     bool y_ok_ = false;              // Y_ = Q_ * H row for row for the matrix of the current update
-    bool cheap_pass_ = std::getenv("DLCO_NO_CHEAP_PASS") == nullptr;
     float cheap_margin_ = 1.6f;         // see update(): how narrow a miss must be for a pass without products
-    bool lock_ = std::getenv("DLCO_NO_LOCKING") == nullptr;           // see update(): converged top pairs leave the filter
-    float tol_pass1_ = std::getenv("DLCO_EIG_TOL_PASS1") ? (float)std::atof(std::getenv("DLCO_EIG_TOL_PASS1")) : 0.85f;  // ... and of the first
-    float tol_pass2_ = 0.5f;            // see update(): tolerance factor of the passes after the first
-    double panel_amp_ = 1e5;         // largest filter-amplification ratio inside one orthonormalisation panel
-    bool debug_ = std::getenv("DLCO_EIG_DEBUG") != nullptr;
-    bool guard_stop_ = std::getenv("DLCO_JACOBI_ALL_PAIRS") == nullptr;       // see update(): guard-guard pairs do not prolong Jacobi
-    bool weighted_crit_ = std::getenv("DLCO_EIG_UNIFORM_CRIT") == nullptr;   // see update(): residuals weighted by their share in A
+    bool lock_ = env_switch("DLCO_NO_LOCKING") == nullptr;           // see update(): converged top pairs leave the filter
+    static constexpr float tol_pass1_ = 0.85f;  // see update(): tolerance factor of the first pass ...
+    float tol_pass2_ = 0.5f;            // ... and of the passes after the first
+    static constexpr double panel_amp_ = 1e5;   // largest filter-amplification ratio inside one orthonormalisation panel
+    bool debug_ = env_switch("DLCO_EIG_DEBUG") != nullptr;
 
     DevBuf<float> buf_[6];           // Ritz vectors, their H-products and temporaries, each cap x F
     float *all_[6] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
@@ -155,8 +151,7 @@ private:
     FView evals_, res_;
     int *sweeps_dev_ = nullptr;
     DevBuf<int32_t> srcrow_;
-    bool bf16_filter_ = false;       // filter products as split-bf16 MFMA (kernels_bf16x2.hip)
-    int ks_ = 4;                     // K slices of such a product over a full matrix (a divisor of F / 128)
+    int ks_ = 4;                     // K slices of a split-bf16 product over a full matrix (a divisor of F / 128)
     DevBuf<char> plane_hi_, plane_lo_, plane_lo2_;
     DevBuf<int> dead_;               // dead-row flags of the panel being factored
     size_t slab_floats_ = 0;
@@ -164,7 +159,6 @@ private:
     std::vector<int32_t> h_sr_;
     float *pin_ = nullptr;           // pinned host staging
     unsigned publish_seq_ = 0;
-    bool poll_readback_ = std::getenv("DLCO_SYNC_READBACK") == nullptr;
     size_t pin_floats_ = 0;
     EigStats st_;
     Profiler *prof_ = nullptr;

@@ -77,7 +77,6 @@ struct Bf2Dev {
     long ldg;
     float *slab;                  // [KS][M][N] raw partial sums
     int tiled;                    // G is stored as contiguous 128 x 128 tiles, tile (I, J) at ((I * K/128) + J) * 16384 floats
-    int xcd_map;                  // rows kernel: give the workgroups of an XCD one K slice (see the kernel)
 };
 
 template <int MT, int NS>
@@ -234,7 +233,7 @@ __global__ __launch_bounds__(RK_T) void skinny_rows_kernel(Bf2Dev g)
     int bx = blockIdx.x, by = blockIdx.y;
     {
         const int gx = gridDim.x, ks = gridDim.y;
-        if (g.xcd_map && ks <= 8 && 8 % ks == 0 && (gx * ks) % 8 == 0 && gx % (8 / ks) == 0) {
+        if (ks <= 8 && 8 % ks == 0 && (gx * ks) % 8 == 0 && gx % (8 / ks) == 0) {
             const int b = by * gx + bx, xcd = b & 7, w = b >> 3, per = 8 / ks;
             by = xcd / per;
             bx = w * per + xcd % per;
@@ -714,7 +713,7 @@ void split_planes_bf16(const float *X, long ldx, int M, int K, void *hi, void *l
 size_t bf16x2_plane_bytes(int M, int K) { return (size_t)((M + 31) / 32) * 32 * K * sizeof(__bf16); }
 size_t bf16x2_slab_floats(int M, int N, int ksplit) { return (size_t)(ksplit > 0 ? ksplit : KS) * M * N; }
 
-// Returns false when the shape is not supported (caller falls back to the fp32 kernel).
+// Returns false when the shape is not supported (the caller then takes gemm_f32).
 bool skinny_product_bf16x2(const float *X, long ldx, int M, const float *G, long ldg, int N, int K, float alpha, float *C,
                            long ldc, const float *E1, float b1, const float *E2, float b2, void *plane_hi, void *plane_lo,
                            float *slab, hipStream_t s, int ksplit, void *plane_lo2, bool g_tiled)
@@ -731,8 +730,6 @@ bool skinny_product_bf16x2(const float *X, long ldx, int M, const float *G, long
     g.xhi = static_cast<const bf16x8 *>(plane_hi); g.xlo = static_cast<const bf16x8 *>(plane_lo);
     g.xlo2 = static_cast<const bf16x8 *>(plane_lo2);
     g.G = G; g.ldg = ldg; g.slab = slab; g.tiled = g_tiled ? 1 : 0;
-    static const int xcd_map = std::getenv("DLCO_NO_XCDMAP") == nullptr ? 1 : 0;
-    g.xcd_map = xcd_map;
     const dim3 grid(N / 128, ks), block(T8);
     // whole symmetric matrix: stream its rows through LDS (skinny_rows_kernel)
     // (four row tiles with the three-way split do not fit the register budget of the split-role kernel)

@@ -525,8 +525,8 @@ void launch_jacobi_blk(const float *T, long ldt, int n, float *evals, float *V, 
 {
     ensure_dynamic_lds(reinterpret_cast<const void *>(jacobi_blk_kernel<E>), 160 * 1024 - 1024);
     // column cosine below which a pair is not rotated
-    static const float rot_tol = std::getenv("DLCO_JACOBI_ROT") ? (float)std::atof(std::getenv("DLCO_JACOBI_ROT")) : 3e-6f;
-    static const char *trace_path = std::getenv("DLCO_JACOBI_TRACE");
+    constexpr float rot_tol = 3e-6f;
+    static const char *trace_path = env_switch("DLCO_JACOBI_TRACE");
     static int calls = 0;
     if (trace_path && E == 3 && ++calls == 40) {                // one call in the steady state of a bench run
         unsigned long long *buf = nullptr;
@@ -804,7 +804,7 @@ void jacobi_eigh(const float *T, long ldt, int n, float *evals, float *V, long l
 {
     DLCO_CHECK(n >= 1 && n <= 4096, -2, "jacobi_eigh: n out of range");
     // largest column cosine of a sweep below which the sweep is the last one (see jacobi_body)
-    static const float stop_cos = std::getenv("DLCO_JACOBI_STOP") ? (float)std::atof(std::getenv("DLCO_JACOBI_STOP")) : 1e-3f;
+    constexpr float stop_cos = 1e-3f;
     if (n <= JBLK_MAX_N) {
         const int e = jblk_chunks(n);
         if (e == 1) launch_jacobi_blk<1>(T, ldt, n, evals, V, ldv, sweeps_out, stop_cos, lam_cut, s);
@@ -824,7 +824,7 @@ void jacobi_eigh(const float *T, long ldt, int n, float *evals, float *V, long l
         unsigned *sync_words = reinterpret_cast<unsigned *>(work + ncol * g.ldc + 2 * ncol);
         DLCO_HIP(hipMemsetAsync(sync_words, 0, 64 * sizeof(unsigned), s));
         // test hook: raise the barrier's give-up flag before the launch, every workgroup then leaves at its first grid barrier
-        static const bool force_timeout = std::getenv("DLCO_TEST_JMW_TIMEOUT") != nullptr;
+        static const bool force_timeout = env_switch("DLCO_TEST_JMW_TIMEOUT") != nullptr;
         if (force_timeout) DLCO_HIP(hipMemsetAsync(sync_words + 1, 1, 1, s));
         g.sync = sync_words; g.sweeps_out = sweeps_out; g.stop_cos = stop_cos; g.lam_cut = lam_cut;
         const size_t lds = ((size_t)16 * g.ldc + 128) * sizeof(float);

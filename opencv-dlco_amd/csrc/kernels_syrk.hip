@@ -631,7 +631,7 @@ static const int32_t *syrk_tile_map(int nt, int slab_t0, int slab_nt, int *count
 }
 
 
-int syrk_planes_mode(bool bf16) { return bf16 ? 1 : (std::getenv("DLCO_SYRK_FP32") == nullptr ? 3 : 0); }
+int syrk_planes_mode(bool bf16) { return bf16 ? 1 : (env_switch("DLCO_SYRK_FP32") == nullptr ? 3 : 0); }
 
 size_t syrk_planes_bytes(int kmax, int F) { return (size_t)2 * (kmax / PL_KD) * (F / TB) * PL_IMG; }
 
@@ -675,7 +675,7 @@ bool syrk_rda_f32(const float *D, long ldd, const int32_t *ids, const int32_t *i
     g.slab_t0 = slab ? slab_col0 / TB : 0; g.slab_nt = slab ? slab_cols / TB : 0;
     const int ntiles = slab ? g.nt * g.slab_nt : g.nt * (g.nt + 1) / 2;
     g.trace = nullptr;
-    static const char *trace_path = std::getenv("DLCO_SYRK_TRACE");          // developer aid: phase time stamps of one launch
+    static const char *trace_path = env_switch("DLCO_SYRK_TRACE");          // developer aid: phase time stamps of one launch
     static int trace_calls = 0;
     static unsigned long long *trace_buf = nullptr;
     const bool tracing = trace_path && !slab && !ids2 && !bf16 && ++trace_calls == 400;
@@ -691,7 +691,7 @@ bool syrk_rda_f32(const float *D, long ldd, const int32_t *ids, const int32_t *i
     // precision of the products: 3 (default) = three-way split bf16 on pre-split planes, fp32-level results at 3/8 of
     // the fp32 matrix time; 0 = fp32 MFMA, a k-ordered fmaf chain (DLCO_SYRK_FP32=1); 1 = operands rounded to bf16
     // once (cfg.grad_bf16, the configs[4] variant)
-    static const bool exact_fp32 = std::getenv("DLCO_SYRK_FP32") != nullptr;
+    static const bool exact_fp32 = env_switch("DLCO_SYRK_FP32") != nullptr;
     const int prec = bf16 ? 1 : (exact_fp32 ? 0 : 3);
     if (prec == 3 || prec == 1) {
         // split (or round) once, then the matrix kernel (see syrk_planes_kernel)

@@ -135,3 +135,28 @@ def test_rda_coefficients_do_not_wrap_at_multi_gpu_batch_sizes(shim, ref):
         a, b = coeffs(B, t)
         want = df * np.float32(b) + dl * np.float32(a)
         assert np.array_equal(ref.rda_update(df, dl, t, B), want)
+
+
+def test_environment_is_read_only_through_the_switch_table():
+    """Every environment read of libdlco.so goes through env_switch() (dlco_api.cpp), the names asked for are exactly those of its
+    table, and the table is the list of switches DESIGN.md §5 documents."""
+    csrc = os.path.join(ROOT, "opencv-dlco_amd", "csrc")
+    api = open(os.path.join(csrc, "dlco_api.cpp")).read()
+    helper = re.search(r"const char \*dlco::env_switch\(const char \*name\)\n\{\n.*?\n\}\n", api, re.S)
+    assert helper, "env_switch() not found in dlco_api.cpp"
+    table = re.search(r"const EnvSwitch kEnvSwitches\[\] = \{\n(.*?)\n\};", api, re.S)
+    assert table, "the switch table not found in dlco_api.cpp"
+    names = re.findall(r'\{"(DLCO_[A-Z0-9_]+)", "[^"]+"\}', table.group(1))
+    assert len(names) == len(set(names)) and len(names) == table.group(1).count("{"), table.group(1)
+    asked = set()
+    for fn in sorted(os.listdir(csrc)):
+        if not fn.endswith((".cpp", ".hpp", ".hip")):
+            continue
+        text = open(os.path.join(csrc, fn)).read()
+        if fn == "dlco_api.cpp":
+            text = text.replace(helper.group(0), "")
+        assert "getenv" not in text, fn
+        asked |= set(re.findall(r'env_switch\("([A-Z0-9_]+)"\)', text))
+    assert asked == set(names), (sorted(asked), names)          # no read outside the table, no name in it that nothing reads
+    documented = re.findall(r"^ *\| `(DLCO_[A-Z0-9_]+)` \| [^|]+ \|$", open(os.path.join(ROOT, "DESIGN.md")).read(), re.M)
+    assert sorted(documented) == sorted(names), (documented, names)

@@ -1,7 +1,8 @@
-"""The library's developer switches are read once per process (getenv), so each one gets a child process: the code
+"""Some of the library's environment switches are read once per process, so each one gets a child process: the code
 behind a switch - the fp32-MFMA gradient kernel `syrk_rda_kernel8` (the k-ordered v_mfma_f32_32x32x2_f32 chain that
-north_star literally names), the fp32 filter / Rayleigh-Ritz products, the unpacked dual average, the recovery from a
-grid-barrier time-out of the multi-workgroup Jacobi - is held to the same oracle gates as the default path."""
+north_star literally names), the unpacked dual average, the recovery from a grid-barrier time-out of the multi-workgroup
+Jacobi - is held to the same oracle gates as the default path.  The names of retired switches must change nothing: a child
+with one of them set, or all of them, computes what a child with none computes, bit for bit."""
 import os
 import subprocess
 import sys
@@ -12,7 +13,7 @@ import pytest
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
-def _child(case):
+def _child(case, out=None):
     """Runs in the child: same bodies and gates as tests/test_gpu_parity.py."""
     import importlib
     sys.path.insert(0, ROOT)
@@ -44,6 +45,13 @@ def _child(case):
         assert e <= TOL_GRAD, (F, B, e)
         ctx.close()
         return e
+
+    def keep(key, ctx):
+        # what a run leaves, for the bit-equality check of the "retired" pair
+        if out is not None:
+            out.update({key + "_A": ctx.A(), key + "_dfavg": ctx.dfavg(), key + "_W": ctx.W()})
+            for name, v in list(ctx.counters().items()) + list(ctx.eig_stats().items()):
+                out[key + "_" + name] = np.array(v)
 
     def teacher_forced(F, B, nstep, N=4000, expect_timeouts=False):
         D, L = synth(N, F, k=20, seed=9)
@@ -78,6 +86,7 @@ def _child(case):
             assert cn["jacobi_barrier_timeouts"] >= 1, cn
         else:
             assert cn["jacobi_barrier_timeouts"] == 0, cn
+        keep("teacher_forced", ctx)
         ctx.close()
         tr.close()
         return worst
@@ -100,6 +109,7 @@ def _child(case):
             assert cn["rank_update_passes"] >= nstep - 8, cn
         elif expect_passes is not None:
             assert cn["rank_update_passes"] == 0, cn
+        keep("free_run", ctx)
         ctx.close()
         return worst, cn
 
@@ -121,16 +131,12 @@ def _child(case):
         worst, cn = free_run(256, 16, True)
         assert cn["locked_passes"] == 0, cn
         print("free run without locking: A+ %.2e" % worst)
-    elif case == "tol_pass1":
-        # the first pass held to the plain tolerance (the library's factor is 0.85): the F = 256 run stays inside the gate
+    elif case == "retired":
+        # the same runs with and without retired names in the environment; the parent compares what they leave
         worst, cn = free_run(256, 30, True)
-        print("free run, first pass to the plain tolerance: A+ %.2e" % worst)
-    elif case.startswith("knob_"):
-        # the remaining developer knobs (tolerances, thresholds, tile and read-back choices): each alternative path is held to
-        # the same oracle gates on a teacher-forced run and on a short free run
-        print("teacher forced F=256: %.2e" % teacher_forced(256, 200, 6))
-        worst, cn = free_run(256, 12, None)
         print("free run: A+ %.2e" % worst)
+        print("teacher forced F=512: %.2e" % teacher_forced(512, 200, 6))
+        np.savez(out.pop("path"), **out)
     elif case == "no_rank_update":
         worst, cn = free_run(256, 30, False)
         print("free run without the shortcut: A+ %.2e" % worst)
@@ -138,7 +144,7 @@ def _child(case):
         for F, B, z in ((128, 8, 0.0), (256, 200, 0.3), (384, 33, 0.9), (544, 200, 0.2)):
             print("grad_rda F=%d B=%d: %.2e" % (F, B, grad_case(F, B, z)))
         print("teacher forced: %.2e" % teacher_forced(256, 200, 8))
-    elif case in ("fp32_products", "no_packed"):
+    elif case == "no_packed":
         print("teacher forced F=512: %.2e" % teacher_forced(512, 200, 10))
         print("teacher forced F=544: %.2e" % teacher_forced(544, 200, 6))
     elif case == "jmw_timeout":
@@ -151,12 +157,17 @@ def _child(case):
 
 CASES = {
     "syrk_fp32": {"DLCO_SYRK_FP32": "1"},
-    "fp32_products": {"DLCO_FP32_FILTER": "1", "DLCO_FP32_RR": "1"},
     "no_packed": {"DLCO_NO_PACKED": "1"},
     "jmw_timeout": {"DLCO_TEST_JMW_TIMEOUT": "1"},
     "rank_update_check": {"DLCO_RANK_UPDATE_CHECK": "1"},
     "no_rank_update": {"DLCO_NO_RANK_UPDATE": "1"},
     "no_locking": {"DLCO_NO_LOCKING": "1"},
+}
+
+# switches the library no longer has, each case at the values it set when the library still had them: each must change
+# nothing
+RETIRED_CASES = {
+    "fp32_products": {"DLCO_FP32_FILTER": "1", "DLCO_FP32_RR": "1"},
     "tol_pass1": {"DLCO_EIG_TOL_PASS1": "1.0"},
     "knob_uniform_crit": {"DLCO_EIG_UNIFORM_CRIT": "1"},
     "knob_eig_tol": {"DLCO_EIG_TOL": "1e-4"},
@@ -169,20 +180,60 @@ CASES = {
     "knob_panel_amp": {"DLCO_PANEL_AMP": "1e3"},
     "knob_sync_readback": {"DLCO_SYNC_READBACK": "1"},
 }
+RETIRED = {k: v for env in RETIRED_CASES.values() for k, v in env.items()}
 
 
-@pytest.mark.gpu
-@pytest.mark.parametrize("case", sorted(CASES))
-def test_switch_in_a_child_process(case):
-    env = dict(os.environ)
-    env.update(CASES[case])
-    p = subprocess.run([sys.executable, os.path.abspath(__file__), "--child", case], capture_output=True, text=True, timeout=600, env=env)
+def _run_child(case, env, *args):
+    p = subprocess.run([sys.executable, os.path.abspath(__file__), "--child", case, *args], capture_output=True, text=True,
+                       timeout=600, env=env)
     print(p.stdout)
     assert p.returncode == 0 and "child ok" in p.stdout, p.stdout[-3000:] + p.stderr[-3000:]
 
 
-if __name__ == "__main__":
-    if len(sys.argv) == 3 and sys.argv[1] == "--child":
-        _child(sys.argv[2])
+def _retired_run(path, names):
+    """The "retired" child (a free run and a teacher-forced run under the oracle gates) with exactly `names` of the retired
+    switches in its environment; returns what the runs left (A, dual average, W, counters)."""
+    env = {k: v for k, v in os.environ.items() if k not in RETIRED}
+    env.update(names)
+    _run_child("retired", env, path)
+    with np.load(path) as z:
+        return {k: z[k] for k in z.files}
+
+
+@pytest.fixture(scope="module")
+def retired_reference(tmp_path_factory):
+    """The same child without any retired name: what every retired case must reproduce bit for bit."""
+    return _retired_run(str(tmp_path_factory.mktemp("retired") / "none.npz"), {})
+
+
+def _assert_bit_equal(got, want):
+    # every kernel is run-to-run deterministic (DESIGN §3)
+    assert sorted(got) == sorted(want) and len(got) >= 2 * 3 + 2 * 8, sorted(got)
+    for k in sorted(got):
+        assert np.array_equal(got[k], want[k]), k
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("case", sorted(CASES) + sorted(RETIRED_CASES))
+def test_switch_in_a_child_process(case, request, tmp_path):
+    if case in CASES:
+        env = dict(os.environ)
+        env.update(CASES[case])
+        _run_child(case, env)
     else:
-        raise SystemExit("usage: test_env_switches_gpu.py --child <case>")
+        got = _retired_run(str(tmp_path / "set.npz"), RETIRED_CASES[case])
+        _assert_bit_equal(got, request.getfixturevalue("retired_reference"))
+
+
+@pytest.mark.gpu
+def test_retired_switches_change_nothing(retired_reference, tmp_path):
+    """All retired names at once: a free run and a teacher-forced run leave the same A, dual average, W and counters, bit
+    for bit, as without any of them."""
+    _assert_bit_equal(_retired_run(str(tmp_path / "all.npz"), RETIRED), retired_reference)
+
+
+if __name__ == "__main__":
+    if len(sys.argv) in (3, 4) and sys.argv[1] == "--child":
+        _child(sys.argv[2], {"path": sys.argv[3]} if len(sys.argv) == 4 else None)
+    else:
+        raise SystemExit("usage: test_env_switches_gpu.py --child <case> [<npz>]")

@@ -224,9 +224,8 @@ int main(int argc, char **argv)
             g.B.p = C.p + cw; g.B.ld = F; g.B.kmajor = true;
             g.C = out.p + cw; g.ldc = F; g.split_k = 32; g.slab = slab.p;
             const float c = time_ms(s, 20, [&] { gemm_f32(g, s); });
-            const float d = time_ms(s, 20, [&] { skinny_product_f32(X.p, F, M, 128, C.p, F, F, F, 1.f, out.p, F, nullptr, 0.f, nullptr, 0.f, s); });
-            std::printf("product M=%d  bf16x2 full %.1f us, slab 1/%d (ks 32) %.1f us;  fp32 full (skinny) %.1f us, slab (gemm split 32) %.1f us\n",
-                        M, a * 1e3, world, b * 1e3, d * 1e3, c * 1e3);
+            std::printf("product M=%d  bf16x2 full %.1f us, slab 1/%d (ks 32) %.1f us;  fp32 slab (gemm split 32) %.1f us\n",
+                        M, a * 1e3, world, b * 1e3, c * 1e3);
             const float e = time_ms(s, 20, [&] { pack_cols(slab.p, out.p, F, cw, cw, M, s); unpack_cols(out.p, F, slab.p, cw, M, world, s); });
             std::printf("pack + unpack %.1f us\n", e * 1e3);
         }
