@@ -336,6 +336,35 @@ int dlco_pr_validate(dlco_pr_ctx *ctx, float *loss_val, float *regul, int32_t *n
 int dlco_pr_stats(dlco_pr_ctx *ctx, const float *w_host, const float *prparams_host, int32_t pr_rows, int32_t pr_cols,
                   int32_t nchannels, int32_t max_dim, int32_t *nPR, int32_t *dim, int32_t *nzdim, float *fpr95, double *auc);
 
+/* A grid of pr-learn settings in one launch per window (the reference runs pr-learn once per data set and
+ * (mu, gamma) pair).  G settings (mu[k], gamma[k]) trained on the resident data of `src` (shared, not
+ * copied: src must outlive the grid), each from w = dfAvg = 0 at t = 0 with the sampler CvRng(seed).
+ * Setting k's w / dfAvg after any sequence of dlco_pr_grid_steps are bit-identical to a dlco_pr_ctx
+ * created with (F, N, mu[k], gamma[k], seed) on the same data after the same total number of iterations:
+ * the settings share the sampled row pairs (the sampler does not depend on w) and each workgroup applies
+ * every pair it fetches to several settings.  The grid has its own stream and sampler; it never advances
+ * src's sampler or t.  DLCO_ERR_INVALID: G outside 1 .. 65535, a gamma <= 0, src without data or with an
+ * empty training or validation split, a configs entry out of range. */
+typedef struct dlco_pr_grid dlco_pr_grid;
+int  dlco_pr_grid_create(dlco_pr_grid **out, dlco_pr_ctx *src, int32_t G, const float *mu, const float *gamma, uint64_t seed);
+void dlco_pr_grid_destroy(dlco_pr_grid *grid);
+const char *dlco_pr_grid_last_error(const dlco_pr_grid *grid);
+/* n iterations of every setting (one launch) */
+int  dlco_pr_grid_steps(dlco_pr_grid *grid, uint32_t n);
+int  dlco_pr_grid_get_state(dlco_pr_grid *grid, uint32_t *t, float *w_host /* [G][F] or NULL */, float *dfavg_host /* [G][F] or NULL */);
+/* dlco_pr_validate of every setting, equal to each setting's own: loss_val [G], regul [G], nnz [G] or NULL */
+int  dlco_pr_grid_validate(dlco_pr_grid *grid, float *loss_val, float *regul, int32_t *nnz);
+/* dlco_pr_stats for the settings configs[0..n) (in any order, repeats allowed), with w_host [n][F] or NULL
+ * (their current w); every output is an array of n, entry i as dlco_pr_stats gives it for configs[i] */
+int  dlco_pr_grid_stats(dlco_pr_grid *grid, const int32_t *configs, int32_t n, const float *w_host, const float *prparams_host,
+                        int32_t pr_rows, int32_t pr_cols, int32_t nchannels, int32_t max_dim,
+                        int32_t *nPR, int32_t *dim, int32_t *nzdim, float *fpr95, double *auc);
+/* Settings per workgroup of later steps: 0 = the library's rule (the default), else 1, 2 or 4 (4 only for
+ * F <= 5120).  Results do not depend on it; it exists for measurement.  dlco_pr_grid_group returns the
+ * value the next steps will use. */
+int  dlco_pr_grid_set_group(dlco_pr_grid *grid, int32_t per_group);
+int32_t dlco_pr_grid_group(const dlco_pr_grid *grid);
+
 /* ===========================================================================================
  * Descriptor generation — comp-uprjdists: the producer of pj-learn's input.
  * Replaces get_desc (src/vgg-desc.cpp:41-152), SelectPRFilters (src/misc.cpp:78-168) and the

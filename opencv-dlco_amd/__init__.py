@@ -152,6 +152,19 @@ def load():
     L.dlco_pr_set_state.argtypes = [vp, C.c_uint32, f32p, f32p]
     L.dlco_pr_validate.argtypes = [vp, f32p, f32p, i32p]
     L.dlco_pr_stats.argtypes = [vp, f32p, f32p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, i32p, i32p, i32p, f32p, C.POINTER(C.c_double)]
+    L.dlco_pr_grid_last_error.restype = C.c_char_p
+    L.dlco_pr_grid_last_error.argtypes = [vp]
+    L.dlco_pr_grid_create.argtypes = [C.POINTER(vp), vp, C.c_int32, f32p, f32p, C.c_uint64]
+    L.dlco_pr_grid_destroy.argtypes = [vp]
+    L.dlco_pr_grid_destroy.restype = None
+    L.dlco_pr_grid_steps.argtypes = [vp, C.c_uint32]
+    L.dlco_pr_grid_get_state.argtypes = [vp, C.POINTER(C.c_uint32), f32p, f32p]
+    L.dlco_pr_grid_validate.argtypes = [vp, f32p, f32p, i32p]
+    L.dlco_pr_grid_stats.argtypes = [vp, i32p, C.c_int32, f32p, f32p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, i32p, i32p, i32p, f32p,
+                                     C.POINTER(C.c_double)]
+    L.dlco_pr_grid_set_group.argtypes = [vp, C.c_int32]
+    L.dlco_pr_grid_group.argtypes = [vp]
+    L.dlco_pr_grid_group.restype = C.c_int32
     _lib = L
     return L
 
@@ -519,6 +532,73 @@ class PrContext:
         self._ck(self.L.dlco_pr_stats(self.h, _p(wv, f32p), _p(p, f32p), p.shape[0], p.shape[1], nchannels, max_dim,
                                       C.byref(npr), C.byref(dim), C.byref(nz), C.byref(f), C.byref(a)))
         return dict(nPR=npr.value, dim=dim.value, nzdim=nz.value, fpr95=f.value, auc=a.value)
+
+
+class PrGrid:
+    """A grid of pr-learn settings (mus[k], gammas[k]) trained together on the data of `src` (thin wrapper over
+    dlco_pr_grid).  Setting k follows, bit for bit, a PrContext(F, N, mus[k], gammas[k], seed) on the same data;
+    `src` must stay open while the grid is used, and its own state is never touched."""
+
+    def __init__(self, src, mus, gammas, seed=2215):
+        self.L = load()
+        mu, ga = _f32(mus).ravel(), _f32(gammas).ravel()
+        assert mu.size == ga.size
+        self.src, self.F, self.N, self.G = src, src.F, src.N, int(mu.size)
+        self.mus, self.gammas = mu.copy(), ga.copy()
+        h = C.c_void_p()
+        rc = self.L.dlco_pr_grid_create(C.byref(h), src.h, self.G, _p(mu, f32p), _p(ga, f32p), seed)
+        if rc != OK:
+            raise DlcoError(rc, self.L.dlco_pr_grid_last_error(None).decode())
+        self.h = h
+
+    def close(self):
+        if getattr(self, "h", None):
+            self.L.dlco_pr_grid_destroy(self.h)
+            self.h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def _ck(self, rc):
+        if rc != OK:
+            raise DlcoError(rc, self.L.dlco_pr_grid_last_error(self.h).decode())
+
+    def set_group(self, per_group):
+        """Settings per workgroup (0 = the library's rule, 1, 2 or 4); results do not depend on it."""
+        self._ck(self.L.dlco_pr_grid_set_group(self.h, per_group))
+
+    def group(self):
+        return int(self.L.dlco_pr_grid_group(self.h))
+
+    def steps(self, n):
+        self._ck(self.L.dlco_pr_grid_steps(self.h, n))
+
+    def state(self):
+        t = C.c_uint32()
+        w, df = np.empty((self.G, self.F), np.float32), np.empty((self.G, self.F), np.float32)
+        self._ck(self.L.dlco_pr_grid_get_state(self.h, C.byref(t), _p(w, f32p), _p(df, f32p)))
+        return dict(t=t.value, w=w, dfavg=df)
+
+    def validate(self):
+        lo, rg, nz = np.empty(self.G, np.float32), np.empty(self.G, np.float32), np.empty(self.G, np.int32)
+        self._ck(self.L.dlco_pr_grid_validate(self.h, _p(lo, f32p), _p(rg, f32p), _p(nz, i32p)))
+        return dict(loss=lo, regul=rg, nnz=nz)
+
+    def stats(self, prparams, configs=None, w=None, nchannels=8, max_dim=-1):
+        """ComputePRStats per listed setting (default: all); arrays in the order of `configs`."""
+        p = _f32(prparams)
+        cf = _i32(np.arange(self.G) if configs is None else configs).ravel()
+        n = cf.size
+        wv = None if w is None else _f32(w).reshape(n, self.F)
+        npr, dim, nz = np.zeros(n, np.int32), np.zeros(n, np.int32), np.zeros(n, np.int32)
+        f, a = np.full(n, -1.0, np.float32), np.zeros(n, np.float64)
+        self._ck(self.L.dlco_pr_grid_stats(self.h, _p(cf, i32p), n, _p(wv, f32p), _p(p, f32p), p.shape[0], p.shape[1], nchannels, max_dim,
+                                           _p(npr, i32p), _p(dim, i32p), _p(nz, i32p), _p(f, f32p),
+                                           a.ctypes.data_as(C.POINTER(C.c_double))))
+        return dict(nPR=npr, dim=dim, nzdim=nz, fpr95=f, auc=a)
 
 
 def select_filters(pr_filters, w):

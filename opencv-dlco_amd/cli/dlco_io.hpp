@@ -350,8 +350,9 @@ inline void append_row_f32(const std::string &path, const char *name, const floa
     if (rc < 0) throw std::runtime_error(path + ": append to dataset " + name + " failed");
 }
 
-// GDAL-style progress bar of the reference (src/misc.cpp:45-76)
-inline int term_progress(double complete, int last_tick)
+// GDAL-style progress bar of the reference (src/misc.cpp:45-76); with `sink` the text is appended there
+// instead of going to stdout
+inline int term_progress(double complete, int last_tick, std::string *sink = nullptr)
 {
     int tick = (int)(complete * 40.0);
     if (tick < 0) tick = 0;
@@ -360,10 +361,12 @@ inline int term_progress(double complete, int last_tick)
     if (tick <= last_tick) return last_tick;
     while (tick > last_tick) {
         last_tick++;
-        if (last_tick % 4 == 0) std::printf("%d", (last_tick / 4) * 10);
-        else std::printf(".");
+        const std::string piece = last_tick % 4 == 0 ? std::to_string((last_tick / 4) * 10) : std::string(".");
+        if (sink) *sink += piece;
+        else std::printf("%s", piece.c_str());
     }
-    if (tick == 40) std::printf(" - done.\n");
+    if (sink) { if (tick == 40) *sink += " - done.\n"; }
+    else if (tick == 40) std::printf(" - done.\n");
     else std::fflush(stdout);
     return last_tick;
 }

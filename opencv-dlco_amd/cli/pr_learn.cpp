@@ -9,6 +9,7 @@
 // (defaults = the reference's constants): -logstep n, -seed n, -device n.
 #include "../../include/dlco.h"
 #include "dlco_io.hpp"
+#include "pr_logstep.hpp"
 
 #include <cfloat>
 #include <chrono>
@@ -60,7 +61,7 @@ int main(int argc, char **argv)
         cout << endl;
         return 1;
     }
-    cout << "mu: " << mu << " gamma: " << gamma << " maxdim: " << MaxDim << " nIters: " << nIter << endl;
+    pr_log::config(cout, mu, gamma, MaxDim, nIter);
 
     try {
         std::vector<size_t> pshape, rshape, dshape, lshape;
@@ -76,8 +77,7 @@ int main(int argc, char **argv)
         const int nDists = (int)dshape[0], FeatDim = (int)dshape[1];
         if ((int)labels.size() < nDists) throw std::runtime_error("Label has fewer rows than Distance");
         if ((int)pshape[0] < 8 * FeatDim) throw std::runtime_error("PRParams needs 8 rows per column of Distance");
-        cout << "Load Labels: " << nDists << endl;
-        cout << "Load Distances: " << nDists << " x " << FeatDim << endl;
+        pr_log::loaded(cout, nDists, FeatDim);
         int tick = -1;
         for (int i = 0; i < nDists; i += 128) tick = dlco_io::term_progress((double)i / (double)nDists, tick);
         dlco_io::term_progress(1.0, tick);
@@ -88,26 +88,16 @@ int main(int argc, char **argv)
         dists.clear(); dists.shrink_to_fit();
         int32_t n_pos = 0, n_pos_trn = 0, n_neg = 0, n_neg_trn = 0;
         dlco_pr_get_index(ctx, &n_pos, &n_pos_trn, &n_neg, &n_neg_trn);
-        cout << "Positive samples #" << n_pos << endl;
-        cout << "Negative samples #" << n_neg << endl;
-        cout << "Positive train #" << n_pos_trn << endl;
-        cout << "Negative train #" << n_neg_trn << endl;
-        cout << "Positive valid #" << n_pos - n_pos_trn << endl;
-        cout << "Negative valid #" << n_neg - n_neg_trn << endl;
         char name[256];
         int cc_major = 0, cc_minor = 0;
         dlco_pr_device_name(ctx, name, sizeof(name), &cc_major, &cc_minor);
-        cout << endl;
-        cout << "Found GPU: " << name << endl;
-        cout << "Compute Capability: " << cc_major << "." << cc_minor << endl;
-        cout << endl;
+        pr_log::split(cout, n_pos, n_pos_trn, n_neg, n_neg_trn, name, cc_major, cc_minor);
 
         // The reference logs inside iteration t when its step counter has reached LogStep, i.e. at
         // t = LogStep, 2 LogStep + ... with `step` restarting from 0 -> every LogStep iterations, the
         // first time after LogStep + 1 of them (src/pr-learn.cpp:331,419-422); t runs to nIter inclusive.
-        float Obj_Best = FLT_MAX;
-        int nnz_best = 0;
-        std::vector<float> w(FeatDim), w_Best(FeatDim, 0.f);
+        pr_log::Best best;
+        std::vector<float> w(FeatDim);
         unsigned t_done = 0;                                   // iterations run so far (t = 0 .. t_done-1)
         unsigned long long next_log = LogStep;                 // t of the next log line: LogStep, 2 LogStep, ... (every t >= 1 for LogStep = 1)
         auto train_start = std::chrono::steady_clock::now();
@@ -126,27 +116,21 @@ int main(int argc, char **argv)
             if (dlco_pr_validate(ctx, &LossVal, &Regul, &nnz) != DLCO_OK) throw std::runtime_error(dlco_pr_last_error(ctx));
             const double vtime = std::chrono::duration<double>(std::chrono::steady_clock::now() - v0).count();
             const unsigned t = (unsigned)next_log;
-            if ((LossVal + Regul) < Obj_Best) {                // :364
-                Obj_Best = LossVal + Regul;
-                w_Best = w;
-                nnz_best = nnz;
-                std::printf("Best: %i  Loss: %.6f Regul: %.6f Obj: %.6f (%.6f)  NNZ: %i (%i)  Ttime: %.4f Vtime: %.4f\n", t, LossVal, Regul,
-                            (LossVal + Regul), Obj_Best, nnz, nnz_best, ttime, vtime);
+            std::string line;
+            const bool is_best = pr_log::objective(line, best, t, LossVal, Regul, nnz, w.data(), (size_t)FeatDim, ttime, vtime);   // :364
+            std::fputs(line.c_str(), stdout);
+            if (is_best) {
                 int32_t nPR = 0, Dim = 0, nzDim = 0;
                 float FPR95 = -1.f;
                 double AUC = 0.0;
                 if (dlco_pr_stats(ctx, w.data(), PRParams.data(), (int32_t)pshape[0], (int32_t)pshape[1], 8, -1, &nPR, &Dim, &nzDim, &FPR95,
                                   &AUC) != DLCO_OK)
                     throw std::runtime_error(dlco_pr_last_error(ctx));
-                if (Dim <= MaxDim) {                           // :385-400
-                    dlco_io::append_row_f32(dst, "w", w_Best.data(), (size_t)FeatDim);
-                    std::printf("Stat: nPR #%i (#%i) Dim/MaxDim [%i/%i] AUC: %.6f FPR95: %.2f [saved]\n", nPR, nzDim, Dim, MaxDim, AUC, FPR95 * 100);
-                } else {
-                    std::printf("Stat: nPR #%i (#%i) Dim/MaxDim [%i/%i] AUC: %.6f FPR95: %.2f\n", nPR, nzDim, Dim, MaxDim, AUC, FPR95 * 100);
-                }
-            } else {
-                std::printf("Step: %i  Loss: %.6f Regul: %.6f Obj: %.6f (%.6f)  NNZ: %i (%i)  Ttime: %.4f Vtime: %.4f\n", t, LossVal, Regul,
-                            (LossVal + Regul), Obj_Best, nnz, nnz_best, ttime, vtime);
+                const bool saved = pr_log::saves(Dim, MaxDim);
+                if (saved) dlco_io::append_row_f32(dst, "w", best.w_Best.data(), (size_t)FeatDim);   // :385-400
+                line.clear();
+                pr_log::stat(line, nPR, nzDim, Dim, MaxDim, AUC, FPR95, saved);
+                std::fputs(line.c_str(), stdout);
             }
             cout << std::flush;
             next_log += LogStep;

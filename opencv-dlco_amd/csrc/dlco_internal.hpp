@@ -255,6 +255,10 @@ void build_active_rows(const int32_t *pos_rows, const int32_t *neg_rows, const i
 // per-row sequential hinge sum (src/kernelop-opencv.cu:49-66), rows then summed in double
 void hinge_rows(const float *pos, int n_pos, const float *neg, int n_neg, float *row_sums, hipStream_t s);
 void sum_f32_to_f64(const float *x, int n, double *out, hipStream_t s);
+// count independent problems of the two calls above in one launch each (problem k at + k * ld)
+void hinge_rows_batched(const float *pos, int n_pos, const float *neg, int n_neg, long ld_in, float *row_sums, long ld_out, int count,
+                        hipStream_t s);
+void sum_f32_to_f64_batched(const float *x, int n, long ldx, double *out, int count, hipStream_t s);
 void trace_f64(const float *A, int F, long ld, double *out, hipStream_t s);
 void axpby_inplace(float *y, const float *x, float a, float b, size_t n, hipStream_t s);  // y = a*y + b*x
 void scale_rows(float *dst, long ldd, const float *src, long lds, const float *scale, const int32_t *src_rows,

@@ -167,10 +167,14 @@ __global__ void viol_active_kernel(const float *pd, const float *nd, int B, int3
 // H1 (src/kernelop-opencv.cu:49-66): one thread per positive row, the inner sum runs over the
 // negatives in index order in fp32 exactly as the reference kernel does:
 //   rsum = src1[idx] + 1 - src2[i]; tsum += (rsum > 0) ? rsum : 0
+// grid.y = independent problem: its pos / neg at + blockIdx.y * ld_in, its row sums at + blockIdx.y * ld_out
 __global__ __launch_bounds__(256) void hinge_rows_kernel(const float *pos, int n_pos, const float *neg, int n_neg,
-                                                         float *row_sums)
+                                                         float *row_sums, long ld_in, long ld_out)
 {
     __shared__ float sn[2048];
+    pos += blockIdx.y * ld_in;
+    neg += blockIdx.y * ld_in;
+    row_sums += blockIdx.y * ld_out;
     const int i = blockIdx.x * blockDim.x + threadIdx.x;
     const float base = (i < n_pos) ? pos[i] + 1.0f : 0.f;
     float tsum = 0.f;
@@ -187,9 +191,12 @@ __global__ __launch_bounds__(256) void hinge_rows_kernel(const float *pos, int n
     if (i < n_pos) row_sums[i] = tsum;
 }
 
-__global__ __launch_bounds__(1024) void sum_f64_kernel(const float *x, int n, double *out)
+// grid.x = independent sums: x + blockIdx.x * ldx into out[blockIdx.x]
+__global__ __launch_bounds__(1024) void sum_f64_kernel(const float *x, int n, double *out, long ldx)
 {
     __shared__ double part[16];
+    x += blockIdx.x * ldx;
+    out += blockIdx.x;
     double s = 0.0;
     for (int i = threadIdx.x; i < n; i += blockDim.x) s += (double)x[i];
     s = wave_sum_d(s);
@@ -369,13 +376,28 @@ void build_active_rows(const int32_t *pos_rows, const int32_t *neg_rows, const i
 void hinge_rows(const float *pos, int n_pos, const float *neg, int n_neg, float *row_sums, hipStream_t s)
 {
     if (n_pos <= 0) return;
-    hipLaunchKernelGGL(hinge_rows_kernel, dim3((n_pos + 255) / 256), dim3(256), 0, s, pos, n_pos, neg, n_neg, row_sums);
+    hipLaunchKernelGGL(hinge_rows_kernel, dim3((n_pos + 255) / 256), dim3(256), 0, s, pos, n_pos, neg, n_neg, row_sums, 0L, 0L);
+    DLCO_HIP(hipGetLastError());
+}
+
+void hinge_rows_batched(const float *pos, int n_pos, const float *neg, int n_neg, long ld_in, float *row_sums, long ld_out, int count,
+                        hipStream_t s)
+{
+    if (n_pos <= 0 || count <= 0) return;
+    hipLaunchKernelGGL(hinge_rows_kernel, dim3((n_pos + 255) / 256, count), dim3(256), 0, s, pos, n_pos, neg, n_neg, row_sums, ld_in, ld_out);
     DLCO_HIP(hipGetLastError());
 }
 
 void sum_f32_to_f64(const float *x, int n, double *out, hipStream_t s)
 {
-    hipLaunchKernelGGL(sum_f64_kernel, dim3(1), dim3(1024), 0, s, x, n, out);
+    hipLaunchKernelGGL(sum_f64_kernel, dim3(1), dim3(1024), 0, s, x, n, out, 0L);
+    DLCO_HIP(hipGetLastError());
+}
+
+void sum_f32_to_f64_batched(const float *x, int n, long ldx, double *out, int count, hipStream_t s)
+{
+    if (count <= 0) return;
+    hipLaunchKernelGGL(sum_f64_kernel, dim3(count), dim3(1024), 0, s, x, n, out, ldx);
     DLCO_HIP(hipGetLastError());
 }
 
