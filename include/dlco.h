@@ -409,7 +409,30 @@ int  dlco_desc_pair_dists_stream(dlco_desc_ctx *ctx, const uint8_t *patches_host
                                  int64_t n_pairs, int64_t chunk_rows, dlco_desc_sink_fn sink, void *user);
 int  dlco_desc_full_dists_stream(dlco_desc_ctx *ctx, const uint8_t *patches_host, int64_t n_patches, const int32_t *pairs_host,
                                  int64_t n_pairs, int64_t chunk_rows, dlco_desc_sink_fn sink, void *user);
-double dlco_desc_last_kernel_ms(const dlco_desc_ctx *ctx);               /* HIP-event time of the last compute call */
+/* ---- Using the learnt model: y = W * min(sPRFilters * get_desc(patch), 1), the descriptor all of the training is for.
+ * The reference has no such call: W (pj-learn's dataset "W", src/pj-learn.cpp:592-597) is only ever applied to pair
+ * differences inside ComputePJStats, and the per-patch form exists in OpenCV's re-encoding of the exported model alone.
+ * The product follows cv::gemm's rule for floats (double accumulation, one rounding to float). ---- */
+/* W [r, F] row-major, F must equal dlco_desc_size(), 1 <= r <= F; copied.  Replaces any earlier projection; rows are used
+ * as given (an all-zero row gives a zero column).  dlco_desc_set_filters drops a projection whose F no longer fits. */
+int  dlco_desc_set_projection(dlco_desc_ctx *ctx, const float *W_host, int32_t r, int32_t F);
+int32_t dlco_desc_projected_size(const dlco_desc_ctx *ctx);               /* r, 0 when none is set */
+/* Y [n, r], one row per patch [n,64,64] u8: stands in for Desc1 of src/comp-uprjdists.cpp:318-325 followed by W * Desc1.
+ * The device form writes r floats per row of pitch ld >= r and leaves the other ld - r untouched. */
+int  dlco_desc_describe(dlco_desc_ctx *ctx, const uint8_t *patches_host, int64_t n, float *out_host);
+int  dlco_desc_describe_device(dlco_desc_ctx *ctx, const uint8_t *patches_host, int64_t n, float *out_dev, int64_t ld);
+/* per pair ||Y[a] - Y[b]||^2 [n_pairs] and Label [n_pairs] (may be NULL) for pairs [n_pairs,4]: the distances
+ * ComputePJStats forms as ||W (Desc1 - Desc2)||^2 from comp-uprjdists' N x F rows (src/misc.cpp:279-292), taken from
+ * the table of projected descriptors instead; that table and the un-projected rows never leave HBM */
+int  dlco_desc_pair_sqdists(dlco_desc_ctx *ctx, const uint8_t *patches_host, int64_t n_patches, const int32_t *pairs_host,
+                            int64_t n_pairs, float *dist_host, uint8_t *label_host);
+/* ComputePJStats semantics (src/misc.cpp:266-333) on those distances, i.e. dlco_stats without the "-unproj" matrix:
+ * dim (may be NULL) = rows of W with a non-zero entry, FPR at 95 % recall, area under the ROC curve */
+int  dlco_desc_pair_stats(dlco_desc_ctx *ctx, const uint8_t *patches_host, int64_t n_patches, const int32_t *pairs_host,
+                          int64_t n_pairs, int32_t *dim, float *fpr95, double *auc);
+/* HIP-event time of the kernels of the last compute / describe call (transform, pooling, projection); the pair_sqdists /
+ * pair_stats calls add their distance kernel */
+double dlco_desc_last_kernel_ms(const dlco_desc_ctx *ctx);
 
 #ifdef __cplusplus
 }

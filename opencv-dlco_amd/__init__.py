@@ -137,6 +137,13 @@ def load():
     L.dlco_desc_compute_device.argtypes = [vp, u8p, i64, vp, i64]
     L.dlco_desc_pair_dists.argtypes = [vp, u8p, i64, i32p, i64, f32p, u8p]
     L.dlco_desc_full_dists.argtypes = [vp, u8p, i64, i32p, i64, f32p, u8p]
+    L.dlco_desc_set_projection.argtypes = [vp, f32p, C.c_int32, C.c_int32]
+    L.dlco_desc_projected_size.argtypes = [vp]
+    L.dlco_desc_projected_size.restype = C.c_int32
+    L.dlco_desc_describe.argtypes = [vp, u8p, i64, f32p]
+    L.dlco_desc_describe_device.argtypes = [vp, u8p, i64, vp, i64]
+    L.dlco_desc_pair_sqdists.argtypes = [vp, u8p, i64, i32p, i64, f32p, u8p]
+    L.dlco_desc_pair_stats.argtypes = [vp, u8p, i64, i32p, i64, C.POINTER(C.c_int32), C.POINTER(C.c_float), C.POINTER(C.c_double)]
     L.dlco_desc_last_kernel_ms.argtypes = [vp]
     L.dlco_desc_last_kernel_ms.restype = C.c_double
     L.dlco_pr_last_error.restype = C.c_char_p
@@ -686,6 +693,47 @@ class DescContext:
         lab = np.empty(q.shape[0], np.uint8)
         self._ck(self.L.dlco_desc_full_dists(self.h, _p(p, u8p), p.shape[0], _p(q, i32p), q.shape[0], _p(dist, f32p), _p(lab, u8p)))
         return dist, lab
+
+    # ---- the learnt descriptor y = W * min(sPRFilters * get_desc(patch), 1) ----
+    def set_projection(self, W):
+        """pj-learn's W [r, F] with F == size; replaces any earlier projection."""
+        w = _f32(W)
+        assert w.ndim == 2
+        self._ck(self.L.dlco_desc_set_projection(self.h, _p(w, f32p), w.shape[0], w.shape[1]))
+
+    @property
+    def projected_size(self):
+        return self.L.dlco_desc_projected_size(self.h)
+
+    def describe(self, patches):
+        """Learnt descriptors [n, r] of patches [n,64,64] u8."""
+        p = np.ascontiguousarray(patches, np.uint8)
+        assert p.ndim == 3 and p.shape[1:] == (64, 64)
+        out = np.empty((p.shape[0], self.projected_size), np.float32)
+        self._ck(self.L.dlco_desc_describe(self.h, _p(p, u8p), p.shape[0], _p(out, f32p)))
+        return out
+
+    def describe_device(self, patches, dev_ptr, ld=None):
+        p = np.ascontiguousarray(patches, np.uint8)
+        assert p.ndim == 3 and p.shape[1:] == (64, 64)
+        self._ck(self.L.dlco_desc_describe_device(self.h, _p(p, u8p), p.shape[0], C.c_void_p(dev_ptr), ld or self.projected_size))
+
+    def pair_sqdists(self, patches, pairs):
+        """Per pair ||y_a - y_b||^2 [n_pairs] f32 and labels [n_pairs] u8; the descriptors stay on the device."""
+        p, q = np.ascontiguousarray(patches, np.uint8), _i32(pairs)
+        assert p.ndim == 3 and p.shape[1:] == (64, 64) and q.ndim == 2 and q.shape[1] == 4
+        dist = np.empty(q.shape[0], np.float32)
+        lab = np.empty(q.shape[0], np.uint8)
+        self._ck(self.L.dlco_desc_pair_sqdists(self.h, _p(p, u8p), p.shape[0], _p(q, i32p), q.shape[0], _p(dist, f32p), _p(lab, u8p)))
+        return dist, lab
+
+    def pair_stats(self, patches, pairs):
+        """(dim, fpr95, auc) of the projected distances of a raw patch-pair set (ComputePJStats semantics)."""
+        p, q = np.ascontiguousarray(patches, np.uint8), _i32(pairs)
+        assert p.ndim == 3 and p.shape[1:] == (64, 64) and q.ndim == 2 and q.shape[1] == 4
+        dim, f, a = C.c_int32(), C.c_float(), C.c_double()
+        self._ck(self.L.dlco_desc_pair_stats(self.h, _p(p, u8p), p.shape[0], _p(q, i32p), q.shape[0], C.byref(dim), C.byref(f), C.byref(a)))
+        return dim.value, f.value, a.value
 
     def last_kernel_ms(self):
         return self.L.dlco_desc_last_kernel_ms(self.h)

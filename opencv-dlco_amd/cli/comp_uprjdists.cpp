@@ -7,8 +7,7 @@
 // [pairs, nsel*8] f32 (:254-349).  Each patch's descriptor is computed once on the GPU; the pair
 // differences are formed there too.  Extra flag: -device N.  A path that does not end in .h5/.hdf5 is a
 // directory of .npy files with the same dataset names (dlco_io.hpp).
-#include "../../include/dlco.h"
-#include "dlco_io.hpp"
+#include "desc_model.hpp"
 
 #include <chrono>
 #include <cstdio>
@@ -53,41 +52,21 @@ int main(int argc, char **argv)
         return 1;
     }
     try {
-        std::vector<size_t> fshape, ishape, pshape, wshape;
-        std::vector<float> PRFilters, w;
+        desc_model::PRFilters filters;
+        std::vector<size_t> ishape, pshape;
+        std::vector<float> sPR;
         std::vector<int32_t> pairs;
         std::vector<uint8_t> patches;
-        cout << "Load PRFilters." << endl;
-        dlco_io::read_dataset<float>(flt, "PRFilters", fshape, PRFilters);
-        if (fshape.size() != 3 || fshape[1] * fshape[2] != 4096) throw std::runtime_error("PRFilters must be [n,64,64]");
-        dlco_io::term_progress(1.0, -1);
+        desc_model::load_pr_filters(flt, filters);
         printf("ImageSet: [%s]\n", img);
         cout << "Load Indices." << endl;
         dlco_io::read_dataset<int32_t>(img, "Indices", ishape, pairs);
         if (ishape.size() != 2 || ishape[1] != 4) throw std::runtime_error("Indices must be [pairs,4]");
-        cout << "Load Patches." << endl;
-        dlco_io::read_dataset<uint8_t>(img, "Patches", pshape, patches);
-        if (pshape.size() != 3 || pshape[1] != 64 || pshape[2] != 64) throw std::runtime_error("Patches must be [n,64,64]");
-        dlco_io::term_progress(1.0, -1);
-        printf("Load Learnt Filters: [%s]#%i\n", prj, widx);
-        dlco_io::read_dataset<float>(prj, "w", wshape, w);
-        if (wshape.size() != 2 || widx < 0 || (size_t)widx >= wshape[0]) throw std::runtime_error("w has no such row");
-        const size_t wcols = wshape[1];
-        if (wcols * 8 != fshape[0]) throw std::runtime_error("PRFilters needs 8 rows per column of w");
-        const float *wrow = w.data() + (size_t)widx * wcols;
-
+        desc_model::load_patches(img, pshape, patches);
         int32_t nsel = 0;
-        if (dlco_desc_select_filters(PRFilters.data(), (int32_t)fshape[0], 4096, wrow, (int32_t)wcols, nullptr, &nsel) != DLCO_OK)
-            throw std::runtime_error("filter selection failed");
-        if (nsel < 1) throw std::runtime_error("no pooling region selected (w has no positive entry on a non-zero filter)");
-        std::vector<float> sPR((size_t)nsel * 4096);
-        dlco_desc_select_filters(PRFilters.data(), (int32_t)fshape[0], 4096, wrow, (int32_t)wcols, sPR.data(), &nsel);
-        printf("PRFilters: %i x %i\n", nsel, 4096);
-        printf("Descriptor size: %i\n", nsel * 8);
+        desc_model::select(filters, prj, widx, sPR, nsel);
 
-        dlco_desc_ctx *ctx = nullptr;
-        if (dlco_desc_create(&ctx, 1.4f, 8, 1, device) != DLCO_OK) throw std::runtime_error(dlco_desc_last_error(nullptr));
-        if (dlco_desc_set_filters(ctx, sPR.data(), nsel) != DLCO_OK) throw std::runtime_error(dlco_desc_last_error(ctx));
+        dlco_desc_ctx *ctx = desc_model::open_ctx(sPR, nsel, device);
         const size_t npairs = ishape[0], F = (size_t)nsel * 8;
         cout << "Export Pair Labels: #" << npairs << endl;
         dlco_io::term_progress(1.0, -1);

@@ -1,7 +1,8 @@
 // dlco_desc_api.cpp — C ABI of descriptor generation (comp-uprjdists): see the
 // dlco_desc_* block of include/dlco.h.  Host orchestration and the filter selection of
 // SelectPRFilters (src/misc.cpp:78-168, pure host logic); the patch transform, the pooling product and
-// the pair differences run in HIP kernels (kernels_desc.hip).
+// the pair differences run in HIP kernels (kernels_desc.hip), the projection by a learnt W and the distances
+// of projected descriptors in kernels_describe.hip.
 #include "../../include/dlco.h"
 
 #include "dlco_internal.hpp"
@@ -20,6 +21,8 @@ void desc_transform(const uint8_t *patches, int n_patches, const float *cf, int 
 void desc_pool(const float *PT, int n_patches, const float *Fl, int nsel, int nsel_pad, float *desc, long desc_ld, hipStream_t s);
 void desc_pair_diff(const float *desc, long ld, int F, const int32_t *pairs, long n_pairs, float *dist, uint8_t *label, hipStream_t s);
 void desc_full_dist(const float *desc, long ld, int n_groups, int n_pairs, float *dist, hipStream_t s);
+void desc_project(const float *desc, long desc_ld, int n, const float *W, int r, int F, float *Y, long y_ld, hipStream_t s);
+void desc_pair_sqdist(const float *Y, long ld, int r, const int32_t *pairs, long n_pairs, float *dist, uint8_t *label, hipStream_t s);
 }
 
 namespace {
@@ -39,6 +42,9 @@ struct dlco_desc_ctx {
     int nsel = 0, nsel_pad = 0;
     DevBuf<float> cf, filt, pt, desc_chunk;
     DevBuf<uint8_t> patches;
+    // the learnt projection W [r, proj_F] (pj-learn's output) and the projected rows of one chunk
+    int r = 0, proj_F = 0, proj_dim = 0;                   // proj_dim: rows of W with a non-zero entry (src/misc.cpp:269-277)
+    DevBuf<float> W, y_chunk;
     double last_ms = 0.0;
 };
 
@@ -65,16 +71,21 @@ int guarded(dlco_desc_ctx *c, Fn &&fn)
 
 void sync(dlco_desc_ctx *c) { DLCO_HIP(hipStreamSynchronize(c->stream)); }
 
-// descriptors of patches [n,64,64] (host) into dst: device memory when dst_dev, else host; row pitch ld floats
-void compute(dlco_desc_ctx *c, const uint8_t *patches_host, int64_t n, float *dst, bool dst_dev, long ld)
+// descriptors of patches [n,64,64] (host) into dst: device memory when dst_dev, else host; row pitch ld floats.
+// With `project` a row is the learnt descriptor W * Desc (r floats): the un-projected rows of a chunk stay in the
+// library's scratch buffer and the projection kernel follows the pooling product on the same stream.
+void compute(dlco_desc_ctx *c, const uint8_t *patches_host, int64_t n, float *dst, bool dst_dev, long ld, bool project = false)
 {
     DLCO_CHECK(c->nsel > 0, DLCO_ERR_INVALID, "dlco_desc: set the filters first");
     const int F = c->nsel * kBins;
-    DLCO_CHECK(ld >= F, DLCO_ERR_INVALID, "dlco_desc: row pitch below the descriptor size");
+    DLCO_CHECK(!project || (c->r > 0 && c->proj_F == F), DLCO_ERR_INVALID, "dlco_desc: set a projection that fits the filters first");
+    const int cols = project ? c->r : F;                   // floats per output row
+    DLCO_CHECK(ld >= cols, DLCO_ERR_INVALID, project ? "dlco_desc: row pitch below the projected size" : "dlco_desc: row pitch below the descriptor size");
     DLCO_HIP(hipSetDevice(c->device));
     c->patches.alloc((size_t)kChunk * kPix);
     c->pt.alloc((size_t)kChunk * kBins * kPix);
-    if (!dst_dev) c->desc_chunk.alloc((size_t)kChunk * F);
+    if (!dst_dev || project) c->desc_chunk.alloc((size_t)kChunk * F);
+    if (!dst_dev && project) c->y_chunk.alloc((size_t)kChunk * cols);
     hipEvent_t e0, e1;
     DLCO_HIP(hipEventCreate(&e0));
     DLCO_HIP(hipEventCreate(&e1));
@@ -84,13 +95,18 @@ void compute(dlco_desc_ctx *c, const uint8_t *patches_host, int64_t n, float *ds
         DLCO_HIP(hipMemcpyAsync(c->patches.p, patches_host + p0 * kPix, (size_t)cnt * kPix, hipMemcpyHostToDevice, c->stream));
         DLCO_HIP(hipEventRecord(e0, c->stream));
         desc_transform(c->patches.p, cnt, c->cf.p, c->ks, c->inv_step, c->norm, c->qk, c->qgamma, c->pt.p, c->stream);
-        float *out = dst_dev ? dst + p0 * ld : c->desc_chunk.p;
-        const long old = dst_dev ? ld : F;
-        desc_pool(c->pt.p, cnt, c->filt.p, c->nsel, c->nsel_pad, out, old, c->stream);
+        float *out = dst_dev ? dst + p0 * ld : (project ? c->y_chunk.p : c->desc_chunk.p);
+        const long old = dst_dev ? ld : cols;
+        if (project) {
+            desc_pool(c->pt.p, cnt, c->filt.p, c->nsel, c->nsel_pad, c->desc_chunk.p, F, c->stream);
+            desc_project(c->desc_chunk.p, F, cnt, c->W.p, c->r, F, out, old, c->stream);
+        } else {
+            desc_pool(c->pt.p, cnt, c->filt.p, c->nsel, c->nsel_pad, out, old, c->stream);
+        }
         DLCO_HIP(hipEventRecord(e1, c->stream));
         if (!dst_dev)
-            DLCO_HIP(hipMemcpy2DAsync(dst + p0 * ld, (size_t)ld * sizeof(float), c->desc_chunk.p, (size_t)F * sizeof(float),
-                                      (size_t)F * sizeof(float), (size_t)cnt, hipMemcpyDeviceToHost, c->stream));
+            DLCO_HIP(hipMemcpy2DAsync(dst + p0 * ld, (size_t)ld * sizeof(float), out, (size_t)cols * sizeof(float),
+                                      (size_t)cols * sizeof(float), (size_t)cnt, hipMemcpyDeviceToHost, c->stream));
         sync(c);
         float ms = 0.f;
         DLCO_HIP(hipEventElapsedTime(&ms, e0, e1));
@@ -220,6 +236,7 @@ int dlco_desc_set_filters(dlco_desc_ctx *c, const float *filters_host, int32_t n
         DLCO_HIP(hipSetDevice(c->device));
         c->nsel = nsel;
         c->nsel_pad = (nsel + 127) / 128 * 128;
+        if (c->proj_F != nsel * kBins) { c->r = 0; c->proj_F = 0; c->proj_dim = 0; }     // a projection of another width no longer fits
         DevBuf<float> raw;
         raw.alloc((size_t)nsel * kPix);
         DLCO_HIP(hipMemcpyAsync(raw.p, filters_host, (size_t)nsel * kPix * sizeof(float), hipMemcpyHostToDevice, c->stream));
@@ -386,7 +403,118 @@ int dlco_desc_full_dists(dlco_desc_ctx *c, const uint8_t *patches_host, int64_t 
     return dlco_desc_full_dists_stream(c, patches_host, n_patches, pairs_host, n_pairs, (int64_t)1 << 40, copy_sink, &k);
 }
 
-// milliseconds the transform + pooling kernels of the last dlco_desc_compute* call took (HIP events)
+// ---- the learnt descriptor: y = W * min(sPRFilters * get_desc(patch), 1) --------------------------------------------
+// W [r, F] is pj-learn's output (dataset "W"), applied there to pair differences (src/pj-learn.cpp:551, ComputePJStats);
+// here it is applied to the descriptor of a patch, which is what a user of the trained model wants back.
+int dlco_desc_set_projection(dlco_desc_ctx *c, const float *W_host, int32_t r, int32_t F)
+{
+    if (!c || !W_host) return DLCO_ERR_INVALID;
+    return guarded(c, [&] {
+        DLCO_CHECK(c->nsel > 0, DLCO_ERR_INVALID, "dlco_desc_set_projection: set the filters first");
+        DLCO_CHECK(F == c->nsel * kBins, DLCO_ERR_INVALID, "dlco_desc_set_projection: W has " + std::to_string(F) + " columns, the descriptor " +
+                                                               std::to_string(c->nsel * kBins) + " entries");
+        DLCO_CHECK(r >= 1 && r <= F, DLCO_ERR_INVALID, "dlco_desc_set_projection: r must be in [1, F]");
+        int dim = 0;
+        for (int i = 0; i < r; i++) {
+            const float *row = W_host + (size_t)i * F;
+            bool any = false;
+            for (int f = 0; f < F && !any; f++) any = row[f] != 0.0f;
+            dim += any ? 1 : 0;
+        }
+        DLCO_HIP(hipSetDevice(c->device));
+        c->r = 0; c->proj_F = 0; c->proj_dim = 0;
+        c->W.alloc((size_t)r * F);
+        DLCO_HIP(hipMemcpyAsync(c->W.p, W_host, (size_t)r * F * sizeof(float), hipMemcpyHostToDevice, c->stream));
+        sync(c);
+        c->r = r; c->proj_F = F; c->proj_dim = dim;
+    });
+}
+
+int32_t dlco_desc_projected_size(const dlco_desc_ctx *c) { return c ? c->r : 0; }
+
+// Y [n, r], one row per patch; the un-projected rows never leave the device
+int dlco_desc_describe(dlco_desc_ctx *c, const uint8_t *patches_host, int64_t n, float *out_host)
+{
+    if (!c || !patches_host || !out_host || n < 1) return DLCO_ERR_INVALID;
+    return guarded(c, [&] { compute(c, patches_host, n, out_host, false, (long)c->r, true); });
+}
+
+int dlco_desc_describe_device(dlco_desc_ctx *c, const uint8_t *patches_host, int64_t n, float *out_dev, int64_t ld)
+{
+    if (!c || !patches_host || !out_dev || n < 1) return DLCO_ERR_INVALID;
+    return guarded(c, [&] { compute(c, patches_host, n, out_dev, true, (long)ld, true); });
+}
+
+namespace {
+// The table Y [n_patches, r] of every patch's learnt descriptor (128 MB at 500k x 64) and, from it, the squared distance
+// and label of every pair, all in device memory: what eval-fpr95 gets out of an N x F "-unproj" file, without that matrix.
+struct PairDists {
+    DevBuf<float> Y, dist;
+    DevBuf<uint8_t> label;
+    DevBuf<int32_t> pairs;
+};
+void projected_pair_dists(dlco_desc_ctx *c, const uint8_t *patches_host, int64_t n_patches, const int32_t *pairs_host, int64_t n_pairs,
+                          PairDists &w)
+{
+    DLCO_CHECK(c->nsel > 0, DLCO_ERR_INVALID, "dlco_desc: set the filters first");
+    DLCO_CHECK(c->r > 0 && c->proj_F == c->nsel * kBins, DLCO_ERR_INVALID, "dlco_desc: set a projection that fits the filters first");
+    DLCO_CHECK(n_pairs <= (int64_t)0x7fffffff / 4, DLCO_ERR_INVALID, "dlco_desc: too many pairs for one call");
+    check_pairs(pairs_host, n_pairs, n_patches);
+    DLCO_HIP(hipSetDevice(c->device));
+    w.Y.alloc((size_t)n_patches * c->r);
+    w.dist.alloc((size_t)n_pairs);
+    w.label.alloc((size_t)n_pairs);
+    w.pairs.alloc((size_t)n_pairs * 4);
+    compute(c, patches_host, n_patches, w.Y.p, true, (long)c->r, true);
+    hipEvent_t e0, e1;
+    DLCO_HIP(hipEventCreate(&e0));
+    DLCO_HIP(hipEventCreate(&e1));
+    DLCO_HIP(hipMemcpyAsync(w.pairs.p, pairs_host, (size_t)n_pairs * 4 * sizeof(int32_t), hipMemcpyHostToDevice, c->stream));
+    DLCO_HIP(hipEventRecord(e0, c->stream));
+    desc_pair_sqdist(w.Y.p, c->r, c->r, w.pairs.p, n_pairs, w.dist.p, w.label.p, c->stream);
+    DLCO_HIP(hipEventRecord(e1, c->stream));
+    sync(c);
+    float ms = 0.f;
+    DLCO_HIP(hipEventElapsedTime(&ms, e0, e1));
+    (void)hipEventDestroy(e0);
+    (void)hipEventDestroy(e1);
+    c->last_ms += ms;
+}
+}  // namespace
+
+// per pair ||Y[a] - Y[b]||^2 and Label: the distances pj-learn's W gives on comp-uprjdists' rows (ComputePJStats forms
+// them as ||W (Desc1 - Desc2)||^2, src/misc.cpp:279-292), computed from the projected descriptors of the patches
+int dlco_desc_pair_sqdists(dlco_desc_ctx *c, const uint8_t *patches_host, int64_t n_patches, const int32_t *pairs_host, int64_t n_pairs,
+                           float *dist_host, uint8_t *label_host)
+{
+    if (!c || !patches_host || !pairs_host || !dist_host || n_patches < 1 || n_pairs < 1) return DLCO_ERR_INVALID;
+    return guarded(c, [&] {
+        PairDists w;
+        projected_pair_dists(c, patches_host, n_patches, pairs_host, n_pairs, w);
+        DLCO_HIP(hipMemcpyAsync(dist_host, w.dist.p, (size_t)n_pairs * sizeof(float), hipMemcpyDeviceToHost, c->stream));
+        if (label_host) DLCO_HIP(hipMemcpyAsync(label_host, w.label.p, (size_t)n_pairs, hipMemcpyDeviceToHost, c->stream));
+        sync(c);
+    });
+}
+
+// ComputePJStats (src/misc.cpp:266-333) on those distances: FPR at 95 % recall and the area under the ROC curve by the
+// trainer's own routine (kernels_stats.hip); dim counts the rows of W that have a non-zero entry (S1, :269-277)
+int dlco_desc_pair_stats(dlco_desc_ctx *c, const uint8_t *patches_host, int64_t n_patches, const int32_t *pairs_host, int64_t n_pairs,
+                         int32_t *dim, float *fpr95, double *auc)
+{
+    if (!c || !patches_host || !pairs_host || !fpr95 || !auc || n_patches < 1 || n_pairs < 1) return DLCO_ERR_INVALID;
+    return guarded(c, [&] {
+        PairDists w;
+        projected_pair_dists(c, patches_host, n_patches, pairs_host, n_pairs, w);
+        RocWork *roc = roc_work_create((int)n_pairs);
+        try { roc_stats(roc, w.dist.p, w.label.p, (int)n_pairs, fpr95, auc, c->stream); } catch (...) { roc_work_destroy(roc); throw; }
+        roc_work_destroy(roc);
+        if (dim) *dim = c->proj_dim;
+    });
+}
+
+// milliseconds the kernels of the last dlco_desc_compute* / dlco_desc_describe* call took (HIP events): transform and
+// pooling, plus the projection for describe; the pair calls add their distance kernel
 double dlco_desc_last_kernel_ms(const dlco_desc_ctx *c) { return c ? c->last_ms : 0.0; }
 
 }  // extern "C"
