@@ -335,7 +335,7 @@ void project_few(dlco_ctx *c, const int32_t *ids_dev, int n, const float *Wd, in
     const int bm = rp <= 128 ? 64 : 128;     // (a 96-row block: two 64-row tiles or one of 128 measured the same, 25 us;
     const int bn = (n <= 64 || bm == 64) ? 64 : 128;                                                         //  64-column tiles as well: 19 us)
     const long tiles = (long)((rp + bm - 1) / bm) * ((n + bn - 1) / bn);
-    long split = std::max(1L, std::min((512 + tiles - 1) / tiles, (long)c->F / 128));
+    const int split = split_k_slices(tiles, 512, c->F, 128);
     const size_t need = (size_t)(split + 1) * rp * n;
     if (need > c->proj_slab_floats) { sync(c); c->proj_slab.alloc(need); c->proj_slab_floats = need; }
     float *proj = c->proj_slab.p + (size_t)split * rp * n;      // reduced [rp][n] projection behind the slabs
@@ -345,7 +345,7 @@ void project_few(dlco_ctx *c, const int32_t *ids_dev, int n, const float *Wd, in
     const RowRef rr = rows_of(c, ids_dev, 0, n);
     g.B.p = c->dists; g.B.ld = c->F; g.B.kmajor = false; g.B.row_ids = rr.a; g.B.row_ids2 = rr.b;
     g.C = proj; g.ldc = n;
-    g.split_k = (int)split; g.slab = c->proj_slab.p;
+    g.split_k = split; g.slab = c->proj_slab.p;
     g.small_m_tiles = bm == 64;
     g.small_n_tiles = bn == 64;
     c->prof.begin(PROF_PROJECT);
@@ -444,7 +444,6 @@ void step_grad(dlco_ctx *c)
     DLCO_CHECK(c->phase == 1, DLCO_ERR_INVALID, "dlco_step_grad: call dlco_step_begin first");
     DLCO_CHECK(!c->shard, DLCO_ERR_INVALID, "dlco_step_grad: a sharded context steps with dlco_step");
     const int B = c->B, Bl = c->Bl, world = c->cfg.world;
-    (void)world;
     gather_dists(c, &c->pd_cur, &c->nd_cur);
     viol_counts_active_rows(c->pd_cur, c->nd_cur, B, c->rho.p, c->kappa.p, c->pos_rows.p, c->neg_rows.p, c->lo, c->lo + Bl,
                             c->act_ids.p, c->act_w.p, c->k_active.p, c->stream, c->act_slot.p);
@@ -1261,7 +1260,7 @@ int dlco_sym_product(dlco_ctx *c, const float *X_host, int32_t rows, const float
             g.C = out.p; g.ldc = F;
             const int bm = rows <= 64 ? 64 : 128;                // K slices as the tracker's products choose them
             const long tiles = (long)((rows + bm - 1) / bm) * ((F + 127) / 128);
-            g.split_k = (int)std::max(1L, std::min((1023 + tiles) / tiles, (long)F / 256));
+            g.split_k = split_k_slices(tiles, 1024, F, 256);
             DevBuf<float> slab;
             slab.alloc(gemm_slab_floats(rows, F, g.split_k));
             g.slab = slab.p;

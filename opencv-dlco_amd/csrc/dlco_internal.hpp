@@ -4,6 +4,8 @@
 
 #include <hip/hip_runtime.h>
 
+#include <algorithm>
+#include <climits>
 #include <cstdint>
 #include <cstdio>
 #include <cstdlib>
@@ -151,8 +153,6 @@ struct GemmArgs {
     int split_k = 1;                    // >1: partial slabs + ordered reduce
     float *slab = nullptr;              // workspace >= split_k*M*N floats when split_k > 1
     bool upper_only = false;            // M==N: compute tiles with j-block >= i-block, mirror the rest
-    bool raw_slab = false;              // keep the [split][M][N] partials in `slab`, skip the reduce (C unused)
-    int *split_out = nullptr;           // receives the number of K slices actually used
     const float *B2 = nullptr;          // twin product in the same launch: C2 = alpha * A * B2 (+ the same epilogue terms), B2 laid
     float *C2 = nullptr;                // out like B; needs split_k == 1
     bool small_m_tiles = false;         // 64-row tiles whatever M ...
@@ -232,6 +232,14 @@ bool skinny_product_sym(const float *X, long ldx, int M, const float *Gpacked, i
 // planes_ready: plane_hi / plane_lo already hold the two-way planes of X (skip the split); emit_planes: the reduction also
 // writes the two-way planes of the RESULT into plane_hi / plane_lo (the next product of a Chebyshev chain takes it as X)
 size_t gemm_slab_floats(int M, int N, int split_k);
+// K slices (GemmArgs::split_k) for a product whose M x N tile grid alone would leave the chip idle: enough that
+// tiles * slices reaches `target` workgroups, no slice shorter than kmin, no more slices than the slab holds
+// (slab_cap = slab floats / (M * N)); never fewer than one.
+inline int split_k_slices(long tiles, long target, long K, long kmin, long slab_cap = LONG_MAX)
+{
+    const long split = std::min(std::min((target + tiles - 1) / tiles, K / kmin), slab_cap);
+    return (int)std::max(1L, split);
+}
 void splitk_reduce_f32(const float *slab, int split, int M, int N, float *C, long ldc, float alpha, float beta,
                        const float *E1, float b1, const float *E2, float b2, hipStream_t s);
 
@@ -259,7 +267,6 @@ void sum_f32_to_f64(const float *x, int n, double *out, hipStream_t s);
 void hinge_rows_batched(const float *pos, int n_pos, const float *neg, int n_neg, long ld_in, float *row_sums, long ld_out, int count,
                         hipStream_t s);
 void sum_f32_to_f64_batched(const float *x, int n, long ldx, double *out, int count, hipStream_t s);
-void trace_f64(const float *A, int F, long ld, double *out, hipStream_t s);
 void axpby_inplace(float *y, const float *x, float a, float b, size_t n, hipStream_t s);  // y = a*y + b*x
 void scale_rows(float *dst, long ldd, const float *src, long lds, const float *scale, const int32_t *src_rows,
                 int rows, int cols, hipStream_t s, const int32_t *src_rows2 = nullptr);    // dst[i] = scale[i]*(src[src_rows[i]] - src[src_rows2[i]])
@@ -315,10 +322,8 @@ size_t jacobi_work_floats(int n);
 // Linv is zero.
 constexpr int CHOL_INV_MAX_N = 160;
 void chol_inverse128(const float *M, long ldm, int n, float rel_thresh, float *Linv, long ldl, int *dead, hipStream_t s);
-// row norms of (Y - theta_i X) and of X
-// n floats -> pinned host memory, then *flag_host = seq with system-scope release (the host polls flag_host)
-void publish_block(const float *src, float *dst_host, int n, unsigned *flag_host, unsigned seq, hipStream_t s,
-                   const int *extra_dev = nullptr, int *extra_host = nullptr);   // extra: one device int copied along
+// row norms of (Y - theta_i X); the publishing form also copies the n floats at `src` into pinned host memory and then
+// sets *flag_host = seq with a system-scope release (the host polls flag_host; extra: one device int copied along)
 // What the residual kernel may emit on the way (see residual_publish_kernel): the rows of W of the pass it closes
 struct ResidualEmit {
     float *W = nullptr;

@@ -13,6 +13,14 @@ namespace {
 inline int ceil_div(long a, long b) { return (int)((a + b - 1) / b); }
 }  // namespace
 
+// Inside a filter chain the reduction of one product emits the two-way planes of its result, which is the X of the next
+// product: that one then skips its split.  The chain lives as long as one filter (filter_plain).
+struct EigTracker::PlaneChain {
+    const float *planes_of = nullptr;   // the matrix whose two-way planes sit in plane_hi_/plane_lo_ (emitted by a reduction)
+    int rows = 0;
+    bool next = false;                  // the product being issued feeds the next one of the chain
+};
+
 EigTracker::EigTracker(int F, int max_rows, int guard, float tol, int max_iter, hipStream_t stream, int live_cols)
     : F_(F), live_(live_cols > 0 ? std::min(live_cols, F) : F), guard_(guard), max_iter_(max_iter), tol_(tol), s_(stream)
 {
@@ -124,7 +132,7 @@ void EigTracker::append_random(float *Q, int have, int add)
 
 // out[rows][F] = alpha * X*G + b1*E1 + b2*E2     (G symmetric F x F)
 void EigTracker::product(const float *X, int rows, const float *G, float alpha, float *out, const float *E1, float b1,
-                         const float *E2, float b2, bool approx)
+                         const float *E2, float b2, bool approx, PlaneChain *chain)
 {
     // the split-bf16 kernels take up to 128 rows: a taller block goes through them in row chunks
     // (one HBM-bound pass over G per chunk, still cheaper than the generic fp32 GEMM)
@@ -132,12 +140,12 @@ void EigTracker::product(const float *X, int rows, const float *G, float alpha, 
     // in ONE pass over G - and 96 with the three-way split; a sharded rank's slab kernel 128)
     const int one_pass = (approx && !shard_) ? 160 : (packed_ ? 96 : 128);   // (symmetric three-way kernel: 96 rows)
     if (rows > one_pass && (packed_ || F_ >= 256)) {
-        chain_next_ = false;                                     // row chunks share the plane buffers: no carried planes
+        if (chain) chain->next = false;                          // row chunks share the plane buffers: no carried planes
         const int step = approx ? (rows <= 2 * one_pass ? (rows / 2 + 31) / 32 * 32 : one_pass) : 96;
         for (int r0 = 0; r0 < rows; r0 += step) {
             const int nr = std::min(step, rows - r0);
             const size_t o = (size_t)r0 * F_;
-            product(X + o, nr, G, alpha, out + o, E1 ? E1 + o : nullptr, b1, E2 ? E2 + o : nullptr, b2, approx);
+            product(X + o, nr, G, alpha, out + o, E1 ? E1 + o : nullptr, b1, E2 ? E2 + o : nullptr, b2, approx, chain);
         }
         return;
     }
@@ -146,13 +154,12 @@ void EigTracker::product(const float *X, int rows, const float *G, float alpha, 
         // G = packed upper tiles: the symmetric kernel (every tile fetched once); two-way split for the filter, three-way
         // for the exact products (rows <= 96 there: the chunking above)
         if (prof_) prof_->begin(PROF_EIG_PRODUCT);
-        // inside a filter chain the planes of X are those the previous product's reduction emitted (chain_next_)
-        const bool ready = approx && chain_planes_of_ == X && chain_rows_ == rows;
-        const bool emit = approx && chain_next_;
+        // inside a filter chain the planes of X are those the previous product's reduction emitted
+        const bool ready = approx && chain && chain->planes_of == X && chain->rows == rows;
+        const bool emit = approx && chain && chain->next;
         const bool ok = skinny_product_sym(X, F_, rows, G, F_, alpha, out, F_, E1, b1, E2, b2, plane_hi_.p, plane_lo_.p, slab_.p, s_,
                                            approx ? nullptr : plane_lo2_.p, ready, emit);
-        chain_planes_of_ = emit ? out : nullptr;                 // (a product without `emit` has overwritten the planes with X's)
-        chain_rows_ = rows;
+        if (chain) { chain->planes_of = emit ? out : nullptr; chain->rows = rows; }   // (a product without `emit` has overwritten the planes with X's)
         if (prof_) prof_->end(PROF_EIG_PRODUCT);
         DLCO_CHECK(ok, -2, "eig tracker: the symmetric product rejected a shape of the packed layout");
         return;
@@ -178,9 +185,7 @@ void EigTracker::product(const float *X, int rows, const float *G, float alpha, 
             g.C = out + c0; g.ldc = F_;
             g.alpha = alpha; g.E1 = E1s; g.b1 = b1; g.E2 = E2s; g.b2 = b2;
             const long tiles = (long)ceil_div(rows, rows <= 64 ? 64 : 128) * ceil_div(cw, 128);
-            long split = std::max(1L, std::min((long)ceil_div(512, tiles), (long)F_ / 256));
-            split = std::min(split, (long)(slab_floats_ / ((size_t)rows * cw)));
-            g.split_k = (int)std::max(1L, split);
+            g.split_k = split_k_slices(tiles, 512, F_, 256, (long)(slab_floats_ / ((size_t)rows * cw)));
             g.slab = slab_.p;
             gemm_f32(g, s_);
         }
@@ -206,34 +211,11 @@ void EigTracker::product(const float *X, int rows, const float *G, float alpha, 
     g.alpha = alpha; g.E1 = E1; g.b1 = b1; g.E2 = E2; g.b2 = b2;
     const int bm = rows <= 64 ? 64 : 128;
     const long tiles = (long)ceil_div(rows, bm) * ceil_div(F_, 128);
-    long split = std::max(1L, std::min((long)ceil_div(1024, tiles), (long)F_ / 256));
-    split = std::min(split, (long)(slab_floats_ / ((size_t)rows * F_)));
-    g.split_k = (int)std::max(1L, split);
+    g.split_k = split_k_slices(tiles, 1024, F_, 256, (long)(slab_floats_ / ((size_t)rows * F_)));
     g.slab = slab_.p;
     if (prof_) prof_->begin(PROF_EIG_PRODUCT);
     gemm_f32(g, s_);
     if (prof_) prof_->end(PROF_EIG_PRODUCT);
-}
-
-// T[rows][rows] (ld cap_) = X * Y^T
-void EigTracker::gram(const float *X, const float *Y, int rows, float *T)
-{
-    GemmArgs g;
-    g.M = rows; g.N = rows; g.K = F_;
-    g.A.p = X; g.A.ld = F_; g.A.kmajor = false;
-    g.B.p = Y; g.B.ld = F_; g.B.kmajor = false;
-    g.C = T; g.ldc = cap_;
-    const int bt = rows <= 64 ? 64 : 128;
-    const long tiles = (long)ceil_div(rows, bt) * ceil_div(rows, bt);
-    // (at most 64 K slices, none shorter than 64: 64 slices of 128 at F = 8192 - with 128 slices of 64 the launch is no faster
-    // and the ordered reduce reads twice as much, 593 -> 608 k on c2 - and ten slices of 64 at the reference's F = 640, where five
-    // of 128 measured 2.5 % slower)
-    const long kslice = std::max(64L, (long)F_ / 64 / 64 * 64);
-    long split = std::max(1L, std::min((long)ceil_div(512, tiles), (long)F_ / kslice));
-    split = std::min(split, (long)(slab_floats_ / ((size_t)rows * rows)));
-    g.split_k = (int)std::max(1L, split);
-    g.slab = slab_.p;
-    gemm_f32(g, s_);
 }
 
 // out[k_out][F] = C X with C [k_out][ldc] holding the coefficient vectors in its rows (jacobi_eigh's layout)
@@ -257,10 +239,11 @@ void EigTracker::gram_rect(const float *X, int xrows, const float *Y, int yrows,
     g.B.p = Y; g.B.ld = F_; g.B.kmajor = false;
     g.C = T; g.ldc = cap_;
     const long tiles = (long)ceil_div(xrows, xrows <= 64 ? 64 : 128) * ceil_div(yrows, yrows <= 64 ? 64 : 128);
-    const long kslice = std::max(64L, (long)F_ / 64 / 64 * 64);          // as in gram()
-    long split = std::max(1L, std::min((long)ceil_div(512, tiles), (long)F_ / kslice));
-    split = std::min(split, (long)(slab_floats_ / ((size_t)xrows * yrows)));
-    g.split_k = (int)std::max(1L, split);
+    // (at most 64 K slices, none shorter than 64: 64 slices of 128 at F = 8192 - with 128 slices of 64 the launch is no faster
+    // and the ordered reduce reads twice as much, 593 -> 608 k on c2 - and ten slices of 64 at the reference's F = 640, where five
+    // of 128 measured 2.5 % slower)
+    const long kslice = std::max(64L, (long)F_ / 64 / 64 * 64);
+    g.split_k = split_k_slices(tiles, 512, F_, kslice, (long)(slab_floats_ / ((size_t)xrows * yrows)));
     g.slab = slab_.p;
     gemm_f32(g, s_);
 }
@@ -312,7 +295,7 @@ int EigTracker::orthonormalize(float *Z, int rows, float *scratch, const std::ve
         for (int pass = 0; pass < 2; pass++) {
             const float *src = pass == 0 ? Wp : Sp;
             float *dst = pass == 0 ? Sp : Wp;
-            gram(src, src, np, Tm_.p);
+            gram_rect(src, np, src, np, Tm_.p);
             chol_inverse128(Tm_.p, cap_, np, 1e-5f, Vm_.p, cap_, dead_.p, s_);
             GemmArgs g;                                           // dst = Linv * src
             g.M = np; g.N = F_; g.K = np;
@@ -384,214 +367,204 @@ void EigTracker::refresh_lower_bound(const float *G, int iters, float theta_top)
     steps_since_lo_ = 0;
 }
 
+// What one update() carries from stage to stage.
+struct EigTracker::UpdateState {
+    const float *G = nullptr;        // update()'s arguments
+    float mu = 0.f, cscale = 0.f;
+    float *W = nullptr;
+    float tol = 0.f;                 // tolerance of this update (a quarter of tol_ when the block is cold)
+    bool ru_ok = false;              // the caller's rank update may form the first filter term of pass 0
+    int ru_nw = 0;                   // Ritz rows of the W its projections were made with
+    int it = 0;                      // pass
+    int nw = 0;                      // Ritz pairs above mu as of the last pass
+    int n_ritz = 0;                  // leading rows that are Ritz vectors with a known theta
+    float theta_top = 0.f, block_min = 0.f;
+    bool conv = false, cheap_done = false;
+    bool w_emitted = false;          // the last pass's residual kernel has written W (all rows of that pass's block, scales too)
+    eig_rules::FilterPlan plan;      // of the current pass
+    std::vector<int> panel_ends;
+};
+
+eig_rules::Block EigTracker::block_of(const UpdateState &u) const
+{
+    eig_rules::Block b;
+    b.theta = h_theta_.data(); b.res = h_res_.data();
+    b.m = m_; b.live = live_; b.guard = guard_;
+    b.mu = u.mu; b.cscale = u.cscale; b.tol = u.tol;
+    return b;
+}
+
 int EigTracker::update(const float *G, float mu, float cscale, float *W, double *trace, bool *converged)
 {
     st_.updates++;
+    UpdateState u;
+    u.G = G; u.mu = mu; u.cscale = cscale; u.W = W;
+    open_update(u);                                                  // seed an empty block, refresh the lower bound
+    for (; u.it < max_iter_; u.it++) {
+        u.plan = eig_rules::plan_filter(block_of(u), u.n_ritz, u.nw, u.it, deg0_, lo_bound_, u.block_min, u.theta_top, lock_,
+                                        !u.cheap_done && y_ok_, last_crit_);
+        float *Z = Q_;
+        if (u.plan.cheap) { u.cheap_done = true; Z = filter_cheap(u); }
+        else if (u.plan.n_lock > 0) Z = filter_locked(u);
+        else if (u.plan.filtered) Z = filter_plain(u);
+        if (u.plan.filtered) last_deg_ = u.plan.d;
+        eig_rules::cut_panels(block_of(u), u.n_ritz, u.plan, CHOL_INV_MAX_N, u.panel_ends);
+        orthonormalize(Z, m_, pick({Z}), u.panel_ends, u.plan.n_lock);   // in place
+        rayleigh_ritz(u, Z);
+        judge(u);
+        // a block whose positive eigenspace reaches into its guards grows; a full one that cannot
+        // cannot certify the rank: the reference keeps EVERY positive eigen-direction
+        // (src/pj-learn.cpp:480-484), so this is reported, never silently truncated
+        const bool crowded = m_ < live_ && eig_rules::reaches_guards(u.nw, m_, guard_);
+        if (crowded) u.conv = false;
+        if (crowded && m_ < cap_) { grow(u); continue; }
+        if (crowded || u.conv) { u.it++; break; }
+    }
+    const double tr = trim_and_emit(u);
+    if (converged) *converged = u.conv;
+    if (trace) *trace = tr;
+    return u.nw;
+}
+
+void EigTracker::open_update(UpdateState &u)
+{
     // The caller may have told what changed: G = beta G_prev + alpha X_a^T diag(w) X_a (offer_rank_update).  With Y_ = Q_ H_prev
     // still there from the last Rayleigh-Ritz step and the projections of X_a on exactly these rows, the first filter
     // term needs no pass over G (kernels_rankupd.hip).
-    const bool ru_ok = ru_offered_ && y_ok_ && have_theta_ && packed_ && !shard_ && wext_rows_ == m_ &&
-                       ru_.rows == m_ && m_ >= 1 && m_ <= 160 && m_ < live_ && ru_.proj && ru_.planes;
+    u.ru_ok = ru_offered_ && y_ok_ && have_theta_ && packed_ && !shard_ && wext_rows_ == m_ &&
+              ru_.rows == m_ && m_ >= 1 && m_ <= 160 && m_ < live_ && ru_.proj && ru_.planes;
     ru_offered_ = false;
-    const int ru_nw = wext_nw_;
-    wext_rows_ = 0;                                                  // W is rewritten below
+    u.ru_nw = wext_nw_;
+    wext_rows_ = 0;                                                  // W is rewritten by this update
     y_ok_ = false;                                                   // G changed since the last Rayleigh-Ritz step
     if (m_ == 0) {
         m_ = std::min(cap_, 2 * guard_ + 32);
         append_random(Q_, 0, m_);
         have_theta_ = false;
     }
-    float theta_top = have_theta_ ? h_theta_[0] : 0.f;
-    float block_min = have_theta_ ? std::min(h_theta_[m_ - 1], mu) : mu;
+    u.theta_top = have_theta_ ? h_theta_[0] : 0.f;
+    u.block_min = have_theta_ ? std::min(h_theta_[m_ - 1], u.mu) : u.mu;
+    u.n_ritz = have_theta_ ? m_ : 0;
     steps_since_lo_++;
-    const int period = st_.updates < 20 ? 1 : (st_.updates < 200 ? 5 : (st_.updates < 400 ? 20 : 50));   // lambda_max(G) drifts as 1/t
-    if (!have_lo_) refresh_lower_bound(G, 30, theta_top);
-    else if (steps_since_lo_ >= period) refresh_lower_bound(G, 6, theta_top);
+    if (!have_lo_) refresh_lower_bound(u.G, 30, u.theta_top);
+    else if (steps_since_lo_ >= eig_rules::lower_bound_period(st_.updates)) refresh_lower_bound(u.G, 6, u.theta_top);
 
     // A block that has just been (re)started - the first step of a run, a teacher-forced state - has no accuracy of
     // earlier steps to lean on: in the steady state a step inherits Ritz vectors that already met the tolerance and the
     // measured error of A+ sits 5-10x below it (1.5e-5 / 3.6e-5 at eig_tol = 2e-4 on the two full-width workloads),
     // while a cold block stops right AT the tolerance (1-2e-4).  The cold update therefore converges to a quarter of
     // it; it happens once per run.
-    const float tol = cold_ ? 0.25f * tol_ : tol_;
+    u.tol = cold_ ? 0.25f * tol_ : tol_;
     cold_ = false;
-    bool conv = false, cheap_done = false;
-    bool w_emitted = false;          // the last pass's residual kernel has written W (all rows of that pass's block, scales too)
-    int nw = 0, it = 0;
-    int n_ritz = have_theta_ ? m_ : 0;        // leading rows that are Ritz vectors with a known theta
-    std::vector<int> panel_ends;
-    for (; it < max_iter_; it++) {
-        float *Z = Q_;
-        panel_ends.clear();
-        int lock_rows = 0;
-        // The filter is only applied to a block of Ritz vectors (theta known): the amplification of
-        // each row is then predictable and the panels of the orthonormalisation can follow it.
-        if (m_ < live_ && n_ritz > 0) {
-            // ---- Chebyshev filter of degree d damping [a, b] of H = -G ---------------------------
-            const float a = lo_bound_;
-            float b = std::min(block_min, mu);
-            const float minw = 1e-3f * (std::fabs(a) + std::fabs(mu)) + 1e-20f;
-            if (b < a + minw) b = a + minw;
-            const float c0 = 0.5f * (a + b), e0 = 0.5f * (b - a);
-            int d = std::min(12, deg0_ + 2 * it);
-            const float xmax = std::max(1.5f, (std::max(theta_top, mu) - c0) / e0);
-            // keep the top/guard amplification ratio T_d(xmax) below ~1e5: the guard rows survive the
-            // cancellation against the amplified rows with ~1e5 * 6e-8 relative noise
-            const int dcap = (int)(12.2f / std::acosh(xmax));
-            // ---- locking (passes after the first): while theta_top / mu is in the hundreds (the start-up transient) the
-            // cap above holds the filter at degree 2-4, and the pairs just above mu - hundreds of them, a dense spectrum -
-            // gain a factor ~1.6 per pass: ten passes per step.  The pairs at the top converge in the first pass or two
-            // (their amplification is the largest).  Once they have - residuals of the CURRENT matrix, a quarter of the
-            // tolerance - they are locked: not filtered, and projected out of every term of the recurrence that runs on
-            // the rows below them, so that the cap is set by the largest UNLOCKED Ritz value and the degree can rise.
-            // (The locked rows stay in the Rayleigh-Ritz step and in the convergence test.)
-            int n_lock = 0, dcap_a = dcap;
-            if (lock_ && it >= 1 && n_ritz == m_ && nw > 0 && m_ > 32 && dcap < d + 4) {
-                const float emax_l = cscale * (h_theta_[0] - mu);
-                int np = 0;
-                while (np < nw && np < m_ - 16 && cscale * h_res_[np] <= 0.25f * tol * emax_l) np++;
-                if (np >= 8) {
-                    const float xa = std::max(1.5f, (std::max(h_theta_[np], mu) - c0) / e0);
-                    const int cap_a = (int)(12.2f / std::acosh(xa));
-                    if (cap_a >= dcap + 2) { n_lock = np; dcap_a = cap_a; }
-                }
-            }
-            if (n_lock > 0) d = std::min(16, d + 4);
-            d = std::max(2, std::min(d, dcap_a));
-            // A pass that missed the tolerance only narrowly is followed by a degree-1 pass that costs
-            // no product at all: Y = Q H is still there from the Rayleigh-Ritz step, and
-            // (H - c0) Q / e0 = (Y - c0 Q) / e0 already damps everything below the block by the
-            // factor the marginal case needs.
-            // (It gains a factor 0.5-0.9 on the criterion, measured, and what it must reach is the tolerance of the passes
-            // after the first: only a miss within 1.6x of THAT is worth a pass without products.)
-            const bool cheap = it >= 1 && !cheap_done && y_ok_ && last_crit_ <= cheap_margin_ * tol_pass2_ * tol;
-            if (cheap) {
-                cheap_done = true;                                   // once per step: if it is not enough, filter properly
-                d = 1;
-                n_lock = 0;
-                axpby_inplace(Y_, Q_, 1.0f / e0, -c0 / e0, (size_t)m_ * F_, s_);
-                Z = Y_;
-                y_ok_ = false;
-                st_.cheap_passes++;
-            } else if (n_lock > 0) {
-                // the recurrence on the rows below the locked ones, every term cleaned of the locked span (its top
-                // components would otherwise grow by ~2 x_top per product against ~2 x_j for the rows' own); no carried
-                // planes here: the projection changes a term after its product's reduction has split it
-                const int na = m_ - n_lock;
-                const size_t off = (size_t)n_lock * F_;
-                y_ok_ = false;
-                const float *prev = Q_;
-                float *cur = pick({Q_, Y_});
-                chain_planes_of_ = nullptr;
-                chain_next_ = false;
-                product(Q_ + off, na, G, -1.0f / e0, cur + off, Q_ + off, -c0 / e0, nullptr, 0.f, true);
-                project_out(cur + off, na, Q_, n_lock);
-                for (int k = 2; k <= d; k++) {
-                    float *nxt = pick({Q_, prev, cur});
-                    product(cur + off, na, G, -2.0f / e0, nxt + off, cur + off, -2.0f * c0 / e0, prev + off, -1.0f, true);
-                    project_out(nxt + off, na, Q_, n_lock);
-                    prev = cur; cur = nxt;
-                }
-                DLCO_HIP(hipMemcpyAsync(cur, Q_, off * sizeof(float), hipMemcpyDeviceToDevice, s_));
-                Z = cur;
-                st_.locked_passes++;
-                st_.locked_rows += n_lock;
-            } else {
-                const float *prev = Q_;
-                float *cur = pick({Q_, Y_});
-                chain_planes_of_ = nullptr;
-                chain_next_ = d >= 2;                            // the result is the X of the next product: emit its planes
-                bool first_done = false;
-                if (it == 0 && ru_ok && n_ritz == m_) {
-                    // (H - c0) Q / e0 = (beta / e0) Y - (alpha / e0) C_w X_a - (c0 / e0) Q, H = -G
-                    coeff_.alloc(rank_coeff_bytes(cap_ < 160 ? cap_ : 160, ru_.kmax));
-                    if (prof_) prof_->begin(PROF_RANK_UPDATE);
-                    first_done = rank_first_term(Y_, Q_, F_, m_, F_, ru_.beta / e0, -c0 / e0, -ru_.alpha / e0, cur, ru_.proj, ru_.ldp,
-                                                 ru_nw, wscale_.p, ru_.slot, ru_.w, ru_.k_dev, ru_.kmax, ru_.planes, coeff_.p,
-                                                 chain_next_ ? plane_hi_.p : nullptr, plane_lo_.p, s_, ru_.coeff_ready, ru_.planes_mode);
-                    if (prof_) prof_->end(PROF_RANK_UPDATE);
-                    if (first_done) {
-                        st_.rank_update_passes++;
-                        chain_planes_of_ = chain_next_ ? cur : nullptr;
-                        chain_rows_ = m_;
-                        if (ru_check_) {
-                            float *ref = pick({Q_, Y_, cur});
-                            const float *keep = chain_planes_of_;
-                            const bool keep_next = chain_next_;
-                            chain_next_ = false; chain_planes_of_ = nullptr;
-                            std::vector<char> ph(bf16x2_plane_bytes(m_, F_)), pl(ph.size());   // the check must not disturb the planes
-                            DLCO_HIP(hipMemcpyAsync(ph.data(), plane_hi_.p, ph.size(), hipMemcpyDeviceToHost, s_));
-                            DLCO_HIP(hipMemcpyAsync(pl.data(), plane_lo_.p, pl.size(), hipMemcpyDeviceToHost, s_));
-                            product(Q_, m_, G, -1.0f / e0, ref, Q_, -c0 / e0, nullptr, 0.f, true);
-                            std::vector<float> a((size_t)m_ * F_), b(a.size());
-                            DLCO_HIP(hipMemcpyAsync(a.data(), cur, a.size() * sizeof(float), hipMemcpyDeviceToHost, s_));
-                            DLCO_HIP(hipMemcpyAsync(b.data(), ref, b.size() * sizeof(float), hipMemcpyDeviceToHost, s_));
-                            DLCO_HIP(hipMemcpyAsync(plane_hi_.p, ph.data(), ph.size(), hipMemcpyHostToDevice, s_));
-                            DLCO_HIP(hipMemcpyAsync(plane_lo_.p, pl.data(), pl.size(), hipMemcpyHostToDevice, s_));
-                            DLCO_HIP(hipStreamSynchronize(s_));
-                            double dmax = 0.0, rmax = 0.0;
-                            for (size_t e = 0; e < a.size(); e++) { dmax = std::max(dmax, (double)std::fabs(a[e] - b[e])); rmax = std::max(rmax, (double)std::fabs(b[e])); }
-                            st_.rank_update_check = std::max(st_.rank_update_check, rmax > 0.0 ? dmax / rmax : 0.0);
-                            st_.product_rows -= m_;
-                            chain_next_ = keep_next; chain_planes_of_ = keep;
-                        }
-                    }
-                }
-                if (!first_done) product(Q_, m_, G, -1.0f / e0, cur, Q_, -c0 / e0, nullptr, 0.f, true);
-                for (int k = 2; k <= d; k++) {
-                    float *nxt = pick({prev, cur});
-                    chain_next_ = k < d;
-                    product(cur, m_, G, -2.0f / e0, nxt, cur, -2.0f * c0 / e0, prev, -1.0f, true);
-                    prev = cur; cur = nxt;
-                }
-                chain_next_ = false;
-                chain_planes_of_ = nullptr;
-                Z = cur;
-            }
-            last_deg_ = d;
-            // panels: at most 128 rows, predicted amplification T_d(x_j) within panel_amp_ inside a
-            // panel.  A Ritz row carries the directions above it only at the level of its own
-            // residual, so after the filter it is at worst (residual level x amplification ratio)
-            // parallel to them: CholQR2 resolves that as long as the product stays below ~1e2.
-            int start = n_lock;
-            double amp0 = 0.0;
-            if (n_lock > 0) panel_ends.push_back(n_lock);
-            lock_rows = n_lock;
-            for (int j = n_lock; j < n_ritz; j++) {
-                const double x = std::max(1.0, (double)(h_theta_[j] - c0) / e0);
-                const double amp = std::cosh((double)d * std::acosh(x));
-                if (j == start) amp0 = amp;
-                else if (j - start >= CHOL_INV_MAX_N || amp0 > panel_amp_ * amp) { panel_ends.push_back(j); start = j; amp0 = amp; }
-            }
-            if (n_ritz < m_) panel_ends.push_back(n_ritz);
+}
+
+// The degree-1 pass: (H - c0) Q / e0 = (Y - c0 Q) / e0 from the Y = Q H the last Rayleigh-Ritz step left, no product
+float *EigTracker::filter_cheap(const UpdateState &u)
+{
+    const float c0 = u.plan.c0, e0 = u.plan.e0;
+    axpby_inplace(Y_, Q_, 1.0f / e0, -c0 / e0, (size_t)m_ * F_, s_);
+    y_ok_ = false;
+    st_.cheap_passes++;
+    return Y_;
+}
+
+// the recurrence on the rows below the locked ones, every term cleaned of the locked span (its top
+// components would otherwise grow by ~2 x_top per product against ~2 x_j for the rows' own); no carried
+// planes here: the projection changes a term after its product's reduction has split it
+float *EigTracker::filter_locked(const UpdateState &u)
+{
+    const float c0 = u.plan.c0, e0 = u.plan.e0;
+    const int n_lock = u.plan.n_lock, na = m_ - n_lock;
+    const size_t off = (size_t)n_lock * F_;
+    y_ok_ = false;
+    const float *prev = Q_;
+    float *cur = pick({Q_, Y_});
+    product(Q_ + off, na, u.G, -1.0f / e0, cur + off, Q_ + off, -c0 / e0, nullptr, 0.f, true);
+    project_out(cur + off, na, Q_, n_lock);
+    for (int k = 2; k <= u.plan.d; k++) {
+        float *nxt = pick({Q_, prev, cur});
+        product(cur + off, na, u.G, -2.0f / e0, nxt + off, cur + off, -2.0f * c0 / e0, prev + off, -1.0f, true);
+        project_out(nxt + off, na, Q_, n_lock);
+        prev = cur; cur = nxt;
+    }
+    DLCO_HIP(hipMemcpyAsync(cur, Q_, off * sizeof(float), hipMemcpyDeviceToDevice, s_));
+    st_.locked_passes++;
+    st_.locked_rows += n_lock;
+    return cur;
+}
+
+// The three-term recurrence on the whole block; the first term comes from the step's rank update where the caller offered one
+float *EigTracker::filter_plain(const UpdateState &u)
+{
+    const float c0 = u.plan.c0, e0 = u.plan.e0;
+    const int d = u.plan.d;
+    const float *prev = Q_;
+    float *cur = pick({Q_, Y_});
+    PlaneChain chain;
+    chain.next = d >= 2;                                 // the result is the X of the next product: emit its planes
+    bool first_done = false;
+    if (u.it == 0 && u.ru_ok && u.n_ritz == m_) {
+        // (H - c0) Q / e0 = (beta / e0) Y - (alpha / e0) C_w X_a - (c0 / e0) Q, H = -G
+        coeff_.alloc(rank_coeff_bytes(cap_ < 160 ? cap_ : 160, ru_.kmax));
+        if (prof_) prof_->begin(PROF_RANK_UPDATE);
+        first_done = rank_first_term(Y_, Q_, F_, m_, F_, ru_.beta / e0, -c0 / e0, -ru_.alpha / e0, cur, ru_.proj, ru_.ldp,
+                                     u.ru_nw, wscale_.p, ru_.slot, ru_.w, ru_.k_dev, ru_.kmax, ru_.planes, coeff_.p,
+                                     chain.next ? plane_hi_.p : nullptr, plane_lo_.p, s_, ru_.coeff_ready, ru_.planes_mode);
+        if (prof_) prof_->end(PROF_RANK_UPDATE);
+        if (first_done) {
+            st_.rank_update_passes++;
+            chain.planes_of = chain.next ? cur : nullptr;
+            chain.rows = m_;
+            if (ru_check_) check_first_term(u, cur);
         }
-        for (int j = n_ritz + 64; j < m_; j += 64) panel_ends.push_back(j);   // rows without a Ritz value: panels of 64
-        panel_ends.push_back(m_);
-        // ---- orthonormalise, Rayleigh-Ritz -------------------------------------------------------
-        float *Qo = Z;
-        orthonormalize(Z, m_, pick({Z}), panel_ends, lock_rows);     // in place
-        float *Yb = pick({Qo});
-        product(Qo, m_, G, -1.0f, Yb, nullptr, 0.f, nullptr, 0.f, false);     // Yb = Qo * H, exact fp32
-        gram(Yb, Qo, m_, Tm_.p);
-        if (prof_) prof_->begin(PROF_JACOBI);
-        // Guard directions only have to span: pairs of two columns below the Ritz value of the guard at a
-        // quarter of the guard depth (known from the last pass; the leading guards above it still count,
-        // they decide guards_ok) are rotated but do not prolong the sweeps.  What this may leave unfinished
-        // shows up in the residuals below, which decide convergence.
-        float lam_cut = -3.0e38f;
-        if (have_theta_ && n_ritz == m_) {
-            int nwp = 0;
-            while (nwp < m_ && h_theta_[nwp] > mu) nwp++;
-            const int ig = nwp + std::max(2, guard_ / 4);
-            if (ig < m_) lam_cut = h_theta_[ig];
-        }
-        float *Qn = pick({Qo, Yb});
-        float *Yn = pick({Qo, Yb, Qn});
-        w_emitted = false;
-        const size_t blk = (size_t)2 * (cap_ + 8) + 1;               // evals | res | sweeps in one copy
-        // (second attempt: only after the multi-workgroup Jacobi gave up at its grid barrier - T, Qo and Yb are untouched
-        // by a failed attempt, the m x m problem is then solved again by the single-workgroup kernel)
-        for (int attempt = 0;; attempt++) {
+    }
+    if (!first_done) product(Q_, m_, u.G, -1.0f / e0, cur, Q_, -c0 / e0, nullptr, 0.f, true, &chain);
+    for (int k = 2; k <= d; k++) {
+        float *nxt = pick({prev, cur});
+        chain.next = k < d;
+        product(cur, m_, u.G, -2.0f / e0, nxt, cur, -2.0f * c0 / e0, prev, -1.0f, true, &chain);
+        prev = cur; cur = nxt;
+    }
+    return cur;
+}
+
+// DLCO_RANK_UPDATE_CHECK (developer aid): the shortcut's first term `cur` against the product it replaces
+void EigTracker::check_first_term(const UpdateState &u, const float *cur)
+{
+    const float c0 = u.plan.c0, e0 = u.plan.e0;
+    float *ref = pick({Q_, Y_, cur});
+    std::vector<char> ph(bf16x2_plane_bytes(m_, F_)), pl(ph.size());   // the check must not disturb the planes
+    DLCO_HIP(hipMemcpyAsync(ph.data(), plane_hi_.p, ph.size(), hipMemcpyDeviceToHost, s_));
+    DLCO_HIP(hipMemcpyAsync(pl.data(), plane_lo_.p, pl.size(), hipMemcpyDeviceToHost, s_));
+    product(Q_, m_, u.G, -1.0f / e0, ref, Q_, -c0 / e0, nullptr, 0.f, true);
+    std::vector<float> a((size_t)m_ * F_), b(a.size());
+    DLCO_HIP(hipMemcpyAsync(a.data(), cur, a.size() * sizeof(float), hipMemcpyDeviceToHost, s_));
+    DLCO_HIP(hipMemcpyAsync(b.data(), ref, b.size() * sizeof(float), hipMemcpyDeviceToHost, s_));
+    DLCO_HIP(hipMemcpyAsync(plane_hi_.p, ph.data(), ph.size(), hipMemcpyHostToDevice, s_));
+    DLCO_HIP(hipMemcpyAsync(plane_lo_.p, pl.data(), pl.size(), hipMemcpyHostToDevice, s_));
+    DLCO_HIP(hipStreamSynchronize(s_));
+    double dmax = 0.0, rmax = 0.0;
+    for (size_t e = 0; e < a.size(); e++) { dmax = std::max(dmax, (double)std::fabs(a[e] - b[e])); rmax = std::max(rmax, (double)std::fabs(b[e])); }
+    st_.rank_update_check = std::max(st_.rank_update_check, rmax > 0.0 ? dmax / rmax : 0.0);
+    st_.product_rows -= m_;
+}
+
+// Rayleigh-Ritz on the orthonormal rows Qo: Q_ and Y_ = Q_ H become the Ritz vectors and their products, the Ritz
+// values and residual norms come back into h_theta_ / h_res_ (one polled read-back per pass)
+void EigTracker::rayleigh_ritz(UpdateState &u, float *Qo)
+{
+    float *Yb = pick({Qo});
+    product(Qo, m_, u.G, -1.0f, Yb, nullptr, 0.f, nullptr, 0.f, false);     // Yb = Qo * H, exact fp32
+    gram_rect(Yb, m_, Qo, m_, Tm_.p);
+    if (prof_) prof_->begin(PROF_JACOBI);
+    const float lam_cut = eig_rules::jacobi_lam_cut(block_of(u), have_theta_ && u.n_ritz == m_);
+    float *Qn = pick({Qo, Yb});
+    float *Yn = pick({Qo, Yb, Qn});
+    u.w_emitted = false;
+    const size_t blk = (size_t)2 * (cap_ + 8) + 1;               // evals | res | sweeps in one copy
+    // (second attempt: only after the multi-workgroup Jacobi gave up at its grid barrier - T, Qo and Yb are untouched
+    // by a failed attempt, the m x m problem is then solved again by the single-workgroup kernel)
+    for (int attempt = 0;; attempt++) {
         jacobi_eigh(Tm_.p, cap_, m_, evals_.p, Vm_.p, cap_, jwork_.p, sweeps_dev_, s_, lam_cut, attempt > 0);
         if (prof_) prof_->end(PROF_JACOBI);
         rotate(Vm_.p, cap_, m_, m_, Qo, Qn, Yb, Yn);
@@ -606,9 +579,9 @@ int EigTracker::update(const float *G, float mu, float cscale, float *W, double 
         // (the kernel also writes this pass's rows of W, guard rows and scales included: if the pass is the update's last,
         // W is already where it belongs)
         ResidualEmit em;
-        em.W = W; em.ldw = F_; em.mu = mu; em.cscale = cscale; em.wscale = wscale_.p; em.guards = emit_guards_;
+        em.W = u.W; em.ldw = F_; em.mu = u.mu; em.cscale = u.cscale; em.wscale = wscale_.p; em.guards = emit_guards_;
         residual_norms_publish(Q_, Y_, F_, evals_.p, m_, F_, res_.p, reinterpret_cast<unsigned *>(sweeps_dev_ + 4), ritz_block_.p, pin_,
-                               (int)blk, flag, seq, s_, extra_dev_, extra_host, &em, &w_emitted);
+                               (int)blk, flag, seq, s_, extra_dev_, extra_host, &em, &u.w_emitted);
         const auto t0 = std::chrono::steady_clock::now();
         bool seen = false;
         for (long spins = 0;; spins++) {
@@ -626,136 +599,76 @@ int EigTracker::update(const float *G, float mu, float cscale, float *W, double 
         st_.jacobi_barrier_timeouts++;
         DLCO_CHECK(attempt == 0, -3, "eig tracker: the Jacobi kernel reported a failure twice (grid barrier of jacobi_mw_kernel, then the single-workgroup kernel)");
         if (prof_) prof_->begin(PROF_JACOBI);
-        }
-        std::memcpy(h_theta_.data(), pin_, (size_t)m_ * sizeof(float));
-        std::memcpy(h_res_.data(), pin_ + (cap_ + 8), (size_t)m_ * sizeof(float));
-        have_theta_ = true;
-        {
-            const int before = m_;
-            theta_dev_valid_ = (drop_dead_rows() == before);    // a compaction leaves evals_ on the device stale
-        }
-        theta_top = h_theta_[0];
-        block_min = std::min(h_theta_[m_ - 1], mu);
-
-        n_ritz = m_;
-        nw = 0;
-        while (nw < m_ && h_theta_[nw] > mu) nw++;
-        // What has to be small is the error of A = c * (G - mu)_+, not every Ritz pair by itself.  The
-        // Ritz pairs of the block are exact eigenpairs of G + E with E = -sum_i (r_i q_i^T + q_i r_i^T),
-        // r_i orthogonal to the block, and the derivative of the matrix function (x - mu)_+ damps the
-        // component of E that couples a pair at theta_i > mu with a direction at lambda < mu by the
-        // divided difference (theta_i - mu) / (theta_i - lambda) <= (theta_i - mu) / (theta_i - b), b
-        // the top of the spectrum outside the converged part of the block (taken at the middle guard):
-        // a pair just above the threshold carries almost no weight in A and its residual counts with
-        // that weight.  Pairs well above mu keep the weight 1 of the plain residual test.
-        float crit = 0.f;
-        const float bsep = nw < m_ ? std::min(mu, h_theta_[nw + (m_ - nw) / 2]) : mu;
-        for (int i = 0; i < nw; i++) {
-            float wgt = 1.f;
-            const float den = h_theta_[i] - bsep;
-            if (den > 0.f) wgt = std::min(1.f, (h_theta_[i] - mu + h_res_[i]) / den);
-            crit = std::max(crit, cscale * h_res_[i] * wgt);
-        }
-        const float emax = nw > 0 ? cscale * (h_theta_[0] - mu) : 0.f;
-        last_crit_ = emax > 0.f ? crit / emax : 0.f;
-        // the leading guards must be resolved too, or an eigenvalue just above mu can hide in them: each
-        // needs theta + |r| < mu (no eigenvalue of that pair's interval reaches mu), or an interval that
-        // reaches above mu by less than the tolerance (what could hide there weighs less than that in A),
-        // or a small residual
-        bool guards_ok = true;
-        const int ng = std::min(m_, nw + std::max(2, guard_ / 4));
-        const float gtol = tol * std::max(emax, cscale * 1e-3f * std::fabs(mu));
-        for (int i = nw; i < ng; i++) {
-            const float excess = h_theta_[i] + h_res_[i] - mu;
-            const bool below = excess < 0.f || cscale * excess <= gtol;
-            const bool small = cscale * h_res_[i] <= gtol;
-            guards_ok = guards_ok && (below || small);
-        }
-        if (m_ >= live_) conv = true;                                // dense: Rayleigh-Ritz is exact
-        else if (nw == 0) conv = guards_ok || it >= 6;
-        // A step that converges in its first pass inherits Ritz vectors that already met the tolerance, and the measured
-        // error of A+ then sits 3-10x below it; one that needed more passes (start-up transient, a growing block) has
-        // nothing to lean on and stops right at the tolerance (free runs against ssyevr step by step: up to 1.03e-4 of
-        // the 1e-4 gate at eig_tol = 2e-4).  Passes after the first therefore converge to half of it.
-        // (And a first pass that stops right AT the tolerance was measured at 0.46 of it in A+ - 9.2e-5 against the 1e-4 gate, in a
-        // small free run; at full width the ratio is 0.25-0.29, tools/full_width_crit_vs_error.py - so the first pass is held to
-        // 0.85 of it: worst free-run step 7.4e-5, and the rank ~128 workload pays 1.12 instead of 1.11 passes per step.)
-        else conv = crit <= (it == 0 ? tol_pass1_ * tol : tol_pass2_ * tol) * emax && guards_ok;
-        if (debug_)
-            std::fprintf(stderr, "[eig] upd %ld it %d deg %d lock %d m %d nw %d theta[%.5g .. %.5g] mu %.5g lo %.5g crit/emax %.3g guards_ok %d conv %d\n",
-                         (long)st_.updates, it, last_deg_, lock_rows, m_, nw, h_theta_[0], h_theta_[m_ - 1], mu, lo_bound_, last_crit_,
-                         (int)guards_ok, (int)conv);
-        if (h_theta_[m_ - 1] < lo_bound_) lo_bound_ = h_theta_[m_ - 1] - 0.5f * std::fabs(h_theta_[m_ - 1]) - 1e-12f;
-        // ---- grow the block when the positive eigenspace reaches into the guard ------------------
-        if (m_ < live_ && m_ < cap_ && nw > m_ - std::max(2, guard_ / 2)) {
-            const int add = std::min(cap_ - m_, std::max(guard_, nw / 4));
-            // half of the new rows from the caller's source (rows of the step's batch), the rest random: the directions
-            // that have just risen above mu lie mostly in the span of recent batch rows, and a block that starts there
-            // needs fewer passes than one that starts from noise; the random half keeps the block able to find the rest
-            int got = 0;
-            if (grow_cb_) got = std::max(0, std::min(add / 2, grow_cb_(Q_ + (size_t)m_ * F_, add / 2)));
-            append_random(Q_, m_ + got, add - got);
-            for (int i = m_; i < m_ + add; i++) { h_theta_[i] = block_min; h_res_[i] = 0.f; }
-            m_ += add;
-            conv = false;
-            continue;
-        }
-        // a full block that cannot grow while the positive eigenspace still reaches into its guards
-        // cannot certify the rank: the reference keeps EVERY positive eigen-direction
-        // (src/pj-learn.cpp:480-484), so this is reported, never silently truncated
-        if (m_ < live_ && m_ >= cap_ && nw > m_ - std::max(2, guard_ / 2)) { conv = false; it++; break; }
-        if (conv) { it++; break; }
     }
-    st_.iters += it;
-    // starting degree for the next step: the cheapest one that has been converging in a single
-    // filter + Rayleigh-Ritz pass (each extra pass costs a Jacobi and an orthonormalisation)
-    if (it >= 2) deg0_ = std::min(10, deg0_ + 2);
-    else if (conv && last_crit_ < 0.15f * tol_) deg0_ = std::max(2, deg0_ - 1);
-    if (!conv) st_.nonconverged++;
-    if (converged) *converged = conv;
+    std::memcpy(h_theta_.data(), pin_, (size_t)m_ * sizeof(float));
+    std::memcpy(h_res_.data(), pin_ + (cap_ + 8), (size_t)m_ * sizeof(float));
+    have_theta_ = true;
+    const int before = m_;
+    theta_dev_valid_ = (drop_dead_rows() == before);            // a compaction leaves evals_ on the device stale
+    u.theta_top = h_theta_[0];
+    u.block_min = std::min(h_theta_[m_ - 1], u.mu);
+    u.n_ritz = m_;
+}
 
-    // ---- trim the block, emit W (ascending eigenvalue order, like LAPACK's) ----------------------
-    {
-        // the products pad the block to a multiple of 32 rows: prefer a block that fills its
-        // padding exactly, as long as at least half of the guard vectors stay
-        int keep = nw + guard_;
-        const int r32 = (keep / 32) * 32;
-        if (r32 >= nw + std::max(4, guard_ / 2)) keep = r32;
-        else if (keep <= 96) {
-            // the m x m solvers work on PAIRS of eight-column blocks (kernels_jacobi.hip): 81-96 rows cost eleven block rounds
-            // per sweep, 65-80 rows nine.  A small block - where that chain is half the step - that can drop to a multiple of
-            // 16 rows and keep three quarters of its guards does (the reference's own shape: rank 55 + 32 guards = 87 rows
-            // -> 80; Jacobi 0.117 -> 0.100 ms, 1.005 -> 1.015 passes per step, +3.5 % on ref544).  Not above 96 rows: at rank
-            // ~115 the same rule (152 -> 144 rows, 24 guards) cost more passes than it saved rounds (1.16 -> 1.24 per step).
-            const int r16 = (keep / 16) * 16;
-            if (r16 >= nw + std::max(4, (3 * guard_) / 4)) keep = r16;
-        }
-        m_ = std::max(1, std::min(m_, keep));
-    }
+void EigTracker::judge(UpdateState &u)
+{
+    const eig_rules::Verdict v = eig_rules::judge(block_of(u), u.it);
+    u.nw = v.nw;
+    u.conv = v.conv;
+    last_crit_ = v.crit;
+    if (debug_)
+        std::fprintf(stderr, "[eig] upd %ld it %d deg %d lock %d m %d nw %d theta[%.5g .. %.5g] mu %.5g lo %.5g crit/emax %.3g guards_ok %d conv %d\n",
+                     (long)st_.updates, u.it, last_deg_, u.plan.n_lock, m_, u.nw, h_theta_[0], h_theta_[m_ - 1], u.mu, lo_bound_, last_crit_,
+                     (int)v.guards_ok, (int)u.conv);
+    lo_bound_ = eig_rules::lowered_bound(lo_bound_, h_theta_[m_ - 1]);
+}
+
+// ---- grow the block when the positive eigenspace reaches into the guard ------------------
+void EigTracker::grow(UpdateState &u)
+{
+    const int add = eig_rules::growth_rows(m_, cap_, guard_, u.nw);
+    // half of the new rows from the caller's source (rows of the step's batch), the rest random: the directions
+    // that have just risen above mu lie mostly in the span of recent batch rows, and a block that starts there
+    // needs fewer passes than one that starts from noise; the random half keeps the block able to find the rest
+    int got = 0;
+    if (grow_cb_) got = std::max(0, std::min(add / 2, grow_cb_(Q_ + (size_t)m_ * F_, add / 2)));
+    append_random(Q_, m_ + got, add - got);
+    for (int i = m_; i < m_ + add; i++) { h_theta_[i] = u.block_min; h_res_[i] = 0.f; }
+    m_ += add;
+}
+
+// ---- adapt the next starting degree, trim the block, emit W (ascending eigenvalue order, like LAPACK's) --------
+// returns the trace of the projected A
+double EigTracker::trim_and_emit(UpdateState &u)
+{
+    st_.iters += u.it;
+    deg0_ = eig_rules::next_deg0(deg0_, u.it, u.conv, last_crit_, tol_);
+    if (!u.conv) st_.nonconverged++;
+    m_ = eig_rules::trimmed_rows(m_, u.nw, guard_);
+    const int nw = u.nw;
     double tr = 0.0;
     if (nw > 0) {
-        for (int i = 0; i < nw; i++) tr += (double)(cscale * (h_theta_[i] - mu));
+        for (int i = 0; i < nw; i++) tr += (double)(u.cscale * (h_theta_[i] - u.mu));
         if (theta_dev_valid_) {
             // the Ritz values are still on the device in the order of the rows of Q: scale and reverse there
             const bool ext = emit_guards_ && y_ok_ && m_ > nw;
-            if (!w_emitted) emit_w_rows(W, F_, Q_, F_, evals_.p, nw, mu, cscale, F_, s_, ext ? m_ : 0, ext ? wscale_.p : nullptr);
+            if (!u.w_emitted) emit_w_rows(u.W, F_, Q_, F_, evals_.p, nw, u.mu, u.cscale, F_, s_, ext ? m_ : 0, ext ? wscale_.p : nullptr);
             if (ext) { wext_rows_ = m_; wext_nw_ = nw; }
         } else {
             h_sc_.resize(nw);
             h_sr_.resize(nw);
             for (int j = 0; j < nw; j++) {
                 const int i = nw - 1 - j;
-                h_sc_[j] = std::sqrt(cscale * (h_theta_[i] - mu));
+                h_sc_[j] = std::sqrt(u.cscale * (h_theta_[i] - u.mu));
                 h_sr_[j] = i;
             }
             DLCO_HIP(hipMemcpyAsync(scale_.p, h_sc_.data(), nw * sizeof(float), hipMemcpyHostToDevice, s_));
             DLCO_HIP(hipMemcpyAsync(srcrow_.p, h_sr_.data(), nw * sizeof(int32_t), hipMemcpyHostToDevice, s_));
             DLCO_HIP(hipStreamSynchronize(s_));
-            scale_rows(W, F_, Q_, F_, scale_.p, srcrow_.p, nw, F_, s_);
+            scale_rows(u.W, F_, Q_, F_, scale_.p, srcrow_.p, nw, F_, s_);
         }
     }
-    if (trace) *trace = tr;
-    return nw;
+    return tr;
 }
 
 }  // namespace dlco

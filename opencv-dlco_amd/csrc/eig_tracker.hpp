@@ -9,9 +9,14 @@
 // the block]) followed by one Rayleigh-Ritz step; all tall products are fp32 MFMA GEMMs,
 // the m x m problems run on one workgroup (one-sided Jacobi).  The block grows when the
 // positive eigenspace does; when it reaches F the method is the dense eigensolver.
+//
+// update() is that algorithm stage by stage: lower bound, then per pass plan -> filter -> panels ->
+// orthonormalise -> Rayleigh-Ritz and read-back -> judge -> grow or stop, then trim and emit.  The
+// stages that launch are members here; the decisions between them are the functions of eig_rules.hpp.
 #pragma once
 
 #include "dlco_internal.hpp"
+#include "eig_rules.hpp"
 
 #include <functional>
 #include <initializer_list>
@@ -91,9 +96,22 @@ public:
     float last_crit() const { return last_crit_; }
 
 private:
+    struct UpdateState;              // what one update() carries from stage to stage (eig_tracker.cpp)
+    struct PlaneChain;               // the two-way planes a filter chain hands from one product to the next
+    // the stages of update(), in the order it runs them
+    void open_update(UpdateState &u);
+    eig_rules::Block block_of(const UpdateState &u) const;
+    float *filter_cheap(const UpdateState &u);
+    float *filter_locked(const UpdateState &u);
+    float *filter_plain(const UpdateState &u);
+    void check_first_term(const UpdateState &u, const float *cur);
+    void rayleigh_ritz(UpdateState &u, float *Qo);
+    void judge(UpdateState &u);
+    void grow(UpdateState &u);
+    double trim_and_emit(UpdateState &u);
+
     void product(const float *X, int rows, const float *G, float alpha, float *out, const float *E1, float b1,
-                 const float *E2, float b2, bool approx);
-    void gram(const float *X, const float *Y, int rows, float *T);
+                 const float *E2, float b2, bool approx, PlaneChain *chain = nullptr);
     void gram_rect(const float *X, int xrows, const float *Y, int yrows, float *T);
     void project_out(float *Wp, int np, const float *Q, int kept);
     void rotate(const float *C, long ldc, int k_in, int k_out, const float *X, float *out, const float *X2 = nullptr, float *out2 = nullptr);
@@ -117,9 +135,6 @@ private:
     bool ru_check_ = env_switch("DLCO_RANK_UPDATE_CHECK") != nullptr;
     DevBuf<float> wscale_;
     DevBuf<char> coeff_;
-    const float *chain_planes_of_ = nullptr;   // the matrix whose two-way planes sit in plane_hi_/plane_lo_ (emitted by a reduction)
-    int chain_rows_ = 0;
-    bool chain_next_ = false;        // the product being issued feeds the next one of a filter chain
     bool cold_ = true;               // no update since construction / reset(): the next one converges to tol_ / 4
     hipStream_t s_;
     int m_ = 0;                      // rows currently in the block
@@ -133,11 +148,7 @@ private:
     int deg0_ = 4;                   // filter degree of the first pass of a step (adapted)
     int last_deg_ = 0;               // degree actually used by the last filter (after the amplification cap)
     bool y_ok_ = false;              // Y_ = Q_ * H row for row for the matrix of the current update
-    float cheap_margin_ = 1.6f;         // see update(): how narrow a miss must be for a pass without products
-    bool lock_ = env_switch("DLCO_NO_LOCKING") == nullptr;           // see update(): converged top pairs leave the filter
-    static constexpr float tol_pass1_ = 0.85f;  // see update(): tolerance factor of the first pass ...
-    float tol_pass2_ = 0.5f;            // ... and of the passes after the first
-    static constexpr double panel_amp_ = 1e5;   // largest filter-amplification ratio inside one orthonormalisation panel
+    bool lock_ = env_switch("DLCO_NO_LOCKING") == nullptr;           // see eig_rules::plan_filter(): converged top pairs leave the filter
     bool debug_ = env_switch("DLCO_EIG_DEBUG") != nullptr;
 
     DevBuf<float> buf_[6];           // Ritz vectors, their H-products and temporaries, each cap x F

@@ -320,21 +320,11 @@ void chol_inverse128(const float *M, long ldm, int n, float rel_thresh, float *L
     DLCO_HIP(hipGetLastError());
 }
 
-// Copies n floats into pinned host memory and then raises a sequence number there (system-scope release): the
-// host polls the number instead of paying a stream synchronisation for a read-back of a few hundred bytes.
-__global__ __launch_bounds__(256) void publish_block_kernel(const float *src, float *dst_host, int n, unsigned *flag_host, unsigned seq,
-                                                            const int *extra_dev, int *extra_host)
-{
-    for (int i = threadIdx.x; i < n; i += 256) dst_host[i] = src[i];
-    if (extra_dev && threadIdx.x == 0) *extra_host = *extra_dev;      // one more word the caller wants back (no copy of its own)
-    __threadfence_system();
-    __syncthreads();
-    if (threadIdx.x == 0) __hip_atomic_store(flag_host, seq, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
-}
-
-// residual_kernel and publish_block_kernel in one launch: the workgroup that finishes LAST (a ticket counter, left at zero
-// again) copies the block - which holds the residuals the other workgroups have just written, hence the agent-scope
-// release / acquire pair around the ticket and the agent-scope loads - and raises the sequence number.
+// residual_kernel and the read-back in one launch: the workgroup that finishes LAST (a ticket counter, left at zero
+// again) copies the n floats of the block into pinned host memory - the block holds the residuals the other workgroups
+// have just written, hence the agent-scope release / acquire pair around the ticket and the agent-scope loads - and
+// then raises a sequence number there (system-scope release): the host polls the number instead of paying a stream
+// synchronisation for a read-back of a few hundred bytes.  extra_dev: one more word the caller wants back.
 // em.W != nullptr: the workgroup of row i also writes that row of W - W[nw-1-i] = sqrt(cscale (theta_i - mu)) * x_i for the nw rows
 // with theta > mu (ascending order and scaling of src/pj-learn.cpp:480-487; the arithmetic of emit_w_kernel, bit for bit), the
 // rows behind them unscaled in place when em.guards - and the scale into em.wscale: the row is in flight anyway, and the pass that
@@ -410,13 +400,6 @@ void residual_norms_publish(const float *X, const float *Y, long ld, const float
     if (emitted) *emitted = em.W != nullptr;
     hipLaunchKernelGGL(residual_publish_kernel, dim3(m), dim3(256), 0, s, X, Y, ld, theta, m, F, res, ticket, src, dst_host, n, flag_host,
                        seq, extra_dev, extra_host, em);
-    DLCO_HIP(hipGetLastError());
-}
-
-void publish_block(const float *src, float *dst_host, int n, unsigned *flag_host, unsigned seq, hipStream_t s, const int *extra_dev,
-                   int *extra_host)
-{
-    hipLaunchKernelGGL(publish_block_kernel, dim3(1), dim3(256), 0, s, src, dst_host, n, flag_host, seq, extra_dev, extra_host);
     DLCO_HIP(hipGetLastError());
 }
 

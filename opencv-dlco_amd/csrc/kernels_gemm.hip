@@ -293,7 +293,7 @@ void splitk_reduce_f32(const float *slab, int split, int M, int N, float *C, lon
 void gemm_f32(const GemmArgs &a, hipStream_t s)
 {
     if (a.M <= 0 || a.N <= 0) return;
-    DLCO_CHECK(a.A.p && a.B.p && (a.C || a.raw_slab), -2, "gemm_f32: null operand");
+    DLCO_CHECK(a.A.p && a.B.p && a.C, -2, "gemm_f32: null operand");
     DLCO_CHECK(!(a.upper_only && (a.M != a.N || a.split_k > 1)), -2, "gemm_f32: upper_only needs M==N, split_k==1");
     GemmDev g;
     g.M = a.M; g.N = a.N; g.K = a.K;
@@ -310,14 +310,13 @@ void gemm_f32(const GemmArgs &a, hipStream_t s)
     split = a.K > 0 ? (a.K + chunk - 1) / chunk : 1;
     g.k_chunk = chunk;
     g.slab = nullptr;
-    if (split > 1 || a.raw_slab) {
+    if (split > 1) {
         DLCO_CHECK(a.slab != nullptr, -2, "gemm_f32: split_k > 1 needs a slab workspace");
         g.slab = a.slab;
     }
-    if (a.split_out) *a.split_out = split;
     g.B2 = a.B2; g.C2 = a.C2;
     if (a.B2) {
-        DLCO_CHECK(a.C2 && split == 1 && !a.raw_slab && !a.upper_only, -2, "gemm_f32: a twin product needs C2 and no K split");
+        DLCO_CHECK(a.C2 && split == 1 && !a.upper_only, -2, "gemm_f32: a twin product needs C2 and no K split");
         split = 2;                                                 // grid z = the two products
     }
     // tile choice: the small dimension decides; a launch that would leave most of the 256 CUs
@@ -344,7 +343,7 @@ void gemm_f32(const GemmArgs &a, hipStream_t s)
         launch<2, 2>(g, a.A.kmajor, a.B.kmajor, grid, s);
     }
     DLCO_HIP(hipGetLastError());
-    if (split > 1 && !a.raw_slab && !a.B2)
+    if (split > 1 && !a.B2)
         splitk_reduce_f32(a.slab, split, a.M, a.N, a.C, a.ldc, a.alpha, a.beta, a.E1, a.b1, a.E2, a.b2, s);
 }
 

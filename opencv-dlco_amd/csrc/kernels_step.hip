@@ -209,21 +209,6 @@ __global__ __launch_bounds__(1024) void sum_f64_kernel(const float *x, int n, do
     }
 }
 
-__global__ __launch_bounds__(1024) void trace_kernel(const float *A, int F, long ld, double *out)
-{
-    __shared__ double part[16];
-    double s = 0.0;
-    for (int i = threadIdx.x; i < F; i += blockDim.x) s += (double)A[(long)i * ld + i];
-    s = wave_sum_d(s);
-    if ((threadIdx.x & 63) == 0) part[threadIdx.x >> 6] = s;
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        double t = 0.0;
-        for (int w = 0; w < (int)(blockDim.x >> 6); w++) t += part[w];
-        *out = t;
-    }
-}
-
 __global__ void axpby_kernel(float *y, const float *x, float a, float b, size_t n)
 {
     for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (size_t)gridDim.x * blockDim.x)
@@ -398,12 +383,6 @@ void sum_f32_to_f64_batched(const float *x, int n, long ldx, double *out, int co
 {
     if (count <= 0) return;
     hipLaunchKernelGGL(sum_f64_kernel, dim3(count), dim3(1024), 0, s, x, n, out, ldx);
-    DLCO_HIP(hipGetLastError());
-}
-
-void trace_f64(const float *A, int F, long ld, double *out, hipStream_t s)
-{
-    hipLaunchKernelGGL(trace_kernel, dim3(1), dim3(1024), 0, s, A, F, ld, out);
     DLCO_HIP(hipGetLastError());
 }
 

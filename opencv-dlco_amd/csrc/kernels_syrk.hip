@@ -60,11 +60,6 @@ union SyrkLds {
 // SLAB = false: the whole symmetric matrix (upper tiles computed, mirrored).
 // SLAB = true : only the tile columns [slab_t0, slab_t0 + slab_nt) of the matrix, all tile rows,
 //               no mirror — the rank's column slab of a dual average that is sharded over GPUs.
-// BF16 = true : the products run on the bf16 matrix cores (v_mfma_f32_32x32x16_bf16, 16x the fp32 MFMA
-//               rate) with fp32 accumulation: the operands w_k x_k and x_k are rounded to bf16 when the
-//               fragments are read (BASELINE configs[4], "bf16 MFMA + fp32 accum"); everything else -
-//               gather, weights, dual average, stores - stays fp32.  Opt-in (cfg.grad_bf16), gated by the
-//               FPR@95 band in the tests: not the reference's arithmetic.
 // ---------------------------------------------------------------------------------------------------
 // Eight waves per workgroup.  A single wave per SIMD issues v_mfma_f32_32x32x2_f32 at HALF the pipe's
 // rate (tools/overlap_probe.cpp: 4 workgroup-waves per CU need 292 us for what 8 do in 155 us), so a
@@ -82,7 +77,7 @@ constexpr int NT8 = 512;
 //               (bi, bj) at tile index bi*nt - bi*(bi-1)/2 + (bj - bi) (the layout the symmetric tracker product reads,
 //               kernels_bf16x2.hip): no mirrored store at all - half the bytes written, and 136 MB instead of 268 MB at
 //               F = 8192.  Diagonal tiles are stored whole and exactly symmetric.
-template <bool PAIR, bool SLAB, int BF16, bool PACKED = false, int UNR = 16>
+template <bool PAIR, bool SLAB, bool PACKED = false, int UNR = 16>
 __global__ __launch_bounds__(NT8, 4) void syrk_rda_kernel8(SyrkDev g)
 {
     __shared__ __attribute__((aligned(16))) SyrkLds lds;
@@ -182,29 +177,13 @@ __global__ __launch_bounds__(NT8, 4) void syrk_rda_kernel8(SyrkDev g)
         const int buf = kt & 1;
         if (kt + 1 < nk) load_rows();
         if (kt + 2 < nk) load_ids(kt + 2);
-        if (BF16 == 1) {
-#pragma unroll
-            for (int ks = 0; ks < KB / 16; ks++) {
-                bf16x8 a0, a1, b0;
-#pragma unroll
-                for (int j = 0; j < 8; j++) {
-                    const int k = 16 * ks + 8 * lk + j;
-                    a0[j] = (__bf16)lds.st.A[buf][k][wm * 64 + lr];
-                    a1[j] = (__bf16)lds.st.A[buf][k][wm * 64 + 32 + lr];
-                    b0[j] = (__bf16)lds.st.B[buf][k][wn * 32 + lr];
-                }
-                acc[0] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a0, b0, acc[0], 0, 0, 0);
-                acc[1] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a1, b0, acc[1], 0, 0, 0);
-            }
-        } else {
 #pragma unroll UNR
-            for (int kk = 0; kk < KB / 2; kk++) {
-                const float a0 = lds.st.A[buf][2 * kk + lk][wm * 64 + lr];
-                const float a1 = lds.st.A[buf][2 * kk + lk][wm * 64 + 32 + lr];
-                const float b0 = lds.st.B[buf][2 * kk + lk][wn * 32 + lr];
-                acc[0] = __builtin_amdgcn_mfma_f32_32x32x2f32(a0, b0, acc[0], 0, 0, 0);
-                acc[1] = __builtin_amdgcn_mfma_f32_32x32x2f32(a1, b0, acc[1], 0, 0, 0);
-            }
+        for (int kk = 0; kk < KB / 2; kk++) {
+            const float a0 = lds.st.A[buf][2 * kk + lk][wm * 64 + lr];
+            const float a1 = lds.st.A[buf][2 * kk + lk][wm * 64 + 32 + lr];
+            const float b0 = lds.st.B[buf][2 * kk + lk][wn * 32 + lr];
+            acc[0] = __builtin_amdgcn_mfma_f32_32x32x2f32(a0, b0, acc[0], 0, 0, 0);
+            acc[1] = __builtin_amdgcn_mfma_f32_32x32x2f32(a1, b0, acc[1], 0, 0, 0);
         }
         if (kt + 1 < nk) store_rows(buf ^ 1);
         __syncthreads();
@@ -724,8 +703,8 @@ bool syrk_rda_f32(const float *D, long ldd, const int32_t *ids, const int32_t *i
         return true;
     }
     // prec == 0: the gathering kernel with v_mfma_f32_32x32x2_f32
-#define DLCO_SYRK_LAUNCH(P, S) hipLaunchKernelGGL((syrk_rda_kernel8<P, S, 0>), dim3(ntiles), dim3(NT8), 0, s, g)
-#define DLCO_SYRK_LAUNCH_PK(P) hipLaunchKernelGGL((syrk_rda_kernel8<P, false, 0, true>), dim3(ntiles), dim3(NT8), 0, s, g)
+#define DLCO_SYRK_LAUNCH(P, S) hipLaunchKernelGGL((syrk_rda_kernel8<P, S>), dim3(ntiles), dim3(NT8), 0, s, g)
+#define DLCO_SYRK_LAUNCH_PK(P) hipLaunchKernelGGL((syrk_rda_kernel8<P, false, true>), dim3(ntiles), dim3(NT8), 0, s, g)
     if (packed) { if (ids2) DLCO_SYRK_LAUNCH_PK(true); else DLCO_SYRK_LAUNCH_PK(false); }
     else if (slab) { if (ids2) DLCO_SYRK_LAUNCH(true, true); else DLCO_SYRK_LAUNCH(false, true); }
     else { if (ids2) DLCO_SYRK_LAUNCH(true, false); else DLCO_SYRK_LAUNCH(false, false); }

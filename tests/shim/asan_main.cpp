@@ -3,12 +3,14 @@
 //   * the product's pair indexing and cv::RNG restatement      opencv-dlco_amd/csrc/pair_index.hpp
 //   * the tools' I/O layer (.npy directories, row streams)      opencv-dlco_amd/cli/dlco_io.hpp
 //   * the export wire format                                     opencv-dlco_amd/cli/export_format.hpp
+//   * the eigen tracker's host rules                             opencv-dlco_amd/csrc/eig_rules.hpp
 //   * the CPU oracle (test infrastructure)                       oracle/dlco_ref.c
 // - on small inputs, cross-checking product against oracle on the way.  (host_comm.cpp and the CLIs' main() call HIP and
 // cannot be linked here; their argument handling is covered by tests/test_cli_gpu.py.)  `make -C tests/shim asan` builds and
 // runs it; tests/test_sanitizers.py does that in the CPU suite.  Exit code 0 = no sanitizer report and all checks passed.
 #include "../../opencv-dlco_amd/cli/dlco_io.hpp"
 #include "../../opencv-dlco_amd/cli/export_format.hpp"
+#include "../../opencv-dlco_amd/csrc/eig_rules.hpp"
 #include "../../opencv-dlco_amd/csrc/pair_index.hpp"
 
 extern "C" {
@@ -179,6 +181,35 @@ int main(int argc, char **argv)
         dlco_export::write_index_array(f, sel.data(), nsel, cols);
         dlco_export::write_value_array(f, sel.data(), nsel, cols);
         std::fclose(f);
+    }
+    // ---- the eigen tracker's host rules on blocks of every size up to 200 rows, each in arrays of exactly m floats: a rule
+    // that looks one row too far (the lock scan, the middle guard, the Jacobi cut) is a heap overflow here
+    {
+        namespace er = dlco::eig_rules;
+        uint32_t s = 99u;
+        for (int m = 1; m <= 200; m++)
+            for (int nw = 0; nw <= m; nw += (m < 12 ? 1 : m / 6)) {
+                std::vector<float> theta(m), res(m);
+                for (int i = 0; i < m; i++) {
+                    theta[i] = i < nw ? 1.0f + 40.0f * (float)(nw - i) / (float)nw : 0.9f - 0.5f * (float)(i - nw) / (float)m;
+                    res[i] = i < nw / 2 ? 1e-9f : 0.01f * std::fabs(unif(s));
+                }
+                er::Block b;
+                b.theta = theta.data(); b.res = res.data(); b.m = m; b.live = 4096; b.guard = 32; b.mu = 1.0f; b.cscale = 2.0f; b.tol = 2e-4f;
+                std::vector<int> ends;
+                for (int it = 0; it < 3; it++) {
+                    const er::Verdict v = er::judge(b, it);
+                    CHECK(v.nw == nw && v.crit >= 0.f);
+                    const er::FilterPlan p = er::plan_filter(b, m, nw, it, 4, -50.0f, std::min(theta[m - 1], b.mu), theta[0], true, it == 2, v.crit);
+                    CHECK(p.filtered && p.d >= 1 && p.d <= 16 && p.n_lock >= 0 && p.n_lock <= std::max(0, m - 16));
+                    er::cut_panels(b, m, p, 160, ends);
+                    CHECK(!ends.empty() && ends.back() == m);
+                    er::cut_panels(b, m / 2, p, 160, ends);
+                    CHECK(!ends.empty() && ends.back() == m);
+                }
+                (void)er::jacobi_lam_cut(b, true);
+                CHECK(er::trimmed_rows(m, nw, 32) >= 1 && er::trimmed_rows(m, nw, 32) <= m);
+            }
     }
     std::printf("asan_main: all host checks passed\n");
     return 0;
