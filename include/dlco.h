@@ -430,8 +430,41 @@ int  dlco_desc_pair_sqdists(dlco_desc_ctx *ctx, const uint8_t *patches_host, int
  * dim (may be NULL) = rows of W with a non-zero entry, FPR at 95 % recall, area under the ROC curve */
 int  dlco_desc_pair_stats(dlco_desc_ctx *ctx, const uint8_t *patches_host, int64_t n_patches, const int32_t *pairs_host,
                           int64_t n_pairs, int32_t *dim, float *fpr95, double *auc);
+/* ---- Matching two descriptor tables: for every row of one, its nearest and second-nearest row in the other (the input
+ * of Lowe's ratio test and of a mutual check; the tool `match` applies both).  The calls use the context for its device,
+ * stream and scratch only: neither filters nor a projection have to be set.  Limits: 1 <= r <= 1024, 1 <= nq,
+ * 1 <= nt < 2^31; anything else is DLCO_ERR_INVALID.
+ *   Arithmetic: d(i,j) = max(0, |q_i|^2 + |t_j|^2 - 2 q_i.t_j), formed in double (dot products on the f64 matrix cores,
+ * squared norms summed in double) and rounded to float once.  Products of two floats are exact in double, so the value
+ * is within 2^-24 d + 4 (r + 2) 2^-53 (|q_i|^2 + |t_j|^2) of the exact distance of the float inputs.  Unlike
+ * dlco_desc_pair_sqdists, which subtracts first, a row against an identical row is NOT guaranteed to give exactly 0: the
+ * value is >= 0 and inside that bound.
+ *   Order: candidates are ordered by the pair (returned float distance, train index), smaller distance first, equal
+ * distances by smaller index; idx[i] are the first two of that order, i.e. the top two of row i of the matrix
+ * dlco_desc_cross_sqdists returns.  The order of an entry's accumulation depends on r alone: no result depends on nq,
+ * on where a row sits in its table, on how the work is split, or on the run.
+ *   Inputs are expected to be finite; with NaN or infinity in a table the values are unspecified, every index stays in
+ * [-1, nt) and nothing faults. ---- */
+/* For every row i of query [nq, r]: the two rows of train [nt, r] with the smallest squared L2 distance
+ * d(i,j) = sum_k (query[i][k] - train[j][k])^2.
+ * idx [nq][2] / sqdist [nq][2]: column 0 the nearest, column 1 the second nearest (another j).
+ * nt == 1: idx[i][1] = -1, sqdist[i][1] = +inf.  train is held in device memory whole (an allocation failure is
+ * DLCO_ERR_HIP), the queries go up a chunk at a time. */
+int dlco_desc_match(dlco_desc_ctx *ctx, const float *query_host, int64_t nq, const float *train_host, int64_t nt,
+                    int32_t r, int32_t *idx_host, float *sqdist_host);
+/* the same on tables that already live in HBM (e.g. written by dlco_desc_describe_device), row pitches ldq, ldt >= r and
+ * multiples of 4, tables 16-byte aligned (rows are read in 16-byte pieces: the ceil(r/4)*4 floats at the start of every
+ * row must be readable, the ones at and beyond r are ignored); idx_dev / sqdist_dev are device memory; queued on the
+ * context's stream, synchronised on return */
+int dlco_desc_match_device(dlco_desc_ctx *ctx, const float *query_dev, int64_t ldq, int64_t nq,
+                           const float *train_dev, int64_t ldt, int64_t nt, int32_t r,
+                           int32_t *idx_dev, float *sqdist_dev);
+/* the whole matrix out[nq][nt] of the same distances, for small problems, tests and tools (nq * nt <= 2^28) */
+int dlco_desc_cross_sqdists(dlco_desc_ctx *ctx, const float *query_host, int64_t nq, const float *train_host, int64_t nt,
+                            int32_t r, float *out_host);
 /* HIP-event time of the kernels of the last compute / describe call (transform, pooling, projection); the pair_sqdists /
- * pair_stats calls add their distance kernel */
+ * pair_stats calls add their distance kernel; after a match / cross_sqdists call, the time of its kernels (norms, tile
+ * loop, merge of the slices) */
 double dlco_desc_last_kernel_ms(const dlco_desc_ctx *ctx);
 
 #ifdef __cplusplus

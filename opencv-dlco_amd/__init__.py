@@ -144,6 +144,9 @@ def load():
     L.dlco_desc_describe_device.argtypes = [vp, u8p, i64, vp, i64]
     L.dlco_desc_pair_sqdists.argtypes = [vp, u8p, i64, i32p, i64, f32p, u8p]
     L.dlco_desc_pair_stats.argtypes = [vp, u8p, i64, i32p, i64, C.POINTER(C.c_int32), C.POINTER(C.c_float), C.POINTER(C.c_double)]
+    L.dlco_desc_match.argtypes = [vp, f32p, i64, f32p, i64, C.c_int32, i32p, f32p]
+    L.dlco_desc_match_device.argtypes = [vp, vp, i64, i64, vp, i64, i64, C.c_int32, vp, vp]
+    L.dlco_desc_cross_sqdists.argtypes = [vp, f32p, i64, f32p, i64, C.c_int32, f32p]
     L.dlco_desc_last_kernel_ms.argtypes = [vp]
     L.dlco_desc_last_kernel_ms.restype = C.c_double
     L.dlco_pr_last_error.restype = C.c_char_p
@@ -734,6 +737,30 @@ class DescContext:
         dim, f, a = C.c_int32(), C.c_float(), C.c_double()
         self._ck(self.L.dlco_desc_pair_stats(self.h, _p(p, u8p), p.shape[0], _p(q, i32p), q.shape[0], C.byref(dim), C.byref(f), C.byref(a)))
         return dim.value, f.value, a.value
+
+    # ---- matching two descriptor tables ----
+    def match(self, query, train):
+        """For every row of query [nq, r] the nearest and second-nearest row of train [nt, r]: (idx [nq,2] int32,
+        sqdist [nq,2] float32), ordered by (distance, index); nt == 1 gives -1 / +inf in column 1."""
+        q, t = _f32(query), _f32(train)
+        assert q.ndim == 2 and t.ndim == 2 and q.shape[1] == t.shape[1]
+        idx = np.empty((q.shape[0], 2), np.int32)
+        d = np.empty((q.shape[0], 2), np.float32)
+        self._ck(self.L.dlco_desc_match(self.h, _p(q, f32p), q.shape[0], _p(t, f32p), t.shape[0], q.shape[1], _p(idx, i32p), _p(d, f32p)))
+        return idx, d
+
+    def match_device(self, q_ptr, nq, t_ptr, nt, r, idx_ptr, d_ptr, ldq=None, ldt=None):
+        """match on tables in device memory (row pitches ldq, ldt: multiples of 4, default r); results to device memory."""
+        self._ck(self.L.dlco_desc_match_device(self.h, C.c_void_p(q_ptr), ldq or r, nq, C.c_void_p(t_ptr), ldt or r, nt, r,
+                                               C.c_void_p(idx_ptr), C.c_void_p(d_ptr)))
+
+    def cross_sqdists(self, query, train):
+        """The whole matrix [nq, nt] float32 of the distances match orders (nq * nt <= 2^28)."""
+        q, t = _f32(query), _f32(train)
+        assert q.ndim == 2 and t.ndim == 2 and q.shape[1] == t.shape[1]
+        out = np.empty((q.shape[0], t.shape[0]), np.float32)
+        self._ck(self.L.dlco_desc_cross_sqdists(self.h, _p(q, f32p), q.shape[0], _p(t, f32p), t.shape[0], q.shape[1], _p(out, f32p)))
+        return out
 
     def last_kernel_ms(self):
         return self.L.dlco_desc_last_kernel_ms(self.h)

@@ -213,6 +213,23 @@ struct Writer {
         }
     }
     void write_f32(const char *name, const float *data, size_t rows, size_t cols) { write<float>(name, data, rows, cols); }
+    // a 1-D dataset [n]; n == 0 writes an empty one
+    template <typename T>
+    void write_vec(const char *name, const T *data, size_t n)
+    {
+        if (is_h5(path)) {
+            H5 &L = h5();
+            const unsigned long long dims[1] = {n};
+            const H5::hid_t s = L.H5Screate_simple(1, dims, nullptr);
+            const H5::hid_t d = L.H5Dcreate2(f, name, ElemType<T>::h5t(L), s, 0, 0, 0);
+            if (d < 0) throw std::runtime_error(path + ": cannot create dataset " + name);
+            const int rc = n != 0 ? L.H5Dwrite(d, ElemType<T>::h5t(L), 0, 0, 0, data) : 0;
+            L.H5Dclose(d); L.H5Sclose(s);
+            if (rc < 0) throw std::runtime_error(path + ": write of dataset " + name + " failed");
+        } else {
+            npy_write(path + "/" + name + ".npy", data, ElemType<T>::npy(), sizeof(T), {n});
+        }
+    }
     ~Writer() { if (f >= 0) h5().H5Fclose(f); }
 };
 

@@ -1,0 +1,42 @@
+// match_rules.hpp — the filters of the tool `match` on the library's nearest / second-nearest answer: pure host
+// functions, no device, no I/O (tests/shim/match_rules_shim.cpp runs them on a machine without a GPU).
+#pragma once
+
+#include <cstdint>
+#include <vector>
+
+namespace match_rules {
+
+// Lowe's ratio test on L2 distances, stated on the squared ones: the nearest row is kept iff it is closer than f times
+// the second nearest, d1 < f^2 d2 in double (so d1 == f^2 d2 is dropped, and d1 = d2 = 0 is dropped).  A query without
+// a second neighbour (idx2 == -1, a train table of one row) has nothing to be compared with and is kept.
+inline bool ratio_keep(float d1, float d2, int32_t idx2, float f)
+{
+    if (idx2 == -1) return true;
+    return (double)d1 < (double)f * (double)f * (double)d2;
+}
+
+// The mutual rule: (i, j) is kept iff the nearest query of train row j is i.  back [nt][2] is the library's answer with
+// the tables swapped.
+inline bool cross_keep(int64_t i, int32_t j, const int32_t *back) { return back[2 * (int64_t)j] == (int32_t)i; }
+
+// The filtered list for nearest [nq][2] / sqdist [nq][2]: pairs (query, train) ascending in query and their squared
+// distances.  use_ratio / back (NULL: no mutual check) select the rules; both may be given; an empty list is a valid result.
+// A query whose nearest index is -1 (no usable neighbour) is never a match.
+inline void select(int64_t nq, const int32_t *nearest, const float *sqdist, bool use_ratio, float f, const int32_t *back,
+                   std::vector<int32_t> &pairs, std::vector<float> &dists)
+{
+    pairs.clear();
+    dists.clear();
+    for (int64_t i = 0; i < nq; i++) {
+        const int32_t j = nearest[2 * i];
+        if (j < 0) continue;
+        if (use_ratio && !ratio_keep(sqdist[2 * i], sqdist[2 * i + 1], nearest[2 * i + 1], f)) continue;
+        if (back && !cross_keep(i, j, back)) continue;
+        pairs.push_back((int32_t)i);
+        pairs.push_back(j);
+        dists.push_back(sqdist[2 * i]);
+    }
+}
+
+}  // namespace match_rules

@@ -23,6 +23,11 @@ void desc_pair_diff(const float *desc, long ld, int F, const int32_t *pairs, lon
 void desc_full_dist(const float *desc, long ld, int n_groups, int n_pairs, float *dist, hipStream_t s);
 void desc_project(const float *desc, long desc_ld, int n, const float *W, int r, int F, float *Y, long y_ld, hipStream_t s);
 void desc_pair_sqdist(const float *Y, long ld, int r, const int32_t *pairs, long n_pairs, float *dist, uint8_t *label, hipStream_t s);
+void match_norms(const float *x, long ld, long n, int r, double *norm, hipStream_t s);
+int match_tiles_per_slice(long nq, long nt, int n_cu);
+int match_slices(long nt, int tiles_per_slice);
+void match_top2(const float *query, long ldq, int nq, const float *train, long ldt, int nt, int r, const double *qnorm, const double *tnorm,
+                int tiles_per_slice, int32_t *idx, float *sqdist, void *part, float *out, hipStream_t s);
 }
 
 namespace {
@@ -45,6 +50,11 @@ struct dlco_desc_ctx {
     // the learnt projection W [r, proj_F] (pj-learn's output) and the projected rows of one chunk
     int r = 0, proj_F = 0, proj_dim = 0;                   // proj_dim: rows of W with a non-zero entry (src/misc.cpp:269-277)
     DevBuf<float> W, y_chunk;
+    // matching (dlco_desc_match*): buffers of their own, so that a match call leaves the scratch of the calls above alone
+    int n_cu = 0;
+    DevBuf<float> m_query, m_train, m_sqdist, m_cross;     // uploaded tables (host forms), the result of a chunk, the matrix
+    DevBuf<int32_t> m_idx, m_part;                         // m_part: [slices][nq] partial (d1, j1, d2, j2), 16 bytes each
+    DevBuf<double> m_qnorm, m_tnorm;
     double last_ms = 0.0;
 };
 
@@ -141,6 +151,7 @@ int dlco_desc_create(dlco_desc_ctx **out, float init_sigma, int32_t n_angle_bins
             throw Error(DLCO_ERR_NODEVICE, std::string("device is ") + prop.gcnArchName + ", this build targets gfx950 only");
         c = new dlco_desc_ctx();
         c->device = device; c->sigma = init_sigma; c->norm = norm != 0;
+        c->n_cu = prop.multiProcessorCount;
         DLCO_HIP(hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking));
         // Gaussian taps exactly as cv::getGaussianKernel(ksize, sigma, CV_32F) forms them [OpenCV-src]
         int ks = (int)std::lrint((double)init_sigma * 4.0 * 2.0 + 1.0) | 1;
@@ -513,8 +524,130 @@ int dlco_desc_pair_stats(dlco_desc_ctx *c, const uint8_t *patches_host, int64_t 
     });
 }
 
+// ---- matching: the two nearest rows of train for every row of query (kernels_match.hip) ----------------------------------
+namespace {
+constexpr int64_t kMatchRows = (int64_t)1 << 20;           // queries per launch (the kernels index a launch's queries with an int)
+
+bool match_args_ok(const void *a, const void *b, const void *o1, const void *o2, int64_t nq, int64_t nt, int32_t r)
+{
+    return a && b && o1 && o2 && r >= 1 && r <= 1024 && nq >= 1 && nt >= 1 && nt < ((int64_t)1 << 31);
+}
+
+struct EventPair {
+    hipEvent_t e0 = nullptr, e1 = nullptr;
+    EventPair() { DLCO_HIP(hipEventCreate(&e0)); if (hipEventCreate(&e1) != hipSuccess) { (void)hipEventDestroy(e0); throw Error(DLCO_ERR_HIP, "hipEventCreate failed"); } }
+    ~EventPair() { (void)hipEventDestroy(e0); (void)hipEventDestroy(e1); }
+};
+
+// device tables in, device results out; adds the kernels' time to *ms.  tnorm holds |t_j|^2 already.
+void match_on_device(dlco_desc_ctx *c, const float *q, long ldq, int64_t nq, const float *t, long ldt, int64_t nt, int r, int32_t *idx,
+                     float *sqdist, float *cross, double *ms)
+{
+    EventPair ev;
+    for (int64_t q0 = 0; q0 < nq; q0 += kMatchRows) {
+        const int cnt = (int)std::min(kMatchRows, nq - q0);
+        const int tps = match_tiles_per_slice(cnt, nt, c->n_cu), slices = match_slices(nt, tps);
+        c->m_qnorm.alloc((size_t)cnt);
+        if (!cross && slices > 1) c->m_part.alloc((size_t)slices * cnt * 4);
+        DLCO_HIP(hipEventRecord(ev.e0, c->stream));
+        match_norms(q + q0 * ldq, ldq, cnt, r, c->m_qnorm.p, c->stream);
+        match_top2(q + q0 * ldq, ldq, cnt, t, ldt, (int)nt, r, c->m_qnorm.p, c->m_tnorm.p, tps, idx ? idx + 2 * q0 : nullptr,
+                   sqdist ? sqdist + 2 * q0 : nullptr, c->m_part.p, cross ? cross + q0 * nt : nullptr, c->stream);
+        DLCO_HIP(hipEventRecord(ev.e1, c->stream));
+        sync(c);
+        float one = 0.f;
+        DLCO_HIP(hipEventElapsedTime(&one, ev.e0, ev.e1));
+        *ms += one;
+    }
+}
+
+double train_norms(dlco_desc_ctx *c, const float *t, long ldt, int64_t nt, int r)
+{
+    EventPair ev;
+    c->m_tnorm.alloc((size_t)nt);
+    DLCO_HIP(hipEventRecord(ev.e0, c->stream));
+    match_norms(t, ldt, nt, r, c->m_tnorm.p, c->stream);
+    DLCO_HIP(hipEventRecord(ev.e1, c->stream));
+    sync(c);
+    float ms = 0.f;
+    DLCO_HIP(hipEventElapsedTime(&ms, ev.e0, ev.e1));
+    return ms;
+}
+
+// rows of r floats on the host -> rows of pitch ld (a multiple of 4) in dst
+void upload_rows(dlco_desc_ctx *c, float *dst, long ld, const float *src_host, int64_t n, int r)
+{
+    DLCO_HIP(hipMemcpy2DAsync(dst, (size_t)ld * sizeof(float), src_host, (size_t)r * sizeof(float), (size_t)r * sizeof(float), (size_t)n,
+                              hipMemcpyHostToDevice, c->stream));
+}
+
+// the host forms: train wholly in HBM, the queries a chunk at a time
+void match_host(dlco_desc_ctx *c, const float *query_host, int64_t nq, const float *train_host, int64_t nt, int r, int32_t *idx_host,
+                float *sqdist_host, float *cross_host)
+{
+    DLCO_HIP(hipSetDevice(c->device));
+    const long ld = (r + 3) / 4 * 4;
+    // queries per chunk: 256 MB of rows, and for the matrix 2^28 entries at most
+    const int64_t qchunk = std::max<int64_t>(1, std::min<int64_t>(nq, ((int64_t)1 << 26) / ld));
+    try {
+        c->m_train.alloc((size_t)nt * ld);
+        c->m_query.alloc((size_t)qchunk * ld);
+        if (cross_host) c->m_cross.alloc((size_t)qchunk * nt);
+        else { c->m_idx.alloc((size_t)qchunk * 2); c->m_sqdist.alloc((size_t)qchunk * 2); }
+    } catch (const Error &e) {
+        throw Error(DLCO_ERR_HIP, std::string("dlco_desc_match: the tables do not fit in device memory: ") + e.what());
+    }
+    upload_rows(c, c->m_train.p, ld, train_host, nt, r);
+    double ms = train_norms(c, c->m_train.p, ld, nt, r);
+    for (int64_t q0 = 0; q0 < nq; q0 += qchunk) {
+        const int64_t cnt = std::min(qchunk, nq - q0);
+        upload_rows(c, c->m_query.p, ld, query_host + q0 * r, cnt, r);
+        if (cross_host) {
+            match_on_device(c, c->m_query.p, ld, cnt, c->m_train.p, ld, nt, r, nullptr, nullptr, c->m_cross.p, &ms);
+            DLCO_HIP(hipMemcpyAsync(cross_host + q0 * nt, c->m_cross.p, (size_t)cnt * nt * sizeof(float), hipMemcpyDeviceToHost, c->stream));
+        } else {
+            match_on_device(c, c->m_query.p, ld, cnt, c->m_train.p, ld, nt, r, c->m_idx.p, c->m_sqdist.p, nullptr, &ms);
+            DLCO_HIP(hipMemcpyAsync(idx_host + 2 * q0, c->m_idx.p, (size_t)cnt * 2 * sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
+            DLCO_HIP(hipMemcpyAsync(sqdist_host + 2 * q0, c->m_sqdist.p, (size_t)cnt * 2 * sizeof(float), hipMemcpyDeviceToHost, c->stream));
+        }
+        sync(c);
+    }
+    c->last_ms = ms;
+}
+}  // namespace
+
+int dlco_desc_match(dlco_desc_ctx *c, const float *query_host, int64_t nq, const float *train_host, int64_t nt, int32_t r, int32_t *idx_host,
+                    float *sqdist_host)
+{
+    if (!c || !match_args_ok(query_host, train_host, idx_host, sqdist_host, nq, nt, r)) return DLCO_ERR_INVALID;
+    return guarded(c, [&] { match_host(c, query_host, nq, train_host, nt, r, idx_host, sqdist_host, nullptr); });
+}
+
+int dlco_desc_match_device(dlco_desc_ctx *c, const float *query_dev, int64_t ldq, int64_t nq, const float *train_dev, int64_t ldt, int64_t nt,
+                           int32_t r, int32_t *idx_dev, float *sqdist_dev)
+{
+    if (!c || !match_args_ok(query_dev, train_dev, idx_dev, sqdist_dev, nq, nt, r)) return DLCO_ERR_INVALID;
+    if (ldq < r || ldt < r || ldq % 4 != 0 || ldt % 4 != 0) return DLCO_ERR_INVALID;
+    if (((uintptr_t)query_dev | (uintptr_t)train_dev) % 16 != 0) return DLCO_ERR_INVALID;          // 16-byte rows
+    return guarded(c, [&] {
+        DLCO_HIP(hipSetDevice(c->device));
+        double ms = train_norms(c, train_dev, (long)ldt, nt, r);
+        match_on_device(c, query_dev, (long)ldq, nq, train_dev, (long)ldt, nt, r, idx_dev, sqdist_dev, nullptr, &ms);
+        c->last_ms = ms;
+    });
+}
+
+int dlco_desc_cross_sqdists(dlco_desc_ctx *c, const float *query_host, int64_t nq, const float *train_host, int64_t nt, int32_t r,
+                            float *out_host)
+{
+    if (!c || !match_args_ok(query_host, train_host, out_host, out_host, nq, nt, r)) return DLCO_ERR_INVALID;
+    if (nq > ((int64_t)1 << 28) / nt) return DLCO_ERR_INVALID;
+    return guarded(c, [&] { match_host(c, query_host, nq, train_host, nt, r, nullptr, nullptr, out_host); });
+}
+
 // milliseconds the kernels of the last dlco_desc_compute* / dlco_desc_describe* call took (HIP events): transform and
-// pooling, plus the projection for describe; the pair calls add their distance kernel
+// pooling, plus the projection for describe; the pair calls add their distance kernel; after a match call, its kernels
+// (norms, top two, merge)
 double dlco_desc_last_kernel_ms(const dlco_desc_ctx *c) { return c ? c->last_ms : 0.0; }
 
 }  // extern "C"

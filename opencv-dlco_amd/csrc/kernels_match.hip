@@ -1,0 +1,349 @@
+// kernels_match.hip — nearest and second-nearest row of one descriptor table in another (dlco_desc_match) and the
+// whole matrix of the same distances (dlco_desc_cross_sqdists):
+//
+//   match_norms_kernel    |row|^2 of a table in double, one wave per row: lane l sums the elements l, l + 64, ...
+//                         in order, then a fixed butterfly; the order depends on r alone
+//   match_top2_kernel     d(i,j) = max(0, |q_i|^2 + |t_j|^2 - 2 q_i.t_j) in double with the dot products on
+//                         v_mfma_f64_16x16x4_f64 (fp32 operands widened exactly: the queries when their fragments
+//                         are read, a train tile when it is stored to LDS), rounded to float once; then either the running top two per query
+//                         under the key (float distance, train index), or (STORE) the matrix itself: one tile loop, two
+//                         epilogues, so the matrix and the top two cannot disagree
+//   match_merge_kernel    the top two of a query over the S slices of train, under the same key
+//
+// The key is a total order and the slices hold disjoint train rows, so the result does not depend on the grouping.
+// An entry's accumulation is one chain of MFMAs over k in an order fixed by r: it depends neither on where the query
+// or the train row sits, nor on nq, nt or the slice count.
+//
+// Tables are [n][ld] floats with ld % 4 == 0 and 16-byte aligned: a row is read in 16-byte pieces up to
+// ceil(r / 4) * 4 <= ld, the elements at and beyond r are replaced by zeros.  Every load is unconditional and in
+// bounds (a row or piece beyond the edge reads a valid one and is replaced by zeros), stores are masked.
+#include "dlco_internal.hpp"
+
+namespace dlco {
+
+typedef float f32x4 __attribute__((ext_vector_type(4)));
+typedef int i32x4 __attribute__((ext_vector_type(4)));
+typedef double f64x4 __attribute__((ext_vector_type(4)));
+typedef double f64x2 __attribute__((ext_vector_type(2)));
+
+namespace {
+
+// A wave owns 16 queries (the M of the f64 MFMA) and keeps their A fragments of a whole 128-wide k chunk in registers
+// (one float per lane and k-step: 32 VGPRs, which the compiler widens once: 64); eight waves, two per SIMD, own 128
+// queries and read every staged tile of train: TN rows x 128 k in LDS as doubles (133 KB: one workgroup per CU), fetched
+// to registers one step ahead of its use and widened once, at the LDS store, so that no conversion sits between the MFMAs.  r <= 128 is one chunk per tile (the
+// case of every shipped model); beyond it (MULTI) the accumulators of all TN / 16 column blocks are kept over the
+// chunks of a tile and the A fragments are re-read per chunk: correct, not tuned.
+constexpr int MQ = 128;                // queries per workgroup
+constexpr int TN = 128;                // train rows per staged tile
+constexpr int KC = 128;                // k per staged chunk
+constexpr int MP = KC + 2;             // LDS pitch in doubles: the 16-byte reads of 16 rows fall into 16 different bank groups
+constexpr int MTH = 512;
+constexpr int NSUB = TN / 16;
+
+struct Top2 { float d1; int j1; float d2; int j2; };
+
+// (distance, index) order: smaller distance first, equal distances by smaller index
+__device__ __forceinline__ bool key_less(float da, int ja, float db, int jb) { return da < db || (da == db && ja < jb); }
+
+// top two of the union of two top-two lists of disjoint candidates
+__device__ __forceinline__ Top2 merge2(const Top2 a, const Top2 b)
+{
+    Top2 o;
+    const bool b_first = key_less(b.d1, b.j1, a.d1, a.j1);
+    const float wd = b_first ? b.d1 : a.d1, ld = b_first ? a.d1 : b.d1;        // winner / loser of the two firsts
+    const int wj = b_first ? b.j1 : a.j1, lj = b_first ? a.j1 : b.j1;
+    const float sd = b_first ? b.d2 : a.d2;                                  // the winner's own second
+    const int sj = b_first ? b.j2 : a.j2;
+    const bool l_second = key_less(ld, lj, sd, sj);
+    o.d1 = wd; o.j1 = wj;
+    o.d2 = l_second ? ld : sd;
+    o.j2 = l_second ? lj : sj;
+    return o;
+}
+
+template <bool STORE, bool MULTI>
+__global__ __launch_bounds__(MTH) void match_top2_kernel(const float *__restrict__ query, long ldq, int nq, const float *__restrict__ train, long ldt,
+                                                         int nt, int r, const double *__restrict__ qnorm, const double *__restrict__ tnorm,
+                                                         int tiles_per_slice, int32_t *__restrict__ idx, float *__restrict__ sqdist,
+                                                         i32x4 *__restrict__ part, float *__restrict__ out)
+{
+    __shared__ double Bs[TN * MP];                         // the staged tile, widened to double once, when it is stored
+    __shared__ double Tn[TN];
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int li = lane & 15, lg = lane >> 4;
+    const int q0 = blockIdx.x * MQ + wave * 16;
+    const bool wave_on = q0 < nq;                          // uniform over the wave
+    const int jbeg = (int)((long)blockIdx.y * tiles_per_slice * TN);    // this slice of train: [jbeg, jend), never empty (jbeg < nt)
+    const int jend = (int)min((long)nt, (long)jbeg + (long)tiles_per_slice * TN);
+    const int ntile = (jend - jbeg + TN - 1) / TN;
+    const int nch = MULTI ? (r + KC - 1) / KC : 1;
+    const int nstep = ntile * nch;
+    const int r4 = (r + 3) & ~3;
+
+    // the piece [k, k + 4) of a row with the elements at and beyond r zeroed
+    auto mask_k = [&](f32x4 v, int k, bool row_ok) {
+        f32x4 o;
+#pragma unroll
+        for (int e = 0; e < 4; e++) o[e] = (row_ok && k + e < r) ? v[e] : 0.f;
+        return o;
+    };
+
+    // loader: thread t fetches the 16-byte piece lseg of the train rows lrow + 16 u of a tile, and the first TN
+    // threads the squared norm of one of its rows
+    const int lrow = tid >> 5, lseg = tid & 31;
+    f32x4 rb[NSUB];
+    double rtn;
+    auto gload = [&](int step) {
+        step = min(step, nstep - 1);                       // past the end: the last step again, never used
+        const int tile = step / nch, kc = step - tile * nch;
+        const int k = kc * KC + 4 * lseg;
+        const int kk = k < r4 ? k : 0;
+        const long jt = (long)jbeg + (long)tile * TN;      // nt may be just below 2^31
+#pragma unroll
+        for (int u = 0; u < NSUB; u++) {
+            const long j = jt + lrow + 16 * u;
+            const bool ok = j < jend;
+            const f32x4 v = *reinterpret_cast<const f32x4 *>(train + (ok ? j : (long)jbeg) * ldt + kk);
+            rb[u] = mask_k(v, k, ok);
+        }
+        const long jn = jt + (tid & (TN - 1));
+        rtn = tnorm[jn < jend ? jn : (long)jbeg];
+    };
+    auto lstore = [&]() {
+#pragma unroll
+        for (int u = 0; u < NSUB; u++) {
+            double *dst = &Bs[(lrow + 16 * u) * MP + 4 * lseg];
+            *reinterpret_cast<f64x2 *>(dst) = f64x2{(double)rb[u][0], (double)rb[u][1]};
+            *reinterpret_cast<f64x2 *>(dst + 2) = f64x2{(double)rb[u][2], (double)rb[u][3]};
+        }
+        if (tid < TN) Tn[tid] = rtn;
+    };
+
+    // A fragments of one k chunk: lane (li, lg) holds query q0 + li at k = 16 c + 4 lg + s, s = element of fa[c]
+    const bool q_ok = q0 + li < nq;
+    const float *qrow = query + (long)(q_ok ? q0 + li : 0) * ldq;
+    f32x4 fa[KC / 16];
+    auto aload = [&](int kc) {
+#pragma unroll
+        for (int c = 0; c < KC / 16; c++) {
+            const int k = kc * KC + 16 * c + 4 * lg;
+            const f32x4 v = *reinterpret_cast<const f32x4 *>(qrow + (k < r4 ? k : 0));
+            fa[c] = mask_k(v, k, q_ok);
+        }
+    };
+    if (!MULTI) aload(0);
+
+    // the lane's four result rows: query q0 + lg + 4 rr
+    double qn[4];
+#pragma unroll
+    for (int rr = 0; rr < 4; rr++) {
+        const int row = q0 + lg + 4 * rr;
+        qn[rr] = qnorm[row < nq ? row : 0];
+    }
+    // running (best, second) of the columns == li (mod 16) for each of the four rows; a lane meets its columns in
+    // ascending order, so a strict comparison keeps the smaller index among equal distances
+    const float inf = __builtin_inff();
+    f32x4 bd1 = f32x4{inf, inf, inf, inf}, bd2 = bd1;
+    i32x4 bj1 = i32x4{-1, -1, -1, -1}, bj2 = bj1;
+
+    // one entry of a 16 x 16 result: row q0 + lg + 4 rr against train row jl, whose squared norm is tn
+    auto entry = [&](double dot, int rr, double tn, long jl) {
+        const bool j_ok = jl < jend;
+        const int j = (int)jl;
+        double d = __builtin_fma(-2.0, dot, qn[rr] + tn);
+        d = __builtin_fmax(d, 0.0);
+        const float f = (float)d;
+        if (STORE) {
+            const int row = q0 + lg + 4 * rr;
+            if (j_ok && row < nq) out[(long)row * nt + j] = f;
+        } else {
+            const bool first = j_ok && f < bd1[rr], second = j_ok && f < bd2[rr];
+            bd2[rr] = first ? bd1[rr] : (second ? f : bd2[rr]);
+            bj2[rr] = first ? bj1[rr] : (second ? j : bj2[rr]);
+            bd1[rr] = first ? f : bd1[rr];
+            bj1[rr] = first ? j : bj1[rr];
+        }
+    };
+    // The finished column blocks of the step before: their epilogue (VALU work) is issued between the MFMAs of the
+    // next pair of blocks, one entry per 16-wide k group, so that it runs beside them instead of after them.
+    f64x4 p0 = f64x4{0.0, 0.0, 0.0, 0.0}, p1 = p0;
+    double ptn0 = 0.0, ptn1 = 0.0;
+    long pj = jend;                                        // no block yet: jl >= jend masks every entry
+    auto prev_entry = [&](int e) {
+        if (e < 4) entry(p0[e], e, ptn0, pj);
+        else entry(p1[e - 4], e - 4, ptn1, pj + 16);
+    };
+    // the k chunk in LDS against the A fragments, for the column blocks sub and sub + 1: two independent MFMA chains
+    // over the nc 16-wide k groups that hold a k below r
+    const int nc = MULTI ? KC / 16 : (r + 15) / 16;
+    auto mfma_pair = [&](int sub, f64x4 &a0, f64x4 &a1, bool fused) {
+        const double *b0 = &Bs[(16 * sub + li) * MP + 4 * lg];
+#pragma unroll
+        for (int c = 0; c < KC / 16; c++) {
+            if (c < nc) {
+#pragma unroll
+                for (int h = 0; h < 2; h++) {
+                    const f64x2 f0 = *reinterpret_cast<const f64x2 *>(b0 + 16 * c + 2 * h);
+                    const f64x2 f1 = *reinterpret_cast<const f64x2 *>(b0 + 16 * MP + 16 * c + 2 * h);
+#pragma unroll
+                    for (int s = 0; s < 2; s++) {
+                        a0 = __builtin_amdgcn_mfma_f64_16x16x4f64((double)fa[c][2 * h + s], f0[s], a0, 0, 0, 0);
+                        a1 = __builtin_amdgcn_mfma_f64_16x16x4f64((double)fa[c][2 * h + s], f1[s], a1, 0, 0, 0);
+                    }
+                }
+            }
+            if (fused) prev_entry(c);
+        }
+    };
+    const f64x4 zacc = f64x4{0.0, 0.0, 0.0, 0.0};
+    f64x4 acc[MULTI ? NSUB : 2];
+
+    gload(0);
+    for (int step = 0; step < nstep; step++) {
+        lstore();
+        __syncthreads();
+        gload(step + 1);
+        if (wave_on) {
+            if (MULTI) {
+                const int tile = step / nch, kc = step - tile * nch;
+                aload(kc);
+#pragma unroll
+                for (int sub = 0; sub < NSUB; sub += 2) {
+                    if (kc == 0) { acc[sub] = zacc; acc[sub + 1] = zacc; }
+                    mfma_pair(sub, acc[sub], acc[sub + 1], false);
+                    if (kc == nch - 1) {
+                        const long jl = (long)jbeg + (long)tile * TN + 16 * sub + li;
+#pragma unroll
+                        for (int rr = 0; rr < 4; rr++) {
+                            entry(acc[sub][rr], rr, Tn[16 * sub + li], jl);
+                            entry(acc[sub + 1][rr], rr, Tn[16 * sub + 16 + li], jl + 16);
+                        }
+                    }
+                }
+            } else {
+#pragma unroll 1
+                for (int sub = 0; sub < NSUB; sub += 2) {
+                    acc[0] = zacc; acc[1] = zacc;
+                    mfma_pair(sub, acc[0], acc[1], true);
+                    p0 = acc[0]; p1 = acc[1];
+                    ptn0 = Tn[16 * sub + li]; ptn1 = Tn[16 * sub + 16 + li];
+                    pj = (long)jbeg + (long)step * TN + 16 * sub + li;
+                }
+            }
+        }
+        __syncthreads();
+    }
+    if (!MULTI && wave_on) {
+#pragma unroll
+        for (int e = 0; e < 8; e++) prev_entry(e);         // the last pair of blocks
+    }
+    if (STORE || !wave_on) return;
+    // the 16 lanes of a row hold disjoint columns: butterfly under the key, every lane ends with the row's top two
+#pragma unroll
+    for (int rr = 0; rr < 4; rr++) {
+        Top2 me{bd1[rr], bj1[rr], bd2[rr], bj2[rr]};
+#pragma unroll
+        for (int o = 1; o < 16; o <<= 1) {
+            Top2 other;
+            other.d1 = __shfl_xor(me.d1, o, 64); other.j1 = __shfl_xor(me.j1, o, 64);
+            other.d2 = __shfl_xor(me.d2, o, 64); other.j2 = __shfl_xor(me.j2, o, 64);
+            me = merge2(me, other);
+        }
+        const int row = q0 + lg + 4 * rr;
+        if (li == 0 && row < nq) {
+            if (part) {
+                part[(long)blockIdx.y * nq + row] = i32x4{__float_as_int(me.d1), me.j1, __float_as_int(me.d2), me.j2};
+            } else {
+                idx[2 * (long)row] = me.j1; idx[2 * (long)row + 1] = me.j2;
+                sqdist[2 * (long)row] = me.d1; sqdist[2 * (long)row + 1] = me.d2;
+            }
+        }
+    }
+}
+
+__global__ __launch_bounds__(256) void match_merge_kernel(const i32x4 *__restrict__ part, int slices, int nq, int32_t *__restrict__ idx,
+                                                          float *__restrict__ sqdist)
+{
+    const int row = blockIdx.x * 256 + threadIdx.x;
+    if (row >= nq) return;
+    const i32x4 p0 = part[row];
+    Top2 me{__int_as_float(p0[0]), p0[1], __int_as_float(p0[2]), p0[3]};
+    for (int s = 1; s < slices; s++) {
+        const i32x4 p = part[(long)s * nq + row];
+        me = merge2(me, Top2{__int_as_float(p[0]), p[1], __int_as_float(p[2]), p[3]});
+    }
+    idx[2 * (long)row] = me.j1; idx[2 * (long)row + 1] = me.j2;
+    sqdist[2 * (long)row] = me.d1; sqdist[2 * (long)row + 1] = me.d2;
+}
+
+constexpr int NTH = 256;               // four rows per workgroup, one wave each
+
+__global__ __launch_bounds__(NTH) void match_norms_kernel(const float *__restrict__ x, long ld, long n, int r, double *__restrict__ norm)
+{
+    const long row = (long)blockIdx.x * (NTH / 64) + (threadIdx.x >> 6);
+    const int lane = threadIdx.x & 63;
+    if (row >= n) return;
+    const float *p = x + row * ld;
+    double s = 0.0;
+    for (int k = lane; k < r; k += 64) s = __builtin_fma((double)p[k], (double)p[k], s);
+#pragma unroll
+    for (int o = 32; o >= 1; o >>= 1) s += __shfl_xor(s, o, 64);
+    if (lane == 0) norm[row] = s;
+}
+
+}  // namespace
+
+void match_norms(const float *x, long ld, long n, int r, double *norm, hipStream_t s)
+{
+    if (n <= 0) return;
+    const long per = NTH / 64;
+    hipLaunchKernelGGL(match_norms_kernel, dim3((unsigned)((n + per - 1) / per)), dim3(NTH), 0, s, x, ld, n, r, norm);
+    DLCO_HIP(hipGetLastError());
+}
+
+// Slices of train for nq queries, whole tiles per slice.  One workgroup runs per CU.  First enough slices that every
+// CU has one (2048 x 2048: 16 query blocks x 16 one-tile slices took 41 us, x 4 four-tile slices 70).  Beyond that a
+// launch is a number of rounds of n_cu workgroups and the last round may be nearly empty (782 query blocks on 256 CUs:
+// 3.05 rounds take the time of 4; 100 000 x 100 000 at r = 128 went from 63.8 to 48.5 ms with three slices, 9.2 rounds):
+// enough slices for eight rounds keep that loss near a tenth, as long as a slice keeps four tiles (a workgroup's start -
+// its A fragments, the first tile's latency - is paid per slice).  Returns the tiles per slice; the slice count is
+// ceil(tiles / that).
+int match_tiles_per_slice(long nq, long nt, int n_cu)
+{
+    const long qblocks = (nq + MQ - 1) / MQ, tiles = (nt + TN - 1) / TN;
+    const long fill = std::min(tiles, (n_cu + qblocks - 1) / qblocks);
+    const long rounds = std::min(tiles / 4, (8L * n_cu + qblocks - 1) / qblocks);
+    const long want = std::max(1L, std::max(fill, rounds));
+    return (int)((tiles + want - 1) / want);
+}
+int match_slices(long nt, int tiles_per_slice)
+{
+    const long tiles = (nt + TN - 1) / TN;
+    return (int)((tiles + tiles_per_slice - 1) / tiles_per_slice);
+}
+
+// query [nq][ldq], train [nt][ldt], norms from match_norms.  out != nullptr: the matrix out[nq][nt]; else idx / sqdist
+// [nq][2], through part [slices][nq] (16 bytes each) when the tiles_per_slice leaves more than one slice.
+void match_top2(const float *query, long ldq, int nq, const float *train, long ldt, int nt, int r, const double *qnorm, const double *tnorm,
+                int tiles_per_slice, int32_t *idx, float *sqdist, void *part, float *out, hipStream_t s)
+{
+    if (nq <= 0 || nt <= 0) return;
+    const int slices = match_slices(nt, tiles_per_slice);
+    const dim3 grid((unsigned)((nq + MQ - 1) / MQ), (unsigned)slices);
+    i32x4 *pp = (!out && slices > 1) ? static_cast<i32x4 *>(part) : nullptr;
+    const bool multi = r > KC;
+#define DLCO_MATCH_LAUNCH(ST, MU)                                                                                                     \
+    hipLaunchKernelGGL((match_top2_kernel<ST, MU>), grid, dim3(MTH), 0, s, query, ldq, nq, train, ldt, nt, r, qnorm, tnorm, tiles_per_slice, \
+                       idx, sqdist, pp, out)
+    if (out) { if (multi) DLCO_MATCH_LAUNCH(true, true); else DLCO_MATCH_LAUNCH(true, false); }
+    else     { if (multi) DLCO_MATCH_LAUNCH(false, true); else DLCO_MATCH_LAUNCH(false, false); }
+#undef DLCO_MATCH_LAUNCH
+    DLCO_HIP(hipGetLastError());
+    if (pp) {
+        hipLaunchKernelGGL(match_merge_kernel, dim3((unsigned)((nq + 255) / 256)), dim3(256), 0, s, pp, slices, nq, idx, sqdist);
+        DLCO_HIP(hipGetLastError());
+    }
+}
+
+}  // namespace dlco

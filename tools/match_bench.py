@@ -1,0 +1,61 @@
+"""Times dlco_desc_match_device on tables resident in HBM: HIP events through last_kernel_ms (norms, tile loop and the merge of
+the slices), one process, one warm-up call per shape, two timed repeats.  Prints one line per shape with milliseconds per
+call, the floor 2 nq nt r / 78.6 TFLOP/s (the f64 MFMA peak DESIGN prices desc_pool_kernel against) and their ratio, and, as
+the thing a user would write without this call, the time of a chunked float64 torch Q @ T.T + topk(2) on the same tables
+(torch events, same warm-up and repeats)."""
+import importlib, os, sys
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+import torch
+dlco = importlib.import_module("opencv-dlco_amd")
+
+PEAK = 78.6e12
+SHAPES = [(2048, 2048, 64), (8192, 8192, 64), (8192, 8192, 128), (100000, 100000, 128)]
+if len(sys.argv) > 1:
+    SHAPES = [tuple(int(v) for v in a.split(",")) for a in sys.argv[1:]]
+
+
+def torch_route(Q, T, chunk=8192):
+    """Nearest two by a float64 product, a chunk of queries at a time so that the nq x nt matrix never exists whole."""
+    T64 = T.double()
+    tn = (T64 * T64).sum(1)
+    idx, d = [], []
+    for i0 in range(0, Q.shape[0], chunk):
+        q = Q[i0:i0 + chunk].double()
+        D = ((q * q).sum(1)[:, None] + tn[None, :] - 2.0 * (q @ T64.T)).clamp_(min=0)
+        v, j = torch.topk(D, min(2, T.shape[0]), dim=1, largest=False)
+        idx.append(j)
+        d.append(v.float())
+    return torch.cat(idx), torch.cat(d)
+
+
+ctx = dlco.DescContext()
+gen = torch.Generator(device="cuda:0").manual_seed(0)
+for nq, nt, r in SHAPES:
+    T = torch.empty((nt, r), dtype=torch.float32, device="cuda:0").normal_(0, 0.25, generator=gen)
+    Q = torch.empty((nq, r), dtype=torch.float32, device="cuda:0").normal_(0, 0.25, generator=gen)
+    Q[: nq // 2] = T[torch.randint(0, nt, (nq // 2,), device="cuda:0", generator=gen)] + 0.02 * torch.randn((nq // 2, r), device="cuda:0", generator=gen)
+    idx = torch.empty((nq, 2), dtype=torch.int32, device="cuda:0")
+    d = torch.empty((nq, 2), dtype=torch.float32, device="cuda:0")
+    torch.cuda.synchronize()
+    call = lambda: ctx.match_device(Q.data_ptr(), nq, T.data_ptr(), nt, r, idx.data_ptr(), d.data_ptr())
+    call()
+    ms = []
+    for _ in range(2):
+        call()
+        ms.append(ctx.last_kernel_ms())
+    torch_route(Q, T)
+    tms = []
+    for _ in range(2):
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record()
+        ti, td = torch_route(Q, T)
+        e1.record()
+        torch.cuda.synchronize()
+        tms.append(e0.elapsed_time(e1))
+    agree = float((ti[:, 0] == idx[:, 0].long()).float().mean())
+    best, floor = min(ms), 1e3 * 2.0 * nq * nt * r / PEAK
+    print(f"match {nq} x {nt} r {r}: {best:.3f} ms per call (repeats {ms[0]:.3f} {ms[1]:.3f}), f64 MFMA floor {floor:.3f} ms, "
+          f"share of the floor {floor / best:.3f}; torch float64 matmul + topk {min(tms):.3f} ms (repeats {tms[0]:.3f} {tms[1]:.3f}), "
+          f"{min(tms) / best:.2f} x the fused call; nearest index agrees for {100 * agree:.3f} % of the queries", flush=True)
+    del T, Q, idx, d
+ctx.close()
