@@ -137,18 +137,7 @@ constexpr int VCHUNK = 65536;
 template <typename Fn>
 int guarded(const dlco_ctx *ctx, Fn &&fn)
 {
-    try {
-        fn();
-        return DLCO_OK;
-    } catch (const Error &e) {
-        g_last_error = e.what();
-        if (ctx) const_cast<dlco_ctx *>(ctx)->err = e.what();
-        return e.code;
-    } catch (const std::exception &e) {
-        g_last_error = e.what();
-        if (ctx) const_cast<dlco_ctx *>(ctx)->err = e.what();
-        return DLCO_ERR_INVALID;
-    }
+    return guarded_call(g_last_error, ctx ? &const_cast<dlco_ctx *>(ctx)->err : nullptr, fn);
 }
 
 void sync(dlco_ctx *c) { DLCO_HIP(hipStreamSynchronize(c->stream)); }
@@ -606,18 +595,13 @@ int dlco_ctx_create(dlco_ctx **out, const dlco_cfg *cfg)
         DLCO_CHECK(cfg->world >= 1 && cfg->rank >= 0 && cfg->rank < cfg->world, DLCO_ERR_INVALID, "bad rank/world");
         DLCO_CHECK(cfg->B % cfg->world == 0, DLCO_ERR_INVALID, "B must be divisible by world");
         DLCO_CHECK(cfg->gamma > 0.f, DLCO_ERR_INVALID, "gamma must be positive");
-        int ndev = 0;
-        if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0 || cfg->device >= ndev)
-            throw Error(DLCO_ERR_NODEVICE, "no usable HIP device (this library has no CPU fallback)");
-        DLCO_HIP(hipSetDevice(cfg->device));
+        const hipDeviceProp_t prop = use_gfx950_device(cfg->device);
         c = new dlco_ctx();
         c->cfg = *cfg;
+        c->prop = prop;
         if (c->cfg.eig_tol <= 0.f) c->cfg.eig_tol = 2e-4f;
         if (c->cfg.eig_guard <= 0) c->cfg.eig_guard = 32;
         if (c->cfg.eig_max_iter <= 0) c->cfg.eig_max_iter = 40;
-        DLCO_HIP(hipGetDeviceProperties(&c->prop, cfg->device));
-        if (std::strncmp(c->prop.gcnArchName, "gfx950", 6) != 0)
-            throw Error(DLCO_ERR_NODEVICE, std::string("device is ") + c->prop.gcnArchName + ", this build targets gfx950 only");
         c->Fu = cfg->F; c->N = cfg->N; c->B = cfg->B;
         c->Bl = cfg->B / cfg->world; c->lo = cfg->rank * c->Bl;
         // column-sharded dual average (world > 1, or forced for single-rank testing of the path)

@@ -14,22 +14,6 @@
 
 using namespace dlco;
 
-namespace dlco {
-void desc_permute_filters(const float *src, int nsel, float *dst, hipStream_t s);
-void desc_transform(const uint8_t *patches, int n_patches, const float *cf, int ks, float inv_step, bool norm, int qk, float qgamma,
-                    float *PT, hipStream_t s);
-void desc_pool(const float *PT, int n_patches, const float *Fl, int nsel, int nsel_pad, float *desc, long desc_ld, hipStream_t s);
-void desc_pair_diff(const float *desc, long ld, int F, const int32_t *pairs, long n_pairs, float *dist, uint8_t *label, hipStream_t s);
-void desc_full_dist(const float *desc, long ld, int n_groups, int n_pairs, float *dist, hipStream_t s);
-void desc_project(const float *desc, long desc_ld, int n, const float *W, int r, int F, float *Y, long y_ld, hipStream_t s);
-void desc_pair_sqdist(const float *Y, long ld, int r, const int32_t *pairs, long n_pairs, float *dist, uint8_t *label, hipStream_t s);
-void match_norms(const float *x, long ld, long n, int r, double *norm, hipStream_t s);
-int match_tiles_per_slice(long nq, long nt, int n_cu);
-int match_slices(long nt, int tiles_per_slice);
-void match_top2(const float *query, long ldq, int nq, const float *train, long ldt, int nt, int r, const double *qnorm, const double *tnorm,
-                int tiles_per_slice, int32_t *idx, float *sqdist, void *part, float *out, hipStream_t s);
-}
-
 namespace {
 constexpr int kPix = 64 * 64;
 constexpr int kBins = 8;
@@ -65,21 +49,33 @@ namespace {
 template <typename Fn>
 int guarded(dlco_desc_ctx *c, Fn &&fn)
 {
-    try {
-        fn();
-        return DLCO_OK;
-    } catch (const Error &e) {
-        g_desc_error = e.what();
-        if (c) c->err = e.what();
-        return e.code;
-    } catch (const std::exception &e) {
-        g_desc_error = e.what();
-        if (c) c->err = e.what();
-        return DLCO_ERR_INVALID;
-    }
+    return guarded_call(g_desc_error, c ? &c->err : nullptr, fn);
 }
 
 void sync(dlco_desc_ctx *c) { DLCO_HIP(hipStreamSynchronize(c->stream)); }
+
+struct EventPair {
+    hipEvent_t e0 = nullptr, e1 = nullptr;
+    EventPair() { DLCO_HIP(hipEventCreate(&e0)); if (hipEventCreate(&e1) != hipSuccess) { (void)hipEventDestroy(e0); throw Error(DLCO_ERR_HIP, "hipEventCreate failed"); } }
+    ~EventPair() { (void)hipEventDestroy(e0); (void)hipEventDestroy(e1); }
+};
+
+// milliseconds the work that `run` queues on the stream takes there; `after` is queued behind it, outside the timing, and
+// the stream has drained on return
+template <typename Run, typename After>
+float timed_ms(dlco_desc_ctx *c, const EventPair &ev, Run &&run, After &&after)
+{
+    DLCO_HIP(hipEventRecord(ev.e0, c->stream));
+    run();
+    DLCO_HIP(hipEventRecord(ev.e1, c->stream));
+    after();
+    sync(c);
+    float ms = 0.f;
+    DLCO_HIP(hipEventElapsedTime(&ms, ev.e0, ev.e1));
+    return ms;
+}
+template <typename Run>
+float timed_ms(dlco_desc_ctx *c, const EventPair &ev, Run &&run) { return timed_ms(c, ev, run, [] {}); }
 
 // descriptors of patches [n,64,64] (host) into dst: device memory when dst_dev, else host; row pitch ld floats.
 // With `project` a row is the learnt descriptor W * Desc (r floats): the un-projected rows of a chunk stay in the
@@ -96,34 +92,27 @@ void compute(dlco_desc_ctx *c, const uint8_t *patches_host, int64_t n, float *ds
     c->pt.alloc((size_t)kChunk * kBins * kPix);
     if (!dst_dev || project) c->desc_chunk.alloc((size_t)kChunk * F);
     if (!dst_dev && project) c->y_chunk.alloc((size_t)kChunk * cols);
-    hipEvent_t e0, e1;
-    DLCO_HIP(hipEventCreate(&e0));
-    DLCO_HIP(hipEventCreate(&e1));
+    EventPair ev;
     double ms_total = 0.0;
     for (int64_t p0 = 0; p0 < n; p0 += kChunk) {
         const int cnt = (int)std::min<int64_t>(kChunk, n - p0);
         DLCO_HIP(hipMemcpyAsync(c->patches.p, patches_host + p0 * kPix, (size_t)cnt * kPix, hipMemcpyHostToDevice, c->stream));
-        DLCO_HIP(hipEventRecord(e0, c->stream));
-        desc_transform(c->patches.p, cnt, c->cf.p, c->ks, c->inv_step, c->norm, c->qk, c->qgamma, c->pt.p, c->stream);
         float *out = dst_dev ? dst + p0 * ld : (project ? c->y_chunk.p : c->desc_chunk.p);
         const long old = dst_dev ? ld : cols;
-        if (project) {
-            desc_pool(c->pt.p, cnt, c->filt.p, c->nsel, c->nsel_pad, c->desc_chunk.p, F, c->stream);
-            desc_project(c->desc_chunk.p, F, cnt, c->W.p, c->r, F, out, old, c->stream);
-        } else {
-            desc_pool(c->pt.p, cnt, c->filt.p, c->nsel, c->nsel_pad, out, old, c->stream);
-        }
-        DLCO_HIP(hipEventRecord(e1, c->stream));
-        if (!dst_dev)
-            DLCO_HIP(hipMemcpy2DAsync(dst + p0 * ld, (size_t)ld * sizeof(float), out, (size_t)cols * sizeof(float),
-                                      (size_t)cols * sizeof(float), (size_t)cnt, hipMemcpyDeviceToHost, c->stream));
-        sync(c);
-        float ms = 0.f;
-        DLCO_HIP(hipEventElapsedTime(&ms, e0, e1));
-        ms_total += ms;
+        ms_total += timed_ms(c, ev, [&] {
+            desc_transform(c->patches.p, cnt, c->cf.p, c->ks, c->inv_step, c->norm, c->qk, c->qgamma, c->pt.p, c->stream);
+            if (project) {
+                desc_pool(c->pt.p, cnt, c->filt.p, c->nsel, c->nsel_pad, c->desc_chunk.p, F, c->stream);
+                desc_project(c->desc_chunk.p, F, cnt, c->W.p, c->r, F, out, old, c->stream);
+            } else {
+                desc_pool(c->pt.p, cnt, c->filt.p, c->nsel, c->nsel_pad, out, old, c->stream);
+            }
+        }, [&] {
+            if (!dst_dev)
+                DLCO_HIP(hipMemcpy2DAsync(dst + p0 * ld, (size_t)ld * sizeof(float), out, (size_t)cols * sizeof(float),
+                                          (size_t)cols * sizeof(float), (size_t)cnt, hipMemcpyDeviceToHost, c->stream));
+        });
     }
-    (void)hipEventDestroy(e0);
-    (void)hipEventDestroy(e1);
     c->last_ms = ms_total;
 }
 
@@ -141,14 +130,7 @@ int dlco_desc_create(dlco_desc_ctx **out, float init_sigma, int32_t n_angle_bins
     const int rc = guarded(nullptr, [&] {
         DLCO_CHECK(n_angle_bins == kBins, DLCO_ERR_INVALID, "dlco_desc: nAngleBins must be 8 (the callers' value, src/comp-uprjdists.cpp:66)");
         DLCO_CHECK(init_sigma > 0.f, DLCO_ERR_INVALID, "dlco_desc: InitSigma must be positive");
-        int ndev = 0;
-        if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0 || device >= ndev)
-            throw Error(DLCO_ERR_NODEVICE, "no usable HIP device (this library has no CPU fallback)");
-        DLCO_HIP(hipSetDevice(device));
-        hipDeviceProp_t prop;
-        DLCO_HIP(hipGetDeviceProperties(&prop, device));
-        if (std::strncmp(prop.gcnArchName, "gfx950", 6) != 0)
-            throw Error(DLCO_ERR_NODEVICE, std::string("device is ") + prop.gcnArchName + ", this build targets gfx950 only");
+        const hipDeviceProp_t prop = use_gfx950_device(device);
         c = new dlco_desc_ctx();
         c->device = device; c->sigma = init_sigma; c->norm = norm != 0;
         c->n_cu = prop.multiProcessorCount;
@@ -477,19 +459,9 @@ void projected_pair_dists(dlco_desc_ctx *c, const uint8_t *patches_host, int64_t
     w.label.alloc((size_t)n_pairs);
     w.pairs.alloc((size_t)n_pairs * 4);
     compute(c, patches_host, n_patches, w.Y.p, true, (long)c->r, true);
-    hipEvent_t e0, e1;
-    DLCO_HIP(hipEventCreate(&e0));
-    DLCO_HIP(hipEventCreate(&e1));
+    EventPair ev;
     DLCO_HIP(hipMemcpyAsync(w.pairs.p, pairs_host, (size_t)n_pairs * 4 * sizeof(int32_t), hipMemcpyHostToDevice, c->stream));
-    DLCO_HIP(hipEventRecord(e0, c->stream));
-    desc_pair_sqdist(w.Y.p, c->r, c->r, w.pairs.p, n_pairs, w.dist.p, w.label.p, c->stream);
-    DLCO_HIP(hipEventRecord(e1, c->stream));
-    sync(c);
-    float ms = 0.f;
-    DLCO_HIP(hipEventElapsedTime(&ms, e0, e1));
-    (void)hipEventDestroy(e0);
-    (void)hipEventDestroy(e1);
-    c->last_ms += ms;
+    c->last_ms += timed_ms(c, ev, [&] { desc_pair_sqdist(w.Y.p, c->r, c->r, w.pairs.p, n_pairs, w.dist.p, w.label.p, c->stream); });
 }
 }  // namespace
 
@@ -533,12 +505,6 @@ bool match_args_ok(const void *a, const void *b, const void *o1, const void *o2,
     return a && b && o1 && o2 && r >= 1 && r <= 1024 && nq >= 1 && nt >= 1 && nt < ((int64_t)1 << 31);
 }
 
-struct EventPair {
-    hipEvent_t e0 = nullptr, e1 = nullptr;
-    EventPair() { DLCO_HIP(hipEventCreate(&e0)); if (hipEventCreate(&e1) != hipSuccess) { (void)hipEventDestroy(e0); throw Error(DLCO_ERR_HIP, "hipEventCreate failed"); } }
-    ~EventPair() { (void)hipEventDestroy(e0); (void)hipEventDestroy(e1); }
-};
-
 // device tables in, device results out; adds the kernels' time to *ms.  tnorm holds |t_j|^2 already.
 void match_on_device(dlco_desc_ctx *c, const float *q, long ldq, int64_t nq, const float *t, long ldt, int64_t nt, int r, int32_t *idx,
                      float *sqdist, float *cross, double *ms)
@@ -549,15 +515,11 @@ void match_on_device(dlco_desc_ctx *c, const float *q, long ldq, int64_t nq, con
         const int tps = match_tiles_per_slice(cnt, nt, c->n_cu), slices = match_slices(nt, tps);
         c->m_qnorm.alloc((size_t)cnt);
         if (!cross && slices > 1) c->m_part.alloc((size_t)slices * cnt * 4);
-        DLCO_HIP(hipEventRecord(ev.e0, c->stream));
-        match_norms(q + q0 * ldq, ldq, cnt, r, c->m_qnorm.p, c->stream);
-        match_top2(q + q0 * ldq, ldq, cnt, t, ldt, (int)nt, r, c->m_qnorm.p, c->m_tnorm.p, tps, idx ? idx + 2 * q0 : nullptr,
-                   sqdist ? sqdist + 2 * q0 : nullptr, c->m_part.p, cross ? cross + q0 * nt : nullptr, c->stream);
-        DLCO_HIP(hipEventRecord(ev.e1, c->stream));
-        sync(c);
-        float one = 0.f;
-        DLCO_HIP(hipEventElapsedTime(&one, ev.e0, ev.e1));
-        *ms += one;
+        *ms += timed_ms(c, ev, [&] {
+            match_norms(q + q0 * ldq, ldq, cnt, r, c->m_qnorm.p, c->stream);
+            match_top2(q + q0 * ldq, ldq, cnt, t, ldt, (int)nt, r, c->m_qnorm.p, c->m_tnorm.p, tps, idx ? idx + 2 * q0 : nullptr,
+                       sqdist ? sqdist + 2 * q0 : nullptr, c->m_part.p, cross ? cross + q0 * nt : nullptr, c->stream);
+        });
     }
 }
 
@@ -565,13 +527,7 @@ double train_norms(dlco_desc_ctx *c, const float *t, long ldt, int64_t nt, int r
 {
     EventPair ev;
     c->m_tnorm.alloc((size_t)nt);
-    DLCO_HIP(hipEventRecord(ev.e0, c->stream));
-    match_norms(t, ldt, nt, r, c->m_tnorm.p, c->stream);
-    DLCO_HIP(hipEventRecord(ev.e1, c->stream));
-    sync(c);
-    float ms = 0.f;
-    DLCO_HIP(hipEventElapsedTime(&ms, ev.e0, ev.e1));
-    return ms;
+    return timed_ms(c, ev, [&] { match_norms(t, ldt, nt, r, c->m_tnorm.p, c->stream); });
 }
 
 // rows of r floats on the host -> rows of pitch ld (a multiple of 4) in dst

@@ -2,6 +2,8 @@
 // Host side C++17, device side HIP.  No torch types, no OpenCV, no CUDA shims.
 #pragma once
 
+#include "../../include/dlco.h"
+
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -9,11 +11,13 @@
 #include <cstdint>
 #include <cstdio>
 #include <cstdlib>
+#include <cstring>
 #include <functional>
 #include <mutex>
 #include <utility>
 #include <stdexcept>
 #include <string>
+#include <type_traits>
 #include <vector>
 
 namespace dlco {
@@ -37,6 +41,50 @@ struct Error : std::runtime_error {
     do {                                                                           \
         if (!(cond)) throw ::dlco::Error((code), std::string(msg));                \
     } while (0)
+
+// The body of every ABI entry point: runs fn and turns an exception into its code; the message
+// goes to the calling file's thread-local string and, when there is a context, to its error string.
+template <typename Fn>
+int guarded_call(std::string &thread_err, std::string *ctx_err, Fn &&fn)
+{
+    try {
+        fn();
+        return DLCO_OK;
+    } catch (const Error &e) {
+        thread_err = e.what();
+        if (ctx_err) *ctx_err = e.what();
+        return e.code;
+    } catch (const std::exception &e) {
+        thread_err = e.what();
+        if (ctx_err) *ctx_err = e.what();
+        return DLCO_ERR_INVALID;
+    }
+}
+
+// Makes `device` current and returns its properties; throws DLCO_ERR_NODEVICE unless it is a gfx950.
+inline hipDeviceProp_t use_gfx950_device(int device)
+{
+    int ndev = 0;
+    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0 || device >= ndev)
+        throw Error(DLCO_ERR_NODEVICE, "no usable HIP device (this library has no CPU fallback)");
+    DLCO_HIP(hipSetDevice(device));
+    hipDeviceProp_t prop;
+    DLCO_HIP(hipGetDeviceProperties(&prop, device));
+    if (std::strncmp(prop.gcnArchName, "gfx950", 6) != 0)
+        throw Error(DLCO_ERR_NODEVICE, std::string("device is ") + prop.gcnArchName + ", this build targets gfx950 only");
+    return prop;
+}
+
+// Runtime count of 32-row tiles -> template argument: calls f(std::integral_constant<int, MT>) with MT = mt clamped to
+// [1, MAX].  MAX is per call: only the forms a caller names are instantiated.
+template <int MAX, typename F>
+void dispatch_mt(int mt, F &&f)
+{
+    if constexpr (MAX > 1) {
+        if (mt < MAX) return dispatch_mt<MAX - 1>(mt, f);
+    }
+    f(std::integral_constant<int, MAX>{});
+}
 
 // The value of one of the library's environment switches, nullptr when it is not set.  The library reads its environment
 // nowhere else: the switches and what each is for are listed beside it (dlco_api.cpp); a name outside that list throws.
@@ -165,6 +213,8 @@ void gemm_f32(const GemmArgs &a, hipStream_t s);
 // bf16x2_plane_bytes(M, K) bytes each.  Returns false for unsupported shapes (the caller then takes gemm_f32).
 size_t bf16x2_plane_bytes(int M, int K);
 size_t bf16x2_slab_floats(int M, int N, int ksplit = 0);
+// fragment-ordered bf16 planes of X [M][K] (M <= 160): hi, lo (and lo2 when given); layout: split_bf16_dev.hpp
+void split_planes_bf16(const float *X, long ldx, int M, int K, void *hi, void *lo, void *lo2, hipStream_t s);
 // plane_lo2 != nullptr selects the three-way split (x = hi + mid + lo, six MFMAs per term): fp32-level accuracy.
 // ksplit: number of K slices (grid y, default 4); K must be a multiple of 128 * ksplit.  A column slab of G
 // (N < K) takes ksplit = 4 * K / N so that the launch still fills the chip.
@@ -350,5 +400,35 @@ RocWork *roc_work_create(int n_max);
 void roc_work_destroy(RocWork *w);
 void roc_stats(RocWork *w, const float *dist_dev, const uint8_t *labels_dev, int n, float *fpr95, double *auc,
                hipStream_t s);
+
+// ---------------------------------------------------------------------------
+// pooling-region stage (kernels_pr.hip), called from dlco_pr_api.cpp
+// ---------------------------------------------------------------------------
+bool pr_steps(const float *D, long ld, const int32_t *pos_rows, const int32_t *neg_rows, unsigned n, unsigned t0, float mu, float gamma,
+              int F, float *w_io, float *df_io, float *last_f, hipStream_t s);
+void pr_gemv(const float *D, long ld, const int32_t *ids, int n, const float *w, int F, float *out, bool in_double, hipStream_t s);
+int pr_grid_group(int G, int F, int cus);
+bool pr_grid_steps(const float *D, long ld, const int32_t *pos_rows, const int32_t *neg_rows, unsigned n, unsigned t0, const float *mu,
+                   const float *gamma, int G, int group, int F, long ldw, float *w_io, float *df_io, hipStream_t s);
+void pr_gemv_multi(const float *D, long ld, const int32_t *ids, int n, const float *W, long ldw, const int32_t *sel, int nsel, int F,
+                   float *out, long ldo, bool in_double, hipStream_t s);
+
+// ---------------------------------------------------------------------------
+// descriptor generation, projection and matching (kernels_desc.hip, kernels_describe.hip, kernels_match.hip),
+// called from dlco_desc_api.cpp
+// ---------------------------------------------------------------------------
+void desc_permute_filters(const float *src, int nsel, float *dst, hipStream_t s);
+void desc_transform(const uint8_t *patches, int n_patches, const float *cf, int ks, float inv_step, bool norm, int qk, float qgamma,
+                    float *PT, hipStream_t s);
+void desc_pool(const float *PT, int n_patches, const float *Fl, int nsel, int nsel_pad, float *desc, long desc_ld, hipStream_t s);
+void desc_pair_diff(const float *desc, long ld, int F, const int32_t *pairs, long n_pairs, float *dist, uint8_t *label, hipStream_t s);
+void desc_full_dist(const float *desc, long ld, int n_groups, int n_pairs, float *dist, hipStream_t s);
+void desc_project(const float *desc, long desc_ld, int n, const float *W, int r, int F, float *Y, long y_ld, hipStream_t s);
+void desc_pair_sqdist(const float *Y, long ld, int r, const int32_t *pairs, long n_pairs, float *dist, uint8_t *label, hipStream_t s);
+void match_norms(const float *x, long ld, long n, int r, double *norm, hipStream_t s);
+int match_tiles_per_slice(long nq, long nt, int n_cu);
+int match_slices(long nt, int tiles_per_slice);
+void match_top2(const float *query, long ldq, int nq, const float *train, long ldt, int nt, int r, const double *qnorm, const double *tnorm,
+                int tiles_per_slice, int32_t *idx, float *sqdist, void *part, float *out, hipStream_t s);
 
 }  // namespace dlco

@@ -12,17 +12,6 @@
 
 using namespace dlco;
 
-namespace dlco {
-bool pr_steps(const float *D, long ld, const int32_t *pos_rows, const int32_t *neg_rows, unsigned n, unsigned t0, float mu, float gamma,
-              int F, float *w_io, float *df_io, float *last_f, hipStream_t s);
-void pr_gemv(const float *D, long ld, const int32_t *ids, int n, const float *w, int F, float *out, bool in_double, hipStream_t s);
-int pr_grid_group(int G, int F, int cus);
-bool pr_grid_steps(const float *D, long ld, const int32_t *pos_rows, const int32_t *neg_rows, unsigned n, unsigned t0, const float *mu,
-                   const float *gamma, int G, int group, int F, long ldw, float *w_io, float *df_io, hipStream_t s);
-void pr_gemv_multi(const float *D, long ld, const int32_t *ids, int n, const float *W, long ldw, const int32_t *sel, int nsel, int F,
-                   float *out, long ldo, bool in_double, hipStream_t s);
-}
-
 struct dlco_pr_ctx {
     int F = 0, N = 0, device = 0;
     float mu = 0.025f, gamma = 0.10f;
@@ -68,18 +57,7 @@ namespace {
 template <typename Ctx, typename Fn>
 int guarded(Ctx *c, Fn &&fn)
 {
-    try {
-        fn();
-        return DLCO_OK;
-    } catch (const Error &e) {
-        g_pr_error = e.what();
-        if (c) c->err = e.what();
-        return e.code;
-    } catch (const std::exception &e) {
-        g_pr_error = e.what();
-        if (c) c->err = e.what();
-        return DLCO_ERR_INVALID;
-    }
+    return guarded_call(g_pr_error, c ? &c->err : nullptr, fn);
 }
 
 template <typename Ctx>
@@ -162,14 +140,7 @@ int dlco_pr_create(dlco_pr_ctx **out, int32_t F, int32_t N, float mu, float gamm
     const int rc = guarded((dlco_pr_ctx *)nullptr, [&] {
         DLCO_CHECK(F >= 4 && F % 4 == 0 && F <= 8192, DLCO_ERR_INVALID, "pr-learn: F must be a multiple of 4, at most 8192");
         DLCO_CHECK(N >= 2 && gamma > 0.f, DLCO_ERR_INVALID, "pr-learn: N >= 2 and gamma > 0 required");
-        int ndev = 0;
-        if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0 || device >= ndev)
-            throw Error(DLCO_ERR_NODEVICE, "no usable HIP device (this library has no CPU fallback)");
-        DLCO_HIP(hipSetDevice(device));
-        hipDeviceProp_t prop;
-        DLCO_HIP(hipGetDeviceProperties(&prop, device));
-        if (std::strncmp(prop.gcnArchName, "gfx950", 6) != 0)
-            throw Error(DLCO_ERR_NODEVICE, std::string("device is ") + prop.gcnArchName + ", this build targets gfx950 only");
+        use_gfx950_device(device);
         c = new dlco_pr_ctx();
         c->F = F; c->N = N; c->mu = mu; c->gamma = gamma; c->device = device;
         c->rng = CvRng(seed);

@@ -20,16 +20,13 @@
 // terms are at the level of one fp32 rounding.  Six bf16 MFMAs still cost 3/8 of the fp32
 // MFMA pass, so the Rayleigh-Ritz product of the tracker runs at fp32 accuracy from one
 // HBM-bound read of G as well.
+// The split, the plane layout, the MFMA term order and the LDS geometry of these kernels are in split_bf16_dev.hpp.
 #include "dlco_internal.hpp"
+#include "split_bf16_dev.hpp"
 
 #include <algorithm>
-#include <type_traits>
 
 namespace dlco {
-
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef float f32x4 __attribute__((ext_vector_type(4)));
 
 namespace {
 
@@ -37,7 +34,7 @@ constexpr int W8 = 8;             // waves per workgroup
 constexpr int T8 = 64 * W8;
 constexpr int KS = 4;             // default K split (gridDim.y); the slices are summed in order by splitk_reduce_f32
 
-// plane element ((k16 * MT + tile) * 64 + lane) * 8 + j  =  X[tile*32 + (lane&31)][k16*16 + 8*(lane>>5) + j]
+// one thread per plane entry t = plane_entry(k16, MT, tile, lane)
 __global__ __launch_bounds__(256) void split_x_kernel(const float *X, long ldx, int M, int MT, int K, bf16x8 *hi, bf16x8 *lo,
                                                       bf16x8 *lo2)
 {
@@ -54,16 +51,9 @@ __global__ __launch_bounds__(256) void split_x_kernel(const float *X, long ldx, 
         const f32x4 a = *reinterpret_cast<const f32x4 *>(X + (long)row * ldx + k);
         const f32x4 b = *reinterpret_cast<const f32x4 *>(X + (long)row * ldx + k + 4);
 #pragma unroll
-        for (int j = 0; j < 8; j++) {
-            const float x = j < 4 ? a[j & 3] : b[j & 3];
-            h[j] = (__bf16)x;
-            const float r1 = x - (float)h[j];
-            l[j] = (__bf16)r1;
-            l2[j] = (__bf16)(r1 - (float)l[j]);
-        }
+        for (int j = 0; j < 8; j++) split_f32<3>(j < 4 ? a[j & 3] : b[j & 3], j, h, l, l2);
     } else {
-#pragma unroll
-        for (int j = 0; j < 8; j++) { h[j] = (__bf16)0.f; l[j] = (__bf16)0.f; l2[j] = (__bf16)0.f; }
+        h = l = l2 = bf16x8{};
     }
     hi[t] = h;
     lo[t] = l;
@@ -113,7 +103,7 @@ __global__ __launch_bounds__(T8) void skinny_bf16x2_kernel(Bf2Dev g)
     auto load_a = [&](int s, bf16x8 (&h)[MT], bf16x8 (&l)[MT], bf16x8 (&m2)[NS == 3 ? MT : 1]) {
 #pragma unroll
         for (int t = 0; t < MT; t++) {
-            const long idx = ((long)s * MT + t) * 64 + lane;
+            const long idx = plane_entry((long)s, MT, t, lane);
             h[t] = g.xhi[idx];
             l[t] = g.xlo[idx];
             if (NS == 3) m2[t] = g.xlo2[idx];
@@ -121,24 +111,8 @@ __global__ __launch_bounds__(T8) void skinny_bf16x2_kernel(Bf2Dev g)
     };
     auto compute = [&](const float (&gv)[8], const bf16x8 (&h)[MT], const bf16x8 (&l)[MT], const bf16x8 (&m2)[NS == 3 ? MT : 1]) {
         bf16x8 bh, bl, bl2;
-#pragma unroll
-        for (int j = 0; j < 8; j++) {
-            bh[j] = (__bf16)gv[j];
-            const float r1 = gv[j] - (float)bh[j];
-            bl[j] = (__bf16)r1;
-            if (NS == 3) bl2[j] = (__bf16)(r1 - (float)bl[j]);
-        }
-#pragma unroll
-        for (int t = 0; t < MT; t++) {
-            if (NS == 3) {                                   // smallest terms first
-                acc[t] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(h[t], bl2, acc[t], 0, 0, 0);
-                acc[t] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(m2[t], bh, acc[t], 0, 0, 0);
-                acc[t] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(l[t], bl, acc[t], 0, 0, 0);
-            }
-            acc[t] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(h[t], bl, acc[t], 0, 0, 0);
-            acc[t] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(l[t], bh, acc[t], 0, 0, 0);
-            acc[t] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(h[t], bh, acc[t], 0, 0, 0);
-        }
+        split_frag<NS>(gv, bh, bl, bl2);
+        mfma_split_terms<MT, NS>(h, l, m2, bh, bl, bl2, acc);
     };
 
     // G fragments run four K steps ahead (HBM latency: ~64 KiB in flight per CU), X fragments two
@@ -207,23 +181,16 @@ __global__ __launch_bounds__(T8) void skinny_bf16x2_kernel(Bf2Dev g)
 // One barrier per chunk.  Same MFMA schedule per K step and the same slab reduction as above; a column's
 // K order is plain ascending inside the slice.  Deterministic.  `tiled`: G stored as contiguous
 // 128 x 128 tiles (a chunk is then half a tile).
-constexpr int RK_KC = 64;                  // chunk depth (floats)
-constexpr int RK_RS = RK_KC + 4;           // LDS row stride of the G image (floats)
-constexpr int RK_T = 768;                  // 8 compute + 4 loader waves
-constexpr int RK_GBYTES = 128 * RK_RS * 4; // one G image
-__host__ __device__ constexpr int rk_abytes(int mt, int ns) { return ns * mt * 4 * 64 * 16; }     // one A image: ns planes x 4 steps x mt tiles x 1 KiB
-inline size_t rk_lds_bytes(int mt, int ns) { return (size_t)2 * (RK_GBYTES + rk_abytes(mt, ns)); }
 
 template <int MT, int NS>
-__global__ __launch_bounds__(RK_T) void skinny_rows_kernel(Bf2Dev g)
+__global__ __launch_bounds__(SB_T) void skinny_rows_kernel(Bf2Dev g)
 {
     extern __shared__ __attribute__((aligned(16))) char lds_raw[];
-    constexpr int ABYTES = rk_abytes(MT, NS);
+    constexpr int ABYTES = sb_abytes(MT, NS);
     constexpr int APLANE = MT * 256;                          // 16-byte entries of one plane's chunk slice
-    constexpr int AENT = NS * APLANE;                          // 16-byte entries of one A image
-    constexpr int NA = (AENT + 255) / 256;                     // A entries per loader thread and chunk
-    float *gb0 = reinterpret_cast<float *>(lds_raw), *gb1 = reinterpret_cast<float *>(lds_raw + RK_GBYTES);
-    bf16x8 *ab0 = reinterpret_cast<bf16x8 *>(lds_raw + 2 * RK_GBYTES), *ab1 = reinterpret_cast<bf16x8 *>(lds_raw + 2 * RK_GBYTES + ABYTES);
+    constexpr int NA = NS * MT;                                // A entries per loader thread and chunk
+    float *gb0 = reinterpret_cast<float *>(lds_raw), *gb1 = reinterpret_cast<float *>(lds_raw + SB_GBYTES);
+    bf16x8 *ab0 = reinterpret_cast<bf16x8 *>(lds_raw + 2 * SB_GBYTES), *ab1 = reinterpret_cast<bf16x8 *>(lds_raw + 2 * SB_GBYTES + ABYTES);
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     // Workgroup -> (column tile bx, K slice by).  Workgroups are dealt round-robin to the 8 XCDs, each with
     // its own L2: all workgroups of one XCD are given the SAME K slice (or as few as possible), so that the
@@ -242,7 +209,7 @@ __global__ __launch_bounds__(RK_T) void skinny_rows_kernel(Bf2Dev g)
     const int j0 = bx * 128;
     const int kslice = g.K / (int)gridDim.y;                  // host: a multiple of 128
     const int kbeg = by * kslice;
-    const int nchunks = kslice / RK_KC;
+    const int nchunks = kslice / SB_KC;
     const int st0 = kbeg / 16;                                // K step (of 16) of chunk c, step q: st0 + 4c + q
 
     if (wave >= 8) {
@@ -257,30 +224,22 @@ __global__ __launch_bounds__(RK_T) void skinny_rows_kernel(Bf2Dev g)
                                   : (long)(j0 + grow) * g.ldg + kbeg + 4 * gc4;
         const int voff = (int)(base * (long)sizeof(float));
         const int row16 = (int)(16 * pitch * (long)sizeof(float));
-        const int plane_bytes = MT * 32 * g.K * 2;
-        const __amdgpu_buffer_rsrc_t rs_hi = __builtin_amdgcn_make_buffer_rsrc(const_cast<bf16x8 *>(g.xhi), 0, plane_bytes, 0x00020000);
-        const __amdgpu_buffer_rsrc_t rs_lo = __builtin_amdgcn_make_buffer_rsrc(const_cast<bf16x8 *>(g.xlo), 0, plane_bytes, 0x00020000);
-        const __amdgpu_buffer_rsrc_t rs_lo2 = __builtin_amdgcn_make_buffer_rsrc(const_cast<bf16x8 *>(NS == 3 ? g.xlo2 : g.xlo), 0, plane_bytes, 0x00020000);
+        const PlaneRsrc rs = make_plane_rsrc<MT, NS>(g.xhi, g.xlo, g.xlo2, g.K);
         struct Stage { f32x4 gq[8]; bf16x8 aq[NA]; };
         Stage s0, s1;
         auto gload = [&](int c, Stage &st) {
-            const int soff = g.tiled ? ((c >> 1) * 16384 + (c & 1) * 64) * (int)sizeof(float) : c * RK_KC * (int)sizeof(float);
+            const int soff = g.tiled ? ((c >> 1) * 16384 + (c & 1) * 64) * (int)sizeof(float) : c * SB_KC * (int)sizeof(float);
 #pragma unroll
             for (int u = 0; u < 8; u++) st.gq[u] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(rsrc, voff, soff + u * row16, 0));
-            // the chunk's slice of every plane is MT * 256 consecutive 16-byte entries (fragment order): entry
-            // lt + 256 v belongs to plane v / MT -> static plane per v, scalar offset, one per-lane offset (16 lt)
-            const int a0 = (st0 + 4 * c) * MT * 64 * 16;       // byte offset of the slice inside a plane
+            const int a0 = slice_bytes<MT>(st0 + 4 * c);
 #pragma unroll
-            for (int v = 0; v < NA; v++) {
-                const __amdgpu_buffer_rsrc_t &ra = (v / MT == 0) ? rs_hi : ((v / MT == 1) ? rs_lo : rs_lo2);
-                st.aq[v] = __builtin_bit_cast(bf16x8, __builtin_amdgcn_raw_buffer_load_b128(ra, 16 * lt, a0 + (v % MT) * 256 * 16, 0));
-            }
+            for (int v = 0; v < NA; v++) st.aq[v] = load_slice_entry<MT>(rs, a0, lt, v);
         };
         auto gstore = [&](int buf, const Stage &st) {
             float *gb = buf ? gb1 : gb0;
             bf16x8 *ab = buf ? ab1 : ab0;
 #pragma unroll
-            for (int u = 0; u < 8; u++) *reinterpret_cast<f32x4 *>(gb + (grow + 16 * u) * RK_RS + 4 * gc4) = st.gq[u];
+            for (int u = 0; u < 8; u++) *reinterpret_cast<f32x4 *>(gb + (grow + 16 * u) * SB_RS + 4 * gc4) = st.gq[u];
 #pragma unroll
             for (int v = 0; v < NA; v++) ab[lt + 256 * v] = st.aq[v];
         };
@@ -321,39 +280,21 @@ __global__ __launch_bounds__(RK_T) void skinny_rows_kernel(Bf2Dev g)
 
     // operands of one K step, read from the LDS images: issued one step ahead of the MFMAs that use them
     // (this wave is alone on its SIMD as far as LDS latency goes)
-    struct Frag { f32x4 g0, g1; bf16x8 a[NS][MT]; };
-    auto fetch = [&](const float *gb, const bf16x8 *ab, int q, Frag &f) {
-        const float *p = gb + (nt * 32 + lc) * RK_RS + 16 * q + 8 * lh;
+    auto fetch = [&](const float *gb, const bf16x8 *ab, int q, Frag<MT, NS> &f) {
+        const float *p = gb + (nt * 32 + lc) * SB_RS + 16 * q + 8 * lh;
         f.g0 = *reinterpret_cast<const f32x4 *>(p);
         f.g1 = *reinterpret_cast<const f32x4 *>(p + 4);
 #pragma unroll
         for (int n = 0; n < NS; n++)
 #pragma unroll
-            for (int t = 0; t < MT; t++) f.a[n][t] = ab[n * APLANE + (q * MT + t) * 64 + lane];
+            for (int t = 0; t < MT; t++) f.a[n][t] = ab[n * APLANE + plane_entry(q, MT, t, lane)];
     };
-    auto multiply = [&](const Frag &f) {
+    auto multiply = [&](const Frag<MT, NS> &f) {              // a lambda of the kernel: see Frag
         bf16x8 bh, bl, bl2;
-#pragma unroll
-        for (int j = 0; j < 8; j++) {
-            const float v = j < 4 ? f.g0[j & 3] : f.g1[j & 3];
-            bh[j] = (__bf16)v;
-            const float r1 = v - (float)bh[j];
-            bl[j] = (__bf16)r1;
-            if (NS == 3) bl2[j] = (__bf16)(r1 - (float)bl[j]);
-        }
-#pragma unroll
-        for (int t = 0; t < MT; t++) {
-            if (NS == 3) {                                   // smallest terms first
-                acc[t] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(f.a[0][t], bl2, acc[t], 0, 0, 0);
-                acc[t] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(f.a[NS - 1][t], bh, acc[t], 0, 0, 0);
-                acc[t] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(f.a[1][t], bl, acc[t], 0, 0, 0);
-            }
-            acc[t] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(f.a[0][t], bl, acc[t], 0, 0, 0);
-            acc[t] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(f.a[1][t], bh, acc[t], 0, 0, 0);
-            acc[t] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(f.a[0][t], bh, acc[t], 0, 0, 0);
-        }
+        split_frag<NS>(f.g0, f.g1, bh, bl, bl2);
+        mfma_split_terms<MT, NS>(f.a[0], f.a[NS >= 2 ? 1 : 0], f.a[NS - 1], bh, bl, bl2, acc);
     };
-    Frag fa;                                                  // (the SIMD's other compute wave covers the LDS latency)
+    Frag<MT, NS> fa;                                          // (the SIMD's other compute wave covers the LDS latency)
     __syncthreads();
     for (int c = 0; c < nchunks; c++) {
         const float *gb = (c & 1) ? gb1 : gb0;
@@ -410,15 +351,9 @@ __global__ __launch_bounds__(256) void reduce_split_kernel(const float *slab, in
         if (E2) { o0 += b2 * *reinterpret_cast<const f32x4 *>(E2 + idx); o1 += b2 * *reinterpret_cast<const f32x4 *>(E2 + idx + 4); }
         *reinterpret_cast<f32x4 *>(C + idx) = o0;
         *reinterpret_cast<f32x4 *>(C + idx + 4) = o1;
-        bf16x8 h, l;
-#pragma unroll
-        for (int u = 0; u < 8; u++) {
-            const float x = u < 4 ? o0[u & 3] : o1[u & 3];
-            h[u] = (__bf16)x;
-            l[u] = (__bf16)(x - (float)h[u]);
-        }
-        // plane entry ((k16 * MT + tile) * 64 + lane): row tile*32 + (lane & 31), columns k16*16 + 8*(lane >> 5) .. +7
-        const long t = ((long)(k8 >> 1) * MT + (i >> 5)) * 64 + (i & 31) + 32 * (k8 & 1);
+        bf16x8 h, l, l2;
+        split_frag<2>(o0, o1, h, l, l2);
+        const long t = plane_entry_at(MT, i, k8);
         hi[t] = h;
         lo[t] = l;
     }
@@ -444,7 +379,7 @@ __global__ __launch_bounds__(256) void reduce_split_kernel(const float *slab, in
 // Roles, LDS images, MFMA schedule and epilogue are those of skinny_rows_kernel; a transposed chunk is staged as
 // [64 k][128 columns] (row stride 132) and its B fragments are eight 4-byte reads of 32 consecutive columns.
 constexpr int SYM_TS = 132;                // LDS row stride of a transposed chunk image (floats)
-static_assert(RK_KC * SYM_TS * 4 <= RK_GBYTES, "a transposed chunk image must fit the G image");
+static_assert(SB_KC * SYM_TS * 4 <= SB_GBYTES, "a transposed chunk image must fit the G image");
 
 // Other widths (round 4): nt = K / 128 tile rows are embedded in Z_2^b, 2^b = the next power of two >= max(nt, 4); the same
 // pairing runs on 4 * 2^b workgroups, of which those of a block I >= nt leave at once and the others skip partners
@@ -461,16 +396,15 @@ struct SymDev {
 // FULL: the tile count is the power of two itself (K = 8192: 64 tile rows) - every partner is real and comes from bit
 // arithmetic alone, no list in LDS inside the loop.
 template <int MT, int NS, bool FULL>
-__global__ __launch_bounds__(RK_T) void skinny_sym_kernel(SymDev g)
+__global__ __launch_bounds__(SB_T) void skinny_sym_kernel(SymDev g)
 {
     extern __shared__ __attribute__((aligned(16))) char lds_raw[];
-    constexpr int ABYTES = rk_abytes(MT, NS);
+    constexpr int ABYTES = sb_abytes(MT, NS);
     constexpr int APLANE = MT * 256;
-    constexpr int AENT = NS * APLANE;
-    constexpr int NA = (AENT + 255) / 256;
+    constexpr int NA = NS * MT;
     const int NT = g.nt, lb = g.lb;                            // tile rows; 2^lb = padded tile count
-    float *gb0 = reinterpret_cast<float *>(lds_raw), *gb1 = reinterpret_cast<float *>(lds_raw + RK_GBYTES);
-    bf16x8 *ab0 = reinterpret_cast<bf16x8 *>(lds_raw + 2 * RK_GBYTES), *ab1 = reinterpret_cast<bf16x8 *>(lds_raw + 2 * RK_GBYTES + ABYTES);
+    float *gb0 = reinterpret_cast<float *>(lds_raw), *gb1 = reinterpret_cast<float *>(lds_raw + SB_GBYTES);
+    bf16x8 *ab0 = reinterpret_cast<bf16x8 *>(lds_raw + 2 * SB_GBYTES), *ab1 = reinterpret_cast<bf16x8 *>(lds_raw + 2 * SB_GBYTES + ABYTES);
     __shared__ int jlist[16];                                  // the real partners of this workgroup, in schedule order
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     // workgroup -> (group p, half c, block I): see above (bits 5, 4 there are bits lb-1, lb-2 here)
@@ -500,7 +434,7 @@ __global__ __launch_bounds__(RK_T) void skinny_sym_kernel(SymDev g)
         // no real partner in this group (only possible beside padding blocks): the group's slab still has to hold zeros
         // for this block's columns, the reduction adds all four
         float *slab = g.slab + (long)p * g.M * g.K;
-        for (int e = tid; e < g.M * 128; e += RK_T) slab[(long)(e >> 7) * g.K + I * 128 + (e & 127)] = 0.f;
+        for (int e = tid; e < g.M * 128; e += SB_T) slab[(long)(e >> 7) * g.K + I * 128 + (e & 127)] = 0.f;
         return;
     }
     // chunk cc: partner block, orientation, byte offset of the stored tile
@@ -516,13 +450,10 @@ __global__ __launch_bounds__(RK_T) void skinny_sym_kernel(SymDev g)
         // direct chunk: thread -> 16-byte column gc4 of tile rows grow + 16 u; transposed: column c4 of tile rows half*64 + kr + 8 u
         const int voff_d = ((lt >> 4) * 128 + 4 * (lt & 15)) * (int)sizeof(float);
         const int voff_t = ((lt >> 5) * 128 + 4 * (lt & 31)) * (int)sizeof(float);
-        const int loff_d = (lt >> 4) * RK_RS + 4 * (lt & 15), loff_t = (lt >> 5) * SYM_TS + 4 * (lt & 31);
+        const int loff_d = (lt >> 4) * SB_RS + 4 * (lt & 15), loff_t = (lt >> 5) * SYM_TS + 4 * (lt & 31);
         const __amdgpu_buffer_rsrc_t rsrc =
             __builtin_amdgcn_make_buffer_rsrc(const_cast<float *>(g.G), 0, (NT * (NT + 1) / 2) * 128 * 128 * (int)sizeof(float), 0x00020000);
-        const int plane_bytes = MT * 32 * g.K * 2;
-        const __amdgpu_buffer_rsrc_t rs_hi = __builtin_amdgcn_make_buffer_rsrc(const_cast<bf16x8 *>(g.xhi), 0, plane_bytes, 0x00020000);
-        const __amdgpu_buffer_rsrc_t rs_lo = __builtin_amdgcn_make_buffer_rsrc(const_cast<bf16x8 *>(g.xlo), 0, plane_bytes, 0x00020000);
-        const __amdgpu_buffer_rsrc_t rs_lo2 = __builtin_amdgcn_make_buffer_rsrc(const_cast<bf16x8 *>(NS == 3 ? g.xlo2 : g.xlo), 0, plane_bytes, 0x00020000);
+        const PlaneRsrc rs = make_plane_rsrc<MT, NS>(g.xhi, g.xlo, g.xlo2, g.K);
         struct Stage { f32x4 gq[8]; bf16x8 aq[NA]; };
         Stage s0, s1;
         // The loads of a chunk are issued in ONE fixed order (G then X planes, fenced against the scheduler): hipcc places
@@ -536,7 +467,7 @@ __global__ __launch_bounds__(RK_T) void skinny_sym_kernel(SymDev g)
             const int voff = direct ? voff_d : voff_t;
             const int soff = tile_bytes(J) + (direct ? half * 64 : half * 64 * 128) * (int)sizeof(float);
             const int ustep = (direct ? 16 : 8) * 128 * (int)sizeof(float);
-            const int a0 = (J * 8 + half * 4) * MT * 64 * 16;  // the X planes' slice for block J, this half: byte offset inside a plane
+            const int a0 = slice_bytes<MT>(J * 8 + half * 4);  // the X planes' slice for block J, this half
             __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
             for (int u = 0; u < 8; u++) {
@@ -545,8 +476,7 @@ __global__ __launch_bounds__(RK_T) void skinny_sym_kernel(SymDev g)
             }
 #pragma unroll
             for (int v = 0; v < NA; v++) {
-                const __amdgpu_buffer_rsrc_t &ra = (v / MT == 0) ? rs_hi : ((v / MT == 1) ? rs_lo : rs_lo2);
-                st.aq[v] = __builtin_bit_cast(bf16x8, __builtin_amdgcn_raw_buffer_load_b128(ra, 16 * lt, a0 + (v % MT) * 256 * 16, 0));
+                st.aq[v] = load_slice_entry<MT>(rs, a0, lt, v);
                 __builtin_amdgcn_sched_barrier(0);
             }
         };
@@ -554,7 +484,7 @@ __global__ __launch_bounds__(RK_T) void skinny_sym_kernel(SymDev g)
             float *gb = (cc & 1) ? gb1 : gb0;
             bf16x8 *ab = (cc & 1) ? ab1 : ab0;
             const bool direct = I <= partner(cc);
-            const int loff = direct ? loff_d : loff_t, lstep = direct ? 16 * RK_RS : 8 * SYM_TS;
+            const int loff = direct ? loff_d : loff_t, lstep = direct ? 16 * SB_RS : 8 * SYM_TS;
 #pragma unroll
             for (int u = 0; u < 8; u++) *reinterpret_cast<f32x4 *>(gb + loff + u * lstep) = st.gq[u];
 #pragma unroll
@@ -599,10 +529,9 @@ __global__ __launch_bounds__(RK_T) void skinny_sym_kernel(SymDev g)
 #pragma unroll
         for (int r = 0; r < 16; r++) acc[a][r] = 0.f;
 
-    struct Frag { f32x4 g0, g1; bf16x8 a[NS][MT]; };
-    auto fetch = [&](const float *gb, const bf16x8 *ab, bool direct, int q, Frag &f) {
+    auto fetch = [&](const float *gb, const bf16x8 *ab, bool direct, int q, Frag<MT, NS> &f) {
         if (direct) {
-            const float *pp = gb + (nt * 32 + lc) * RK_RS + 16 * q + 8 * lh;
+            const float *pp = gb + (nt * 32 + lc) * SB_RS + 16 * q + 8 * lh;
             f.g0 = *reinterpret_cast<const f32x4 *>(pp);
             f.g1 = *reinterpret_cast<const f32x4 *>(pp + 4);
         } else {
@@ -613,35 +542,18 @@ __global__ __launch_bounds__(RK_T) void skinny_sym_kernel(SymDev g)
 #pragma unroll
         for (int n = 0; n < NS; n++)
 #pragma unroll
-            for (int t = 0; t < MT; t++) f.a[n][t] = ab[n * APLANE + (q * MT + t) * 64 + lane];
-    };
-    auto multiply = [&](const Frag &f) {
-        bf16x8 bh, bl, bl2;
-#pragma unroll
-        for (int j = 0; j < 8; j++) {
-            const float v = j < 4 ? f.g0[j & 3] : f.g1[j & 3];
-            bh[j] = (__bf16)v;
-            const float r1 = v - (float)bh[j];
-            bl[j] = (__bf16)r1;
-            if (NS == 3) bl2[j] = (__bf16)(r1 - (float)bl[j]);
-        }
-#pragma unroll
-        for (int t = 0; t < MT; t++) {
-            if (NS == 3) {                                   // smallest terms first
-                acc[t] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(f.a[0][t], bl2, acc[t], 0, 0, 0);
-                acc[t] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(f.a[NS - 1][t], bh, acc[t], 0, 0, 0);
-                acc[t] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(f.a[1][t], bl, acc[t], 0, 0, 0);
-            }
-            acc[t] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(f.a[0][t], bl, acc[t], 0, 0, 0);
-            acc[t] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(f.a[1][t], bh, acc[t], 0, 0, 0);
-            acc[t] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(f.a[0][t], bh, acc[t], 0, 0, 0);
-        }
+            for (int t = 0; t < MT; t++) f.a[n][t] = ab[n * APLANE + plane_entry(q, MT, t, lane)];
     };
     // (Two fragment sets per wave - the second K step's reads in flight under the first one's MFMAs - were measured and
     // changed nothing: 59.3 against 59.6 us per pass.  Ablation of this kernel at M = 96, two-way, per pass incl. 10 us of
     // split + reduce: 60 us as is, 61 us without the G loads, 44 us without the compute waves' work, 32 us with neither -
     // the loaders' LDS stores and the compute waves' LDS reads and conversions add up rather than overlap.)
-    Frag fa;
+    auto multiply = [&](const Frag<MT, NS> &f) {              // a lambda of the kernel: see Frag
+        bf16x8 bh, bl, bl2;
+        split_frag<NS>(f.g0, f.g1, bh, bl, bl2);
+        mfma_split_terms<MT, NS>(f.a[0], f.a[NS >= 2 ? 1 : 0], f.a[NS - 1], bh, bl, bl2, acc);
+    };
+    Frag<MT, NS> fa;
     __syncthreads();
     for (int cc = 0; cc < nchunks; cc++) {
         const float *gb = (cc & 1) ? gb1 : gb0;
@@ -680,27 +592,26 @@ __global__ __launch_bounds__(RK_T) void skinny_sym_kernel(SymDev g)
 template <int MT, int NS>
 void launch_sym(const SymDev &g, hipStream_t s)
 {
-    const size_t lds = rk_lds_bytes(MT, NS);
+    const size_t lds = sb_lds_bytes(MT, NS);
     if (g.nt == (1 << g.lb)) {
         ensure_dynamic_lds(reinterpret_cast<const void *>(skinny_sym_kernel<MT, NS, true>), (int)lds);
-        hipLaunchKernelGGL((skinny_sym_kernel<MT, NS, true>), dim3(4u << g.lb), dim3(RK_T), lds, s, g);
+        hipLaunchKernelGGL((skinny_sym_kernel<MT, NS, true>), dim3(4u << g.lb), dim3(SB_T), lds, s, g);
     } else {
         ensure_dynamic_lds(reinterpret_cast<const void *>(skinny_sym_kernel<MT, NS, false>), (int)lds);
-        hipLaunchKernelGGL((skinny_sym_kernel<MT, NS, false>), dim3(4u << g.lb), dim3(RK_T), lds, s, g);
+        hipLaunchKernelGGL((skinny_sym_kernel<MT, NS, false>), dim3(4u << g.lb), dim3(SB_T), lds, s, g);
     }
 }
 
 template <int MT, int NS>
 void launch_rows(const Bf2Dev &g, dim3 grid, hipStream_t s)
 {
-    const size_t lds = rk_lds_bytes(MT, NS);
+    const size_t lds = sb_lds_bytes(MT, NS);
     ensure_dynamic_lds(reinterpret_cast<const void *>(skinny_rows_kernel<MT, NS>), (int)lds);
-    hipLaunchKernelGGL((skinny_rows_kernel<MT, NS>), grid, dim3(RK_T), lds, s, g);
+    hipLaunchKernelGGL((skinny_rows_kernel<MT, NS>), grid, dim3(SB_T), lds, s, g);
 }
 
 }  // namespace
 
-// fragment-ordered bf16 planes of X [M][K] (M <= 160): hi, lo (and lo2 when given); see split_x_kernel
 void split_planes_bf16(const float *X, long ldx, int M, int K, void *hi, void *lo, void *lo2, hipStream_t s)
 {
     const int mt = (M + 31) / 32;
@@ -722,9 +633,7 @@ bool skinny_product_bf16x2(const float *X, long ldx, int M, const float *G, long
     const int ks = ksplit > 0 ? ksplit : KS;
     if (M < 1 || mt > 5 || N % 128 != 0 || K % (16 * ks * 2 * 4) != 0) return false;   // 4 steps per loop trip
     if (ldx % 4 != 0 || (reinterpret_cast<uintptr_t>(X) & 15) != 0) return false;
-    const long total = (long)(K / 16) * mt * 64;
-    hipLaunchKernelGGL(split_x_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, s, X, ldx, M, mt, K,
-                       static_cast<bf16x8 *>(plane_hi), static_cast<bf16x8 *>(plane_lo), static_cast<bf16x8 *>(plane_lo2));
+    split_planes_bf16(X, ldx, M, K, plane_hi, plane_lo, plane_lo2, s);
     Bf2Dev g;
     g.M = M; g.N = N; g.K = K;
     g.xhi = static_cast<const bf16x8 *>(plane_hi); g.xlo = static_cast<const bf16x8 *>(plane_lo);
@@ -735,34 +644,15 @@ bool skinny_product_bf16x2(const float *X, long ldx, int M, const float *G, long
     // (four row tiles with the three-way split do not fit the register budget of the split-role kernel)
     if (N == K && K % (128 * ks) == 0 && ldg % 4 == 0 && (reinterpret_cast<uintptr_t>(G) & 15) == 0 &&
         (long)K * ldg * 4 < (1L << 31) && !(mt >= 4 && plane_lo2)) {
-        if (plane_lo2) {
-            if (mt == 1) launch_rows<1, 3>(g, grid, s);
-            else if (mt == 2) launch_rows<2, 3>(g, grid, s);
-            else if (mt == 3) launch_rows<3, 3>(g, grid, s);
-            else launch_rows<4, 3>(g, grid, s);
-        } else {
-            if (mt == 1) launch_rows<1, 2>(g, grid, s);
-            else if (mt == 2) launch_rows<2, 2>(g, grid, s);
-            else if (mt == 3) launch_rows<3, 2>(g, grid, s);
-            else if (mt == 4) launch_rows<4, 2>(g, grid, s);
-            else launch_rows<5, 2>(g, grid, s);               // 160 rows: blocks of rank ~128 + guards in ONE pass over G
-        }
+        if (plane_lo2) dispatch_mt<4>(mt, [&](auto MT) { launch_rows<MT(), 3>(g, grid, s); });
+        else dispatch_mt<5>(mt, [&](auto MT) { launch_rows<MT(), 2>(g, grid, s); });   // 160 rows: blocks of rank ~128 + guards in ONE pass over G
         DLCO_HIP(hipGetLastError());
         splitk_reduce_f32(slab, ks, M, N, C, ldc, alpha, 0.f, E1, b1, E2, b2, s);
         return true;
     }
     if (g_tiled || mt > 4) return false;                       // only the row-streaming kernel reads the tiled layout / takes five row tiles
-    if (plane_lo2) {                                         // three-way split: fp32-level accuracy
-        if (mt == 1) hipLaunchKernelGGL((skinny_bf16x2_kernel<1, 3>), grid, block, 0, s, g);
-        else if (mt == 2) hipLaunchKernelGGL((skinny_bf16x2_kernel<2, 3>), grid, block, 0, s, g);
-        else if (mt == 3) hipLaunchKernelGGL((skinny_bf16x2_kernel<3, 3>), grid, block, 0, s, g);
-        else hipLaunchKernelGGL((skinny_bf16x2_kernel<4, 3>), grid, block, 0, s, g);
-    } else {
-        if (mt == 1) hipLaunchKernelGGL((skinny_bf16x2_kernel<1, 2>), grid, block, 0, s, g);
-        else if (mt == 2) hipLaunchKernelGGL((skinny_bf16x2_kernel<2, 2>), grid, block, 0, s, g);
-        else if (mt == 3) hipLaunchKernelGGL((skinny_bf16x2_kernel<3, 2>), grid, block, 0, s, g);
-        else hipLaunchKernelGGL((skinny_bf16x2_kernel<4, 2>), grid, block, 0, s, g);
-    }
+    if (plane_lo2) dispatch_mt<4>(mt, [&](auto MT) { hipLaunchKernelGGL((skinny_bf16x2_kernel<MT(), 3>), grid, block, 0, s, g); });   // three-way split: fp32-level accuracy
+    else dispatch_mt<4>(mt, [&](auto MT) { hipLaunchKernelGGL((skinny_bf16x2_kernel<MT(), 2>), grid, block, 0, s, g); });
     DLCO_HIP(hipGetLastError());
     splitk_reduce_f32(slab, ks, M, N, C, ldc, alpha, 0.f, E1, b1, E2, b2, s);
     return true;
@@ -778,27 +668,15 @@ bool skinny_product_sym(const float *X, long ldx, int M, const float *Gpacked, i
     if (F % 128 != 0 || nt < 1 || nt > 64 || M < 1 || mt > 5 || (mt >= 4 && plane_lo2)) return false;
     if (ldx % 4 != 0 || (reinterpret_cast<uintptr_t>(X) & 15) != 0 || (reinterpret_cast<uintptr_t>(Gpacked) & 15) != 0) return false;
     if ((planes_ready || emit_planes) && plane_lo2) return false;       // the carried planes are the two-way ones
-    const long total = (long)(F / 16) * mt * 64;
-    if (!planes_ready)
-        hipLaunchKernelGGL(split_x_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, s, X, ldx, M, mt, F,
-                           static_cast<bf16x8 *>(plane_hi), static_cast<bf16x8 *>(plane_lo), static_cast<bf16x8 *>(plane_lo2));
+    if (!planes_ready) split_planes_bf16(X, ldx, M, F, plane_hi, plane_lo, plane_lo2, s);
     SymDev g;
     g.M = M; g.K = F;
     g.nt = nt; g.lb = 2;
     while ((1 << g.lb) < nt) g.lb++;
     g.xhi = static_cast<const bf16x8 *>(plane_hi); g.xlo = static_cast<const bf16x8 *>(plane_lo); g.xlo2 = static_cast<const bf16x8 *>(plane_lo2);
     g.G = Gpacked; g.slab = slab;
-    if (plane_lo2) {
-        if (mt == 1) launch_sym<1, 3>(g, s);
-        else if (mt == 2) launch_sym<2, 3>(g, s);
-        else launch_sym<3, 3>(g, s);
-    } else {
-        if (mt == 1) launch_sym<1, 2>(g, s);
-        else if (mt == 2) launch_sym<2, 2>(g, s);
-        else if (mt == 3) launch_sym<3, 2>(g, s);
-        else if (mt == 4) launch_sym<4, 2>(g, s);
-        else launch_sym<5, 2>(g, s);
-    }
+    if (plane_lo2) dispatch_mt<3>(mt, [&](auto MT) { launch_sym<MT(), 3>(g, s); });
+    else dispatch_mt<5>(mt, [&](auto MT) { launch_sym<MT(), 2>(g, s); });
     DLCO_HIP(hipGetLastError());
     if (emit_planes && ldc % 4 == 0 && (reinterpret_cast<uintptr_t>(C) & 15) == 0) {
         // the product kernel has read the planes of X: they now receive the planes of the result, rows up to 32 mt zeroed by

@@ -24,29 +24,19 @@
 // through in passes of 96: a later pass continues the running sums of the one before, so the order over q is kept.
 // SLAB = true (the training batch in the bf16 variant, a few hundred rows): K is split over gridDim.y and the raw
 // partial projections go to a [slice][M][ldn] slab that sqdist_from_proj sums in slice order.
+// The split, the MFMA term order, the plane layout and the LDS geometry are those of the tracker's products
+// (split_bf16_dev.hpp): a projected distance and a filter product round alike.
 #include "dlco_internal.hpp"
+#include "split_bf16_dev.hpp"
 
 #include <algorithm>
 
 namespace dlco {
 
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-
-// kernels_bf16x2.hip: plane element ((k16 * MT + tile) * 64 + lane) * 8 + j = X[tile*32 + (lane&31)][k16*16 + 8*(lane>>5) + j]
-void split_planes_bf16(const float *X, long ldx, int M, int K, void *hi, void *lo, void *lo2, hipStream_t s);
-
 namespace {
 
-constexpr int PK_KC = 64;                  // chunk depth (floats)
-constexpr int PK_RS = PK_KC + 4;           // LDS row stride of the D image (floats): conflict-free 32-byte fragment reads
-constexpr int PK_T = 768;                  // 8 compute + 4 loader waves
-constexpr int PK_ROWS = 128;               // D rows per workgroup
-constexpr int PK_GBYTES = PK_ROWS * PK_RS * 4;
-__host__ __device__ constexpr int pk_abytes(int mt, int ns) { return ns * mt * 4 * 64 * 16; }
 // two images of each operand; the epilogue reuses the space for the K-half exchange (16 KB per row tile) and the [q][n] image (16 KB per tile)
-inline size_t pk_lds_bytes(int mt, int ns) { return std::max((size_t)2 * (PK_GBYTES + pk_abytes(mt, ns)), (size_t)32768 * mt); }
+inline size_t project_lds_bytes(int mt, int ns) { return std::max(sb_lds_bytes(mt, ns), (size_t)32768 * mt); }
 
 struct ProjDev {
     int M, K, nrows;              // rows of W in this pass (<= 32 MT), F, rows of D to project
@@ -61,21 +51,20 @@ struct ProjDev {
 };
 
 template <int MT, int NS, bool PAIR, bool SLAB>
-__global__ __launch_bounds__(PK_T) void project_rows_kernel(ProjDev g)
+__global__ __launch_bounds__(SB_T) void project_rows_kernel(ProjDev g)
 {
     extern __shared__ __attribute__((aligned(16))) char lds_raw[];
-    constexpr int ABYTES = pk_abytes(MT, NS);
+    constexpr int ABYTES = sb_abytes(MT, NS);
     constexpr int APLANE = MT * 256;                          // 16-byte entries of one plane's chunk slice
-    constexpr int AENT = NS * APLANE;
-    constexpr int NA = (AENT + 255) / 256;                     // A entries per loader thread and chunk
+    constexpr int NA = NS * MT;                                // A entries per loader thread and chunk
     constexpr int NSTAGE = PAIR ? 1 : 2;                       // chunks a loader keeps in flight in registers
-    float *gb0 = reinterpret_cast<float *>(lds_raw), *gb1 = reinterpret_cast<float *>(lds_raw + PK_GBYTES);
-    bf16x8 *ab0 = reinterpret_cast<bf16x8 *>(lds_raw + 2 * PK_GBYTES), *ab1 = reinterpret_cast<bf16x8 *>(lds_raw + 2 * PK_GBYTES + ABYTES);
+    float *gb0 = reinterpret_cast<float *>(lds_raw), *gb1 = reinterpret_cast<float *>(lds_raw + SB_GBYTES);
+    bf16x8 *ab0 = reinterpret_cast<bf16x8 *>(lds_raw + 2 * SB_GBYTES), *ab1 = reinterpret_cast<bf16x8 *>(lds_raw + 2 * SB_GBYTES + ABYTES);
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const int j0 = blockIdx.x * PK_ROWS;
+    const int j0 = blockIdx.x * SB_ROWS;
     const int kslice = g.K / (int)gridDim.y;                  // host: a multiple of 64
     const int kbeg = blockIdx.y * kslice;
-    const int nchunks = kslice / PK_KC;
+    const int nchunks = kslice / SB_KC;
     const int st0 = kbeg / 16;
 
     if (wave >= 8) {
@@ -94,10 +83,7 @@ __global__ __launch_bounds__(PK_T) void project_rows_kernel(ProjDev g)
             rp[u] = g.D + row * g.ldd + kbeg + 4 * gc4;
             if (PAIR) rq[u] = g.D + (long)g.ids2[j] * g.ldd + kbeg + 4 * gc4;
         }
-        const int plane_bytes = MT * 32 * g.K * 2;
-        const __amdgpu_buffer_rsrc_t rs_hi = __builtin_amdgcn_make_buffer_rsrc(const_cast<bf16x8 *>(g.xhi), 0, plane_bytes, 0x00020000);
-        const __amdgpu_buffer_rsrc_t rs_lo = __builtin_amdgcn_make_buffer_rsrc(const_cast<bf16x8 *>(NS >= 2 ? g.xlo : g.xhi), 0, plane_bytes, 0x00020000);
-        const __amdgpu_buffer_rsrc_t rs_lo2 = __builtin_amdgcn_make_buffer_rsrc(const_cast<bf16x8 *>(NS == 3 ? g.xlo2 : g.xhi), 0, plane_bytes, 0x00020000);
+        const PlaneRsrc rs = make_plane_rsrc<MT, NS>(g.xhi, g.xlo, g.xlo2, g.K);
         // D rows come from HBM and are requested three iterations ahead (two register sets); the W planes come from L2
         // and are requested two ahead (one set) - and BEFORE the D request of the same iteration, so that waiting for
         // them (a wave's loads retire in order) never waits for the youngest D chunk.
@@ -108,17 +94,14 @@ __global__ __launch_bounds__(PK_T) void project_rows_kernel(ProjDev g)
         auto gload = [&](int c, GStage &st) {
 #pragma unroll
             for (int u = 0; u < 8; u++) {
-                st.gq[u] = *reinterpret_cast<const f32x4 *>(rp[u] + c * PK_KC);
-                if (PAIR) st.gr[u] = *reinterpret_cast<const f32x4 *>(rq[u] + c * PK_KC);
+                st.gq[u] = *reinterpret_cast<const f32x4 *>(rp[u] + c * SB_KC);
+                if (PAIR) st.gr[u] = *reinterpret_cast<const f32x4 *>(rq[u] + c * SB_KC);
             }
         };
         auto aload = [&](int c, AStage &st) {
-            const int a0 = (st0 + 4 * c) * MT * 64 * 16;       // byte offset of the chunk's slice inside a plane
+            const int a0 = slice_bytes<MT>(st0 + 4 * c);
 #pragma unroll
-            for (int v = 0; v < NA; v++) {
-                const __amdgpu_buffer_rsrc_t &ra = (v / MT == 0) ? rs_hi : ((v / MT == 1) ? rs_lo : rs_lo2);
-                st.aq[v] = __builtin_bit_cast(bf16x8, __builtin_amdgcn_raw_buffer_load_b128(ra, 16 * lt, a0 + (v % MT) * 256 * 16, 0));
-            }
+            for (int v = 0; v < NA; v++) st.aq[v] = load_slice_entry<MT>(rs, a0, lt, v);
         };
         auto gstore = [&](int buf, const GStage &st, const AStage &at) {
             float *gb = buf ? gb1 : gb0;
@@ -127,7 +110,7 @@ __global__ __launch_bounds__(PK_T) void project_rows_kernel(ProjDev g)
             for (int u = 0; u < 8; u++) {
                 f32x4 v = st.gq[u];
                 if (PAIR) v -= st.gr[u];                       // Dist = Desc1 - Desc2, src/comp-uprjdists.cpp:327
-                *reinterpret_cast<f32x4 *>(gb + (grow + 16 * u) * PK_RS + 4 * gc4) = v;
+                *reinterpret_cast<f32x4 *>(gb + (grow + 16 * u) * SB_RS + 4 * gc4) = v;
             }
 #pragma unroll
             for (int v = 0; v < NA; v++) ab[lt + 256 * v] = at.aq[v];
@@ -181,44 +164,21 @@ __global__ __launch_bounds__(PK_T) void project_rows_kernel(ProjDev g)
     for (int a = 0; a < MT; a++)
 #pragma unroll
         for (int r = 0; r < 16; r++) acc[a][r] = 0.f;
-
-    struct Frag { f32x4 g0, g1; bf16x8 a[NS][MT]; };
-    auto fetch = [&](const float *gb, const bf16x8 *ab, int q, Frag &f) {
-        const float *p = gb + (nt * 32 + lc) * PK_RS + 16 * q + 8 * lh;
+    auto fetch = [&](const float *gb, const bf16x8 *ab, int q, Frag<MT, NS> &f) {
+        const float *p = gb + (nt * 32 + lc) * SB_RS + 16 * q + 8 * lh;
         f.g0 = *reinterpret_cast<const f32x4 *>(p);
         f.g1 = *reinterpret_cast<const f32x4 *>(p + 4);
 #pragma unroll
         for (int n = 0; n < NS; n++)
 #pragma unroll
-            for (int t = 0; t < MT; t++) f.a[n][t] = ab[n * APLANE + (q * MT + t) * 64 + lane];
+            for (int t = 0; t < MT; t++) f.a[n][t] = ab[n * APLANE + plane_entry(q, MT, t, lane)];
     };
-    auto multiply = [&](const Frag &f) {
+    auto multiply = [&](const Frag<MT, NS> &f) {              // a lambda of the kernel: see Frag
         bf16x8 bh, bl, bl2;
-#pragma unroll
-        for (int j = 0; j < 8; j++) {
-            const float v = j < 4 ? f.g0[j & 3] : f.g1[j & 3];
-            bh[j] = (__bf16)v;
-            if (NS >= 2) {
-                const float r1 = v - (float)bh[j];
-                bl[j] = (__bf16)r1;
-                if (NS == 3) bl2[j] = (__bf16)(r1 - (float)bl[j]);
-            }
-        }
-#pragma unroll
-        for (int t = 0; t < MT; t++) {
-            if (NS == 3) {                                   // smallest terms first
-                acc[t] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(f.a[0][t], bl2, acc[t], 0, 0, 0);
-                acc[t] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(f.a[NS - 1][t], bh, acc[t], 0, 0, 0);
-                acc[t] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(f.a[NS >= 2 ? 1 : 0][t], bl, acc[t], 0, 0, 0);
-            }
-            if (NS >= 2) {
-                acc[t] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(f.a[0][t], bl, acc[t], 0, 0, 0);
-                acc[t] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(f.a[NS >= 2 ? 1 : 0][t], bh, acc[t], 0, 0, 0);
-            }
-            acc[t] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(f.a[0][t], bh, acc[t], 0, 0, 0);
-        }
+        split_frag<NS>(f.g0, f.g1, bh, bl, bl2);
+        mfma_split_terms<MT, NS>(f.a[0], f.a[NS >= 2 ? 1 : 0], f.a[NS - 1], bh, bl, bl2, acc);
     };
-    Frag fa;
+    Frag<MT, NS> fa;
     __syncthreads();
     for (int c = 0; c < nchunks; c++) {
         const float *gb = (c & 1) ? gb1 : gb0;
@@ -251,17 +211,17 @@ __global__ __launch_bounds__(PK_T) void project_rows_kernel(ProjDev g)
                     const int n = j0 + nt * 32 + lc;
                     if (q < g.M && n < g.nrows) g.out[((long)blockIdx.y * g.M + q) * g.ldn + n] = sum;
                 } else {
-                    P[q * PK_ROWS + nt * 32 + lc] = sum;
+                    P[q * SB_ROWS + nt * 32 + lc] = sum;
                 }
             }
     }
     if (SLAB) return;
     __syncthreads();
     // P2: squares added row after row in fp32, like cv::reduce(dim 0, SUM) after cv::pow (src/pj-learn.cpp:346-347)
-    if (tid < PK_ROWS && j0 + tid < g.nrows) {
+    if (tid < SB_ROWS && j0 + tid < g.nrows) {
         float d = g.accumulate ? g.out[j0 + tid] : 0.f;
         for (int q = 0; q < g.M; q++) {
-            const float p = P[q * PK_ROWS + tid];
+            const float p = P[q * SB_ROWS + tid];
             d += p * p;
         }
         g.out[j0 + tid] = d;
@@ -271,17 +231,27 @@ __global__ __launch_bounds__(PK_T) void project_rows_kernel(ProjDev g)
 template <int MT, int NS, bool PAIR, bool SLAB>
 void launch_project(const ProjDev &g, dim3 grid, hipStream_t s)
 {
-    const size_t lds = pk_lds_bytes(MT, NS);
+    const size_t lds = project_lds_bytes(MT, NS);
     ensure_dynamic_lds(reinterpret_cast<const void *>(project_rows_kernel<MT, NS, PAIR, SLAB>), (int)lds);
-    hipLaunchKernelGGL((project_rows_kernel<MT, NS, PAIR, SLAB>), grid, dim3(PK_T), lds, s, g);
+    hipLaunchKernelGGL((project_rows_kernel<MT, NS, PAIR, SLAB>), grid, dim3(SB_T), lds, s, g);
 }
 
-template <int NS, bool PAIR, bool SLAB>
-void launch_project_mt(int mt, const ProjDev &g, dim3 grid, hipStream_t s)
+// splits the m <= 96 rows of W into the planes and launches the pass over them: bf16 selects NS = 1, ids2 the pair mode
+template <bool SLAB>
+void split_and_project(const float *W, long ldw, int m, int F, void *plane_hi, void *plane_lo, void *plane_lo2, bool bf16, ProjDev g,
+                       dim3 grid, hipStream_t s)
 {
-    if (mt == 1) launch_project<1, NS, PAIR, SLAB>(g, grid, s);
-    else if (mt == 2) launch_project<2, NS, PAIR, SLAB>(g, grid, s);
-    else launch_project<3, NS, PAIR, SLAB>(g, grid, s);
+    split_planes_bf16(W, ldw, m, F, plane_hi, plane_lo, bf16 ? nullptr : plane_lo2, s);
+    g.M = m; g.K = F;
+    g.xhi = static_cast<const bf16x8 *>(plane_hi); g.xlo = static_cast<const bf16x8 *>(plane_lo); g.xlo2 = static_cast<const bf16x8 *>(plane_lo2);
+    dispatch_mt<3>((m + 31) / 32, [&](auto MT) {
+        if (bf16) {
+            if (g.ids2) launch_project<MT(), 1, true, SLAB>(g, grid, s); else launch_project<MT(), 1, false, SLAB>(g, grid, s);
+        } else {
+            if (g.ids2) launch_project<MT(), 3, true, SLAB>(g, grid, s); else launch_project<MT(), 3, false, SLAB>(g, grid, s);
+        }
+    });
+    DLCO_HIP(hipGetLastError());
 }
 
 }  // namespace
@@ -296,21 +266,13 @@ bool project_rows_sqdist(const float *W, long ldw, int r, const float *D, long l
     if (r < 1 || nrows < 1 || F % 64 != 0 || ldd % 4 != 0 || ldw % 4 != 0 || (reinterpret_cast<uintptr_t>(D) & 15) != 0 ||
         (reinterpret_cast<uintptr_t>(W) & 15) != 0 || (long)96 * F * 2 >= (1L << 31))
         return false;
-    const dim3 grid((nrows + PK_ROWS - 1) / PK_ROWS, 1);
+    const dim3 grid((nrows + SB_ROWS - 1) / SB_ROWS, 1);
+    ProjDev g{};
+    g.nrows = nrows; g.D = D; g.ldd = ldd; g.ids = ids; g.ids2 = ids2; g.row0 = row0;
+    g.out = dist; g.ldn = 0;
     for (int q0 = 0; q0 < r; q0 += 96) {
-        const int m = std::min(96, r - q0), mt = (m + 31) / 32;
-        split_planes_bf16(W + (long)q0 * ldw, ldw, m, F, plane_hi, plane_lo, bf16 ? nullptr : plane_lo2, s);
-        ProjDev g;
-        g.M = m; g.K = F; g.nrows = nrows;
-        g.xhi = static_cast<const bf16x8 *>(plane_hi); g.xlo = static_cast<const bf16x8 *>(plane_lo); g.xlo2 = static_cast<const bf16x8 *>(plane_lo2);
-        g.D = D; g.ldd = ldd; g.ids = ids; g.ids2 = ids2; g.row0 = row0;
-        g.out = dist; g.ldn = 0; g.accumulate = q0 > 0 ? 1 : 0;
-        if (bf16) {
-            if (ids2) launch_project_mt<1, true, false>(mt, g, grid, s); else launch_project_mt<1, false, false>(mt, g, grid, s);
-        } else {
-            if (ids2) launch_project_mt<3, true, false>(mt, g, grid, s); else launch_project_mt<3, false, false>(mt, g, grid, s);
-        }
-        DLCO_HIP(hipGetLastError());
+        g.accumulate = q0 > 0 ? 1 : 0;
+        split_and_project<false>(W + (long)q0 * ldw, ldw, std::min(96, r - q0), F, plane_hi, plane_lo, plane_lo2, bf16, g, grid, s);
     }
     return true;
 }
@@ -325,20 +287,10 @@ bool project_rows_slab(const float *W, long ldw, int r, const float *D, long ldd
     if (r < 1 || r > 96 || nrows < 1 || ksplit < 1 || F % (64 * ksplit) != 0 || ldd % 4 != 0 || ldw % 4 != 0 || !ids ||
         (reinterpret_cast<uintptr_t>(D) & 15) != 0 || (reinterpret_cast<uintptr_t>(W) & 15) != 0 || (long)96 * F * 2 >= (1L << 31))
         return false;
-    const int mt = (r + 31) / 32;
-    split_planes_bf16(W, ldw, r, F, plane_hi, plane_lo, bf16 ? nullptr : plane_lo2, s);
-    ProjDev g;
-    g.M = r; g.K = F; g.nrows = nrows;
-    g.xhi = static_cast<const bf16x8 *>(plane_hi); g.xlo = static_cast<const bf16x8 *>(plane_lo); g.xlo2 = static_cast<const bf16x8 *>(plane_lo2);
-    g.D = D; g.ldd = ldd; g.ids = ids; g.ids2 = ids2; g.row0 = 0;
+    ProjDev g{};
+    g.nrows = nrows; g.D = D; g.ldd = ldd; g.ids = ids; g.ids2 = ids2; g.row0 = 0;
     g.out = slab; g.ldn = ldn; g.accumulate = 0;
-    const dim3 grid((nrows + PK_ROWS - 1) / PK_ROWS, ksplit);
-    if (bf16) {
-        if (ids2) launch_project_mt<1, true, true>(mt, g, grid, s); else launch_project_mt<1, false, true>(mt, g, grid, s);
-    } else {
-        if (ids2) launch_project_mt<3, true, true>(mt, g, grid, s); else launch_project_mt<3, false, true>(mt, g, grid, s);
-    }
-    DLCO_HIP(hipGetLastError());
+    split_and_project<true>(W, ldw, r, F, plane_hi, plane_lo, plane_lo2, bf16, g, dim3((nrows + SB_ROWS - 1) / SB_ROWS, ksplit), s);
     return true;
 }
 

@@ -22,12 +22,9 @@
 // test still use the matrix itself, so a stale Y could cost passes, never a wrong result.
 #include "dlco_internal.hpp"
 #include "rank_coeff_dev.hpp"
+#include "split_bf16_dev.hpp"
 
 namespace dlco {
-
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef float f32x4 __attribute__((ext_vector_type(4)));
 
 namespace {
 
@@ -169,9 +166,7 @@ __global__ __launch_bounds__(64 * MT * KS) void rank_first_term_kernel(RankUpdDe
         for (int j = 0; j < 8; j++) { h[j] = (__bf16)0.f; l[j] = (__bf16)0.f; }       // rows >= m of a tile: zero planes
     }
     if (g.hi) {
-        // plane entry ((k16 * MT + tile) * 64 + pl): row tile*32 + (pl & 31), columns k16*16 + 8 (pl >> 5) .. + 7
-        const int col = f0 + ec8;
-        const long t = ((long)(col >> 4) * MT + (erow >> 5)) * 64 + (erow & 31) + 32 * ((col >> 3) & 1);
+        const long t = plane_entry_at(MT, erow, (f0 + ec8) >> 3);
         g.hi[t] = h;
         g.lo[t] = l;
     }

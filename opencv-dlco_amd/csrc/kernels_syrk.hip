@@ -16,16 +16,13 @@
 // the same two new kernels (syrk_round_rows_kernel).  Epilogue everywhere: dual-average update in registers.
 #include "dlco_internal.hpp"
 #include "rank_coeff_dev.hpp"
+#include "split_bf16_dev.hpp"
 
 #include <mutex>
 #include <type_traits>
 #include <vector>
 
 namespace dlco {
-
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
 
 namespace {
 
@@ -282,13 +279,8 @@ __global__ __launch_bounds__(256) void syrk_split_rows_kernel(const float *D, lo
 #pragma unroll
     for (int j = 0; j < 8; j++)
 #pragma unroll
-        for (int op = 0; op < 2; op++) {
-            const float x = op == 0 ? v[j] * wv[j] : v[j];              // w_k x_k for the A operand
-            const __bf16 h = (__bf16)x;
-            const float r1 = x - (float)h;
-            const __bf16 m = (__bf16)r1;
-            e[op][0][j] = h; e[op][1][j] = m; e[op][2][j] = (__bf16)(r1 - (float)m);
-        }
+        for (int op = 0; op < 2; op++)                                  // w_k x_k for the A operand
+            split_f32<3>(op == 0 ? v[j] * wv[j] : v[j], j, e[op][0], e[op][1], e[op][2]);
 #pragma unroll
     for (int op = 0; op < 2; op++) {
         bf16x8 *img = reinterpret_cast<bf16x8 *>(planes + (((long)op * nkb + kb) * nt + ct) * PL_IMG);
