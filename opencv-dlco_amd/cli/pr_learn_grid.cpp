@@ -12,11 +12,9 @@
 // Defaults are pr-learn's (mu 0.025, gamma 0.10, maxdim 640, 5 000 000 iterations, LogStep 100 000,
 // seed 2215); -name defaults to the file name of src_h5_dist_file without its extension.
 #include "../../include/dlco.h"
-#include "dlco_io.hpp"
+#include "pr_cli.hpp"
 #include "pr_logstep.hpp"
 
-#include <chrono>
-#include <cstdlib>
 #include <iostream>
 #include <set>
 #include <sstream>
@@ -50,10 +48,7 @@ static void append_text(const std::string &path, const std::string &text)
 int main(int argc, char **argv)
 {
     std::vector<float> mus{0.025f}, gammas{0.10f};          // pr-learn's defaults, src/pr-learn.cpp:78-79
-    int MaxDim = 640;
-    unsigned nIter = 5000000, LogStep = 100000;
-    unsigned long long seed = 2215;
-    int device = 0;
+    pr_cli::CommonFlags f;
     bool help = false, npy = false;
     std::string tag;
     const char *flt = nullptr, *src = nullptr, *dst = nullptr;
@@ -72,11 +67,7 @@ int main(int argc, char **argv)
                 continue;
             }
             if (std::strcmp(argv[i], "-name") == 0 && has_val) { tag = argv[++i]; continue; }
-            if (std::strcmp(argv[i], "-maxdim") == 0 && has_val) { MaxDim = atoi(argv[++i]); continue; }
-            if (std::strcmp(argv[i], "-iters") == 0 && has_val) { nIter = (unsigned)atoi(argv[++i]); continue; }
-            if (std::strcmp(argv[i], "-logstep") == 0 && has_val) { LogStep = (unsigned)atoi(argv[++i]); continue; }
-            if (std::strcmp(argv[i], "-seed") == 0 && has_val) { seed = strtoull(argv[++i], nullptr, 10); continue; }
-            if (std::strcmp(argv[i], "-device") == 0 && has_val) { device = atoi(argv[++i]); continue; }
+            if (f.parse(argc, argv, i)) continue;
             cout << "ERROR: Invalid " << argv[i] << " option." << endl;
             help = true;
         } else {
@@ -86,7 +77,7 @@ int main(int argc, char **argv)
         }
     }
     if (!flt || !src || !dst) help = true;
-    if (LogStep < 1) { cout << "ERROR: -logstep must be at least 1." << endl; help = true; }
+    if (f.LogStep < 1) { cout << "ERROR: -logstep must be at least 1." << endl; help = true; }
 
     // the settings (mu-major) and their file names
     struct Setting { float mu, gamma; std::string log, out; pr_log::Best best; std::string text; };
@@ -126,31 +117,22 @@ int main(int argc, char **argv)
         return 1;
     }
     const int G = (int)set.size();
-    cout << "Grid: " << mus.size() << " mu x " << gammas.size() << " gamma = " << G << " settings, maxdim: " << MaxDim << " nIters: " << nIter
+    cout << "Grid: " << mus.size() << " mu x " << gammas.size() << " gamma = " << G << " settings, maxdim: " << f.MaxDim << " nIters: " << f.nIter
          << endl;
 
     try {
         mkdir(dst, 0777);
-        std::vector<size_t> pshape, rshape, dshape, lshape;
-        std::vector<float> PRParams, RingParams, dists;
-        std::vector<uint8_t> labels;
-        dlco_io::read_dataset<float>(flt, "PRParams", pshape, PRParams);
-        dlco_io::read_dataset<float>(flt, "RingParams", rshape, RingParams);      // read like pr-learn; not used by this stage
-        dlco_io::read_dataset<float>(src, "Distance", dshape, dists);
-        dlco_io::read_dataset<uint8_t>(src, "Label", lshape, labels);
-        if (dshape.size() != 2 || pshape.size() != 2) throw std::runtime_error("Distance and PRParams must be 2-D datasets");
-        const int nDists = (int)dshape[0], FeatDim = (int)dshape[1];
-        if ((int)labels.size() < nDists) throw std::runtime_error("Label has fewer rows than Distance");
-        if ((int)pshape[0] < 8 * FeatDim) throw std::runtime_error("PRParams needs 8 rows per column of Distance");
+        pr_cli::Inputs in = pr_cli::load(flt, src, nullptr);
+        const int nDists = in.nDists, FeatDim = in.FeatDim;
 
         dlco_pr_ctx *ctx = nullptr;
-        if (dlco_pr_create(&ctx, FeatDim, nDists, set[0].mu, set[0].gamma, seed, device) != DLCO_OK) throw std::runtime_error(dlco_pr_last_error(nullptr));
-        if (dlco_pr_set_data(ctx, dists.data(), labels.data()) != DLCO_OK) throw std::runtime_error(dlco_pr_last_error(ctx));
-        dists.clear(); dists.shrink_to_fit();
+        if (dlco_pr_create(&ctx, FeatDim, nDists, set[0].mu, set[0].gamma, f.seed, f.device) != DLCO_OK) throw std::runtime_error(dlco_pr_last_error(nullptr));
+        if (dlco_pr_set_data(ctx, in.dists.data(), in.labels.data()) != DLCO_OK) throw std::runtime_error(dlco_pr_last_error(ctx));
+        in.dists.clear(); in.dists.shrink_to_fit();
         std::vector<float> mu(G), gamma(G);
         for (int k = 0; k < G; k++) { mu[k] = set[k].mu; gamma[k] = set[k].gamma; }
         dlco_pr_grid *grid = nullptr;
-        if (dlco_pr_grid_create(&grid, ctx, G, mu.data(), gamma.data(), seed) != DLCO_OK) throw std::runtime_error(dlco_pr_grid_last_error(nullptr));
+        if (dlco_pr_grid_create(&grid, ctx, G, mu.data(), gamma.data(), f.seed) != DLCO_OK) throw std::runtime_error(dlco_pr_grid_last_error(nullptr));
         int32_t n_pos = 0, n_pos_trn = 0, n_neg = 0, n_neg_trn = 0;
         dlco_pr_get_index(ctx, &n_pos, &n_pos_trn, &n_neg, &n_neg_trn);
         char name[256];
@@ -164,7 +146,7 @@ int main(int argc, char **argv)
         dlco_io::term_progress(1.0, tick, &progress);
         for (Setting &s : set) {
             std::ostringstream o;
-            pr_log::config(o, s.mu, s.gamma, MaxDim, nIter);
+            pr_log::config(o, s.mu, s.gamma, f.MaxDim, f.nIter);
             o << "Load PRParams." << endl;
             o << "Load RingParams." << endl;
             pr_log::loaded(o, nDists, FeatDim);
@@ -179,48 +161,44 @@ int main(int argc, char **argv)
         // the LogStep schedule of pr-learn: lines at t = LogStep, 2 LogStep, ... <= nIter
         std::vector<float> w((size_t)G * FeatDim), loss(G), regul(G);
         std::vector<int32_t> nnz(G);
-        unsigned t_done = 0;
-        unsigned long long next_log = LogStep;
-        auto train_start = std::chrono::steady_clock::now();
-        while (t_done <= nIter) {
-            const unsigned upto = next_log <= nIter ? (unsigned)next_log + 1 : nIter + 1;
-            if (dlco_pr_grid_steps(grid, upto - t_done) != DLCO_OK) throw std::runtime_error(dlco_pr_grid_last_error(grid));
-            t_done = upto;
-            if (next_log > nIter) break;
-            uint32_t tt = 0;
-            dlco_pr_grid_get_state(grid, &tt, w.data(), nullptr);   // also synchronises
-            const double ttime = std::chrono::duration<double>(std::chrono::steady_clock::now() - train_start).count();
-            const auto v0 = std::chrono::steady_clock::now();
-            if (dlco_pr_grid_validate(grid, loss.data(), regul.data(), nnz.data()) != DLCO_OK) throw std::runtime_error(dlco_pr_grid_last_error(grid));
-            const double vtime = std::chrono::duration<double>(std::chrono::steady_clock::now() - v0).count();
-            const unsigned t = (unsigned)next_log;
-            std::vector<int32_t> bests;
-            for (int k = 0; k < G; k++) {
-                Setting &s = set[k];
-                if (pr_log::objective(s.text, s.best, t, loss[k], regul[k], nnz[k], w.data() + (size_t)k * FeatDim, (size_t)FeatDim, ttime, vtime))
-                    bests.push_back(k);
-            }
-            if (!bests.empty()) {                                   // ComputePRStats of every new best in one call
-                const int nb = (int)bests.size();
-                std::vector<int32_t> nPR(nb), Dim(nb), nzDim(nb);
-                std::vector<float> FPR95(nb, -1.f);
-                std::vector<double> AUC(nb, 0.0);
-                if (dlco_pr_grid_stats(grid, bests.data(), nb, nullptr, PRParams.data(), (int32_t)pshape[0], (int32_t)pshape[1], 8, -1, nPR.data(),
-                                       Dim.data(), nzDim.data(), FPR95.data(), AUC.data()) != DLCO_OK)
+        pr_cli::logstep_schedule(
+            f.nIter, f.LogStep,
+            [&](unsigned n) {
+                if (dlco_pr_grid_steps(grid, n) != DLCO_OK) throw std::runtime_error(dlco_pr_grid_last_error(grid));
+            },
+            [&](unsigned t, pr_cli::Clock::time_point train_start) {
+                uint32_t tt = 0;
+                dlco_pr_grid_get_state(grid, &tt, w.data(), nullptr);   // also synchronises
+                const double ttime = pr_cli::seconds_since(train_start);
+                const auto v0 = pr_cli::Clock::now();
+                if (dlco_pr_grid_validate(grid, loss.data(), regul.data(), nnz.data()) != DLCO_OK)
                     throw std::runtime_error(dlco_pr_grid_last_error(grid));
-                for (int i = 0; i < nb; i++) {
-                    Setting &s = set[bests[i]];
-                    const bool saved = pr_log::saves(Dim[i], MaxDim);
-                    if (saved) dlco_io::append_row_f32(s.out, "w", s.best.w_Best.data(), (size_t)FeatDim);
-                    pr_log::stat(s.text, nPR[i], nzDim[i], Dim[i], MaxDim, AUC[i], FPR95[i], saved);
+                const double vtime = pr_cli::seconds_since(v0);
+                std::vector<int32_t> bests;
+                for (int k = 0; k < G; k++) {
+                    Setting &s = set[k];
+                    if (pr_log::objective(s.text, s.best, t, loss[k], regul[k], nnz[k], w.data() + (size_t)k * FeatDim, (size_t)FeatDim, ttime, vtime))
+                        bests.push_back(k);
                 }
-            }
-            for (Setting &s : set) { append_text(s.log, s.text); s.text.clear(); }
-            std::printf("Grid: %u  Best: %i of %i  Ttime: %.4f Vtime: %.4f\n", t, (int)bests.size(), G, ttime, vtime);
-            cout << std::flush;
-            next_log += LogStep;
-            train_start = std::chrono::steady_clock::now();
-        }
+                if (!bests.empty()) {                                   // ComputePRStats of every new best in one call
+                    const int nb = (int)bests.size();
+                    std::vector<int32_t> nPR(nb), Dim(nb), nzDim(nb);
+                    std::vector<float> FPR95(nb, -1.f);
+                    std::vector<double> AUC(nb, 0.0);
+                    if (dlco_pr_grid_stats(grid, bests.data(), nb, nullptr, in.PRParams.data(), (int32_t)in.pshape[0], (int32_t)in.pshape[1], 8, -1,
+                                           nPR.data(), Dim.data(), nzDim.data(), FPR95.data(), AUC.data()) != DLCO_OK)
+                        throw std::runtime_error(dlco_pr_grid_last_error(grid));
+                    for (int i = 0; i < nb; i++) {
+                        Setting &s = set[bests[i]];
+                        const bool saved = pr_log::saves(Dim[i], f.MaxDim);
+                        if (saved) dlco_io::append_row_f32(s.out, "w", s.best.w_Best.data(), (size_t)FeatDim);
+                        pr_log::stat(s.text, nPR[i], nzDim[i], Dim[i], f.MaxDim, AUC[i], FPR95[i], saved);
+                    }
+                }
+                for (Setting &s : set) { append_text(s.log, s.text); s.text.clear(); }
+                std::printf("Grid: %u  Best: %i of %i  Ttime: %.4f Vtime: %.4f\n", t, (int)bests.size(), G, ttime, vtime);
+                cout << std::flush;
+            });
         dlco_pr_grid_destroy(grid);
         dlco_pr_destroy(ctx);
     } catch (const std::exception &e) {

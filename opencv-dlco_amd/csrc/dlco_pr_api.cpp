@@ -12,67 +12,100 @@
 
 using namespace dlco;
 
-struct dlco_pr_ctx {
-    int F = 0, N = 0, device = 0;
-    float mu = 0.025f, gamma = 0.10f;
-    hipStream_t stream = nullptr;
-    std::string err;
-    DevBuf<float> dists, w, df, vdist, hrows, wtmp;
+// What training, validation and statistics read and never write: Distance [N,F], Label [N], the index split and
+// the validation row ids of one context.
+struct PrData {
+    int F = 0, N = 0;
+    bool have = false;
+    DevBuf<float> dists;
     DevBuf<uint8_t> labels_dev;
-    DevBuf<int32_t> val_pos_ids, val_neg_ids, win_pos, win_neg;
-    DevBuf<double> dscal;
-    std::vector<uint8_t> labels;
-    std::vector<int32_t> h_pos, h_neg;
+    DevBuf<int32_t> val_pos_ids, val_neg_ids;
     PairIndex idx;
-    CvRng rng{2215};
-    uint32_t t = 0;
-    bool have_data = false;
-    RocWork *roc = nullptr;
-    size_t win_cap = 0;
+    int npv() const { return (int)idx.pos.size() - idx.n_pos_trn; }
+    int nnv() const { return (int)idx.neg.size() - idx.n_neg_trn; }
 };
 
-// G settings (mu[k], gamma[k]) trained on the data of `src` (not copied) with a sampler of their own.
-// w and dfAvg are [G][F] (rows of F floats, 16-byte aligned since F % 4 == 0; no padding).
-struct dlco_pr_grid {
-    dlco_pr_ctx *src = nullptr;
-    int F = 0, N = 0, G = 0, device = 0, cus = 0;
+// A chain set: G settings (mu[k], gamma[k]) trained together from w = dfAvg = 0 at t = 0 on one stream with one
+// sampler.  w and dfAvg are [G][F] (rows of F floats, 16-byte aligned since F % 4 == 0; no padding).
+struct PrChains {
+    int G = 0, device = 0, cus = 0;
     int group = 0;                                    // settings per workgroup, 0 = pr_grid_group's rule
+    bool solo = false;                                // a context's own chain: launches the single-setting kernels
     hipStream_t stream = nullptr;
-    std::string err;
     std::vector<float> mu, gamma;
-    DevBuf<float> w, df, mu_dev, gamma_dev, vdist, hrows, wtmp, sdist;
+    DevBuf<float> mu_dev, gamma_dev, w, df, vdist, hrows, wtmp, sdist;
     DevBuf<int32_t> win_pos, win_neg, sel;
     DevBuf<double> dscal;
     std::vector<int32_t> h_pos, h_neg;
     CvRng rng{2215};
     uint32_t t = 0;
     RocWork *roc = nullptr;
-    size_t win_cap = 0;
+
+    // on the current device, which is `device`
+    void init(int G_, const float *mu_, const float *gamma_, uint64_t seed, int F, int N, int device_, int cus_);
+    // the validation and statistics workspaces for the data d (a split may be empty; statistics of more than one
+    // setting at a time grow theirs on demand)
+    void fit(const PrData &d)
+    {
+        vdist.alloc((size_t)G * std::max(d.npv() + d.nnv(), 1));
+        hrows.alloc((size_t)G * std::max(d.npv(), 1));
+        wtmp.alloc(d.F);
+        sdist.alloc(d.N);
+    }
+    int per_group(int F) const { return group ? group : pr_grid_group(G, F, cus); }
+    ~PrChains()
+    {
+        (void)hipSetDevice(device);
+        if (stream) (void)hipStreamSynchronize(stream);
+        if (roc) roc_work_destroy(roc);
+        if (stream) (void)hipStreamDestroy(stream);
+    }
+};
+
+struct dlco_pr_ctx {
+    PrData data;
+    PrChains ch;                                      // G = 1
+    std::string err;
+};
+
+// trains on the data of `src` (not copied); never touches src's chain
+struct dlco_pr_grid {
+    const PrData *data = nullptr;
+    PrChains ch;
+    std::string err;
 };
 
 static thread_local std::string g_pr_error;
 
 namespace {
 
-template <typename Ctx, typename Fn>
-int guarded(Ctx *c, Fn &&fn)
+// The body of an entry point on a live context or grid: makes its device current, runs fn and turns an exception
+// into its code and a message that starts with the entry point's name.
+template <typename H, typename Fn>
+int entry(H *h, const char *who, Fn &&fn)
 {
-    return guarded_call(g_pr_error, c ? &c->err : nullptr, fn);
+    return guarded_call(g_pr_error, &h->err, [&] {
+        try {
+            DLCO_HIP(hipSetDevice(h->ch.device));
+            fn();
+        } catch (const Error &e) {
+            throw Error(e.code, std::string(who) + ": " + e.what());
+        } catch (const std::exception &e) {
+            throw Error(DLCO_ERR_INVALID, std::string(who) + ": " + e.what());
+        }
+    });
 }
 
-template <typename Ctx>
-void sync(Ctx *c) { DLCO_HIP(hipStreamSynchronize(c->stream)); }
-template <typename Ctx>
-void h2d(Ctx *c, void *dst, const void *src, size_t bytes)
+void sync(hipStream_t s) { DLCO_HIP(hipStreamSynchronize(s)); }
+void h2d(hipStream_t s, void *dst, const void *src, size_t bytes)
 {
-    DLCO_HIP(hipMemcpyAsync(dst, src, bytes, hipMemcpyHostToDevice, c->stream));
-    sync(c);
+    DLCO_HIP(hipMemcpyAsync(dst, src, bytes, hipMemcpyHostToDevice, s));
+    sync(s);
 }
-template <typename Ctx>
-void d2h(Ctx *c, void *dst, const void *src, size_t bytes)
+void d2h(hipStream_t s, void *dst, const void *src, size_t bytes)
 {
-    DLCO_HIP(hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToHost, c->stream));
-    sync(c);
+    DLCO_HIP(hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToHost, s));
+    sync(s);
 }
 
 // The window's row pairs from the sampler, iPos then iNeg per iteration (src/pr-learn.cpp:303-306)
@@ -128,6 +161,131 @@ void pr_counts(const float *w, int F, const float *prparams, int pr_cols, int nc
 
 }  // namespace
 
+void PrChains::init(int G_, const float *mu_, const float *gamma_, uint64_t seed, int F, int N, int device_, int cus_)
+{
+    G = G_; device = device_; cus = cus_;
+    mu.assign(mu_, mu_ + G); gamma.assign(gamma_, gamma_ + G);
+    rng = CvRng(seed);
+    DLCO_HIP(hipStreamCreateWithFlags(&stream, hipStreamNonBlocking));
+    w.alloc((size_t)G * F); df.alloc((size_t)G * F);
+    w.zero(stream); df.zero(stream);                              // src/pr-learn.cpp:195-196
+    mu_dev.alloc(G); gamma_dev.alloc(G);
+    h2d(stream, mu_dev.p, mu_, (size_t)G * sizeof(float));
+    h2d(stream, gamma_dev.p, gamma_, (size_t)G * sizeof(float));
+    dscal.alloc(G);
+    roc = roc_work_create(N);
+    sync(stream);
+}
+
+namespace {
+
+// n iterations of the loop body, src/pr-learn.cpp:302-329, for every setting: one window of row pairs drawn on the
+// host from the chain set's sampler, one launch
+void steps(PrChains &ch, const PrData &d, uint32_t n)
+{
+    if (n == 0) return;
+    if (n > ch.win_pos.n) {
+        sync(ch.stream);
+        ch.win_pos.alloc(std::max<size_t>(n, 1024)); ch.win_neg.alloc(std::max<size_t>(n, 1024));
+    }
+    draw_window(ch.rng, d.idx, n, ch.h_pos, ch.h_neg);
+    h2d(ch.stream, ch.win_pos.p, ch.h_pos.data(), (size_t)n * sizeof(int32_t));
+    h2d(ch.stream, ch.win_neg.p, ch.h_neg.data(), (size_t)n * sizeof(int32_t));
+    const bool ok = ch.solo ? pr_steps(d.dists.p, d.F, ch.win_pos.p, ch.win_neg.p, n, ch.t, ch.mu[0], ch.gamma[0], d.F, ch.w.p, ch.df.p, nullptr,
+                                       ch.stream)
+                            : pr_grid_steps(d.dists.p, d.F, ch.win_pos.p, ch.win_neg.p, n, ch.t, ch.mu_dev.p, ch.gamma_dev.p, ch.G,
+                                            ch.per_group(d.F), d.F, d.F, ch.w.p, ch.df.p, ch.stream);
+    DLCO_CHECK(ok, DLCO_ERR_INVALID, "shape not supported");
+    ch.t += n;
+}
+
+// w_host / dfavg_host [G][F] or NULL; synchronises the stream either way
+void get_state(PrChains &ch, const PrData &d, uint32_t *t, float *w_host, float *dfavg_host)
+{
+    const size_t bytes = (size_t)ch.G * d.F * sizeof(float);
+    if (t) *t = ch.t;
+    if (w_host) d2h(ch.stream, w_host, ch.w.p, bytes);
+    if (dfavg_host) d2h(ch.stream, dfavg_host, ch.df.p, bytes);
+    if (!w_host && !dfavg_host) sync(ch.stream);
+}
+
+void set_state(PrChains &ch, const PrData &d, uint32_t t, const float *w_host, const float *dfavg_host)
+{
+    const size_t bytes = (size_t)ch.G * d.F * sizeof(float);
+    ch.t = t;
+    if (w_host) h2d(ch.stream, ch.w.p, w_host, bytes);
+    if (dfavg_host) h2d(ch.stream, ch.df.p, dfavg_host, bytes);
+}
+
+// src/pr-learn.cpp:340-361, the validation objective on the current w of every setting (loss_val, regul [G], nnz [G]
+// or NULL): the validation rows are read once for all settings, one launch each for the products, the hinge rows and
+// the double sums; regul / NNZ summed on the host in index order
+void validate(PrChains &ch, const PrData &d, float *loss_val, float *regul, int32_t *nnz)
+{
+    const int npv = d.npv(), nnv = d.nnv(), G = ch.G, F = d.F;
+    DLCO_CHECK(npv > 0 && nnv > 0, DLCO_ERR_INVALID, "empty validation split");
+    const long ldv = (long)npv + nnv;
+    float *pdv = ch.vdist.p, *ndv = ch.vdist.p + npv;
+    if (ch.solo) {
+        pr_gemv(d.dists.p, F, d.val_pos_ids.p, npv, ch.w.p, F, pdv, false, ch.stream);                         // :343
+        pr_gemv(d.dists.p, F, d.val_neg_ids.p, nnv, ch.w.p, F, ndv, false, ch.stream);                         // :344
+    } else {
+        pr_gemv_multi(d.dists.p, F, d.val_pos_ids.p, npv, ch.w.p, F, nullptr, G, F, pdv, ldv, false, ch.stream);
+        pr_gemv_multi(d.dists.p, F, d.val_neg_ids.p, nnv, ch.w.p, F, nullptr, G, F, ndv, ldv, false, ch.stream);
+    }
+    hinge_rows_batched(pdv, npv, ndv, nnv, ldv, ch.hrows.p, npv, G, ch.stream);                                // :348
+    sum_f32_to_f64_batched(ch.hrows.p, npv, npv, ch.dscal.p, G, ch.stream);                                    // :351
+    std::vector<double> total(G);
+    d2h(ch.stream, total.data(), ch.dscal.p, (size_t)G * sizeof(double));
+    std::vector<float> w((size_t)G * F);
+    d2h(ch.stream, w.data(), ch.w.p, w.size() * sizeof(float));
+    for (int k = 0; k < G; k++) {
+        const float Loss = (float)total[k];
+        loss_val[k] = Loss / (float)((size_t)npv * (size_t)nnv);                                               // :355
+        regul_nnz(w.data() + (size_t)k * F, F, ch.mu[k], regul + k, nnz ? nnz + k : nullptr);                  // :358
+    }
+}
+
+// ComputePRStats (src/misc.cpp:171-264) for the settings configs[0..n) (repeats allowed) with w_host [n][F] or NULL
+// (their current w): counts on the host per setting, the all-N distances of those that pass max_dim in one pass over
+// the rows, then the ROC per setting.  Every output is an array of n; fpr95 / auc of a setting cut by max_dim stay.
+void stats(PrChains &ch, const PrData &d, const int32_t *configs, int32_t n, const float *w_host, const float *prparams_host, int32_t pr_rows,
+           int32_t pr_cols, int32_t nchannels, int32_t max_dim, int32_t *nPR, int32_t *dim, int32_t *nzdim, float *fpr95, double *auc)
+{
+    DLCO_CHECK(n >= 0, DLCO_ERR_INVALID, "n < 0");
+    for (int i = 0; i < n; i++) DLCO_CHECK(configs[i] >= 0 && configs[i] < ch.G, DLCO_ERR_INVALID, "config out of range");
+    DLCO_CHECK(pr_rows >= 8 * d.F && pr_cols >= 1, DLCO_ERR_INVALID, "PRParams needs 8 rows per weight");
+    if (n == 0) return;
+    const size_t F = (size_t)d.F;
+    std::vector<float> w;
+    if (w_host) w.assign(w_host, w_host + (size_t)n * F);
+    else {
+        std::vector<float> all((size_t)ch.G * F);
+        d2h(ch.stream, all.data(), ch.w.p, all.size() * sizeof(float));
+        w.resize((size_t)n * F);
+        for (int i = 0; i < n; i++) std::memcpy(w.data() + i * F, all.data() + (size_t)configs[i] * F, F * sizeof(float));
+    }
+    std::vector<int32_t> sel;                                    // list positions that need the ROC pass
+    for (int i = 0; i < n; i++) {
+        pr_counts(w.data() + i * F, d.F, prparams_host, pr_cols, nchannels, nPR + i, dim + i, nzdim + i);   // :183-217
+        if (max_dim != -1 && dim[i] > max_dim) continue;                                                    // :219-221
+        sel.push_back(i);
+    }
+    if (sel.empty()) return;
+    const int ns = (int)sel.size();
+    ch.wtmp.alloc((size_t)n * F);
+    ch.sel.alloc(ns);
+    ch.sdist.alloc((size_t)ns * d.N);
+    h2d(ch.stream, ch.wtmp.p, w.data(), w.size() * sizeof(float));
+    h2d(ch.stream, ch.sel.p, sel.data(), sel.size() * sizeof(int32_t));
+    if (ch.solo) pr_gemv(d.dists.p, d.F, nullptr, d.N, ch.wtmp.p, d.F, ch.sdist.p, true, ch.stream);                      // :226
+    else pr_gemv_multi(d.dists.p, d.F, nullptr, d.N, ch.wtmp.p, d.F, ch.sel.p, ns, d.F, ch.sdist.p, d.N, true, ch.stream);
+    for (int j = 0; j < ns; j++)
+        roc_stats(ch.roc, ch.sdist.p + (size_t)j * d.N, d.labels_dev.p, d.N, fpr95 + sel[j], auc + sel[j], ch.stream);    // :227-263
+}
+
+}  // namespace
+
 extern "C" {
 
 const char *dlco_pr_last_error(const dlco_pr_ctx *c) { return c ? c->err.c_str() : g_pr_error.c_str(); }
@@ -137,155 +295,94 @@ int dlco_pr_create(dlco_pr_ctx **out, int32_t F, int32_t N, float mu, float gamm
     if (!out) return DLCO_ERR_INVALID;
     *out = nullptr;
     dlco_pr_ctx *c = nullptr;
-    const int rc = guarded((dlco_pr_ctx *)nullptr, [&] {
+    const int rc = guarded_call(g_pr_error, nullptr, [&] {
         DLCO_CHECK(F >= 4 && F % 4 == 0 && F <= 8192, DLCO_ERR_INVALID, "pr-learn: F must be a multiple of 4, at most 8192");
         DLCO_CHECK(N >= 2 && gamma > 0.f, DLCO_ERR_INVALID, "pr-learn: N >= 2 and gamma > 0 required");
-        use_gfx950_device(device);
+        const hipDeviceProp_t prop = use_gfx950_device(device);
         c = new dlco_pr_ctx();
-        c->F = F; c->N = N; c->mu = mu; c->gamma = gamma; c->device = device;
-        c->rng = CvRng(seed);
-        DLCO_HIP(hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking));
-        c->w.alloc(F); c->df.alloc(F); c->wtmp.alloc(F);
-        c->w.zero(c->stream); c->df.zero(c->stream);              // src/pr-learn.cpp:195-196
-        c->dscal.alloc(4);
-        sync(c);
+        c->data.F = F; c->data.N = N;
+        c->ch.init(1, &mu, &gamma, seed, F, N, device, prop.multiProcessorCount);
+        c->ch.solo = true;
     });
     if (rc != DLCO_OK) { delete c; return rc; }
     *out = c;
     return DLCO_OK;
 }
 
-void dlco_pr_destroy(dlco_pr_ctx *c)
-{
-    if (!c) return;
-    (void)hipSetDevice(c->device);
-    if (c->stream) (void)hipStreamSynchronize(c->stream);
-    if (c->roc) roc_work_destroy(c->roc);
-    if (c->stream) (void)hipStreamDestroy(c->stream);
-    delete c;
-}
+void dlco_pr_destroy(dlco_pr_ctx *c) { delete c; }
 
-// Uploads Distance [N,F] and Label [N]; index build, shuffle and 80/20 split as src/pr-learn.cpp:229-253
+// Uploads Distance [N,F] and Label [N]; index build, shuffle and 80/20 split as src/pr-learn.cpp:229-253.  A split may
+// come out empty: the context then refuses at dlco_pr_steps / dlco_pr_validate, not here.
 int dlco_pr_set_data(dlco_pr_ctx *c, const float *dists_host, const uint8_t *labels_host)
 {
     if (!c || !dists_host || !labels_host) return DLCO_ERR_INVALID;
-    return guarded(c, [&] {
-        DLCO_HIP(hipSetDevice(c->device));
-        c->dists.alloc((size_t)c->N * c->F);
-        h2d(c, c->dists.p, dists_host, (size_t)c->N * c->F * sizeof(float));
-        c->labels.assign(labels_host, labels_host + c->N);
-        c->labels_dev.alloc(c->N);
-        h2d(c, c->labels_dev.p, c->labels.data(), c->N);
-        c->idx.build(c->labels.data(), c->N);
-        const int npv = (int)c->idx.pos.size() - c->idx.n_pos_trn, nnv = (int)c->idx.neg.size() - c->idx.n_neg_trn;
-        c->val_pos_ids.alloc(std::max(npv, 1)); c->val_neg_ids.alloc(std::max(nnv, 1));
-        if (npv > 0) h2d(c, c->val_pos_ids.p, c->idx.pos.data() + c->idx.n_pos_trn, (size_t)npv * sizeof(int32_t));
-        if (nnv > 0) h2d(c, c->val_neg_ids.p, c->idx.neg.data() + c->idx.n_neg_trn, (size_t)nnv * sizeof(int32_t));
-        c->vdist.alloc((size_t)c->N + 16);
-        c->hrows.alloc((size_t)std::max(npv, 1));
-        if (c->roc) roc_work_destroy(c->roc);
-        c->roc = roc_work_create(c->N);
-        c->have_data = true;
+    return entry(c, "dlco_pr_set_data", [&] {
+        PrData &d = c->data;
+        const hipStream_t s = c->ch.stream;
+        d.dists.alloc((size_t)d.N * d.F);
+        h2d(s, d.dists.p, dists_host, (size_t)d.N * d.F * sizeof(float));
+        d.labels_dev.alloc(d.N);
+        h2d(s, d.labels_dev.p, labels_host, d.N);
+        d.idx.build(labels_host, d.N);
+        const int npv = d.npv(), nnv = d.nnv();
+        d.val_pos_ids.alloc(std::max(npv, 1)); d.val_neg_ids.alloc(std::max(nnv, 1));
+        if (npv > 0) h2d(s, d.val_pos_ids.p, d.idx.pos.data() + d.idx.n_pos_trn, (size_t)npv * sizeof(int32_t));
+        if (nnv > 0) h2d(s, d.val_neg_ids.p, d.idx.neg.data() + d.idx.n_neg_trn, (size_t)nnv * sizeof(int32_t));
+        c->ch.fit(d);
+        d.have = true;
     });
 }
 
 int dlco_pr_get_index(const dlco_pr_ctx *c, int32_t *n_pos, int32_t *n_pos_trn, int32_t *n_neg, int32_t *n_neg_trn)
 {
-    if (!c || !c->have_data) return DLCO_ERR_INVALID;
-    if (n_pos) *n_pos = (int32_t)c->idx.pos.size();
-    if (n_neg) *n_neg = (int32_t)c->idx.neg.size();
-    if (n_pos_trn) *n_pos_trn = c->idx.n_pos_trn;
-    if (n_neg_trn) *n_neg_trn = c->idx.n_neg_trn;
+    if (!c || !c->data.have) return DLCO_ERR_INVALID;
+    const PairIndex &idx = c->data.idx;
+    if (n_pos) *n_pos = (int32_t)idx.pos.size();
+    if (n_neg) *n_neg = (int32_t)idx.neg.size();
+    if (n_pos_trn) *n_pos_trn = idx.n_pos_trn;
+    if (n_neg_trn) *n_neg_trn = idx.n_neg_trn;
     return DLCO_OK;
 }
 
-// n iterations of the loop body, src/pr-learn.cpp:302-329 (one launch; the sample list of the window is
-// drawn on the host from the reference's generator, iPos then iNeg per iteration)
 int dlco_pr_steps(dlco_pr_ctx *c, uint32_t n)
 {
     if (!c) return DLCO_ERR_INVALID;
-    return guarded(c, [&] {
-        DLCO_HIP(hipSetDevice(c->device));
-        DLCO_CHECK(c->have_data, DLCO_ERR_INVALID, "dlco_pr_steps: no data set");
-        DLCO_CHECK(c->idx.n_pos_trn > 0 && c->idx.n_neg_trn > 0, DLCO_ERR_INVALID, "dlco_pr_steps: empty training split");
-        if (n == 0) return;
-        if (n > c->win_cap) {
-            sync(c);
-            c->win_cap = std::max<size_t>(n, 1024);
-            c->win_pos.alloc(c->win_cap); c->win_neg.alloc(c->win_cap);
-        }
-        draw_window(c->rng, c->idx, n, c->h_pos, c->h_neg);
-        h2d(c, c->win_pos.p, c->h_pos.data(), (size_t)n * sizeof(int32_t));
-        h2d(c, c->win_neg.p, c->h_neg.data(), (size_t)n * sizeof(int32_t));
-        const bool ok = pr_steps(c->dists.p, c->F, c->win_pos.p, c->win_neg.p, n, c->t, c->mu, c->gamma, c->F, c->w.p, c->df.p, nullptr,
-                                 c->stream);
-        DLCO_CHECK(ok, DLCO_ERR_INVALID, "dlco_pr_steps: shape not supported");
-        c->t += n;
+    return entry(c, "dlco_pr_steps", [&] {
+        DLCO_CHECK(c->data.have, DLCO_ERR_INVALID, "no data set");
+        DLCO_CHECK(c->data.idx.n_pos_trn > 0 && c->data.idx.n_neg_trn > 0, DLCO_ERR_INVALID, "empty training split");
+        steps(c->ch, c->data, n);
     });
 }
 
 int dlco_pr_get_state(dlco_pr_ctx *c, uint32_t *t, float *w_host, float *dfavg_host)
 {
     if (!c) return DLCO_ERR_INVALID;
-    return guarded(c, [&] {
-        if (t) *t = c->t;
-        if (w_host) d2h(c, w_host, c->w.p, (size_t)c->F * sizeof(float));
-        if (dfavg_host) d2h(c, dfavg_host, c->df.p, (size_t)c->F * sizeof(float));
-    });
+    return entry(c, "dlco_pr_get_state", [&] { get_state(c->ch, c->data, t, w_host, dfavg_host); });
 }
 
 int dlco_pr_set_state(dlco_pr_ctx *c, uint32_t t, const float *w_host, const float *dfavg_host)
 {
     if (!c) return DLCO_ERR_INVALID;
-    return guarded(c, [&] {
-        c->t = t;
-        if (w_host) h2d(c, c->w.p, w_host, (size_t)c->F * sizeof(float));
-        if (dfavg_host) h2d(c, c->df.p, dfavg_host, (size_t)c->F * sizeof(float));
-    });
+    return entry(c, "dlco_pr_set_state", [&] { set_state(c->ch, c->data, t, w_host, dfavg_host); });
 }
 
-// src/pr-learn.cpp:340-361: validation objective on the current w
 int dlco_pr_validate(dlco_pr_ctx *c, float *loss_val, float *regul, int32_t *nnz)
 {
     if (!c || !loss_val || !regul) return DLCO_ERR_INVALID;
-    return guarded(c, [&] {
-        DLCO_HIP(hipSetDevice(c->device));
-        DLCO_CHECK(c->have_data, DLCO_ERR_INVALID, "dlco_pr_validate: no data set");
-        const int npv = (int)c->idx.pos.size() - c->idx.n_pos_trn, nnv = (int)c->idx.neg.size() - c->idx.n_neg_trn;
-        DLCO_CHECK(npv > 0 && nnv > 0, DLCO_ERR_INVALID, "dlco_pr_validate: empty validation split");
-        float *pdv = c->vdist.p, *ndv = c->vdist.p + npv;
-        pr_gemv(c->dists.p, c->F, c->val_pos_ids.p, npv, c->w.p, c->F, pdv, false, c->stream);     // :343
-        pr_gemv(c->dists.p, c->F, c->val_neg_ids.p, nnv, c->w.p, c->F, ndv, false, c->stream);     // :344
-        hinge_rows(pdv, npv, ndv, nnv, c->hrows.p, c->stream);                                      // :348
-        sum_f32_to_f64(c->hrows.p, npv, c->dscal.p, c->stream);                                     // :351
-        double total = 0.0;
-        d2h(c, &total, c->dscal.p, sizeof(double));
-        const float Loss = (float)total;
-        *loss_val = Loss / (float)((size_t)npv * (size_t)nnv);                                      // :355
-        std::vector<float> w(c->F);
-        d2h(c, w.data(), c->w.p, (size_t)c->F * sizeof(float));
-        regul_nnz(w.data(), c->F, c->mu, regul, nnz);                                               // :358
+    return entry(c, "dlco_pr_validate", [&] {
+        DLCO_CHECK(c->data.have, DLCO_ERR_INVALID, "no data set");
+        validate(c->ch, c->data, loss_val, regul, nnz);
     });
 }
 
-// ComputePRStats (src/misc.cpp:171-264): pooling-region counts on the host, distances + ROC on the device
 int dlco_pr_stats(dlco_pr_ctx *c, const float *w_host, const float *prparams_host, int32_t pr_rows, int32_t pr_cols, int32_t nchannels,
                   int32_t max_dim, int32_t *nPR, int32_t *dim, int32_t *nzdim, float *fpr95, double *auc)
 {
     if (!c || !prparams_host || !nPR || !dim || !nzdim || !fpr95 || !auc) return DLCO_ERR_INVALID;
-    return guarded(c, [&] {
-        DLCO_HIP(hipSetDevice(c->device));
-        DLCO_CHECK(c->have_data, DLCO_ERR_INVALID, "dlco_pr_stats: no data set");
-        DLCO_CHECK(pr_rows >= 8 * c->F && pr_cols >= 1, DLCO_ERR_INVALID, "dlco_pr_stats: PRParams needs 8 rows per weight");
-        std::vector<float> w(c->F);
-        if (w_host) std::memcpy(w.data(), w_host, (size_t)c->F * sizeof(float));
-        else d2h(c, w.data(), c->w.p, (size_t)c->F * sizeof(float));
-        pr_counts(w.data(), c->F, prparams_host, pr_cols, nchannels, nPR, dim, nzdim);              // :183-217
-        if (max_dim != -1 && *dim > max_dim) return;                        // :219-221
-        const float *wd = c->w.p;
-        if (w_host) { h2d(c, c->wtmp.p, w.data(), (size_t)c->F * sizeof(float)); wd = c->wtmp.p; }
-        pr_gemv(c->dists.p, c->F, nullptr, c->N, wd, c->F, c->vdist.p, true, c->stream);             // :226
-        roc_stats(c->roc, c->vdist.p, c->labels_dev.p, c->N, fpr95, auc, c->stream);                 // :227-263
+    return entry(c, "dlco_pr_stats", [&] {
+        DLCO_CHECK(c->data.have, DLCO_ERR_INVALID, "no data set");
+        const int32_t only = 0;
+        stats(c->ch, c->data, &only, 1, w_host, prparams_host, pr_rows, pr_cols, nchannels, max_dim, nPR, dim, nzdim, fpr95, auc);
     });
 }
 
@@ -298,164 +395,67 @@ int dlco_pr_grid_create(dlco_pr_grid **out, dlco_pr_ctx *src, int32_t G, const f
     if (!out) return DLCO_ERR_INVALID;
     *out = nullptr;
     dlco_pr_grid *g = nullptr;
-    const int rc = guarded((dlco_pr_grid *)nullptr, [&] {
+    const int rc = guarded_call(g_pr_error, nullptr, [&] {
         DLCO_CHECK(src && mu && gamma, DLCO_ERR_INVALID, "dlco_pr_grid_create: NULL argument");
         DLCO_CHECK(G >= 1 && G <= 65535, DLCO_ERR_INVALID, "dlco_pr_grid_create: G must be 1 .. 65535");
         for (int k = 0; k < G; k++) DLCO_CHECK(gamma[k] > 0.f, DLCO_ERR_INVALID, "dlco_pr_grid_create: every gamma must be > 0");
-        DLCO_CHECK(src->have_data, DLCO_ERR_INVALID, "dlco_pr_grid_create: src has no data");
-        const int npv = (int)src->idx.pos.size() - src->idx.n_pos_trn, nnv = (int)src->idx.neg.size() - src->idx.n_neg_trn;
-        DLCO_CHECK(src->idx.n_pos_trn > 0 && src->idx.n_neg_trn > 0 && npv > 0 && nnv > 0, DLCO_ERR_INVALID,
+        const PrData &d = src->data;
+        DLCO_CHECK(d.have, DLCO_ERR_INVALID, "dlco_pr_grid_create: src has no data");
+        DLCO_CHECK(d.idx.n_pos_trn > 0 && d.idx.n_neg_trn > 0 && d.npv() > 0 && d.nnv() > 0, DLCO_ERR_INVALID,
                    "dlco_pr_grid_create: empty training or validation split");
-        DLCO_HIP(hipSetDevice(src->device));
+        DLCO_HIP(hipSetDevice(src->ch.device));
         g = new dlco_pr_grid();
-        g->src = src; g->F = src->F; g->N = src->N; g->G = G; g->device = src->device;
-        hipDeviceProp_t prop;
-        DLCO_HIP(hipGetDeviceProperties(&prop, g->device));
-        g->cus = prop.multiProcessorCount;
-        g->mu.assign(mu, mu + G); g->gamma.assign(gamma, gamma + G);
-        g->rng = CvRng(seed);
-        DLCO_HIP(hipStreamCreateWithFlags(&g->stream, hipStreamNonBlocking));
-        g->w.alloc((size_t)G * g->F); g->df.alloc((size_t)G * g->F);
-        g->w.zero(g->stream); g->df.zero(g->stream);
-        g->mu_dev.alloc(G); g->gamma_dev.alloc(G);
-        h2d(g, g->mu_dev.p, mu, (size_t)G * sizeof(float));
-        h2d(g, g->gamma_dev.p, gamma, (size_t)G * sizeof(float));
-        g->vdist.alloc((size_t)G * (npv + nnv));
-        g->hrows.alloc((size_t)G * npv);
-        g->dscal.alloc(G);
-        g->roc = roc_work_create(g->N);
-        sync(g);
+        g->data = &d;
+        g->ch.init(G, mu, gamma, seed, d.F, d.N, src->ch.device, src->ch.cus);
+        g->ch.fit(d);
     });
-    if (rc != DLCO_OK) { dlco_pr_grid_destroy(g); return rc; }
+    if (rc != DLCO_OK) { delete g; return rc; }
     *out = g;
     return DLCO_OK;
 }
 
-void dlco_pr_grid_destroy(dlco_pr_grid *g)
-{
-    if (!g) return;
-    (void)hipSetDevice(g->device);
-    if (g->stream) (void)hipStreamSynchronize(g->stream);
-    if (g->roc) roc_work_destroy(g->roc);
-    if (g->stream) (void)hipStreamDestroy(g->stream);
-    delete g;
-}
+void dlco_pr_grid_destroy(dlco_pr_grid *g) { delete g; }
 
 int dlco_pr_grid_set_group(dlco_pr_grid *g, int32_t per_group)
 {
     if (!g) return DLCO_ERR_INVALID;
-    return guarded(g, [&] {
-        DLCO_CHECK(per_group == 0 || per_group == 1 || per_group == 2 || per_group == 4, DLCO_ERR_INVALID,
-                   "dlco_pr_grid_set_group: 0, 1, 2 or 4");
-        DLCO_CHECK(per_group != 4 || g->F <= 1024 * 5, DLCO_ERR_INVALID, "dlco_pr_grid_set_group: 4 settings per workgroup need F <= 5120");
-        g->group = per_group;
+    return entry(g, "dlco_pr_grid_set_group", [&] {
+        DLCO_CHECK(per_group == 0 || per_group == 1 || per_group == 2 || per_group == 4, DLCO_ERR_INVALID, "0, 1, 2 or 4");
+        DLCO_CHECK(per_group != 4 || g->data->F <= 1024 * 5, DLCO_ERR_INVALID, "4 settings per workgroup need F <= 5120");
+        g->ch.group = per_group;
     });
 }
 
 int32_t dlco_pr_grid_group(const dlco_pr_grid *g)
 {
     if (!g) return DLCO_ERR_INVALID;
-    return g->group ? g->group : pr_grid_group(g->G, g->F, g->cus);
+    return g->ch.per_group(g->data->F);
 }
 
-// n iterations of every setting: one window of row pairs from the grid's sampler, one launch
 int dlco_pr_grid_steps(dlco_pr_grid *g, uint32_t n)
 {
     if (!g) return DLCO_ERR_INVALID;
-    return guarded(g, [&] {
-        DLCO_HIP(hipSetDevice(g->device));
-        if (n == 0) return;
-        if (n > g->win_cap) {
-            sync(g);
-            g->win_cap = std::max<size_t>(n, 1024);
-            g->win_pos.alloc(g->win_cap); g->win_neg.alloc(g->win_cap);
-        }
-        draw_window(g->rng, g->src->idx, n, g->h_pos, g->h_neg);
-        h2d(g, g->win_pos.p, g->h_pos.data(), (size_t)n * sizeof(int32_t));
-        h2d(g, g->win_neg.p, g->h_neg.data(), (size_t)n * sizeof(int32_t));
-        const bool ok = pr_grid_steps(g->src->dists.p, g->F, g->win_pos.p, g->win_neg.p, n, g->t, g->mu_dev.p, g->gamma_dev.p, g->G,
-                                      dlco_pr_grid_group(g), g->F, g->F, g->w.p, g->df.p, g->stream);
-        DLCO_CHECK(ok, DLCO_ERR_INVALID, "dlco_pr_grid_steps: shape not supported");
-        g->t += n;
-    });
+    return entry(g, "dlco_pr_grid_steps", [&] { steps(g->ch, *g->data, n); });
 }
 
 int dlco_pr_grid_get_state(dlco_pr_grid *g, uint32_t *t, float *w_host, float *dfavg_host)
 {
     if (!g) return DLCO_ERR_INVALID;
-    return guarded(g, [&] {
-        DLCO_HIP(hipSetDevice(g->device));
-        if (t) *t = g->t;
-        if (w_host) d2h(g, w_host, g->w.p, (size_t)g->G * g->F * sizeof(float));
-        if (dfavg_host) d2h(g, dfavg_host, g->df.p, (size_t)g->G * g->F * sizeof(float));
-        if (!w_host && !dfavg_host) sync(g);
-    });
+    return entry(g, "dlco_pr_grid_get_state", [&] { get_state(g->ch, *g->data, t, w_host, dfavg_host); });
 }
 
-// dlco_pr_validate for every setting: the validation rows are read once for all of them, one launch each for
-// the products, the hinge rows and the double sums; regul / NNZ summed on the host in index order
 int dlco_pr_grid_validate(dlco_pr_grid *g, float *loss_val, float *regul, int32_t *nnz)
 {
     if (!g || !loss_val || !regul) return DLCO_ERR_INVALID;
-    return guarded(g, [&] {
-        DLCO_HIP(hipSetDevice(g->device));
-        const dlco_pr_ctx *c = g->src;
-        const int npv = (int)c->idx.pos.size() - c->idx.n_pos_trn, nnv = (int)c->idx.neg.size() - c->idx.n_neg_trn;
-        const long ldv = (long)npv + nnv;
-        float *pdv = g->vdist.p, *ndv = g->vdist.p + npv;
-        pr_gemv_multi(c->dists.p, g->F, c->val_pos_ids.p, npv, g->w.p, g->F, nullptr, g->G, g->F, pdv, ldv, false, g->stream);   // :343
-        pr_gemv_multi(c->dists.p, g->F, c->val_neg_ids.p, nnv, g->w.p, g->F, nullptr, g->G, g->F, ndv, ldv, false, g->stream);   // :344
-        hinge_rows_batched(pdv, npv, ndv, nnv, ldv, g->hrows.p, npv, g->G, g->stream);                                           // :348
-        sum_f32_to_f64_batched(g->hrows.p, npv, npv, g->dscal.p, g->G, g->stream);                                                // :351
-        std::vector<double> total(g->G);
-        d2h(g, total.data(), g->dscal.p, (size_t)g->G * sizeof(double));
-        std::vector<float> w((size_t)g->G * g->F);
-        d2h(g, w.data(), g->w.p, w.size() * sizeof(float));
-        for (int k = 0; k < g->G; k++) {
-            const float Loss = (float)total[k];
-            loss_val[k] = Loss / (float)((size_t)npv * (size_t)nnv);                                                              // :355
-            regul_nnz(w.data() + (size_t)k * g->F, g->F, g->mu[k], regul + k, nnz ? nnz + k : nullptr);                           // :358
-        }
-    });
+    return entry(g, "dlco_pr_grid_validate", [&] { validate(g->ch, *g->data, loss_val, regul, nnz); });
 }
 
-// ComputePRStats for the settings configs[0..n) (repeats allowed): counts on the host per setting, the all-N
-// distances of those that pass max_dim in one pass over the rows, then the ROC per setting
 int dlco_pr_grid_stats(dlco_pr_grid *g, const int32_t *configs, int32_t n, const float *w_host, const float *prparams_host, int32_t pr_rows,
                        int32_t pr_cols, int32_t nchannels, int32_t max_dim, int32_t *nPR, int32_t *dim, int32_t *nzdim, float *fpr95, double *auc)
 {
     if (!g || !configs || !prparams_host || !nPR || !dim || !nzdim || !fpr95 || !auc) return DLCO_ERR_INVALID;
-    return guarded(g, [&] {
-        DLCO_HIP(hipSetDevice(g->device));
-        DLCO_CHECK(n >= 0, DLCO_ERR_INVALID, "dlco_pr_grid_stats: n < 0");
-        for (int i = 0; i < n; i++) DLCO_CHECK(configs[i] >= 0 && configs[i] < g->G, DLCO_ERR_INVALID, "dlco_pr_grid_stats: config out of range");
-        DLCO_CHECK(pr_rows >= 8 * g->F && pr_cols >= 1, DLCO_ERR_INVALID, "dlco_pr_grid_stats: PRParams needs 8 rows per weight");
-        if (n == 0) return;
-        const size_t F = (size_t)g->F;
-        std::vector<float> w;
-        if (w_host) w.assign(w_host, w_host + (size_t)n * F);
-        else {
-            std::vector<float> all((size_t)g->G * F);
-            d2h(g, all.data(), g->w.p, all.size() * sizeof(float));
-            w.resize((size_t)n * F);
-            for (int i = 0; i < n; i++) std::memcpy(w.data() + i * F, all.data() + (size_t)configs[i] * F, F * sizeof(float));
-        }
-        std::vector<int32_t> sel;                                    // list positions that need the ROC pass
-        for (int i = 0; i < n; i++) {
-            pr_counts(w.data() + i * F, g->F, prparams_host, pr_cols, nchannels, nPR + i, dim + i, nzdim + i);   // :183-217
-            if (max_dim != -1 && dim[i] > max_dim) continue;                                                     // :219-221
-            sel.push_back(i);
-        }
-        if (sel.empty()) return;
-        const int ns = (int)sel.size();
-        g->wtmp.alloc((size_t)n * F);
-        g->sel.alloc(ns);
-        g->sdist.alloc((size_t)ns * g->N);
-        h2d(g, g->wtmp.p, w.data(), w.size() * sizeof(float));
-        h2d(g, g->sel.p, sel.data(), sel.size() * sizeof(int32_t));
-        pr_gemv_multi(g->src->dists.p, g->F, nullptr, g->N, g->wtmp.p, g->F, g->sel.p, ns, g->F, g->sdist.p, g->N, true, g->stream);   // :226
-        for (int j = 0; j < ns; j++)
-            roc_stats(g->roc, g->sdist.p + (size_t)j * g->N, g->src->labels_dev.p, g->N, fpr95 + sel[j], auc + sel[j], g->stream);     // :227-263
+    return entry(g, "dlco_pr_grid_stats", [&] {
+        stats(g->ch, *g->data, configs, n, w_host, prparams_host, pr_rows, pr_cols, nchannels, max_dim, nPR, dim, nzdim, fpr95, auc);
     });
 }
 
@@ -463,7 +463,7 @@ int dlco_pr_device_name(const dlco_pr_ctx *c, char *buf, size_t cap, int *cc_maj
 {
     if (!c || !buf || cap == 0) return DLCO_ERR_INVALID;
     hipDeviceProp_t prop;
-    if (hipGetDeviceProperties(&prop, c->device) != hipSuccess) return DLCO_ERR_HIP;
+    if (hipGetDeviceProperties(&prop, c->ch.device) != hipSuccess) return DLCO_ERR_HIP;
     std::snprintf(buf, cap, "%s (%s)", prop.name, prop.gcnArchName);
     if (cc_major) *cc_major = prop.major;
     if (cc_minor) *cc_minor = prop.minor;
