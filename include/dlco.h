@@ -421,6 +421,31 @@ int32_t dlco_desc_projected_size(const dlco_desc_ctx *ctx);               /* r, 
  * The device form writes r floats per row of pitch ld >= r and leaves the other ld - r untouched. */
 int  dlco_desc_describe(dlco_desc_ctx *ctx, const uint8_t *patches_host, int64_t n, float *out_host);
 int  dlco_desc_describe_device(dlco_desc_ctx *ctx, const uint8_t *patches_host, int64_t n, float *out_dev, int64_t ld);
+/* ---- From an image and a detector's keypoints: the patches are sampled on the device, so that image -> descriptors ->
+ * dlco_desc_match_device never leaves HBM (a keypoint is 16 bytes on the way up, a ready patch 4 KiB).
+ *   A keypoint is four floats (x, y, size, angle) with cv::KeyPoint's meaning: integer coordinates are pixel centres, angle
+ * in degrees, a negative angle means none.  The patch covers size * scale_factor source pixels on a side; without
+ * use_orientation every patch is upright.  The sampling rule is this library's own, in integers and bit-exact on every
+ * machine: csrc/patch_rules.hpp states it.  It is NOT the sampling of OpenCV's VGG::compute, which nothing here can run
+ * or pin.
+ *   status [n] (may be NULL): 0 the keypoint is invalid (x, y or size not finite, size * scale_factor outside (0, 4096],
+ * |x| or |y| above 2^20): its patch and its descriptor row are all zeros; 1 sampled, part of the patch lies outside the
+ * image, whose border is replicated; 2 sampled wholly inside.
+ *   Limits: 1 <= width, height <= 32768, pitch >= width (bytes per row), n >= 1, scale_factor finite and > 0; anything
+ * else, a null pointer, or a keypoint call before an image is set is DLCO_ERR_INVALID. ---- */
+/* image [height][pitch] u8, one image per context: copied */
+int  dlco_desc_set_image(dlco_desc_ctx *ctx, const uint8_t *image_host, int32_t width, int32_t height, int64_t pitch);
+/* the same in device memory: adopted, the caller keeps it alive and unchanged for the keypoint calls that follow */
+int  dlco_desc_set_image_device(dlco_desc_ctx *ctx, const uint8_t *image_dev, int32_t width, int32_t height, int64_t pitch);
+/* patches [n][64][64] u8 of keypoints [n][4], the table every patch call above takes; needs neither filters nor a projection */
+int  dlco_desc_extract_patches(dlco_desc_ctx *ctx, const float *keypoints_host, int64_t n, float scale_factor,
+                               int32_t use_orientation, uint8_t *patches_host, uint8_t *status_host);
+/* Y [n, r]: dlco_desc_describe of those patches bit for bit, with the rows of status 0 set to zero; the patches stay in HBM.
+ * The device form writes r floats per row of pitch ld >= r and leaves the other ld - r untouched. */
+int  dlco_desc_describe_keypoints(dlco_desc_ctx *ctx, const float *keypoints_host, int64_t n, float scale_factor,
+                                  int32_t use_orientation, float *out_host, uint8_t *status_host);
+int  dlco_desc_describe_keypoints_device(dlco_desc_ctx *ctx, const float *keypoints_host, int64_t n, float scale_factor,
+                                         int32_t use_orientation, float *out_dev, int64_t ld, uint8_t *status_host);
 /* per pair ||Y[a] - Y[b]||^2 [n_pairs] and Label [n_pairs] (may be NULL) for pairs [n_pairs,4]: the distances
  * ComputePJStats forms as ||W (Desc1 - Desc2)||^2 from comp-uprjdists' N x F rows (src/misc.cpp:279-292), taken from
  * the table of projected descriptors instead; that table and the un-projected rows never leave HBM */
@@ -462,7 +487,8 @@ int dlco_desc_match_device(dlco_desc_ctx *ctx, const float *query_dev, int64_t l
 /* the whole matrix out[nq][nt] of the same distances, for small problems, tests and tools (nq * nt <= 2^28) */
 int dlco_desc_cross_sqdists(dlco_desc_ctx *ctx, const float *query_host, int64_t nq, const float *train_host, int64_t nt,
                             int32_t r, float *out_host);
-/* HIP-event time of the kernels of the last compute / describe call (transform, pooling, projection); the pair_sqdists /
+/* HIP-event time of the kernels of the last compute / describe call (transform, pooling, projection, and the sampling
+ * for the keypoint calls; extract_patches: the sampling alone); the pair_sqdists /
  * pair_stats calls add their distance kernel; after a match / cross_sqdists call, the time of its kernels (norms, tile
  * loop, merge of the slices) */
 double dlco_desc_last_kernel_ms(const dlco_desc_ctx *ctx);

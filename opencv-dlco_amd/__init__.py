@@ -142,6 +142,11 @@ def load():
     L.dlco_desc_projected_size.restype = C.c_int32
     L.dlco_desc_describe.argtypes = [vp, u8p, i64, f32p]
     L.dlco_desc_describe_device.argtypes = [vp, u8p, i64, vp, i64]
+    L.dlco_desc_set_image.argtypes = [vp, u8p, C.c_int32, C.c_int32, i64]
+    L.dlco_desc_set_image_device.argtypes = [vp, vp, C.c_int32, C.c_int32, i64]
+    L.dlco_desc_extract_patches.argtypes = [vp, f32p, i64, C.c_float, C.c_int32, u8p, u8p]
+    L.dlco_desc_describe_keypoints.argtypes = [vp, f32p, i64, C.c_float, C.c_int32, f32p, u8p]
+    L.dlco_desc_describe_keypoints_device.argtypes = [vp, f32p, i64, C.c_float, C.c_int32, vp, i64, u8p]
     L.dlco_desc_pair_sqdists.argtypes = [vp, u8p, i64, i32p, i64, f32p, u8p]
     L.dlco_desc_pair_stats.argtypes = [vp, u8p, i64, i32p, i64, C.POINTER(C.c_int32), C.POINTER(C.c_float), C.POINTER(C.c_double)]
     L.dlco_desc_match.argtypes = [vp, f32p, i64, f32p, i64, C.c_int32, i32p, f32p]
@@ -720,6 +725,49 @@ class DescContext:
         p = np.ascontiguousarray(patches, np.uint8)
         assert p.ndim == 3 and p.shape[1:] == (64, 64)
         self._ck(self.L.dlco_desc_describe_device(self.h, _p(p, u8p), p.shape[0], C.c_void_p(dev_ptr), ld or self.projected_size))
+
+    # ---- keypoints of an image: patches sampled on the device (csrc/patch_rules.hpp states the rule) ----
+    def set_image(self, img):
+        """img [H, W] u8 (rows may be strided); copied to the device."""
+        a = np.asarray(img)
+        if a.dtype != np.uint8 or a.ndim != 2 or a.strides[1] != 1 or a.strides[0] < a.shape[1]:
+            a = np.ascontiguousarray(a, np.uint8)
+        assert a.ndim == 2
+        self._ck(self.L.dlco_desc_set_image(self.h, C.cast(C.c_void_p(a.ctypes.data), u8p), a.shape[1], a.shape[0], a.strides[0]))
+
+    def set_image_device(self, ptr, w, h, pitch=None):
+        """An image [h][pitch] u8 already in device memory: adopted, the caller keeps it alive."""
+        self._ck(self.L.dlco_desc_set_image_device(self.h, C.c_void_p(ptr), w, h, pitch or w))
+
+    @staticmethod
+    def _keypoints(kp):
+        k = _f32(kp)
+        assert k.ndim == 2 and k.shape[1] == 4, "keypoints are [n, 4] = (x, y, size, angle)"
+        return k
+
+    def extract_patches(self, kp, scale_factor=6.25, use_orientation=True):
+        """(patches [n,64,64] u8, status [n] u8) of keypoints [n,4] = (x, y, size, angle) on the image set."""
+        k = self._keypoints(kp)
+        patches, status = np.empty((k.shape[0], 64, 64), np.uint8), np.empty(k.shape[0], np.uint8)
+        self._ck(self.L.dlco_desc_extract_patches(self.h, _p(k, f32p), k.shape[0], scale_factor, 1 if use_orientation else 0, _p(patches, u8p),
+                                                  _p(status, u8p)))
+        return patches, status
+
+    def describe_keypoints(self, kp, scale_factor=6.25, use_orientation=True):
+        """(Y [n, r], status [n]): describe(extract_patches(kp)) without the patches leaving the device; status-0 rows are zero."""
+        k = self._keypoints(kp)
+        out, status = np.empty((k.shape[0], self.projected_size), np.float32), np.empty(k.shape[0], np.uint8)
+        self._ck(self.L.dlco_desc_describe_keypoints(self.h, _p(k, f32p), k.shape[0], scale_factor, 1 if use_orientation else 0, _p(out, f32p),
+                                                     _p(status, u8p)))
+        return out, status
+
+    def describe_keypoints_device(self, kp, dev_ptr, ld=None, scale_factor=6.25, use_orientation=True):
+        """The same rows into device memory at dev_ptr, row pitch ld floats; returns status [n]."""
+        k = self._keypoints(kp)
+        status = np.empty(k.shape[0], np.uint8)
+        self._ck(self.L.dlco_desc_describe_keypoints_device(self.h, _p(k, f32p), k.shape[0], scale_factor, 1 if use_orientation else 0,
+                                                            C.c_void_p(dev_ptr), ld or self.projected_size, _p(status, u8p)))
+        return status
 
     def pair_sqdists(self, patches, pairs):
         """Per pair ||y_a - y_b||^2 [n_pairs] f32 and labels [n_pairs] u8; the descriptors stay on the device."""

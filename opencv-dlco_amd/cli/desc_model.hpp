@@ -1,7 +1,8 @@
-// desc_model.hpp — how the descriptor tools read a trained model, shared by comp-uprjdists, describe and
-// eval-patches so that the three select the same pooling regions from the same files and print the same lines:
-// "PRFilters" [n,64,64] f32, row `rowid` of pr-learn's "w" (src/comp-uprjdists.cpp:143-232), "Patches" [n,64,64] u8,
-// and, for the tools that apply it, pj-learn's "W" [r, nsel*8].
+// desc_model.hpp — how the descriptor tools read a trained model, shared by comp-uprjdists, describe, describe-image
+// and eval-patches so that they select the same pooling regions from the same files and print the same lines:
+// "PRFilters" [n,64,64] f32, row `rowid` of pr-learn's "w" (src/comp-uprjdists.cpp:143-232), "Patches" [n,64,64] u8
+// (describe-image: "Image" [H,W] u8 and "Keypoints" [n,4] f32 in their place), and, for the tools that apply it,
+// pj-learn's "W" [r, nsel*8].
 #pragma once
 
 #include "../../include/dlco.h"
@@ -33,6 +34,19 @@ inline void load_patches(const char *img, std::vector<size_t> &shape, std::vecto
     std::cout << "Load Patches." << std::endl;
     dlco_io::read_dataset<uint8_t>(img, "Patches", shape, patches);
     if (shape.size() != 3 || shape[1] != 64 || shape[2] != 64) throw std::runtime_error("Patches must be [n,64,64]");
+    dlco_io::term_progress(1.0, -1);
+}
+
+// describe-image's input: one grey image and a detector's keypoints (x, y, size, angle) on it
+inline void load_image_keypoints(const char *img, std::vector<size_t> &ishape, std::vector<uint8_t> &image, std::vector<size_t> &kshape,
+                                 std::vector<float> &keypoints)
+{
+    std::cout << "Load Image." << std::endl;
+    dlco_io::read_dataset<uint8_t>(img, "Image", ishape, image);
+    if (ishape.size() != 2 || ishape[0] < 1 || ishape[1] < 1 || ishape[0] > 32768 || ishape[1] > 32768)
+        throw std::runtime_error("Image must be [H,W] with 1 <= H, W <= 32768");
+    dlco_io::read_dataset<float>(img, "Keypoints", kshape, keypoints);
+    if (kshape.size() != 2 || kshape[0] < 1 || kshape[1] != 4) throw std::runtime_error("Keypoints must be a non-empty [n,4] table");
     dlco_io::term_progress(1.0, -1);
 }
 

@@ -230,6 +230,23 @@ struct Writer {
             npy_write(path + "/" + name + ".npy", data, ElemType<T>::npy(), sizeof(T), {n});
         }
     }
+    // a 3-D dataset [n, rows, cols] ("Patches" [n,64,64]); n == 0 writes an empty one
+    template <typename T>
+    void write_3d(const char *name, const T *data, size_t n, size_t rows, size_t cols)
+    {
+        if (is_h5(path)) {
+            H5 &L = h5();
+            const unsigned long long dims[3] = {n, rows, cols};
+            const H5::hid_t s = L.H5Screate_simple(3, dims, nullptr);
+            const H5::hid_t d = L.H5Dcreate2(f, name, ElemType<T>::h5t(L), s, 0, 0, 0);
+            if (d < 0) throw std::runtime_error(path + ": cannot create dataset " + name);
+            const int rc = (n != 0 && rows != 0 && cols != 0) ? L.H5Dwrite(d, ElemType<T>::h5t(L), 0, 0, 0, data) : 0;
+            L.H5Dclose(d); L.H5Sclose(s);
+            if (rc < 0) throw std::runtime_error(path + ": write of dataset " + name + " failed");
+        } else {
+            npy_write(path + "/" + name + ".npy", data, ElemType<T>::npy(), sizeof(T), {n, rows, cols});
+        }
+    }
     ~Writer() { if (f >= 0) h5().H5Fclose(f); }
 };
 

@@ -2,10 +2,11 @@
 // dlco_desc_* block of include/dlco.h.  Host orchestration and the filter selection of
 // SelectPRFilters (src/misc.cpp:78-168, pure host logic); the patch transform, the pooling product and
 // the pair differences run in HIP kernels (kernels_desc.hip), the projection by a learnt W and the distances
-// of projected descriptors in kernels_describe.hip.
+// of projected descriptors in kernels_describe.hip, the sampling of patches around keypoints in kernels_patch.hip.
 #include "../../include/dlco.h"
 
 #include "dlco_internal.hpp"
+#include "patch_rules.hpp"
 
 #include <algorithm>
 #include <cmath>
@@ -39,6 +40,12 @@ struct dlco_desc_ctx {
     DevBuf<float> m_query, m_train, m_sqdist, m_cross;     // uploaded tables (host forms), the result of a chunk, the matrix
     DevBuf<int32_t> m_idx, m_part;                         // m_part: [slices][nq] partial (d1, j1, d2, j2), 16 bytes each
     DevBuf<double> m_qnorm, m_tnorm;
+    // keypoint calls (dlco_desc_set_image* and after): the image, copied (img_own) or the caller's, and a chunk's frames
+    const uint8_t *img = nullptr;
+    int img_w = 0, img_h = 0;
+    long img_pitch = 0;
+    DevBuf<uint8_t> img_own;
+    DevBuf<patch_rules::Frame> frames;
     double last_ms = 0.0;
 };
 
@@ -77,10 +84,35 @@ float timed_ms(dlco_desc_ctx *c, const EventPair &ev, Run &&run, After &&after)
 template <typename Run>
 float timed_ms(dlco_desc_ctx *c, const EventPair &ev, Run &&run) { return timed_ms(c, ev, run, [] {}); }
 
-// descriptors of patches [n,64,64] (host) into dst: device memory when dst_dev, else host; row pitch ld floats.
+// Where the patches of a chunk come from: the caller's table on the host, copied up, or the frames of keypoints
+// (patch_rules.hpp), for which the sampling kernel writes the chunk's patch buffer from the image in HBM.
+struct PatchSource {
+    const uint8_t *host = nullptr;                          // [n,64,64]
+    const patch_rules::Frame *frames = nullptr;             // [n], on the host
+};
+
+// The copy that brings chunk [p0, p0 + cnt) of `src` to the device: the patches themselves into c->patches, or the frames
+// that sample_chunk turns into them.
+void upload_chunk(dlco_desc_ctx *c, const PatchSource &src, int64_t p0, int cnt)
+{
+    if (src.host)
+        DLCO_HIP(hipMemcpyAsync(c->patches.p, src.host + p0 * kPix, (size_t)cnt * kPix, hipMemcpyHostToDevice, c->stream));
+    else
+        DLCO_HIP(hipMemcpyAsync(c->frames.p, src.frames + p0, (size_t)cnt * sizeof(patch_rules::Frame), hipMemcpyHostToDevice, c->stream));
+}
+
+// the sampling kernel on the uploaded frames of a chunk (frames_host: the same cnt frames): c->patches from c->img
+void sample_chunk(dlco_desc_ctx *c, const patch_rules::Frame *frames_host, int cnt)
+{
+    patch_sample(c->img, c->img_w, c->img_h, c->img_pitch, c->frames.p, cnt, c->patches.p,
+                 patch_stage_bytes(frames_host, cnt, c->img_w, c->img_h), c->stream);
+}
+
+// descriptors of n patches of `src` into dst: device memory when dst_dev, else host; row pitch ld floats.
 // With `project` a row is the learnt descriptor W * Desc (r floats): the un-projected rows of a chunk stay in the
-// library's scratch buffer and the projection kernel follows the pooling product on the same stream.
-void compute(dlco_desc_ctx *c, const uint8_t *patches_host, int64_t n, float *dst, bool dst_dev, long ld, bool project = false)
+// library's scratch buffer and the projection kernel follows the pooling product on the same stream.  The rows of
+// invalid frames are zeroed behind the last kernel.
+void compute(dlco_desc_ctx *c, const PatchSource &src, int64_t n, float *dst, bool dst_dev, long ld, bool project = false)
 {
     DLCO_CHECK(c->nsel > 0, DLCO_ERR_INVALID, "dlco_desc: set the filters first");
     const int F = c->nsel * kBins;
@@ -90,16 +122,18 @@ void compute(dlco_desc_ctx *c, const uint8_t *patches_host, int64_t n, float *ds
     DLCO_HIP(hipSetDevice(c->device));
     c->patches.alloc((size_t)kChunk * kPix);
     c->pt.alloc((size_t)kChunk * kBins * kPix);
+    if (src.frames) c->frames.alloc((size_t)kChunk);
     if (!dst_dev || project) c->desc_chunk.alloc((size_t)kChunk * F);
     if (!dst_dev && project) c->y_chunk.alloc((size_t)kChunk * cols);
     EventPair ev;
     double ms_total = 0.0;
     for (int64_t p0 = 0; p0 < n; p0 += kChunk) {
         const int cnt = (int)std::min<int64_t>(kChunk, n - p0);
-        DLCO_HIP(hipMemcpyAsync(c->patches.p, patches_host + p0 * kPix, (size_t)cnt * kPix, hipMemcpyHostToDevice, c->stream));
+        upload_chunk(c, src, p0, cnt);
         float *out = dst_dev ? dst + p0 * ld : (project ? c->y_chunk.p : c->desc_chunk.p);
         const long old = dst_dev ? ld : cols;
         ms_total += timed_ms(c, ev, [&] {
+            if (src.frames) sample_chunk(c, src.frames + p0, cnt);
             desc_transform(c->patches.p, cnt, c->cf.p, c->ks, c->inv_step, c->norm, c->qk, c->qgamma, c->pt.p, c->stream);
             if (project) {
                 desc_pool(c->pt.p, cnt, c->filt.p, c->nsel, c->nsel_pad, c->desc_chunk.p, F, c->stream);
@@ -108,12 +142,22 @@ void compute(dlco_desc_ctx *c, const uint8_t *patches_host, int64_t n, float *ds
                 desc_pool(c->pt.p, cnt, c->filt.p, c->nsel, c->nsel_pad, out, old, c->stream);
             }
         }, [&] {
+            for (int i = 0; src.frames && i < cnt; i++)
+                if (!src.frames[p0 + i].valid) DLCO_HIP(hipMemsetAsync(out + (size_t)i * old, 0, (size_t)cols * sizeof(float), c->stream));
             if (!dst_dev)
                 DLCO_HIP(hipMemcpy2DAsync(dst + p0 * ld, (size_t)ld * sizeof(float), out, (size_t)cols * sizeof(float),
                                           (size_t)cols * sizeof(float), (size_t)cnt, hipMemcpyDeviceToHost, c->stream));
         });
     }
     c->last_ms = ms_total;
+}
+
+// the same for patches [n,64,64] on the host
+void compute(dlco_desc_ctx *c, const uint8_t *patches_host, int64_t n, float *dst, bool dst_dev, long ld, bool project = false)
+{
+    PatchSource src;
+    src.host = patches_host;
+    compute(c, src, n, dst, dst_dev, ld, project);
 }
 
 }  // namespace
@@ -438,6 +482,110 @@ int dlco_desc_describe_device(dlco_desc_ctx *c, const uint8_t *patches_host, int
     return guarded(c, [&] { compute(c, patches_host, n, out_dev, true, (long)ld, true); });
 }
 
+// ---- keypoints of an image: the patches are sampled on the device (kernels_patch.hip) by the rule of patch_rules.hpp ------
+namespace {
+bool image_args_ok(const uint8_t *image, int32_t width, int32_t height, int64_t pitch)
+{
+    return image && width >= 1 && width <= 32768 && height >= 1 && height <= 32768 && pitch >= width;
+}
+
+bool keypoint_args_ok(const float *keypoints, int64_t n, float scale_factor)
+{
+    return keypoints && n >= 1 && std::isfinite(scale_factor) && scale_factor > 0.0f;
+}
+
+// the frames of keypoints [n][4] = (x, y, size, angle) on the context's image, and their status when asked for
+void keypoint_frames(const dlco_desc_ctx *c, const float *keypoints, int64_t n, float scale_factor, bool use_orientation, uint8_t *status,
+                     std::vector<patch_rules::Frame> &frames)
+{
+    DLCO_CHECK(c->img, DLCO_ERR_INVALID, "dlco_desc: set an image first");
+    frames.resize((size_t)n);
+    for (int64_t i = 0; i < n; i++) {
+        const float *k = keypoints + 4 * i;
+        frames[i] = patch_rules::make_frame(k[0], k[1], k[2], k[3], scale_factor, use_orientation);
+        if (status) status[i] = (uint8_t)patch_rules::status(frames[i], c->img_w, c->img_h);
+    }
+}
+
+void describe_keypoints(dlco_desc_ctx *c, const float *keypoints, int64_t n, float scale_factor, bool use_orientation, float *dst, bool dst_dev,
+                        long ld, uint8_t *status)
+{
+    std::vector<patch_rules::Frame> frames;
+    keypoint_frames(c, keypoints, n, scale_factor, use_orientation, status, frames);
+    PatchSource src;
+    src.frames = frames.data();
+    compute(c, src, n, dst, dst_dev, ld, true);
+}
+}  // namespace
+
+// image [height][pitch] u8 on the host; copied to rows of a 16-byte multiple
+int dlco_desc_set_image(dlco_desc_ctx *c, const uint8_t *image_host, int32_t width, int32_t height, int64_t pitch)
+{
+    if (!c || !image_args_ok(image_host, width, height, pitch)) return DLCO_ERR_INVALID;
+    return guarded(c, [&] {
+        DLCO_HIP(hipSetDevice(c->device));
+        c->img = nullptr;
+        const size_t dpitch = ((size_t)width + 15) / 16 * 16;
+        c->img_own.alloc(dpitch * (size_t)height);
+        DLCO_HIP(hipMemcpy2DAsync(c->img_own.p, dpitch, image_host, (size_t)pitch, (size_t)width, (size_t)height, hipMemcpyHostToDevice, c->stream));
+        sync(c);
+        c->img = c->img_own.p; c->img_w = width; c->img_h = height; c->img_pitch = (long)dpitch;
+    });
+}
+
+// the same image already in device memory: used where it is, the caller keeps it alive and unchanged while keypoint calls run
+int dlco_desc_set_image_device(dlco_desc_ctx *c, const uint8_t *image_dev, int32_t width, int32_t height, int64_t pitch)
+{
+    if (!c || !image_args_ok(image_dev, width, height, pitch)) return DLCO_ERR_INVALID;
+    return guarded(c, [&] {
+        DLCO_HIP(hipSetDevice(c->device));
+        c->img_own.release();
+        c->img = image_dev; c->img_w = width; c->img_h = height; c->img_pitch = (long)pitch;
+    });
+}
+
+// patches [n][64][64] u8 and status [n] (may be NULL) of keypoints [n][4]; needs neither filters nor a projection
+int dlco_desc_extract_patches(dlco_desc_ctx *c, const float *keypoints_host, int64_t n, float scale_factor, int32_t use_orientation,
+                              uint8_t *patches_host, uint8_t *status_host)
+{
+    if (!c || !patches_host || !keypoint_args_ok(keypoints_host, n, scale_factor)) return DLCO_ERR_INVALID;
+    return guarded(c, [&] {
+        std::vector<patch_rules::Frame> frames;
+        keypoint_frames(c, keypoints_host, n, scale_factor, use_orientation != 0, status_host, frames);
+        PatchSource src;
+        src.frames = frames.data();
+        DLCO_HIP(hipSetDevice(c->device));
+        c->patches.alloc((size_t)kChunk * kPix);
+        c->frames.alloc((size_t)kChunk);
+        EventPair ev;
+        double ms_total = 0.0;
+        for (int64_t p0 = 0; p0 < n; p0 += kChunk) {
+            const int cnt = (int)std::min<int64_t>(kChunk, n - p0);
+            upload_chunk(c, src, p0, cnt);
+            ms_total += timed_ms(c, ev, [&] { sample_chunk(c, src.frames + p0, cnt); }, [&] {
+                DLCO_HIP(hipMemcpyAsync(patches_host + p0 * kPix, c->patches.p, (size_t)cnt * kPix, hipMemcpyDeviceToHost, c->stream));
+            });
+        }
+        c->last_ms = ms_total;
+    });
+}
+
+// Y [n, r] of keypoints: dlco_desc_describe on the patches dlco_desc_extract_patches gives, which stay in HBM; the rows of
+// status 0 are zero
+int dlco_desc_describe_keypoints(dlco_desc_ctx *c, const float *keypoints_host, int64_t n, float scale_factor, int32_t use_orientation,
+                                 float *out_host, uint8_t *status_host)
+{
+    if (!c || !out_host || !keypoint_args_ok(keypoints_host, n, scale_factor)) return DLCO_ERR_INVALID;
+    return guarded(c, [&] { describe_keypoints(c, keypoints_host, n, scale_factor, use_orientation != 0, out_host, false, (long)c->r, status_host); });
+}
+
+int dlco_desc_describe_keypoints_device(dlco_desc_ctx *c, const float *keypoints_host, int64_t n, float scale_factor, int32_t use_orientation,
+                                        float *out_dev, int64_t ld, uint8_t *status_host)
+{
+    if (!c || !out_dev || !keypoint_args_ok(keypoints_host, n, scale_factor)) return DLCO_ERR_INVALID;
+    return guarded(c, [&] { describe_keypoints(c, keypoints_host, n, scale_factor, use_orientation != 0, out_dev, true, (long)ld, status_host); });
+}
+
 namespace {
 // The table Y [n_patches, r] of every patch's learnt descriptor (128 MB at 500k x 64) and, from it, the squared distance
 // and label of every pair, all in device memory: what eval-fpr95 gets out of an N x F "-unproj" file, without that matrix.
@@ -602,8 +750,8 @@ int dlco_desc_cross_sqdists(dlco_desc_ctx *c, const float *query_host, int64_t n
 }
 
 // milliseconds the kernels of the last dlco_desc_compute* / dlco_desc_describe* call took (HIP events): transform and
-// pooling, plus the projection for describe; the pair calls add their distance kernel; after a match call, its kernels
-// (norms, top two, merge)
+// pooling, plus the projection for describe and the sampling for the keypoint calls (extract_patches: the sampling alone);
+// the pair calls add their distance kernel; after a match call, its kernels (norms, top two, merge)
 double dlco_desc_last_kernel_ms(const dlco_desc_ctx *c) { return c ? c->last_ms : 0.0; }
 
 }  // extern "C"

@@ -20,6 +20,8 @@
 #include <type_traits>
 #include <vector>
 
+namespace patch_rules { struct Frame; }                      // patch_rules.hpp
+
 namespace dlco {
 
 // ---------------------------------------------------------------------------
@@ -430,5 +432,9 @@ int match_tiles_per_slice(long nq, long nt, int n_cu);
 int match_slices(long nt, int tiles_per_slice);
 void match_top2(const float *query, long ldq, int nq, const float *train, long ldt, int nt, int r, const double *qnorm, const double *tnorm,
                 int tiles_per_slice, int32_t *idx, float *sqdist, void *part, float *out, hipStream_t s);
+// keypoint patches (kernels_patch.hip; the frames and the sampling rule are patch_rules.hpp)
+int patch_stage_bytes(const patch_rules::Frame *frames_host, int n, int W, int H);
+void patch_sample(const uint8_t *img, int W, int H, long pitch, const patch_rules::Frame *frames, int n, uint8_t *patches, int lds_bytes,
+                  hipStream_t s);
 
 }  // namespace dlco
