@@ -487,10 +487,54 @@ int dlco_desc_match_device(dlco_desc_ctx *ctx, const float *query_dev, int64_t l
 /* the whole matrix out[nq][nt] of the same distances, for small problems, tests and tools (nq * nt <= 2^28) */
 int dlco_desc_cross_sqdists(dlco_desc_ctx *ctx, const float *query_host, int64_t nq, const float *train_host, int64_t nt,
                             int32_t r, float *out_host);
+/* ---- Eight-bit descriptors: a table of bytes is a quarter of the float one, and its distances are integers.
+ *   The quantiser is a scale s > 0 and an offset o[r]; csrc/quant_rules.hpp states the rule.  One element:
+ * t = y - o_k in float, v = t * s in float (two roundings, never an FMA), q = rintf(v) (half to even); the byte is 0 if v is
+ * NaN, else clamp(q, 0, 255).  It is this library's own rule, NOT OpenCV's VGG dsc_normalize, which nothing here can run or
+ * pin.  One global scale and a per-dimension offset: distances do not see the offset, so ||u_a - u_b|| ~ s ||y_a - y_b||
+ * with an error of at most 1 per coordinate while nothing clamps.
+ *   Limits: 1 <= r <= 1024, n >= 1, scale finite and > 0, offsets finite (NULL = all zero); anything else, or a null
+ * pointer, is DLCO_ERR_INVALID. ---- */
+/* The quantiser fitted to a sample Y [n, r] of finite values: o_k = min_i Y[i][k], s = 255 / max_k (max_i Y[i][k] - o_k)
+ * with the subtraction in float, s = 1 when that range is 0: the sample itself never clamps.  A non-finite entry (or a
+ * range beyond float) is DLCO_ERR_INVALID.  Host logic, no device needed. */
+int  dlco_desc_quant_fit(const float *Y_host, int64_t n, int32_t r, float *scale, float *offset_out);
+/* out_u8 [n, r] of Y [n, r] by the rule above.  Host logic, no device needed. */
+int  dlco_desc_quantize(const float *Y_host, int64_t n, int32_t r, float scale, const float *offset, uint8_t *out_u8);
+/* Attaches a quantiser to the context for the _u8 calls below: copied, replaces any earlier one.  dlco_desc_set_projection
+ * drops a quantiser whose r is not the projection's. */
+int  dlco_desc_set_quantizer(dlco_desc_ctx *ctx, float scale, const float *offset, int32_t r);
+/* The bytes dlco_desc_quantize gives on the rows of dlco_desc_describe / dlco_desc_describe_keypoints, bit for bit, quantised
+ * on the device (a keypoint row of status 0 is therefore the quantisation of the zero vector).  The device forms write r
+ * bytes per row of pitch ld >= r bytes and leave the other ld - r untouched.  Without a quantiser, or with one whose r is not
+ * dlco_desc_projected_size(): DLCO_ERR_INVALID. */
+int  dlco_desc_describe_u8(dlco_desc_ctx *ctx, const uint8_t *patches_host, int64_t n, uint8_t *out_host);
+int  dlco_desc_describe_u8_device(dlco_desc_ctx *ctx, const uint8_t *patches_host, int64_t n, uint8_t *out_dev, int64_t ld);
+int  dlco_desc_describe_keypoints_u8(dlco_desc_ctx *ctx, const float *keypoints_host, int64_t n, float scale_factor,
+                                     int32_t use_orientation, uint8_t *out_host, uint8_t *status_host);
+int  dlco_desc_describe_keypoints_u8_device(dlco_desc_ctx *ctx, const float *keypoints_host, int64_t n, float scale_factor,
+                                            int32_t use_orientation, uint8_t *out_dev, int64_t ld, uint8_t *status_host);
+/* Matching two tables of bytes, the limits of dlco_desc_match: 1 <= r <= 1024, 1 <= nq, 1 <= nt < 2^31.
+ *   d(i,j) = sum_k (query[i][k] - train[j][k])^2 as an int32, at most 1024 * 255^2 = 66 585 600.  The distances are exact:
+ * integer dot products on the int8 matrix cores, no rounding anywhere, so the result depends on nothing but the bytes.
+ *   Order: candidates are ordered by (d, train index); idx[i] / sqdist[i] are the first two of that order, i.e. the top two
+ * of row i of the matrix dlco_desc_cross_sqdists_u8 returns.  nt == 1: idx[i][1] = -1, sqdist[i][1] = INT32_MAX. */
+int dlco_desc_match_u8(dlco_desc_ctx *ctx, const uint8_t *query_u8, int64_t nq, const uint8_t *train_u8, int64_t nt,
+                       int32_t r, int32_t *idx_host, int32_t *sqdist_host);
+/* the same on tables that already live in HBM (e.g. written by dlco_desc_describe_u8_device): pitches ldq, ldt in bytes,
+ * >= r and multiples of 16, tables 16-byte aligned (rows are read in 16-byte pieces: the ceil(r/16)*16 bytes at the start of
+ * every row must be readable, the ones at and beyond r are ignored); idx_dev / sqdist_dev are device memory; queued on the
+ * context's stream, synchronised on return */
+int dlco_desc_match_u8_device(dlco_desc_ctx *ctx, const uint8_t *query_dev, int64_t ldq, int64_t nq,
+                              const uint8_t *train_dev, int64_t ldt, int64_t nt, int32_t r,
+                              int32_t *idx_dev, int32_t *sqdist_dev);
+/* the whole matrix out[nq][nt] of the same distances, for small problems, tests and tools (nq * nt <= 2^28) */
+int dlco_desc_cross_sqdists_u8(dlco_desc_ctx *ctx, const uint8_t *query_u8, int64_t nq, const uint8_t *train_u8, int64_t nt,
+                               int32_t r, int32_t *out_host);
 /* HIP-event time of the kernels of the last compute / describe call (transform, pooling, projection, and the sampling
  * for the keypoint calls; extract_patches: the sampling alone); the pair_sqdists /
- * pair_stats calls add their distance kernel; after a match / cross_sqdists call, the time of its kernels (norms, tile
- * loop, merge of the slices) */
+ * pair_stats calls add their distance kernel; after a match / cross_sqdists call, float or _u8, the time of its kernels
+ * (norms, tile loop, merge of the slices); the _u8 forms of describe add their quantising kernel */
 double dlco_desc_last_kernel_ms(const dlco_desc_ctx *ctx);
 
 #ifdef __cplusplus

@@ -152,6 +152,16 @@ def load():
     L.dlco_desc_match.argtypes = [vp, f32p, i64, f32p, i64, C.c_int32, i32p, f32p]
     L.dlco_desc_match_device.argtypes = [vp, vp, i64, i64, vp, i64, i64, C.c_int32, vp, vp]
     L.dlco_desc_cross_sqdists.argtypes = [vp, f32p, i64, f32p, i64, C.c_int32, f32p]
+    L.dlco_desc_quant_fit.argtypes = [f32p, i64, C.c_int32, C.POINTER(C.c_float), f32p]
+    L.dlco_desc_quantize.argtypes = [f32p, i64, C.c_int32, C.c_float, f32p, u8p]
+    L.dlco_desc_set_quantizer.argtypes = [vp, C.c_float, f32p, C.c_int32]
+    L.dlco_desc_describe_u8.argtypes = [vp, u8p, i64, u8p]
+    L.dlco_desc_describe_u8_device.argtypes = [vp, u8p, i64, vp, i64]
+    L.dlco_desc_describe_keypoints_u8.argtypes = [vp, f32p, i64, C.c_float, C.c_int32, u8p, u8p]
+    L.dlco_desc_describe_keypoints_u8_device.argtypes = [vp, f32p, i64, C.c_float, C.c_int32, vp, i64, u8p]
+    L.dlco_desc_match_u8.argtypes = [vp, u8p, i64, u8p, i64, C.c_int32, i32p, i32p]
+    L.dlco_desc_match_u8_device.argtypes = [vp, vp, i64, i64, vp, i64, i64, C.c_int32, vp, vp]
+    L.dlco_desc_cross_sqdists_u8.argtypes = [vp, u8p, i64, u8p, i64, C.c_int32, i32p]
     L.dlco_desc_last_kernel_ms.argtypes = [vp]
     L.dlco_desc_last_kernel_ms.restype = C.c_double
     L.dlco_pr_last_error.restype = C.c_char_p
@@ -631,6 +641,32 @@ def select_filters(pr_filters, w):
     return out
 
 
+def quant_fit(Y):
+    """(scale, offset [r]) of the quantiser fitted to the sample Y [n, r] (csrc/quant_rules.hpp): host logic, no device needed."""
+    L = load()
+    y = _f32(Y)
+    assert y.ndim == 2
+    scale, off = C.c_float(), np.empty(y.shape[1], np.float32)
+    rc = L.dlco_desc_quant_fit(_p(y, f32p), y.shape[0], y.shape[1], C.byref(scale), _p(off, f32p))
+    if rc != OK:
+        raise DlcoError(rc, "dlco_desc_quant_fit")
+    return scale.value, off
+
+
+def quantize(Y, scale, offset=None):
+    """Bytes [n, r] of the rows Y [n, r] under the quantiser (scale, offset; None = zeros): host logic, no device needed."""
+    L = load()
+    y = _f32(Y)
+    assert y.ndim == 2
+    off = None if offset is None else _f32(offset).ravel()
+    assert off is None or off.size == y.shape[1]
+    out = np.empty(y.shape, np.uint8)
+    rc = L.dlco_desc_quantize(_p(y, f32p), y.shape[0], y.shape[1], scale, _p(off, f32p), _p(out, u8p))
+    if rc != OK:
+        raise DlcoError(rc, "dlco_desc_quantize")
+    return out
+
+
 class DescContext:
     """comp-uprjdists on the GPU: get_desc + pooling product per patch (thin wrapper over dlco_desc_ctx)."""
 
@@ -808,6 +844,64 @@ class DescContext:
         assert q.ndim == 2 and t.ndim == 2 and q.shape[1] == t.shape[1]
         out = np.empty((q.shape[0], t.shape[0]), np.float32)
         self._ck(self.L.dlco_desc_cross_sqdists(self.h, _p(q, f32p), q.shape[0], _p(t, f32p), t.shape[0], q.shape[1], _p(out, f32p)))
+        return out
+
+    # ---- eight-bit descriptors: rows quantised on the device, byte tables matched with exact integer distances ----
+    def set_quantizer(self, scale, offset=None, r=None):
+        """The quantiser of the _u8 calls (quant_fit gives one); offset None = zeros, then r says how wide."""
+        off = None if offset is None else _f32(offset).ravel()
+        self._ck(self.L.dlco_desc_set_quantizer(self.h, scale, _p(off, f32p), off.size if off is not None else (r or self.projected_size)))
+
+    def describe_u8(self, patches):
+        """quantize(describe(patches)) [n, r] uint8, quantised on the device."""
+        p = np.ascontiguousarray(patches, np.uint8)
+        assert p.ndim == 3 and p.shape[1:] == (64, 64)
+        out = np.empty((p.shape[0], self.projected_size), np.uint8)
+        self._ck(self.L.dlco_desc_describe_u8(self.h, _p(p, u8p), p.shape[0], _p(out, u8p)))
+        return out
+
+    def describe_u8_device(self, patches, dev_ptr, ld=None):
+        p = np.ascontiguousarray(patches, np.uint8)
+        assert p.ndim == 3 and p.shape[1:] == (64, 64)
+        self._ck(self.L.dlco_desc_describe_u8_device(self.h, _p(p, u8p), p.shape[0], C.c_void_p(dev_ptr), ld or self.projected_size))
+
+    def describe_keypoints_u8(self, kp, scale_factor=6.25, use_orientation=True):
+        """(bytes [n, r], status [n]): quantize(describe_keypoints(kp)); a status-0 row is the quantised zero vector."""
+        k = self._keypoints(kp)
+        out, status = np.empty((k.shape[0], self.projected_size), np.uint8), np.empty(k.shape[0], np.uint8)
+        self._ck(self.L.dlco_desc_describe_keypoints_u8(self.h, _p(k, f32p), k.shape[0], scale_factor, 1 if use_orientation else 0,
+                                                        _p(out, u8p), _p(status, u8p)))
+        return out, status
+
+    def describe_keypoints_u8_device(self, kp, dev_ptr, ld=None, scale_factor=6.25, use_orientation=True):
+        """The same rows into device memory at dev_ptr, row pitch ld bytes; returns status [n]."""
+        k = self._keypoints(kp)
+        status = np.empty(k.shape[0], np.uint8)
+        self._ck(self.L.dlco_desc_describe_keypoints_u8_device(self.h, _p(k, f32p), k.shape[0], scale_factor, 1 if use_orientation else 0,
+                                                               C.c_void_p(dev_ptr), ld or self.projected_size, _p(status, u8p)))
+        return status
+
+    def match_u8(self, query, train):
+        """match on byte tables [nq, r] / [nt, r] uint8: (idx [nq,2] int32, sqdist [nq,2] int32), exact integer distances
+        ordered by (distance, index); nt == 1 gives -1 / INT32_MAX in column 1."""
+        q, t = np.ascontiguousarray(query, np.uint8), np.ascontiguousarray(train, np.uint8)
+        assert q.ndim == 2 and t.ndim == 2 and q.shape[1] == t.shape[1]
+        idx = np.empty((q.shape[0], 2), np.int32)
+        d = np.empty((q.shape[0], 2), np.int32)
+        self._ck(self.L.dlco_desc_match_u8(self.h, _p(q, u8p), q.shape[0], _p(t, u8p), t.shape[0], q.shape[1], _p(idx, i32p), _p(d, i32p)))
+        return idx, d
+
+    def match_u8_device(self, q_ptr, nq, t_ptr, nt, r, idx_ptr, d_ptr, ldq=None, ldt=None):
+        """match_u8 on tables in device memory (row pitches ldq, ldt in bytes: multiples of 16); results to device memory."""
+        self._ck(self.L.dlco_desc_match_u8_device(self.h, C.c_void_p(q_ptr), ldq or r, nq, C.c_void_p(t_ptr), ldt or r, nt, r,
+                                                  C.c_void_p(idx_ptr), C.c_void_p(d_ptr)))
+
+    def cross_sqdists_u8(self, query, train):
+        """The whole matrix [nq, nt] int32 of the distances match_u8 orders (nq * nt <= 2^28)."""
+        q, t = np.ascontiguousarray(query, np.uint8), np.ascontiguousarray(train, np.uint8)
+        assert q.ndim == 2 and t.ndim == 2 and q.shape[1] == t.shape[1]
+        out = np.empty((q.shape[0], t.shape[0]), np.int32)
+        self._ck(self.L.dlco_desc_cross_sqdists_u8(self.h, _p(q, u8p), q.shape[0], _p(t, u8p), t.shape[0], q.shape[1], _p(out, i32p)))
         return out
 
     def last_kernel_ms(self):

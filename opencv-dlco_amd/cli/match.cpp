@@ -1,6 +1,6 @@
 // match — nearest-neighbour matching of two descriptor tables, over libdlco.so.
 //
-//     match query_desc_file train_desc_file -out dst [-ratio f] [-cross] [-device n]
+//     match query_desc_file train_desc_file -out dst [-u8] [-ratio f] [-cross] [-device n]
 //
 // Both inputs hold the dataset "Descriptor" [n, r] f32 that `describe` writes (the two r must agree).  Writes
 //     "Nearest" [nq,2] i32 and "NearestSqDist" [nq,2] f32   the library's answer for every query (dlco_desc_match)
@@ -8,10 +8,15 @@
 // The filters are host rules (match_rules.hpp): -ratio f (0 < f <= 1) is Lowe's test d1 < f^2 d2 on the squared
 // distances, -cross keeps (i, j) iff the nearest query of train row j is i (a second library call with the tables
 // swapped).  Both may be given; without either every query with a neighbour is a match.  The reference has no such tool.
+//   With -u8 both inputs hold "DescriptorU8" [n, r] u8 (`quantize`, `describe -quant`) instead, the library call is
+// dlco_desc_match_u8, and "NearestSqDist" / "MatchSqDist" are i32: exact integer distances.  If both files carry a quantiser
+// ("QuantScale", "QuantOffset") and the two differ in any bit the tool refuses: distances between differently quantised
+// tables mean nothing.
 // A path that does not end in .h5/.hdf5 is a directory of .npy files with the same dataset names (dlco_io.hpp).
 #include "../../include/dlco.h"
 #include "dlco_io.hpp"
 #include "match_rules.hpp"
+#include "quant_io.hpp"
 
 #include <chrono>
 #include <cstdlib>
@@ -29,12 +34,60 @@ void load_table(const char *path, std::vector<size_t> &shape, std::vector<float>
     for (float v : rows)
         if (!(v == v) || v > 3.0e38f || v < -3.0e38f) throw std::runtime_error(std::string(path) + ": Descriptor contains NaN");
 }
+
+void load_table_u8(const char *path, std::vector<size_t> &shape, std::vector<uint8_t> &rows)
+{
+    dlco_io::read_dataset<uint8_t>(path, "DescriptorU8", shape, rows);
+    if (shape.size() != 2 || shape[0] < 1 || shape[1] < 1) throw std::runtime_error(std::string(path) + ": DescriptorU8 must be a non-empty [n, r] table");
+}
+
+// the -u8 line of main: the same steps on byte tables
+void match_u8(const char *qf, const char *tf, const char *out, bool use_ratio, float ratio, bool cross, int device, dlco_desc_ctx *&ctx)
+{
+    std::vector<size_t> qs, ts;
+    std::vector<uint8_t> Q, T;
+    load_table_u8(qf, qs, Q);
+    load_table_u8(tf, ts, T);
+    if (qs[1] != ts[1])
+        throw std::runtime_error("the descriptors differ in size: " + std::to_string(qs[1]) + " (query) against " + std::to_string(ts[1]) + " (train)");
+    const size_t nq = qs[0], nt = ts[0], r = qs[1];
+    float sq = 0.f, st = 0.f;
+    std::vector<float> oq, ot;
+    if (quant_io::present(qf, r, sq, oq) && quant_io::present(tf, r, st, ot) && !quant_io::same_bits(sq, oq, st, ot))
+        throw std::runtime_error("the two tables were quantised differently (QuantScale / QuantOffset differ): their distances mean nothing");
+    printf("Queries: %zu x %zu (u8)\n", nq, r);
+    printf("Train: %zu x %zu (u8)\n", nt, r);
+
+    if (dlco_desc_create(&ctx, 1.4f, 8, 1, device) != DLCO_OK) throw std::runtime_error(dlco_desc_last_error(nullptr));
+    const auto t0 = std::chrono::steady_clock::now();
+    std::vector<int32_t> nearest(nq * 2), sqdist(nq * 2), back;
+    if (dlco_desc_match_u8(ctx, Q.data(), (int64_t)nq, T.data(), (int64_t)nt, (int32_t)r, nearest.data(), sqdist.data()) != DLCO_OK)
+        throw std::runtime_error(dlco_desc_last_error(ctx));
+    if (cross) {
+        back.resize(nt * 2);
+        std::vector<int32_t> back_d(nt * 2);
+        if (dlco_desc_match_u8(ctx, T.data(), (int64_t)nt, Q.data(), (int64_t)nq, (int32_t)r, back.data(), back_d.data()) != DLCO_OK)
+            throw std::runtime_error(dlco_desc_last_error(ctx));
+    }
+    std::vector<int32_t> pairs, dists;
+    match_rules::select((int64_t)nq, nearest.data(), sqdist.data(), use_ratio, ratio, cross ? back.data() : nullptr, pairs, dists);
+    {
+        dlco_io::Writer wr(out);
+        wr.write<int32_t>("Nearest", nearest.data(), nq, 2);
+        wr.write<int32_t>("NearestSqDist", sqdist.data(), nq, 2);
+        wr.write<int32_t>("Matches", pairs.data(), dists.size(), 2);
+        wr.write_vec<int32_t>("MatchSqDist", dists.data(), dists.size());
+    }
+    const double sec = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
+    printf("Matches: %zu / %zu\n", dists.size(), nq);
+    printf("Total: %.09f sec\n", sec);
+}
 }  // namespace
 
 int main(int argc, char **argv)
 {
     int device = 0;
-    bool help = false, cross = false, use_ratio = false;
+    bool help = false, cross = false, use_ratio = false, u8 = false;
     float ratio = 1.0f;
     const char *qf = nullptr, *tf = nullptr, *out = nullptr;
     for (int i = 1; i < argc; i++) {
@@ -44,6 +97,7 @@ int main(int argc, char **argv)
             if (std::strcmp(argv[i], "-out") == 0 && has_val) { out = argv[++i]; continue; }
             if (std::strcmp(argv[i], "-ratio") == 0 && has_val) { ratio = (float)atof(argv[++i]); use_ratio = true; continue; }
             if (std::strcmp(argv[i], "-cross") == 0) { cross = true; continue; }
+            if (std::strcmp(argv[i], "-u8") == 0) { u8 = true; continue; }
             if (std::strcmp(argv[i], "-device") == 0 && has_val) { device = atoi(argv[++i]); continue; }
             cout << "ERROR: Invalid " << argv[i] << " option." << endl;
             help = true;
@@ -60,12 +114,17 @@ int main(int argc, char **argv)
     }
     if (help) {
         cout << endl;
-        cout << "Usage: match query_desc_file train_desc_file -out dst_h5_filename [-ratio f] [-cross] [-device n]" << endl;
+        cout << "Usage: match query_desc_file train_desc_file -out dst_h5_filename [-u8] [-ratio f] [-cross] [-device n]" << endl;
         cout << endl;
         return 1;
     }
     dlco_desc_ctx *ctx = nullptr;
     try {
+        if (u8) {
+            match_u8(qf, tf, out, use_ratio, ratio, cross, device, ctx);
+            dlco_desc_destroy(ctx);
+            return 0;
+        }
         std::vector<size_t> qs, ts;
         std::vector<float> Q, T;
         load_table(qf, qs, Q);

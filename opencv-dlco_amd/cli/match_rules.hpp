@@ -16,6 +16,14 @@ inline bool ratio_keep(float d1, float d2, int32_t idx2, float f)
     return (double)d1 < (double)f * (double)f * (double)d2;
 }
 
+// The same test on the exact integer distances of byte tables (dlco_desc_match_u8): the same comparison in double, in which
+// an int32 and its product with f^2 of a float f are exact enough that d1 == f^2 d2 is still dropped.
+inline bool ratio_keep(int32_t d1, int32_t d2, int32_t idx2, float f)
+{
+    if (idx2 == -1) return true;
+    return (double)d1 < (double)f * (double)f * (double)d2;
+}
+
 // The mutual rule: (i, j) is kept iff the nearest query of train row j is i.  back [nt][2] is the library's answer with
 // the tables swapped.
 inline bool cross_keep(int64_t i, int32_t j, const int32_t *back) { return back[2 * (int64_t)j] == (int32_t)i; }
@@ -25,6 +33,23 @@ inline bool cross_keep(int64_t i, int32_t j, const int32_t *back) { return back[
 // A query whose nearest index is -1 (no usable neighbour) is never a match.
 inline void select(int64_t nq, const int32_t *nearest, const float *sqdist, bool use_ratio, float f, const int32_t *back,
                    std::vector<int32_t> &pairs, std::vector<float> &dists)
+{
+    pairs.clear();
+    dists.clear();
+    for (int64_t i = 0; i < nq; i++) {
+        const int32_t j = nearest[2 * i];
+        if (j < 0) continue;
+        if (use_ratio && !ratio_keep(sqdist[2 * i], sqdist[2 * i + 1], nearest[2 * i + 1], f)) continue;
+        if (back && !cross_keep(i, j, back)) continue;
+        pairs.push_back((int32_t)i);
+        pairs.push_back(j);
+        dists.push_back(sqdist[2 * i]);
+    }
+}
+
+// The same list for the int32 distances of dlco_desc_match_u8.
+inline void select(int64_t nq, const int32_t *nearest, const int32_t *sqdist, bool use_ratio, float f, const int32_t *back,
+                   std::vector<int32_t> &pairs, std::vector<int32_t> &dists)
 {
     pairs.clear();
     dists.clear();

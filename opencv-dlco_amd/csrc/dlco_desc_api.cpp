@@ -2,11 +2,13 @@
 // dlco_desc_* block of include/dlco.h.  Host orchestration and the filter selection of
 // SelectPRFilters (src/misc.cpp:78-168, pure host logic); the patch transform, the pooling product and
 // the pair differences run in HIP kernels (kernels_desc.hip), the projection by a learnt W and the distances
-// of projected descriptors in kernels_describe.hip, the sampling of patches around keypoints in kernels_patch.hip.
+// of projected descriptors in kernels_describe.hip, the sampling of patches around keypoints in kernels_patch.hip, the
+// quantisation of rows to bytes (quant_rules.hpp) and the match of byte tables in kernels_match_u8.hip.
 #include "../../include/dlco.h"
 
 #include "dlco_internal.hpp"
 #include "patch_rules.hpp"
+#include "quant_rules.hpp"
 
 #include <algorithm>
 #include <cmath>
@@ -40,6 +42,14 @@ struct dlco_desc_ctx {
     DevBuf<float> m_query, m_train, m_sqdist, m_cross;     // uploaded tables (host forms), the result of a chunk, the matrix
     DevBuf<int32_t> m_idx, m_part;                         // m_part: [slices][nq] partial (d1, j1, d2, j2), 16 bytes each
     DevBuf<double> m_qnorm, m_tnorm;
+    // the quantiser of the _u8 forms of describe (quant_rules.hpp): scale, offsets [q_r] on the device; q_r == 0: none
+    int q_r = 0;
+    float q_scale = 1.f;
+    DevBuf<float> q_off;
+    DevBuf<uint8_t> u8_chunk;                              // the bytes of one chunk on their way to the host
+    // matching byte tables (dlco_desc_match_u8*): again buffers of their own; u_part as m_part, under the integer key
+    DevBuf<uint8_t> u_query, u_train;
+    DevBuf<int32_t> u_idx, u_sqdist, u_cross, u_part, u_qnorm, u_tneg;
     // keypoint calls (dlco_desc_set_image* and after): the image, copied (img_own) or the caller's, and a chunk's frames
     const uint8_t *img = nullptr;
     int img_w = 0, img_h = 0;
@@ -112,26 +122,32 @@ void sample_chunk(dlco_desc_ctx *c, const patch_rules::Frame *frames_host, int c
 // With `project` a row is the learnt descriptor W * Desc (r floats): the un-projected rows of a chunk stay in the
 // library's scratch buffer and the projection kernel follows the pooling product on the same stream.  The rows of
 // invalid frames are zeroed behind the last kernel.
-void compute(dlco_desc_ctx *c, const PatchSource &src, int64_t n, float *dst, bool dst_dev, long ld, bool project = false)
+//   With dst_u8 (and project) the float rows of a chunk stay in the scratch as well, and one elementwise kernel behind
+// the zeroing turns them into bytes by the context's quantiser: r bytes per row of pitch ld bytes.  dst is not used then.
+void compute(dlco_desc_ctx *c, const PatchSource &src, int64_t n, float *dst, bool dst_dev, long ld, bool project = false,
+             uint8_t *dst_u8 = nullptr)
 {
     DLCO_CHECK(c->nsel > 0, DLCO_ERR_INVALID, "dlco_desc: set the filters first");
     const int F = c->nsel * kBins;
     DLCO_CHECK(!project || (c->r > 0 && c->proj_F == F), DLCO_ERR_INVALID, "dlco_desc: set a projection that fits the filters first");
     const int cols = project ? c->r : F;                   // floats per output row
+    DLCO_CHECK(!dst_u8 || (c->q_r > 0 && c->q_r == c->r), DLCO_ERR_INVALID, "dlco_desc: set a quantiser that fits the projection first");
     DLCO_CHECK(ld >= cols, DLCO_ERR_INVALID, project ? "dlco_desc: row pitch below the projected size" : "dlco_desc: row pitch below the descriptor size");
     DLCO_HIP(hipSetDevice(c->device));
     c->patches.alloc((size_t)kChunk * kPix);
     c->pt.alloc((size_t)kChunk * kBins * kPix);
     if (src.frames) c->frames.alloc((size_t)kChunk);
     if (!dst_dev || project) c->desc_chunk.alloc((size_t)kChunk * F);
-    if (!dst_dev && project) c->y_chunk.alloc((size_t)kChunk * cols);
+    if ((!dst_dev || dst_u8) && project) c->y_chunk.alloc((size_t)kChunk * cols);
+    if (dst_u8 && !dst_dev) c->u8_chunk.alloc((size_t)kChunk * cols);
     EventPair ev;
     double ms_total = 0.0;
     for (int64_t p0 = 0; p0 < n; p0 += kChunk) {
         const int cnt = (int)std::min<int64_t>(kChunk, n - p0);
         upload_chunk(c, src, p0, cnt);
-        float *out = dst_dev ? dst + p0 * ld : (project ? c->y_chunk.p : c->desc_chunk.p);
-        const long old = dst_dev ? ld : cols;
+        const bool to_caller = dst_dev && !dst_u8;          // the kernels write the caller's float rows directly
+        float *out = to_caller ? dst + p0 * ld : (project ? c->y_chunk.p : c->desc_chunk.p);
+        const long old = to_caller ? ld : cols;
         ms_total += timed_ms(c, ev, [&] {
             if (src.frames) sample_chunk(c, src.frames + p0, cnt);
             desc_transform(c->patches.p, cnt, c->cf.p, c->ks, c->inv_step, c->norm, c->qk, c->qgamma, c->pt.p, c->stream);
@@ -144,20 +160,30 @@ void compute(dlco_desc_ctx *c, const PatchSource &src, int64_t n, float *dst, bo
         }, [&] {
             for (int i = 0; src.frames && i < cnt; i++)
                 if (!src.frames[p0 + i].valid) DLCO_HIP(hipMemsetAsync(out + (size_t)i * old, 0, (size_t)cols * sizeof(float), c->stream));
-            if (!dst_dev)
+            if (!dst_dev && !dst_u8)
                 DLCO_HIP(hipMemcpy2DAsync(dst + p0 * ld, (size_t)ld * sizeof(float), out, (size_t)cols * sizeof(float),
                                           (size_t)cols * sizeof(float), (size_t)cnt, hipMemcpyDeviceToHost, c->stream));
         });
+        if (dst_u8) {
+            uint8_t *bytes = dst_dev ? dst_u8 + p0 * ld : c->u8_chunk.p;
+            const long bld = dst_dev ? ld : cols;
+            ms_total += timed_ms(c, ev, [&] { desc_quantize_rows(out, old, cnt, cols, c->q_scale, c->q_off.p, bytes, bld, c->stream); }, [&] {
+                if (!dst_dev)
+                    DLCO_HIP(hipMemcpy2DAsync(dst_u8 + p0 * ld, (size_t)ld, bytes, (size_t)cols, (size_t)cols, (size_t)cnt, hipMemcpyDeviceToHost,
+                                              c->stream));
+            });
+        }
     }
     c->last_ms = ms_total;
 }
 
 // the same for patches [n,64,64] on the host
-void compute(dlco_desc_ctx *c, const uint8_t *patches_host, int64_t n, float *dst, bool dst_dev, long ld, bool project = false)
+void compute(dlco_desc_ctx *c, const uint8_t *patches_host, int64_t n, float *dst, bool dst_dev, long ld, bool project = false,
+             uint8_t *dst_u8 = nullptr)
 {
     PatchSource src;
     src.host = patches_host;
-    compute(c, src, n, dst, dst_dev, ld, project);
+    compute(c, src, n, dst, dst_dev, ld, project, dst_u8);
 }
 
 }  // namespace
@@ -464,6 +490,7 @@ int dlco_desc_set_projection(dlco_desc_ctx *c, const float *W_host, int32_t r, i
         DLCO_HIP(hipMemcpyAsync(c->W.p, W_host, (size_t)r * F * sizeof(float), hipMemcpyHostToDevice, c->stream));
         sync(c);
         c->r = r; c->proj_F = F; c->proj_dim = dim;
+        if (c->q_r != r) c->q_r = 0;                       // a quantiser of another width no longer fits
     });
 }
 
@@ -508,13 +535,13 @@ void keypoint_frames(const dlco_desc_ctx *c, const float *keypoints, int64_t n, 
 }
 
 void describe_keypoints(dlco_desc_ctx *c, const float *keypoints, int64_t n, float scale_factor, bool use_orientation, float *dst, bool dst_dev,
-                        long ld, uint8_t *status)
+                        long ld, uint8_t *status, uint8_t *dst_u8 = nullptr)
 {
     std::vector<patch_rules::Frame> frames;
     keypoint_frames(c, keypoints, n, scale_factor, use_orientation, status, frames);
     PatchSource src;
     src.frames = frames.data();
-    compute(c, src, n, dst, dst_dev, ld, true);
+    compute(c, src, n, dst, dst_dev, ld, true, dst_u8);
 }
 }  // namespace
 
@@ -749,9 +776,166 @@ int dlco_desc_cross_sqdists(dlco_desc_ctx *c, const float *query_host, int64_t n
     return guarded(c, [&] { match_host(c, query_host, nq, train_host, nt, r, nullptr, nullptr, out_host); });
 }
 
+// ---- byte descriptors: the quantiser (quant_rules.hpp), the _u8 forms of describe, the match of byte tables -------------------
+// o_k = min_i Y[i][k], s = 255 / max_k (max_i Y[i][k] - o_k) or 1: host only
+int dlco_desc_quant_fit(const float *Y_host, int64_t n, int32_t r, float *scale, float *offset_out)
+{
+    if (!Y_host || !scale || !offset_out || n < 1 || r < 1 || r > quant_rules::kMaxDim) return DLCO_ERR_INVALID;
+    return quant_rules::fit(Y_host, n, r, scale, offset_out) ? DLCO_OK : DLCO_ERR_INVALID;
+}
+
+// bytes [n, r] of Y [n, r] by the rule of quant_rules.hpp: host only
+int dlco_desc_quantize(const float *Y_host, int64_t n, int32_t r, float scale, const float *offset, uint8_t *out_u8)
+{
+    if (!Y_host || !out_u8 || n < 1 || r < 1 || r > quant_rules::kMaxDim || !quant_rules::scale_ok(scale)) return DLCO_ERR_INVALID;
+    for (int k = 0; offset && k < r; k++)
+        if (!std::isfinite(offset[k])) return DLCO_ERR_INVALID;
+    quant_rules::quantize(Y_host, n, r, scale, offset, out_u8);
+    return DLCO_OK;
+}
+
+int dlco_desc_set_quantizer(dlco_desc_ctx *c, float scale, const float *offset, int32_t r)
+{
+    if (!c || r < 1 || r > quant_rules::kMaxDim || !quant_rules::scale_ok(scale)) return DLCO_ERR_INVALID;
+    for (int k = 0; offset && k < r; k++)
+        if (!std::isfinite(offset[k])) return DLCO_ERR_INVALID;
+    return guarded(c, [&] {
+        DLCO_HIP(hipSetDevice(c->device));
+        c->q_r = 0;
+        c->q_off.alloc((size_t)r);
+        if (offset) DLCO_HIP(hipMemcpyAsync(c->q_off.p, offset, (size_t)r * sizeof(float), hipMemcpyHostToDevice, c->stream));
+        else DLCO_HIP(hipMemsetAsync(c->q_off.p, 0, (size_t)r * sizeof(float), c->stream));
+        sync(c);
+        c->q_scale = scale; c->q_r = r;
+    });
+}
+
+// dlco_desc_quantize of dlco_desc_describe's rows, quantised on the device
+int dlco_desc_describe_u8(dlco_desc_ctx *c, const uint8_t *patches_host, int64_t n, uint8_t *out_host)
+{
+    if (!c || !patches_host || !out_host || n < 1) return DLCO_ERR_INVALID;
+    return guarded(c, [&] { compute(c, patches_host, n, nullptr, false, (long)c->r, true, out_host); });
+}
+
+int dlco_desc_describe_u8_device(dlco_desc_ctx *c, const uint8_t *patches_host, int64_t n, uint8_t *out_dev, int64_t ld)
+{
+    if (!c || !patches_host || !out_dev || n < 1) return DLCO_ERR_INVALID;
+    return guarded(c, [&] { compute(c, patches_host, n, nullptr, true, (long)ld, true, out_dev); });
+}
+
+// the same of dlco_desc_describe_keypoints' rows: a row of status 0 is the quantisation of the zero vector
+int dlco_desc_describe_keypoints_u8(dlco_desc_ctx *c, const float *keypoints_host, int64_t n, float scale_factor, int32_t use_orientation,
+                                    uint8_t *out_host, uint8_t *status_host)
+{
+    if (!c || !out_host || !keypoint_args_ok(keypoints_host, n, scale_factor)) return DLCO_ERR_INVALID;
+    return guarded(c, [&] {
+        describe_keypoints(c, keypoints_host, n, scale_factor, use_orientation != 0, nullptr, false, (long)c->r, status_host, out_host);
+    });
+}
+
+int dlco_desc_describe_keypoints_u8_device(dlco_desc_ctx *c, const float *keypoints_host, int64_t n, float scale_factor,
+                                           int32_t use_orientation, uint8_t *out_dev, int64_t ld, uint8_t *status_host)
+{
+    if (!c || !out_dev || !keypoint_args_ok(keypoints_host, n, scale_factor)) return DLCO_ERR_INVALID;
+    return guarded(c, [&] {
+        describe_keypoints(c, keypoints_host, n, scale_factor, use_orientation != 0, nullptr, true, (long)ld, status_host, out_dev);
+    });
+}
+
+namespace {
+// device tables in, device results out; adds the kernels' time to *ms.  u_tneg holds -|a_t|^2 already.
+void match_u8_on_device(dlco_desc_ctx *c, const uint8_t *q, long ldq, int64_t nq, const uint8_t *t, long ldt, int64_t nt, int r, int32_t *idx,
+                        int32_t *sqdist, int32_t *cross, double *ms)
+{
+    EventPair ev;
+    for (int64_t q0 = 0; q0 < nq; q0 += kMatchRows) {
+        const int cnt = (int)std::min(kMatchRows, nq - q0);
+        const int tps = match_u8_tiles_per_slice(cnt, nt, c->n_cu), slices = match_u8_slices(nt, tps);
+        c->u_qnorm.alloc((size_t)cnt);
+        if (!cross && slices > 1) c->u_part.alloc((size_t)slices * cnt * 4);
+        *ms += timed_ms(c, ev, [&] {
+            match_u8_norms(q + q0 * ldq, ldq, cnt, r, false, c->u_qnorm.p, c->stream);
+            match_u8_top2(q + q0 * ldq, ldq, cnt, t, ldt, (int)nt, r, c->u_qnorm.p, c->u_tneg.p, tps, idx ? idx + 2 * q0 : nullptr,
+                          sqdist ? sqdist + 2 * q0 : nullptr, c->u_part.p, cross ? cross + q0 * nt : nullptr, c->stream);
+        });
+    }
+}
+
+double train_norms_u8(dlco_desc_ctx *c, const uint8_t *t, long ldt, int64_t nt, int r)
+{
+    EventPair ev;
+    c->u_tneg.alloc((size_t)nt);
+    return timed_ms(c, ev, [&] { match_u8_norms(t, ldt, nt, r, true, c->u_tneg.p, c->stream); });
+}
+
+// the host forms: train wholly in HBM, the queries a chunk at a time; rows of r bytes go up to rows of pitch ceil(r/16)*16
+void match_u8_host(dlco_desc_ctx *c, const uint8_t *query_host, int64_t nq, const uint8_t *train_host, int64_t nt, int r, int32_t *idx_host,
+                   int32_t *sqdist_host, int32_t *cross_host)
+{
+    DLCO_HIP(hipSetDevice(c->device));
+    const long ld = (r + 15) / 16 * 16;
+    // queries per chunk: 256 MB of rows, and for the matrix 2^28 entries at most
+    const int64_t qchunk = std::max<int64_t>(1, std::min<int64_t>(nq, ((int64_t)1 << 28) / ld));
+    try {
+        c->u_train.alloc((size_t)nt * ld);
+        c->u_query.alloc((size_t)qchunk * ld);
+        if (cross_host) c->u_cross.alloc((size_t)qchunk * nt);
+        else { c->u_idx.alloc((size_t)qchunk * 2); c->u_sqdist.alloc((size_t)qchunk * 2); }
+    } catch (const Error &e) {
+        throw Error(DLCO_ERR_HIP, std::string("dlco_desc_match_u8: the tables do not fit in device memory: ") + e.what());
+    }
+    DLCO_HIP(hipMemcpy2DAsync(c->u_train.p, (size_t)ld, train_host, (size_t)r, (size_t)r, (size_t)nt, hipMemcpyHostToDevice, c->stream));
+    double ms = train_norms_u8(c, c->u_train.p, ld, nt, r);
+    for (int64_t q0 = 0; q0 < nq; q0 += qchunk) {
+        const int64_t cnt = std::min(qchunk, nq - q0);
+        DLCO_HIP(hipMemcpy2DAsync(c->u_query.p, (size_t)ld, query_host + q0 * r, (size_t)r, (size_t)r, (size_t)cnt, hipMemcpyHostToDevice, c->stream));
+        if (cross_host) {
+            match_u8_on_device(c, c->u_query.p, ld, cnt, c->u_train.p, ld, nt, r, nullptr, nullptr, c->u_cross.p, &ms);
+            DLCO_HIP(hipMemcpyAsync(cross_host + q0 * nt, c->u_cross.p, (size_t)cnt * nt * sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
+        } else {
+            match_u8_on_device(c, c->u_query.p, ld, cnt, c->u_train.p, ld, nt, r, c->u_idx.p, c->u_sqdist.p, nullptr, &ms);
+            DLCO_HIP(hipMemcpyAsync(idx_host + 2 * q0, c->u_idx.p, (size_t)cnt * 2 * sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
+            DLCO_HIP(hipMemcpyAsync(sqdist_host + 2 * q0, c->u_sqdist.p, (size_t)cnt * 2 * sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
+        }
+        sync(c);
+    }
+    c->last_ms = ms;
+}
+}  // namespace
+
+int dlco_desc_match_u8(dlco_desc_ctx *c, const uint8_t *query_u8, int64_t nq, const uint8_t *train_u8, int64_t nt, int32_t r, int32_t *idx_host,
+                       int32_t *sqdist_host)
+{
+    if (!c || !match_args_ok(query_u8, train_u8, idx_host, sqdist_host, nq, nt, r)) return DLCO_ERR_INVALID;
+    return guarded(c, [&] { match_u8_host(c, query_u8, nq, train_u8, nt, r, idx_host, sqdist_host, nullptr); });
+}
+
+int dlco_desc_match_u8_device(dlco_desc_ctx *c, const uint8_t *query_dev, int64_t ldq, int64_t nq, const uint8_t *train_dev, int64_t ldt,
+                              int64_t nt, int32_t r, int32_t *idx_dev, int32_t *sqdist_dev)
+{
+    if (!c || !match_args_ok(query_dev, train_dev, idx_dev, sqdist_dev, nq, nt, r)) return DLCO_ERR_INVALID;
+    if (ldq < r || ldt < r || ldq % 16 != 0 || ldt % 16 != 0) return DLCO_ERR_INVALID;
+    if (((uintptr_t)query_dev | (uintptr_t)train_dev) % 16 != 0) return DLCO_ERR_INVALID;          // 16-byte pieces
+    return guarded(c, [&] {
+        DLCO_HIP(hipSetDevice(c->device));
+        double ms = train_norms_u8(c, train_dev, (long)ldt, nt, r);
+        match_u8_on_device(c, query_dev, (long)ldq, nq, train_dev, (long)ldt, nt, r, idx_dev, sqdist_dev, nullptr, &ms);
+        c->last_ms = ms;
+    });
+}
+
+int dlco_desc_cross_sqdists_u8(dlco_desc_ctx *c, const uint8_t *query_u8, int64_t nq, const uint8_t *train_u8, int64_t nt, int32_t r,
+                               int32_t *out_host)
+{
+    if (!c || !match_args_ok(query_u8, train_u8, out_host, out_host, nq, nt, r)) return DLCO_ERR_INVALID;
+    if (nq > ((int64_t)1 << 28) / nt) return DLCO_ERR_INVALID;
+    return guarded(c, [&] { match_u8_host(c, query_u8, nq, train_u8, nt, r, nullptr, nullptr, out_host); });
+}
+
 // milliseconds the kernels of the last dlco_desc_compute* / dlco_desc_describe* call took (HIP events): transform and
 // pooling, plus the projection for describe and the sampling for the keypoint calls (extract_patches: the sampling alone);
-// the pair calls add their distance kernel; after a match call, its kernels (norms, top two, merge)
+// the pair calls add their distance kernel; after a match call, float or byte, its kernels (norms, top two, merge); the _u8
+// forms of describe add their quantising kernel
 double dlco_desc_last_kernel_ms(const dlco_desc_ctx *c) { return c ? c->last_ms : 0.0; }
 
 }  // extern "C"

@@ -432,7 +432,14 @@ int match_tiles_per_slice(long nq, long nt, int n_cu);
 int match_slices(long nt, int tiles_per_slice);
 void match_top2(const float *query, long ldq, int nq, const float *train, long ldt, int nt, int r, const double *qnorm, const double *tnorm,
                 int tiles_per_slice, int32_t *idx, float *sqdist, void *part, float *out, hipStream_t s);
-// keypoint patches (kernels_patch.hip; the frames and the sampling rule are patch_rules.hpp)
+// byte descriptors (kernels_match_u8.hip; the quantiser is quant_rules.hpp): float rows to bytes, and the match of byte tables
+void desc_quantize_rows(const float *Y, long ldy, int n, int r, float scale, const float *offset, uint8_t *out, long ldo, hipStream_t s);
+void match_u8_norms(const uint8_t *x, long ld, long n, int r, bool negate, int32_t *norm, hipStream_t s);
+int match_u8_tiles_per_slice(long nq, long nt, int n_cu);
+int match_u8_slices(long nt, int tiles_per_slice);
+void match_u8_top2(const uint8_t *query, long ldq, int nq, const uint8_t *train, long ldt, int nt, int r, const int32_t *qnorm,
+                   const int32_t *tneg, int tiles_per_slice, int32_t *idx, int32_t *sqdist, void *part, int32_t *out, hipStream_t s);
+// keypoint patches (kernels_patch.hip;the frames and the sampling rule are patch_rules.hpp)
 int patch_stage_bytes(const patch_rules::Frame *frames_host, int n, int W, int H);
 void patch_sample(const uint8_t *img, int W, int H, long pitch, const patch_rules::Frame *frames, int n, uint8_t *patches, int lds_bytes,
                   hipStream_t s);

@@ -2,13 +2,21 @@
 the slices), one process, one warm-up call per shape, two timed repeats.  Prints one line per shape with milliseconds per
 call, the floor 2 nq nt r / 78.6 TFLOP/s (the f64 MFMA peak DESIGN prices desc_pool_kernel against) and their ratio, and, as
 the thing a user would write without this call, the time of a chunked float64 torch Q @ T.T + topk(2) on the same tables
-(torch events, same warm-up and repeats)."""
+(torch events, same warm-up and repeats).
+
+With --u8 the same tables are quantised to bytes (one scale, per-dimension offsets fitted on both, as dlco_desc_quant_fit
+does) and dlco_desc_match_u8_device is timed the same way; the line shows the float call's time of the same shape from the
+same run beside it, the int8 MFMA floor 2 nq nt r / 5.0 POP/s (twice the dense BF16 peak of 2.5 PF) and the share of it."""
 import importlib, os, sys
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch
 dlco = importlib.import_module("opencv-dlco_amd")
 
 PEAK = 78.6e12
+PEAK_I8 = 5.0e15
+U8 = "--u8" in sys.argv
+if U8:
+    sys.argv.remove("--u8")
 SHAPES = [(2048, 2048, 64), (8192, 8192, 64), (8192, 8192, 128), (100000, 100000, 128)]
 if len(sys.argv) > 1:
     SHAPES = [tuple(int(v) for v in a.split(",")) for a in sys.argv[1:]]
@@ -43,6 +51,27 @@ for nq, nt, r in SHAPES:
     for _ in range(2):
         call()
         ms.append(ctx.last_kernel_ms())
+    if U8:
+        lo = torch.minimum(Q.min(0).values, T.min(0).values)
+        scale = 255.0 / float(torch.maximum(Q.max(0).values, T.max(0).values).sub(lo).max())
+        ld = (r + 15) // 16 * 16
+        Qu, Tu = (torch.zeros((len(X), ld), dtype=torch.uint8, device="cuda:0") for X in (Q, T))
+        Qu[:, :r], Tu[:, :r] = (((X - lo) * scale).round().clamp(0, 255).to(torch.uint8) for X in (Q, T))
+        iu, du = torch.empty((nq, 2), dtype=torch.int32, device="cuda:0"), torch.empty((nq, 2), dtype=torch.int32, device="cuda:0")
+        torch.cuda.synchronize()
+        call8 = lambda: ctx.match_u8_device(Qu.data_ptr(), nq, Tu.data_ptr(), nt, r, iu.data_ptr(), du.data_ptr(), ldq=ld, ldt=ld)
+        call8()
+        ms8 = []
+        for _ in range(2):
+            call8()
+            ms8.append(ctx.last_kernel_ms())
+        agree = float((iu[:, 0] == idx[:, 0]).float().mean())
+        best8, best, floor8 = min(ms8), min(ms), 1e3 * 2.0 * nq * nt * r / PEAK_I8
+        print(f"match_u8 {nq} x {nt} r {r}: {best8:.3f} ms per call (repeats {ms8[0]:.3f} {ms8[1]:.3f}), int8 MFMA floor {floor8:.3f} ms, "
+              f"share of the floor {floor8 / best8:.3f}; float call {best:.3f} ms (repeats {ms[0]:.3f} {ms[1]:.3f}), {best / best8:.2f} x the "
+              f"byte call; nearest index agrees with the float call for {100 * agree:.3f} % of the queries", flush=True)
+        del T, Q, idx, d, Qu, Tu, iu, du
+        continue
     torch_route(Q, T)
     tms = []
     for _ in range(2):
