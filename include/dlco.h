@@ -421,7 +421,7 @@ int32_t dlco_desc_projected_size(const dlco_desc_ctx *ctx);               /* r, 
  * The device form writes r floats per row of pitch ld >= r and leaves the other ld - r untouched. */
 int  dlco_desc_describe(dlco_desc_ctx *ctx, const uint8_t *patches_host, int64_t n, float *out_host);
 int  dlco_desc_describe_device(dlco_desc_ctx *ctx, const uint8_t *patches_host, int64_t n, float *out_dev, int64_t ld);
-/* ---- From an image and a detector's keypoints: the patches are sampled on the device, so that image -> descriptors ->
+/* ---- From an image and a detector's keypoints (dlco_desc_detect below, or any other detector's): the patches are sampled on the device, so that image -> descriptors ->
  * dlco_desc_match_device never leaves HBM (a keypoint is 16 bytes on the way up, a ready patch 4 KiB).
  *   A keypoint is four floats (x, y, size, angle) with cv::KeyPoint's meaning: integer coordinates are pixel centres, angle
  * in degrees, a negative angle means none.  The patch covers size * scale_factor source pixels on a side; without
@@ -446,6 +446,28 @@ int  dlco_desc_describe_keypoints(dlco_desc_ctx *ctx, const float *keypoints_hos
                                   int32_t use_orientation, float *out_host, uint8_t *status_host);
 int  dlco_desc_describe_keypoints_device(dlco_desc_ctx *ctx, const float *keypoints_host, int64_t n, float scale_factor,
                                          int32_t use_orientation, float *out_dev, int64_t ld, uint8_t *status_host);
+/* ---- The keypoints themselves: a detector on the image of dlco_desc_set_image*, so that image -> keypoints -> descriptors
+ * -> matches runs on this library alone.  A multi-scale determinant of the Hessian on box filters over an integral image
+ * (the Fast-Hessian family, whose keypoint sizes the scale factor 6.25 belongs to), by a rule of this library's own, in
+ * integers and bit-exact on every machine: csrc/detect_rules.hpp states it.  It is NOT OpenCV's SURF; no orientation is
+ * assigned (every angle is -1) and the refinement is one parabola per axis.  Needs neither filters nor a projection.
+ *   n_octaves in 1 .. 4 (filter sides 9 .. 27, 15 .. 51, 27 .. 99, 51 .. 195 on grids of step 1, 2, 4, 8); a keypoint has a
+ * response R >= threshold >= 1, where R = 100 N(Dxx) N(Dyy) - 81 N(Dxy)^2 on box differences scaled by 256 / L^2: 6 553 600
+ * times a determinant in squared grey levels.  *n_found is the number of keypoints of the whole image (may be NULL); they
+ * are ordered by R descending, then by (octave, layer, row, column), and the first *n_out = min(n_found, max_keypoints) are
+ * returned in that order: keypoints [n_out][4] = (x, y, size, -1), what dlco_desc_extract_patches /
+ * dlco_desc_describe_keypoints* take, and response [n_out] (may be NULL).  Rows at and beyond *n_out are left untouched.
+ * An image too small for octave 0 (below 27 x 27, or without a candidate) is no error: *n_out = 0.  The integral image is
+ * kept with the image until the next dlco_desc_set_image*.  DLCO_ERR_INVALID: no image, n_octaves outside 1 .. 4,
+ * threshold < 1, max_keypoints < 1, keypoints or n_out NULL.
+ *   The device form writes to device memory (keypoints_dev 16-byte aligned); n_out and n_found are host pointers. */
+int  dlco_desc_detect(dlco_desc_ctx *ctx, int32_t n_octaves, int64_t threshold, int64_t max_keypoints, float *keypoints_host,
+                      int64_t *response_host, int64_t *n_out, int64_t *n_found);
+int  dlco_desc_detect_device(dlco_desc_ctx *ctx, int32_t n_octaves, int64_t threshold, int64_t max_keypoints, float *keypoints_dev,
+                             int64_t *response_dev, int64_t *n_out, int64_t *n_found);
+/* HIP-event time of the last detect call by stage, ms [6]: the integral image (0 when the call found it cached), octaves
+ * 0 .. 3, the selection (ordering and copy-out); the sum is dlco_desc_last_kernel_ms */
+int  dlco_desc_detect_stage_ms(const dlco_desc_ctx *ctx, double *ms);
 /* per pair ||Y[a] - Y[b]||^2 [n_pairs] and Label [n_pairs] (may be NULL) for pairs [n_pairs,4]: the distances
  * ComputePJStats forms as ||W (Desc1 - Desc2)||^2 from comp-uprjdists' N x F rows (src/misc.cpp:279-292), taken from
  * the table of projected descriptors instead; that table and the un-projected rows never leave HBM */
@@ -534,7 +556,8 @@ int dlco_desc_cross_sqdists_u8(dlco_desc_ctx *ctx, const uint8_t *query_u8, int6
 /* HIP-event time of the kernels of the last compute / describe call (transform, pooling, projection, and the sampling
  * for the keypoint calls; extract_patches: the sampling alone); the pair_sqdists /
  * pair_stats calls add their distance kernel; after a match / cross_sqdists call, float or _u8, the time of its kernels
- * (norms, tile loop, merge of the slices); the _u8 forms of describe add their quantising kernel */
+ * (norms, tile loop, merge of the slices); the _u8 forms of describe add their quantising kernel; after a detect call the
+ * detector's kernels (the integral image when the call formed it, the octaves, the selection) */
 double dlco_desc_last_kernel_ms(const dlco_desc_ctx *ctx);
 
 #ifdef __cplusplus

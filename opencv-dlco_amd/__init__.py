@@ -20,6 +20,7 @@ HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "dlco.h")
 OK, ERR_INVALID, ERR_HIP, ERR_NODEVICE, ERR_NOCONV, ERR_COMM = 0, -2, -3, -4, -5, -6
 BUF_DIST, BUF_GRAD, BUF_DFAVG, BUF_W, BUF_GATHER, BUF_DATA = 1, 2, 3, 4, 5, 6
 ALLGATHER_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_int32, C.c_size_t)
+DETECT_THRESHOLD = 100 * 100 * 256 * 256                 # the detector's R of a determinant of 100 (csrc/detect_rules.hpp)
 
 
 class DlcoError(RuntimeError):
@@ -147,6 +148,10 @@ def load():
     L.dlco_desc_extract_patches.argtypes = [vp, f32p, i64, C.c_float, C.c_int32, u8p, u8p]
     L.dlco_desc_describe_keypoints.argtypes = [vp, f32p, i64, C.c_float, C.c_int32, f32p, u8p]
     L.dlco_desc_describe_keypoints_device.argtypes = [vp, f32p, i64, C.c_float, C.c_int32, vp, i64, u8p]
+    i64p = C.POINTER(C.c_int64)
+    L.dlco_desc_detect.argtypes = [vp, C.c_int32, i64, i64, f32p, i64p, i64p, i64p]
+    L.dlco_desc_detect_device.argtypes = [vp, C.c_int32, i64, i64, vp, vp, i64p, i64p]
+    L.dlco_desc_detect_stage_ms.argtypes = [vp, C.POINTER(C.c_double)]
     L.dlco_desc_pair_sqdists.argtypes = [vp, u8p, i64, i32p, i64, f32p, u8p]
     L.dlco_desc_pair_stats.argtypes = [vp, u8p, i64, i32p, i64, C.POINTER(C.c_int32), C.POINTER(C.c_float), C.POINTER(C.c_double)]
     L.dlco_desc_match.argtypes = [vp, f32p, i64, f32p, i64, C.c_int32, i32p, f32p]
@@ -804,6 +809,30 @@ class DescContext:
         self._ck(self.L.dlco_desc_describe_keypoints_device(self.h, _p(k, f32p), k.shape[0], scale_factor, 1 if use_orientation else 0,
                                                             C.c_void_p(dev_ptr), ld or self.projected_size, _p(status, u8p)))
         return status
+
+    # ---- the keypoints themselves: a detector on the image set (csrc/detect_rules.hpp states the rule) ----
+    def detect(self, n_octaves=3, threshold=DETECT_THRESHOLD, max_keypoints=100000):
+        """(keypoints [n,4] f32 = (x, y, size, -1), response [n] i64, n_found) of the image set: the n = min(n_found,
+        max_keypoints) strongest keypoints, strongest first.  The default threshold is a determinant of 100 squared grey levels."""
+        kp, resp = np.empty((max(max_keypoints, 1), 4), np.float32), np.empty(max(max_keypoints, 1), np.int64)
+        n, found = C.c_int64(), C.c_int64()
+        self._ck(self.L.dlco_desc_detect(self.h, n_octaves, threshold, max_keypoints, _p(kp, f32p), _p(resp, C.POINTER(C.c_int64)),
+                                         C.byref(n), C.byref(found)))
+        return kp[:n.value].copy(), resp[:n.value].copy(), found.value
+
+    def detect_device(self, kp_ptr, resp_ptr, n_octaves=3, threshold=DETECT_THRESHOLD, max_keypoints=100000):
+        """The same rows into device memory: kp_ptr [max_keypoints][4] f32 (16-byte aligned), resp_ptr [max_keypoints] i64 or
+        None; returns (n, n_found).  Rows at and beyond n keep what they held."""
+        n, found = C.c_int64(), C.c_int64()
+        self._ck(self.L.dlco_desc_detect_device(self.h, n_octaves, threshold, max_keypoints, C.c_void_p(kp_ptr), C.c_void_p(resp_ptr),
+                                                C.byref(n), C.byref(found)))
+        return n.value, found.value
+
+    def detect_stage_ms(self):
+        """Kernel milliseconds of the last detect call: {"integral": (0 when cached), "octaves": [4], "selection":}."""
+        ms = (C.c_double * 6)()
+        self._ck(self.L.dlco_desc_detect_stage_ms(self.h, ms))
+        return {"integral": ms[0], "octaves": [ms[1], ms[2], ms[3], ms[4]], "selection": ms[5]}
 
     def pair_sqdists(self, patches, pairs):
         """Per pair ||y_a - y_b||^2 [n_pairs] f32 and labels [n_pairs] u8; the descriptors stay on the device."""

@@ -49,7 +49,7 @@ struct H5 {
     int (*H5Sclose)(hid_t) = nullptr;
     int (*H5Lexists)(hid_t, const char *, hid_t) = nullptr;
     int (*H5Eset_auto2)(hid_t, void *, void *) = nullptr;
-    hid_t native_float = -1, native_uchar = -1, native_int = -1;
+    hid_t native_float = -1, native_uchar = -1, native_int = -1, native_int64 = -1;
 
     bool load()
     {
@@ -81,8 +81,9 @@ struct H5 {
         hid_t *pf = reinterpret_cast<hid_t *>(dlsym(h, "H5T_NATIVE_FLOAT_g"));
         hid_t *pu = reinterpret_cast<hid_t *>(dlsym(h, "H5T_NATIVE_UCHAR_g"));
         hid_t *pi = reinterpret_cast<hid_t *>(dlsym(h, "H5T_NATIVE_INT_g"));
-        if (!pf || !pu || !pi) return false;
-        native_float = *pf; native_uchar = *pu; native_int = *pi;
+        hid_t *pl = reinterpret_cast<hid_t *>(dlsym(h, "H5T_NATIVE_INT64_g"));
+        if (!pf || !pu || !pi || !pl) return false;
+        native_float = *pf; native_uchar = *pu; native_int = *pi; native_int64 = *pl;
         return true;
     }
 };
@@ -152,8 +153,9 @@ template <typename T> struct ElemType;
 template <> struct ElemType<float>   { static const char *npy() { return "<f4"; } static H5::hid_t h5t(H5 &L) { return L.native_float; } };
 template <> struct ElemType<uint8_t> { static const char *npy() { return "|u1"; } static H5::hid_t h5t(H5 &L) { return L.native_uchar; } };
 template <> struct ElemType<int32_t> { static const char *npy() { return "<i4"; } static H5::hid_t h5t(H5 &L) { return L.native_int; } };
+template <> struct ElemType<int64_t> { static const char *npy() { return "<i8"; } static H5::hid_t h5t(H5 &L) { return L.native_int64; } };
 
-// Reads dataset `name` as f32, u8 or i32 into `out`; shape receives its dimensions.
+// Reads dataset `name` as f32, u8, i32 or i64 into `out`; shape receives its dimensions.
 template <typename T>
 void read_dataset(const std::string &path, const char *name, std::vector<size_t> &shape, std::vector<T> &out)
 {

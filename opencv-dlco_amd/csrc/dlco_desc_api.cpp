@@ -3,10 +3,12 @@
 // SelectPRFilters (src/misc.cpp:78-168, pure host logic); the patch transform, the pooling product and
 // the pair differences run in HIP kernels (kernels_desc.hip), the projection by a learnt W and the distances
 // of projected descriptors in kernels_describe.hip, the sampling of patches around keypoints in kernels_patch.hip, the
-// quantisation of rows to bytes (quant_rules.hpp) and the match of byte tables in kernels_match_u8.hip.
+// quantisation of rows to bytes (quant_rules.hpp) and the match of byte tables in kernels_match_u8.hip, the detection of
+// keypoints (detect_rules.hpp) in kernels_detect.hip.
 #include "../../include/dlco.h"
 
 #include "dlco_internal.hpp"
+#include "detect_rules.hpp"
 #include "patch_rules.hpp"
 #include "quant_rules.hpp"
 
@@ -56,6 +58,16 @@ struct dlco_desc_ctx {
     long img_pitch = 0;
     DevBuf<uint8_t> img_own;
     DevBuf<patch_rules::Frame> frames;
+    // the detector (dlco_desc_detect*): the integral image of the image set (d_S_valid: it is that image's), the survivors of
+    // the octaves and the scratch of their selection; d_cap survivors fit, and it only grows
+    bool d_S_valid = false;
+    DevBuf<uint32_t> d_S, d_seg, d_idx_a, d_idx_b, d_count;
+    DevBuf<uint64_t> d_pos, d_key_a, d_key_b;
+    DevBuf<int64_t> d_resp, d_resp_out;
+    DevBuf<float> d_kp, d_kp_out;
+    DevBuf<uint8_t> d_tmp;
+    size_t d_cap = 0;
+    double d_stage_ms[2 + detect_rules::kMaxOctaves] = {0};  // integral, the octaves, selection
     double last_ms = 0.0;
 };
 
@@ -552,6 +564,7 @@ int dlco_desc_set_image(dlco_desc_ctx *c, const uint8_t *image_host, int32_t wid
     return guarded(c, [&] {
         DLCO_HIP(hipSetDevice(c->device));
         c->img = nullptr;
+        c->d_S_valid = false;
         const size_t dpitch = ((size_t)width + 15) / 16 * 16;
         c->img_own.alloc(dpitch * (size_t)height);
         DLCO_HIP(hipMemcpy2DAsync(c->img_own.p, dpitch, image_host, (size_t)pitch, (size_t)width, (size_t)height, hipMemcpyHostToDevice, c->stream));
@@ -567,6 +580,7 @@ int dlco_desc_set_image_device(dlco_desc_ctx *c, const uint8_t *image_dev, int32
     return guarded(c, [&] {
         DLCO_HIP(hipSetDevice(c->device));
         c->img_own.release();
+        c->d_S_valid = false;
         c->img = image_dev; c->img_w = width; c->img_h = height; c->img_pitch = (long)pitch;
     });
 }
@@ -611,6 +625,94 @@ int dlco_desc_describe_keypoints_device(dlco_desc_ctx *c, const float *keypoints
 {
     if (!c || !out_dev || !keypoint_args_ok(keypoints_host, n, scale_factor)) return DLCO_ERR_INVALID;
     return guarded(c, [&] { describe_keypoints(c, keypoints_host, n, scale_factor, use_orientation != 0, out_dev, true, (long)ld, status_host); });
+}
+
+// ---- keypoints of the image set: the detector of detect_rules.hpp (kernels_detect.hip) ------------------------------------
+namespace {
+bool detect_args_ok(int32_t n_octaves, int64_t threshold, int64_t max_keypoints, const void *keypoints, const int64_t *n_out)
+{
+    return n_octaves >= 1 && n_octaves <= detect_rules::kMaxOctaves && threshold >= 1 && max_keypoints >= 1 && keypoints && n_out;
+}
+
+// The first min(n_found, max_keypoints) keypoints in the rule's order, to device memory (dst_dev) or to the host.  The
+// survivors of the octaves are counted even where their buffers are full: the octaves then run again with room for all.
+void detect(dlco_desc_ctx *c, int n_octaves, int64_t threshold, int64_t max_keypoints, float *kp_dst, int64_t *resp_dst, bool dst_dev,
+            int64_t *n_out, int64_t *n_found)
+{
+    DLCO_CHECK(c->img, DLCO_ERR_INVALID, "dlco_desc: set an image first");
+    DLCO_HIP(hipSetDevice(c->device));
+    const int W = c->img_w, H = c->img_h;
+    EventPair ev;
+    for (double &ms : c->d_stage_ms) ms = 0.0;
+    if (!c->d_S_valid) {
+        c->d_S.alloc((size_t)(H + 1) * (size_t)detect_integral_pitch(W));
+        c->d_seg.alloc(detect_colsum_count(W, H));
+        c->d_stage_ms[0] = timed_ms(c, ev, [&] { detect_integral(c->img, W, H, c->img_pitch, c->d_S.p, c->d_seg.p, c->stream); });
+        c->d_S_valid = true;
+    }
+    c->d_count.alloc(1);
+    size_t cap = std::max<size_t>(std::max<size_t>(c->d_cap, 1024), (size_t)W * (size_t)H / 128);
+    unsigned found = 0;
+    for (;;) {
+        c->d_pos.alloc(cap); c->d_resp.alloc(cap); c->d_kp.alloc(cap * 4);
+        c->d_cap = cap;
+        DLCO_HIP(hipMemsetAsync(c->d_count.p, 0, sizeof(unsigned), c->stream));
+        for (int o = 0; o < n_octaves; o++)
+            c->d_stage_ms[1 + o] += timed_ms(c, ev, [&] {
+                detect_octave(c->d_S.p, W, H, o, threshold, (unsigned)cap, c->d_count.p, c->d_pos.p, c->d_resp.p, c->d_kp.p, c->stream);
+            });
+        DLCO_HIP(hipMemcpyAsync(&found, c->d_count.p, sizeof(unsigned), hipMemcpyDeviceToHost, c->stream));
+        sync(c);
+        if (found <= cap) break;
+        cap = found;
+    }
+    const unsigned n = found, keep = (unsigned)std::min<int64_t>(n, max_keypoints);
+    if (keep > 0) {
+        c->d_key_a.alloc(n); c->d_key_b.alloc(n); c->d_idx_a.alloc(n); c->d_idx_b.alloc(n);
+        const size_t tmp_bytes = detect_select_bytes(n);
+        c->d_tmp.alloc(tmp_bytes + 256);
+        if (!dst_dev) { c->d_kp_out.alloc((size_t)keep * 4); if (resp_dst) c->d_resp_out.alloc(keep); }
+        float *kp_out = dst_dev ? kp_dst : c->d_kp_out.p;
+        int64_t *resp_out = !resp_dst ? nullptr : (dst_dev ? resp_dst : c->d_resp_out.p);
+        c->d_stage_ms[1 + detect_rules::kMaxOctaves] = timed_ms(c, ev, [&] {
+            detect_select(c->d_pos.p, c->d_resp.p, c->d_kp.p, n, keep, c->d_key_a.p, c->d_key_b.p, c->d_idx_a.p, c->d_idx_b.p, c->d_tmp.p, tmp_bytes,
+                          kp_out, resp_out, c->stream);
+        }, [&] {
+            if (dst_dev) return;
+            DLCO_HIP(hipMemcpyAsync(kp_dst, kp_out, (size_t)keep * 4 * sizeof(float), hipMemcpyDeviceToHost, c->stream));
+            if (resp_dst) DLCO_HIP(hipMemcpyAsync(resp_dst, resp_out, (size_t)keep * sizeof(int64_t), hipMemcpyDeviceToHost, c->stream));
+        });
+    }
+    *n_out = keep;
+    if (n_found) *n_found = n;
+    c->last_ms = std::accumulate(std::begin(c->d_stage_ms), std::end(c->d_stage_ms), 0.0);
+}
+}  // namespace
+
+// keypoints [n_out][4] = (x, y, size, -1) and their responses, strongest first; rows at and beyond *n_out are left untouched
+int dlco_desc_detect(dlco_desc_ctx *c, int32_t n_octaves, int64_t threshold, int64_t max_keypoints, float *keypoints_host,
+                     int64_t *response_host, int64_t *n_out, int64_t *n_found)
+{
+    if (!c || !detect_args_ok(n_octaves, threshold, max_keypoints, keypoints_host, n_out)) return DLCO_ERR_INVALID;
+    return guarded(c, [&] { detect(c, n_octaves, threshold, max_keypoints, keypoints_host, response_host, false, n_out, n_found); });
+}
+
+// the same into device memory; keypoints_dev is 16-byte aligned (a row is one store)
+int dlco_desc_detect_device(dlco_desc_ctx *c, int32_t n_octaves, int64_t threshold, int64_t max_keypoints, float *keypoints_dev,
+                            int64_t *response_dev, int64_t *n_out, int64_t *n_found)
+{
+    if (!c || !detect_args_ok(n_octaves, threshold, max_keypoints, keypoints_dev, n_out)) return DLCO_ERR_INVALID;
+    if ((uintptr_t)keypoints_dev % 16 != 0 || (uintptr_t)response_dev % 8 != 0) return DLCO_ERR_INVALID;
+    return guarded(c, [&] { detect(c, n_octaves, threshold, max_keypoints, keypoints_dev, response_dev, true, n_out, n_found); });
+}
+
+// milliseconds of the last detect call by stage: ms[0] the integral image (0 when it was cached), ms[1 .. 4] the octaves,
+// ms[5] the selection; their sum is dlco_desc_last_kernel_ms
+int dlco_desc_detect_stage_ms(const dlco_desc_ctx *c, double *ms)
+{
+    if (!c || !ms) return DLCO_ERR_INVALID;
+    for (int i = 0; i < 2 + detect_rules::kMaxOctaves; i++) ms[i] = c->d_stage_ms[i];
+    return DLCO_OK;
 }
 
 namespace {
@@ -935,7 +1037,8 @@ int dlco_desc_cross_sqdists_u8(dlco_desc_ctx *c, const uint8_t *query_u8, int64_
 // milliseconds the kernels of the last dlco_desc_compute* / dlco_desc_describe* call took (HIP events): transform and
 // pooling, plus the projection for describe and the sampling for the keypoint calls (extract_patches: the sampling alone);
 // the pair calls add their distance kernel; after a match call, float or byte, its kernels (norms, top two, merge); the _u8
-// forms of describe add their quantising kernel
+// forms of describe add their quantising kernel; after a detect call the detector's kernels (the integral image when the call
+// formed it, the octaves, the selection)
 double dlco_desc_last_kernel_ms(const dlco_desc_ctx *c) { return c ? c->last_ms : 0.0; }
 
 }  // extern "C"

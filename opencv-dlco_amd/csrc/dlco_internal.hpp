@@ -443,5 +443,15 @@ void match_u8_top2(const uint8_t *query, long ldq, int nq, const uint8_t *train,
 int patch_stage_bytes(const patch_rules::Frame *frames_host, int n, int W, int H);
 void patch_sample(const uint8_t *img, int W, int H, long pitch, const patch_rules::Frame *frames, int n, uint8_t *patches, int lds_bytes,
                   hipStream_t s);
+// the detector (kernels_detect.hip; the rule is detect_rules.hpp): the integral image S [(H+1)][detect_integral_pitch(W)] u32,
+// the keypoints of an octave appended through a counter, and the first rows of the survivors in the rule's order
+long detect_integral_pitch(int W);
+size_t detect_colsum_count(int W, int H);
+void detect_integral(const uint8_t *img, int W, int H, long pitch, uint32_t *S, uint32_t *seg, hipStream_t s);
+void detect_octave(const uint32_t *S, int W, int H, int o, int64_t threshold, unsigned cap, unsigned *count, uint64_t *pos, int64_t *resp,
+                   float *kp, hipStream_t s);
+size_t detect_select_bytes(size_t n);
+void detect_select(const uint64_t *pos, const int64_t *resp, const float *kp, unsigned n, unsigned n_out, uint64_t *key_a, uint64_t *key_b,
+                   uint32_t *idx_a, uint32_t *idx_b, void *tmp, size_t tmp_bytes, float *kp_out, int64_t *resp_out, hipStream_t s);
 
 }  // namespace dlco
