@@ -8,7 +8,8 @@
 //                         are read, a train tile when it is stored to LDS), rounded to float once; then either the running top two per query
 //                         under the key (float distance, train index), or (STORE) the matrix itself: one tile loop, two
 //                         epilogues, so the matrix and the top two cannot disagree
-//   match_merge_kernel    the top two of a query over the S slices of train, under the same key
+//   match_merge_kernel    the top two of a query over the S slices of train, under the same key (the slicing rule:
+//                         match_slices.hpp)
 //
 // The key is a total order and the slices hold disjoint train rows, so the result does not depend on the grouping.
 // An entry's accumulation is one chain of MFMAs over k in an order fixed by r: it depends neither on where the query
@@ -18,6 +19,7 @@
 // ceil(r / 4) * 4 <= ld, the elements at and beyond r are replaced by zeros.  Every load is unconditional and in
 // bounds (a row or piece beyond the edge reads a valid one and is replaced by zeros), stores are masked.
 #include "dlco_internal.hpp"
+#include "match_slices.hpp"
 
 namespace dlco {
 
@@ -34,8 +36,8 @@ namespace {
 // to registers one step ahead of its use and widened once, at the LDS store, so that no conversion sits between the MFMAs.  r <= 128 is one chunk per tile (the
 // case of every shipped model); beyond it (MULTI) the accumulators of all TN / 16 column blocks are kept over the
 // chunks of a tile and the A fragments are re-read per chunk: correct, not tuned.
-constexpr int MQ = 128;                // queries per workgroup
-constexpr int TN = 128;                // train rows per staged tile
+using match_slicing::MQ;                // queries per workgroup: 128 (match_slices.hpp, with the slicing rule)
+using match_slicing::TN;                // train rows per staged tile: 128
 constexpr int KC = 128;                // k per staged chunk
 constexpr int MP = KC + 2;             // LDS pitch in doubles: the 16-byte reads of 16 rows fall into 16 different bank groups
 constexpr int MTH = 512;
@@ -300,27 +302,6 @@ void match_norms(const float *x, long ld, long n, int r, double *norm, hipStream
     const long per = NTH / 64;
     hipLaunchKernelGGL(match_norms_kernel, dim3((unsigned)((n + per - 1) / per)), dim3(NTH), 0, s, x, ld, n, r, norm);
     DLCO_HIP(hipGetLastError());
-}
-
-// Slices of train for nq queries, whole tiles per slice.  One workgroup runs per CU.  First enough slices that every
-// CU has one (2048 x 2048: 16 query blocks x 16 one-tile slices took 41 us, x 4 four-tile slices 70).  Beyond that a
-// launch is a number of rounds of n_cu workgroups and the last round may be nearly empty (782 query blocks on 256 CUs:
-// 3.05 rounds take the time of 4; 100 000 x 100 000 at r = 128 went from 63.8 to 48.5 ms with three slices, 9.2 rounds):
-// enough slices for eight rounds keep that loss near a tenth, as long as a slice keeps four tiles (a workgroup's start -
-// its A fragments, the first tile's latency - is paid per slice).  Returns the tiles per slice; the slice count is
-// ceil(tiles / that).
-int match_tiles_per_slice(long nq, long nt, int n_cu)
-{
-    const long qblocks = (nq + MQ - 1) / MQ, tiles = (nt + TN - 1) / TN;
-    const long fill = std::min(tiles, (n_cu + qblocks - 1) / qblocks);
-    const long rounds = std::min(tiles / 4, (8L * n_cu + qblocks - 1) / qblocks);
-    const long want = std::max(1L, std::max(fill, rounds));
-    return (int)((tiles + want - 1) / want);
-}
-int match_slices(long nt, int tiles_per_slice)
-{
-    const long tiles = (nt + TN - 1) / TN;
-    return (int)((tiles + tiles_per_slice - 1) / tiles_per_slice);
 }
 
 // query [nq][ldq], train [nt][ldt], norms from match_norms.  out != nullptr: the matrix out[nq][nt]; else idx / sqdist

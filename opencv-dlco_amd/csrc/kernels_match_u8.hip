@@ -7,7 +7,7 @@
 //   match_u8_kernel         d(i,j) = |a_q|^2 + |a_t|^2 - 2 a_q.a_t in int32, the dot products on v_mfma_i32_16x16x64_i8;
 //                           then either the running top two per query, or (STORE) the matrix itself: one tile loop, two
 //                           epilogues, so the matrix and the top two cannot disagree
-//   match_u8_merge_kernel   the top two of a query over the S slices of train
+//   match_u8_merge_kernel   the top two of a query over the S slices of train (the slicing rule: match_slices.hpp)
 //
 // Everything is an integer: differences do not see the shift by 128, |a|^2 <= 1024 * 128^2 = 2^24 and every partial stays
 // below 2^26 in magnitude, so d is the exact sum_k (q_ik - t_jk)^2 <= 1024 * 255^2 and nothing depends on an order of
@@ -22,6 +22,7 @@
 // ceil(r / 16) * 16 <= ld, the bytes at and beyond r are replaced by zeros after the flip.  Every load is unconditional
 // and in bounds (a row or piece beyond the edge reads a valid one and is replaced by zeros), stores are masked.
 #include "dlco_internal.hpp"
+#include "match_slices.hpp"
 #include "quant_rules.hpp"
 
 namespace dlco {
@@ -39,10 +40,10 @@ namespace {
 // bytes [16 g, 16 g + 16) of every 64), so whatever order of k the instruction gives those bytes, it is the same on both
 // sides.  r <= 128 is one chunk per tile; beyond it (MULTI) the accumulators of all UT / 16 row blocks are kept over the
 // chunks of a tile and the query fragments are re-read per chunk: correct, not tuned.
-constexpr int UQ = 256;                // queries per workgroup
+using match_slicing::UQ;                // queries per workgroup: 256 (match_slices.hpp, with the slicing rule)
 constexpr int UWQ = 64;                // queries per wave
 constexpr int UQB = UWQ / 16;          // 16-query blocks per wave
-constexpr int UT = 128;                // train rows per staged tile
+using match_slicing::UT;                // train rows per staged tile: 128
 constexpr int UK = 128;                // bytes of k per staged chunk
 constexpr int UP = UK + 16;            // LDS pitch in bytes: the 16-byte reads of 16 rows fall into 16 different bank groups
 constexpr int UTH = 256;
@@ -308,24 +309,6 @@ void match_u8_norms(const uint8_t *x, long ld, long n, int r, bool negate, int32
     const long per = NTH / 64;
     hipLaunchKernelGGL(match_u8_norms_kernel, dim3((unsigned)((n + per - 1) / per)), dim3(NTH), 0, s, x, ld, n, r, negate ? 1 : 0, norm);
     DLCO_HIP(hipGetLastError());
-}
-
-// Slices of train for nq queries, whole tiles per slice: the rule of match_tiles_per_slice (kernels_match.hip) with this
-// kernel's numbers, which is why it is not that function: a query block is 256 rows, and a CU holds several workgroups
-// (37 KB of LDS, one wave per SIMD each), so twice the CUs are to be filled first and sixteen workgroups per CU keep the
-// loss of the last round small, as long as a slice keeps four tiles.
-int match_u8_tiles_per_slice(long nq, long nt, int n_cu)
-{
-    const long qblocks = (nq + UQ - 1) / UQ, tiles = (nt + UT - 1) / UT;
-    const long fill = std::min(tiles, (2L * n_cu + qblocks - 1) / qblocks);
-    const long rounds = std::min(tiles / 4, (16L * n_cu + qblocks - 1) / qblocks);
-    const long want = std::max(1L, std::max(fill, rounds));
-    return (int)((tiles + want - 1) / want);
-}
-int match_u8_slices(long nt, int tiles_per_slice)
-{
-    const long tiles = (nt + UT - 1) / UT;
-    return (int)((tiles + tiles_per_slice - 1) / tiles_per_slice);
 }
 
 // query [nq][ldq], train [nt][ldt], qnorm = |a_q|^2 and tneg = -|a_t|^2 from match_u8_norms.  out != nullptr: the matrix

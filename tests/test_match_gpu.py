@@ -113,7 +113,12 @@ def test_match_is_the_top_two_of_the_cross_matrix(ctx, nq, nt, r):
 # ---- 3. against the reference ---------------------------------------------------------------------------------------------
 @pytest.mark.parametrize("nq,nt,r", [(3000, 5000, r) for r in (1, 48, 64, 67, 128)] + [(1000, 20000, 64), (4100, 4100, 128)])
 def test_match_against_the_float64_reference(ctx, nq, nt, r):
-    Q, T, D, G = case(nq, nt, r)
+    check_against_the_reference(ctx, *case(nq, nt, r))
+
+
+def check_against_the_reference(ctx, Q, T, D, G):
+    """match(Q, T) against the reference's distances D and gates G; returns the library's (idx, d)."""
+    nq, nt, r = len(Q), len(T), Q.shape[1]
     o3 = top_by_key(D, 3)
     rows = np.arange(nq)[:, None]
     d3, g3 = D[rows, o3], G[rows, o3]
@@ -135,6 +140,7 @@ def test_match_against_the_float64_reference(ctx, nq, nt, r):
     assert not amb1[nq - 1] and not amb2[nq - 1] and not amb1[nq - 2]
     assert tuple(idx[nq - 1]) == (3, nt // 2) and d[nq - 1, 0] == d[nq - 1, 1]
     assert idx[nq - 2, 0] == 5
+    return idx, d
 
 
 # ---- 4. independence ----------------------------------------------------------------------------------------------------
@@ -175,6 +181,43 @@ def test_match_with_more_queries_than_one_slice_rule(ctx):
         order = top_by_key(X, 2)
         assert np.array_equal(idx, order.astype(np.int32)), (nq, nt, r)
         assert np.array_equal(d.view(np.uint32), X[np.arange(nq)[:, None], order].view(np.uint32)), (nq, nt, r)
+
+
+# ---- 4b. the loop over blocks of 2^20 queries -------------------------------------------------------------------------------
+BLOCK, BASE = 2 ** 20, 1009                                # queries per launch of the host loop; a prime period of repeated queries
+
+
+def test_match_over_the_query_block_loop(ctx):
+    """2^20 + 77 queries are two launches (the first: one slice that holds all six tiles of train, no merge; the second:
+    one-tile slices, merged), their results at an offset of 2^20 rows.  The queries repeat a base of 1009 rows: a row's
+    answer depends on the row alone (the test above), so row i carries the bits of row i mod 1009 of the base's own match,
+    and the base is held against the float64 reference like every other case."""
+    nq, nt, r = BLOCK + 77, 700, 4
+    Qb, T = make_tables(BASE, nt, r)
+    D = ref_dists(Qb, T)
+    bi, bd = check_against_the_reference(ctx, Qb, T, D, gate(Qb, T, D))
+    rep = np.arange(nq) % BASE
+    idx, d = ctx.match(Qb[rep], T)
+    bad = np.nonzero((idx != bi[rep]).any(1) | (d.view(np.uint32) != bd[rep].view(np.uint32)).any(1))[0]
+    print("match %d x %d r %d: %d rows differ from the base's" % (nq, nt, r, len(bad)))
+    assert len(bad) == 0, "rows %s differ; %s" % (bad[:8].tolist(), "; ".join(
+        "row %d: got %s / %s, want %s / %s" % (i, idx[i].tolist(), d[i].tolist(), bi[i % BASE].tolist(), bd[i % BASE].tolist())
+        for i in (BLOCK - 1, BLOCK, BLOCK + 76)))
+
+
+def test_cross_sqdists_over_the_query_block_loop(ctx):
+    nq, nt, r = BLOCK + 77, 40, 4
+    Qb, T = make_tables(BASE, nt, r)
+    D = ref_dists(Qb, T)
+    Xb = ctx.cross_sqdists(Qb, T)
+    assert (np.abs(Xb.astype(np.float64) - D) <= gate(Qb, T, D)).all() and (Xb >= 0).all()
+    rep = np.arange(nq) % BASE
+    X = ctx.cross_sqdists(Qb[rep], T)
+    want = Xb[rep]
+    bad = np.nonzero((X.view(np.uint32) != want.view(np.uint32)).any(1))[0]
+    print("cross_sqdists %d x %d r %d: %d rows differ from the base's" % (nq, nt, r, len(bad)))
+    assert len(bad) == 0, "rows %s differ; rows 2^20 - 1, 2^20, 2^20 + 76 equal: %s" % (
+        bad[:8].tolist(), [bool((X[i].view(np.uint32) == want[i].view(np.uint32)).all()) for i in (BLOCK - 1, BLOCK, BLOCK + 76)])
 
 
 def test_non_finite_inputs_keep_the_indices_in_range(ctx):

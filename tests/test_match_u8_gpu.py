@@ -210,6 +210,85 @@ def test_describe_keypoints_u8_is_quantize_of_describe_keypoints(dlco, model):
     assert Y2.tobytes() == Y.tobytes()
 
 
+# ---- 4b. the same across the boundary of a launch chunk (2048 patches) ------------------------------------------------------
+@pytest.fixture(scope="module")
+def tiny(dlco):
+    """The model of test_keypoints_gpu.py, the image and the 2048 + 5 keypoints of its test across the chunk boundary (an
+    invalid keypoint on each side), and the patches of those keypoints: all distinct but the two of the invalid ones."""
+    c = dlco.DescContext()
+    c.set_filters(make_filters(16, seed=4))
+    c.set_projection(make_w(12, 128, seed=2))
+    rng = np.random.default_rng(5)
+    img = rng.integers(0, 256, (80, 90), dtype=np.uint8)
+    n = 2048 + 5
+    kp = np.stack([rng.uniform(-5, 95, n), rng.uniform(-5, 85, n), rng.uniform(8, 40, n), rng.uniform(-30, 360, n)], axis=1).astype(np.float32)
+    kp[2047, 2] = 0
+    kp[2050, 0] = np.inf
+    c.set_image(img)
+    patches, st = c.extract_patches(kp, scale_factor=1.0)
+    assert (st == 0).tolist() == [i in (2047, 2050) for i in range(n)]
+    yield c, kp, patches, st
+    c.close()
+
+
+def rows_differ(got, want, rows=range(2046, 2053)):
+    bad = np.nonzero((got != want).any(1))[0]
+    return "%d rows differ, the first at %s; %s" % (len(bad), bad[:8].tolist(), "; ".join(
+        "row %d: got %s, want %s" % (i, got[i].tolist(), want[i].tolist()) for i in rows))
+
+
+def test_describe_u8_across_the_chunk_boundary(dlco, tiny):
+    import torch
+    model, _, patches, _ = tiny
+    n, r = len(patches), model.projected_size
+    assert n == 2048 + 5 and r == 12
+    Y = model.describe(patches)
+    scale, off = dlco.quant_fit(Y)
+    want = dlco.quantize(Y, scale, off)
+    assert want.min() == 0 and want.max() == 255 and len(np.unique(want, axis=0)) > 0.9 * n     # a row put in another place would show
+    model.set_quantizer(scale, off)
+    got = model.describe_u8(patches)
+    assert got.dtype == np.uint8 and got.shape == (n, r)
+    print("describe_u8 of %d patches: %d rows differ from quantize(describe)" % (n, (got != want).any(1).sum()))
+    assert np.array_equal(got, want), rows_differ(got, want)
+    ld = 16
+    buf = torch.full((n, ld), 0xA5, dtype=torch.uint8, device="cuda:0")
+    torch.cuda.synchronize()
+    model.describe_u8_device(patches, buf.data_ptr(), ld=ld)
+    torch.cuda.synchronize()
+    g = buf.cpu().numpy()
+    assert np.array_equal(g[:, :r], want), rows_differ(g[:, :r], want)
+    assert (g[:, r:] == 0xA5).all(), "padding overwritten in rows %s" % np.nonzero((g[:, r:] != 0xA5).any(1))[0][:8].tolist()
+
+
+def test_describe_keypoints_u8_across_the_chunk_boundary(dlco, tiny):
+    import torch
+    model, kp, _, st = tiny
+    n, r = len(kp), model.projected_size
+    Y, st1 = model.describe_keypoints(kp, scale_factor=1.0)
+    assert np.array_equal(st1, st) and (Y[st == 0] == 0).all()
+    scale, off = dlco.quant_fit(Y[st != 0])
+    off = off - np.float32(3.0) / np.float32(scale)                      # a zero row is then not a row of zero bytes
+    want = dlco.quantize(Y, scale, off)
+    zero_row = dlco.quantize(np.zeros((1, r), np.float32), scale, off)[0]
+    assert zero_row.any() and (want[[2047, 2050]] == zero_row).all()
+    model.set_quantizer(scale, off)
+    got, st2 = model.describe_keypoints_u8(kp, scale_factor=1.0)
+    assert np.array_equal(st2, st)
+    assert np.array_equal(got, want), rows_differ(got, want)
+    assert (got[st == 0] == zero_row).all() and (st == 0).sum() == 2
+    ld = 16
+    buf = torch.full((n, ld), 0x5A, dtype=torch.uint8, device="cuda:0")
+    torch.cuda.synchronize()
+    st3 = model.describe_keypoints_u8_device(kp, buf.data_ptr(), ld=ld, scale_factor=1.0)
+    torch.cuda.synchronize()
+    g = buf.cpu().numpy()
+    assert np.array_equal(st3, st)
+    assert np.array_equal(g[:, :r], want), rows_differ(g[:, :r], want)
+    assert (g[:, r:] == 0x5A).all(), "padding overwritten in rows %s" % np.nonzero((g[:, r:] != 0x5A).any(1))[0][:8].tolist()
+    assert (g[st == 0][:, :r] == zero_row).all()
+
+
 # ---- 5. nearest neighbours survive quantisation, with the derived bound ------------------------------------------------------
 @pytest.mark.parametrize("r", [64, 128])
 def test_nearest_neighbours_survive_quantisation(ctx, dlco, r):
