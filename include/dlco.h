@@ -449,8 +449,9 @@ int  dlco_desc_describe_keypoints_device(dlco_desc_ctx *ctx, const float *keypoi
 /* ---- The keypoints themselves: a detector on the image of dlco_desc_set_image*, so that image -> keypoints -> descriptors
  * -> matches runs on this library alone.  A multi-scale determinant of the Hessian on box filters over an integral image
  * (the Fast-Hessian family, whose keypoint sizes the scale factor 6.25 belongs to), by a rule of this library's own, in
- * integers and bit-exact on every machine: csrc/detect_rules.hpp states it.  It is NOT OpenCV's SURF; no orientation is
- * assigned (every angle is -1) and the refinement is one parabola per axis.  Needs neither filters nor a projection.
+ * integers and bit-exact on every machine: csrc/detect_rules.hpp states it.  It is NOT OpenCV's SURF; these two calls assign
+ * no orientation (every angle is -1: dlco_desc_detect_oriented and dlco_desc_orient below do) and the refinement is one
+ * parabola per axis.  Needs neither filters nor a projection.
  *   n_octaves in 1 .. 4 (filter sides 9 .. 27, 15 .. 51, 27 .. 99, 51 .. 195 on grids of step 1, 2, 4, 8); a keypoint has a
  * response R >= threshold >= 1, where R = 100 N(Dxx) N(Dyy) - 81 N(Dxy)^2 on box differences scaled by 256 / L^2: 6 553 600
  * times a determinant in squared grey levels.  *n_found is the number of keypoints of the whole image (may be NULL); they
@@ -468,6 +469,28 @@ int  dlco_desc_detect_device(dlco_desc_ctx *ctx, int32_t n_octaves, int64_t thre
 /* HIP-event time of the last detect call by stage, ms [6]: the integral image (0 when the call found it cached), octaves
  * 0 .. 3, the selection (ordering and copy-out); the sum is dlco_desc_last_kernel_ms */
 int  dlco_desc_detect_stage_ms(const dlco_desc_ctx *ctx, double *ms);
+/* ---- The orientation of keypoints, so that the chain is rotation invariant on this library alone: Haar-wavelet responses
+ * on the detector's integral image at 109 samples around the keypoint (scale s = round(size / 7.5) in 1 .. 128), weighted,
+ * binned into 36 directions, and the strongest window of 60 degrees; csrc/orient_rules.hpp states the rule.  It is NOT the
+ * orientation of OpenCV's SURF.  Everything up to the winning vector (SX, SY) is integer and bit-exact on every machine; the
+ * angle is atan2(SY, SX) in degrees in [0, 360), image axes with y down (what use_orientation above expects), computed on
+ * the host, and -1 (none: the patch is upright) for the vector (0, 0).
+ *   angles [n] of keypoints [n][4] on the context's image; the fourth column that comes in is ignored.  vectors [n][2]
+ * int64 and status [n] may be NULL; status 0: the keypoint is invalid (x, y or size not finite, size <= 0, |x| or |y| above
+ * 2^20: vector (0, 0), angle -1), 1: some of the 109 samples were skipped because their Haar square leaves the image, 2: all
+ * were used.  The integral image is formed if the context has none for its image and is shared with dlco_desc_detect*.
+ * DLCO_ERR_INVALID: no image, n < 1, keypoints or angles NULL.
+ *   Out of scope: a device-memory form of the oriented keypoints (the angle is defined through the host's atan2); more than
+ * one orientation per keypoint. */
+int  dlco_desc_orient(dlco_desc_ctx *ctx, const float *keypoints_host, int64_t n, float *angles_host, int64_t *vectors_host,
+                      uint8_t *status_host);
+/* dlco_desc_detect with the fourth column filled by the rule: the selected keypoints never leave the device before
+ * orientation.  The first three columns, the responses, *n_out and *n_found are dlco_desc_detect's; dlco_desc_detect_stage_ms
+ * keeps its six entries, dlco_desc_last_kernel_ms is their sum plus the orientation kernel. */
+int  dlco_desc_detect_oriented(dlco_desc_ctx *ctx, int32_t n_octaves, int64_t threshold, int64_t max_keypoints, float *keypoints_host,
+                               int64_t *response_host, int64_t *n_out, int64_t *n_found);
+/* HIP-event time of the last orientation kernel (dlco_desc_orient, dlco_desc_detect_oriented) */
+double dlco_desc_last_orient_ms(const dlco_desc_ctx *ctx);
 /* per pair ||Y[a] - Y[b]||^2 [n_pairs] and Label [n_pairs] (may be NULL) for pairs [n_pairs,4]: the distances
  * ComputePJStats forms as ||W (Desc1 - Desc2)||^2 from comp-uprjdists' N x F rows (src/misc.cpp:279-292), taken from
  * the table of projected descriptors instead; that table and the un-projected rows never leave HBM */
@@ -557,7 +580,8 @@ int dlco_desc_cross_sqdists_u8(dlco_desc_ctx *ctx, const uint8_t *query_u8, int6
  * for the keypoint calls; extract_patches: the sampling alone); the pair_sqdists /
  * pair_stats calls add their distance kernel; after a match / cross_sqdists call, float or _u8, the time of its kernels
  * (norms, tile loop, merge of the slices); the _u8 forms of describe add their quantising kernel; after a detect call the
- * detector's kernels (the integral image when the call formed it, the octaves, the selection) */
+ * detector's kernels (the integral image when the call formed it, the octaves, the selection; detect_oriented adds the
+ * orientation kernel); after an orient call the orientation kernel and the integral image when the call formed it */
 double dlco_desc_last_kernel_ms(const dlco_desc_ctx *ctx);
 
 #ifdef __cplusplus

@@ -152,6 +152,10 @@ def load():
     L.dlco_desc_detect.argtypes = [vp, C.c_int32, i64, i64, f32p, i64p, i64p, i64p]
     L.dlco_desc_detect_device.argtypes = [vp, C.c_int32, i64, i64, vp, vp, i64p, i64p]
     L.dlco_desc_detect_stage_ms.argtypes = [vp, C.POINTER(C.c_double)]
+    L.dlco_desc_orient.argtypes = [vp, f32p, i64, f32p, i64p, u8p]
+    L.dlco_desc_detect_oriented.argtypes = [vp, C.c_int32, i64, i64, f32p, i64p, i64p, i64p]
+    L.dlco_desc_last_orient_ms.argtypes = [vp]
+    L.dlco_desc_last_orient_ms.restype = C.c_double
     L.dlco_desc_pair_sqdists.argtypes = [vp, u8p, i64, i32p, i64, f32p, u8p]
     L.dlco_desc_pair_stats.argtypes = [vp, u8p, i64, i32p, i64, C.POINTER(C.c_int32), C.POINTER(C.c_float), C.POINTER(C.c_double)]
     L.dlco_desc_match.argtypes = [vp, f32p, i64, f32p, i64, C.c_int32, i32p, f32p]
@@ -819,6 +823,28 @@ class DescContext:
         self._ck(self.L.dlco_desc_detect(self.h, n_octaves, threshold, max_keypoints, _p(kp, f32p), _p(resp, C.POINTER(C.c_int64)),
                                          C.byref(n), C.byref(found)))
         return kp[:n.value].copy(), resp[:n.value].copy(), found.value
+
+    def detect_oriented(self, n_octaves=3, threshold=DETECT_THRESHOLD, max_keypoints=100000):
+        """detect with the fourth column filled by the orientation rule (csrc/orient_rules.hpp): (keypoints [n,4] f32 =
+        (x, y, size, angle), response [n] i64, n_found).  The keypoints are oriented before they leave the device."""
+        kp, resp = np.empty((max(max_keypoints, 1), 4), np.float32), np.empty(max(max_keypoints, 1), np.int64)
+        n, found = C.c_int64(), C.c_int64()
+        self._ck(self.L.dlco_desc_detect_oriented(self.h, n_octaves, threshold, max_keypoints, _p(kp, f32p), _p(resp, C.POINTER(C.c_int64)),
+                                                  C.byref(n), C.byref(found)))
+        return kp[:n.value].copy(), resp[:n.value].copy(), found.value
+
+    def orient(self, kp):
+        """(angles [n] f32, vectors [n,2] i64, status [n] u8) of keypoints [n,4] on the image set; the angle that comes in is
+        ignored.  An angle is in [0, 360) or -1 (none); status 0 invalid, 1 some samples skipped at the border, 2 all used."""
+        k = self._keypoints(kp)
+        n = k.shape[0]
+        angles, vectors, status = np.empty(n, np.float32), np.empty((n, 2), np.int64), np.empty(n, np.uint8)
+        self._ck(self.L.dlco_desc_orient(self.h, _p(k, f32p), n, _p(angles, f32p), _p(vectors, C.POINTER(C.c_int64)), _p(status, u8p)))
+        return angles, vectors, status
+
+    def last_orient_ms(self):
+        """Kernel milliseconds of the last orientation kernel (orient, detect_oriented)."""
+        return self.L.dlco_desc_last_orient_ms(self.h)
 
     def detect_device(self, kp_ptr, resp_ptr, n_octaves=3, threshold=DETECT_THRESHOLD, max_keypoints=100000):
         """The same rows into device memory: kp_ptr [max_keypoints][4] f32 (16-byte aligned), resp_ptr [max_keypoints] i64 or

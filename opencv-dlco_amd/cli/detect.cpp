@@ -1,13 +1,15 @@
 // detect — the keypoints of an image, over libdlco.so: the front of describe-image.
 //
-//     detect src_h5_img_file -out dst [-octaves n] [-threshold t] [-max n] [-device n]
+//     detect src_h5_img_file -out dst [-octaves n] [-threshold t] [-max n] [-device n] [-orient]
 //
 // src_h5_img_file holds "Image" [H,W] u8.  The detector is the library's own (the rule: csrc/detect_rules.hpp): a
 // multi-scale determinant of the Hessian on box filters, -octaves n of them (1 .. 4, default 3), keypoints with a response
 // of at least -threshold t (default 655360000: a determinant of 100 squared grey levels), the strongest -max n (default
-// 100000) strongest first.  It is not OpenCV's SURF and assigns no orientation: every angle is -1.  Writes
+// 100000) strongest first.  It is not OpenCV's SURF.  Without -orient it assigns no orientation: every angle is -1.  With
+// -orient every keypoint gets the angle of the library's orientation rule (csrc/orient_rules.hpp, dlco_desc_detect_oriented),
+// which describe-image uses unless it is given -upright.  Writes
 //     "Image" [H,W] u8           copied through
-//     "Keypoints" [n,4] f32      (x, y, size, -1): with "Image", what describe-image takes as its second argument
+//     "Keypoints" [n,4] f32      (x, y, size, angle): with "Image", what describe-image takes as its second argument
 //     "Response" [n] i64         the response of every keypoint, descending
 // and prints "Keypoints: n of n_found".
 // The reference has no such tool.  A path that does not end in .h5/.hdf5 is a directory of .npy files with the same
@@ -28,12 +30,13 @@ int main(int argc, char **argv)
 {
     int octaves = 3, device = 0;
     long long threshold = 655360000LL, max_kp = 100000;
-    bool help = false;
+    bool help = false, orient = false;
     const char *img = nullptr, *out = nullptr;
     for (int i = 1; i < argc; i++) {
         if (argv[i][0] == '-') {
             const bool has_val = i + 1 < argc;
             if (std::strcmp(argv[i], "-help") == 0) { help = true; continue; }
+            if (std::strcmp(argv[i], "-orient") == 0) { orient = true; continue; }
             if (std::strcmp(argv[i], "-out") == 0 && has_val) { out = argv[++i]; continue; }
             if (std::strcmp(argv[i], "-octaves") == 0 && has_val) { octaves = atoi(argv[++i]); continue; }
             if (std::strcmp(argv[i], "-threshold") == 0 && has_val) { threshold = atoll(argv[++i]); continue; }
@@ -59,6 +62,7 @@ int main(int argc, char **argv)
         cout << endl;
         cout << "Usage: detect src_h5_img_file -out dst_h5_filename" << endl;
         cout << "        [-octaves n] [-threshold t] [-max n] [-device n]" << endl;
+        cout << "        [-orient]      assign every keypoint its angle (default: every angle is -1)" << endl;
         cout << endl;
         return 1;
     }
@@ -81,7 +85,7 @@ int main(int argc, char **argv)
         std::vector<float> kp((size_t)rows * 4);
         std::vector<int64_t> resp((size_t)rows);
         int64_t n = 0, found = 0;
-        ck(dlco_desc_detect(ctx, octaves, threshold, rows, kp.data(), resp.data(), &n, &found));
+        ck((orient ? dlco_desc_detect_oriented : dlco_desc_detect)(ctx, octaves, threshold, rows, kp.data(), resp.data(), &n, &found));
         const double sec = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
         {
             dlco_io::Writer wr(out);

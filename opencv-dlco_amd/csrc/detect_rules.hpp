@@ -8,8 +8,9 @@
 // operations, and a total order of the keypoints, so that every keypoint is the same on every machine and the tests
 // compare with equality.
 //
-// Out of scope: orientation assignment (every angle is -1, so the describe calls give the same rows with and without
-// use_orientation); a 3-D quadratic fit (the refinement is one parabola per axis); a device-keypoint form of
+// Orientation is not part of this rule: every angle it gives is -1, so the describe calls give the same rows with and without
+// use_orientation.  orient_rules.hpp assigns angles (dlco_desc_orient, dlco_desc_detect_oriented).
+// Out of scope: a 3-D quadratic fit (the refinement is one parabola per axis); a device-keypoint form of
 // dlco_desc_describe_keypoints (a keypoint is 16 bytes: the rows go through the host).
 //
 // Integral image.  S[y][x] = sum of img[v][u] over v < y, u < x: (H+1) x (W+1) entries of uint32 with wrap-around.  The

@@ -4,11 +4,12 @@
 // the pair differences run in HIP kernels (kernels_desc.hip), the projection by a learnt W and the distances
 // of projected descriptors in kernels_describe.hip, the sampling of patches around keypoints in kernels_patch.hip, the
 // quantisation of rows to bytes (quant_rules.hpp) and the match of byte tables in kernels_match_u8.hip, the detection of
-// keypoints (detect_rules.hpp) in kernels_detect.hip.
+// keypoints (detect_rules.hpp) in kernels_detect.hip, their orientation (orient_rules.hpp) in kernels_orient.hip.
 #include "../../include/dlco.h"
 
 #include "dlco_internal.hpp"
 #include "detect_rules.hpp"
+#include "orient_rules.hpp"
 #include "patch_rules.hpp"
 #include "quant_rules.hpp"
 
@@ -68,6 +69,11 @@ struct dlco_desc_ctx {
     DevBuf<uint8_t> d_tmp;
     size_t d_cap = 0;
     double d_stage_ms[2 + detect_rules::kMaxOctaves] = {0};  // integral, the octaves, selection
+    // orientation (dlco_desc_orient, dlco_desc_detect_oriented): uploaded keypoints, vectors and status of the last call
+    DevBuf<float> o_kp;
+    DevBuf<int64_t> o_vec;
+    DevBuf<uint8_t> o_status;
+    double o_ms = 0.0;
     double last_ms = 0.0;
 };
 
@@ -634,22 +640,45 @@ bool detect_args_ok(int32_t n_octaves, int64_t threshold, int64_t max_keypoints,
     return n_octaves >= 1 && n_octaves <= detect_rules::kMaxOctaves && threshold >= 1 && max_keypoints >= 1 && keypoints && n_out;
 }
 
+// The integral image of the image set, formed unless it is cached; returns the milliseconds of its kernels, 0 when cached.
+double integral_image(dlco_desc_ctx *c, const EventPair &ev)
+{
+    if (c->d_S_valid) return 0.0;
+    const int W = c->img_w, H = c->img_h;
+    c->d_S.alloc((size_t)(H + 1) * (size_t)detect_integral_pitch(W));
+    c->d_seg.alloc(detect_colsum_count(W, H));
+    const double ms = timed_ms(c, ev, [&] { detect_integral(c->img, W, H, c->img_pitch, c->d_S.p, c->d_seg.p, c->stream); });
+    c->d_S_valid = true;
+    return ms;
+}
+
+// The orientation kernel on n keypoints in device memory (16-byte aligned): angles [n] to the host, at a stride of
+// angle_stride floats, vectors and status too when asked for.  Sets c->o_ms; the stream has drained on return.
+void orient_rows(dlco_desc_ctx *c, const EventPair &ev, const float *kp_dev, int64_t n, float *angles, int64_t angle_stride, int64_t *vectors,
+                 uint8_t *status)
+{
+    c->o_vec.alloc((size_t)n * 2);
+    c->o_status.alloc((size_t)n);
+    std::vector<int64_t> vec_own;
+    if (!vectors) { vec_own.resize((size_t)n * 2); vectors = vec_own.data(); }
+    c->o_ms = timed_ms(c, ev, [&] { orient_keypoints(c->d_S.p, c->img_w, c->img_h, kp_dev, n, c->o_vec.p, c->o_status.p, c->stream); }, [&] {
+        DLCO_HIP(hipMemcpyAsync(vectors, c->o_vec.p, (size_t)n * 2 * sizeof(int64_t), hipMemcpyDeviceToHost, c->stream));
+        if (status) DLCO_HIP(hipMemcpyAsync(status, c->o_status.p, (size_t)n, hipMemcpyDeviceToHost, c->stream));
+    });
+    for (int64_t k = 0; k < n; k++) angles[k * angle_stride] = orient_rules::angle_of(vectors[2 * k], vectors[2 * k + 1]);
+}
+
 // The first min(n_found, max_keypoints) keypoints in the rule's order, to device memory (dst_dev) or to the host.  The
 // survivors of the octaves are counted even where their buffers are full: the octaves then run again with room for all.
 void detect(dlco_desc_ctx *c, int n_octaves, int64_t threshold, int64_t max_keypoints, float *kp_dst, int64_t *resp_dst, bool dst_dev,
-            int64_t *n_out, int64_t *n_found)
+            int64_t *n_out, int64_t *n_found, bool oriented = false)
 {
     DLCO_CHECK(c->img, DLCO_ERR_INVALID, "dlco_desc: set an image first");
     DLCO_HIP(hipSetDevice(c->device));
     const int W = c->img_w, H = c->img_h;
     EventPair ev;
     for (double &ms : c->d_stage_ms) ms = 0.0;
-    if (!c->d_S_valid) {
-        c->d_S.alloc((size_t)(H + 1) * (size_t)detect_integral_pitch(W));
-        c->d_seg.alloc(detect_colsum_count(W, H));
-        c->d_stage_ms[0] = timed_ms(c, ev, [&] { detect_integral(c->img, W, H, c->img_pitch, c->d_S.p, c->d_seg.p, c->stream); });
-        c->d_S_valid = true;
-    }
+    c->d_stage_ms[0] = integral_image(c, ev);
     c->d_count.alloc(1);
     size_t cap = std::max<size_t>(std::max<size_t>(c->d_cap, 1024), (size_t)W * (size_t)H / 128);
     unsigned found = 0;
@@ -683,9 +712,12 @@ void detect(dlco_desc_ctx *c, int n_octaves, int64_t threshold, int64_t max_keyp
             if (resp_dst) DLCO_HIP(hipMemcpyAsync(resp_dst, resp_out, (size_t)keep * sizeof(int64_t), hipMemcpyDeviceToHost, c->stream));
         });
     }
+    // oriented (host form only): the kernel takes the selected rows where the selection left them, in device scratch
+    c->o_ms = 0.0;
+    if (oriented && keep > 0) orient_rows(c, ev, c->d_kp_out.p, keep, kp_dst + 3, 4, nullptr, nullptr);
     *n_out = keep;
     if (n_found) *n_found = n;
-    c->last_ms = std::accumulate(std::begin(c->d_stage_ms), std::end(c->d_stage_ms), 0.0);
+    c->last_ms = std::accumulate(std::begin(c->d_stage_ms), std::end(c->d_stage_ms), 0.0) + (oriented ? c->o_ms : 0.0);
 }
 }  // namespace
 
@@ -705,6 +737,34 @@ int dlco_desc_detect_device(dlco_desc_ctx *c, int32_t n_octaves, int64_t thresho
     if ((uintptr_t)keypoints_dev % 16 != 0 || (uintptr_t)response_dev % 8 != 0) return DLCO_ERR_INVALID;
     return guarded(c, [&] { detect(c, n_octaves, threshold, max_keypoints, keypoints_dev, response_dev, true, n_out, n_found); });
 }
+
+// dlco_desc_detect with the fourth column filled by the rule of orient_rules.hpp: the orientation kernel runs on the selected
+// rows before they leave the device; its time is dlco_desc_last_orient_ms and part of dlco_desc_last_kernel_ms, not of the
+// six stages
+int dlco_desc_detect_oriented(dlco_desc_ctx *c, int32_t n_octaves, int64_t threshold, int64_t max_keypoints, float *keypoints_host,
+                              int64_t *response_host, int64_t *n_out, int64_t *n_found)
+{
+    if (!c || !detect_args_ok(n_octaves, threshold, max_keypoints, keypoints_host, n_out)) return DLCO_ERR_INVALID;
+    return guarded(c, [&] { detect(c, n_octaves, threshold, max_keypoints, keypoints_host, response_host, false, n_out, n_found, true); });
+}
+
+// angles [n] of keypoints [n][4] on the image set, by the rule of orient_rules.hpp; vectors [n][2] and status [n] may be NULL
+int dlco_desc_orient(dlco_desc_ctx *c, const float *keypoints_host, int64_t n, float *angles_host, int64_t *vectors_host, uint8_t *status_host)
+{
+    if (!c || !keypoints_host || !angles_host || n < 1) return DLCO_ERR_INVALID;
+    return guarded(c, [&] {
+        DLCO_CHECK(c->img, DLCO_ERR_INVALID, "dlco_desc: set an image first");
+        DLCO_HIP(hipSetDevice(c->device));
+        EventPair ev;
+        const double integral_ms = integral_image(c, ev);
+        c->o_kp.alloc((size_t)n * 4);
+        DLCO_HIP(hipMemcpyAsync(c->o_kp.p, keypoints_host, (size_t)n * 4 * sizeof(float), hipMemcpyHostToDevice, c->stream));
+        orient_rows(c, ev, c->o_kp.p, n, angles_host, 1, vectors_host, status_host);
+        c->last_ms = integral_ms + c->o_ms;
+    });
+}
+
+double dlco_desc_last_orient_ms(const dlco_desc_ctx *c) { return c ? c->o_ms : 0.0; }
 
 // milliseconds of the last detect call by stage: ms[0] the integral image (0 when it was cached), ms[1 .. 4] the octaves,
 // ms[5] the selection; their sum is dlco_desc_last_kernel_ms
@@ -1037,7 +1097,8 @@ int dlco_desc_cross_sqdists_u8(dlco_desc_ctx *c, const uint8_t *query_u8, int64_
 // milliseconds the kernels of the last dlco_desc_compute* / dlco_desc_describe* call took (HIP events): transform and
 // pooling, plus the projection for describe and the sampling for the keypoint calls (extract_patches: the sampling alone);
 // the pair calls add their distance kernel; after a match call, float or byte, its kernels (norms, top two, merge); the _u8
-// forms of describe add their quantising kernel; after a detect call the detector's kernels (the integral image when the call
+// forms of describe add their quantising kernel; after an orient call the orientation kernel and the integral image when the
+// call formed it; after a detect call the detector's kernels (the integral image when the call
 // formed it, the octaves, the selection)
 double dlco_desc_last_kernel_ms(const dlco_desc_ctx *c) { return c ? c->last_ms : 0.0; }
 

@@ -454,5 +454,7 @@ void detect_octave(const uint32_t *S, int W, int H, int o, int64_t threshold, un
 size_t detect_select_bytes(size_t n);
 void detect_select(const uint64_t *pos, const int64_t *resp, const float *kp, unsigned n, unsigned n_out, uint64_t *key_a, uint64_t *key_b,
                    uint32_t *idx_a, uint32_t *idx_b, void *tmp, size_t tmp_bytes, float *kp_out, int64_t *resp_out, hipStream_t s);
+// orientation (kernels_orient.hip; the rule is orient_rules.hpp): vectors [n][2] and status [n] of keypoints [n][4] from S
+void orient_keypoints(const uint32_t *S, int W, int H, const float *kp, int64_t n, int64_t *vec, uint8_t *status, hipStream_t s);
 
 }  // namespace dlco
