@@ -5,6 +5,8 @@
 // of projected descriptors in kernels_describe.hip, the sampling of patches around keypoints in kernels_patch.hip, the
 // quantisation of rows to bytes (quant_rules.hpp) and the match of byte tables in kernels_match_u8.hip, the detection of
 // keypoints (detect_rules.hpp) in kernels_detect.hip, their orientation (orient_rules.hpp) in kernels_orient.hip.
+// compute() serves every describe call: a PatchSource in, the rows a RowsOut names out.  The float and the byte matcher
+// share one host path (match_host, match_device) over a FloatLine / ByteLine.
 #include "../../include/dlco.h"
 
 #include "dlco_internal.hpp"
@@ -26,6 +28,16 @@ constexpr int kBins = 8;
 constexpr int kChunk = 2048;            // patches per launch pair: 256 MB of PatchTrans
 }
 
+// The buffers of one matcher (FloatLine, ByteLine below): the uploaded tables of the host forms, the result of a chunk and
+// the matrix, part [slices][nq] partial (d1, j1, d2, j2) of 16 bytes each, the norms of the queries and of train
+template <typename Elem, typename Dist, typename Norm>
+struct MatchBufs {
+    DevBuf<Elem> query, train;
+    DevBuf<Dist> sqdist, cross;
+    DevBuf<int32_t> idx, part;
+    DevBuf<Norm> qnorm, tnorm;
+};
+
 struct dlco_desc_ctx {
     int device = 0;
     hipStream_t stream = nullptr;
@@ -42,17 +54,14 @@ struct dlco_desc_ctx {
     DevBuf<float> W, y_chunk;
     // matching (dlco_desc_match*): buffers of their own, so that a match call leaves the scratch of the calls above alone
     int n_cu = 0;
-    DevBuf<float> m_query, m_train, m_sqdist, m_cross;     // uploaded tables (host forms), the result of a chunk, the matrix
-    DevBuf<int32_t> m_idx, m_part;                         // m_part: [slices][nq] partial (d1, j1, d2, j2), 16 bytes each
-    DevBuf<double> m_qnorm, m_tnorm;
+    MatchBufs<float, float, double> m_float;
     // the quantiser of the _u8 forms of describe (quant_rules.hpp): scale, offsets [q_r] on the device; q_r == 0: none
     int q_r = 0;
     float q_scale = 1.f;
     DevBuf<float> q_off;
     DevBuf<uint8_t> u8_chunk;                              // the bytes of one chunk on their way to the host
-    // matching byte tables (dlco_desc_match_u8*): again buffers of their own; u_part as m_part, under the integer key
-    DevBuf<uint8_t> u_query, u_train;
-    DevBuf<int32_t> u_idx, u_sqdist, u_cross, u_part, u_qnorm, u_tneg;
+    // matching byte tables (dlco_desc_match_u8*): again buffers of their own; part under the integer key, tnorm = -|a_t|^2
+    MatchBufs<uint8_t, int32_t, int32_t> m_u8;
     // keypoint calls (dlco_desc_set_image* and after): the image, copied (img_own) or the caller's, and a chunk's frames
     const uint8_t *img = nullptr;
     int img_w = 0, img_h = 0;
@@ -117,6 +126,21 @@ float timed_ms(dlco_desc_ctx *c, const EventPair &ev, Run &&run) { return timed_
 struct PatchSource {
     const uint8_t *host = nullptr;                          // [n,64,64]
     const patch_rules::Frame *frames = nullptr;             // [n], on the host
+    static PatchSource patches(const uint8_t *host) { PatchSource s; s.host = host; return s; }
+    static PatchSource keypoints(const patch_rules::Frame *frames) { PatchSource s; s.frames = frames; return s; }
+};
+
+// What a compute call produces: the kind of rows, where they go (the caller's memory on the host or on the device) and
+// their pitch in elements of the row type.
+enum class Where { Host, Device };
+struct RowsOut {
+    enum Kind { Pooled, Projected, Bytes } kind;            // F floats; r floats, W * Desc; r bytes, those under the quantiser
+    void *dst;
+    Where where;
+    long ld;
+    static RowsOut pooled(float *dst, Where where, long ld) { return {Pooled, dst, where, ld}; }
+    static RowsOut projected(float *dst, Where where, long ld) { return {Projected, dst, where, ld}; }
+    static RowsOut bytes(uint8_t *dst, Where where, long ld) { return {Bytes, dst, where, ld}; }
 };
 
 // The copy that brings chunk [p0, p0 + cnt) of `src` to the device: the patches themselves into c->patches, or the frames
@@ -136,36 +160,38 @@ void sample_chunk(dlco_desc_ctx *c, const patch_rules::Frame *frames_host, int c
                  patch_stage_bytes(frames_host, cnt, c->img_w, c->img_h), c->stream);
 }
 
-// descriptors of n patches of `src` into dst: device memory when dst_dev, else host; row pitch ld floats.
-// With `project` a row is the learnt descriptor W * Desc (r floats): the un-projected rows of a chunk stay in the
-// library's scratch buffer and the projection kernel follows the pooling product on the same stream.  The rows of
-// invalid frames are zeroed behind the last kernel.
-//   With dst_u8 (and project) the float rows of a chunk stay in the scratch as well, and one elementwise kernel behind
-// the zeroing turns them into bytes by the context's quantiser: r bytes per row of pitch ld bytes.  dst is not used then.
-void compute(dlco_desc_ctx *c, const PatchSource &src, int64_t n, float *dst, bool dst_dev, long ld, bool project = false,
-             uint8_t *dst_u8 = nullptr)
+// descriptors of n patches of `src`, as `o` says.  Projected rows are the learnt descriptor W * Desc: the un-projected rows
+// of a chunk stay in the library's scratch buffer and the projection kernel follows the pooling product on the same
+// stream.  The rows of invalid frames are zeroed behind the last kernel.
+//   For bytes the float rows of a chunk stay in the scratch as well, and one elementwise kernel behind the zeroing turns
+// them into bytes by the context's quantiser.
+void compute(dlco_desc_ctx *c, const PatchSource &src, int64_t n, const RowsOut &o)
 {
+    const bool project = o.kind != RowsOut::Pooled, to_bytes = o.kind == RowsOut::Bytes, to_dev = o.where == Where::Device;
+    const long ld = o.ld;
     DLCO_CHECK(c->nsel > 0, DLCO_ERR_INVALID, "dlco_desc: set the filters first");
     const int F = c->nsel * kBins;
     DLCO_CHECK(!project || (c->r > 0 && c->proj_F == F), DLCO_ERR_INVALID, "dlco_desc: set a projection that fits the filters first");
-    const int cols = project ? c->r : F;                   // floats per output row
-    DLCO_CHECK(!dst_u8 || (c->q_r > 0 && c->q_r == c->r), DLCO_ERR_INVALID, "dlco_desc: set a quantiser that fits the projection first");
+    const int cols = project ? c->r : F;                   // elements per output row
+    DLCO_CHECK(!to_bytes || (c->q_r > 0 && c->q_r == c->r), DLCO_ERR_INVALID, "dlco_desc: set a quantiser that fits the projection first");
     DLCO_CHECK(ld >= cols, DLCO_ERR_INVALID, project ? "dlco_desc: row pitch below the projected size" : "dlco_desc: row pitch below the descriptor size");
+    const bool direct = to_dev && !to_bytes;               // the kernels write the caller's float rows themselves
+    float *dst = to_bytes ? nullptr : static_cast<float *>(o.dst);
+    uint8_t *dst_u8 = to_bytes ? static_cast<uint8_t *>(o.dst) : nullptr;
     DLCO_HIP(hipSetDevice(c->device));
     c->patches.alloc((size_t)kChunk * kPix);
     c->pt.alloc((size_t)kChunk * kBins * kPix);
     if (src.frames) c->frames.alloc((size_t)kChunk);
-    if (!dst_dev || project) c->desc_chunk.alloc((size_t)kChunk * F);
-    if ((!dst_dev || dst_u8) && project) c->y_chunk.alloc((size_t)kChunk * cols);
-    if (dst_u8 && !dst_dev) c->u8_chunk.alloc((size_t)kChunk * cols);
+    if (!direct || project) c->desc_chunk.alloc((size_t)kChunk * F);
+    if (!direct && project) c->y_chunk.alloc((size_t)kChunk * cols);
+    if (to_bytes && !to_dev) c->u8_chunk.alloc((size_t)kChunk * cols);
     EventPair ev;
     double ms_total = 0.0;
     for (int64_t p0 = 0; p0 < n; p0 += kChunk) {
         const int cnt = (int)std::min<int64_t>(kChunk, n - p0);
         upload_chunk(c, src, p0, cnt);
-        const bool to_caller = dst_dev && !dst_u8;          // the kernels write the caller's float rows directly
-        float *out = to_caller ? dst + p0 * ld : (project ? c->y_chunk.p : c->desc_chunk.p);
-        const long old = to_caller ? ld : cols;
+        float *out = direct ? dst + p0 * ld : (project ? c->y_chunk.p : c->desc_chunk.p);     // the float rows of the chunk
+        const long old = direct ? ld : cols;
         ms_total += timed_ms(c, ev, [&] {
             if (src.frames) sample_chunk(c, src.frames + p0, cnt);
             desc_transform(c->patches.p, cnt, c->cf.p, c->ks, c->inv_step, c->norm, c->qk, c->qgamma, c->pt.p, c->stream);
@@ -178,15 +204,15 @@ void compute(dlco_desc_ctx *c, const PatchSource &src, int64_t n, float *dst, bo
         }, [&] {
             for (int i = 0; src.frames && i < cnt; i++)
                 if (!src.frames[p0 + i].valid) DLCO_HIP(hipMemsetAsync(out + (size_t)i * old, 0, (size_t)cols * sizeof(float), c->stream));
-            if (!dst_dev && !dst_u8)
+            if (!to_dev && !to_bytes)
                 DLCO_HIP(hipMemcpy2DAsync(dst + p0 * ld, (size_t)ld * sizeof(float), out, (size_t)cols * sizeof(float),
                                           (size_t)cols * sizeof(float), (size_t)cnt, hipMemcpyDeviceToHost, c->stream));
         });
-        if (dst_u8) {
-            uint8_t *bytes = dst_dev ? dst_u8 + p0 * ld : c->u8_chunk.p;
-            const long bld = dst_dev ? ld : cols;
+        if (to_bytes) {
+            uint8_t *bytes = to_dev ? dst_u8 + p0 * ld : c->u8_chunk.p;
+            const long bld = to_dev ? ld : cols;
             ms_total += timed_ms(c, ev, [&] { desc_quantize_rows(out, old, cnt, cols, c->q_scale, c->q_off.p, bytes, bld, c->stream); }, [&] {
-                if (!dst_dev)
+                if (!to_dev)
                     DLCO_HIP(hipMemcpy2DAsync(dst_u8 + p0 * ld, (size_t)ld, bytes, (size_t)cols, (size_t)cols, (size_t)cnt, hipMemcpyDeviceToHost,
                                               c->stream));
             });
@@ -195,15 +221,121 @@ void compute(dlco_desc_ctx *c, const PatchSource &src, int64_t n, float *dst, bo
     c->last_ms = ms_total;
 }
 
-// the same for patches [n,64,64] on the host
-void compute(dlco_desc_ctx *c, const uint8_t *patches_host, int64_t n, float *dst, bool dst_dev, long ld, bool project = false,
-             uint8_t *dst_u8 = nullptr)
+// ---- matching: the two nearest rows of train for every row of query (kernels_match.hip, kernels_match_u8.hip) --------------
+// One host path serves both matchers.  A line (FloatLine, ByteLine) says what differs: the types of an element, a distance
+// and a norm, the Shape of the slicing rule, the context's buffers, the kernel wrappers, and the name in the "do not fit"
+// message.
+struct FloatLine {
+    using Elem = float; using Dist = float; using Norm = double;
+    static constexpr match_slicing::Shape shape = match_slicing::kFloat;
+    static constexpr const char *name = "dlco_desc_match";
+    static MatchBufs<Elem, Dist, Norm> &bufs(dlco_desc_ctx *c) { return c->m_float; }
+    static void query_norms(const Elem *x, long ld, long n, int r, Norm *norm, hipStream_t s) { match_norms(x, ld, n, r, norm, s); }
+    static void train_norms(const Elem *x, long ld, long n, int r, Norm *norm, hipStream_t s) { match_norms(x, ld, n, r, norm, s); }
+    static constexpr auto top2 = match_top2;
+};
+struct ByteLine {
+    using Elem = uint8_t; using Dist = int32_t; using Norm = int32_t;
+    static constexpr match_slicing::Shape shape = match_slicing::kU8;
+    static constexpr const char *name = "dlco_desc_match_u8";
+    static MatchBufs<Elem, Dist, Norm> &bufs(dlco_desc_ctx *c) { return c->m_u8; }
+    static void query_norms(const Elem *x, long ld, long n, int r, Norm *norm, hipStream_t s) { match_u8_norms(x, ld, n, r, false, norm, s); }
+    // negated: the form the tile loop takes for train
+    static void train_norms(const Elem *x, long ld, long n, int r, Norm *norm, hipStream_t s) { match_u8_norms(x, ld, n, r, true, norm, s); }
+    static constexpr auto top2 = match_u8_top2;
+};
+
+constexpr int64_t kMatchRows = (int64_t)1 << 20;           // queries per launch (the kernels index a launch's queries with an int)
+constexpr int64_t kRowPitchBytes = 16;                     // the host forms pad uploaded rows to this: the kernels fetch 16-byte pieces
+constexpr int64_t kQueryChunkBytes = (int64_t)1 << 28;     // the host forms upload this much of padded query rows at a time
+
+bool match_args_ok(const void *a, const void *b, const void *o1, const void *o2, int64_t nq, int64_t nt, int32_t r)
 {
-    PatchSource src;
-    src.host = patches_host;
-    compute(c, src, n, dst, dst_dev, ld, project, dst_u8);
+    return a && b && o1 && o2 && r >= 1 && r <= 1024 && nq >= 1 && nt >= 1 && nt < ((int64_t)1 << 31);
 }
 
+// device tables in, device results out; adds the kernels' time to *ms.  The line's tnorm holds train's norms already.
+template <typename L>
+void match_on_device(dlco_desc_ctx *c, const typename L::Elem *q, long ldq, int64_t nq, const typename L::Elem *t, long ldt, int64_t nt, int r,
+                     int32_t *idx, typename L::Dist *sqdist, typename L::Dist *cross, double *ms)
+{
+    auto &b = L::bufs(c);
+    EventPair ev;
+    for (int64_t q0 = 0; q0 < nq; q0 += kMatchRows) {
+        const int cnt = (int)std::min(kMatchRows, nq - q0);
+        const int tps = match_slicing::tiles_per_slice(L::shape, cnt, nt, c->n_cu), slices = match_slicing::slices(L::shape, nt, tps);
+        b.qnorm.alloc((size_t)cnt);
+        if (!cross && slices > 1) b.part.alloc((size_t)slices * cnt * 4);
+        *ms += timed_ms(c, ev, [&] {
+            L::query_norms(q + q0 * ldq, ldq, cnt, r, b.qnorm.p, c->stream);
+            L::top2(q + q0 * ldq, ldq, cnt, t, ldt, (int)nt, r, b.qnorm.p, b.tnorm.p, tps, idx ? idx + 2 * q0 : nullptr,
+                    sqdist ? sqdist + 2 * q0 : nullptr, b.part.p, cross ? cross + q0 * nt : nullptr, c->stream);
+        });
+    }
+}
+
+template <typename L>
+double train_norms(dlco_desc_ctx *c, const typename L::Elem *t, long ldt, int64_t nt, int r)
+{
+    auto &b = L::bufs(c);
+    EventPair ev;
+    b.tnorm.alloc((size_t)nt);
+    return timed_ms(c, ev, [&] { L::train_norms(t, ldt, nt, r, b.tnorm.p, c->stream); });
+}
+
+// the device forms: both tables where the caller has them
+template <typename L>
+void match_device(dlco_desc_ctx *c, const typename L::Elem *query_dev, long ldq, int64_t nq, const typename L::Elem *train_dev, long ldt,
+                  int64_t nt, int r, int32_t *idx_dev, typename L::Dist *sqdist_dev)
+{
+    DLCO_HIP(hipSetDevice(c->device));
+    double ms = train_norms<L>(c, train_dev, ldt, nt, r);
+    match_on_device<L>(c, query_dev, ldq, nq, train_dev, ldt, nt, r, idx_dev, sqdist_dev, nullptr, &ms);
+    c->last_ms = ms;
+}
+
+// the host forms: train wholly in HBM, the queries a chunk at a time; cross_host: the matrix instead of the top two
+template <typename L>
+void match_host(dlco_desc_ctx *c, const typename L::Elem *query_host, int64_t nq, const typename L::Elem *train_host, int64_t nt, int r,
+                int32_t *idx_host, typename L::Dist *sqdist_host, typename L::Dist *cross_host)
+{
+    using Elem = typename L::Elem;
+    using Dist = typename L::Dist;
+    auto &b = L::bufs(c);
+    DLCO_HIP(hipSetDevice(c->device));
+    constexpr long per = kRowPitchBytes / sizeof(Elem);
+    const long ld = (r + per - 1) / per * per;
+    const int64_t qchunk = std::max<int64_t>(1, std::min<int64_t>(nq, kQueryChunkBytes / (ld * (int64_t)sizeof(Elem))));
+    try {
+        b.train.alloc((size_t)nt * ld);
+        b.query.alloc((size_t)qchunk * ld);
+        if (cross_host) b.cross.alloc((size_t)qchunk * nt);
+        else { b.idx.alloc((size_t)qchunk * 2); b.sqdist.alloc((size_t)qchunk * 2); }
+    } catch (const Error &e) {
+        throw Error(DLCO_ERR_HIP, std::string(L::name) + ": the tables do not fit in device memory: " + e.what());
+    }
+    // rows of r elements on the host -> rows of pitch ld in dst
+    auto upload_rows = [&](Elem *dst, const Elem *src_host, int64_t n) {
+        DLCO_HIP(hipMemcpy2DAsync(dst, (size_t)ld * sizeof(Elem), src_host, (size_t)r * sizeof(Elem), (size_t)r * sizeof(Elem), (size_t)n,
+                                  hipMemcpyHostToDevice, c->stream));
+    };
+    upload_rows(b.train.p, train_host, nt);
+    double ms = train_norms<L>(c, b.train.p, ld, nt, r);
+    for (int64_t q0 = 0; q0 < nq; q0 += qchunk) {
+        const int64_t cnt = std::min(qchunk, nq - q0);
+        upload_rows(b.query.p, query_host + q0 * r, cnt);
+        if (cross_host) {
+            match_on_device<L>(c, b.query.p, ld, cnt, b.train.p, ld, nt, r, nullptr, nullptr, b.cross.p, &ms);
+            DLCO_HIP(hipMemcpyAsync(cross_host + q0 * nt, b.cross.p, (size_t)cnt * nt * sizeof(Dist), hipMemcpyDeviceToHost, c->stream));
+        } else {
+            match_on_device<L>(c, b.query.p, ld, cnt, b.train.p, ld, nt, r, b.idx.p, b.sqdist.p, nullptr, &ms);
+            DLCO_HIP(hipMemcpyAsync(idx_host + 2 * q0, b.idx.p, (size_t)cnt * 2 * sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
+            DLCO_HIP(hipMemcpyAsync(sqdist_host + 2 * q0, b.sqdist.p, (size_t)cnt * 2 * sizeof(Dist), hipMemcpyDeviceToHost, c->stream));
+        }
+        sync(c);
+    }
+    c->last_ms = ms;
+}
 }  // namespace
 
 extern "C" {
@@ -353,13 +485,13 @@ int dlco_desc_transform(dlco_desc_ctx *c, const uint8_t *patch_host, float *patc
 int dlco_desc_compute(dlco_desc_ctx *c, const uint8_t *patches_host, int64_t n, float *desc_host)
 {
     if (!c || !patches_host || !desc_host || n < 1) return DLCO_ERR_INVALID;
-    return guarded(c, [&] { compute(c, patches_host, n, desc_host, false, (long)c->nsel * kBins); });
+    return guarded(c, [&] { compute(c, PatchSource::patches(patches_host), n, RowsOut::pooled(desc_host, Where::Host, (long)c->nsel * kBins)); });
 }
 
 int dlco_desc_compute_device(dlco_desc_ctx *c, const uint8_t *patches_host, int64_t n, float *desc_dev, int64_t ld)
 {
     if (!c || !patches_host || !desc_dev || n < 1) return DLCO_ERR_INVALID;
-    return guarded(c, [&] { compute(c, patches_host, n, desc_dev, true, (long)ld); });
+    return guarded(c, [&] { compute(c, PatchSource::patches(patches_host), n, RowsOut::pooled(desc_dev, Where::Device, (long)ld)); });
 }
 
 // The output of comp-uprjdists: Distance [n_pairs, nsel*8] and Label [n_pairs] for pairs [n_pairs,4] =
@@ -405,7 +537,7 @@ int dlco_desc_pair_dists_stream(dlco_desc_ctx *c, const uint8_t *patches_host, i
         DLCO_HIP(hipSetDevice(c->device));
         DevBuf<float> table, dist;
         table.alloc((size_t)n_patches * F);
-        compute(c, patches_host, n_patches, table.p, true, F);
+        compute(c, PatchSource::patches(patches_host), n_patches, RowsOut::pooled(table.p, Where::Device, F));
         const int64_t pchunk = std::max<int64_t>(1, std::min<int64_t>(std::min(n_pairs, chunk_rows), ((int64_t)1 << 28) / F));
         DevBuf<int32_t> pairs;
         DevBuf<uint8_t> lab;
@@ -464,7 +596,7 @@ int dlco_desc_full_dists_stream(dlco_desc_ctx *c, const uint8_t *patches_host, i
                 std::memcpy(stage.data() + (size_t)(cnt + i) * kPix, patches_host + (size_t)q[2] * kPix, kPix);
                 st.label[i] = (q[1] == q[3]) ? 1 : 0;                              // :268-272 of both tools
             }
-            compute(c, stage.data(), 2 * cnt, desc.p, true, F);
+            compute(c, PatchSource::patches(stage.data()), 2 * cnt, RowsOut::pooled(desc.p, Where::Device, F));
             ms_total += c->last_ms;
             desc_full_dist(desc.p, F, groups, (int)cnt, dist.p, c->stream);
             DLCO_HIP(hipMemcpyAsync(st.dist, dist.p, (size_t)cnt * groups * sizeof(float), hipMemcpyDeviceToHost, c->stream));
@@ -518,13 +650,13 @@ int32_t dlco_desc_projected_size(const dlco_desc_ctx *c) { return c ? c->r : 0; 
 int dlco_desc_describe(dlco_desc_ctx *c, const uint8_t *patches_host, int64_t n, float *out_host)
 {
     if (!c || !patches_host || !out_host || n < 1) return DLCO_ERR_INVALID;
-    return guarded(c, [&] { compute(c, patches_host, n, out_host, false, (long)c->r, true); });
+    return guarded(c, [&] { compute(c, PatchSource::patches(patches_host), n, RowsOut::projected(out_host, Where::Host, (long)c->r)); });
 }
 
 int dlco_desc_describe_device(dlco_desc_ctx *c, const uint8_t *patches_host, int64_t n, float *out_dev, int64_t ld)
 {
     if (!c || !patches_host || !out_dev || n < 1) return DLCO_ERR_INVALID;
-    return guarded(c, [&] { compute(c, patches_host, n, out_dev, true, (long)ld, true); });
+    return guarded(c, [&] { compute(c, PatchSource::patches(patches_host), n, RowsOut::projected(out_dev, Where::Device, (long)ld)); });
 }
 
 // ---- keypoints of an image: the patches are sampled on the device (kernels_patch.hip) by the rule of patch_rules.hpp ------
@@ -552,14 +684,12 @@ void keypoint_frames(const dlco_desc_ctx *c, const float *keypoints, int64_t n, 
     }
 }
 
-void describe_keypoints(dlco_desc_ctx *c, const float *keypoints, int64_t n, float scale_factor, bool use_orientation, float *dst, bool dst_dev,
-                        long ld, uint8_t *status, uint8_t *dst_u8 = nullptr)
+void describe_keypoints(dlco_desc_ctx *c, const float *keypoints, int64_t n, float scale_factor, bool use_orientation, uint8_t *status,
+                        const RowsOut &o)
 {
     std::vector<patch_rules::Frame> frames;
     keypoint_frames(c, keypoints, n, scale_factor, use_orientation, status, frames);
-    PatchSource src;
-    src.frames = frames.data();
-    compute(c, src, n, dst, dst_dev, ld, true, dst_u8);
+    compute(c, PatchSource::keypoints(frames.data()), n, o);
 }
 }  // namespace
 
@@ -599,8 +729,7 @@ int dlco_desc_extract_patches(dlco_desc_ctx *c, const float *keypoints_host, int
     return guarded(c, [&] {
         std::vector<patch_rules::Frame> frames;
         keypoint_frames(c, keypoints_host, n, scale_factor, use_orientation != 0, status_host, frames);
-        PatchSource src;
-        src.frames = frames.data();
+        const PatchSource src = PatchSource::keypoints(frames.data());
         DLCO_HIP(hipSetDevice(c->device));
         c->patches.alloc((size_t)kChunk * kPix);
         c->frames.alloc((size_t)kChunk);
@@ -623,14 +752,18 @@ int dlco_desc_describe_keypoints(dlco_desc_ctx *c, const float *keypoints_host, 
                                  float *out_host, uint8_t *status_host)
 {
     if (!c || !out_host || !keypoint_args_ok(keypoints_host, n, scale_factor)) return DLCO_ERR_INVALID;
-    return guarded(c, [&] { describe_keypoints(c, keypoints_host, n, scale_factor, use_orientation != 0, out_host, false, (long)c->r, status_host); });
+    return guarded(c, [&] {
+        describe_keypoints(c, keypoints_host, n, scale_factor, use_orientation != 0, status_host, RowsOut::projected(out_host, Where::Host, (long)c->r));
+    });
 }
 
 int dlco_desc_describe_keypoints_device(dlco_desc_ctx *c, const float *keypoints_host, int64_t n, float scale_factor, int32_t use_orientation,
                                         float *out_dev, int64_t ld, uint8_t *status_host)
 {
     if (!c || !out_dev || !keypoint_args_ok(keypoints_host, n, scale_factor)) return DLCO_ERR_INVALID;
-    return guarded(c, [&] { describe_keypoints(c, keypoints_host, n, scale_factor, use_orientation != 0, out_dev, true, (long)ld, status_host); });
+    return guarded(c, [&] {
+        describe_keypoints(c, keypoints_host, n, scale_factor, use_orientation != 0, status_host, RowsOut::projected(out_dev, Where::Device, (long)ld));
+    });
 }
 
 // ---- keypoints of the image set: the detector of detect_rules.hpp (kernels_detect.hip) ------------------------------------
@@ -795,7 +928,7 @@ void projected_pair_dists(dlco_desc_ctx *c, const uint8_t *patches_host, int64_t
     w.dist.alloc((size_t)n_pairs);
     w.label.alloc((size_t)n_pairs);
     w.pairs.alloc((size_t)n_pairs * 4);
-    compute(c, patches_host, n_patches, w.Y.p, true, (long)c->r, true);
+    compute(c, PatchSource::patches(patches_host), n_patches, RowsOut::projected(w.Y.p, Where::Device, (long)c->r));
     EventPair ev;
     DLCO_HIP(hipMemcpyAsync(w.pairs.p, pairs_host, (size_t)n_pairs * 4 * sizeof(int32_t), hipMemcpyHostToDevice, c->stream));
     c->last_ms += timed_ms(c, ev, [&] { desc_pair_sqdist(w.Y.p, c->r, c->r, w.pairs.p, n_pairs, w.dist.p, w.label.p, c->stream); });
@@ -833,87 +966,12 @@ int dlco_desc_pair_stats(dlco_desc_ctx *c, const uint8_t *patches_host, int64_t 
     });
 }
 
-// ---- matching: the two nearest rows of train for every row of query (kernels_match.hip) ----------------------------------
-namespace {
-constexpr int64_t kMatchRows = (int64_t)1 << 20;           // queries per launch (the kernels index a launch's queries with an int)
-
-bool match_args_ok(const void *a, const void *b, const void *o1, const void *o2, int64_t nq, int64_t nt, int32_t r)
-{
-    return a && b && o1 && o2 && r >= 1 && r <= 1024 && nq >= 1 && nt >= 1 && nt < ((int64_t)1 << 31);
-}
-
-// device tables in, device results out; adds the kernels' time to *ms.  tnorm holds |t_j|^2 already.
-void match_on_device(dlco_desc_ctx *c, const float *q, long ldq, int64_t nq, const float *t, long ldt, int64_t nt, int r, int32_t *idx,
-                     float *sqdist, float *cross, double *ms)
-{
-    EventPair ev;
-    for (int64_t q0 = 0; q0 < nq; q0 += kMatchRows) {
-        const int cnt = (int)std::min(kMatchRows, nq - q0);
-        const int tps = match_tiles_per_slice(cnt, nt, c->n_cu), slices = match_slices(nt, tps);
-        c->m_qnorm.alloc((size_t)cnt);
-        if (!cross && slices > 1) c->m_part.alloc((size_t)slices * cnt * 4);
-        *ms += timed_ms(c, ev, [&] {
-            match_norms(q + q0 * ldq, ldq, cnt, r, c->m_qnorm.p, c->stream);
-            match_top2(q + q0 * ldq, ldq, cnt, t, ldt, (int)nt, r, c->m_qnorm.p, c->m_tnorm.p, tps, idx ? idx + 2 * q0 : nullptr,
-                       sqdist ? sqdist + 2 * q0 : nullptr, c->m_part.p, cross ? cross + q0 * nt : nullptr, c->stream);
-        });
-    }
-}
-
-double train_norms(dlco_desc_ctx *c, const float *t, long ldt, int64_t nt, int r)
-{
-    EventPair ev;
-    c->m_tnorm.alloc((size_t)nt);
-    return timed_ms(c, ev, [&] { match_norms(t, ldt, nt, r, c->m_tnorm.p, c->stream); });
-}
-
-// rows of r floats on the host -> rows of pitch ld (a multiple of 4) in dst
-void upload_rows(dlco_desc_ctx *c, float *dst, long ld, const float *src_host, int64_t n, int r)
-{
-    DLCO_HIP(hipMemcpy2DAsync(dst, (size_t)ld * sizeof(float), src_host, (size_t)r * sizeof(float), (size_t)r * sizeof(float), (size_t)n,
-                              hipMemcpyHostToDevice, c->stream));
-}
-
-// the host forms: train wholly in HBM, the queries a chunk at a time
-void match_host(dlco_desc_ctx *c, const float *query_host, int64_t nq, const float *train_host, int64_t nt, int r, int32_t *idx_host,
-                float *sqdist_host, float *cross_host)
-{
-    DLCO_HIP(hipSetDevice(c->device));
-    const long ld = (r + 3) / 4 * 4;
-    // queries per chunk: 256 MB of rows, and for the matrix 2^28 entries at most
-    const int64_t qchunk = std::max<int64_t>(1, std::min<int64_t>(nq, ((int64_t)1 << 26) / ld));
-    try {
-        c->m_train.alloc((size_t)nt * ld);
-        c->m_query.alloc((size_t)qchunk * ld);
-        if (cross_host) c->m_cross.alloc((size_t)qchunk * nt);
-        else { c->m_idx.alloc((size_t)qchunk * 2); c->m_sqdist.alloc((size_t)qchunk * 2); }
-    } catch (const Error &e) {
-        throw Error(DLCO_ERR_HIP, std::string("dlco_desc_match: the tables do not fit in device memory: ") + e.what());
-    }
-    upload_rows(c, c->m_train.p, ld, train_host, nt, r);
-    double ms = train_norms(c, c->m_train.p, ld, nt, r);
-    for (int64_t q0 = 0; q0 < nq; q0 += qchunk) {
-        const int64_t cnt = std::min(qchunk, nq - q0);
-        upload_rows(c, c->m_query.p, ld, query_host + q0 * r, cnt, r);
-        if (cross_host) {
-            match_on_device(c, c->m_query.p, ld, cnt, c->m_train.p, ld, nt, r, nullptr, nullptr, c->m_cross.p, &ms);
-            DLCO_HIP(hipMemcpyAsync(cross_host + q0 * nt, c->m_cross.p, (size_t)cnt * nt * sizeof(float), hipMemcpyDeviceToHost, c->stream));
-        } else {
-            match_on_device(c, c->m_query.p, ld, cnt, c->m_train.p, ld, nt, r, c->m_idx.p, c->m_sqdist.p, nullptr, &ms);
-            DLCO_HIP(hipMemcpyAsync(idx_host + 2 * q0, c->m_idx.p, (size_t)cnt * 2 * sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
-            DLCO_HIP(hipMemcpyAsync(sqdist_host + 2 * q0, c->m_sqdist.p, (size_t)cnt * 2 * sizeof(float), hipMemcpyDeviceToHost, c->stream));
-        }
-        sync(c);
-    }
-    c->last_ms = ms;
-}
-}  // namespace
-
+// ---- matching: the float entry points; the host path they share with the byte ones is with compute(), outside extern "C" ----
 int dlco_desc_match(dlco_desc_ctx *c, const float *query_host, int64_t nq, const float *train_host, int64_t nt, int32_t r, int32_t *idx_host,
                     float *sqdist_host)
 {
     if (!c || !match_args_ok(query_host, train_host, idx_host, sqdist_host, nq, nt, r)) return DLCO_ERR_INVALID;
-    return guarded(c, [&] { match_host(c, query_host, nq, train_host, nt, r, idx_host, sqdist_host, nullptr); });
+    return guarded(c, [&] { match_host<FloatLine>(c, query_host, nq, train_host, nt, r, idx_host, sqdist_host, nullptr); });
 }
 
 int dlco_desc_match_device(dlco_desc_ctx *c, const float *query_dev, int64_t ldq, int64_t nq, const float *train_dev, int64_t ldt, int64_t nt,
@@ -922,12 +980,7 @@ int dlco_desc_match_device(dlco_desc_ctx *c, const float *query_dev, int64_t ldq
     if (!c || !match_args_ok(query_dev, train_dev, idx_dev, sqdist_dev, nq, nt, r)) return DLCO_ERR_INVALID;
     if (ldq < r || ldt < r || ldq % 4 != 0 || ldt % 4 != 0) return DLCO_ERR_INVALID;
     if (((uintptr_t)query_dev | (uintptr_t)train_dev) % 16 != 0) return DLCO_ERR_INVALID;          // 16-byte rows
-    return guarded(c, [&] {
-        DLCO_HIP(hipSetDevice(c->device));
-        double ms = train_norms(c, train_dev, (long)ldt, nt, r);
-        match_on_device(c, query_dev, (long)ldq, nq, train_dev, (long)ldt, nt, r, idx_dev, sqdist_dev, nullptr, &ms);
-        c->last_ms = ms;
-    });
+    return guarded(c, [&] { match_device<FloatLine>(c, query_dev, (long)ldq, nq, train_dev, (long)ldt, nt, r, idx_dev, sqdist_dev); });
 }
 
 int dlco_desc_cross_sqdists(dlco_desc_ctx *c, const float *query_host, int64_t nq, const float *train_host, int64_t nt, int32_t r,
@@ -935,7 +988,7 @@ int dlco_desc_cross_sqdists(dlco_desc_ctx *c, const float *query_host, int64_t n
 {
     if (!c || !match_args_ok(query_host, train_host, out_host, out_host, nq, nt, r)) return DLCO_ERR_INVALID;
     if (nq > ((int64_t)1 << 28) / nt) return DLCO_ERR_INVALID;
-    return guarded(c, [&] { match_host(c, query_host, nq, train_host, nt, r, nullptr, nullptr, out_host); });
+    return guarded(c, [&] { match_host<FloatLine>(c, query_host, nq, train_host, nt, r, nullptr, nullptr, out_host); });
 }
 
 // ---- byte descriptors: the quantiser (quant_rules.hpp), the _u8 forms of describe, the match of byte tables -------------------
@@ -976,13 +1029,13 @@ int dlco_desc_set_quantizer(dlco_desc_ctx *c, float scale, const float *offset, 
 int dlco_desc_describe_u8(dlco_desc_ctx *c, const uint8_t *patches_host, int64_t n, uint8_t *out_host)
 {
     if (!c || !patches_host || !out_host || n < 1) return DLCO_ERR_INVALID;
-    return guarded(c, [&] { compute(c, patches_host, n, nullptr, false, (long)c->r, true, out_host); });
+    return guarded(c, [&] { compute(c, PatchSource::patches(patches_host), n, RowsOut::bytes(out_host, Where::Host, (long)c->r)); });
 }
 
 int dlco_desc_describe_u8_device(dlco_desc_ctx *c, const uint8_t *patches_host, int64_t n, uint8_t *out_dev, int64_t ld)
 {
     if (!c || !patches_host || !out_dev || n < 1) return DLCO_ERR_INVALID;
-    return guarded(c, [&] { compute(c, patches_host, n, nullptr, true, (long)ld, true, out_dev); });
+    return guarded(c, [&] { compute(c, PatchSource::patches(patches_host), n, RowsOut::bytes(out_dev, Where::Device, (long)ld)); });
 }
 
 // the same of dlco_desc_describe_keypoints' rows: a row of status 0 is the quantisation of the zero vector
@@ -991,7 +1044,7 @@ int dlco_desc_describe_keypoints_u8(dlco_desc_ctx *c, const float *keypoints_hos
 {
     if (!c || !out_host || !keypoint_args_ok(keypoints_host, n, scale_factor)) return DLCO_ERR_INVALID;
     return guarded(c, [&] {
-        describe_keypoints(c, keypoints_host, n, scale_factor, use_orientation != 0, nullptr, false, (long)c->r, status_host, out_host);
+        describe_keypoints(c, keypoints_host, n, scale_factor, use_orientation != 0, status_host, RowsOut::bytes(out_host, Where::Host, (long)c->r));
     });
 }
 
@@ -1000,76 +1053,15 @@ int dlco_desc_describe_keypoints_u8_device(dlco_desc_ctx *c, const float *keypoi
 {
     if (!c || !out_dev || !keypoint_args_ok(keypoints_host, n, scale_factor)) return DLCO_ERR_INVALID;
     return guarded(c, [&] {
-        describe_keypoints(c, keypoints_host, n, scale_factor, use_orientation != 0, nullptr, true, (long)ld, status_host, out_dev);
+        describe_keypoints(c, keypoints_host, n, scale_factor, use_orientation != 0, status_host, RowsOut::bytes(out_dev, Where::Device, (long)ld));
     });
 }
-
-namespace {
-// device tables in, device results out; adds the kernels' time to *ms.  u_tneg holds -|a_t|^2 already.
-void match_u8_on_device(dlco_desc_ctx *c, const uint8_t *q, long ldq, int64_t nq, const uint8_t *t, long ldt, int64_t nt, int r, int32_t *idx,
-                        int32_t *sqdist, int32_t *cross, double *ms)
-{
-    EventPair ev;
-    for (int64_t q0 = 0; q0 < nq; q0 += kMatchRows) {
-        const int cnt = (int)std::min(kMatchRows, nq - q0);
-        const int tps = match_u8_tiles_per_slice(cnt, nt, c->n_cu), slices = match_u8_slices(nt, tps);
-        c->u_qnorm.alloc((size_t)cnt);
-        if (!cross && slices > 1) c->u_part.alloc((size_t)slices * cnt * 4);
-        *ms += timed_ms(c, ev, [&] {
-            match_u8_norms(q + q0 * ldq, ldq, cnt, r, false, c->u_qnorm.p, c->stream);
-            match_u8_top2(q + q0 * ldq, ldq, cnt, t, ldt, (int)nt, r, c->u_qnorm.p, c->u_tneg.p, tps, idx ? idx + 2 * q0 : nullptr,
-                          sqdist ? sqdist + 2 * q0 : nullptr, c->u_part.p, cross ? cross + q0 * nt : nullptr, c->stream);
-        });
-    }
-}
-
-double train_norms_u8(dlco_desc_ctx *c, const uint8_t *t, long ldt, int64_t nt, int r)
-{
-    EventPair ev;
-    c->u_tneg.alloc((size_t)nt);
-    return timed_ms(c, ev, [&] { match_u8_norms(t, ldt, nt, r, true, c->u_tneg.p, c->stream); });
-}
-
-// the host forms: train wholly in HBM, the queries a chunk at a time; rows of r bytes go up to rows of pitch ceil(r/16)*16
-void match_u8_host(dlco_desc_ctx *c, const uint8_t *query_host, int64_t nq, const uint8_t *train_host, int64_t nt, int r, int32_t *idx_host,
-                   int32_t *sqdist_host, int32_t *cross_host)
-{
-    DLCO_HIP(hipSetDevice(c->device));
-    const long ld = (r + 15) / 16 * 16;
-    // queries per chunk: 256 MB of rows, and for the matrix 2^28 entries at most
-    const int64_t qchunk = std::max<int64_t>(1, std::min<int64_t>(nq, ((int64_t)1 << 28) / ld));
-    try {
-        c->u_train.alloc((size_t)nt * ld);
-        c->u_query.alloc((size_t)qchunk * ld);
-        if (cross_host) c->u_cross.alloc((size_t)qchunk * nt);
-        else { c->u_idx.alloc((size_t)qchunk * 2); c->u_sqdist.alloc((size_t)qchunk * 2); }
-    } catch (const Error &e) {
-        throw Error(DLCO_ERR_HIP, std::string("dlco_desc_match_u8: the tables do not fit in device memory: ") + e.what());
-    }
-    DLCO_HIP(hipMemcpy2DAsync(c->u_train.p, (size_t)ld, train_host, (size_t)r, (size_t)r, (size_t)nt, hipMemcpyHostToDevice, c->stream));
-    double ms = train_norms_u8(c, c->u_train.p, ld, nt, r);
-    for (int64_t q0 = 0; q0 < nq; q0 += qchunk) {
-        const int64_t cnt = std::min(qchunk, nq - q0);
-        DLCO_HIP(hipMemcpy2DAsync(c->u_query.p, (size_t)ld, query_host + q0 * r, (size_t)r, (size_t)r, (size_t)cnt, hipMemcpyHostToDevice, c->stream));
-        if (cross_host) {
-            match_u8_on_device(c, c->u_query.p, ld, cnt, c->u_train.p, ld, nt, r, nullptr, nullptr, c->u_cross.p, &ms);
-            DLCO_HIP(hipMemcpyAsync(cross_host + q0 * nt, c->u_cross.p, (size_t)cnt * nt * sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
-        } else {
-            match_u8_on_device(c, c->u_query.p, ld, cnt, c->u_train.p, ld, nt, r, c->u_idx.p, c->u_sqdist.p, nullptr, &ms);
-            DLCO_HIP(hipMemcpyAsync(idx_host + 2 * q0, c->u_idx.p, (size_t)cnt * 2 * sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
-            DLCO_HIP(hipMemcpyAsync(sqdist_host + 2 * q0, c->u_sqdist.p, (size_t)cnt * 2 * sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
-        }
-        sync(c);
-    }
-    c->last_ms = ms;
-}
-}  // namespace
 
 int dlco_desc_match_u8(dlco_desc_ctx *c, const uint8_t *query_u8, int64_t nq, const uint8_t *train_u8, int64_t nt, int32_t r, int32_t *idx_host,
                        int32_t *sqdist_host)
 {
     if (!c || !match_args_ok(query_u8, train_u8, idx_host, sqdist_host, nq, nt, r)) return DLCO_ERR_INVALID;
-    return guarded(c, [&] { match_u8_host(c, query_u8, nq, train_u8, nt, r, idx_host, sqdist_host, nullptr); });
+    return guarded(c, [&] { match_host<ByteLine>(c, query_u8, nq, train_u8, nt, r, idx_host, sqdist_host, nullptr); });
 }
 
 int dlco_desc_match_u8_device(dlco_desc_ctx *c, const uint8_t *query_dev, int64_t ldq, int64_t nq, const uint8_t *train_dev, int64_t ldt,
@@ -1078,12 +1070,7 @@ int dlco_desc_match_u8_device(dlco_desc_ctx *c, const uint8_t *query_dev, int64_
     if (!c || !match_args_ok(query_dev, train_dev, idx_dev, sqdist_dev, nq, nt, r)) return DLCO_ERR_INVALID;
     if (ldq < r || ldt < r || ldq % 16 != 0 || ldt % 16 != 0) return DLCO_ERR_INVALID;
     if (((uintptr_t)query_dev | (uintptr_t)train_dev) % 16 != 0) return DLCO_ERR_INVALID;          // 16-byte pieces
-    return guarded(c, [&] {
-        DLCO_HIP(hipSetDevice(c->device));
-        double ms = train_norms_u8(c, train_dev, (long)ldt, nt, r);
-        match_u8_on_device(c, query_dev, (long)ldq, nq, train_dev, (long)ldt, nt, r, idx_dev, sqdist_dev, nullptr, &ms);
-        c->last_ms = ms;
-    });
+    return guarded(c, [&] { match_device<ByteLine>(c, query_dev, (long)ldq, nq, train_dev, (long)ldt, nt, r, idx_dev, sqdist_dev); });
 }
 
 int dlco_desc_cross_sqdists_u8(dlco_desc_ctx *c, const uint8_t *query_u8, int64_t nq, const uint8_t *train_u8, int64_t nt, int32_t r,
@@ -1091,7 +1078,7 @@ int dlco_desc_cross_sqdists_u8(dlco_desc_ctx *c, const uint8_t *query_u8, int64_
 {
     if (!c || !match_args_ok(query_u8, train_u8, out_host, out_host, nq, nt, r)) return DLCO_ERR_INVALID;
     if (nq > ((int64_t)1 << 28) / nt) return DLCO_ERR_INVALID;
-    return guarded(c, [&] { match_u8_host(c, query_u8, nq, train_u8, nt, r, nullptr, nullptr, out_host); });
+    return guarded(c, [&] { match_host<ByteLine>(c, query_u8, nq, train_u8, nt, r, nullptr, nullptr, out_host); });
 }
 
 // milliseconds the kernels of the last dlco_desc_compute* / dlco_desc_describe* call took (HIP events): transform and

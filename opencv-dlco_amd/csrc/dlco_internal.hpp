@@ -429,15 +429,11 @@ void desc_full_dist(const float *desc, long ld, int n_groups, int n_pairs, float
 void desc_project(const float *desc, long desc_ld, int n, const float *W, int r, int F, float *Y, long y_ld, hipStream_t s);
 void desc_pair_sqdist(const float *Y, long ld, int r, const int32_t *pairs, long n_pairs, float *dist, uint8_t *label, hipStream_t s);
 void match_norms(const float *x, long ld, long n, int r, double *norm, hipStream_t s);
-using match_slicing::match_tiles_per_slice;                 // the slicing rule: match_slices.hpp
-using match_slicing::match_slices;
 void match_top2(const float *query, long ldq, int nq, const float *train, long ldt, int nt, int r, const double *qnorm, const double *tnorm,
                 int tiles_per_slice, int32_t *idx, float *sqdist, void *part, float *out, hipStream_t s);
 // byte descriptors (kernels_match_u8.hip; the quantiser is quant_rules.hpp): float rows to bytes, and the match of byte tables
 void desc_quantize_rows(const float *Y, long ldy, int n, int r, float scale, const float *offset, uint8_t *out, long ldo, hipStream_t s);
 void match_u8_norms(const uint8_t *x, long ld, long n, int r, bool negate, int32_t *norm, hipStream_t s);
-using match_slicing::match_u8_tiles_per_slice;
-using match_slicing::match_u8_slices;
 void match_u8_top2(const uint8_t *query, long ldq, int nq, const uint8_t *train, long ldt, int nt, int r, const int32_t *qnorm,
                    const int32_t *tneg, int tiles_per_slice, int32_t *idx, int32_t *sqdist, void *part, int32_t *out, hipStream_t s);
 // keypoint patches (kernels_patch.hip;the frames and the sampling rule are patch_rules.hpp)

@@ -310,7 +310,7 @@ void match_top2(const float *query, long ldq, int nq, const float *train, long l
                 int tiles_per_slice, int32_t *idx, float *sqdist, void *part, float *out, hipStream_t s)
 {
     if (nq <= 0 || nt <= 0) return;
-    const int slices = match_slices(nt, tiles_per_slice);
+    const int slices = match_slicing::slices(match_slicing::kFloat, nt, tiles_per_slice);
     const dim3 grid((unsigned)((nq + MQ - 1) / MQ), (unsigned)slices);
     i32x4 *pp = (!out && slices > 1) ? static_cast<i32x4 *>(part) : nullptr;
     const bool multi = r > KC;

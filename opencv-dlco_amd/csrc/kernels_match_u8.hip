@@ -318,7 +318,7 @@ void match_u8_top2(const uint8_t *query, long ldq, int nq, const uint8_t *train,
                    const int32_t *tneg, int tiles_per_slice, int32_t *idx, int32_t *sqdist, void *part, int32_t *out, hipStream_t s)
 {
     if (nq <= 0 || nt <= 0) return;
-    const int slices = match_u8_slices(nt, tiles_per_slice);
+    const int slices = match_slicing::slices(match_slicing::kU8, nt, tiles_per_slice);
     const dim3 grid((unsigned)((nq + UQ - 1) / UQ), (unsigned)slices);
     i32x4 *pp = (!out && slices > 1) ? static_cast<i32x4 *>(part) : nullptr;
     const bool multi = r > UK;

@@ -14,47 +14,38 @@
 
 namespace match_slicing {
 
-constexpr int MQ = 128;                // float matcher: queries per workgroup
-constexpr int TN = 128;                //                train rows per staged tile
-constexpr int UQ = 256;                // byte matcher: queries per workgroup
-constexpr int UT = 128;                //               train rows per staged tile
+// The numbers of a matcher's kernel that the rule takes.
+struct Shape {
+    int qblock;                        // queries per workgroup
+    int tile;                          // train rows per staged tile
+    int fill_cu;                       // workgroups that a CU holds at once
+    int per_cu;                        // workgroups per CU wanted from a launch
+};
+// The float matcher: one workgroup runs per CU (133 KB of LDS).  The byte matcher: a CU holds several workgroups (37 KB of
+// LDS, one wave per SIMD each), so twice the CUs are to be filled first and sixteen workgroups per CU wanted.
+constexpr Shape kFloat{128, 128, 1, 8}, kU8{256, 128, 2, 16};
 
-// Slices of train for nq queries, whole tiles per slice.  One workgroup runs per CU.  First enough slices that every
-// CU has one (2048 x 2048: 16 query blocks x 16 one-tile slices took 41 us, x 4 four-tile slices 70).  Beyond that a
-// launch is a number of rounds of n_cu workgroups and the last round may be nearly empty (782 query blocks on 256 CUs:
+constexpr int MQ = kFloat.qblock, TN = kFloat.tile;        // the kernels' compile-time ints
+constexpr int UQ = kU8.qblock, UT = kU8.tile;
+
+// Slices of train for nq queries, whole tiles per slice.  First enough slices that every CU has its workgroups (float,
+// 2048 x 2048: 16 query blocks x 16 one-tile slices took 41 us, x 4 four-tile slices 70).  Beyond that a launch is a
+// number of rounds of fill_cu * n_cu workgroups and the last round may be nearly empty (float, 782 query blocks on 256 CUs:
 // 3.05 rounds take the time of 4; 100 000 x 100 000 at r = 128 went from 63.8 to 48.5 ms with three slices, 9.2 rounds):
-// enough slices for eight rounds keep that loss near a tenth, as long as a slice keeps four tiles (a workgroup's start -
-// its A fragments, the first tile's latency - is paid per slice).  Returns the tiles per slice; the slice count is
-// ceil(tiles / that).
-inline int match_tiles_per_slice(long nq, long nt, int n_cu)
+// enough slices for per_cu workgroups per CU keep that loss near a tenth, as long as a slice keeps four tiles (a
+// workgroup's start - its A fragments, the first tile's latency - is paid per slice).  Returns the tiles per slice; the
+// slice count is slices() of that.
+inline int tiles_per_slice(const Shape &s, long nq, long nt, int n_cu)
 {
-    const long qblocks = (nq + MQ - 1) / MQ, tiles = (nt + TN - 1) / TN;
-    const long fill = std::min(tiles, (n_cu + qblocks - 1) / qblocks);
-    const long rounds = std::min(tiles / 4, (8L * n_cu + qblocks - 1) / qblocks);
+    const long qblocks = (nq + s.qblock - 1) / s.qblock, tiles = (nt + s.tile - 1) / s.tile;
+    const long fill = std::min(tiles, ((long)s.fill_cu * n_cu + qblocks - 1) / qblocks);
+    const long rounds = std::min(tiles / 4, ((long)s.per_cu * n_cu + qblocks - 1) / qblocks);
     const long want = std::max(1L, std::max(fill, rounds));
     return (int)((tiles + want - 1) / want);
 }
-inline int match_slices(long nt, int tiles_per_slice)
+inline int slices(const Shape &s, long nt, int tiles_per_slice)
 {
-    const long tiles = (nt + TN - 1) / TN;
-    return (int)((tiles + tiles_per_slice - 1) / tiles_per_slice);
-}
-
-// The same for the byte matcher: the rule of match_tiles_per_slice with that kernel's numbers, which is why it is not
-// that function: a query block is 256 rows, and a CU holds several workgroups (37 KB of LDS, one wave per SIMD each), so
-// twice the CUs are to be filled first and sixteen workgroups per CU keep the loss of the last round small, as long as a
-// slice keeps four tiles.
-inline int match_u8_tiles_per_slice(long nq, long nt, int n_cu)
-{
-    const long qblocks = (nq + UQ - 1) / UQ, tiles = (nt + UT - 1) / UT;
-    const long fill = std::min(tiles, (2L * n_cu + qblocks - 1) / qblocks);
-    const long rounds = std::min(tiles / 4, (16L * n_cu + qblocks - 1) / qblocks);
-    const long want = std::max(1L, std::max(fill, rounds));
-    return (int)((tiles + want - 1) / want);
-}
-inline int match_u8_slices(long nt, int tiles_per_slice)
-{
-    const long tiles = (nt + UT - 1) / UT;
+    const long tiles = (nt + s.tile - 1) / s.tile;
     return (int)((tiles + tiles_per_slice - 1) / tiles_per_slice);
 }
 

@@ -6,15 +6,11 @@
 extern "C" {
 
 // kind 0: the float matcher, kind 1: the byte matcher
-int shim_tiles_per_slice(int64_t nq, int64_t nt, int n_cu, int kind)
-{
-    return kind ? match_slicing::match_u8_tiles_per_slice((long)nq, (long)nt, n_cu) : match_slicing::match_tiles_per_slice((long)nq, (long)nt, n_cu);
-}
+static const match_slicing::Shape &shape(int kind) { return kind ? match_slicing::kU8 : match_slicing::kFloat; }
 
-int shim_slices(int64_t nt, int tiles_per_slice, int kind)
-{
-    return kind ? match_slicing::match_u8_slices((long)nt, tiles_per_slice) : match_slicing::match_slices((long)nt, tiles_per_slice);
-}
+int shim_tiles_per_slice(int64_t nq, int64_t nt, int n_cu, int kind) { return match_slicing::tiles_per_slice(shape(kind), (long)nq, (long)nt, n_cu); }
+
+int shim_slices(int64_t nt, int tiles_per_slice, int kind) { return match_slicing::slices(shape(kind), (long)nt, tiles_per_slice); }
 
 int shim_query_block(int kind) { return kind ? match_slicing::UQ : match_slicing::MQ; }
 

@@ -220,6 +220,43 @@ def test_cross_sqdists_over_the_query_block_loop(ctx):
         bad[:8].tolist(), [bool((X[i].view(np.uint32) == want[i].view(np.uint32)).all()) for i in (BLOCK - 1, BLOCK, BLOCK + 76)])
 
 
+# ---- 4c. the loop over chunks of queries of the host forms ------------------------------------------------------------------
+CHUNK_BYTES = 2 ** 28                                      # the library's documented chunk size: query rows, padded to 16 bytes, per upload
+WIDE = 1021                                                # the widest rows whose host pitch (1021 floats) and device pitch (1024) differ
+CHUNK = CHUNK_BYTES // ((4 * WIDE + 15) // 16 * 16)        # 65 536 rows
+
+
+def test_match_over_the_query_chunk_loop(ctx):
+    """65 536 + 37 queries of 1021 floats are two uploads of the host form, the second read at row 65 536 of the caller's
+    table (pitch 1021) into rows of pitch 1024, its results written at an offset of 65 536 rows.  The queries repeat the
+    base as in the block-loop test, and the base is held against the float64 reference, planted ties included."""
+    nq, nt, r = CHUNK + 37, 40, WIDE
+    assert CHUNK == 65536
+    Qb, T, D, G = case(BASE, nt, r)
+    bi, bd = check_against_the_reference(ctx, Qb, T, D, G)
+    rep = np.arange(nq) % BASE
+    idx, d = ctx.match(Qb[rep], T)
+    bad = np.nonzero((idx != bi[rep]).any(1) | (d.view(np.uint32) != bd[rep].view(np.uint32)).any(1))[0]
+    print("match %d x %d r %d: %d rows differ from the base's" % (nq, nt, r, len(bad)))
+    assert len(bad) == 0, "rows %s differ; %s" % (bad[:8].tolist(), "; ".join(
+        "row %d: got %s / %s, want %s / %s" % (i, idx[i].tolist(), d[i].tolist(), bi[i % BASE].tolist(), bd[i % BASE].tolist())
+        for i in (CHUNK - 1, CHUNK, CHUNK + 36)))
+
+
+def test_cross_sqdists_over_the_query_chunk_loop(ctx):
+    nq, nt, r = CHUNK + 37, 40, WIDE
+    Qb, T, D, G = case(BASE, nt, r)
+    Xb = ctx.cross_sqdists(Qb, T)
+    assert (np.abs(Xb.astype(np.float64) - D) <= G).all() and (Xb >= 0).all()
+    rep = np.arange(nq) % BASE
+    X = ctx.cross_sqdists(Qb[rep], T)
+    want = Xb[rep]
+    bad = np.nonzero((X.view(np.uint32) != want.view(np.uint32)).any(1))[0]
+    print("cross_sqdists %d x %d r %d: %d rows differ from the base's" % (nq, nt, r, len(bad)))
+    assert len(bad) == 0, "rows %s differ; rows 65535, 65536, 65572 equal: %s" % (
+        bad[:8].tolist(), [bool((X[i].view(np.uint32) == want[i].view(np.uint32)).all()) for i in (CHUNK - 1, CHUNK, CHUNK + 36)])
+
+
 def test_non_finite_inputs_keep_the_indices_in_range(ctx):
     Q, T = make_tables(200, 300, 64)
     Q[5, 7], Q[9, :] = np.nan, np.inf

@@ -1,6 +1,7 @@
 """The byte matcher where it was written to work: slices of several tiles (both LDS buffers, the hand-over between them, a
 train-row decode with tile > 0, a ragged last tile behind whole ones: cases b and d), the chunks of r > 128 interleaved with those tiles,
-every level of the merge under ties, one slice that holds all tiles, and the host loop over blocks of 2^20 queries.  The
+every level of the merge under ties, one slice that holds all tiles, and the host loops over blocks of 2^20 queries and
+over the chunks in which the queries go up.  The
 small shapes of test_match_u8_gpu.py never leave one tile per slice (tests/test_match_slices.py pins that).
 
 Which regime a shape reaches depends on the device's CU count, so the shapes are picked with the restated rule of
@@ -176,8 +177,7 @@ def test_ties_across_every_merge_level(ctx, n_cu, r):
 
 
 # ---- d. one slice that holds all tiles, and the loop over blocks of 2^20 queries --------------------------------------------
-def block_case(nt):
-    r = 16
+def block_case(nt, r=16):
     rng = np.random.default_rng(9300 + nt)
     base = rng.integers(0, 256, (BASE, r), dtype=np.uint8)
     T = rng.integers(0, 256, (nt, r), dtype=np.uint8)
@@ -214,3 +214,34 @@ def test_cross_sqdists_u8_over_the_query_block_loop(ctx):
     print("cross_sqdists_u8 %d x %d: %d rows differ" % (nq, nt, len(bad)))
     assert np.array_equal(X, want), "rows %s differ; row 2^20 - 1: %s, row 2^20: %s, row 2^20 + 76: %s" % (
         bad[:8].tolist(), (X[BLOCK - 1] == want[BLOCK - 1]).all(), (X[BLOCK] == want[BLOCK]).all(), (X[BLOCK + 76] == want[BLOCK + 76]).all())
+
+
+# ---- e. the loop over chunks of queries of the host forms -----------------------------------------------------------------
+CHUNK_BYTES = 2 ** 28                                         # the library's documented chunk size: query rows, padded to 16 bytes, per upload
+WIDE = 1021                                                   # the widest rows whose host pitch (1021 bytes) and device pitch (1024) differ
+CHUNK = CHUNK_BYTES // ((WIDE + 15) // 16 * 16)               # 262 144 rows
+
+
+def test_match_u8_over_the_query_chunk_loop(ctx):
+    """262 144 + 37 queries of 1021 bytes are two uploads: the second is read at row 262 144 of the caller's table (pitch
+    1021) into rows of pitch 1024, and its results land at an offset of 262 144 rows.  Three tiles of train, the last ragged."""
+    nq, nt = CHUNK + 37, 300
+    assert CHUNK == 262144
+    base, T, D = block_case(nt, WIDE)
+    bi, bd = ref_top2(D)
+    rep = np.arange(nq) % BASE
+    idx, d = ctx.match_u8(base[rep], T)
+    print("    match_u8: %d index and %d distance mismatches" % ((idx != bi[rep]).sum(), (d != bd[rep]).sum()))
+    assert np.array_equal(idx, bi[rep]) and np.array_equal(d, bd[rep]), report("match_u8", idx, d, bi[rep], bd[rep], [CHUNK - 1, CHUNK, CHUNK + 36])
+
+
+def test_cross_sqdists_u8_over_the_query_chunk_loop(ctx):
+    nq, nt = CHUNK + 37, 40
+    base, T, D = block_case(nt, WIDE)
+    rep = np.arange(nq) % BASE
+    X = ctx.cross_sqdists_u8(base[rep], T)
+    want = D.astype(np.int32)[rep]
+    bad = np.nonzero((X != want).any(1))[0]
+    print("cross_sqdists_u8 %d x %d: %d rows differ" % (nq, nt, len(bad)))
+    assert np.array_equal(X, want), "rows %s differ; row 262143: %s, row 262144: %s, row 262180: %s" % (
+        bad[:8].tolist(), (X[CHUNK - 1] == want[CHUNK - 1]).all(), (X[CHUNK] == want[CHUNK]).all(), (X[CHUNK + 36] == want[CHUNK + 36]).all())
