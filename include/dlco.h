@@ -256,6 +256,36 @@ int dlco_psd_project(dlco_ctx *ctx, const float *dfavg_host, uint32_t t,
  * and every 128 x 128 tile is fetched from HBM once per product.  rows <= 160 for modes 1 / 3. */
 int dlco_sym_product(dlco_ctx *ctx, const float *X_host, int32_t rows, const float *G_host, int32_t mode,
                      float *out_host);
+/* The generic fp32 GEMM under every Gram matrix, rotation and projection of the step (no reference line: the reference
+ * calls cuBLAS / OpenBLAS sgemm), on host arrays, for tests and for timing single shapes:
+ *   C [M,N] = alpha * A(M,K) * B(K,N) + beta * C + b1 * E1 + b2 * E2, and with a twin operand C2 = the same with B2.
+ * An operand is `rows` memory rows of pitch ld.  kmajor: memory rows run along K, element (x, k) at row(k) * ld + x; else
+ * along M / N, element (x, k) at row(x) * ld + k.  row(i) = row_ids ? row_ids[i] : i, and with row_ids2 the operand row is
+ * memory row row_ids[i] minus memory row row_ids2[i]; row_scale [K] (k-major operands only) scales row k.
+ * split_k > 1: K slices summed in a fixed order.  k_dev >= 0: a K limit the kernel reads from device memory (<= K), -1:
+ * none.  B2_host: laid out like B; needs split_k == 1.  small_m_tiles / small_n_tiles: 64-wide tiles whatever M / N.
+ * depth: K tiles of global loads in flight per workgroup, 0 = the library's choice (what every other entry point runs),
+ * 1 = one tile (the schedule every launch had before the choice existed).  Results do not depend on it bit for bit; it
+ * exists for measurement.  *depth_used (may be NULL): the depth the launch ran with.  reps > 0: the launch is also
+ * repeated reps times between two HIP events, *us_per_launch (may be NULL) = their distance / reps.
+ * C_host [M,N] holds C on entry (read when beta != 0) and the result on return; C2_host likewise, NULL without B2. */
+typedef struct dlco_gemm_operand {
+    const float   *host;
+    int32_t        rows, ld;
+    int32_t        kmajor;
+    const int32_t *row_ids, *row_ids2;
+    const float   *row_scale;
+} dlco_gemm_operand;
+typedef struct dlco_gemm_probe_args {
+    int32_t M, N, K;
+    dlco_gemm_operand A, B;
+    const float *B2_host;
+    int32_t split_k, k_dev, small_m_tiles, small_n_tiles, depth, reps;
+    float   alpha, beta, b1, b2;
+    const float *E1_host, *E2_host;     /* [M,N] or NULL */
+} dlco_gemm_probe_args;
+int dlco_gemm_probe(dlco_ctx *ctx, const dlco_gemm_probe_args *args, float *C_host, float *C2_host, int32_t *depth_used,
+                    double *us_per_launch);
 /* H1: sum_i sum_j max(pos_i + 1 - neg_j, 0)  (src/kernelop-opencv.cu:49-80). */
 int dlco_hinge_sum(dlco_ctx *ctx, const float *pos_host, int32_t n_pos,
                    const float *neg_host, int32_t n_neg, double *out);

@@ -53,6 +53,25 @@ class LogEntry(C.Structure):
     ]
 
 
+class GemmOperand(C.Structure):
+    _fields_ = [
+        ("host", C.POINTER(C.c_float)), ("rows", C.c_int32), ("ld", C.c_int32), ("kmajor", C.c_int32),
+        ("row_ids", C.POINTER(C.c_int32)), ("row_ids2", C.POINTER(C.c_int32)), ("row_scale", C.POINTER(C.c_float)),
+    ]
+
+
+class GemmProbeArgs(C.Structure):
+    _fields_ = [
+        ("M", C.c_int32), ("N", C.c_int32), ("K", C.c_int32),
+        ("A", GemmOperand), ("B", GemmOperand),
+        ("B2_host", C.POINTER(C.c_float)),
+        ("split_k", C.c_int32), ("k_dev", C.c_int32), ("small_m_tiles", C.c_int32), ("small_n_tiles", C.c_int32),
+        ("depth", C.c_int32), ("reps", C.c_int32),
+        ("alpha", C.c_float), ("beta", C.c_float), ("b1", C.c_float), ("b2", C.c_float),
+        ("E1_host", C.POINTER(C.c_float)), ("E2_host", C.POINTER(C.c_float)),
+    ]
+
+
 def build(verbose=False):
     """Compile libdlco.so in-tree with hipcc for gfx950 (cross-compiles without a GPU)."""
     cmd = ["make", "-C", os.path.join(_HERE, "csrc"), "-j8"]
@@ -115,6 +134,7 @@ def load():
     L.dlco_psd_project.argtypes = [vp, f32p, C.c_uint32, f32p, i32p, f32p]
     L.dlco_hinge_sum.argtypes = [vp, f32p, C.c_int32, f32p, C.c_int32, C.POINTER(C.c_double)]
     L.dlco_sym_product.argtypes = [vp, f32p, C.c_int32, f32p, C.c_int32, f32p]
+    L.dlco_gemm_probe.argtypes = [vp, C.POINTER(GemmProbeArgs), f32p, f32p, i32p, C.POINTER(C.c_double)]
     L.dlco_roc_stats.argtypes = [vp, f32p, u8p, C.c_int32, f32p, C.POINTER(C.c_double)]
     L.dlco_log_step.argtypes = [vp, C.POINTER(LogEntry)]
     L.dlco_get_saved.argtypes = [vp, f32p, i32p, f32p]
@@ -469,6 +489,41 @@ class Context:
         out = np.empty_like(x)
         self._ck(self.L.dlco_sym_product(self.h, _p(x, f32p), x.shape[0], _p(g, f32p), mode, _p(out, f32p)))
         return out
+
+    def gemm_probe(self, A, B, M, N, K, a_kmajor=False, b_kmajor=False, a_ids=None, a_ids2=None, a_scale=None, b_ids=None,
+                   b_ids2=None, b_scale=None, B2=None, split_k=1, k_dev=-1, small_m_tiles=False, small_n_tiles=False, depth=0,
+                   alpha=1.0, beta=0.0, C_in=None, E1=None, b1=0.0, E2=None, b2=0.0, reps=0):
+        """The generic fp32 GEMM on host arrays (dlco_gemm_probe).  A, B (and B2, laid out like B) are the operands as they
+        lie in memory, 2-D [rows, ld]: k-major ones hold K (or gathered) rows of M / N elements, the others M / N (or
+        gathered) rows of K elements.  Returns dict(C, C2 (None without B2), depth, us (None without reps))."""
+        keep = []
+
+        def operand(x, kmajor, ids, ids2, scale):
+            x = _f32(x)
+            assert x.ndim == 2
+            ids, ids2 = (None if i is None else _i32(i) for i in (ids, ids2))
+            scale = None if scale is None else _f32(scale)
+            keep.extend([x, ids, ids2, scale])
+            return GemmOperand(_p(x, f32p), x.shape[0], x.shape[1], int(kmajor), _p(ids, i32p), _p(ids2, i32p), _p(scale, f32p)), x
+
+        a = GemmProbeArgs()
+        a.M, a.N, a.K = M, N, K
+        a.A, _ = operand(A, a_kmajor, a_ids, a_ids2, a_scale)
+        a.B, b = operand(B, b_kmajor, b_ids, b_ids2, b_scale)
+        twin = None if B2 is None else _f32(B2)
+        assert twin is None or twin.shape == b.shape
+        e1, e2 = (None if e is None else _f32(e) for e in (E1, E2))
+        assert all(e is None or e.shape == (M, N) for e in (e1, e2))
+        a.B2_host, a.E1_host, a.E2_host = _p(twin, f32p), _p(e1, f32p), _p(e2, f32p)
+        a.split_k, a.k_dev, a.depth, a.reps = split_k, k_dev, depth, reps
+        a.small_m_tiles, a.small_n_tiles = int(small_m_tiles), int(small_n_tiles)
+        a.alpha, a.beta, a.b1, a.b2 = alpha, beta, b1, b2
+        out = np.zeros((M, N), np.float32) if C_in is None else np.array(C_in, dtype=np.float32, order="C")
+        assert out.shape == (M, N)
+        out2 = None if twin is None else out.copy()
+        used, us = C.c_int32(), C.c_double()
+        self._ck(self.L.dlco_gemm_probe(self.h, C.byref(a), _p(out, f32p), _p(out2, f32p), C.byref(used), C.byref(us)))
+        return dict(C=out, C2=out2, depth=used.value, us=us.value if reps else None)
 
     def hinge_sum(self, pos, neg):
         p, n = _f32(pos), _f32(neg)

@@ -1257,6 +1257,80 @@ int dlco_sym_product(dlco_ctx *c, const float *X_host, int32_t rows, const float
     });
 }
 
+int dlco_gemm_probe(dlco_ctx *c, const dlco_gemm_probe_args *a, float *C_host, float *C2_host, int32_t *depth_used,
+                    double *us_per_launch)
+{
+    if (!c || !a || !C_host || a->M < 1 || a->N < 1 || a->K < 1 || a->split_k < 1 || a->reps < 0 || a->k_dev > a->K) return DLCO_ERR_INVALID;
+    if ((a->B2_host != nullptr) != (C2_host != nullptr)) return DLCO_ERR_INVALID;
+    return guarded(c, [&] {
+        DLCO_HIP(hipSetDevice(c->cfg.device));
+        // an operand must hold every element the product addresses: t = its M or N extent
+        auto check = [&](const dlco_gemm_operand &o, int t) {
+            const int along = o.kmajor ? t : a->K, ids = o.kmajor ? a->K : t;   // contiguous extent, memory rows addressed
+            DLCO_CHECK(o.host && o.rows >= 1 && o.ld >= along, DLCO_ERR_INVALID, "dlco_gemm_probe: operand smaller than the product");
+            DLCO_CHECK(!o.row_ids2 || o.row_ids, DLCO_ERR_INVALID, "dlco_gemm_probe: row_ids2 without row_ids");
+            DLCO_CHECK(!o.row_scale || o.kmajor, DLCO_ERR_INVALID, "dlco_gemm_probe: row_scale needs a k-major operand");
+            DLCO_CHECK(o.row_ids || o.rows >= ids, DLCO_ERR_INVALID, "dlco_gemm_probe: operand has too few rows");
+            for (const int32_t *id : {o.row_ids, o.row_ids2})
+                for (int x = 0; id && x < ids; x++)
+                    DLCO_CHECK(id[x] >= 0 && id[x] < o.rows, DLCO_ERR_INVALID, "dlco_gemm_probe: row id out of range");
+        };
+        check(a->A, a->M);
+        check(a->B, a->N);
+        struct Dev { DevBuf<float> p, scale; DevBuf<int32_t> ids, ids2; };
+        auto upload = [&](const dlco_gemm_operand &o, int t, const float *host, Dev &d, GemmOperand &g) {
+            const int ids = o.kmajor ? a->K : t;
+            d.p.alloc((size_t)o.rows * o.ld);
+            h2d(c, d.p.p, host, (size_t)o.rows * o.ld * sizeof(float));
+            g.p = d.p.p; g.ld = o.ld; g.kmajor = o.kmajor != 0;
+            if (o.row_ids) { d.ids.alloc(ids); h2d(c, d.ids.p, o.row_ids, (size_t)ids * sizeof(int32_t)); g.row_ids = d.ids.p; }
+            if (o.row_ids2) { d.ids2.alloc(ids); h2d(c, d.ids2.p, o.row_ids2, (size_t)ids * sizeof(int32_t)); g.row_ids2 = d.ids2.p; }
+            if (o.row_scale) { d.scale.alloc(a->K); h2d(c, d.scale.p, o.row_scale, (size_t)a->K * sizeof(float)); g.row_scale = d.scale.p; }
+        };
+        const size_t mn = (size_t)a->M * a->N;
+        Dev dA, dB, dB2;
+        DevBuf<float> C, C2, E1, E2, slab;
+        DevBuf<int> kdev;
+        GemmArgs g;
+        GemmOperand twin;
+        g.M = a->M; g.N = a->N; g.K = a->K;
+        upload(a->A, a->M, a->A.host, dA, g.A);
+        upload(a->B, a->N, a->B.host, dB, g.B);
+        if (a->B2_host) { upload(a->B, a->N, a->B2_host, dB2, twin); g.B2 = twin.p; C2.alloc(mn); g.C2 = C2.p; }
+        C.alloc(mn); g.C = C.p; g.ldc = a->N;
+        g.alpha = a->alpha; g.beta = a->beta; g.b1 = a->b1; g.b2 = a->b2;
+        if (a->E1_host) { E1.alloc(mn); h2d(c, E1.p, a->E1_host, mn * sizeof(float)); g.E1 = E1.p; }
+        if (a->E2_host) { E2.alloc(mn); h2d(c, E2.p, a->E2_host, mn * sizeof(float)); g.E2 = E2.p; }
+        if (a->k_dev >= 0) { const int k = a->k_dev; kdev.alloc(1); h2d(c, kdev.p, &k, sizeof(int)); g.k_dev = kdev.p; }
+        g.split_k = a->split_k;
+        slab.alloc(gemm_slab_floats(a->M, a->N, a->split_k)); g.slab = slab.p;
+        g.small_m_tiles = a->small_m_tiles != 0; g.small_n_tiles = a->small_n_tiles != 0;
+        g.depth = a->depth;
+        int used = 0;
+        g.depth_used = &used;
+        if (a->reps > 0) {                                       // timed launches first: they overwrite C
+            hipEvent_t e0, e1;
+            DLCO_HIP(hipEventCreate(&e0)); DLCO_HIP(hipEventCreate(&e1));
+            for (int i = 0; i < 3; i++) gemm_f32(g, c->stream);
+            DLCO_HIP(hipEventRecord(e0, c->stream));
+            for (int i = 0; i < a->reps; i++) gemm_f32(g, c->stream);
+            DLCO_HIP(hipEventRecord(e1, c->stream));
+            sync(c);
+            float ms = 0.f;
+            DLCO_HIP(hipEventElapsedTime(&ms, e0, e1));
+            (void)hipEventDestroy(e0); (void)hipEventDestroy(e1);
+            if (us_per_launch) *us_per_launch = 1e3 * ms / a->reps;
+        }
+        h2d(c, C.p, C_host, mn * sizeof(float));
+        if (C2_host) h2d(c, C2.p, C2_host, mn * sizeof(float));
+        gemm_f32(g, c->stream);
+        sync(c);
+        d2h(c, C_host, C.p, mn * sizeof(float));
+        if (C2_host) d2h(c, C2_host, C2.p, mn * sizeof(float));
+        if (depth_used) *depth_used = used;
+    });
+}
+
 int dlco_hinge_sum(dlco_ctx *c, const float *pos_host, int32_t n_pos, const float *neg_host, int32_t n_neg, double *out)
 {
     if (!c || !out || n_pos < 0 || n_neg < 0) return DLCO_ERR_INVALID;

@@ -208,9 +208,13 @@ struct GemmArgs {
     float *C2 = nullptr;                // out like B; needs split_k == 1
     bool small_m_tiles = false;         // 64-row tiles whatever M ...
     bool small_n_tiles = false;         // ... and 64-column tiles whatever N: the 96 x 400 batch projection fills 64 x 64 tiles to 67 %, 64 x 128 ones to 58 % (-6 us)
+    int depth = 0;                      // K tiles in flight: 0 = gemm_f32's own choice (what every library path passes), 1 = one; same bits
+    int *depth_used = nullptr;          // host pointer, optional: the depth the launch ran with
 };
 
 void gemm_f32(const GemmArgs &a, hipStream_t s);
+// K tiles gemm_f32 keeps in flight at depth 0 where it takes 64-wide tiles of plain operands (elsewhere: 1)
+int gemm_ring_depth();
 // Same product on the bf16 matrix cores with split operands (x = hi + lo, three MFMAs per term,
 // fp32 accumulation; ~1e-5 relative error): kernels_bf16x2.hip.  plane_hi/lo are workspaces of
 // bf16x2_plane_bytes(M, K) bytes each.  Returns false for unsupported shapes (the caller then takes gemm_f32).

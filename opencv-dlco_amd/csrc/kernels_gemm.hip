@@ -19,6 +19,13 @@ namespace {
 constexpr int BK = 16;
 constexpr int PAD = 4;
 constexpr int NT = 256;
+// K tiles in flight in the 64-wide instantiations (gemm_kernel's DEPTH); 128 x 128 tiles keep one.  Chosen by
+// measurement among 2, 4 and 8; a build with -DDLCO_GEMM_DEPTH=n repeats the measurement.
+#ifndef DLCO_GEMM_DEPTH
+#define DLCO_GEMM_DEPTH 4
+#endif
+constexpr int RING_DEPTH = DLCO_GEMM_DEPTH;
+static_assert(RING_DEPTH == 2 || RING_DEPTH == 4 || RING_DEPTH == 8, "ring depth: 2, 4 or 8");
 
 struct OperandDev {
     const float *p;
@@ -61,6 +68,7 @@ struct GemmDev {
 
 // Stage one BK x BT tile of an operand into LDS (k-major image [BK][BT+PAD]).
 // KM = memory rows run along K (contiguous along the M/N index), else along M/N.
+// A tile at or beyond kend is all zeros and touches no memory.
 template <int BT, bool KM>
 __device__ __forceinline__ void load_tile(const OperandDev &op, int t0, int tmax, int k0, int kend,
                                           f32x4 (&regs)[BT / 64])
@@ -95,6 +103,78 @@ __device__ __forceinline__ void load_tile(const OperandDev &op, int t0, int tmax
     }
 }
 
+// ---- plain operands: the loader of the deeper schedules ---------------------------------------------------------
+// A load that sits behind a branch, be it a lane's bounds test, cannot be counted by hipcc among the requests in flight:
+// the wait for an older tile then becomes a wait for all of them, and every test of load_tile is such a branch.  An
+// operand is plain (gemm_f32: plain_operand) when one unconditional 16-byte load per piece, at a clamped address inside
+// the operand, and a select afterwards give load_tile's values: 16-byte rows, nothing subtracted or scaled, no row ids
+// along K, and the contiguous extent (M or N of a k-major operand, else K) a multiple of 4.
+
+// The part of a row-major operand's addressing that no K tile changes: the memory row of each tile row a thread stages
+// (rows beyond tmax: the last one, never used).  A gathered row id fetched inside the K loop would be the youngest
+// request in flight; waiting for it drains every tile behind it.
+template <int BT>
+struct TileRows {
+    const float *r[BT / 64];
+};
+
+template <int BT, bool KM>
+__device__ __forceinline__ void tile_rows(const OperandDev &op, int t0, int tmax, TileRows<BT> &rows)
+{
+#pragma unroll
+    for (int u = 0; u < BT / 64; u++) {
+        rows.r[u] = op.p;
+        if (KM) continue;
+        const int t = min(t0 + (int)(threadIdx.x + NT * u) / (BK / 4), tmax - 1);
+        rows.r[u] = op.p + (op.row_ids ? (long)op.row_ids[t] : (long)t) * op.ld;
+    }
+}
+
+// A plain operand's tile in two steps that together give load_tile's values.  fetch_plain: the loads alone, unconditional,
+// at addresses clamped into the operand (K = its whole K extent, a multiple of 4 when !KM).  zero_beyond: the zero fill
+// beyond M / N and kend, applied when the tile is copied to LDS, DEPTH - 1 iterations later: next to the load hipcc
+// turns the select back into a branch around it.
+template <int BT, bool KM>
+__device__ __forceinline__ void fetch_plain(const OperandDev &op, const TileRows<BT> &rows, int t0, int tmax, int k0, int kend, int K,
+                                            f32x4 (&regs)[BT / 64])
+{
+    const int tid = threadIdx.x;
+#pragma unroll
+    for (int u = 0; u < BT / 64; u++) {
+        const int f = tid + NT * u;
+        if (KM) {
+            const int row = f / (BT / 4), c4 = f % (BT / 4);
+            regs[u] = *reinterpret_cast<const f32x4 *>(op.p + (long)min(k0 + row, kend - 1) * op.ld + min(t0 + c4 * 4, tmax - 4));
+        } else {
+            const int kq = f % (BK / 4);
+            regs[u] = *reinterpret_cast<const f32x4 *>(rows.r[u] + min(k0 + kq * 4, K - 4));
+        }
+    }
+}
+
+template <int BT, bool KM>
+__device__ __forceinline__ void zero_beyond(int t0, int tmax, int k0, int kend, f32x4 (&regs)[BT / 64])
+{
+    const int tid = threadIdx.x;
+#pragma unroll
+    for (int u = 0; u < BT / 64; u++) {
+        const int f = tid + NT * u;
+        int live;                                                 // elements of the piece that are the operand's
+        if (KM) {
+            const int row = f / (BT / 4), c4 = f % (BT / 4);
+            live = (k0 + row < kend && t0 + c4 * 4 < tmax) ? 4 : 0;
+        } else {
+            const int row = f / (BK / 4), kq = f % (BK / 4);
+            live = t0 + row < tmax ? kend - (k0 + kq * 4) : 0;
+        }
+        regs[u][0] = live > 0 ? regs[u][0] : 0.f;
+        regs[u][1] = live > 1 ? regs[u][1] : 0.f;
+        regs[u][2] = live > 2 ? regs[u][2] : 0.f;
+        regs[u][3] = live > 3 ? regs[u][3] : 0.f;
+    }
+}
+
+// Copy a fetched tile into its LDS image (k-major [BK][BT+PAD]).
 template <int BT, bool KM>
 __device__ __forceinline__ void store_tile(float (*lds)[BT + PAD], const f32x4 (&regs)[BT / 64])
 {
@@ -115,7 +195,16 @@ __device__ __forceinline__ void store_tile(float (*lds)[BT + PAD], const f32x4 (
     }
 }
 
-template <int WM, int WN, bool A_KM, bool B_KM>
+// DEPTH = K tiles whose global loads are in flight.  Tile p is multiplied from LDS image p & 1 during iteration p,
+// copied there from register set p % DEPTH at the end of iteration p - 1 and requested into that set at the top of
+// iteration p - DEPTH (tiles 0 .. DEPTH-1: before the loop), so the copy waits for a request DEPTH - 1 tiles old
+// (s_waitcnt vmcnt(n), n > 0) instead of for the youngest one.  DEPTH 1 is the single-tile schedule on load_tile: one
+// exposed global-load latency per K tile, which is all a 64-wide launch of 6 - 15 tiles consists of.  DEPTH > 1 needs
+// plain operands (fetch_plain).  The loop is unrolled by DEPTH so that every register set has a static name (one
+// chosen at run time would live in scratch memory), and a trip has no branch: a request beyond the last tile yields
+// zeros, which go to the image nobody reads any more.  The arithmetic does not depend on DEPTH: every accumulator is
+// the same k-ordered chain over the same LDS images.
+template <int WM, int WN, bool A_KM, bool B_KM, int DEPTH>
 __global__ __launch_bounds__(NT) void gemm_kernel(GemmDev g)
 {
     constexpr int BM = 64 * WM, BN = 64 * WN;
@@ -133,7 +222,7 @@ __global__ __launch_bounds__(NT) void gemm_kernel(GemmDev g)
         if (kz == 1) { g.B.p = g.B2; g.C = g.C2; }
         kz = 0;
     }
-    int kbeg = kz * g.k_chunk;
+    const int kbeg = kz * g.k_chunk;
     int kend = min(g.K, kbeg + g.k_chunk);
     if (g.k_dev) kend = min(kend, *g.k_dev);
 
@@ -146,21 +235,36 @@ __global__ __launch_bounds__(NT) void gemm_kernel(GemmDev g)
             for (int r = 0; r < 16; r++) acc[a][b][r] = 0.f;
 
     const int nk = kend > kbeg ? (kend - kbeg + BK - 1) / BK : 0;
-    f32x4 ra[BM / 64], rb[BN / 64];
-    if (nk > 0) {
-        load_tile<BM, A_KM>(g.A, i0, g.M, kbeg, kend, ra);
-        load_tile<BN, B_KM>(g.B, j0, g.N, kbeg, kend, rb);
-        store_tile<BM, A_KM>(As[0], ra);
-        store_tile<BN, B_KM>(Bs[0], rb);
+    if (nk > 0) {                                            // (the same for the whole workgroup)
+    TileRows<BM> rows_a;
+    TileRows<BN> rows_b;
+    if (DEPTH > 1) {
+        tile_rows<BM, A_KM>(g.A, i0, g.M, rows_a);
+        tile_rows<BN, B_KM>(g.B, j0, g.N, rows_b);
     }
-    __syncthreads();
-    for (int kt = 0; kt < nk; kt++) {
-        const int buf = kt & 1;
-        if (kt + 1 < nk) {
-            load_tile<BM, A_KM>(g.A, i0, g.M, kbeg + (kt + 1) * BK, kend, ra);
-            load_tile<BN, B_KM>(g.B, j0, g.N, kbeg + (kt + 1) * BK, kend, rb);
+    struct Slot { f32x4 a[BM / 64], b[BN / 64]; };
+    Slot ring[DEPTH];
+    // one fixed order of a set's loads, before the loop and inside it
+    auto request = [&](int p, Slot &s) {
+        if (DEPTH > 1) {
+            fetch_plain<BM, A_KM>(g.A, rows_a, i0, g.M, kbeg + p * BK, kend, g.K, s.a);
+            fetch_plain<BN, B_KM>(g.B, rows_b, j0, g.N, kbeg + p * BK, kend, g.K, s.b);
+        } else {
+            load_tile<BM, A_KM>(g.A, i0, g.M, kbeg + p * BK, kend, s.a);
+            load_tile<BN, B_KM>(g.B, j0, g.N, kbeg + p * BK, kend, s.b);
         }
-        const int lr = lane & 31, lk = lane >> 5;
+    };
+    auto commit = [&](int buf, int p, const Slot &s) {       // s holds tile p
+        Slot t = s;
+        if (DEPTH > 1) {
+            zero_beyond<BM, A_KM>(i0, g.M, kbeg + p * BK, kend, t.a);
+            zero_beyond<BN, B_KM>(j0, g.N, kbeg + p * BK, kend, t.b);
+        }
+        store_tile<BM, A_KM>(As[buf], t.a);
+        store_tile<BN, B_KM>(Bs[buf], t.b);
+    };
+    const int lr = lane & 31, lk = lane >> 5;
+    auto multiply = [&](int buf) {
 #pragma unroll
         for (int kk = 0; kk < BK / 2; kk++) {
             float af[WM], bf[WN];
@@ -174,11 +278,31 @@ __global__ __launch_bounds__(NT) void gemm_kernel(GemmDev g)
                 for (int b = 0; b < WN; b++)
                     acc[a][b] = __builtin_amdgcn_mfma_f32_32x32x2f32(af[a], bf[b], acc[a][b], 0, 0, 0);
         }
-        if (kt + 1 < nk) {
-            store_tile<BM, A_KM>(As[buf ^ 1], ra);
-            store_tile<BN, B_KM>(Bs[buf ^ 1], rb);
+    };
+
+#pragma unroll
+    for (int d = 0; d < DEPTH; d++) request(d, ring[d]);
+    commit(0, 0, ring[0]);
+    __syncthreads();
+    int kt = 0;
+    for (; kt + DEPTH <= nk; kt += DEPTH) {
+#pragma unroll
+        for (int d = 0; d < DEPTH; d++) {
+            request(kt + d + DEPTH, ring[d]);
+            multiply((kt + d) & 1);
+            commit(((kt + d) & 1) ^ 1, kt + d + 1, ring[(d + 1) % DEPTH]);
+            __syncthreads();
         }
-        __syncthreads();
+    }
+    // the last nk % DEPTH tiles: everything they need was requested above
+#pragma unroll
+    for (int d = 0; d + 1 < DEPTH; d++) {
+        if (kt + d < nk) {
+            multiply((kt + d) & 1);
+            commit(((kt + d) & 1) ^ 1, kt + d + 1, ring[d + 1]);
+            __syncthreads();
+        }
+    }
     }
 
     // epilogue: C/D layout of the 32x32 MFMA: col = lane&31, row = (r&3) + 8*(r>>2) + 4*(lane>>5)
@@ -253,16 +377,31 @@ __global__ __launch_bounds__(256) void splitk_reduce_wide_kernel(const float *sl
     }
 }
 
-template <int WM, int WN>
+template <int WM, int WN, int DEPTH>
 void launch(const GemmDev &g, bool akm, bool bkm, dim3 grid, hipStream_t s)
 {
-    if (akm && bkm) hipLaunchKernelGGL((gemm_kernel<WM, WN, true, true>), grid, dim3(NT), 0, s, g);
-    else if (akm && !bkm) hipLaunchKernelGGL((gemm_kernel<WM, WN, true, false>), grid, dim3(NT), 0, s, g);
-    else if (!akm && bkm) hipLaunchKernelGGL((gemm_kernel<WM, WN, false, true>), grid, dim3(NT), 0, s, g);
-    else hipLaunchKernelGGL((gemm_kernel<WM, WN, false, false>), grid, dim3(NT), 0, s, g);
+    if (akm && bkm) hipLaunchKernelGGL((gemm_kernel<WM, WN, true, true, DEPTH>), grid, dim3(NT), 0, s, g);
+    else if (akm && !bkm) hipLaunchKernelGGL((gemm_kernel<WM, WN, true, false, DEPTH>), grid, dim3(NT), 0, s, g);
+    else if (!akm && bkm) hipLaunchKernelGGL((gemm_kernel<WM, WN, false, true, DEPTH>), grid, dim3(NT), 0, s, g);
+    else hipLaunchKernelGGL((gemm_kernel<WM, WN, false, false, DEPTH>), grid, dim3(NT), 0, s, g);
+}
+
+// a 64-wide instantiation: RING_DEPTH tiles in flight, or one
+template <int WM, int WN>
+void launch_small(const GemmDev &g, bool akm, bool bkm, dim3 grid, bool ring, hipStream_t s)
+{
+    if (ring) launch<WM, WN, RING_DEPTH>(g, akm, bkm, grid, s);
+    else launch<WM, WN, 1>(g, akm, bkm, grid, s);
 }
 
 inline int vec_ok(const GemmOperand &o) { return (o.ld % 4 == 0) && ((reinterpret_cast<uintptr_t>(o.p) & 15) == 0); }
+
+// fetch_plain's conditions; t = the operand's M or N extent
+inline bool plain_operand(const GemmOperand &o, int t, int K)
+{
+    if (!vec_ok(o) || o.row_ids2 || (o.kmajor && (o.row_scale || o.row_ids))) return false;
+    return (o.kmajor ? t : K) % 4 == 0;
+}
 
 }  // namespace
 
@@ -290,9 +429,12 @@ void splitk_reduce_f32(const float *slab, int split, int M, int N, float *C, lon
     DLCO_HIP(hipGetLastError());
 }
 
+int gemm_ring_depth() { return RING_DEPTH; }
+
 void gemm_f32(const GemmArgs &a, hipStream_t s)
 {
     if (a.M <= 0 || a.N <= 0) return;
+    DLCO_CHECK(a.depth == 0 || a.depth == 1, -2, "gemm_f32: depth is 0 (the library's choice) or 1");
     DLCO_CHECK(a.A.p && a.B.p && a.C, -2, "gemm_f32: null operand");
     DLCO_CHECK(!(a.upper_only && (a.M != a.N || a.split_k > 1)), -2, "gemm_f32: upper_only needs M==N, split_k==1");
     GemmDev g;
@@ -329,18 +471,22 @@ void gemm_f32(const GemmArgs &a, hipStream_t s)
         if (!small_m && n_wg(small_m, small_n) < 256) small_m = true;
         if (!small_n && n_wg(small_m, small_n) < 256) small_n = true;
     }
+    // K tiles in flight (gemm_kernel): the ring for 64-wide tiles of plain operands, which is every small product of a
+    // training step; one tile, the schedule and loader of before, for everything else and on request
+    const bool ring = a.depth != 1 && plain_operand(a.A, a.M, a.K) && plain_operand(a.B, a.N, a.K);
+    if (a.depth_used) *a.depth_used = ring && (small_m || small_n) ? RING_DEPTH : 1;
     if (small_m && small_n) {
         dim3 grid((a.N + 63) / 64, (a.M + 63) / 64, split);
-        launch<1, 1>(g, a.A.kmajor, a.B.kmajor, grid, s);
+        launch_small<1, 1>(g, a.A.kmajor, a.B.kmajor, grid, ring, s);
     } else if (small_m) {
         dim3 grid((a.N + 127) / 128, (a.M + 63) / 64, split);
-        launch<1, 2>(g, a.A.kmajor, a.B.kmajor, grid, s);
+        launch_small<1, 2>(g, a.A.kmajor, a.B.kmajor, grid, ring, s);
     } else if (small_n) {
         dim3 grid((a.N + 63) / 64, (a.M + 127) / 128, split);
-        launch<2, 1>(g, a.A.kmajor, a.B.kmajor, grid, s);
+        launch_small<2, 1>(g, a.A.kmajor, a.B.kmajor, grid, ring, s);
     } else {
         dim3 grid((a.N + 127) / 128, (a.M + 127) / 128, split);
-        launch<2, 2>(g, a.A.kmajor, a.B.kmajor, grid, s);
+        launch<2, 2, 1>(g, a.A.kmajor, a.B.kmajor, grid, s);              // 128 x 128 tiles: one tile in flight
     }
     DLCO_HIP(hipGetLastError());
     if (split > 1 && !a.B2)
