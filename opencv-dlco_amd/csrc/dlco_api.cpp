@@ -267,11 +267,16 @@ void project_many(dlco_ctx *c, const int32_t *ids_dev, int row0, int n, const fl
     const RowRef rr = rows_of(c, ids_dev, row0, n);
     // fused project + square + column sum, the rows of D streamed once and no r x n buffer (W up to 384 rows: four
     // passes of 96; taller W - the start-up transient - takes the GEMM path below)
-    if (r <= 384 && c->F % 64 == 0) {
+    if (r <= 384) {
         for (auto &pl : c->pplane) pl.alloc(project_rows_plane_bytes(c->F));
-        if (project_rows_sqdist(Wd, c->F, r, c->dists, c->F, c->F, rr.a, rr.b, row0, n, out_dev, c->pplane[0].p, c->pplane[1].p,
-                                c->pplane[2].p, c->cfg.grad_bf16 != 0, c->stream))
-            return;
+        ProjectRowsArgs a;
+        a.W = Wd; a.ldw = c->F; a.r = r;
+        a.D = c->dists; a.ldd = c->F; a.F = c->F;
+        a.ids = rr.a; a.ids2 = rr.b; a.row0 = row0; a.nrows = n;
+        a.planes.hi = c->pplane[0].p; a.planes.lo = c->pplane[1].p; a.planes.lo2 = c->pplane[2].p;
+        a.bf16 = c->cfg.grad_bf16 != 0;
+        a.dist = out_dev;
+        if (project_rows_sqdist(a, c->stream)) return;
     }
     c->vproj.alloc((size_t)r * VCHUNK);
     for (int c0 = 0; c0 < n; c0 += VCHUNK) {
@@ -297,7 +302,7 @@ void project_few(dlco_ctx *c, const int32_t *ids_dev, int n, const float *Wd, in
     if (n <= 0) return;
     if (r <= 0) { fill_f32(out_dev, 0.f, (size_t)n, c->stream); return; }
     const int rp = std::max(r, r_ext);
-    if (c->cfg.grad_bf16 && rp <= 96 && c->F % 64 == 0) {
+    if (c->cfg.grad_bf16 && rp <= 96) {
         // BASELINE configs[4] variant: the batch projection on the bf16 matrix cores too (operands rounded to bf16 once,
         // fp32 accumulation), K split over enough slices to fill the chip, slices summed in order
         const int blocks = (n + 127) / 128;
@@ -309,8 +314,14 @@ void project_few(dlco_ctx *c, const int32_t *ids_dev, int n, const float *Wd, in
         for (auto &pl : c->pplane) pl.alloc(project_rows_plane_bytes(c->F));
         const RowRef rr = rows_of(c, ids_dev, 0, n);
         c->prof.begin(PROF_PROJECT);
-        const bool ok = project_rows_slab(Wd, c->F, rp, c->dists, c->F, c->F, rr.a, rr.b, n, ks, c->proj_slab.p, n, c->pplane[0].p,
-                                          c->pplane[1].p, c->pplane[2].p, true, c->stream);
+        ProjectRowsArgs a;
+        a.W = Wd; a.ldw = c->F; a.r = rp;
+        a.D = c->dists; a.ldd = c->F; a.F = c->F;
+        a.ids = rr.a; a.ids2 = rr.b; a.nrows = n;
+        a.planes.hi = c->pplane[0].p; a.planes.lo = c->pplane[1].p; a.planes.lo2 = c->pplane[2].p;
+        a.bf16 = true;
+        a.slab = c->proj_slab.p; a.ldn = n; a.ksplit = ks;
+        const bool ok = project_rows_slab(a, c->stream);
         if (ok) {
             if (ks > 2) sqdist_from_proj(c->proj_slab.p, ks, r, n, n, out_dev, c->stream, rp, reduced);
             else { sqdist_from_proj(c->proj_slab.p, ks, r, n, n, out_dev, c->stream); reduced = nullptr; }   // (never with F >= 256)
@@ -324,7 +335,7 @@ void project_few(dlco_ctx *c, const int32_t *ids_dev, int n, const float *Wd, in
     const int bm = rp <= 128 ? 64 : 128;     // (a 96-row block: two 64-row tiles or one of 128 measured the same, 25 us;
     const int bn = (n <= 64 || bm == 64) ? 64 : 128;                                                         //  64-column tiles as well: 19 us)
     const long tiles = (long)((rp + bm - 1) / bm) * ((n + bn - 1) / bn);
-    const int split = split_k_slices(tiles, 512, c->F, 128);
+    const int split = split_k_slices(tiles, 512, c->F, 128, LONG_MAX);   // (the slab below is sized by it)
     const size_t need = (size_t)(split + 1) * rp * n;
     if (need > c->proj_slab_floats) { sync(c); c->proj_slab.alloc(need); c->proj_slab_floats = need; }
     float *proj = c->proj_slab.p + (size_t)split * rp * n;      // reduced [rp][n] projection behind the slabs
@@ -350,15 +361,22 @@ void grad_syrk(dlco_ctx *c, const int32_t *ids, const float *w, const int *k_dev
 {
     const int kpad = (kmax + 31) & ~31;                 // the lists are zero padded up to here
     const RowRef rr = rows_of(c, ids, 0, kpad);
-    // fused, symmetric, branch-free kernel when the shape allows it (F a multiple of 128)
+    // fused, symmetric, branch-free kernel.  dlco_ctx_create pads every width (and a rank's column slab) to whole 128-column
+    // tiles, so what still reaches the GEMM below is a caller's device pointer that is not 16-byte aligned
     if (c->F % 128 == 0 && (reinterpret_cast<uintptr_t>(c->dists) & 15) == 0 &&
         (!c->shard || (c->comm.c0 % 128 == 0 && c->comm.cw % 128 == 0))) {
         c->prof.begin(PROF_GRAD_SYRK);
         const size_t pbytes = syrk_planes_bytes(kpad, c->F);
         if (pbytes > c->syrk_planes.n) { sync(c); c->syrk_planes.alloc(pbytes); }
-        const bool done = syrk_rda_f32(c->dists, c->F, rr.a, rr.b, w, k_dev, kpad, c->F, alpha, beta, dst, c->F, c->stream,
-                                       c->shard ? c->comm.c0 : 0, c->shard ? c->comm.cw : 0, c->cfg.grad_bf16 != 0, packed,
-                                       c->syrk_planes.p, coeff_job);
+        SyrkArgs a;
+        a.D = c->dists; a.ldd = c->F; a.ids = rr.a; a.ids2 = rr.b;
+        a.w = w; a.k_dev = k_dev; a.kmax = kpad; a.F = c->F;
+        a.alpha = alpha; a.beta = beta; a.C = dst; a.ldc = c->F;
+        if (c->shard) { a.slab_col0 = c->comm.c0; a.slab_cols = c->comm.cw; }
+        a.bf16 = c->cfg.grad_bf16 != 0; a.packed = packed;
+        a.planes = c->syrk_planes.p;
+        if (coeff_job) a.coeff_job = *coeff_job;
+        const bool done = syrk_rda_f32(a, c->stream);
         c->prof.end(PROF_GRAD_SYRK);
         DLCO_CHECK(done, DLCO_ERR_INVALID, "grad_syrk: fused kernel rejected an eligible shape");
         return;
@@ -435,7 +453,7 @@ void step_grad(dlco_ctx *c)
     const int B = c->B, Bl = c->Bl, world = c->cfg.world;
     gather_dists(c, &c->pd_cur, &c->nd_cur);
     viol_counts_active_rows(c->pd_cur, c->nd_cur, B, c->rho.p, c->kappa.p, c->pos_rows.p, c->neg_rows.p, c->lo, c->lo + Bl,
-                            c->act_ids.p, c->act_w.p, c->k_active.p, c->stream, c->act_slot.p);
+                            c->act_ids.p, c->act_w.p, c->k_active.p, c->act_slot.p, c->stream);
     float alpha, beta;
     rda_coeffs(c, &alpha, &beta);
     // (the coefficient fragments of the tracker's rank-update first term ride in the gradient's row-split launch)
@@ -509,7 +527,7 @@ void step_sharded(dlco_ctx *c)
     const int B = c->B;
     gather_dists(c, &c->pd_cur, &c->nd_cur);
     viol_counts_active_rows(c->pd_cur, c->nd_cur, B, c->rho.p, c->kappa.p, c->pos_rows.p, c->neg_rows.p, 0, B, c->act_ids.p,
-                            c->act_w.p, c->k_active.p, c->stream);
+                            c->act_w.p, c->k_active.p, nullptr, c->stream);
     float alpha, beta;
     rda_coeffs(c, &alpha, &beta);
     grad_syrk(c, c->act_ids.p, c->act_w.p, c->k_active.p, 2 * B, alpha, beta, c->dfavg.p);
@@ -663,7 +681,7 @@ int dlco_ctx_create(dlco_ctx **out, const dlco_cfg *cfg)
                 const int cnt = std::min(want, k);
                 if (cnt <= 0) return 0;
                 const RowRef rr = rows_of(c, c->act_ids.p + (k - cnt), 0, cnt);
-                scale_rows(dst, c->F, c->dists, c->F, nullptr, rr.a, cnt, c->F, c->stream, rr.b);
+                scale_rows(dst, c->F, c->dists, c->F, nullptr, rr.a, rr.b, cnt, c->F, c->stream);
                 return cnt;
             });
         }
@@ -826,7 +844,7 @@ int dlco_get_rows(dlco_ctx *c, int32_t row0, int32_t n, float *out_host)
         if (c->pair_mode) {                                // materialise the differences of the asked rows
             DevBuf<float> tmp;
             tmp.alloc((size_t)std::max(n, 1) * c->F);
-            scale_rows(tmp.p, c->F, c->dists, c->F, nullptr, c->pair_a.p + row0, n, c->F, c->stream, c->pair_b.p + row0);
+            scale_rows(tmp.p, c->F, c->dists, c->F, nullptr, c->pair_a.p + row0, c->pair_b.p + row0, n, c->F, c->stream);
             d2h_rows(c, out_host, tmp.p, (size_t)n);
             return;
         }
@@ -1224,17 +1242,27 @@ int dlco_sym_product(dlco_ctx *c, const float *X_host, int32_t rows, const float
             Gp.alloc(syrk_packed_floats(F));
             syrk_mirror_upper(G.p, F, F, c->stream);              // diagonal tiles are stored whole: take their lower half from the upper
             syrk_pack_upper(G.p, F, F, Gp.p, c->stream);
-            ok = skinny_product_sym(X.p, F, rows, Gp.p, F, 1.0f, out.p, F, nullptr, 0.f, nullptr, 0.f, hi.p, lo.p, slab.p, c->stream,
-                                    mode == 4 ? lo2.p : nullptr);
+            SkinnyArgs a;
+            a.X = X.p; a.ldx = F; a.M = rows;
+            a.G = Gp.p; a.N = F; a.K = F;
+            a.C = out.p; a.ldc = F;
+            a.planes.hi = hi.p; a.planes.lo = lo.p; a.planes.lo2 = mode == 4 ? lo2.p : nullptr;
+            a.slab = slab.p;
+            ok = skinny_product_sym(a, c->stream);
             sync(c);
         } else if (mode == 1 || mode == 2) {
             DevBuf<char> hi, lo, lo2;
             hi.alloc(bf16x2_plane_bytes(rows, F)); lo.alloc(bf16x2_plane_bytes(rows, F));
             if (mode == 2) lo2.alloc(bf16x2_plane_bytes(rows, F));
             DevBuf<float> slab;
-            slab.alloc(bf16x2_slab_floats(rows, F));
-            ok = skinny_product_bf16x2(X.p, F, rows, G.p, F, F, F, 1.0f, out.p, F, nullptr, 0.f, nullptr, 0.f, hi.p, lo.p, slab.p,
-                                       c->stream, 0, mode == 2 ? lo2.p : nullptr);
+            slab.alloc(bf16x2_slab_floats(rows, F, 0));
+            SkinnyArgs a;
+            a.X = X.p; a.ldx = F; a.M = rows;
+            a.G = G.p; a.ldg = F; a.N = F; a.K = F;
+            a.C = out.p; a.ldc = F;
+            a.planes.hi = hi.p; a.planes.lo = lo.p; a.planes.lo2 = mode == 2 ? lo2.p : nullptr;
+            a.slab = slab.p;
+            ok = skinny_product_bf16x2(a, c->stream);
             sync(c);
         } else {                                                 // the generic fp32 GEMM, K slices summed in order
             GemmArgs g;
@@ -1244,7 +1272,7 @@ int dlco_sym_product(dlco_ctx *c, const float *X_host, int32_t rows, const float
             g.C = out.p; g.ldc = F;
             const int bm = rows <= 64 ? 64 : 128;                // K slices as the tracker's products choose them
             const long tiles = (long)((rows + bm - 1) / bm) * ((F + 127) / 128);
-            g.split_k = split_k_slices(tiles, 1024, F, 256);
+            g.split_k = split_k_slices(tiles, 1024, F, 256, LONG_MAX);
             DevBuf<float> slab;
             slab.alloc(gemm_slab_floats(rows, F, g.split_k));
             g.slab = slab.p;

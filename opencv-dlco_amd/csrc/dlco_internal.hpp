@@ -216,28 +216,66 @@ void gemm_f32(const GemmArgs &a, hipStream_t s);
 // K tiles gemm_f32 keeps in flight at depth 0 where it takes 64-wide tiles of plain operands (elsewhere: 1)
 int gemm_ring_depth();
 // Same product on the bf16 matrix cores with split operands (x = hi + lo, three MFMAs per term,
-// fp32 accumulation; ~1e-5 relative error): kernels_bf16x2.hip.  plane_hi/lo are workspaces of
+// fp32 accumulation; ~1e-5 relative error): kernels_bf16x2.hip.  The planes are workspaces of
 // bf16x2_plane_bytes(M, K) bytes each.  Returns false for unsupported shapes (the caller then takes gemm_f32).
 size_t bf16x2_plane_bytes(int M, int K);
-size_t bf16x2_slab_floats(int M, int N, int ksplit = 0);
+size_t bf16x2_slab_floats(int M, int N, int ksplit);     // ksplit as in SkinnyArgs (0: the default four slices)
 // fragment-ordered bf16 planes of X [M][K] (M <= 160): hi, lo (and lo2 when given); layout: split_bf16_dev.hpp
 void split_planes_bf16(const float *X, long ldx, int M, int K, void *hi, void *lo, void *lo2, hipStream_t s);
-// plane_lo2 != nullptr selects the three-way split (x = hi + mid + lo, six MFMAs per term): fp32-level accuracy.
-// ksplit: number of K slices (grid y, default 4); K must be a multiple of 128 * ksplit.  A column slab of G
-// (N < K) takes ksplit = 4 * K / N so that the launch still fills the chip.
-bool skinny_product_bf16x2(const float *X, long ldx, int M, const float *G, long ldg, int N, int K, float alpha, float *C,
-                           long ldc, const float *E1, float b1, const float *E2, float b2, void *plane_hi, void *plane_lo,
-                           float *slab, hipStream_t s, int ksplit = 0, void *plane_lo2 = nullptr, bool g_tiled = false);
+// The plane workspaces of a split operand.  lo2 != nullptr selects the three-way split (x = hi + mid + lo, six MFMAs
+// per term): fp32-level accuracy.
+struct SplitPlanes {
+    void *hi = nullptr, *lo = nullptr, *lo2 = nullptr;
+};
+// C[M][N] = alpha * X[M][K] * G + b1*E1 + b2*E2 (E1/E2 share C's ld), for skinny_product_bf16x2 and skinny_product_sym
+struct SkinnyArgs {
+    const float *X = nullptr;
+    long ldx = 0;
+    int M = 0;
+    const float *G = nullptr;           // bf16x2: [K][ldg], N of its columns; sym: the packed upper tiles (ldg unused)
+    long ldg = 0;
+    int N = 0, K = 0;                   // sym: N == K == F
+    float alpha = 1.0f;
+    float *C = nullptr;
+    long ldc = 0;
+    const float *E1 = nullptr;
+    float b1 = 0.0f;
+    const float *E2 = nullptr;
+    float b2 = 0.0f;
+    SplitPlanes planes;                 // workspaces of bf16x2_plane_bytes(M, K) bytes each for the planes of X
+    float *slab = nullptr;              // bf16x2: >= bf16x2_slab_floats(M, N, ksplit) floats; sym: >= 4*M*F
+    int ksplit = 0;                     // bf16x2: number of K slices (grid y, 0 = the default 4); K must be a multiple of 128 * ksplit.
+                                        // A column slab of G (N < K) takes ksplit = 4 * K / N so that the launch still fills the chip.
+    // sym only.  planes_ready: planes.hi / lo already hold the two-way planes of X (skip the split); emit_planes: the reduction
+    // also writes the two-way planes of the RESULT into planes.hi / lo (the next product of a Chebyshev chain takes it as X)
+    bool planes_ready = false;
+    bool emit_planes = false;
+};
+bool skinny_product_bf16x2(const SkinnyArgs &a, hipStream_t s);
 // P1 + P2 for many rows without the r x N projection (kernels_project.hip): dist[n] = |W x_n|^2, x_n = row ids[n] (or
 // row0 + n) of D, minus row ids2[n] in pair mode.  Three-way split-bf16 MFMA (fp32-level accuracy) or, with bf16 = true,
 // operands rounded to bf16 once (BASELINE configs[4]).  planes: workspaces of project_rows_plane_bytes(F) bytes each.
 size_t project_rows_plane_bytes(int K);
-bool project_rows_sqdist(const float *W, long ldw, int r, const float *D, long ldd, int F, const int32_t *ids, const int32_t *ids2,
-                         long row0, int nrows, float *dist, void *plane_hi, void *plane_lo, void *plane_lo2, bool bf16, hipStream_t s);
-// raw partial projections of a few rows, K split over ksplit slices: slab [ksplit][r][ldn] (r <= 96)
-bool project_rows_slab(const float *W, long ldw, int r, const float *D, long ldd, int F, const int32_t *ids, const int32_t *ids2,
-                       int nrows, int ksplit, float *slab, long ldn, void *plane_hi, void *plane_lo, void *plane_lo2, bool bf16,
-                       hipStream_t s);
+struct ProjectRowsArgs {
+    const float *W = nullptr;           // [r][ldw]
+    long ldw = 0;
+    int r = 0;
+    const float *D = nullptr;
+    long ldd = 0;
+    int F = 0;
+    const int32_t *ids = nullptr, *ids2 = nullptr;
+    long row0 = 0;                      // sqdist form without ids: the rows row0 .. row0 + nrows of D
+    int nrows = 0;
+    SplitPlanes planes;                 // all three are used (bf16: hi and lo only)
+    bool bf16 = false;
+    float *dist = nullptr;              // project_rows_sqdist: out [nrows]
+    float *slab = nullptr;              // project_rows_slab: out [ksplit][r][ldn]
+    long ldn = 0;
+    int ksplit = 1;
+};
+bool project_rows_sqdist(const ProjectRowsArgs &a, hipStream_t s);
+// raw partial projections of a few rows (ids required), K split over ksplit slices: slab [ksplit][r][ldn] (r <= 96)
+bool project_rows_slab(const ProjectRowsArgs &a, hipStream_t s);
 // The coefficient fragments of the rank-update first filter term (kernels_rankupd.hip), as a job that rides in the
 // gradient's row-split launch (its extra column of blocks): frag = nullptr means no job.
 struct RankCoeffJob {
@@ -247,6 +285,21 @@ struct RankCoeffJob {
     const float *wscale = nullptr;   // scale row i of the block went into W with
     const int32_t *slot = nullptr;   // slot[k]: column of proj of active row k
     void *frag = nullptr;            // out: rank_coeff_bytes(m, kmax) bytes
+};
+// What the trainer knows about the matrix of the tracker's NEXT update(): G = beta * G_prev + alpha * X_a^T diag(w) X_a, G_prev
+// the matrix of the last update(), X_a the active rows of the step (kernels_rankupd.hip).
+struct RankUpdate {
+    const float *proj = nullptr;     // [rows][ldp]: projections of the batch slots on the rows of W as the last update() emitted them (guard rows included)
+    long ldp = 0;
+    int rows = 0;
+    const int32_t *slot = nullptr;   // slot[k]: column of proj that belongs to active row k
+    const float *w = nullptr;        // weights of the active rows
+    const int *k_dev = nullptr;      // their count (device)
+    int kmax = 0;                    // capacity of the lists (multiple of 32, zero padded)
+    const void *planes = nullptr;    // syrk_split_rows_kernel's planes of the active rows
+    float alpha = 0.f, beta = 1.f;
+    int planes_mode = 3;             // syrk_planes_mode(): 3 = three-way split planes, 1 = bf16-once planes
+    bool coeff_ready = false;        // the coefficient fragments were written by the gradient's row split (rank_coeff_job)
 };
 // Fused gradient SYRK + dual average (kernels_syrk.hip): C = beta*C + alpha * sum_k w_k x_k x_k^T over the
 // rows ids[0 .. *k_dev) of D, upper tiles computed and mirrored.  ids/w hold kmax entries (multiple of 32,
@@ -259,40 +312,59 @@ struct RankCoeffJob {
 void syrk_mirror_upper(float *C, long ldc, int F, hipStream_t s);
 // packed = true: C holds the packed upper tiles (syrk_packed_floats(F) floats, ldc ignored): tile (bi, bj), bi <= bj, is a
 // contiguous row-major 128 x 128 block at tile index bi*nt - bi*(bi-1)/2 + (bj - bi); no mirrored store.
-// planes_ws: >= syrk_planes_bytes(kmax, F) bytes of device memory for the split (or bf16-rounded) row planes of the launch;
-// nullptr: a per-device workspace inside the library (single-stream callers only).
+// planes: >= syrk_planes_bytes(kmax, F) bytes of device memory for the split (or bf16-rounded) row planes of the launch,
+// the caller's own (launches of two contexts on two streams must not share planes).
 size_t syrk_planes_bytes(int kmax, int F);
-bool syrk_rda_f32(const float *D, long ldd, const int32_t *ids, const int32_t *ids2, const float *w, const int *k_dev,
-                  int kmax, int F, float alpha, float beta, float *C, long ldc, hipStream_t s, int slab_col0 = 0,
-                  int slab_cols = 0, bool bf16 = false, bool packed = false, void *planes_ws = nullptr,
-                  const RankCoeffJob *coeff_job = nullptr);
-// which planes syrk_rda_f32(bf16) writes into planes_ws: rank_first_term() reads operand 1 of them
+struct SyrkArgs {
+    const float *D = nullptr;
+    long ldd = 0;
+    const int32_t *ids = nullptr, *ids2 = nullptr;
+    const float *w = nullptr;
+    const int *k_dev = nullptr;
+    int kmax = 0;
+    int F = 0;
+    float alpha = 1.0f, beta = 0.0f;
+    float *C = nullptr;
+    long ldc = 0;
+    int slab_col0 = 0, slab_cols = 0;
+    bool bf16 = false;                  // operands rounded to bf16 once (cfg.grad_bf16)
+    bool packed = false;
+    void *planes = nullptr;             // required
+    RankCoeffJob coeff_job;             // rides in the row split of the default arithmetic (frag = nullptr: no job)
+};
+bool syrk_rda_f32(const SyrkArgs &a, hipStream_t s);
+// which planes syrk_rda_f32 writes into SyrkArgs::planes: rank_first_term() reads operand 1 of them
 int syrk_planes_mode(bool bf16);     // 3: three-way split planes (default arithmetic), 1: bf16-once planes (cfg.grad_bf16), 0: no planes (DLCO_SYRK_FP32)
 // The first Chebyshev term of a step's filter from the step's own rank update, without a pass over the matrix
-// (kernels_rankupd.hip): out = ay*Y + aq*Q + ac * C_w X_a, C_w[i][k] = w[k] * proj[row(i)][slot[k]] / wscale[i] with
-// row(i) = nw-1-i for i < nw (W's ascending order), i for the guard rows behind; X_a = operand 1 of `planes`; also emits
-// the two-way planes of `out` (split_x_kernel's order) when plane_hi/lo are given.  coeff_ws: rank_coeff_bytes(m, kmax).
+// (kernels_rankupd.hip): out = ay*Y + aq*Q + ac * C_w X_a, C_w[i][k] = ru.w[k] * ru.proj[row(i)][ru.slot[k]] / wscale[i] with
+// row(i) = nw-1-i for i < nw (W's ascending order), i for the guard rows behind; X_a = operand 1 of ru.planes.
+// The block side of that term:
 size_t rank_coeff_bytes(int m, int kmax);
-bool rank_first_term(const float *Y, const float *Q, long ld, int m, int F, float ay, float aq, float ac, float *out,
-                     const float *proj, long ldp, int nw, const float *wscale, const int32_t *slot, const float *w,
-                     const int *k_dev, int kmax, const void *planes, void *coeff_ws, void *plane_hi, void *plane_lo, hipStream_t s,
-                     bool coeff_ready = false, int planes_mode = 3);   // coeff_ws already holds the fragments (they rode in the gradient's row split)
+struct RankTermBlock {
+    const float *Y = nullptr, *Q = nullptr;   // [m][ld]
+    long ld = 0;
+    int m = 0, F = 0;
+    float ay = 0.f, aq = 0.f, ac = 0.f;
+    float *out = nullptr;               // [m][ld]
+    int nw = 0;                         // Ritz rows among the m
+    const float *wscale = nullptr;      // scale row i of the block went into W with
+    void *coeff_ws = nullptr;           // rank_coeff_bytes(m, ru.kmax) bytes; with ru.coeff_ready it already holds the fragments
+    SplitPlanes out_planes;             // hi / lo given: also emits the two-way planes of `out` (split_x_kernel's order)
+};
+// (of ru, the lists, planes, planes_mode and coeff_ready are read; alpha / beta have gone into ay and ac)
+bool rank_first_term(const RankTermBlock &b, const RankUpdate &ru, hipStream_t s);
 size_t syrk_packed_floats(int F);
 void syrk_pack_upper(const float *C, long ldc, int F, float *packed, hipStream_t s);      // upper tiles of a full matrix -> packed
 void syrk_unpack_upper(const float *packed, int F, float *C, long ldc, hipStream_t s);    // packed -> full symmetric matrix
 // out[M][F] = alpha * X[M][F] * G + b1*E1 + b2*E2 for a symmetric G given as its packed upper tiles, every tile fetched
 // from HBM once (kernels_bf16x2.hip, skinny_sym_kernel).  F == 8192 only (64 x 64 tiles on 8 XCDs x 32 CUs); M <= 160
-// (two-way split) / 96 (three-way, plane_lo2 != nullptr).  slab: >= 4*M*F floats.  Returns false for other shapes.
-bool skinny_product_sym(const float *X, long ldx, int M, const float *Gpacked, int F, float alpha, float *C, long ldc,
-                        const float *E1, float b1, const float *E2, float b2, void *plane_hi, void *plane_lo, float *slab,
-                        hipStream_t s, void *plane_lo2 = nullptr, bool planes_ready = false, bool emit_planes = false);
-// planes_ready: plane_hi / plane_lo already hold the two-way planes of X (skip the split); emit_planes: the reduction also
-// writes the two-way planes of the RESULT into plane_hi / plane_lo (the next product of a Chebyshev chain takes it as X)
+// (two-way split) / 96 (three-way, planes.lo2 != nullptr).  slab: >= 4*M*F floats.  Returns false for other shapes.
+bool skinny_product_sym(const SkinnyArgs &a, hipStream_t s);
 size_t gemm_slab_floats(int M, int N, int split_k);
 // K slices (GemmArgs::split_k) for a product whose M x N tile grid alone would leave the chip idle: enough that
 // tiles * slices reaches `target` workgroups, no slice shorter than kmin, no more slices than the slab holds
-// (slab_cap = slab floats / (M * N)); never fewer than one.
-inline int split_k_slices(long tiles, long target, long K, long kmin, long slab_cap = LONG_MAX)
+// (slab_cap = slab floats / (M * N), LONG_MAX where the caller sizes the slab by the result); never fewer than one.
+inline int split_k_slices(long tiles, long target, long K, long kmin, long slab_cap)
 {
     const long split = std::min(std::min((target + tiles - 1) / tiles, K / kmin), slab_cap);
     return (int)std::max(1L, split);
@@ -309,10 +381,11 @@ void sqdist_from_proj(const float *proj, int split, int r, int n, long ld, float
 // rho/kappa + signed weights + compact active list for one batch
 //   pd, nd: [B] distances; out rho[B], kappa[B]; weights[2B] (rho_i for positives, -kappa_j for negatives)
 void viol_counts(const float *pd, const float *nd, int B, int32_t *rho, int32_t *kappa, hipStream_t s);
-// viol_counts + build_active_rows in one launch
+// viol_counts + build_active_rows in one launch; slots (may be null): slots[k] = position of active row k in the rank's
+// [pos | neg] slot list
 void viol_counts_active_rows(const float *pd, const float *nd, int B, int32_t *rho, int32_t *kappa, const int32_t *pos_rows,
-                             const int32_t *neg_rows, int slot_lo, int slot_hi, int32_t *ids, float *w, int *k_active, hipStream_t s,
-                             int32_t *slots = nullptr);   // slots[k]: position of active row k in the rank's [pos | neg] slot list
+                             const int32_t *neg_rows, int slot_lo, int slot_hi, int32_t *ids, float *w, int *k_active, int32_t *slots,
+                             hipStream_t s);
 // build the stacked weighted row list of the SYRK: ids[2B] = (pos rows, neg rows), w[2B] = (rho, -kappa);
 // rows with zero weight are dropped; *k_active receives the count. [lo,hi) selects the slots owned by a rank.
 void build_active_rows(const int32_t *pos_rows, const int32_t *neg_rows, const int32_t *rho, const int32_t *kappa,
@@ -325,15 +398,17 @@ void hinge_rows_batched(const float *pos, int n_pos, const float *neg, int n_neg
                         hipStream_t s);
 void sum_f32_to_f64_batched(const float *x, int n, long ldx, double *out, int count, hipStream_t s);
 void axpby_inplace(float *y, const float *x, float a, float b, size_t n, hipStream_t s);  // y = a*y + b*x
+// dst[i] = scale[i] * (src[src_rows[i]] - src[src_rows2[i]]); scale, src_rows and src_rows2 may each be null (1, i, no subtrahend)
 void scale_rows(float *dst, long ldd, const float *src, long lds, const float *scale, const int32_t *src_rows,
-                int rows, int cols, hipStream_t s, const int32_t *src_rows2 = nullptr);    // dst[i] = scale[i]*(src[src_rows[i]] - src[src_rows2[i]])
+                const int32_t *src_rows2, int rows, int cols, hipStream_t s);
 // out_a[i] = pa[ids ? ids[i] : base + i], out_b likewise: row ids -> (patch, patch) ids of the pair table
 // W[j][:] = sqrt(cscale * (theta[nw-1-j] - mu)) * Q[nw-1-j][:] for j < nw: the kept Ritz pairs in ascending
 // eigenvalue order, scaled like the reference's W = sqrt(e) * v^T (src/pj-learn.cpp:480-487)
 // m_ext > nw: the rows nw..m_ext-1 of Q (the guard rows) are copied unscaled behind the nw rows of W, and wscale[i]
 // receives the factor row i of Q went out with (1 for guards) - what the next step's rank update divides by
+// (m_ext = 0, wscale = nullptr: the nw rows only)
 void emit_w_rows(float *W, long ldw, const float *Q, long ldq, const float *theta, int nw, float mu, float cscale, int F,
-                 hipStream_t s, int m_ext = 0, float *wscale = nullptr);
+                 int m_ext, float *wscale, hipStream_t s);
 void translate_ids(const int32_t *ids, int base, int n, const int32_t *pa, const int32_t *pb, int32_t *out_a, int32_t *out_b,
                    hipStream_t s);
 void fill_f32(float *p, float v, size_t n, hipStream_t s);
@@ -366,11 +441,12 @@ void synth_rows(float *D, int N, int F, long ld, const float *U, int k, uint64_t
 // eigenvector j.  work: >= jacobi_work_floats(n) floats.  n <= 4096.
 // lam_cut: a pair of columns whose eigenvalue estimates are BOTH below it is still rotated but does not
 // keep the sweeps going (the tracker's guard vectors: only their span matters, and the caller checks the
-// residuals of the pairs it keeps); the default counts every pair.
+// residuals of the pairs it keeps); JACOBI_COUNT_ALL counts every pair.
 // *sweeps_out < 0: the multi-workgroup kernel (160 < n <= 2048) gave up at its bounded grid barrier (its workgroups were
 // not all resident at once); evals / V are then NOT written and the caller repeats the call with single_workgroup = true.
+constexpr float JACOBI_COUNT_ALL = -3.0e38f;
 void jacobi_eigh(const float *T, long ldt, int n, float *evals, float *V, long ldv, float *work, int *sweeps_out,
-                 hipStream_t s, float lam_cut = -3.0e38f, bool single_workgroup = false);
+                 float lam_cut, bool single_workgroup, hipStream_t s);
 size_t jacobi_work_floats(int n);
 // CholQR building block for panels of <= 160 rows: factors the panel's Gram matrix M = L L^T
 // (only its lower triangle is read) and returns Linv = L^-1 [n][ldl] (lower triangular, upper
@@ -389,13 +465,28 @@ struct ResidualEmit {
     float *wscale = nullptr;         // scale row i of the block went out with (1 for the rows behind the nw kept ones)
     bool guards = false;             // also write the rows with theta <= mu, unscaled and in place
 };
-void residual_norms_publish(const float *X, const float *Y, long ld, const float *theta, int m, int F, float *res, unsigned *ticket,
-                            const float *src, float *dst_host, int n, unsigned *flag_host, unsigned seq, hipStream_t s,
-                            const int *extra_dev = nullptr, int *extra_host = nullptr, const ResidualEmit *emit = nullptr,
-                            bool *emitted = nullptr);
+struct ResidualPublish {
+    const float *X = nullptr, *Y = nullptr;   // [m][ld]
+    long ld = 0;
+    const float *theta = nullptr;
+    int m = 0, F = 0;
+    float *res = nullptr;            // out [m]
+    unsigned *ticket = nullptr;      // device word, zero between launches: finds the workgroup that finishes last
+    const float *src = nullptr;      // the n device floats that workgroup copies ...
+    float *dst_host = nullptr;       // ... into pinned host memory
+    int n = 0;
+    unsigned *flag_host = nullptr;   // pinned: receives seq once the copy is visible
+    unsigned seq = 0;
+    const int *extra_dev = nullptr;  // optional: one device int copied along ...
+    int *extra_host = nullptr;       // ... to here
+    ResidualEmit emit;               // W = nullptr: no rows of W
+};
+// returns whether the launch writes emit's rows (false: W not given, or a pointer / stride the vector stores do not take)
+bool residual_norms_publish(const ResidualPublish &a, hipStream_t s);
 void residual_norms(const float *X, const float *Y, long ld, const float *theta, int m, int F, float *res,
                     hipStream_t s);
-void row_normalize(float *X, long ld, int m, int F, hipStream_t s, float min_norm = 0.f);
+// rows whose norm is below min_norm become zero rows (0: every row is scaled)
+void row_normalize(float *X, long ld, int m, int F, float min_norm, hipStream_t s);
 // y = H x style GEMV on a symmetric matrix (memory-bound), used by the spectral-bound estimator
 void symv(const float *H, long ld, int F, const float *x, float *y, hipStream_t s);
 

@@ -100,7 +100,7 @@ void EigTracker::seed_rows(const float *src, long ld, const int32_t *ids_dev, in
     wext_rows_ = 0;
     ru_offered_ = false;
     if (k <= 0) { m_ = 0; return; }
-    scale_rows(Q_, F_, src, ld, nullptr, ids_dev, k, F_, s_, ids2_dev);
+    scale_rows(Q_, F_, src, ld, nullptr, ids_dev, ids2_dev, k, F_, s_);
     m_ = k;
 }
 
@@ -150,6 +150,14 @@ void EigTracker::product(const float *X, int rows, const float *G, float alpha, 
         return;
     }
     st_.product_rows += rows;
+    // what the three split-bf16 forms below share; each adds its G, N and the fields only it has
+    SkinnyArgs a;
+    a.X = X; a.ldx = F_; a.M = rows; a.K = F_;
+    a.alpha = alpha; a.C = out; a.ldc = F_;
+    a.E1 = E1; a.b1 = b1; a.E2 = E2; a.b2 = b2;
+    a.planes.hi = plane_hi_.p; a.planes.lo = plane_lo_.p;
+    a.planes.lo2 = approx ? nullptr : plane_lo2_.p;             // exact products: the three-way split
+    a.slab = slab_.p;
     if (packed_) {
         // G = packed upper tiles: the symmetric kernel (every tile fetched once); two-way split for the filter, three-way
         // for the exact products (rows <= 96 there: the chunking above)
@@ -157,8 +165,9 @@ void EigTracker::product(const float *X, int rows, const float *G, float alpha, 
         // inside a filter chain the planes of X are those the previous product's reduction emitted
         const bool ready = approx && chain && chain->planes_of == X && chain->rows == rows;
         const bool emit = approx && chain && chain->next;
-        const bool ok = skinny_product_sym(X, F_, rows, G, F_, alpha, out, F_, E1, b1, E2, b2, plane_hi_.p, plane_lo_.p, slab_.p, s_,
-                                           approx ? nullptr : plane_lo2_.p, ready, emit);
+        a.G = G; a.N = F_;
+        a.planes_ready = ready; a.emit_planes = emit;
+        const bool ok = skinny_product_sym(a, s_);
         if (chain) { chain->planes_of = emit ? out : nullptr; chain->rows = rows; }   // (a product without `emit` has overwritten the planes with X's)
         if (prof_) prof_->end(PROF_EIG_PRODUCT);
         DLCO_CHECK(ok, -2, "eig tracker: the symmetric product rejected a shape of the packed layout");
@@ -174,8 +183,10 @@ void EigTracker::product(const float *X, int rows, const float *G, float alpha, 
         if (rows <= 128) {
             int ks = ks_;                                            // keep ~256 workgroups in flight
             while (ks < 4 * world && F_ % (128 * ks * 2) == 0 && bf16x2_slab_floats(rows, cw, ks * 2) <= slab_floats_) ks *= 2;
-            done = skinny_product_bf16x2(X, F_, rows, G + c0, F_, cw, F_, alpha, out + c0, F_, E1s, b1, E2s, b2, plane_hi_.p,
-                                         plane_lo_.p, slab_.p, s_, ks, approx ? nullptr : plane_lo2_.p);
+            a.G = G + c0; a.ldg = F_; a.N = cw;
+            a.C = out + c0; a.E1 = E1s; a.E2 = E2s;
+            a.ksplit = ks;
+            done = skinny_product_bf16x2(a, s_);
         }
         if (!done) {
             GemmArgs g;
@@ -198,8 +209,9 @@ void EigTracker::product(const float *X, int rows, const float *G, float alpha, 
     if (rows <= one_pass && F_ >= 256) {
         // filter products: two-way split (~1e-5); exact products (Rayleigh-Ritz): three-way split (~1e-7)
         if (prof_) prof_->begin(PROF_EIG_PRODUCT);
-        const bool ok = skinny_product_bf16x2(X, F_, rows, G, F_, F_, F_, alpha, out, F_, E1, b1, E2, b2, plane_hi_.p,
-                                              plane_lo_.p, slab_.p, s_, ks_, approx ? nullptr : plane_lo2_.p);
+        a.G = G; a.ldg = F_; a.N = F_;
+        a.ksplit = ks_;
+        const bool ok = skinny_product_bf16x2(a, s_);
         if (prof_) prof_->end(PROF_EIG_PRODUCT);
         if (ok) return;
     }
@@ -275,7 +287,7 @@ int EigTracker::orthonormalize(float *Z, int rows, float *scratch, const std::ve
     // filter left them.  With several panels the rows are normalised first: the Gram-Schmidt step between panels zeroes
     // what is left of a row after projection against a threshold that assumes unit rows.
     const bool one_panel = skip == 0 && rows <= CHOL_INV_MAX_N && (panel_ends.empty() || panel_ends[0] >= rows);
-    if (!one_panel) row_normalize(Z + (size_t)skip * F_, F_, rows - skip, F_, s_);
+    if (!one_panel) row_normalize(Z + (size_t)skip * F_, F_, rows - skip, F_, 0.f, s_);
     size_t pi = 0;
     // (the first `skip` rows are orthonormal as they are - locked Ritz vectors - and only serve as the span the panels
     // behind them are projected against)
@@ -289,7 +301,7 @@ int EigTracker::orthonormalize(float *Z, int rows, float *scratch, const std::ve
             for (int pass = 0; pass < 2; pass++) {
                 project_out(Wp, np, Z, p0);
                 // after the first projection, rows that lie (to fp32 accuracy) inside the span above are zeroed
-                row_normalize(Wp, F_, np, F_, s_, pass == 0 ? 2e-5f : 0.f);
+                row_normalize(Wp, F_, np, F_, pass == 0 ? 2e-5f : 0.f, s_);
             }
         }
         for (int pass = 0; pass < 2; pass++) {
@@ -320,9 +332,9 @@ int EigTracker::drop_dead_rows()
     DLCO_HIP(hipMemcpyAsync(srcrow_.p, live.data(), (size_t)k * sizeof(int32_t), hipMemcpyHostToDevice, s_));
     DLCO_HIP(hipStreamSynchronize(s_));
     float *Qn = pick({Q_, Y_});
-    scale_rows(Qn, F_, Q_, F_, nullptr, srcrow_.p, k, F_, s_);
+    scale_rows(Qn, F_, Q_, F_, nullptr, srcrow_.p, nullptr, k, F_, s_);
     float *Yn = pick({Q_, Y_, Qn});
-    scale_rows(Yn, F_, Y_, F_, nullptr, srcrow_.p, k, F_, s_);
+    scale_rows(Yn, F_, Y_, F_, nullptr, srcrow_.p, nullptr, k, F_, s_);
     Q_ = Qn; Y_ = Yn;
     for (int j = 0; j < k; j++) { h_theta_[j] = h_theta_[live[j]]; h_res_[j] = h_res_[live[j]]; }
     m_ = k;
@@ -339,7 +351,7 @@ void EigTracker::refresh_lower_bound(const float *G, int iters, float theta_top)
         for (int i = 0; i < live_; i++) v[i] = next_uniform();
         DLCO_HIP(hipMemcpyAsync(pv_.p, v.data(), F_ * sizeof(float), hipMemcpyHostToDevice, s_));
         DLCO_HIP(hipStreamSynchronize(s_));
-        row_normalize(pv_.p, F_, 1, F_, s_);
+        row_normalize(pv_.p, F_, 1, F_, 0.f, s_);
     }
     DLCO_HIP(hipMemcpyAsync(scale_.p, &kZero, sizeof(float), hipMemcpyHostToDevice, s_));   // theta = 0: plain norm
     auto run = [&](float shift, int n) -> float {
@@ -349,7 +361,7 @@ void EigTracker::refresh_lower_bound(const float *G, int iters, float theta_top)
             else symv(G, F_, F_, v, w, s_);
             if (shift != 0.f) axpby_inplace(w, v, 1.0f, shift, F_, s_);
             if (i == n - 1) residual_norms(v, w, F_, scale_.p, 1, F_, res_.p, s_);   // |w|
-            row_normalize(w, F_, 1, F_, s_);
+            row_normalize(w, F_, 1, F_, 0.f, s_);
             std::swap(v, w);
         }
         if (v != pv_.p) DLCO_HIP(hipMemcpyAsync(pv_.p, v, F_ * sizeof(float), hipMemcpyDeviceToDevice, s_));
@@ -507,9 +519,13 @@ float *EigTracker::filter_plain(const UpdateState &u)
         // (H - c0) Q / e0 = (beta / e0) Y - (alpha / e0) C_w X_a - (c0 / e0) Q, H = -G
         coeff_.alloc(rank_coeff_bytes(cap_ < 160 ? cap_ : 160, ru_.kmax));
         if (prof_) prof_->begin(PROF_RANK_UPDATE);
-        first_done = rank_first_term(Y_, Q_, F_, m_, F_, ru_.beta / e0, -c0 / e0, -ru_.alpha / e0, cur, ru_.proj, ru_.ldp,
-                                     u.ru_nw, wscale_.p, ru_.slot, ru_.w, ru_.k_dev, ru_.kmax, ru_.planes, coeff_.p,
-                                     chain.next ? plane_hi_.p : nullptr, plane_lo_.p, s_, ru_.coeff_ready, ru_.planes_mode);
+        RankTermBlock b;
+        b.Y = Y_; b.Q = Q_; b.ld = F_; b.m = m_; b.F = F_;
+        b.ay = ru_.beta / e0; b.aq = -c0 / e0; b.ac = -ru_.alpha / e0;
+        b.out = cur;
+        b.nw = u.ru_nw; b.wscale = wscale_.p; b.coeff_ws = coeff_.p;
+        b.out_planes.hi = chain.next ? plane_hi_.p : nullptr; b.out_planes.lo = plane_lo_.p;
+        first_done = rank_first_term(b, ru_, s_);
         if (prof_) prof_->end(PROF_RANK_UPDATE);
         if (first_done) {
             st_.rank_update_passes++;
@@ -565,7 +581,7 @@ void EigTracker::rayleigh_ritz(UpdateState &u, float *Qo)
     // (second attempt: only after the multi-workgroup Jacobi gave up at its grid barrier - T, Qo and Yb are untouched
     // by a failed attempt, the m x m problem is then solved again by the single-workgroup kernel)
     for (int attempt = 0;; attempt++) {
-        jacobi_eigh(Tm_.p, cap_, m_, evals_.p, Vm_.p, cap_, jwork_.p, sweeps_dev_, s_, lam_cut, attempt > 0);
+        jacobi_eigh(Tm_.p, cap_, m_, evals_.p, Vm_.p, cap_, jwork_.p, sweeps_dev_, lam_cut, attempt > 0, s_);
         if (prof_) prof_->end(PROF_JACOBI);
         rotate(Vm_.p, cap_, m_, m_, Qo, Qn, Yb, Yn);
         Q_ = Qn; Y_ = Yn;
@@ -578,10 +594,15 @@ void EigTracker::rayleigh_ritz(UpdateState &u, float *Qo)
         // (the residual kernel's last workgroup publishes: one launch)
         // (the kernel also writes this pass's rows of W, guard rows and scales included: if the pass is the update's last,
         // W is already where it belongs)
-        ResidualEmit em;
-        em.W = u.W; em.ldw = F_; em.mu = u.mu; em.cscale = u.cscale; em.wscale = wscale_.p; em.guards = emit_guards_;
-        residual_norms_publish(Q_, Y_, F_, evals_.p, m_, F_, res_.p, reinterpret_cast<unsigned *>(sweeps_dev_ + 4), ritz_block_.p, pin_,
-                               (int)blk, flag, seq, s_, extra_dev_, extra_host, &em, &u.w_emitted);
+        ResidualPublish rp;
+        rp.X = Q_; rp.Y = Y_; rp.ld = F_; rp.theta = evals_.p; rp.m = m_; rp.F = F_; rp.res = res_.p;
+        rp.ticket = reinterpret_cast<unsigned *>(sweeps_dev_ + 4);
+        rp.src = ritz_block_.p; rp.dst_host = pin_; rp.n = (int)blk;
+        rp.flag_host = flag; rp.seq = seq;
+        rp.extra_dev = extra_dev_; rp.extra_host = extra_host;
+        rp.emit.W = u.W; rp.emit.ldw = F_; rp.emit.mu = u.mu; rp.emit.cscale = u.cscale;
+        rp.emit.wscale = wscale_.p; rp.emit.guards = emit_guards_;
+        u.w_emitted = residual_norms_publish(rp, s_);
         const auto t0 = std::chrono::steady_clock::now();
         bool seen = false;
         for (long spins = 0;; spins++) {
@@ -652,7 +673,7 @@ double EigTracker::trim_and_emit(UpdateState &u)
         if (theta_dev_valid_) {
             // the Ritz values are still on the device in the order of the rows of Q: scale and reverse there
             const bool ext = emit_guards_ && y_ok_ && m_ > nw;
-            if (!u.w_emitted) emit_w_rows(u.W, F_, Q_, F_, evals_.p, nw, u.mu, u.cscale, F_, s_, ext ? m_ : 0, ext ? wscale_.p : nullptr);
+            if (!u.w_emitted) emit_w_rows(u.W, F_, Q_, F_, evals_.p, nw, u.mu, u.cscale, F_, ext ? m_ : 0, ext ? wscale_.p : nullptr, s_);
             if (ext) { wext_rows_ = m_; wext_nw_ = nw; }
         } else {
             h_sc_.resize(nw);
@@ -665,7 +686,7 @@ double EigTracker::trim_and_emit(UpdateState &u)
             DLCO_HIP(hipMemcpyAsync(scale_.p, h_sc_.data(), nw * sizeof(float), hipMemcpyHostToDevice, s_));
             DLCO_HIP(hipMemcpyAsync(srcrow_.p, h_sr_.data(), nw * sizeof(int32_t), hipMemcpyHostToDevice, s_));
             DLCO_HIP(hipStreamSynchronize(s_));
-            scale_rows(u.W, F_, Q_, F_, scale_.p, srcrow_.p, nw, F_, s_);
+            scale_rows(u.W, F_, Q_, F_, scale_.p, srcrow_.p, nullptr, nw, F_, s_);
         }
     }
     return tr;

@@ -31,22 +31,6 @@ struct EigStats {
     double rank_update_check = 0.0;        // DLCO_RANK_UPDATE_CHECK=1: largest |shortcut - product| / max|product| seen (developer aid)
 };
 
-// What the trainer knows about the matrix of the NEXT update(): G = beta * G_prev + alpha * X_a^T diag(w) X_a, G_prev the
-// matrix of the last update(), X_a the active rows of the step (kernels_rankupd.hip).
-struct RankUpdate {
-    const float *proj = nullptr;     // [rows][ldp]: projections of the batch slots on the rows of W as the last update() emitted them (guard rows included)
-    long ldp = 0;
-    int rows = 0;
-    const int32_t *slot = nullptr;   // slot[k]: column of proj that belongs to active row k
-    const float *w = nullptr;        // weights of the active rows
-    const int *k_dev = nullptr;      // their count (device)
-    int kmax = 0;                    // capacity of the lists (multiple of 32, zero padded)
-    const void *planes = nullptr;    // syrk_split_rows_kernel's planes of the active rows
-    float alpha = 0.f, beta = 1.f;
-    int planes_mode = 3;             // syrk_planes_mode(): 3 = three-way split planes, 1 = bf16-once planes
-    bool coeff_ready = false;        // the coefficient fragments were written by the gradient's row split (rank_coeff_job)
-};
-
 class EigTracker {
 public:
     // live_cols: the columns [live_cols, F) of every row of G are zero padding (dlco_api.cpp pads FeatDim to whole
@@ -84,7 +68,7 @@ public:
     // keeps the scale of every row: the step's own projection of its batch on these rows is what offer_rank_update() hands back
     void set_emit_guards(bool on) { emit_guards_ = on; }
     int ext_rows() const { return wext_rows_; }          // rows of W the last update() wrote, guard rows included (0: none)
-    // consumed by the next update() only; ignored when the block is not the one the projection was made with
+    // (RankUpdate: dlco_internal.hpp) consumed by the next update() only; ignored when the block is not the one the projection was made with
     void offer_rank_update(const RankUpdate &ru) { ru_ = ru; ru_offered_ = true; }
     // The part of the coefficient job the tracker knows (rows, scales, output buffer) for a row list of capacity kmax;
     // false when the block is not one the shortcut takes.  The caller adds proj / slot and lets the job ride in its gradient.

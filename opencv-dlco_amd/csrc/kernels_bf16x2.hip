@@ -66,7 +66,6 @@ struct Bf2Dev {
     const float *G;
     long ldg;
     float *slab;                  // [KS][M][N] raw partial sums
-    int tiled;                    // G is stored as contiguous 128 x 128 tiles, tile (I, J) at ((I * K/128) + J) * 16384 floats
 };
 
 template <int MT, int NS>
@@ -179,8 +178,7 @@ __global__ __launch_bounds__(T8) void skinny_bf16x2_kernel(Bf2Dev g)
 //     32-byte reads of 32 different rows (row stride 68 floats: conflict-free), A fragments whole
 //     1-KiB reads; they issue no global load at all.
 // One barrier per chunk.  Same MFMA schedule per K step and the same slab reduction as above; a column's
-// K order is plain ascending inside the slice.  Deterministic.  `tiled`: G stored as contiguous
-// 128 x 128 tiles (a chunk is then half a tile).
+// K order is plain ascending inside the slice.  Deterministic.
 
 template <int MT, int NS>
 __global__ __launch_bounds__(SB_T) void skinny_rows_kernel(Bf2Dev g)
@@ -219,16 +217,14 @@ __global__ __launch_bounds__(SB_T) void skinny_rows_kernel(Bf2Dev g)
         const int lt = tid - 512, grow = lt >> 4, gc4 = lt & 15;
         const __amdgpu_buffer_rsrc_t rsrc =
             __builtin_amdgcn_make_buffer_rsrc(const_cast<float *>(g.G), 0, (int)((long)g.K * g.ldg * (long)sizeof(float)), 0x00020000);
-        const long pitch = g.tiled ? 128 : g.ldg;
-        const long base = g.tiled ? ((long)bx * (g.K / 128) + kbeg / 128) * 16384 + (long)grow * 128 + 4 * gc4
-                                  : (long)(j0 + grow) * g.ldg + kbeg + 4 * gc4;
+        const long base = (long)(j0 + grow) * g.ldg + kbeg + 4 * gc4;
         const int voff = (int)(base * (long)sizeof(float));
-        const int row16 = (int)(16 * pitch * (long)sizeof(float));
+        const int row16 = (int)(16 * g.ldg * (long)sizeof(float));
         const PlaneRsrc rs = make_plane_rsrc<MT, NS>(g.xhi, g.xlo, g.xlo2, g.K);
         struct Stage { f32x4 gq[8]; bf16x8 aq[NA]; };
         Stage s0, s1;
         auto gload = [&](int c, Stage &st) {
-            const int soff = g.tiled ? ((c >> 1) * 16384 + (c & 1) * 64) * (int)sizeof(float) : c * SB_KC * (int)sizeof(float);
+            const int soff = c * SB_KC * (int)sizeof(float);
 #pragma unroll
             for (int u = 0; u < 8; u++) st.gq[u] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(rsrc, voff, soff + u * row16, 0));
             const int a0 = slice_bytes<MT>(st0 + 4 * c);
@@ -249,6 +245,7 @@ __global__ __launch_bounds__(SB_T) void skinny_rows_kernel(Bf2Dev g)
         gload(0, s0);
         gload(min(1, last), s1);
         gstore(0, s0);
+        __builtin_amdgcn_sched_barrier(0);                     // chunk 2 goes into s0's registers, not a third set hoisted above the copy
         gload(min(2, last), s0);
         __syncthreads();
         // iteration cc: copy chunk cc+1 (waiting in `set`) into image `buf`, request chunk cc+3 into the same registers
@@ -625,20 +622,22 @@ size_t bf16x2_plane_bytes(int M, int K) { return (size_t)((M + 31) / 32) * 32 * 
 size_t bf16x2_slab_floats(int M, int N, int ksplit) { return (size_t)(ksplit > 0 ? ksplit : KS) * M * N; }
 
 // Returns false when the shape is not supported (the caller then takes gemm_f32).
-bool skinny_product_bf16x2(const float *X, long ldx, int M, const float *G, long ldg, int N, int K, float alpha, float *C,
-                           long ldc, const float *E1, float b1, const float *E2, float b2, void *plane_hi, void *plane_lo,
-                           float *slab, hipStream_t s, int ksplit, void *plane_lo2, bool g_tiled)
+bool skinny_product_bf16x2(const SkinnyArgs &a, hipStream_t s)
 {
+    const int M = a.M, N = a.N, K = a.K;
+    const long ldg = a.ldg;
+    const float *G = a.G;
+    void *plane_lo2 = a.planes.lo2;
     const int mt = (M + 31) / 32;
-    const int ks = ksplit > 0 ? ksplit : KS;
+    const int ks = a.ksplit > 0 ? a.ksplit : KS;
     if (M < 1 || mt > 5 || N % 128 != 0 || K % (16 * ks * 2 * 4) != 0) return false;   // 4 steps per loop trip
-    if (ldx % 4 != 0 || (reinterpret_cast<uintptr_t>(X) & 15) != 0) return false;
-    split_planes_bf16(X, ldx, M, K, plane_hi, plane_lo, plane_lo2, s);
+    if (a.ldx % 4 != 0 || (reinterpret_cast<uintptr_t>(a.X) & 15) != 0) return false;
+    split_planes_bf16(a.X, a.ldx, M, K, a.planes.hi, a.planes.lo, plane_lo2, s);
     Bf2Dev g;
     g.M = M; g.N = N; g.K = K;
-    g.xhi = static_cast<const bf16x8 *>(plane_hi); g.xlo = static_cast<const bf16x8 *>(plane_lo);
+    g.xhi = static_cast<const bf16x8 *>(a.planes.hi); g.xlo = static_cast<const bf16x8 *>(a.planes.lo);
     g.xlo2 = static_cast<const bf16x8 *>(plane_lo2);
-    g.G = G; g.ldg = ldg; g.slab = slab; g.tiled = g_tiled ? 1 : 0;
+    g.G = G; g.ldg = ldg; g.slab = a.slab;
     const dim3 grid(N / 128, ks), block(T8);
     // whole symmetric matrix: stream its rows through LDS (skinny_rows_kernel)
     // (four row tiles with the three-way split do not fit the register budget of the split-role kernel)
@@ -647,46 +646,46 @@ bool skinny_product_bf16x2(const float *X, long ldx, int M, const float *G, long
         if (plane_lo2) dispatch_mt<4>(mt, [&](auto MT) { launch_rows<MT(), 3>(g, grid, s); });
         else dispatch_mt<5>(mt, [&](auto MT) { launch_rows<MT(), 2>(g, grid, s); });   // 160 rows: blocks of rank ~128 + guards in ONE pass over G
         DLCO_HIP(hipGetLastError());
-        splitk_reduce_f32(slab, ks, M, N, C, ldc, alpha, 0.f, E1, b1, E2, b2, s);
+        splitk_reduce_f32(a.slab, ks, M, N, a.C, a.ldc, a.alpha, 0.f, a.E1, a.b1, a.E2, a.b2, s);
         return true;
     }
-    if (g_tiled || mt > 4) return false;                       // only the row-streaming kernel reads the tiled layout / takes five row tiles
+    if (mt > 4) return false;                                  // only the row-streaming kernel takes five row tiles
     if (plane_lo2) dispatch_mt<4>(mt, [&](auto MT) { hipLaunchKernelGGL((skinny_bf16x2_kernel<MT(), 3>), grid, block, 0, s, g); });   // three-way split: fp32-level accuracy
     else dispatch_mt<4>(mt, [&](auto MT) { hipLaunchKernelGGL((skinny_bf16x2_kernel<MT(), 2>), grid, block, 0, s, g); });
     DLCO_HIP(hipGetLastError());
-    splitk_reduce_f32(slab, ks, M, N, C, ldc, alpha, 0.f, E1, b1, E2, b2, s);
+    splitk_reduce_f32(a.slab, ks, M, N, a.C, a.ldc, a.alpha, 0.f, a.E1, a.b1, a.E2, a.b2, s);
     return true;
 }
 
 // The same product for a symmetric G given as its packed upper tiles (see skinny_sym_kernel).
-bool skinny_product_sym(const float *X, long ldx, int M, const float *Gpacked, int F, float alpha, float *C, long ldc,
-                        const float *E1, float b1, const float *E2, float b2, void *plane_hi, void *plane_lo, float *slab,
-                        hipStream_t s, void *plane_lo2, bool planes_ready, bool emit_planes)
+bool skinny_product_sym(const SkinnyArgs &a, hipStream_t s)
 {
+    const int M = a.M, F = a.K;
+    void *plane_hi = a.planes.hi, *plane_lo = a.planes.lo, *plane_lo2 = a.planes.lo2;
     const int mt = (M + 31) / 32;
     const int nt = F / 128;
-    if (F % 128 != 0 || nt < 1 || nt > 64 || M < 1 || mt > 5 || (mt >= 4 && plane_lo2)) return false;
-    if (ldx % 4 != 0 || (reinterpret_cast<uintptr_t>(X) & 15) != 0 || (reinterpret_cast<uintptr_t>(Gpacked) & 15) != 0) return false;
-    if ((planes_ready || emit_planes) && plane_lo2) return false;       // the carried planes are the two-way ones
-    if (!planes_ready) split_planes_bf16(X, ldx, M, F, plane_hi, plane_lo, plane_lo2, s);
+    if (a.N != F || F % 128 != 0 || nt < 1 || nt > 64 || M < 1 || mt > 5 || (mt >= 4 && plane_lo2)) return false;
+    if (a.ldx % 4 != 0 || (reinterpret_cast<uintptr_t>(a.X) & 15) != 0 || (reinterpret_cast<uintptr_t>(a.G) & 15) != 0) return false;
+    if ((a.planes_ready || a.emit_planes) && plane_lo2) return false;   // the carried planes are the two-way ones
+    if (!a.planes_ready) split_planes_bf16(a.X, a.ldx, M, F, plane_hi, plane_lo, plane_lo2, s);
     SymDev g;
     g.M = M; g.K = F;
     g.nt = nt; g.lb = 2;
     while ((1 << g.lb) < nt) g.lb++;
     g.xhi = static_cast<const bf16x8 *>(plane_hi); g.xlo = static_cast<const bf16x8 *>(plane_lo); g.xlo2 = static_cast<const bf16x8 *>(plane_lo2);
-    g.G = Gpacked; g.slab = slab;
+    g.G = a.G; g.slab = a.slab;
     if (plane_lo2) dispatch_mt<3>(mt, [&](auto MT) { launch_sym<MT(), 3>(g, s); });
     else dispatch_mt<5>(mt, [&](auto MT) { launch_sym<MT(), 2>(g, s); });
     DLCO_HIP(hipGetLastError());
-    if (emit_planes && ldc % 4 == 0 && (reinterpret_cast<uintptr_t>(C) & 15) == 0) {
+    if (a.emit_planes && a.ldc % 4 == 0 && (reinterpret_cast<uintptr_t>(a.C) & 15) == 0) {
         // the product kernel has read the planes of X: they now receive the planes of the result, rows up to 32 mt zeroed by
         // the split of the first product of the chain (rows >= M of a tile are never written here and stay zero)
         const long work = (long)M * (F / 8);
-        hipLaunchKernelGGL(reduce_split_kernel, dim3((unsigned)std::min<long>((work + 255) / 256, 4096)), dim3(256), 0, s, slab, 4, M, mt, F, C, ldc,
-                           alpha, E1, b1, E2, b2, static_cast<bf16x8 *>(plane_hi), static_cast<bf16x8 *>(plane_lo));
+        hipLaunchKernelGGL(reduce_split_kernel, dim3((unsigned)std::min<long>((work + 255) / 256, 4096)), dim3(256), 0, s, a.slab, 4, M, mt, F, a.C, a.ldc,
+                           a.alpha, a.E1, a.b1, a.E2, a.b2, static_cast<bf16x8 *>(plane_hi), static_cast<bf16x8 *>(plane_lo));
         DLCO_HIP(hipGetLastError());
     } else {
-        splitk_reduce_f32(slab, 4, M, F, C, ldc, alpha, 0.f, E1, b1, E2, b2, s);
+        splitk_reduce_f32(a.slab, 4, M, F, a.C, a.ldc, a.alpha, 0.f, a.E1, a.b1, a.E2, a.b2, s);
     }
     return true;
 }

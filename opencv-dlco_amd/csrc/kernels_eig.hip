@@ -390,17 +390,15 @@ __global__ __launch_bounds__(256) void residual_publish_kernel(const float *X, c
     if (threadIdx.x == 0) __hip_atomic_store(flag_host, seq, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
 }
 
-void residual_norms_publish(const float *X, const float *Y, long ld, const float *theta, int m, int F, float *res, unsigned *ticket,
-                            const float *src, float *dst_host, int n, unsigned *flag_host, unsigned seq, hipStream_t s,
-                            const int *extra_dev, int *extra_host, const ResidualEmit *emit, bool *emitted)
+bool residual_norms_publish(const ResidualPublish &a, hipStream_t s)
 {
-    DLCO_CHECK(m > 0, -2, "residual_norms_publish: empty block");
+    DLCO_CHECK(a.m > 0, -2, "residual_norms_publish: empty block");
     ResidualEmit em;
-    if (emit && emit->W && (F & 3) == 0 && (ld & 3) == 0 && (emit->ldw & 3) == 0 && (reinterpret_cast<uintptr_t>(emit->W) & 15) == 0) em = *emit;
-    if (emitted) *emitted = em.W != nullptr;
-    hipLaunchKernelGGL(residual_publish_kernel, dim3(m), dim3(256), 0, s, X, Y, ld, theta, m, F, res, ticket, src, dst_host, n, flag_host,
-                       seq, extra_dev, extra_host, em);
+    if (a.emit.W && (a.F & 3) == 0 && (a.ld & 3) == 0 && (a.emit.ldw & 3) == 0 && (reinterpret_cast<uintptr_t>(a.emit.W) & 15) == 0) em = a.emit;
+    hipLaunchKernelGGL(residual_publish_kernel, dim3(a.m), dim3(256), 0, s, a.X, a.Y, a.ld, a.theta, a.m, a.F, a.res, a.ticket, a.src,
+                       a.dst_host, a.n, a.flag_host, a.seq, a.extra_dev, a.extra_host, em);
     DLCO_HIP(hipGetLastError());
+    return em.W != nullptr;
 }
 
 void residual_norms(const float *X, const float *Y, long ld, const float *theta, int m, int F, float *res,
@@ -411,7 +409,7 @@ void residual_norms(const float *X, const float *Y, long ld, const float *theta,
     DLCO_HIP(hipGetLastError());
 }
 
-void row_normalize(float *X, long ld, int m, int F, hipStream_t s, float min_norm)
+void row_normalize(float *X, long ld, int m, int F, float min_norm, hipStream_t s)
 {
     if (m <= 0) return;
     hipLaunchKernelGGL(row_normalize_kernel, dim3(m), dim3(256), 0, s, X, ld, m, F, min_norm);

@@ -800,7 +800,7 @@ static bool jmw_fits(int nwg, size_t lds)
 }
 
 void jacobi_eigh(const float *T, long ldt, int n, float *evals, float *V, long ldv, float *work, int *sweeps_out,
-                 hipStream_t s, float lam_cut, bool single_workgroup)
+                 float lam_cut, bool single_workgroup, hipStream_t s)
 {
     DLCO_CHECK(n >= 1 && n <= 4096, -2, "jacobi_eigh: n out of range");
     // largest column cosine of a sweep below which the sweep is the last one (see jacobi_body)

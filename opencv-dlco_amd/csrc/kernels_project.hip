@@ -238,12 +238,11 @@ void launch_project(const ProjDev &g, dim3 grid, hipStream_t s)
 
 // splits the m <= 96 rows of W into the planes and launches the pass over them: bf16 selects NS = 1, ids2 the pair mode
 template <bool SLAB>
-void split_and_project(const float *W, long ldw, int m, int F, void *plane_hi, void *plane_lo, void *plane_lo2, bool bf16, ProjDev g,
-                       dim3 grid, hipStream_t s)
+void split_and_project(const float *W, long ldw, int m, int F, const SplitPlanes &pl, bool bf16, ProjDev g, dim3 grid, hipStream_t s)
 {
-    split_planes_bf16(W, ldw, m, F, plane_hi, plane_lo, bf16 ? nullptr : plane_lo2, s);
+    split_planes_bf16(W, ldw, m, F, pl.hi, pl.lo, bf16 ? nullptr : pl.lo2, s);
     g.M = m; g.K = F;
-    g.xhi = static_cast<const bf16x8 *>(plane_hi); g.xlo = static_cast<const bf16x8 *>(plane_lo); g.xlo2 = static_cast<const bf16x8 *>(plane_lo2);
+    g.xhi = static_cast<const bf16x8 *>(pl.hi); g.xlo = static_cast<const bf16x8 *>(pl.lo); g.xlo2 = static_cast<const bf16x8 *>(pl.lo2);
     dispatch_mt<3>((m + 31) / 32, [&](auto MT) {
         if (bf16) {
             if (g.ids2) launch_project<MT(), 1, true, SLAB>(g, grid, s); else launch_project<MT(), 1, false, SLAB>(g, grid, s);
@@ -260,19 +259,18 @@ size_t project_rows_plane_bytes(int K) { return (size_t)96 * K * sizeof(__bf16);
 
 // dist[n] = |W x_n|^2 for n < nrows.  planes: three workspaces of project_rows_plane_bytes(F) bytes.  bf16 = the
 // configs[4] variant (operands rounded to bf16 once).  Returns false when the shape is not supported (F % 64).
-bool project_rows_sqdist(const float *W, long ldw, int r, const float *D, long ldd, int F, const int32_t *ids, const int32_t *ids2,
-                         long row0, int nrows, float *dist, void *plane_hi, void *plane_lo, void *plane_lo2, bool bf16, hipStream_t s)
+bool project_rows_sqdist(const ProjectRowsArgs &a, hipStream_t s)
 {
-    if (r < 1 || nrows < 1 || F % 64 != 0 || ldd % 4 != 0 || ldw % 4 != 0 || (reinterpret_cast<uintptr_t>(D) & 15) != 0 ||
-        (reinterpret_cast<uintptr_t>(W) & 15) != 0 || (long)96 * F * 2 >= (1L << 31))
+    if (a.r < 1 || a.nrows < 1 || a.F % 64 != 0 || a.ldd % 4 != 0 || a.ldw % 4 != 0 || (reinterpret_cast<uintptr_t>(a.D) & 15) != 0 ||
+        (reinterpret_cast<uintptr_t>(a.W) & 15) != 0 || (long)96 * a.F * 2 >= (1L << 31))
         return false;
-    const dim3 grid((nrows + SB_ROWS - 1) / SB_ROWS, 1);
+    const dim3 grid((a.nrows + SB_ROWS - 1) / SB_ROWS, 1);
     ProjDev g{};
-    g.nrows = nrows; g.D = D; g.ldd = ldd; g.ids = ids; g.ids2 = ids2; g.row0 = row0;
-    g.out = dist; g.ldn = 0;
-    for (int q0 = 0; q0 < r; q0 += 96) {
+    g.nrows = a.nrows; g.D = a.D; g.ldd = a.ldd; g.ids = a.ids; g.ids2 = a.ids2; g.row0 = a.row0;
+    g.out = a.dist; g.ldn = 0;
+    for (int q0 = 0; q0 < a.r; q0 += 96) {
         g.accumulate = q0 > 0 ? 1 : 0;
-        split_and_project<false>(W + (long)q0 * ldw, ldw, std::min(96, r - q0), F, plane_hi, plane_lo, plane_lo2, bf16, g, grid, s);
+        split_and_project<false>(a.W + (long)q0 * a.ldw, a.ldw, std::min(96, a.r - q0), a.F, a.planes, a.bf16, g, grid, s);
     }
     return true;
 }
@@ -280,17 +278,15 @@ bool project_rows_sqdist(const float *W, long ldw, int r, const float *D, long l
 // Raw partial projections of a FEW rows (the training batch) with K split over `ksplit` slices:
 // slab[z][q][n] = sum over slice z of W[q][k] x_n[k], q < r <= 96, n < nrows; sqdist_from_proj(slab, ksplit, r, nrows, ldn, ...)
 // finishes P2.  Used by the bf16 variant of the step (the fp32 step keeps the exact fp32 MFMA kernel).
-bool project_rows_slab(const float *W, long ldw, int r, const float *D, long ldd, int F, const int32_t *ids, const int32_t *ids2,
-                       int nrows, int ksplit, float *slab, long ldn, void *plane_hi, void *plane_lo, void *plane_lo2, bool bf16,
-                       hipStream_t s)
+bool project_rows_slab(const ProjectRowsArgs &a, hipStream_t s)
 {
-    if (r < 1 || r > 96 || nrows < 1 || ksplit < 1 || F % (64 * ksplit) != 0 || ldd % 4 != 0 || ldw % 4 != 0 || !ids ||
-        (reinterpret_cast<uintptr_t>(D) & 15) != 0 || (reinterpret_cast<uintptr_t>(W) & 15) != 0 || (long)96 * F * 2 >= (1L << 31))
+    if (a.r < 1 || a.r > 96 || a.nrows < 1 || a.ksplit < 1 || a.F % (64 * a.ksplit) != 0 || a.ldd % 4 != 0 || a.ldw % 4 != 0 || !a.ids ||
+        (reinterpret_cast<uintptr_t>(a.D) & 15) != 0 || (reinterpret_cast<uintptr_t>(a.W) & 15) != 0 || (long)96 * a.F * 2 >= (1L << 31))
         return false;
     ProjDev g{};
-    g.nrows = nrows; g.D = D; g.ldd = ldd; g.ids = ids; g.ids2 = ids2; g.row0 = 0;
-    g.out = slab; g.ldn = ldn; g.accumulate = 0;
-    split_and_project<true>(W, ldw, r, F, plane_hi, plane_lo, plane_lo2, bf16, g, dim3((nrows + SB_ROWS - 1) / SB_ROWS, ksplit), s);
+    g.nrows = a.nrows; g.D = a.D; g.ldd = a.ldd; g.ids = a.ids; g.ids2 = a.ids2; g.row0 = 0;
+    g.out = a.slab; g.ldn = a.ldn; g.accumulate = 0;
+    split_and_project<true>(a.W, a.ldw, a.r, a.F, a.planes, a.bf16, g, dim3((a.nrows + SB_ROWS - 1) / SB_ROWS, a.ksplit), s);
     return true;
 }
 

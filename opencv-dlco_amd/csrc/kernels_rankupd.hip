@@ -185,34 +185,33 @@ size_t rank_coeff_bytes(int m, int kmax) { return (size_t)(kmax / RU_KD) * ((m +
 
 // out = ay*Y + aq*Q + ac * C_w X_a with C_w built from the step's projection (see the header comment); returns false for
 // shapes the kernels do not take (the caller then forms the term with a product over the matrix).
-bool rank_first_term(const float *Y, const float *Q, long ld, int m, int F, float ay, float aq, float ac, float *out,
-                     const float *proj, long ldp, int nw, const float *wscale, const int32_t *slot, const float *w,
-                     const int *k_dev, int kmax, const void *planes, void *coeff_ws, void *plane_hi, void *plane_lo, hipStream_t s,
-                     bool coeff_ready, int planes_mode)
+bool rank_first_term(const RankTermBlock &b, const RankUpdate &ru, hipStream_t s)
 {
-    if (planes_mode != 3 && planes_mode != 1) return false;
+    if (ru.planes_mode != 3 && ru.planes_mode != 1) return false;
+    const int m = b.m, F = b.F, kmax = ru.kmax;
     const int mt = (m + 31) / 32;
     if (m < 1 || mt > 5 || F % 128 != 0 || kmax % 32 != 0 || kmax < 32) return false;
-    if (ld % 4 != 0 || (reinterpret_cast<uintptr_t>(Y) & 15) != 0 || (reinterpret_cast<uintptr_t>(Q) & 15) != 0 ||
-        (reinterpret_cast<uintptr_t>(out) & 15) != 0) return false;
-    if (!coeff_ready) {
+    if (b.ld % 4 != 0 || (reinterpret_cast<uintptr_t>(b.Y) & 15) != 0 || (reinterpret_cast<uintptr_t>(b.Q) & 15) != 0 ||
+        (reinterpret_cast<uintptr_t>(b.out) & 15) != 0) return false;
+    if (!ru.coeff_ready) {
         RankCoeffJob job;
-        job.proj = proj; job.ldp = ldp; job.nw = nw; job.m = m; job.MT = mt; job.wscale = wscale; job.slot = slot; job.frag = coeff_ws;
-        hipLaunchKernelGGL(rank_coeff_kernel, dim3(kmax / RU_KD, mt), dim3(64), 0, s, job, w, k_dev, kmax);
+        job.proj = ru.proj; job.ldp = ru.ldp; job.nw = b.nw; job.m = m; job.MT = mt; job.wscale = b.wscale; job.slot = ru.slot;
+        job.frag = b.coeff_ws;
+        hipLaunchKernelGGL(rank_coeff_kernel, dim3(kmax / RU_KD, mt), dim3(64), 0, s, job, ru.w, ru.k_dev, kmax);
     }
     RankUpdDev g;
-    g.Y = Y; g.Q = Q; g.out = out; g.ld = ld;
-    g.frag = static_cast<const bf16x8 *>(coeff_ws);
-    g.planes = static_cast<const char *>(planes);
-    g.k_dev = k_dev; g.kmax = kmax; g.nkb = kmax / RU_KD; g.nt = F / RU_TB;
-    g.m = m; g.F = F; g.ay = ay; g.aq = aq; g.ac = ac;
-    g.hi = static_cast<bf16x8 *>(plane_hi); g.lo = static_cast<bf16x8 *>(plane_lo);
+    g.Y = b.Y; g.Q = b.Q; g.out = b.out; g.ld = b.ld;
+    g.frag = static_cast<const bf16x8 *>(b.coeff_ws);
+    g.planes = static_cast<const char *>(ru.planes);
+    g.k_dev = ru.k_dev; g.kmax = kmax; g.nkb = kmax / RU_KD; g.nt = F / RU_TB;
+    g.m = m; g.F = F; g.ay = b.ay; g.aq = b.aq; g.ac = b.ac;
+    g.hi = static_cast<bf16x8 *>(b.out_planes.hi); g.lo = static_cast<bf16x8 *>(b.out_planes.lo);
     switch (mt) {
-    case 1: launch_first_term<1, 4>(g, planes_mode, s); break;
-    case 2: launch_first_term<2, 4>(g, planes_mode, s); break;
-    case 3: launch_first_term<3, 4>(g, planes_mode, s); break;
-    case 4: launch_first_term<4, 2>(g, planes_mode, s); break;
-    default: launch_first_term<5, 2>(g, planes_mode, s); break;
+    case 1: launch_first_term<1, 4>(g, ru.planes_mode, s); break;
+    case 2: launch_first_term<2, 4>(g, ru.planes_mode, s); break;
+    case 3: launch_first_term<3, 4>(g, ru.planes_mode, s); break;
+    case 4: launch_first_term<4, 2>(g, ru.planes_mode, s); break;
+    default: launch_first_term<5, 2>(g, ru.planes_mode, s); break;
     }
     DLCO_HIP(hipGetLastError());
     return true;

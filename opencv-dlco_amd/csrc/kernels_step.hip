@@ -340,8 +340,8 @@ void viol_counts(const float *pd, const float *nd, int B, int32_t *rho, int32_t 
 }
 
 void viol_counts_active_rows(const float *pd, const float *nd, int B, int32_t *rho, int32_t *kappa, const int32_t *pos_rows,
-                             const int32_t *neg_rows, int slot_lo, int slot_hi, int32_t *ids, float *w, int *k_active, hipStream_t s,
-                             int32_t *slots)
+                             const int32_t *neg_rows, int slot_lo, int slot_hi, int32_t *ids, float *w, int *k_active, int32_t *slots,
+                             hipStream_t s)
 {
     if (B <= 0) return;
     DLCO_CHECK(B <= 8192, -2, "viol_counts: batch too large for one workgroup's LDS");
@@ -405,7 +405,7 @@ void fill_f32(float *p, float v, size_t n, hipStream_t s)
 }
 
 void scale_rows(float *dst, long ldd, const float *src, long lds, const float *scale, const int32_t *src_rows,
-                int rows, int cols, hipStream_t s, const int32_t *src_rows2)
+                const int32_t *src_rows2, int rows, int cols, hipStream_t s)
 {
     if (rows <= 0) return;
     hipLaunchKernelGGL(scale_rows_kernel, dim3(rows), dim3(256), 0, s, dst, ldd, src, lds, scale, src_rows, src_rows2, rows,
@@ -430,7 +430,7 @@ void unpack_cols(float *dst, long ld, const float *src, int cw, int rows, int wo
 }
 
 void emit_w_rows(float *W, long ldw, const float *Q, long ldq, const float *theta, int nw, float mu, float cscale, int F,
-                 hipStream_t s, int m_ext, float *wscale)
+                 int m_ext, float *wscale, hipStream_t s)
 {
     const int rows = std::max(nw, m_ext);
     if (rows <= 0) return;

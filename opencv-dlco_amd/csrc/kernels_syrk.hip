@@ -74,7 +74,7 @@ constexpr int NT8 = 512;
 //               (bi, bj) at tile index bi*nt - bi*(bi-1)/2 + (bj - bi) (the layout the symmetric tracker product reads,
 //               kernels_bf16x2.hip): no mirrored store at all - half the bytes written, and 136 MB instead of 268 MB at
 //               F = 8192.  Diagonal tiles are stored whole and exactly symmetric.
-template <bool PAIR, bool SLAB, bool PACKED = false, int UNR = 16>
+template <bool PAIR, bool SLAB, bool PACKED = false>
 __global__ __launch_bounds__(NT8, 4) void syrk_rda_kernel8(SyrkDev g)
 {
     __shared__ __attribute__((aligned(16))) SyrkLds lds;
@@ -174,7 +174,7 @@ __global__ __launch_bounds__(NT8, 4) void syrk_rda_kernel8(SyrkDev g)
         const int buf = kt & 1;
         if (kt + 1 < nk) load_rows();
         if (kt + 2 < nk) load_ids(kt + 2);
-#pragma unroll UNR
+#pragma unroll 16
         for (int kk = 0; kk < KB / 2; kk++) {
             const float a0 = lds.st.A[buf][2 * kk + lk][wm * 64 + lr];
             const float a1 = lds.st.A[buf][2 * kk + lk][wm * 64 + 32 + lr];
@@ -250,6 +250,7 @@ constexpr int PL_KD = 16;                 // K rows per block
 constexpr int PL_IMG = 3 * 2 * TB * 16;   // bytes of one (operand, K block, column tile) image: 12,288
 constexpr int PL_STAGE = 2 * PL_IMG;      // A image + B image
 constexpr int NTP = 256;
+constexpr int PL_NSTAGE = 3;              // LDS stages of the matrix kernel (see launch_syrk_planes)
 
 // (coeff.frag != nullptr: the launch has one more column of blocks, which writes the coefficient fragments of the
 // tracker's rank-update first term for their K block - a by-product of the same row list, see kernels_rankupd.hip)
@@ -323,10 +324,9 @@ __global__ __launch_bounds__(256) void syrk_round_rows_kernel(const float *D, lo
     }
 }
 
-template <bool SLAB, bool PACKED, int NST, bool ONCE = false>
-__global__ __launch_bounds__(NTP, NST == 2 ? 3 : 2) void syrk_planes_kernel(SyrkDev g, const char *planes)
+template <bool SLAB, bool PACKED, bool ONCE>
+__global__ __launch_bounds__(NTP, 2) void syrk_planes_kernel(SyrkDev g, const char *planes)
 {
-    constexpr int PL_NSTAGE = NST;
     constexpr int KD = ONCE ? 3 * PL_KD : PL_KD;               // K rows per image (see syrk_round_rows_kernel)
     extern __shared__ __attribute__((aligned(16))) char smem[];
     const unsigned long long tr0 = g.trace ? wall_clock64() : 0ull;
@@ -383,7 +383,7 @@ __global__ __launch_bounds__(NTP, NST == 2 ? 3 : 2) void syrk_planes_kernel(Syrk
             dst[r] = __builtin_nontemporal_load(rowb + old_lane);          // streamed once: keep the L2 for the planes
         }
     };
-    constexpr int DEPTH = NST - 1;                            // K blocks requested ahead of the one being multiplied
+    constexpr int DEPTH = PL_NSTAGE - 1;                      // K blocks requested ahead of the one being multiplied
     if (nk > 0) issue(0, 0);
     if (DEPTH > 1 && nk > 1) issue(1, 1);
     const unsigned long long tr1 = g.trace ? wall_clock64() : 0ull;
@@ -606,43 +606,36 @@ int syrk_planes_mode(bool bf16) { return bf16 ? 1 : (env_switch("DLCO_SYRK_FP32"
 
 size_t syrk_planes_bytes(int kmax, int F) { return (size_t)2 * (kmax / PL_KD) * (F / TB) * PL_IMG; }
 
-// Workspace of the split planes for callers that bring none: one per device, grown on demand (2 operands x 6 bytes per staged value).
-static char *syrk_planes_buffer(size_t bytes)
+// One instantiation of the matrix kernel, registered for its dynamic LDS where it is launched.
+// Three stages of 24 KB, two workgroups per CU.  (Two stages and three workgroups per CU - twelve waves - measured
+// the same: 0.133 against 0.132 ms per launch; so did eight waves of 64 x 32 per tile: 0.137 against 0.133.  What the launch loses is spread over the K loop, where two
+// workgroups sharing a CU reach 72 % of the matrix rate, the 5 us of a tile's 23 outside the loop - first
+// pieces, old tile, stores - and the last of its 4.06 rounds.)
+template <bool SLAB, bool PACKED, bool ONCE>
+static void launch_syrk_planes(const SyrkDev &g, int ntiles, const char *planes, hipStream_t s)
 {
-    struct Entry { int dev; char *p; size_t cap; };
-    static std::vector<Entry> cache;
-    static std::mutex mu;
-    int dev = 0;
-    DLCO_HIP(hipGetDevice(&dev));
-    std::lock_guard<std::mutex> lock(mu);
-    for (Entry &e : cache)
-        if (e.dev == dev) {
-            if (e.cap < bytes) {
-                DLCO_HIP(hipDeviceSynchronize());              // launches that still read the old buffer
-                DLCO_HIP(hipFree(e.p));
-                e.p = nullptr; e.cap = 0;
-                DLCO_HIP(hipMalloc((void **)&e.p, bytes));
-                e.cap = bytes;
-            }
-            return e.p;
-        }
-    Entry e{dev, nullptr, bytes};
-    DLCO_HIP(hipMalloc((void **)&e.p, bytes));
-    cache.push_back(e);
-    return e.p;
+    constexpr int lds = PL_NSTAGE * PL_STAGE;
+    ensure_dynamic_lds(reinterpret_cast<const void *>(syrk_planes_kernel<SLAB, PACKED, ONCE>), lds);
+    hipLaunchKernelGGL((syrk_planes_kernel<SLAB, PACKED, ONCE>), dim3(ntiles), dim3(NTP), lds, s, g, planes);
 }
 
-bool syrk_rda_f32(const float *D, long ldd, const int32_t *ids, const int32_t *ids2, const float *w, const int *k_dev,
-                  int kmax, int F, float alpha, float beta, float *C, long ldc, hipStream_t s, int slab_col0, int slab_cols, bool bf16,
-                  bool packed, void *planes_ws, const RankCoeffJob *coeff_job)
+bool syrk_rda_f32(const SyrkArgs &a, hipStream_t s)
 {
+    DLCO_CHECK(a.planes != nullptr, -2, "syrk_rda_f32: no planes workspace");
+    const float *D = a.D;
+    const long ldd = a.ldd;
+    const int32_t *ids = a.ids, *ids2 = a.ids2;
+    const float *w = a.w;
+    const int *k_dev = a.k_dev;
+    const int kmax = a.kmax, F = a.F, slab_col0 = a.slab_col0, slab_cols = a.slab_cols;
+    const bool bf16 = a.bf16, packed = a.packed;
     if (F % TB != 0 || kmax % KB != 0 || ldd % 4 != 0 || (reinterpret_cast<uintptr_t>(D) & 15) != 0) return false;
     const bool slab = slab_cols > 0;
     if (packed && slab) return false;
     if (slab && (slab_col0 % TB != 0 || slab_cols % TB != 0 || slab_col0 + slab_cols > F)) return false;
     SyrkDev g;
     g.D = D; g.ldd = ldd; g.ids = ids; g.ids2 = ids2; g.w = w; g.k_dev = k_dev; g.kmax = kmax; g.F = F;
-    g.C = C; g.ldc = ldc; g.alpha = alpha; g.beta = beta; g.nt = F / TB;
+    g.C = a.C; g.ldc = a.ldc; g.alpha = a.alpha; g.beta = a.beta; g.nt = F / TB;
     g.slab_t0 = slab ? slab_col0 / TB : 0; g.slab_nt = slab ? slab_cols / TB : 0;
     const int ntiles = slab ? g.nt * g.slab_nt : g.nt * (g.nt + 1) / 2;
     g.trace = nullptr;
@@ -666,30 +659,17 @@ bool syrk_rda_f32(const float *D, long ldd, const int32_t *ids, const int32_t *i
     const int prec = bf16 ? 1 : (exact_fp32 ? 0 : 3);
     if (prec == 3 || prec == 1) {
         // split (or round) once, then the matrix kernel (see syrk_planes_kernel)
-        // the caller's workspace (a context owns one: launches of two contexts on two streams must not share planes), or
-        // the per-device one for callers without (developer tools: one stream)
-        char *planes = planes_ws ? static_cast<char *>(planes_ws) : syrk_planes_buffer(syrk_planes_bytes(kmax, F));
-        const RankCoeffJob job = (coeff_job && prec == 3) ? *coeff_job : RankCoeffJob();
+        char *planes = static_cast<char *>(a.planes);
+        const RankCoeffJob job = prec == 3 ? a.coeff_job : RankCoeffJob();
         if (prec == 3) hipLaunchKernelGGL(syrk_split_rows_kernel, dim3(g.nt + (job.frag ? 1 : 0), kmax / PL_KD), dim3(256), 0, s, D, ldd, ids, ids2, w, k_dev, kmax, g.nt, planes, job);
         else hipLaunchKernelGGL(syrk_round_rows_kernel, dim3(g.nt, (kmax + 3 * PL_KD - 1) / (3 * PL_KD)), dim3(256), 0, s, D, ldd, ids, ids2, w, k_dev, kmax, g.nt, planes);
-        // three stages of 24 KB, two workgroups per CU.  (Two stages and three workgroups per CU - twelve waves - measured
-        // the same: 0.133 against 0.132 ms per launch; so did eight waves of 64 x 32 per tile: 0.137 against 0.133.  What the launch loses is spread over the K loop, where two
-        // workgroups sharing a CU reach 72 % of the matrix rate, the 5 us of a tile's 23 outside the loop - first
-        // pieces, old tile, stores - and the last of its 4.06 rounds.)
-        constexpr int NST = 3;
-        ensure_dynamic_lds(reinterpret_cast<const void *>(syrk_planes_kernel<false, false, NST>), NST * PL_STAGE);
-        ensure_dynamic_lds(reinterpret_cast<const void *>(syrk_planes_kernel<true, false, NST>), NST * PL_STAGE);
-        ensure_dynamic_lds(reinterpret_cast<const void *>(syrk_planes_kernel<false, true, NST>), NST * PL_STAGE);
-        ensure_dynamic_lds(reinterpret_cast<const void *>(syrk_planes_kernel<false, false, NST, true>), NST * PL_STAGE);
-        ensure_dynamic_lds(reinterpret_cast<const void *>(syrk_planes_kernel<true, false, NST, true>), NST * PL_STAGE);
-        ensure_dynamic_lds(reinterpret_cast<const void *>(syrk_planes_kernel<false, true, NST, true>), NST * PL_STAGE);
         if (prec == 1) {
-            if (packed) hipLaunchKernelGGL((syrk_planes_kernel<false, true, NST, true>), dim3(ntiles), dim3(NTP), NST * PL_STAGE, s, g, planes);
-            else if (slab) hipLaunchKernelGGL((syrk_planes_kernel<true, false, NST, true>), dim3(ntiles), dim3(NTP), NST * PL_STAGE, s, g, planes);
-            else hipLaunchKernelGGL((syrk_planes_kernel<false, false, NST, true>), dim3(ntiles), dim3(NTP), NST * PL_STAGE, s, g, planes);
-        } else if (packed) hipLaunchKernelGGL((syrk_planes_kernel<false, true, NST>), dim3(ntiles), dim3(NTP), NST * PL_STAGE, s, g, planes);
-        else if (slab) hipLaunchKernelGGL((syrk_planes_kernel<true, false, NST>), dim3(ntiles), dim3(NTP), NST * PL_STAGE, s, g, planes);
-        else hipLaunchKernelGGL((syrk_planes_kernel<false, false, NST>), dim3(ntiles), dim3(NTP), NST * PL_STAGE, s, g, planes);
+            if (packed) launch_syrk_planes<false, true, true>(g, ntiles, planes, s);
+            else if (slab) launch_syrk_planes<true, false, true>(g, ntiles, planes, s);
+            else launch_syrk_planes<false, false, true>(g, ntiles, planes, s);
+        } else if (packed) launch_syrk_planes<false, true, false>(g, ntiles, planes, s);
+        else if (slab) launch_syrk_planes<true, false, false>(g, ntiles, planes, s);
+        else launch_syrk_planes<false, false, false>(g, ntiles, planes, s);
         DLCO_HIP(hipGetLastError());
         if (tracing) syrk_dump_trace(trace_path, trace_buf, ntiles, s);
         return true;

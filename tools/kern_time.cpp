@@ -28,6 +28,18 @@ static float time_ms(hipStream_t s, int reps, const std::function<void()> &fn)
     return ms / reps;
 }
 
+// a product over a whole F x F matrix G (or, with n < F, over n of its columns), no epilogue terms
+static SkinnyArgs skinny_args(const float *X, int M, const float *G, int n, int F, float *out, void *hi, void *lo, void *lo2, float *slab, int ksplit)
+{
+    SkinnyArgs a;
+    a.X = X; a.ldx = F; a.M = M;
+    a.G = G; a.ldg = F; a.N = n; a.K = F;
+    a.C = out; a.ldc = F;
+    a.planes.hi = hi; a.planes.lo = lo; a.planes.lo2 = lo2;
+    a.slab = slab; a.ksplit = ksplit;
+    return a;
+}
+
 int main(int argc, char **argv)
 {
     const bool small_only = argc > 1 && std::string(argv[1]) == "small";
@@ -46,11 +58,12 @@ int main(int argc, char **argv)
         for (auto &x : h) x = g0(r0);
         hipMemcpy(X.p, h.data(), h.size() * 4, hipMemcpyHostToDevice);
         for (int i = 0; i < 64; i++) hipMemcpy(C.p + (size_t)i * 128 * F, h.data(), h.size() * 4, hipMemcpyHostToDevice);
-        const float a = time_ms(s0, 30, [&] { skinny_product_bf16x2(X.p, F, M, C.p, F, F, F, 1.f, out.p, F, nullptr, 0.f, nullptr, 0.f, ph.p, pl.p, slab.p, s0); });
-        const float b = time_ms(s0, 30, [&] { skinny_product_bf16x2(X.p, F, M, C.p, F, F, F, 1.f, out.p, F, nullptr, 0.f, nullptr, 0.f, ph.p, pl.p, slab.p, s0, 0, pl2.p); });
-        const float c8 = time_ms(s0, 30, [&] { skinny_product_bf16x2(X.p, F, M, C.p, F, F, F, 1.f, out.p, F, nullptr, 0.f, nullptr, 0.f, ph.p, pl.p, slab.p, s0, 8); });
-        const float t2 = time_ms(s0, 30, [&] { skinny_product_bf16x2(X.p, F, M, C.p, F, F, F, 1.f, out.p, F, nullptr, 0.f, nullptr, 0.f, ph.p, pl.p, slab.p, s0, 0, nullptr, true); });
-        const float t3 = time_ms(s0, 30, [&] { skinny_product_bf16x2(X.p, F, M, C.p, F, F, F, 1.f, out.p, F, nullptr, 0.f, nullptr, 0.f, ph.p, pl.p, slab.p, s0, 0, pl2.p, true); });
+        const SkinnyArgs two = skinny_args(X.p, M, C.p, F, F, out.p, ph.p, pl.p, nullptr, slab.p, 0);
+        const SkinnyArgs three = skinny_args(X.p, M, C.p, F, F, out.p, ph.p, pl.p, pl2.p, slab.p, 0);
+        const SkinnyArgs two8 = skinny_args(X.p, M, C.p, F, F, out.p, ph.p, pl.p, nullptr, slab.p, 8);
+        const float a = time_ms(s0, 30, [&] { skinny_product_bf16x2(two, s0); });
+        const float b = time_ms(s0, 30, [&] { skinny_product_bf16x2(three, s0); });
+        const float c8 = time_ms(s0, 30, [&] { skinny_product_bf16x2(two8, s0); });
         {   // symmetric G as packed upper tiles: every tile fetched once (skinny_sym_kernel)
             DevBuf<float> Gp, slab4, X160, out160; DevBuf<char> qh, ql;
             Gp.alloc(syrk_packed_floats(F)); slab4.alloc((size_t)4 * 160 * F); X160.alloc((size_t)160 * F); out160.alloc((size_t)160 * F);
@@ -58,15 +71,17 @@ int main(int argc, char **argv)
             hipMemcpy(X160.p, h.data(), (size_t)128 * F * 4, hipMemcpyHostToDevice);
             hipMemcpy(X160.p + (size_t)128 * F, h.data(), (size_t)32 * F * 4, hipMemcpyHostToDevice);
             syrk_pack_upper(C.p, F, F, Gp.p, s0);
-            const float y2 = time_ms(s0, 30, [&] { skinny_product_sym(X.p, F, M, Gp.p, F, 1.f, out.p, F, nullptr, 0.f, nullptr, 0.f, ph.p, pl.p, slab4.p, s0); });
-            const float y3 = time_ms(s0, 30, [&] { skinny_product_sym(X.p, F, M, Gp.p, F, 1.f, out.p, F, nullptr, 0.f, nullptr, 0.f, ph.p, pl.p, slab4.p, s0, pl2.p); });
-            const float y5 = time_ms(s0, 30, [&] { skinny_product_sym(X160.p, F, 160, Gp.p, F, 1.f, out160.p, F, nullptr, 0.f, nullptr, 0.f, qh.p, ql.p, slab4.p, s0); });
-            const float z5 = time_ms(s0, 30, [&] { skinny_product_bf16x2(X160.p, F, 160, C.p, F, F, F, 1.f, out160.p, F, nullptr, 0.f, nullptr, 0.f, qh.p, ql.p, slab4.p, s0); });
+            const SkinnyArgs sym2 = skinny_args(X.p, M, Gp.p, F, F, out.p, ph.p, pl.p, nullptr, slab4.p, 0);
+            const SkinnyArgs sym3 = skinny_args(X.p, M, Gp.p, F, F, out.p, ph.p, pl.p, pl2.p, slab4.p, 0);
+            const SkinnyArgs sym160 = skinny_args(X160.p, 160, Gp.p, F, F, out160.p, qh.p, ql.p, nullptr, slab4.p, 0);
+            const SkinnyArgs full160 = skinny_args(X160.p, 160, C.p, F, F, out160.p, qh.p, ql.p, nullptr, slab4.p, 0);
+            const float y2 = time_ms(s0, 30, [&] { skinny_product_sym(sym2, s0); });
+            const float y3 = time_ms(s0, 30, [&] { skinny_product_sym(sym3, s0); });
+            const float y5 = time_ms(s0, 30, [&] { skinny_product_sym(sym160, s0); });
+            const float z5 = time_ms(s0, 30, [&] { skinny_product_bf16x2(full160, s0); });
             std::printf("SYMMETRIC product on packed upper tiles (136 MB): M=96 two-way %.1f us, three-way %.1f us; M=160 two-way %.1f us (full-matrix kernel %.1f us)  [split + kernel + reduce]\n",
                         y2 * 1e3, y3 * 1e3, y5 * 1e3, z5 * 1e3);
         }
-        std::printf("product on a TILED matrix (128 x 128 tiles contiguous): two-way %.1f us (%.2f TB/s), three-way %.1f us (%.2f TB/s)\n", t2 * 1e3,
-                    4.0 * F * F / (t2 * 1e-3) / 1e12, t3 * 1e3, 4.0 * F * F / (t3 * 1e-3) / 1e12);
         std::printf("product M=%d F=%d: two-way %.1f us (%.2f TB/s), three-way %.1f us (%.2f TB/s), two-way ks=8 %.1f us  [split + kernel + reduce]\n", M, F,
                     a * 1e3, 4.0 * F * F / (a * 1e-3) / 1e12, b * 1e3, 4.0 * F * F / (b * 1e-3) / 1e12, c8 * 1e3);
         return 0;
@@ -121,7 +136,7 @@ int main(int argc, char **argv)
         DevBuf<float> dT, dV, ev, work; DevBuf<int> sw;
         dT.alloc(T.size()); dV.alloc(T.size()); ev.alloc(n + 8); work.alloc(jacobi_work_floats(n)); sw.alloc(4);
         hipMemcpy(dT.p, T.data(), T.size() * 4, hipMemcpyHostToDevice);
-        const float msj = time_ms(s, n > 160 ? 5 : 100, [&] { jacobi_eigh(dT.p, ld, n, ev.p, dV.p, ld, work.p, sw.p, s); });
+        const float msj = time_ms(s, n > 160 ? 5 : 100, [&] { jacobi_eigh(dT.p, ld, n, ev.p, dV.p, ld, work.p, sw.p, JACOBI_COUNT_ALL, false, s); });
         int sweeps = 0;
         hipMemcpy(&sweeps, sw.p, 4, hipMemcpyDeviceToHost);
         std::vector<float> V(T.size()), e(n);
@@ -153,7 +168,7 @@ int main(int argc, char **argv)
                     H[(size_t)i * ld + j] = (float)(acc / K);
                 }
             hipMemcpy(dT.p, H.data(), H.size() * 4, hipMemcpyHostToDevice);
-            const float msh = time_ms(s, n > 160 ? 3 : 20, [&] { jacobi_eigh(dT.p, ld, n, ev.p, dV.p, ld, work.p, sw.p, s); });
+            const float msh = time_ms(s, n > 160 ? 3 : 20, [&] { jacobi_eigh(dT.p, ld, n, ev.p, dV.p, ld, work.p, sw.p, JACOBI_COUNT_ALL, false, s); });
             hipMemcpy(&sweeps, sw.p, 4, hipMemcpyDeviceToHost);
             hipMemcpy(V.data(), dV.p, T.size() * 4, hipMemcpyDeviceToHost);
             hipMemcpy(e.data(), ev.p, n * 4, hipMemcpyDeviceToHost);
@@ -179,10 +194,20 @@ int main(int argc, char **argv)
     // ---- slab-mode kernels at the 8-GPU shape (F = 8192, slab of 1024 columns, global batch 1600+1600) ----
     {
         const int F = 8192, R = 4096, world = 8, cw = F / world;
-        DevBuf<float> D, C, X, out, slab; DevBuf<int32_t> ids; DevBuf<float> w; DevBuf<int> kd; DevBuf<char> ph, pl;
+        DevBuf<float> D, C, X, out, slab; DevBuf<int32_t> ids; DevBuf<float> w; DevBuf<int> kd; DevBuf<char> ph, pl, syrk_planes;
         D.alloc((size_t)R * F); C.alloc((size_t)F * F); X.alloc((size_t)128 * F); out.alloc((size_t)128 * F);
         slab.alloc((size_t)32 * 128 * F / 4); ids.alloc(3200); w.alloc(3200); kd.alloc(4);
         ph.alloc(bf16x2_plane_bytes(128, F)); pl.alloc(bf16x2_plane_bytes(128, F));
+        syrk_planes.alloc(syrk_planes_bytes(3200, F));
+        // the gradient over the first kmax list entries: the whole symmetric matrix, or (cols > 0) the column slab [cols, 2 * cols)
+        auto syrk_args = [&](int kmax, float beta, int cols) {
+            SyrkArgs a;
+            a.D = D.p; a.ldd = F; a.ids = ids.p; a.w = w.p; a.k_dev = kd.p; a.kmax = kmax; a.F = F;
+            a.alpha = 1e-3f; a.beta = beta; a.C = C.p; a.ldc = F;
+            a.slab_col0 = cols; a.slab_cols = cols;
+            a.planes = syrk_planes.p;
+            return a;
+        };
         std::vector<float> h((size_t)R * F);
         for (auto &x : h) x = 0.1f * nd(rng);
         hipMemcpy(D.p, h.data(), h.size() * 4, hipMemcpyHostToDevice);
@@ -194,14 +219,14 @@ int main(int argc, char **argv)
         hipMemcpy(w.p, hw.data(), 3200 * 4, hipMemcpyHostToDevice);
         for (int K : {0, 32, 64, 128, 224, 448, 896}) {                      // fixed cost vs per-K-tile cost of the SYRK
             hipMemcpy(kd.p, &K, 4, hipMemcpyHostToDevice);
-            const float a = time_ms(s, 20, [&] { syrk_rda_f32(D.p, F, ids.p, nullptr, w.p, kd.p, 3200, F, 1e-3f, 0.5f, C.p, F, s); });
-            const float b0 = time_ms(s, 20, [&] { syrk_rda_f32(D.p, F, ids.p, nullptr, w.p, kd.p, 3200, F, 1e-3f, 0.0f, C.p, F, s); });
+            const float a = time_ms(s, 20, [&] { syrk_rda_f32(syrk_args(3200, 0.5f, 0), s); });
+            const float b0 = time_ms(s, 20, [&] { syrk_rda_f32(syrk_args(3200, 0.0f, 0), s); });
             std::printf("syrk K=%4d  symmetric full: beta=0.5 %.1f us   beta=0 (no read of the old tile) %.1f us\n", K, a * 1e3, b0 * 1e3);
         }
         for (int K : {224, 1696}) {
             hipMemcpy(kd.p, &K, 4, hipMemcpyHostToDevice);
-            const float a = time_ms(s, 20, [&] { syrk_rda_f32(D.p, F, ids.p, nullptr, w.p, kd.p, 3200, F, 1e-3f, 0.5f, C.p, F, s); });
-            const float b = time_ms(s, 20, [&] { syrk_rda_f32(D.p, F, ids.p, nullptr, w.p, kd.p, 3200, F, 1e-3f, 0.5f, C.p, F, s, cw, cw); });
+            const float a = time_ms(s, 20, [&] { syrk_rda_f32(syrk_args(3200, 0.5f, 0), s); });
+            const float b = time_ms(s, 20, [&] { syrk_rda_f32(syrk_args(3200, 0.5f, cw), s); });
             std::printf("syrk K=%4d  symmetric full %.1f us   column slab 1/%d (dense) %.1f us\n", K, a * 1e3, world, b * 1e3);
         }
         // the per-rank kernels of the same-global-batch (strong scaling) mode at G = 2, 4, 8: column slab of the gradient over the
@@ -209,15 +234,18 @@ int main(int argc, char **argv)
         for (int G : {2, 4, 8}) {
             const int cwg = F / G, K = 305;
             hipMemcpy(kd.p, &K, 4, hipMemcpyHostToDevice);
-            const float a = time_ms(s, 20, [&] { syrk_rda_f32(D.p, F, ids.p, nullptr, w.p, kd.p, 416, F, 1e-3f, 0.5f, C.p, F, s, cwg, cwg); });
-            const float b = time_ms(s, 20, [&] { skinny_product_bf16x2(X.p, F, 96, C.p + cwg, F, cwg, F, 1.f, out.p + cwg, F, nullptr, 0.f, nullptr, 0.f, ph.p, pl.p, slab.p, s, 4 * G); });
+            const SkinnyArgs pslab = skinny_args(X.p, 96, C.p + cwg, cwg, F, out.p + cwg, ph.p, pl.p, nullptr, slab.p, 4 * G);
+            const float a = time_ms(s, 20, [&] { syrk_rda_f32(syrk_args(416, 0.5f, cwg), s); });
+            const float b = time_ms(s, 20, [&] { skinny_product_bf16x2(pslab, s); });
             const float e = time_ms(s, 20, [&] { pack_cols(slab.p, out.p, F, cwg, cwg, 96, s); unpack_cols(out.p, F, slab.p, cwg, 96, G, s); });
             std::printf("G=%d: gradient column slab (K = 305 active rows, %d dense tiles) %.1f us; product slab 96 x 8192 x %d (two-way, ks %d) %.1f us; pack + unpack %.1f us\n",
                         G, (F / 128) * (cwg / 128), a * 1e3, cwg, 4 * G, b * 1e3, e * 1e3);
         }
         for (int M : {96}) {
-            const float a = time_ms(s, 20, [&] { skinny_product_bf16x2(X.p, F, M, C.p, F, F, F, 1.f, out.p, F, nullptr, 0.f, nullptr, 0.f, ph.p, pl.p, slab.p, s); });
-            const float b = time_ms(s, 20, [&] { skinny_product_bf16x2(X.p, F, M, C.p + cw, F, cw, F, 1.f, out.p + cw, F, nullptr, 0.f, nullptr, 0.f, ph.p, pl.p, slab.p, s, 32); });
+            const SkinnyArgs pfull = skinny_args(X.p, M, C.p, F, F, out.p, ph.p, pl.p, nullptr, slab.p, 0);
+            const SkinnyArgs pslab = skinny_args(X.p, M, C.p + cw, cw, F, out.p + cw, ph.p, pl.p, nullptr, slab.p, 32);
+            const float a = time_ms(s, 20, [&] { skinny_product_bf16x2(pfull, s); });
+            const float b = time_ms(s, 20, [&] { skinny_product_bf16x2(pslab, s); });
             GemmArgs g;
             g.M = M; g.N = cw; g.K = F;
             g.A.p = X.p; g.A.ld = F; g.A.kmajor = false;
