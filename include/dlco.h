@@ -606,12 +606,37 @@ int dlco_desc_match_u8_device(dlco_desc_ctx *ctx, const uint8_t *query_dev, int6
 /* the whole matrix out[nq][nt] of the same distances, for small problems, tests and tools (nq * nt <= 2^28) */
 int dlco_desc_cross_sqdists_u8(dlco_desc_ctx *ctx, const uint8_t *query_u8, int64_t nq, const uint8_t *train_u8, int64_t nt,
                                int32_t r, int32_t *out_host);
+/* ---- Geometric verification: a homography between the two sides of a match list, so that the chain ends in a verified
+ * result on this library alone.  A deterministic RANSAC by a rule of this library's own, csrc/verify_rules.hpp states it:
+ * n_hyp hypotheses from four matches each (a counter-based sampler on `seed`), scored on the device by forward transfer
+ * error (X - u W)^2 + (Y - v W)^2 <= threshold^2 W^2 with W > 0, the best by (count descending, hypothesis ascending), then at
+ * most `refine` rounds of a normalised DLT on the inliers, formed on the host and scored on the device.  Every step of the
+ * device path is IEEE double + - x without fused multiply-add or division, counts are integers: the answer is the same in
+ * every bit on every machine.  It is NOT cv::findHomography.  Like the matcher, the calls use the context for its device,
+ * stream and scratch only.
+ *   src_xy, dst_xy [m][2] float (x, y), expected finite with |x|, |y| <= 2^20 (not checked: a match with a non-finite
+ * coordinate is never an inlier).  H_out [9] row-major maps src to dst, max |H| in [1, 2); inlier_host [m] (0 / 1) and
+ * best_hyp may be NULL.  No model (no valid hypothesis) is no error: DLCO_OK with *n_inliers = 0, *best_hyp = -1, H and the
+ * mask all zero.
+ *   DLCO_ERR_INVALID, before the handle is used and with no output touched: a null handle, a required pointer NULL, m < 4 or
+ * m >= 2^31, a threshold that is not finite or <= 0, n_hyp outside 1 .. 2^20, refine outside 0 .. 8.
+ *   Out of scope: a device-memory form (the match list is filtered on the host); a fundamental or essential matrix;
+ * symmetric transfer error; an adaptive hypothesis count. */
+int  dlco_desc_verify_homography(dlco_desc_ctx *ctx, const float *src_xy_host, const float *dst_xy_host, int64_t m, float threshold,
+                                 int32_t n_hyp, uint64_t seed, int32_t refine, double *H_out, uint8_t *inlier_host, int64_t *n_inliers,
+                                 int32_t *best_hyp);
+/* every hypothesis of that call and its inlier count, H_all [n_hyp][9] (all zero: invalid) and count [n_hyp]: for tests and
+ * tools, what dlco_desc_cross_sqdists is to the matcher */
+int  dlco_desc_verify_hypotheses(dlco_desc_ctx *ctx, const float *src_xy_host, const float *dst_xy_host, int64_t m, float threshold,
+                                 int32_t n_hyp, uint64_t seed, double *H_all_host, int32_t *count_host);
 /* HIP-event time of the kernels of the last compute / describe call (transform, pooling, projection, and the sampling
  * for the keypoint calls; extract_patches: the sampling alone); the pair_sqdists /
  * pair_stats calls add their distance kernel; after a match / cross_sqdists call, float or _u8, the time of its kernels
  * (norms, tile loop, merge of the slices); the _u8 forms of describe add their quantising kernel; after a detect call the
  * detector's kernels (the integral image when the call formed it, the octaves, the selection; detect_oriented adds the
- * orientation kernel); after an orient call the orientation kernel and the integral image when the call formed it */
+ * orientation kernel); after an orient call the orientation kernel and the integral image when the call formed it; after a
+ * verify call the verify kernels (hypotheses, scoring, selection; verify_homography adds the mask kernel of the best model and
+ * of every refit round) */
 double dlco_desc_last_kernel_ms(const dlco_desc_ctx *ctx);
 
 #ifdef __cplusplus

@@ -191,6 +191,9 @@ def load():
     L.dlco_desc_match_u8.argtypes = [vp, u8p, i64, u8p, i64, C.c_int32, i32p, i32p]
     L.dlco_desc_match_u8_device.argtypes = [vp, vp, i64, i64, vp, i64, i64, C.c_int32, vp, vp]
     L.dlco_desc_cross_sqdists_u8.argtypes = [vp, u8p, i64, u8p, i64, C.c_int32, i32p]
+    f64p = C.POINTER(C.c_double)
+    L.dlco_desc_verify_homography.argtypes = [vp, f32p, f32p, i64, C.c_float, C.c_int32, C.c_uint64, C.c_int32, f64p, u8p, i64p, i32p]
+    L.dlco_desc_verify_hypotheses.argtypes = [vp, f32p, f32p, i64, C.c_float, C.c_int32, C.c_uint64, f64p, i32p]
     L.dlco_desc_last_kernel_ms.argtypes = [vp]
     L.dlco_desc_last_kernel_ms.restype = C.c_double
     L.dlco_pr_last_error.restype = C.c_char_p
@@ -942,6 +945,34 @@ class DescContext:
         d = np.empty((q.shape[0], 2), np.float32)
         self._ck(self.L.dlco_desc_match(self.h, _p(q, f32p), q.shape[0], _p(t, f32p), t.shape[0], q.shape[1], _p(idx, i32p), _p(d, f32p)))
         return idx, d
+
+    # ---- verifying a match list against a homography (csrc/verify_rules.hpp states the rule) ----
+    @staticmethod
+    def _match_points(src, dst):
+        s, d = _f32(src), _f32(dst)
+        assert s.ndim == 2 and s.shape[1] == 2 and d.shape == s.shape
+        return s, d
+
+    def verify_homography(self, src, dst, threshold=3.0, n_hyp=2048, seed=0, refine=2):
+        """The homography of the matches src [m,2] -> dst [m,2] by the library's deterministic RANSAC: (H [3,3] f64 with
+        max |H| in [1, 2), inlier [m] bool, best_hyp).  No model: H and inlier all zero, best_hyp = -1."""
+        s, d = self._match_points(src, dst)
+        m = s.shape[0]
+        H, mask = np.zeros((3, 3), np.float64), np.zeros(m, np.uint8)
+        n, best = C.c_int64(), C.c_int32()
+        self._ck(self.L.dlco_desc_verify_homography(self.h, _p(s, f32p), _p(d, f32p), m, threshold, n_hyp, seed, refine,
+                                                    _p(H, C.POINTER(C.c_double)), _p(mask, u8p), C.byref(n), C.byref(best)))
+        assert n.value == int(mask.sum())
+        return H, mask.astype(bool), best.value
+
+    def verify_hypotheses(self, src, dst, threshold=3.0, n_hyp=2048, seed=0):
+        """Every hypothesis of verify_homography and its inlier count: (H_all [n_hyp,3,3] f64, all zero where invalid,
+        count [n_hyp] int32)."""
+        s, d = self._match_points(src, dst)
+        H_all, count = np.zeros((n_hyp, 3, 3), np.float64), np.zeros(n_hyp, np.int32)
+        self._ck(self.L.dlco_desc_verify_hypotheses(self.h, _p(s, f32p), _p(d, f32p), s.shape[0], threshold, n_hyp, seed,
+                                                    _p(H_all, C.POINTER(C.c_double)), _p(count, i32p)))
+        return H_all, count
 
     def match_device(self, q_ptr, nq, t_ptr, nt, r, idx_ptr, d_ptr, ldq=None, ldt=None):
         """match on tables in device memory (row pitches ldq, ldt: multiples of 4, default r); results to device memory."""

@@ -4,7 +4,8 @@
 // the pair differences run in HIP kernels (kernels_desc.hip), the projection by a learnt W and the distances
 // of projected descriptors in kernels_describe.hip, the sampling of patches around keypoints in kernels_patch.hip, the
 // quantisation of rows to bytes (quant_rules.hpp) and the match of byte tables in kernels_match_u8.hip, the detection of
-// keypoints (detect_rules.hpp) in kernels_detect.hip, their orientation (orient_rules.hpp) in kernels_orient.hip.
+// keypoints (detect_rules.hpp) in kernels_detect.hip, their orientation (orient_rules.hpp) in kernels_orient.hip, the
+// verification of a match list against a homography (verify_rules.hpp) in kernels_verify.hip.
 // compute() serves every describe call: a PatchSource in, the rows a RowsOut names out.  The float and the byte matcher
 // share one host path (match_host, match_device) over a FloatLine / ByteLine.
 #include "../../include/dlco.h"
@@ -14,6 +15,7 @@
 #include "orient_rules.hpp"
 #include "patch_rules.hpp"
 #include "quant_rules.hpp"
+#include "verify_rules.hpp"
 
 #include <algorithm>
 #include <cmath>
@@ -83,6 +85,13 @@ struct dlco_desc_ctx {
     DevBuf<int64_t> o_vec;
     DevBuf<uint8_t> o_status;
     double o_ms = 0.0;
+    // verification (dlco_desc_verify_*): the uploaded matches, every hypothesis and its count, the selection key, the mask of
+    // one model and its count; buffers of their own, like the matchers'
+    DevBuf<float> v_src, v_dst;
+    DevBuf<double> v_H;
+    DevBuf<int32_t> v_count, v_n;
+    DevBuf<uint64_t> v_key;
+    DevBuf<uint8_t> v_mask;
     double last_ms = 0.0;
 };
 
@@ -991,6 +1000,97 @@ int dlco_desc_cross_sqdists(dlco_desc_ctx *c, const float *query_host, int64_t n
     return guarded(c, [&] { match_host<FloatLine>(c, query_host, nq, train_host, nt, r, nullptr, nullptr, out_host); });
 }
 
+// ---- verification: a homography between the two sides of a match list (verify_rules.hpp, kernels_verify.hip) ---------------
+namespace {
+bool verify_args_ok(const float *src, const float *dst, int64_t m, float threshold, int32_t n_hyp)
+{
+    return src && dst && m >= 4 && m < ((int64_t)1 << 31) && std::isfinite(threshold) && threshold > 0.0f && n_hyp >= 1 &&
+           n_hyp <= verify_rules::kMaxHyp;
+}
+
+// the matches to the device, every hypothesis and its count there; returns the kernels' milliseconds
+double verify_all(dlco_desc_ctx *c, const EventPair &ev, const float *src_host, const float *dst_host, int64_t m, double t2, int32_t n_hyp,
+                  uint64_t seed)
+{
+    DLCO_HIP(hipSetDevice(c->device));
+    c->v_src.alloc((size_t)m * 2); c->v_dst.alloc((size_t)m * 2);
+    c->v_H.alloc((size_t)n_hyp * 9); c->v_count.alloc((size_t)n_hyp);
+    c->v_key.alloc(1); c->v_n.alloc(1);
+    DLCO_HIP(hipMemcpyAsync(c->v_src.p, src_host, (size_t)m * 2 * sizeof(float), hipMemcpyHostToDevice, c->stream));
+    DLCO_HIP(hipMemcpyAsync(c->v_dst.p, dst_host, (size_t)m * 2 * sizeof(float), hipMemcpyHostToDevice, c->stream));
+    DLCO_HIP(hipMemsetAsync(c->v_count.p, 0, (size_t)n_hyp * sizeof(int32_t), c->stream));
+    return timed_ms(c, ev, [&] {
+        verify_hypotheses(c->v_src.p, c->v_dst.p, m, seed, n_hyp, c->v_H.p, c->stream);
+        verify_score(c->v_src.p, c->v_dst.p, m, c->v_H.p, n_hyp, t2, c->v_count.p, c->stream);
+        verify_select(c->v_count.p, n_hyp, c->v_key.p, c->stream);
+    });
+}
+
+// mask [m] on the host and the count of H over the uploaded matches; adds the kernel's time to *ms
+int64_t verify_score_one(dlco_desc_ctx *c, const EventPair &ev, int64_t m, const double *H, double t2, uint8_t *mask_host, double *ms)
+{
+    int32_t n = 0;
+    c->v_mask.alloc((size_t)m);
+    DLCO_HIP(hipMemsetAsync(c->v_n.p, 0, sizeof(int32_t), c->stream));
+    *ms += timed_ms(c, ev, [&] { verify_mask(c->v_src.p, c->v_dst.p, m, H, t2, c->v_mask.p, c->v_n.p, c->stream); }, [&] {
+        DLCO_HIP(hipMemcpyAsync(mask_host, c->v_mask.p, (size_t)m, hipMemcpyDeviceToHost, c->stream));
+        DLCO_HIP(hipMemcpyAsync(&n, c->v_n.p, sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
+    });
+    return n;
+}
+}  // namespace
+
+// H_all [n_hyp][9] and count [n_hyp] of every hypothesis of the rule: what dlco_desc_verify_homography selects from
+int dlco_desc_verify_hypotheses(dlco_desc_ctx *c, const float *src_xy_host, const float *dst_xy_host, int64_t m, float threshold, int32_t n_hyp,
+                                uint64_t seed, double *H_all_host, int32_t *count_host)
+{
+    if (!c || !H_all_host || !count_host || !verify_args_ok(src_xy_host, dst_xy_host, m, threshold, n_hyp)) return DLCO_ERR_INVALID;
+    return guarded(c, [&] {
+        EventPair ev;
+        c->last_ms = verify_all(c, ev, src_xy_host, dst_xy_host, m, verify_rules::threshold_sq(threshold), n_hyp, seed);
+        DLCO_HIP(hipMemcpyAsync(H_all_host, c->v_H.p, (size_t)n_hyp * 9 * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+        DLCO_HIP(hipMemcpyAsync(count_host, c->v_count.p, (size_t)n_hyp * sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
+        sync(c);
+    });
+}
+
+// H [9] row-major, the inlier mask [m] (may be NULL), its count and the winning hypothesis (may be NULL); no model is no
+// error: H and the mask are zero, *n_inliers = 0, *best_hyp = -1.  The refit's rounds are formed on the host from the mask and
+// scored by the mask kernel.
+int dlco_desc_verify_homography(dlco_desc_ctx *c, const float *src_xy_host, const float *dst_xy_host, int64_t m, float threshold, int32_t n_hyp,
+                                uint64_t seed, int32_t refine, double *H_out, uint8_t *inlier_host, int64_t *n_inliers, int32_t *best_hyp)
+{
+    if (!c || !H_out || !n_inliers || refine < 0 || refine > verify_rules::kMaxRefine ||
+        !verify_args_ok(src_xy_host, dst_xy_host, m, threshold, n_hyp))
+        return DLCO_ERR_INVALID;
+    return guarded(c, [&] {
+        namespace vr = verify_rules;
+        const double t2 = vr::threshold_sq(threshold);
+        EventPair ev;
+        double ms = verify_all(c, ev, src_xy_host, dst_xy_host, m, t2, n_hyp, seed);
+        uint64_t key = 0;
+        DLCO_HIP(hipMemcpyAsync(&key, c->v_key.p, sizeof key, hipMemcpyDeviceToHost, c->stream));
+        sync(c);
+        double H[9] = {0};
+        std::vector<uint8_t> mask((size_t)m, 0);
+        int64_t count = 0;
+        int32_t best = -1;
+        if (vr::key_count(key) > 0) {
+            best = vr::key_hyp(key);
+            DLCO_HIP(hipMemcpyAsync(H, c->v_H.p + 9 * (size_t)best, sizeof H, hipMemcpyDeviceToHost, c->stream));
+            sync(c);
+            count = verify_score_one(c, ev, m, H, t2, mask.data(), &ms);
+            vr::refit(src_xy_host, dst_xy_host, m, refine, H, mask.data(), count,
+                      [&](const double *Hn, uint8_t *trial) { return verify_score_one(c, ev, m, Hn, t2, trial, &ms); }, nullptr);
+        }
+        std::memcpy(H_out, H, sizeof H);
+        if (inlier_host) std::memcpy(inlier_host, mask.data(), (size_t)m);
+        *n_inliers = count;
+        if (best_hyp) *best_hyp = best;
+        c->last_ms = ms;
+    });
+}
+
 // ---- byte descriptors: the quantiser (quant_rules.hpp), the _u8 forms of describe, the match of byte tables -------------------
 // o_k = min_i Y[i][k], s = 255 / max_k (max_i Y[i][k] - o_k) or 1: host only
 int dlco_desc_quant_fit(const float *Y_host, int64_t n, int32_t r, float *scale, float *offset_out)
@@ -1086,7 +1186,8 @@ int dlco_desc_cross_sqdists_u8(dlco_desc_ctx *c, const uint8_t *query_u8, int64_
 // the pair calls add their distance kernel; after a match call, float or byte, its kernels (norms, top two, merge); the _u8
 // forms of describe add their quantising kernel; after an orient call the orientation kernel and the integral image when the
 // call formed it; after a detect call the detector's kernels (the integral image when the call
-// formed it, the octaves, the selection)
+// formed it, the octaves, the selection); after a verify call the verify kernels (hypotheses, scoring, selection, and for
+// verify_homography the mask kernel of the best model and of every refit round)
 double dlco_desc_last_kernel_ms(const dlco_desc_ctx *c) { return c ? c->last_ms : 0.0; }
 
 }  // extern "C"

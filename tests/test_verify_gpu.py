@@ -1,0 +1,158 @@
+"""Geometric verification on a GPU: dlco_desc_verify_hypotheses / dlco_desc_verify_homography.  The rule
+(opencv-dlco_amd/csrc/verify_rules.hpp) is IEEE double + - x in a stated order and integer counts, so every hypothesis, every
+count, the winner, the mask and the refitted matrix are compared bit for bit against the numpy restatement of
+tests/test_verify_rules.py (which the CPU tests hold against the header)."""
+import ctypes as C
+
+import numpy as np
+import pytest
+
+from test_verify_rules import bits, build_shim, inliers_ref, planted_case, reference, verify_ref
+
+pytestmark = pytest.mark.gpu
+f32p, f64p, i64p = (C.POINTER(t) for t in (C.c_float, C.c_double, C.c_int64))
+SHIFT = (16, 8)                                                              # a multiple of every octave's grid step
+
+
+@pytest.fixture(scope="module")
+def ctx(dlco):
+    c = dlco.DescContext()
+    yield c
+    c.close()
+
+
+@pytest.fixture(scope="module")
+def rules(tmp_path_factory):
+    return build_shim(tmp_path_factory)
+
+
+def same(ctx, src, dst, want, threshold=3.0, n_hyp=2048, seed=0, refine=2):
+    """the library's two calls against a restated answer: H_all, counts, best, mask, final H and inlier count, every bit"""
+    H_all, count = ctx.verify_hypotheses(src, dst, threshold, n_hyp, seed)
+    ok = H_all.shape == (n_hyp, 3, 3) and np.array_equal(bits(H_all).reshape(n_hyp, 9), bits(want["H_all"])) and np.array_equal(count, want["counts"])
+    H, mask, best = ctx.verify_homography(src, dst, threshold, n_hyp, seed, refine)
+    return (ok and best == want["best"] and mask.dtype == bool and np.array_equal(mask, want["mask"]) and int(mask.sum()) == want["count"]
+            and np.array_equal(bits(H).reshape(9), bits(want["H"])))
+
+
+def case(m, seed):
+    return planted_case(m, 0.0 if m < 16 else 0.5, seed)[:2]
+
+
+# ---- parity with the restatement ---------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("m, n_hyp", [(4, 65), (5, 63), (63, 1), (65, 300), (257, 2048)])
+@pytest.mark.parametrize("refine", [0, 2])
+def test_small_match_lists_against_the_restatement(ctx, m, n_hyp, refine):
+    src, dst = case(m, 10 + m)
+    want = reference("planted257")[2] if (m, refine) == (257, 2) else verify_ref(src, dst, n_hyp=n_hyp, seed=m, refine=refine)
+    if (m, refine) == (257, 2):
+        src, dst = reference("planted257")[:2]
+        assert same(ctx, src, dst, want) and want["count"] >= 100
+    else:
+        assert same(ctx, src, dst, want, n_hyp=n_hyp, seed=m, refine=refine)
+    assert ctx.last_kernel_ms() > 0
+
+
+def test_match_lists_around_the_scoring_chunk(ctx, rules):
+    chunk = rules.shim_verify_score_chunk()
+    assert chunk >= 64
+    for m in (chunk - 1, chunk, chunk + 1, 3 * chunk + 7):                   # the last spans four workgroups of the grid's second dimension
+        src, dst = case(m, m)
+        want = verify_ref(src, dst, n_hyp=300, seed=3, refine=2)
+        assert want["count"] >= 0.45 * m and same(ctx, src, dst, want, n_hyp=300, seed=3), m
+
+
+def test_a_tighter_threshold_runs_more_than_one_round(ctx):
+    src, dst, _ = reference("planted257")
+    want = verify_ref(src, dst, threshold=0.75, n_hyp=63, seed=5, refine=2)
+    assert same(ctx, src, dst, want, threshold=0.75, n_hyp=63, seed=5)
+    want8 = verify_ref(src, dst, threshold=1.5, n_hyp=65, seed=7, refine=8)
+    assert same(ctx, src, dst, want8, threshold=1.5, n_hyp=65, seed=7, refine=8)
+    assert max(len(want["rounds"]), len(want8["rounds"])) >= 2
+
+
+@pytest.mark.parametrize("name", ["planted1000", "collinear", "translation", "nan", "far"])
+def test_the_cases_of_the_cpu_tests(ctx, name):
+    src, dst, want = reference(name)
+    assert same(ctx, src, dst, want)
+    H, mask, best = ctx.verify_homography(src, dst)
+    if name == "collinear":                                                  # no model is no error
+        assert best == -1 and not mask.any() and (H == 0).all() and not want["valid"].any()
+    if name == "translation":
+        assert best == int(np.flatnonzero(want["valid"])[0]) and mask.all() and (want["counts"][want["valid"]] == len(src)).all()
+    if name == "nan":
+        assert not mask[[0, 5, 17]].any() and mask.sum() == len(src) - 3 and np.isfinite(H).all()
+    if name == "far":
+        assert np.isfinite(H).all() and np.isfinite(ctx.verify_hypotheses(src, dst)[0]).all()
+
+
+def test_the_same_call_twice_and_another_seed(ctx):
+    src, dst, want = reference("planted257")
+    first, again = ctx.verify_homography(src, dst), ctx.verify_homography(src, dst)
+    assert all(np.array_equal(a, b) for a, b in zip(first[:2], again[:2])) and first[2] == again[2] == want["best"]
+    other = verify_ref(src, dst, seed=1)
+    assert other["best"] != want["best"] and same(ctx, src, dst, other, seed=1)
+
+
+def test_a_larger_call_before_leaves_nothing_behind(ctx):
+    big_src, big_dst = case(775, 20)
+    ctx.verify_homography(big_src, big_dst, n_hyp=2048)
+    src, dst = case(63, 21)
+    want = verify_ref(src, dst, n_hyp=65, seed=9)
+    assert same(ctx, src, dst, want, n_hyp=65, seed=9)
+    ctx.verify_hypotheses(big_src, big_dst, n_hyp=2048)
+    assert same(ctx, src, dst, want, n_hyp=65, seed=9)
+
+
+def test_optional_outputs_may_be_null(ctx):
+    src, dst, want = reference("planted257")
+    H, n = np.zeros(9), C.c_int64(-1)
+    assert ctx.L.dlco_desc_verify_homography(ctx.h, src.ctypes.data_as(f32p), dst.ctypes.data_as(f32p), len(src), 3.0, 2048, 0, 2, H.ctypes.data_as(f64p), None,
+                                             C.byref(n), None) == 0
+    assert n.value == want["count"] and np.array_equal(bits(H), bits(want["H"]))
+
+
+# ---- the chain ---------------------------------------------------------------------------------------------------------------
+def shifted_pair():
+    """a 256 x 256 image and its copy shifted by SHIFT: two crops of one canvas of noise.  The restated detector finds 219 of
+    the 300 strongest keypoints of the first at their shifted places among the 300 strongest of the second."""
+    canvas = np.random.default_rng(61).integers(0, 256, (256 + SHIFT[1], 256 + SHIFT[0]), dtype=np.uint8)
+    return np.ascontiguousarray(canvas[:256, :256]), np.ascontiguousarray(canvas[SHIFT[1]:, SHIFT[0]:])
+
+
+def chain_model(c):
+    from test_describe_gpu import make_w
+    from test_descriptors import make_filters
+    c.set_filters(make_filters(16, seed=4))                                  # the tiny model of tests/test_keypoints_gpu.py
+    c.set_projection(make_w(12, 128, seed=2))
+
+
+def ratio_cross_ref(nearest, sqdist, back, f):
+    """match's two host rules restated (cli/match_rules.hpp): d1 < f^2 d2 in double, and the nearest query of train row j is i"""
+    f = float(np.float32(f))
+    return np.array([(i, j) for i, ((j, j2), (d1, d2)) in enumerate(zip(nearest.tolist(), sqdist.astype(np.float64).tolist()))
+                     if j >= 0 and (j2 == -1 or d1 < f * f * d2) and int(back[j][0]) == i], np.int32).reshape(-1, 2)
+
+
+def test_image_to_verified_matches(ctx):
+    a, b = shifted_pair()
+    chain_model(ctx)
+    kps, Ys = [], []
+    for img in (a, b):
+        ctx.set_image(img)
+        kp, _, _ = ctx.detect_oriented(2, 3000000, 300)
+        Y, st = ctx.describe_keypoints(kp)
+        kps.append(kp)
+        Ys.append(Y)
+    nearest, sqdist = ctx.match(Ys[0], Ys[1])
+    back, _ = ctx.match(Ys[1], Ys[0])
+    matches = ratio_cross_ref(nearest, sqdist, back, 0.8)
+    assert len(matches) >= 8, len(matches)
+    src, dst = kps[0][matches[:, 0], :2], kps[1][matches[:, 1], :2]
+    H, mask, best = ctx.verify_homography(src, dst)
+    want = verify_ref(src, dst)
+    assert best == want["best"] >= 0 and np.array_equal(mask, want["mask"]) and np.array_equal(bits(H).reshape(9), bits(want["H"]))
+    assert mask.sum() >= 8
+    corners = np.array([(0, 0, 1), (255, 0, 1), (255, 255, 1), (0, 255, 1)], np.float64)
+    p = corners @ (H / H[2, 2]).T
+    assert np.abs(p[:, :2] / p[:, 2:] - (corners[:, :2] - SHIFT)).max() <= 1.0
