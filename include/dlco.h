@@ -562,6 +562,44 @@ int dlco_desc_match_device(dlco_desc_ctx *ctx, const float *query_dev, int64_t l
 /* the whole matrix out[nq][nt] of the same distances, for small problems, tests and tools (nq * nt <= 2^28) */
 int dlco_desc_cross_sqdists(dlco_desc_ctx *ctx, const float *query_host, int64_t nq, const float *train_host, int64_t nt,
                             int32_t r, float *out_host);
+/* ---- Guided matching: the nearest two among the rows a homography admits.  Once a model exists (dlco_desc_verify_homography)
+ * every query is matched again, but only against the train keypoints the model puts within `radius` pixels of it: the step
+ * that recovers the correspondences the ratio test and the mutual check threw away in repeated structure, and the input of
+ * a second, tighter verification.  csrc/guided_rules.hpp states the rule.
+ *   Geometry: query_xy [nq][2] and train_xy [nt][2] float, the (x, y) of the keypoint each descriptor row belongs to; H [9]
+ * row-major, it need not be normalised; radius in pixels of the image H maps to.  The pair predicate P(i, j) is the inlier
+ * test of the verification, (X - u W)^2 + (Y - v W)^2 <= radius^2 W^2 with W > 0, in IEEE double + - x without fused
+ * multiply-add or division, the same in every bit on every machine:
+ *     h_side = 0: H maps the query image to the train image, (X, Y, W) = H (qx_i, qy_i, 1) and (u, v) = train_xy[j]
+ *     h_side = 1: H maps the train image to the query image, (X, Y, W) = H (tx_j, ty_j, 1) and (u, v) = query_xy[i]
+ * h_side = 1 exists so that a mutual check can swap the tables and keep H: that call sees the transpose of the same
+ * admissible set.
+ *   Result: idx[i] / sqdist[i] are the first two admitted candidates of row i under dlco_desc_match's (distance, index) key,
+ * i.e. the top two of the finite entries of row i of the matrix dlco_desc_cross_sqdists_guided returns; every distance has
+ * the bits of the same entry of dlco_desc_cross_sqdists.  Fewer than two admitted candidates leave -1 / +inf in the free
+ * columns.  A point with a non-finite coordinate is admitted, and admits, where the rule's comparisons say so (a NaN fails
+ * them all); indices stay in [-1, nt) and nothing faults.  The limits and the arithmetic of the distances are
+ * dlco_desc_match's.
+ *   DLCO_ERR_INVALID, before the handle is used and with no output touched: whatever dlco_desc_match (_device, cross_sqdists)
+ * rejects, a null coordinate pointer or a null H, an entry of H that is not finite, a radius that is not finite or <= 0, an
+ * h_side other than 0 or 1, a coordinate pitch below 2 (device form).
+ *   Out of scope: a spatially bucketed form that skips tiles no query of which can admit a row (a distance's bits are defined
+ * by the tile loop's chain of matrix-core operations, which a kernel that gathers candidates does not reproduce); the byte
+ * line (there is no dlco_desc_match_u8_guided); a fundamental-matrix predicate. ---- */
+int dlco_desc_match_guided(dlco_desc_ctx *ctx, const float *query_host, const float *query_xy_host, int64_t nq,
+                           const float *train_host, const float *train_xy_host, int64_t nt, int32_t r, const double *H,
+                           float radius, int32_t h_side, int32_t *idx_host, float *sqdist_host);
+/* the same on tables in HBM, as dlco_desc_match_device takes them.  The coordinates are device memory as well, 4-byte aligned,
+ * row i at xy + i * ldxy with a pitch in floats >= 2: with pitch 4 the [n][4] keypoint rows (x, y, scale, angle) that
+ * dlco_desc_detect_device wrote can be passed as they are.  H is host memory. */
+int dlco_desc_match_guided_device(dlco_desc_ctx *ctx, const float *query_dev, int64_t ldq, const float *query_xy_dev,
+                                  int64_t ldxy_q, int64_t nq, const float *train_dev, int64_t ldt,
+                                  const float *train_xy_dev, int64_t ldxy_t, int64_t nt, int32_t r, const double *H,
+                                  float radius, int32_t h_side, int32_t *idx_dev, float *sqdist_dev);
+/* the matrix out[nq][nt] of dlco_desc_cross_sqdists with +inf where P fails (nq * nt <= 2^28) */
+int dlco_desc_cross_sqdists_guided(dlco_desc_ctx *ctx, const float *query_host, const float *query_xy_host, int64_t nq,
+                                   const float *train_host, const float *train_xy_host, int64_t nt, int32_t r,
+                                   const double *H, float radius, int32_t h_side, float *out_host);
 /* ---- Eight-bit descriptors: a table of bytes is a quarter of the float one, and its distances are integers.
  *   The quantiser is a scale s > 0 and an offset o[r]; csrc/quant_rules.hpp states the rule.  One element:
  * t = y - o_k in float, v = t * s in float (two roundings, never an FMA), q = rintf(v) (half to even); the byte is 0 if v is
@@ -632,7 +670,7 @@ int  dlco_desc_verify_hypotheses(dlco_desc_ctx *ctx, const float *src_xy_host, c
 /* HIP-event time of the kernels of the last compute / describe call (transform, pooling, projection, and the sampling
  * for the keypoint calls; extract_patches: the sampling alone); the pair_sqdists /
  * pair_stats calls add their distance kernel; after a match / cross_sqdists call, float or _u8, the time of its kernels
- * (norms, tile loop, merge of the slices); the _u8 forms of describe add their quantising kernel; after a detect call the
+ * (norms, tile loop, merge of the slices, and for the guided forms the kernel that writes the records); the _u8 forms of describe add their quantising kernel; after a detect call the
  * detector's kernels (the integral image when the call formed it, the octaves, the selection; detect_oriented adds the
  * orientation kernel); after an orient call the orientation kernel and the integral image when the call formed it; after a
  * verify call the verify kernels (hypotheses, scoring, selection; verify_homography adds the mask kernel of the best model and

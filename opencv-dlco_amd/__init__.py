@@ -194,6 +194,10 @@ def load():
     f64p = C.POINTER(C.c_double)
     L.dlco_desc_verify_homography.argtypes = [vp, f32p, f32p, i64, C.c_float, C.c_int32, C.c_uint64, C.c_int32, f64p, u8p, i64p, i32p]
     L.dlco_desc_verify_hypotheses.argtypes = [vp, f32p, f32p, i64, C.c_float, C.c_int32, C.c_uint64, f64p, i32p]
+    L.dlco_desc_match_guided.argtypes = [vp, f32p, f32p, i64, f32p, f32p, i64, C.c_int32, f64p, C.c_float, C.c_int32, i32p, f32p]
+    L.dlco_desc_match_guided_device.argtypes = [vp, vp, i64, vp, i64, i64, vp, i64, vp, i64, i64, C.c_int32, f64p, C.c_float,
+                                                C.c_int32, vp, vp]
+    L.dlco_desc_cross_sqdists_guided.argtypes = [vp, f32p, f32p, i64, f32p, f32p, i64, C.c_int32, f64p, C.c_float, C.c_int32, f32p]
     L.dlco_desc_last_kernel_ms.argtypes = [vp]
     L.dlco_desc_last_kernel_ms.restype = C.c_double
     L.dlco_pr_last_error.restype = C.c_char_p
@@ -985,6 +989,47 @@ class DescContext:
         assert q.ndim == 2 and t.ndim == 2 and q.shape[1] == t.shape[1]
         out = np.empty((q.shape[0], t.shape[0]), np.float32)
         self._ck(self.L.dlco_desc_cross_sqdists(self.h, _p(q, f32p), q.shape[0], _p(t, f32p), t.shape[0], q.shape[1], _p(out, f32p)))
+        return out
+
+    # ---- guided matching: the nearest two among the rows a homography admits (csrc/guided_rules.hpp states the rule) ----
+    @staticmethod
+    def _guided_tables(query, query_xy, train, train_xy, H):
+        q, t, qxy, txy = _f32(query), _f32(train), _f32(query_xy), _f32(train_xy)
+        assert q.ndim == 2 and t.ndim == 2 and q.shape[1] == t.shape[1]
+        assert qxy.shape == (q.shape[0], 2) and txy.shape == (t.shape[0], 2)
+        h = np.ascontiguousarray(H, np.float64)
+        assert h.size == 9
+        return q, qxy, t, txy, h
+
+    def match_guided(self, query, query_xy, train, train_xy, H, radius=6.0, h_side=0):
+        """match among the rows of train the homography H [3,3] admits for a query: those whose keypoint train_xy [nt,2] lies
+        within radius pixels of H applied to the query's query_xy [nq,2] (h_side=0: H maps the query image to the train
+        image; h_side=1: H maps the train image to the query image, the call of a mutual check with the tables swapped).
+        (idx [nq,2] int32, sqdist [nq,2] float32); fewer than two admitted rows leave -1 / +inf."""
+        q, qxy, t, txy, h = self._guided_tables(query, query_xy, train, train_xy, H)
+        idx = np.empty((q.shape[0], 2), np.int32)
+        d = np.empty((q.shape[0], 2), np.float32)
+        self._ck(self.L.dlco_desc_match_guided(self.h, _p(q, f32p), _p(qxy, f32p), q.shape[0], _p(t, f32p), _p(txy, f32p), t.shape[0],
+                                               q.shape[1], _p(h, C.POINTER(C.c_double)), radius, h_side, _p(idx, i32p), _p(d, f32p)))
+        return idx, d
+
+    def match_guided_device(self, q_ptr, qxy_ptr, nq, t_ptr, txy_ptr, nt, r, H, idx_ptr, d_ptr, radius=6.0, h_side=0, ldq=None,
+                            ldt=None, ldxy_q=2, ldxy_t=2):
+        """match_guided on tables in device memory (row pitches ldq, ldt: multiples of 4, default r; coordinate pitches in
+        floats, >= 2: 4 takes the keypoint rows detect_device wrote); results to device memory."""
+        h = np.ascontiguousarray(H, np.float64)
+        assert h.size == 9
+        self._ck(self.L.dlco_desc_match_guided_device(self.h, C.c_void_p(q_ptr), ldq or r, C.c_void_p(qxy_ptr), ldxy_q, nq,
+                                                      C.c_void_p(t_ptr), ldt or r, C.c_void_p(txy_ptr), ldxy_t, nt, r,
+                                                      _p(h, C.POINTER(C.c_double)), radius, h_side, C.c_void_p(idx_ptr), C.c_void_p(d_ptr)))
+
+    def cross_sqdists_guided(self, query, query_xy, train, train_xy, H, radius=6.0, h_side=0):
+        """cross_sqdists with +inf where H does not admit the pair: match_guided is the top two of its finite entries."""
+        q, qxy, t, txy, h = self._guided_tables(query, query_xy, train, train_xy, H)
+        out = np.empty((q.shape[0], t.shape[0]), np.float32)
+        self._ck(self.L.dlco_desc_cross_sqdists_guided(self.h, _p(q, f32p), _p(qxy, f32p), q.shape[0], _p(t, f32p), _p(txy, f32p),
+                                                       t.shape[0], q.shape[1], _p(h, C.POINTER(C.c_double)), radius, h_side,
+                                                       _p(out, f32p)))
         return out
 
     # ---- eight-bit descriptors: rows quantised on the device, byte tables matched with exact integer distances ----

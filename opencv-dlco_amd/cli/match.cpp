@@ -1,6 +1,7 @@
 // match — nearest-neighbour matching of two descriptor tables, over libdlco.so.
 //
 //     match query_desc_file train_desc_file -out dst [-u8] [-ratio f] [-cross] [-device n]
+//           [-guided verify_out -kp query_kp_file train_kp_file [-radius f]]
 //
 // Both inputs hold the dataset "Descriptor" [n, r] f32 that `describe` writes (the two r must agree).  Writes
 //     "Nearest" [nq,2] i32 and "NearestSqDist" [nq,2] f32   the library's answer for every query (dlco_desc_match)
@@ -12,6 +13,13 @@
 // dlco_desc_match_u8, and "NearestSqDist" / "MatchSqDist" are i32: exact integer distances.  If both files carry a quantiser
 // ("QuantScale", "QuantOffset") and the two differ in any bit the tool refuses: distances between differently quantised
 // tables mean nothing.
+//   With -guided the library call is dlco_desc_match_guided: every query is matched among the train keypoints that the
+// homography of a `verify` output ("HomographyBits", query image -> train image) puts within -radius pixels (default 6) of
+// it.  The two -kp files hold "Keypoints" [n,4] f32 as `detect` writes them, row for row the keypoints of the two descriptor
+// tables (a row count that differs is an error, and so is a verify output without a model, "BestHypothesis" = -1).  -cross
+// makes its second call with the tables swapped and h_side = 1, which sees the transpose of the same admissible set; -ratio
+// and -cross are the same host rules on the guided answer (a query with no admitted row is no match).  There is no guided
+// form of -u8.
 // A path that does not end in .h5/.hdf5 is a directory of .npy files with the same dataset names (dlco_io.hpp).
 #include "../../include/dlco.h"
 #include "dlco_io.hpp"
@@ -19,6 +27,7 @@
 #include "quant_io.hpp"
 
 #include <chrono>
+#include <cmath>
 #include <cstdlib>
 #include <cstring>
 #include <iostream>
@@ -39,6 +48,33 @@ void load_table_u8(const char *path, std::vector<size_t> &shape, std::vector<uin
 {
     dlco_io::read_dataset<uint8_t>(path, "DescriptorU8", shape, rows);
     if (shape.size() != 2 || shape[0] < 1 || shape[1] < 1) throw std::runtime_error(std::string(path) + ": DescriptorU8 must be a non-empty [n, r] table");
+}
+
+// the (x, y) of the "Keypoints" [n,4] of a detect output, which must have `rows` rows: those of its descriptor table
+void load_xy(const char *path, size_t rows, const char *desc_path, std::vector<float> &xy)
+{
+    std::vector<size_t> shape;
+    std::vector<float> kp;
+    dlco_io::read_dataset<float>(path, "Keypoints", shape, kp);
+    if (shape.size() != 2 || shape[1] != 4) throw std::runtime_error(std::string(path) + ": Keypoints must be an [n, 4] table");
+    if (shape[0] != rows)
+        throw std::runtime_error(std::string(path) + ": " + std::to_string(shape[0]) + " keypoints against " + std::to_string(rows) + " descriptors in " + desc_path);
+    xy.resize(rows * 2);
+    for (size_t i = 0; i < rows; i++) { xy[2 * i] = kp[4 * i]; xy[2 * i + 1] = kp[4 * i + 1]; }
+}
+
+// H [9] of a verify output; refuses one without a model
+void load_model(const char *path, double H[9])
+{
+    std::vector<size_t> shape;
+    std::vector<int32_t> best;
+    std::vector<int64_t> bits;
+    dlco_io::read_dataset<int32_t>(path, "BestHypothesis", shape, best);
+    if (best.size() != 1) throw std::runtime_error(std::string(path) + ": BestHypothesis must hold one value");
+    if (best[0] < 0) throw std::runtime_error(std::string(path) + ": the verification found no model (BestHypothesis = -1): nothing to guide by");
+    dlco_io::read_dataset<int64_t>(path, "HomographyBits", shape, bits);
+    if (bits.size() != 9) throw std::runtime_error(std::string(path) + ": HomographyBits must hold nine values");
+    std::memcpy(H, bits.data(), 9 * sizeof(double));
 }
 
 // the -u8 line of main: the same steps on byte tables
@@ -88,8 +124,8 @@ int main(int argc, char **argv)
 {
     int device = 0;
     bool help = false, cross = false, use_ratio = false, u8 = false;
-    float ratio = 1.0f;
-    const char *qf = nullptr, *tf = nullptr, *out = nullptr;
+    float ratio = 1.0f, radius = 6.0f;
+    const char *qf = nullptr, *tf = nullptr, *out = nullptr, *guided = nullptr, *qkp = nullptr, *tkp = nullptr;
     for (int i = 1; i < argc; i++) {
         if (argv[i][0] == '-') {
             const bool has_val = i + 1 < argc;
@@ -98,6 +134,9 @@ int main(int argc, char **argv)
             if (std::strcmp(argv[i], "-ratio") == 0 && has_val) { ratio = (float)atof(argv[++i]); use_ratio = true; continue; }
             if (std::strcmp(argv[i], "-cross") == 0) { cross = true; continue; }
             if (std::strcmp(argv[i], "-u8") == 0) { u8 = true; continue; }
+            if (std::strcmp(argv[i], "-guided") == 0 && has_val) { guided = argv[++i]; continue; }
+            if (std::strcmp(argv[i], "-kp") == 0 && i + 2 < argc) { qkp = argv[++i]; tkp = argv[++i]; continue; }
+            if (std::strcmp(argv[i], "-radius") == 0 && has_val) { radius = (float)atof(argv[++i]); continue; }
             if (std::strcmp(argv[i], "-device") == 0 && has_val) { device = atoi(argv[++i]); continue; }
             cout << "ERROR: Invalid " << argv[i] << " option." << endl;
             help = true;
@@ -112,9 +151,22 @@ int main(int argc, char **argv)
         cout << "ERROR: -ratio must be in (0, 1]." << endl;
         help = true;
     }
+    if (guided && u8) {
+        cout << "ERROR: -guided has no -u8 form." << endl;
+        help = true;
+    }
+    if ((guided != nullptr) != (qkp != nullptr)) {
+        cout << "ERROR: -guided and -kp go together." << endl;
+        help = true;
+    }
+    if (!(std::isfinite(radius) && radius > 0.0f)) {
+        cout << "ERROR: -radius must be finite and > 0." << endl;
+        help = true;
+    }
     if (help) {
         cout << endl;
-        cout << "Usage: match query_desc_file train_desc_file -out dst_h5_filename [-u8] [-ratio f] [-cross] [-device n]" << endl;
+        cout << "Usage: match query_desc_file train_desc_file -out dst_h5_filename [-u8] [-ratio f] [-cross] [-device n] "
+                "[-guided verify_out -kp query_kp_file train_kp_file [-radius f]]" << endl;
         cout << endl;
         return 1;
     }
@@ -134,18 +186,31 @@ int main(int argc, char **argv)
         const size_t nq = qs[0], nt = ts[0], r = qs[1];
         printf("Queries: %zu x %zu\n", nq, r);
         printf("Train: %zu x %zu\n", nt, r);
+        double H[9] = {0};
+        std::vector<float> qxy, txy;
+        if (guided) {
+            load_model(guided, H);
+            load_xy(qkp, nq, qf, qxy);
+            load_xy(tkp, nt, tf, txy);
+            printf("Guided: radius %g\n", radius);
+        }
 
         if (dlco_desc_create(&ctx, 1.4f, 8, 1, device) != DLCO_OK) throw std::runtime_error(dlco_desc_last_error(nullptr));
         const auto t0 = std::chrono::steady_clock::now();
         std::vector<int32_t> nearest(nq * 2), back;
         std::vector<float> sqdist(nq * 2);
-        if (dlco_desc_match(ctx, Q.data(), (int64_t)nq, T.data(), (int64_t)nt, (int32_t)r, nearest.data(), sqdist.data()) != DLCO_OK)
-            throw std::runtime_error(dlco_desc_last_error(ctx));
+        const int rc = guided ? dlco_desc_match_guided(ctx, Q.data(), qxy.data(), (int64_t)nq, T.data(), txy.data(), (int64_t)nt, (int32_t)r, H, radius, 0,
+                                                       nearest.data(), sqdist.data())
+                              : dlco_desc_match(ctx, Q.data(), (int64_t)nq, T.data(), (int64_t)nt, (int32_t)r, nearest.data(), sqdist.data());
+        if (rc != DLCO_OK) throw std::runtime_error(dlco_desc_last_error(ctx));
         if (cross) {
             back.resize(nt * 2);
             std::vector<float> back_d(nt * 2);
-            if (dlco_desc_match(ctx, T.data(), (int64_t)nt, Q.data(), (int64_t)nq, (int32_t)r, back.data(), back_d.data()) != DLCO_OK)
-                throw std::runtime_error(dlco_desc_last_error(ctx));
+            // guided: the tables swapped and H kept, h_side = 1: the transpose of the same admissible set
+            const int rb = guided ? dlco_desc_match_guided(ctx, T.data(), txy.data(), (int64_t)nt, Q.data(), qxy.data(), (int64_t)nq, (int32_t)r, H, radius, 1,
+                                                           back.data(), back_d.data())
+                                  : dlco_desc_match(ctx, T.data(), (int64_t)nt, Q.data(), (int64_t)nq, (int32_t)r, back.data(), back_d.data());
+            if (rb != DLCO_OK) throw std::runtime_error(dlco_desc_last_error(ctx));
         }
         std::vector<int32_t> pairs;
         std::vector<float> dists;

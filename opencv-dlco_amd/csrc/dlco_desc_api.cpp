@@ -12,6 +12,7 @@
 
 #include "dlco_internal.hpp"
 #include "detect_rules.hpp"
+#include "guided_rules.hpp"
 #include "orient_rules.hpp"
 #include "patch_rules.hpp"
 #include "quant_rules.hpp"
@@ -31,13 +32,17 @@ constexpr int kChunk = 2048;            // patches per launch pair: 256 MB of Pa
 }
 
 // The buffers of one matcher (FloatLine, ByteLine below): the uploaded tables of the host forms, the result of a chunk and
-// the matrix, part [slices][nq] partial (d1, j1, d2, j2) of 16 bytes each, the norms of the queries and of train
+// the matrix, part [slices][nq] partial (d1, j1, d2, j2) of 16 bytes each, the norms of the queries and of train; for the
+// guided forms of the float line the uploaded (x, y) of both tables and rec [n][4], the records of the side the homography
+// applies to (guided_rules.hpp): a launch's queries or all of train
 template <typename Elem, typename Dist, typename Norm>
 struct MatchBufs {
     DevBuf<Elem> query, train;
     DevBuf<Dist> sqdist, cross;
     DevBuf<int32_t> idx, part;
     DevBuf<Norm> qnorm, tnorm;
+    DevBuf<float> qxy, txy;
+    DevBuf<double> rec;
 };
 
 struct dlco_desc_ctx {
@@ -241,6 +246,7 @@ struct FloatLine {
     static MatchBufs<Elem, Dist, Norm> &bufs(dlco_desc_ctx *c) { return c->m_float; }
     static void query_norms(const Elem *x, long ld, long n, int r, Norm *norm, hipStream_t s) { match_norms(x, ld, n, r, norm, s); }
     static void train_norms(const Elem *x, long ld, long n, int r, Norm *norm, hipStream_t s) { match_norms(x, ld, n, r, norm, s); }
+    static constexpr bool guided = true;                   // the tile loop has the guided epilogue
     static constexpr auto top2 = match_top2;
 };
 struct ByteLine {
@@ -251,7 +257,23 @@ struct ByteLine {
     static void query_norms(const Elem *x, long ld, long n, int r, Norm *norm, hipStream_t s) { match_u8_norms(x, ld, n, r, false, norm, s); }
     // negated: the form the tile loop takes for train
     static void train_norms(const Elem *x, long ld, long n, int r, Norm *norm, hipStream_t s) { match_u8_norms(x, ld, n, r, true, norm, s); }
-    static constexpr auto top2 = match_u8_top2;
+    static constexpr bool guided = false;
+    static void top2(const Elem *query, long ldq, int nq, const Elem *train, long ldt, int nt, int r, const Norm *qnorm, const Norm *tnorm,
+                     int tiles_per_slice, int32_t *idx, Dist *sqdist, void *part, Dist *out, const MatchGuide *, hipStream_t s)
+    {
+        match_u8_top2(query, ldq, nq, train, ldt, nt, r, qnorm, tnorm, tiles_per_slice, idx, sqdist, part, out, s);
+    }
+};
+
+// The geometry of a guided call (guided_rules.hpp), an optional argument of the float line's host path: the (x, y) of the
+// rows of both tables at pitches in floats (device memory in match_on_device and match_device, host memory with pitch 2 in
+// match_host), the homography, the squared radius and the side H applies to.
+struct Geometry {
+    const float *qxy; long ldq;
+    const float *txy; long ldt;
+    const double *H;
+    double t2;
+    int h_side;
 };
 
 constexpr int64_t kMatchRows = (int64_t)1 << 20;           // queries per launch (the kernels index a launch's queries with an int)
@@ -263,50 +285,68 @@ bool match_args_ok(const void *a, const void *b, const void *o1, const void *o2,
     return a && b && o1 && o2 && r >= 1 && r <= 1024 && nq >= 1 && nt >= 1 && nt < ((int64_t)1 << 31);
 }
 
-// device tables in, device results out; adds the kernels' time to *ms.  The line's tnorm holds train's norms already.
+// device tables in, device results out; adds the kernels' time to *ms.  The line's tnorm holds train's norms already, and
+// with a geometry of h_side 1 its rec train's records (train_norms); geo's tables are device memory, and the queries'
+// coordinates move with the rows.
 template <typename L>
 void match_on_device(dlco_desc_ctx *c, const typename L::Elem *q, long ldq, int64_t nq, const typename L::Elem *t, long ldt, int64_t nt, int r,
-                     int32_t *idx, typename L::Dist *sqdist, typename L::Dist *cross, double *ms)
+                     int32_t *idx, typename L::Dist *sqdist, typename L::Dist *cross, double *ms, const Geometry *geo = nullptr)
 {
     auto &b = L::bufs(c);
+    DLCO_CHECK(!geo || L::guided, DLCO_ERR_INVALID, "guided matching exists for the float line only");
     EventPair ev;
     for (int64_t q0 = 0; q0 < nq; q0 += kMatchRows) {
         const int cnt = (int)std::min(kMatchRows, nq - q0);
         const int tps = match_slicing::tiles_per_slice(L::shape, cnt, nt, c->n_cu), slices = match_slicing::slices(L::shape, nt, tps);
         b.qnorm.alloc((size_t)cnt);
         if (!cross && slices > 1) b.part.alloc((size_t)slices * cnt * 4);
+        MatchGuide guide{nullptr, nullptr, 0, 0};
+        if (geo && geo->h_side == 0) {
+            b.rec.alloc((size_t)cnt * 4);
+            guide = MatchGuide{b.rec.p, geo->txy, geo->ldt, 0};
+        } else if (geo) {
+            guide = MatchGuide{b.rec.p, geo->qxy + q0 * geo->ldq, geo->ldq, 1};
+        }
         *ms += timed_ms(c, ev, [&] {
             L::query_norms(q + q0 * ldq, ldq, cnt, r, b.qnorm.p, c->stream);
+            if (geo && geo->h_side == 0) match_records(geo->qxy + q0 * geo->ldq, geo->ldq, cnt, geo->H, geo->t2, b.rec.p, c->stream);
             L::top2(q + q0 * ldq, ldq, cnt, t, ldt, (int)nt, r, b.qnorm.p, b.tnorm.p, tps, idx ? idx + 2 * q0 : nullptr,
-                    sqdist ? sqdist + 2 * q0 : nullptr, b.part.p, cross ? cross + q0 * nt : nullptr, c->stream);
+                    sqdist ? sqdist + 2 * q0 : nullptr, b.part.p, cross ? cross + q0 * nt : nullptr, geo ? &guide : nullptr, c->stream);
         });
     }
 }
 
+// train's norms, and with a geometry of h_side 1 train's records
 template <typename L>
-double train_norms(dlco_desc_ctx *c, const typename L::Elem *t, long ldt, int64_t nt, int r)
+double train_norms(dlco_desc_ctx *c, const typename L::Elem *t, long ldt, int64_t nt, int r, const Geometry *geo = nullptr)
 {
     auto &b = L::bufs(c);
     EventPair ev;
     b.tnorm.alloc((size_t)nt);
-    return timed_ms(c, ev, [&] { L::train_norms(t, ldt, nt, r, b.tnorm.p, c->stream); });
+    const bool records = geo && geo->h_side == 1;
+    if (records) b.rec.alloc((size_t)nt * 4);
+    return timed_ms(c, ev, [&] {
+        L::train_norms(t, ldt, nt, r, b.tnorm.p, c->stream);
+        if (records) match_records(geo->txy, geo->ldt, nt, geo->H, geo->t2, b.rec.p, c->stream);
+    });
 }
 
 // the device forms: both tables where the caller has them
 template <typename L>
 void match_device(dlco_desc_ctx *c, const typename L::Elem *query_dev, long ldq, int64_t nq, const typename L::Elem *train_dev, long ldt,
-                  int64_t nt, int r, int32_t *idx_dev, typename L::Dist *sqdist_dev)
+                  int64_t nt, int r, int32_t *idx_dev, typename L::Dist *sqdist_dev, const Geometry *geo = nullptr)
 {
     DLCO_HIP(hipSetDevice(c->device));
-    double ms = train_norms<L>(c, train_dev, ldt, nt, r);
-    match_on_device<L>(c, query_dev, ldq, nq, train_dev, ldt, nt, r, idx_dev, sqdist_dev, nullptr, &ms);
+    double ms = train_norms<L>(c, train_dev, ldt, nt, r, geo);
+    match_on_device<L>(c, query_dev, ldq, nq, train_dev, ldt, nt, r, idx_dev, sqdist_dev, nullptr, &ms, geo);
     c->last_ms = ms;
 }
 
-// the host forms: train wholly in HBM, the queries a chunk at a time; cross_host: the matrix instead of the top two
+// the host forms: train wholly in HBM, the queries a chunk at a time; cross_host: the matrix instead of the top two; geo:
+// the guided form, its tables [n][2] on the host: train's go up with train, a chunk's queries' with the chunk
 template <typename L>
 void match_host(dlco_desc_ctx *c, const typename L::Elem *query_host, int64_t nq, const typename L::Elem *train_host, int64_t nt, int r,
-                int32_t *idx_host, typename L::Dist *sqdist_host, typename L::Dist *cross_host)
+                int32_t *idx_host, typename L::Dist *sqdist_host, typename L::Dist *cross_host, const Geometry *geo = nullptr)
 {
     using Elem = typename L::Elem;
     using Dist = typename L::Dist;
@@ -320,6 +360,7 @@ void match_host(dlco_desc_ctx *c, const typename L::Elem *query_host, int64_t nq
         b.query.alloc((size_t)qchunk * ld);
         if (cross_host) b.cross.alloc((size_t)qchunk * nt);
         else { b.idx.alloc((size_t)qchunk * 2); b.sqdist.alloc((size_t)qchunk * 2); }
+        if (geo) { b.txy.alloc((size_t)nt * 2); b.qxy.alloc((size_t)qchunk * 2); }
     } catch (const Error &e) {
         throw Error(DLCO_ERR_HIP, std::string(L::name) + ": the tables do not fit in device memory: " + e.what());
     }
@@ -329,15 +370,22 @@ void match_host(dlco_desc_ctx *c, const typename L::Elem *query_host, int64_t nq
                                   hipMemcpyHostToDevice, c->stream));
     };
     upload_rows(b.train.p, train_host, nt);
-    double ms = train_norms<L>(c, b.train.p, ld, nt, r);
+    Geometry dev_geo{};                                    // the same geometry on the uploaded tables
+    if (geo) {
+        dev_geo = Geometry{b.qxy.p, 2, b.txy.p, 2, geo->H, geo->t2, geo->h_side};
+        DLCO_HIP(hipMemcpyAsync(b.txy.p, geo->txy, (size_t)nt * 2 * sizeof(float), hipMemcpyHostToDevice, c->stream));
+    }
+    const Geometry *dg = geo ? &dev_geo : nullptr;
+    double ms = train_norms<L>(c, b.train.p, ld, nt, r, dg);
     for (int64_t q0 = 0; q0 < nq; q0 += qchunk) {
         const int64_t cnt = std::min(qchunk, nq - q0);
         upload_rows(b.query.p, query_host + q0 * r, cnt);
+        if (geo) DLCO_HIP(hipMemcpyAsync(b.qxy.p, geo->qxy + 2 * q0, (size_t)cnt * 2 * sizeof(float), hipMemcpyHostToDevice, c->stream));
         if (cross_host) {
-            match_on_device<L>(c, b.query.p, ld, cnt, b.train.p, ld, nt, r, nullptr, nullptr, b.cross.p, &ms);
+            match_on_device<L>(c, b.query.p, ld, cnt, b.train.p, ld, nt, r, nullptr, nullptr, b.cross.p, &ms, dg);
             DLCO_HIP(hipMemcpyAsync(cross_host + q0 * nt, b.cross.p, (size_t)cnt * nt * sizeof(Dist), hipMemcpyDeviceToHost, c->stream));
         } else {
-            match_on_device<L>(c, b.query.p, ld, cnt, b.train.p, ld, nt, r, b.idx.p, b.sqdist.p, nullptr, &ms);
+            match_on_device<L>(c, b.query.p, ld, cnt, b.train.p, ld, nt, r, b.idx.p, b.sqdist.p, nullptr, &ms, dg);
             DLCO_HIP(hipMemcpyAsync(idx_host + 2 * q0, b.idx.p, (size_t)cnt * 2 * sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
             DLCO_HIP(hipMemcpyAsync(sqdist_host + 2 * q0, b.sqdist.p, (size_t)cnt * 2 * sizeof(Dist), hipMemcpyDeviceToHost, c->stream));
         }
@@ -1000,6 +1048,58 @@ int dlco_desc_cross_sqdists(dlco_desc_ctx *c, const float *query_host, int64_t n
     return guarded(c, [&] { match_host<FloatLine>(c, query_host, nq, train_host, nt, r, nullptr, nullptr, out_host); });
 }
 
+// ---- guided matching: the nearest two among the rows a homography admits (guided_rules.hpp; the guided epilogue of the tile
+// loop in kernels_match.hip).  The float line's host path with a Geometry; the byte line has no guided form. ----------------
+namespace {
+bool guided_args_ok(const float *qxy, const float *txy, const double *H, float radius, int32_t h_side)
+{
+    if (!qxy || !txy || !H || !std::isfinite(radius) || !(radius > 0.0f) || (h_side != 0 && h_side != 1)) return false;
+    for (int i = 0; i < 9; i++)
+        if (!std::isfinite(H[i])) return false;
+    return true;
+}
+}  // namespace
+
+int dlco_desc_match_guided(dlco_desc_ctx *c, const float *query_host, const float *query_xy_host, int64_t nq, const float *train_host,
+                           const float *train_xy_host, int64_t nt, int32_t r, const double *H, float radius, int32_t h_side, int32_t *idx_host,
+                           float *sqdist_host)
+{
+    if (!c || !match_args_ok(query_host, train_host, idx_host, sqdist_host, nq, nt, r)) return DLCO_ERR_INVALID;
+    if (!guided_args_ok(query_xy_host, train_xy_host, H, radius, h_side)) return DLCO_ERR_INVALID;
+    return guarded(c, [&] {
+        const Geometry geo{query_xy_host, 2, train_xy_host, 2, H, verify_rules::threshold_sq(radius), h_side};
+        match_host<FloatLine>(c, query_host, nq, train_host, nt, r, idx_host, sqdist_host, nullptr, &geo);
+    });
+}
+
+int dlco_desc_match_guided_device(dlco_desc_ctx *c, const float *query_dev, int64_t ldq, const float *query_xy_dev, int64_t ldxy_q, int64_t nq,
+                                  const float *train_dev, int64_t ldt, const float *train_xy_dev, int64_t ldxy_t, int64_t nt, int32_t r,
+                                  const double *H, float radius, int32_t h_side, int32_t *idx_dev, float *sqdist_dev)
+{
+    if (!c || !match_args_ok(query_dev, train_dev, idx_dev, sqdist_dev, nq, nt, r)) return DLCO_ERR_INVALID;
+    if (ldq < r || ldt < r || ldq % 4 != 0 || ldt % 4 != 0) return DLCO_ERR_INVALID;
+    if (((uintptr_t)query_dev | (uintptr_t)train_dev) % 16 != 0) return DLCO_ERR_INVALID;          // 16-byte rows
+    if (!guided_args_ok(query_xy_dev, train_xy_dev, H, radius, h_side) || ldxy_q < 2 || ldxy_t < 2) return DLCO_ERR_INVALID;
+    if (((uintptr_t)query_xy_dev | (uintptr_t)train_xy_dev) % 4 != 0) return DLCO_ERR_INVALID;
+    return guarded(c, [&] {
+        const Geometry geo{query_xy_dev, (long)ldxy_q, train_xy_dev, (long)ldxy_t, H, verify_rules::threshold_sq(radius), h_side};
+        match_device<FloatLine>(c, query_dev, (long)ldq, nq, train_dev, (long)ldt, nt, r, idx_dev, sqdist_dev, &geo);
+    });
+}
+
+int dlco_desc_cross_sqdists_guided(dlco_desc_ctx *c, const float *query_host, const float *query_xy_host, int64_t nq, const float *train_host,
+                                   const float *train_xy_host, int64_t nt, int32_t r, const double *H, float radius, int32_t h_side,
+                                   float *out_host)
+{
+    if (!c || !match_args_ok(query_host, train_host, out_host, out_host, nq, nt, r)) return DLCO_ERR_INVALID;
+    if (nq > ((int64_t)1 << 28) / nt) return DLCO_ERR_INVALID;
+    if (!guided_args_ok(query_xy_host, train_xy_host, H, radius, h_side)) return DLCO_ERR_INVALID;
+    return guarded(c, [&] {
+        const Geometry geo{query_xy_host, 2, train_xy_host, 2, H, verify_rules::threshold_sq(radius), h_side};
+        match_host<FloatLine>(c, query_host, nq, train_host, nt, r, nullptr, nullptr, out_host, &geo);
+    });
+}
+
 // ---- verification: a homography between the two sides of a match list (verify_rules.hpp, kernels_verify.hip) ---------------
 namespace {
 bool verify_args_ok(const float *src, const float *dst, int64_t m, float threshold, int32_t n_hyp)
@@ -1183,7 +1283,8 @@ int dlco_desc_cross_sqdists_u8(dlco_desc_ctx *c, const uint8_t *query_u8, int64_
 
 // milliseconds the kernels of the last dlco_desc_compute* / dlco_desc_describe* call took (HIP events): transform and
 // pooling, plus the projection for describe and the sampling for the keypoint calls (extract_patches: the sampling alone);
-// the pair calls add their distance kernel; after a match call, float or byte, its kernels (norms, top two, merge); the _u8
+// the pair calls add their distance kernel; after a match call, float or byte, its kernels (norms, top two, merge, and for
+// the guided forms the record kernel); the _u8
 // forms of describe add their quantising kernel; after an orient call the orientation kernel and the integral image when the
 // call formed it; after a detect call the detector's kernels (the integral image when the call
 // formed it, the octaves, the selection); after a verify call the verify kernels (hypotheses, scoring, selection, and for

@@ -524,8 +524,13 @@ void desc_full_dist(const float *desc, long ld, int n_groups, int n_pairs, float
 void desc_project(const float *desc, long desc_ld, int n, const float *W, int r, int F, float *Y, long y_ld, hipStream_t s);
 void desc_pair_sqdist(const float *Y, long ld, int r, const int32_t *pairs, long n_pairs, float *dist, uint8_t *label, hipStream_t s);
 void match_norms(const float *x, long ld, long n, int r, double *norm, hipStream_t s);
+// The geometry of a guided launch (the rule is guided_rules.hpp): rec [n][4] doubles, the records of the rows of the side the
+// homography applies to (match_records; 16-byte aligned), and xy, the (x, y) floats of the other side's rows at a pitch of
+// ldxy floats.  h_side 0: rec belongs to the launch's queries and xy to train; h_side 1: rec to train and xy to the queries.
+struct MatchGuide { const double *rec; const float *xy; long ldxy; int h_side; };
+void match_records(const float *xy, long ld, long n, const double H[9], double t2, double *rec, hipStream_t s);
 void match_top2(const float *query, long ldq, int nq, const float *train, long ldt, int nt, int r, const double *qnorm, const double *tnorm,
-                int tiles_per_slice, int32_t *idx, float *sqdist, void *part, float *out, hipStream_t s);
+                int tiles_per_slice, int32_t *idx, float *sqdist, void *part, float *out, const MatchGuide *guide, hipStream_t s);
 // byte descriptors (kernels_match_u8.hip; the quantiser is quant_rules.hpp): float rows to bytes, and the match of byte tables
 void desc_quantize_rows(const float *Y, long ldy, int n, int r, float scale, const float *offset, uint8_t *out, long ldo, hipStream_t s);
 void match_u8_norms(const uint8_t *x, long ld, long n, int r, bool negate, int32_t *norm, hipStream_t s);

@@ -8,6 +8,16 @@
 //                         are read, a train tile when it is stored to LDS), rounded to float once; then either the running top two per query
 //                         under the key (float distance, train index), or (STORE) the matrix itself: one tile loop, two
 //                         epilogues, so the matrix and the top two cannot disagree
+//   match_records_kernel  the guided forms (dlco_desc_match_guided, guided_rules.hpp): the record (X, Y, W, T) of every row
+//                         of the side the homography applies to, one lane per row
+//   match_top2_kernel<.., GUIDED>   the same tile loop with a third epilogue: a candidate enters the running top two only
+//                         if guided_rules::admits says so, and STORE writes +inf for one that is not admitted.  GUIDED = 1:
+//                         the queries carry records (h_side 0) and a train tile brings its (x, y), 16 bytes a row, staged
+//                         beside Tn; GUIDED = 2: the train rows carry records, 32 bytes a row, and the queries their (x, y).
+//                         The workgroup's queries' geometry sits in LDS, and a lane keeps the verdicts of a pair of column
+//                         blocks as a bit mask.  Distance, key, merge and slices are those of the plain form, so a guided answer is the top two of the plain matrix with +inf where the
+//                         predicate fails.  The predicate's arithmetic is reached through guided_rules.hpp alone, which
+//                         switches contraction off.
 //   match_merge_kernel    the top two of a query over the S slices of train, under the same key (the slicing rule:
 //                         match_slices.hpp)
 //
@@ -19,6 +29,7 @@
 // ceil(r / 4) * 4 <= ld, the elements at and beyond r are replaced by zeros.  Every load is unconditional and in
 // bounds (a row or piece beyond the edge reads a valid one and is replaced by zeros), stores are masked.
 #include "dlco_internal.hpp"
+#include "guided_rules.hpp"
 #include "match_slices.hpp"
 
 namespace dlco {
@@ -64,14 +75,18 @@ __device__ __forceinline__ Top2 merge2(const Top2 a, const Top2 b)
     return o;
 }
 
-template <bool STORE, bool MULTI>
+template <bool STORE, bool MULTI, int GUIDED>
 __global__ __launch_bounds__(MTH) void match_top2_kernel(const float *__restrict__ query, long ldq, int nq, const float *__restrict__ train, long ldt,
                                                          int nt, int r, const double *__restrict__ qnorm, const double *__restrict__ tnorm,
                                                          int tiles_per_slice, int32_t *__restrict__ idx, float *__restrict__ sqdist,
-                                                         i32x4 *__restrict__ part, float *__restrict__ out)
+                                                         i32x4 *__restrict__ part, float *__restrict__ out, const MatchGuide g)
 {
+    constexpr int CW = GUIDED == 2 ? 4 : 2;                // doubles of geometry a train row brings: (x, y) or a record
+    constexpr int QW = GUIDED == 1 ? 4 : 2;                // and a query
     __shared__ double Bs[TN * MP];                         // the staged tile, widened to double once, when it is stored
     __shared__ double Tn[TN];
+    __shared__ __attribute__((aligned(16))) double Tg[GUIDED ? TN * CW : 1];            // GUIDED: the tile's geometry, staged with it,
+    __shared__ __attribute__((aligned(16))) double Qg[GUIDED ? MQ * QW : 1];            // and the workgroup's queries': written once, before the loop
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int li = lane & 15, lg = lane >> 4;
     const int q0 = blockIdx.x * MQ + wave * 16;
@@ -96,6 +111,7 @@ __global__ __launch_bounds__(MTH) void match_top2_kernel(const float *__restrict
     const int lrow = tid >> 5, lseg = tid & 31;
     f32x4 rb[NSUB];
     double rtn;
+    double rg[CW];
     auto gload = [&](int step) {
         step = min(step, nstep - 1);                       // past the end: the last step again, never used
         const int tile = step / nch, kc = step - tile * nch;
@@ -110,7 +126,16 @@ __global__ __launch_bounds__(MTH) void match_top2_kernel(const float *__restrict
             rb[u] = mask_k(v, k, ok);
         }
         const long jn = jt + (tid & (TN - 1));
-        rtn = tnorm[jn < jend ? jn : (long)jbeg];
+        const long js = jn < jend ? jn : (long)jbeg;
+        rtn = tnorm[js];
+        if constexpr (GUIDED == 1) {
+            const float *p = g.xy + js * g.ldxy;
+            rg[0] = (double)p[0]; rg[1] = (double)p[1];
+        }
+        if constexpr (GUIDED == 2) {
+            const f64x2 a = *reinterpret_cast<const f64x2 *>(g.rec + 4 * js), b = *reinterpret_cast<const f64x2 *>(g.rec + 4 * js + 2);
+            rg[0] = a[0]; rg[1] = a[1]; rg[2] = b[0]; rg[3] = b[1];
+        }
     };
     auto lstore = [&]() {
 #pragma unroll
@@ -119,7 +144,28 @@ __global__ __launch_bounds__(MTH) void match_top2_kernel(const float *__restrict
             *reinterpret_cast<f64x2 *>(dst) = f64x2{(double)rb[u][0], (double)rb[u][1]};
             *reinterpret_cast<f64x2 *>(dst + 2) = f64x2{(double)rb[u][2], (double)rb[u][3]};
         }
-        if (tid < TN) Tn[tid] = rtn;
+        if (tid < TN) {
+            Tn[tid] = rtn;
+            if constexpr (GUIDED != 0) {
+#pragma unroll
+                for (int e = 0; e < CW; e += 2) *reinterpret_cast<f64x2 *>(&Tg[tid * CW + e]) = f64x2{rg[e], rg[e + 1]};
+            }
+        }
+    };
+    // the geometry of column c of the staged tile
+    struct ColGeom { double v[CW]; };
+    auto cload = [&](int c) {
+        ColGeom o;
+        if constexpr (GUIDED != 0) {
+#pragma unroll
+            for (int e = 0; e < CW; e += 2) {
+                const f64x2 t = *reinterpret_cast<const f64x2 *>(&Tg[c * CW + e]);
+                o.v[e] = t[0]; o.v[e + 1] = t[1];
+            }
+        } else {
+            o.v[0] = o.v[1] = 0.0;
+        }
+        return o;
     };
 
     // A fragments of one k chunk: lane (li, lg) holds query q0 + li at k = 16 c + 4 lg + s, s = element of fa[c]
@@ -143,6 +189,50 @@ __global__ __launch_bounds__(MTH) void match_top2_kernel(const float *__restrict
         const int row = q0 + lg + 4 * rr;
         qn[rr] = qnorm[row < nq ? row : 0];
     }
+    // GUIDED: the geometry of the workgroup's queries, the record of a query (1) or its (x, y) (2), goes to LDS (the first
+    // barrier of the loop below orders it) and is read again for every pair of column blocks: four rows' records held in
+    // registers over the loop would put the kernel into scratch
+    if constexpr (GUIDED != 0) {
+        if (tid < MQ) {
+            const long row = (long)blockIdx.x * MQ + tid;
+            const long rs = row < nq ? row : 0;
+            if constexpr (GUIDED == 1) {
+                *reinterpret_cast<f64x2 *>(&Qg[tid * 4]) = *reinterpret_cast<const f64x2 *>(g.rec + 4 * rs);
+                *reinterpret_cast<f64x2 *>(&Qg[tid * 4 + 2]) = *reinterpret_cast<const f64x2 *>(g.rec + 4 * rs + 2);
+            } else {
+                const float *p = g.xy + rs * g.ldxy;
+                *reinterpret_cast<f64x2 *>(&Qg[tid * 2]) = f64x2{(double)p[0], (double)p[1]};
+            }
+        }
+    }
+    // GUIDED: which of the eight entries of the column blocks at c0 and c0 + 16 of the staged tile the rule admits, bit e as
+    // prev_entry counts them.  One burst of LDS reads and fp64 VALU work per pair of blocks, whose only result that lives
+    // on is the mask.  The empty asm hides from the compiler that the queries' address does not change over the tile loop:
+    // hoisted out of it, their geometry would sit in registers again.
+    auto admit_mask = [&](int c0) -> unsigned {
+        unsigned m = 0xffu;
+        if constexpr (GUIDED != 0) {
+            int qoff = (wave * 16 + lg) * QW;
+            asm volatile("" : "+v"(qoff));
+            const ColGeom a = cload(c0), b = cload(c0 + 16);
+            m = 0;
+#pragma unroll
+            for (int rr = 0; rr < 4; rr++) {
+                const double *q = &Qg[qoff + 4 * rr * QW];
+                if constexpr (GUIDED == 1) {
+                    const f64x2 q0v = *reinterpret_cast<const f64x2 *>(q), q1v = *reinterpret_cast<const f64x2 *>(q + 2);
+                    const guided_rules::Rec rec{q0v[0], q0v[1], q1v[0], q1v[1]};
+                    m |= (guided_rules::admits(rec, a.v[0], a.v[1]) ? 1u : 0u) << rr;
+                    m |= (guided_rules::admits(rec, b.v[0], b.v[1]) ? 1u : 0u) << (4 + rr);
+                } else {
+                    const f64x2 uv = *reinterpret_cast<const f64x2 *>(q);
+                    m |= (guided_rules::admits(guided_rules::Rec{a.v[0], a.v[1], a.v[2], a.v[3]}, uv[0], uv[1]) ? 1u : 0u) << rr;
+                    m |= (guided_rules::admits(guided_rules::Rec{b.v[0], b.v[1], b.v[2], b.v[3]}, uv[0], uv[1]) ? 1u : 0u) << (4 + rr);
+                }
+            }
+        }
+        return m;
+    };
     // running (best, second) of the columns == li (mod 16) for each of the four rows; a lane meets its columns in
     // ascending order, so a strict comparison keeps the smaller index among equal distances
     const float inf = __builtin_inff();
@@ -150,17 +240,19 @@ __global__ __launch_bounds__(MTH) void match_top2_kernel(const float *__restrict
     i32x4 bj1 = i32x4{-1, -1, -1, -1}, bj2 = bj1;
 
     // one entry of a 16 x 16 result: row q0 + lg + 4 rr against train row jl, whose squared norm is tn
-    auto entry = [&](double dot, int rr, double tn, long jl) {
+    auto entry = [&](double dot, int rr, double tn, long jl, unsigned mask, int e) {
         const bool j_ok = jl < jend;
+        const bool adm = GUIDED == 0 || ((mask >> e) & 1u) != 0;
         const int j = (int)jl;
         double d = __builtin_fma(-2.0, dot, qn[rr] + tn);
         d = __builtin_fmax(d, 0.0);
         const float f = (float)d;
         if (STORE) {
             const int row = q0 + lg + 4 * rr;
-            if (j_ok && row < nq) out[(long)row * nt + j] = f;
+            if (j_ok && row < nq) out[(long)row * nt + j] = adm ? f : inf;
         } else {
-            const bool first = j_ok && f < bd1[rr], second = j_ok && f < bd2[rr];
+            const bool in = j_ok && adm;
+            const bool first = in && f < bd1[rr], second = in && f < bd2[rr];
             bd2[rr] = first ? bd1[rr] : (second ? f : bd2[rr]);
             bj2[rr] = first ? bj1[rr] : (second ? j : bj2[rr]);
             bd1[rr] = first ? f : bd1[rr];
@@ -171,10 +263,11 @@ __global__ __launch_bounds__(MTH) void match_top2_kernel(const float *__restrict
     // next pair of blocks, one entry per 16-wide k group, so that it runs beside them instead of after them.
     f64x4 p0 = f64x4{0.0, 0.0, 0.0, 0.0}, p1 = p0;
     double ptn0 = 0.0, ptn1 = 0.0;
+    unsigned pm = 0;
     long pj = jend;                                        // no block yet: jl >= jend masks every entry
     auto prev_entry = [&](int e) {
-        if (e < 4) entry(p0[e], e, ptn0, pj);
-        else entry(p1[e - 4], e - 4, ptn1, pj + 16);
+        if (e < 4) entry(p0[e], e, ptn0, pj, pm, e);
+        else entry(p1[e - 4], e - 4, ptn1, pj + 16, pm, e);
     };
     // the k chunk in LDS against the A fragments, for the column blocks sub and sub + 1: two independent MFMA chains
     // over the nc 16-wide k groups that hold a k below r
@@ -216,10 +309,11 @@ __global__ __launch_bounds__(MTH) void match_top2_kernel(const float *__restrict
                     mfma_pair(sub, acc[sub], acc[sub + 1], false);
                     if (kc == nch - 1) {
                         const long jl = (long)jbeg + (long)tile * TN + 16 * sub + li;
+                        const unsigned m = admit_mask(16 * sub + li);
 #pragma unroll
                         for (int rr = 0; rr < 4; rr++) {
-                            entry(acc[sub][rr], rr, Tn[16 * sub + li], jl);
-                            entry(acc[sub + 1][rr], rr, Tn[16 * sub + 16 + li], jl + 16);
+                            entry(acc[sub][rr], rr, Tn[16 * sub + li], jl, m, rr);
+                            entry(acc[sub + 1][rr], rr, Tn[16 * sub + 16 + li], jl + 16, m, 4 + rr);
                         }
                     }
                 }
@@ -230,6 +324,7 @@ __global__ __launch_bounds__(MTH) void match_top2_kernel(const float *__restrict
                     mfma_pair(sub, acc[0], acc[1], true);
                     p0 = acc[0]; p1 = acc[1];
                     ptn0 = Tn[16 * sub + li]; ptn1 = Tn[16 * sub + 16 + li];
+                    pm = admit_mask(16 * sub + li);
                     pj = (long)jbeg + (long)step * TN + 16 * sub + li;
                 }
             }
@@ -279,6 +374,18 @@ __global__ __launch_bounds__(256) void match_merge_kernel(const i32x4 *__restric
     sqdist[2 * (long)row] = me.d1; sqdist[2 * (long)row + 1] = me.d2;
 }
 
+// the records of n rows (x, y) = xy[i * ld], xy[i * ld + 1] under H: rec [n][4] = (X, Y, W, T), one lane per row
+struct H9 { double h[9]; };
+__global__ __launch_bounds__(256) void match_records_kernel(const float *__restrict__ xy, long ld, long n, const H9 H, double t2,
+                                                            double *__restrict__ rec)
+{
+    const long i = (long)blockIdx.x * 256 + threadIdx.x;
+    if (i >= n) return;
+    const guided_rules::Rec r = guided_rules::record(H.h, (double)xy[i * ld], (double)xy[i * ld + 1], t2);
+    *reinterpret_cast<f64x2 *>(rec + 4 * i) = f64x2{r.X, r.Y};
+    *reinterpret_cast<f64x2 *>(rec + 4 * i + 2) = f64x2{r.W, r.T};
+}
+
 constexpr int NTH = 256;               // four rows per workgroup, one wave each
 
 __global__ __launch_bounds__(NTH) void match_norms_kernel(const float *__restrict__ x, long ld, long n, int r, double *__restrict__ norm)
@@ -304,21 +411,39 @@ void match_norms(const float *x, long ld, long n, int r, double *norm, hipStream
     DLCO_HIP(hipGetLastError());
 }
 
+void match_records(const float *xy, long ld, long n, const double H[9], double t2, double *rec, hipStream_t s)
+{
+    if (n <= 0) return;
+    H9 h;
+    for (int i = 0; i < 9; i++) h.h[i] = H[i];
+    hipLaunchKernelGGL(match_records_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, xy, ld, n, h, t2, rec);
+    DLCO_HIP(hipGetLastError());
+}
+
 // query [nq][ldq], train [nt][ldt], norms from match_norms.  out != nullptr: the matrix out[nq][nt]; else idx / sqdist
-// [nq][2], through part [slices][nq] (16 bytes each) when the tiles_per_slice leaves more than one slice.
+// [nq][2], through part [slices][nq] (16 bytes each) when the tiles_per_slice leaves more than one slice.  guide: nullptr, or
+// the geometry of the guided form (dlco_internal.hpp).
 void match_top2(const float *query, long ldq, int nq, const float *train, long ldt, int nt, int r, const double *qnorm, const double *tnorm,
-                int tiles_per_slice, int32_t *idx, float *sqdist, void *part, float *out, hipStream_t s)
+                int tiles_per_slice, int32_t *idx, float *sqdist, void *part, float *out, const MatchGuide *guide, hipStream_t s)
 {
     if (nq <= 0 || nt <= 0) return;
     const int slices = match_slicing::slices(match_slicing::kFloat, nt, tiles_per_slice);
     const dim3 grid((unsigned)((nq + MQ - 1) / MQ), (unsigned)slices);
     i32x4 *pp = (!out && slices > 1) ? static_cast<i32x4 *>(part) : nullptr;
     const bool multi = r > KC;
-#define DLCO_MATCH_LAUNCH(ST, MU)                                                                                                     \
-    hipLaunchKernelGGL((match_top2_kernel<ST, MU>), grid, dim3(MTH), 0, s, query, ldq, nq, train, ldt, nt, r, qnorm, tnorm, tiles_per_slice, \
-                       idx, sqdist, pp, out)
-    if (out) { if (multi) DLCO_MATCH_LAUNCH(true, true); else DLCO_MATCH_LAUNCH(true, false); }
-    else     { if (multi) DLCO_MATCH_LAUNCH(false, true); else DLCO_MATCH_LAUNCH(false, false); }
+    const MatchGuide g = guide ? *guide : MatchGuide{nullptr, nullptr, 0, 0};
+#define DLCO_MATCH_LAUNCH(ST, MU, GU)                                                                                                 \
+    hipLaunchKernelGGL((match_top2_kernel<ST, MU, GU>), grid, dim3(MTH), 0, s, query, ldq, nq, train, ldt, nt, r, qnorm, tnorm,       \
+                       tiles_per_slice, idx, sqdist, pp, out, g)
+#define DLCO_MATCH_FORM(GU)                                                                                                           \
+    do {                                                                                                                              \
+        if (out) { if (multi) DLCO_MATCH_LAUNCH(true, true, GU); else DLCO_MATCH_LAUNCH(true, false, GU); }                           \
+        else     { if (multi) DLCO_MATCH_LAUNCH(false, true, GU); else DLCO_MATCH_LAUNCH(false, false, GU); }                         \
+    } while (0)
+    if (!guide) DLCO_MATCH_FORM(0);
+    else if (g.h_side == 0) DLCO_MATCH_FORM(1);
+    else DLCO_MATCH_FORM(2);
+#undef DLCO_MATCH_FORM
 #undef DLCO_MATCH_LAUNCH
     DLCO_HIP(hipGetLastError());
     if (pp) {

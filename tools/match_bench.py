@@ -6,7 +6,12 @@ the thing a user would write without this call, the time of a chunked float64 to
 
 With --u8 the same tables are quantised to bytes (one scale, per-dimension offsets fitted on both, as dlco_desc_quant_fit
 does) and dlco_desc_match_u8_device is timed the same way; the line shows the float call's time of the same shape from the
-same run beside it, the int8 MFMA floor 2 nq nt r / 5.0 POP/s (twice the dense BF16 peak of 2.5 PF) and the share of it."""
+same run beside it, the int8 MFMA floor 2 nq nt r / 5.0 POP/s (twice the dense BF16 peak of 2.5 PF) and the share of it.
+
+With --guided the rows get keypoints, uniform in a square of side 8 sqrt(nt) (one per 64 px^2), a mild homography and radius
+12 (about seven admitted train rows a query), and dlco_desc_match_guided_device is timed for both h_side beside the plain
+call: one warm-up each, then three rounds that alternate plain, h_side 0, h_side 1.  The line shows the three times, the
+guided calls' ratio to the plain one and their share of the f64 MFMA floor, and how many queries found two admitted rows."""
 import importlib, os, sys
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch
@@ -17,6 +22,9 @@ PEAK_I8 = 5.0e15
 U8 = "--u8" in sys.argv
 if U8:
     sys.argv.remove("--u8")
+GUIDED = "--guided" in sys.argv
+if GUIDED:
+    sys.argv.remove("--guided")
 SHAPES = [(2048, 2048, 64), (8192, 8192, 64), (8192, 8192, 128), (100000, 100000, 128)]
 if len(sys.argv) > 1:
     SHAPES = [tuple(int(v) for v in a.split(",")) for a in sys.argv[1:]]
@@ -46,6 +54,33 @@ for nq, nt, r in SHAPES:
     d = torch.empty((nq, 2), dtype=torch.float32, device="cuda:0")
     torch.cuda.synchronize()
     call = lambda: ctx.match_device(Q.data_ptr(), nq, T.data_ptr(), nt, r, idx.data_ptr(), d.data_ptr())
+    if GUIDED:
+        import numpy as np
+        S = 8.0 * nt ** 0.5
+        H = np.array([[0.98, -0.05, 0.03 * S], [0.04, 1.02, -0.02 * S], [0.02 / S, -0.01 / S, 1.0]])
+        txy = torch.rand((nt, 2), device="cuda:0", generator=gen) * S
+        qxy = torch.rand((nq, 2), device="cuda:0", generator=gen) * S
+        gi = [torch.empty((nq, 2), dtype=torch.int32, device="cuda:0") for _ in range(2)]
+        gd = [torch.empty((nq, 2), dtype=torch.float32, device="cuda:0") for _ in range(2)]
+        torch.cuda.synchronize()
+        calls = [call] + [lambda h=h: ctx.match_guided_device(Q.data_ptr(), qxy.data_ptr(), nq, T.data_ptr(), txy.data_ptr(), nt, r, H, gi[h].data_ptr(),
+                                                              gd[h].data_ptr(), radius=12.0, h_side=h) for h in (0, 1)]
+        for f in calls:
+            f()
+        ms3 = [[], [], []]
+        for _ in range(3):
+            for k, f in enumerate(calls):
+                f()
+                ms3[k].append(ctx.last_kernel_ms())
+        best, floor = [min(m) for m in ms3], 1e3 * 2.0 * nq * nt * r / PEAK
+        two = [100 * float((g[:, 1] >= 0).float().mean()) for g in gi]
+        fmt = lambda m: " ".join("%.3f" % v for v in m)
+        print(f"match_guided {nq} x {nt} r {r}: plain {best[0]:.3f} ms (rounds {fmt(ms3[0])}), h_side 0 {best[1]:.3f} ms (rounds {fmt(ms3[1])}), "
+              f"h_side 1 {best[2]:.3f} ms (rounds {fmt(ms3[2])}); guided / plain {best[1] / best[0]:.3f} and {best[2] / best[0]:.3f}; f64 MFMA floor "
+              f"{floor:.3f} ms, share of the floor: plain {floor / best[0]:.3f}, guided {floor / best[1]:.3f} and {floor / best[2]:.3f}; two admitted rows "
+              f"for {two[0]:.1f} % and {two[1]:.1f} % of the queries", flush=True)
+        del T, Q, idx, d, txy, qxy, gi, gd
+        continue
     call()
     ms = []
     for _ in range(2):
