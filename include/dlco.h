@@ -658,7 +658,8 @@ int dlco_desc_cross_sqdists_u8(dlco_desc_ctx *ctx, const uint8_t *query_u8, int6
  * mask all zero.
  *   DLCO_ERR_INVALID, before the handle is used and with no output touched: a null handle, a required pointer NULL, m < 4 or
  * m >= 2^31, a threshold that is not finite or <= 0, n_hyp outside 1 .. 2^20, refine outside 0 .. 8.
- *   Out of scope: a device-memory form (the match list is filtered on the host); a fundamental or essential matrix;
+ *   Out of scope of this call: a device-memory form (the match list is filtered on the host); a fundamental or essential matrix
+ * (the fundamental matrix has calls of its own, dlco_desc_verify_fundamental below; an essential matrix has none);
  * symmetric transfer error; an adaptive hypothesis count. */
 int  dlco_desc_verify_homography(dlco_desc_ctx *ctx, const float *src_xy_host, const float *dst_xy_host, int64_t m, float threshold,
                                  int32_t n_hyp, uint64_t seed, int32_t refine, double *H_out, uint8_t *inlier_host, int64_t *n_inliers,
@@ -667,14 +668,36 @@ int  dlco_desc_verify_homography(dlco_desc_ctx *ctx, const float *src_xy_host, c
  * tools, what dlco_desc_cross_sqdists is to the matcher */
 int  dlco_desc_verify_hypotheses(dlco_desc_ctx *ctx, const float *src_xy_host, const float *dst_xy_host, int64_t m, float threshold,
                                  int32_t n_hyp, uint64_t seed, double *H_all_host, int32_t *count_host);
+/* ---- The same verification against a fundamental matrix F, x'^T F x = 0 with x = (x, y, 1) of src and x' = (u, v, 1) of dst:
+ * the model of a camera that moves in front of a scene with depth, where a homography keeps one plane only.
+ * csrc/epipolar_rules.hpp states the rule: n_hyp hypotheses from eight matches each (the same sampler), the linear eight-point
+ * system of locally normalised points solved by Gaussian elimination with complete pivoting, scored on the device by the
+ * Sampson error without a division, e^2 <= threshold^2 S with S > 0, the same selection, then at most `refine` rounds on the
+ * host: Hartley normalisation, the smallest eigenvector of the 9 x 9 normal matrix by a cyclic Jacobi rule, the nearest
+ * rank-2 matrix, scored on the device.  The device path is IEEE double + - x / without fused multiply-add, the host adds
+ * sqrt: the answer is the same in every bit on every machine.  It is NOT cv::findFundamentalMat.
+ *   The arguments, the optional outputs, "no model" and DLCO_ERR_INVALID are dlco_desc_verify_homography's, except m >= 8.
+ * F_out [9] row-major, max |F| in [1, 2), its first entry of that magnitude positive.  With refine = 0, or when no round was
+ * accepted, F is the linear eight-point hypothesis, which need not be singular; after an accepted round it is of rank 2 up to
+ * rounding.
+ *   Degeneracy is documented and not detected: matches related by a homography (a plane, a camera that only rotates, a
+ * shifted image) satisfy a three-dimensional family of F, and the call returns some member of it.
+ *   Out of scope: a choice between H and F; a seven-point solver; an essential matrix; an epipolar predicate for guided
+ * matching; an adaptive hypothesis count. */
+int  dlco_desc_verify_fundamental(dlco_desc_ctx *ctx, const float *src_xy_host, const float *dst_xy_host, int64_t m, float threshold,
+                                  int32_t n_hyp, uint64_t seed, int32_t refine, double *F_out, uint8_t *inlier_host, int64_t *n_inliers,
+                                  int32_t *best_hyp);
+/* every hypothesis of that call and its inlier count, F_all [n_hyp][9] (all zero: invalid) and count [n_hyp] */
+int  dlco_desc_verify_fundamental_hypotheses(dlco_desc_ctx *ctx, const float *src_xy_host, const float *dst_xy_host, int64_t m,
+                                             float threshold, int32_t n_hyp, uint64_t seed, double *F_all_host, int32_t *count_host);
 /* HIP-event time of the kernels of the last compute / describe call (transform, pooling, projection, and the sampling
  * for the keypoint calls; extract_patches: the sampling alone); the pair_sqdists /
  * pair_stats calls add their distance kernel; after a match / cross_sqdists call, float or _u8, the time of its kernels
  * (norms, tile loop, merge of the slices, and for the guided forms the kernel that writes the records); the _u8 forms of describe add their quantising kernel; after a detect call the
  * detector's kernels (the integral image when the call formed it, the octaves, the selection; detect_oriented adds the
  * orientation kernel); after an orient call the orientation kernel and the integral image when the call formed it; after a
- * verify call the verify kernels (hypotheses, scoring, selection; verify_homography adds the mask kernel of the best model and
- * of every refit round) */
+ * verify call the verify kernels (hypotheses, scoring, selection, of either model; verify_homography and verify_fundamental add
+ * the mask kernel of the best model and of every refit round) */
 double dlco_desc_last_kernel_ms(const dlco_desc_ctx *ctx);
 
 #ifdef __cplusplus

@@ -194,6 +194,8 @@ def load():
     f64p = C.POINTER(C.c_double)
     L.dlco_desc_verify_homography.argtypes = [vp, f32p, f32p, i64, C.c_float, C.c_int32, C.c_uint64, C.c_int32, f64p, u8p, i64p, i32p]
     L.dlco_desc_verify_hypotheses.argtypes = [vp, f32p, f32p, i64, C.c_float, C.c_int32, C.c_uint64, f64p, i32p]
+    L.dlco_desc_verify_fundamental.argtypes = L.dlco_desc_verify_homography.argtypes
+    L.dlco_desc_verify_fundamental_hypotheses.argtypes = L.dlco_desc_verify_hypotheses.argtypes
     L.dlco_desc_match_guided.argtypes = [vp, f32p, f32p, i64, f32p, f32p, i64, C.c_int32, f64p, C.c_float, C.c_int32, i32p, f32p]
     L.dlco_desc_match_guided_device.argtypes = [vp, vp, i64, vp, i64, i64, vp, i64, vp, i64, i64, C.c_int32, f64p, C.c_float,
                                                 C.c_int32, vp, vp]
@@ -977,6 +979,30 @@ class DescContext:
         self._ck(self.L.dlco_desc_verify_hypotheses(self.h, _p(s, f32p), _p(d, f32p), s.shape[0], threshold, n_hyp, seed,
                                                     _p(H_all, C.POINTER(C.c_double)), _p(count, i32p)))
         return H_all, count
+
+    # ---- the same against a fundamental matrix (csrc/epipolar_rules.hpp states the rule) ----
+    def verify_fundamental(self, src, dst, threshold=1.0, n_hyp=2048, seed=0, refine=2):
+        """The fundamental matrix F, dst^T F src = 0, of the matches src [m,2] -> dst [m,2] (m >= 8) by the library's
+        deterministic eight-point RANSAC: (F [3,3] f64 with max |F| in [1, 2), inlier [m] bool, best_hyp).  F is of rank 2 up to
+        rounding once a refit round was accepted, the linear eight-point hypothesis otherwise.  No model: F and inlier all
+        zero, best_hyp = -1."""
+        s, d = self._match_points(src, dst)
+        m = s.shape[0]
+        F, mask = np.zeros((3, 3), np.float64), np.zeros(m, np.uint8)
+        n, best = C.c_int64(), C.c_int32()
+        self._ck(self.L.dlco_desc_verify_fundamental(self.h, _p(s, f32p), _p(d, f32p), m, threshold, n_hyp, seed, refine,
+                                                     _p(F, C.POINTER(C.c_double)), _p(mask, u8p), C.byref(n), C.byref(best)))
+        assert n.value == int(mask.sum())
+        return F, mask.astype(bool), best.value
+
+    def verify_fundamental_hypotheses(self, src, dst, threshold=1.0, n_hyp=2048, seed=0):
+        """Every hypothesis of verify_fundamental and its inlier count: (F_all [n_hyp,3,3] f64, all zero where invalid,
+        count [n_hyp] int32)."""
+        s, d = self._match_points(src, dst)
+        F_all, count = np.zeros((n_hyp, 3, 3), np.float64), np.zeros(n_hyp, np.int32)
+        self._ck(self.L.dlco_desc_verify_fundamental_hypotheses(self.h, _p(s, f32p), _p(d, f32p), s.shape[0], threshold, n_hyp, seed,
+                                                                _p(F_all, C.POINTER(C.c_double)), _p(count, i32p)))
+        return F_all, count
 
     def match_device(self, q_ptr, nq, t_ptr, nt, r, idx_ptr, d_ptr, ldq=None, ldt=None):
         """match on tables in device memory (row pitches ldq, ldt: multiples of 4, default r); results to device memory."""

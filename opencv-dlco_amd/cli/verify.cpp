@@ -1,6 +1,7 @@
 // verify — geometric verification of a match list, over libdlco.so: the end of detect -> describe-image -> match.
 //
 //     verify query_kp_file train_kp_file match_file -out dst [-thresh f] [-hyp n] [-seed n] [-refine n] [-device n]
+//            [-model homography|fundamental]
 //
 // The two keypoint files hold "Keypoints" [n,4] f32 as `detect` writes them, match_file holds "Matches" [m,2] i32 =
 // (query, train) as `match` writes them.  The (x, y) columns of the matched keypoints go to the library's deterministic
@@ -14,6 +15,10 @@
 //     "BestHypothesis" [1] i32      the winning hypothesis, -1: no model (H and Inlier are zero)
 // and prints "Matches: m", "Inliers: k / m", "Hypothesis: h".  Fewer than 4 matches give the no-model result without a device.
 // An index of "Matches" outside its keypoint table is an error before a device is opened.
+// With -model fundamental the model is a fundamental matrix F, train^T F query = 0 (dlco_desc_verify_fundamental; the rule:
+// csrc/epipolar_rules.hpp; it is not cv::findFundamentalMat): -thresh bounds the Sampson error, and the first two datasets
+// are "Fundamental" [3,3] f32 and "FundamentalBits" [9] i64 instead.  Fewer than 8 matches give the no-model result.  Without
+// the option the tool does what it did before the option existed.
 // The reference has no such tool.  A path that does not end in .h5/.hdf5 is a directory of .npy files with the same
 // dataset names (dlco_io.hpp).
 #include "../../include/dlco.h"
@@ -42,7 +47,7 @@ int main(int argc, char **argv)
     long long n_hyp = 2048, refine = 2;
     unsigned long long seed = 0;
     float thresh = 3.0f;
-    bool help = false;
+    bool help = false, fundamental = false, model_given = false;
     const char *qf = nullptr, *tf = nullptr, *mf = nullptr, *out = nullptr;
     for (int i = 1; i < argc; i++) {
         if (argv[i][0] == '-') {
@@ -54,6 +59,15 @@ int main(int argc, char **argv)
             if (std::strcmp(argv[i], "-seed") == 0 && has_val) { seed = strtoull(argv[++i], nullptr, 0); continue; }
             if (std::strcmp(argv[i], "-refine") == 0 && has_val) { refine = atoll(argv[++i]); continue; }
             if (std::strcmp(argv[i], "-device") == 0 && has_val) { device = atoi(argv[++i]); continue; }
+            if (std::strcmp(argv[i], "-model") == 0 && has_val) {
+                const char *name = argv[++i];
+                model_given = true;
+                if (std::strcmp(name, "fundamental") == 0) { fundamental = true; continue; }
+                if (std::strcmp(name, "homography") == 0) { fundamental = false; continue; }
+                cout << "ERROR: -model must be homography or fundamental." << endl;
+                help = true;
+                continue;
+            }
             cout << "ERROR: Invalid " << argv[i] << " option." << endl;
             help = true;
         } else {
@@ -70,6 +84,7 @@ int main(int argc, char **argv)
     if (help) {
         cout << endl;
         cout << "Usage: verify query_kp_file train_kp_file match_file -out dst_h5_filename [-thresh f] [-hyp n] [-seed n] [-refine n] [-device n]" << endl;
+        if (model_given) cout << "       -model homography|fundamental (default homography)" << endl;
         cout << endl;
         return 1;
     }
@@ -99,10 +114,11 @@ int main(int argc, char **argv)
         std::vector<uint8_t> inlier(m, 0);
         int64_t k = 0;
         int32_t best = -1;
-        if (m >= 4) {
+        if (m >= (fundamental ? 8u : 4u)) {
             if (dlco_desc_create(&ctx, 1.4f, 8, 1, device) != DLCO_OK) throw std::runtime_error(dlco_desc_last_error(nullptr));
-            if (dlco_desc_verify_homography(ctx, src.data(), dst.data(), (int64_t)m, thresh, (int32_t)n_hyp, (uint64_t)seed, (int32_t)refine, H,
-                                            inlier.data(), &k, &best) != DLCO_OK)
+            const auto verify = fundamental ? dlco_desc_verify_fundamental : dlco_desc_verify_homography;      // one signature
+            if (verify(ctx, src.data(), dst.data(), (int64_t)m, thresh, (int32_t)n_hyp, (uint64_t)seed, (int32_t)refine, H, inlier.data(), &k, &best) !=
+                DLCO_OK)
                 throw std::runtime_error(dlco_desc_last_error(ctx));
         }
         float Hf[9];
@@ -113,8 +129,8 @@ int main(int argc, char **argv)
             if (inlier[i]) { kept.push_back(M[2 * i]); kept.push_back(M[2 * i + 1]); }
         {
             dlco_io::Writer wr(out);
-            wr.write<float>("Homography", Hf, 3, 3);
-            wr.write_vec<int64_t>("HomographyBits", bits, 9);
+            wr.write<float>(fundamental ? "Fundamental" : "Homography", Hf, 3, 3);
+            wr.write_vec<int64_t>(fundamental ? "FundamentalBits" : "HomographyBits", bits, 9);
             wr.write_vec<uint8_t>("Inlier", inlier.data(), m);
             wr.write<int32_t>("VerifiedMatches", kept.data(), kept.size() / 2, 2);
             wr.write_vec<int32_t>("BestHypothesis", &best, 1);

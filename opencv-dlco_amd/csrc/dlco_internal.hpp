@@ -561,4 +561,9 @@ void verify_score(const float *src, const float *dst, int64_t m, const double *H
 void verify_select(const int32_t *count, int n_hyp, uint64_t *best, hipStream_t s);
 void verify_mask(const float *src, const float *dst, int64_t m, const double *H, double t2, uint8_t *mask, int32_t *count, hipStream_t s);
 
+// the same against a fundamental matrix (kernels_epipolar.hip; the rule is epipolar_rules.hpp); the selection is verify_select
+void epipolar_hypotheses(const float *src, const float *dst, int64_t m, uint64_t seed, int n_hyp, double *F_all, hipStream_t s);
+void epipolar_score(const float *src, const float *dst, int64_t m, const double *F_all, int n_hyp, double t2, int32_t *count, hipStream_t s);
+void epipolar_mask(const float *src, const float *dst, int64_t m, const double *F, double t2, uint8_t *mask, int32_t *count, hipStream_t s);
+
 }  // namespace dlco

@@ -9,8 +9,8 @@
 // functions below switch contraction off themselves (VERIFY_RULES_NO_FMA); a compiler that does not know the pragma
 // builds this header with -ffp-contract=off.
 //
-// Out of scope: a device-memory form (the match list is filtered on the host); a fundamental or essential matrix;
-// symmetric transfer error; an adaptive hypothesis count.
+// Out of scope: a device-memory form (the match list is filtered on the host); an essential matrix (the fundamental matrix
+// is epipolar_rules.hpp); symmetric transfer error; an adaptive hypothesis count.
 //
 // Inputs.  src [m][2] and dst [m][2] float, widened to double; 4 <= m < 2^31.  Expected finite with |x|, |y| <= 2^20;
 // nothing is checked: a non-finite coordinate fails every comparison below, so its match is never an inlier and a sample
@@ -297,7 +297,7 @@ inline bool hartley(const float *pts, const uint8_t *mask, int64_t m, double &cx
 }
 
 // C = A B of 3 x 3 matrices by the dot rule
-inline void mul3(const double A[9], const double B[9], double C[9])
+VERIFY_RULES_HD inline void mul3(const double A[9], const double B[9], double C[9])
 {
     VERIFY_RULES_NO_FMA
     for (int i = 0; i < 3; i++)
@@ -365,29 +365,37 @@ inline bool refit_round(const float *src, const float *dst, int64_t m, const uin
     return true;
 }
 
-// The refit of a model (H, mask [m], count).  score(H', trial mask [m]) -> count of H' over all matches: the host's
-// count_inliers here, the mask kernel in the library.  rounds [refine][9] (may be NULL) receives every H' a round formed;
-// returns their number.
-template <typename Score>
-inline int refit(const float *src, const float *dst, int64_t m, int32_t refine, double H[9], uint8_t *mask, int64_t &count, Score &&score,
-                 double *rounds)
+// The refit's loop for a model M [9] with (mask [m], count).  round(mask, M') forms the model of one round from the inliers of
+// mask (false: rejected), score(M', trial mask [m]) -> count of M' over all matches.  rounds [refine][9] (may be NULL) receives
+// every M' a round formed; returns their number.
+template <typename Round, typename Score>
+inline int refit_rounds(int64_t m, int32_t refine, double M[9], uint8_t *mask, int64_t &count, Round &&round, Score &&score, double *rounds)
 {
     std::vector<uint8_t> trial((size_t)m);
     int formed = 0;
     for (int32_t k = 0; k < refine; k++) {
-        double Hn[9];
-        if (!refit_round(src, dst, m, mask, Hn)) break;
-        if (rounds) std::memcpy(rounds + 9 * formed, Hn, sizeof Hn);
+        double Mn[9];
+        if (!round(mask, Mn)) break;
+        if (rounds) std::memcpy(rounds + 9 * formed, Mn, sizeof Mn);
         formed++;
-        const int64_t c = score(Hn, trial.data());
+        const int64_t c = score(Mn, trial.data());
         if (c < count) break;
         const bool same = std::memcmp(trial.data(), mask, (size_t)m) == 0;
-        std::memcpy(H, Hn, sizeof Hn);
+        std::memcpy(M, Mn, sizeof Mn);
         std::memcpy(mask, trial.data(), (size_t)m);
         count = c;
         if (same) break;
     }
     return formed;
+}
+
+// The refit of a homography (H, mask [m], count): refit_rounds with refit_round.  score is the host's count_inliers here, the
+// mask kernel in the library.
+template <typename Score>
+inline int refit(const float *src, const float *dst, int64_t m, int32_t refine, double H[9], uint8_t *mask, int64_t &count, Score &&score,
+                 double *rounds)
+{
+    return refit_rounds(m, refine, H, mask, count, [&](const uint8_t *cur, double *Hn) { return refit_round(src, dst, m, cur, Hn); }, score, rounds);
 }
 
 // The whole rule on the host.  H [9], mask [m], *count, *best_hyp (-1: no model, H and mask zero); H_all [n_hyp][9] and

@@ -6,14 +6,23 @@ multiply-add (256 CUs x 64 lanes a clock x 2.4 GHz = 39.3e12 operations a second
 peak counts with FMA), and a float64 torch evaluation of the same counts on the same GPU, in chunks of hypotheses that keep
 its temporaries near 256 MB, timed by torch's events.  torch may contract a multiply and an add, so its counts are compared
 and the number that differ is printed, not asserted.  One process, three warm-up calls per shape, then `reps` timed calls, the
-median.  No gate: it prints what it measured."""
+median.  No gate: it prints what it measured.
+
+    verify_bench.py [reps] --fundamental
+times dlco_desc_verify_fundamental_hypotheses / dlco_desc_verify_fundamental instead, at the same three shapes on a planted
+two-camera scene (points with depth, a turned camera moved sideways, 0.3 pixels of noise) with half the matches outliers, at a
+threshold of 1 pixel.  The floor counts the 33 fp64 operations of the Sampson test per pair (epipolar_rules.hpp, kOpsPerPair).
+Here torch's counts must agree with the library's: the run ends with an error when they do not."""
 import importlib, os, sys
 import numpy as np
 import torch                                                # before libdlco.so: one HIP runtime per process, torch's first
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 dlco = importlib.import_module("opencv-dlco_amd")
 
-reps = int(sys.argv[1]) if len(sys.argv) > 1 else 15
+FUNDAMENTAL = "--fundamental" in sys.argv[1:]
+args = [a for a in sys.argv[1:] if a != "--fundamental"]
+reps = int(args[0]) if args else 15
+OPS_PER_PAIR, THRESHOLD = (33.0, 1.0) if FUNDAMENTAL else (19.0, 3.0)
 OPS_PER_SECOND = 256 * 64 * 2.4e9
 H_TRUE = np.array([[0.92, -0.11, 140.0], [0.08, 1.05, -60.0], [1.5e-5, -1.0e-5, 1.0]])
 
@@ -24,6 +33,17 @@ def planted(m, rng):
     dst = p[:, :2] / p[:, 2:] + rng.normal(0, 0.5, (m, 2))
     out = rng.permutation(m)[:m // 2]
     dst[out] = rng.uniform((0, 0), (4000, 3000), (len(out), 2))
+    return src.astype(np.float32), dst.astype(np.float32)
+
+
+def two_cameras(m, rng):
+    P = np.c_[rng.uniform(-2.0, 2.0, m), rng.uniform(-1.5, 1.5, m), rng.uniform(4.0, 8.0, m)]
+    cy, sy, cx, sx = np.cos(0.1), np.sin(0.1), np.cos(0.03), np.sin(0.03)
+    R = np.array([[cy, 0, sy], [0, 1, 0], [-sy, 0, cy]]) @ np.array([[1, 0, 0], [0, cx, -sx], [0, sx, cx]])
+    Q = P @ R.T + np.array([-0.5, 0.02, 0.05])
+    src, dst = 800.0 * P[:, :2] / P[:, 2:] + (512, 384), 800.0 * Q[:, :2] / Q[:, 2:] + (512, 384) + rng.normal(0, 0.3, (m, 2))
+    out = rng.permutation(m)[:m // 2]
+    dst[out] = rng.uniform((0, 0), (1024, 768), (len(out), 2))
     return src.astype(np.float32), dst.astype(np.float32)
 
 
@@ -38,6 +58,16 @@ def torch_counts(H_all, src, dst, t2):
     def run():
         for h0 in range(0, len(H), chunk):
             h = H[h0:h0 + chunk, :, None]
+            if FUNDAMENTAL:
+                l0 = (h[:, 0] * x + h[:, 1] * y) + h[:, 2]
+                l1 = (h[:, 3] * x + h[:, 4] * y) + h[:, 5]
+                l2 = (h[:, 6] * x + h[:, 7] * y) + h[:, 8]
+                e = (u * l0 + v * l1) + l2
+                m0 = (h[:, 0] * u + h[:, 3] * v) + h[:, 6]
+                m1 = (h[:, 1] * u + h[:, 4] * v) + h[:, 7]
+                S = ((l0 * l0 + l1 * l1) + m0 * m0) + m1 * m1
+                out[h0:h0 + chunk] = ((S > 0) & (e * e <= t2 * S)).sum(dim=1)
+                continue
             X = (h[:, 0] * x + h[:, 1] * y) + h[:, 2]
             Y = (h[:, 3] * x + h[:, 4] * y) + h[:, 5]
             W = (h[:, 6] * x + h[:, 7] * y) + h[:, 8]
@@ -59,23 +89,27 @@ def torch_counts(H_all, src, dst, t2):
 
 ctx = dlco.DescContext()
 rng = np.random.default_rng(0)
-print(f"{reps} timed calls per row, medians; floor = 19 m n_hyp / {OPS_PER_SECOND:.3g} fp64 operations a second")
-print("| m | n_hyp | verify_hypotheses kernels | instruction floor | torch float64 | verify_homography kernels (refine 2) | inliers |")
+hypotheses, model = (ctx.verify_fundamental_hypotheses, ctx.verify_fundamental) if FUNDAMENTAL else (ctx.verify_hypotheses, ctx.verify_homography)
+names = ("verify_fundamental_hypotheses", "verify_fundamental") if FUNDAMENTAL else ("verify_hypotheses", "verify_homography")
+print(f"{reps} timed calls per row, medians; floor = {OPS_PER_PAIR:.0f} m n_hyp / {OPS_PER_SECOND:.3g} fp64 operations a second")
+print(f"| m | n_hyp | {names[0]} kernels | instruction floor | torch float64 | {names[1]} kernels (refine 2) | inliers |")
 print("|---|---|---|---|---|---|---|")
 for m, n_hyp in ((2000, 2048), (20000, 4096), (100000, 4096)):
-    src, dst = planted(m, rng)
+    src, dst = (two_cameras if FUNDAMENTAL else planted)(m, rng)
     for _ in range(3):
-        H_all, count = ctx.verify_hypotheses(src, dst, 3.0, n_hyp, 0)
+        H_all, count = hypotheses(src, dst, THRESHOLD, n_hyp, 0)
     ms = []
     for _ in range(reps):
-        ctx.verify_hypotheses(src, dst, 3.0, n_hyp, 0)
+        hypotheses(src, dst, THRESHOLD, n_hyp, 0)
         ms.append(ctx.last_kernel_ms())
     full = []
     for _ in range(reps):
-        H, mask, best = ctx.verify_homography(src, dst, 3.0, n_hyp, 0, 2)
+        H, mask, best = model(src, dst, THRESHOLD, n_hyp, 0, 2)
         full.append(ctx.last_kernel_ms())
-    floor_ms = 1e3 * 19.0 * m * n_hyp / OPS_PER_SECOND
-    tc, t_ms = torch_counts(H_all, src, dst, 9.0)
+    floor_ms = 1e3 * OPS_PER_PAIR * m * n_hyp / OPS_PER_SECOND
+    tc, t_ms = torch_counts(H_all, src, dst, THRESHOLD * THRESHOLD)
     print(f"| {m} | {n_hyp} | {np.median(ms):.3f} ms (min {min(ms):.3f}, max {max(ms):.3f}) | {floor_ms:.3f} ms | {t_ms:.2f} ms, {int((tc != count).sum())} counts differ "
           f"| {np.median(full):.3f} ms | {int(mask.sum())} of {m}, hypothesis {best} |")
+    if FUNDAMENTAL and (tc != count).any():
+        sys.exit(f"verify_bench: {int((tc != count).sum())} of torch's counts differ from the library's at m = {m}")
 ctx.close()
