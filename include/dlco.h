@@ -286,6 +286,12 @@ typedef struct dlco_gemm_probe_args {
 } dlco_gemm_probe_args;
 int dlco_gemm_probe(dlco_ctx *ctx, const dlco_gemm_probe_args *args, float *C_host, float *C2_host, int32_t *depth_used,
                     double *us_per_launch);
+/* CholQR's Cholesky inverse alone (no reference line: the reference orthonormalises by LAPACK), on host arrays, for
+ * tests: M_host [n, ld] is a symmetric positive semi-definite Gram matrix (lower triangle read), 1 <= n <= 160, ld >= n.
+ * Linv_host [n, ld] receives L^-1 of M = L L^T (lower triangular, entries beyond column n untouched), dead_host [n] a 1 for
+ * every row whose pivot fell below rel_thresh times its diagonal entry of M (that row of Linv is zero). */
+int dlco_chol_probe(dlco_ctx *ctx, const float *M_host, int32_t n, int32_t ld, float rel_thresh, float *Linv_host,
+                    int32_t *dead_host);
 /* H1: sum_i sum_j max(pos_i + 1 - neg_j, 0)  (src/kernelop-opencv.cu:49-80). */
 int dlco_hinge_sum(dlco_ctx *ctx, const float *pos_host, int32_t n_pos,
                    const float *neg_host, int32_t n_neg, double *out);

@@ -135,6 +135,7 @@ def load():
     L.dlco_hinge_sum.argtypes = [vp, f32p, C.c_int32, f32p, C.c_int32, C.POINTER(C.c_double)]
     L.dlco_sym_product.argtypes = [vp, f32p, C.c_int32, f32p, C.c_int32, f32p]
     L.dlco_gemm_probe.argtypes = [vp, C.POINTER(GemmProbeArgs), f32p, f32p, i32p, C.POINTER(C.c_double)]
+    L.dlco_chol_probe.argtypes = [vp, f32p, C.c_int32, C.c_int32, C.c_float, f32p, i32p]
     L.dlco_roc_stats.argtypes = [vp, f32p, u8p, C.c_int32, f32p, C.POINTER(C.c_double)]
     L.dlco_log_step.argtypes = [vp, C.POINTER(LogEntry)]
     L.dlco_get_saved.argtypes = [vp, f32p, i32p, f32p]
@@ -533,6 +534,15 @@ class Context:
         used, us = C.c_int32(), C.c_double()
         self._ck(self.L.dlco_gemm_probe(self.h, C.byref(a), _p(out, f32p), _p(out2, f32p), C.byref(used), C.byref(us)))
         return dict(C=out, C2=out2, depth=used.value, us=us.value if reps else None)
+
+    def chol_probe(self, M, rel_thresh=1e-5):
+        """CholQR's Cholesky inverse alone (dlco_chol_probe): M [n, n] symmetric, n <= 160.  Returns (Linv [n, n], dead [n])."""
+        m = _f32(M)
+        assert m.ndim == 2 and m.shape[0] == m.shape[1]
+        n = m.shape[0]
+        linv, dead = np.zeros((n, n), np.float32), np.zeros(n, np.int32)
+        self._ck(self.L.dlco_chol_probe(self.h, _p(m, f32p), n, n, rel_thresh, _p(linv, f32p), _p(dead, i32p)))
+        return linv, dead
 
     def hinge_sum(self, pos, neg):
         p, n = _f32(pos), _f32(neg)

@@ -1359,6 +1359,24 @@ int dlco_gemm_probe(dlco_ctx *c, const dlco_gemm_probe_args *a, float *C_host, f
     });
 }
 
+int dlco_chol_probe(dlco_ctx *c, const float *M_host, int32_t n, int32_t ld, float rel_thresh, float *Linv_host, int32_t *dead_host)
+{
+    if (!c || !M_host || !Linv_host || !dead_host || n < 1 || n > CHOL_INV_MAX_N || ld < n) return DLCO_ERR_INVALID;
+    return guarded(c, [&] {
+        DLCO_HIP(hipSetDevice(c->cfg.device));
+        const size_t bytes = (size_t)n * ld * sizeof(float);
+        DevBuf<float> M, Linv;
+        DevBuf<int> dead;
+        M.alloc((size_t)n * ld); Linv.alloc((size_t)n * ld); dead.alloc(CHOL_INV_MAX_N);
+        h2d(c, M.p, M_host, bytes);
+        h2d(c, Linv.p, Linv_host, bytes);                      // entries the kernel leaves alone come back as they went in
+        chol_inverse128(M.p, ld, n, rel_thresh, Linv.p, ld, dead.p, c->stream);
+        sync(c);
+        d2h(c, Linv_host, Linv.p, bytes);
+        d2h(c, dead_host, dead.p, (size_t)n * sizeof(int32_t));
+    });
+}
+
 int dlco_hinge_sum(dlco_ctx *c, const float *pos_host, int32_t n_pos, const float *neg_host, int32_t n_neg, double *out)
 {
     if (!c || !out || n_pos < 0 || n_neg < 0) return DLCO_ERR_INVALID;

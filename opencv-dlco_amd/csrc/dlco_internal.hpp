@@ -455,6 +455,11 @@ size_t jacobi_work_floats(int n);
 // Linv is zero.
 constexpr int CHOL_INV_MAX_N = 160;
 void chol_inverse128(const float *M, long ldm, int n, float rel_thresh, float *Linv, long ldl, int *dead, hipStream_t s);
+// developer aid (tools/kern_time): the same launch built with phase time stamps; trace [CHOL_INV_STAMPS] on the device
+// receives the stamp count in [0], the s_memtime stamps of the eliminating wave behind it and s_memrealtime of both ends last
+constexpr int CHOL_INV_STAMPS = 64;
+void chol_inverse128_stamped(const float *M, long ldm, int n, float rel_thresh, float *Linv, long ldl, int *dead, unsigned long long *trace,
+                             hipStream_t s);
 // row norms of (Y - theta_i X); the publishing form also copies the n floats at `src` into pinned host memory and then
 // sets *flag_host = seq with a system-scope release (the host polls flag_host; extra: one device int copied along)
 // What the residual kernel may emit on the way (see residual_publish_kernel): the rows of W of the pass it closes

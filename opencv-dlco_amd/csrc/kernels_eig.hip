@@ -91,45 +91,78 @@ __global__ __launch_bounds__(256) void symv_kernel(const float *H, long ld, int 
 // kernel did this one pivot per workgroup barrier - ~1.2 us each, 114 us at n = 96; it left the library in round 4.)
 // ---- blocked: 32 pivots per workgroup barrier instead of one --------------------------------------------
 // The elimination of [M | I] proceeds in blocks of 32 pivots:
-//   1. the 32 x 32 diagonal block goes to LDS and ONE wave eliminates it in registers (lane i = row i of
-//      [D | I]; the pivot row reaches the other lanes through v_readlane, no barrier inside the 32
-//      steps), which yields the pivots d, the dead flags and the unit lower triangular T = L1^-1 of
-//      the block;
-//   2. every thread then applies the block's 32 steps at once to its entries: the block's rows become
+//   1. the 32 x 32 diagonal block D goes to LDS and ONE wave eliminates it in registers (lane i = row i of D; the
+//      pivot row reaches the other lanes through v_readlane, no barrier inside the 32 steps), which yields the
+//      pivots d, the dead flags and the multipliers f_ij of the block's steps.  That wave is the kernel's chain: one
+//      wave issues a dependent instruction every 4-5 cycles, so a step costs what its readlane + FMA pairs cost;
+//   2. the identity half of [D | I] - the unit lower triangular T = L1^-1 - is not on that chain: its column k joins at
+//      step k and needs only the multipliers.  All sixteen waves build it from them, two columns each;
+//   3. every thread then applies the block's 32 steps at once to its entries: the block's rows become
 //      P = T * rows, the multipliers of the rows below are F = (A[:,K] T^T) / d (the Schur complement
 //      is symmetric, so U_KK^-1 = T^T D^-1), and the trailing update is the rank-32 product F * P.
 // The matrix stays in registers (thread (ty, tx) holds rows ty + 32 r, columns tx + 32 c of [M | I]); LDS only
-// carries the block's rows, columns, T, P and F.  Four barriers per block of 32 pivots.  The multipliers are
-// a[j] * rcp(d) instead of a[j] / d (CholQR2's second pass absorbs that).  Fast path for M = I + E with
+// carries the block's rows, columns, multipliers, T, P and F.  Four barriers per block of 32 pivots.  The multipliers
+// are a[j] * rcp(d) instead of a[j] / d (CholQR2's second pass absorbs that).  Fast path for M = I + E with
 // |E|_F^2 <= 1e-6 (the second pass of CholQR2): M^-1/2 = I - E/2, no elimination.
+// Measured (tools/kern_time small, s_memtime stamps of the eliminating wave: profiles/chol_phases_*.txt).  Until the
+// eliminating wave shed the identity half it carried both halves - 32 pairs per step whatever the step, 16 000 cycles
+// per block, half the kernel at n = 96 - and parked its matrix entries in LDS meanwhile; the products of step 3 read
+// LDS four bytes at a time along j.  Now: D alone 10 800 cycles per block, T 3 500, step 3 on 16-byte reads (P and F
+// 11 900 -> 5 400 cycles in the first block of n = 96, the trailing update 7 500 -> 5 600 with the wait for the slowest
+// wave); 39.7 -> 30.8 us at n = 96, 63.4 -> 48.6 at 128, 94.2 -> 71.9 at 160 (10.0 -> 10.3 at n = 32: one barrier
+// more), every entry of Linv through the same FMAs in the same order: the same bits
+// (tests/test_chol_probe_gpu.py).  Tried and taken out: D in the lower and the
+// identity half in the upper half-wave (the multiplier handed over by v_permlane32_swap) - the same 32 pairs per
+// step in two EXEC regions, 18 000 cycles per block instead of 16 000.  Not built: the next block's diagonal
+// eliminated beside the trailing update (its wave must first redo the F * P update of the 32 x 32 diagonal block on
+// its own, ~2 000 cycles, to hide a trailing update of 3 100 - 5 600 with its wait: DESIGN section 9, item 2).
 // NBM = blocks of 32 rows the kernel is built for: 4 (n <= 128) or 5 (n <= 160: the block of the rank ~128 workload in ONE
 // orthonormalisation panel instead of two panels with a Gram-Schmidt step between them; 50 registers of matrix per thread).
 constexpr int C2_T = 1024;
-__host__ __device__ constexpr int c2_pld(int nbm) { return 64 * nbm + 4; }            // row stride of the P images (floats)
+// LDS images read along the pivot index j are stored j-contiguous with a row stride of C2_LD = 36 floats: a thread
+// fetches four consecutive j with one ds_read_b128 (rows stay 16-byte aligned), and the 16 lanes a ds_read_b128 serves
+// per cycle - consecutive rows modulo 16 - fall on the 16 distinct 16-byte slots of the bank row (9 * row mod 16).
+constexpr int C2_LD = 36;
 __host__ __device__ constexpr size_t c2_lds_floats(int nbm)
 {
-    return (size_t)2 * 32 * 33 + 2 * 32 * c2_pld(nbm) + 2 * 32 * nbm * 33 + 32 * nbm * 3 + 64 + 2 * nbm * nbm * 64;
+    return (size_t)32 * 33 + 32 * C2_LD + 4 * 32 * nbm * C2_LD + 32 * nbm * 3 + 64;
 }
 
 __device__ __forceinline__ float readlane_f(float v, int l) { return __int_as_float(__builtin_amdgcn_readlane(__float_as_int(v), l)); }
 
-template <int NBM>
+// TR (developer aid, tools/kern_time): lane 0 of wave 0 - the eliminating wave - stamps s_memtime at the phase boundaries
+// of every block into trace[1..]; trace[0] = number of stamps, trace[62], trace[63] = s_memrealtime at both ends.
+constexpr int C2_STAMPS = CHOL_INV_STAMPS;
+template <int NBM, bool TR = false>
 __global__ __launch_bounds__(C2_T) void chol_inv2_kernel(const float *M, long ldm, int n, float rel_thresh, float *Linv, long ldl,
-                                                         int *dead)
+                                                         int *dead, unsigned long long *trace)
 {
+    int tri = 1;
+    auto stamp = [&]() {
+        if constexpr (TR) {
+            unsigned long long now;
+            __builtin_amdgcn_sched_barrier(0);
+            asm volatile("s_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(now) :: "memory");
+            __builtin_amdgcn_sched_barrier(0);
+            if (threadIdx.x == 0 && tri < C2_STAMPS - 2) trace[tri++] = now;
+        }
+    };
+    if constexpr (TR) { if (threadIdx.x == 0) trace[C2_STAMPS - 2] = __builtin_amdgcn_s_memrealtime(); }
+    stamp();
     extern __shared__ __attribute__((aligned(16))) float c2[];
     float (*Dblk)[33] = reinterpret_cast<float (*)[33]>(c2);
-    float (*Tblk)[33] = reinterpret_cast<float (*)[33]>(c2 + 32 * 33);
-    constexpr int C2_PLD = c2_pld(NBM), NR = 32 * NBM;         // NR: rows / columns the registers cover
-    float (*Praw)[C2_PLD] = reinterpret_cast<float (*)[C2_PLD]>(c2 + 2 * 32 * 33);
-    float (*Pbuf)[C2_PLD] = reinterpret_cast<float (*)[C2_PLD]>(c2 + 2 * 32 * 33 + 32 * C2_PLD);
-    float (*Acol)[33] = reinterpret_cast<float (*)[33]>(c2 + 2 * 32 * 33 + 2 * 32 * C2_PLD);
-    float (*Fbuf)[33] = reinterpret_cast<float (*)[33]>(c2 + 2 * 32 * 33 + 2 * 32 * C2_PLD + NR * 33);
-    float *diag0 = c2 + 2 * 32 * 33 + 2 * 32 * C2_PLD + 2 * NR * 33;
+    constexpr int NR = 32 * NBM;                               // NR: rows / columns the registers cover
+    // Tblk[i][j] = T_ij; Praw / Pbuf[32 c + k][j]: entry (j, k) of column block c of the block's rows before / after T (of
+    // M for c > kb, of the identity half for c <= kb: one slot per c serves both); Acol / Fbuf[row][j]: column j of the block
+    float (*Tblk)[C2_LD] = reinterpret_cast<float (*)[C2_LD]>(c2 + 32 * 33);
+    float (*Praw)[C2_LD] = reinterpret_cast<float (*)[C2_LD]>(c2 + 32 * 33 + 32 * C2_LD);
+    float (*Pbuf)[C2_LD] = reinterpret_cast<float (*)[C2_LD]>(c2 + 32 * 33 + 32 * C2_LD + NR * C2_LD);
+    float (*Acol)[C2_LD] = reinterpret_cast<float (*)[C2_LD]>(c2 + 32 * 33 + 32 * C2_LD + 2 * NR * C2_LD);
+    float (*Fbuf)[C2_LD] = reinterpret_cast<float (*)[C2_LD]>(c2 + 32 * 33 + 32 * C2_LD + 3 * NR * C2_LD);
+    float *diag0 = c2 + 32 * 33 + 32 * C2_LD + 4 * NR * C2_LD;
     float *dpiv = diag0 + NR;
     int *deadf = reinterpret_cast<int *>(dpiv + NR);
     float *dinv = dpiv + 2 * NR;                               // [32] of the current block, then scratch [16]
-    float *stash = dinv + 64;                                  // [2 NBM^2][64]: the eliminating wave's own entries
     const int t = threadIdx.x, tx = t & 31, ty = t >> 5;
     const int nb = (n + 31) >> 5;
 
@@ -175,104 +208,141 @@ __global__ __launch_bounds__(C2_T) void chol_inv2_kernel(const float *M, long ld
     auto block = [&](auto KBc) {
         constexpr int kb = decltype(KBc)::value;
         if (kb < nb) {                                         // workgroup-uniform
+            stamp();
             // ---- 1. the diagonal block of the current Schur complement -------------------------------
             Dblk[ty][tx] = reg[kb][kb];
             __syncthreads();
-            // ---- 2. one wave eliminates [D | I] in registers ----------------------------------------------
+            stamp();
+            // ---- 2a. one wave eliminates D in registers and leaves the multipliers in LDS -----------------------
+            // Only the D half of [D | I] is a chain: the pivot of step j needs every step before it.  Lane i holds row i
+            // of D (32 registers next to the wave's own matrix entries: nothing to park) and stores its multiplier of
+            // step j - zero for i <= j or a dead pivot - over the block it has read: Dblk[j][i].
             if (t < 64) {
-                // this wave's own matrix entries wait in LDS meanwhile: the elimination needs 64 registers
-                // per lane and must not spill (a spilled register costs a trip to memory per pivot)
-#pragma unroll
-                for (int r = 0; r < NBM; r++)
-#pragma unroll
-                    for (int c = 0; c < 2 * NBM; c++) stash[(r * 2 * NBM + c) * 64 + t] = reg[r][c];
                 const int i = t & 31;
-                float a[32], x[32];
+                float a[32];
 #pragma unroll
-                for (int k = 0; k < 32; k++) { a[k] = Dblk[i][k]; x[k] = (i == k) ? 1.f : 0.f; }
+                for (int k = 0; k < 32; k++) a[k] = Dblk[i][k];
                 const float d0_mine = diag0[32 * kb + i];
+                float piv_mine = 0.f;
 #pragma unroll
                 for (int j = 0; j < 32; j++) {
                     const float piv = readlane_f(a[j], j);
                     const float d0 = readlane_f(d0_mine, j);
                     const bool dd = !(piv > rel_thresh * d0) || !(d0 > 0.f);
                     const float rinv = dd ? 0.f : __builtin_amdgcn_rcpf(piv);
-                    if (t == 0) { dpiv[32 * kb + j] = piv; deadf[32 * kb + j] = dd ? 1 : 0; dinv[j] = rinv; }
+                    if (i == j) piv_mine = a[j];
                     const float f = (i > j) ? a[j] * rinv : 0.f;
+                    Dblk[j][i] = f;                                  // (both half-waves: the same value to the same word)
 #pragma unroll
-                    for (int k = j + 1; k < 32; k++) a[k] -= f * readlane_f(a[k], j);
-#pragma unroll
-                    for (int k = 0; k <= j; k++) x[k] -= f * readlane_f(x[k], j);
+                    for (int k = j + 1; k < 32; k++) a[k] = __builtin_fmaf(-f, readlane_f(a[k], j), a[k]);
                 }
-                if (t < 32) {
-#pragma unroll
-                    for (int k = 0; k < 32; k++) Tblk[i][k] = x[k];
-                }
-#pragma unroll
-                for (int r = 0; r < NBM; r++)
-#pragma unroll
-                    for (int c = 0; c < 2 * NBM; c++) reg[r][c] = stash[(r * 2 * NBM + c) * 64 + t];
+                // what the block leaves for the phases behind it, once per lane instead of once per step: lane j
+                // repeats the step's test and reciprocal on its own pivot (the same instructions on the same values)
+                const bool dd = !(piv_mine > rel_thresh * d0_mine) || !(d0_mine > 0.f);
+                const float rinv = dd ? 0.f : __builtin_amdgcn_rcpf(piv_mine);
+                dpiv[32 * kb + i] = piv_mine; deadf[32 * kb + i] = dd ? 1 : 0; dinv[i] = rinv;
             }
+            stamp();
             // ---- 3a. the block's rows (columns still needed) and the block's columns of the rows below ---
 #pragma unroll
             for (int c = 0; c < NBM; c++) {
-                if (c > kb && c < nb) Praw[ty][32 * c + tx] = reg[kb][c];            // M part right of the block
-                if (c <= kb) Praw[ty][NR + 32 * c + tx] = reg[kb][NBM + c];           // identity part up to the block
+                if (c > kb && c < nb) Praw[32 * c + tx][ty] = reg[kb][c];              // M part right of the block
+                if (c <= kb) Praw[32 * c + tx][ty] = reg[kb][NBM + c];                // identity part up to the block
             }
 #pragma unroll
             for (int r = 0; r < NBM; r++)
                 if (r > kb && r < nb) Acol[32 * r + ty][tx] = reg[r][kb];
             __syncthreads();
-            // ---- 3b. P = T * rows (this thread's row of the block), F = (A[:,K] T^T) / d --------------------
+            stamp();
+            // ---- 2b. the identity half, T = L1^-1, by columns on all waves ---------------------------------------
+            // Column k of the identity half takes part in the steps j >= k only and in them needs nothing but the
+            // multipliers: x_i -= f_ij * x_j, the same FMAs on the same entries as when the eliminating wave carried
+            // them along.  Wave w takes columns w and 31 - w (33 readlane + FMA pairs) and lane i row i.
             {
-                float pacc[2 * NBM];
+                const int i = t & 31;
+                const int k0 = __builtin_amdgcn_readfirstlane(t >> 6), k1 = 31 - k0;
+                float f[32];
 #pragma unroll
-                for (int c = 0; c < 2 * NBM; c++) pacc[c] = 0.f;
-#pragma unroll 2
+                for (int j = 0; j < 32; j++) f[j] = Dblk[j][i];
+                float x0 = (i == k0) ? 1.f : 0.f, x1 = (i == k1) ? 1.f : 0.f;
+#pragma unroll
                 for (int j = 0; j < 32; j++) {
-                    const float tj = Tblk[ty][j];                     // zero for j > ty
+                    if (j >= k0) x0 = __builtin_fmaf(-f[j], readlane_f(x0, j), x0);
+                    if (j >= k1) x1 = __builtin_fmaf(-f[j], readlane_f(x1, j), x1);
+                }
+                if ((t & 32) == 0) { Tblk[i][k0] = x0; Tblk[i][k1] = x1; }
+            }
+            __syncthreads();
+            stamp();
+            // ---- 3b. P = T * rows (this thread's row of the block), F = (A[:,K] T^T) / d --------------------
+            // Every accumulator takes its 32 terms in ascending j, one FMA each (spelled out: left to contraction, the
+            // products of a four-wide read come out as packed multiplies and separate adds); four j per LDS read.  The
+            // loops carry no test of nb: a column or row block beyond it accumulates stale LDS into a value nobody stores.
+            {
+                constexpr int QUADS_3B = NBM <= 3 ? 4 : 2;        // quads of j in flight (registers: 4 (NBM + 1) each)
+                float pacc[NBM];                                  // slot c: M part for c > kb, identity part for c <= kb
+#pragma unroll
+                for (int c = 0; c < NBM; c++) pacc[c] = 0.f;
+#pragma unroll QUADS_3B
+                for (int j = 0; j < 32; j += 4) {
+                    const f32x4 tj = *reinterpret_cast<const f32x4 *>(&Tblk[ty][j]);   // zero for j > ty
 #pragma unroll
                     for (int c = 0; c < NBM; c++) {
-                        if (c > kb && c < nb) pacc[c] += tj * Praw[j][32 * c + tx];
-                        if (c <= kb) pacc[NBM + c] += tj * Praw[j][NR + 32 * c + tx];
+                        const f32x4 pj = *reinterpret_cast<const f32x4 *>(&Praw[32 * c + tx][j]);
+#pragma unroll
+                        for (int e = 0; e < 4; e++) pacc[c] = __builtin_fmaf(tj[e], pj[e], pacc[c]);
                     }
                 }
 #pragma unroll
                 for (int c = 0; c < NBM; c++) {
-                    if (c > kb && c < nb) { reg[kb][c] = pacc[c]; Pbuf[ty][32 * c + tx] = pacc[c]; }
-                    if (c <= kb) { reg[kb][NBM + c] = pacc[NBM + c]; Pbuf[ty][NR + 32 * c + tx] = pacc[NBM + c]; }
+                    if (c > kb && c < nb) { reg[kb][c] = pacc[c]; Pbuf[32 * c + tx][ty] = pacc[c]; }
+                    if (c <= kb) { reg[kb][NBM + c] = pacc[c]; Pbuf[32 * c + tx][ty] = pacc[c]; }
                 }
                 const float di = dinv[tx];
+                float facc[NBM];
 #pragma unroll
-                for (int r = 0; r < NBM; r++) {
-                    if (r > kb && r < nb) {
-                        float facc = 0.f;
-#pragma unroll 4
-                        for (int l = 0; l < 32; l++) facc += Tblk[tx][l] * Acol[32 * r + ty][l];
-                        Fbuf[32 * r + ty][tx] = facc * di;
-                    }
-                }
-            }
-            __syncthreads();
-            // ---- 4. trailing update of the rows below the block: rank-32 product F * P ---------------------
-            if (kb + 1 < nb) {
-#pragma unroll 2
-                for (int j = 0; j < 32; j++) {
-                    float fr[NBM], pc[2 * NBM];
-#pragma unroll
-                    for (int r = 0; r < NBM; r++) fr[r] = (r > kb && r < nb) ? Fbuf[32 * r + ty][j] : 0.f;
-#pragma unroll
-                    for (int c = 0; c < NBM; c++) {
-                        pc[c] = (c > kb && c < nb) ? Pbuf[j][32 * c + tx] : 0.f;
-                        pc[NBM + c] = (c <= kb) ? Pbuf[j][NR + 32 * c + tx] : 0.f;
-                    }
+                for (int r = 0; r < NBM; r++) facc[r] = 0.f;
+#pragma unroll QUADS_3B
+                for (int l = 0; l < 32; l += 4) {
+                    const f32x4 tl = *reinterpret_cast<const f32x4 *>(&Tblk[tx][l]);
 #pragma unroll
                     for (int r = 0; r < NBM; r++) {
                         if (r > kb) {
+                            const f32x4 al = *reinterpret_cast<const f32x4 *>(&Acol[32 * r + ty][l]);
 #pragma unroll
-                            for (int c = 0; c < NBM; c++) {
-                                if (c > kb) reg[r][c] -= fr[r] * pc[c];
-                                if (c <= kb) reg[r][NBM + c] -= fr[r] * pc[NBM + c];
+                            for (int e = 0; e < 4; e++) facc[r] = __builtin_fmaf(tl[e], al[e], facc[r]);
+                        }
+                    }
+                }
+#pragma unroll
+                for (int r = 0; r < NBM; r++)
+                    if (r > kb && r < nb) Fbuf[32 * r + ty][tx] = facc[r] * di;
+            }
+            __syncthreads();
+            stamp();
+            // ---- 4. trailing update of the rows below the block: rank-32 product F * P ---------------------
+            if (kb + 1 < nb) {
+                const f32x4 zero4 = {0.f, 0.f, 0.f, 0.f};
+                constexpr int QUADS_IN_FLIGHT = NBM <= 3 ? 4 : NBM == 4 ? 2 : 1;          // registers: 4 (2 NBM - kb - 1) per quad of j
+#pragma unroll QUADS_IN_FLIGHT
+                for (int j = 0; j < 32; j += 4) {
+                    f32x4 fr[NBM], pc[NBM];                                          // pc[c]: the slot of column block c
+#pragma unroll
+                    for (int r = 0; r < NBM; r++) {
+                        if (r > kb) { const f32x4 v = *reinterpret_cast<const f32x4 *>(&Fbuf[32 * r + ty][j]); fr[r] = r < nb ? v : zero4; }
+                    }
+#pragma unroll
+                    for (int c = 0; c < NBM; c++) { const f32x4 v = *reinterpret_cast<const f32x4 *>(&Pbuf[32 * c + tx][j]); pc[c] = c < nb ? v : zero4; }
+#pragma unroll
+                    for (int e = 0; e < 4; e++) {
+#pragma unroll
+                        for (int r = 0; r < NBM; r++) {
+                            if (r > kb) {
+#pragma unroll
+                                for (int c = 0; c < NBM; c++) {
+                                    if (c > kb) reg[r][c] = __builtin_fmaf(-fr[r][e], pc[c][e], reg[r][c]);
+                                    if (c <= kb) reg[r][NBM + c] = __builtin_fmaf(-fr[r][e], pc[c][e], reg[r][NBM + c]);
+                                }
                             }
                         }
                     }
@@ -285,6 +355,7 @@ __global__ __launch_bounds__(C2_T) void chol_inv2_kernel(const float *M, long ld
     block(std::integral_constant<int, 2>{});
     if constexpr (NBM > 3) block(std::integral_constant<int, 3>{});
     if constexpr (NBM > 4) block(std::integral_constant<int, NBM - 1>{});
+    stamp();
     __syncthreads();
     // Linv = D^-1/2 U^-1 (lower triangular); dead rows and the padding are zero
 #pragma unroll
@@ -300,24 +371,41 @@ __global__ __launch_bounds__(C2_T) void chol_inv2_kernel(const float *M, long ld
         }
     }
     if (t < n) dead[t] = deadf[t];
+    stamp();
+    if constexpr (TR) { if (t == 0) { trace[0] = tri - 1; trace[C2_STAMPS - 1] = __builtin_amdgcn_s_memrealtime(); } }
 }
 
 }  // namespace
 
-template <int NBM>
-static void launch_chol_inv2(const float *M, long ldm, int n, float rel_thresh, float *Linv, long ldl, int *dead, hipStream_t s)
+template <int NBM, bool TR>
+static void launch_chol_inv2(const float *M, long ldm, int n, float rel_thresh, float *Linv, long ldl, int *dead, unsigned long long *trace,
+                             hipStream_t s)
 {
-    ensure_dynamic_lds(reinterpret_cast<const void *>(chol_inv2_kernel<NBM>), (int)(c2_lds_floats(NBM) * sizeof(float)));
-    hipLaunchKernelGGL(chol_inv2_kernel<NBM>, dim3(1), dim3(C2_T), c2_lds_floats(NBM) * sizeof(float), s, M, ldm, n, rel_thresh, Linv, ldl, dead);
+    ensure_dynamic_lds(reinterpret_cast<const void *>(chol_inv2_kernel<NBM, TR>), (int)(c2_lds_floats(NBM) * sizeof(float)));
+    hipLaunchKernelGGL((chol_inv2_kernel<NBM, TR>), dim3(1), dim3(C2_T), c2_lds_floats(NBM) * sizeof(float), s, M, ldm, n, rel_thresh, Linv,
+                       ldl, dead, trace);
+}
+
+template <bool TR>
+static void chol_inverse_dispatch(const float *M, long ldm, int n, float rel_thresh, float *Linv, long ldl, int *dead,
+                                  unsigned long long *trace, hipStream_t s)
+{
+    DLCO_CHECK(n >= 1 && n <= CHOL_INV_MAX_N, -2, "chol_inverse128: n out of range");
+    if (n <= 96) launch_chol_inv2<3, TR>(M, ldm, n, rel_thresh, Linv, ldl, dead, trace, s);      // (the steady-state block: 18 matrix registers per thread instead of 32: 44.2 -> 39.7 us at n = 96)
+    else if (n <= 128) launch_chol_inv2<4, TR>(M, ldm, n, rel_thresh, Linv, ldl, dead, trace, s);
+    else launch_chol_inv2<5, TR>(M, ldm, n, rel_thresh, Linv, ldl, dead, trace, s);
+    DLCO_HIP(hipGetLastError());
 }
 
 void chol_inverse128(const float *M, long ldm, int n, float rel_thresh, float *Linv, long ldl, int *dead, hipStream_t s)
 {
-    DLCO_CHECK(n >= 1 && n <= CHOL_INV_MAX_N, -2, "chol_inverse128: n out of range");
-    if (n <= 96) launch_chol_inv2<3>(M, ldm, n, rel_thresh, Linv, ldl, dead, s);      // (the steady-state block: 18 matrix registers per thread instead of 32: 44.2 -> 39.7 us at n = 96)
-    else if (n <= 128) launch_chol_inv2<4>(M, ldm, n, rel_thresh, Linv, ldl, dead, s);
-    else launch_chol_inv2<5>(M, ldm, n, rel_thresh, Linv, ldl, dead, s);
-    DLCO_HIP(hipGetLastError());
+    chol_inverse_dispatch<false>(M, ldm, n, rel_thresh, Linv, ldl, dead, nullptr, s);
+}
+
+void chol_inverse128_stamped(const float *M, long ldm, int n, float rel_thresh, float *Linv, long ldl, int *dead, unsigned long long *trace,
+                             hipStream_t s)
+{
+    chol_inverse_dispatch<true>(M, ldm, n, rel_thresh, Linv, ldl, dead, trace, s);
 }
 
 // residual_kernel and the read-back in one launch: the workgroup that finishes LAST (a ticket counter, left at zero

@@ -106,7 +106,7 @@ int main(int argc, char **argv)
             }
         if (n <= CHOL_INV_MAX_N) {
         DevBuf<float> dM, dL; DevBuf<int> dead;
-        dM.alloc(M.size()); dL.alloc(M.size()); dead.alloc(128);
+        dM.alloc(M.size()); dL.alloc(M.size()); dead.alloc(CHOL_INV_MAX_N);
         hipMemcpy(dM.p, M.data(), M.size() * 4, hipMemcpyHostToDevice);
         hipMemset(dL.p, 0, M.size() * 4);
         const float ms = time_ms(s, 200, [&] { chol_inverse128(dM.p, ld, n, 1e-5f, dL.p, ld, dead.p, s); });
@@ -124,6 +124,32 @@ int main(int argc, char **argv)
                 err = std::max(err, std::fabs(acc - (i == j ? 1.0 : 0.0)));
             }
         std::printf("chol_inverse128 n=%3d  %.1f us  |Linv M Linv^T - I|max = %.2e\n", n, ms * 1e3, err);
+        if (n % 32 == 0) {
+            // phase stamps of the eliminating wave (the build with stamps; one launch after a warm one)
+            constexpr int NP = 6;
+            static const char *const phase[NP] = {"D to LDS + barrier", "2a elimination of D", "3a rows/columns to LDS + barrier",
+                                                  "2b T by columns + barrier", "3b P and F + barrier", "4 trailing update"};
+            DevBuf<unsigned long long> tr;
+            tr.alloc(CHOL_INV_STAMPS);
+            std::vector<unsigned long long> h(CHOL_INV_STAMPS);
+            for (int rep = 0; rep < 2; rep++) {
+                hipMemsetAsync(tr.p, 0, CHOL_INV_STAMPS * 8, s);
+                chol_inverse128_stamped(dM.p, ld, n, 1e-5f, dL.p, ld, dead.p, tr.p, s);
+                hipStreamSynchronize(s);
+            }
+            hipMemcpy(h.data(), tr.p, CHOL_INV_STAMPS * 8, hipMemcpyDeviceToHost);
+            const int ns = (int)h[0];
+            const double cyc_per_us = (double)(h[ns] - h[1]) / ((double)(h[CHOL_INV_STAMPS - 1] - h[CHOL_INV_STAMPS - 2]) / 100.0);
+            std::printf("  chol phases n=%3d (s_memtime cycles of wave 0, %.0f cycles/us, stamped build %.1f us from first to last stamp)\n", n,
+                        cyc_per_us, (double)(h[ns] - h[1]) / cyc_per_us);
+            std::printf("    %-36s %8llu\n", "load, fast-path test", h[2] - h[1]);
+            for (int b = 0; b < n / 32; b++)
+                for (int p = 0; p < NP; p++) {
+                    const int i = 2 + NP * b + p;
+                    if (i + 1 <= ns - 1) std::printf("    block %d  %-28s %8llu\n", b, phase[p], h[i + 1] - h[i]);
+                }
+            std::printf("    %-36s %8llu\n", "barrier, scale and store", h[ns] - h[ns - 1]);
+        }
         }
 
         // ---- Jacobi on a nearly diagonal symmetric matrix (steady-state Rayleigh-Ritz); eigenvectors = ROWS of V ----
