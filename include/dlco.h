@@ -591,7 +591,8 @@ int dlco_desc_cross_sqdists(dlco_desc_ctx *ctx, const float *query_host, int64_t
  * h_side other than 0 or 1, a coordinate pitch below 2 (device form).
  *   Out of scope: a spatially bucketed form that skips tiles no query of which can admit a row (a distance's bits are defined
  * by the tile loop's chain of matrix-core operations, which a kernel that gathers candidates does not reproduce); the byte
- * line (there is no dlco_desc_match_u8_guided); a fundamental-matrix predicate. ---- */
+ * line (there is no dlco_desc_match_u8_guided).  In scope since: a fundamental-matrix predicate, which has calls of its own,
+ * dlco_desc_match_guided_epipolar below. ---- */
 int dlco_desc_match_guided(dlco_desc_ctx *ctx, const float *query_host, const float *query_xy_host, int64_t nq,
                            const float *train_host, const float *train_xy_host, int64_t nt, int32_t r, const double *H,
                            float radius, int32_t h_side, int32_t *idx_host, float *sqdist_host);
@@ -606,6 +607,41 @@ int dlco_desc_match_guided_device(dlco_desc_ctx *ctx, const float *query_dev, in
 int dlco_desc_cross_sqdists_guided(dlco_desc_ctx *ctx, const float *query_host, const float *query_xy_host, int64_t nq,
                                    const float *train_host, const float *train_xy_host, int64_t nt, int32_t r,
                                    const double *H, float radius, int32_t h_side, float *out_host);
+/* ---- Guided matching under a fundamental matrix: the same second pass for a scene with depth, where no single homography
+ * admits the matches (dlco_desc_verify_fundamental below gives the model).  csrc/guided_epipolar_rules.hpp states the rule.
+ *   Geometry: query_xy, train_xy as above; F [9] row-major, it need not be normalised; threshold in pixels.  The pair
+ * predicate P(i, j) is the inlier test of that verification, the Sampson error without a division: with x = (x, y, 1) of the
+ * image F applies to (src) and x' = (u, v, 1) of the other (dst),
+ *     l = F x, e = (u l0 + v l1) + l2, m = F^T x' (its first two entries), S = ((l0 l0 + l1 l1) + m0 m0) + m1 m1,
+ *     P = S > 0 and e e <= threshold^2 S
+ * in IEEE double + - x without fused multiply-add or division, the same in every bit on every machine.  The library forms
+ * l0, l1, l2 and l0 l0 + l1 l1 once per src point, u, v, m0 m0 and m1 m1 once per dst point, and spends 8 operations a pair.
+ *     f_side = 0: the query image is src, x = query_xy[i] and x' = train_xy[j]: F as
+ *                 dlco_desc_verify_fundamental(src = query keypoints, dst = train keypoints) returns it
+ *     f_side = 1: the train image is src, x = train_xy[j] and x' = query_xy[i]
+ * f_side = 1 exists so that a mutual check can swap the tables and keep F: that call sees the transpose of the same
+ * admissible set.
+ *   Documented and not detected: an all-zero F (what the verification returns for "no model") is valid and admits nothing,
+ * S = 0; a point at an epipole of F (l = 0, or m = 0) admits every point of the other side, which is the verdict of the
+ * verification's own inlier test.
+ *   Result, limits, the arithmetic of the distances and the treatment of non-finite coordinates: as dlco_desc_match_guided,
+ * with dlco_desc_cross_sqdists_guided_epipolar as the matrix.
+ *   DLCO_ERR_INVALID, before the handle is used and with no output touched: whatever dlco_desc_match (_device, cross_sqdists)
+ * rejects, a null coordinate pointer or a null F, an entry of F that is not finite, a threshold that is not finite or <= 0, an
+ * f_side other than 0 or 1, a coordinate pitch below 2 (device form).
+ *   Out of scope: the byte line; a spatially bucketed form; a choice between H and F. ---- */
+int dlco_desc_match_guided_epipolar(dlco_desc_ctx *ctx, const float *query_host, const float *query_xy_host, int64_t nq,
+                                    const float *train_host, const float *train_xy_host, int64_t nt, int32_t r, const double *F,
+                                    float threshold, int32_t f_side, int32_t *idx_host, float *sqdist_host);
+/* the same on tables in HBM, tables and coordinates as dlco_desc_match_guided_device takes them.  F is host memory. */
+int dlco_desc_match_guided_epipolar_device(dlco_desc_ctx *ctx, const float *query_dev, int64_t ldq, const float *query_xy_dev,
+                                           int64_t ldxy_q, int64_t nq, const float *train_dev, int64_t ldt,
+                                           const float *train_xy_dev, int64_t ldxy_t, int64_t nt, int32_t r, const double *F,
+                                           float threshold, int32_t f_side, int32_t *idx_dev, float *sqdist_dev);
+/* the matrix out[nq][nt] of dlco_desc_cross_sqdists with +inf where P fails (nq * nt <= 2^28) */
+int dlco_desc_cross_sqdists_guided_epipolar(dlco_desc_ctx *ctx, const float *query_host, const float *query_xy_host, int64_t nq,
+                                            const float *train_host, const float *train_xy_host, int64_t nt, int32_t r,
+                                            const double *F, float threshold, int32_t f_side, float *out_host);
 /* ---- Eight-bit descriptors: a table of bytes is a quarter of the float one, and its distances are integers.
  *   The quantiser is a scale s > 0 and an offset o[r]; csrc/quant_rules.hpp states the rule.  One element:
  * t = y - o_k in float, v = t * s in float (two roundings, never an FMA), q = rintf(v) (half to even); the byte is 0 if v is
@@ -688,8 +724,8 @@ int  dlco_desc_verify_hypotheses(dlco_desc_ctx *ctx, const float *src_xy_host, c
  * rounding.
  *   Degeneracy is documented and not detected: matches related by a homography (a plane, a camera that only rotates, a
  * shifted image) satisfy a three-dimensional family of F, and the call returns some member of it.
- *   Out of scope: a choice between H and F; a seven-point solver; an essential matrix; an epipolar predicate for guided
- * matching; an adaptive hypothesis count. */
+ *   Out of scope: a choice between H and F; a seven-point solver; an essential matrix; an adaptive hypothesis count.
+ * In scope since: an epipolar predicate for guided matching, dlco_desc_match_guided_epipolar above. */
 int  dlco_desc_verify_fundamental(dlco_desc_ctx *ctx, const float *src_xy_host, const float *dst_xy_host, int64_t m, float threshold,
                                   int32_t n_hyp, uint64_t seed, int32_t refine, double *F_out, uint8_t *inlier_host, int64_t *n_inliers,
                                   int32_t *best_hyp);
@@ -699,7 +735,7 @@ int  dlco_desc_verify_fundamental_hypotheses(dlco_desc_ctx *ctx, const float *sr
 /* HIP-event time of the kernels of the last compute / describe call (transform, pooling, projection, and the sampling
  * for the keypoint calls; extract_patches: the sampling alone); the pair_sqdists /
  * pair_stats calls add their distance kernel; after a match / cross_sqdists call, float or _u8, the time of its kernels
- * (norms, tile loop, merge of the slices, and for the guided forms the kernel that writes the records); the _u8 forms of describe add their quantising kernel; after a detect call the
+ * (norms, tile loop, merge of the slices, and for the guided forms the kernel that writes the records, launched once per side for the epipolar ones); the _u8 forms of describe add their quantising kernel; after a detect call the
  * detector's kernels (the integral image when the call formed it, the octaves, the selection; detect_oriented adds the
  * orientation kernel); after an orient call the orientation kernel and the integral image when the call formed it; after a
  * verify call the verify kernels (hypotheses, scoring, selection, of either model; verify_homography and verify_fundamental add

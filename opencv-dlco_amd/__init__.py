@@ -201,6 +201,9 @@ def load():
     L.dlco_desc_match_guided_device.argtypes = [vp, vp, i64, vp, i64, i64, vp, i64, vp, i64, i64, C.c_int32, f64p, C.c_float,
                                                 C.c_int32, vp, vp]
     L.dlco_desc_cross_sqdists_guided.argtypes = [vp, f32p, f32p, i64, f32p, f32p, i64, C.c_int32, f64p, C.c_float, C.c_int32, f32p]
+    L.dlco_desc_match_guided_epipolar.argtypes = L.dlco_desc_match_guided.argtypes
+    L.dlco_desc_match_guided_epipolar_device.argtypes = L.dlco_desc_match_guided_device.argtypes
+    L.dlco_desc_cross_sqdists_guided_epipolar.argtypes = L.dlco_desc_cross_sqdists_guided.argtypes
     L.dlco_desc_last_kernel_ms.argtypes = [vp]
     L.dlco_desc_last_kernel_ms.restype = C.c_double
     L.dlco_pr_last_error.restype = C.c_char_p
@@ -1066,6 +1069,40 @@ class DescContext:
         self._ck(self.L.dlco_desc_cross_sqdists_guided(self.h, _p(q, f32p), _p(qxy, f32p), q.shape[0], _p(t, f32p), _p(txy, f32p),
                                                        t.shape[0], q.shape[1], _p(h, C.POINTER(C.c_double)), radius, h_side,
                                                        _p(out, f32p)))
+        return out
+
+    # ---- guided matching under a fundamental matrix (csrc/guided_epipolar_rules.hpp states the rule) ----
+    def match_guided_epipolar(self, query, query_xy, train, train_xy, F, threshold=3.0, f_side=0):
+        """match among the rows of train the fundamental matrix F [3,3] admits for a query: those whose keypoint and the
+        query's have a Sampson error within threshold pixels, the inlier test of verify_fundamental (f_side=0: the query image
+        is src, F as verify_fundamental(query keypoints, train keypoints) returns it; f_side=1: the train image is src, the
+        call of a mutual check with the tables swapped).  (idx [nq,2] int32, sqdist [nq,2] float32); fewer than two admitted
+        rows leave -1 / +inf."""
+        q, qxy, t, txy, f = self._guided_tables(query, query_xy, train, train_xy, F)
+        idx = np.empty((q.shape[0], 2), np.int32)
+        d = np.empty((q.shape[0], 2), np.float32)
+        self._ck(self.L.dlco_desc_match_guided_epipolar(self.h, _p(q, f32p), _p(qxy, f32p), q.shape[0], _p(t, f32p), _p(txy, f32p),
+                                                        t.shape[0], q.shape[1], _p(f, C.POINTER(C.c_double)), threshold, f_side,
+                                                        _p(idx, i32p), _p(d, f32p)))
+        return idx, d
+
+    def match_guided_epipolar_device(self, q_ptr, qxy_ptr, nq, t_ptr, txy_ptr, nt, r, F, idx_ptr, d_ptr, threshold=3.0, f_side=0,
+                                     ldq=None, ldt=None, ldxy_q=2, ldxy_t=2):
+        """match_guided_epipolar on tables in device memory, pitches as match_guided_device; results to device memory."""
+        f = np.ascontiguousarray(F, np.float64)
+        assert f.size == 9
+        self._ck(self.L.dlco_desc_match_guided_epipolar_device(self.h, C.c_void_p(q_ptr), ldq or r, C.c_void_p(qxy_ptr), ldxy_q, nq,
+                                                               C.c_void_p(t_ptr), ldt or r, C.c_void_p(txy_ptr), ldxy_t, nt, r,
+                                                               _p(f, C.POINTER(C.c_double)), threshold, f_side, C.c_void_p(idx_ptr),
+                                                               C.c_void_p(d_ptr)))
+
+    def cross_sqdists_guided_epipolar(self, query, query_xy, train, train_xy, F, threshold=3.0, f_side=0):
+        """cross_sqdists with +inf where F does not admit the pair: match_guided_epipolar is the top two of its finite entries."""
+        q, qxy, t, txy, f = self._guided_tables(query, query_xy, train, train_xy, F)
+        out = np.empty((q.shape[0], t.shape[0]), np.float32)
+        self._ck(self.L.dlco_desc_cross_sqdists_guided_epipolar(self.h, _p(q, f32p), _p(qxy, f32p), q.shape[0], _p(t, f32p),
+                                                                _p(txy, f32p), t.shape[0], q.shape[1], _p(f, C.POINTER(C.c_double)),
+                                                                threshold, f_side, _p(out, f32p)))
         return out
 
     # ---- eight-bit descriptors: rows quantised on the device, byte tables matched with exact integer distances ----

@@ -1,7 +1,7 @@
 // match — nearest-neighbour matching of two descriptor tables, over libdlco.so.
 //
 //     match query_desc_file train_desc_file -out dst [-u8] [-ratio f] [-cross] [-device n]
-//           [-guided verify_out -kp query_kp_file train_kp_file [-radius f]]
+//           [-guided verify_out -kp query_kp_file train_kp_file [-radius f]] [-model homography|fundamental]
 //
 // Both inputs hold the dataset "Descriptor" [n, r] f32 that `describe` writes (the two r must agree).  Writes
 //     "Nearest" [nq,2] i32 and "NearestSqDist" [nq,2] f32   the library's answer for every query (dlco_desc_match)
@@ -20,6 +20,9 @@
 // makes its second call with the tables swapped and h_side = 1, which sees the transpose of the same admissible set; -ratio
 // and -cross are the same host rules on the guided answer (a query with no admitted row is no match).  There is no guided
 // form of -u8.
+//   -model fundamental (with -guided only; the default is homography) guides by the fundamental matrix of a
+// `verify -model fundamental` output instead ("FundamentalBits", src = the query image): the library call is
+// dlco_desc_match_guided_epipolar with -radius as its threshold, the Sampson error in pixels, and f_side = 1 for -cross.
 // A path that does not end in .h5/.hdf5 is a directory of .npy files with the same dataset names (dlco_io.hpp).
 #include "../../include/dlco.h"
 #include "dlco_io.hpp"
@@ -63,8 +66,8 @@ void load_xy(const char *path, size_t rows, const char *desc_path, std::vector<f
     for (size_t i = 0; i < rows; i++) { xy[2 * i] = kp[4 * i]; xy[2 * i + 1] = kp[4 * i + 1]; }
 }
 
-// H [9] of a verify output; refuses one without a model
-void load_model(const char *path, double H[9])
+// H [9] of a verify output, the dataset `name` of it ("HomographyBits", "FundamentalBits"); refuses one without a model
+void load_model(const char *path, const char *name, double H[9])
 {
     std::vector<size_t> shape;
     std::vector<int32_t> best;
@@ -72,8 +75,8 @@ void load_model(const char *path, double H[9])
     dlco_io::read_dataset<int32_t>(path, "BestHypothesis", shape, best);
     if (best.size() != 1) throw std::runtime_error(std::string(path) + ": BestHypothesis must hold one value");
     if (best[0] < 0) throw std::runtime_error(std::string(path) + ": the verification found no model (BestHypothesis = -1): nothing to guide by");
-    dlco_io::read_dataset<int64_t>(path, "HomographyBits", shape, bits);
-    if (bits.size() != 9) throw std::runtime_error(std::string(path) + ": HomographyBits must hold nine values");
+    dlco_io::read_dataset<int64_t>(path, name, shape, bits);
+    if (bits.size() != 9) throw std::runtime_error(std::string(path) + ": " + name + " must hold nine values");
     std::memcpy(H, bits.data(), 9 * sizeof(double));
 }
 
@@ -125,7 +128,7 @@ int main(int argc, char **argv)
     int device = 0;
     bool help = false, cross = false, use_ratio = false, u8 = false;
     float ratio = 1.0f, radius = 6.0f;
-    const char *qf = nullptr, *tf = nullptr, *out = nullptr, *guided = nullptr, *qkp = nullptr, *tkp = nullptr;
+    const char *qf = nullptr, *tf = nullptr, *out = nullptr, *guided = nullptr, *qkp = nullptr, *tkp = nullptr, *model = nullptr;
     for (int i = 1; i < argc; i++) {
         if (argv[i][0] == '-') {
             const bool has_val = i + 1 < argc;
@@ -136,6 +139,7 @@ int main(int argc, char **argv)
             if (std::strcmp(argv[i], "-u8") == 0) { u8 = true; continue; }
             if (std::strcmp(argv[i], "-guided") == 0 && has_val) { guided = argv[++i]; continue; }
             if (std::strcmp(argv[i], "-kp") == 0 && i + 2 < argc) { qkp = argv[++i]; tkp = argv[++i]; continue; }
+            if (std::strcmp(argv[i], "-model") == 0 && has_val) { model = argv[++i]; continue; }
             if (std::strcmp(argv[i], "-radius") == 0 && has_val) { radius = (float)atof(argv[++i]); continue; }
             if (std::strcmp(argv[i], "-device") == 0 && has_val) { device = atoi(argv[++i]); continue; }
             cout << "ERROR: Invalid " << argv[i] << " option." << endl;
@@ -159,6 +163,15 @@ int main(int argc, char **argv)
         cout << "ERROR: -guided and -kp go together." << endl;
         help = true;
     }
+    const bool fundamental = model && std::strcmp(model, "fundamental") == 0;
+    if (model && !fundamental && std::strcmp(model, "homography") != 0) {
+        cout << "ERROR: -model must be homography or fundamental." << endl;
+        help = true;
+    }
+    if (model && !guided) {
+        cout << "ERROR: -model needs -guided." << endl;
+        help = true;
+    }
     if (!(std::isfinite(radius) && radius > 0.0f)) {
         cout << "ERROR: -radius must be finite and > 0." << endl;
         help = true;
@@ -166,7 +179,7 @@ int main(int argc, char **argv)
     if (help) {
         cout << endl;
         cout << "Usage: match query_desc_file train_desc_file -out dst_h5_filename [-u8] [-ratio f] [-cross] [-device n] "
-                "[-guided verify_out -kp query_kp_file train_kp_file [-radius f]]" << endl;
+                "[-guided verify_out -kp query_kp_file train_kp_file [-radius f]] [-model homography|fundamental]" << endl;
         cout << endl;
         return 1;
     }
@@ -189,25 +202,28 @@ int main(int argc, char **argv)
         double H[9] = {0};
         std::vector<float> qxy, txy;
         if (guided) {
-            load_model(guided, H);
+            load_model(guided, fundamental ? "FundamentalBits" : "HomographyBits", H);
             load_xy(qkp, nq, qf, qxy);
             load_xy(tkp, nt, tf, txy);
-            printf("Guided: radius %g\n", radius);
+            if (fundamental) printf("Guided: fundamental, radius %g\n", radius);
+            else printf("Guided: radius %g\n", radius);
         }
 
         if (dlco_desc_create(&ctx, 1.4f, 8, 1, device) != DLCO_OK) throw std::runtime_error(dlco_desc_last_error(nullptr));
         const auto t0 = std::chrono::steady_clock::now();
         std::vector<int32_t> nearest(nq * 2), back;
         std::vector<float> sqdist(nq * 2);
-        const int rc = guided ? dlco_desc_match_guided(ctx, Q.data(), qxy.data(), (int64_t)nq, T.data(), txy.data(), (int64_t)nt, (int32_t)r, H, radius, 0,
+        // the two guided calls take the same arguments: the model [9], the radius or threshold, the side
+        const auto guided_call = fundamental ? dlco_desc_match_guided_epipolar : dlco_desc_match_guided;
+        const int rc = guided ? guided_call(ctx, Q.data(), qxy.data(), (int64_t)nq, T.data(), txy.data(), (int64_t)nt, (int32_t)r, H, radius, 0,
                                                        nearest.data(), sqdist.data())
                               : dlco_desc_match(ctx, Q.data(), (int64_t)nq, T.data(), (int64_t)nt, (int32_t)r, nearest.data(), sqdist.data());
         if (rc != DLCO_OK) throw std::runtime_error(dlco_desc_last_error(ctx));
         if (cross) {
             back.resize(nt * 2);
             std::vector<float> back_d(nt * 2);
-            // guided: the tables swapped and H kept, h_side = 1: the transpose of the same admissible set
-            const int rb = guided ? dlco_desc_match_guided(ctx, T.data(), txy.data(), (int64_t)nt, Q.data(), qxy.data(), (int64_t)nq, (int32_t)r, H, radius, 1,
+            // guided: the tables swapped and the model kept, side = 1: the transpose of the same admissible set
+            const int rb = guided ? guided_call(ctx, T.data(), txy.data(), (int64_t)nt, Q.data(), qxy.data(), (int64_t)nq, (int32_t)r, H, radius, 1,
                                                            back.data(), back_d.data())
                                   : dlco_desc_match(ctx, T.data(), (int64_t)nt, Q.data(), (int64_t)nq, (int32_t)r, back.data(), back_d.data());
             if (rb != DLCO_OK) throw std::runtime_error(dlco_desc_last_error(ctx));

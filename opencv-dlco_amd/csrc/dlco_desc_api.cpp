@@ -13,6 +13,7 @@
 #include "dlco_internal.hpp"
 #include "detect_rules.hpp"
 #include "guided_rules.hpp"
+#include "guided_epipolar_rules.hpp"
 #include "orient_rules.hpp"
 #include "patch_rules.hpp"
 #include "quant_rules.hpp"
@@ -35,7 +36,8 @@ constexpr int kChunk = 2048;            // patches per launch pair: 256 MB of Pa
 // The buffers of one matcher (FloatLine, ByteLine below): the uploaded tables of the host forms, the result of a chunk and
 // the matrix, part [slices][nq] partial (d1, j1, d2, j2) of 16 bytes each, the norms of the queries and of train; for the
 // guided forms of the float line the uploaded (x, y) of both tables and rec [n][4], the records of the side the homography
-// applies to (guided_rules.hpp): a launch's queries or all of train
+// applies to (guided_rules.hpp): a launch's queries or all of train; for the epipolar guided forms (guided_epipolar_rules.hpp)
+// rec holds train's records and qrec a launch's queries'
 template <typename Elem, typename Dist, typename Norm>
 struct MatchBufs {
     DevBuf<Elem> query, train;
@@ -43,7 +45,7 @@ struct MatchBufs {
     DevBuf<int32_t> idx, part;
     DevBuf<Norm> qnorm, tnorm;
     DevBuf<float> qxy, txy;
-    DevBuf<double> rec;
+    DevBuf<double> rec, qrec;
 };
 
 struct dlco_desc_ctx {
@@ -268,13 +270,15 @@ struct ByteLine {
 
 // The geometry of a guided call (guided_rules.hpp), an optional argument of the float line's host path: the (x, y) of the
 // rows of both tables at pitches in floats (device memory in match_on_device and match_device, host memory with pitch 2 in
-// match_host), the homography, the squared radius and the side H applies to.
+// match_host), the model (kGuideHomography: H, guided_rules.hpp; kGuideFundamental: F, guided_epipolar_rules.hpp), its nine
+// entries, the squared radius or threshold and the side the model applies to.
 struct Geometry {
     const float *qxy; long ldq;
     const float *txy; long ldt;
     const double *H;
     double t2;
-    int h_side;
+    int side;
+    int model;
 };
 
 constexpr int64_t kMatchRows = (int64_t)1 << 20;           // queries per launch (the kernels index a launch's queries with an int)
@@ -287,8 +291,8 @@ bool match_args_ok(const void *a, const void *b, const void *o1, const void *o2,
 }
 
 // device tables in, device results out; adds the kernels' time to *ms.  The line's tnorm holds train's norms already, and
-// with a geometry of h_side 1 its rec train's records (train_norms); geo's tables are device memory, and the queries'
-// coordinates move with the rows.
+// with a homography of side 1, or a fundamental matrix, its rec train's records (train_norms); geo's tables are device
+// memory, and the queries' coordinates move with the rows.
 template <typename L>
 void match_on_device(dlco_desc_ctx *c, const typename L::Elem *q, long ldq, int64_t nq, const typename L::Elem *t, long ldt, int64_t nt, int r,
                      int32_t *idx, typename L::Dist *sqdist, typename L::Dist *cross, double *ms, const Geometry *geo = nullptr)
@@ -301,34 +305,42 @@ void match_on_device(dlco_desc_ctx *c, const typename L::Elem *q, long ldq, int6
         const int tps = match_slicing::tiles_per_slice(L::shape, cnt, nt, c->n_cu), slices = match_slicing::slices(L::shape, nt, tps);
         b.qnorm.alloc((size_t)cnt);
         if (!cross && slices > 1) b.part.alloc((size_t)slices * cnt * 4);
-        MatchGuide guide{nullptr, nullptr, 0, 0};
-        if (geo && geo->h_side == 0) {
+        const bool epi = geo && geo->model == kGuideFundamental;
+        const float *qxy0 = geo ? geo->qxy + q0 * geo->ldq : nullptr;       // the coordinates of the launch's first query
+        MatchGuide guide;
+        if (epi) {
+            b.qrec.alloc((size_t)cnt * 4);
+            guide.rec = b.rec.p; guide.qrec = b.qrec.p; guide.side = geo->side; guide.model = kGuideFundamental; guide.t2 = geo->t2;
+        } else if (geo && geo->side == 0) {
             b.rec.alloc((size_t)cnt * 4);
-            guide = MatchGuide{b.rec.p, geo->txy, geo->ldt, 0};
+            guide.rec = b.rec.p; guide.xy = geo->txy; guide.ldxy = geo->ldt; guide.side = 0;
         } else if (geo) {
-            guide = MatchGuide{b.rec.p, geo->qxy + q0 * geo->ldq, geo->ldq, 1};
+            guide.rec = b.rec.p; guide.xy = qxy0; guide.ldxy = geo->ldq; guide.side = 1;
         }
         *ms += timed_ms(c, ev, [&] {
             L::query_norms(q + q0 * ldq, ldq, cnt, r, b.qnorm.p, c->stream);
-            if (geo && geo->h_side == 0) match_records(geo->qxy + q0 * geo->ldq, geo->ldq, cnt, geo->H, geo->t2, b.rec.p, c->stream);
+            if (epi) match_epi_records(qxy0, geo->ldq, cnt, geo->H, geo->side == 0 ? 0 : 1, b.qrec.p, c->stream);   // side 0: the queries are src
+            else if (geo && geo->side == 0) match_records(qxy0, geo->ldq, cnt, geo->H, geo->t2, b.rec.p, c->stream);
             L::top2(q + q0 * ldq, ldq, cnt, t, ldt, (int)nt, r, b.qnorm.p, b.tnorm.p, tps, idx ? idx + 2 * q0 : nullptr,
                     sqdist ? sqdist + 2 * q0 : nullptr, b.part.p, cross ? cross + q0 * nt : nullptr, geo ? &guide : nullptr, c->stream);
         });
     }
 }
 
-// train's norms, and with a geometry of h_side 1 train's records
+// train's norms, and train's records: with a homography of side 1, or a fundamental matrix (dst records when the queries are src)
 template <typename L>
 double train_norms(dlco_desc_ctx *c, const typename L::Elem *t, long ldt, int64_t nt, int r, const Geometry *geo = nullptr)
 {
     auto &b = L::bufs(c);
     EventPair ev;
     b.tnorm.alloc((size_t)nt);
-    const bool records = geo && geo->h_side == 1;
+    const bool epi = geo && geo->model == kGuideFundamental;
+    const bool records = geo && (epi || geo->side == 1);
     if (records) b.rec.alloc((size_t)nt * 4);
     return timed_ms(c, ev, [&] {
         L::train_norms(t, ldt, nt, r, b.tnorm.p, c->stream);
-        if (records) match_records(geo->txy, geo->ldt, nt, geo->H, geo->t2, b.rec.p, c->stream);
+        if (epi) match_epi_records(geo->txy, geo->ldt, nt, geo->H, geo->side == 0 ? 1 : 0, b.rec.p, c->stream);
+        else if (records) match_records(geo->txy, geo->ldt, nt, geo->H, geo->t2, b.rec.p, c->stream);
     });
 }
 
@@ -373,7 +385,7 @@ void match_host(dlco_desc_ctx *c, const typename L::Elem *query_host, int64_t nq
     upload_rows(b.train.p, train_host, nt);
     Geometry dev_geo{};                                    // the same geometry on the uploaded tables
     if (geo) {
-        dev_geo = Geometry{b.qxy.p, 2, b.txy.p, 2, geo->H, geo->t2, geo->h_side};
+        dev_geo = Geometry{b.qxy.p, 2, b.txy.p, 2, geo->H, geo->t2, geo->side, geo->model};
         DLCO_HIP(hipMemcpyAsync(b.txy.p, geo->txy, (size_t)nt * 2 * sizeof(float), hipMemcpyHostToDevice, c->stream));
     }
     const Geometry *dg = geo ? &dev_geo : nullptr;
@@ -1068,7 +1080,7 @@ int dlco_desc_match_guided(dlco_desc_ctx *c, const float *query_host, const floa
     if (!c || !match_args_ok(query_host, train_host, idx_host, sqdist_host, nq, nt, r)) return DLCO_ERR_INVALID;
     if (!guided_args_ok(query_xy_host, train_xy_host, H, radius, h_side)) return DLCO_ERR_INVALID;
     return guarded(c, [&] {
-        const Geometry geo{query_xy_host, 2, train_xy_host, 2, H, verify_rules::threshold_sq(radius), h_side};
+        const Geometry geo{query_xy_host, 2, train_xy_host, 2, H, verify_rules::threshold_sq(radius), h_side, kGuideHomography};
         match_host<FloatLine>(c, query_host, nq, train_host, nt, r, idx_host, sqdist_host, nullptr, &geo);
     });
 }
@@ -1083,7 +1095,7 @@ int dlco_desc_match_guided_device(dlco_desc_ctx *c, const float *query_dev, int6
     if (!guided_args_ok(query_xy_dev, train_xy_dev, H, radius, h_side) || ldxy_q < 2 || ldxy_t < 2) return DLCO_ERR_INVALID;
     if (((uintptr_t)query_xy_dev | (uintptr_t)train_xy_dev) % 4 != 0) return DLCO_ERR_INVALID;
     return guarded(c, [&] {
-        const Geometry geo{query_xy_dev, (long)ldxy_q, train_xy_dev, (long)ldxy_t, H, verify_rules::threshold_sq(radius), h_side};
+        const Geometry geo{query_xy_dev, (long)ldxy_q, train_xy_dev, (long)ldxy_t, H, verify_rules::threshold_sq(radius), h_side, kGuideHomography};
         match_device<FloatLine>(c, query_dev, (long)ldq, nq, train_dev, (long)ldt, nt, r, idx_dev, sqdist_dev, &geo);
     });
 }
@@ -1096,7 +1108,50 @@ int dlco_desc_cross_sqdists_guided(dlco_desc_ctx *c, const float *query_host, co
     if (nq > ((int64_t)1 << 28) / nt) return DLCO_ERR_INVALID;
     if (!guided_args_ok(query_xy_host, train_xy_host, H, radius, h_side)) return DLCO_ERR_INVALID;
     return guarded(c, [&] {
-        const Geometry geo{query_xy_host, 2, train_xy_host, 2, H, verify_rules::threshold_sq(radius), h_side};
+        const Geometry geo{query_xy_host, 2, train_xy_host, 2, H, verify_rules::threshold_sq(radius), h_side, kGuideHomography};
+        match_host<FloatLine>(c, query_host, nq, train_host, nt, r, nullptr, nullptr, out_host, &geo);
+    });
+}
+
+// ---- guided matching under a fundamental matrix (guided_epipolar_rules.hpp; GUIDED 3 and 4 of the tile loop): the same host
+// path with a Geometry of the other model, records on both sides -------------------------------------------------------------
+int dlco_desc_match_guided_epipolar(dlco_desc_ctx *c, const float *query_host, const float *query_xy_host, int64_t nq, const float *train_host,
+                                    const float *train_xy_host, int64_t nt, int32_t r, const double *F, float threshold, int32_t f_side,
+                                    int32_t *idx_host, float *sqdist_host)
+{
+    if (!c || !match_args_ok(query_host, train_host, idx_host, sqdist_host, nq, nt, r)) return DLCO_ERR_INVALID;
+    if (!guided_args_ok(query_xy_host, train_xy_host, F, threshold, f_side)) return DLCO_ERR_INVALID;
+    return guarded(c, [&] {
+        const Geometry geo{query_xy_host, 2, train_xy_host, 2, F, verify_rules::threshold_sq(threshold), f_side, kGuideFundamental};
+        match_host<FloatLine>(c, query_host, nq, train_host, nt, r, idx_host, sqdist_host, nullptr, &geo);
+    });
+}
+
+int dlco_desc_match_guided_epipolar_device(dlco_desc_ctx *c, const float *query_dev, int64_t ldq, const float *query_xy_dev, int64_t ldxy_q,
+                                           int64_t nq, const float *train_dev, int64_t ldt, const float *train_xy_dev, int64_t ldxy_t, int64_t nt,
+                                           int32_t r, const double *F, float threshold, int32_t f_side, int32_t *idx_dev, float *sqdist_dev)
+{
+    if (!c || !match_args_ok(query_dev, train_dev, idx_dev, sqdist_dev, nq, nt, r)) return DLCO_ERR_INVALID;
+    if (ldq < r || ldt < r || ldq % 4 != 0 || ldt % 4 != 0) return DLCO_ERR_INVALID;
+    if (((uintptr_t)query_dev | (uintptr_t)train_dev) % 16 != 0) return DLCO_ERR_INVALID;          // 16-byte rows
+    if (!guided_args_ok(query_xy_dev, train_xy_dev, F, threshold, f_side) || ldxy_q < 2 || ldxy_t < 2) return DLCO_ERR_INVALID;
+    if (((uintptr_t)query_xy_dev | (uintptr_t)train_xy_dev) % 4 != 0) return DLCO_ERR_INVALID;
+    return guarded(c, [&] {
+        const Geometry geo{query_xy_dev, (long)ldxy_q, train_xy_dev, (long)ldxy_t, F, verify_rules::threshold_sq(threshold), f_side,
+                           kGuideFundamental};
+        match_device<FloatLine>(c, query_dev, (long)ldq, nq, train_dev, (long)ldt, nt, r, idx_dev, sqdist_dev, &geo);
+    });
+}
+
+int dlco_desc_cross_sqdists_guided_epipolar(dlco_desc_ctx *c, const float *query_host, const float *query_xy_host, int64_t nq,
+                                            const float *train_host, const float *train_xy_host, int64_t nt, int32_t r, const double *F,
+                                            float threshold, int32_t f_side, float *out_host)
+{
+    if (!c || !match_args_ok(query_host, train_host, out_host, out_host, nq, nt, r)) return DLCO_ERR_INVALID;
+    if (nq > ((int64_t)1 << 28) / nt) return DLCO_ERR_INVALID;
+    if (!guided_args_ok(query_xy_host, train_xy_host, F, threshold, f_side)) return DLCO_ERR_INVALID;
+    return guarded(c, [&] {
+        const Geometry geo{query_xy_host, 2, train_xy_host, 2, F, verify_rules::threshold_sq(threshold), f_side, kGuideFundamental};
         match_host<FloatLine>(c, query_host, nq, train_host, nt, r, nullptr, nullptr, out_host, &geo);
     });
 }

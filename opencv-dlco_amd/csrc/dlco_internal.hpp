@@ -531,9 +531,15 @@ void desc_pair_sqdist(const float *Y, long ld, int r, const int32_t *pairs, long
 void match_norms(const float *x, long ld, long n, int r, double *norm, hipStream_t s);
 // The geometry of a guided launch (the rule is guided_rules.hpp): rec [n][4] doubles, the records of the rows of the side the
 // homography applies to (match_records; 16-byte aligned), and xy, the (x, y) floats of the other side's rows at a pitch of
-// ldxy floats.  h_side 0: rec belongs to the launch's queries and xy to train; h_side 1: rec to train and xy to the queries.
-struct MatchGuide { const double *rec; const float *xy; long ldxy; int h_side; };
+// ldxy floats.  side 0: rec belongs to the launch's queries and xy to train; side 1: rec to train and xy to the queries.
+// The epipolar model (guided_epipolar_rules.hpp) has records on both sides and no xy: rec [nt][4] are train's, qrec [nq][4] the
+// launch's queries' (match_epi_records), the src records of the side F applies to (side 0: the queries, side 1: train) and
+// the dst records of the other; t2 is the squared threshold, which the pair predicate takes itself.
+enum { kGuideHomography = 0, kGuideFundamental = 1 };
+struct MatchGuide { const double *rec = nullptr; const float *xy = nullptr; long ldxy = 0; int side = 0; int model = kGuideHomography;
+                    const double *qrec = nullptr; double t2 = 0.0; };
 void match_records(const float *xy, long ld, long n, const double H[9], double t2, double *rec, hipStream_t s);
+void match_epi_records(const float *xy, long ld, long n, const double F[9], int dst_side, double *rec, hipStream_t s);
 void match_top2(const float *query, long ldq, int nq, const float *train, long ldt, int nt, int r, const double *qnorm, const double *tnorm,
                 int tiles_per_slice, int32_t *idx, float *sqdist, void *part, float *out, const MatchGuide *guide, hipStream_t s);
 // byte descriptors (kernels_match_u8.hip; the quantiser is quant_rules.hpp): float rows to bytes, and the match of byte tables

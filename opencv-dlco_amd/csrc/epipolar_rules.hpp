@@ -11,7 +11,7 @@
 // restatement agree in every bit.  The functions below switch contraction off themselves (VERIFY_RULES_NO_FMA).
 //
 // Out of scope: a device-memory form; a seven-point solver; an essential matrix; a choice between a homography and F; an
-// epipolar predicate for guided matching; an adaptive hypothesis count.
+// adaptive hypothesis count.  (The inlier test as the predicate of guided matching: guided_epipolar_rules.hpp.)
 //
 // Degeneracy, documented and not detected.  Matches related by a homography (a plane, a camera that only rotates, a shifted
 // image) satisfy a three-dimensional family of F.  The pivot floor below makes an exactly degenerate sample invalid; a nearly

@@ -18,6 +18,13 @@
 //                         blocks as a bit mask.  Distance, key, merge and slices are those of the plain form, so a guided answer is the top two of the plain matrix with +inf where the
 //                         predicate fails.  The predicate's arithmetic is reached through guided_rules.hpp alone, which
 //                         switches contraction off.
+//   match_epi_records_kernel, match_top2_kernel<.., GUIDED = 3, 4>   the epipolar guided forms (dlco_desc_match_guided_epipolar,
+//                         guided_epipolar_rules.hpp): both sides carry a record of 32 bytes a row, the src record of the
+//                         image F applies to and the dst record of the other.  GUIDED = 3: the queries are src (f_side 0);
+//                         GUIDED = 4: train is.  A train tile's records take the staging of GUIDED = 2, the queries' the
+//                         LDS fill of GUIDED = 1, and the verdict is guided_epipolar::admits, with t2 from MatchGuide.  MULTI
+//                         forms a tile's verdicts before the A fragments of its last chunk are fetched, one byte per
+//                         pair of column blocks: beside the epilogue, with every accumulator live, they cost scratch.
 //   match_merge_kernel    the top two of a query over the S slices of train, under the same key (the slicing rule:
 //                         match_slices.hpp)
 //
@@ -30,6 +37,7 @@
 // bounds (a row or piece beyond the edge reads a valid one and is replaced by zeros), stores are masked.
 #include "dlco_internal.hpp"
 #include "guided_rules.hpp"
+#include "guided_epipolar_rules.hpp"
 #include "match_slices.hpp"
 
 namespace dlco {
@@ -81,8 +89,8 @@ __global__ __launch_bounds__(MTH) void match_top2_kernel(const float *__restrict
                                                          int tiles_per_slice, int32_t *__restrict__ idx, float *__restrict__ sqdist,
                                                          i32x4 *__restrict__ part, float *__restrict__ out, const MatchGuide g)
 {
-    constexpr int CW = GUIDED == 2 ? 4 : 2;                // doubles of geometry a train row brings: (x, y) or a record
-    constexpr int QW = GUIDED == 1 ? 4 : 2;                // and a query
+    constexpr int CW = GUIDED >= 2 ? 4 : 2;                // doubles of geometry a train row brings: (x, y) or a record
+    constexpr int QW = GUIDED == 1 || GUIDED >= 3 ? 4 : 2; // and a query
     __shared__ double Bs[TN * MP];                         // the staged tile, widened to double once, when it is stored
     __shared__ double Tn[TN];
     __shared__ __attribute__((aligned(16))) double Tg[GUIDED ? TN * CW : 1];            // GUIDED: the tile's geometry, staged with it,
@@ -132,7 +140,7 @@ __global__ __launch_bounds__(MTH) void match_top2_kernel(const float *__restrict
             const float *p = g.xy + js * g.ldxy;
             rg[0] = (double)p[0]; rg[1] = (double)p[1];
         }
-        if constexpr (GUIDED == 2) {
+        if constexpr (GUIDED >= 2) {
             const f64x2 a = *reinterpret_cast<const f64x2 *>(g.rec + 4 * js), b = *reinterpret_cast<const f64x2 *>(g.rec + 4 * js + 2);
             rg[0] = a[0]; rg[1] = a[1]; rg[2] = b[0]; rg[3] = b[1];
         }
@@ -189,22 +197,36 @@ __global__ __launch_bounds__(MTH) void match_top2_kernel(const float *__restrict
         const int row = q0 + lg + 4 * rr;
         qn[rr] = qnorm[row < nq ? row : 0];
     }
-    // GUIDED: the geometry of the workgroup's queries, the record of a query (1) or its (x, y) (2), goes to LDS (the first
+    // GUIDED: the geometry of the workgroup's queries, the record of a query (1; 3, 4: from qrec) or its (x, y) (2), goes to LDS (the first
     // barrier of the loop below orders it) and is read again for every pair of column blocks: four rows' records held in
     // registers over the loop would put the kernel into scratch
     if constexpr (GUIDED != 0) {
         if (tid < MQ) {
             const long row = (long)blockIdx.x * MQ + tid;
             const long rs = row < nq ? row : 0;
-            if constexpr (GUIDED == 1) {
-                *reinterpret_cast<f64x2 *>(&Qg[tid * 4]) = *reinterpret_cast<const f64x2 *>(g.rec + 4 * rs);
-                *reinterpret_cast<f64x2 *>(&Qg[tid * 4 + 2]) = *reinterpret_cast<const f64x2 *>(g.rec + 4 * rs + 2);
+            if constexpr (GUIDED == 1 || GUIDED >= 3) {
+                const double *qr = GUIDED == 1 ? g.rec : g.qrec;
+                *reinterpret_cast<f64x2 *>(&Qg[tid * 4]) = *reinterpret_cast<const f64x2 *>(qr + 4 * rs);
+                *reinterpret_cast<f64x2 *>(&Qg[tid * 4 + 2]) = *reinterpret_cast<const f64x2 *>(qr + 4 * rs + 2);
             } else {
                 const float *p = g.xy + rs * g.ldxy;
                 *reinterpret_cast<f64x2 *>(&Qg[tid * 2]) = f64x2{(double)p[0], (double)p[1]};
             }
         }
     }
+    // GUIDED 3, 4: the verdict on the query whose record sits at q and the column c, whichever of the two is src
+    auto epi_admits = [&](const double *q, const ColGeom &c) -> bool {
+        if constexpr (GUIDED >= 3) {
+            const f64x2 q0v = *reinterpret_cast<const f64x2 *>(q), q1v = *reinterpret_cast<const f64x2 *>(q + 2);
+            if constexpr (GUIDED == 3)
+                return guided_epipolar::admits(guided_epipolar::SrcRec{q0v[0], q0v[1], q1v[0], q1v[1]},
+                                               guided_epipolar::DstRec{c.v[0], c.v[1], c.v[2], c.v[3]}, g.t2);
+            else
+                return guided_epipolar::admits(guided_epipolar::SrcRec{c.v[0], c.v[1], c.v[2], c.v[3]},
+                                               guided_epipolar::DstRec{q0v[0], q0v[1], q1v[0], q1v[1]}, g.t2);
+        }
+        return true;
+    };
     // GUIDED: which of the eight entries of the column blocks at c0 and c0 + 16 of the staged tile the rule admits, bit e as
     // prev_entry counts them.  One burst of LDS reads and fp64 VALU work per pair of blocks, whose only result that lives
     // on is the mask.  The empty asm hides from the compiler that the queries' address does not change over the tile loop:
@@ -224,6 +246,9 @@ __global__ __launch_bounds__(MTH) void match_top2_kernel(const float *__restrict
                     const guided_rules::Rec rec{q0v[0], q0v[1], q1v[0], q1v[1]};
                     m |= (guided_rules::admits(rec, a.v[0], a.v[1]) ? 1u : 0u) << rr;
                     m |= (guided_rules::admits(rec, b.v[0], b.v[1]) ? 1u : 0u) << (4 + rr);
+                } else if constexpr (GUIDED >= 3) {
+                    m |= (epi_admits(q, a) ? 1u : 0u) << rr;
+                    m |= (epi_admits(q, b) ? 1u : 0u) << (4 + rr);
                 } else {
                     const f64x2 uv = *reinterpret_cast<const f64x2 *>(q);
                     m |= (guided_rules::admits(guided_rules::Rec{a.v[0], a.v[1], a.v[2], a.v[3]}, uv[0], uv[1]) ? 1u : 0u) << rr;
@@ -302,6 +327,16 @@ __global__ __launch_bounds__(MTH) void match_top2_kernel(const float *__restrict
         if (wave_on) {
             if (MULTI) {
                 const int tile = step / nch, kc = step - tile * nch;
+                // GUIDED 3, 4: the verdicts of the whole tile, a byte per pair of column blocks, before the chunk's A fragments
+                // are fetched: between two chunks their registers are free, and 16 doubles of geometry fit without scratch
+                unsigned mtile = 0;
+                if constexpr (GUIDED >= 3) {
+                    if (kc == nch - 1) {
+#pragma unroll
+                        for (int sub = 0; sub < NSUB; sub += 2) mtile |= admit_mask(16 * sub + li) << (4 * sub);
+                    }
+                    asm volatile("" : "+v"(mtile));           // formed here, not beside the epilogue below
+                }
                 aload(kc);
 #pragma unroll
                 for (int sub = 0; sub < NSUB; sub += 2) {
@@ -309,7 +344,7 @@ __global__ __launch_bounds__(MTH) void match_top2_kernel(const float *__restrict
                     mfma_pair(sub, acc[sub], acc[sub + 1], false);
                     if (kc == nch - 1) {
                         const long jl = (long)jbeg + (long)tile * TN + 16 * sub + li;
-                        const unsigned m = admit_mask(16 * sub + li);
+                        const unsigned m = GUIDED >= 3 ? (mtile >> (4 * sub)) & 0xffu : admit_mask(16 * sub + li);
 #pragma unroll
                         for (int rr = 0; rr < 4; rr++) {
                             entry(acc[sub][rr], rr, Tn[16 * sub + li], jl, m, rr);
@@ -386,6 +421,26 @@ __global__ __launch_bounds__(256) void match_records_kernel(const float *__restr
     *reinterpret_cast<f64x2 *>(rec + 4 * i + 2) = f64x2{r.W, r.T};
 }
 
+// the epipolar records of n rows (x, y) under F: rec [n][4] = the src record (l0, l1, l2, L) of a row of the image F applies to
+// (dst_side 0) or the dst record (u, v, A, B) of a row of the other (dst_side 1), one lane per row
+__global__ __launch_bounds__(256) void match_epi_records_kernel(const float *__restrict__ xy, long ld, long n, const H9 F, int dst_side,
+                                                                double *__restrict__ rec)
+{
+    const long i = (long)blockIdx.x * 256 + threadIdx.x;
+    if (i >= n) return;
+    const double x = (double)xy[i * ld], y = (double)xy[i * ld + 1];
+    f64x2 lo, hi;
+    if (dst_side) {
+        const guided_epipolar::DstRec d = guided_epipolar::dst_record(F.h, x, y);
+        lo = f64x2{d.u, d.v}; hi = f64x2{d.A, d.B};
+    } else {
+        const guided_epipolar::SrcRec s = guided_epipolar::src_record(F.h, x, y);
+        lo = f64x2{s.l0, s.l1}; hi = f64x2{s.l2, s.L};
+    }
+    *reinterpret_cast<f64x2 *>(rec + 4 * i) = lo;
+    *reinterpret_cast<f64x2 *>(rec + 4 * i + 2) = hi;
+}
+
 constexpr int NTH = 256;               // four rows per workgroup, one wave each
 
 __global__ __launch_bounds__(NTH) void match_norms_kernel(const float *__restrict__ x, long ld, long n, int r, double *__restrict__ norm)
@@ -420,6 +475,15 @@ void match_records(const float *xy, long ld, long n, const double H[9], double t
     DLCO_HIP(hipGetLastError());
 }
 
+void match_epi_records(const float *xy, long ld, long n, const double F[9], int dst_side, double *rec, hipStream_t s)
+{
+    if (n <= 0) return;
+    H9 f;
+    for (int i = 0; i < 9; i++) f.h[i] = F[i];
+    hipLaunchKernelGGL(match_epi_records_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, xy, ld, n, f, dst_side, rec);
+    DLCO_HIP(hipGetLastError());
+}
+
 // query [nq][ldq], train [nt][ldt], norms from match_norms.  out != nullptr: the matrix out[nq][nt]; else idx / sqdist
 // [nq][2], through part [slices][nq] (16 bytes each) when the tiles_per_slice leaves more than one slice.  guide: nullptr, or
 // the geometry of the guided form (dlco_internal.hpp).
@@ -431,7 +495,7 @@ void match_top2(const float *query, long ldq, int nq, const float *train, long l
     const dim3 grid((unsigned)((nq + MQ - 1) / MQ), (unsigned)slices);
     i32x4 *pp = (!out && slices > 1) ? static_cast<i32x4 *>(part) : nullptr;
     const bool multi = r > KC;
-    const MatchGuide g = guide ? *guide : MatchGuide{nullptr, nullptr, 0, 0};
+    const MatchGuide g = guide ? *guide : MatchGuide{};
 #define DLCO_MATCH_LAUNCH(ST, MU, GU)                                                                                                 \
     hipLaunchKernelGGL((match_top2_kernel<ST, MU, GU>), grid, dim3(MTH), 0, s, query, ldq, nq, train, ldt, nt, r, qnorm, tnorm,       \
                        tiles_per_slice, idx, sqdist, pp, out, g)
@@ -441,8 +505,10 @@ void match_top2(const float *query, long ldq, int nq, const float *train, long l
         else     { if (multi) DLCO_MATCH_LAUNCH(false, true, GU); else DLCO_MATCH_LAUNCH(false, false, GU); }                         \
     } while (0)
     if (!guide) DLCO_MATCH_FORM(0);
-    else if (g.h_side == 0) DLCO_MATCH_FORM(1);
-    else DLCO_MATCH_FORM(2);
+    else if (g.model == kGuideHomography && g.side == 0) DLCO_MATCH_FORM(1);
+    else if (g.model == kGuideHomography) DLCO_MATCH_FORM(2);
+    else if (g.side == 0) DLCO_MATCH_FORM(3);
+    else DLCO_MATCH_FORM(4);
 #undef DLCO_MATCH_FORM
 #undef DLCO_MATCH_LAUNCH
     DLCO_HIP(hipGetLastError());

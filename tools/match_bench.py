@@ -11,7 +11,14 @@ same run beside it, the int8 MFMA floor 2 nq nt r / 5.0 POP/s (twice the dense B
 With --guided the rows get keypoints, uniform in a square of side 8 sqrt(nt) (one per 64 px^2), a mild homography and radius
 12 (about seven admitted train rows a query), and dlco_desc_match_guided_device is timed for both h_side beside the plain
 call: one warm-up each, then three rounds that alternate plain, h_side 0, h_side 1.  The line shows the three times, the
-guided calls' ratio to the plain one and their share of the f64 MFMA floor, and how many queries found two admitted rows."""
+guided calls' ratio to the plain one and their share of the f64 MFMA floor, and how many queries found two admitted rows.
+
+With --guided-epipolar the same keypoints get, beside that homography H, the fundamental matrix F = [e']x H with the epipole
+e' = (3 S, 0.4 S, 1), S the side of the square, divided by its largest magnitude, and the threshold 2 of the tests:
+dlco_desc_match_guided_epipolar_device is timed for both f_side beside the plain call and the homography-guided call of the
+same run, one warm-up each, then three rounds that alternate the five calls.  The line shows the five times with their rounds,
+the epipolar calls' ratio to the plain call and to the homography-guided call of the same side, and how many queries found two
+admitted rows."""
 import importlib, os, sys
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch
@@ -25,6 +32,9 @@ if U8:
 GUIDED = "--guided" in sys.argv
 if GUIDED:
     sys.argv.remove("--guided")
+EPI = "--guided-epipolar" in sys.argv
+if EPI:
+    sys.argv.remove("--guided-epipolar")
 SHAPES = [(2048, 2048, 64), (8192, 8192, 64), (8192, 8192, 128), (100000, 100000, 128)]
 if len(sys.argv) > 1:
     SHAPES = [tuple(int(v) for v in a.split(",")) for a in sys.argv[1:]]
@@ -54,7 +64,7 @@ for nq, nt, r in SHAPES:
     d = torch.empty((nq, 2), dtype=torch.float32, device="cuda:0")
     torch.cuda.synchronize()
     call = lambda: ctx.match_device(Q.data_ptr(), nq, T.data_ptr(), nt, r, idx.data_ptr(), d.data_ptr())
-    if GUIDED:
+    if GUIDED or EPI:
         import numpy as np
         S = 8.0 * nt ** 0.5
         H = np.array([[0.98, -0.05, 0.03 * S], [0.04, 1.02, -0.02 * S], [0.02 / S, -0.01 / S, 1.0]])
@@ -65,9 +75,17 @@ for nq, nt, r in SHAPES:
         torch.cuda.synchronize()
         calls = [call] + [lambda h=h: ctx.match_guided_device(Q.data_ptr(), qxy.data_ptr(), nq, T.data_ptr(), txy.data_ptr(), nt, r, H, gi[h].data_ptr(),
                                                               gd[h].data_ptr(), radius=12.0, h_side=h) for h in (0, 1)]
+        if EPI:
+            F = np.array([[0.0, -1.0, 0.4 * S], [1.0, 0.0, -3.0 * S], [-0.4 * S, 3.0 * S, 0.0]]) @ H
+            F = F / np.abs(F).max()
+            ei = [torch.empty((nq, 2), dtype=torch.int32, device="cuda:0") for _ in range(2)]
+            ed = [torch.empty((nq, 2), dtype=torch.float32, device="cuda:0") for _ in range(2)]
+            torch.cuda.synchronize()
+            calls += [lambda h=h: ctx.match_guided_epipolar_device(Q.data_ptr(), qxy.data_ptr(), nq, T.data_ptr(), txy.data_ptr(), nt, r, F, ei[h].data_ptr(),
+                                                                   ed[h].data_ptr(), threshold=2.0, f_side=h) for h in (0, 1)]
         for f in calls:
             f()
-        ms3 = [[], [], []]
+        ms3 = [[] for _ in calls]
         for _ in range(3):
             for k, f in enumerate(calls):
                 f()
@@ -75,6 +93,16 @@ for nq, nt, r in SHAPES:
         best, floor = [min(m) for m in ms3], 1e3 * 2.0 * nq * nt * r / PEAK
         two = [100 * float((g[:, 1] >= 0).float().mean()) for g in gi]
         fmt = lambda m: " ".join("%.3f" % v for v in m)
+        if EPI:
+            two_e = [100 * float((g[:, 1] >= 0).float().mean()) for g in ei]
+            print(f"match_guided_epipolar {nq} x {nt} r {r}: plain {best[0]:.3f} ms (rounds {fmt(ms3[0])}), homography h_side 0 {best[1]:.3f} ms (rounds "
+                  f"{fmt(ms3[1])}), h_side 1 {best[2]:.3f} ms (rounds {fmt(ms3[2])}), epipolar f_side 0 {best[3]:.3f} ms (rounds {fmt(ms3[3])}), f_side 1 "
+                  f"{best[4]:.3f} ms (rounds {fmt(ms3[4])}); epipolar / plain {best[3] / best[0]:.3f} and {best[4] / best[0]:.3f}, homography / plain "
+                  f"{best[1] / best[0]:.3f} and {best[2] / best[0]:.3f}, epipolar / homography {best[3] / best[1]:.3f} and {best[4] / best[2]:.3f}; f64 MFMA "
+                  f"floor {floor:.3f} ms; two admitted rows for {two_e[0]:.1f} % and {two_e[1]:.1f} % of the queries (homography: {two[0]:.1f} % and "
+                  f"{two[1]:.1f} %)", flush=True)
+            del T, Q, idx, d, txy, qxy, gi, gd, ei, ed
+            continue
         print(f"match_guided {nq} x {nt} r {r}: plain {best[0]:.3f} ms (rounds {fmt(ms3[0])}), h_side 0 {best[1]:.3f} ms (rounds {fmt(ms3[1])}), "
               f"h_side 1 {best[2]:.3f} ms (rounds {fmt(ms3[2])}); guided / plain {best[1] / best[0]:.3f} and {best[2] / best[0]:.3f}; f64 MFMA floor "
               f"{floor:.3f} ms, share of the floor: plain {floor / best[0]:.3f}, guided {floor / best[1]:.3f} and {floor / best[2]:.3f}; two admitted rows "
