@@ -292,6 +292,25 @@ int dlco_gemm_probe(dlco_ctx *ctx, const dlco_gemm_probe_args *args, float *C_ho
  * every row whose pivot fell below rel_thresh times its diagonal entry of M (that row of Linv is zero). */
 int dlco_chol_probe(dlco_ctx *ctx, const float *M_host, int32_t n, int32_t ld, float rel_thresh, float *Linv_host,
                     int32_t *dead_host);
+/* The tail of one eigen-tracker pass on host arrays, for tests (no reference line): the last filter product
+ * Z' = alpha * Z * G + b1 * Z + b2 * Zprev (split-bf16, two-way), CholQR2 of Z' -> Qo, the exact product Yb = -Qo * G and
+ * T = Yb * Qo^T.  The context's F must be whole 128-column tiles (at most 64).  Gp_host is G as its packed upper tiles:
+ * tile (I, J), I <= J, is a contiguous row-major 128 x 128 block at tile index I*nt - I*(I-1)/2 + (J - I), nt = F / 128,
+ * diagonal tiles stored whole.  Zprev_host may be NULL (no third term).  panel_end = 0 and n_lock = 0: the block is one
+ * orthonormalisation panel, the steady state; panel_end cuts a second panel there, n_lock > 0 leaves that many leading rows
+ * as they are.  unfused != 0 forces every Gram product, every application of L^-1 and the split of Qo into a launch of
+ * its own.  Qo_host, Yb_host [m, F], T_host [m, m]; fused (may be NULL): [0] = reductions that also formed the Gram
+ * partials behind them, [1] = applications of L^-1 that also fed the next launch (two each in the steady state). */
+typedef struct dlco_ortho_probe_args {
+    const float *Z_host, *Zprev_host, *Gp_host;
+    int32_t m, panel_end, n_lock, unfused;
+    float   alpha, b1, b2;
+} dlco_ortho_probe_args;
+int dlco_ortho_probe(dlco_ctx *ctx, const dlco_ortho_probe_args *args, float *Qo_host, float *Yb_host, float *T_host,
+                     int64_t fused[2]);
+/* out[0] = product reductions of the context's eigen tracker that also formed the Gram partials behind them; out[1] =
+ * CholQR applications of L^-1 that also fed the next launch (Gram partials or split planes). */
+int dlco_fused_counters(const dlco_ctx *ctx, int64_t out[2]);
 /* H1: sum_i sum_j max(pos_i + 1 - neg_j, 0)  (src/kernelop-opencv.cu:49-80). */
 int dlco_hinge_sum(dlco_ctx *ctx, const float *pos_host, int32_t n_pos,
                    const float *neg_host, int32_t n_neg, double *out);

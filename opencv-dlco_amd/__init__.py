@@ -72,6 +72,14 @@ class GemmProbeArgs(C.Structure):
     ]
 
 
+class OrthoProbeArgs(C.Structure):
+    _fields_ = [
+        ("Z_host", C.POINTER(C.c_float)), ("Zprev_host", C.POINTER(C.c_float)), ("Gp_host", C.POINTER(C.c_float)),
+        ("m", C.c_int32), ("panel_end", C.c_int32), ("n_lock", C.c_int32), ("unfused", C.c_int32),
+        ("alpha", C.c_float), ("b1", C.c_float), ("b2", C.c_float),
+    ]
+
+
 def build(verbose=False):
     """Compile libdlco.so in-tree with hipcc for gfx950 (cross-compiles without a GPU)."""
     cmd = ["make", "-C", os.path.join(_HERE, "csrc"), "-j8"]
@@ -136,6 +144,8 @@ def load():
     L.dlco_sym_product.argtypes = [vp, f32p, C.c_int32, f32p, C.c_int32, f32p]
     L.dlco_gemm_probe.argtypes = [vp, C.POINTER(GemmProbeArgs), f32p, f32p, i32p, C.POINTER(C.c_double)]
     L.dlco_chol_probe.argtypes = [vp, f32p, C.c_int32, C.c_int32, C.c_float, f32p, i32p]
+    L.dlco_ortho_probe.argtypes = [vp, C.POINTER(OrthoProbeArgs), f32p, f32p, f32p, C.POINTER(C.c_int64)]
+    L.dlco_fused_counters.argtypes = [vp, C.POINTER(C.c_int64)]
     L.dlco_roc_stats.argtypes = [vp, f32p, u8p, C.c_int32, f32p, C.POINTER(C.c_double)]
     L.dlco_log_step.argtypes = [vp, C.POINTER(LogEntry)]
     L.dlco_get_saved.argtypes = [vp, f32p, i32p, f32p]
@@ -547,6 +557,24 @@ class Context:
         self._ck(self.L.dlco_chol_probe(self.h, _p(m, f32p), n, n, rel_thresh, _p(linv, f32p), _p(dead, i32p)))
         return linv, dead
 
+    def ortho_probe(self, Z, Gp, alpha, b1, b2=0.0, Zprev=None, panel_end=0, n_lock=0, unfused=False):
+        """The tail of one tracker pass (dlco_ortho_probe): Z [m, F], Gp = the packed upper tiles of G (a flat array,
+        layout in dlco.h).  Returns dict(Qo [m, F], Yb [m, F], T [m, m], fused = reductions that formed Gram partials,
+        applied = applications of L^-1 that fed the next launch)."""
+        z, gp = _f32(Z), _f32(Gp).ravel()
+        zp = None if Zprev is None else _f32(Zprev)
+        m, F = z.shape
+        nt = F // 128
+        assert F == self.F and F % 128 == 0 and gp.size == nt * (nt + 1) // 2 * 128 * 128 and (zp is None or zp.shape == z.shape)
+        a = OrthoProbeArgs()
+        a.Z_host, a.Zprev_host, a.Gp_host = _p(z, f32p), _p(zp, f32p), _p(gp, f32p)
+        a.m, a.panel_end, a.n_lock, a.unfused = m, panel_end, n_lock, int(unfused)
+        a.alpha, a.b1, a.b2 = alpha, b1, b2
+        qo, yb, t = np.zeros((m, F), np.float32), np.zeros((m, F), np.float32), np.zeros((m, m), np.float32)
+        fused = (C.c_int64 * 2)()
+        self._ck(self.L.dlco_ortho_probe(self.h, C.byref(a), _p(qo, f32p), _p(yb, f32p), _p(t, f32p), fused))
+        return dict(Qo=qo, Yb=yb, T=t, fused=fused[0], applied=fused[1])
+
     def hinge_sum(self, pos, neg):
         p, n = _f32(pos), _f32(neg)
         out = C.c_double()
@@ -571,7 +599,9 @@ class Context:
     def counters(self):
         out = (C.c_int64 * 8)()
         self._ck(self.L.dlco_counters(self.h, out))
-        return dict(steps=out[0], active_rows=out[1], nonconverged=out[2], jacobi_barrier_timeouts=out[3],
+        fused = (C.c_int64 * 2)()
+        self._ck(self.L.dlco_fused_counters(self.h, fused))
+        return dict(fused_gram_reductions=fused[0], fused_applications=fused[1], steps=out[0], active_rows=out[1], nonconverged=out[2], jacobi_barrier_timeouts=out[3],
                     rank_update_passes=out[4], rank_update_check=out[5] * 1e-9, locked_passes=out[6], locked_rows=out[7])
 
     def eig_stats(self):

@@ -1377,6 +1377,41 @@ int dlco_chol_probe(dlco_ctx *c, const float *M_host, int32_t n, int32_t ld, flo
     });
 }
 
+int dlco_ortho_probe(dlco_ctx *c, const dlco_ortho_probe_args *a, float *Qo_host, float *Yb_host, float *T_host, int64_t fused[2])
+{
+    if (!c || !a || !a->Z_host || !a->Gp_host || !Qo_host || !Yb_host || !T_host) return DLCO_ERR_INVALID;
+    if (a->m < 1 || a->m > CHOL_INV_MAX_N || a->n_lock < 0 || a->n_lock >= a->m || a->panel_end < 0) return DLCO_ERR_INVALID;
+    return guarded(c, [&] {
+        DLCO_HIP(hipSetDevice(c->cfg.device));
+        const int F = c->F, m = a->m;
+        DLCO_CHECK(c->Fu == F && EigTracker::packed_supported(F), DLCO_ERR_INVALID, "dlco_ortho_probe: F must be whole 128-column tiles, 64 at the most");
+        const size_t rows = (size_t)m * F;
+        DevBuf<float> X, Xprev, Gp, Qo, Yb, T;
+        X.alloc(rows); Qo.alloc(rows); Yb.alloc(rows); T.alloc((size_t)m * m);
+        Gp.alloc(syrk_packed_floats(F));
+        h2d(c, X.p, a->Z_host, rows * sizeof(float));
+        if (a->Zprev_host) { Xprev.alloc(rows); h2d(c, Xprev.p, a->Zprev_host, rows * sizeof(float)); }
+        h2d(c, Gp.p, a->Gp_host, syrk_packed_floats(F) * sizeof(float));
+        EigTracker t(F, m, 8, c->cfg.eig_tol, c->cfg.eig_max_iter, c->stream);
+        t.set_packed(true);
+        t.set_fuse_gram(a->unfused == 0);
+        t.ortho_probe(X.p, a->Zprev_host ? Xprev.p : nullptr, m, Gp.p, a->alpha, a->b1, a->b2, a->panel_end, a->n_lock, Qo.p, Yb.p, T.p);
+        sync(c);
+        d2h(c, Qo_host, Qo.p, rows * sizeof(float));
+        d2h(c, Yb_host, Yb.p, rows * sizeof(float));
+        d2h(c, T_host, T.p, (size_t)m * m * sizeof(float));
+        if (fused) { fused[0] = t.stats().fused_gram_reductions; fused[1] = t.stats().fused_applications; }
+    });
+}
+
+int dlco_fused_counters(const dlco_ctx *c, int64_t out[2])
+{
+    if (!c || !out) return DLCO_ERR_INVALID;
+    out[0] = c->eig->stats().fused_gram_reductions;
+    out[1] = c->eig->stats().fused_applications;
+    return DLCO_OK;
+}
+
 int dlco_hinge_sum(dlco_ctx *c, const float *pos_host, int32_t n_pos, const float *neg_host, int32_t n_neg, double *out)
 {
     if (!c || !out || n_pos < 0 || n_neg < 0) return DLCO_ERR_INVALID;

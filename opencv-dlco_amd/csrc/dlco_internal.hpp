@@ -246,10 +246,20 @@ struct SkinnyArgs {
     float *slab = nullptr;              // bf16x2: >= bf16x2_slab_floats(M, N, ksplit) floats; sym: >= 4*M*F
     int ksplit = 0;                     // bf16x2: number of K slices (grid y, 0 = the default 4); K must be a multiple of 128 * ksplit.
                                         // A column slab of G (N < K) takes ksplit = 4 * K / N so that the launch still fills the chip.
-    // sym only.  planes_ready: planes.hi / lo already hold the two-way planes of X (skip the split); emit_planes: the reduction
+    // sym only.  planes_ready: the planes already hold the split of X, two-way or, with planes.lo2, three-way (skip the split); emit_planes: the reduction
     // also writes the two-way planes of the RESULT into planes.hi / lo (the next product of a Chebyshev chain takes it as X)
     bool planes_ready = false;
     bool emit_planes = false;
+    // sym only, M <= 96, without emit_planes.  gram_slab != nullptr: the reduction also writes the raw K-slice partials
+    // [K / gram_chunk][M][M] of C * C^T (gram_with == nullptr) or of C * gram_with^T (gram_with [M][gram_ld]), bit for bit
+    // what gemm_f32 puts into its slab for that product split into slices of gram_chunk (64 or 128) columns; the caller
+    // finishes with splitk_reduce_f32.  *gram_done (host, optional) is set when that form ran; otherwise the plain
+    // reduction ran and the caller forms the Gram product itself.
+    const float *gram_with = nullptr;
+    long gram_ld = 0;
+    float *gram_slab = nullptr;
+    int gram_chunk = 0;
+    bool *gram_done = nullptr;
 };
 bool skinny_product_bf16x2(const SkinnyArgs &a, hipStream_t s);
 // P1 + P2 for many rows without the r x N projection (kernels_project.hip): dist[n] = |W x_n|^2, x_n = row ids[n] (or
@@ -360,6 +370,23 @@ void syrk_unpack_upper(const float *packed, int F, float *C, long ldc, hipStream
 // from HBM once (kernels_bf16x2.hip, skinny_sym_kernel).  F == 8192 only (64 x 64 tiles on 8 XCDs x 32 CUs); M <= 160
 // (two-way split) / 96 (three-way, planes.lo2 != nullptr).  slab: >= 4*M*F floats.  Returns false for other shapes.
 bool skinny_product_sym(const SkinnyArgs &a, hipStream_t s);
+// its reduction alone where it is the form that also emits the Gram partials (SkinnyArgs::gram_slab); false: nothing launched
+bool reduce_gram_sym(const SkinnyArgs &a, hipStream_t s);
+// CholQR's dst[n][F] = Linv[n][n] * src[n][F] (n <= 96, F whole 128-column tiles) with gemm_f32's bits, by column slabs,
+// and one of: the raw Gram partials of dst (gram_slab [F / gram_chunk][n][n], as SkinnyArgs::gram_slab) or the three-way
+// split planes of dst (all of planes.hi / lo / lo2).  Returns false, nothing launched, for other shapes.
+struct LinvApplyArgs {
+    const float *Linv = nullptr;
+    long ldl = 0;
+    int n = 0, F = 0;
+    const float *src = nullptr;
+    float *dst = nullptr;
+    long ld = 0;
+    float *gram_slab = nullptr;
+    int gram_chunk = 0;
+    SplitPlanes planes;
+};
+bool linv_apply_slab(const LinvApplyArgs &a, hipStream_t s);
 size_t gemm_slab_floats(int M, int N, int split_k);
 // K slices (GemmArgs::split_k) for a product whose M x N tile grid alone would leave the chip idle: enough that
 // tiles * slices reaches `target` workgroups, no slice shorter than kmin, no more slices than the slab holds
@@ -371,6 +398,9 @@ inline int split_k_slices(long tiles, long target, long K, long kmin, long slab_
 }
 void splitk_reduce_f32(const float *slab, int split, int M, int N, float *C, long ldc, float alpha, float beta,
                        const float *E1, float b1, const float *E2, float b2, hipStream_t s);
+// which of its two kernels splitk_reduce_f32 takes for these arguments: the wide one adds the slices one after the other,
+// the other one pairs them in a butterfly over 16 lanes.  A kernel that stands in for the launch has to add the same way.
+bool splitk_reduce_is_wide(const float *slab, int split, int M, int N, const float *C, long ldc, const float *E1, const float *E2);
 
 // ---------------------------------------------------------------------------
 // step kernels (kernels_step.hip)

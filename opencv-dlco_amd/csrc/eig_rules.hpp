@@ -27,6 +27,27 @@ struct Block {
     float mu = 0.f, cscale = 0.f, tol = 0.f;
 };
 
+// K slices of a Gram product X * Y^T over K = F columns whose output is `tiles` tiles of the generic GEMM: enough slices
+// that 512 workgroups run, none shorter than 64 columns (128 at F = 8192: with 128 slices of 64 the launch is no faster
+// and the ordered reduce reads twice as much, 593 -> 608 k on c2; ten slices of 64 at the reference's F = 640, where five
+// of 128 measured 2.5 % slower), no more than the slab holds (slab_cap = slab floats / output floats).  split_k is what the
+// GEMM is asked for; chunk and slices are what it makes of that (whole 16-column K tiles per slice).  Both the GEMM form
+// and the reduction that emits the partials itself (reduce_gram_kernel) slice by this rule; the latter needs whole().
+struct GramSlicing {
+    int split_k = 1, chunk = 0, slices = 1;
+    // every slice is 64 or 128 columns, none is short, and none straddles a 128-column slab
+    bool whole(long F) const { return (chunk == 64 || chunk == 128) && (long)chunk * slices == F && F % 128 == 0; }
+};
+inline GramSlicing gram_slicing(long F, long tiles, long slab_cap)
+{
+    GramSlicing g;
+    const long kslice = std::max(64L, F / 64 / 64 * 64);
+    g.split_k = (int)std::max(1L, std::min(std::min((512 + tiles - 1) / tiles, F / kslice), slab_cap));
+    g.chunk = (int)std::max(16L, ((F + g.split_k - 1) / g.split_k + 15) / 16 * 16);
+    g.slices = F > 0 ? (int)((F + g.chunk - 1) / g.chunk) : 1;
+    return g;
+}
+
 // How many updates may pass between two refreshes of the lower spectral bound: lambda_max(G) drifts as 1/t
 inline int lower_bound_period(int64_t updates)
 {

@@ -21,6 +21,14 @@ struct EigTracker::PlaneChain {
     bool next = false;                  // the product being issued feeds the next one of the chain
 };
 
+// A product whose result goes straight into a Gram product (CholQR's first pass, the Rayleigh-Ritz T): its reduction may
+// form that product's K-slice partials while the result is still on chip (skinny_product_sym).  `done` then tells the
+// caller to finish with gram_finish() instead of gram_rect().
+struct EigTracker::GramTail {
+    const float *with = nullptr;        // the second row block; nullptr: the result itself
+    bool done = false;
+};
+
 EigTracker::EigTracker(int F, int max_rows, int guard, float tol, int max_iter, hipStream_t stream, int live_cols)
     : F_(F), live_(live_cols > 0 ? std::min(live_cols, F) : F), guard_(guard), max_iter_(max_iter), tol_(tol), s_(stream)
 {
@@ -132,7 +140,7 @@ void EigTracker::append_random(float *Q, int have, int add)
 
 // out[rows][F] = alpha * X*G + b1*E1 + b2*E2     (G symmetric F x F)
 void EigTracker::product(const float *X, int rows, const float *G, float alpha, float *out, const float *E1, float b1,
-                         const float *E2, float b2, bool approx, PlaneChain *chain)
+                         const float *E2, float b2, bool approx, PlaneChain *chain, GramTail *gram)
 {
     // the split-bf16 kernels take up to 128 rows: a taller block goes through them in row chunks
     // (one HBM-bound pass over G per chunk, still cheaper than the generic fp32 GEMM)
@@ -163,11 +171,25 @@ void EigTracker::product(const float *X, int rows, const float *G, float alpha, 
         // for the exact products (rows <= 96 there: the chunking above)
         if (prof_) prof_->begin(PROF_EIG_PRODUCT);
         // inside a filter chain the planes of X are those the previous product's reduction emitted
-        const bool ready = approx && chain && chain->planes_of == X && chain->rows == rows;
+        // (an exact product right behind CholQR finds the three-way planes its second pass wrote)
+        const bool ready = (approx && chain && chain->planes_of == X && chain->rows == rows) ||
+                           (!approx && planes3_of_ == X && planes3_rows_ == rows);
+        planes3_of_ = nullptr;                                   // whatever runs now overwrites the planes
         const bool emit = approx && chain && chain->next;
         a.G = G; a.N = F_;
         a.planes_ready = ready; a.emit_planes = emit;
+        if (gram && fuse_gram_ && !emit && rows <= 96) {
+            // the Gram partials go behind the product's own four slabs
+            const eig_rules::GramSlicing gs = gram_slices(rows, rows);
+            const size_t off = (size_t)4 * rows * F_;
+            if (gs.whole(F_) && off + (size_t)gs.slices * rows * rows <= slab_floats_) {
+                a.gram_with = gram->with; a.gram_ld = F_;
+                a.gram_slab = slab_.p + off; a.gram_chunk = gs.chunk;
+                a.gram_done = &gram->done;
+            }
+        }
         const bool ok = skinny_product_sym(a, s_);
+        if (gram && gram->done) st_.fused_gram_reductions++;
         if (chain) { chain->planes_of = emit ? out : nullptr; chain->rows = rows; }   // (a product without `emit` has overwritten the planes with X's)
         if (prof_) prof_->end(PROF_EIG_PRODUCT);
         DLCO_CHECK(ok, -2, "eig tracker: the symmetric product rejected a shape of the packed layout");
@@ -250,14 +272,22 @@ void EigTracker::gram_rect(const float *X, int xrows, const float *Y, int yrows,
     g.A.p = X; g.A.ld = F_; g.A.kmajor = false;
     g.B.p = Y; g.B.ld = F_; g.B.kmajor = false;
     g.C = T; g.ldc = cap_;
-    const long tiles = (long)ceil_div(xrows, xrows <= 64 ? 64 : 128) * ceil_div(yrows, yrows <= 64 ? 64 : 128);
-    // (at most 64 K slices, none shorter than 64: 64 slices of 128 at F = 8192 - with 128 slices of 64 the launch is no faster
-    // and the ordered reduce reads twice as much, 593 -> 608 k on c2 - and ten slices of 64 at the reference's F = 640, where five
-    // of 128 measured 2.5 % slower)
-    const long kslice = std::max(64L, (long)F_ / 64 / 64 * 64);
-    g.split_k = split_k_slices(tiles, 512, F_, kslice, (long)(slab_floats_ / ((size_t)xrows * yrows)));
+    g.split_k = gram_slices(xrows, yrows).split_k;
     g.slab = slab_.p;
     gemm_f32(g, s_);
+}
+
+eig_rules::GramSlicing EigTracker::gram_slices(int xrows, int yrows) const
+{
+    const long tiles = (long)ceil_div(xrows, xrows <= 64 ? 64 : 128) * ceil_div(yrows, yrows <= 64 ? 64 : 128);
+    return eig_rules::gram_slicing(F_, tiles, (long)(slab_floats_ / ((size_t)xrows * yrows)));
+}
+
+// T[rows][rows] (ld cap_) from the partials a product's reduction left behind its slabs (GramTail::done): gram_rect's second launch
+void EigTracker::gram_finish(int rows, float *T)
+{
+    splitk_reduce_f32(slab_.p + (size_t)4 * rows * F_, gram_slices(rows, rows).slices, rows, rows, T, cap_, 1.0f, 0.f, nullptr, 0.f,
+                      nullptr, 0.f, s_);
 }
 
 // Wp[np][F] -= (Wp Q^T) Q for the `kept` orthonormal rows of Q
@@ -280,15 +310,17 @@ void EigTracker::project_out(float *Wp, int np, const float *Q, int kept)
 // value, i.e. by how strongly the filter amplified them; the caller cuts the panels so that
 // rows of different provenance or of very different amplification never share one.  Nothing
 // here synchronises with the host and no row is dropped (dependent rows become zero rows).
-int EigTracker::orthonormalize(float *Z, int rows, float *scratch, const std::vector<int> &panel_ends, int skip)
+int EigTracker::orthonormalize(float *Z, int rows, float *scratch, const std::vector<int> &panel_ends, int skip, bool gram_ready)
 {
     // One panel (the steady state): Cholesky QR is invariant under a scaling of the rows - the Gram entries keep their
     // relative accuracy, the dead-row rule compares a pivot with the row's own diagonal entry - so the rows go in as the
     // filter left them.  With several panels the rows are normalised first: the Gram-Schmidt step between panels zeroes
     // what is left of a row after projection against a threshold that assumes unit rows.
-    const bool one_panel = skip == 0 && rows <= CHOL_INV_MAX_N && (panel_ends.empty() || panel_ends[0] >= rows);
+    const bool one_panel = is_one_panel(rows, panel_ends, skip);
+    DLCO_CHECK(!gram_ready || one_panel, -2, "eig tracker: Gram partials were formed for a block that is not one panel");
     if (!one_panel) row_normalize(Z + (size_t)skip * F_, F_, rows - skip, F_, 0.f, s_);
     size_t pi = 0;
+    bool applied = false;                                        // the last L^-1 application was the column-slab kernel
     // (the first `skip` rows are orthonormal as they are - locked Ritz vectors - and only serve as the span the panels
     // behind them are projected against)
     for (int p0 = skip; p0 < rows;) {
@@ -307,8 +339,32 @@ int EigTracker::orthonormalize(float *Z, int rows, float *scratch, const std::ve
         for (int pass = 0; pass < 2; pass++) {
             const float *src = pass == 0 ? Wp : Sp;
             float *dst = pass == 0 ? Sp : Wp;
-            gram_rect(src, np, src, np, Tm_.p);
+            if (gram_ready && pass == 0) gram_finish(np, Tm_.p);   // the last filter product's reduction formed the partials
+            else if (applied && pass == 1) gram_finish(np, Tm_.p);   // ... the first pass's application did
+            else gram_rect(src, np, src, np, Tm_.p);
             chol_inverse128(Tm_.p, cap_, np, 1e-5f, Vm_.p, cap_, dead_.p, s_);
+            if (one_panel && fuse_apply_ && packed_ && !shard_) {
+                // dst = Linv * src by column slabs; the first pass leaves the Gram partials of the second, the second the
+                // three-way planes of the block for the exact product of the Rayleigh-Ritz step
+                LinvApplyArgs la;
+                la.Linv = Vm_.p; la.ldl = cap_; la.n = np; la.F = F_;
+                la.src = src; la.dst = dst; la.ld = F_;
+                const eig_rules::GramSlicing gs = gram_slices(np, np);
+                const size_t off = (size_t)4 * np * F_;
+                bool fits = np <= 96;
+                if (pass == 0) {
+                    fits = fits && gs.whole(F_) && off + (size_t)gs.slices * np * np <= slab_floats_;
+                    la.gram_slab = slab_.p + off; la.gram_chunk = gs.chunk;
+                } else {
+                    la.planes.hi = plane_hi_.p; la.planes.lo = plane_lo_.p; la.planes.lo2 = plane_lo2_.p;
+                }
+                applied = fits && linv_apply_slab(la, s_);
+                if (applied) {
+                    st_.fused_applications++;
+                    if (pass == 1) { planes3_of_ = dst; planes3_rows_ = np; }
+                    continue;
+                }
+            }
             GemmArgs g;                                           // dst = Linv * src
             g.M = np; g.N = F_; g.K = np;
             g.A.p = Vm_.p; g.A.ld = cap_; g.A.kmajor = false;
@@ -393,6 +449,8 @@ struct EigTracker::UpdateState {
     float theta_top = 0.f, block_min = 0.f;
     bool conv = false, cheap_done = false;
     bool w_emitted = false;          // the last pass's residual kernel has written W (all rows of that pass's block, scales too)
+    bool gram_wanted = false;        // the filtered block goes into CholQR as one panel: its last product may form the Gram partials
+    bool gram_ready = false;         // ... and did
     eig_rules::FilterPlan plan;      // of the current pass
     std::vector<int> panel_ends;
 };
@@ -415,13 +473,16 @@ int EigTracker::update(const float *G, float mu, float cscale, float *W, double 
     for (; u.it < max_iter_; u.it++) {
         u.plan = eig_rules::plan_filter(block_of(u), u.n_ritz, u.nw, u.it, deg0_, lo_bound_, u.block_min, u.theta_top, lock_,
                                         !u.cheap_done && y_ok_, last_crit_);
+        // (the panels depend on the plan alone: cut before the filter, which has to know whether one panel follows it)
+        eig_rules::cut_panels(block_of(u), u.n_ritz, u.plan, CHOL_INV_MAX_N, u.panel_ends);
+        u.gram_wanted = is_one_panel(m_, u.panel_ends, u.plan.n_lock);
+        u.gram_ready = false;
         float *Z = Q_;
         if (u.plan.cheap) { u.cheap_done = true; Z = filter_cheap(u); }
         else if (u.plan.n_lock > 0) Z = filter_locked(u);
         else if (u.plan.filtered) Z = filter_plain(u);
         if (u.plan.filtered) last_deg_ = u.plan.d;
-        eig_rules::cut_panels(block_of(u), u.n_ritz, u.plan, CHOL_INV_MAX_N, u.panel_ends);
-        orthonormalize(Z, m_, pick({Z}), u.panel_ends, u.plan.n_lock);   // in place
+        orthonormalize(Z, m_, pick({Z}), u.panel_ends, u.plan.n_lock, u.gram_ready);   // in place
         rayleigh_ritz(u, Z);
         judge(u);
         // a block whose positive eigenspace reaches into its guards grows; a full one that cannot
@@ -506,7 +567,7 @@ float *EigTracker::filter_locked(const UpdateState &u)
 }
 
 // The three-term recurrence on the whole block; the first term comes from the step's rank update where the caller offered one
-float *EigTracker::filter_plain(const UpdateState &u)
+float *EigTracker::filter_plain(UpdateState &u)
 {
     const float c0 = u.plan.c0, e0 = u.plan.e0;
     const int d = u.plan.d;
@@ -515,6 +576,7 @@ float *EigTracker::filter_plain(const UpdateState &u)
     PlaneChain chain;
     chain.next = d >= 2;                                 // the result is the X of the next product: emit its planes
     bool first_done = false;
+    planes3_of_ = nullptr;
     if (u.it == 0 && u.ru_ok && u.n_ritz == m_) {
         // (H - c0) Q / e0 = (beta / e0) Y - (alpha / e0) C_w X_a - (c0 / e0) Q, H = -G
         coeff_.alloc(rank_coeff_bytes(cap_ < 160 ? cap_ : 160, ru_.kmax));
@@ -534,13 +596,16 @@ float *EigTracker::filter_plain(const UpdateState &u)
             if (ru_check_) check_first_term(u, cur);
         }
     }
-    if (!first_done) product(Q_, m_, u.G, -1.0f / e0, cur, Q_, -c0 / e0, nullptr, 0.f, true, &chain);
+    // the last product of the recurrence is the block CholQR takes next
+    GramTail tail;
+    if (!first_done) product(Q_, m_, u.G, -1.0f / e0, cur, Q_, -c0 / e0, nullptr, 0.f, true, &chain, d == 1 && u.gram_wanted ? &tail : nullptr);
     for (int k = 2; k <= d; k++) {
         float *nxt = pick({prev, cur});
         chain.next = k < d;
-        product(cur, m_, u.G, -2.0f / e0, nxt, cur, -2.0f * c0 / e0, prev, -1.0f, true, &chain);
+        product(cur, m_, u.G, -2.0f / e0, nxt, cur, -2.0f * c0 / e0, prev, -1.0f, true, &chain, k == d && u.gram_wanted ? &tail : nullptr);
         prev = cur; cur = nxt;
     }
+    u.gram_ready = tail.done;
     return cur;
 }
 
@@ -565,13 +630,28 @@ void EigTracker::check_first_term(const UpdateState &u, const float *cur)
     st_.product_rows -= m_;
 }
 
+// Yb = Qo * H (exact fp32) and T = Yb * Qo^T into Tm_
+void EigTracker::project_block(const float *G, const float *Qo, float *Yb)
+{
+    GramTail tail;
+    tail.with = Qo;
+    product(Qo, m_, G, -1.0f, Yb, nullptr, 0.f, nullptr, 0.f, false, nullptr, &tail);
+    if (tail.done) gram_finish(m_, Tm_.p);
+    else gram_rect(Yb, m_, Qo, m_, Tm_.p);
+}
+
+// One panel (orthonormalize): the whole block goes through CholQR2 as it is
+bool EigTracker::is_one_panel(int rows, const std::vector<int> &panel_ends, int skip)
+{
+    return skip == 0 && rows <= CHOL_INV_MAX_N && (panel_ends.empty() || panel_ends[0] >= rows);
+}
+
 // Rayleigh-Ritz on the orthonormal rows Qo: Q_ and Y_ = Q_ H become the Ritz vectors and their products, the Ritz
 // values and residual norms come back into h_theta_ / h_res_ (one polled read-back per pass)
 void EigTracker::rayleigh_ritz(UpdateState &u, float *Qo)
 {
     float *Yb = pick({Qo});
-    product(Qo, m_, u.G, -1.0f, Yb, nullptr, 0.f, nullptr, 0.f, false);     // Yb = Qo * H, exact fp32
-    gram_rect(Yb, m_, Qo, m_, Tm_.p);
+    project_block(u.G, Qo, Yb);
     if (prof_) prof_->begin(PROF_JACOBI);
     const float lam_cut = eig_rules::jacobi_lam_cut(block_of(u), have_theta_ && u.n_ritz == m_);
     float *Qn = pick({Qo, Yb});
@@ -629,6 +709,32 @@ void EigTracker::rayleigh_ritz(UpdateState &u, float *Qo)
     u.theta_top = h_theta_[0];
     u.block_min = std::min(h_theta_[m_ - 1], u.mu);
     u.n_ritz = m_;
+}
+
+void EigTracker::ortho_probe(const float *X, const float *Xprev, int m, const float *G, float alpha, float b1, float b2, int panel_end,
+                             int n_lock, float *Qo, float *Yb, float *T)
+{
+    DLCO_CHECK(packed_ && !shard_ && m >= 1 && m <= cap_ && n_lock >= 0 && n_lock < m, -2, "eig tracker: ortho_probe needs a packed single-rank tracker that holds m rows");
+    m_ = m;
+    const size_t bytes = (size_t)m * F_ * sizeof(float);
+    float *cur = all_[0], *prev = all_[1], *Z = all_[2], *scratch = all_[3], *Yp = all_[4];
+    DLCO_HIP(hipMemcpyAsync(cur, X, bytes, hipMemcpyDeviceToDevice, s_));
+    if (Xprev) DLCO_HIP(hipMemcpyAsync(prev, Xprev, bytes, hipMemcpyDeviceToDevice, s_));
+    std::vector<int> panel_ends;
+    if (n_lock > 0) panel_ends.push_back(n_lock);
+    if (panel_end > n_lock && panel_end < m) panel_ends.push_back(panel_end);
+    panel_ends.push_back(m);
+    GramTail tail;
+    product(cur, m, G, alpha, Z, cur, b1, Xprev ? prev : nullptr, b2, true, nullptr, is_one_panel(m, panel_ends, n_lock) ? &tail : nullptr);
+    if (n_lock > 0) DLCO_HIP(hipMemcpyAsync(Z, cur, (size_t)n_lock * F_ * sizeof(float), hipMemcpyDeviceToDevice, s_));   // locked rows pass the filter untouched
+    orthonormalize(Z, m, scratch, panel_ends, n_lock, tail.done);
+    project_block(G, Z, Yp);
+    DLCO_HIP(hipMemcpyAsync(Qo, Z, bytes, hipMemcpyDeviceToDevice, s_));
+    DLCO_HIP(hipMemcpyAsync(Yb, Yp, bytes, hipMemcpyDeviceToDevice, s_));
+    DLCO_HIP(hipMemcpy2DAsync(T, (size_t)m * sizeof(float), Tm_.p, (size_t)cap_ * sizeof(float), (size_t)m * sizeof(float), m,
+                              hipMemcpyDeviceToDevice, s_));
+    DLCO_HIP(hipStreamSynchronize(s_));
+    m_ = 0;
 }
 
 void EigTracker::judge(UpdateState &u)

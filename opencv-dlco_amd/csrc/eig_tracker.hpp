@@ -27,6 +27,8 @@ struct EigStats {
     int64_t iters = 0, product_rows = 0, jacobi_sweeps = 0, updates = 0, nonconverged = 0, cheap_passes = 0;
     int64_t jacobi_barrier_timeouts = 0;   // multi-workgroup Jacobi calls that gave up at their grid barrier and were redone on one workgroup
     int64_t locked_passes = 0, locked_rows = 0;   // filter passes that ran with the converged top of the block locked, rows locked in them
+    int64_t fused_gram_reductions = 0;     // product reductions that also formed the K-slice partials of the Gram product behind them
+    int64_t fused_applications = 0;        // CholQR applications of L^-1 by the column-slab kernel that feeds the next launch
     int64_t rank_update_passes = 0;        // first filter terms formed from the step's rank update instead of a pass over the matrix
     double rank_update_check = 0.0;        // DLCO_RANK_UPDATE_CHECK=1: largest |shortcut - product| / max|product| seen (developer aid)
 };
@@ -78,16 +80,25 @@ public:
     static bool packed_supported(int F) { return F % 128 == 0 && F / 128 <= 64 && env_switch("DLCO_NO_PACKED") == nullptr; }
     const EigStats &stats() const { return st_; }
     float last_crit() const { return last_crit_; }
+    // false: every Gram product is a launch of its own (the form the fused reductions are compared with)
+    void set_fuse_gram(bool on) { fuse_gram_ = on; fuse_apply_ = on; }
+    // For tests (dlco_ortho_probe): the tail of a pass on device arrays, without the tracker's state.  Z = alpha * X * G +
+    // b1 * X + b2 * Xprev (the last filter product; Xprev may be null) -> CholQR2 with the panels cut at panel_end (0: one
+    // panel) behind n_lock untouched rows -> Qo -> Yb = -Qo * G (exact) -> T = Yb * Qo^T.  X, Xprev: [m][F]; Qo, Yb: [m][F]
+    // out; T: [m][m] out.
+    void ortho_probe(const float *X, const float *Xprev, int m, const float *G, float alpha, float b1, float b2, int panel_end,
+                     int n_lock, float *Qo, float *Yb, float *T);
 
 private:
     struct UpdateState;              // what one update() carries from stage to stage (eig_tracker.cpp)
     struct PlaneChain;               // the two-way planes a filter chain hands from one product to the next
+    struct GramTail;                 // a product whose reduction may form the Gram partials of its result
     // the stages of update(), in the order it runs them
     void open_update(UpdateState &u);
     eig_rules::Block block_of(const UpdateState &u) const;
     float *filter_cheap(const UpdateState &u);
     float *filter_locked(const UpdateState &u);
-    float *filter_plain(const UpdateState &u);
+    float *filter_plain(UpdateState &u);
     void check_first_term(const UpdateState &u, const float *cur);
     void rayleigh_ritz(UpdateState &u, float *Qo);
     void judge(UpdateState &u);
@@ -95,11 +106,15 @@ private:
     double trim_and_emit(UpdateState &u);
 
     void product(const float *X, int rows, const float *G, float alpha, float *out, const float *E1, float b1,
-                 const float *E2, float b2, bool approx, PlaneChain *chain = nullptr);
+                 const float *E2, float b2, bool approx, PlaneChain *chain = nullptr, GramTail *gram = nullptr);
     void gram_rect(const float *X, int xrows, const float *Y, int yrows, float *T);
+    eig_rules::GramSlicing gram_slices(int xrows, int yrows) const;
+    void gram_finish(int rows, float *T);
+    void project_block(const float *G, const float *Qo, float *Yb);
+    static bool is_one_panel(int rows, const std::vector<int> &panel_ends, int skip);
     void project_out(float *Wp, int np, const float *Q, int kept);
     void rotate(const float *C, long ldc, int k_in, int k_out, const float *X, float *out, const float *X2 = nullptr, float *out2 = nullptr);
-    int orthonormalize(float *Z, int rows, float *scratch, const std::vector<int> &panel_ends, int skip = 0);
+    int orthonormalize(float *Z, int rows, float *scratch, const std::vector<int> &panel_ends, int skip = 0, bool gram_ready = false);
     int drop_dead_rows();
     void refresh_lower_bound(const float *G, int iters, float theta_top);
     void append_random(float *Q, int have, int add);
@@ -113,6 +128,10 @@ private:
     int extra_val_ = 0;
     bool packed_ = false;
     bool emit_guards_ = false;
+    bool fuse_gram_ = true;
+    bool fuse_apply_ = true;
+    const float *planes3_of_ = nullptr;   // the block whose three-way planes CholQR's second pass left in the plane buffers
+    int planes3_rows_ = 0;
     int wext_rows_ = 0, wext_nw_ = 0;   // W as the last update() left it: rows in all, Ritz rows among them
     RankUpdate ru_;
     bool ru_offered_ = false;

@@ -356,6 +356,245 @@ __global__ __launch_bounds__(256) void reduce_split_kernel(const float *slab, in
     }
 }
 
+// The same ordered sum that ALSO forms the raw K-slice partials of a Gram product of its result, C * B^T with B = C itself
+// (CholQR's first Gram matrix, SELF) or B = a second row block Y (the Rayleigh-Ritz T = Yb * Qo^T): the generic GEMM would
+// read C back a few microseconds later for 150 MFLOP, in a launch of its own.  Workgroup = (128-column slab of C, 32-row
+// tile ti of C); a slab is one or two whole Gram slices (eig_rules::gram_slicing).
+//   * reduce: C = alpha * sum_z slab[z] + b1*E1 + b2*E2 with the operations of the reduce launch this one replaces, spelled
+//     out so that no contraction can differ: the wide kernel's ((s0 + s1) + s2) + s3, or with `tree` what
+//     splitk_reduce_kernel's butterfly leaves in lane 0 for four slices, ((0 + s0) + (0 + s1)) + ((0 + s2) + (0 + s3)) (the zeros
+//     of its idle lanes added afterwards change nothing: that sum is never -0); then one multiply and two fused multiply-adds.
+//     SELF reduces the rows of its own tile and of its partner tile (self_partner) and stores its own; otherwise the
+//     tile's rows only, and B = Y's columns come from memory.  Both sit in LDS k-major ([column][row], gemm_kernel's image).
+//   * Gram: wave = (32-row tile tj of B, slice of the slab): the k-ascending chain from zero of gemm_kernel on the same
+//     v_mfma_f32_32x32x2_f32 with the same k pairing, so the partial slab holds the bits gemm_f32 would have written and
+//     the ordered reduce of that slab is the unchanged second launch.
+// No grid barrier, no atomics: every workgroup writes its own rows of C and its own entries of the Gram slab.
+struct ReduceGramDev {
+    const float *slab;            // [4][M][F] group sums of skinny_sym_kernel
+    int M, F;
+    float *C;
+    long ldc;                     // also the row stride of E1 / E2
+    float alpha;
+    const float *E1;
+    float b1;
+    const float *E2;
+    float b2;
+    int tree;
+    const float *Y;               // !SELF: [M][ldy]
+    long ldy;
+    float *gram;                  // [F / chunk][M][M]
+    int chunk;                    // Gram slice: 64 or 128 columns
+};
+constexpr int RG_T = 512;
+constexpr int RG_SA = 36;         // row stride of the A image (!SELF)
+constexpr int rg_sb(int mt) { return mt * 32 + 4; }
+constexpr int rg_lds_bytes(int mt, bool self) { return (128 * rg_sb(mt) + (self ? 0 : 128 * RG_SA)) * (int)sizeof(float); }
+
+// SELF: C * C^T is symmetric bit for bit (element (j, i) is the same chain of the same products), so row tile ti forms the
+// diagonal tile (ti, ti) and ONE off-diagonal tile (ti, partner) and stores the latter mirrored as well: with three row
+// tiles the partners 1, 2, 0 cover all nine tiles, with two tile 0 takes tile 1.  A workgroup then needs the rows of two
+// tiles, not of all.  -1: no partner.
+template <int MT>
+__device__ __forceinline__ int self_partner(int ti)
+{
+    return MT == 3 ? (ti + 1) % 3 : (MT == 2 && ti == 0 ? 1 : -1);
+}
+
+// The Gram phase of a workgroup that holds its operands k-major in LDS (A: the 32 rows of tile ti at As[k * SA + r], B: all
+// rows at Bs[k * SB + row], k = column of the 128-column slab at c0): wave = (tile of B, slice of the slab), each the
+// k-ascending chain from zero on v_mfma_f32_32x32x2_f32 with gemm_kernel's k pairing; raw partials to gram[slice][M][M].
+template <int MT, bool SELF>
+__device__ __forceinline__ void gram_tiles(const float *As, int SA, const float *Bs, int SB, int ti, int c0, int chunk, int M, float *gram)
+{
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, lr = lane & 31, lh = lane >> 5;
+    const int nsl = 128 / chunk, ntj = SELF ? (self_partner<MT>(ti) >= 0 ? 2 : 1) : MT;
+    if (wave >= ntj * nsl) return;
+    const int tj = SELF ? (wave % ntj == 0 ? ti : self_partner<MT>(ti)) : wave % ntj, sl = wave / ntj;
+    f32x16 acc;
+#pragma unroll
+    for (int r = 0; r < 16; r++) acc[r] = 0.f;
+    const float *ap = As + (sl * chunk + lh) * SA + lr, *bp = Bs + (sl * chunk + lh) * SB + tj * 32 + lr;
+    for (int k0 = 0; k0 < chunk; k0 += 16) {                  // (a slice is whole 16-column K tiles)
+        float af[8], bf[8];
+#pragma unroll
+        for (int kk = 0; kk < 8; kk++) { af[kk] = ap[(k0 + 2 * kk) * SA]; bf[kk] = bp[(k0 + 2 * kk) * SB]; }
+#pragma unroll
+        for (int kk = 0; kk < 8; kk++) acc = __builtin_amdgcn_mfma_f32_32x32x2f32(af[kk], bf[kk], acc, 0, 0, 0);
+    }
+    float *gs = gram + (long)(c0 / chunk + sl) * M * M;
+    const int j = tj * 32 + lr;
+    const bool mirror = SELF && tj != ti;
+#pragma unroll
+    for (int r = 0; r < 16; r++) {
+        const int i = ti * 32 + (r & 3) + 8 * (r >> 2) + 4 * lh;
+        if (i < M && j < M) {
+            gs[(long)i * M + j] = acc[r];
+            if (mirror) gs[(long)j * M + i] = acc[r];
+        }
+    }
+}
+
+template <int MT, bool SELF>
+__global__ __launch_bounds__(RG_T) void reduce_gram_kernel(ReduceGramDev g)
+{
+    extern __shared__ __attribute__((aligned(16))) char lds_raw[];
+    constexpr int SB = rg_sb(MT), SA = SELF ? SB : RG_SA;
+    const int tid = threadIdx.x, ti = blockIdx.y, c0 = blockIdx.x * 128;
+    float *Bs = reinterpret_cast<float *>(lds_raw);
+    float *As = SELF ? Bs + ti * 32 : Bs + 128 * SB;
+    const long total = (long)g.M * g.F;
+
+    // unit f of an image with ROWS rows: 16 bytes of row (f / 4) % ROWS, columns 16 * (f / 4 / ROWS) + 4 * (f % 4).
+    // The loads are unconditional at a clamped row (a branch around them would serialise the units); rows >= M become zeros.
+    auto reduced = [&](int row, int col, bool store) {
+        const int rc = min(row, g.M - 1);
+        const float *p = g.slab + (long)rc * g.F + c0 + col;
+        const f32x4 s0 = *reinterpret_cast<const f32x4 *>(p), s1 = *reinterpret_cast<const f32x4 *>(p + total);
+        const f32x4 s2 = *reinterpret_cast<const f32x4 *>(p + 2 * total), s3 = *reinterpret_cast<const f32x4 *>(p + 3 * total);
+        const long idx = (long)rc * g.ldc + c0 + col;
+        f32x4 e1 = {0.f, 0.f, 0.f, 0.f}, e2 = {0.f, 0.f, 0.f, 0.f};
+        if (g.E1) e1 = *reinterpret_cast<const f32x4 *>(g.E1 + idx);
+        if (g.E2) e2 = *reinterpret_cast<const f32x4 *>(g.E2 + idx);
+        f32x4 o;
+#pragma unroll
+        for (int c = 0; c < 4; c++) {
+            float s;
+            if (g.tree) s = __fadd_rn(__fadd_rn(__fadd_rn(0.f, s0[c]), __fadd_rn(0.f, s1[c])), __fadd_rn(__fadd_rn(0.f, s2[c]), __fadd_rn(0.f, s3[c])));
+            else s = __fadd_rn(__fadd_rn(__fadd_rn(s0[c], s1[c]), s2[c]), s3[c]);
+            float v = __fmul_rn(g.alpha, s);
+            if (g.E1) v = __fmaf_rn(g.b1, e1[c], v);
+            if (g.E2) v = __fmaf_rn(g.b2, e2[c], v);
+            o[c] = v;
+        }
+        if (store && row < g.M) *reinterpret_cast<f32x4 *>(g.C + idx) = o;
+        if (row >= g.M) o = f32x4{0.f, 0.f, 0.f, 0.f};
+        return o;
+    };
+    auto to_image = [&](float *img, int stride, int r, int col, const f32x4 &v) {
+#pragma unroll
+        for (int c = 0; c < 4; c++) img[(col + c) * stride + r] = v[c];
+    };
+    if (SELF) {
+        // the rows of the tile itself and of its partner (self_partner): the tiles the workgroup's Gram products need
+        const int tp = self_partner<MT>(ti);
+#pragma unroll
+        for (int t = 0; t < (MT > 1 ? 2 : 1); t++) {
+            if (t == 1 && tp < 0) break;
+            const int r0 = 32 * (t == 0 ? ti : tp);
+#pragma unroll
+            for (int it = 0; it < 32 * 32 / RG_T; it++) {
+                const int f = tid + RG_T * it, r = r0 + ((f >> 2) & 31), col = 16 * (f >> 7) + 4 * (f & 3);
+                to_image(Bs, SB, r, col, reduced(r, col, t == 0));
+            }
+        }
+    } else {
+#pragma unroll
+        for (int it = 0; it < 32 * 32 / RG_T; it++) {
+            const int f = tid + RG_T * it, r = (f >> 2) & 31, col = 16 * (f >> 7) + 4 * (f & 3);
+            to_image(As, SA, r, col, reduced(ti * 32 + r, col, true));
+        }
+#pragma unroll
+        for (int it = 0; it < MT * 32 * 32 / RG_T; it++) {
+            const int f = tid + RG_T * it, r = (f >> 2) % (MT * 32), col = 16 * ((f >> 2) / (MT * 32)) + 4 * (f & 3);
+            f32x4 v = *reinterpret_cast<const f32x4 *>(g.Y + (long)min(r, g.M - 1) * g.ldy + c0 + col);
+            if (r >= g.M) v = f32x4{0.f, 0.f, 0.f, 0.f};
+            to_image(Bs, SB, r, col, v);
+        }
+    }
+    __syncthreads();
+    gram_tiles<MT, SELF>(As, SA, Bs, SB, ti, c0, g.chunk, g.M, g.gram);
+}
+
+// CholQR's dst = L^-1 * src by 128-column slabs, feeding what comes next.  Workgroup = (slab, 32-row tile ti of dst); L^-1
+// (n <= 96 rows, transposed: the A operand k-major) and the slab of src (the B operand, k-major as it lies in memory) sit
+// in LDS; wave = (row tile, 32 columns): gemm_kernel's chain for this product - k ascending from zero over K = n padded with
+// zeros to whole 16-wide K tiles, the same MFMA and k pairing, alpha = 1 - so dst has the bits the GEMM launch gave it.
+//   TAIL 0 (first pass): the Gram partials of dst for the second pass, as reduce_gram_kernel forms them (SELF: the
+//   workgroup also computes the rows of its partner tile, self_partner).
+//   TAIL 1 (second pass): the three-way split planes of its rows of dst (split_x_kernel's entries), so the exact product
+//   that follows starts with its planes ready.
+struct LinvApplyDev {
+    const float *Linv;            // [n][ldl]
+    long ldl;
+    int n, F;
+    const float *src;             // [n][ld]
+    float *dst;
+    long ld;
+    float *gram;                  // TAIL 0: [F / chunk][n][n]
+    int chunk;
+    bf16x8 *hi, *lo, *lo2;        // TAIL 1
+};
+constexpr int LA_SS = 132;        // row stride of the src image [k][128 columns]
+constexpr int LA_SL = 68;         // row stride of the L^-1 image [k][rows of tile ti | rows of its partner]
+constexpr int la_lds_bytes(int mt) { return (96 * LA_SS + 96 * LA_SL + 128 * rg_sb(mt)) * (int)sizeof(float); }
+
+template <int MT, int TAIL>
+__global__ __launch_bounds__(RG_T) void linv_apply_kernel(LinvApplyDev g)
+{
+    extern __shared__ __attribute__((aligned(16))) char lds_raw[];
+    constexpr int SB = rg_sb(MT);
+    float *Ss = reinterpret_cast<float *>(lds_raw), *Lt = Ss + 96 * LA_SS, *Ds = Lt + 96 * LA_SL;
+    const int tid = threadIdx.x, ti = blockIdx.y, c0 = blockIdx.x * 128;
+    const int KP = (g.n + 15) / 16 * 16;                      // K as gemm_kernel walks it
+    const int tp = TAIL == 0 ? self_partner<MT>(ti) : -1;
+    // src: 16 bytes per thread, a row of the slab per 32 threads; rows beyond n are zeros
+#pragma unroll
+    for (int it = 0; it < 96 * 32 / RG_T; it++) {
+        const int f = tid + RG_T * it, k = f >> 5, c4 = f & 31;
+        f32x4 v = *reinterpret_cast<const f32x4 *>(g.src + (long)min(k, g.n - 1) * g.ld + c0 + 4 * c4);
+        if (k >= g.n) v = f32x4{0.f, 0.f, 0.f, 0.f};
+        if (k < KP) *reinterpret_cast<f32x4 *>(Ss + k * LA_SS + 4 * c4) = v;
+    }
+    // L^-1 transposed: rows of tile ti in columns 0..31 of the image, of the partner in 32..63
+#pragma unroll
+    for (int it = 0; it < 64 * 96 / RG_T; it++) {
+        const int f = tid + RG_T * it, il = f / 96, k = f % 96;
+        const int row = 32 * (il < 32 ? ti : max(tp, 0)) + (il & 31);
+        float v = g.Linv[(long)min(row, g.n - 1) * g.ldl + min(k, g.n - 1)];
+        if (row >= g.n || k >= g.n || (il >= 32 && tp < 0)) v = 0.f;
+        if (k < KP) Lt[k * LA_SL + il] = v;
+    }
+    __syncthreads();
+
+    const int lane = tid & 63, wave = tid >> 6, lr = lane & 31, lh = lane >> 5;
+    const int t = wave >> 2, jt = wave & 3;
+    if (t == 0 || tp >= 0) {
+        f32x16 acc;
+#pragma unroll
+        for (int r = 0; r < 16; r++) acc[r] = 0.f;
+        const float *ap = Lt + lh * LA_SL + t * 32 + lr, *bp = Ss + lh * LA_SS + jt * 32 + lr;
+        for (int k0 = 0; k0 < KP; k0 += 16) {
+            float af[8], bf[8];
+#pragma unroll
+            for (int kk = 0; kk < 8; kk++) { af[kk] = ap[(k0 + 2 * kk) * LA_SL]; bf[kk] = bp[(k0 + 2 * kk) * LA_SS]; }
+#pragma unroll
+            for (int kk = 0; kk < 8; kk++) acc = __builtin_amdgcn_mfma_f32_32x32x2f32(af[kk], bf[kk], acc, 0, 0, 0);
+        }
+        const int i0 = 32 * (t == 0 ? ti : tp), col = jt * 32 + lr;
+#pragma unroll
+        for (int r = 0; r < 16; r++) {
+            const int i = i0 + (r & 3) + 8 * (r >> 2) + 4 * lh;
+            if (t == 0 && i < g.n) g.dst[(long)i * g.ld + c0 + col] = acc[r];
+            Ds[col * SB + i] = acc[r];                        // (rows beyond n: their row of the L^-1 image is zero)
+        }
+    }
+    __syncthreads();
+    if (TAIL == 0) {
+        gram_tiles<MT, true>(Ds + ti * 32, SB, Ds, SB, ti, c0, g.chunk, g.n, g.gram);
+    } else {
+        // one plane entry per thread: row ti * 32 + (tid & 31), the eight columns c8
+        const int rr = tid & 31, c8 = tid >> 5;
+        bf16x8 h, l, l2;
+#pragma unroll
+        for (int j = 0; j < 8; j++) split_f32<3>(Ds[(c8 * 8 + j) * SB + ti * 32 + rr], j, h, l, l2);
+        const long e = plane_entry_at(MT, ti * 32 + rr, c0 / 8 + c8);
+        g.hi[e] = h;
+        g.lo[e] = l;
+        g.lo2[e] = l2;
+    }
+}
+
 // ---- symmetric G stored as its packed upper tiles: every tile leaves HBM once ------------------------------------------
 // out[:, I] = sum_J X[:, J] G[J][I] over tile blocks; G[J][I] is the stored tile (I, J) read along its rows when I <= J
 // ("direct", exactly the chunk of skinny_rows_kernel), or the stored tile (J, I) read along its COLUMNS when J < I
@@ -607,6 +846,24 @@ void launch_rows(const Bf2Dev &g, dim3 grid, hipStream_t s)
     hipLaunchKernelGGL((skinny_rows_kernel<MT, NS>), grid, dim3(SB_T), lds, s, g);
 }
 
+template <int MT, bool SELF>
+void launch_reduce_gram(const ReduceGramDev &r, hipStream_t s)
+{
+    constexpr int lds = rg_lds_bytes(MT, SELF);
+    ensure_dynamic_lds(reinterpret_cast<const void *>(reduce_gram_kernel<MT, SELF>), lds);
+    hipLaunchKernelGGL((reduce_gram_kernel<MT, SELF>), dim3(r.F / 128, MT), dim3(RG_T), lds, s, r);
+}
+
+// May the reduction of this symmetric product be the one that also emits the Gram partials the caller asked for?
+bool reduce_gram_fits(const SkinnyArgs &a)
+{
+    auto al16 = [](const void *p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; };
+    if (!a.gram_slab || a.emit_planes || a.M > 96 || (a.gram_chunk != 64 && a.gram_chunk != 128)) return false;
+    if (a.ldc % 4 != 0 || !al16(a.slab) || !al16(a.C) || !al16(a.E1) || !al16(a.E2) || a.C == a.E1 || a.C == a.E2) return false;
+    if (a.gram_with && (a.gram_ld % 4 != 0 || !al16(a.gram_with) || a.gram_with == a.C)) return false;
+    return true;
+}
+
 }  // namespace
 
 void split_planes_bf16(const float *X, long ldx, int M, int K, void *hi, void *lo, void *lo2, hipStream_t s)
@@ -657,6 +914,55 @@ bool skinny_product_bf16x2(const SkinnyArgs &a, hipStream_t s)
     return true;
 }
 
+// CholQR's dst = Linv * src as the column-slab kernel that also feeds the next launch (linv_apply_kernel); false, and
+// nothing launched, where the shape does not fit: the caller then takes gemm_f32.
+bool linv_apply_slab(const LinvApplyArgs &a, hipStream_t s)
+{
+    auto al16 = [](const void *p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; };
+    const bool planes = a.planes.hi != nullptr;
+    if (a.n < 1 || a.n > 96 || a.F % 128 != 0 || a.ld % 4 != 0 || !al16(a.src) || !al16(a.dst) || a.src == a.dst) return false;
+    if (planes ? (!a.planes.lo || !a.planes.lo2 || a.gram_slab != nullptr) : (!a.gram_slab || (a.gram_chunk != 64 && a.gram_chunk != 128))) return false;
+    LinvApplyDev g;
+    g.Linv = a.Linv; g.ldl = a.ldl; g.n = a.n; g.F = a.F;
+    g.src = a.src; g.dst = a.dst; g.ld = a.ld;
+    g.gram = a.gram_slab; g.chunk = a.gram_chunk;
+    g.hi = static_cast<bf16x8 *>(a.planes.hi); g.lo = static_cast<bf16x8 *>(a.planes.lo); g.lo2 = static_cast<bf16x8 *>(a.planes.lo2);
+    dispatch_mt<3>((a.n + 31) / 32, [&](auto MT) {
+        constexpr int lds = la_lds_bytes(MT());
+        const dim3 grid(a.F / 128, MT());
+        if (planes) {
+            ensure_dynamic_lds(reinterpret_cast<const void *>(linv_apply_kernel<MT(), 1>), lds);
+            hipLaunchKernelGGL((linv_apply_kernel<MT(), 1>), grid, dim3(RG_T), lds, s, g);
+        } else {
+            ensure_dynamic_lds(reinterpret_cast<const void *>(linv_apply_kernel<MT(), 0>), lds);
+            hipLaunchKernelGGL((linv_apply_kernel<MT(), 0>), grid, dim3(RG_T), lds, s, g);
+        }
+    });
+    DLCO_HIP(hipGetLastError());
+    return true;
+}
+
+// The reduction of skinny_product_sym alone, in the form that also emits the Gram partials a.gram_slab asks for
+// (reduce_gram_kernel); false, and nothing launched, where a does not ask for them or the shape does not fit.
+bool reduce_gram_sym(const SkinnyArgs &a, hipStream_t s)
+{
+    const int M = a.M, F = a.K;
+    if (a.N != F || F % 128 != 0 || M < 1 || !reduce_gram_fits(a)) return false;
+    ReduceGramDev r;
+    r.slab = a.slab; r.M = M; r.F = F;
+    r.C = a.C; r.ldc = a.ldc;
+    r.alpha = a.alpha; r.E1 = a.E1; r.b1 = a.b1; r.E2 = a.E2; r.b2 = a.b2;
+    r.tree = splitk_reduce_is_wide(a.slab, 4, M, F, a.C, a.ldc, a.E1, a.E2) ? 0 : 1;
+    r.Y = a.gram_with; r.ldy = a.gram_ld;
+    r.gram = a.gram_slab; r.chunk = a.gram_chunk;
+    dispatch_mt<3>((M + 31) / 32, [&](auto MT) {
+        if (a.gram_with) launch_reduce_gram<MT(), false>(r, s);
+        else launch_reduce_gram<MT(), true>(r, s);
+    });
+    DLCO_HIP(hipGetLastError());
+    return true;
+}
+
 // The same product for a symmetric G given as its packed upper tiles (see skinny_sym_kernel).
 bool skinny_product_sym(const SkinnyArgs &a, hipStream_t s)
 {
@@ -666,7 +972,7 @@ bool skinny_product_sym(const SkinnyArgs &a, hipStream_t s)
     const int nt = F / 128;
     if (a.N != F || F % 128 != 0 || nt < 1 || nt > 64 || M < 1 || mt > 5 || (mt >= 4 && plane_lo2)) return false;
     if (a.ldx % 4 != 0 || (reinterpret_cast<uintptr_t>(a.X) & 15) != 0 || (reinterpret_cast<uintptr_t>(a.G) & 15) != 0) return false;
-    if ((a.planes_ready || a.emit_planes) && plane_lo2) return false;   // the carried planes are the two-way ones
+    if (a.emit_planes && plane_lo2) return false;              // the planes a reduction emits are the two-way ones
     if (!a.planes_ready) split_planes_bf16(a.X, a.ldx, M, F, plane_hi, plane_lo, plane_lo2, s);
     SymDev g;
     g.M = M; g.K = F;
@@ -684,6 +990,8 @@ bool skinny_product_sym(const SkinnyArgs &a, hipStream_t s)
         hipLaunchKernelGGL(reduce_split_kernel, dim3((unsigned)std::min<long>((work + 255) / 256, 4096)), dim3(256), 0, s, a.slab, 4, M, mt, F, a.C, a.ldc,
                            a.alpha, a.E1, a.b1, a.E2, a.b2, static_cast<bf16x8 *>(plane_hi), static_cast<bf16x8 *>(plane_lo));
         DLCO_HIP(hipGetLastError());
+    } else if (reduce_gram_sym(a, s)) {
+        if (a.gram_done) *a.gram_done = true;
     } else {
         splitk_reduce_f32(a.slab, 4, M, F, a.C, a.ldc, a.alpha, 0.f, a.E1, a.b1, a.E2, a.b2, s);
     }

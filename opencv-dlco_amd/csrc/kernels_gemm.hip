@@ -407,14 +407,19 @@ inline bool plain_operand(const GemmOperand &o, int t, int K)
 
 size_t gemm_slab_floats(int M, int N, int split_k) { return split_k > 1 ? (size_t)split_k * M * N : 0; }
 
+bool splitk_reduce_is_wide(const float *slab, int split, int M, int N, const float *C, long ldc, const float *E1, const float *E2)
+{
+    auto al16 = [](const void *p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; };
+    return split <= 32 && (long)M * N >= 65536 && N % 4 == 0 && ldc % 4 == 0 && al16(slab) && al16(C) && (!E1 || al16(E1)) &&
+           (!E2 || al16(E2));
+}
+
 // C = alpha * sum_z slab[z] + beta*C + b1*E1 + b2*E2 over `split` [M][N] partial slabs (fixed order)
 void splitk_reduce_f32(const float *slab, int split, int M, int N, float *C, long ldc, float alpha, float beta,
                        const float *E1, float b1, const float *E2, float b2, hipStream_t s)
 {
     const long total = (long)M * N;
-    auto al16 = [](const void *p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; };
-    if (split <= 32 && total >= 65536 && N % 4 == 0 && ldc % 4 == 0 && al16(slab) && al16(C) && (!E1 || al16(E1)) &&
-        (!E2 || al16(E2))) {
+    if (splitk_reduce_is_wide(slab, split, M, N, C, ldc, E1, E2)) {
         long blocks = (total / 4 + 255) / 256;
         if (blocks > 4096) blocks = 4096;
         hipLaunchKernelGGL(splitk_reduce_wide_kernel, dim3((unsigned)blocks), dim3(256), 0, s, slab, split, M, N, C, ldc, alpha,

@@ -2,6 +2,8 @@
 // (links against libdlco.so; not part of the product or of the tests).
 //   hipcc --offload-arch=gfx950 -O2 -std=c++17 -I opencv-dlco_amd/csrc tools/kern_time.cpp \
 //         -L opencv-dlco_amd -ldlco -Wl,-rpath,'$ORIGIN/../opencv-dlco_amd' -o tools/kern_time
+// modes: (none) everything; `small` the m x m kernels; `prod` the tracker's product passes; `gram` the fused reductions and
+// L^-1 applications of CholQR / Rayleigh-Ritz against the launches they replace
 #include "dlco_internal.hpp"
 
 #include <cmath>
@@ -84,6 +86,66 @@ int main(int argc, char **argv)
         }
         std::printf("product M=%d F=%d: two-way %.1f us (%.2f TB/s), three-way %.1f us (%.2f TB/s), two-way ks=8 %.1f us  [split + kernel + reduce]\n", M, F,
                     a * 1e3, 4.0 * F * F / (a * 1e-3) / 1e12, b * 1e3, 4.0 * F * F / (b * 1e-3) / 1e12, c8 * 1e3);
+        return 0;
+    }
+    if (argc > 1 && std::string(argv[1]) == "gram") {
+        // `kern_time gram`: the reduction of a symmetric product that also emits the Gram partials (reduce_gram_kernel) against
+        // the two launches it replaces (ordered reduce, Gram GEMM); the ordered reduce of the Gram slab follows both forms
+        const int M = 96;
+        for (int F : {640, 8192}) {
+            const int chunk = F == 8192 ? 128 : 64, slices = F / chunk;      // eig_rules::gram_slicing at these widths
+            DevBuf<float> slab, C, E1, E2, Q, gslab, T;
+            slab.alloc((size_t)4 * M * F); C.alloc((size_t)M * F); E1.alloc((size_t)M * F); E2.alloc((size_t)M * F); Q.alloc((size_t)M * F);
+            gslab.alloc((size_t)slices * M * M); T.alloc((size_t)M * M);
+            std::mt19937 r0(5);
+            std::normal_distribution<float> g0(0.f, 1.f);
+            std::vector<float> h((size_t)4 * M * F);
+            for (auto &x : h) x = g0(r0);
+            hipMemcpy(slab.p, h.data(), h.size() * 4, hipMemcpyHostToDevice);
+            for (float *p : {E1.p, E2.p, Q.p}) hipMemcpy(p, h.data() + (p == Q.p ? 1000 : 0), (size_t)M * F * 4, hipMemcpyHostToDevice);
+            for (int with = 0; with < 2; with++) {
+                SkinnyArgs a;
+                a.M = M; a.N = F; a.K = F; a.C = C.p; a.ldc = F; a.slab = slab.p;
+                a.alpha = -0.4f; a.E1 = E1.p; a.b1 = 0.2f; a.E2 = E2.p; a.b2 = -1.0f;
+                a.gram_slab = gslab.p; a.gram_chunk = chunk; a.gram_with = with ? Q.p : nullptr; a.gram_ld = F;
+                GemmArgs g;
+                g.M = M; g.N = M; g.K = F;
+                g.A.p = C.p; g.A.ld = F; g.B.p = with ? Q.p : C.p; g.B.ld = F;
+                g.C = T.p; g.ldc = M; g.split_k = slices; g.slab = gslab.p;
+                bool ok = true;
+                const float pair = time_ms(s0, 200, [&] { splitk_reduce_f32(slab.p, 4, M, F, C.p, F, a.alpha, 0.f, a.E1, a.b1, a.E2, a.b2, s0); gemm_f32(g, s0); });
+                const float fused = time_ms(s0, 200, [&] { ok = reduce_gram_sym(a, s0) && ok; splitk_reduce_f32(gslab.p, slices, M, M, T.p, M, 1.0f, 0.f, nullptr, 0.f, nullptr, 0.f, s0); });
+                const float tail = time_ms(s0, 200, [&] { splitk_reduce_f32(gslab.p, slices, M, M, T.p, M, 1.0f, 0.f, nullptr, 0.f, nullptr, 0.f, s0); });
+                std::printf("gram F=%4d M=%d %s: reduce + Gram GEMM + Gram reduce %.1f us; reduce_gram%s + Gram reduce %.1f us; the Gram reduce alone %.1f us\n", F, M,
+                            with ? "C * Q^T" : "C * C^T", pair * 1e3, ok ? "" : " (REFUSED)", fused * 1e3, tail * 1e3);
+            }
+            // CholQR's dst = Linv * src: the column-slab kernel against the GEMM plus the launch it feeds (the Gram GEMM of the
+            // second pass, or the three-way split of the result)
+            DevBuf<float> Linv; DevBuf<char> ph, pl, pl2;
+            Linv.alloc((size_t)M * M);
+            ph.alloc(bf16x2_plane_bytes(M, F)); pl.alloc(bf16x2_plane_bytes(M, F)); pl2.alloc(bf16x2_plane_bytes(M, F));
+            hipMemcpy(Linv.p, h.data() + 77, (size_t)M * M * 4, hipMemcpyHostToDevice);
+            GemmArgs ap;
+            ap.M = M; ap.N = F; ap.K = M;
+            ap.A.p = Linv.p; ap.A.ld = M; ap.B.p = Q.p; ap.B.ld = F; ap.B.kmajor = true;
+            ap.C = C.p; ap.ldc = F;
+            GemmArgs g2;
+            g2.M = M; g2.N = M; g2.K = F;
+            g2.A.p = C.p; g2.A.ld = F; g2.B.p = C.p; g2.B.ld = F;
+            g2.C = T.p; g2.ldc = M; g2.split_k = slices; g2.slab = gslab.p;
+            LinvApplyArgs la;
+            la.Linv = Linv.p; la.ldl = M; la.n = M; la.F = F; la.src = Q.p; la.dst = C.p; la.ld = F;
+            LinvApplyArgs la1 = la, la2 = la;
+            la1.gram_slab = gslab.p; la1.gram_chunk = chunk;
+            la2.planes.hi = ph.p; la2.planes.lo = pl.p; la2.planes.lo2 = pl2.p;
+            bool ok = true;
+            const float p1 = time_ms(s0, 200, [&] { gemm_f32(ap, s0); gemm_f32(g2, s0); });
+            const float f1 = time_ms(s0, 200, [&] { ok = linv_apply_slab(la1, s0) && ok; splitk_reduce_f32(gslab.p, slices, M, M, T.p, M, 1.0f, 0.f, nullptr, 0.f, nullptr, 0.f, s0); });
+            const float p2 = time_ms(s0, 200, [&] { gemm_f32(ap, s0); split_planes_bf16(C.p, F, M, F, ph.p, pl.p, pl2.p, s0); });
+            const float f2 = time_ms(s0, 200, [&] { ok = linv_apply_slab(la2, s0) && ok; });
+            std::printf("apply F=%4d M=%d: L^-1 GEMM + Gram GEMM + Gram reduce %.1f us; linv_apply%s + Gram reduce %.1f us;  L^-1 GEMM + three-way split %.1f us; linv_apply with planes %.1f us\n",
+                        F, M, p1 * 1e3, ok ? "" : " (REFUSED)", f1 * 1e3, p2 * 1e3, f2 * 1e3);
+        }
         return 0;
     }
     hipStream_t s;
