@@ -1002,26 +1002,33 @@ class DescContext:
         assert s.ndim == 2 and s.shape[1] == 2 and d.shape == s.shape
         return s, d
 
+    def _verify_model(self, call, src, dst, threshold, n_hyp, seed, refine):
+        """call is dlco_desc_verify_homography or dlco_desc_verify_fundamental: (M [3,3], inlier [m] bool, best_hyp)."""
+        s, d = self._match_points(src, dst)
+        m = s.shape[0]
+        M, mask = np.zeros((3, 3), np.float64), np.zeros(m, np.uint8)
+        n, best = C.c_int64(), C.c_int32()
+        self._ck(call(self.h, _p(s, f32p), _p(d, f32p), m, threshold, n_hyp, seed, refine, _p(M, C.POINTER(C.c_double)), _p(mask, u8p),
+                      C.byref(n), C.byref(best)))
+        assert n.value == int(mask.sum())
+        return M, mask.astype(bool), best.value
+
+    def _verify_hypotheses(self, call, src, dst, threshold, n_hyp, seed):
+        """call is dlco_desc_verify_hypotheses or dlco_desc_verify_fundamental_hypotheses: (M_all [n_hyp,3,3], count [n_hyp])."""
+        s, d = self._match_points(src, dst)
+        M_all, count = np.zeros((n_hyp, 3, 3), np.float64), np.zeros(n_hyp, np.int32)
+        self._ck(call(self.h, _p(s, f32p), _p(d, f32p), s.shape[0], threshold, n_hyp, seed, _p(M_all, C.POINTER(C.c_double)), _p(count, i32p)))
+        return M_all, count
+
     def verify_homography(self, src, dst, threshold=3.0, n_hyp=2048, seed=0, refine=2):
         """The homography of the matches src [m,2] -> dst [m,2] by the library's deterministic RANSAC: (H [3,3] f64 with
         max |H| in [1, 2), inlier [m] bool, best_hyp).  No model: H and inlier all zero, best_hyp = -1."""
-        s, d = self._match_points(src, dst)
-        m = s.shape[0]
-        H, mask = np.zeros((3, 3), np.float64), np.zeros(m, np.uint8)
-        n, best = C.c_int64(), C.c_int32()
-        self._ck(self.L.dlco_desc_verify_homography(self.h, _p(s, f32p), _p(d, f32p), m, threshold, n_hyp, seed, refine,
-                                                    _p(H, C.POINTER(C.c_double)), _p(mask, u8p), C.byref(n), C.byref(best)))
-        assert n.value == int(mask.sum())
-        return H, mask.astype(bool), best.value
+        return self._verify_model(self.L.dlco_desc_verify_homography, src, dst, threshold, n_hyp, seed, refine)
 
     def verify_hypotheses(self, src, dst, threshold=3.0, n_hyp=2048, seed=0):
         """Every hypothesis of verify_homography and its inlier count: (H_all [n_hyp,3,3] f64, all zero where invalid,
         count [n_hyp] int32)."""
-        s, d = self._match_points(src, dst)
-        H_all, count = np.zeros((n_hyp, 3, 3), np.float64), np.zeros(n_hyp, np.int32)
-        self._ck(self.L.dlco_desc_verify_hypotheses(self.h, _p(s, f32p), _p(d, f32p), s.shape[0], threshold, n_hyp, seed,
-                                                    _p(H_all, C.POINTER(C.c_double)), _p(count, i32p)))
-        return H_all, count
+        return self._verify_hypotheses(self.L.dlco_desc_verify_hypotheses, src, dst, threshold, n_hyp, seed)
 
     # ---- the same against a fundamental matrix (csrc/epipolar_rules.hpp states the rule) ----
     def verify_fundamental(self, src, dst, threshold=1.0, n_hyp=2048, seed=0, refine=2):
@@ -1029,23 +1036,12 @@ class DescContext:
         deterministic eight-point RANSAC: (F [3,3] f64 with max |F| in [1, 2), inlier [m] bool, best_hyp).  F is of rank 2 up to
         rounding once a refit round was accepted, the linear eight-point hypothesis otherwise.  No model: F and inlier all
         zero, best_hyp = -1."""
-        s, d = self._match_points(src, dst)
-        m = s.shape[0]
-        F, mask = np.zeros((3, 3), np.float64), np.zeros(m, np.uint8)
-        n, best = C.c_int64(), C.c_int32()
-        self._ck(self.L.dlco_desc_verify_fundamental(self.h, _p(s, f32p), _p(d, f32p), m, threshold, n_hyp, seed, refine,
-                                                     _p(F, C.POINTER(C.c_double)), _p(mask, u8p), C.byref(n), C.byref(best)))
-        assert n.value == int(mask.sum())
-        return F, mask.astype(bool), best.value
+        return self._verify_model(self.L.dlco_desc_verify_fundamental, src, dst, threshold, n_hyp, seed, refine)
 
     def verify_fundamental_hypotheses(self, src, dst, threshold=1.0, n_hyp=2048, seed=0):
         """Every hypothesis of verify_fundamental and its inlier count: (F_all [n_hyp,3,3] f64, all zero where invalid,
         count [n_hyp] int32)."""
-        s, d = self._match_points(src, dst)
-        F_all, count = np.zeros((n_hyp, 3, 3), np.float64), np.zeros(n_hyp, np.int32)
-        self._ck(self.L.dlco_desc_verify_fundamental_hypotheses(self.h, _p(s, f32p), _p(d, f32p), s.shape[0], threshold, n_hyp, seed,
-                                                                _p(F_all, C.POINTER(C.c_double)), _p(count, i32p)))
-        return F_all, count
+        return self._verify_hypotheses(self.L.dlco_desc_verify_fundamental_hypotheses, src, dst, threshold, n_hyp, seed)
 
     def match_device(self, q_ptr, nq, t_ptr, nt, r, idx_ptr, d_ptr, ldq=None, ldt=None):
         """match on tables in device memory (row pitches ldq, ldt: multiples of 4, default r); results to device memory."""

@@ -5,7 +5,8 @@
 // of projected descriptors in kernels_describe.hip, the sampling of patches around keypoints in kernels_patch.hip, the
 // quantisation of rows to bytes (quant_rules.hpp) and the match of byte tables in kernels_match_u8.hip, the detection of
 // keypoints (detect_rules.hpp) in kernels_detect.hip, their orientation (orient_rules.hpp) in kernels_orient.hip, the
-// verification of a match list against a homography (verify_rules.hpp) in kernels_verify.hip.
+// verification of a match list against a homography (verify_rules.hpp) or a fundamental matrix (epipolar_rules.hpp) in
+// kernels_verify.hip.
 // compute() serves every describe call: a PatchSource in, the rows a RowsOut names out.  The float and the byte matcher
 // share one host path (match_host, match_device) over a FloatLine / ByteLine.
 #include "../../include/dlco.h"
@@ -405,6 +406,106 @@ void match_host(dlco_desc_ctx *c, const typename L::Elem *query_host, int64_t nq
         sync(c);
     }
     c->last_ms = ms;
+}
+
+// ---- verification: a homography (verify_rules.hpp) or a fundamental matrix (epipolar_rules.hpp) between the two sides of
+// a match list, both in kernels_verify.hip; one host path over the rule header's Model (verify_rules::Homography,
+// epipolar_rules::Fundamental): the kernels of its hypotheses, of their counts and of the mask of one model, its refit round
+// on the host; Model::kSample matches make a sample -----------------------------------------------------------------------
+using verify_rules::Homography;
+using epipolar_rules::Fundamental;
+
+template <typename Model>
+bool verify_args_ok(const float *src, const float *dst, int64_t m, float threshold, int32_t n_hyp)
+{
+    return src && dst && m >= Model::kSample && m < ((int64_t)1 << 31) && std::isfinite(threshold) && threshold > 0.0f && n_hyp >= 1 &&
+           n_hyp <= verify_rules::kMaxHyp;
+}
+
+// the matches to the device, every hypothesis and its count there; returns the kernels' milliseconds
+template <typename Model>
+double verify_all(dlco_desc_ctx *c, const EventPair &ev, const float *src_host, const float *dst_host, int64_t m, double t2,
+                  int32_t n_hyp, uint64_t seed)
+{
+    DLCO_HIP(hipSetDevice(c->device));
+    c->v_src.alloc((size_t)m * 2); c->v_dst.alloc((size_t)m * 2);
+    c->v_H.alloc((size_t)n_hyp * 9); c->v_count.alloc((size_t)n_hyp);
+    c->v_key.alloc(1); c->v_n.alloc(1);
+    DLCO_HIP(hipMemcpyAsync(c->v_src.p, src_host, (size_t)m * 2 * sizeof(float), hipMemcpyHostToDevice, c->stream));
+    DLCO_HIP(hipMemcpyAsync(c->v_dst.p, dst_host, (size_t)m * 2 * sizeof(float), hipMemcpyHostToDevice, c->stream));
+    DLCO_HIP(hipMemsetAsync(c->v_count.p, 0, (size_t)n_hyp * sizeof(int32_t), c->stream));
+    return timed_ms(c, ev, [&] {
+        verify_hypotheses<Model>(c->v_src.p, c->v_dst.p, m, seed, n_hyp, c->v_H.p, c->stream);
+        verify_score<Model>(c->v_src.p, c->v_dst.p, m, c->v_H.p, n_hyp, t2, c->v_count.p, c->stream);
+        verify_select(c->v_count.p, n_hyp, c->v_key.p, c->stream);
+    });
+}
+
+// mask [m] on the host and the count of H over the uploaded matches; adds the kernel's time to *ms
+template <typename Model>
+int64_t verify_score_one(dlco_desc_ctx *c, const EventPair &ev, int64_t m, const double *H, double t2, uint8_t *mask_host,
+                         double *ms)
+{
+    int32_t n = 0;
+    c->v_mask.alloc((size_t)m);
+    DLCO_HIP(hipMemsetAsync(c->v_n.p, 0, sizeof(int32_t), c->stream));
+    *ms += timed_ms(c, ev, [&] { verify_mask<Model>(c->v_src.p, c->v_dst.p, m, H, t2, c->v_mask.p, c->v_n.p, c->stream); }, [&] {
+        DLCO_HIP(hipMemcpyAsync(mask_host, c->v_mask.p, (size_t)m, hipMemcpyDeviceToHost, c->stream));
+        DLCO_HIP(hipMemcpyAsync(&n, c->v_n.p, sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
+    });
+    return n;
+}
+
+// every hypothesis of the model and its count, to the host
+template <typename Model>
+int verify_hypotheses_call(dlco_desc_ctx *c, const float *src_xy_host, const float *dst_xy_host, int64_t m, float threshold,
+                           int32_t n_hyp, uint64_t seed, double *M_all_host, int32_t *count_host)
+{
+    if (!c || !M_all_host || !count_host || !verify_args_ok<Model>(src_xy_host, dst_xy_host, m, threshold, n_hyp)) return DLCO_ERR_INVALID;
+    return guarded(c, [&] {
+        EventPair ev;
+        c->last_ms = verify_all<Model>(c, ev, src_xy_host, dst_xy_host, m, verify_rules::threshold_sq(threshold), n_hyp, seed);
+        DLCO_HIP(hipMemcpyAsync(M_all_host, c->v_H.p, (size_t)n_hyp * 9 * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+        DLCO_HIP(hipMemcpyAsync(count_host, c->v_count.p, (size_t)n_hyp * sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
+        sync(c);
+    });
+}
+
+// the best model, its mask and the refit: a round's model is formed on the host, the mask kernel scores it
+template <typename Model>
+int verify_model_call(dlco_desc_ctx *c, const float *src_xy_host, const float *dst_xy_host, int64_t m, float threshold,
+                      int32_t n_hyp, uint64_t seed, int32_t refine, double *M_out, uint8_t *inlier_host, int64_t *n_inliers, int32_t *best_hyp)
+{
+    if (!c || !M_out || !n_inliers || refine < 0 || refine > verify_rules::kMaxRefine ||
+        !verify_args_ok<Model>(src_xy_host, dst_xy_host, m, threshold, n_hyp))
+        return DLCO_ERR_INVALID;
+    return guarded(c, [&] {
+        namespace vr = verify_rules;
+        const double t2 = vr::threshold_sq(threshold);
+        EventPair ev;
+        double ms = verify_all<Model>(c, ev, src_xy_host, dst_xy_host, m, t2, n_hyp, seed);
+        uint64_t key = 0;
+        DLCO_HIP(hipMemcpyAsync(&key, c->v_key.p, sizeof key, hipMemcpyDeviceToHost, c->stream));
+        sync(c);
+        double M[9] = {0};
+        std::vector<uint8_t> mask((size_t)m, 0);
+        int64_t count = 0;
+        int32_t best = -1;
+        if (vr::key_count(key) > 0) {
+            best = vr::key_hyp(key);
+            DLCO_HIP(hipMemcpyAsync(M, c->v_H.p + 9 * (size_t)best, sizeof M, hipMemcpyDeviceToHost, c->stream));
+            sync(c);
+            count = verify_score_one<Model>(c, ev, m, M, t2, mask.data(), &ms);
+            vr::refit_rounds(m, refine, M, mask.data(), count,
+                             [&](const uint8_t *cur, double *Mn) { return Model::refit_round(src_xy_host, dst_xy_host, m, cur, Mn); },
+                             [&](const double *Mn, uint8_t *trial) { return verify_score_one<Model>(c, ev, m, Mn, t2, trial, &ms); }, nullptr);
+        }
+        std::memcpy(M_out, M, sizeof M);
+        if (inlier_host) std::memcpy(inlier_host, mask.data(), (size_t)m);
+        *n_inliers = count;
+        if (best_hyp) *best_hyp = best;
+        c->last_ms = ms;
+    });
 }
 }  // namespace
 
@@ -1156,116 +1257,11 @@ int dlco_desc_cross_sqdists_guided_epipolar(dlco_desc_ctx *c, const float *query
     });
 }
 
-// ---- verification: a homography (verify_rules.hpp, kernels_verify.hip) or a fundamental matrix (epipolar_rules.hpp,
-// kernels_epipolar.hip) between the two sides of a match list; one host path for both, the selection kernel is shared ------
-namespace {
-// one model: the kernels of its hypotheses, of their counts and of the mask of one model, the rule header's refit round on
-// the host; min_m matches make a sample
-struct VerifyModel {
-    decltype(&verify_hypotheses) hypotheses;
-    decltype(&verify_score) score;
-    decltype(&verify_mask) mask;
-    decltype(&verify_rules::refit_round) round;
-    int64_t min_m;
-};
-constexpr VerifyModel kHomography{verify_hypotheses, verify_score, verify_mask, verify_rules::refit_round, 4};
-constexpr VerifyModel kFundamental{epipolar_hypotheses, epipolar_score, epipolar_mask, epipolar_rules::refit_round,
-                                   epipolar_rules::kSample};
-
-bool verify_args_ok(const VerifyModel &k, const float *src, const float *dst, int64_t m, float threshold, int32_t n_hyp)
-{
-    return src && dst && m >= k.min_m && m < ((int64_t)1 << 31) && std::isfinite(threshold) && threshold > 0.0f && n_hyp >= 1 &&
-           n_hyp <= verify_rules::kMaxHyp;
-}
-
-// the matches to the device, every hypothesis and its count there; returns the kernels' milliseconds
-double verify_all(dlco_desc_ctx *c, const EventPair &ev, const VerifyModel &k, const float *src_host, const float *dst_host, int64_t m, double t2,
-                  int32_t n_hyp, uint64_t seed)
-{
-    DLCO_HIP(hipSetDevice(c->device));
-    c->v_src.alloc((size_t)m * 2); c->v_dst.alloc((size_t)m * 2);
-    c->v_H.alloc((size_t)n_hyp * 9); c->v_count.alloc((size_t)n_hyp);
-    c->v_key.alloc(1); c->v_n.alloc(1);
-    DLCO_HIP(hipMemcpyAsync(c->v_src.p, src_host, (size_t)m * 2 * sizeof(float), hipMemcpyHostToDevice, c->stream));
-    DLCO_HIP(hipMemcpyAsync(c->v_dst.p, dst_host, (size_t)m * 2 * sizeof(float), hipMemcpyHostToDevice, c->stream));
-    DLCO_HIP(hipMemsetAsync(c->v_count.p, 0, (size_t)n_hyp * sizeof(int32_t), c->stream));
-    return timed_ms(c, ev, [&] {
-        k.hypotheses(c->v_src.p, c->v_dst.p, m, seed, n_hyp, c->v_H.p, c->stream);
-        k.score(c->v_src.p, c->v_dst.p, m, c->v_H.p, n_hyp, t2, c->v_count.p, c->stream);
-        verify_select(c->v_count.p, n_hyp, c->v_key.p, c->stream);
-    });
-}
-
-// mask [m] on the host and the count of H over the uploaded matches; adds the kernel's time to *ms
-int64_t verify_score_one(dlco_desc_ctx *c, const EventPair &ev, const VerifyModel &k, int64_t m, const double *H, double t2, uint8_t *mask_host,
-                         double *ms)
-{
-    int32_t n = 0;
-    c->v_mask.alloc((size_t)m);
-    DLCO_HIP(hipMemsetAsync(c->v_n.p, 0, sizeof(int32_t), c->stream));
-    *ms += timed_ms(c, ev, [&] { k.mask(c->v_src.p, c->v_dst.p, m, H, t2, c->v_mask.p, c->v_n.p, c->stream); }, [&] {
-        DLCO_HIP(hipMemcpyAsync(mask_host, c->v_mask.p, (size_t)m, hipMemcpyDeviceToHost, c->stream));
-        DLCO_HIP(hipMemcpyAsync(&n, c->v_n.p, sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
-    });
-    return n;
-}
-
-// every hypothesis of the model and its count, to the host
-int verify_hypotheses_call(dlco_desc_ctx *c, const VerifyModel &k, const float *src_xy_host, const float *dst_xy_host, int64_t m, float threshold,
-                           int32_t n_hyp, uint64_t seed, double *M_all_host, int32_t *count_host)
-{
-    if (!c || !M_all_host || !count_host || !verify_args_ok(k, src_xy_host, dst_xy_host, m, threshold, n_hyp)) return DLCO_ERR_INVALID;
-    return guarded(c, [&] {
-        EventPair ev;
-        c->last_ms = verify_all(c, ev, k, src_xy_host, dst_xy_host, m, verify_rules::threshold_sq(threshold), n_hyp, seed);
-        DLCO_HIP(hipMemcpyAsync(M_all_host, c->v_H.p, (size_t)n_hyp * 9 * sizeof(double), hipMemcpyDeviceToHost, c->stream));
-        DLCO_HIP(hipMemcpyAsync(count_host, c->v_count.p, (size_t)n_hyp * sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
-        sync(c);
-    });
-}
-
-// the best model, its mask and the refit: a round's model is formed on the host, the mask kernel scores it
-int verify_model_call(dlco_desc_ctx *c, const VerifyModel &k, const float *src_xy_host, const float *dst_xy_host, int64_t m, float threshold,
-                      int32_t n_hyp, uint64_t seed, int32_t refine, double *M_out, uint8_t *inlier_host, int64_t *n_inliers, int32_t *best_hyp)
-{
-    if (!c || !M_out || !n_inliers || refine < 0 || refine > verify_rules::kMaxRefine ||
-        !verify_args_ok(k, src_xy_host, dst_xy_host, m, threshold, n_hyp))
-        return DLCO_ERR_INVALID;
-    return guarded(c, [&] {
-        namespace vr = verify_rules;
-        const double t2 = vr::threshold_sq(threshold);
-        EventPair ev;
-        double ms = verify_all(c, ev, k, src_xy_host, dst_xy_host, m, t2, n_hyp, seed);
-        uint64_t key = 0;
-        DLCO_HIP(hipMemcpyAsync(&key, c->v_key.p, sizeof key, hipMemcpyDeviceToHost, c->stream));
-        sync(c);
-        double M[9] = {0};
-        std::vector<uint8_t> mask((size_t)m, 0);
-        int64_t count = 0;
-        int32_t best = -1;
-        if (vr::key_count(key) > 0) {
-            best = vr::key_hyp(key);
-            DLCO_HIP(hipMemcpyAsync(M, c->v_H.p + 9 * (size_t)best, sizeof M, hipMemcpyDeviceToHost, c->stream));
-            sync(c);
-            count = verify_score_one(c, ev, k, m, M, t2, mask.data(), &ms);
-            vr::refit_rounds(m, refine, M, mask.data(), count,
-                             [&](const uint8_t *cur, double *Mn) { return k.round(src_xy_host, dst_xy_host, m, cur, Mn); },
-                             [&](const double *Mn, uint8_t *trial) { return verify_score_one(c, ev, k, m, Mn, t2, trial, &ms); }, nullptr);
-        }
-        std::memcpy(M_out, M, sizeof M);
-        if (inlier_host) std::memcpy(inlier_host, mask.data(), (size_t)m);
-        *n_inliers = count;
-        if (best_hyp) *best_hyp = best;
-        c->last_ms = ms;
-    });
-}
-}  // namespace
-
 // H_all [n_hyp][9] and count [n_hyp] of every hypothesis of the rule: what dlco_desc_verify_homography selects from
 int dlco_desc_verify_hypotheses(dlco_desc_ctx *c, const float *src_xy_host, const float *dst_xy_host, int64_t m, float threshold, int32_t n_hyp,
                                 uint64_t seed, double *H_all_host, int32_t *count_host)
 {
-    return verify_hypotheses_call(c, kHomography, src_xy_host, dst_xy_host, m, threshold, n_hyp, seed, H_all_host, count_host);
+    return verify_hypotheses_call<Homography>(c, src_xy_host, dst_xy_host, m, threshold, n_hyp, seed, H_all_host, count_host);
 }
 
 // H [9] row-major, the inlier mask [m] (may be NULL), its count and the winning hypothesis (may be NULL); no model is no
@@ -1274,20 +1270,20 @@ int dlco_desc_verify_hypotheses(dlco_desc_ctx *c, const float *src_xy_host, cons
 int dlco_desc_verify_homography(dlco_desc_ctx *c, const float *src_xy_host, const float *dst_xy_host, int64_t m, float threshold, int32_t n_hyp,
                                 uint64_t seed, int32_t refine, double *H_out, uint8_t *inlier_host, int64_t *n_inliers, int32_t *best_hyp)
 {
-    return verify_model_call(c, kHomography, src_xy_host, dst_xy_host, m, threshold, n_hyp, seed, refine, H_out, inlier_host, n_inliers, best_hyp);
+    return verify_model_call<Homography>(c, src_xy_host, dst_xy_host, m, threshold, n_hyp, seed, refine, H_out, inlier_host, n_inliers, best_hyp);
 }
 
 // the same two calls for a fundamental matrix F, x'^T F x = 0 (epipolar_rules.hpp), with m >= 8
 int dlco_desc_verify_fundamental_hypotheses(dlco_desc_ctx *c, const float *src_xy_host, const float *dst_xy_host, int64_t m, float threshold,
                                             int32_t n_hyp, uint64_t seed, double *F_all_host, int32_t *count_host)
 {
-    return verify_hypotheses_call(c, kFundamental, src_xy_host, dst_xy_host, m, threshold, n_hyp, seed, F_all_host, count_host);
+    return verify_hypotheses_call<Fundamental>(c, src_xy_host, dst_xy_host, m, threshold, n_hyp, seed, F_all_host, count_host);
 }
 
 int dlco_desc_verify_fundamental(dlco_desc_ctx *c, const float *src_xy_host, const float *dst_xy_host, int64_t m, float threshold, int32_t n_hyp,
                                  uint64_t seed, int32_t refine, double *F_out, uint8_t *inlier_host, int64_t *n_inliers, int32_t *best_hyp)
 {
-    return verify_model_call(c, kFundamental, src_xy_host, dst_xy_host, m, threshold, n_hyp, seed, refine, F_out, inlier_host, n_inliers, best_hyp);
+    return verify_model_call<Fundamental>(c, src_xy_host, dst_xy_host, m, threshold, n_hyp, seed, refine, F_out, inlier_host, n_inliers, best_hyp);
 }
 
 // ---- byte descriptors: the quantiser (quant_rules.hpp), the _u8 forms of describe, the match of byte tables -------------------

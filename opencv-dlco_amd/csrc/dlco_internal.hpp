@@ -594,17 +594,16 @@ void detect_select(const uint64_t *pos, const int64_t *resp, const float *kp, un
 // orientation (kernels_orient.hip; the rule is orient_rules.hpp): vectors [n][2] and status [n] of keypoints [n][4] from S
 void orient_keypoints(const uint32_t *S, int W, int H, const float *kp, int64_t n, int64_t *vec, uint8_t *status, hipStream_t s);
 
-// verification (kernels_verify.hip; the rule is verify_rules.hpp): the matches src, dst [m][2] in device memory, 8-byte aligned.
-// H_all [n_hyp][9] of every hypothesis; count [n_hyp] += their inliers (the caller zeroes it); *best = the largest selection
-// key; mask [m] of the host's H [9] and *count += its inliers
-void verify_hypotheses(const float *src, const float *dst, int64_t m, uint64_t seed, int n_hyp, double *H_all, hipStream_t s);
-void verify_score(const float *src, const float *dst, int64_t m, const double *H_all, int n_hyp, double t2, int32_t *count, hipStream_t s);
+// verification (kernels_verify.hip): the matches src, dst [m][2] in device memory, 8-byte aligned.  Model is
+// verify_rules::Homography (the rule is verify_rules.hpp) or epipolar_rules::Fundamental (epipolar_rules.hpp), the two that
+// kernels_verify.hip instantiates.  M_all [n_hyp][9] of every hypothesis; count [n_hyp] += their inliers (the caller zeroes
+// it); *best = the largest selection key; mask [m] of the host's M [9] and *count += its inliers
+template <typename Model>
+void verify_hypotheses(const float *src, const float *dst, int64_t m, uint64_t seed, int n_hyp, double *M_all, hipStream_t s);
+template <typename Model>
+void verify_score(const float *src, const float *dst, int64_t m, const double *M_all, int n_hyp, double t2, int32_t *count, hipStream_t s);
 void verify_select(const int32_t *count, int n_hyp, uint64_t *best, hipStream_t s);
-void verify_mask(const float *src, const float *dst, int64_t m, const double *H, double t2, uint8_t *mask, int32_t *count, hipStream_t s);
-
-// the same against a fundamental matrix (kernels_epipolar.hip; the rule is epipolar_rules.hpp); the selection is verify_select
-void epipolar_hypotheses(const float *src, const float *dst, int64_t m, uint64_t seed, int n_hyp, double *F_all, hipStream_t s);
-void epipolar_score(const float *src, const float *dst, int64_t m, const double *F_all, int n_hyp, double t2, int32_t *count, hipStream_t s);
-void epipolar_mask(const float *src, const float *dst, int64_t m, const double *F, double t2, uint8_t *mask, int32_t *count, hipStream_t s);
+template <typename Model>
+void verify_mask(const float *src, const float *dst, int64_t m, const double *M, double t2, uint8_t *mask, int32_t *count, hipStream_t s);
 
 }  // namespace dlco

@@ -2,7 +2,7 @@
 // (dlco_desc_verify_fundamental, dlco_desc_verify_fundamental_hypotheses): the deterministic RANSAC of verify_rules.hpp with
 // the epipolar model x'^T F x = 0, x = (x, y, 1) from src and x' = (u, v, 1) from dst.  Hypotheses from eight matches each, an
 // inlier count for every hypothesis, the best by the same total order, and a refit on the inliers.  The rule stated once for
-// the host, the kernels (kernels_epipolar.hip) and the CPU tests (tests/shim/epipolar_rules_shim.cpp).  Plain C++: no HIP
+// the host, the kernels (kernels_verify.hip) and the CPU tests (tests/shim/epipolar_rules_shim.cpp).  Plain C++: no HIP
 // header, no device, no I/O.
 //
 // This is NOT cv::findFundamentalMat, which nothing here can run or pin, and no parity with it is claimed.  It is a rule of
@@ -298,30 +298,6 @@ VERIFY_RULES_HD inline bool inlier(const double F[9], double x, double y, double
 }
 
 // ---- the rule on the host: what the kernels must reproduce ---------------------------------------------------------------
-// F_all [n_hyp][9]; idx_all [n_hyp][8] and valid [n_hyp] may be NULL
-inline void all_hypotheses(const float *src, const float *dst, int64_t m, int32_t n_hyp, uint64_t seed, double *F_all, int32_t *idx_all,
-                           uint8_t *valid)
-{
-    for (int32_t h = 0; h < n_hyp; h++) {
-        int32_t idx[kSample];
-        const bool ok = hypothesis(src, dst, (uint32_t)m, seed, (uint32_t)h, idx, F_all + 9 * (int64_t)h);
-        if (idx_all) std::memcpy(idx_all + kSample * (int64_t)h, idx, sizeof idx);
-        if (valid) valid[h] = ok ? 1 : 0;
-    }
-}
-
-// the inliers of F among all matches; mask [m] may be NULL
-inline int64_t count_inliers(const double F[9], const float *src, const float *dst, int64_t m, double t2, uint8_t *mask)
-{
-    int64_t n = 0;
-    for (int64_t i = 0; i < m; i++) {
-        const bool in = inlier(F, (double)src[2 * i], (double)src[2 * i + 1], (double)dst[2 * i], (double)dst[2 * i + 1], t2);
-        if (mask) mask[i] = in ? 1 : 0;
-        n += in ? 1 : 0;
-    }
-    return n;
-}
-
 // cyclic Jacobi of the symmetric N [n][n] (row-major, n <= 9): N's diagonal becomes the eigenvalues, V [n][n] the eigenvectors
 // in its columns; returns the number of sweeps that rotated
 inline int jacobi(double *N, int n, double *V)
@@ -403,29 +379,38 @@ inline bool refit_round(const float *src, const float *dst, int64_t m, const uin
     return finish(Fn, ss, -(ss * cxs), -(ss * cys), sd, -(sd * cxd), -(sd * cyd), F_out);
 }
 
-// The whole rule on the host, as verify_rules::verify_host: F [9], mask [m], *count, *best_hyp (-1: no model, F and mask
-// zero); F_all [n_hyp][9] and counts [n_hyp] scratch of the caller; rounds [refine][9] (may be NULL) every F' a round formed,
-// *n_rounds their number (may be NULL).
+// The fundamental matrix as the frame of verify_rules.hpp (all_hypotheses, count_inliers, verify_host) and the kernels
+// (kernels_verify.hip) take a model: the sample size and the three functions above, nothing of its own.
+struct Fundamental {
+    static constexpr int kSample = epipolar_rules::kSample;
+    VERIFY_RULES_HD static bool hypothesis(const float *src, const float *dst, uint32_t m, uint64_t seed, uint32_t h, int32_t idx[kSample], double F[9])
+    {
+        return epipolar_rules::hypothesis(src, dst, m, seed, h, idx, F);
+    }
+    VERIFY_RULES_HD static bool inlier(const double F[9], double x, double y, double u, double v, double t2)
+    {
+        return epipolar_rules::inlier(F, x, y, u, v, t2);
+    }
+    static bool refit_round(const float *src, const float *dst, int64_t m, const uint8_t *mask, double F_out[9])
+    {
+        return epipolar_rules::refit_round(src, dst, m, mask, F_out);
+    }
+};
+
+// the frame with the fundamental matrix under this namespace's plain names: what the tests' shims call
+inline void all_hypotheses(const float *src, const float *dst, int64_t m, int32_t n_hyp, uint64_t seed, double *F_all, int32_t *idx_all,
+                           uint8_t *valid)
+{
+    vr::all_hypotheses<Fundamental>(src, dst, m, n_hyp, seed, F_all, idx_all, valid);
+}
+inline int64_t count_inliers(const double F[9], const float *src, const float *dst, int64_t m, double t2, uint8_t *mask)
+{
+    return vr::count_inliers<Fundamental>(F, src, dst, m, t2, mask);
+}
 inline void verify_host(const float *src, const float *dst, int64_t m, float threshold, int32_t n_hyp, uint64_t seed, int32_t refine, double *F_all,
                         int32_t *counts, double F[9], uint8_t *mask, int64_t *count, int32_t *best_hyp, double *rounds, int32_t *n_rounds)
 {
-    const double t2 = vr::threshold_sq(threshold);
-    all_hypotheses(src, dst, m, n_hyp, seed, F_all, nullptr, nullptr);
-    for (int32_t h = 0; h < n_hyp; h++) counts[h] = (int32_t)count_inliers(F_all + 9 * (int64_t)h, src, dst, m, t2, nullptr);
-    const uint64_t key = vr::select(counts, n_hyp);
-    if (n_rounds) *n_rounds = 0;
-    if (vr::key_count(key) == 0) {
-        for (int i = 0; i < 9; i++) F[i] = 0.0;
-        std::memset(mask, 0, (size_t)m);
-        *count = 0; *best_hyp = -1;
-        return;
-    }
-    *best_hyp = vr::key_hyp(key);
-    std::memcpy(F, F_all + 9 * (int64_t)*best_hyp, 9 * sizeof(double));
-    *count = count_inliers(F, src, dst, m, t2, mask);
-    const int formed = vr::refit_rounds(m, refine, F, mask, *count, [&](const uint8_t *cur, double *Fn) { return refit_round(src, dst, m, cur, Fn); },
-                                        [&](const double *Fn, uint8_t *trial) { return count_inliers(Fn, src, dst, m, t2, trial); }, rounds);
-    if (n_rounds) *n_rounds = formed;
+    vr::verify_host<Fundamental>(src, dst, m, threshold, n_hyp, seed, refine, F_all, counts, F, mask, count, best_hyp, rounds, n_rounds);
 }
 
 }  // namespace epipolar_rules

@@ -1,18 +1,25 @@
-// kernels_verify.hip — geometric verification of a match list (dlco_desc_verify_homography, dlco_desc_verify_hypotheses).  The
-// rule is verify_rules.hpp, where it is stated; this file only decides where the numbers are read from and in which order
-// the work is done.  Every floating-point operation is the header's (contraction off there), every sum is of integers.
+// kernels_verify.hip — geometric verification of a match list against a two-view model: the homography
+// (dlco_desc_verify_homography, dlco_desc_verify_hypotheses; verify_rules::Homography) or the fundamental matrix
+// (dlco_desc_verify_fundamental, dlco_desc_verify_fundamental_hypotheses; epipolar_rules::Fundamental).  The rules are
+// verify_rules.hpp and epipolar_rules.hpp, where they are stated; this file only decides where the numbers are read from and
+// in which order the work is done, once for every Model.  Every floating-point operation is the headers' (contraction off
+// there), every sum is of integers.
 //
-//   verify_hyp_kernel     one lane per hypothesis: its sample, its model, H_all [n_hyp][9] (all zero when invalid).
-//   verify_score_kernel   the hot loop, on a grid of ceil(n_hyp / 256) x ceil(m / kScoreChunk) workgroups of 256.  A lane
-//                         owns one hypothesis and keeps its H in registers (9 doubles).  The chunk's matches are widened to
+//   hyp_kernel<Model>     one lane per hypothesis: its sample, its model, M_all [n_hyp][9] (all zero when invalid).  For the
+//                         fundamental matrix that is the 8 x 9 system eliminated with complete pivoting.  The system lives in
+//                         registers: the header's loops unroll to constant indices and every run-time pivot is a predicated
+//                         swap, so there is no scratch.  Workgroups of kHypLanes<Model>.
+//   score_kernel<Model>   the hot loop, on a grid of ceil(n_hyp / 256) x ceil(m / kScoreChunk) workgroups of 256.  A lane
+//                         owns one hypothesis and keeps its M in registers (9 doubles).  The chunk's matches are widened to
 //                         double once and staged in LDS as (x, y, u, v); in the loop every lane reads the same address, an
-//                         LDS broadcast without conflicts: two 16-byte reads and about 19 fp64 operations per (hypothesis,
-//                         match).  A private int32 counter per lane, one integer atomicAdd per (hypothesis, chunk) into
-//                         count [h]: integer sums do not depend on the order, so neither on the chunking.
+//                         LDS broadcast without conflicts: two 16-byte reads and about 19 (homography) or 33 (fundamental
+//                         matrix) fp64 operations per (hypothesis, match).  A private int32 counter per lane, one integer
+//                         atomicAdd per (hypothesis, chunk) into count [h]: integer sums do not depend on the order, so
+//                         neither on the chunking.
 //   verify_select_kernel  one workgroup: the maximum of the key (count << 32) | (0xFFFFFFFF - h).
-//   verify_mask_kernel    one lane per match for one H: the u8 mask and, by a ballot per wave and one atomicAdd, its count.
+//   mask_kernel<Model>    one lane per match for one M: the u8 mask and, by a ballot per wave and one atomicAdd, its count.
 #include "dlco_internal.hpp"
-#include "verify_rules.hpp"
+#include "epipolar_rules.hpp"
 
 namespace dlco {
 
@@ -23,21 +30,27 @@ namespace vr = verify_rules;
 constexpr int VTH = 256;
 constexpr int VSEL = 1024;                                  // lanes of the selection's one workgroup
 
-struct Homography { double h[9]; };
+// lanes of a workgroup of the hypothesis kernel: 64 for the eight-point model, so that a lane may hold the 72 doubles of
+// its system and the compiler need not spill
+template <typename Model> constexpr int kHypLanes = VTH;
+template <> constexpr int kHypLanes<epipolar_rules::Fundamental> = 64;
 
-__global__ __launch_bounds__(VTH) void verify_hyp_kernel(const float *src, const float *dst, unsigned m, unsigned long long seed, int n_hyp,
-                                                         double *H_all)
+struct Matrix3 { double m[9]; };
+
+template <typename Model>
+__global__ __launch_bounds__(kHypLanes<Model>) void hyp_kernel(const float *src, const float *dst, unsigned m, unsigned long long seed, int n_hyp,
+                                                               double *M_all)
 {
-    const int h = blockIdx.x * VTH + threadIdx.x;
+    const int h = blockIdx.x * kHypLanes<Model> + threadIdx.x;
     if (h >= n_hyp) return;
-    int32_t idx[4];
-    double H[9];
-    vr::hypothesis(src, dst, m, seed, (uint32_t)h, idx, H);
-    for (int i = 0; i < 9; i++) H_all[9 * (long)h + i] = H[i];
+    int32_t idx[Model::kSample];
+    double M[9];
+    Model::hypothesis(src, dst, m, seed, (uint32_t)h, idx, M);
+    for (int i = 0; i < 9; i++) M_all[9 * (long)h + i] = M[i];
 }
 
-__global__ __launch_bounds__(VTH) void verify_score_kernel(const float2 *src, const float2 *dst, int m, const double *H_all, int n_hyp, double t2,
-                                                           int *count)
+template <typename Model>
+__global__ __launch_bounds__(VTH) void score_kernel(const float2 *src, const float2 *dst, int m, const double *M_all, int n_hyp, double t2, int *count)
 {
     __shared__ double4 pts[vr::kScoreChunk];
     static_assert(vr::kScoreChunk == VTH, "a lane stages one match of the chunk");
@@ -48,13 +61,14 @@ __global__ __launch_bounds__(VTH) void verify_score_kernel(const float2 *src, co
         const float2 s = src[i0 + threadIdx.x], d = dst[i0 + threadIdx.x];
         pts[threadIdx.x] = make_double4((double)s.x, (double)s.y, (double)d.x, (double)d.y);
     }
-    double H[9];
-    for (int i = 0; i < 9; i++) H[i] = h < n_hyp ? H_all[9 * (long)h + i] : 0.0;      // H = 0 has no inlier: W > 0 fails
+    double M[9];
+    // M = 0 has no inlier: W > 0 fails for a homography, S > 0 for a fundamental matrix
+    for (int i = 0; i < 9; i++) M[i] = h < n_hyp ? M_all[9 * (long)h + i] : 0.0;
     __syncthreads();
     int n = 0;
     for (int j = 0; j < cnt; j++) {
         const double4 p = pts[j];
-        n += vr::inlier(H, p.x, p.y, p.z, p.w, t2) ? 1 : 0;
+        n += Model::inlier(M, p.x, p.y, p.z, p.w, t2) ? 1 : 0;
     }
     if (h < n_hyp && n > 0) atomicAdd(&count[h], n);
 }
@@ -79,14 +93,14 @@ __global__ __launch_bounds__(VSEL) void verify_select_kernel(const int *count, i
     }
 }
 
-__global__ __launch_bounds__(VTH) void verify_mask_kernel(const float2 *src, const float2 *dst, int m, Homography Hm, double t2, uint8_t *mask,
-                                                          int *count)
+template <typename Model>
+__global__ __launch_bounds__(VTH) void mask_kernel(const float2 *src, const float2 *dst, int m, Matrix3 Mm, double t2, uint8_t *mask, int *count)
 {
     const long i = (long)blockIdx.x * VTH + threadIdx.x;
     bool in = false;
     if (i < m) {
         const float2 s = src[i], d = dst[i];
-        in = vr::inlier(Hm.h, (double)s.x, (double)s.y, (double)d.x, (double)d.y, t2);
+        in = Model::inlier(Mm.m, (double)s.x, (double)s.y, (double)d.x, (double)d.y, t2);
         mask[i] = in ? 1 : 0;
     }
     const int n = __popcll(__ballot(in));
@@ -95,23 +109,26 @@ __global__ __launch_bounds__(VTH) void verify_mask_kernel(const float2 *src, con
 
 }  // namespace
 
-// H_all [n_hyp][9] of the matches src, dst [m][2] (8-byte aligned), all in device memory
-void verify_hypotheses(const float *src, const float *dst, int64_t m, uint64_t seed, int n_hyp, double *H_all, hipStream_t s)
+// M_all [n_hyp][9] of the matches src, dst [m][2] (8-byte aligned), all in device memory
+template <typename Model>
+void verify_hypotheses(const float *src, const float *dst, int64_t m, uint64_t seed, int n_hyp, double *M_all, hipStream_t s)
 {
-    hipLaunchKernelGGL(verify_hyp_kernel, dim3((unsigned)((n_hyp + VTH - 1) / VTH)), dim3(VTH), 0, s, src, dst, (unsigned)m,
-                       (unsigned long long)seed, n_hyp, H_all);
+    constexpr int lanes = kHypLanes<Model>;
+    hipLaunchKernelGGL(hyp_kernel<Model>, dim3((unsigned)((n_hyp + lanes - 1) / lanes)), dim3(lanes), 0, s, src, dst, (unsigned)m,
+                       (unsigned long long)seed, n_hyp, M_all);
     DLCO_HIP(hipGetLastError());
 }
 
 // count [n_hyp] += the inliers of every hypothesis among the m matches; the caller zeroes count.  The grid's second
 // dimension holds 65535 chunks: more matches go by several launches.
-void verify_score(const float *src, const float *dst, int64_t m, const double *H_all, int n_hyp, double t2, int32_t *count, hipStream_t s)
+template <typename Model>
+void verify_score(const float *src, const float *dst, int64_t m, const double *M_all, int n_hyp, double t2, int32_t *count, hipStream_t s)
 {
     constexpr int64_t kLaunchMatches = (int64_t)32768 * vr::kScoreChunk;
     for (int64_t i0 = 0; i0 < m; i0 += kLaunchMatches) {
         const int cnt = (int)std::min<int64_t>(kLaunchMatches, m - i0);
-        hipLaunchKernelGGL(verify_score_kernel, dim3((unsigned)((n_hyp + VTH - 1) / VTH), (unsigned)((cnt + vr::kScoreChunk - 1) / vr::kScoreChunk)),
-                           dim3(VTH), 0, s, reinterpret_cast<const float2 *>(src) + i0, reinterpret_cast<const float2 *>(dst) + i0, cnt, H_all,
+        hipLaunchKernelGGL(score_kernel<Model>, dim3((unsigned)((n_hyp + VTH - 1) / VTH), (unsigned)((cnt + vr::kScoreChunk - 1) / vr::kScoreChunk)),
+                           dim3(VTH), 0, s, reinterpret_cast<const float2 *>(src) + i0, reinterpret_cast<const float2 *>(dst) + i0, cnt, M_all,
                            n_hyp, t2, count);
     }
     DLCO_HIP(hipGetLastError());
@@ -124,14 +141,23 @@ void verify_select(const int32_t *count, int n_hyp, uint64_t *best, hipStream_t 
     DLCO_HIP(hipGetLastError());
 }
 
-// mask [m] of the host's H [9] and *count += its inliers; the caller zeroes count
-void verify_mask(const float *src, const float *dst, int64_t m, const double *H, double t2, uint8_t *mask, int32_t *count, hipStream_t s)
+// mask [m] of the host's M [9] and *count += its inliers; the caller zeroes count
+template <typename Model>
+void verify_mask(const float *src, const float *dst, int64_t m, const double *M, double t2, uint8_t *mask, int32_t *count, hipStream_t s)
 {
-    Homography Hm;
-    for (int i = 0; i < 9; i++) Hm.h[i] = H[i];
-    hipLaunchKernelGGL(verify_mask_kernel, dim3((unsigned)((m + VTH - 1) / VTH)), dim3(VTH), 0, s, reinterpret_cast<const float2 *>(src),
-                       reinterpret_cast<const float2 *>(dst), (int)m, Hm, t2, mask, count);
+    Matrix3 Mm;
+    for (int i = 0; i < 9; i++) Mm.m[i] = M[i];
+    hipLaunchKernelGGL(mask_kernel<Model>, dim3((unsigned)((m + VTH - 1) / VTH)), dim3(VTH), 0, s, reinterpret_cast<const float2 *>(src),
+                       reinterpret_cast<const float2 *>(dst), (int)m, Mm, t2, mask, count);
     DLCO_HIP(hipGetLastError());
 }
+
+#define DLCO_VERIFY_MODEL(Model)                                                                                                 \
+    template void verify_hypotheses<Model>(const float *, const float *, int64_t, uint64_t, int, double *, hipStream_t);                \
+    template void verify_score<Model>(const float *, const float *, int64_t, const double *, int, double, int32_t *, hipStream_t);      \
+    template void verify_mask<Model>(const float *, const float *, int64_t, const double *, double, uint8_t *, int32_t *, hipStream_t);
+DLCO_VERIFY_MODEL(verify_rules::Homography)
+DLCO_VERIFY_MODEL(epipolar_rules::Fundamental)
+#undef DLCO_VERIFY_MODEL
 
 }  // namespace dlco

@@ -43,7 +43,7 @@
 // Selection.  count[h] = inliers of hypothesis h (0 for an invalid one: W = 0 everywhere).  The best has the largest count,
 // ties go to the smallest h: the maximum of the key (count << 32) | (0xFFFFFFFF - h).  A best count of 0: no model.
 //
-// Refit, on the host only (refit_round, refit).  At most `refine` rounds; a round runs on the inliers of the current model
+// Refit, on the host only (refit_round; the loop is refit_rounds).  At most `refine` rounds; a round runs on the inliers of the current model
 // in ascending match index:
 //   Hartley normalisation of each side: centroid c = (sum x / n, sum y / n), d = (sum sqrt(dx dx + dy dy)) / n with
 //   dx = x - cx, s = sqrt(2) / d, sums in index order; a normalised point is ((x - cx) s, (y - cy) s).
@@ -241,30 +241,6 @@ VERIFY_RULES_HD inline int32_t key_count(uint64_t key) { return (int32_t)(key >>
 VERIFY_RULES_HD inline int32_t key_hyp(uint64_t key) { return (int32_t)(0xFFFFFFFFu - (uint32_t)key); }
 
 // ---- the rule on the host: what the kernels must reproduce ---------------------------------------------------------------
-// H_all [n_hyp][9]; idx_all [n_hyp][4] and valid [n_hyp] may be NULL
-inline void all_hypotheses(const float *src, const float *dst, int64_t m, int32_t n_hyp, uint64_t seed, double *H_all, int32_t *idx_all,
-                           uint8_t *valid)
-{
-    for (int32_t h = 0; h < n_hyp; h++) {
-        int32_t idx[4];
-        const bool ok = hypothesis(src, dst, (uint32_t)m, seed, (uint32_t)h, idx, H_all + 9 * (int64_t)h);
-        if (idx_all) std::memcpy(idx_all + 4 * (int64_t)h, idx, sizeof idx);
-        if (valid) valid[h] = ok ? 1 : 0;
-    }
-}
-
-// the inliers of H among all matches; mask [m] may be NULL
-inline int64_t count_inliers(const double H[9], const float *src, const float *dst, int64_t m, double t2, uint8_t *mask)
-{
-    int64_t n = 0;
-    for (int64_t i = 0; i < m; i++) {
-        const bool in = inlier(H, (double)src[2 * i], (double)src[2 * i + 1], (double)dst[2 * i], (double)dst[2 * i + 1], t2);
-        if (mask) mask[i] = in ? 1 : 0;
-        n += in ? 1 : 0;
-    }
-    return n;
-}
-
 // the key of the best hypothesis; its count is 0 when there is no model
 inline uint64_t select(const int32_t *count, int32_t n_hyp)
 {
@@ -389,37 +365,91 @@ inline int refit_rounds(int64_t m, int32_t refine, double M[9], uint8_t *mask, i
     return formed;
 }
 
-// The refit of a homography (H, mask [m], count): refit_rounds with refit_round.  score is the host's count_inliers here, the
-// mask kernel in the library.
-template <typename Score>
-inline int refit(const float *src, const float *dst, int64_t m, int32_t refine, double H[9], uint8_t *mask, int64_t &count, Score &&score,
-                 double *rounds)
+// The homography as the frame below and the kernels (kernels_verify.hip) take a model: the sample size and the three
+// functions above, nothing of its own.  The fundamental matrix is epipolar_rules::Fundamental.
+struct Homography {
+    static constexpr int kSample = 4;
+    VERIFY_RULES_HD static bool hypothesis(const float *src, const float *dst, uint32_t m, uint64_t seed, uint32_t h, int32_t idx[kSample], double H[9])
+    {
+        return verify_rules::hypothesis(src, dst, m, seed, h, idx, H);
+    }
+    VERIFY_RULES_HD static bool inlier(const double H[9], double x, double y, double u, double v, double t2)
+    {
+        return verify_rules::inlier(H, x, y, u, v, t2);
+    }
+    static bool refit_round(const float *src, const float *dst, int64_t m, const uint8_t *mask, double H_out[9])
+    {
+        return verify_rules::refit_round(src, dst, m, mask, H_out);
+    }
+};
+
+// ---- the frame of every model: Model is Homography or epipolar_rules::Fundamental, M its 3 x 3 matrix row-major -----------
+// M_all [n_hyp][9]; idx_all [n_hyp][Model::kSample] and valid [n_hyp] may be NULL
+template <typename Model>
+inline void all_hypotheses(const float *src, const float *dst, int64_t m, int32_t n_hyp, uint64_t seed, double *M_all, int32_t *idx_all,
+                           uint8_t *valid)
 {
-    return refit_rounds(m, refine, H, mask, count, [&](const uint8_t *cur, double *Hn) { return refit_round(src, dst, m, cur, Hn); }, score, rounds);
+    for (int32_t h = 0; h < n_hyp; h++) {
+        int32_t idx[Model::kSample];
+        const bool ok = Model::hypothesis(src, dst, (uint32_t)m, seed, (uint32_t)h, idx, M_all + 9 * (int64_t)h);
+        if (idx_all) std::memcpy(idx_all + Model::kSample * (int64_t)h, idx, sizeof idx);
+        if (valid) valid[h] = ok ? 1 : 0;
+    }
 }
 
-// The whole rule on the host.  H [9], mask [m], *count, *best_hyp (-1: no model, H and mask zero); H_all [n_hyp][9] and
-// counts [n_hyp] scratch of the caller; rounds as for refit, *n_rounds the number formed (both may be NULL).
-inline void verify_host(const float *src, const float *dst, int64_t m, float threshold, int32_t n_hyp, uint64_t seed, int32_t refine, double *H_all,
-                        int32_t *counts, double H[9], uint8_t *mask, int64_t *count, int32_t *best_hyp, double *rounds, int32_t *n_rounds)
+// the inliers of M among all matches; mask [m] may be NULL
+template <typename Model>
+inline int64_t count_inliers(const double M[9], const float *src, const float *dst, int64_t m, double t2, uint8_t *mask)
+{
+    int64_t n = 0;
+    for (int64_t i = 0; i < m; i++) {
+        const bool in = Model::inlier(M, (double)src[2 * i], (double)src[2 * i + 1], (double)dst[2 * i], (double)dst[2 * i + 1], t2);
+        if (mask) mask[i] = in ? 1 : 0;
+        n += in ? 1 : 0;
+    }
+    return n;
+}
+
+// The whole rule on the host.  M [9], mask [m], *count, *best_hyp (-1: no model, M and mask zero); M_all [n_hyp][9] and
+// counts [n_hyp] scratch of the caller; rounds as for refit_rounds, *n_rounds the number formed (both may be NULL).  The
+// refit's score is count_inliers here, the mask kernel in the library.
+template <typename Model>
+inline void verify_host(const float *src, const float *dst, int64_t m, float threshold, int32_t n_hyp, uint64_t seed, int32_t refine, double *M_all,
+                        int32_t *counts, double M[9], uint8_t *mask, int64_t *count, int32_t *best_hyp, double *rounds, int32_t *n_rounds)
 {
     const double t2 = threshold_sq(threshold);
-    all_hypotheses(src, dst, m, n_hyp, seed, H_all, nullptr, nullptr);
-    for (int32_t h = 0; h < n_hyp; h++) counts[h] = (int32_t)count_inliers(H_all + 9 * (int64_t)h, src, dst, m, t2, nullptr);
+    all_hypotheses<Model>(src, dst, m, n_hyp, seed, M_all, nullptr, nullptr);
+    for (int32_t h = 0; h < n_hyp; h++) counts[h] = (int32_t)count_inliers<Model>(M_all + 9 * (int64_t)h, src, dst, m, t2, nullptr);
     const uint64_t key = select(counts, n_hyp);
     if (n_rounds) *n_rounds = 0;
     if (key_count(key) == 0) {
-        for (int i = 0; i < 9; i++) H[i] = 0.0;
+        for (int i = 0; i < 9; i++) M[i] = 0.0;
         std::memset(mask, 0, (size_t)m);
         *count = 0; *best_hyp = -1;
         return;
     }
     *best_hyp = key_hyp(key);
-    std::memcpy(H, H_all + 9 * (int64_t)*best_hyp, 9 * sizeof(double));
-    *count = count_inliers(H, src, dst, m, t2, mask);
-    const int formed = refit(src, dst, m, refine, H, mask, *count,
-                             [&](const double *Hn, uint8_t *trial) { return count_inliers(Hn, src, dst, m, t2, trial); }, rounds);
+    std::memcpy(M, M_all + 9 * (int64_t)*best_hyp, 9 * sizeof(double));
+    *count = count_inliers<Model>(M, src, dst, m, t2, mask);
+    const int formed = refit_rounds(m, refine, M, mask, *count, [&](const uint8_t *cur, double *Mn) { return Model::refit_round(src, dst, m, cur, Mn); },
+                                    [&](const double *Mn, uint8_t *trial) { return count_inliers<Model>(Mn, src, dst, m, t2, trial); }, rounds);
     if (n_rounds) *n_rounds = formed;
+}
+
+// the frame with the homography under this namespace's plain names: what the tests' shims call
+inline void all_hypotheses(const float *src, const float *dst, int64_t m, int32_t n_hyp, uint64_t seed, double *H_all, int32_t *idx_all,
+                           uint8_t *valid)
+{
+    all_hypotheses<Homography>(src, dst, m, n_hyp, seed, H_all, idx_all, valid);
+}
+inline int64_t count_inliers(const double H[9], const float *src, const float *dst, int64_t m, double t2, uint8_t *mask)
+{
+    return count_inliers<Homography>(H, src, dst, m, t2, mask);
+}
+inline void verify_host(const float *src, const float *dst, int64_t m, float threshold, int32_t n_hyp, uint64_t seed, int32_t refine, double *H_all,
+                        int32_t *counts, double H[9], uint8_t *mask, int64_t *count, int32_t *best_hyp, double *rounds, int32_t *n_rounds)
+{
+    verify_host<Homography>(src, dst, m, threshold, n_hyp, seed, refine, H_all, counts, H, mask, count, best_hyp, rounds, n_rounds);
 }
 
 }  // namespace verify_rules

@@ -7,6 +7,8 @@ after touching a kernel - a private segment > 0 means spills or a dynamically in
         identical    the same instruction text (block labels apart from the function's number in the file)
         reordered    equal VGPR, AGPR, scratch, spills and LDS and equal per-mnemonic instruction counts (SGPRs may differ)
         DIFFERENT    anything else, with what differs; also a kernel that only one file has
+        --rename OLD=NEW (repeatable, after the two files): the one kernel of OLD.s whose name contains OLD is paired with
+        the one of NEW.s whose name contains NEW, and listed as OLD=NEW
     --compare exits with status 1 when a kernel is DIFFERENT."""
 import collections
 import re
@@ -50,10 +52,14 @@ def table(path, pat):
         print("%-100s " % name[:100] + " ".join("%s %s" % (s, r[k]) for s, k in zip(SHORT, KEYS)))
 
 
-def compare(old_path, new_path):
+def compare(old_path, new_path, renames=()):
     old_txt, new_txt = open(old_path).read(), open(new_path).read()
     ro, rn = resources(old_txt), resources(new_txt)
     bo, bn = bodies(old_txt, ro), bodies(new_txt, rn)
+    for pair in renames:
+        for sub, r, b in zip(pair.split("="), (ro, rn), (bo, bn)):
+            name, = [k for k in r if sub in k and "=" not in k]                      # exactly one kernel, not yet paired
+            r[pair], b[pair] = r.pop(name), b.pop(name)
     bad = 0
     for name in sorted(set(ro) | set(rn)):
         if name not in ro or name not in rn:
@@ -75,6 +81,7 @@ def compare(old_path, new_path):
 
 
 if __name__ == "__main__":
-    if len(sys.argv) == 4 and sys.argv[1] == "--compare":
-        sys.exit(compare(sys.argv[2], sys.argv[3]))
+    if len(sys.argv) >= 4 and sys.argv[1] == "--compare":
+        assert len(sys.argv) % 2 == 0 and set(sys.argv[4::2]) <= {"--rename"}, __doc__
+        sys.exit(compare(sys.argv[2], sys.argv[3], sys.argv[5::2]))
     table(sys.argv[1], sys.argv[2] if len(sys.argv) > 2 else "")
