@@ -587,6 +587,40 @@ int dlco_desc_match_device(dlco_desc_ctx *ctx, const float *query_dev, int64_t l
 /* the whole matrix out[nq][nt] of the same distances, for small problems, tests and tools (nq * nt <= 2^28) */
 int dlco_desc_cross_sqdists(dlco_desc_ctx *ctx, const float *query_host, int64_t nq, const float *train_host, int64_t nt,
                             int32_t r, float *out_host);
+/* ---- Matching many pairs of images in one call.  Structure from motion, retrieval re-ranking and loop closure match one set of
+ * images pairwise; a call per pair forms every image's norms once per pair it appears in and launches kernels that cannot fill
+ * the device at a few thousand rows an image.  Here the set is ONE table [n_rows][r] holding the rows of image 0, then image 1,
+ * and so on: seg [n_img + 1] int64, host memory in every form, seg[0] = 0, non-decreasing, image s owns the rows
+ * [seg[s], seg[s + 1]) and n_rows = seg[n_img].  pairs [n_pairs][2] int32, host memory in every form, each (a, b) = (query
+ * image, train image); self pairs and repeated pairs are allowed.  csrc/match_batch.hpp states how a call is cut into launches.
+ *   Output: row0[p] = the running sum of the query images' row counts over the pairs in order (dlco_desc_match_pairs_rows);
+ * pair p owns the rows row0[p] .. row0[p + 1] - 1 of idx [.][2] / sqdist [.][2], and those rows are, byte for byte, what
+ * dlco_desc_match(query = image a, train = image b) returns: indices are rows of image b counted from its own first row, the
+ * second column is -1 / +inf when b has one row (-1 / INT32_MAX on the byte line).  No result depends on the other pairs of
+ * the batch, on their order, or on the run.
+ *   Empty images are normal: a pair whose query image is empty owns no rows; a pair whose train image is empty gets -1 / +inf
+ * (-1 / INT32_MAX) in both columns of every row.
+ *   DLCO_ERR_INVALID, before the handle is used and with no output touched: a null handle or pointer, n_img < 1, n_pairs < 1 or
+ * n_pairs >= 2^31, seg[0] != 0, a decreasing seg, an image of 2^31 rows or more, seg[n_img] < 1, a pair index outside
+ * [0, n_img), r outside 1 .. 1024; in the device forms ld < r, ld not a multiple of 4 floats (16 bytes on the byte line), a
+ * table that is not 16-byte aligned.
+ *   Out of scope: guided forms of the batch; a batched distance matrix; seg / pairs in device memory; a batched verify. ---- */
+/* row0 [n_pairs + 1]; needs neither a context nor a device */
+int dlco_desc_match_pairs_rows(const int64_t *seg, int32_t n_img, const int32_t *pairs, int64_t n_pairs, int64_t *row0);
+/* the table on the host, [n_rows][r] dense; idx_host / sqdist_host [row0[n_pairs]][2].  The table is held in device memory
+ * whole, padded to 16-byte rows, and so are the results (an allocation failure is DLCO_ERR_HIP) */
+int dlco_desc_match_pairs(dlco_desc_ctx *ctx, const float *table_host, const int64_t *seg, int32_t n_img,
+                          const int32_t *pairs, int64_t n_pairs, int32_t r, int32_t *idx_host, float *sqdist_host);
+/* the same on a table that already lives in HBM, as dlco_desc_match_device takes one (row pitch ld floats); idx_dev /
+ * sqdist_dev are device memory; queued on the context's stream, synchronised on return */
+int dlco_desc_match_pairs_device(dlco_desc_ctx *ctx, const float *table_dev, int64_t ld, const int64_t *seg, int32_t n_img,
+                                 const int32_t *pairs, int64_t n_pairs, int32_t r, int32_t *idx_dev, float *sqdist_dev);
+/* the plan only, nothing is launched: slices [n_pairs] = the slices of train that pair p is cut into in such a call on this
+ * context's device (the most of its row ranges when a pair of more than 2^20 query rows is cut), 0 for a pair that launches
+ * nothing (an empty image on either side); u8 = 0: the float line, 1: the byte line.  More than one: the pair goes through
+ * partials and a merge.  For tests and tools */
+int dlco_desc_match_pairs_slices(dlco_desc_ctx *ctx, const int64_t *seg, int32_t n_img, const int32_t *pairs, int64_t n_pairs,
+                                 int32_t u8, int32_t *slices);
 /* ---- Guided matching: the nearest two among the rows a homography admits.  Once a model exists (dlco_desc_verify_homography)
  * every query is matched again, but only against the train keypoints the model puts within `radius` pixels of it: the step
  * that recovers the correspondences the ratio test and the mutual check threw away in repeated structure, and the input of
@@ -705,6 +739,13 @@ int dlco_desc_match_u8_device(dlco_desc_ctx *ctx, const uint8_t *query_dev, int6
 /* the whole matrix out[nq][nt] of the same distances, for small problems, tests and tools (nq * nt <= 2^28) */
 int dlco_desc_cross_sqdists_u8(dlco_desc_ctx *ctx, const uint8_t *query_u8, int64_t nq, const uint8_t *train_u8, int64_t nt,
                                int32_t r, int32_t *out_host);
+/* dlco_desc_match_pairs on a table of bytes (see there for seg, pairs, the output layout, empty images and the checks): every
+ * pair's rows are what dlco_desc_match_u8 returns for it */
+int dlco_desc_match_pairs_u8(dlco_desc_ctx *ctx, const uint8_t *table_u8, const int64_t *seg, int32_t n_img,
+                             const int32_t *pairs, int64_t n_pairs, int32_t r, int32_t *idx_host, int32_t *sqdist_host);
+/* the same on a table in HBM, as dlco_desc_match_u8_device takes one (row pitch ld bytes, a multiple of 16) */
+int dlco_desc_match_pairs_u8_device(dlco_desc_ctx *ctx, const uint8_t *table_dev, int64_t ld, const int64_t *seg, int32_t n_img,
+                                    const int32_t *pairs, int64_t n_pairs, int32_t r, int32_t *idx_dev, int32_t *sqdist_dev);
 /* ---- Geometric verification: a homography between the two sides of a match list, so that the chain ends in a verified
  * result on this library alone.  A deterministic RANSAC by a rule of this library's own, csrc/verify_rules.hpp states it:
  * n_hyp hypotheses from four matches each (a counter-based sampler on `seed`), scored on the device by forward transfer
@@ -754,7 +795,8 @@ int  dlco_desc_verify_fundamental_hypotheses(dlco_desc_ctx *ctx, const float *sr
 /* HIP-event time of the kernels of the last compute / describe call (transform, pooling, projection, and the sampling
  * for the keypoint calls; extract_patches: the sampling alone); the pair_sqdists /
  * pair_stats calls add their distance kernel; after a match / cross_sqdists call, float or _u8, the time of its kernels
- * (norms, tile loop, merge of the slices, and for the guided forms the kernel that writes the records, launched once per side for the epipolar ones); the _u8 forms of describe add their quantising kernel; after a detect call the
+ * (norms, tile loop, merge of the slices, and for the guided forms the kernel that writes the records, launched once per side for the epipolar ones); after a match_pairs call, float or _u8, every kernel of the call (the norms of
+ * the whole table, the fill of the pairs with an empty train image, the tile loop and the merge of every launch); the _u8 forms of describe add their quantising kernel; after a detect call the
  * detector's kernels (the integral image when the call formed it, the octaves, the selection; detect_oriented adds the
  * orientation kernel); after an orient call the orientation kernel and the integral image when the call formed it; after a
  * verify call the verify kernels (hypotheses, scoring, selection, of either model; verify_homography and verify_fundamental add

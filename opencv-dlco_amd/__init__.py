@@ -89,7 +89,7 @@ def build(verbose=False):
 
 
 _lib = None
-f32p, i32p, u8p = C.POINTER(C.c_float), C.POINTER(C.c_int32), C.POINTER(C.c_uint8)
+f32p, i32p, u8p, i64p = C.POINTER(C.c_float), C.POINTER(C.c_int32), C.POINTER(C.c_uint8), C.POINTER(C.c_int64)
 
 
 def load():
@@ -214,6 +214,12 @@ def load():
     L.dlco_desc_match_guided_epipolar.argtypes = L.dlco_desc_match_guided.argtypes
     L.dlco_desc_match_guided_epipolar_device.argtypes = L.dlco_desc_match_guided_device.argtypes
     L.dlco_desc_cross_sqdists_guided_epipolar.argtypes = L.dlco_desc_cross_sqdists_guided.argtypes
+    L.dlco_desc_match_pairs_rows.argtypes = [i64p, C.c_int32, i32p, i64, i64p]
+    L.dlco_desc_match_pairs.argtypes = [vp, f32p, i64p, C.c_int32, i32p, i64, C.c_int32, i32p, f32p]
+    L.dlco_desc_match_pairs_device.argtypes = [vp, vp, i64, i64p, C.c_int32, i32p, i64, C.c_int32, vp, vp]
+    L.dlco_desc_match_pairs_u8.argtypes = [vp, u8p, i64p, C.c_int32, i32p, i64, C.c_int32, i32p, i32p]
+    L.dlco_desc_match_pairs_u8_device.argtypes = [vp, vp, i64, i64p, C.c_int32, i32p, i64, C.c_int32, vp, vp]
+    L.dlco_desc_match_pairs_slices.argtypes = [vp, i64p, C.c_int32, i32p, i64, C.c_int32, i32p]
     L.dlco_desc_last_kernel_ms.argtypes = [vp]
     L.dlco_desc_last_kernel_ms.restype = C.c_double
     L.dlco_pr_last_error.restype = C.c_char_p
@@ -265,6 +271,25 @@ def exported_symbols():
 
 def _p(a, t):
     return None if a is None else a.ctypes.data_as(t)
+
+
+def _seg_pairs(seg, pairs):
+    """seg [n_img + 1] int64 and pairs [n_pairs, 2] int32 as the match_pairs calls take them"""
+    s, q = np.ascontiguousarray(seg, np.int64), np.ascontiguousarray(pairs, np.int32)
+    assert s.ndim == 1 and s.size >= 2 and q.ndim == 2 and q.shape[1] == 2
+    return s, q
+
+
+def match_pairs_rows(seg, pairs):
+    """row0 [n_pairs + 1] int64 of a match_pairs call: pair p = (a, b) owns the output rows row0[p] .. row0[p + 1] - 1, as
+    many as image a has rows (seg [n_img + 1]: image s owns the rows seg[s] .. seg[s + 1] - 1 of the table).  No device."""
+    s, q = _seg_pairs(seg, pairs)
+    row0 = np.empty(q.shape[0] + 1, np.int64)
+    rc = load().dlco_desc_match_pairs_rows(_p(s, i64p), s.size - 1, _p(q, i32p), q.shape[0],
+                                           _p(row0, i64p))
+    if rc != OK:
+        raise DlcoError(rc, "match_pairs_rows: invalid seg or pairs")
+    return row0
 
 
 def _f32(a):
@@ -1187,6 +1212,50 @@ class DescContext:
         assert q.ndim == 2 and t.ndim == 2 and q.shape[1] == t.shape[1]
         out = np.empty((q.shape[0], t.shape[0]), np.int32)
         self._ck(self.L.dlco_desc_cross_sqdists_u8(self.h, _p(q, u8p), q.shape[0], _p(t, u8p), t.shape[0], q.shape[1], _p(out, i32p)))
+        return out
+
+    # ---- matching many pairs of images in one call (csrc/match_batch.hpp states the plan) ----
+    def _match_pairs(self, call, tables, pairs, dtype, ptr, dist):
+        tabs = [np.ascontiguousarray(t, dtype) for t in tables]
+        assert tabs and all(t.ndim == 2 and t.shape[1] == tabs[0].shape[1] for t in tabs)
+        seg = np.concatenate([[0], np.cumsum([t.shape[0] for t in tabs])]).astype(np.int64)
+        seg, q = _seg_pairs(seg, pairs)
+        table = np.ascontiguousarray(np.concatenate(tabs, axis=0))
+        row0 = match_pairs_rows(seg, q)
+        idx, d = np.empty((row0[-1], 2), np.int32), np.empty((row0[-1], 2), dist)
+        self._ck(call(self.h, _p(table, ptr), _p(seg, i64p), seg.size - 1, _p(q, i32p), q.shape[0], table.shape[1], _p(idx, i32p),
+                      _p(d, C.POINTER(C.c_float if dist == np.float32 else C.c_int32))))
+        return [(idx[row0[p]:row0[p + 1]], d[row0[p]:row0[p + 1]]) for p in range(q.shape[0])]
+
+    def match_pairs(self, tables, pairs):
+        """Many pairs of images in one call: tables is a list of [n_s, r] arrays (an image may have no rows), pairs [n_pairs, 2]
+        of (query image, train image).  Returns a list of (idx [n_a, 2] int32, sqdist [n_a, 2] float32), one per pair, each
+        byte for byte what match(tables[a], tables[b]) returns; an empty train image gives -1 / +inf in both columns."""
+        return self._match_pairs(self.L.dlco_desc_match_pairs, tables, pairs, np.float32, f32p, np.float32)
+
+    def match_pairs_u8(self, tables, pairs):
+        """match_pairs on byte tables: every pair is what match_u8 returns for it; an empty train image gives -1 / INT32_MAX."""
+        return self._match_pairs(self.L.dlco_desc_match_pairs_u8, tables, pairs, np.uint8, u8p, np.int32)
+
+    def match_pairs_device(self, table_ptr, seg, pairs, r, idx_ptr, d_ptr, ld=None):
+        """match_pairs on one table in device memory (row pitch ld floats, a multiple of 4, default r) whose segments seg
+        [n_img + 1] are the images; results [match_pairs_rows(seg, pairs)[-1], 2] to device memory."""
+        s, q = _seg_pairs(seg, pairs)
+        self._ck(self.L.dlco_desc_match_pairs_device(self.h, C.c_void_p(table_ptr), ld or r, _p(s, i64p), s.size - 1, _p(q, i32p), q.shape[0], r,
+                                                     C.c_void_p(idx_ptr), C.c_void_p(d_ptr)))
+
+    def match_pairs_u8_device(self, table_ptr, seg, pairs, r, idx_ptr, d_ptr, ld=None):
+        """match_pairs_u8 on one table in device memory (row pitch ld bytes, a multiple of 16)."""
+        s, q = _seg_pairs(seg, pairs)
+        self._ck(self.L.dlco_desc_match_pairs_u8_device(self.h, C.c_void_p(table_ptr), ld or r, _p(s, i64p), s.size - 1, _p(q, i32p), q.shape[0],
+                                                        r, C.c_void_p(idx_ptr), C.c_void_p(d_ptr)))
+
+    def match_pairs_slices(self, seg, pairs, u8=False):
+        """The plan only: slices [n_pairs] int32 of train that each pair is cut into in such a call on this context's device
+        (0: the pair launches nothing); more than one means partials and a merge.  Nothing is launched."""
+        s, q = _seg_pairs(seg, pairs)
+        out = np.empty(q.shape[0], np.int32)
+        self._ck(self.L.dlco_desc_match_pairs_slices(self.h, _p(s, i64p), s.size - 1, _p(q, i32p), q.shape[0], 1 if u8 else 0, _p(out, i32p)))
         return out
 
     def last_kernel_ms(self):

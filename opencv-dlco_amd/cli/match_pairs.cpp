@@ -1,0 +1,188 @@
+// match-pairs — nearest-neighbour matching of many pairs of descriptor tables in one library call, over libdlco.so.
+//
+//     match-pairs -pairs pairs_file -out dst [-u8] [-ratio f] [-cross] [-device n] desc_file_0 desc_file_1 ...
+//
+// Every desc_file holds the dataset "Descriptor" [n, r] f32 that `describe` writes (the r must agree; n may be 0: an image
+// without keypoints), pairs_file the dataset "Pairs" [P, 2] i32 of (query file, train file), numbers in the file list.
+// The tables are concatenated and matched by ONE dlco_desc_match_pairs call.  Writes
+//     "Pairs" [P,2] i32 and "RowOffsets" [P+1] i64: pair p owns the rows RowOffsets[p] .. RowOffsets[p+1] - 1 of
+//     "Nearest" [.,2] i32 and "NearestSqDist" [.,2] f32   the library's answer for the queries of every pair, which is what
+//                                                          `match` writes for the pair's two files
+//     "MatchOffsets" [P+1] i64: pair p owns the rows MatchOffsets[p] .. MatchOffsets[p+1] - 1 of
+//     "Matches" [M,2] i32 = (query, train) as rows of the pair's own two tables, and "MatchSqDist" [M] f32   the filtered lists
+// The filters are `match`'s host rules (match_rules.hpp), applied per pair: -ratio f (0 < f <= 1) is Lowe's test, -cross the
+// mutual check, for which the reversed pairs are appended to the same batch instead of making second calls.
+//   With -u8 the files hold "DescriptorU8" [n, r] u8 instead, the call is dlco_desc_match_pairs_u8 and the distances are
+// i32.  Files that carry a quantiser ("QuantScale", "QuantOffset") must all carry the same one, bit for bit.
+// A path that does not end in .h5/.hdf5 is a directory of .npy files with the same dataset names (dlco_io.hpp).
+#include "../../include/dlco.h"
+#include "dlco_io.hpp"
+#include "match_rules.hpp"
+#include "quant_io.hpp"
+
+#include <chrono>
+#include <cstdlib>
+#include <cstring>
+#include <iostream>
+
+using std::cout;
+using std::endl;
+
+namespace {
+template <typename T> struct Line;
+template <> struct Line<float> {
+    using Dist = float;
+    static constexpr const char *dataset = "Descriptor";
+    static constexpr const char *tag = "";
+    static int call(dlco_desc_ctx *c, const float *t, const int64_t *seg, int32_t n_img, const int32_t *pairs, int64_t n_pairs, int32_t r,
+                    int32_t *idx, float *d) { return dlco_desc_match_pairs(c, t, seg, n_img, pairs, n_pairs, r, idx, d); }
+};
+template <> struct Line<uint8_t> {
+    using Dist = int32_t;
+    static constexpr const char *dataset = "DescriptorU8";
+    static constexpr const char *tag = " (u8)";
+    static int call(dlco_desc_ctx *c, const uint8_t *t, const int64_t *seg, int32_t n_img, const int32_t *pairs, int64_t n_pairs, int32_t r,
+                    int32_t *idx, int32_t *d) { return dlco_desc_match_pairs_u8(c, t, seg, n_img, pairs, n_pairs, r, idx, d); }
+};
+
+template <typename T>
+void run(const char *pairs_file, const std::vector<const char *> &files, const char *out, bool use_ratio, float ratio, bool cross, int device,
+         dlco_desc_ctx *&ctx)
+{
+    using Dist = typename Line<T>::Dist;
+    const size_t n_img = files.size();
+    std::vector<T> table;
+    std::vector<int64_t> seg(n_img + 1, 0);
+    size_t r = 0;
+    for (size_t f = 0; f < n_img; f++) {
+        std::vector<size_t> shape;
+        std::vector<T> rows;
+        dlco_io::read_dataset<T>(files[f], Line<T>::dataset, shape, rows);
+        if (shape.size() != 2 || shape[1] < 1) throw std::runtime_error(std::string(files[f]) + ": " + Line<T>::dataset + " must be an [n, r] table");
+        if (f == 0) r = shape[1];
+        if (shape[1] != r)
+            throw std::runtime_error("the descriptors differ in size: " + std::to_string(r) + " (" + files[0] + ") against " + std::to_string(shape[1]) +
+                                     " (" + files[f] + ")");
+        if constexpr (std::is_same<T, float>::value) {
+            for (float v : rows)
+                if (!(v == v) || v > 3.0e38f || v < -3.0e38f) throw std::runtime_error(std::string(files[f]) + ": Descriptor contains NaN");
+        }
+        seg[f + 1] = seg[f] + (int64_t)shape[0];
+        table.insert(table.end(), rows.begin(), rows.end());
+    }
+    if (seg[n_img] < 1) throw std::runtime_error("every descriptor table is empty");
+    if (std::is_same<T, uint8_t>::value) {              // match's rule across all files: the quantisers that are there agree
+        float s0 = 0.f;
+        std::vector<float> o0;
+        const char *first = nullptr;
+        for (size_t f = 0; f < n_img; f++) {
+            float s = 0.f;
+            std::vector<float> o;
+            if (!quant_io::present(files[f], r, s, o)) continue;
+            if (!first) { first = files[f]; s0 = s; o0 = o; continue; }
+            if (!quant_io::same_bits(s0, o0, s, o))
+                throw std::runtime_error(std::string(first) + " and " + files[f] +
+                                         " were quantised differently (QuantScale / QuantOffset differ): their distances mean nothing");
+        }
+    }
+    std::vector<size_t> pshape;
+    std::vector<int32_t> pairs;
+    dlco_io::read_dataset<int32_t>(pairs_file, "Pairs", pshape, pairs);
+    if (pshape.size() != 2 || pshape[0] < 1 || pshape[1] != 2) throw std::runtime_error(std::string(pairs_file) + ": Pairs must be a non-empty [P, 2] table");
+    const size_t P = pshape[0];
+    for (size_t i = 0; i < 2 * P; i++)
+        if (pairs[i] < 0 || (size_t)pairs[i] >= n_img)
+            throw std::runtime_error(std::string(pairs_file) + ": pair " + std::to_string(i / 2) + " names file " + std::to_string(pairs[i]) + " of " +
+                                     std::to_string(n_img));
+    printf("Tables: %zu, %lld x %zu%s\n", n_img, (long long)seg[n_img], r, Line<T>::tag);
+    printf("Pairs: %zu\n", P);
+
+    // -cross: the reversed pairs ride in the same batch, pair P + p is pair p swapped
+    std::vector<int32_t> batch(pairs);
+    if (cross)
+        for (size_t p = 0; p < P; p++) { batch.push_back(pairs[2 * p + 1]); batch.push_back(pairs[2 * p]); }
+    const size_t B = batch.size() / 2;
+    std::vector<int64_t> row0(B + 1);
+    if (dlco_desc_match_pairs_rows(seg.data(), (int32_t)n_img, batch.data(), (int64_t)B, row0.data()) != DLCO_OK)
+        throw std::runtime_error("the segment table or the pairs are invalid");
+
+    if (dlco_desc_create(&ctx, 1.4f, 8, 1, device) != DLCO_OK) throw std::runtime_error(dlco_desc_last_error(nullptr));
+    const auto t0 = std::chrono::steady_clock::now();
+    std::vector<int32_t> nearest((size_t)row0[B] * 2);
+    std::vector<Dist> sqdist((size_t)row0[B] * 2);
+    if (Line<T>::call(ctx, table.data(), seg.data(), (int32_t)n_img, batch.data(), (int64_t)B, (int32_t)r, nearest.data(), sqdist.data()) != DLCO_OK)
+        throw std::runtime_error(dlco_desc_last_error(ctx));
+    std::vector<int64_t> moff(P + 1, 0);
+    std::vector<int32_t> matches, mp;
+    std::vector<Dist> mdist, md;
+    for (size_t p = 0; p < P; p++) {
+        const int64_t nq = row0[p + 1] - row0[p];
+        match_rules::select(nq, nearest.data() + 2 * row0[p], sqdist.data() + 2 * row0[p], use_ratio, ratio,
+                            cross ? nearest.data() + 2 * row0[P + p] : nullptr, mp, md);
+        matches.insert(matches.end(), mp.begin(), mp.end());
+        mdist.insert(mdist.end(), md.begin(), md.end());
+        moff[p + 1] = (int64_t)mdist.size();
+    }
+    {
+        dlco_io::Writer wr(out);
+        wr.write<int32_t>("Pairs", pairs.data(), P, 2);
+        wr.write_vec<int64_t>("RowOffsets", row0.data(), P + 1);
+        wr.write<int32_t>("Nearest", nearest.data(), (size_t)row0[P], 2);
+        wr.write<Dist>("NearestSqDist", sqdist.data(), (size_t)row0[P], 2);
+        wr.write_vec<int64_t>("MatchOffsets", moff.data(), P + 1);
+        wr.write<int32_t>("Matches", matches.data(), mdist.size(), 2);
+        wr.write_vec<Dist>("MatchSqDist", mdist.data(), mdist.size());
+    }
+    const double sec = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
+    printf("Matches: %zu / %lld\n", mdist.size(), (long long)row0[P]);
+    printf("Kernels: %.6f ms\n", dlco_desc_last_kernel_ms(ctx));
+    printf("Total: %.09f sec\n", sec);
+}
+}  // namespace
+
+int main(int argc, char **argv)
+{
+    int device = 0;
+    bool help = false, cross = false, use_ratio = false, u8 = false;
+    float ratio = 1.0f;
+    const char *pairs_file = nullptr, *out = nullptr;
+    std::vector<const char *> files;
+    for (int i = 1; i < argc; i++) {
+        if (argv[i][0] == '-') {
+            const bool has_val = i + 1 < argc;
+            if (std::strcmp(argv[i], "-help") == 0) { help = true; continue; }
+            if (std::strcmp(argv[i], "-pairs") == 0 && has_val) { pairs_file = argv[++i]; continue; }
+            if (std::strcmp(argv[i], "-out") == 0 && has_val) { out = argv[++i]; continue; }
+            if (std::strcmp(argv[i], "-ratio") == 0 && has_val) { ratio = (float)atof(argv[++i]); use_ratio = true; continue; }
+            if (std::strcmp(argv[i], "-cross") == 0) { cross = true; continue; }
+            if (std::strcmp(argv[i], "-u8") == 0) { u8 = true; continue; }
+            if (std::strcmp(argv[i], "-device") == 0 && has_val) { device = atoi(argv[++i]); continue; }
+            cout << "ERROR: Invalid " << argv[i] << " option." << endl;
+            help = true;
+        } else {
+            files.push_back(argv[i]);
+        }
+    }
+    if (!pairs_file || !out || files.empty()) help = true;
+    if (use_ratio && !(ratio > 0.0f && ratio <= 1.0f)) {
+        cout << "ERROR: -ratio must be in (0, 1]." << endl;
+        help = true;
+    }
+    if (help) {
+        cout << endl;
+        cout << "Usage: match-pairs -pairs pairs_file -out dst_h5_filename [-u8] [-ratio f] [-cross] [-device n] desc_file_0 desc_file_1 ..." << endl;
+        cout << endl;
+        return 1;
+    }
+    dlco_desc_ctx *ctx = nullptr;
+    try {
+        if (u8) run<uint8_t>(pairs_file, files, out, use_ratio, ratio, cross, device, ctx);
+        else run<float>(pairs_file, files, out, use_ratio, ratio, cross, device, ctx);
+        dlco_desc_destroy(ctx);
+    } catch (const std::exception &e) {
+        if (ctx) dlco_desc_destroy(ctx);
+        std::fprintf(stderr, "match-pairs: %s\n", e.what());
+        return 2;
+    }
+    return 0;
+}

@@ -38,7 +38,8 @@ constexpr int kChunk = 2048;            // patches per launch pair: 256 MB of Pa
 // the matrix, part [slices][nq] partial (d1, j1, d2, j2) of 16 bytes each, the norms of the queries and of train; for the
 // guided forms of the float line the uploaded (x, y) of both tables and rec [n][4], the records of the side the homography
 // applies to (guided_rules.hpp): a launch's queries or all of train; for the epipolar guided forms (guided_epipolar_rules.hpp)
-// rec holds train's records and qrec a launch's queries'
+// rec holds train's records and qrec a launch's queries'; for the batch forms (dlco_desc_match_pairs*) plan, the uploaded
+// entries of every launch and behind them the fill list (match_batch.hpp), train the one table and tnorm / qnorm its norms
 template <typename Elem, typename Dist, typename Norm>
 struct MatchBufs {
     DevBuf<Elem> query, train;
@@ -47,6 +48,7 @@ struct MatchBufs {
     DevBuf<Norm> qnorm, tnorm;
     DevBuf<float> qxy, txy;
     DevBuf<double> rec, qrec;
+    DevBuf<uint8_t> plan;
 };
 
 struct dlco_desc_ctx {
@@ -252,6 +254,14 @@ struct FloatLine {
     static void train_norms(const Elem *x, long ld, long n, int r, Norm *norm, hipStream_t s) { match_norms(x, ld, n, r, norm, s); }
     static constexpr bool guided = true;                   // the tile loop has the guided epilogue
     static constexpr auto top2 = match_top2;
+    // the batch forms: the norms of a whole table serve both sides; the bits of "no candidate" (+inf)
+    static constexpr bool two_norms = false;
+    static constexpr int32_t none = 0x7f800000;
+    static void top2_batch(const Elem *table, long ld, int r, const Norm *, const Norm *tnorm, const match_batch::Entry *ent, int n_ent, long wgs,
+                           long merge_wgs, int32_t *idx, Dist *sqdist, void *part, hipStream_t s)
+    {
+        match_top2_batch(table, ld, r, tnorm, ent, n_ent, wgs, merge_wgs, idx, sqdist, part, s);
+    }
 };
 struct ByteLine {
     using Elem = uint8_t; using Dist = int32_t; using Norm = int32_t;
@@ -267,6 +277,10 @@ struct ByteLine {
     {
         match_u8_top2(query, ldq, nq, train, ldt, nt, r, qnorm, tnorm, tiles_per_slice, idx, sqdist, part, out, s);
     }
+    // the batch forms: a whole table's norms in both signs, a launch each; the bits of "no candidate" (INT32_MAX)
+    static constexpr bool two_norms = true;
+    static constexpr int32_t none = INT32_MAX;
+    static constexpr auto top2_batch = match_u8_top2_batch;
 };
 
 // The geometry of a guided call (guided_rules.hpp), an optional argument of the float line's host path: the (x, y) of the
@@ -406,6 +420,87 @@ void match_host(dlco_desc_ctx *c, const typename L::Elem *query_host, int64_t nq
         sync(c);
     }
     c->last_ms = ms;
+}
+
+// ---- the batch forms (dlco_desc_match_pairs*): many (query image, train image) pairs over one table whose segments are the
+// images, by the plan of match_batch.hpp.  The same lines, buffers and norm kernels as above; what differs is that the
+// norms of the table are formed once per call and that a launch carries the workgroups of many pairs. ------------------------
+bool match_pairs_args_ok(const int64_t *seg, int32_t n_img, const int32_t *pairs, int64_t n_pairs)
+{
+    if (!seg || !pairs || n_img < 1 || n_pairs < 1 || n_pairs >= ((int64_t)1 << 31) || seg[0] != 0) return false;
+    for (int32_t i = 0; i < n_img; i++)
+        if (seg[i + 1] < seg[i] || seg[i + 1] - seg[i] >= ((int64_t)1 << 31)) return false;
+    if (seg[n_img] < 1) return false;
+    for (int64_t p = 0; p < 2 * n_pairs; p++)
+        if (pairs[p] < 0 || pairs[p] >= n_img) return false;
+    return true;
+}
+
+// the table in device memory in, device results out: the norms of every row once, the fill rows, then the launches of the
+// plan one after another (they share the partial buffer); returns the kernels' time
+template <typename L>
+double match_pairs_on_device(dlco_desc_ctx *c, const typename L::Elem *table, long ld, const int64_t *seg, int32_t n_img,
+                             const match_batch::Plan &pl, int r, int32_t *idx, typename L::Dist *sqdist)
+{
+    auto &b = L::bufs(c);
+    const int64_t n_rows = seg[n_img];
+    const size_t ent_bytes = pl.entries.size() * sizeof(match_batch::Entry), fill_bytes = pl.fills.size() * sizeof(match_batch::Fill);
+    b.tnorm.alloc((size_t)n_rows);
+    if (L::two_norms) b.qnorm.alloc((size_t)n_rows);
+    b.plan.alloc(ent_bytes + fill_bytes);
+    if (pl.max_parts > 0) b.part.alloc((size_t)pl.max_parts * 4);
+    if (ent_bytes) DLCO_HIP(hipMemcpyAsync(b.plan.p, pl.entries.data(), ent_bytes, hipMemcpyHostToDevice, c->stream));
+    if (fill_bytes) DLCO_HIP(hipMemcpyAsync(b.plan.p + ent_bytes, pl.fills.data(), fill_bytes, hipMemcpyHostToDevice, c->stream));
+    const auto *ent = reinterpret_cast<const match_batch::Entry *>(b.plan.p);
+    const auto *fill = reinterpret_cast<const match_batch::Fill *>(b.plan.p + ent_bytes);
+    EventPair ev;
+    return timed_ms(c, ev, [&] {
+        L::train_norms(table, ld, n_rows, r, b.tnorm.p, c->stream);
+        if (L::two_norms) L::query_norms(table, ld, n_rows, r, b.qnorm.p, c->stream);
+        match_fill(fill, (int)pl.fills.size(), pl.fill_rows, L::none, idx, sqdist, c->stream);
+        for (const match_batch::Launch &la : pl.launches)
+            L::top2_batch(table, ld, r, b.qnorm.p, b.tnorm.p, ent + la.e0, (int)la.n, la.wgs, la.merge_wgs, idx, sqdist, b.part.p, c->stream);
+    });
+}
+
+template <typename L>
+void match_pairs_device(dlco_desc_ctx *c, const typename L::Elem *table_dev, long ld, const int64_t *seg, int32_t n_img, const int32_t *pairs,
+                        int64_t n_pairs, int r, int32_t *idx_dev, typename L::Dist *sqdist_dev)
+{
+    DLCO_HIP(hipSetDevice(c->device));
+    const match_batch::Plan pl = match_batch::plan(L::shape, seg, pairs, n_pairs, c->n_cu);
+    c->last_ms = match_pairs_on_device<L>(c, table_dev, ld, seg, n_img, pl, r, idx_dev, sqdist_dev);
+}
+
+// the host form: the table goes up once, padded to the 16-byte row pitch, the outputs of every pair come down once
+template <typename L>
+void match_pairs_host(dlco_desc_ctx *c, const typename L::Elem *table_host, const int64_t *seg, int32_t n_img, const int32_t *pairs,
+                      int64_t n_pairs, int r, int32_t *idx_host, typename L::Dist *sqdist_host)
+{
+    using Elem = typename L::Elem;
+    using Dist = typename L::Dist;
+    auto &b = L::bufs(c);
+    DLCO_HIP(hipSetDevice(c->device));
+    constexpr long per = kRowPitchBytes / sizeof(Elem);
+    const long ld = (r + per - 1) / per * per;
+    const int64_t n_rows = seg[n_img];
+    const match_batch::Plan pl = match_batch::plan(L::shape, seg, pairs, n_pairs, c->n_cu);
+    const int64_t out_rows = pl.row0[(size_t)n_pairs];
+    try {
+        b.train.alloc((size_t)n_rows * ld);
+        b.idx.alloc((size_t)out_rows * 2);
+        b.sqdist.alloc((size_t)out_rows * 2);
+    } catch (const Error &e) {
+        throw Error(DLCO_ERR_HIP, std::string(L::name) + "_pairs: the table and the results do not fit in device memory: " + e.what());
+    }
+    DLCO_HIP(hipMemcpy2DAsync(b.train.p, (size_t)ld * sizeof(Elem), table_host, (size_t)r * sizeof(Elem), (size_t)r * sizeof(Elem), (size_t)n_rows,
+                              hipMemcpyHostToDevice, c->stream));
+    c->last_ms = match_pairs_on_device<L>(c, b.train.p, ld, seg, n_img, pl, r, b.idx.p, b.sqdist.p);
+    if (out_rows > 0) {
+        DLCO_HIP(hipMemcpyAsync(idx_host, b.idx.p, (size_t)out_rows * 2 * sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
+        DLCO_HIP(hipMemcpyAsync(sqdist_host, b.sqdist.p, (size_t)out_rows * 2 * sizeof(Dist), hipMemcpyDeviceToHost, c->stream));
+    }
+    sync(c);
 }
 
 // ---- verification: a homography (verify_rules.hpp) or a fundamental matrix (epipolar_rules.hpp) between the two sides of
@@ -1162,6 +1257,41 @@ int dlco_desc_cross_sqdists(dlco_desc_ctx *c, const float *query_host, int64_t n
     return guarded(c, [&] { match_host<FloatLine>(c, query_host, nq, train_host, nt, r, nullptr, nullptr, out_host); });
 }
 
+// ---- matching many pairs of images in one call (match_batch.hpp); the float entry points and the two that take no line ----
+int dlco_desc_match_pairs_rows(const int64_t *seg, int32_t n_img, const int32_t *pairs, int64_t n_pairs, int64_t *row0)
+{
+    if (!row0 || !match_pairs_args_ok(seg, n_img, pairs, n_pairs)) return DLCO_ERR_INVALID;
+    match_batch::row_offsets(seg, pairs, n_pairs, row0);
+    return DLCO_OK;
+}
+
+int dlco_desc_match_pairs(dlco_desc_ctx *c, const float *table_host, const int64_t *seg, int32_t n_img, const int32_t *pairs, int64_t n_pairs,
+                          int32_t r, int32_t *idx_host, float *sqdist_host)
+{
+    if (!c || !table_host || !idx_host || !sqdist_host || r < 1 || r > 1024 || !match_pairs_args_ok(seg, n_img, pairs, n_pairs))
+        return DLCO_ERR_INVALID;
+    return guarded(c, [&] { match_pairs_host<FloatLine>(c, table_host, seg, n_img, pairs, n_pairs, r, idx_host, sqdist_host); });
+}
+
+int dlco_desc_match_pairs_device(dlco_desc_ctx *c, const float *table_dev, int64_t ld, const int64_t *seg, int32_t n_img, const int32_t *pairs,
+                                 int64_t n_pairs, int32_t r, int32_t *idx_dev, float *sqdist_dev)
+{
+    if (!c || !table_dev || !idx_dev || !sqdist_dev || r < 1 || r > 1024 || !match_pairs_args_ok(seg, n_img, pairs, n_pairs))
+        return DLCO_ERR_INVALID;
+    if (ld < r || ld % 4 != 0 || (uintptr_t)table_dev % 16 != 0) return DLCO_ERR_INVALID;                  // 16-byte rows
+    return guarded(c, [&] { match_pairs_device<FloatLine>(c, table_dev, (long)ld, seg, n_img, pairs, n_pairs, r, idx_dev, sqdist_dev); });
+}
+
+int dlco_desc_match_pairs_slices(dlco_desc_ctx *c, const int64_t *seg, int32_t n_img, const int32_t *pairs, int64_t n_pairs, int32_t u8,
+                                 int32_t *slices)
+{
+    if (!c || !slices || (u8 != 0 && u8 != 1) || !match_pairs_args_ok(seg, n_img, pairs, n_pairs)) return DLCO_ERR_INVALID;
+    return guarded(c, [&] {
+        const match_batch::Plan pl = match_batch::plan(u8 ? ByteLine::shape : FloatLine::shape, seg, pairs, n_pairs, c->n_cu);
+        std::copy(pl.slices.begin(), pl.slices.end(), slices);
+    });
+}
+
 // ---- guided matching: the nearest two among the rows a homography admits (guided_rules.hpp; the guided epilogue of the tile
 // loop in kernels_match.hip).  The float line's host path with a Geometry; the byte line has no guided form. ----------------
 namespace {
@@ -1366,6 +1496,23 @@ int dlco_desc_match_u8_device(dlco_desc_ctx *c, const uint8_t *query_dev, int64_
     if (ldq < r || ldt < r || ldq % 16 != 0 || ldt % 16 != 0) return DLCO_ERR_INVALID;
     if (((uintptr_t)query_dev | (uintptr_t)train_dev) % 16 != 0) return DLCO_ERR_INVALID;          // 16-byte pieces
     return guarded(c, [&] { match_device<ByteLine>(c, query_dev, (long)ldq, nq, train_dev, (long)ldt, nt, r, idx_dev, sqdist_dev); });
+}
+
+int dlco_desc_match_pairs_u8(dlco_desc_ctx *c, const uint8_t *table_u8, const int64_t *seg, int32_t n_img, const int32_t *pairs, int64_t n_pairs,
+                             int32_t r, int32_t *idx_host, int32_t *sqdist_host)
+{
+    if (!c || !table_u8 || !idx_host || !sqdist_host || r < 1 || r > 1024 || !match_pairs_args_ok(seg, n_img, pairs, n_pairs))
+        return DLCO_ERR_INVALID;
+    return guarded(c, [&] { match_pairs_host<ByteLine>(c, table_u8, seg, n_img, pairs, n_pairs, r, idx_host, sqdist_host); });
+}
+
+int dlco_desc_match_pairs_u8_device(dlco_desc_ctx *c, const uint8_t *table_dev, int64_t ld, const int64_t *seg, int32_t n_img,
+                                    const int32_t *pairs, int64_t n_pairs, int32_t r, int32_t *idx_dev, int32_t *sqdist_dev)
+{
+    if (!c || !table_dev || !idx_dev || !sqdist_dev || r < 1 || r > 1024 || !match_pairs_args_ok(seg, n_img, pairs, n_pairs))
+        return DLCO_ERR_INVALID;
+    if (ld < r || ld % 16 != 0 || (uintptr_t)table_dev % 16 != 0) return DLCO_ERR_INVALID;                 // 16-byte pieces
+    return guarded(c, [&] { match_pairs_device<ByteLine>(c, table_dev, (long)ld, seg, n_img, pairs, n_pairs, r, idx_dev, sqdist_dev); });
 }
 
 int dlco_desc_cross_sqdists_u8(dlco_desc_ctx *c, const uint8_t *query_u8, int64_t nq, const uint8_t *train_u8, int64_t nt, int32_t r,

@@ -3,6 +3,7 @@
 #pragma once
 
 #include "../../include/dlco.h"
+#include "match_batch.hpp"
 #include "match_slices.hpp"
 
 #include <hip/hip_runtime.h>
@@ -572,6 +573,13 @@ void match_records(const float *xy, long ld, long n, const double H[9], double t
 void match_epi_records(const float *xy, long ld, long n, const double F[9], int dst_side, double *rec, hipStream_t s);
 void match_top2(const float *query, long ldq, int nq, const float *train, long ldt, int nt, int r, const double *qnorm, const double *tnorm,
                 int tiles_per_slice, int32_t *idx, float *sqdist, void *part, float *out, const MatchGuide *guide, hipStream_t s);
+// the batch forms (match_batch.hpp states the plan): one launch of the plan over the one table [.][ld] and the norms of all its
+// rows, ent [n_ent] in device memory; and the rows of the pairs with an empty train image, `none` the bits of "no candidate"
+void match_top2_batch(const float *table, long ld, int r, const double *norm, const match_batch::Entry *ent, int n_ent, long wgs, long merge_wgs,
+                      int32_t *idx, float *sqdist, void *part, hipStream_t s);
+void match_u8_top2_batch(const uint8_t *table, long ld, int r, const int32_t *qnorm, const int32_t *tneg, const match_batch::Entry *ent, int n_ent,
+                         long wgs, long merge_wgs, int32_t *idx, int32_t *sqdist, void *part, hipStream_t s);
+void match_fill(const match_batch::Fill *fill, int n_fill, long rows, int32_t none, int32_t *idx, void *sqdist, hipStream_t s);
 // byte descriptors (kernels_match_u8.hip; the quantiser is quant_rules.hpp): float rows to bytes, and the match of byte tables
 void desc_quantize_rows(const float *Y, long ldy, int n, int r, float scale, const float *offset, uint8_t *out, long ldo, hipStream_t s);
 void match_u8_norms(const uint8_t *x, long ld, long n, int r, bool negate, int32_t *norm, hipStream_t s);

@@ -27,6 +27,9 @@
 //                         pair of column blocks: beside the epilogue, with every accumulator live, they cost scratch.
 //   match_merge_kernel    the top two of a query over the S slices of train, under the same key (the slicing rule:
 //                         match_slices.hpp)
+//   match_top2_kernel<.., BATCH>, match_merge_batch_kernel, match_fill_kernel   the batch forms (dlco_desc_match_pairs, the plan:
+//                         match_batch.hpp): many (query image, train image) pairs over one segmented table in one 1-D
+//                         launch; a workgroup finds its pair in the uploaded plan and runs the plain form's tile loop
 //
 // The key is a total order and the slices hold disjoint train rows, so the result does not depend on the grouping.
 // An entry's accumulation is one chain of MFMAs over k in an order fixed by r: it depends neither on where the query
@@ -38,6 +41,7 @@
 #include "dlco_internal.hpp"
 #include "guided_rules.hpp"
 #include "guided_epipolar_rules.hpp"
+#include "match_batch.hpp"
 #include "match_slices.hpp"
 
 namespace dlco {
@@ -83,12 +87,46 @@ __device__ __forceinline__ Top2 merge2(const Top2 a, const Top2 b)
     return o;
 }
 
-template <bool STORE, bool MULTI, int GUIDED>
+// The entry of the plan that workgroup wg of a batched launch belongs to: the last one whose first workgroup (`first`
+// picks wg0 or mwg0) is not above wg.  wg is the same for the whole workgroup, so the search is scalar loads and branches.
+template <typename First>
+__device__ __forceinline__ int batch_entry_of(const match_batch::Entry *__restrict__ ent, int n_ent, int wg, First first)
+{
+    int lo = 0, hi = n_ent;
+    while (hi - lo > 1) {
+        const int mid = (lo + hi) >> 1;
+        if (first(ent[mid]) <= wg) lo = mid; else hi = mid;
+    }
+    return lo;
+}
+
+// BATCH (dlco_desc_match_pairs; STORE = 0, GUIDED = 0): a 1-D grid over the workgroups of every entry of a launch of the plan
+// (match_batch.hpp).  query is the one table [.][ldq] whose segments are the images and qnorm the norms of all its rows;
+// the workgroup finds its entry and takes from it what the plain form takes from its arguments and its grid: the query
+// image's and the train image's first row (tables, norms), nq, nt, tiles_per_slice, the first output row, the offset of the
+// entry's partials (part stays null when the entry has one slice), its query block and its slice.  Tiles are counted from
+// the slice's first row, which need not be tile-aligned in the table; the rows at and beyond jend belong to the next image
+// (or lie beyond the table) and are never read: the loads clamp to jbeg.  The loop below is the plain form's.
+template <bool STORE, bool MULTI, int GUIDED, bool BATCH = false>
 __global__ __launch_bounds__(MTH) void match_top2_kernel(const float *__restrict__ query, long ldq, int nq, const float *__restrict__ train, long ldt,
                                                          int nt, int r, const double *__restrict__ qnorm, const double *__restrict__ tnorm,
                                                          int tiles_per_slice, int32_t *__restrict__ idx, float *__restrict__ sqdist,
-                                                         i32x4 *__restrict__ part, float *__restrict__ out, const MatchGuide g)
+                                                         i32x4 *__restrict__ part, float *__restrict__ out, const MatchGuide g,
+                                                         const match_batch::Entry *__restrict__ ent, int n_ent)
 {
+    unsigned qblk = blockIdx.x, slice = blockIdx.y;
+    if constexpr (BATCH) {
+        const int wg = (int)blockIdx.x;
+        const match_batch::Entry e = ent[batch_entry_of(ent, n_ent, wg, [](const match_batch::Entry &x) { return x.wg0; })];
+        const unsigned w = (unsigned)(wg - e.wg0);
+        slice = w / (unsigned)e.qblocks;
+        qblk = w - slice * (unsigned)e.qblocks;
+        train = query + e.t0 * ldq; ldt = ldq; tnorm = qnorm + e.t0;
+        query += e.q0 * ldq; qnorm += e.q0;
+        nq = e.nq; nt = e.nt; tiles_per_slice = e.tiles_per_slice;
+        idx += 2 * e.out0; sqdist += 2 * e.out0;
+        part = e.slices > 1 ? part + e.part0 : nullptr;
+    }
     constexpr int CW = GUIDED >= 2 ? 4 : 2;                // doubles of geometry a train row brings: (x, y) or a record
     constexpr int QW = GUIDED == 1 || GUIDED >= 3 ? 4 : 2; // and a query
     __shared__ double Bs[TN * MP];                         // the staged tile, widened to double once, when it is stored
@@ -97,9 +135,9 @@ __global__ __launch_bounds__(MTH) void match_top2_kernel(const float *__restrict
     __shared__ __attribute__((aligned(16))) double Qg[GUIDED ? MQ * QW : 1];            // and the workgroup's queries': written once, before the loop
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int li = lane & 15, lg = lane >> 4;
-    const int q0 = blockIdx.x * MQ + wave * 16;
+    const int q0 = qblk * MQ + wave * 16;
     const bool wave_on = q0 < nq;                          // uniform over the wave
-    const int jbeg = (int)((long)blockIdx.y * tiles_per_slice * TN);    // this slice of train: [jbeg, jend), never empty (jbeg < nt)
+    const int jbeg = (int)((long)slice * tiles_per_slice * TN);    // this slice of train: [jbeg, jend), never empty (jbeg < nt)
     const int jend = (int)min((long)nt, (long)jbeg + (long)tiles_per_slice * TN);
     const int ntile = (jend - jbeg + TN - 1) / TN;
     const int nch = MULTI ? (r + KC - 1) / KC : 1;
@@ -202,7 +240,7 @@ __global__ __launch_bounds__(MTH) void match_top2_kernel(const float *__restrict
     // registers over the loop would put the kernel into scratch
     if constexpr (GUIDED != 0) {
         if (tid < MQ) {
-            const long row = (long)blockIdx.x * MQ + tid;
+            const long row = (long)qblk * MQ + tid;
             const long rs = row < nq ? row : 0;
             if constexpr (GUIDED == 1 || GUIDED >= 3) {
                 const double *qr = GUIDED == 1 ? g.rec : g.qrec;
@@ -385,7 +423,7 @@ __global__ __launch_bounds__(MTH) void match_top2_kernel(const float *__restrict
         const int row = q0 + lg + 4 * rr;
         if (li == 0 && row < nq) {
             if (part) {
-                part[(long)blockIdx.y * nq + row] = i32x4{__float_as_int(me.d1), me.j1, __float_as_int(me.d2), me.j2};
+                part[(long)slice * nq + row] = i32x4{__float_as_int(me.d1), me.j1, __float_as_int(me.d2), me.j2};
             } else {
                 idx[2 * (long)row] = me.j1; idx[2 * (long)row + 1] = me.j2;
                 sqdist[2 * (long)row] = me.d1; sqdist[2 * (long)row + 1] = me.d2;
@@ -407,6 +445,43 @@ __global__ __launch_bounds__(256) void match_merge_kernel(const i32x4 *__restric
     }
     idx[2 * (long)row] = me.j1; idx[2 * (long)row + 1] = me.j2;
     sqdist[2 * (long)row] = me.d1; sqdist[2 * (long)row + 1] = me.d2;
+}
+
+// the merge of a batched launch: 256 rows of an entry with more than one slice per workgroup, numbered from its mwg0
+__global__ __launch_bounds__(256) void match_merge_batch_kernel(const i32x4 *__restrict__ part, const match_batch::Entry *__restrict__ ent,
+                                                                int n_ent, int32_t *__restrict__ idx, float *__restrict__ sqdist)
+{
+    const int wg = (int)blockIdx.x;
+    const match_batch::Entry e = ent[batch_entry_of(ent, n_ent, wg, [](const match_batch::Entry &x) { return x.mwg0; })];
+    const int row = (wg - e.mwg0) * 256 + threadIdx.x;
+    if (row >= e.nq) return;
+    const i32x4 *pp = part + e.part0;
+    const i32x4 p0 = pp[row];
+    Top2 me{__int_as_float(p0[0]), p0[1], __int_as_float(p0[2]), p0[3]};
+    for (int s = 1; s < e.slices; s++) {
+        const i32x4 p = pp[(long)s * e.nq + row];
+        me = merge2(me, Top2{__int_as_float(p[0]), p[1], __int_as_float(p[2]), p[3]});
+    }
+    const long o = 2 * (e.out0 + row);
+    idx[o] = me.j1; idx[o + 1] = me.j2;
+    sqdist[o] = me.d1; sqdist[o + 1] = me.d2;
+}
+
+// the rows of the pairs of a batch whose train image is empty: -1 and the line's "no candidate" distance (the bits of +inf
+// or INT32_MAX) in both columns; one lane per row, which finds its fill by its number among all fill rows
+__global__ __launch_bounds__(256) void match_fill_kernel(const match_batch::Fill *__restrict__ fill, int n_fill, long rows, int32_t none,
+                                                         int32_t *__restrict__ idx, int32_t *__restrict__ sqdist)
+{
+    const long i = (long)blockIdx.x * 256 + threadIdx.x;
+    if (i >= rows) return;
+    int lo = 0, hi = n_fill;
+    while (hi - lo > 1) {
+        const int mid = (lo + hi) >> 1;
+        if (fill[mid].first <= i) lo = mid; else hi = mid;
+    }
+    const long o = 2 * (fill[lo].out0 + (i - fill[lo].first));
+    idx[o] = -1; idx[o + 1] = -1;
+    sqdist[o] = none; sqdist[o + 1] = none;
 }
 
 // the records of n rows (x, y) = xy[i * ld], xy[i * ld + 1] under H: rec [n][4] = (X, Y, W, T), one lane per row
@@ -498,7 +573,7 @@ void match_top2(const float *query, long ldq, int nq, const float *train, long l
     const MatchGuide g = guide ? *guide : MatchGuide{};
 #define DLCO_MATCH_LAUNCH(ST, MU, GU)                                                                                                 \
     hipLaunchKernelGGL((match_top2_kernel<ST, MU, GU>), grid, dim3(MTH), 0, s, query, ldq, nq, train, ldt, nt, r, qnorm, tnorm,       \
-                       tiles_per_slice, idx, sqdist, pp, out, g)
+                       tiles_per_slice, idx, sqdist, pp, out, g, nullptr, 0)
 #define DLCO_MATCH_FORM(GU)                                                                                                           \
     do {                                                                                                                              \
         if (out) { if (multi) DLCO_MATCH_LAUNCH(true, true, GU); else DLCO_MATCH_LAUNCH(true, false, GU); }                           \
@@ -516,6 +591,35 @@ void match_top2(const float *query, long ldq, int nq, const float *train, long l
         hipLaunchKernelGGL(match_merge_kernel, dim3((unsigned)((nq + 255) / 256)), dim3(256), 0, s, pp, slices, nq, idx, sqdist);
         DLCO_HIP(hipGetLastError());
     }
+}
+
+// One launch of a batched match (match_batch.hpp): table [.][ld] with its norms, the launch's n_ent entries in device memory,
+// wgs workgroups of the tile loop, merge_wgs of the merge (0: every entry has one slice); idx / sqdist are the call's.
+void match_top2_batch(const float *table, long ld, int r, const double *norm, const match_batch::Entry *ent, int n_ent, long wgs, long merge_wgs,
+                      int32_t *idx, float *sqdist, void *part, hipStream_t s)
+{
+    if (n_ent <= 0 || wgs <= 0) return;
+    i32x4 *pp = static_cast<i32x4 *>(part);
+    const dim3 grid((unsigned)wgs);
+#define DLCO_MATCH_BATCH_LAUNCH(MU)                                                                                                   \
+    hipLaunchKernelGGL((match_top2_kernel<false, MU, 0, true>), grid, dim3(MTH), 0, s, table, ld, 0, nullptr, 0L, 0, r, norm, nullptr, 0,   \
+                       idx, sqdist, pp, nullptr, MatchGuide{}, ent, n_ent)
+    if (r > KC) DLCO_MATCH_BATCH_LAUNCH(true); else DLCO_MATCH_BATCH_LAUNCH(false);
+#undef DLCO_MATCH_BATCH_LAUNCH
+    DLCO_HIP(hipGetLastError());
+    if (merge_wgs > 0) {
+        hipLaunchKernelGGL(match_merge_batch_kernel, dim3((unsigned)merge_wgs), dim3(256), 0, s, pp, ent, n_ent, idx, sqdist);
+        DLCO_HIP(hipGetLastError());
+    }
+}
+
+// rows of pairs with an empty train image, either line: `none` is the bit pattern of the distance that means "no candidate"
+void match_fill(const match_batch::Fill *fill, int n_fill, long rows, int32_t none, int32_t *idx, void *sqdist, hipStream_t s)
+{
+    if (n_fill <= 0 || rows <= 0) return;
+    hipLaunchKernelGGL(match_fill_kernel, dim3((unsigned)((rows + 255) / 256)), dim3(256), 0, s, fill, n_fill, rows, none, idx,
+                       static_cast<int32_t *>(sqdist));
+    DLCO_HIP(hipGetLastError());
 }
 
 }  // namespace dlco

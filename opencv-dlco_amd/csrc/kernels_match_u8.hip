@@ -8,6 +8,9 @@
 //                           then either the running top two per query, or (STORE) the matrix itself: one tile loop, two
 //                           epilogues, so the matrix and the top two cannot disagree
 //   match_u8_merge_kernel   the top two of a query over the S slices of train (the slicing rule: match_slices.hpp)
+//   match_u8_kernel<.., BATCH>, match_u8_merge_batch_kernel   the batch forms (dlco_desc_match_pairs_u8, the plan: match_batch.hpp):
+//                           many (query image, train image) pairs over one segmented table in one 1-D launch; a workgroup
+//                           finds its pair in the uploaded plan and runs the plain form's tile loop
 //
 // Everything is an integer: differences do not see the shift by 128, |a|^2 <= 1024 * 128^2 = 2^24 and every partial stays
 // below 2^26 in magnitude, so d is the exact sum_k (q_ik - t_jk)^2 <= 1024 * 255^2 and nothing depends on an order of
@@ -22,6 +25,7 @@
 // ceil(r / 16) * 16 <= ld, the bytes at and beyond r are replaced by zeros after the flip.  Every load is unconditional
 // and in bounds (a row or piece beyond the edge reads a valid one and is replaced by zeros), stores are masked.
 #include "dlco_internal.hpp"
+#include "match_batch.hpp"
 #include "match_slices.hpp"
 #include "quant_rules.hpp"
 
@@ -84,19 +88,53 @@ __device__ __forceinline__ i32x4 piece(i32x4 v, int k, int r, bool ok)
     return o;
 }
 
-template <bool STORE, bool MULTI>
+// The entry of the plan that workgroup wg of a batched launch belongs to: the last one whose first workgroup (`first`
+// picks wg0 or mwg0) is not above wg.  wg is the same for the whole workgroup, so the search is scalar loads and branches.
+template <typename First>
+__device__ __forceinline__ int batch_entry_of(const match_batch::Entry *__restrict__ ent, int n_ent, int wg, First first)
+{
+    int lo = 0, hi = n_ent;
+    while (hi - lo > 1) {
+        const int mid = (lo + hi) >> 1;
+        if (first(ent[mid]) <= wg) lo = mid; else hi = mid;
+    }
+    return lo;
+}
+
+// BATCH (dlco_desc_match_pairs_u8; STORE = 0): a 1-D grid over the workgroups of every entry of a launch of the plan
+// (match_batch.hpp).  query is the one table [.][ldq] whose segments are the images, qnorm and tneg the norms of all its rows
+// in both signs; the workgroup finds its entry and takes from it what the plain form takes from its arguments and its grid:
+// the query image's and the train image's first row (tables, norms), nq, nt, tiles_per_slice, the first output row, the
+// offset of the entry's partials (part stays null when the entry has one slice), its query block and its slice.  Tiles are
+// counted from the slice's first row, which need not be tile-aligned in the table; the rows at and beyond jend belong to
+// the next image (or lie beyond the table) and are never read: the loads clamp to jbeg.  The loop below is the plain form's.
+template <bool STORE, bool MULTI, bool BATCH = false>
 __global__ __launch_bounds__(UTH) void match_u8_kernel(const uint8_t *__restrict__ query, long ldq, int nq, const uint8_t *__restrict__ train,
                                                        long ldt, int nt, int r, const int32_t *__restrict__ qnorm,
                                                        const int32_t *__restrict__ tneg, int tiles_per_slice, int32_t *__restrict__ idx,
-                                                       int32_t *__restrict__ sqdist, i32x4 *__restrict__ part, int32_t *__restrict__ out)
+                                                       int32_t *__restrict__ sqdist, i32x4 *__restrict__ part, int32_t *__restrict__ out,
+                                                       const match_batch::Entry *__restrict__ ent, int n_ent)
 {
+    unsigned qblk = blockIdx.x, slice = blockIdx.y;
+    if constexpr (BATCH) {
+        const int wg = (int)blockIdx.x;
+        const match_batch::Entry e = ent[batch_entry_of(ent, n_ent, wg, [](const match_batch::Entry &x) { return x.wg0; })];
+        const unsigned w = (unsigned)(wg - e.wg0);
+        slice = w / (unsigned)e.qblocks;
+        qblk = w - slice * (unsigned)e.qblocks;
+        train = query + e.t0 * ldq; ldt = ldq; tneg += e.t0;
+        query += e.q0 * ldq; qnorm += e.q0;
+        nq = e.nq; nt = e.nt; tiles_per_slice = e.tiles_per_slice;
+        idx += 2 * e.out0; sqdist += 2 * e.out0;
+        part = e.slices > 1 ? part + e.part0 : nullptr;
+    }
     __shared__ __attribute__((aligned(16))) uint8_t Bs[2][UT * UP];            // the staged tile, flipped and masked when stored
     __shared__ __attribute__((aligned(16))) int32_t Tn[2][UT];                 // -|a_t|^2 of its rows, kEmpty beyond the slice
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int li = lane & 15, lg = lane >> 4;
-    const int q0 = blockIdx.x * UQ + wave * UWQ;
+    const int q0 = qblk * UQ + wave * UWQ;
     const bool wave_on = q0 < nq;                          // uniform over the wave
-    const int jbeg = (int)((long)blockIdx.y * tiles_per_slice * UT);    // this slice of train: [jbeg, jend), never empty (jbeg < nt)
+    const int jbeg = (int)((long)slice * tiles_per_slice * UT);    // this slice of train: [jbeg, jend), never empty (jbeg < nt)
     const int jend = (int)min((long)nt, (long)jbeg + (long)tiles_per_slice * UT);
     const int ntile = (jend - jbeg + UT - 1) / UT;
     const int nch = MULTI ? (r + UK - 1) / UK : 1;
@@ -232,7 +270,7 @@ __global__ __launch_bounds__(UTH) void match_u8_kernel(const uint8_t *__restrict
         const int q = q0 + 16 * qb + li;
         if (lg == 0 && q < nq) {
             if (part) {
-                part[(long)blockIdx.y * nq + q] = i32x4{me.k1, me.j1, me.k2, me.j2};
+                part[(long)slice * nq + q] = i32x4{me.k1, me.j1, me.k2, me.j2};
             } else {
                 const int n = qnorm[q];
                 idx[2 * (long)q] = me.j1; idx[2 * (long)q + 1] = me.j2;
@@ -241,6 +279,29 @@ __global__ __launch_bounds__(UTH) void match_u8_kernel(const uint8_t *__restrict
             }
         }
     }
+}
+
+// the merge of a batched launch: 256 rows of an entry with more than one slice per workgroup, numbered from its mwg0
+__global__ __launch_bounds__(256) void match_u8_merge_batch_kernel(const i32x4 *__restrict__ part, const match_batch::Entry *__restrict__ ent,
+                                                                   int n_ent, const int32_t *__restrict__ qnorm, int32_t *__restrict__ idx,
+                                                                   int32_t *__restrict__ sqdist)
+{
+    const int wg = (int)blockIdx.x;
+    const match_batch::Entry e = ent[batch_entry_of(ent, n_ent, wg, [](const match_batch::Entry &x) { return x.mwg0; })];
+    const int row = (wg - e.mwg0) * 256 + threadIdx.x;
+    if (row >= e.nq) return;
+    const i32x4 *pp = part + e.part0;
+    const i32x4 p0 = pp[row];
+    Top2 me{p0[0], p0[1], p0[2], p0[3]};
+    for (int s = 1; s < e.slices; s++) {
+        const i32x4 p = pp[(long)s * e.nq + row];
+        me = merge2(me, Top2{p[0], p[1], p[2], p[3]});
+    }
+    const int n = qnorm[e.q0 + row];
+    const long o = 2 * (e.out0 + row);
+    idx[o] = me.j1; idx[o + 1] = me.j2;
+    sqdist[o] = me.j1 < 0 ? INT_MAX : n - me.k1;
+    sqdist[o + 1] = me.j2 < 0 ? INT_MAX : n - me.k2;
 }
 
 __global__ __launch_bounds__(256) void match_u8_merge_kernel(const i32x4 *__restrict__ part, int slices, int nq, const int32_t *__restrict__ qnorm,
@@ -324,13 +385,33 @@ void match_u8_top2(const uint8_t *query, long ldq, int nq, const uint8_t *train,
     const bool multi = r > UK;
 #define DLCO_MATCH_U8_LAUNCH(ST, MU)                                                                                                  \
     hipLaunchKernelGGL((match_u8_kernel<ST, MU>), grid, dim3(UTH), 0, s, query, ldq, nq, train, ldt, nt, r, qnorm, tneg, tiles_per_slice, \
-                       idx, sqdist, pp, out)
+                       idx, sqdist, pp, out, nullptr, 0)
     if (out) { if (multi) DLCO_MATCH_U8_LAUNCH(true, true); else DLCO_MATCH_U8_LAUNCH(true, false); }
     else     { if (multi) DLCO_MATCH_U8_LAUNCH(false, true); else DLCO_MATCH_U8_LAUNCH(false, false); }
 #undef DLCO_MATCH_U8_LAUNCH
     DLCO_HIP(hipGetLastError());
     if (pp) {
         hipLaunchKernelGGL(match_u8_merge_kernel, dim3((unsigned)((nq + 255) / 256)), dim3(256), 0, s, pp, slices, nq, qnorm, idx, sqdist);
+        DLCO_HIP(hipGetLastError());
+    }
+}
+
+// One launch of a batched match (match_batch.hpp): table [.][ld], qnorm = |a|^2 and tneg = -|a|^2 of all its rows, the launch's
+// n_ent entries in device memory, wgs workgroups of the tile loop, merge_wgs of the merge (0: every entry has one slice).
+void match_u8_top2_batch(const uint8_t *table, long ld, int r, const int32_t *qnorm, const int32_t *tneg, const match_batch::Entry *ent, int n_ent,
+                         long wgs, long merge_wgs, int32_t *idx, int32_t *sqdist, void *part, hipStream_t s)
+{
+    if (n_ent <= 0 || wgs <= 0) return;
+    i32x4 *pp = static_cast<i32x4 *>(part);
+    const dim3 grid((unsigned)wgs);
+#define DLCO_MATCH_U8_BATCH_LAUNCH(MU)                                                                                                \
+    hipLaunchKernelGGL((match_u8_kernel<false, MU, true>), grid, dim3(UTH), 0, s, table, ld, 0, nullptr, 0L, 0, r, qnorm, tneg, 0, idx, sqdist, \
+                       pp, nullptr, ent, n_ent)
+    if (r > UK) DLCO_MATCH_U8_BATCH_LAUNCH(true); else DLCO_MATCH_U8_BATCH_LAUNCH(false);
+#undef DLCO_MATCH_U8_BATCH_LAUNCH
+    DLCO_HIP(hipGetLastError());
+    if (merge_wgs > 0) {
+        hipLaunchKernelGGL(match_u8_merge_batch_kernel, dim3((unsigned)merge_wgs), dim3(256), 0, s, pp, ent, n_ent, qnorm, idx, sqdist);
         DLCO_HIP(hipGetLastError());
     }
 }

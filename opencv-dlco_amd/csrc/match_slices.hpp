@@ -35,13 +35,19 @@ constexpr int UQ = kU8.qblock, UT = kU8.tile;
 // enough slices for per_cu workgroups per CU keep that loss near a tenth, as long as a slice keeps four tiles (a
 // workgroup's start - its A fragments, the first tile's latency - is paid per slice).  Returns the tiles per slice; the
 // slice count is slices() of that.
-inline int tiles_per_slice(const Shape &s, long nq, long nt, int n_cu)
+// tiles_per_slice_of takes the query blocks counted by the caller: those of one call (tiles_per_slice), or of every pair of
+// a batched launch (match_batch.hpp), whose workgroups fill the CUs together.
+inline int tiles_per_slice_of(const Shape &s, long qblocks, long nt, int n_cu)
 {
-    const long qblocks = (nq + s.qblock - 1) / s.qblock, tiles = (nt + s.tile - 1) / s.tile;
+    const long tiles = (nt + s.tile - 1) / s.tile;
     const long fill = std::min(tiles, ((long)s.fill_cu * n_cu + qblocks - 1) / qblocks);
     const long rounds = std::min(tiles / 4, ((long)s.per_cu * n_cu + qblocks - 1) / qblocks);
     const long want = std::max(1L, std::max(fill, rounds));
     return (int)((tiles + want - 1) / want);
+}
+inline int tiles_per_slice(const Shape &s, long nq, long nt, int n_cu)
+{
+    return tiles_per_slice_of(s, (nq + s.qblock - 1) / s.qblock, nt, n_cu);
 }
 inline int slices(const Shape &s, long nt, int tiles_per_slice)
 {

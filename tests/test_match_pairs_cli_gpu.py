@@ -1,0 +1,70 @@
+"""The tool match-pairs on a GPU: four small descriptor files, with and without -ratio 0.8 -cross, float and -u8.  Every pair's
+Nearest, NearestSqDist, Matches and MatchSqDist are byte-equal to a run of the tool match on that pair's two files with the
+same flags."""
+import os
+import subprocess
+
+import numpy as np
+import pytest
+
+from test_match_gpu import make_tables
+from test_match_u8_gpu import byte_tables
+
+pytestmark = pytest.mark.gpu
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+CLI = os.path.join(ROOT, "opencv-dlco_amd", "cli")
+PAIRS = [(0, 1), (1, 0), (2, 3), (3, 3), (0, 2), (0, 1)]      # a self pair and a repeated pair among them
+R = 20
+
+
+@pytest.fixture(scope="module")
+def files(tmp_path_factory):
+    subprocess.check_call(["make", "-s", "-C", CLI])
+    root = tmp_path_factory.mktemp("match_pairs_cli")
+    out = {}
+    for u8 in (False, True):
+        names = []
+        for k, n in enumerate((76, 300, 17, 129)):           # views of the 300-row table and the table itself: neighbours and ties exist
+            Q, T = byte_tables(n, 300, R, 4) if u8 else make_tables(n, 300, R)
+            d = root / ("%s%d" % ("u" if u8 else "f", k))
+            d.mkdir()
+            np.save(d / ("DescriptorU8.npy" if u8 else "Descriptor.npy"), T if n == 300 else Q)
+            names.append(str(d))
+        out[u8] = names
+    p = root / "pairs"
+    p.mkdir()
+    np.save(p / "Pairs.npy", np.array(PAIRS, np.int32))
+    out["pairs"] = str(p)
+    return out
+
+
+@pytest.mark.parametrize("u8", [False, True])
+@pytest.mark.parametrize("flags", [[], ["-ratio", "0.8", "-cross"]])
+def test_match_pairs_writes_what_match_writes_for_every_pair(files, tmp_path, u8, flags):
+    flags = flags + (["-u8"] if u8 else [])
+    out = tmp_path / "batch"
+    q = subprocess.run([os.path.join(CLI, "match-pairs"), "-pairs", files["pairs"], "-out", str(out)] + flags + files[u8], capture_output=True, text=True,
+                       timeout=600)
+    assert q.returncode == 0, q.stderr
+    load = lambda d, name: np.load(os.path.join(str(d), name + ".npy"))
+    pairs, row0, moff = load(out, "Pairs"), load(out, "RowOffsets"), load(out, "MatchOffsets")
+    near, near_d, mat, mat_d = (load(out, n) for n in ("Nearest", "NearestSqDist", "Matches", "MatchSqDist"))
+    assert pairs.dtype == np.int32 and np.array_equal(pairs, PAIRS) and row0.dtype == np.int64 and moff.dtype == np.int64
+    assert row0.shape == moff.shape == (len(PAIRS) + 1,) and row0[0] == 0 and moff[0] == 0
+    assert near.shape == (row0[-1], 2) and near_d.shape == (row0[-1], 2) and mat.shape == (moff[-1], 2) and mat_d.shape == (moff[-1],)
+    dist = np.int32 if u8 else np.float32
+    assert near.dtype == np.int32 and mat.dtype == np.int32 and near_d.dtype == dist and mat_d.dtype == dist
+    total = 0
+    for p, (a, b) in enumerate(PAIRS):
+        one = tmp_path / ("pair%d" % p)
+        s = subprocess.run([os.path.join(CLI, "match"), files[u8][a], files[u8][b], "-out", str(one)] + flags, capture_output=True, text=True, timeout=600)
+        assert s.returncode == 0, s.stderr
+        for got, name in ((near[row0[p]:row0[p + 1]], "Nearest"), (near_d[row0[p]:row0[p + 1]], "NearestSqDist"),
+                          (mat[moff[p]:moff[p + 1]], "Matches"), (mat_d[moff[p]:moff[p + 1]], "MatchSqDist")):
+            want = load(one, name)
+            assert got.dtype == want.dtype and got.shape == want.shape and got.tobytes() == want.tobytes(), (p, a, b, name)
+        total += moff[p + 1] - moff[p]
+    assert "Pairs: %d" % len(PAIRS) in q.stdout and "Matches: %d / %d" % (total, row0[-1]) in q.stdout and "Total: " in q.stdout
+    if flags[:1] == ["-ratio"]:
+        assert 0 < total < row0[-1]                         # the filters did filter

@@ -18,7 +18,16 @@ e' = (3 S, 0.4 S, 1), S the side of the square, divided by its largest magnitude
 dlco_desc_match_guided_epipolar_device is timed for both f_side beside the plain call and the homography-guided call of the
 same run, one warm-up each, then three rounds that alternate the five calls.  The line shows the five times with their rounds,
 the epipolar calls' ratio to the plain call and to the homography-guided call of the same side, and how many queries found two
-admitted rows."""
+admitted rows.
+
+With --pairs (and --u8 for the byte line) the batched call is measured instead: dlco_desc_match_pairs_device on a set of images
+in one table in HBM against a loop of dlco_desc_match_device calls over the same pairs on the same sub-tables, the thing the
+batch replaces.  The sets: a, 9 images of 2048 rows, all 72 ordered pairs (also at r = 64); b, 33 x 512 rows, all 1056; c,
+4 x 8192 rows, all 12; d, 20 images of 500 .. 8000 rows (seeded), all 380; r = 128 unless said.  One warm-up of both, then
+three rounds that alternate the batch and the loop in one process.  For each the kernel time (last_kernel_ms, summed over the
+loop's calls) and the wall time from sync to sync; the figure is the best of the three rounds, the loop's spread its largest
+minus its smallest round.  The line adds the floor 2 sum(nq nt) r / 78.6 TFLOP/s (5.0 POP/s with --u8), the batch's share of
+it, and whether the two routes returned the same bytes."""
 import importlib, os, sys
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch
@@ -35,6 +44,9 @@ if GUIDED:
 EPI = "--guided-epipolar" in sys.argv
 if EPI:
     sys.argv.remove("--guided-epipolar")
+PAIRS = "--pairs" in sys.argv
+if PAIRS:
+    sys.argv.remove("--pairs")
 SHAPES = [(2048, 2048, 64), (8192, 8192, 64), (8192, 8192, 128), (100000, 100000, 128)]
 if len(sys.argv) > 1:
     SHAPES = [tuple(int(v) for v in a.split(",")) for a in sys.argv[1:]]
@@ -53,6 +65,73 @@ def torch_route(Q, T, chunk=8192):
         d.append(v.float())
     return torch.cat(idx), torch.cat(d)
 
+
+def pairs_bench():
+    import time
+    import numpy as np
+    rng = np.random.default_rng(4)
+    sets = [("a", [2048] * 9, 128), ("a", [2048] * 9, 64), ("b", [512] * 33, 128), ("c", [8192] * 4, 128),
+            ("d", [int(v) for v in rng.integers(500, 8001, 20)], 128)]
+    ctx = dlco.DescContext()
+    gen = torch.Generator(device="cuda:0").manual_seed(0)
+    peak, unit = (PEAK_I8, "int8") if U8 else (PEAK, "f64")
+    for name, sizes, r in sets:
+        n_img = len(sizes)
+        seg = np.concatenate([[0], np.cumsum(sizes)]).astype(np.int64)
+        pairs = np.array([(a, b) for a in range(n_img) for b in range(n_img) if a != b], np.int32)
+        row0 = dlco.match_pairs_rows(seg, pairs)
+        X = torch.empty((int(seg[-1]), r), dtype=torch.float32, device="cuda:0").normal_(0, 0.25, generator=gen)
+        if U8:
+            lo = X.min(0).values
+            X = ((X - lo) * (255.0 / float((X.max(0).values - lo).max()))).round().clamp(0, 255).to(torch.uint8)
+        esz, ddt = X.element_size(), (torch.int32 if U8 else torch.float32)
+        out = [(torch.empty((int(row0[-1]), 2), dtype=torch.int32, device="cuda:0"), torch.empty((int(row0[-1]), 2), dtype=ddt, device="cuda:0"))
+               for _ in range(2)]
+        torch.cuda.synchronize()
+        one = ctx.match_u8_device if U8 else ctx.match_device
+        many = ctx.match_pairs_u8_device if U8 else ctx.match_pairs_device
+
+        def batch():
+            many(X.data_ptr(), seg, pairs, r, out[0][0].data_ptr(), out[0][1].data_ptr(), ld=r)
+            return ctx.last_kernel_ms()
+
+        def loop():
+            ms = 0.0
+            for p, (a, b) in enumerate(pairs):
+                one(X.data_ptr() + int(seg[a]) * r * esz, sizes[a], X.data_ptr() + int(seg[b]) * r * esz, sizes[b], r,
+                    out[1][0].data_ptr() + int(row0[p]) * 8, out[1][1].data_ptr() + int(row0[p]) * 8)
+                ms += ctx.last_kernel_ms()
+            return ms
+
+        def timed(f):
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            ms = f()
+            torch.cuda.synchronize()
+            return ms, 1e3 * (time.perf_counter() - t0)
+
+        batch()
+        loop()
+        same = bool(torch.equal(out[0][0], out[1][0]) and torch.equal(out[0][1].view(torch.int32), out[1][1].view(torch.int32)))
+        rounds = [(timed(batch), timed(loop)) for _ in range(3)]
+        bk, bw = min(x[0][0] for x in rounds), min(x[0][1] for x in rounds)
+        lk, lw = [x[1][0] for x in rounds], [x[1][1] for x in rounds]
+        floor = 1e3 * 2.0 * float(sum(sizes[a] * sizes[b] for a, b in pairs)) * r / peak
+        sl = ctx.match_pairs_slices(seg, pairs, u8=U8)
+        fmt = lambda m: " ".join("%.3f" % v for v in m)
+        print(f"match_pairs{'_u8' if U8 else ''} set {name}: {n_img} images of {min(sizes)}..{max(sizes)} rows, {len(pairs)} pairs, r {r}, slices "
+              f"{int(sl.min())}..{int(sl.max())}: batch kernels {bk:.3f} ms (rounds {fmt(x[0][0] for x in rounds)}), wall {bw:.3f} ms (rounds "
+              f"{fmt(x[0][1] for x in rounds)}); loop kernels {min(lk):.3f} ms (rounds {fmt(lk)}, spread {max(lk) - min(lk):.3f}), wall {min(lw):.3f} ms "
+              f"(rounds {fmt(lw)}, spread {max(lw) - min(lw):.3f}); loop / batch kernels {min(lk) / bk:.2f}, wall {min(lw) / bw:.2f}; {unit} MFMA floor "
+              f"{floor:.3f} ms, share of the floor: batch {floor / bk:.3f}, loop {floor / min(lk):.3f}; same bytes: {same}; batch not slower within the "
+              f"loop's spread: kernels {bk <= min(lk) + (max(lk) - min(lk))}, wall {bw <= min(lw) + (max(lw) - min(lw))}", flush=True)
+        del X, out
+    ctx.close()
+
+
+if PAIRS:
+    pairs_bench()
+    sys.exit(0)
 
 ctx = dlco.DescContext()
 gen = torch.Generator(device="cuda:0").manual_seed(0)
