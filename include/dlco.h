@@ -604,7 +604,8 @@ int dlco_desc_cross_sqdists(dlco_desc_ctx *ctx, const float *query_host, int64_t
  * n_pairs >= 2^31, seg[0] != 0, a decreasing seg, an image of 2^31 rows or more, seg[n_img] < 1, a pair index outside
  * [0, n_img), r outside 1 .. 1024; in the device forms ld < r, ld not a multiple of 4 floats (16 bytes on the byte line), a
  * table that is not 16-byte aligned.
- *   Out of scope: guided forms of the batch; a batched distance matrix; seg / pairs in device memory; a batched verify. ---- */
+ *   Out of scope: guided forms of the batch; a batched distance matrix; seg / pairs in device memory.
+ *   In scope since: a batched verify, dlco_desc_verify_pairs_* below. ---- */
 /* row0 [n_pairs + 1]; needs neither a context nor a device */
 int dlco_desc_match_pairs_rows(const int64_t *seg, int32_t n_img, const int32_t *pairs, int64_t n_pairs, int64_t *row0);
 /* the table on the host, [n_rows][r] dense; idx_host / sqdist_host [row0[n_pairs]][2].  The table is held in device memory
@@ -792,6 +793,41 @@ int  dlco_desc_verify_fundamental(dlco_desc_ctx *ctx, const float *src_xy_host, 
 /* every hypothesis of that call and its inlier count, F_all [n_hyp][9] (all zero: invalid) and count [n_hyp] */
 int  dlco_desc_verify_fundamental_hypotheses(dlco_desc_ctx *ctx, const float *src_xy_host, const float *dst_xy_host, int64_t m,
                                              float threshold, int32_t n_hyp, uint64_t seed, double *F_all_host, int32_t *count_host);
+/* ---- Verifying many pairs in one call.  Every caller of dlco_desc_match_pairs verifies each matched pair next, and a call per
+ * pair is launch-bound: three launches of a few dozen workgroups and several stream synchronisations for a few thousand
+ * matches.  Here the match lists of all pairs are ONE list: src_xy, dst_xy [M][2] float, host memory; moff [n_pairs + 1] int64,
+ * host memory, moff[0] = 0, non-decreasing, pair p owns the matches [moff[p], moff[p + 1]) and M = moff[n_pairs] (match-pairs'
+ * MatchOffsets).  csrc/verify_batch.hpp states how a call is cut into launches; a launch carries the workgroups of many pairs,
+ * and the refit rounds of all pairs still refining share one mask launch per round.
+ *   Output: M_out [n_pairs][9], inlier_host [M] (may be NULL), n_inliers [n_pairs], best_hyp [n_pairs] (may be NULL).  Pair p's
+ * matrix, its slice of the mask, its count and its best hypothesis are, byte for byte, what dlco_desc_verify_homography
+ * (dlco_desc_verify_fundamental) returns for src_xy + 2 moff[p], dst_xy + 2 moff[p], m_p and the same threshold, n_hyp, seed
+ * and refine: one seed serves all pairs, as a loop of single calls would use it.  No result depends on the other pairs of the
+ * batch, on their order, or on the run.
+ *   A pair with fewer matches than a sample (4, or 8 for the fundamental matrix; 0 is normal) is no error: it gets the "no
+ * model" answer, matrix and mask zero, count 0, best -1; in the hypotheses forms all-zero matrices and counts.  moff[n_pairs]
+ * = 0 is valid: every pair gets that answer.
+ *   DLCO_ERR_INVALID, before the handle is used and with no output touched: a null handle or required pointer, n_pairs < 1 or
+ * n_pairs >= 2^31, moff[0] != 0, a decreasing moff, a pair of 2^31 matches or more, a threshold, n_hyp or refine outside the
+ * single call's limits.
+ *   Out of scope: a device-memory form; seeds or thresholds per pair; a choice between H and F. ---- */
+int  dlco_desc_verify_pairs_homography(dlco_desc_ctx *ctx, const float *src_xy_host, const float *dst_xy_host, const int64_t *moff,
+                                       int64_t n_pairs, float threshold, int32_t n_hyp, uint64_t seed, int32_t refine, double *H_out,
+                                       uint8_t *inlier_host, int64_t *n_inliers, int32_t *best_hyp);
+int  dlco_desc_verify_pairs_fundamental(dlco_desc_ctx *ctx, const float *src_xy_host, const float *dst_xy_host, const int64_t *moff,
+                                        int64_t n_pairs, float threshold, int32_t n_hyp, uint64_t seed, int32_t refine, double *F_out,
+                                        uint8_t *inlier_host, int64_t *n_inliers, int32_t *best_hyp);
+/* every hypothesis of every pair and its count, M_all [n_pairs][n_hyp][9] and count [n_pairs][n_hyp]: for tests and tools */
+int  dlco_desc_verify_pairs_hypotheses(dlco_desc_ctx *ctx, const float *src_xy_host, const float *dst_xy_host, const int64_t *moff,
+                                       int64_t n_pairs, float threshold, int32_t n_hyp, uint64_t seed, double *H_all_host,
+                                       int32_t *count_host);
+int  dlco_desc_verify_pairs_fundamental_hypotheses(dlco_desc_ctx *ctx, const float *src_xy_host, const float *dst_xy_host,
+                                                   const int64_t *moff, int64_t n_pairs, float threshold, int32_t n_hyp, uint64_t seed,
+                                                   double *F_all_host, int32_t *count_host);
+/* the plan only, needs neither a context nor a device: launch_of_pair [n_pairs] = the launch that carries pair p in such a
+ * call, -1 for a pair that launches nothing (fewer matches than a sample); fundamental = 0: the homography, 1: the fundamental
+ * matrix.  DLCO_ERR_INVALID as above, and for another value of fundamental.  For tests and tools */
+int  dlco_desc_verify_pairs_launches(const int64_t *moff, int64_t n_pairs, int32_t n_hyp, int32_t fundamental, int32_t *launch_of_pair);
 /* HIP-event time of the kernels of the last compute / describe call (transform, pooling, projection, and the sampling
  * for the keypoint calls; extract_patches: the sampling alone); the pair_sqdists /
  * pair_stats calls add their distance kernel; after a match / cross_sqdists call, float or _u8, the time of its kernels
@@ -800,7 +836,9 @@ int  dlco_desc_verify_fundamental_hypotheses(dlco_desc_ctx *ctx, const float *sr
  * detector's kernels (the integral image when the call formed it, the octaves, the selection; detect_oriented adds the
  * orientation kernel); after an orient call the orientation kernel and the integral image when the call formed it; after a
  * verify call the verify kernels (hypotheses, scoring, selection, of either model; verify_homography and verify_fundamental add
- * the mask kernel of the best model and of every refit round) */
+ * the mask kernel of the best model and of every refit round); after a verify_pairs call every kernel of the call (the
+ * hypotheses and the scoring of every launch; verify_pairs_homography and verify_pairs_fundamental add the selection, the mask
+ * of the best models and the mask launch of every lockstep refit round) */
 double dlco_desc_last_kernel_ms(const dlco_desc_ctx *ctx);
 
 #ifdef __cplusplus

@@ -207,6 +207,11 @@ def load():
     L.dlco_desc_verify_hypotheses.argtypes = [vp, f32p, f32p, i64, C.c_float, C.c_int32, C.c_uint64, f64p, i32p]
     L.dlco_desc_verify_fundamental.argtypes = L.dlco_desc_verify_homography.argtypes
     L.dlco_desc_verify_fundamental_hypotheses.argtypes = L.dlco_desc_verify_hypotheses.argtypes
+    L.dlco_desc_verify_pairs_homography.argtypes = [vp, f32p, f32p, i64p, i64, C.c_float, C.c_int32, C.c_uint64, C.c_int32, f64p, u8p, i64p, i32p]
+    L.dlco_desc_verify_pairs_hypotheses.argtypes = [vp, f32p, f32p, i64p, i64, C.c_float, C.c_int32, C.c_uint64, f64p, i32p]
+    L.dlco_desc_verify_pairs_fundamental.argtypes = L.dlco_desc_verify_pairs_homography.argtypes
+    L.dlco_desc_verify_pairs_fundamental_hypotheses.argtypes = L.dlco_desc_verify_pairs_hypotheses.argtypes
+    L.dlco_desc_verify_pairs_launches.argtypes = [i64p, i64, C.c_int32, C.c_int32, i32p]
     L.dlco_desc_match_guided.argtypes = [vp, f32p, f32p, i64, f32p, f32p, i64, C.c_int32, f64p, C.c_float, C.c_int32, i32p, f32p]
     L.dlco_desc_match_guided_device.argtypes = [vp, vp, i64, vp, i64, i64, vp, i64, vp, i64, i64, C.c_int32, f64p, C.c_float,
                                                 C.c_int32, vp, vp]
@@ -290,6 +295,18 @@ def match_pairs_rows(seg, pairs):
     if rc != OK:
         raise DlcoError(rc, "match_pairs_rows: invalid seg or pairs")
     return row0
+
+
+def verify_pairs_launches(moff, n_hyp, fundamental=False):
+    """launch [n_pairs] int32 of a verify_pairs call over the match offsets moff [n_pairs + 1]: the launch that carries pair p,
+    -1 for a pair of fewer matches than a sample (4, or 8 with fundamental), which launches nothing.  No device."""
+    o = np.ascontiguousarray(moff, np.int64)
+    assert o.ndim == 1 and o.size >= 2
+    out = np.empty(o.size - 1, np.int32)
+    rc = load().dlco_desc_verify_pairs_launches(_p(o, i64p), o.size - 1, n_hyp, 1 if fundamental else 0, _p(out, i32p))
+    if rc != OK:
+        raise DlcoError(rc, "verify_pairs_launches: invalid moff or n_hyp")
+    return out
 
 
 def _f32(a):
@@ -1067,6 +1084,53 @@ class DescContext:
         """Every hypothesis of verify_fundamental and its inlier count: (F_all [n_hyp,3,3] f64, all zero where invalid,
         count [n_hyp] int32)."""
         return self._verify_hypotheses(self.L.dlco_desc_verify_fundamental_hypotheses, src, dst, threshold, n_hyp, seed)
+
+    # ---- verifying many pairs in one call: the lists as one list (csrc/verify_batch.hpp states the plan) ----
+    def _match_lists(self, lists):
+        """lists of (src [m,2], dst [m,2]), m >= 0, as one list: (src, dst [M + 1,2] with a row of padding, so that an empty
+        list still has an address, moff [n_pairs + 1] int64)"""
+        pts = [self._match_points(np.reshape(_f32(s), (-1, 2)), np.reshape(_f32(d), (-1, 2))) for s, d in lists]
+        assert pts, "verify_pairs: no pair"
+        moff = np.concatenate([[0], np.cumsum([len(s) for s, _ in pts])]).astype(np.int64)
+        pad = [np.zeros((1, 2), np.float32)]
+        return np.concatenate([s for s, _ in pts] + pad), np.concatenate([d for _, d in pts] + pad), moff
+
+    def _verify_pairs_model(self, call, lists, threshold, n_hyp, seed, refine):
+        s, d, moff = self._match_lists(lists)
+        P = moff.size - 1
+        M, mask = np.zeros((P, 3, 3), np.float64), np.zeros(max(int(moff[-1]), 1), np.uint8)
+        n, best = np.zeros(P, np.int64), np.zeros(P, np.int32)
+        self._ck(call(self.h, _p(s, f32p), _p(d, f32p), _p(moff, i64p), P, threshold, n_hyp, seed, refine, _p(M, C.POINTER(C.c_double)), _p(mask, u8p),
+                      _p(n, i64p), _p(best, i32p)))
+        out = [(M[p], mask[moff[p]:moff[p + 1]].astype(bool), int(best[p])) for p in range(P)]
+        assert all(int(o[1].sum()) == n[p] for p, o in enumerate(out))
+        return out
+
+    def _verify_pairs_hypotheses(self, call, lists, threshold, n_hyp, seed):
+        s, d, moff = self._match_lists(lists)
+        P = moff.size - 1
+        M_all, count = np.zeros((P, n_hyp, 3, 3), np.float64), np.zeros((P, n_hyp), np.int32)
+        self._ck(call(self.h, _p(s, f32p), _p(d, f32p), _p(moff, i64p), P, threshold, n_hyp, seed, _p(M_all, C.POINTER(C.c_double)), _p(count, i32p)))
+        return M_all, count
+
+    def verify_pairs_homography(self, lists, threshold=3.0, n_hyp=2048, seed=0, refine=2):
+        """verify_homography for a list of (src [m,2], dst [m,2]) in one call: a list of (H [3,3], inlier [m] bool, best_hyp),
+        each what verify_homography returns for its pair, byte for byte.  A pair of fewer than 4 matches (0 is allowed) gets
+        "no model": zeros and best_hyp = -1."""
+        return self._verify_pairs_model(self.L.dlco_desc_verify_pairs_homography, lists, threshold, n_hyp, seed, refine)
+
+    def verify_pairs_fundamental(self, lists, threshold=1.0, n_hyp=2048, seed=0, refine=2):
+        """verify_fundamental for a list of (src, dst) in one call; a pair of fewer than 8 matches gets "no model"."""
+        return self._verify_pairs_model(self.L.dlco_desc_verify_pairs_fundamental, lists, threshold, n_hyp, seed, refine)
+
+    def verify_pairs_hypotheses(self, lists, threshold=3.0, n_hyp=2048, seed=0):
+        """Every hypothesis of verify_pairs_homography and its count: (H_all [n_pairs,n_hyp,3,3] f64, count [n_pairs,n_hyp]
+        int32), all zero for a pair of fewer than 4 matches."""
+        return self._verify_pairs_hypotheses(self.L.dlco_desc_verify_pairs_hypotheses, lists, threshold, n_hyp, seed)
+
+    def verify_pairs_fundamental_hypotheses(self, lists, threshold=1.0, n_hyp=2048, seed=0):
+        """Every hypothesis of verify_pairs_fundamental and its count, all zero for a pair of fewer than 8 matches."""
+        return self._verify_pairs_hypotheses(self.L.dlco_desc_verify_pairs_fundamental_hypotheses, lists, threshold, n_hyp, seed)
 
     def match_device(self, q_ptr, nq, t_ptr, nt, r, idx_ptr, d_ptr, ldq=None, ldt=None):
         """match on tables in device memory (row pitches ldq, ldt: multiples of 4, default r); results to device memory."""

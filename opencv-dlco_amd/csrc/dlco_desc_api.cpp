@@ -97,12 +97,14 @@ struct dlco_desc_ctx {
     DevBuf<uint8_t> o_status;
     double o_ms = 0.0;
     // verification (dlco_desc_verify_*, either model): the uploaded matches, every hypothesis and its count, the selection
-    // key, the mask of one model and its count; buffers of their own, like the matchers'
+    // key, the mask of one model and its count; buffers of their own, like the matchers'.  The batch forms
+    // (dlco_desc_verify_pairs_*) hold one launch of verify_batch.hpp's plan in the same buffers, a slot per entry, and add
+    // v_plan, the uploaded entries and behind them the active list, and v_cur, the matrix the mask kernel scores per entry
     DevBuf<float> v_src, v_dst;
-    DevBuf<double> v_H;
+    DevBuf<double> v_H, v_cur;
     DevBuf<int32_t> v_count, v_n;
     DevBuf<uint64_t> v_key;
-    DevBuf<uint8_t> v_mask;
+    DevBuf<uint8_t> v_mask, v_plan;
     double last_ms = 0.0;
 };
 
@@ -599,6 +601,167 @@ int verify_model_call(dlco_desc_ctx *c, const float *src_xy_host, const float *d
         if (inlier_host) std::memcpy(inlier_host, mask.data(), (size_t)m);
         *n_inliers = count;
         if (best_hyp) *best_hyp = best;
+        c->last_ms = ms;
+    });
+}
+
+// ---- the batch forms (dlco_desc_verify_pairs_*): the match lists of many pairs as one segmented list, by the plan of
+// verify_batch.hpp.  The same buffers, rule headers and acceptance rule as above; what differs is that a launch carries the
+// workgroups of many pairs, that the selection leaves the winning matrices on the device for the first mask, and that the
+// refit runs in lockstep: one mask launch scores a round's models of every pair still refining. ----------------------------
+namespace vb = verify_batch;
+
+template <typename Model>
+bool verify_pairs_args_ok(const float *src, const float *dst, const int64_t *moff, int64_t n_pairs, float threshold, int32_t n_hyp)
+{
+    return src && dst && vb::offsets_ok(moff, n_pairs) && std::isfinite(threshold) && threshold > 0.0f && n_hyp >= 1 && n_hyp <= verify_rules::kMaxHyp;
+}
+
+// One launch of the plan on the device: its matches, its entries and, behind them, room for an active list.
+struct VerifyLaunch {
+    const vb::Entry *ent_host;
+    const vb::Entry *ent;
+    vb::Active *active;
+    int64_t n, matches;
+};
+
+// the launch's matches and entries to the device, count and n zeroed
+VerifyLaunch verify_pairs_upload(dlco_desc_ctx *c, const vb::Plan &pl, const vb::Launch &la, const float *src_host, const float *dst_host, int32_t n_hyp)
+{
+    const size_t n = (size_t)la.n, ent_bytes = n * sizeof(vb::Entry);
+    c->v_src.alloc((size_t)la.matches * 2); c->v_dst.alloc((size_t)la.matches * 2);
+    c->v_H.alloc((size_t)la.hyps * 9); c->v_count.alloc((size_t)la.hyps);
+    c->v_key.alloc(n); c->v_cur.alloc(n * 9); c->v_n.alloc(n);
+    c->v_mask.alloc((size_t)la.matches);
+    c->v_plan.alloc(ent_bytes + n * sizeof(vb::Active));
+    const vb::Entry *ent_host = pl.entries.data() + la.e0;
+    DLCO_HIP(hipMemcpyAsync(c->v_src.p, src_host + 2 * la.match0, (size_t)la.matches * 2 * sizeof(float), hipMemcpyHostToDevice, c->stream));
+    DLCO_HIP(hipMemcpyAsync(c->v_dst.p, dst_host + 2 * la.match0, (size_t)la.matches * 2 * sizeof(float), hipMemcpyHostToDevice, c->stream));
+    DLCO_HIP(hipMemcpyAsync(c->v_plan.p, ent_host, ent_bytes, hipMemcpyHostToDevice, c->stream));
+    DLCO_HIP(hipMemsetAsync(c->v_count.p, 0, (size_t)la.hyps * sizeof(int32_t), c->stream));
+    DLCO_HIP(hipMemsetAsync(c->v_n.p, 0, n * sizeof(int32_t), c->stream));
+    return VerifyLaunch{ent_host, reinterpret_cast<const vb::Entry *>(c->v_plan.p), reinterpret_cast<vb::Active *>(c->v_plan.p + ent_bytes), la.n, la.matches};
+}
+
+// every hypothesis of every pair and its count, to the host; a pair without an entry keeps its zeros
+template <typename Model>
+int verify_pairs_hypotheses_call(dlco_desc_ctx *c, const float *src_xy_host, const float *dst_xy_host, const int64_t *moff, int64_t n_pairs,
+                                 float threshold, int32_t n_hyp, uint64_t seed, double *M_all_host, int32_t *count_host)
+{
+    if (!c || !M_all_host || !count_host || !verify_pairs_args_ok<Model>(src_xy_host, dst_xy_host, moff, n_pairs, threshold, n_hyp))
+        return DLCO_ERR_INVALID;
+    return guarded(c, [&] {
+        DLCO_HIP(hipSetDevice(c->device));
+        const double t2 = verify_rules::threshold_sq(threshold);
+        const vb::Plan pl = vb::plan(moff, n_pairs, n_hyp, Model::kSample);
+        std::memset(M_all_host, 0, (size_t)n_pairs * n_hyp * 9 * sizeof(double));
+        std::memset(count_host, 0, (size_t)n_pairs * n_hyp * sizeof(int32_t));
+        std::vector<double> M_all((size_t)pl.max_hyps * 9);
+        std::vector<int32_t> count((size_t)pl.max_hyps);
+        EventPair ev;
+        double ms = 0.0;
+        for (const vb::Launch &la : pl.launches) {
+            const VerifyLaunch v = verify_pairs_upload(c, pl, la, src_xy_host, dst_xy_host, n_hyp);
+            ms += timed_ms(c, ev, [&] {
+                verify_pairs_hypotheses<Model>(c->v_src.p, c->v_dst.p, v.ent, v.n, seed, n_hyp, c->v_H.p, c->stream);
+                verify_pairs_score<Model>(c->v_src.p, c->v_dst.p, v.ent, v.n, la.score_wgs, c->v_H.p, n_hyp, t2, c->v_count.p, c->stream);
+            }, [&] {
+                DLCO_HIP(hipMemcpyAsync(M_all.data(), c->v_H.p, (size_t)la.hyps * 9 * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+                DLCO_HIP(hipMemcpyAsync(count.data(), c->v_count.p, (size_t)la.hyps * sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
+            });
+            for (int64_t e = 0; e < v.n; e++) {
+                const size_t p = (size_t)v.ent_host[e].pair;
+                std::memcpy(M_all_host + p * n_hyp * 9, M_all.data() + (size_t)e * n_hyp * 9, (size_t)n_hyp * 9 * sizeof(double));
+                std::memcpy(count_host + p * n_hyp, count.data() + (size_t)e * n_hyp, (size_t)n_hyp * sizeof(int32_t));
+            }
+        }
+        c->last_ms = ms;
+    });
+}
+
+// the best model of every pair, its mask and the refit in lockstep: in a round the host forms Model::refit_round for every
+// pair still refining, on the pair's own slice, one mask launch scores them, and verify_rules::refit_step decides per pair
+template <typename Model>
+int verify_pairs_model_call(dlco_desc_ctx *c, const float *src_xy_host, const float *dst_xy_host, const int64_t *moff, int64_t n_pairs,
+                            float threshold, int32_t n_hyp, uint64_t seed, int32_t refine, double *M_out, uint8_t *inlier_host, int64_t *n_inliers,
+                            int32_t *best_hyp)
+{
+    if (!c || !M_out || !n_inliers || refine < 0 || refine > verify_rules::kMaxRefine ||
+        !verify_pairs_args_ok<Model>(src_xy_host, dst_xy_host, moff, n_pairs, threshold, n_hyp))
+        return DLCO_ERR_INVALID;
+    return guarded(c, [&] {
+        namespace vr = verify_rules;
+        DLCO_HIP(hipSetDevice(c->device));
+        const double t2 = vr::threshold_sq(threshold);
+        const vb::Plan pl = vb::plan(moff, n_pairs, n_hyp, Model::kSample);
+        // "no model" everywhere; the entries overwrite their slots
+        std::memset(M_out, 0, (size_t)n_pairs * 9 * sizeof(double));
+        if (inlier_host) std::memset(inlier_host, 0, (size_t)moff[n_pairs]);
+        for (int64_t p = 0; p < n_pairs; p++) { n_inliers[p] = 0; if (best_hyp) best_hyp[p] = -1; }
+        const size_t ne = (size_t)pl.max_entries;
+        std::vector<uint64_t> key(ne);
+        std::vector<double> M_try(ne * 9);
+        std::vector<int32_t> cnt(ne), live;
+        std::vector<uint8_t> cur((size_t)pl.max_matches), trial((size_t)pl.max_matches);
+        std::vector<vb::Active> act(ne);
+        EventPair ev;
+        double ms = 0.0;
+        for (const vb::Launch &la : pl.launches) {
+            const VerifyLaunch v = verify_pairs_upload(c, pl, la, src_xy_host, dst_xy_host, n_hyp);
+            const float *src = src_xy_host + 2 * la.match0, *dst = dst_xy_host + 2 * la.match0;
+            for (int64_t e = 0; e < v.n; e++) act[(size_t)e] = vb::Active{(int32_t)e, v.ent_host[e].mwg0};
+            DLCO_HIP(hipMemcpyAsync(v.active, act.data(), (size_t)v.n * sizeof(vb::Active), hipMemcpyHostToDevice, c->stream));
+            ms += timed_ms(c, ev, [&] {
+                verify_pairs_hypotheses<Model>(c->v_src.p, c->v_dst.p, v.ent, v.n, seed, n_hyp, c->v_H.p, c->stream);
+                verify_pairs_score<Model>(c->v_src.p, c->v_dst.p, v.ent, v.n, la.score_wgs, c->v_H.p, n_hyp, t2, c->v_count.p, c->stream);
+                verify_pairs_select(c->v_count.p, c->v_H.p, v.n, n_hyp, c->v_key.p, c->v_cur.p, c->stream);
+                verify_pairs_mask<Model>(c->v_src.p, c->v_dst.p, v.ent, v.active, v.n, la.mask_wgs, c->v_cur.p, t2, c->v_mask.p, c->v_n.p, c->stream);
+            }, [&] {
+                DLCO_HIP(hipMemcpyAsync(key.data(), c->v_key.p, (size_t)v.n * sizeof(uint64_t), hipMemcpyDeviceToHost, c->stream));
+                DLCO_HIP(hipMemcpyAsync(M_try.data(), c->v_cur.p, (size_t)v.n * 9 * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+                DLCO_HIP(hipMemcpyAsync(cur.data(), c->v_mask.p, (size_t)v.matches, hipMemcpyDeviceToHost, c->stream));
+                DLCO_HIP(hipMemcpyAsync(cnt.data(), c->v_n.p, (size_t)v.n * sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
+            });
+            live.clear();
+            for (int64_t e = 0; e < v.n; e++) {
+                if (vr::key_count(key[(size_t)e]) == 0) continue;
+                const size_t p = (size_t)v.ent_host[e].pair;
+                std::memcpy(M_out + 9 * p, M_try.data() + 9 * (size_t)e, 9 * sizeof(double));
+                n_inliers[p] = cnt[(size_t)e];
+                if (best_hyp) best_hyp[p] = vr::key_hyp(key[(size_t)e]);
+                live.push_back((int32_t)e);
+            }
+            for (int32_t k = 0; k < refine && !live.empty(); k++) {
+                int64_t n_act = 0, wgs = 0;
+                for (int32_t e : live) {
+                    const vb::Entry &en = v.ent_host[e];
+                    if (!Model::refit_round(src + 2 * en.m0, dst + 2 * en.m0, en.m, cur.data() + en.m0, M_try.data() + 9 * (size_t)e)) continue;
+                    act[(size_t)n_act++] = vb::Active{e, (int32_t)wgs};
+                    wgs += vb::blocks(en.m);
+                }
+                if (n_act == 0) break;
+                DLCO_HIP(hipMemcpyAsync(c->v_cur.p, M_try.data(), (size_t)v.n * 9 * sizeof(double), hipMemcpyHostToDevice, c->stream));
+                DLCO_HIP(hipMemcpyAsync(v.active, act.data(), (size_t)n_act * sizeof(vb::Active), hipMemcpyHostToDevice, c->stream));
+                DLCO_HIP(hipMemsetAsync(c->v_n.p, 0, (size_t)v.n * sizeof(int32_t), c->stream));
+                ms += timed_ms(c, ev, [&] {
+                    verify_pairs_mask<Model>(c->v_src.p, c->v_dst.p, v.ent, v.active, n_act, wgs, c->v_cur.p, t2, c->v_mask.p, c->v_n.p, c->stream);
+                }, [&] {
+                    DLCO_HIP(hipMemcpyAsync(trial.data(), c->v_mask.p, (size_t)v.matches, hipMemcpyDeviceToHost, c->stream));
+                    DLCO_HIP(hipMemcpyAsync(cnt.data(), c->v_n.p, (size_t)v.n * sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
+                });
+                live.clear();
+                for (int64_t a = 0; a < n_act; a++) {
+                    const int32_t e = act[(size_t)a].entry;
+                    const vb::Entry &en = v.ent_host[e];
+                    if (vr::refit_step(en.m, M_out + 9 * (size_t)en.pair, cur.data() + en.m0, n_inliers[en.pair], M_try.data() + 9 * (size_t)e,
+                                       trial.data() + en.m0, cnt[(size_t)e]))
+                        live.push_back(e);
+                }
+            }
+            if (inlier_host)
+                for (int64_t e = 0; e < v.n; e++)
+                    std::memcpy(inlier_host + la.match0 + v.ent_host[e].m0, cur.data() + v.ent_host[e].m0, (size_t)v.ent_host[e].m);
+        }
         c->last_ms = ms;
     });
 }
@@ -1416,6 +1579,48 @@ int dlco_desc_verify_fundamental(dlco_desc_ctx *c, const float *src_xy_host, con
     return verify_model_call<Fundamental>(c, src_xy_host, dst_xy_host, m, threshold, n_hyp, seed, refine, F_out, inlier_host, n_inliers, best_hyp);
 }
 
+// the four calls over the match lists of many pairs as one list cut by moff [n_pairs + 1]: pair p's answers are the single
+// call's on its slice
+int dlco_desc_verify_pairs_homography(dlco_desc_ctx *c, const float *src_xy_host, const float *dst_xy_host, const int64_t *moff, int64_t n_pairs,
+                                      float threshold, int32_t n_hyp, uint64_t seed, int32_t refine, double *H_out, uint8_t *inlier_host,
+                                      int64_t *n_inliers, int32_t *best_hyp)
+{
+    return verify_pairs_model_call<Homography>(c, src_xy_host, dst_xy_host, moff, n_pairs, threshold, n_hyp, seed, refine, H_out, inlier_host, n_inliers,
+                                               best_hyp);
+}
+
+int dlco_desc_verify_pairs_fundamental(dlco_desc_ctx *c, const float *src_xy_host, const float *dst_xy_host, const int64_t *moff, int64_t n_pairs,
+                                       float threshold, int32_t n_hyp, uint64_t seed, int32_t refine, double *F_out, uint8_t *inlier_host,
+                                       int64_t *n_inliers, int32_t *best_hyp)
+{
+    return verify_pairs_model_call<Fundamental>(c, src_xy_host, dst_xy_host, moff, n_pairs, threshold, n_hyp, seed, refine, F_out, inlier_host, n_inliers,
+                                                best_hyp);
+}
+
+int dlco_desc_verify_pairs_hypotheses(dlco_desc_ctx *c, const float *src_xy_host, const float *dst_xy_host, const int64_t *moff, int64_t n_pairs,
+                                      float threshold, int32_t n_hyp, uint64_t seed, double *H_all_host, int32_t *count_host)
+{
+    return verify_pairs_hypotheses_call<Homography>(c, src_xy_host, dst_xy_host, moff, n_pairs, threshold, n_hyp, seed, H_all_host, count_host);
+}
+
+int dlco_desc_verify_pairs_fundamental_hypotheses(dlco_desc_ctx *c, const float *src_xy_host, const float *dst_xy_host, const int64_t *moff,
+                                                  int64_t n_pairs, float threshold, int32_t n_hyp, uint64_t seed, double *F_all_host,
+                                                  int32_t *count_host)
+{
+    return verify_pairs_hypotheses_call<Fundamental>(c, src_xy_host, dst_xy_host, moff, n_pairs, threshold, n_hyp, seed, F_all_host, count_host);
+}
+
+// the plan only: the launch of every pair, -1 for a pair that launches nothing; host only
+int dlco_desc_verify_pairs_launches(const int64_t *moff, int64_t n_pairs, int32_t n_hyp, int32_t fundamental, int32_t *launch_of_pair)
+{
+    if (!launch_of_pair || !verify_batch::offsets_ok(moff, n_pairs) || n_hyp < 1 || n_hyp > verify_rules::kMaxHyp || (fundamental != 0 && fundamental != 1))
+        return DLCO_ERR_INVALID;
+    return guarded(nullptr, [&] {
+        const verify_batch::Plan pl = verify_batch::plan(moff, n_pairs, n_hyp, fundamental ? Fundamental::kSample : Homography::kSample);
+        std::copy(pl.launch_of_pair.begin(), pl.launch_of_pair.end(), launch_of_pair);
+    });
+}
+
 // ---- byte descriptors: the quantiser (quant_rules.hpp), the _u8 forms of describe, the match of byte tables -------------------
 // o_k = min_i Y[i][k], s = 255 / max_k (max_i Y[i][k] - o_k) or 1: host only
 int dlco_desc_quant_fit(const float *Y_host, int64_t n, int32_t r, float *scale, float *offset_out)
@@ -1530,7 +1735,8 @@ int dlco_desc_cross_sqdists_u8(dlco_desc_ctx *c, const uint8_t *query_u8, int64_
 // forms of describe add their quantising kernel; after an orient call the orientation kernel and the integral image when the
 // call formed it; after a detect call the detector's kernels (the integral image when the call
 // formed it, the octaves, the selection); after a verify call the verify kernels (hypotheses, scoring, selection, and for
-// verify_homography and verify_fundamental the mask kernel of the best model and of every refit round)
+// verify_homography and verify_fundamental the mask kernel of the best model and of every refit round); after a
+// verify_pairs call every kernel of every launch of the call, the mask launches of the lockstep refit rounds included
 double dlco_desc_last_kernel_ms(const dlco_desc_ctx *c) { return c ? c->last_ms : 0.0; }
 
 }  // extern "C"

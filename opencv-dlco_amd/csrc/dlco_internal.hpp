@@ -5,6 +5,7 @@
 #include "../../include/dlco.h"
 #include "match_batch.hpp"
 #include "match_slices.hpp"
+#include "verify_batch.hpp"
 
 #include <hip/hip_runtime.h>
 
@@ -613,5 +614,19 @@ void verify_score(const float *src, const float *dst, int64_t m, const double *M
 void verify_select(const int32_t *count, int n_hyp, uint64_t *best, hipStream_t s);
 template <typename Model>
 void verify_mask(const float *src, const float *dst, int64_t m, const double *M, double t2, uint8_t *mask, int32_t *count, hipStream_t s);
+// the same steps for one launch of verify_batch.hpp's plan (dlco_desc_verify_pairs_*): ent [n_ent] and the launch's matches in
+// device memory, slot e of M_all [.][n_hyp][9], count [.][n_hyp], best, M_cur [.][9] and n belongs to the entry at position e.
+// best [e] = the largest key of entry e and M_cur [e] its matrix (zero: no model); the mask kernel scores M_cur [entry] for
+// the entries of active [n_active] (mask_wgs workgroups) into mask at the entry's matches and n [entry] (the caller zeroes it)
+template <typename Model>
+void verify_pairs_hypotheses(const float *src, const float *dst, const verify_batch::Entry *ent, int64_t n_ent, uint64_t seed, int n_hyp, double *M_all,
+                             hipStream_t s);
+template <typename Model>
+void verify_pairs_score(const float *src, const float *dst, const verify_batch::Entry *ent, int64_t n_ent, int64_t wgs, const double *M_all, int n_hyp,
+                        double t2, int32_t *count, hipStream_t s);
+void verify_pairs_select(const int32_t *count, const double *M_all, int64_t n_ent, int n_hyp, uint64_t *best, double *M_cur, hipStream_t s);
+template <typename Model>
+void verify_pairs_mask(const float *src, const float *dst, const verify_batch::Entry *ent, const verify_batch::Active *active, int64_t n_active,
+                       int64_t mask_wgs, const double *M_cur, double t2, uint8_t *mask, int32_t *n, hipStream_t s);
 
 }  // namespace dlco

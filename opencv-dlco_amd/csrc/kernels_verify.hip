@@ -18,6 +18,19 @@
 //                         neither on the chunking.
 //   verify_select_kernel  one workgroup: the maximum of the key (count << 32) | (0xFFFFFFFF - h).
 //   mask_kernel<Model>    one lane per match for one M: the u8 mask and, by a ballot per wave and one atomicAdd, its count.
+//
+// The _pairs forms (dlco_desc_verify_pairs_*) run the same steps for the entries of one launch of verify_batch.hpp's plan,
+// many pairs of one segmented match list; the entry at position e of the launch owns slot e of every device array.  The
+// functions of the rule headers are called on the pair's own base pointers and match count, so a pair's numbers are the
+// single call's.
+//   hyp_pairs_kernel<Model>    (entry, hypothesis) to a lane: every entry has the same ceil(n_hyp / kHypLanes) workgroups.
+//   score_pairs_kernel<Model>  score_kernel's loop on a 1-D grid: a workgroup is (entry, block of 256 hypotheses, chunk of
+//                              matches), the block the faster index; it finds its entry by a scalar binary search over swg0.
+//   select_pairs_kernel        one workgroup per entry: the largest key and, with no host round trip, the winning matrix in
+//                              M_cur [e] (zero when the best count is 0).
+//   mask_pairs_kernel<Model>   a workgroup is (active entry, 256 matches of it), found by the same search over the active
+//                              list; M_cur [e] comes from device memory; the trial mask at the entry's matches, the count by
+//                              a ballot and one atomicAdd per wave into n [e].
 #include "dlco_internal.hpp"
 #include "epipolar_rules.hpp"
 
@@ -26,6 +39,7 @@ namespace dlco {
 namespace {
 
 namespace vr = verify_rules;
+namespace vb = verify_batch;
 
 constexpr int VTH = 256;
 constexpr int VSEL = 1024;                                  // lanes of the selection's one workgroup
@@ -107,6 +121,110 @@ __global__ __launch_bounds__(VTH) void mask_kernel(const float2 *src, const floa
     if ((threadIdx.x & 63) == 0 && n > 0) atomicAdd(count, n);
 }
 
+// the position of the last item whose first workgroup (first(item)) is not above wg; wg is the same for the whole workgroup,
+// so the search is scalar loads and branches
+template <typename Item, typename First>
+__device__ __forceinline__ int pairs_item_of(const Item *__restrict__ items, int n, long wg, First first)
+{
+    int lo = 0, hi = n;
+    while (hi - lo > 1) {
+        const int mid = (lo + hi) >> 1;
+        if ((long)first(items[mid]) <= wg) lo = mid; else hi = mid;
+    }
+    return lo;
+}
+
+template <typename Model>
+__global__ __launch_bounds__(kHypLanes<Model>) void hyp_pairs_kernel(const float *src, const float *dst, const vb::Entry *__restrict__ ent,
+                                                                     unsigned long long seed, int n_hyp, int hblocks, double *M_all)
+{
+    const int e = blockIdx.x / hblocks;
+    const int h = (blockIdx.x - e * hblocks) * kHypLanes<Model> + threadIdx.x;
+    if (h >= n_hyp) return;
+    const vb::Entry en = ent[e];
+    int32_t idx[Model::kSample];
+    double M[9];
+    Model::hypothesis(src + 2 * en.m0, dst + 2 * en.m0, (unsigned)en.m, seed, (uint32_t)h, idx, M);
+    double *out = M_all + 9 * ((long)e * n_hyp + h);
+    for (int i = 0; i < 9; i++) out[i] = M[i];
+}
+
+// workgroup wg_base + blockIdx.x of the launch's scoring grid: wg_base is 0 unless one entry's grid is walked in pieces
+template <typename Model>
+__global__ __launch_bounds__(VTH) void score_pairs_kernel(const float2 *src, const float2 *dst, const vb::Entry *__restrict__ ent, int n_ent,
+                                                          const double *M_all, int n_hyp, int hblocks, double t2, int *count, long wg_base)
+{
+    __shared__ double4 pts[vr::kScoreChunk];
+    static_assert(vr::kScoreChunk == VTH && vb::kLanes == VTH, "a lane stages one match of the chunk; the plan counts blocks of VTH");
+    const long wg = wg_base + blockIdx.x;
+    const int e = pairs_item_of(ent, n_ent, wg, [](const vb::Entry &x) { return x.swg0; });
+    const vb::Entry en = ent[e];
+    const long w = wg - en.swg0;
+    const long chunk = w / hblocks;
+    const int h = (int)(w - chunk * hblocks) * VTH + threadIdx.x;
+    const long i0 = en.m0 + chunk * vr::kScoreChunk;
+    const int cnt = (int)min((long)vr::kScoreChunk, en.m0 + en.m - i0);
+    if ((int)threadIdx.x < cnt) {
+        const float2 s = src[i0 + threadIdx.x], d = dst[i0 + threadIdx.x];
+        pts[threadIdx.x] = make_double4((double)s.x, (double)s.y, (double)d.x, (double)d.y);
+    }
+    const long slot = (long)e * n_hyp + h;
+    double M[9];
+    for (int i = 0; i < 9; i++) M[i] = h < n_hyp ? M_all[9 * slot + i] : 0.0;
+    __syncthreads();
+    int n = 0;
+    for (int j = 0; j < cnt; j++) {
+        const double4 p = pts[j];
+        n += Model::inlier(M, p.x, p.y, p.z, p.w, t2) ? 1 : 0;
+    }
+    if (h < n_hyp && n > 0) atomicAdd(&count[slot], n);
+}
+
+__global__ __launch_bounds__(VSEL) void select_pairs_kernel(const int *count, const double *M_all, int n_hyp, unsigned long long *best, double *M_cur)
+{
+    __shared__ unsigned long long part[VSEL / 64];
+    const long e = blockIdx.x;
+    const int *cnt = count + e * n_hyp;
+    unsigned long long key = 0;
+    for (int h = threadIdx.x; h < n_hyp; h += VSEL) {
+        const unsigned long long k = vr::select_key(cnt[h], (uint32_t)h);
+        key = k > key ? k : key;
+    }
+    for (int d = 32; d >= 1; d >>= 1) {
+        const unsigned long long other = __shfl_xor(key, d);
+        key = other > key ? other : key;
+    }
+    if ((threadIdx.x & 63) == 0) part[threadIdx.x >> 6] = key;
+    __syncthreads();
+    for (int w = 0; w < VSEL / 64; w++) key = part[w] > key ? part[w] : key;
+    if (threadIdx.x == 0) best[e] = key;
+    if (threadIdx.x < 9) {
+        const bool any = vr::key_count(key) > 0;
+        M_cur[9 * e + threadIdx.x] = any ? M_all[9 * (e * n_hyp + vr::key_hyp(key)) + threadIdx.x] : 0.0;
+    }
+}
+
+template <typename Model>
+__global__ __launch_bounds__(VTH) void mask_pairs_kernel(const float2 *src, const float2 *dst, const vb::Entry *__restrict__ ent,
+                                                         const vb::Active *__restrict__ active, int n_active, const double *M_cur, double t2,
+                                                         uint8_t *mask, int *count)
+{
+    const long wg = blockIdx.x;
+    const vb::Active a = active[pairs_item_of(active, n_active, wg, [](const vb::Active &x) { return x.wg0; })];
+    const vb::Entry en = ent[a.entry];
+    const long i = (wg - a.wg0) * VTH + threadIdx.x;
+    double M[9];
+    for (int k = 0; k < 9; k++) M[k] = M_cur[9 * (long)a.entry + k];
+    bool in = false;
+    if (i < en.m) {
+        const float2 s = src[en.m0 + i], d = dst[en.m0 + i];
+        in = Model::inlier(M, (double)s.x, (double)s.y, (double)d.x, (double)d.y, t2);
+        mask[en.m0 + i] = in ? 1 : 0;
+    }
+    const int n = __popcll(__ballot(in));
+    if ((threadIdx.x & 63) == 0 && n > 0) atomicAdd(&count[a.entry], n);
+}
+
 }  // namespace
 
 // M_all [n_hyp][9] of the matches src, dst [m][2] (8-byte aligned), all in device memory
@@ -152,10 +270,60 @@ void verify_mask(const float *src, const float *dst, int64_t m, const double *M,
     DLCO_HIP(hipGetLastError());
 }
 
+// ---- the _pairs forms: one launch of verify_batch.hpp's plan, ent [n_ent] and the launch's matches src, dst in device memory ----
+// M_all [n_ent][n_hyp][9]
+template <typename Model>
+void verify_pairs_hypotheses(const float *src, const float *dst, const verify_batch::Entry *ent, int64_t n_ent, uint64_t seed, int n_hyp, double *M_all,
+                             hipStream_t s)
+{
+    constexpr int lanes = kHypLanes<Model>;
+    const int hblocks = (n_hyp + lanes - 1) / lanes;
+    hipLaunchKernelGGL(hyp_pairs_kernel<Model>, dim3((unsigned)(n_ent * hblocks)), dim3(lanes), 0, s, src, dst, ent, (unsigned long long)seed, n_hyp,
+                       hblocks, M_all);
+    DLCO_HIP(hipGetLastError());
+}
+
+// count [n_ent][n_hyp] += the inliers of every hypothesis among its entry's matches; the caller zeroes count.  wgs is the
+// launch's scoring grid; one entry's grid beyond a 1-D grid's reach goes in pieces.
+template <typename Model>
+void verify_pairs_score(const float *src, const float *dst, const verify_batch::Entry *ent, int64_t n_ent, int64_t wgs, const double *M_all, int n_hyp,
+                        double t2, int32_t *count, hipStream_t s)
+{
+    const int hblocks = (int)verify_batch::blocks(n_hyp);
+    for (int64_t base = 0; base < wgs; base += verify_batch::kLaunchWgs)
+        hipLaunchKernelGGL(score_pairs_kernel<Model>, dim3((unsigned)std::min(verify_batch::kLaunchWgs, wgs - base)), dim3(VTH), 0, s,
+                           reinterpret_cast<const float2 *>(src), reinterpret_cast<const float2 *>(dst), ent, (int)n_ent, M_all, n_hyp, hblocks, t2, count,
+                           (long)base);
+    DLCO_HIP(hipGetLastError());
+}
+
+// best [n_ent] = the largest selection key of every entry, M_cur [n_ent][9] = its matrix (zero: no model)
+void verify_pairs_select(const int32_t *count, const double *M_all, int64_t n_ent, int n_hyp, uint64_t *best, double *M_cur, hipStream_t s)
+{
+    hipLaunchKernelGGL(select_pairs_kernel, dim3((unsigned)n_ent), dim3(VSEL), 0, s, count, M_all, n_hyp, reinterpret_cast<unsigned long long *>(best), M_cur);
+    DLCO_HIP(hipGetLastError());
+}
+
+// for the entries of active [n_active] (wgs workgroups in all): the mask of M_cur [entry] at the entry's matches and
+// n [entry] += its inliers; the caller zeroes n
+template <typename Model>
+void verify_pairs_mask(const float *src, const float *dst, const verify_batch::Entry *ent, const verify_batch::Active *active, int64_t n_active,
+                       int64_t wgs, const double *M_cur, double t2, uint8_t *mask, int32_t *n, hipStream_t s)
+{
+    hipLaunchKernelGGL(mask_pairs_kernel<Model>, dim3((unsigned)wgs), dim3(VTH), 0, s, reinterpret_cast<const float2 *>(src),
+                       reinterpret_cast<const float2 *>(dst), ent, active, (int)n_active, M_cur, t2, mask, n);
+    DLCO_HIP(hipGetLastError());
+}
+
 #define DLCO_VERIFY_MODEL(Model)                                                                                                 \
     template void verify_hypotheses<Model>(const float *, const float *, int64_t, uint64_t, int, double *, hipStream_t);                \
     template void verify_score<Model>(const float *, const float *, int64_t, const double *, int, double, int32_t *, hipStream_t);      \
-    template void verify_mask<Model>(const float *, const float *, int64_t, const double *, double, uint8_t *, int32_t *, hipStream_t);
+    template void verify_mask<Model>(const float *, const float *, int64_t, const double *, double, uint8_t *, int32_t *, hipStream_t);      \
+    template void verify_pairs_hypotheses<Model>(const float *, const float *, const verify_batch::Entry *, int64_t, uint64_t, int, double *, hipStream_t); \
+    template void verify_pairs_score<Model>(const float *, const float *, const verify_batch::Entry *, int64_t, int64_t, const double *, int, double,      \
+                                            int32_t *, hipStream_t);                                                                                       \
+    template void verify_pairs_mask<Model>(const float *, const float *, const verify_batch::Entry *, const verify_batch::Active *, int64_t, int64_t,      \
+                                           const double *, double, uint8_t *, int32_t *, hipStream_t);
 DLCO_VERIFY_MODEL(verify_rules::Homography)
 DLCO_VERIFY_MODEL(epipolar_rules::Fundamental)
 #undef DLCO_VERIFY_MODEL

@@ -43,7 +43,7 @@
 // Selection.  count[h] = inliers of hypothesis h (0 for an invalid one: W = 0 everywhere).  The best has the largest count,
 // ties go to the smallest h: the maximum of the key (count << 32) | (0xFFFFFFFF - h).  A best count of 0: no model.
 //
-// Refit, on the host only (refit_round; the loop is refit_rounds).  At most `refine` rounds; a round runs on the inliers of the current model
+// Refit, on the host only (refit_round; the loop is refit_rounds, a round's acceptance refit_step).  At most `refine` rounds; a round runs on the inliers of the current model
 // in ascending match index:
 //   Hartley normalisation of each side: centroid c = (sum x / n, sum y / n), d = (sum sqrt(dx dx + dy dy)) / n with
 //   dx = x - cx, s = sqrt(2) / d, sums in index order; a normalised point is ((x - cx) s, (y - cy) s).
@@ -341,6 +341,20 @@ inline bool refit_round(const float *src, const float *dst, int64_t m, const uin
     return true;
 }
 
+// The acceptance rule of one round: the model M [9] with (mask [m], count) meets the round's Mn [9], scored as (trial [m], c).
+// Mn replaces the model iff c >= count.  Returns whether the refit goes on: not after a rejected round, nor after one that
+// left the mask unchanged.  The single call's loop below and the batch's lockstep loop (dlco_desc_verify_pairs_*) both end
+// a round here.
+inline bool refit_step(int64_t m, double M[9], uint8_t *mask, int64_t &count, const double Mn[9], const uint8_t *trial, int64_t c)
+{
+    if (c < count) return false;
+    const bool same = std::memcmp(trial, mask, (size_t)m) == 0;
+    std::memcpy(M, Mn, 9 * sizeof(double));
+    std::memcpy(mask, trial, (size_t)m);
+    count = c;
+    return !same;
+}
+
 // The refit's loop for a model M [9] with (mask [m], count).  round(mask, M') forms the model of one round from the inliers of
 // mask (false: rejected), score(M', trial mask [m]) -> count of M' over all matches.  rounds [refine][9] (may be NULL) receives
 // every M' a round formed; returns their number.
@@ -355,12 +369,7 @@ inline int refit_rounds(int64_t m, int32_t refine, double M[9], uint8_t *mask, i
         if (rounds) std::memcpy(rounds + 9 * formed, Mn, sizeof Mn);
         formed++;
         const int64_t c = score(Mn, trial.data());
-        if (c < count) break;
-        const bool same = std::memcmp(trial.data(), mask, (size_t)m) == 0;
-        std::memcpy(M, Mn, sizeof Mn);
-        std::memcpy(mask, trial.data(), (size_t)m);
-        count = c;
-        if (same) break;
+        if (!refit_step(m, M, mask, count, Mn, trial.data(), c)) break;
     }
     return formed;
 }

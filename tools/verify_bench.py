@@ -12,15 +12,24 @@ median.  No gate: it prints what it measured.
 times dlco_desc_verify_fundamental_hypotheses / dlco_desc_verify_fundamental instead, at the same three shapes on a planted
 two-camera scene (points with depth, a turned camera moved sideways, 0.3 pixels of noise) with half the matches outliers, at a
 threshold of 1 pixel.  The floor counts the 33 fp64 operations of the Sampson test per pair (epipolar_rules.hpp, kOpsPerPair).
-Here torch's counts must agree with the library's: the run ends with an error when they do not."""
-import importlib, os, sys
+Here torch's counts must agree with the library's: the run ends with an error when they do not.
+
+    verify_bench.py --pairs [--fundamental]
+times one dlco_desc_verify_pairs_homography (_fundamental) call over many match lists against a Python loop of the single
+calls on the same lists in the same process: 72 pairs x 2 000 matches x 2 048 hypotheses and 1 056 pairs x 500 matches x 1 024
+hypotheses, refine 2, the same planted scenes.  One warm-up each, then three rounds that alternate batch and loop; per side the
+best round and the range, for the kernels (last_kernel_ms, summed over the loop's calls) and for the wall clock around the
+Python call(s).  The answers of the two sides are compared for equality, and the run ends with an error when they differ; the
+last line says whether the batch's slowest wall time is below the loop's fastest on every workload."""
+import importlib, os, sys, time
 import numpy as np
 import torch                                                # before libdlco.so: one HIP runtime per process, torch's first
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 dlco = importlib.import_module("opencv-dlco_amd")
 
 FUNDAMENTAL = "--fundamental" in sys.argv[1:]
-args = [a for a in sys.argv[1:] if a != "--fundamental"]
+PAIRS = "--pairs" in sys.argv[1:]
+args = [a for a in sys.argv[1:] if a not in ("--fundamental", "--pairs")]
 reps = int(args[0]) if args else 15
 OPS_PER_PAIR, THRESHOLD = (33.0, 1.0) if FUNDAMENTAL else (19.0, 3.0)
 OPS_PER_SECOND = 256 * 64 * 2.4e9
@@ -86,6 +95,51 @@ def torch_counts(H_all, src, dst, t2):
         ms.append(e0.elapsed_time(e1))
     return out.cpu().numpy(), float(np.median(ms))
 
+
+def pairs_bench():
+    ctx = dlco.DescContext()
+    single, batch = (ctx.verify_fundamental, ctx.verify_pairs_fundamental) if FUNDAMENTAL else (ctx.verify_homography, ctx.verify_pairs_homography)
+    name = "fundamental" if FUNDAMENTAL else "homography"
+    print(f"verify_pairs_{name} against a loop of verify_{name}: best of 3 alternating rounds (min .. max), threshold {THRESHOLD}, refine 2")
+    print("| pairs | m | n_hyp | batch kernels | loop kernels | batch wall | loop wall | wall ratio | inliers |")
+    print("|---|---|---|---|---|---|---|---|---|")
+    faster = True
+    for P, m, n_hyp in ((72, 2000, 2048), (1056, 500, 1024)):
+        rng = np.random.default_rng(P)
+        lists = [(two_cameras if FUNDAMENTAL else planted)(m, rng) for _ in range(P)]
+
+        def run_batch():
+            t0 = time.perf_counter()
+            out = batch(lists, THRESHOLD, n_hyp, 0, 2)
+            return out, 1e3 * (time.perf_counter() - t0), ctx.last_kernel_ms()
+
+        def run_loop():
+            out, kernels = [], 0.0
+            t0 = time.perf_counter()
+            for src, dst in lists:
+                out.append(single(src, dst, THRESHOLD, n_hyp, 0, 2))
+                kernels += ctx.last_kernel_ms()
+            return out, 1e3 * (time.perf_counter() - t0), kernels
+
+        got, want = run_batch()[0], run_loop()[0]              # the warm-up of each side, and the comparison
+        for p, (g, w) in enumerate(zip(got, want)):
+            if not (np.array_equal(g[0].view(np.uint64), w[0].view(np.uint64)) and np.array_equal(g[1], w[1]) and g[2] == w[2]):
+                sys.exit(f"verify_bench: pair {p} of the batch differs from the single call")
+        b, l = [], []
+        for _ in range(3):
+            b.append(run_batch()[1:])
+            l.append(run_loop()[1:])
+        (bw, bk), (lw, lk) = (np.array(x).T for x in (b, l))
+        row = lambda a: f"{a.min():.3f} ms ({a.min():.3f} .. {a.max():.3f})"
+        print(f"| {P} | {m} | {n_hyp} | {row(bk)} | {row(lk)} | {row(bw)} | {row(lw)} | {lw.min() / bw.min():.1f}x | {sum(int(g[1].sum()) for g in got)} of {P * m} |")
+        faster = faster and bw.max() < lw.min()
+    print("the batch's slowest wall time is below the loop's fastest on every workload" if faster else "the batch did NOT beat the loop by more than the spread")
+    ctx.close()
+
+
+if PAIRS:
+    pairs_bench()
+    sys.exit(0)
 
 ctx = dlco.DescContext()
 rng = np.random.default_rng(0)
