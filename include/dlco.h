@@ -604,8 +604,9 @@ int dlco_desc_cross_sqdists(dlco_desc_ctx *ctx, const float *query_host, int64_t
  * n_pairs >= 2^31, seg[0] != 0, a decreasing seg, an image of 2^31 rows or more, seg[n_img] < 1, a pair index outside
  * [0, n_img), r outside 1 .. 1024; in the device forms ld < r, ld not a multiple of 4 floats (16 bytes on the byte line), a
  * table that is not 16-byte aligned.
- *   Out of scope: guided forms of the batch; a batched distance matrix; seg / pairs in device memory.
- *   In scope since: a batched verify, dlco_desc_verify_pairs_* below. ---- */
+ *   Out of scope: a batched distance matrix; seg / pairs in device memory.
+ *   In scope since: a batched verify, dlco_desc_verify_pairs_* below; guided forms of the batch,
+ * dlco_desc_match_pairs_guided* below. ---- */
 /* row0 [n_pairs + 1]; needs neither a context nor a device */
 int dlco_desc_match_pairs_rows(const int64_t *seg, int32_t n_img, const int32_t *pairs, int64_t n_pairs, int64_t *row0);
 /* the table on the host, [n_rows][r] dense; idx_host / sqdist_host [row0[n_pairs]][2].  The table is held in device memory
@@ -696,6 +697,41 @@ int dlco_desc_match_guided_epipolar_device(dlco_desc_ctx *ctx, const float *quer
 int dlco_desc_cross_sqdists_guided_epipolar(dlco_desc_ctx *ctx, const float *query_host, const float *query_xy_host, int64_t nq,
                                             const float *train_host, const float *train_xy_host, int64_t nt, int32_t r,
                                             const double *F, float threshold, int32_t f_side, float *out_host);
+/* ---- Guided matching of many pairs of images in one call: the last step of the two-view chain over an image set, after
+ * dlco_desc_match_pairs and dlco_desc_verify_pairs_*.  table, seg, pairs, the output layout and row0 are
+ * dlco_desc_match_pairs' own (dlco_desc_match_pairs_rows serves unchanged).  xy is ONE coordinate table with the rows of
+ * table: row i of the table is the keypoint (x, y) at xy + i * ldxy ([n_rows][2] dense in the host forms).  The model belongs
+ * to the PAIR: H (F) [n_pairs][9] row-major doubles, host memory in every form, as dlco_desc_verify_pairs_* writes H_out; the
+ * same image meets another matrix in every pair it appears in.  radius / threshold and the side are one per call.
+ *   Contract: pair p = (a, b) owns the rows row0[p] .. row0[p + 1] - 1, and those rows are, byte for byte, what
+ * dlco_desc_match_guided (dlco_desc_match_guided_epipolar) returns for query = image a with its coordinates, train = image b
+ * with its coordinates, the matrix H + 9 p and the same radius (threshold) and side.  Nothing depends on the other pairs,
+ * their order or the run.
+ *   An all-zero matrix is the verification's "no model": it is valid and admits nothing, the pair's rows are -1 / +inf in
+ * both columns (what the single call returns) and the pair launches nothing.  A pair with an empty train image is filled the
+ * same way; a pair with an empty query image owns no rows.
+ *   DLCO_ERR_INVALID, before the handle is used and with no output touched: whatever dlco_desc_match_pairs (_device) rejects,
+ * a null xy or matrix pointer, an entry of any of the n_pairs matrices that is not finite, a radius or threshold that is not
+ * finite or <= 0, a side other than 0 or 1, ldxy < 2 or an xy that is not 4-byte aligned (device forms).
+ *   csrc/match_batch.hpp states the plan: records are per pair, 32 bytes a row in one buffer per launch of at most 2^22 record
+ * rows.  Out of scope: the byte line; a batched guided distance matrix; seg, pairs or the matrices in device memory; a radius
+ * per pair; a choice between H and F. ---- */
+int dlco_desc_match_pairs_guided(dlco_desc_ctx *ctx, const float *table_host, const float *xy_host, const int64_t *seg,
+                                 int32_t n_img, const int32_t *pairs, int64_t n_pairs, int32_t r, const double *H, float radius,
+                                 int32_t h_side, int32_t *idx_host, float *sqdist_host);
+/* the same on a table in HBM, as dlco_desc_match_pairs_device takes it; xy_dev is device memory, 4-byte aligned, at a pitch of
+ * ldxy >= 2 floats: with pitch 4 the [n][4] keypoint rows dlco_desc_detect_device wrote pass as they are.  H is host memory */
+int dlco_desc_match_pairs_guided_device(dlco_desc_ctx *ctx, const float *table_dev, int64_t ld, const float *xy_dev, int64_t ldxy,
+                                        const int64_t *seg, int32_t n_img, const int32_t *pairs, int64_t n_pairs, int32_t r,
+                                        const double *H, float radius, int32_t h_side, int32_t *idx_dev, float *sqdist_dev);
+/* under fundamental matrices F [n_pairs][9]: every pair is what dlco_desc_match_guided_epipolar returns for it */
+int dlco_desc_match_pairs_guided_epipolar(dlco_desc_ctx *ctx, const float *table_host, const float *xy_host, const int64_t *seg,
+                                          int32_t n_img, const int32_t *pairs, int64_t n_pairs, int32_t r, const double *F,
+                                          float threshold, int32_t f_side, int32_t *idx_host, float *sqdist_host);
+int dlco_desc_match_pairs_guided_epipolar_device(dlco_desc_ctx *ctx, const float *table_dev, int64_t ld, const float *xy_dev,
+                                                 int64_t ldxy, const int64_t *seg, int32_t n_img, const int32_t *pairs,
+                                                 int64_t n_pairs, int32_t r, const double *F, float threshold, int32_t f_side,
+                                                 int32_t *idx_dev, float *sqdist_dev);
 /* ---- Eight-bit descriptors: a table of bytes is a quarter of the float one, and its distances are integers.
  *   The quantiser is a scale s > 0 and an offset o[r]; csrc/quant_rules.hpp states the rule.  One element:
  * t = y - o_k in float, v = t * s in float (two roundings, never an FMA), q = rintf(v) (half to even); the byte is 0 if v is

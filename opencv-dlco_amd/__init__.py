@@ -225,6 +225,11 @@ def load():
     L.dlco_desc_match_pairs_u8.argtypes = [vp, u8p, i64p, C.c_int32, i32p, i64, C.c_int32, i32p, i32p]
     L.dlco_desc_match_pairs_u8_device.argtypes = [vp, vp, i64, i64p, C.c_int32, i32p, i64, C.c_int32, vp, vp]
     L.dlco_desc_match_pairs_slices.argtypes = [vp, i64p, C.c_int32, i32p, i64, C.c_int32, i32p]
+    L.dlco_desc_match_pairs_guided.argtypes = [vp, f32p, f32p, i64p, C.c_int32, i32p, i64, C.c_int32, f64p, C.c_float, C.c_int32, i32p, f32p]
+    L.dlco_desc_match_pairs_guided_device.argtypes = [vp, vp, i64, vp, i64, i64p, C.c_int32, i32p, i64, C.c_int32, f64p, C.c_float, C.c_int32,
+                                                      vp, vp]
+    L.dlco_desc_match_pairs_guided_epipolar.argtypes = L.dlco_desc_match_pairs_guided.argtypes
+    L.dlco_desc_match_pairs_guided_epipolar_device.argtypes = L.dlco_desc_match_pairs_guided_device.argtypes
     L.dlco_desc_last_kernel_ms.argtypes = [vp]
     L.dlco_desc_last_kernel_ms.restype = C.c_double
     L.dlco_pr_last_error.restype = C.c_char_p
@@ -1313,6 +1318,52 @@ class DescContext:
         s, q = _seg_pairs(seg, pairs)
         self._ck(self.L.dlco_desc_match_pairs_u8_device(self.h, C.c_void_p(table_ptr), ld or r, _p(s, i64p), s.size - 1, _p(q, i32p), q.shape[0],
                                                         r, C.c_void_p(idx_ptr), C.c_void_p(d_ptr)))
+
+    # ---- guided matching of many pairs in one call: a matrix per pair (csrc/match_batch.hpp states the plan) ----
+    def _match_pairs_guided(self, call, tables, xys, pairs, M, radius, side):
+        tabs, cs = [_f32(t) for t in tables], [_f32(x) for x in xys]
+        assert tabs and len(cs) == len(tabs) and all(t.ndim == 2 and t.shape[1] == tabs[0].shape[1] for t in tabs)
+        assert all(x.shape == (t.shape[0], 2) for x, t in zip(cs, tabs))
+        seg = np.concatenate([[0], np.cumsum([t.shape[0] for t in tabs])]).astype(np.int64)
+        seg, q = _seg_pairs(seg, pairs)
+        m = np.ascontiguousarray(M, np.float64).reshape(-1, 9)
+        assert m.shape[0] == q.shape[0]
+        table, xy = np.ascontiguousarray(np.concatenate(tabs, axis=0)), np.ascontiguousarray(np.concatenate(cs, axis=0))
+        row0 = match_pairs_rows(seg, q)
+        idx, d = np.empty((row0[-1], 2), np.int32), np.empty((row0[-1], 2), np.float32)
+        self._ck(call(self.h, _p(table, f32p), _p(xy, f32p), _p(seg, i64p), seg.size - 1, _p(q, i32p), q.shape[0], table.shape[1],
+                      _p(m, C.POINTER(C.c_double)), radius, side, _p(idx, i32p), _p(d, f32p)))
+        return [(idx[row0[p]:row0[p + 1]], d[row0[p]:row0[p + 1]]) for p in range(q.shape[0])]
+
+    def match_pairs_guided(self, tables, xys, pairs, H, radius=6.0, h_side=0):
+        """match_pairs under a homography per pair: tables and pairs as match_pairs takes them, xys a list of [n_s, 2] keypoint
+        coordinates, one per table, H [n_pairs, 3, 3] (or [n_pairs, 9]) as verify_pairs_homography returns it.  Returns a list of
+        (idx, sqdist), one per pair, each byte for byte what match_guided(tables[a], xys[a], tables[b], xys[b], H[p], radius,
+        h_side) returns; an all-zero H[p] ("no model") or an empty train image gives -1 / +inf in both columns."""
+        return self._match_pairs_guided(self.L.dlco_desc_match_pairs_guided, tables, xys, pairs, H, radius, h_side)
+
+    def match_pairs_guided_epipolar(self, tables, xys, pairs, F, threshold=3.0, f_side=0):
+        """match_pairs under a fundamental matrix per pair: every pair is what match_guided_epipolar returns for it."""
+        return self._match_pairs_guided(self.L.dlco_desc_match_pairs_guided_epipolar, tables, xys, pairs, F, threshold, f_side)
+
+    def _match_pairs_guided_device(self, call, table_ptr, xy_ptr, seg, pairs, r, M, idx_ptr, d_ptr, radius, side, ld, ldxy):
+        s, q = _seg_pairs(seg, pairs)
+        m = np.ascontiguousarray(M, np.float64).reshape(-1, 9)
+        assert m.shape[0] == q.shape[0]
+        self._ck(call(self.h, C.c_void_p(table_ptr), ld or r, C.c_void_p(xy_ptr), ldxy, _p(s, i64p), s.size - 1, _p(q, i32p), q.shape[0], r,
+                      _p(m, C.POINTER(C.c_double)), radius, side, C.c_void_p(idx_ptr), C.c_void_p(d_ptr)))
+
+    def match_pairs_guided_device(self, table_ptr, xy_ptr, seg, pairs, r, H, idx_ptr, d_ptr, radius=6.0, h_side=0, ld=None, ldxy=2):
+        """match_pairs_guided on one table in device memory (row pitch ld floats, default r) and one coordinate table with the
+        same rows (pitch ldxy floats >= 2: 4 takes the keypoint rows detect_device wrote); H on the host; results
+        [match_pairs_rows(seg, pairs)[-1], 2] to device memory."""
+        self._match_pairs_guided_device(self.L.dlco_desc_match_pairs_guided_device, table_ptr, xy_ptr, seg, pairs, r, H, idx_ptr, d_ptr, radius,
+                                        h_side, ld, ldxy)
+
+    def match_pairs_guided_epipolar_device(self, table_ptr, xy_ptr, seg, pairs, r, F, idx_ptr, d_ptr, threshold=3.0, f_side=0, ld=None, ldxy=2):
+        """match_pairs_guided_epipolar on tables in device memory, pitches as match_pairs_guided_device."""
+        self._match_pairs_guided_device(self.L.dlco_desc_match_pairs_guided_epipolar_device, table_ptr, xy_ptr, seg, pairs, r, F, idx_ptr, d_ptr,
+                                        threshold, f_side, ld, ldxy)
 
     def match_pairs_slices(self, seg, pairs, u8=False):
         """The plan only: slices [n_pairs] int32 of train that each pair is cut into in such a call on this context's device

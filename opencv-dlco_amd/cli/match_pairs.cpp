@@ -1,6 +1,7 @@
 // match-pairs — nearest-neighbour matching of many pairs of descriptor tables in one library call, over libdlco.so.
 //
 //     match-pairs -pairs pairs_file -out dst [-u8] [-ratio f] [-cross] [-device n] desc_file_0 desc_file_1 ...
+//                 [-guided verify_pairs_out -kp kp_file_0 kp_file_1 ... [-radius f] [-model homography|fundamental]]
 //
 // Every desc_file holds the dataset "Descriptor" [n, r] f32 that `describe` writes (the r must agree; n may be 0: an image
 // without keypoints), pairs_file the dataset "Pairs" [P, 2] i32 of (query file, train file), numbers in the file list.
@@ -14,6 +15,14 @@
 // mutual check, for which the reversed pairs are appended to the same batch instead of making second calls.
 //   With -u8 the files hold "DescriptorU8" [n, r] u8 instead, the call is dlco_desc_match_pairs_u8 and the distances are
 // i32.  Files that carry a quantiser ("QuantScale", "QuantOffset") must all carry the same one, bit for bit.
+//   With -guided the call is dlco_desc_match_pairs_guided: every pair is matched again under its own model of a `verify-pairs`
+// output ("HomographyBits" [P,9], query image -> train image), among the train keypoints the model puts within -radius pixels
+// (default 6) of the query.  The output's "Pairs" must be the -pairs list, row for row; a pair without a model (an all-zero
+// matrix) is valid and gets -1 / +inf.  The files after -kp, up to the next option, hold "Keypoints" [n,4] f32 as `detect`
+// writes them, one per descriptor file in the same order and row for row its keypoints.  -cross runs the reversed pairs as a
+// second call with side 1 and the same matrices, as `match -guided -cross` does for one pair.  -model fundamental guides by
+// "FundamentalBits" of a `verify-pairs -model fundamental` output (dlco_desc_match_pairs_guided_epipolar, -radius its
+// threshold).  The datasets written are the same; per pair they are what `match -guided` writes.  There is no guided -u8.
 // A path that does not end in .h5/.hdf5 is a directory of .npy files with the same dataset names (dlco_io.hpp).
 #include "../../include/dlco.h"
 #include "dlco_io.hpp"
@@ -21,6 +30,7 @@
 #include "quant_io.hpp"
 
 #include <chrono>
+#include <cmath>
 #include <cstdlib>
 #include <cstring>
 #include <iostream>
@@ -45,9 +55,17 @@ template <> struct Line<uint8_t> {
                     int32_t *idx, int32_t *d) { return dlco_desc_match_pairs_u8(c, t, seg, n_img, pairs, n_pairs, r, idx, d); }
 };
 
+// -guided: the verify-pairs output, the keypoint files, the radius or threshold and the model
+struct Guided {
+    const char *verify_out = nullptr;
+    std::vector<const char *> kp;
+    float radius = 6.0f;
+    bool fundamental = false;
+};
+
 template <typename T>
 void run(const char *pairs_file, const std::vector<const char *> &files, const char *out, bool use_ratio, float ratio, bool cross, int device,
-         dlco_desc_ctx *&ctx)
+         dlco_desc_ctx *&ctx, const Guided *guided = nullptr)
 {
     using Dist = typename Line<T>::Dist;
     const size_t n_img = files.size();
@@ -94,8 +112,38 @@ void run(const char *pairs_file, const std::vector<const char *> &files, const c
         if (pairs[i] < 0 || (size_t)pairs[i] >= n_img)
             throw std::runtime_error(std::string(pairs_file) + ": pair " + std::to_string(i / 2) + " names file " + std::to_string(pairs[i]) + " of " +
                                      std::to_string(n_img));
+    // -guided: the coordinates of every row, and the matrix of every pair of a verify-pairs output on the same pairs
+    std::vector<float> xy;
+    std::vector<double> models;
+    if (guided) {
+        xy.resize((size_t)seg[n_img] * 2);
+        for (size_t f = 0; f < n_img; f++) {
+            std::vector<size_t> shape;
+            std::vector<float> kp;
+            dlco_io::read_dataset<float>(guided->kp[f], "Keypoints", shape, kp);
+            if (shape.size() != 2 || shape[1] != 4) throw std::runtime_error(std::string(guided->kp[f]) + ": Keypoints must be an [n, 4] table");
+            if ((int64_t)shape[0] != seg[f + 1] - seg[f])
+                throw std::runtime_error(std::string(guided->kp[f]) + ": " + std::to_string(shape[0]) + " keypoints against " +
+                                         std::to_string(seg[f + 1] - seg[f]) + " descriptors in " + files[f]);
+            for (size_t i = 0; i < shape[0]; i++) { xy[2 * ((size_t)seg[f] + i)] = kp[4 * i]; xy[2 * ((size_t)seg[f] + i) + 1] = kp[4 * i + 1]; }
+        }
+        std::vector<size_t> vs, bs;
+        std::vector<int32_t> vpairs;
+        std::vector<int64_t> bits;
+        dlco_io::read_dataset<int32_t>(guided->verify_out, "Pairs", vs, vpairs);
+        if (vs.size() != 2 || vs[0] != P || vs[1] != 2 || vpairs != pairs)
+            throw std::runtime_error(std::string(guided->verify_out) + ": its Pairs are not the pairs of " + pairs_file + ": the models belong to other pairs");
+        const char *name = guided->fundamental ? "FundamentalBits" : "HomographyBits";
+        dlco_io::read_dataset<int64_t>(guided->verify_out, name, bs, bits);
+        if (bs.size() != 2 || bs[0] != P || bs[1] != 9) throw std::runtime_error(std::string(guided->verify_out) + ": " + name + " must be a [P, 9] table");
+        models.resize(9 * P);
+        std::memcpy(models.data(), bits.data(), 9 * P * sizeof(double));
+        for (double v : models)
+            if (!std::isfinite(v)) throw std::runtime_error(std::string(guided->verify_out) + ": " + name + " holds a value that is not finite");
+    }
     printf("Tables: %zu, %lld x %zu%s\n", n_img, (long long)seg[n_img], r, Line<T>::tag);
     printf("Pairs: %zu\n", P);
+    if (guided) printf(guided->fundamental ? "Guided: fundamental, radius %g\n" : "Guided: radius %g\n", guided->radius);
 
     // -cross: the reversed pairs ride in the same batch, pair P + p is pair p swapped
     std::vector<int32_t> batch(pairs);
@@ -110,8 +158,24 @@ void run(const char *pairs_file, const std::vector<const char *> &files, const c
     const auto t0 = std::chrono::steady_clock::now();
     std::vector<int32_t> nearest((size_t)row0[B] * 2);
     std::vector<Dist> sqdist((size_t)row0[B] * 2);
-    if (Line<T>::call(ctx, table.data(), seg.data(), (int32_t)n_img, batch.data(), (int64_t)B, (int32_t)r, nearest.data(), sqdist.data()) != DLCO_OK)
-        throw std::runtime_error(dlco_desc_last_error(ctx));
+    double kernel_ms = 0.0;
+    if constexpr (std::is_same<T, float>::value) {
+        if (guided) {
+            // the pairs under side 0, then (-cross) the reversed pairs under side 1 and the same matrices: two calls, one output
+            const auto call = guided->fundamental ? dlco_desc_match_pairs_guided_epipolar : dlco_desc_match_pairs_guided;
+            for (size_t k = 0; k < B / P; k++) {
+                if (call(ctx, table.data(), xy.data(), seg.data(), (int32_t)n_img, batch.data() + 2 * P * k, (int64_t)P, (int32_t)r, models.data(),
+                         guided->radius, (int32_t)k, nearest.data() + 2 * row0[P * k], sqdist.data() + 2 * row0[P * k]) != DLCO_OK)
+                    throw std::runtime_error(dlco_desc_last_error(ctx));
+                kernel_ms += dlco_desc_last_kernel_ms(ctx);
+            }
+        }
+    }
+    if (!guided) {
+        if (Line<T>::call(ctx, table.data(), seg.data(), (int32_t)n_img, batch.data(), (int64_t)B, (int32_t)r, nearest.data(), sqdist.data()) != DLCO_OK)
+            throw std::runtime_error(dlco_desc_last_error(ctx));
+        kernel_ms = dlco_desc_last_kernel_ms(ctx);
+    }
     std::vector<int64_t> moff(P + 1, 0);
     std::vector<int32_t> matches, mp;
     std::vector<Dist> mdist, md;
@@ -135,7 +199,7 @@ void run(const char *pairs_file, const std::vector<const char *> &files, const c
     }
     const double sec = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
     printf("Matches: %zu / %lld\n", mdist.size(), (long long)row0[P]);
-    printf("Kernels: %.6f ms\n", dlco_desc_last_kernel_ms(ctx));
+    printf("Kernels: %.6f ms\n", kernel_ms);
     printf("Total: %.09f sec\n", sec);
 }
 }  // namespace
@@ -145,11 +209,21 @@ int main(int argc, char **argv)
     int device = 0;
     bool help = false, cross = false, use_ratio = false, u8 = false;
     float ratio = 1.0f;
-    const char *pairs_file = nullptr, *out = nullptr;
+    const char *pairs_file = nullptr, *out = nullptr, *model = nullptr;
     std::vector<const char *> files;
+    Guided guided;
+    bool kp_given = false;
     for (int i = 1; i < argc; i++) {
         if (argv[i][0] == '-') {
             const bool has_val = i + 1 < argc;
+            if (std::strcmp(argv[i], "-guided") == 0 && has_val && argv[i + 1][0] != '-') { guided.verify_out = argv[++i]; continue; }
+            if (std::strcmp(argv[i], "-kp") == 0) {            // the files up to the next option
+                kp_given = true;
+                while (i + 1 < argc && argv[i + 1][0] != '-') guided.kp.push_back(argv[++i]);
+                continue;
+            }
+            if (std::strcmp(argv[i], "-radius") == 0 && has_val) { guided.radius = (float)atof(argv[++i]); continue; }
+            if (std::strcmp(argv[i], "-model") == 0 && has_val) { model = argv[++i]; continue; }
             if (std::strcmp(argv[i], "-help") == 0) { help = true; continue; }
             if (std::strcmp(argv[i], "-pairs") == 0 && has_val) { pairs_file = argv[++i]; continue; }
             if (std::strcmp(argv[i], "-out") == 0 && has_val) { out = argv[++i]; continue; }
@@ -168,16 +242,38 @@ int main(int argc, char **argv)
         cout << "ERROR: -ratio must be in (0, 1]." << endl;
         help = true;
     }
+    guided.fundamental = model && std::strcmp(model, "fundamental") == 0;
+    if (model && !guided.fundamental && std::strcmp(model, "homography") != 0) {
+        cout << "ERROR: -model must be homography or fundamental." << endl;
+        help = true;
+    }
+    if ((model || kp_given) && !guided.verify_out) {
+        cout << "ERROR: -kp and -model need -guided." << endl;
+        help = true;
+    }
+    if (guided.verify_out && (guided.kp.empty() || guided.kp.size() != files.size())) {
+        cout << "ERROR: Invalid -guided option: it needs -kp with one keypoint file per descriptor file." << endl;
+        help = true;
+    }
+    if (guided.verify_out && u8) {
+        cout << "ERROR: -guided has no -u8 form." << endl;
+        help = true;
+    }
+    if (!(std::isfinite(guided.radius) && guided.radius > 0.0f)) {
+        cout << "ERROR: -radius must be finite and > 0." << endl;
+        help = true;
+    }
     if (help) {
         cout << endl;
         cout << "Usage: match-pairs -pairs pairs_file -out dst_h5_filename [-u8] [-ratio f] [-cross] [-device n] desc_file_0 desc_file_1 ..." << endl;
+        cout << "       [-guided verify_pairs_out -kp kp_file_0 kp_file_1 ... [-radius f] [-model homography|fundamental]]" << endl;
         cout << endl;
         return 1;
     }
     dlco_desc_ctx *ctx = nullptr;
     try {
         if (u8) run<uint8_t>(pairs_file, files, out, use_ratio, ratio, cross, device, ctx);
-        else run<float>(pairs_file, files, out, use_ratio, ratio, cross, device, ctx);
+        else run<float>(pairs_file, files, out, use_ratio, ratio, cross, device, ctx, guided.verify_out ? &guided : nullptr);
         dlco_desc_destroy(ctx);
     } catch (const std::exception &e) {
         if (ctx) dlco_desc_destroy(ctx);

@@ -39,7 +39,9 @@ constexpr int kChunk = 2048;            // patches per launch pair: 256 MB of Pa
 // guided forms of the float line the uploaded (x, y) of both tables and rec [n][4], the records of the side the homography
 // applies to (guided_rules.hpp): a launch's queries or all of train; for the epipolar guided forms (guided_epipolar_rules.hpp)
 // rec holds train's records and qrec a launch's queries'; for the batch forms (dlco_desc_match_pairs*) plan, the uploaded
-// entries of every launch and behind them the fill list (match_batch.hpp), train the one table and tnorm / qnorm its norms
+// entries of every launch and behind them the fill list (match_batch.hpp), train the one table and tnorm / qnorm its norms;
+// for the guided batch forms (dlco_desc_match_pairs_guided*) plan holds the guide offsets and the pairs' matrices behind the
+// fill list, txy the coordinates of the one table and rec the records of one launch
 template <typename Elem, typename Dist, typename Norm>
 struct MatchBufs {
     DevBuf<Elem> query, train;
@@ -262,7 +264,7 @@ struct FloatLine {
     static void top2_batch(const Elem *table, long ld, int r, const Norm *, const Norm *tnorm, const match_batch::Entry *ent, int n_ent, long wgs,
                            long merge_wgs, int32_t *idx, Dist *sqdist, void *part, hipStream_t s)
     {
-        match_top2_batch(table, ld, r, tnorm, ent, n_ent, wgs, merge_wgs, idx, sqdist, part, s);
+        match_top2_batch(table, ld, r, tnorm, ent, n_ent, wgs, merge_wgs, idx, sqdist, part, nullptr, nullptr, nullptr, s);
     }
 };
 struct ByteLine {
@@ -438,46 +440,97 @@ bool match_pairs_args_ok(const int64_t *seg, int32_t n_img, const int32_t *pairs
     return true;
 }
 
+// The geometry of a guided batch (dlco_desc_match_pairs_guided*), an optional argument of the float line's batch path: xy, the
+// coordinates of the rows of the one table in device memory at a pitch of ldxy floats, M [n_pairs][9] the pairs' matrices on
+// the host, and the model, squared radius or threshold and side of every pair.
+struct PairsGeometry {
+    const float *xy; long ldxy;
+    const double *M;
+    double t2;
+    int side;
+    int model;
+};
+
+// the plan's Guide of a guided batch: none[p] is set for an all-zero matrix, "no model", which admits nothing
+match_batch::Guide pairs_guide(const PairsGeometry &geo, int64_t n_pairs, std::vector<uint8_t> &none)
+{
+    none.assign((size_t)n_pairs, 0);
+    for (int64_t p = 0; p < n_pairs; p++)
+        none[(size_t)p] = std::all_of(geo.M + 9 * p, geo.M + 9 * p + 9, [](double v) { return v == 0.0; }) ? 1 : 0;
+    match_batch::Guide g;
+    g.no_model = none.data();
+    g.both_sides = geo.model == kGuideFundamental;
+    g.side = geo.side;
+    return g;
+}
+
 // the table in device memory in, device results out: the norms of every row once, the fill rows, then the launches of the
-// plan one after another (they share the partial buffer); returns the kernels' time
+// plan one after another (they share the partial buffer); returns the kernels' time.  geo: the guided form (pl was planned
+// with pairs_guide): the guide offsets and the matrices go up behind the plan, and every launch forms its records first
 template <typename L>
 double match_pairs_on_device(dlco_desc_ctx *c, const typename L::Elem *table, long ld, const int64_t *seg, int32_t n_img,
-                             const match_batch::Plan &pl, int r, int32_t *idx, typename L::Dist *sqdist)
+                             const match_batch::Plan &pl, int r, int32_t *idx, typename L::Dist *sqdist, const PairsGeometry *geo = nullptr,
+                             int64_t n_pairs = 0)
 {
     auto &b = L::bufs(c);
+    DLCO_CHECK(!geo || L::guided, DLCO_ERR_INVALID, "guided matching exists for the float line only");
     const int64_t n_rows = seg[n_img];
     const size_t ent_bytes = pl.entries.size() * sizeof(match_batch::Entry), fill_bytes = pl.fills.size() * sizeof(match_batch::Fill);
+    const size_t off_bytes = geo ? pl.guide.size() * sizeof(match_batch::GuideOff) : 0, mat_bytes = geo ? (size_t)n_pairs * 9 * sizeof(double) : 0;
     b.tnorm.alloc((size_t)n_rows);
     if (L::two_norms) b.qnorm.alloc((size_t)n_rows);
-    b.plan.alloc(ent_bytes + fill_bytes);
+    b.plan.alloc(ent_bytes + fill_bytes + off_bytes + mat_bytes);
     if (pl.max_parts > 0) b.part.alloc((size_t)pl.max_parts * 4);
+    if (geo && pl.max_rec_rows > 0) b.rec.alloc((size_t)pl.max_rec_rows * 4);
     if (ent_bytes) DLCO_HIP(hipMemcpyAsync(b.plan.p, pl.entries.data(), ent_bytes, hipMemcpyHostToDevice, c->stream));
     if (fill_bytes) DLCO_HIP(hipMemcpyAsync(b.plan.p + ent_bytes, pl.fills.data(), fill_bytes, hipMemcpyHostToDevice, c->stream));
+    if (off_bytes) DLCO_HIP(hipMemcpyAsync(b.plan.p + ent_bytes + fill_bytes, pl.guide.data(), off_bytes, hipMemcpyHostToDevice, c->stream));
+    if (mat_bytes) DLCO_HIP(hipMemcpyAsync(b.plan.p + ent_bytes + fill_bytes + off_bytes, geo->M, mat_bytes, hipMemcpyHostToDevice, c->stream));
     const auto *ent = reinterpret_cast<const match_batch::Entry *>(b.plan.p);
     const auto *fill = reinterpret_cast<const match_batch::Fill *>(b.plan.p + ent_bytes);
+    const auto *off = reinterpret_cast<const match_batch::GuideOff *>(b.plan.p + ent_bytes + fill_bytes);
+    const auto *mat = reinterpret_cast<const double *>(b.plan.p + ent_bytes + fill_bytes + off_bytes);
     EventPair ev;
     return timed_ms(c, ev, [&] {
         L::train_norms(table, ld, n_rows, r, b.tnorm.p, c->stream);
         if (L::two_norms) L::query_norms(table, ld, n_rows, r, b.qnorm.p, c->stream);
         match_fill(fill, (int)pl.fills.size(), pl.fill_rows, L::none, idx, sqdist, c->stream);
-        for (const match_batch::Launch &la : pl.launches)
+        for (const match_batch::Launch &la : pl.launches) {
+            if constexpr (L::guided) {
+                if (geo) {
+                    MatchGuide g;
+                    g.rec = b.rec.p; g.xy = geo->xy; g.ldxy = geo->ldxy; g.side = geo->side; g.model = geo->model; g.t2 = geo->t2;
+                    g.off = off + la.e0;
+                    match_records_batch(geo->xy, geo->ldxy, ent + la.e0, off + la.e0, (int)la.n, la.rec_rows, mat, geo->t2, geo->side, geo->model,
+                                        b.rec.p, c->stream);
+                    match_top2_batch(table, ld, r, b.tnorm.p, ent + la.e0, (int)la.n, la.wgs, la.merge_wgs, idx, sqdist, b.part.p, &g,
+                                     pl.entries.data() + la.e0, pl.guide.data() + la.e0, c->stream);
+                    continue;
+                }
+            }
             L::top2_batch(table, ld, r, b.qnorm.p, b.tnorm.p, ent + la.e0, (int)la.n, la.wgs, la.merge_wgs, idx, sqdist, b.part.p, c->stream);
+        }
     });
 }
 
+// geo: the guided form, its xy in device memory
 template <typename L>
 void match_pairs_device(dlco_desc_ctx *c, const typename L::Elem *table_dev, long ld, const int64_t *seg, int32_t n_img, const int32_t *pairs,
-                        int64_t n_pairs, int r, int32_t *idx_dev, typename L::Dist *sqdist_dev)
+                        int64_t n_pairs, int r, int32_t *idx_dev, typename L::Dist *sqdist_dev, const PairsGeometry *geo = nullptr)
 {
     DLCO_HIP(hipSetDevice(c->device));
-    const match_batch::Plan pl = match_batch::plan(L::shape, seg, pairs, n_pairs, c->n_cu);
-    c->last_ms = match_pairs_on_device<L>(c, table_dev, ld, seg, n_img, pl, r, idx_dev, sqdist_dev);
+    std::vector<uint8_t> none;
+    match_batch::Guide guide;
+    if (geo) guide = pairs_guide(*geo, n_pairs, none);
+    const match_batch::Plan pl = match_batch::plan(L::shape, seg, pairs, n_pairs, c->n_cu, geo ? &guide : nullptr);
+    c->last_ms = match_pairs_on_device<L>(c, table_dev, ld, seg, n_img, pl, r, idx_dev, sqdist_dev, geo, n_pairs);
 }
 
-// the host form: the table goes up once, padded to the 16-byte row pitch, the outputs of every pair come down once
+// the host form: the table goes up once, padded to the 16-byte row pitch, the outputs of every pair come down once; geo: the
+// guided form, its xy [n_rows][2] on the host, which goes up with the table
 template <typename L>
 void match_pairs_host(dlco_desc_ctx *c, const typename L::Elem *table_host, const int64_t *seg, int32_t n_img, const int32_t *pairs,
-                      int64_t n_pairs, int r, int32_t *idx_host, typename L::Dist *sqdist_host)
+                      int64_t n_pairs, int r, int32_t *idx_host, typename L::Dist *sqdist_host, const PairsGeometry *geo = nullptr)
 {
     using Elem = typename L::Elem;
     using Dist = typename L::Dist;
@@ -486,18 +539,27 @@ void match_pairs_host(dlco_desc_ctx *c, const typename L::Elem *table_host, cons
     constexpr long per = kRowPitchBytes / sizeof(Elem);
     const long ld = (r + per - 1) / per * per;
     const int64_t n_rows = seg[n_img];
-    const match_batch::Plan pl = match_batch::plan(L::shape, seg, pairs, n_pairs, c->n_cu);
+    std::vector<uint8_t> none;
+    match_batch::Guide guide;
+    if (geo) guide = pairs_guide(*geo, n_pairs, none);
+    const match_batch::Plan pl = match_batch::plan(L::shape, seg, pairs, n_pairs, c->n_cu, geo ? &guide : nullptr);
     const int64_t out_rows = pl.row0[(size_t)n_pairs];
     try {
         b.train.alloc((size_t)n_rows * ld);
         b.idx.alloc((size_t)out_rows * 2);
         b.sqdist.alloc((size_t)out_rows * 2);
+        if (geo) b.txy.alloc((size_t)n_rows * 2);
     } catch (const Error &e) {
         throw Error(DLCO_ERR_HIP, std::string(L::name) + "_pairs: the table and the results do not fit in device memory: " + e.what());
     }
     DLCO_HIP(hipMemcpy2DAsync(b.train.p, (size_t)ld * sizeof(Elem), table_host, (size_t)r * sizeof(Elem), (size_t)r * sizeof(Elem), (size_t)n_rows,
                               hipMemcpyHostToDevice, c->stream));
-    c->last_ms = match_pairs_on_device<L>(c, b.train.p, ld, seg, n_img, pl, r, b.idx.p, b.sqdist.p);
+    PairsGeometry dev_geo{};                               // the same geometry on the uploaded coordinates
+    if (geo) {
+        dev_geo = PairsGeometry{b.txy.p, 2, geo->M, geo->t2, geo->side, geo->model};
+        DLCO_HIP(hipMemcpyAsync(b.txy.p, geo->xy, (size_t)n_rows * 2 * sizeof(float), hipMemcpyHostToDevice, c->stream));
+    }
+    c->last_ms = match_pairs_on_device<L>(c, b.train.p, ld, seg, n_img, pl, r, b.idx.p, b.sqdist.p, geo ? &dev_geo : nullptr, n_pairs);
     if (out_rows > 0) {
         DLCO_HIP(hipMemcpyAsync(idx_host, b.idx.p, (size_t)out_rows * 2 * sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
         DLCO_HIP(hipMemcpyAsync(sqdist_host, b.sqdist.p, (size_t)out_rows * 2 * sizeof(Dist), hipMemcpyDeviceToHost, c->stream));
@@ -1548,6 +1610,77 @@ int dlco_desc_cross_sqdists_guided_epipolar(dlco_desc_ctx *c, const float *query
         const Geometry geo{query_xy_host, 2, train_xy_host, 2, F, verify_rules::threshold_sq(threshold), f_side, kGuideFundamental};
         match_host<FloatLine>(c, query_host, nq, train_host, nt, r, nullptr, nullptr, out_host, &geo);
     });
+}
+
+// ---- guided matching of many pairs in one call: the batch path with a PairsGeometry; a matrix per pair, one radius or
+// threshold and one side per call; the byte line has no such form -------------------------------------------------------------
+namespace {
+static bool pairs_guided_args_ok(const float *xy, const double *M, int64_t n_pairs, float radius, int32_t side)
+{
+    if (!xy || !M || !std::isfinite(radius) || !(radius > 0.0f) || (side != 0 && side != 1)) return false;
+    for (int64_t i = 0; i < 9 * n_pairs; i++)
+        if (!std::isfinite(M[i])) return false;
+    return true;
+}
+
+static int match_pairs_guided_call(dlco_desc_ctx *c, const float *table_host, const float *xy_host, const int64_t *seg, int32_t n_img,
+                            const int32_t *pairs, int64_t n_pairs, int32_t r, const double *M, float radius, int32_t side, int model,
+                            int32_t *idx_host, float *sqdist_host)
+{
+    if (!c || !table_host || !idx_host || !sqdist_host || r < 1 || r > 1024 || !match_pairs_args_ok(seg, n_img, pairs, n_pairs))
+        return DLCO_ERR_INVALID;
+    if (!pairs_guided_args_ok(xy_host, M, n_pairs, radius, side)) return DLCO_ERR_INVALID;
+    return guarded(c, [&] {
+        const PairsGeometry geo{xy_host, 2, M, verify_rules::threshold_sq(radius), side, model};
+        match_pairs_host<FloatLine>(c, table_host, seg, n_img, pairs, n_pairs, r, idx_host, sqdist_host, &geo);
+    });
+}
+
+static int match_pairs_guided_device_call(dlco_desc_ctx *c, const float *table_dev, int64_t ld, const float *xy_dev, int64_t ldxy, const int64_t *seg,
+                                   int32_t n_img, const int32_t *pairs, int64_t n_pairs, int32_t r, const double *M, float radius,
+                                   int32_t side, int model, int32_t *idx_dev, float *sqdist_dev)
+{
+    if (!c || !table_dev || !idx_dev || !sqdist_dev || r < 1 || r > 1024 || !match_pairs_args_ok(seg, n_img, pairs, n_pairs))
+        return DLCO_ERR_INVALID;
+    if (ld < r || ld % 4 != 0 || (uintptr_t)table_dev % 16 != 0) return DLCO_ERR_INVALID;                  // 16-byte rows
+    if (!pairs_guided_args_ok(xy_dev, M, n_pairs, radius, side) || ldxy < 2 || (uintptr_t)xy_dev % 4 != 0) return DLCO_ERR_INVALID;
+    return guarded(c, [&] {
+        const PairsGeometry geo{xy_dev, (long)ldxy, M, verify_rules::threshold_sq(radius), side, model};
+        match_pairs_device<FloatLine>(c, table_dev, (long)ld, seg, n_img, pairs, n_pairs, r, idx_dev, sqdist_dev, &geo);
+    });
+}
+}  // namespace
+
+int dlco_desc_match_pairs_guided(dlco_desc_ctx *c, const float *table_host, const float *xy_host, const int64_t *seg, int32_t n_img,
+                                 const int32_t *pairs, int64_t n_pairs, int32_t r, const double *H, float radius, int32_t h_side,
+                                 int32_t *idx_host, float *sqdist_host)
+{
+    return match_pairs_guided_call(c, table_host, xy_host, seg, n_img, pairs, n_pairs, r, H, radius, h_side, kGuideHomography, idx_host,
+                                   sqdist_host);
+}
+
+int dlco_desc_match_pairs_guided_device(dlco_desc_ctx *c, const float *table_dev, int64_t ld, const float *xy_dev, int64_t ldxy, const int64_t *seg,
+                                        int32_t n_img, const int32_t *pairs, int64_t n_pairs, int32_t r, const double *H, float radius,
+                                        int32_t h_side, int32_t *idx_dev, float *sqdist_dev)
+{
+    return match_pairs_guided_device_call(c, table_dev, ld, xy_dev, ldxy, seg, n_img, pairs, n_pairs, r, H, radius, h_side, kGuideHomography,
+                                          idx_dev, sqdist_dev);
+}
+
+int dlco_desc_match_pairs_guided_epipolar(dlco_desc_ctx *c, const float *table_host, const float *xy_host, const int64_t *seg, int32_t n_img,
+                                          const int32_t *pairs, int64_t n_pairs, int32_t r, const double *F, float threshold, int32_t f_side,
+                                          int32_t *idx_host, float *sqdist_host)
+{
+    return match_pairs_guided_call(c, table_host, xy_host, seg, n_img, pairs, n_pairs, r, F, threshold, f_side, kGuideFundamental, idx_host,
+                                   sqdist_host);
+}
+
+int dlco_desc_match_pairs_guided_epipolar_device(dlco_desc_ctx *c, const float *table_dev, int64_t ld, const float *xy_dev, int64_t ldxy,
+                                                 const int64_t *seg, int32_t n_img, const int32_t *pairs, int64_t n_pairs, int32_t r,
+                                                 const double *F, float threshold, int32_t f_side, int32_t *idx_dev, float *sqdist_dev)
+{
+    return match_pairs_guided_device_call(c, table_dev, ld, xy_dev, ldxy, seg, n_img, pairs, n_pairs, r, F, threshold, f_side,
+                                          kGuideFundamental, idx_dev, sqdist_dev);
 }
 
 // H_all [n_hyp][9] and count [n_hyp] of every hypothesis of the rule: what dlco_desc_verify_homography selects from

@@ -568,8 +568,10 @@ void match_norms(const float *x, long ld, long n, int r, double *norm, hipStream
 // launch's queries' (match_epi_records), the src records of the side F applies to (side 0: the queries, side 1: train) and
 // the dst records of the other; t2 is the squared threshold, which the pair predicate takes itself.
 enum { kGuideHomography = 0, kGuideFundamental = 1 };
+// The guided batch (match_batch.hpp): rec is the record buffer of a launch (match_records_batch), off [n_ent] the record rows of
+// its entries and xy the coordinates of the whole table; qrec is unused.
 struct MatchGuide { const double *rec = nullptr; const float *xy = nullptr; long ldxy = 0; int side = 0; int model = kGuideHomography;
-                    const double *qrec = nullptr; double t2 = 0.0; };
+                    const double *qrec = nullptr; double t2 = 0.0; const match_batch::GuideOff *off = nullptr; };
 void match_records(const float *xy, long ld, long n, const double H[9], double t2, double *rec, hipStream_t s);
 void match_epi_records(const float *xy, long ld, long n, const double F[9], int dst_side, double *rec, hipStream_t s);
 void match_top2(const float *query, long ldq, int nq, const float *train, long ldt, int nt, int r, const double *qnorm, const double *tnorm,
@@ -577,7 +579,10 @@ void match_top2(const float *query, long ldq, int nq, const float *train, long l
 // the batch forms (match_batch.hpp states the plan): one launch of the plan over the one table [.][ld] and the norms of all its
 // rows, ent [n_ent] in device memory; and the rows of the pairs with an empty train image, `none` the bits of "no candidate"
 void match_top2_batch(const float *table, long ld, int r, const double *norm, const match_batch::Entry *ent, int n_ent, long wgs, long merge_wgs,
-                      int32_t *idx, float *sqdist, void *part, hipStream_t s);
+                      int32_t *idx, float *sqdist, void *part, const MatchGuide *guide, const match_batch::Entry *ent_host,
+                      const match_batch::GuideOff *off_host, hipStream_t s);
+void match_records_batch(const float *xy, long ldxy, const match_batch::Entry *ent, const match_batch::GuideOff *off, int n_ent, long rows,
+                         const double *M, double t2, int side, int model, double *rec, hipStream_t s);
 void match_u8_top2_batch(const uint8_t *table, long ld, int r, const int32_t *qnorm, const int32_t *tneg, const match_batch::Entry *ent, int n_ent,
                          long wgs, long merge_wgs, int32_t *idx, int32_t *sqdist, void *part, hipStream_t s);
 void match_fill(const match_batch::Fill *fill, int n_fill, long rows, int32_t none, int32_t *idx, void *sqdist, hipStream_t s);

@@ -30,6 +30,9 @@
 //   match_top2_kernel<.., BATCH>, match_merge_batch_kernel, match_fill_kernel   the batch forms (dlco_desc_match_pairs, the plan:
 //                         match_batch.hpp): many (query image, train image) pairs over one segmented table in one 1-D
 //                         launch; a workgroup finds its pair in the uploaded plan and runs the plain form's tile loop
+//   match_records_batch_kernel, match_top2_kernel<.., GUIDED, BATCH>   the guided batch (dlco_desc_match_pairs_guided*): every
+//                         pair has a matrix of its own, so a launch forms the records of its entries into one buffer, a
+//                         lane per record row, and the tile loop's batch prologue binds an entry's records and coordinates
 //
 // The key is a total order and the slices hold disjoint train rows, so the result does not depend on the grouping.
 // An entry's accumulation is one chain of MFMAs over k in an order fixed by r: it depends neither on where the query
@@ -107,6 +110,9 @@ __device__ __forceinline__ int batch_entry_of(const match_batch::Entry *__restri
 // entry's partials (part stays null when the entry has one slice), its query block and its slice.  Tiles are counted from
 // the slice's first row, which need not be tile-aligned in the table; the rows at and beyond jend belong to the next image
 // (or lie beyond the table) and are never read: the loads clamp to jbeg.  The loop below is the plain form's.
+//   BATCH with GUIDED 1 .. 4 (dlco_desc_match_pairs_guided*): geometry belongs to the pair, so g.rec is the launch's record
+// buffer, g.off the record rows of every entry (match_batch::GuideOff, indexed like ent) and g.xy the coordinates of the whole
+// table; the prologue rebinds the records to the entry's own and the coordinates to the rows of the image that brings them.
 template <bool STORE, bool MULTI, int GUIDED, bool BATCH = false>
 __global__ __launch_bounds__(MTH) void match_top2_kernel(const float *__restrict__ query, long ldq, int nq, const float *__restrict__ train, long ldt,
                                                          int nt, int r, const double *__restrict__ qnorm, const double *__restrict__ tnorm,
@@ -115,9 +121,19 @@ __global__ __launch_bounds__(MTH) void match_top2_kernel(const float *__restrict
                                                          const match_batch::Entry *__restrict__ ent, int n_ent)
 {
     unsigned qblk = blockIdx.x, slice = blockIdx.y;
+    const double *grec = g.rec, *gqrec = g.qrec;           // GUIDED: the records and the coordinates the loop reads
+    const float *gxy = g.xy;
     if constexpr (BATCH) {
         const int wg = (int)blockIdx.x;
-        const match_batch::Entry e = ent[batch_entry_of(ent, n_ent, wg, [](const match_batch::Entry &x) { return x.wg0; })];
+        const int ei = batch_entry_of(ent, n_ent, wg, [](const match_batch::Entry &x) { return x.wg0; });
+        const match_batch::Entry e = ent[ei];
+        if constexpr (GUIDED != 0) {
+            const match_batch::GuideOff o = g.off[ei];
+            const double *qr = g.rec + 4 * o.rec0, *tr = qr + 4 * (long)o.nqrec;
+            grec = GUIDED == 1 ? qr : tr;
+            gqrec = qr;
+            gxy = g.xy + (GUIDED == 1 ? e.t0 : e.q0) * g.ldxy;
+        }
         const unsigned w = (unsigned)(wg - e.wg0);
         slice = w / (unsigned)e.qblocks;
         qblk = w - slice * (unsigned)e.qblocks;
@@ -175,11 +191,11 @@ __global__ __launch_bounds__(MTH) void match_top2_kernel(const float *__restrict
         const long js = jn < jend ? jn : (long)jbeg;
         rtn = tnorm[js];
         if constexpr (GUIDED == 1) {
-            const float *p = g.xy + js * g.ldxy;
+            const float *p = gxy + js * g.ldxy;
             rg[0] = (double)p[0]; rg[1] = (double)p[1];
         }
         if constexpr (GUIDED >= 2) {
-            const f64x2 a = *reinterpret_cast<const f64x2 *>(g.rec + 4 * js), b = *reinterpret_cast<const f64x2 *>(g.rec + 4 * js + 2);
+            const f64x2 a = *reinterpret_cast<const f64x2 *>(grec + 4 * js), b = *reinterpret_cast<const f64x2 *>(grec + 4 * js + 2);
             rg[0] = a[0]; rg[1] = a[1]; rg[2] = b[0]; rg[3] = b[1];
         }
     };
@@ -243,11 +259,11 @@ __global__ __launch_bounds__(MTH) void match_top2_kernel(const float *__restrict
             const long row = (long)qblk * MQ + tid;
             const long rs = row < nq ? row : 0;
             if constexpr (GUIDED == 1 || GUIDED >= 3) {
-                const double *qr = GUIDED == 1 ? g.rec : g.qrec;
+                const double *qr = GUIDED == 1 ? grec : gqrec;
                 *reinterpret_cast<f64x2 *>(&Qg[tid * 4]) = *reinterpret_cast<const f64x2 *>(qr + 4 * rs);
                 *reinterpret_cast<f64x2 *>(&Qg[tid * 4 + 2]) = *reinterpret_cast<const f64x2 *>(qr + 4 * rs + 2);
             } else {
-                const float *p = g.xy + rs * g.ldxy;
+                const float *p = gxy + rs * g.ldxy;
                 *reinterpret_cast<f64x2 *>(&Qg[tid * 2]) = f64x2{(double)p[0], (double)p[1]};
             }
         }
@@ -516,6 +532,47 @@ __global__ __launch_bounds__(256) void match_epi_records_kernel(const float *__r
     *reinterpret_cast<f64x2 *>(rec + 4 * i + 2) = hi;
 }
 
+// The records of one launch of a guided batch (match_batch.hpp): one lane per record row of the launch, which is also the
+// row's place in rec.  The lane finds its entry by its row among the entries' first record rows, as match_fill_kernel finds
+// its fill; rows below nqrec are the entry's queries, the others its train image.  M [n_pairs][9] holds every pair's
+// matrix and xy the coordinates of the whole table.  EPI: the side F applies to (side 0: the queries) gets src records and
+// the other dst records; else every row is on the side H applies to.
+template <bool EPI>
+__global__ __launch_bounds__(256) void match_records_batch_kernel(const float *__restrict__ xy, long ld, const match_batch::Entry *__restrict__ ent,
+                                                                  const match_batch::GuideOff *__restrict__ off, int n_ent, long rows,
+                                                                  const double *__restrict__ M, double t2, int side, double *__restrict__ rec)
+{
+    const long i = (long)blockIdx.x * 256 + threadIdx.x;
+    if (i >= rows) return;
+    int lo = 0, hi = n_ent;
+    while (hi - lo > 1) {
+        const int mid = (lo + hi) >> 1;
+        if (off[mid].rec0 <= i) lo = mid; else hi = mid;
+    }
+    const long k = i - off[lo].rec0;
+    const bool is_query = k < off[lo].nqrec;
+    const long row = is_query ? ent[lo].q0 + k : ent[lo].t0 + (k - off[lo].nqrec);
+    double h[9];
+#pragma unroll
+    for (int e = 0; e < 9; e++) h[e] = M[9 * (long)ent[lo].pair + e];
+    const double x = (double)xy[row * ld], y = (double)xy[row * ld + 1];
+    f64x2 a, b;
+    if constexpr (EPI) {
+        if (is_query == (side == 0)) {
+            const guided_epipolar::SrcRec s = guided_epipolar::src_record(h, x, y);
+            a = f64x2{s.l0, s.l1}; b = f64x2{s.l2, s.L};
+        } else {
+            const guided_epipolar::DstRec d = guided_epipolar::dst_record(h, x, y);
+            a = f64x2{d.u, d.v}; b = f64x2{d.A, d.B};
+        }
+    } else {
+        const guided_rules::Rec r = guided_rules::record(h, x, y, t2);
+        a = f64x2{r.X, r.Y}; b = f64x2{r.W, r.T};
+    }
+    *reinterpret_cast<f64x2 *>(rec + 4 * i) = a;
+    *reinterpret_cast<f64x2 *>(rec + 4 * i + 2) = b;
+}
+
 constexpr int NTH = 256;               // four rows per workgroup, one wave each
 
 __global__ __launch_bounds__(NTH) void match_norms_kernel(const float *__restrict__ x, long ld, long n, int r, double *__restrict__ norm)
@@ -593,18 +650,57 @@ void match_top2(const float *query, long ldq, int nq, const float *train, long l
     }
 }
 
+// The records of one launch of a guided batch: rows record rows into rec, by the launch's entries and their record rows
+void match_records_batch(const float *xy, long ldxy, const match_batch::Entry *ent, const match_batch::GuideOff *off, int n_ent, long rows,
+                         const double *M, double t2, int side, int model, double *rec, hipStream_t s)
+{
+    if (n_ent <= 0 || rows <= 0) return;
+    const dim3 grid((unsigned)((rows + 255) / 256));
+    if (model == kGuideFundamental)
+        hipLaunchKernelGGL(match_records_batch_kernel<true>, grid, dim3(256), 0, s, xy, ldxy, ent, off, n_ent, rows, M, t2, side, rec);
+    else
+        hipLaunchKernelGGL(match_records_batch_kernel<false>, grid, dim3(256), 0, s, xy, ldxy, ent, off, n_ent, rows, M, t2, side, rec);
+    DLCO_HIP(hipGetLastError());
+}
+
 // One launch of a batched match (match_batch.hpp): table [.][ld] with its norms, the launch's n_ent entries in device memory,
 // wgs workgroups of the tile loop, merge_wgs of the merge (0: every entry has one slice); idx / sqdist are the call's.
+// guide: nullptr, or the geometry of the guided batch: rec the launch's record buffer, already written
+// (match_records_batch), off its entries' record rows, xy / ldxy the coordinates of the whole table; ent_host / off_host
+// are the same entries and record rows in host memory.
+//   The homography of side 1 (GUIDED = 2) has no batch form beyond r = 128: with the batch prologue its MULTI loop needs 10
+// spilled registers.  Such a launch is served entry by entry with the single call's kernel on the entry's rows, norms,
+// records, coordinates and partials, which returns the same bytes: the plan, the norms and the records are still the batch's.
 void match_top2_batch(const float *table, long ld, int r, const double *norm, const match_batch::Entry *ent, int n_ent, long wgs, long merge_wgs,
-                      int32_t *idx, float *sqdist, void *part, hipStream_t s)
+                      int32_t *idx, float *sqdist, void *part, const MatchGuide *guide, const match_batch::Entry *ent_host,
+                      const match_batch::GuideOff *off_host, hipStream_t s)
 {
     if (n_ent <= 0 || wgs <= 0) return;
     i32x4 *pp = static_cast<i32x4 *>(part);
     const dim3 grid((unsigned)wgs);
-#define DLCO_MATCH_BATCH_LAUNCH(MU)                                                                                                   \
-    hipLaunchKernelGGL((match_top2_kernel<false, MU, 0, true>), grid, dim3(MTH), 0, s, table, ld, 0, nullptr, 0L, 0, r, norm, nullptr, 0,   \
-                       idx, sqdist, pp, nullptr, MatchGuide{}, ent, n_ent)
-    if (r > KC) DLCO_MATCH_BATCH_LAUNCH(true); else DLCO_MATCH_BATCH_LAUNCH(false);
+    const MatchGuide g = guide ? *guide : MatchGuide{};
+    if (guide && r > KC && g.model == kGuideHomography && g.side != 0) {
+        for (int k = 0; k < n_ent; k++) {
+            const match_batch::Entry &e = ent_host[k];
+            MatchGuide ge = g;
+            ge.rec = g.rec + 4 * (off_host[k].rec0 + off_host[k].nqrec);
+            ge.xy = g.xy + e.q0 * g.ldxy;
+            ge.off = nullptr;
+            match_top2(table + e.q0 * ld, ld, e.nq, table + e.t0 * ld, ld, e.nt, r, norm + e.q0, norm + e.t0, e.tiles_per_slice, idx + 2 * e.out0,
+                       sqdist + 2 * e.out0, pp + e.part0, nullptr, &ge, s);
+        }
+        return;
+    }
+#define DLCO_MATCH_BATCH_LAUNCH(MU, GU)                                                                                               \
+    hipLaunchKernelGGL((match_top2_kernel<false, MU, GU, true>), grid, dim3(MTH), 0, s, table, ld, 0, nullptr, 0L, 0, r, norm, nullptr, 0,  \
+                       idx, sqdist, pp, nullptr, g, ent, n_ent)
+#define DLCO_MATCH_BATCH_FORM(GU) do { if (r > KC) DLCO_MATCH_BATCH_LAUNCH(true, GU); else DLCO_MATCH_BATCH_LAUNCH(false, GU); } while (0)
+    if (!guide) DLCO_MATCH_BATCH_FORM(0);
+    else if (g.model == kGuideHomography && g.side == 0) DLCO_MATCH_BATCH_FORM(1);
+    else if (g.model == kGuideHomography) DLCO_MATCH_BATCH_LAUNCH(false, 2);       // r <= KC: see above
+    else if (g.side == 0) DLCO_MATCH_BATCH_FORM(3);
+    else DLCO_MATCH_BATCH_FORM(4);
+#undef DLCO_MATCH_BATCH_FORM
 #undef DLCO_MATCH_BATCH_LAUNCH
     DLCO_HIP(hipGetLastError());
     if (merge_wgs > 0) {

@@ -27,7 +27,16 @@ batch replaces.  The sets: a, 9 images of 2048 rows, all 72 ordered pairs (also 
 three rounds that alternate the batch and the loop in one process.  For each the kernel time (last_kernel_ms, summed over the
 loop's calls) and the wall time from sync to sync; the figure is the best of the three rounds, the loop's spread its largest
 minus its smallest round.  The line adds the floor 2 sum(nq nt) r / 78.6 TFLOP/s (5.0 POP/s with --u8), the batch's share of
-it, and whether the two routes returned the same bytes."""
+it, and whether the two routes returned the same bytes.
+
+With --pairs --guided (--pairs --guided-epipolar) the guided batch is measured: dlco_desc_match_pairs_guided_device (_epipolar)
+on sets a and b at r = 128 against a loop of dlco_desc_match_guided_device (_epipolar) calls over the same pairs, with the plain
+batch of the same run beside both.  The keypoints are those of --guided, uniform in a square of side 8 sqrt(n) per image; every
+pair has a matrix of its own, the mild homography of --guided (the F of --guided-epipolar) behind a shift of up to 2 px that
+depends on the pair; radius 12, threshold 2; both sides.  One warm-up of the three, a check that the batch and the loop returned
+the same bytes (the tool stops if they did not), then three rounds that alternate them.  The line shows kernels and wall of
+each with their rounds, loop / batch, guided batch / plain batch, and the gate: the batch's slowest round below the loop's
+fastest."""
 import importlib, os, sys
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch
@@ -129,8 +138,86 @@ def pairs_bench():
     ctx.close()
 
 
+def pairs_guided_bench():
+    import time
+    import numpy as np
+    sets = [("a", [2048] * 9, 128), ("b", [512] * 33, 128)]
+    ctx = dlco.DescContext()
+    gen = torch.Generator(device="cuda:0").manual_seed(0)
+    name_of = "match_pairs_guided_epipolar" if EPI else "match_pairs_guided"
+    for name, sizes, r in sets:
+        n_img, n = len(sizes), sizes[0]
+        seg = np.concatenate([[0], np.cumsum(sizes)]).astype(np.int64)
+        pairs = np.array([(a, b) for a in range(n_img) for b in range(n_img) if a != b], np.int32)
+        row0 = dlco.match_pairs_rows(seg, pairs)
+        X = torch.empty((int(seg[-1]), r), dtype=torch.float32, device="cuda:0").normal_(0, 0.25, generator=gen)
+        S = 8.0 * n ** 0.5
+        xy = torch.rand((int(seg[-1]), 2), device="cuda:0", generator=gen) * S
+        H = np.array([[0.98, -0.05, 0.03 * S], [0.04, 1.02, -0.02 * S], [0.02 / S, -0.01 / S, 1.0]])
+        M = []
+        for p in range(len(pairs)):                        # a matrix per pair: the model behind a small shift of the source image
+            m = H @ np.array([[1.0, 0.0, 2.0 * np.cos(p)], [0.0, 1.0, 2.0 * np.sin(p)], [0.0, 0.0, 1.0]])
+            if EPI:
+                m = np.array([[0.0, -1.0, 0.4 * S], [1.0, 0.0, -3.0 * S], [-0.4 * S, 3.0 * S, 0.0]]) @ m
+                m = m / np.abs(m).max()
+            M.append(m)
+        M = np.stack(M)
+        t = 2.0 if EPI else 12.0
+        out = [(torch.empty((int(row0[-1]), 2), dtype=torch.int32, device="cuda:0"), torch.empty((int(row0[-1]), 2), dtype=torch.float32, device="cuda:0"))
+               for _ in range(3)]
+        torch.cuda.synchronize()
+        many = ctx.match_pairs_guided_epipolar_device if EPI else ctx.match_pairs_guided_device
+        one = ctx.match_guided_epipolar_device if EPI else ctx.match_guided_device
+        for side in (0, 1):
+            def batch():
+                many(X.data_ptr(), xy.data_ptr(), seg, pairs, r, M, out[0][0].data_ptr(), out[0][1].data_ptr(), t, side, ld=r, ldxy=2)
+                return ctx.last_kernel_ms()
+
+            def loop():
+                ms = 0.0
+                for p, (a, b) in enumerate(pairs):
+                    one(X.data_ptr() + int(seg[a]) * r * 4, xy.data_ptr() + int(seg[a]) * 8, sizes[a], X.data_ptr() + int(seg[b]) * r * 4,
+                        xy.data_ptr() + int(seg[b]) * 8, sizes[b], r, M[p], out[1][0].data_ptr() + int(row0[p]) * 8, out[1][1].data_ptr() + int(row0[p]) * 8,
+                        t, side)
+                    ms += ctx.last_kernel_ms()
+                return ms
+
+            def plain():
+                ctx.match_pairs_device(X.data_ptr(), seg, pairs, r, out[2][0].data_ptr(), out[2][1].data_ptr(), ld=r)
+                return ctx.last_kernel_ms()
+
+            def timed(f):
+                torch.cuda.synchronize()
+                t0 = time.perf_counter()
+                ms = f()
+                torch.cuda.synchronize()
+                return ms, 1e3 * (time.perf_counter() - t0)
+
+            batch(), loop(), plain()
+            torch.cuda.synchronize()
+            same = bool(torch.equal(out[0][0], out[1][0]) and torch.equal(out[0][1].view(torch.int32), out[1][1].view(torch.int32)))
+            if not same:
+                sys.exit(f"{name_of} set {name} side {side}: the batch and the loop of single calls returned different bytes")
+            two = 100 * float((out[0][0][:, 1] >= 0).float().mean())
+            rounds = [(timed(batch), timed(loop), timed(plain)) for _ in range(3)]
+            col = lambda k, w: [x[k][w] for x in rounds]
+            fmt = lambda m: " ".join("%.3f" % v for v in m)
+            bk, bw, lk, lw, pk, pw = col(0, 0), col(0, 1), col(1, 0), col(1, 1), col(2, 0), col(2, 1)
+            print(f"{name_of} set {name}: {n_img} images of {n} rows, {len(pairs)} pairs, r {r}, side {side}: batch kernels {min(bk):.3f} ms (rounds "
+                  f"{fmt(bk)}), wall {min(bw):.3f} ms (rounds {fmt(bw)}); loop kernels {min(lk):.3f} ms (rounds {fmt(lk)}), wall {min(lw):.3f} ms (rounds "
+                  f"{fmt(lw)}); plain batch kernels {min(pk):.3f} ms (rounds {fmt(pk)}), wall {min(pw):.3f} ms (rounds {fmt(pw)}); loop / batch kernels "
+                  f"{min(lk) / min(bk):.2f}, wall {min(lw) / min(bw):.2f}; guided batch / plain batch kernels {min(bk) / min(pk):.3f}; same bytes: {same}; "
+                  f"two admitted rows for {two:.1f} % of the queries; the batch's slowest round below the loop's fastest: kernels {max(bk) < min(lk)}, "
+                  f"wall {max(bw) < min(lw)}", flush=True)
+        del X, xy, out
+    ctx.close()
+
+
 if PAIRS:
-    pairs_bench()
+    if GUIDED or EPI:
+        pairs_guided_bench()
+    else:
+        pairs_bench()
     sys.exit(0)
 
 ctx = dlco.DescContext()
