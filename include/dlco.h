@@ -830,8 +830,8 @@ int  dlco_desc_verify_fundamental(dlco_desc_ctx *ctx, const float *src_xy_host, 
 int  dlco_desc_verify_fundamental_hypotheses(dlco_desc_ctx *ctx, const float *src_xy_host, const float *dst_xy_host, int64_t m,
                                              float threshold, int32_t n_hyp, uint64_t seed, double *F_all_host, int32_t *count_host);
 /* ---- Verifying many pairs in one call.  Every caller of dlco_desc_match_pairs verifies each matched pair next, and a call per
- * pair is launch-bound: three launches of a few dozen workgroups and several stream synchronisations for a few thousand
- * matches.  Here the match lists of all pairs are ONE list: src_xy, dst_xy [M][2] float, host memory; moff [n_pairs + 1] int64,
+ * pair is launch-bound: four launches of a few dozen workgroups and a stream synchronisation per refit round for a few
+ * thousand matches.  Here the match lists of all pairs are ONE list: src_xy, dst_xy [M][2] float, host memory; moff [n_pairs + 1] int64,
  * host memory, moff[0] = 0, non-decreasing, pair p owns the matches [moff[p], moff[p + 1]) and M = moff[n_pairs] (match-pairs'
  * MatchOffsets).  csrc/verify_batch.hpp states how a call is cut into launches; a launch carries the workgroups of many pairs,
  * and the refit rounds of all pairs still refining share one mask launch per round.
@@ -871,9 +871,9 @@ int  dlco_desc_verify_pairs_launches(const int64_t *moff, int64_t n_pairs, int32
  * the whole table, the fill of the pairs with an empty train image, the tile loop and the merge of every launch); the _u8 forms of describe add their quantising kernel; after a detect call the
  * detector's kernels (the integral image when the call formed it, the octaves, the selection; detect_oriented adds the
  * orientation kernel); after an orient call the orientation kernel and the integral image when the call formed it; after a
- * verify call the verify kernels (hypotheses, scoring, selection, of either model; verify_homography and verify_fundamental add
- * the mask kernel of the best model and of every refit round); after a verify_pairs call every kernel of the call (the
- * hypotheses and the scoring of every launch; verify_pairs_homography and verify_pairs_fundamental add the selection, the mask
+ * verify call the verify kernels, of either model, as after a verify_pairs call of one pair, which is what a verify call
+ * runs; after a verify_pairs call every kernel of the call (the hypotheses and the scoring of every launch; the model forms,
+ * verify_homography, verify_fundamental, verify_pairs_homography and verify_pairs_fundamental, add the selection, the mask
  * of the best models and the mask launch of every lockstep refit round) */
 double dlco_desc_last_kernel_ms(const dlco_desc_ctx *ctx);
 

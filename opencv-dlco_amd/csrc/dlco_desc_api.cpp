@@ -98,10 +98,10 @@ struct dlco_desc_ctx {
     DevBuf<int64_t> o_vec;
     DevBuf<uint8_t> o_status;
     double o_ms = 0.0;
-    // verification (dlco_desc_verify_*, either model): the uploaded matches, every hypothesis and its count, the selection
-    // key, the mask of one model and its count; buffers of their own, like the matchers'.  The batch forms
-    // (dlco_desc_verify_pairs_*) hold one launch of verify_batch.hpp's plan in the same buffers, a slot per entry, and add
-    // v_plan, the uploaded entries and behind them the active list, and v_cur, the matrix the mask kernel scores per entry
+    // verification (dlco_desc_verify_*, either model; a single call is a launch of one entry): one launch of
+    // verify_batch.hpp's plan, a slot per entry.  The uploaded matches, every hypothesis and its count, the selection key,
+    // v_cur, the matrix the mask kernel scores per entry, the trial mask and its count, and v_plan, the uploaded entries and
+    // behind them the active list; buffers of their own, like the matchers'
     DevBuf<float> v_src, v_dst;
     DevBuf<double> v_H, v_cur;
     DevBuf<int32_t> v_count, v_n;
@@ -569,109 +569,23 @@ void match_pairs_host(dlco_desc_ctx *c, const typename L::Elem *table_host, cons
 
 // ---- verification: a homography (verify_rules.hpp) or a fundamental matrix (epipolar_rules.hpp) between the two sides of
 // a match list, both in kernels_verify.hip; one host path over the rule header's Model (verify_rules::Homography,
-// epipolar_rules::Fundamental): the kernels of its hypotheses, of their counts and of the mask of one model, its refit round
-// on the host; Model::kSample matches make a sample -----------------------------------------------------------------------
+// epipolar_rules::Fundamental) and over the match lists of many pairs as one segmented list, by the plan of verify_batch.hpp.
+// A launch carries the workgroups of many pairs, the selection leaves the winning matrices on the device for the first mask,
+// and the refit runs in lockstep: the host forms a round's models, one mask launch scores those of every pair still refining.
+// The single calls (dlco_desc_verify_homography and its kin) are this path with one pair, moff = {0, m}: a launch of one
+// entry.  Model::kSample matches make a sample -------------------------------------------------------------------------------
 using verify_rules::Homography;
 using epipolar_rules::Fundamental;
+namespace vb = verify_batch;
 
+// what a single call checks of its list before anything else; a list below the sample is invalid there, where the _pairs
+// forms answer "no model" for it
 template <typename Model>
 bool verify_args_ok(const float *src, const float *dst, int64_t m, float threshold, int32_t n_hyp)
 {
     return src && dst && m >= Model::kSample && m < ((int64_t)1 << 31) && std::isfinite(threshold) && threshold > 0.0f && n_hyp >= 1 &&
            n_hyp <= verify_rules::kMaxHyp;
 }
-
-// the matches to the device, every hypothesis and its count there; returns the kernels' milliseconds
-template <typename Model>
-double verify_all(dlco_desc_ctx *c, const EventPair &ev, const float *src_host, const float *dst_host, int64_t m, double t2,
-                  int32_t n_hyp, uint64_t seed)
-{
-    DLCO_HIP(hipSetDevice(c->device));
-    c->v_src.alloc((size_t)m * 2); c->v_dst.alloc((size_t)m * 2);
-    c->v_H.alloc((size_t)n_hyp * 9); c->v_count.alloc((size_t)n_hyp);
-    c->v_key.alloc(1); c->v_n.alloc(1);
-    DLCO_HIP(hipMemcpyAsync(c->v_src.p, src_host, (size_t)m * 2 * sizeof(float), hipMemcpyHostToDevice, c->stream));
-    DLCO_HIP(hipMemcpyAsync(c->v_dst.p, dst_host, (size_t)m * 2 * sizeof(float), hipMemcpyHostToDevice, c->stream));
-    DLCO_HIP(hipMemsetAsync(c->v_count.p, 0, (size_t)n_hyp * sizeof(int32_t), c->stream));
-    return timed_ms(c, ev, [&] {
-        verify_hypotheses<Model>(c->v_src.p, c->v_dst.p, m, seed, n_hyp, c->v_H.p, c->stream);
-        verify_score<Model>(c->v_src.p, c->v_dst.p, m, c->v_H.p, n_hyp, t2, c->v_count.p, c->stream);
-        verify_select(c->v_count.p, n_hyp, c->v_key.p, c->stream);
-    });
-}
-
-// mask [m] on the host and the count of H over the uploaded matches; adds the kernel's time to *ms
-template <typename Model>
-int64_t verify_score_one(dlco_desc_ctx *c, const EventPair &ev, int64_t m, const double *H, double t2, uint8_t *mask_host,
-                         double *ms)
-{
-    int32_t n = 0;
-    c->v_mask.alloc((size_t)m);
-    DLCO_HIP(hipMemsetAsync(c->v_n.p, 0, sizeof(int32_t), c->stream));
-    *ms += timed_ms(c, ev, [&] { verify_mask<Model>(c->v_src.p, c->v_dst.p, m, H, t2, c->v_mask.p, c->v_n.p, c->stream); }, [&] {
-        DLCO_HIP(hipMemcpyAsync(mask_host, c->v_mask.p, (size_t)m, hipMemcpyDeviceToHost, c->stream));
-        DLCO_HIP(hipMemcpyAsync(&n, c->v_n.p, sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
-    });
-    return n;
-}
-
-// every hypothesis of the model and its count, to the host
-template <typename Model>
-int verify_hypotheses_call(dlco_desc_ctx *c, const float *src_xy_host, const float *dst_xy_host, int64_t m, float threshold,
-                           int32_t n_hyp, uint64_t seed, double *M_all_host, int32_t *count_host)
-{
-    if (!c || !M_all_host || !count_host || !verify_args_ok<Model>(src_xy_host, dst_xy_host, m, threshold, n_hyp)) return DLCO_ERR_INVALID;
-    return guarded(c, [&] {
-        EventPair ev;
-        c->last_ms = verify_all<Model>(c, ev, src_xy_host, dst_xy_host, m, verify_rules::threshold_sq(threshold), n_hyp, seed);
-        DLCO_HIP(hipMemcpyAsync(M_all_host, c->v_H.p, (size_t)n_hyp * 9 * sizeof(double), hipMemcpyDeviceToHost, c->stream));
-        DLCO_HIP(hipMemcpyAsync(count_host, c->v_count.p, (size_t)n_hyp * sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
-        sync(c);
-    });
-}
-
-// the best model, its mask and the refit: a round's model is formed on the host, the mask kernel scores it
-template <typename Model>
-int verify_model_call(dlco_desc_ctx *c, const float *src_xy_host, const float *dst_xy_host, int64_t m, float threshold,
-                      int32_t n_hyp, uint64_t seed, int32_t refine, double *M_out, uint8_t *inlier_host, int64_t *n_inliers, int32_t *best_hyp)
-{
-    if (!c || !M_out || !n_inliers || refine < 0 || refine > verify_rules::kMaxRefine ||
-        !verify_args_ok<Model>(src_xy_host, dst_xy_host, m, threshold, n_hyp))
-        return DLCO_ERR_INVALID;
-    return guarded(c, [&] {
-        namespace vr = verify_rules;
-        const double t2 = vr::threshold_sq(threshold);
-        EventPair ev;
-        double ms = verify_all<Model>(c, ev, src_xy_host, dst_xy_host, m, t2, n_hyp, seed);
-        uint64_t key = 0;
-        DLCO_HIP(hipMemcpyAsync(&key, c->v_key.p, sizeof key, hipMemcpyDeviceToHost, c->stream));
-        sync(c);
-        double M[9] = {0};
-        std::vector<uint8_t> mask((size_t)m, 0);
-        int64_t count = 0;
-        int32_t best = -1;
-        if (vr::key_count(key) > 0) {
-            best = vr::key_hyp(key);
-            DLCO_HIP(hipMemcpyAsync(M, c->v_H.p + 9 * (size_t)best, sizeof M, hipMemcpyDeviceToHost, c->stream));
-            sync(c);
-            count = verify_score_one<Model>(c, ev, m, M, t2, mask.data(), &ms);
-            vr::refit_rounds(m, refine, M, mask.data(), count,
-                             [&](const uint8_t *cur, double *Mn) { return Model::refit_round(src_xy_host, dst_xy_host, m, cur, Mn); },
-                             [&](const double *Mn, uint8_t *trial) { return verify_score_one<Model>(c, ev, m, Mn, t2, trial, &ms); }, nullptr);
-        }
-        std::memcpy(M_out, M, sizeof M);
-        if (inlier_host) std::memcpy(inlier_host, mask.data(), (size_t)m);
-        *n_inliers = count;
-        if (best_hyp) *best_hyp = best;
-        c->last_ms = ms;
-    });
-}
-
-// ---- the batch forms (dlco_desc_verify_pairs_*): the match lists of many pairs as one segmented list, by the plan of
-// verify_batch.hpp.  The same buffers, rule headers and acceptance rule as above; what differs is that a launch carries the
-// workgroups of many pairs, that the selection leaves the winning matrices on the device for the first mask, and that the
-// refit runs in lockstep: one mask launch scores a round's models of every pair still refining. ----------------------------
-namespace vb = verify_batch;
 
 template <typename Model>
 bool verify_pairs_args_ok(const float *src, const float *dst, const int64_t *moff, int64_t n_pairs, float threshold, int32_t n_hyp)
@@ -705,7 +619,7 @@ VerifyLaunch verify_pairs_upload(dlco_desc_ctx *c, const vb::Plan &pl, const vb:
     return VerifyLaunch{ent_host, reinterpret_cast<const vb::Entry *>(c->v_plan.p), reinterpret_cast<vb::Active *>(c->v_plan.p + ent_bytes), la.n, la.matches};
 }
 
-// every hypothesis of every pair and its count, to the host; a pair without an entry keeps its zeros
+// every hypothesis of every pair and its count, to the host; a pair without an entry gets zeros
 template <typename Model>
 int verify_pairs_hypotheses_call(dlco_desc_ctx *c, const float *src_xy_host, const float *dst_xy_host, const int64_t *moff, int64_t n_pairs,
                                  float threshold, int32_t n_hyp, uint64_t seed, double *M_all_host, int32_t *count_host)
@@ -716,10 +630,12 @@ int verify_pairs_hypotheses_call(dlco_desc_ctx *c, const float *src_xy_host, con
         DLCO_HIP(hipSetDevice(c->device));
         const double t2 = verify_rules::threshold_sq(threshold);
         const vb::Plan pl = vb::plan(moff, n_pairs, n_hyp, Model::kSample);
-        std::memset(M_all_host, 0, (size_t)n_pairs * n_hyp * 9 * sizeof(double));
-        std::memset(count_host, 0, (size_t)n_pairs * n_hyp * sizeof(int32_t));
-        std::vector<double> M_all((size_t)pl.max_hyps * 9);
-        std::vector<int32_t> count((size_t)pl.max_hyps);
+        const size_t nh = (size_t)n_hyp;
+        for (int64_t p = 0; p < n_pairs; p++) {
+            if (pl.launch_of_pair[(size_t)p] >= 0) continue;
+            std::memset(M_all_host + (size_t)p * nh * 9, 0, nh * 9 * sizeof(double));
+            std::memset(count_host + (size_t)p * nh, 0, nh * sizeof(int32_t));
+        }
         EventPair ev;
         double ms = 0.0;
         for (const vb::Launch &la : pl.launches) {
@@ -728,14 +644,14 @@ int verify_pairs_hypotheses_call(dlco_desc_ctx *c, const float *src_xy_host, con
                 verify_pairs_hypotheses<Model>(c->v_src.p, c->v_dst.p, v.ent, v.n, seed, n_hyp, c->v_H.p, c->stream);
                 verify_pairs_score<Model>(c->v_src.p, c->v_dst.p, v.ent, v.n, la.score_wgs, c->v_H.p, n_hyp, t2, c->v_count.p, c->stream);
             }, [&] {
-                DLCO_HIP(hipMemcpyAsync(M_all.data(), c->v_H.p, (size_t)la.hyps * 9 * sizeof(double), hipMemcpyDeviceToHost, c->stream));
-                DLCO_HIP(hipMemcpyAsync(count.data(), c->v_count.p, (size_t)la.hyps * sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
+                // entries [e, r) whose pairs are consecutive own one range of the caller's arrays: their slots go straight there
+                for (int64_t e = 0, r; e < v.n; e = r) {
+                    for (r = e + 1; r < v.n && v.ent_host[r].pair == v.ent_host[r - 1].pair + 1; r++) {}
+                    const size_t p = (size_t)v.ent_host[e].pair, run = (size_t)(r - e) * nh;
+                    DLCO_HIP(hipMemcpyAsync(M_all_host + p * nh * 9, c->v_H.p + (size_t)e * nh * 9, run * 9 * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+                    DLCO_HIP(hipMemcpyAsync(count_host + p * nh, c->v_count.p + (size_t)e * nh, run * sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
+                }
             });
-            for (int64_t e = 0; e < v.n; e++) {
-                const size_t p = (size_t)v.ent_host[e].pair;
-                std::memcpy(M_all_host + p * n_hyp * 9, M_all.data() + (size_t)e * n_hyp * 9, (size_t)n_hyp * 9 * sizeof(double));
-                std::memcpy(count_host + p * n_hyp, count.data() + (size_t)e * n_hyp, (size_t)n_hyp * sizeof(int32_t));
-            }
         }
         c->last_ms = ms;
     });
@@ -1683,11 +1599,15 @@ int dlco_desc_match_pairs_guided_epipolar_device(dlco_desc_ctx *c, const float *
                                           kGuideFundamental, idx_dev, sqdist_dev);
 }
 
+// The four single calls are the _pairs forms below with one pair, moff = {0, m}, after their own check of the list: their
+// outputs are the batch's arrays for one pair.
 // H_all [n_hyp][9] and count [n_hyp] of every hypothesis of the rule: what dlco_desc_verify_homography selects from
 int dlco_desc_verify_hypotheses(dlco_desc_ctx *c, const float *src_xy_host, const float *dst_xy_host, int64_t m, float threshold, int32_t n_hyp,
                                 uint64_t seed, double *H_all_host, int32_t *count_host)
 {
-    return verify_hypotheses_call<Homography>(c, src_xy_host, dst_xy_host, m, threshold, n_hyp, seed, H_all_host, count_host);
+    if (!verify_args_ok<Homography>(src_xy_host, dst_xy_host, m, threshold, n_hyp)) return DLCO_ERR_INVALID;
+    const int64_t moff[2] = {0, m};
+    return verify_pairs_hypotheses_call<Homography>(c, src_xy_host, dst_xy_host, moff, 1, threshold, n_hyp, seed, H_all_host, count_host);
 }
 
 // H [9] row-major, the inlier mask [m] (may be NULL), its count and the winning hypothesis (may be NULL); no model is no
@@ -1696,20 +1616,28 @@ int dlco_desc_verify_hypotheses(dlco_desc_ctx *c, const float *src_xy_host, cons
 int dlco_desc_verify_homography(dlco_desc_ctx *c, const float *src_xy_host, const float *dst_xy_host, int64_t m, float threshold, int32_t n_hyp,
                                 uint64_t seed, int32_t refine, double *H_out, uint8_t *inlier_host, int64_t *n_inliers, int32_t *best_hyp)
 {
-    return verify_model_call<Homography>(c, src_xy_host, dst_xy_host, m, threshold, n_hyp, seed, refine, H_out, inlier_host, n_inliers, best_hyp);
+    if (!verify_args_ok<Homography>(src_xy_host, dst_xy_host, m, threshold, n_hyp)) return DLCO_ERR_INVALID;
+    const int64_t moff[2] = {0, m};
+    return verify_pairs_model_call<Homography>(c, src_xy_host, dst_xy_host, moff, 1, threshold, n_hyp, seed, refine, H_out, inlier_host, n_inliers,
+                                                  best_hyp);
 }
 
 // the same two calls for a fundamental matrix F, x'^T F x = 0 (epipolar_rules.hpp), with m >= 8
 int dlco_desc_verify_fundamental_hypotheses(dlco_desc_ctx *c, const float *src_xy_host, const float *dst_xy_host, int64_t m, float threshold,
                                             int32_t n_hyp, uint64_t seed, double *F_all_host, int32_t *count_host)
 {
-    return verify_hypotheses_call<Fundamental>(c, src_xy_host, dst_xy_host, m, threshold, n_hyp, seed, F_all_host, count_host);
+    if (!verify_args_ok<Fundamental>(src_xy_host, dst_xy_host, m, threshold, n_hyp)) return DLCO_ERR_INVALID;
+    const int64_t moff[2] = {0, m};
+    return verify_pairs_hypotheses_call<Fundamental>(c, src_xy_host, dst_xy_host, moff, 1, threshold, n_hyp, seed, F_all_host, count_host);
 }
 
 int dlco_desc_verify_fundamental(dlco_desc_ctx *c, const float *src_xy_host, const float *dst_xy_host, int64_t m, float threshold, int32_t n_hyp,
                                  uint64_t seed, int32_t refine, double *F_out, uint8_t *inlier_host, int64_t *n_inliers, int32_t *best_hyp)
 {
-    return verify_model_call<Fundamental>(c, src_xy_host, dst_xy_host, m, threshold, n_hyp, seed, refine, F_out, inlier_host, n_inliers, best_hyp);
+    if (!verify_args_ok<Fundamental>(src_xy_host, dst_xy_host, m, threshold, n_hyp)) return DLCO_ERR_INVALID;
+    const int64_t moff[2] = {0, m};
+    return verify_pairs_model_call<Fundamental>(c, src_xy_host, dst_xy_host, moff, 1, threshold, n_hyp, seed, refine, F_out, inlier_host, n_inliers,
+                                                   best_hyp);
 }
 
 // the four calls over the match lists of many pairs as one list cut by moff [n_pairs + 1]: pair p's answers are the single
@@ -1867,9 +1795,9 @@ int dlco_desc_cross_sqdists_u8(dlco_desc_ctx *c, const uint8_t *query_u8, int64_
 // the guided forms the record kernel); the _u8
 // forms of describe add their quantising kernel; after an orient call the orientation kernel and the integral image when the
 // call formed it; after a detect call the detector's kernels (the integral image when the call
-// formed it, the octaves, the selection); after a verify call the verify kernels (hypotheses, scoring, selection, and for
-// verify_homography and verify_fundamental the mask kernel of the best model and of every refit round); after a
-// verify_pairs call every kernel of every launch of the call, the mask launches of the lockstep refit rounds included
+// formed it, the octaves, the selection); after a verify or verify_pairs call every kernel of every launch of the call: for
+// the _hypotheses forms the hypotheses and the scoring, for the model forms these, the selection, the mask of the best models
+// and the mask launches of the lockstep refit rounds
 double dlco_desc_last_kernel_ms(const dlco_desc_ctx *c) { return c ? c->last_ms : 0.0; }
 
 }  // extern "C"

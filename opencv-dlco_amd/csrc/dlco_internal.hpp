@@ -610,17 +610,9 @@ void orient_keypoints(const uint32_t *S, int W, int H, const float *kp, int64_t 
 
 // verification (kernels_verify.hip): the matches src, dst [m][2] in device memory, 8-byte aligned.  Model is
 // verify_rules::Homography (the rule is verify_rules.hpp) or epipolar_rules::Fundamental (epipolar_rules.hpp), the two that
-// kernels_verify.hip instantiates.  M_all [n_hyp][9] of every hypothesis; count [n_hyp] += their inliers (the caller zeroes
-// it); *best = the largest selection key; mask [m] of the host's M [9] and *count += its inliers
-template <typename Model>
-void verify_hypotheses(const float *src, const float *dst, int64_t m, uint64_t seed, int n_hyp, double *M_all, hipStream_t s);
-template <typename Model>
-void verify_score(const float *src, const float *dst, int64_t m, const double *M_all, int n_hyp, double t2, int32_t *count, hipStream_t s);
-void verify_select(const int32_t *count, int n_hyp, uint64_t *best, hipStream_t s);
-template <typename Model>
-void verify_mask(const float *src, const float *dst, int64_t m, const double *M, double t2, uint8_t *mask, int32_t *count, hipStream_t s);
-// the same steps for one launch of verify_batch.hpp's plan (dlco_desc_verify_pairs_*): ent [n_ent] and the launch's matches in
-// device memory, slot e of M_all [.][n_hyp][9], count [.][n_hyp], best, M_cur [.][9] and n belongs to the entry at position e.
+// kernels_verify.hip instantiates.  The steps of one launch of verify_batch.hpp's plan (a single call's launch has one entry):
+// ent [n_ent] and the launch's matches in device memory, slot e of M_all [.][n_hyp][9], count [.][n_hyp], best, M_cur [.][9]
+// and n belongs to the entry at position e.  M_all of every hypothesis; count += their inliers (the caller zeroes it);
 // best [e] = the largest key of entry e and M_cur [e] its matrix (zero: no model); the mask kernel scores M_cur [entry] for
 // the entries of active [n_active] (mask_wgs workgroups) into mask at the entry's matches and n [entry] (the caller zeroes it)
 template <typename Model>

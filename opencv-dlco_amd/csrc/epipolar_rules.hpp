@@ -52,7 +52,8 @@
 //
 // Selection.  verify_rules::select_key, unchanged; a best count of 0: no model.
 //
-// Refit, on the host only (refit_round; the loop is verify_rules::refit_rounds).  At most `refine` rounds; a round runs on the
+// Refit, on the host only (refit_round; a round's acceptance is verify_rules::refit_step, the loop the library's lockstep one
+// and, in the CPU frame verify_host, verify_rules::refit_rounds).  At most `refine` rounds; a round runs on the
 // inliers of the current model in ascending match index and is rejected when there are fewer than 8:
 //   verify_rules::hartley on each side; a normalised point is ((x - cx) s, (y - cy) s).
 //   N = sum a a^T, 9 x 9, a the row above of the normalised match, N[p][q] = N[p][q] + a[p] a[q] in index order.

@@ -1,36 +1,32 @@
-// kernels_verify.hip — geometric verification of a match list against a two-view model: the homography
-// (dlco_desc_verify_homography, dlco_desc_verify_hypotheses; verify_rules::Homography) or the fundamental matrix
-// (dlco_desc_verify_fundamental, dlco_desc_verify_fundamental_hypotheses; epipolar_rules::Fundamental).  The rules are
-// verify_rules.hpp and epipolar_rules.hpp, where they are stated; this file only decides where the numbers are read from and
-// in which order the work is done, once for every Model.  Every floating-point operation is the headers' (contraction off
-// there), every sum is of integers.
+// kernels_verify.hip — geometric verification of match lists against a two-view model: the homography
+// (dlco_desc_verify_homography, dlco_desc_verify_hypotheses and their _pairs forms; verify_rules::Homography) or the
+// fundamental matrix (dlco_desc_verify_fundamental, dlco_desc_verify_fundamental_hypotheses and their _pairs forms;
+// epipolar_rules::Fundamental).  The rules are verify_rules.hpp and epipolar_rules.hpp, where they are stated; this file only
+// decides where the numbers are read from and in which order the work is done, once for every Model.  Every floating-point
+// operation is the headers' (contraction off there), every sum is of integers.
 //
-//   hyp_kernel<Model>     one lane per hypothesis: its sample, its model, M_all [n_hyp][9] (all zero when invalid).  For the
-//                         fundamental matrix that is the 8 x 9 system eliminated with complete pivoting.  The system lives in
-//                         registers: the header's loops unroll to constant indices and every run-time pivot is a predicated
-//                         swap, so there is no scratch.  Workgroups of kHypLanes<Model>.
-//   score_kernel<Model>   the hot loop, on a grid of ceil(n_hyp / 256) x ceil(m / kScoreChunk) workgroups of 256.  A lane
-//                         owns one hypothesis and keeps its M in registers (9 doubles).  The chunk's matches are widened to
-//                         double once and staged in LDS as (x, y, u, v); in the loop every lane reads the same address, an
-//                         LDS broadcast without conflicts: two 16-byte reads and about 19 (homography) or 33 (fundamental
-//                         matrix) fp64 operations per (hypothesis, match).  A private int32 counter per lane, one integer
-//                         atomicAdd per (hypothesis, chunk) into count [h]: integer sums do not depend on the order, so
-//                         neither on the chunking.
-//   verify_select_kernel  one workgroup: the maximum of the key (count << 32) | (0xFFFFFFFF - h).
-//   mask_kernel<Model>    one lane per match for one M: the u8 mask and, by a ballot per wave and one atomicAdd, its count.
-//
-// The _pairs forms (dlco_desc_verify_pairs_*) run the same steps for the entries of one launch of verify_batch.hpp's plan,
-// many pairs of one segmented match list; the entry at position e of the launch owns slot e of every device array.  The
-// functions of the rule headers are called on the pair's own base pointers and match count, so a pair's numbers are the
-// single call's.
-//   hyp_pairs_kernel<Model>    (entry, hypothesis) to a lane: every entry has the same ceil(n_hyp / kHypLanes) workgroups.
-//   score_pairs_kernel<Model>  score_kernel's loop on a 1-D grid: a workgroup is (entry, block of 256 hypotheses, chunk of
-//                              matches), the block the faster index; it finds its entry by a scalar binary search over swg0.
-//   select_pairs_kernel        one workgroup per entry: the largest key and, with no host round trip, the winning matrix in
-//                              M_cur [e] (zero when the best count is 0).
-//   mask_pairs_kernel<Model>   a workgroup is (active entry, 256 matches of it), found by the same search over the active
-//                              list; M_cur [e] comes from device memory; the trial mask at the entry's matches, the count by
-//                              a ballot and one atomicAdd per wave into n [e].
+// One kernel set.  It runs the entries of one launch of verify_batch.hpp's plan: many pairs of one segmented match list, or
+// the one pair of a single call, whose launch has one entry.  The entry at position e of the launch owns slot e of every
+// device array.  The functions of the rule headers are called on the pair's own base pointers and match count, so a pair's
+// numbers do not depend on its neighbours.
+//   hyp_pairs_kernel<Model>    one lane per (entry, hypothesis): its sample, its model, M_all [e][n_hyp][9] (all zero when
+//                              invalid); every entry has the same ceil(n_hyp / kHypLanes) workgroups of kHypLanes<Model>.  For
+//                              the fundamental matrix that is the 8 x 9 system eliminated with complete pivoting.  The system
+//                              lives in registers: the header's loops unroll to constant indices and every run-time pivot is a
+//                              predicated swap, so there is no scratch.
+//   score_pairs_kernel<Model>  the hot loop, on a 1-D grid of workgroups of 256: a workgroup is (entry, block of 256
+//                              hypotheses, chunk of kScoreChunk matches), the block the faster index; it finds its entry by a
+//                              scalar binary search over swg0.  A lane owns one hypothesis and keeps its M in registers (9
+//                              doubles).  The chunk's matches are widened to double once and staged in LDS as (x, y, u, v), 8 KB;
+//                              in the loop every lane reads the same address, an LDS broadcast without conflicts: two 16-byte
+//                              reads and about 19 (homography) or 33 (fundamental matrix) fp64 operations per (hypothesis,
+//                              match).  A private int32 counter per lane, one integer atomicAdd per (hypothesis, chunk) into
+//                              count [e][h]: integer sums do not depend on the order, so neither on the chunking.
+//   select_pairs_kernel        one workgroup per entry: the maximum of the key (count << 32) | (0xFFFFFFFF - h) and, with no
+//                              host round trip, the winning matrix in M_cur [e] (zero when the best count is 0).
+//   mask_pairs_kernel<Model>   one lane per match: a workgroup is (active entry, 256 matches of it), found by the same search
+//                              over the active list; M_cur [e] comes from device memory; the u8 trial mask at the entry's
+//                              matches, the count by a ballot and one atomicAdd per wave into n [e].
 #include "dlco_internal.hpp"
 #include "epipolar_rules.hpp"
 
@@ -48,78 +44,6 @@ constexpr int VSEL = 1024;                                  // lanes of the sele
 // its system and the compiler need not spill
 template <typename Model> constexpr int kHypLanes = VTH;
 template <> constexpr int kHypLanes<epipolar_rules::Fundamental> = 64;
-
-struct Matrix3 { double m[9]; };
-
-template <typename Model>
-__global__ __launch_bounds__(kHypLanes<Model>) void hyp_kernel(const float *src, const float *dst, unsigned m, unsigned long long seed, int n_hyp,
-                                                               double *M_all)
-{
-    const int h = blockIdx.x * kHypLanes<Model> + threadIdx.x;
-    if (h >= n_hyp) return;
-    int32_t idx[Model::kSample];
-    double M[9];
-    Model::hypothesis(src, dst, m, seed, (uint32_t)h, idx, M);
-    for (int i = 0; i < 9; i++) M_all[9 * (long)h + i] = M[i];
-}
-
-template <typename Model>
-__global__ __launch_bounds__(VTH) void score_kernel(const float2 *src, const float2 *dst, int m, const double *M_all, int n_hyp, double t2, int *count)
-{
-    __shared__ double4 pts[vr::kScoreChunk];
-    static_assert(vr::kScoreChunk == VTH, "a lane stages one match of the chunk");
-    const int h = blockIdx.x * VTH + threadIdx.x;
-    const long i0 = (long)blockIdx.y * vr::kScoreChunk;
-    const int cnt = (int)min((long)vr::kScoreChunk, (long)m - i0);
-    if ((int)threadIdx.x < cnt) {
-        const float2 s = src[i0 + threadIdx.x], d = dst[i0 + threadIdx.x];
-        pts[threadIdx.x] = make_double4((double)s.x, (double)s.y, (double)d.x, (double)d.y);
-    }
-    double M[9];
-    // M = 0 has no inlier: W > 0 fails for a homography, S > 0 for a fundamental matrix
-    for (int i = 0; i < 9; i++) M[i] = h < n_hyp ? M_all[9 * (long)h + i] : 0.0;
-    __syncthreads();
-    int n = 0;
-    for (int j = 0; j < cnt; j++) {
-        const double4 p = pts[j];
-        n += Model::inlier(M, p.x, p.y, p.z, p.w, t2) ? 1 : 0;
-    }
-    if (h < n_hyp && n > 0) atomicAdd(&count[h], n);
-}
-
-__global__ __launch_bounds__(VSEL) void verify_select_kernel(const int *count, int n_hyp, unsigned long long *best)
-{
-    __shared__ unsigned long long part[VSEL / 64];
-    unsigned long long key = 0;
-    for (int h = threadIdx.x; h < n_hyp; h += VSEL) {
-        const unsigned long long k = vr::select_key(count[h], (uint32_t)h);
-        key = k > key ? k : key;
-    }
-    for (int d = 32; d >= 1; d >>= 1) {
-        const unsigned long long other = __shfl_xor(key, d);
-        key = other > key ? other : key;
-    }
-    if ((threadIdx.x & 63) == 0) part[threadIdx.x >> 6] = key;
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        for (int w = 1; w < VSEL / 64; w++) key = part[w] > key ? part[w] : key;
-        *best = key;
-    }
-}
-
-template <typename Model>
-__global__ __launch_bounds__(VTH) void mask_kernel(const float2 *src, const float2 *dst, int m, Matrix3 Mm, double t2, uint8_t *mask, int *count)
-{
-    const long i = (long)blockIdx.x * VTH + threadIdx.x;
-    bool in = false;
-    if (i < m) {
-        const float2 s = src[i], d = dst[i];
-        in = Model::inlier(Mm.m, (double)s.x, (double)s.y, (double)d.x, (double)d.y, t2);
-        mask[i] = in ? 1 : 0;
-    }
-    const int n = __popcll(__ballot(in));
-    if ((threadIdx.x & 63) == 0 && n > 0) atomicAdd(count, n);
-}
 
 // the position of the last item whose first workgroup (first(item)) is not above wg; wg is the same for the whole workgroup,
 // so the search is scalar loads and branches
@@ -227,50 +151,7 @@ __global__ __launch_bounds__(VTH) void mask_pairs_kernel(const float2 *src, cons
 
 }  // namespace
 
-// M_all [n_hyp][9] of the matches src, dst [m][2] (8-byte aligned), all in device memory
-template <typename Model>
-void verify_hypotheses(const float *src, const float *dst, int64_t m, uint64_t seed, int n_hyp, double *M_all, hipStream_t s)
-{
-    constexpr int lanes = kHypLanes<Model>;
-    hipLaunchKernelGGL(hyp_kernel<Model>, dim3((unsigned)((n_hyp + lanes - 1) / lanes)), dim3(lanes), 0, s, src, dst, (unsigned)m,
-                       (unsigned long long)seed, n_hyp, M_all);
-    DLCO_HIP(hipGetLastError());
-}
-
-// count [n_hyp] += the inliers of every hypothesis among the m matches; the caller zeroes count.  The grid's second
-// dimension holds 65535 chunks: more matches go by several launches.
-template <typename Model>
-void verify_score(const float *src, const float *dst, int64_t m, const double *M_all, int n_hyp, double t2, int32_t *count, hipStream_t s)
-{
-    constexpr int64_t kLaunchMatches = (int64_t)32768 * vr::kScoreChunk;
-    for (int64_t i0 = 0; i0 < m; i0 += kLaunchMatches) {
-        const int cnt = (int)std::min<int64_t>(kLaunchMatches, m - i0);
-        hipLaunchKernelGGL(score_kernel<Model>, dim3((unsigned)((n_hyp + VTH - 1) / VTH), (unsigned)((cnt + vr::kScoreChunk - 1) / vr::kScoreChunk)),
-                           dim3(VTH), 0, s, reinterpret_cast<const float2 *>(src) + i0, reinterpret_cast<const float2 *>(dst) + i0, cnt, M_all,
-                           n_hyp, t2, count);
-    }
-    DLCO_HIP(hipGetLastError());
-}
-
-// *best = the largest selection key of count [n_hyp]
-void verify_select(const int32_t *count, int n_hyp, uint64_t *best, hipStream_t s)
-{
-    hipLaunchKernelGGL(verify_select_kernel, dim3(1), dim3(VSEL), 0, s, count, n_hyp, reinterpret_cast<unsigned long long *>(best));
-    DLCO_HIP(hipGetLastError());
-}
-
-// mask [m] of the host's M [9] and *count += its inliers; the caller zeroes count
-template <typename Model>
-void verify_mask(const float *src, const float *dst, int64_t m, const double *M, double t2, uint8_t *mask, int32_t *count, hipStream_t s)
-{
-    Matrix3 Mm;
-    for (int i = 0; i < 9; i++) Mm.m[i] = M[i];
-    hipLaunchKernelGGL(mask_kernel<Model>, dim3((unsigned)((m + VTH - 1) / VTH)), dim3(VTH), 0, s, reinterpret_cast<const float2 *>(src),
-                       reinterpret_cast<const float2 *>(dst), (int)m, Mm, t2, mask, count);
-    DLCO_HIP(hipGetLastError());
-}
-
-// ---- the _pairs forms: one launch of verify_batch.hpp's plan, ent [n_ent] and the launch's matches src, dst in device memory ----
+// ---- one launch of verify_batch.hpp's plan: ent [n_ent] and the launch's matches src, dst [.][2] (8-byte aligned) in device memory ----
 // M_all [n_ent][n_hyp][9]
 template <typename Model>
 void verify_pairs_hypotheses(const float *src, const float *dst, const verify_batch::Entry *ent, int64_t n_ent, uint64_t seed, int n_hyp, double *M_all,
@@ -316,9 +197,6 @@ void verify_pairs_mask(const float *src, const float *dst, const verify_batch::E
 }
 
 #define DLCO_VERIFY_MODEL(Model)                                                                                                 \
-    template void verify_hypotheses<Model>(const float *, const float *, int64_t, uint64_t, int, double *, hipStream_t);                \
-    template void verify_score<Model>(const float *, const float *, int64_t, const double *, int, double, int32_t *, hipStream_t);      \
-    template void verify_mask<Model>(const float *, const float *, int64_t, const double *, double, uint8_t *, int32_t *, hipStream_t);      \
     template void verify_pairs_hypotheses<Model>(const float *, const float *, const verify_batch::Entry *, int64_t, uint64_t, int, double *, hipStream_t); \
     template void verify_pairs_score<Model>(const float *, const float *, const verify_batch::Entry *, int64_t, int64_t, const double *, int, double,      \
                                             int32_t *, hipStream_t);                                                                                       \

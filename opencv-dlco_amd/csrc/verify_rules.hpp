@@ -43,8 +43,9 @@
 // Selection.  count[h] = inliers of hypothesis h (0 for an invalid one: W = 0 everywhere).  The best has the largest count,
 // ties go to the smallest h: the maximum of the key (count << 32) | (0xFFFFFFFF - h).  A best count of 0: no model.
 //
-// Refit, on the host only (refit_round; the loop is refit_rounds, a round's acceptance refit_step).  At most `refine` rounds; a round runs on the inliers of the current model
-// in ascending match index:
+// Refit, on the host only (refit_round; a round's acceptance is refit_step, the loop the library's lockstep one and, in the
+// CPU frame verify_host, refit_rounds).  At most `refine` rounds; a round runs on the inliers of the current model in
+// ascending match index:
 //   Hartley normalisation of each side: centroid c = (sum x / n, sum y / n), d = (sum sqrt(dx dx + dy dy)) / n with
 //   dx = x - cx, s = sqrt(2) / d, sums in index order; a normalised point is ((x - cx) s, (y - cy) s).
 //   The 8 x 8 normal equations of the DLT with h33 = 1: a1 = (x, y, 1, 0, 0, 0, -(u x), -(u y)),
@@ -343,8 +344,8 @@ inline bool refit_round(const float *src, const float *dst, int64_t m, const uin
 
 // The acceptance rule of one round: the model M [9] with (mask [m], count) meets the round's Mn [9], scored as (trial [m], c).
 // Mn replaces the model iff c >= count.  Returns whether the refit goes on: not after a rejected round, nor after one that
-// left the mask unchanged.  The single call's loop below and the batch's lockstep loop (dlco_desc_verify_pairs_*) both end
-// a round here.
+// left the mask unchanged.  The library's lockstep loop (dlco_desc_api.cpp, every dlco_desc_verify_* call) and the CPU
+// frame's loop below both end a round here.
 inline bool refit_step(int64_t m, double M[9], uint8_t *mask, int64_t &count, const double Mn[9], const uint8_t *trial, int64_t c)
 {
     if (c < count) return false;
@@ -355,7 +356,8 @@ inline bool refit_step(int64_t m, double M[9], uint8_t *mask, int64_t &count, co
     return !same;
 }
 
-// The refit's loop for a model M [9] with (mask [m], count).  round(mask, M') forms the model of one round from the inliers of
+// The refit's loop of the CPU frame (verify_host) for a model M [9] with (mask [m], count); the library drops a pair from its
+// lockstep loop under the same two conditions.  round(mask, M') forms the model of one round from the inliers of
 // mask (false: rejected), score(M', trial mask [m]) -> count of M' over all matches.  rounds [refine][9] (may be NULL) receives
 // every M' a round formed; returns their number.
 template <typename Round, typename Score>
@@ -421,7 +423,7 @@ inline int64_t count_inliers(const double M[9], const float *src, const float *d
 
 // The whole rule on the host.  M [9], mask [m], *count, *best_hyp (-1: no model, M and mask zero); M_all [n_hyp][9] and
 // counts [n_hyp] scratch of the caller; rounds as for refit_rounds, *n_rounds the number formed (both may be NULL).  The
-// refit's score is count_inliers here, the mask kernel in the library.
+// refit's score is count_inliers here, the mask kernel in the library, whose loop runs the rounds of many pairs in lockstep.
 template <typename Model>
 inline void verify_host(const float *src, const float *dst, int64_t m, float threshold, int32_t n_hyp, uint64_t seed, int32_t refine, double *M_all,
                         int32_t *counts, double M[9], uint8_t *mask, int64_t *count, int32_t *best_hyp, double *rounds, int32_t *n_rounds)

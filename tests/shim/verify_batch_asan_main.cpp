@@ -1,7 +1,8 @@
 // Sanitizer walk of the batched verification's plan (opencv-dlco_amd/csrc/verify_batch.hpp) and of the refit loop through
 // verify_rules::refit_step: built with -fsanitize=address,undefined by tests/test_verify_batch_rules.py and run as a
 // program.  Seeded offset tables under the library's limits and under small ones; every plan is checked for the properties
-// the kernels rely on, and the kernels' index arithmetic is replayed on the host over every workgroup of the small plans.
+// the kernels rely on, and the kernels' index arithmetic is replayed on the host over every workgroup of the small plans
+// and of the plan of one pair, which is what a single call runs.
 // Pure host code.
 #include "../../opencv-dlco_amd/csrc/verify_batch.hpp"
 #include "../../opencv-dlco_amd/csrc/epipolar_rules.hpp"
@@ -86,6 +87,22 @@ void check(const std::vector<int64_t> &moff, int32_t n_hyp, int k_sample, int64_
     for (int64_t p = p_next; p < P; p++) REQUIRE(pl.launch_of_pair[(size_t)p] == -1);
 }
 
+// the plan a single call hands the batch path, n_pairs = 1 and moff = {0, m} under the library's limits: one launch of one
+// entry that starts every range at 0, and the replay of the kernels' index arithmetic over it
+void check_one_pair(int64_t m, int32_t n_hyp, int k_sample)
+{
+    const std::vector<int64_t> moff = {0, m};
+    const vb::Plan pl = vb::plan(moff.data(), 1, n_hyp, k_sample);
+    REQUIRE(pl.launches.size() == 1 && pl.entries.size() == 1 && pl.launch_of_pair[0] == 0);
+    const vb::Entry &e = pl.entries[0];
+    const vb::Launch &l = pl.launches[0];
+    REQUIRE(e.m0 == 0 && e.m == m && e.pair == 0 && e.swg0 == 0 && e.mwg0 == 0);
+    REQUIRE(l.e0 == 0 && l.n == 1 && l.match0 == 0 && l.matches == m && l.hyps == n_hyp);
+    REQUIRE(l.score_wgs == vb::blocks(n_hyp) * vb::blocks(m) && l.mask_wgs == vb::blocks(m));
+    REQUIRE(pl.max_entries == 1 && pl.max_matches == m && pl.max_hyps == n_hyp);
+    check(moff, n_hyp, k_sample, vb::kLaunchHyp, vb::kLaunchWgs, true);
+}
+
 // the refit loop of both models on a small planted list: the loop and its step under the sanitizers
 template <typename Model>
 void refit(int64_t m)
@@ -132,6 +149,11 @@ int main()
                 plans += 4;
             }
         }
+    }
+    for (int fundamental = 0; fundamental < 2; fundamental++) {
+        const int k = fundamental ? epipolar_rules::Fundamental::kSample : verify_rules::Homography::kSample;
+        for (int64_t m : {(int64_t)k, (int64_t)255, (int64_t)256, (int64_t)257})
+            for (int32_t n_hyp : {1, 256, 257}) { check_one_pair(m, n_hyp, k); plans++; }
     }
     // offsets that must be refused
     const int64_t bad0[] = {1, 5}, bad1[] = {0, 5, 4}, bad2[] = {0, (int64_t)1 << 31};

@@ -105,6 +105,23 @@ def test_a_larger_call_before_leaves_nothing_behind(ctx):
     assert same(ctx, src, dst, want, n_hyp=65, seed=9)
 
 
+@pytest.mark.parametrize("m", [8, 257])
+def test_a_pairs_call_before_leaves_nothing_behind(ctx, m):
+    """a single call is a launch of one entry on the plan buffer and the scratch that the pairs calls use: after a batch of
+    several pairs and more hypotheses it still answers as the restatement, the model form and the _hypotheses form alike"""
+    big = [case(300 + 75 * k, 30 + k) for k in range(4)]
+    src, dst = case(m, 40 + m)
+    want = fundamental_ref(src, dst, n_hyp=65, seed=9)
+    ctx.verify_pairs_fundamental(big, n_hyp=2048)
+    F, mask, best = ctx.verify_fundamental(src, dst, n_hyp=65, seed=9)
+    assert best == want["best"] and np.array_equal(mask, want["mask"]) and int(mask.sum()) == want["count"]
+    assert np.array_equal(bits(F).reshape(9), bits(want["F"]))
+    ctx.verify_pairs_fundamental_hypotheses(big, n_hyp=2048)
+    F_all, count = ctx.verify_fundamental_hypotheses(src, dst, n_hyp=65, seed=9)
+    assert np.array_equal(bits(F_all).reshape(65, 9), bits(want["F_all"])) and np.array_equal(count, want["counts"])
+    assert same(ctx, src, dst, want, n_hyp=65, seed=9)
+
+
 def test_optional_outputs_may_be_null(ctx):
     src, dst, want = reference("planted257")
     F, n = np.zeros(9), C.c_int64(-1)

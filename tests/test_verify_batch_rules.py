@@ -134,6 +134,21 @@ def test_the_librarys_limits_cut_a_large_call(rules):
     assert pl["e"]["pair"].tolist() == [1, 4] and pl["e"]["m0"].tolist() == [0, 12] and pl["l"]["match0"].tolist() == [3] and pl["l"]["matches"].tolist() == [22]
 
 
+@pytest.mark.parametrize("fundamental", [False, True])
+def test_the_plan_of_one_pair(rules, fundamental):
+    """what a single call (dlco_desc_verify_homography and its kin) hands the batch path: n_pairs = 1, moff = {0, m} under the
+    library's limits is one launch of one entry that starts every range at 0"""
+    lanes, k_sample = rules.shim_vbatch_lanes(), rules.shim_vbatch_sample(int(fundamental))
+    for m in (k_sample, 255, 256, 257):
+        for n_hyp in (1, 256, 257):
+            pl = plan(rules, [0, m], n_hyp, fundamental)
+            e, l = pl["e"], pl["l"]
+            assert {f: e[f].tolist() for f in E_FIELDS} == dict(m0=[0], m=[m], pair=[0], swg0=[0], mwg0=[0])
+            assert {f: l[f].tolist() for f in L_FIELDS} == dict(e0=[0], n=[1], match0=[0], matches=[m], hyps=[n_hyp],
+                                                                 score_wgs=[ceil_div(n_hyp, lanes) * ceil_div(m, lanes)], mask_wgs=[ceil_div(m, lanes)])
+            assert pl["launch"].tolist() == [0] and (pl["max_entries"], pl["max_matches"], pl["max_hyps"]) == (1, m, n_hyp)
+
+
 def test_offsets_validation(rules):
     ok = lambda o, n=None: bool(rules.shim_vbatch_offsets_ok(np.asarray(o, np.int64).ctypes.data_as(i64p), len(o) - 1 if n is None else n))
     assert ok([0, 0]) and ok([0, 5, 5, 9]) and ok([0, 2 ** 31 - 1]) and ok([0, 2 ** 31 - 1, 2 ** 32 - 2])

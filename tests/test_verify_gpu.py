@@ -104,6 +104,23 @@ def test_a_larger_call_before_leaves_nothing_behind(ctx):
     assert same(ctx, src, dst, want, n_hyp=65, seed=9)
 
 
+@pytest.mark.parametrize("m", [4, 257])
+def test_a_pairs_call_before_leaves_nothing_behind(ctx, m):
+    """a single call is a launch of one entry on the plan buffer and the scratch that the pairs calls use: after a batch of
+    several pairs and more hypotheses it still answers as the restatement, the model form and the _hypotheses form alike"""
+    big = [case(300 + 75 * k, 30 + k) for k in range(4)]
+    src, dst = case(m, 40 + m)
+    want = verify_ref(src, dst, n_hyp=65, seed=9)
+    ctx.verify_pairs_homography(big, n_hyp=2048)
+    H, mask, best = ctx.verify_homography(src, dst, n_hyp=65, seed=9)
+    assert best == want["best"] and np.array_equal(mask, want["mask"]) and int(mask.sum()) == want["count"]
+    assert np.array_equal(bits(H).reshape(9), bits(want["H"]))
+    ctx.verify_pairs_hypotheses(big, n_hyp=2048)
+    H_all, count = ctx.verify_hypotheses(src, dst, n_hyp=65, seed=9)
+    assert np.array_equal(bits(H_all).reshape(65, 9), bits(want["H_all"])) and np.array_equal(count, want["counts"])
+    assert same(ctx, src, dst, want, n_hyp=65, seed=9)
+
+
 def test_optional_outputs_may_be_null(ctx):
     src, dst, want = reference("planted257")
     H, n = np.zeros(9), C.c_int64(-1)

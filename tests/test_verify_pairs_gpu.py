@@ -1,13 +1,17 @@
 """Batched verification on a GPU: dlco_desc_verify_pairs_* over one segmented match list.  Both rules are IEEE double arithmetic
 in a stated order and integer counts, a hypothesis depends on (seed, h, m) and its pair's own matches only, so every pair's
 answer in a batch is compared byte for byte with a loop of the single calls (ctx.verify_homography, ctx.verify_fundamental and
-their _hypotheses forms), and with the numpy restatements of tests/test_verify_rules.py and tests/test_epipolar_rules.py."""
+their _hypotheses forms), and with the numpy restatements of tests/test_verify_rules.py and tests/test_epipolar_rules.py.  A
+single call is a batch of one pair on the same kernels, so the loop shows that a pair's answer does not depend on its
+neighbours and no more; the independent yardsticks are the numpy restatements and, where those would take too long, the C++
+host frame verify_rules::verify_host<Model> on the CPU (tests/shim/verify_batch_shim.cpp)."""
 import ctypes as C
 
 import numpy as np
 import pytest
 
 import test_epipolar_rules as E
+import test_verify_batch_rules as B
 import test_verify_rules as V
 from test_verify_rules import bits
 
@@ -61,6 +65,11 @@ def ctx(dlco):
     c.close()
 
 
+@pytest.fixture(scope="module")
+def host_frame(tmp_path_factory):
+    return B.build_shim(tmp_path_factory)
+
+
 def same_triple(a, b):
     """two (M [3,3], inlier [m] bool, best_hyp): every bit"""
     return np.array_equal(bits(a[0]), bits(b[0])) and a[1].dtype == b[1].dtype == bool and np.array_equal(a[1], b[1]) and a[2] == b[2]
@@ -89,6 +98,18 @@ def check_against_restatement(M, got, lists, want):
             assert no_model(g, len(lists[p][0])), p
         else:
             assert np.array_equal(bits(g[0]).reshape(9), bits(w[M.key])) and np.array_equal(g[1], w["mask"]) and g[2] == w["best"], (M.name, p)
+
+
+def check_against_host_frame(M, rules, got, lists, pairs, threshold, n_hyp, seed, refine):
+    """the pairs `pairs` of a batch's answers against the whole rule in C++ on the CPU, which runs no kernel"""
+    for p in pairs:
+        s, d = lists[p]
+        if len(s) < M.sample:
+            assert no_model(got[p], len(s)), (M.name, p)
+            continue
+        w = B.shim_whole_rule(rules, M.name == "fundamental", s, d, threshold, n_hyp, seed, refine)
+        g = got[p]
+        assert np.array_equal(bits(g[0]).reshape(9), bits(w["M"])) and np.array_equal(g[1], w["mask"]) and g[2] == w["best"], (M.name, p, len(s))
 
 
 # ---- the main batch: pairs that leave the lockstep refit at different rounds -----------------------------------------------
@@ -167,21 +188,30 @@ def test_independence(ctx, name):
 
 # ---- more than one launch ----------------------------------------------------------------------------------------------------
 @pytest.mark.parametrize("name", MODELS)
-def test_several_launches(ctx, dlco, name):
+def test_several_launches(ctx, dlco, host_frame, name):
     M = Model(ctx, name)
     lists = [M.planted(12, 40 + k) for k in range(5)]
     launch = dlco.verify_pairs_launches(np.arange(6) * 12, 2 ** 20, name == "fundamental")
     assert launch.max() >= 1 and launch.tolist() == sorted(launch.tolist()) and launch.min() == 0
-    check_against_loop(M, lists, threshold=1.5, n_hyp=2 ** 20, seed=7, refine=2)
+    kw = dict(threshold=1.5, n_hyp=2 ** 20, seed=7, refine=2)
+    got = check_against_loop(M, lists, **kw)
+    # The host frame on the first pair of every launch, as verify_pairs_launches numbers them.  All five pairs took the frame
+    # 1.0 s for the homography and 10.2 s for the fundamental matrix (about 2 s a pair) on one CPU core: over ten seconds for
+    # the two models together, so not all five.
+    firsts = [p for p in range(len(lists)) if p == 0 or launch[p] != launch[p - 1]]
+    assert len(firsts) == launch.max() + 1 >= 2
+    check_against_host_frame(M, host_frame, got, lists, firsts, **kw)
 
 
 # ---- many small pairs --------------------------------------------------------------------------------------------------------
 @pytest.mark.parametrize("name", MODELS)
-def test_many_small_pairs(ctx, name):
+def test_many_small_pairs(ctx, host_frame, name):
     M = Model(ctx, name)
     lists = [M.planted(4 + k % 37, 1000 + k) for k in range(600)]
     assert {len(s) for s, _ in lists} == set(range(4, 41))
-    got = check_against_loop(M, lists, threshold=1.5, n_hyp=65, seed=11, refine=2)
+    kw = dict(threshold=1.5, n_hyp=65, seed=11, refine=2)
+    got = check_against_loop(M, lists, **kw)
+    check_against_host_frame(M, host_frame, got, lists, range(len(lists)), **kw)
     assert sum(g[2] >= 0 for g in got) >= 300                                # most pairs have a model: the test is not one of "no model"
 
 
