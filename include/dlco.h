@@ -647,7 +647,8 @@ int dlco_desc_match_pairs_slices(dlco_desc_ctx *ctx, const int64_t *seg, int32_t
  *   Out of scope: a spatially bucketed form that skips tiles no query of which can admit a row (a distance's bits are defined
  * by the tile loop's chain of matrix-core operations, which a kernel that gathers candidates does not reproduce); the byte
  * line (there is no dlco_desc_match_u8_guided).  In scope since: a fundamental-matrix predicate, which has calls of its own,
- * dlco_desc_match_guided_epipolar below. ---- */
+ * dlco_desc_match_guided_epipolar below.  In scope since: the byte line, which has calls of its own with _u8 at the end of the
+ * name, dlco_desc_match_guided_u8 below. ---- */
 int dlco_desc_match_guided(dlco_desc_ctx *ctx, const float *query_host, const float *query_xy_host, int64_t nq,
                            const float *train_host, const float *train_xy_host, int64_t nt, int32_t r, const double *H,
                            float radius, int32_t h_side, int32_t *idx_host, float *sqdist_host);
@@ -684,7 +685,8 @@ int dlco_desc_cross_sqdists_guided(dlco_desc_ctx *ctx, const float *query_host, 
  *   DLCO_ERR_INVALID, before the handle is used and with no output touched: whatever dlco_desc_match (_device, cross_sqdists)
  * rejects, a null coordinate pointer or a null F, an entry of F that is not finite, a threshold that is not finite or <= 0, an
  * f_side other than 0 or 1, a coordinate pitch below 2 (device form).
- *   Out of scope: the byte line; a spatially bucketed form; a choice between H and F. ---- */
+ *   Out of scope: the byte line; a spatially bucketed form; a choice between H and F.  In scope since: the byte line,
+ * dlco_desc_match_guided_epipolar_u8 below. ---- */
 int dlco_desc_match_guided_epipolar(dlco_desc_ctx *ctx, const float *query_host, const float *query_xy_host, int64_t nq,
                                     const float *train_host, const float *train_xy_host, int64_t nt, int32_t r, const double *F,
                                     float threshold, int32_t f_side, int32_t *idx_host, float *sqdist_host);
@@ -715,7 +717,8 @@ int dlco_desc_cross_sqdists_guided_epipolar(dlco_desc_ctx *ctx, const float *que
  * finite or <= 0, a side other than 0 or 1, ldxy < 2 or an xy that is not 4-byte aligned (device forms).
  *   csrc/match_batch.hpp states the plan: records are per pair, 32 bytes a row in one buffer per launch of at most 2^22 record
  * rows.  Out of scope: the byte line; a batched guided distance matrix; seg, pairs or the matrices in device memory; a radius
- * per pair; a choice between H and F. ---- */
+ * per pair; a choice between H and F.  In scope since: the byte line, dlco_desc_match_pairs_guided_u8 and
+ * dlco_desc_match_pairs_guided_epipolar_u8 below. ---- */
 int dlco_desc_match_pairs_guided(dlco_desc_ctx *ctx, const float *table_host, const float *xy_host, const int64_t *seg,
                                  int32_t n_img, const int32_t *pairs, int64_t n_pairs, int32_t r, const double *H, float radius,
                                  int32_t h_side, int32_t *idx_host, float *sqdist_host);
@@ -783,6 +786,63 @@ int dlco_desc_match_pairs_u8(dlco_desc_ctx *ctx, const uint8_t *table_u8, const 
 /* the same on a table in HBM, as dlco_desc_match_u8_device takes one (row pitch ld bytes, a multiple of 16) */
 int dlco_desc_match_pairs_u8_device(dlco_desc_ctx *ctx, const uint8_t *table_dev, int64_t ld, const int64_t *seg, int32_t n_img,
                                     const int32_t *pairs, int64_t n_pairs, int32_t r, int32_t *idx_dev, int32_t *sqdist_dev);
+/* ---- Guided matching on byte tables: the second pass of the two-view chain for descriptors that were quantised, so that the
+ * float tables need not be kept.  Ten calls, each its float counterpart argument for argument with uint8_t tables, int32_t
+ * distances and, in the device forms, pitches in bytes that are multiples of 16 (as dlco_desc_match_u8_device takes tables).
+ * The geometry, the two models, the pair predicate P(i, j), the sides and the coordinates are those of dlco_desc_match_guided
+ * and dlco_desc_match_guided_epipolar above: the verdict is formed by the same rule headers in the same IEEE double
+ * arithmetic, as a further epilogue of the int8 tile loop.
+ *   Result: idx[i] / sqdist[i] are the first two admitted candidates of dlco_desc_match_u8's (d, train index) order, i.e. the
+ * top two of the entries below INT32_MAX of row i of the matrix dlco_desc_cross_sqdists_guided_u8
+ * (dlco_desc_cross_sqdists_guided_epipolar_u8) returns, which is the matrix of dlco_desc_cross_sqdists_u8 with INT32_MAX where P
+ * fails; every distance is the integer dlco_desc_cross_sqdists_u8 gives for that entry.  Fewer than two admitted candidates
+ * leave -1 / INT32_MAX in the free columns.  Non-finite coordinates: as dlco_desc_match_guided.
+ *   The pair calls: pair p owns the rows row0[p] .. row0[p + 1] - 1, and they are, byte for byte, what the single byte guided
+ * call returns for that pair with the matrix M + 9 p.  An all-zero matrix ("no model") launches nothing and fills -1 /
+ * INT32_MAX; a pair with an empty train image likewise.
+ *   DLCO_ERR_INVALID, before the handle is used and with no output touched: whatever the byte call of the same form
+ * (dlco_desc_match_u8, _device, dlco_desc_cross_sqdists_u8, dlco_desc_match_pairs_u8, _device) and the float guided call of
+ * the same form reject: a null pointer; an entry of a matrix that is not finite; a radius or threshold that is not finite or
+ * <= 0; a side other than 0 or 1; a coordinate pitch below 2 or coordinates that are not 4-byte aligned (device forms); a
+ * table pitch below r or not a multiple of 16, or a table that is not 16-byte aligned (device forms); the limits on nq, nt
+ * and r, and nq * nt <= 2^28 for the matrices.
+ *   Out of scope: a slicing rule tuned to the guided forms' occupancy (they use the byte matcher's); a spatially bucketed
+ * form; a batched guided matrix; seg, pairs or the matrices in device memory; a choice between H and F. ---- */
+int dlco_desc_match_guided_u8(dlco_desc_ctx *ctx, const uint8_t *query_u8, const float *query_xy_host, int64_t nq,
+                              const uint8_t *train_u8, const float *train_xy_host, int64_t nt, int32_t r, const double *H,
+                              float radius, int32_t h_side, int32_t *idx_host, int32_t *sqdist_host);
+int dlco_desc_match_guided_u8_device(dlco_desc_ctx *ctx, const uint8_t *query_dev, int64_t ldq, const float *query_xy_dev,
+                                     int64_t ldxy_q, int64_t nq, const uint8_t *train_dev, int64_t ldt,
+                                     const float *train_xy_dev, int64_t ldxy_t, int64_t nt, int32_t r, const double *H,
+                                     float radius, int32_t h_side, int32_t *idx_dev, int32_t *sqdist_dev);
+/* the matrix out[nq][nt] of dlco_desc_cross_sqdists_u8 with INT32_MAX where P fails (nq * nt <= 2^28) */
+int dlco_desc_cross_sqdists_guided_u8(dlco_desc_ctx *ctx, const uint8_t *query_u8, const float *query_xy_host, int64_t nq,
+                                      const uint8_t *train_u8, const float *train_xy_host, int64_t nt, int32_t r,
+                                      const double *H, float radius, int32_t h_side, int32_t *out_host);
+int dlco_desc_match_guided_epipolar_u8(dlco_desc_ctx *ctx, const uint8_t *query_u8, const float *query_xy_host, int64_t nq,
+                                       const uint8_t *train_u8, const float *train_xy_host, int64_t nt, int32_t r,
+                                       const double *F, float threshold, int32_t f_side, int32_t *idx_host, int32_t *sqdist_host);
+int dlco_desc_match_guided_epipolar_u8_device(dlco_desc_ctx *ctx, const uint8_t *query_dev, int64_t ldq, const float *query_xy_dev,
+                                              int64_t ldxy_q, int64_t nq, const uint8_t *train_dev, int64_t ldt,
+                                              const float *train_xy_dev, int64_t ldxy_t, int64_t nt, int32_t r, const double *F,
+                                              float threshold, int32_t f_side, int32_t *idx_dev, int32_t *sqdist_dev);
+int dlco_desc_cross_sqdists_guided_epipolar_u8(dlco_desc_ctx *ctx, const uint8_t *query_u8, const float *query_xy_host, int64_t nq,
+                                               const uint8_t *train_u8, const float *train_xy_host, int64_t nt, int32_t r,
+                                               const double *F, float threshold, int32_t f_side, int32_t *out_host);
+int dlco_desc_match_pairs_guided_u8(dlco_desc_ctx *ctx, const uint8_t *table_u8, const float *xy_host, const int64_t *seg,
+                                    int32_t n_img, const int32_t *pairs, int64_t n_pairs, int32_t r, const double *H,
+                                    float radius, int32_t h_side, int32_t *idx_host, int32_t *sqdist_host);
+int dlco_desc_match_pairs_guided_u8_device(dlco_desc_ctx *ctx, const uint8_t *table_dev, int64_t ld, const float *xy_dev,
+                                           int64_t ldxy, const int64_t *seg, int32_t n_img, const int32_t *pairs, int64_t n_pairs,
+                                           int32_t r, const double *H, float radius, int32_t h_side, int32_t *idx_dev,
+                                           int32_t *sqdist_dev);
+int dlco_desc_match_pairs_guided_epipolar_u8(dlco_desc_ctx *ctx, const uint8_t *table_u8, const float *xy_host, const int64_t *seg,
+                                             int32_t n_img, const int32_t *pairs, int64_t n_pairs, int32_t r, const double *F,
+                                             float threshold, int32_t f_side, int32_t *idx_host, int32_t *sqdist_host);
+int dlco_desc_match_pairs_guided_epipolar_u8_device(dlco_desc_ctx *ctx, const uint8_t *table_dev, int64_t ld, const float *xy_dev,
+                                                    int64_t ldxy, const int64_t *seg, int32_t n_img, const int32_t *pairs,
+                                                    int64_t n_pairs, int32_t r, const double *F, float threshold, int32_t f_side,
+                                                    int32_t *idx_dev, int32_t *sqdist_dev);
 /* ---- Geometric verification: a homography between the two sides of a match list, so that the chain ends in a verified
  * result on this library alone.  A deterministic RANSAC by a rule of this library's own, csrc/verify_rules.hpp states it:
  * n_hyp hypotheses from four matches each (a counter-based sampler on `seed`), scored on the device by forward transfer
@@ -867,7 +927,7 @@ int  dlco_desc_verify_pairs_launches(const int64_t *moff, int64_t n_pairs, int32
 /* HIP-event time of the kernels of the last compute / describe call (transform, pooling, projection, and the sampling
  * for the keypoint calls; extract_patches: the sampling alone); the pair_sqdists /
  * pair_stats calls add their distance kernel; after a match / cross_sqdists call, float or _u8, the time of its kernels
- * (norms, tile loop, merge of the slices, and for the guided forms the kernel that writes the records, launched once per side for the epipolar ones); after a match_pairs call, float or _u8, every kernel of the call (the norms of
+ * (norms, tile loop, merge of the slices, and for the guided forms the kernel that writes the records, launched once per side for the epipolar ones; the guided _u8 calls, single or pairs, likewise: norms, record kernels, tile loop, merge); after a match_pairs call, float or _u8, every kernel of the call (the norms of
  * the whole table, the fill of the pairs with an empty train image, the tile loop and the merge of every launch); the _u8 forms of describe add their quantising kernel; after a detect call the
  * detector's kernels (the integral image when the call formed it, the octaves, the selection; detect_oriented adds the
  * orientation kernel); after an orient call the orientation kernel and the integral image when the call formed it; after a

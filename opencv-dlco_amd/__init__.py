@@ -230,6 +230,17 @@ def load():
                                                       vp, vp]
     L.dlco_desc_match_pairs_guided_epipolar.argtypes = L.dlco_desc_match_pairs_guided.argtypes
     L.dlco_desc_match_pairs_guided_epipolar_device.argtypes = L.dlco_desc_match_pairs_guided_device.argtypes
+    # the byte line's guided calls: the float ones argument for argument, byte tables and int32 distances
+    L.dlco_desc_match_guided_u8.argtypes = [vp, u8p, f32p, i64, u8p, f32p, i64, C.c_int32, f64p, C.c_float, C.c_int32, i32p, i32p]
+    L.dlco_desc_match_guided_u8_device.argtypes = L.dlco_desc_match_guided_device.argtypes
+    L.dlco_desc_cross_sqdists_guided_u8.argtypes = [vp, u8p, f32p, i64, u8p, f32p, i64, C.c_int32, f64p, C.c_float, C.c_int32, i32p]
+    L.dlco_desc_match_guided_epipolar_u8.argtypes = L.dlco_desc_match_guided_u8.argtypes
+    L.dlco_desc_match_guided_epipolar_u8_device.argtypes = L.dlco_desc_match_guided_u8_device.argtypes
+    L.dlco_desc_cross_sqdists_guided_epipolar_u8.argtypes = L.dlco_desc_cross_sqdists_guided_u8.argtypes
+    L.dlco_desc_match_pairs_guided_u8.argtypes = [vp, u8p, f32p, i64p, C.c_int32, i32p, i64, C.c_int32, f64p, C.c_float, C.c_int32, i32p, i32p]
+    L.dlco_desc_match_pairs_guided_u8_device.argtypes = L.dlco_desc_match_pairs_guided_device.argtypes
+    L.dlco_desc_match_pairs_guided_epipolar_u8.argtypes = L.dlco_desc_match_pairs_guided_u8.argtypes
+    L.dlco_desc_match_pairs_guided_epipolar_u8_device.argtypes = L.dlco_desc_match_pairs_guided_u8_device.argtypes
     L.dlco_desc_last_kernel_ms.argtypes = [vp]
     L.dlco_desc_last_kernel_ms.restype = C.c_double
     L.dlco_pr_last_error.restype = C.c_char_p
@@ -1283,6 +1294,70 @@ class DescContext:
         self._ck(self.L.dlco_desc_cross_sqdists_u8(self.h, _p(q, u8p), q.shape[0], _p(t, u8p), t.shape[0], q.shape[1], _p(out, i32p)))
         return out
 
+    # ---- guided matching on byte tables: the float guided calls argument for argument, integer distances ----
+    @staticmethod
+    def _guided_tables_u8(query, query_xy, train, train_xy, M):
+        q, t = np.ascontiguousarray(query, np.uint8), np.ascontiguousarray(train, np.uint8)
+        qxy, txy = _f32(query_xy), _f32(train_xy)
+        assert q.ndim == 2 and t.ndim == 2 and q.shape[1] == t.shape[1]
+        assert qxy.shape == (q.shape[0], 2) and txy.shape == (t.shape[0], 2)
+        m = np.ascontiguousarray(M, np.float64)
+        assert m.size == 9
+        return q, qxy, t, txy, m
+
+    def _match_guided_u8(self, call, query, query_xy, train, train_xy, M, radius, side):
+        q, qxy, t, txy, m = self._guided_tables_u8(query, query_xy, train, train_xy, M)
+        idx = np.empty((q.shape[0], 2), np.int32)
+        d = np.empty((q.shape[0], 2), np.int32)
+        self._ck(call(self.h, _p(q, u8p), _p(qxy, f32p), q.shape[0], _p(t, u8p), _p(txy, f32p), t.shape[0], q.shape[1],
+                      _p(m, C.POINTER(C.c_double)), radius, side, _p(idx, i32p), _p(d, i32p)))
+        return idx, d
+
+    def _cross_guided_u8(self, call, query, query_xy, train, train_xy, M, radius, side):
+        q, qxy, t, txy, m = self._guided_tables_u8(query, query_xy, train, train_xy, M)
+        out = np.empty((q.shape[0], t.shape[0]), np.int32)
+        self._ck(call(self.h, _p(q, u8p), _p(qxy, f32p), q.shape[0], _p(t, u8p), _p(txy, f32p), t.shape[0], q.shape[1],
+                      _p(m, C.POINTER(C.c_double)), radius, side, _p(out, i32p)))
+        return out
+
+    def _match_guided_u8_device(self, call, q_ptr, qxy_ptr, nq, t_ptr, txy_ptr, nt, r, M, idx_ptr, d_ptr, radius, side, ldq, ldt, ldxy_q,
+                                ldxy_t):
+        m = np.ascontiguousarray(M, np.float64)
+        assert m.size == 9
+        self._ck(call(self.h, C.c_void_p(q_ptr), ldq or r, C.c_void_p(qxy_ptr), ldxy_q, nq, C.c_void_p(t_ptr), ldt or r, C.c_void_p(txy_ptr),
+                      ldxy_t, nt, r, _p(m, C.POINTER(C.c_double)), radius, side, C.c_void_p(idx_ptr), C.c_void_p(d_ptr)))
+
+    def match_guided_u8(self, query, query_xy, train, train_xy, H, radius=6.0, h_side=0):
+        """match_guided on byte tables [n, r] uint8: the first two rows of match_u8's (d, index) order among those the homography
+        admits.  (idx [nq,2] int32, sqdist [nq,2] int32); fewer than two admitted rows leave -1 / INT32_MAX."""
+        return self._match_guided_u8(self.L.dlco_desc_match_guided_u8, query, query_xy, train, train_xy, H, radius, h_side)
+
+    def match_guided_u8_device(self, q_ptr, qxy_ptr, nq, t_ptr, txy_ptr, nt, r, H, idx_ptr, d_ptr, radius=6.0, h_side=0, ldq=None,
+                               ldt=None, ldxy_q=2, ldxy_t=2):
+        """match_guided_u8 on tables in device memory (row pitches ldq, ldt in bytes: multiples of 16; coordinate pitches in
+        floats, >= 2); results to device memory."""
+        self._match_guided_u8_device(self.L.dlco_desc_match_guided_u8_device, q_ptr, qxy_ptr, nq, t_ptr, txy_ptr, nt, r, H, idx_ptr, d_ptr,
+                                     radius, h_side, ldq, ldt, ldxy_q, ldxy_t)
+
+    def cross_sqdists_guided_u8(self, query, query_xy, train, train_xy, H, radius=6.0, h_side=0):
+        """cross_sqdists_u8 with INT32_MAX where H does not admit the pair: match_guided_u8 is the top two of the entries below it."""
+        return self._cross_guided_u8(self.L.dlco_desc_cross_sqdists_guided_u8, query, query_xy, train, train_xy, H, radius, h_side)
+
+    def match_guided_epipolar_u8(self, query, query_xy, train, train_xy, F, threshold=3.0, f_side=0):
+        """match_guided_epipolar on byte tables: (idx [nq,2] int32, sqdist [nq,2] int32), -1 / INT32_MAX in free columns."""
+        return self._match_guided_u8(self.L.dlco_desc_match_guided_epipolar_u8, query, query_xy, train, train_xy, F, threshold, f_side)
+
+    def match_guided_epipolar_u8_device(self, q_ptr, qxy_ptr, nq, t_ptr, txy_ptr, nt, r, F, idx_ptr, d_ptr, threshold=3.0, f_side=0,
+                                        ldq=None, ldt=None, ldxy_q=2, ldxy_t=2):
+        """match_guided_epipolar_u8 on tables in device memory, pitches as match_guided_u8_device."""
+        self._match_guided_u8_device(self.L.dlco_desc_match_guided_epipolar_u8_device, q_ptr, qxy_ptr, nq, t_ptr, txy_ptr, nt, r, F, idx_ptr,
+                                     d_ptr, threshold, f_side, ldq, ldt, ldxy_q, ldxy_t)
+
+    def cross_sqdists_guided_epipolar_u8(self, query, query_xy, train, train_xy, F, threshold=3.0, f_side=0):
+        """cross_sqdists_u8 with INT32_MAX where F does not admit the pair."""
+        return self._cross_guided_u8(self.L.dlco_desc_cross_sqdists_guided_epipolar_u8, query, query_xy, train, train_xy, F, threshold,
+                                     f_side)
+
     # ---- matching many pairs of images in one call (csrc/match_batch.hpp states the plan) ----
     def _match_pairs(self, call, tables, pairs, dtype, ptr, dist):
         tabs = [np.ascontiguousarray(t, dtype) for t in tables]
@@ -1320,8 +1395,8 @@ class DescContext:
                                                         r, C.c_void_p(idx_ptr), C.c_void_p(d_ptr)))
 
     # ---- guided matching of many pairs in one call: a matrix per pair (csrc/match_batch.hpp states the plan) ----
-    def _match_pairs_guided(self, call, tables, xys, pairs, M, radius, side):
-        tabs, cs = [_f32(t) for t in tables], [_f32(x) for x in xys]
+    def _match_pairs_guided(self, call, tables, xys, pairs, M, radius, side, dtype=np.float32, ptr=f32p, dist=np.float32):
+        tabs, cs = [np.ascontiguousarray(t, dtype) for t in tables], [_f32(x) for x in xys]
         assert tabs and len(cs) == len(tabs) and all(t.ndim == 2 and t.shape[1] == tabs[0].shape[1] for t in tabs)
         assert all(x.shape == (t.shape[0], 2) for x, t in zip(cs, tabs))
         seg = np.concatenate([[0], np.cumsum([t.shape[0] for t in tabs])]).astype(np.int64)
@@ -1330,9 +1405,10 @@ class DescContext:
         assert m.shape[0] == q.shape[0]
         table, xy = np.ascontiguousarray(np.concatenate(tabs, axis=0)), np.ascontiguousarray(np.concatenate(cs, axis=0))
         row0 = match_pairs_rows(seg, q)
-        idx, d = np.empty((row0[-1], 2), np.int32), np.empty((row0[-1], 2), np.float32)
-        self._ck(call(self.h, _p(table, f32p), _p(xy, f32p), _p(seg, i64p), seg.size - 1, _p(q, i32p), q.shape[0], table.shape[1],
-                      _p(m, C.POINTER(C.c_double)), radius, side, _p(idx, i32p), _p(d, f32p)))
+        idx, d = np.empty((row0[-1], 2), np.int32), np.empty((row0[-1], 2), dist)
+        self._ck(call(self.h, _p(table, ptr), _p(xy, f32p), _p(seg, i64p), seg.size - 1, _p(q, i32p), q.shape[0], table.shape[1],
+                      _p(m, C.POINTER(C.c_double)), radius, side, _p(idx, i32p),
+                      _p(d, C.POINTER(C.c_float if dist == np.float32 else C.c_int32))))
         return [(idx[row0[p]:row0[p + 1]], d[row0[p]:row0[p + 1]]) for p in range(q.shape[0])]
 
     def match_pairs_guided(self, tables, xys, pairs, H, radius=6.0, h_side=0):
@@ -1364,6 +1440,28 @@ class DescContext:
         """match_pairs_guided_epipolar on tables in device memory, pitches as match_pairs_guided_device."""
         self._match_pairs_guided_device(self.L.dlco_desc_match_pairs_guided_epipolar_device, table_ptr, xy_ptr, seg, pairs, r, F, idx_ptr, d_ptr,
                                         threshold, f_side, ld, ldxy)
+
+    def match_pairs_guided_u8(self, tables, xys, pairs, H, radius=6.0, h_side=0):
+        """match_pairs_guided on byte tables: every pair is byte for byte what match_guided_u8 returns for it with H[p]; an
+        all-zero H[p] or an empty train image gives -1 / INT32_MAX in both columns."""
+        return self._match_pairs_guided(self.L.dlco_desc_match_pairs_guided_u8, tables, xys, pairs, H, radius, h_side, np.uint8, u8p, np.int32)
+
+    def match_pairs_guided_epipolar_u8(self, tables, xys, pairs, F, threshold=3.0, f_side=0):
+        """match_pairs_guided_epipolar on byte tables: every pair is what match_guided_epipolar_u8 returns for it."""
+        return self._match_pairs_guided(self.L.dlco_desc_match_pairs_guided_epipolar_u8, tables, xys, pairs, F, threshold, f_side, np.uint8,
+                                        u8p, np.int32)
+
+    def match_pairs_guided_u8_device(self, table_ptr, xy_ptr, seg, pairs, r, H, idx_ptr, d_ptr, radius=6.0, h_side=0, ld=None, ldxy=2):
+        """match_pairs_guided_u8 on one table in device memory (row pitch ld bytes, a multiple of 16) and one coordinate table
+        (pitch ldxy floats >= 2); H on the host; results to device memory."""
+        self._match_pairs_guided_device(self.L.dlco_desc_match_pairs_guided_u8_device, table_ptr, xy_ptr, seg, pairs, r, H, idx_ptr, d_ptr,
+                                        radius, h_side, ld, ldxy)
+
+    def match_pairs_guided_epipolar_u8_device(self, table_ptr, xy_ptr, seg, pairs, r, F, idx_ptr, d_ptr, threshold=3.0, f_side=0, ld=None,
+                                              ldxy=2):
+        """match_pairs_guided_epipolar_u8 on tables in device memory, pitches as match_pairs_guided_u8_device."""
+        self._match_pairs_guided_device(self.L.dlco_desc_match_pairs_guided_epipolar_u8_device, table_ptr, xy_ptr, seg, pairs, r, F, idx_ptr,
+                                        d_ptr, threshold, f_side, ld, ldxy)
 
     def match_pairs_slices(self, seg, pairs, u8=False):
         """The plan only: slices [n_pairs] int32 of train that each pair is cut into in such a call on this context's device

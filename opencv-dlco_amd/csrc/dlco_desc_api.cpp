@@ -36,7 +36,7 @@ constexpr int kChunk = 2048;            // patches per launch pair: 256 MB of Pa
 
 // The buffers of one matcher (FloatLine, ByteLine below): the uploaded tables of the host forms, the result of a chunk and
 // the matrix, part [slices][nq] partial (d1, j1, d2, j2) of 16 bytes each, the norms of the queries and of train; for the
-// guided forms of the float line the uploaded (x, y) of both tables and rec [n][4], the records of the side the homography
+// guided forms of either line the uploaded (x, y) of both tables and rec [n][4], the records of the side the homography
 // applies to (guided_rules.hpp): a launch's queries or all of train; for the epipolar guided forms (guided_epipolar_rules.hpp)
 // rec holds train's records and qrec a launch's queries'; for the batch forms (dlco_desc_match_pairs*) plan, the uploaded
 // entries of every launch and behind them the fill list (match_batch.hpp), train the one table and tnorm / qnorm its norms;
@@ -248,7 +248,7 @@ void compute(dlco_desc_ctx *c, const PatchSource &src, int64_t n, const RowsOut 
 // ---- matching: the two nearest rows of train for every row of query (kernels_match.hip, kernels_match_u8.hip) --------------
 // One host path serves both matchers.  A line (FloatLine, ByteLine) says what differs: the types of an element, a distance
 // and a norm, the Shape of the slicing rule, the context's buffers, the kernel wrappers, and the name in the "do not fit"
-// message.
+// message.  Both tile loops have the guided epilogue, so the guided forms (a Geometry, a PairsGeometry) are this path too.
 struct FloatLine {
     using Elem = float; using Dist = float; using Norm = double;
     static constexpr match_slicing::Shape shape = match_slicing::kFloat;
@@ -256,15 +256,16 @@ struct FloatLine {
     static MatchBufs<Elem, Dist, Norm> &bufs(dlco_desc_ctx *c) { return c->m_float; }
     static void query_norms(const Elem *x, long ld, long n, int r, Norm *norm, hipStream_t s) { match_norms(x, ld, n, r, norm, s); }
     static void train_norms(const Elem *x, long ld, long n, int r, Norm *norm, hipStream_t s) { match_norms(x, ld, n, r, norm, s); }
-    static constexpr bool guided = true;                   // the tile loop has the guided epilogue
     static constexpr auto top2 = match_top2;
     // the batch forms: the norms of a whole table serve both sides; the bits of "no candidate" (+inf)
     static constexpr bool two_norms = false;
     static constexpr int32_t none = 0x7f800000;
+    // guide: nullptr, or the geometry of a guided launch, with the launch's entries and record rows in host memory as well
     static void top2_batch(const Elem *table, long ld, int r, const Norm *, const Norm *tnorm, const match_batch::Entry *ent, int n_ent, long wgs,
-                           long merge_wgs, int32_t *idx, Dist *sqdist, void *part, hipStream_t s)
+                           long merge_wgs, int32_t *idx, Dist *sqdist, void *part, const MatchGuide *guide, const match_batch::Entry *ent_host,
+                           const match_batch::GuideOff *off_host, hipStream_t s)
     {
-        match_top2_batch(table, ld, r, tnorm, ent, n_ent, wgs, merge_wgs, idx, sqdist, part, nullptr, nullptr, nullptr, s);
+        match_top2_batch(table, ld, r, tnorm, ent, n_ent, wgs, merge_wgs, idx, sqdist, part, guide, ent_host, off_host, s);
     }
 };
 struct ByteLine {
@@ -275,19 +276,19 @@ struct ByteLine {
     static void query_norms(const Elem *x, long ld, long n, int r, Norm *norm, hipStream_t s) { match_u8_norms(x, ld, n, r, false, norm, s); }
     // negated: the form the tile loop takes for train
     static void train_norms(const Elem *x, long ld, long n, int r, Norm *norm, hipStream_t s) { match_u8_norms(x, ld, n, r, true, norm, s); }
-    static constexpr bool guided = false;
-    static void top2(const Elem *query, long ldq, int nq, const Elem *train, long ldt, int nt, int r, const Norm *qnorm, const Norm *tnorm,
-                     int tiles_per_slice, int32_t *idx, Dist *sqdist, void *part, Dist *out, const MatchGuide *, hipStream_t s)
-    {
-        match_u8_top2(query, ldq, nq, train, ldt, nt, r, qnorm, tnorm, tiles_per_slice, idx, sqdist, part, out, s);
-    }
+    static constexpr auto top2 = match_u8_top2;
     // the batch forms: a whole table's norms in both signs, a launch each; the bits of "no candidate" (INT32_MAX)
     static constexpr bool two_norms = true;
     static constexpr int32_t none = INT32_MAX;
-    static constexpr auto top2_batch = match_u8_top2_batch;
+    static void top2_batch(const Elem *table, long ld, int r, const Norm *qnorm, const Norm *tnorm, const match_batch::Entry *ent, int n_ent,
+                           long wgs, long merge_wgs, int32_t *idx, Dist *sqdist, void *part, const MatchGuide *guide, const match_batch::Entry *,
+                           const match_batch::GuideOff *, hipStream_t s)
+    {
+        match_u8_top2_batch(table, ld, r, qnorm, tnorm, ent, n_ent, wgs, merge_wgs, idx, sqdist, part, guide, s);
+    }
 };
 
-// The geometry of a guided call (guided_rules.hpp), an optional argument of the float line's host path: the (x, y) of the
+// The geometry of a guided call (guided_rules.hpp), an optional argument of either line's host path: the (x, y) of the
 // rows of both tables at pitches in floats (device memory in match_on_device and match_device, host memory with pitch 2 in
 // match_host), the model (kGuideHomography: H, guided_rules.hpp; kGuideFundamental: F, guided_epipolar_rules.hpp), its nine
 // entries, the squared radius or threshold and the side the model applies to.
@@ -317,7 +318,6 @@ void match_on_device(dlco_desc_ctx *c, const typename L::Elem *q, long ldq, int6
                      int32_t *idx, typename L::Dist *sqdist, typename L::Dist *cross, double *ms, const Geometry *geo = nullptr)
 {
     auto &b = L::bufs(c);
-    DLCO_CHECK(!geo || L::guided, DLCO_ERR_INVALID, "guided matching exists for the float line only");
     EventPair ev;
     for (int64_t q0 = 0; q0 < nq; q0 += kMatchRows) {
         const int cnt = (int)std::min(kMatchRows, nq - q0);
@@ -440,7 +440,7 @@ bool match_pairs_args_ok(const int64_t *seg, int32_t n_img, const int32_t *pairs
     return true;
 }
 
-// The geometry of a guided batch (dlco_desc_match_pairs_guided*), an optional argument of the float line's batch path: xy, the
+// The geometry of a guided batch (dlco_desc_match_pairs_guided*), an optional argument of either line's batch path: xy, the
 // coordinates of the rows of the one table in device memory at a pitch of ldxy floats, M [n_pairs][9] the pairs' matrices on
 // the host, and the model, squared radius or threshold and side of every pair.
 struct PairsGeometry {
@@ -473,7 +473,6 @@ double match_pairs_on_device(dlco_desc_ctx *c, const typename L::Elem *table, lo
                              int64_t n_pairs = 0)
 {
     auto &b = L::bufs(c);
-    DLCO_CHECK(!geo || L::guided, DLCO_ERR_INVALID, "guided matching exists for the float line only");
     const int64_t n_rows = seg[n_img];
     const size_t ent_bytes = pl.entries.size() * sizeof(match_batch::Entry), fill_bytes = pl.fills.size() * sizeof(match_batch::Fill);
     const size_t off_bytes = geo ? pl.guide.size() * sizeof(match_batch::GuideOff) : 0, mat_bytes = geo ? (size_t)n_pairs * 9 * sizeof(double) : 0;
@@ -496,19 +495,15 @@ double match_pairs_on_device(dlco_desc_ctx *c, const typename L::Elem *table, lo
         if (L::two_norms) L::query_norms(table, ld, n_rows, r, b.qnorm.p, c->stream);
         match_fill(fill, (int)pl.fills.size(), pl.fill_rows, L::none, idx, sqdist, c->stream);
         for (const match_batch::Launch &la : pl.launches) {
-            if constexpr (L::guided) {
-                if (geo) {
-                    MatchGuide g;
-                    g.rec = b.rec.p; g.xy = geo->xy; g.ldxy = geo->ldxy; g.side = geo->side; g.model = geo->model; g.t2 = geo->t2;
-                    g.off = off + la.e0;
-                    match_records_batch(geo->xy, geo->ldxy, ent + la.e0, off + la.e0, (int)la.n, la.rec_rows, mat, geo->t2, geo->side, geo->model,
-                                        b.rec.p, c->stream);
-                    match_top2_batch(table, ld, r, b.tnorm.p, ent + la.e0, (int)la.n, la.wgs, la.merge_wgs, idx, sqdist, b.part.p, &g,
-                                     pl.entries.data() + la.e0, pl.guide.data() + la.e0, c->stream);
-                    continue;
-                }
+            MatchGuide g;
+            if (geo) {
+                g.rec = b.rec.p; g.xy = geo->xy; g.ldxy = geo->ldxy; g.side = geo->side; g.model = geo->model; g.t2 = geo->t2;
+                g.off = off + la.e0;
+                match_records_batch(geo->xy, geo->ldxy, ent + la.e0, off + la.e0, (int)la.n, la.rec_rows, mat, geo->t2, geo->side, geo->model,
+                                    b.rec.p, c->stream);
             }
-            L::top2_batch(table, ld, r, b.qnorm.p, b.tnorm.p, ent + la.e0, (int)la.n, la.wgs, la.merge_wgs, idx, sqdist, b.part.p, c->stream);
+            L::top2_batch(table, ld, r, b.qnorm.p, b.tnorm.p, ent + la.e0, (int)la.n, la.wgs, la.merge_wgs, idx, sqdist, b.part.p,
+                          geo ? &g : nullptr, pl.entries.data() + la.e0, geo ? pl.guide.data() + la.e0 : nullptr, c->stream);
         }
     });
 }
@@ -1433,8 +1428,11 @@ int dlco_desc_match_pairs_slices(dlco_desc_ctx *c, const int64_t *seg, int32_t n
     });
 }
 
-// ---- guided matching: the nearest two among the rows a homography admits (guided_rules.hpp; the guided epilogue of the tile
-// loop in kernels_match.hip).  The float line's host path with a Geometry; the byte line has no guided form. ----------------
+// ---- guided matching: the nearest two among the rows a two-view model admits: a homography (guided_rules.hpp) or a
+// fundamental matrix (guided_epipolar_rules.hpp; records on both sides), the guided epilogue of the tile loop in
+// kernels_match.hip and kernels_match_u8.hip.  Either line's host path with a Geometry: the calls below are one body per
+// form (host, device, matrix) over the line, and the model is an argument. ------------------------------------------------------
+extern "C++" {
 namespace {
 bool guided_args_ok(const float *qxy, const float *txy, const double *H, float radius, int32_t h_side)
 {
@@ -1443,95 +1441,59 @@ bool guided_args_ok(const float *qxy, const float *txy, const double *H, float r
         if (!std::isfinite(H[i])) return false;
     return true;
 }
-}  // namespace
 
-int dlco_desc_match_guided(dlco_desc_ctx *c, const float *query_host, const float *query_xy_host, int64_t nq, const float *train_host,
-                           const float *train_xy_host, int64_t nt, int32_t r, const double *H, float radius, int32_t h_side, int32_t *idx_host,
-                           float *sqdist_host)
+// a device table of the line: rows of at least r elements at a pitch of whole 16-byte pieces, 16-byte aligned
+template <typename L>
+bool device_table_ok(const typename L::Elem *table, int64_t ld, int32_t r)
+{
+    return ld >= r && ld % (kRowPitchBytes / (int64_t)sizeof(typename L::Elem)) == 0 && (uintptr_t)table % 16 == 0;
+}
+
+template <typename L>
+int match_guided_call(dlco_desc_ctx *c, const typename L::Elem *query_host, const float *query_xy_host, int64_t nq,
+                      const typename L::Elem *train_host, const float *train_xy_host, int64_t nt, int32_t r, const double *M, float radius,
+                      int32_t side, int model, int32_t *idx_host, typename L::Dist *sqdist_host)
 {
     if (!c || !match_args_ok(query_host, train_host, idx_host, sqdist_host, nq, nt, r)) return DLCO_ERR_INVALID;
-    if (!guided_args_ok(query_xy_host, train_xy_host, H, radius, h_side)) return DLCO_ERR_INVALID;
+    if (!guided_args_ok(query_xy_host, train_xy_host, M, radius, side)) return DLCO_ERR_INVALID;
     return guarded(c, [&] {
-        const Geometry geo{query_xy_host, 2, train_xy_host, 2, H, verify_rules::threshold_sq(radius), h_side, kGuideHomography};
-        match_host<FloatLine>(c, query_host, nq, train_host, nt, r, idx_host, sqdist_host, nullptr, &geo);
+        const Geometry geo{query_xy_host, 2, train_xy_host, 2, M, verify_rules::threshold_sq(radius), side, model};
+        match_host<L>(c, query_host, nq, train_host, nt, r, idx_host, sqdist_host, nullptr, &geo);
     });
 }
 
-int dlco_desc_match_guided_device(dlco_desc_ctx *c, const float *query_dev, int64_t ldq, const float *query_xy_dev, int64_t ldxy_q, int64_t nq,
-                                  const float *train_dev, int64_t ldt, const float *train_xy_dev, int64_t ldxy_t, int64_t nt, int32_t r,
-                                  const double *H, float radius, int32_t h_side, int32_t *idx_dev, float *sqdist_dev)
+template <typename L>
+int match_guided_device_call(dlco_desc_ctx *c, const typename L::Elem *query_dev, int64_t ldq, const float *query_xy_dev, int64_t ldxy_q,
+                             int64_t nq, const typename L::Elem *train_dev, int64_t ldt, const float *train_xy_dev, int64_t ldxy_t, int64_t nt,
+                             int32_t r, const double *M, float radius, int32_t side, int model, int32_t *idx_dev, typename L::Dist *sqdist_dev)
 {
     if (!c || !match_args_ok(query_dev, train_dev, idx_dev, sqdist_dev, nq, nt, r)) return DLCO_ERR_INVALID;
-    if (ldq < r || ldt < r || ldq % 4 != 0 || ldt % 4 != 0) return DLCO_ERR_INVALID;
-    if (((uintptr_t)query_dev | (uintptr_t)train_dev) % 16 != 0) return DLCO_ERR_INVALID;          // 16-byte rows
-    if (!guided_args_ok(query_xy_dev, train_xy_dev, H, radius, h_side) || ldxy_q < 2 || ldxy_t < 2) return DLCO_ERR_INVALID;
+    if (!device_table_ok<L>(query_dev, ldq, r) || !device_table_ok<L>(train_dev, ldt, r)) return DLCO_ERR_INVALID;
+    if (!guided_args_ok(query_xy_dev, train_xy_dev, M, radius, side) || ldxy_q < 2 || ldxy_t < 2) return DLCO_ERR_INVALID;
     if (((uintptr_t)query_xy_dev | (uintptr_t)train_xy_dev) % 4 != 0) return DLCO_ERR_INVALID;
     return guarded(c, [&] {
-        const Geometry geo{query_xy_dev, (long)ldxy_q, train_xy_dev, (long)ldxy_t, H, verify_rules::threshold_sq(radius), h_side, kGuideHomography};
-        match_device<FloatLine>(c, query_dev, (long)ldq, nq, train_dev, (long)ldt, nt, r, idx_dev, sqdist_dev, &geo);
+        const Geometry geo{query_xy_dev, (long)ldxy_q, train_xy_dev, (long)ldxy_t, M, verify_rules::threshold_sq(radius), side, model};
+        match_device<L>(c, query_dev, (long)ldq, nq, train_dev, (long)ldt, nt, r, idx_dev, sqdist_dev, &geo);
     });
 }
 
-int dlco_desc_cross_sqdists_guided(dlco_desc_ctx *c, const float *query_host, const float *query_xy_host, int64_t nq, const float *train_host,
-                                   const float *train_xy_host, int64_t nt, int32_t r, const double *H, float radius, int32_t h_side,
-                                   float *out_host)
+template <typename L>
+int cross_guided_call(dlco_desc_ctx *c, const typename L::Elem *query_host, const float *query_xy_host, int64_t nq,
+                      const typename L::Elem *train_host, const float *train_xy_host, int64_t nt, int32_t r, const double *M, float radius,
+                      int32_t side, int model, typename L::Dist *out_host)
 {
     if (!c || !match_args_ok(query_host, train_host, out_host, out_host, nq, nt, r)) return DLCO_ERR_INVALID;
     if (nq > ((int64_t)1 << 28) / nt) return DLCO_ERR_INVALID;
-    if (!guided_args_ok(query_xy_host, train_xy_host, H, radius, h_side)) return DLCO_ERR_INVALID;
+    if (!guided_args_ok(query_xy_host, train_xy_host, M, radius, side)) return DLCO_ERR_INVALID;
     return guarded(c, [&] {
-        const Geometry geo{query_xy_host, 2, train_xy_host, 2, H, verify_rules::threshold_sq(radius), h_side, kGuideHomography};
-        match_host<FloatLine>(c, query_host, nq, train_host, nt, r, nullptr, nullptr, out_host, &geo);
+        const Geometry geo{query_xy_host, 2, train_xy_host, 2, M, verify_rules::threshold_sq(radius), side, model};
+        match_host<L>(c, query_host, nq, train_host, nt, r, nullptr, nullptr, out_host, &geo);
     });
 }
 
-// ---- guided matching under a fundamental matrix (guided_epipolar_rules.hpp; GUIDED 3 and 4 of the tile loop): the same host
-// path with a Geometry of the other model, records on both sides -------------------------------------------------------------
-int dlco_desc_match_guided_epipolar(dlco_desc_ctx *c, const float *query_host, const float *query_xy_host, int64_t nq, const float *train_host,
-                                    const float *train_xy_host, int64_t nt, int32_t r, const double *F, float threshold, int32_t f_side,
-                                    int32_t *idx_host, float *sqdist_host)
-{
-    if (!c || !match_args_ok(query_host, train_host, idx_host, sqdist_host, nq, nt, r)) return DLCO_ERR_INVALID;
-    if (!guided_args_ok(query_xy_host, train_xy_host, F, threshold, f_side)) return DLCO_ERR_INVALID;
-    return guarded(c, [&] {
-        const Geometry geo{query_xy_host, 2, train_xy_host, 2, F, verify_rules::threshold_sq(threshold), f_side, kGuideFundamental};
-        match_host<FloatLine>(c, query_host, nq, train_host, nt, r, idx_host, sqdist_host, nullptr, &geo);
-    });
-}
-
-int dlco_desc_match_guided_epipolar_device(dlco_desc_ctx *c, const float *query_dev, int64_t ldq, const float *query_xy_dev, int64_t ldxy_q,
-                                           int64_t nq, const float *train_dev, int64_t ldt, const float *train_xy_dev, int64_t ldxy_t, int64_t nt,
-                                           int32_t r, const double *F, float threshold, int32_t f_side, int32_t *idx_dev, float *sqdist_dev)
-{
-    if (!c || !match_args_ok(query_dev, train_dev, idx_dev, sqdist_dev, nq, nt, r)) return DLCO_ERR_INVALID;
-    if (ldq < r || ldt < r || ldq % 4 != 0 || ldt % 4 != 0) return DLCO_ERR_INVALID;
-    if (((uintptr_t)query_dev | (uintptr_t)train_dev) % 16 != 0) return DLCO_ERR_INVALID;          // 16-byte rows
-    if (!guided_args_ok(query_xy_dev, train_xy_dev, F, threshold, f_side) || ldxy_q < 2 || ldxy_t < 2) return DLCO_ERR_INVALID;
-    if (((uintptr_t)query_xy_dev | (uintptr_t)train_xy_dev) % 4 != 0) return DLCO_ERR_INVALID;
-    return guarded(c, [&] {
-        const Geometry geo{query_xy_dev, (long)ldxy_q, train_xy_dev, (long)ldxy_t, F, verify_rules::threshold_sq(threshold), f_side,
-                           kGuideFundamental};
-        match_device<FloatLine>(c, query_dev, (long)ldq, nq, train_dev, (long)ldt, nt, r, idx_dev, sqdist_dev, &geo);
-    });
-}
-
-int dlco_desc_cross_sqdists_guided_epipolar(dlco_desc_ctx *c, const float *query_host, const float *query_xy_host, int64_t nq,
-                                            const float *train_host, const float *train_xy_host, int64_t nt, int32_t r, const double *F,
-                                            float threshold, int32_t f_side, float *out_host)
-{
-    if (!c || !match_args_ok(query_host, train_host, out_host, out_host, nq, nt, r)) return DLCO_ERR_INVALID;
-    if (nq > ((int64_t)1 << 28) / nt) return DLCO_ERR_INVALID;
-    if (!guided_args_ok(query_xy_host, train_xy_host, F, threshold, f_side)) return DLCO_ERR_INVALID;
-    return guarded(c, [&] {
-        const Geometry geo{query_xy_host, 2, train_xy_host, 2, F, verify_rules::threshold_sq(threshold), f_side, kGuideFundamental};
-        match_host<FloatLine>(c, query_host, nq, train_host, nt, r, nullptr, nullptr, out_host, &geo);
-    });
-}
-
-// ---- guided matching of many pairs in one call: the batch path with a PairsGeometry; a matrix per pair, one radius or
-// threshold and one side per call; the byte line has no such form -------------------------------------------------------------
-namespace {
-static bool pairs_guided_args_ok(const float *xy, const double *M, int64_t n_pairs, float radius, int32_t side)
+// guided matching of many pairs in one call: the batch path with a PairsGeometry; a matrix per pair, one radius or threshold
+// and one side per call
+bool pairs_guided_args_ok(const float *xy, const double *M, int64_t n_pairs, float radius, int32_t side)
 {
     if (!xy || !M || !std::isfinite(radius) || !(radius > 0.0f) || (side != 0 && side != 1)) return false;
     for (int64_t i = 0; i < 9 * n_pairs; i++)
@@ -1539,64 +1501,181 @@ static bool pairs_guided_args_ok(const float *xy, const double *M, int64_t n_pai
     return true;
 }
 
-static int match_pairs_guided_call(dlco_desc_ctx *c, const float *table_host, const float *xy_host, const int64_t *seg, int32_t n_img,
+template <typename L>
+int match_pairs_guided_call(dlco_desc_ctx *c, const typename L::Elem *table_host, const float *xy_host, const int64_t *seg, int32_t n_img,
                             const int32_t *pairs, int64_t n_pairs, int32_t r, const double *M, float radius, int32_t side, int model,
-                            int32_t *idx_host, float *sqdist_host)
+                            int32_t *idx_host, typename L::Dist *sqdist_host)
 {
     if (!c || !table_host || !idx_host || !sqdist_host || r < 1 || r > 1024 || !match_pairs_args_ok(seg, n_img, pairs, n_pairs))
         return DLCO_ERR_INVALID;
     if (!pairs_guided_args_ok(xy_host, M, n_pairs, radius, side)) return DLCO_ERR_INVALID;
     return guarded(c, [&] {
         const PairsGeometry geo{xy_host, 2, M, verify_rules::threshold_sq(radius), side, model};
-        match_pairs_host<FloatLine>(c, table_host, seg, n_img, pairs, n_pairs, r, idx_host, sqdist_host, &geo);
+        match_pairs_host<L>(c, table_host, seg, n_img, pairs, n_pairs, r, idx_host, sqdist_host, &geo);
     });
 }
 
-static int match_pairs_guided_device_call(dlco_desc_ctx *c, const float *table_dev, int64_t ld, const float *xy_dev, int64_t ldxy, const int64_t *seg,
-                                   int32_t n_img, const int32_t *pairs, int64_t n_pairs, int32_t r, const double *M, float radius,
-                                   int32_t side, int model, int32_t *idx_dev, float *sqdist_dev)
+template <typename L>
+int match_pairs_guided_device_call(dlco_desc_ctx *c, const typename L::Elem *table_dev, int64_t ld, const float *xy_dev, int64_t ldxy,
+                                   const int64_t *seg, int32_t n_img, const int32_t *pairs, int64_t n_pairs, int32_t r, const double *M,
+                                   float radius, int32_t side, int model, int32_t *idx_dev, typename L::Dist *sqdist_dev)
 {
     if (!c || !table_dev || !idx_dev || !sqdist_dev || r < 1 || r > 1024 || !match_pairs_args_ok(seg, n_img, pairs, n_pairs))
         return DLCO_ERR_INVALID;
-    if (ld < r || ld % 4 != 0 || (uintptr_t)table_dev % 16 != 0) return DLCO_ERR_INVALID;                  // 16-byte rows
+    if (!device_table_ok<L>(table_dev, ld, r)) return DLCO_ERR_INVALID;
     if (!pairs_guided_args_ok(xy_dev, M, n_pairs, radius, side) || ldxy < 2 || (uintptr_t)xy_dev % 4 != 0) return DLCO_ERR_INVALID;
     return guarded(c, [&] {
         const PairsGeometry geo{xy_dev, (long)ldxy, M, verify_rules::threshold_sq(radius), side, model};
-        match_pairs_device<FloatLine>(c, table_dev, (long)ld, seg, n_img, pairs, n_pairs, r, idx_dev, sqdist_dev, &geo);
+        match_pairs_device<L>(c, table_dev, (long)ld, seg, n_img, pairs, n_pairs, r, idx_dev, sqdist_dev, &geo);
     });
 }
 }  // namespace
+}  // extern "C++"
+
+// the float line: a homography, a fundamental matrix, and their forms for many pairs
+int dlco_desc_match_guided(dlco_desc_ctx *c, const float *query_host, const float *query_xy_host, int64_t nq, const float *train_host,
+        const float *train_xy_host, int64_t nt, int32_t r, const double *H, float radius, int32_t h_side, int32_t *idx_host, float *sqdist_host)
+{
+    return match_guided_call<FloatLine>(c, query_host, query_xy_host, nq, train_host, train_xy_host, nt, r, H, radius, h_side, kGuideHomography, idx_host,
+                                  sqdist_host);
+}
+
+int dlco_desc_match_guided_device(dlco_desc_ctx *c, const float *query_dev, int64_t ldq, const float *query_xy_dev, int64_t ldxy_q, int64_t nq,
+        const float *train_dev, int64_t ldt, const float *train_xy_dev, int64_t ldxy_t, int64_t nt, int32_t r, const double *H, float radius,
+        int32_t h_side, int32_t *idx_dev, float *sqdist_dev)
+{
+    return match_guided_device_call<FloatLine>(c, query_dev, ldq, query_xy_dev, ldxy_q, nq, train_dev, ldt, train_xy_dev, ldxy_t, nt, r, H, radius,
+                                         h_side, kGuideHomography, idx_dev, sqdist_dev);
+}
+
+int dlco_desc_cross_sqdists_guided(dlco_desc_ctx *c, const float *query_host, const float *query_xy_host, int64_t nq, const float *train_host,
+        const float *train_xy_host, int64_t nt, int32_t r, const double *H, float radius, int32_t h_side, float *out_host)
+{
+    return cross_guided_call<FloatLine>(c, query_host, query_xy_host, nq, train_host, train_xy_host, nt, r, H, radius, h_side, kGuideHomography, out_host);
+}
+
+int dlco_desc_match_guided_epipolar(dlco_desc_ctx *c, const float *query_host, const float *query_xy_host, int64_t nq, const float *train_host,
+        const float *train_xy_host, int64_t nt, int32_t r, const double *F, float threshold, int32_t f_side, int32_t *idx_host, float *sqdist_host)
+{
+    return match_guided_call<FloatLine>(c, query_host, query_xy_host, nq, train_host, train_xy_host, nt, r, F, threshold, f_side, kGuideFundamental, idx_host,
+                                  sqdist_host);
+}
+
+int dlco_desc_match_guided_epipolar_device(dlco_desc_ctx *c, const float *query_dev, int64_t ldq, const float *query_xy_dev, int64_t ldxy_q, int64_t nq,
+        const float *train_dev, int64_t ldt, const float *train_xy_dev, int64_t ldxy_t, int64_t nt, int32_t r, const double *F, float threshold,
+        int32_t f_side, int32_t *idx_dev, float *sqdist_dev)
+{
+    return match_guided_device_call<FloatLine>(c, query_dev, ldq, query_xy_dev, ldxy_q, nq, train_dev, ldt, train_xy_dev, ldxy_t, nt, r, F, threshold,
+                                         f_side, kGuideFundamental, idx_dev, sqdist_dev);
+}
+
+int dlco_desc_cross_sqdists_guided_epipolar(dlco_desc_ctx *c, const float *query_host, const float *query_xy_host, int64_t nq, const float *train_host,
+        const float *train_xy_host, int64_t nt, int32_t r, const double *F, float threshold, int32_t f_side, float *out_host)
+{
+    return cross_guided_call<FloatLine>(c, query_host, query_xy_host, nq, train_host, train_xy_host, nt, r, F, threshold, f_side, kGuideFundamental, out_host);
+}
 
 int dlco_desc_match_pairs_guided(dlco_desc_ctx *c, const float *table_host, const float *xy_host, const int64_t *seg, int32_t n_img,
-                                 const int32_t *pairs, int64_t n_pairs, int32_t r, const double *H, float radius, int32_t h_side,
-                                 int32_t *idx_host, float *sqdist_host)
+        const int32_t *pairs, int64_t n_pairs, int32_t r, const double *H, float radius, int32_t h_side, int32_t *idx_host, float *sqdist_host)
 {
-    return match_pairs_guided_call(c, table_host, xy_host, seg, n_img, pairs, n_pairs, r, H, radius, h_side, kGuideHomography, idx_host,
-                                   sqdist_host);
+    return match_pairs_guided_call<FloatLine>(c, table_host, xy_host, seg, n_img, pairs, n_pairs, r, H, radius, h_side, kGuideHomography, idx_host,
+                                        sqdist_host);
 }
 
 int dlco_desc_match_pairs_guided_device(dlco_desc_ctx *c, const float *table_dev, int64_t ld, const float *xy_dev, int64_t ldxy, const int64_t *seg,
-                                        int32_t n_img, const int32_t *pairs, int64_t n_pairs, int32_t r, const double *H, float radius,
-                                        int32_t h_side, int32_t *idx_dev, float *sqdist_dev)
+        int32_t n_img, const int32_t *pairs, int64_t n_pairs, int32_t r, const double *H, float radius, int32_t h_side, int32_t *idx_dev,
+        float *sqdist_dev)
 {
-    return match_pairs_guided_device_call(c, table_dev, ld, xy_dev, ldxy, seg, n_img, pairs, n_pairs, r, H, radius, h_side, kGuideHomography,
-                                          idx_dev, sqdist_dev);
+    return match_pairs_guided_device_call<FloatLine>(c, table_dev, ld, xy_dev, ldxy, seg, n_img, pairs, n_pairs, r, H, radius, h_side, kGuideHomography,
+                                               idx_dev, sqdist_dev);
 }
 
 int dlco_desc_match_pairs_guided_epipolar(dlco_desc_ctx *c, const float *table_host, const float *xy_host, const int64_t *seg, int32_t n_img,
-                                          const int32_t *pairs, int64_t n_pairs, int32_t r, const double *F, float threshold, int32_t f_side,
-                                          int32_t *idx_host, float *sqdist_host)
+        const int32_t *pairs, int64_t n_pairs, int32_t r, const double *F, float threshold, int32_t f_side, int32_t *idx_host, float *sqdist_host)
 {
-    return match_pairs_guided_call(c, table_host, xy_host, seg, n_img, pairs, n_pairs, r, F, threshold, f_side, kGuideFundamental, idx_host,
-                                   sqdist_host);
+    return match_pairs_guided_call<FloatLine>(c, table_host, xy_host, seg, n_img, pairs, n_pairs, r, F, threshold, f_side, kGuideFundamental, idx_host,
+                                        sqdist_host);
 }
 
-int dlco_desc_match_pairs_guided_epipolar_device(dlco_desc_ctx *c, const float *table_dev, int64_t ld, const float *xy_dev, int64_t ldxy,
-                                                 const int64_t *seg, int32_t n_img, const int32_t *pairs, int64_t n_pairs, int32_t r,
-                                                 const double *F, float threshold, int32_t f_side, int32_t *idx_dev, float *sqdist_dev)
+int dlco_desc_match_pairs_guided_epipolar_device(dlco_desc_ctx *c, const float *table_dev, int64_t ld, const float *xy_dev, int64_t ldxy, const int64_t *seg,
+        int32_t n_img, const int32_t *pairs, int64_t n_pairs, int32_t r, const double *F, float threshold, int32_t f_side, int32_t *idx_dev,
+        float *sqdist_dev)
 {
-    return match_pairs_guided_device_call(c, table_dev, ld, xy_dev, ldxy, seg, n_img, pairs, n_pairs, r, F, threshold, f_side,
-                                          kGuideFundamental, idx_dev, sqdist_dev);
+    return match_pairs_guided_device_call<FloatLine>(c, table_dev, ld, xy_dev, ldxy, seg, n_img, pairs, n_pairs, r, F, threshold, f_side, kGuideFundamental,
+                                               idx_dev, sqdist_dev);
+}
+
+// the byte line: the same calls on byte tables, integer distances and pitches in bytes
+int dlco_desc_match_guided_u8(dlco_desc_ctx *c, const uint8_t *query_host, const float *query_xy_host, int64_t nq, const uint8_t *train_host,
+        const float *train_xy_host, int64_t nt, int32_t r, const double *H, float radius, int32_t h_side, int32_t *idx_host, int32_t *sqdist_host)
+{
+    return match_guided_call<ByteLine>(c, query_host, query_xy_host, nq, train_host, train_xy_host, nt, r, H, radius, h_side, kGuideHomography, idx_host,
+                                  sqdist_host);
+}
+
+int dlco_desc_match_guided_u8_device(dlco_desc_ctx *c, const uint8_t *query_dev, int64_t ldq, const float *query_xy_dev, int64_t ldxy_q, int64_t nq,
+        const uint8_t *train_dev, int64_t ldt, const float *train_xy_dev, int64_t ldxy_t, int64_t nt, int32_t r, const double *H, float radius,
+        int32_t h_side, int32_t *idx_dev, int32_t *sqdist_dev)
+{
+    return match_guided_device_call<ByteLine>(c, query_dev, ldq, query_xy_dev, ldxy_q, nq, train_dev, ldt, train_xy_dev, ldxy_t, nt, r, H, radius,
+                                         h_side, kGuideHomography, idx_dev, sqdist_dev);
+}
+
+int dlco_desc_cross_sqdists_guided_u8(dlco_desc_ctx *c, const uint8_t *query_host, const float *query_xy_host, int64_t nq, const uint8_t *train_host,
+        const float *train_xy_host, int64_t nt, int32_t r, const double *H, float radius, int32_t h_side, int32_t *out_host)
+{
+    return cross_guided_call<ByteLine>(c, query_host, query_xy_host, nq, train_host, train_xy_host, nt, r, H, radius, h_side, kGuideHomography, out_host);
+}
+
+int dlco_desc_match_guided_epipolar_u8(dlco_desc_ctx *c, const uint8_t *query_host, const float *query_xy_host, int64_t nq, const uint8_t *train_host,
+        const float *train_xy_host, int64_t nt, int32_t r, const double *F, float threshold, int32_t f_side, int32_t *idx_host, int32_t *sqdist_host)
+{
+    return match_guided_call<ByteLine>(c, query_host, query_xy_host, nq, train_host, train_xy_host, nt, r, F, threshold, f_side, kGuideFundamental, idx_host,
+                                  sqdist_host);
+}
+
+int dlco_desc_match_guided_epipolar_u8_device(dlco_desc_ctx *c, const uint8_t *query_dev, int64_t ldq, const float *query_xy_dev, int64_t ldxy_q, int64_t nq,
+        const uint8_t *train_dev, int64_t ldt, const float *train_xy_dev, int64_t ldxy_t, int64_t nt, int32_t r, const double *F, float threshold,
+        int32_t f_side, int32_t *idx_dev, int32_t *sqdist_dev)
+{
+    return match_guided_device_call<ByteLine>(c, query_dev, ldq, query_xy_dev, ldxy_q, nq, train_dev, ldt, train_xy_dev, ldxy_t, nt, r, F, threshold,
+                                         f_side, kGuideFundamental, idx_dev, sqdist_dev);
+}
+
+int dlco_desc_cross_sqdists_guided_epipolar_u8(dlco_desc_ctx *c, const uint8_t *query_host, const float *query_xy_host, int64_t nq, const uint8_t *train_host,
+        const float *train_xy_host, int64_t nt, int32_t r, const double *F, float threshold, int32_t f_side, int32_t *out_host)
+{
+    return cross_guided_call<ByteLine>(c, query_host, query_xy_host, nq, train_host, train_xy_host, nt, r, F, threshold, f_side, kGuideFundamental, out_host);
+}
+
+int dlco_desc_match_pairs_guided_u8(dlco_desc_ctx *c, const uint8_t *table_host, const float *xy_host, const int64_t *seg, int32_t n_img,
+        const int32_t *pairs, int64_t n_pairs, int32_t r, const double *H, float radius, int32_t h_side, int32_t *idx_host, int32_t *sqdist_host)
+{
+    return match_pairs_guided_call<ByteLine>(c, table_host, xy_host, seg, n_img, pairs, n_pairs, r, H, radius, h_side, kGuideHomography, idx_host,
+                                        sqdist_host);
+}
+
+int dlco_desc_match_pairs_guided_u8_device(dlco_desc_ctx *c, const uint8_t *table_dev, int64_t ld, const float *xy_dev, int64_t ldxy, const int64_t *seg,
+        int32_t n_img, const int32_t *pairs, int64_t n_pairs, int32_t r, const double *H, float radius, int32_t h_side, int32_t *idx_dev,
+        int32_t *sqdist_dev)
+{
+    return match_pairs_guided_device_call<ByteLine>(c, table_dev, ld, xy_dev, ldxy, seg, n_img, pairs, n_pairs, r, H, radius, h_side, kGuideHomography,
+                                               idx_dev, sqdist_dev);
+}
+
+int dlco_desc_match_pairs_guided_epipolar_u8(dlco_desc_ctx *c, const uint8_t *table_host, const float *xy_host, const int64_t *seg, int32_t n_img,
+        const int32_t *pairs, int64_t n_pairs, int32_t r, const double *F, float threshold, int32_t f_side, int32_t *idx_host, int32_t *sqdist_host)
+{
+    return match_pairs_guided_call<ByteLine>(c, table_host, xy_host, seg, n_img, pairs, n_pairs, r, F, threshold, f_side, kGuideFundamental, idx_host,
+                                        sqdist_host);
+}
+
+int dlco_desc_match_pairs_guided_epipolar_u8_device(dlco_desc_ctx *c, const uint8_t *table_dev, int64_t ld, const float *xy_dev, int64_t ldxy, const int64_t *seg,
+        int32_t n_img, const int32_t *pairs, int64_t n_pairs, int32_t r, const double *F, float threshold, int32_t f_side, int32_t *idx_dev,
+        int32_t *sqdist_dev)
+{
+    return match_pairs_guided_device_call<ByteLine>(c, table_dev, ld, xy_dev, ldxy, seg, n_img, pairs, n_pairs, r, F, threshold, f_side, kGuideFundamental,
+                                               idx_dev, sqdist_dev);
 }
 
 // The four single calls are the _pairs forms below with one pair, moff = {0, m}, after their own check of the list: their
@@ -1792,7 +1871,7 @@ int dlco_desc_cross_sqdists_u8(dlco_desc_ctx *c, const uint8_t *query_u8, int64_
 // milliseconds the kernels of the last dlco_desc_compute* / dlco_desc_describe* call took (HIP events): transform and
 // pooling, plus the projection for describe and the sampling for the keypoint calls (extract_patches: the sampling alone);
 // the pair calls add their distance kernel; after a match call, float or byte, its kernels (norms, top two, merge, and for
-// the guided forms the record kernel); the _u8
+// the guided forms, float or byte, single or many pairs, the record kernels: norms, record kernels, tile loop, merge); the _u8
 // forms of describe add their quantising kernel; after an orient call the orientation kernel and the integral image when the
 // call formed it; after a detect call the detector's kernels (the integral image when the call
 // formed it, the octaves, the selection); after a verify or verify_pairs call every kernel of every launch of the call: for

@@ -584,13 +584,15 @@ void match_top2_batch(const float *table, long ld, int r, const double *norm, co
 void match_records_batch(const float *xy, long ldxy, const match_batch::Entry *ent, const match_batch::GuideOff *off, int n_ent, long rows,
                          const double *M, double t2, int side, int model, double *rec, hipStream_t s);
 void match_u8_top2_batch(const uint8_t *table, long ld, int r, const int32_t *qnorm, const int32_t *tneg, const match_batch::Entry *ent, int n_ent,
-                         long wgs, long merge_wgs, int32_t *idx, int32_t *sqdist, void *part, hipStream_t s);
+                         long wgs, long merge_wgs, int32_t *idx, int32_t *sqdist, void *part, const MatchGuide *guide, hipStream_t s);
 void match_fill(const match_batch::Fill *fill, int n_fill, long rows, int32_t none, int32_t *idx, void *sqdist, hipStream_t s);
-// byte descriptors (kernels_match_u8.hip; the quantiser is quant_rules.hpp): float rows to bytes, and the match of byte tables
+// byte descriptors (kernels_match_u8.hip; the quantiser is quant_rules.hpp): float rows to bytes, and the match of byte tables;
+// guide as match_top2 and match_top2_batch take it: the records and coordinates are the float line's
 void desc_quantize_rows(const float *Y, long ldy, int n, int r, float scale, const float *offset, uint8_t *out, long ldo, hipStream_t s);
 void match_u8_norms(const uint8_t *x, long ld, long n, int r, bool negate, int32_t *norm, hipStream_t s);
 void match_u8_top2(const uint8_t *query, long ldq, int nq, const uint8_t *train, long ldt, int nt, int r, const int32_t *qnorm,
-                   const int32_t *tneg, int tiles_per_slice, int32_t *idx, int32_t *sqdist, void *part, int32_t *out, hipStream_t s);
+                   const int32_t *tneg, int tiles_per_slice, int32_t *idx, int32_t *sqdist, void *part, int32_t *out, const MatchGuide *guide,
+                   hipStream_t s);
 // keypoint patches (kernels_patch.hip;the frames and the sampling rule are patch_rules.hpp)
 int patch_stage_bytes(const patch_rules::Frame *frames_host, int n, int W, int H);
 void patch_sample(const uint8_t *img, int W, int H, long pitch, const patch_rules::Frame *frames, int n, uint8_t *patches, int lds_bytes,

@@ -7,6 +7,9 @@
 //   match_u8_kernel         d(i,j) = |a_q|^2 + |a_t|^2 - 2 a_q.a_t in int32, the dot products on v_mfma_i32_16x16x64_i8;
 //                           then either the running top two per query, or (STORE) the matrix itself: one tile loop, two
 //                           epilogues, so the matrix and the top two cannot disagree
+//   match_u8_kernel<.., GUIDED>   the guided forms (dlco_desc_match_guided_u8, _epipolar_u8 and their kin): the same tile loop with a
+//                           third epilogue, the verdict of guided_rules.hpp / guided_epipolar_rules.hpp on the records the float
+//                           line's record kernels write (kernels_match.hip); GUIDED as in match_top2_kernel, stated at the kernel
 //   match_u8_merge_kernel   the top two of a query over the S slices of train (the slicing rule: match_slices.hpp)
 //   match_u8_kernel<.., BATCH>, match_u8_merge_batch_kernel   the batch forms (dlco_desc_match_pairs_u8, the plan: match_batch.hpp):
 //                           many (query image, train image) pairs over one segmented table in one 1-D launch; a workgroup
@@ -25,6 +28,8 @@
 // ceil(r / 16) * 16 <= ld, the bytes at and beyond r are replaced by zeros after the flip.  Every load is unconditional
 // and in bounds (a row or piece beyond the edge reads a valid one and is replaced by zeros), stores are masked.
 #include "dlco_internal.hpp"
+#include "guided_rules.hpp"
+#include "guided_epipolar_rules.hpp"
 #include "match_batch.hpp"
 #include "match_slices.hpp"
 #include "quant_rules.hpp"
@@ -32,6 +37,7 @@
 namespace dlco {
 
 typedef int i32x4 __attribute__((ext_vector_type(4)));
+typedef double f64x2 __attribute__((ext_vector_type(2)));
 
 namespace {
 
@@ -108,17 +114,44 @@ __device__ __forceinline__ int batch_entry_of(const match_batch::Entry *__restri
 // offset of the entry's partials (part stays null when the entry has one slice), its query block and its slice.  Tiles are
 // counted from the slice's first row, which need not be tile-aligned in the table; the rows at and beyond jend belong to
 // the next image (or lie beyond the table) and are never read: the loads clamp to jbeg.  The loop below is the plain form's.
-template <bool STORE, bool MULTI, bool BATCH = false>
+//   GUIDED 1 .. 4 (dlco_desc_match_guided*_u8; the meaning of kernels_match.hip's): the same tile loop with a third epilogue.  A
+// candidate that guided_rules::admits (1: the queries carry the records, h_side 0; 2: train does) or guided_epipolar::admits
+// (3: the queries are src, f_side 0; 4: train is) does not admit takes the key kEmpty before it meets the running top two, and
+// then loses as a row beyond the slice does; STORE writes INT32_MAX for it.  The geometry is the float line's: records [n][4]
+// doubles from the record kernels of kernels_match.hip, (x, y) floats widened when they are staged, t2 of the epipolar model
+// from MatchGuide.  The workgroup's queries' geometry is written to LDS once, before the loop; a train tile's is staged
+// beside Tn, both buffers, under the same barrier.  Per 16-row block a lane reads the geometry of its four train rows once
+// and that of its query of every block, and keeps the sixteen verdicts as a bit mask (bit 4 qb + reg).  MULTI forms them
+// with the last chunk of a tile.  BATCH rebinds records and coordinates to the entry's own, as match_top2_kernel does.
+struct NoGuide {};
+template <int GUIDED> struct GuideArg { using type = MatchGuide; };
+template <> struct GuideArg<0> { using type = NoGuide; };      // the plain forms keep their arguments
+
+template <bool STORE, bool MULTI, int GUIDED = 0, bool BATCH = false>
 __global__ __launch_bounds__(UTH) void match_u8_kernel(const uint8_t *__restrict__ query, long ldq, int nq, const uint8_t *__restrict__ train,
                                                        long ldt, int nt, int r, const int32_t *__restrict__ qnorm,
                                                        const int32_t *__restrict__ tneg, int tiles_per_slice, int32_t *__restrict__ idx,
                                                        int32_t *__restrict__ sqdist, i32x4 *__restrict__ part, int32_t *__restrict__ out,
-                                                       const match_batch::Entry *__restrict__ ent, int n_ent)
+                                                       const match_batch::Entry *__restrict__ ent, int n_ent,
+                                                       const typename GuideArg<GUIDED>::type g)
 {
     unsigned qblk = blockIdx.x, slice = blockIdx.y;
+    const double *grec = nullptr, *gqrec = nullptr;        // GUIDED: the records and the coordinates the loop reads
+    const float *gxy = nullptr;
+    long gld = 0;
+    double gt2 = 0.0;
+    if constexpr (GUIDED != 0) { grec = g.rec; gqrec = g.qrec; gxy = g.xy; gld = g.ldxy; gt2 = g.t2; }
     if constexpr (BATCH) {
         const int wg = (int)blockIdx.x;
-        const match_batch::Entry e = ent[batch_entry_of(ent, n_ent, wg, [](const match_batch::Entry &x) { return x.wg0; })];
+        const int ei = batch_entry_of(ent, n_ent, wg, [](const match_batch::Entry &x) { return x.wg0; });
+        const match_batch::Entry e = ent[ei];
+        if constexpr (GUIDED != 0) {
+            const match_batch::GuideOff o = g.off[ei];
+            const double *qr = g.rec + 4 * o.rec0, *tr = qr + 4 * (long)o.nqrec;
+            grec = GUIDED == 1 ? qr : tr;
+            gqrec = qr;
+            gxy = g.xy + (GUIDED == 1 ? e.t0 : e.q0) * g.ldxy;
+        }
         const unsigned w = (unsigned)(wg - e.wg0);
         slice = w / (unsigned)e.qblocks;
         qblk = w - slice * (unsigned)e.qblocks;
@@ -130,6 +163,10 @@ __global__ __launch_bounds__(UTH) void match_u8_kernel(const uint8_t *__restrict
     }
     __shared__ __attribute__((aligned(16))) uint8_t Bs[2][UT * UP];            // the staged tile, flipped and masked when stored
     __shared__ __attribute__((aligned(16))) int32_t Tn[2][UT];                 // -|a_t|^2 of its rows, kEmpty beyond the slice
+    constexpr int CW = GUIDED >= 2 ? 4 : 2;                // doubles of geometry a train row brings: (x, y) or a record
+    constexpr int QW = GUIDED == 1 || GUIDED >= 3 ? 4 : 2; // and a query
+    __shared__ __attribute__((aligned(16))) double Tg[GUIDED ? 2 : 1][GUIDED ? UT * CW : 1];   // GUIDED: the tile's geometry, staged with it,
+    __shared__ __attribute__((aligned(16))) double Qg[GUIDED ? UQ * QW : 1];   // and the workgroup's queries': written once, before the loop
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int li = lane & 15, lg = lane >> 4;
     const int q0 = qblk * UQ + wave * UWQ;
@@ -146,6 +183,7 @@ __global__ __launch_bounds__(UTH) void match_u8_kernel(const uint8_t *__restrict
     const int lrow = tid >> 3, lseg = tid & 7;
     i32x4 rb[UT / 32];
     int rtn;
+    double rg[CW];
     auto gload = [&](int step) {
         step = min(step, nstep - 1);                       // past the end: the last step again, never used
         const int tile = step / nch, kc = step - tile * nch;
@@ -162,11 +200,77 @@ __global__ __launch_bounds__(UTH) void match_u8_kernel(const uint8_t *__restrict
         const long jn = jt + (tid & (UT - 1));
         const int tn = tneg[jn < jend ? jn : (long)jbeg];
         rtn = jn < jend ? tn : kEmpty;
+        if constexpr (GUIDED != 0) {                       // a row beyond the slice: the slice's first row's, never consulted
+            const long js = jn < jend ? jn : (long)jbeg;
+            if constexpr (GUIDED == 1) {
+                const float *p = gxy + js * gld;
+                rg[0] = (double)p[0]; rg[1] = (double)p[1];
+            } else {
+                const f64x2 a = *reinterpret_cast<const f64x2 *>(grec + 4 * js), b = *reinterpret_cast<const f64x2 *>(grec + 4 * js + 2);
+                rg[0] = a[0]; rg[1] = a[1]; rg[2] = b[0]; rg[3] = b[1];
+            }
+        }
     };
     auto lstore = [&](int buf) {
 #pragma unroll
         for (int u = 0; u < UT / 32; u++) *reinterpret_cast<i32x4 *>(&Bs[buf][(lrow + 32 * u) * UP + 16 * lseg]) = rb[u];
-        if (tid < UT) Tn[buf][tid] = rtn;
+        if (tid < UT) {
+            Tn[buf][tid] = rtn;
+            if constexpr (GUIDED != 0) {
+#pragma unroll
+                for (int e = 0; e < CW; e += 2) *reinterpret_cast<f64x2 *>(&Tg[buf][tid * CW + e]) = f64x2{rg[e], rg[e + 1]};
+            }
+        }
+    };
+    // GUIDED: the geometry of one row, a record or (x, y) in v[0], v[1]; that of row `row` of the staged tile, and that of the
+    // lane's query of block qb.  The empty asm hides from the compiler that the queries' address does not change over the
+    // tile loop: hoisted out of it, the four records would sit in registers for the whole loop.
+    struct Geom { double v[4]; };
+    auto tgeom = [&](int buf, int row) {
+        Geom o{};
+#pragma unroll
+        for (int e = 0; e < CW; e += 2) {
+            const f64x2 t = *reinterpret_cast<const f64x2 *>(&Tg[buf][row * CW + e]);
+            o.v[e] = t[0]; o.v[e + 1] = t[1];
+        }
+        return o;
+    };
+    auto qgeom = [&](int qb) {
+        Geom o{};
+        int qoff = (wave * UWQ + 16 * qb + li) * QW;
+        asm volatile("" : "+v"(qoff));
+#pragma unroll
+        for (int e = 0; e < QW; e += 2) {
+            const f64x2 t = *reinterpret_cast<const f64x2 *>(&Qg[qoff + e]);
+            o.v[e] = t[0]; o.v[e + 1] = t[1];
+        }
+        return o;
+    };
+    // the verdict on a query and a train row, whichever of the two carries the record (1, 2) or is src (3, 4)
+    auto admits = [&](const Geom &q, const Geom &t) -> bool {
+        if constexpr (GUIDED == 1) return guided_rules::admits(guided_rules::Rec{q.v[0], q.v[1], q.v[2], q.v[3]}, t.v[0], t.v[1]);
+        else if constexpr (GUIDED == 2) return guided_rules::admits(guided_rules::Rec{t.v[0], t.v[1], t.v[2], t.v[3]}, q.v[0], q.v[1]);
+        else if constexpr (GUIDED == 3)
+            return guided_epipolar::admits(guided_epipolar::SrcRec{q.v[0], q.v[1], q.v[2], q.v[3]},
+                                           guided_epipolar::DstRec{t.v[0], t.v[1], t.v[2], t.v[3]}, gt2);
+        else if constexpr (GUIDED == 4)
+            return guided_epipolar::admits(guided_epipolar::SrcRec{t.v[0], t.v[1], t.v[2], t.v[3]},
+                                           guided_epipolar::DstRec{q.v[0], q.v[1], q.v[2], q.v[3]}, gt2);
+        else return true;
+    };
+    // which of the sixteen entries of the 16-row block sub of the staged tile the rule admits: bit 4 qb + reg
+    auto admit_mask = [&](int buf, int sub) -> unsigned {
+        unsigned m = 0;
+        Geom t[4];
+#pragma unroll
+        for (int reg = 0; reg < 4; reg++) t[reg] = tgeom(buf, 16 * sub + 4 * lg + reg);
+#pragma unroll
+        for (int qb = 0; qb < UQB; qb++) {
+            const Geom q = qgeom(qb);
+#pragma unroll
+            for (int reg = 0; reg < 4; reg++) m |= (admits(q, t[reg]) ? 1u : 0u) << (4 * qb + reg);
+        }
+        return m;
     };
 
     // B fragments of one k chunk: lane (li, lg) holds query q0 + 16 qb + li at the bytes 64 c + 16 lg ... + 15 of the chunk
@@ -187,6 +291,20 @@ __global__ __launch_bounds__(UTH) void match_u8_kernel(const uint8_t *__restrict
     };
     if (!MULTI) bload(0);
 
+    // GUIDED: the geometry of the workgroup's queries, a record (1; 3, 4: from qrec) or (x, y) (2), a thread per query; the
+    // barrier before the loop orders it
+    if constexpr (GUIDED != 0) {
+        const long row = (long)qblk * UQ + tid;
+        const long rs = row < nq ? row : 0;
+        if constexpr (QW == 4) {
+            const double *qr = GUIDED == 1 ? grec : gqrec;
+            *reinterpret_cast<f64x2 *>(&Qg[tid * 4]) = *reinterpret_cast<const f64x2 *>(qr + 4 * rs);
+            *reinterpret_cast<f64x2 *>(&Qg[tid * 4 + 2]) = *reinterpret_cast<const f64x2 *>(qr + 4 * rs + 2);
+        } else {
+            const float *p = gxy + rs * gld;
+            *reinterpret_cast<f64x2 *>(&Qg[tid * 2]) = f64x2{(double)p[0], (double)p[1]};
+        }
+    }
     int qn[UQB];                                           // STORE: |a_q|^2 of the lane's query of every block
     if (STORE) {
 #pragma unroll
@@ -203,15 +321,19 @@ __global__ __launch_bounds__(UTH) void match_u8_kernel(const uint8_t *__restrict
     for (int qb = 0; qb < UQB; qb++) { b1[qb] = kEmpty; b2[qb] = kEmpty; c1[qb] = -1; c2[qb] = -1; }
 
     // the four results of one MFMA: query q0 + 16 qb + li against the train rows jt + 16 sub + 4 lg + reg
-    auto entries = [&](const i32x4 dot, int qb, const i32x4 tn, int blk, long jrow0) {
+    // GUIDED: bit reg of m is the verdict of the entry
+    auto entries = [&](const i32x4 dot, int qb, const i32x4 tn, int blk, long jrow0, unsigned m) {
 #pragma unroll
         for (int reg = 0; reg < 4; reg++) {
-            const int key = (dot[reg] << 1) + tn[reg];
+            int key = (dot[reg] << 1) + tn[reg];
             if (STORE) {
                 const int q = q0 + 16 * qb + li;
                 const long j = jrow0 + reg;
-                if (q < nq && j < jend) out[(long)q * nt + j] = qn[qb] - key;
+                int d = qn[qb] - key;
+                if constexpr (GUIDED != 0) d = ((m >> reg) & 1u) != 0 ? d : INT_MAX;
+                if (q < nq && j < jend) out[(long)q * nt + j] = d;
             } else {
+                if constexpr (GUIDED != 0) key = ((m >> reg) & 1u) != 0 ? key : kEmpty;
                 const int cnt = blk * 4 + reg;
                 const bool first = key > b1[qb], second = key > b2[qb];
                 c2[qb] = first ? c1[qb] : (second ? cnt : c2[qb]);
@@ -239,13 +361,17 @@ __global__ __launch_bounds__(UTH) void match_u8_kernel(const uint8_t *__restrict
                 const i32x4 a0 = *reinterpret_cast<const i32x4 *>(ap), a1 = *reinterpret_cast<const i32x4 *>(ap + 64);
                 const i32x4 tn = *reinterpret_cast<const i32x4 *>(&Tn[buf][16 * sub + 4 * lg]);
                 const long jrow0 = (long)jbeg + (long)tile * UT + 16 * sub + 4 * lg;
+                unsigned adm = 0;
+                if constexpr (GUIDED != 0) {
+                    if (!MULTI || kc == nch - 1) adm = admit_mask(buf, sub);
+                }
 #pragma unroll
                 for (int qb = 0; qb < UQB; qb++) {
                     i32x4 d = MULTI ? (kc == 0 ? zacc : acc[MULTI ? sub : 0][MULTI ? qb : 0]) : zacc;
                     d = __builtin_amdgcn_mfma_i32_16x16x64_i8(a0, fb[qb][0], d, 0, 0, 0);
                     d = __builtin_amdgcn_mfma_i32_16x16x64_i8(a1, fb[qb][1], d, 0, 0, 0);
                     if (MULTI) acc[MULTI ? sub : 0][MULTI ? qb : 0] = d;
-                    if (!MULTI || kc == nch - 1) entries(d, qb, tn, tile * USUB + sub, jrow0);
+                    if (!MULTI || kc == nch - 1) entries(d, qb, tn, tile * USUB + sub, jrow0, adm >> (4 * qb));
                 }
             }
         }
@@ -321,6 +447,12 @@ __global__ __launch_bounds__(256) void match_u8_merge_kernel(const i32x4 *__rest
     sqdist[2 * (long)row + 1] = me.j2 < 0 ? INT_MAX : n - me.k2;
 }
 
+// what a launch passes for the guide: the geometry, or nothing at all for the plain forms
+template <int GUIDED> typename GuideArg<GUIDED>::type guide_arg(const MatchGuide &g)
+{
+    if constexpr (GUIDED != 0) return g; else return NoGuide{};
+}
+
 constexpr int NTH = 256;               // four rows per workgroup, one wave each
 
 __global__ __launch_bounds__(NTH) void match_u8_norms_kernel(const uint8_t *__restrict__ x, long ld, long n, int r, int negate,
@@ -374,20 +506,31 @@ void match_u8_norms(const uint8_t *x, long ld, long n, int r, bool negate, int32
 
 // query [nq][ldq], train [nt][ldt], qnorm = |a_q|^2 and tneg = -|a_t|^2 from match_u8_norms.  out != nullptr: the matrix
 // out[nq][nt]; else idx / sqdist [nq][2], through part [slices][nq] (16 bytes each) when tiles_per_slice leaves more than
-// one slice.
+// one slice.  guide: nullptr, or the geometry of the guided form (dlco_internal.hpp), as match_top2 takes it.
 void match_u8_top2(const uint8_t *query, long ldq, int nq, const uint8_t *train, long ldt, int nt, int r, const int32_t *qnorm,
-                   const int32_t *tneg, int tiles_per_slice, int32_t *idx, int32_t *sqdist, void *part, int32_t *out, hipStream_t s)
+                   const int32_t *tneg, int tiles_per_slice, int32_t *idx, int32_t *sqdist, void *part, int32_t *out, const MatchGuide *guide,
+                   hipStream_t s)
 {
     if (nq <= 0 || nt <= 0) return;
     const int slices = match_slicing::slices(match_slicing::kU8, nt, tiles_per_slice);
     const dim3 grid((unsigned)((nq + UQ - 1) / UQ), (unsigned)slices);
     i32x4 *pp = (!out && slices > 1) ? static_cast<i32x4 *>(part) : nullptr;
     const bool multi = r > UK;
-#define DLCO_MATCH_U8_LAUNCH(ST, MU)                                                                                                  \
-    hipLaunchKernelGGL((match_u8_kernel<ST, MU>), grid, dim3(UTH), 0, s, query, ldq, nq, train, ldt, nt, r, qnorm, tneg, tiles_per_slice, \
-                       idx, sqdist, pp, out, nullptr, 0)
-    if (out) { if (multi) DLCO_MATCH_U8_LAUNCH(true, true); else DLCO_MATCH_U8_LAUNCH(true, false); }
-    else     { if (multi) DLCO_MATCH_U8_LAUNCH(false, true); else DLCO_MATCH_U8_LAUNCH(false, false); }
+    const MatchGuide g = guide ? *guide : MatchGuide{};
+#define DLCO_MATCH_U8_LAUNCH(ST, MU, GU)                                                                                              \
+    hipLaunchKernelGGL((match_u8_kernel<ST, MU, GU>), grid, dim3(UTH), 0, s, query, ldq, nq, train, ldt, nt, r, qnorm, tneg,          \
+                       tiles_per_slice, idx, sqdist, pp, out, nullptr, 0, guide_arg<GU>(g))
+#define DLCO_MATCH_U8_FORM(GU)                                                                                                        \
+    do {                                                                                                                              \
+        if (out) { if (multi) DLCO_MATCH_U8_LAUNCH(true, true, GU); else DLCO_MATCH_U8_LAUNCH(true, false, GU); }                     \
+        else     { if (multi) DLCO_MATCH_U8_LAUNCH(false, true, GU); else DLCO_MATCH_U8_LAUNCH(false, false, GU); }                   \
+    } while (0)
+    if (!guide) DLCO_MATCH_U8_FORM(0);
+    else if (g.model == kGuideHomography && g.side == 0) DLCO_MATCH_U8_FORM(1);
+    else if (g.model == kGuideHomography) DLCO_MATCH_U8_FORM(2);
+    else if (g.side == 0) DLCO_MATCH_U8_FORM(3);
+    else DLCO_MATCH_U8_FORM(4);
+#undef DLCO_MATCH_U8_FORM
 #undef DLCO_MATCH_U8_LAUNCH
     DLCO_HIP(hipGetLastError());
     if (pp) {
@@ -398,16 +541,25 @@ void match_u8_top2(const uint8_t *query, long ldq, int nq, const uint8_t *train,
 
 // One launch of a batched match (match_batch.hpp): table [.][ld], qnorm = |a|^2 and tneg = -|a|^2 of all its rows, the launch's
 // n_ent entries in device memory, wgs workgroups of the tile loop, merge_wgs of the merge (0: every entry has one slice).
+// guide: nullptr, or the geometry of the guided batch, as match_top2_batch takes it: rec the launch's record buffer, already
+// written (match_records_batch), off its entries' record rows, xy / ldxy the coordinates of the whole table.
 void match_u8_top2_batch(const uint8_t *table, long ld, int r, const int32_t *qnorm, const int32_t *tneg, const match_batch::Entry *ent, int n_ent,
-                         long wgs, long merge_wgs, int32_t *idx, int32_t *sqdist, void *part, hipStream_t s)
+                         long wgs, long merge_wgs, int32_t *idx, int32_t *sqdist, void *part, const MatchGuide *guide, hipStream_t s)
 {
     if (n_ent <= 0 || wgs <= 0) return;
     i32x4 *pp = static_cast<i32x4 *>(part);
     const dim3 grid((unsigned)wgs);
-#define DLCO_MATCH_U8_BATCH_LAUNCH(MU)                                                                                                \
-    hipLaunchKernelGGL((match_u8_kernel<false, MU, true>), grid, dim3(UTH), 0, s, table, ld, 0, nullptr, 0L, 0, r, qnorm, tneg, 0, idx, sqdist, \
-                       pp, nullptr, ent, n_ent)
-    if (r > UK) DLCO_MATCH_U8_BATCH_LAUNCH(true); else DLCO_MATCH_U8_BATCH_LAUNCH(false);
+    const MatchGuide g = guide ? *guide : MatchGuide{};
+#define DLCO_MATCH_U8_BATCH_LAUNCH(MU, GU)                                                                                            \
+    hipLaunchKernelGGL((match_u8_kernel<false, MU, GU, true>), grid, dim3(UTH), 0, s, table, ld, 0, nullptr, 0L, 0, r, qnorm, tneg, 0, idx,  \
+                       sqdist, pp, nullptr, ent, n_ent, guide_arg<GU>(g))
+#define DLCO_MATCH_U8_BATCH_FORM(GU) do { if (r > UK) DLCO_MATCH_U8_BATCH_LAUNCH(true, GU); else DLCO_MATCH_U8_BATCH_LAUNCH(false, GU); } while (0)
+    if (!guide) DLCO_MATCH_U8_BATCH_FORM(0);
+    else if (g.model == kGuideHomography && g.side == 0) DLCO_MATCH_U8_BATCH_FORM(1);
+    else if (g.model == kGuideHomography) DLCO_MATCH_U8_BATCH_FORM(2);
+    else if (g.side == 0) DLCO_MATCH_U8_BATCH_FORM(3);
+    else DLCO_MATCH_U8_BATCH_FORM(4);
+#undef DLCO_MATCH_U8_BATCH_FORM
 #undef DLCO_MATCH_U8_BATCH_LAUNCH
     DLCO_HIP(hipGetLastError());
     if (merge_wgs > 0) {

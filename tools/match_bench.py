@@ -36,7 +36,16 @@ pair has a matrix of its own, the mild homography of --guided (the F of --guided
 depends on the pair; radius 12, threshold 2; both sides.  One warm-up of the three, a check that the batch and the loop returned
 the same bytes (the tool stops if they did not), then three rounds that alternate them.  The line shows kernels and wall of
 each with their rounds, loop / batch, guided batch / plain batch, and the gate: the batch's slowest round below the loop's
-fastest."""
+fastest.
+
+With --u8 --guided (--u8 --guided-epipolar) the byte line's guided call is measured: dlco_desc_match_guided_u8_device
+(_epipolar_u8_device) on the geometry of --guided (--guided-epipolar) and the float tables quantised with one fitted scale, as
+--u8 does.  One process alternates the plain byte call, the byte guided call of both sides and the float guided call of both
+sides on the same shape: one warm-up each, three rounds, kernel time from last_kernel_ms.  The line shows the best round of
+each with the three rounds' range (largest minus smallest), byte guided / plain byte and float guided / byte guided, and how
+many queries found two admitted rows.  With --u8 --pairs --guided (--u8 --pairs --guided-epipolar) the same five calls are
+the batches dlco_desc_match_pairs_u8_device, dlco_desc_match_pairs_guided_u8_device (_epipolar_u8_device) and the float guided
+batch on the sets a (72 pairs) and b (1056 pairs) of --pairs --guided, with a matrix of its own per pair."""
 import importlib, os, sys
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch
@@ -212,6 +221,117 @@ def pairs_guided_bench():
         del X, xy, out
     ctx.close()
 
+
+def quantised(X, lo, scale, r):
+    """the float rows as bytes at a pitch of whole 16-byte pieces: one scale, per-dimension offsets"""
+    ld = (r + 15) // 16 * 16
+    B = torch.zeros((len(X), ld), dtype=torch.uint8, device="cuda:0")
+    B[:, :r] = ((X - lo) * scale).round().clamp(0, 255).to(torch.uint8)
+    return B, ld
+
+
+def rounds_line(names, calls, ctx):
+    """one warm-up of every call, then three rounds that alternate them: (best [k], range [k], text)"""
+    for f in calls:
+        f()
+    ms3 = [[] for _ in calls]
+    for _ in range(3):
+        for k, f in enumerate(calls):
+            f()
+            ms3[k].append(ctx.last_kernel_ms())
+    best, rng = [min(m) for m in ms3], [max(m) - min(m) for m in ms3]
+    text = ", ".join("%s %.3f ms (rounds %s, range %.3f)" % (n, b, " ".join("%.3f" % v for v in m), g) for n, b, m, g in zip(names, best, ms3, rng))
+    return best, rng, text
+
+
+def u8_guided_bench():
+    import numpy as np
+    ctx = dlco.DescContext()
+    gen = torch.Generator(device="cuda:0").manual_seed(0)
+    what = "match_guided_epipolar_u8" if EPI else "match_guided_u8"
+    for nq, nt, r in SHAPES:
+        T = torch.empty((nt, r), dtype=torch.float32, device="cuda:0").normal_(0, 0.25, generator=gen)
+        Q = torch.empty((nq, r), dtype=torch.float32, device="cuda:0").normal_(0, 0.25, generator=gen)
+        Q[: nq // 2] = T[torch.randint(0, nt, (nq // 2,), device="cuda:0", generator=gen)] + 0.02 * torch.randn((nq // 2, r), device="cuda:0", generator=gen)
+        S = 8.0 * nt ** 0.5
+        M = np.array([[0.98, -0.05, 0.03 * S], [0.04, 1.02, -0.02 * S], [0.02 / S, -0.01 / S, 1.0]])
+        if EPI:
+            M = np.array([[0.0, -1.0, 0.4 * S], [1.0, 0.0, -3.0 * S], [-0.4 * S, 3.0 * S, 0.0]]) @ M
+            M = M / np.abs(M).max()
+        t = 2.0 if EPI else 12.0
+        txy = torch.rand((nt, 2), device="cuda:0", generator=gen) * S
+        qxy = torch.rand((nq, 2), device="cuda:0", generator=gen) * S
+        lo = torch.minimum(Q.min(0).values, T.min(0).values)
+        scale = 255.0 / float(torch.maximum(Q.max(0).values, T.max(0).values).sub(lo).max())
+        (Qu, ld), (Tu, _) = quantised(Q, lo, scale, r), quantised(T, lo, scale, r)
+        oi = [torch.empty((nq, 2), dtype=torch.int32, device="cuda:0") for _ in range(5)]
+        od = [torch.empty((nq, 2), dtype=torch.int32, device="cuda:0") for _ in range(3)] + [torch.empty((nq, 2), dtype=torch.float32, device="cuda:0") for _ in range(2)]
+        torch.cuda.synchronize()
+        g8 = ctx.match_guided_epipolar_u8_device if EPI else ctx.match_guided_u8_device
+        gf = ctx.match_guided_epipolar_device if EPI else ctx.match_guided_device
+        calls = [lambda: ctx.match_u8_device(Qu.data_ptr(), nq, Tu.data_ptr(), nt, r, oi[0].data_ptr(), od[0].data_ptr(), ldq=ld, ldt=ld)]
+        calls += [lambda h=h: g8(Qu.data_ptr(), qxy.data_ptr(), nq, Tu.data_ptr(), txy.data_ptr(), nt, r, M, oi[1 + h].data_ptr(), od[1 + h].data_ptr(), t, h,
+                                 ldq=ld, ldt=ld) for h in (0, 1)]
+        calls += [lambda h=h: gf(Q.data_ptr(), qxy.data_ptr(), nq, T.data_ptr(), txy.data_ptr(), nt, r, M, oi[3 + h].data_ptr(), od[3 + h].data_ptr(), t, h)
+                  for h in (0, 1)]
+        best, _, text = rounds_line(["plain byte", "byte guided side 0", "byte guided side 1", "float guided side 0", "float guided side 1"], calls, ctx)
+        two = [100 * float((oi[k][:, 1] >= 0).float().mean()) for k in (1, 2)]
+        print(f"{what} {nq} x {nt} r {r}: {text}; byte guided / plain byte {best[1] / best[0]:.3f} and {best[2] / best[0]:.3f}; float guided / byte guided "
+              f"{best[3] / best[1]:.3f} and {best[4] / best[2]:.3f}; two admitted rows for {two[0]:.1f} % and {two[1]:.1f} % of the queries", flush=True)
+        del T, Q, Qu, Tu, txy, qxy, oi, od
+    ctx.close()
+
+
+def pairs_u8_guided_bench():
+    import numpy as np
+    sets = [("a", [2048] * 9, 128), ("b", [512] * 33, 128)]
+    ctx = dlco.DescContext()
+    gen = torch.Generator(device="cuda:0").manual_seed(0)
+    what = "match_pairs_guided_epipolar_u8" if EPI else "match_pairs_guided_u8"
+    for name, sizes, r in sets:
+        n_img, n = len(sizes), sizes[0]
+        seg = np.concatenate([[0], np.cumsum(sizes)]).astype(np.int64)
+        pairs = np.array([(a, b) for a in range(n_img) for b in range(n_img) if a != b], np.int32)
+        rows = int(dlco.match_pairs_rows(seg, pairs)[-1])
+        X = torch.empty((int(seg[-1]), r), dtype=torch.float32, device="cuda:0").normal_(0, 0.25, generator=gen)
+        S = 8.0 * n ** 0.5
+        xy = torch.rand((int(seg[-1]), 2), device="cuda:0", generator=gen) * S
+        H = np.array([[0.98, -0.05, 0.03 * S], [0.04, 1.02, -0.02 * S], [0.02 / S, -0.01 / S, 1.0]])
+        M = []
+        for p in range(len(pairs)):                        # a matrix per pair: the model behind a small shift of the source image
+            m = H @ np.array([[1.0, 0.0, 2.0 * np.cos(p)], [0.0, 1.0, 2.0 * np.sin(p)], [0.0, 0.0, 1.0]])
+            if EPI:
+                m = np.array([[0.0, -1.0, 0.4 * S], [1.0, 0.0, -3.0 * S], [-0.4 * S, 3.0 * S, 0.0]]) @ m
+                m = m / np.abs(m).max()
+            M.append(m)
+        M = np.stack(M)
+        t = 2.0 if EPI else 12.0
+        lo = X.min(0).values
+        Xu, ld = quantised(X, lo, 255.0 / float((X.max(0).values - lo).max()), r)
+        oi = [torch.empty((rows, 2), dtype=torch.int32, device="cuda:0") for _ in range(5)]
+        od = [torch.empty((rows, 2), dtype=torch.int32, device="cuda:0") for _ in range(3)] + [torch.empty((rows, 2), dtype=torch.float32, device="cuda:0") for _ in range(2)]
+        torch.cuda.synchronize()
+        g8 = ctx.match_pairs_guided_epipolar_u8_device if EPI else ctx.match_pairs_guided_u8_device
+        gf = ctx.match_pairs_guided_epipolar_device if EPI else ctx.match_pairs_guided_device
+        calls = [lambda: ctx.match_pairs_u8_device(Xu.data_ptr(), seg, pairs, r, oi[0].data_ptr(), od[0].data_ptr(), ld=ld)]
+        calls += [lambda h=h: g8(Xu.data_ptr(), xy.data_ptr(), seg, pairs, r, M, oi[1 + h].data_ptr(), od[1 + h].data_ptr(), t, h, ld=ld, ldxy=2) for h in (0, 1)]
+        calls += [lambda h=h: gf(X.data_ptr(), xy.data_ptr(), seg, pairs, r, M, oi[3 + h].data_ptr(), od[3 + h].data_ptr(), t, h, ld=r, ldxy=2) for h in (0, 1)]
+        best, _, text = rounds_line(["plain byte batch", "byte guided batch side 0", "byte guided batch side 1", "float guided batch side 0",
+                                     "float guided batch side 1"], calls, ctx)
+        two = [100 * float((oi[k][:, 1] >= 0).float().mean()) for k in (1, 2)]
+        print(f"{what} set {name}: {n_img} images of {n} rows, {len(pairs)} pairs, r {r}: {text}; byte guided / plain byte {best[1] / best[0]:.3f} and "
+              f"{best[2] / best[0]:.3f}; float guided / byte guided {best[3] / best[1]:.3f} and {best[4] / best[2]:.3f}; two admitted rows for {two[0]:.1f} % "
+              f"and {two[1]:.1f} % of the queries", flush=True)
+        del X, Xu, xy, oi, od
+    ctx.close()
+
+
+if U8 and (GUIDED or EPI):
+    if PAIRS:
+        pairs_u8_guided_bench()
+    else:
+        u8_guided_bench()
+    sys.exit(0)
 
 if PAIRS:
     if GUIDED or EPI:
