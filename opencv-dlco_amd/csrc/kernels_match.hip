@@ -8,31 +8,25 @@
 //                         are read, a train tile when it is stored to LDS), rounded to float once; then either the running top two per query
 //                         under the key (float distance, train index), or (STORE) the matrix itself: one tile loop, two
 //                         epilogues, so the matrix and the top two cannot disagree
-//   match_records_kernel  the guided forms (dlco_desc_match_guided, guided_rules.hpp): the record (X, Y, W, T) of every row
-//                         of the side the homography applies to, one lane per row
-//   match_top2_kernel<.., GUIDED>   the same tile loop with a third epilogue: a candidate enters the running top two only
-//                         if guided_rules::admits says so, and STORE writes +inf for one that is not admitted.  GUIDED = 1:
-//                         the queries carry records (h_side 0) and a train tile brings its (x, y), 16 bytes a row, staged
-//                         beside Tn; GUIDED = 2: the train rows carry records, 32 bytes a row, and the queries their (x, y).
-//                         The workgroup's queries' geometry sits in LDS, and a lane keeps the verdicts of a pair of column
-//                         blocks as a bit mask.  Distance, key, merge and slices are those of the plain form, so a guided answer is the top two of the plain matrix with +inf where the
-//                         predicate fails.  The predicate's arithmetic is reached through guided_rules.hpp alone, which
-//                         switches contraction off.
-//   match_epi_records_kernel, match_top2_kernel<.., GUIDED = 3, 4>   the epipolar guided forms (dlco_desc_match_guided_epipolar,
-//                         guided_epipolar_rules.hpp): both sides carry a record of 32 bytes a row, the src record of the
-//                         image F applies to and the dst record of the other.  GUIDED = 3: the queries are src (f_side 0);
-//                         GUIDED = 4: train is.  A train tile's records take the staging of GUIDED = 2, the queries' the
-//                         LDS fill of GUIDED = 1, and the verdict is guided_epipolar::admits, with t2 from MatchGuide.  MULTI
-//                         forms a tile's verdicts before the A fragments of its last chunk are fetched, one byte per
-//                         pair of column blocks: beside the epilogue, with every accumulator live, they cost scratch.
-//   match_merge_kernel    the top two of a query over the S slices of train, under the same key (the slicing rule:
-//                         match_slices.hpp)
-//   match_top2_kernel<.., BATCH>, match_merge_batch_kernel, match_fill_kernel   the batch forms (dlco_desc_match_pairs, the plan:
-//                         match_batch.hpp): many (query image, train image) pairs over one segmented table in one 1-D
-//                         launch; a workgroup finds its pair in the uploaded plan and runs the plain form's tile loop
-//   match_records_batch_kernel, match_top2_kernel<.., GUIDED, BATCH>   the guided batch (dlco_desc_match_pairs_guided*): every
-//                         pair has a matrix of its own, so a launch forms the records of its entries into one buffer, a
-//                         lane per record row, and the tile loop's batch prologue binds an entry's records and coordinates
+//   match_top2_kernel<.., GUIDED>   the guided forms (dlco_desc_match_guided*, dlco_desc_match_guided_epipolar*; GuidedForm,
+//                         match_dev.hpp): the same tile loop with a third epilogue.  A candidate enters the running top two only if
+//                         admits<GUIDED> says so, and STORE writes +inf for one that is not admitted; distance, key, merge and
+//                         slices are those of the plain form, so a guided answer is the top two of the plain matrix with +inf where
+//                         the predicate fails.  A train tile's geometry is staged beside Tn, the workgroup's queries' sits in
+//                         LDS, and a lane keeps the verdicts of a pair of column blocks as a bit mask: eight entries of two
+//                         column blocks, the layout of the f64 MFMA's result.  MULTI forms a tile's epipolar verdicts before
+//                         the A fragments of its last chunk are fetched, one byte per pair of column blocks: beside the
+//                         epilogue, with every accumulator live, they cost scratch.
+//   match_records_kernel, match_epi_records_kernel, match_records_batch_kernel   the records of the rows of a table under H or F
+//                         (record_of, store_record: match_dev.hpp), one lane per row; both lines read them
+//   match_top2_kernel<.., BATCH>, match_fill_kernel   the batch forms (dlco_desc_match_pairs*, the plan: match_batch.hpp): many
+//                         (query image, train image) pairs over one segmented table in one 1-D launch; a workgroup finds its
+//                         pair in the uploaded plan and runs the plain form's tile loop.  Guided: every pair has a matrix of its
+//                         own, so a launch forms the records of its entries into one buffer
+//
+// What the byte line (kernels_match_u8.hip) states too is in match_dev.hpp: the guided forms and their dispatch, the geometry
+// a row brings and how it moves, the verdict, the top two under a key with the merge over slices (match_merge_kernel; the
+// slicing rule: match_slices.hpp), a batched workgroup's entry.
 //
 // The key is a total order and the slices hold disjoint train rows, so the result does not depend on the grouping.
 // An entry's accumulation is one chain of MFMAs over k in an order fixed by r: it depends neither on where the query
@@ -41,18 +35,13 @@
 // Tables are [n][ld] floats with ld % 4 == 0 and 16-byte aligned: a row is read in 16-byte pieces up to
 // ceil(r / 4) * 4 <= ld, the elements at and beyond r are replaced by zeros.  Every load is unconditional and in
 // bounds (a row or piece beyond the edge reads a valid one and is replaced by zeros), stores are masked.
-#include "dlco_internal.hpp"
-#include "guided_rules.hpp"
-#include "guided_epipolar_rules.hpp"
-#include "match_batch.hpp"
+#include "match_dev.hpp"
 #include "match_slices.hpp"
 
 namespace dlco {
 
 typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef int i32x4 __attribute__((ext_vector_type(4)));
 typedef double f64x4 __attribute__((ext_vector_type(4)));
-typedef double f64x2 __attribute__((ext_vector_type(2)));
 
 namespace {
 
@@ -69,50 +58,28 @@ constexpr int MP = KC + 2;             // LDS pitch in doubles: the 16-byte read
 constexpr int MTH = 512;
 constexpr int NSUB = TN / 16;
 
-struct Top2 { float d1; int j1; float d2; int j2; };
-
-// (distance, index) order: smaller distance first, equal distances by smaller index
-__device__ __forceinline__ bool key_less(float da, int ja, float db, int jb) { return da < db || (da == db && ja < jb); }
-
-// top two of the union of two top-two lists of disjoint candidates
-__device__ __forceinline__ Top2 merge2(const Top2 a, const Top2 b)
-{
-    Top2 o;
-    const bool b_first = key_less(b.d1, b.j1, a.d1, a.j1);
-    const float wd = b_first ? b.d1 : a.d1, ld = b_first ? a.d1 : b.d1;        // winner / loser of the two firsts
-    const int wj = b_first ? b.j1 : a.j1, lj = b_first ? a.j1 : b.j1;
-    const float sd = b_first ? b.d2 : a.d2;                                  // the winner's own second
-    const int sj = b_first ? b.j2 : a.j2;
-    const bool l_second = key_less(ld, lj, sd, sj);
-    o.d1 = wd; o.j1 = wj;
-    o.d2 = l_second ? ld : sd;
-    o.j2 = l_second ? lj : sj;
-    return o;
-}
-
-// The entry of the plan that workgroup wg of a batched launch belongs to: the last one whose first workgroup (`first`
-// picks wg0 or mwg0) is not above wg.  wg is the same for the whole workgroup, so the search is scalar loads and branches.
-template <typename First>
-__device__ __forceinline__ int batch_entry_of(const match_batch::Entry *__restrict__ ent, int n_ent, int wg, First first)
-{
-    int lo = 0, hi = n_ent;
-    while (hi - lo > 1) {
-        const int mid = (lo + hi) >> 1;
-        if (first(ent[mid]) <= wg) lo = mid; else hi = mid;
+// the float line's key is the distance itself: smaller distance first, equal distances by smaller index; a partial holds
+// the distances' bits
+struct FloatKey {
+    using Key = float;
+    static __device__ __forceinline__ bool first(float da, int ja, float db, int jb) { return da < db || (da == db && ja < jb); }
+    static __device__ __forceinline__ i32x4 pack(const Top2<float> t) { return i32x4{__float_as_int(t.k1), t.j1, __float_as_int(t.k2), t.j2}; }
+    static __device__ __forceinline__ Top2<float> unpack(const i32x4 p) { return Top2<float>{__int_as_float(p[0]), p[1], __int_as_float(p[2]), p[3]}; }
+    static __device__ __forceinline__ void write(const Top2<float> t, long, long row, int32_t *idx, float *sqdist)
+    {
+        idx[2 * row] = t.j1; idx[2 * row + 1] = t.j2;
+        sqdist[2 * row] = t.k1; sqdist[2 * row + 1] = t.k2;
     }
-    return lo;
-}
+};
 
-// BATCH (dlco_desc_match_pairs; STORE = 0, GUIDED = 0): a 1-D grid over the workgroups of every entry of a launch of the plan
+// BATCH (dlco_desc_match_pairs; STORE = 0, GUIDED = kPlain): a 1-D grid over the workgroups of every entry of a launch of the plan
 // (match_batch.hpp).  query is the one table [.][ldq] whose segments are the images and qnorm the norms of all its rows;
 // the workgroup finds its entry and takes from it what the plain form takes from its arguments and its grid: the query
 // image's and the train image's first row (tables, norms), nq, nt, tiles_per_slice, the first output row, the offset of the
 // entry's partials (part stays null when the entry has one slice), its query block and its slice.  Tiles are counted from
 // the slice's first row, which need not be tile-aligned in the table; the rows at and beyond jend belong to the next image
 // (or lie beyond the table) and are never read: the loads clamp to jbeg.  The loop below is the plain form's.
-//   BATCH with GUIDED 1 .. 4 (dlco_desc_match_pairs_guided*): geometry belongs to the pair, so g.rec is the launch's record
-// buffer, g.off the record rows of every entry (match_batch::GuideOff, indexed like ent) and g.xy the coordinates of the whole
-// table; the prologue rebinds the records to the entry's own and the coordinates to the rows of the image that brings them.
+//   BATCH with a guided form (dlco_desc_match_pairs_guided*): geometry belongs to the pair, and bind_entry_guide rebinds it.
 template <bool STORE, bool MULTI, int GUIDED, bool BATCH = false>
 __global__ __launch_bounds__(MTH) void match_top2_kernel(const float *__restrict__ query, long ldq, int nq, const float *__restrict__ train, long ldt,
                                                          int nt, int r, const double *__restrict__ qnorm, const double *__restrict__ tnorm,
@@ -127,13 +94,7 @@ __global__ __launch_bounds__(MTH) void match_top2_kernel(const float *__restrict
         const int wg = (int)blockIdx.x;
         const int ei = batch_entry_of(ent, n_ent, wg, [](const match_batch::Entry &x) { return x.wg0; });
         const match_batch::Entry e = ent[ei];
-        if constexpr (GUIDED != 0) {
-            const match_batch::GuideOff o = g.off[ei];
-            const double *qr = g.rec + 4 * o.rec0, *tr = qr + 4 * (long)o.nqrec;
-            grec = GUIDED == 1 ? qr : tr;
-            gqrec = qr;
-            gxy = g.xy + (GUIDED == 1 ? e.t0 : e.q0) * g.ldxy;
-        }
+        if constexpr (GUIDED != kPlain) bind_entry_guide<GUIDED>(g, e, ei, grec, gqrec, gxy);
         const unsigned w = (unsigned)(wg - e.wg0);
         slice = w / (unsigned)e.qblocks;
         qblk = w - slice * (unsigned)e.qblocks;
@@ -143,8 +104,7 @@ __global__ __launch_bounds__(MTH) void match_top2_kernel(const float *__restrict
         idx += 2 * e.out0; sqdist += 2 * e.out0;
         part = e.slices > 1 ? part + e.part0 : nullptr;
     }
-    constexpr int CW = GUIDED >= 2 ? 4 : 2;                // doubles of geometry a train row brings: (x, y) or a record
-    constexpr int QW = GUIDED == 1 || GUIDED >= 3 ? 4 : 2; // and a query
+    constexpr int CW = train_geom_width(GUIDED), QW = query_geom_width(GUIDED);
     __shared__ double Bs[TN * MP];                         // the staged tile, widened to double once, when it is stored
     __shared__ double Tn[TN];
     __shared__ __attribute__((aligned(16))) double Tg[GUIDED ? TN * CW : 1];            // GUIDED: the tile's geometry, staged with it,
@@ -190,14 +150,7 @@ __global__ __launch_bounds__(MTH) void match_top2_kernel(const float *__restrict
         const long jn = jt + (tid & (TN - 1));
         const long js = jn < jend ? jn : (long)jbeg;
         rtn = tnorm[js];
-        if constexpr (GUIDED == 1) {
-            const float *p = gxy + js * g.ldxy;
-            rg[0] = (double)p[0]; rg[1] = (double)p[1];
-        }
-        if constexpr (GUIDED >= 2) {
-            const f64x2 a = *reinterpret_cast<const f64x2 *>(grec + 4 * js), b = *reinterpret_cast<const f64x2 *>(grec + 4 * js + 2);
-            rg[0] = a[0]; rg[1] = a[1]; rg[2] = b[0]; rg[3] = b[1];
-        }
+        geom_fetch<GUIDED>(rg, grec, gxy, g.ldxy, js);
     };
     auto lstore = [&]() {
 #pragma unroll
@@ -208,26 +161,8 @@ __global__ __launch_bounds__(MTH) void match_top2_kernel(const float *__restrict
         }
         if (tid < TN) {
             Tn[tid] = rtn;
-            if constexpr (GUIDED != 0) {
-#pragma unroll
-                for (int e = 0; e < CW; e += 2) *reinterpret_cast<f64x2 *>(&Tg[tid * CW + e]) = f64x2{rg[e], rg[e + 1]};
-            }
+            if constexpr (GUIDED != kPlain) geom_store(&Tg[tid * CW], rg);
         }
-    };
-    // the geometry of column c of the staged tile
-    struct ColGeom { double v[CW]; };
-    auto cload = [&](int c) {
-        ColGeom o;
-        if constexpr (GUIDED != 0) {
-#pragma unroll
-            for (int e = 0; e < CW; e += 2) {
-                const f64x2 t = *reinterpret_cast<const f64x2 *>(&Tg[c * CW + e]);
-                o.v[e] = t[0]; o.v[e + 1] = t[1];
-            }
-        } else {
-            o.v[0] = o.v[1] = 0.0;
-        }
-        return o;
     };
 
     // A fragments of one k chunk: lane (li, lg) holds query q0 + li at k = 16 c + 4 lg + s, s = element of fa[c]
@@ -251,63 +186,30 @@ __global__ __launch_bounds__(MTH) void match_top2_kernel(const float *__restrict
         const int row = q0 + lg + 4 * rr;
         qn[rr] = qnorm[row < nq ? row : 0];
     }
-    // GUIDED: the geometry of the workgroup's queries, the record of a query (1; 3, 4: from qrec) or its (x, y) (2), goes to LDS (the first
+    // GUIDED: the geometry of the workgroup's queries, a record or (x, y) (query_geom_fill), goes to LDS (the first
     // barrier of the loop below orders it) and is read again for every pair of column blocks: four rows' records held in
     // registers over the loop would put the kernel into scratch
-    if constexpr (GUIDED != 0) {
+    if constexpr (GUIDED != kPlain) {
         if (tid < MQ) {
-            const long row = (long)qblk * MQ + tid;
-            const long rs = row < nq ? row : 0;
-            if constexpr (GUIDED == 1 || GUIDED >= 3) {
-                const double *qr = GUIDED == 1 ? grec : gqrec;
-                *reinterpret_cast<f64x2 *>(&Qg[tid * 4]) = *reinterpret_cast<const f64x2 *>(qr + 4 * rs);
-                *reinterpret_cast<f64x2 *>(&Qg[tid * 4 + 2]) = *reinterpret_cast<const f64x2 *>(qr + 4 * rs + 2);
-            } else {
-                const float *p = gxy + rs * g.ldxy;
-                *reinterpret_cast<f64x2 *>(&Qg[tid * 2]) = f64x2{(double)p[0], (double)p[1]};
-            }
+            query_geom_fill<GUIDED>(&Qg[tid * QW], grec, gqrec, gxy, g.ldxy, (long)qblk * MQ + tid, nq);
         }
     }
-    // GUIDED 3, 4: the verdict on the query whose record sits at q and the column c, whichever of the two is src
-    auto epi_admits = [&](const double *q, const ColGeom &c) -> bool {
-        if constexpr (GUIDED >= 3) {
-            const f64x2 q0v = *reinterpret_cast<const f64x2 *>(q), q1v = *reinterpret_cast<const f64x2 *>(q + 2);
-            if constexpr (GUIDED == 3)
-                return guided_epipolar::admits(guided_epipolar::SrcRec{q0v[0], q0v[1], q1v[0], q1v[1]},
-                                               guided_epipolar::DstRec{c.v[0], c.v[1], c.v[2], c.v[3]}, g.t2);
-            else
-                return guided_epipolar::admits(guided_epipolar::SrcRec{c.v[0], c.v[1], c.v[2], c.v[3]},
-                                               guided_epipolar::DstRec{q0v[0], q0v[1], q1v[0], q1v[1]}, g.t2);
-        }
-        return true;
-    };
     // GUIDED: which of the eight entries of the column blocks at c0 and c0 + 16 of the staged tile the rule admits, bit e as
     // prev_entry counts them.  One burst of LDS reads and fp64 VALU work per pair of blocks, whose only result that lives
     // on is the mask.  The empty asm hides from the compiler that the queries' address does not change over the tile loop:
     // hoisted out of it, their geometry would sit in registers again.
     auto admit_mask = [&](int c0) -> unsigned {
         unsigned m = 0xffu;
-        if constexpr (GUIDED != 0) {
+        if constexpr (GUIDED != kPlain) {
             int qoff = (wave * 16 + lg) * QW;
             asm volatile("" : "+v"(qoff));
-            const ColGeom a = cload(c0), b = cload(c0 + 16);
+            const Geom a = geom_read<CW>(&Tg[c0 * CW]), b = geom_read<CW>(&Tg[(c0 + 16) * CW]);
             m = 0;
 #pragma unroll
             for (int rr = 0; rr < 4; rr++) {
-                const double *q = &Qg[qoff + 4 * rr * QW];
-                if constexpr (GUIDED == 1) {
-                    const f64x2 q0v = *reinterpret_cast<const f64x2 *>(q), q1v = *reinterpret_cast<const f64x2 *>(q + 2);
-                    const guided_rules::Rec rec{q0v[0], q0v[1], q1v[0], q1v[1]};
-                    m |= (guided_rules::admits(rec, a.v[0], a.v[1]) ? 1u : 0u) << rr;
-                    m |= (guided_rules::admits(rec, b.v[0], b.v[1]) ? 1u : 0u) << (4 + rr);
-                } else if constexpr (GUIDED >= 3) {
-                    m |= (epi_admits(q, a) ? 1u : 0u) << rr;
-                    m |= (epi_admits(q, b) ? 1u : 0u) << (4 + rr);
-                } else {
-                    const f64x2 uv = *reinterpret_cast<const f64x2 *>(q);
-                    m |= (guided_rules::admits(guided_rules::Rec{a.v[0], a.v[1], a.v[2], a.v[3]}, uv[0], uv[1]) ? 1u : 0u) << rr;
-                    m |= (guided_rules::admits(guided_rules::Rec{b.v[0], b.v[1], b.v[2], b.v[3]}, uv[0], uv[1]) ? 1u : 0u) << (4 + rr);
-                }
+                const Geom q = geom_read<QW>(&Qg[qoff + 4 * rr * QW]);
+                m |= (admits<GUIDED>(q, a, g.t2) ? 1u : 0u) << rr;
+                m |= (admits<GUIDED>(q, b, g.t2) ? 1u : 0u) << (4 + rr);
             }
         }
         return m;
@@ -321,7 +223,7 @@ __global__ __launch_bounds__(MTH) void match_top2_kernel(const float *__restrict
     // one entry of a 16 x 16 result: row q0 + lg + 4 rr against train row jl, whose squared norm is tn
     auto entry = [&](double dot, int rr, double tn, long jl, unsigned mask, int e) {
         const bool j_ok = jl < jend;
-        const bool adm = GUIDED == 0 || ((mask >> e) & 1u) != 0;
+        const bool adm = GUIDED == kPlain || ((mask >> e) & 1u) != 0;
         const int j = (int)jl;
         double d = __builtin_fma(-2.0, dot, qn[rr] + tn);
         d = __builtin_fmax(d, 0.0);
@@ -381,10 +283,10 @@ __global__ __launch_bounds__(MTH) void match_top2_kernel(const float *__restrict
         if (wave_on) {
             if (MULTI) {
                 const int tile = step / nch, kc = step - tile * nch;
-                // GUIDED 3, 4: the verdicts of the whole tile, a byte per pair of column blocks, before the chunk's A fragments
+                // the epipolar forms: the verdicts of the whole tile, a byte per pair of column blocks, before the chunk's A fragments
                 // are fetched: between two chunks their registers are free, and 16 doubles of geometry fit without scratch
                 unsigned mtile = 0;
-                if constexpr (GUIDED >= 3) {
+                if constexpr (GUIDED >= kEpiQuerySrc) {
                     if (kc == nch - 1) {
 #pragma unroll
                         for (int sub = 0; sub < NSUB; sub += 2) mtile |= admit_mask(16 * sub + li) << (4 * sub);
@@ -398,7 +300,7 @@ __global__ __launch_bounds__(MTH) void match_top2_kernel(const float *__restrict
                     mfma_pair(sub, acc[sub], acc[sub + 1], false);
                     if (kc == nch - 1) {
                         const long jl = (long)jbeg + (long)tile * TN + 16 * sub + li;
-                        const unsigned m = GUIDED >= 3 ? (mtile >> (4 * sub)) & 0xffu : admit_mask(16 * sub + li);
+                        const unsigned m = GUIDED >= kEpiQuerySrc ? (mtile >> (4 * sub)) & 0xffu : admit_mask(16 * sub + li);
 #pragma unroll
                         for (int rr = 0; rr < 4; rr++) {
                             entry(acc[sub][rr], rr, Tn[16 * sub + li], jl, m, rr);
@@ -428,59 +330,15 @@ __global__ __launch_bounds__(MTH) void match_top2_kernel(const float *__restrict
     // the 16 lanes of a row hold disjoint columns: butterfly under the key, every lane ends with the row's top two
 #pragma unroll
     for (int rr = 0; rr < 4; rr++) {
-        Top2 me{bd1[rr], bj1[rr], bd2[rr], bj2[rr]};
+        Top2<float> me{bd1[rr], bj1[rr], bd2[rr], bj2[rr]};
 #pragma unroll
-        for (int o = 1; o < 16; o <<= 1) {
-            Top2 other;
-            other.d1 = __shfl_xor(me.d1, o, 64); other.j1 = __shfl_xor(me.j1, o, 64);
-            other.d2 = __shfl_xor(me.d2, o, 64); other.j2 = __shfl_xor(me.j2, o, 64);
-            me = merge2(me, other);
-        }
+        for (int o = 1; o < 16; o <<= 1) me = merge2<FloatKey>(me, shfl_xor_top2(me, o));
         const int row = q0 + lg + 4 * rr;
         if (li == 0 && row < nq) {
-            if (part) {
-                part[(long)slice * nq + row] = i32x4{__float_as_int(me.d1), me.j1, __float_as_int(me.d2), me.j2};
-            } else {
-                idx[2 * (long)row] = me.j1; idx[2 * (long)row + 1] = me.j2;
-                sqdist[2 * (long)row] = me.d1; sqdist[2 * (long)row + 1] = me.d2;
-            }
+            if (part) part[(long)slice * nq + row] = FloatKey::pack(me);
+            else FloatKey::write(me, row, row, idx, sqdist);
         }
     }
-}
-
-__global__ __launch_bounds__(256) void match_merge_kernel(const i32x4 *__restrict__ part, int slices, int nq, int32_t *__restrict__ idx,
-                                                          float *__restrict__ sqdist)
-{
-    const int row = blockIdx.x * 256 + threadIdx.x;
-    if (row >= nq) return;
-    const i32x4 p0 = part[row];
-    Top2 me{__int_as_float(p0[0]), p0[1], __int_as_float(p0[2]), p0[3]};
-    for (int s = 1; s < slices; s++) {
-        const i32x4 p = part[(long)s * nq + row];
-        me = merge2(me, Top2{__int_as_float(p[0]), p[1], __int_as_float(p[2]), p[3]});
-    }
-    idx[2 * (long)row] = me.j1; idx[2 * (long)row + 1] = me.j2;
-    sqdist[2 * (long)row] = me.d1; sqdist[2 * (long)row + 1] = me.d2;
-}
-
-// the merge of a batched launch: 256 rows of an entry with more than one slice per workgroup, numbered from its mwg0
-__global__ __launch_bounds__(256) void match_merge_batch_kernel(const i32x4 *__restrict__ part, const match_batch::Entry *__restrict__ ent,
-                                                                int n_ent, int32_t *__restrict__ idx, float *__restrict__ sqdist)
-{
-    const int wg = (int)blockIdx.x;
-    const match_batch::Entry e = ent[batch_entry_of(ent, n_ent, wg, [](const match_batch::Entry &x) { return x.mwg0; })];
-    const int row = (wg - e.mwg0) * 256 + threadIdx.x;
-    if (row >= e.nq) return;
-    const i32x4 *pp = part + e.part0;
-    const i32x4 p0 = pp[row];
-    Top2 me{__int_as_float(p0[0]), p0[1], __int_as_float(p0[2]), p0[3]};
-    for (int s = 1; s < e.slices; s++) {
-        const i32x4 p = pp[(long)s * e.nq + row];
-        me = merge2(me, Top2{__int_as_float(p[0]), p[1], __int_as_float(p[2]), p[3]});
-    }
-    const long o = 2 * (e.out0 + row);
-    idx[o] = me.j1; idx[o + 1] = me.j2;
-    sqdist[o] = me.d1; sqdist[o + 1] = me.d2;
 }
 
 // the rows of the pairs of a batch whose train image is empty: -1 and the line's "no candidate" distance (the bits of +inf
@@ -507,9 +365,7 @@ __global__ __launch_bounds__(256) void match_records_kernel(const float *__restr
 {
     const long i = (long)blockIdx.x * 256 + threadIdx.x;
     if (i >= n) return;
-    const guided_rules::Rec r = guided_rules::record(H.h, (double)xy[i * ld], (double)xy[i * ld + 1], t2);
-    *reinterpret_cast<f64x2 *>(rec + 4 * i) = f64x2{r.X, r.Y};
-    *reinterpret_cast<f64x2 *>(rec + 4 * i + 2) = f64x2{r.W, r.T};
+    store_record(rec + 4 * i, record_of<kRecHom>(H.h, (double)xy[i * ld], (double)xy[i * ld + 1], t2));
 }
 
 // the epipolar records of n rows (x, y) under F: rec [n][4] = the src record (l0, l1, l2, L) of a row of the image F applies to
@@ -520,16 +376,7 @@ __global__ __launch_bounds__(256) void match_epi_records_kernel(const float *__r
     const long i = (long)blockIdx.x * 256 + threadIdx.x;
     if (i >= n) return;
     const double x = (double)xy[i * ld], y = (double)xy[i * ld + 1];
-    f64x2 lo, hi;
-    if (dst_side) {
-        const guided_epipolar::DstRec d = guided_epipolar::dst_record(F.h, x, y);
-        lo = f64x2{d.u, d.v}; hi = f64x2{d.A, d.B};
-    } else {
-        const guided_epipolar::SrcRec s = guided_epipolar::src_record(F.h, x, y);
-        lo = f64x2{s.l0, s.l1}; hi = f64x2{s.l2, s.L};
-    }
-    *reinterpret_cast<f64x2 *>(rec + 4 * i) = lo;
-    *reinterpret_cast<f64x2 *>(rec + 4 * i + 2) = hi;
+    store_record(rec + 4 * i, dst_side ? record_of<kRecDst>(F.h, x, y, 0.0) : record_of<kRecSrc>(F.h, x, y, 0.0));
 }
 
 // The records of one launch of a guided batch (match_batch.hpp): one lane per record row of the launch, which is also the
@@ -556,21 +403,8 @@ __global__ __launch_bounds__(256) void match_records_batch_kernel(const float *_
 #pragma unroll
     for (int e = 0; e < 9; e++) h[e] = M[9 * (long)ent[lo].pair + e];
     const double x = (double)xy[row * ld], y = (double)xy[row * ld + 1];
-    f64x2 a, b;
-    if constexpr (EPI) {
-        if (is_query == (side == 0)) {
-            const guided_epipolar::SrcRec s = guided_epipolar::src_record(h, x, y);
-            a = f64x2{s.l0, s.l1}; b = f64x2{s.l2, s.L};
-        } else {
-            const guided_epipolar::DstRec d = guided_epipolar::dst_record(h, x, y);
-            a = f64x2{d.u, d.v}; b = f64x2{d.A, d.B};
-        }
-    } else {
-        const guided_rules::Rec r = guided_rules::record(h, x, y, t2);
-        a = f64x2{r.X, r.Y}; b = f64x2{r.W, r.T};
-    }
-    *reinterpret_cast<f64x2 *>(rec + 4 * i) = a;
-    *reinterpret_cast<f64x2 *>(rec + 4 * i + 2) = b;
+    if constexpr (EPI) store_record(rec + 4 * i, is_query == (side == 0) ? record_of<kRecSrc>(h, x, y, t2) : record_of<kRecDst>(h, x, y, t2));
+    else store_record(rec + 4 * i, record_of<kRecHom>(h, x, y, t2));
 }
 
 constexpr int NTH = 256;               // four rows per workgroup, one wave each
@@ -626,26 +460,19 @@ void match_top2(const float *query, long ldq, int nq, const float *train, long l
     const int slices = match_slicing::slices(match_slicing::kFloat, nt, tiles_per_slice);
     const dim3 grid((unsigned)((nq + MQ - 1) / MQ), (unsigned)slices);
     i32x4 *pp = (!out && slices > 1) ? static_cast<i32x4 *>(part) : nullptr;
-    const bool multi = r > KC;
     const MatchGuide g = guide ? *guide : MatchGuide{};
-#define DLCO_MATCH_LAUNCH(ST, MU, GU)                                                                                                 \
-    hipLaunchKernelGGL((match_top2_kernel<ST, MU, GU>), grid, dim3(MTH), 0, s, query, ldq, nq, train, ldt, nt, r, qnorm, tnorm,       \
-                       tiles_per_slice, idx, sqdist, pp, out, g, nullptr, 0)
-#define DLCO_MATCH_FORM(GU)                                                                                                           \
-    do {                                                                                                                              \
-        if (out) { if (multi) DLCO_MATCH_LAUNCH(true, true, GU); else DLCO_MATCH_LAUNCH(true, false, GU); }                           \
-        else     { if (multi) DLCO_MATCH_LAUNCH(false, true, GU); else DLCO_MATCH_LAUNCH(false, false, GU); }                         \
-    } while (0)
-    if (!guide) DLCO_MATCH_FORM(0);
-    else if (g.model == kGuideHomography && g.side == 0) DLCO_MATCH_FORM(1);
-    else if (g.model == kGuideHomography) DLCO_MATCH_FORM(2);
-    else if (g.side == 0) DLCO_MATCH_FORM(3);
-    else DLCO_MATCH_FORM(4);
-#undef DLCO_MATCH_FORM
-#undef DLCO_MATCH_LAUNCH
+    dispatch_form(guided_form_of(guide), [&](auto form) {
+        dispatch_bool(out != nullptr, [&](auto store) {
+            dispatch_bool(r > KC, [&](auto multi) {
+                hipLaunchKernelGGL((match_top2_kernel<store.value, multi.value, form.value>), grid, dim3(MTH), 0, s, query, ldq, nq, train, ldt, nt, r,
+                                   qnorm, tnorm, tiles_per_slice, idx, sqdist, pp, out, g, nullptr, 0);
+            });
+        });
+    });
     DLCO_HIP(hipGetLastError());
     if (pp) {
-        hipLaunchKernelGGL(match_merge_kernel, dim3((unsigned)((nq + 255) / 256)), dim3(256), 0, s, pp, slices, nq, idx, sqdist);
+        hipLaunchKernelGGL((match_merge_kernel<FloatKey, false, int32_t, float>), dim3((unsigned)((nq + 255) / 256)), dim3(256), 0, s, pp, slices, nq,
+                           idx, sqdist);
         DLCO_HIP(hipGetLastError());
     }
 }
@@ -668,7 +495,7 @@ void match_records_batch(const float *xy, long ldxy, const match_batch::Entry *e
 // guide: nullptr, or the geometry of the guided batch: rec the launch's record buffer, already written
 // (match_records_batch), off its entries' record rows, xy / ldxy the coordinates of the whole table; ent_host / off_host
 // are the same entries and record rows in host memory.
-//   The homography of side 1 (GUIDED = 2) has no batch form beyond r = 128: with the batch prologue its MULTI loop needs 10
+//   The homography with records on train (kHomTrain) has no batch form beyond r = 128: with the batch prologue its MULTI loop needs 10
 // spilled registers.  Such a launch is served entry by entry with the single call's kernel on the entry's rows, norms,
 // records, coordinates and partials, which returns the same bytes: the plan, the norms and the records are still the batch's.
 void match_top2_batch(const float *table, long ld, int r, const double *norm, const match_batch::Entry *ent, int n_ent, long wgs, long merge_wgs,
@@ -679,7 +506,7 @@ void match_top2_batch(const float *table, long ld, int r, const double *norm, co
     i32x4 *pp = static_cast<i32x4 *>(part);
     const dim3 grid((unsigned)wgs);
     const MatchGuide g = guide ? *guide : MatchGuide{};
-    if (guide && r > KC && g.model == kGuideHomography && g.side != 0) {
+    if (guided_form_of(guide) == kHomTrain && r > KC) {
         for (int k = 0; k < n_ent; k++) {
             const match_batch::Entry &e = ent_host[k];
             MatchGuide ge = g;
@@ -691,20 +518,17 @@ void match_top2_batch(const float *table, long ld, int r, const double *norm, co
         }
         return;
     }
-#define DLCO_MATCH_BATCH_LAUNCH(MU, GU)                                                                                               \
-    hipLaunchKernelGGL((match_top2_kernel<false, MU, GU, true>), grid, dim3(MTH), 0, s, table, ld, 0, nullptr, 0L, 0, r, norm, nullptr, 0,  \
-                       idx, sqdist, pp, nullptr, g, ent, n_ent)
-#define DLCO_MATCH_BATCH_FORM(GU) do { if (r > KC) DLCO_MATCH_BATCH_LAUNCH(true, GU); else DLCO_MATCH_BATCH_LAUNCH(false, GU); } while (0)
-    if (!guide) DLCO_MATCH_BATCH_FORM(0);
-    else if (g.model == kGuideHomography && g.side == 0) DLCO_MATCH_BATCH_FORM(1);
-    else if (g.model == kGuideHomography) DLCO_MATCH_BATCH_LAUNCH(false, 2);       // r <= KC: see above
-    else if (g.side == 0) DLCO_MATCH_BATCH_FORM(3);
-    else DLCO_MATCH_BATCH_FORM(4);
-#undef DLCO_MATCH_BATCH_FORM
-#undef DLCO_MATCH_BATCH_LAUNCH
+    dispatch_form(guided_form_of(guide), [&](auto form) {
+        dispatch_bool(r > KC, [&](auto multi) {
+            if constexpr (!(form.value == kHomTrain && multi.value))   // served above: that form is not instantiated
+                hipLaunchKernelGGL((match_top2_kernel<false, multi.value, form.value, true>), grid, dim3(MTH), 0, s, table, ld, 0, nullptr, 0L, 0, r,
+                                   norm, nullptr, 0, idx, sqdist, pp, nullptr, g, ent, n_ent);
+        });
+    });
     DLCO_HIP(hipGetLastError());
     if (merge_wgs > 0) {
-        hipLaunchKernelGGL(match_merge_batch_kernel, dim3((unsigned)merge_wgs), dim3(256), 0, s, pp, ent, n_ent, idx, sqdist);
+        hipLaunchKernelGGL((match_merge_kernel<FloatKey, true, int32_t, float>), dim3((unsigned)merge_wgs), dim3(256), 0, s, pp, ent, n_ent,
+                           idx, sqdist);
         DLCO_HIP(hipGetLastError());
     }
 }

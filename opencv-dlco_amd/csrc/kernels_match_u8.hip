@@ -8,12 +8,14 @@
 //                           then either the running top two per query, or (STORE) the matrix itself: one tile loop, two
 //                           epilogues, so the matrix and the top two cannot disagree
 //   match_u8_kernel<.., GUIDED>   the guided forms (dlco_desc_match_guided_u8, _epipolar_u8 and their kin): the same tile loop with a
-//                           third epilogue, the verdict of guided_rules.hpp / guided_epipolar_rules.hpp on the records the float
-//                           line's record kernels write (kernels_match.hip); GUIDED as in match_top2_kernel, stated at the kernel
-//   match_u8_merge_kernel   the top two of a query over the S slices of train (the slicing rule: match_slices.hpp)
-//   match_u8_kernel<.., BATCH>, match_u8_merge_batch_kernel   the batch forms (dlco_desc_match_pairs_u8, the plan: match_batch.hpp):
-//                           many (query image, train image) pairs over one segmented table in one 1-D launch; a workgroup
-//                           finds its pair in the uploaded plan and runs the plain form's tile loop
+//                           third epilogue, on the records the float line's record kernels write
+//   match_u8_kernel<.., BATCH>   the batch forms (dlco_desc_match_pairs_u8, the plan: match_batch.hpp): many (query image, train
+//                           image) pairs over one segmented table in one 1-D launch; a workgroup finds its pair in the
+//                           uploaded plan and runs the plain form's tile loop
+//
+// What the float line states too is in match_dev.hpp: the guided forms and their dispatch, the geometry a row brings and how it
+// moves, the verdict, the top two under a key with the merge over slices (match_merge_kernel; the slicing rule:
+// match_slices.hpp), a batched workgroup's entry.
 //
 // Everything is an integer: differences do not see the shift by 128, |a|^2 <= 1024 * 128^2 = 2^24 and every partial stays
 // below 2^26 in magnitude, so d is the exact sum_k (q_ik - t_jk)^2 <= 1024 * 255^2 and nothing depends on an order of
@@ -27,17 +29,11 @@
 // Tables are [n][ld] bytes with ld % 16 == 0 and 16-byte aligned: a row is read in 16-byte pieces up to
 // ceil(r / 16) * 16 <= ld, the bytes at and beyond r are replaced by zeros after the flip.  Every load is unconditional
 // and in bounds (a row or piece beyond the edge reads a valid one and is replaced by zeros), stores are masked.
-#include "dlco_internal.hpp"
-#include "guided_rules.hpp"
-#include "guided_epipolar_rules.hpp"
-#include "match_batch.hpp"
+#include "match_dev.hpp"
 #include "match_slices.hpp"
 #include "quant_rules.hpp"
 
 namespace dlco {
-
-typedef int i32x4 __attribute__((ext_vector_type(4)));
-typedef double f64x2 __attribute__((ext_vector_type(2)));
 
 namespace {
 
@@ -60,26 +56,21 @@ constexpr int UTH = 256;
 constexpr int USUB = UT / 16;
 constexpr int kEmpty = -(1 << 30);
 
-struct Top2 { int k1; int j1; int k2; int j2; };
-
-// (key, index) order: larger key (smaller distance) first, equal keys by smaller index
-__device__ __forceinline__ bool key_first(int ka, int ja, int kb, int jb) { return ka > kb || (ka == kb && ja < jb); }
-
-// top two of the union of two top-two lists of disjoint candidates
-__device__ __forceinline__ Top2 merge2(const Top2 a, const Top2 b)
-{
-    Top2 o;
-    const bool b_first = key_first(b.k1, b.j1, a.k1, a.j1);
-    const int wk = b_first ? b.k1 : a.k1, lk = b_first ? a.k1 : b.k1;          // winner / loser of the two firsts
-    const int wj = b_first ? b.j1 : a.j1, lj = b_first ? a.j1 : b.j1;
-    const int sk = b_first ? b.k2 : a.k2;                                      // the winner's own second
-    const int sj = b_first ? b.j2 : a.j2;
-    const bool l_second = key_first(lk, lj, sk, sj);
-    o.k1 = wk; o.j1 = wj;
-    o.k2 = l_second ? lk : sk;
-    o.j2 = l_second ? lj : sj;
-    return o;
-}
+// the byte line's key: larger key (smaller distance) first, equal keys by smaller index; a partial holds the keys, and a
+// result is the query's norm |a_q|^2 = qnorm[qrow] less the key, INT32_MAX for an empty slot
+struct ByteKey {
+    using Key = int;
+    static __device__ __forceinline__ bool first(int ka, int ja, int kb, int jb) { return ka > kb || (ka == kb && ja < jb); }
+    static __device__ __forceinline__ i32x4 pack(const Top2<int> t) { return i32x4{t.k1, t.j1, t.k2, t.j2}; }
+    static __device__ __forceinline__ Top2<int> unpack(const i32x4 p) { return Top2<int>{p[0], p[1], p[2], p[3]}; }
+    static __device__ __forceinline__ void write(const Top2<int> t, long qrow, long row, const int32_t *qnorm, int32_t *idx, int32_t *sqdist)
+    {
+        const int n = qnorm[qrow];
+        idx[2 * row] = t.j1; idx[2 * row + 1] = t.j2;
+        sqdist[2 * row] = t.j1 < 0 ? INT_MAX : n - t.k1;
+        sqdist[2 * row + 1] = t.j2 < 0 ? INT_MAX : n - t.k2;
+    }
+};
 
 // the 16 bytes [k, k + 16) of a row as int8 a = u - 128, with the bytes at and beyond r, or all of them (!ok), zero
 __device__ __forceinline__ i32x4 piece(i32x4 v, int k, int r, bool ok)
@@ -94,19 +85,6 @@ __device__ __forceinline__ i32x4 piece(i32x4 v, int k, int r, bool ok)
     return o;
 }
 
-// The entry of the plan that workgroup wg of a batched launch belongs to: the last one whose first workgroup (`first`
-// picks wg0 or mwg0) is not above wg.  wg is the same for the whole workgroup, so the search is scalar loads and branches.
-template <typename First>
-__device__ __forceinline__ int batch_entry_of(const match_batch::Entry *__restrict__ ent, int n_ent, int wg, First first)
-{
-    int lo = 0, hi = n_ent;
-    while (hi - lo > 1) {
-        const int mid = (lo + hi) >> 1;
-        if (first(ent[mid]) <= wg) lo = mid; else hi = mid;
-    }
-    return lo;
-}
-
 // BATCH (dlco_desc_match_pairs_u8; STORE = 0): a 1-D grid over the workgroups of every entry of a launch of the plan
 // (match_batch.hpp).  query is the one table [.][ldq] whose segments are the images, qnorm and tneg the norms of all its rows
 // in both signs; the workgroup finds its entry and takes from it what the plain form takes from its arguments and its grid:
@@ -114,20 +92,18 @@ __device__ __forceinline__ int batch_entry_of(const match_batch::Entry *__restri
 // offset of the entry's partials (part stays null when the entry has one slice), its query block and its slice.  Tiles are
 // counted from the slice's first row, which need not be tile-aligned in the table; the rows at and beyond jend belong to
 // the next image (or lie beyond the table) and are never read: the loads clamp to jbeg.  The loop below is the plain form's.
-//   GUIDED 1 .. 4 (dlco_desc_match_guided*_u8; the meaning of kernels_match.hip's): the same tile loop with a third epilogue.  A
-// candidate that guided_rules::admits (1: the queries carry the records, h_side 0; 2: train does) or guided_epipolar::admits
-// (3: the queries are src, f_side 0; 4: train is) does not admit takes the key kEmpty before it meets the running top two, and
-// then loses as a row beyond the slice does; STORE writes INT32_MAX for it.  The geometry is the float line's: records [n][4]
-// doubles from the record kernels of kernels_match.hip, (x, y) floats widened when they are staged, t2 of the epipolar model
-// from MatchGuide.  The workgroup's queries' geometry is written to LDS once, before the loop; a train tile's is staged
-// beside Tn, both buffers, under the same barrier.  Per 16-row block a lane reads the geometry of its four train rows once
-// and that of its query of every block, and keeps the sixteen verdicts as a bit mask (bit 4 qb + reg).  MULTI forms them
-// with the last chunk of a tile.  BATCH rebinds records and coordinates to the entry's own, as match_top2_kernel does.
+//   A guided form (dlco_desc_match_guided*_u8; GuidedForm, match_dev.hpp): the same tile loop with a third epilogue.  A
+// candidate that admits<GUIDED> does not admit takes the key kEmpty before it meets the running top two, and then loses as a
+// row beyond the slice does; STORE writes INT32_MAX for it.  The workgroup's queries' geometry is written to LDS once, before
+// the loop; a train tile's is staged beside Tn, both buffers, under the same barrier.  Per 16-row block a lane reads the
+// geometry of its four train rows once and that of its query of every block, and keeps the sixteen verdicts as a bit mask
+// (bit 4 qb + reg: sixteen entries of one row block, the layout of the int8 MFMA's result).  MULTI forms them with the last
+// chunk of a tile.  BATCH: bind_entry_guide rebinds records and coordinates to the entry's own.
 struct NoGuide {};
 template <int GUIDED> struct GuideArg { using type = MatchGuide; };
-template <> struct GuideArg<0> { using type = NoGuide; };      // the plain forms keep their arguments
+template <> struct GuideArg<kPlain> { using type = NoGuide; };      // the plain forms keep their arguments
 
-template <bool STORE, bool MULTI, int GUIDED = 0, bool BATCH = false>
+template <bool STORE, bool MULTI, int GUIDED = kPlain, bool BATCH = false>
 __global__ __launch_bounds__(UTH) void match_u8_kernel(const uint8_t *__restrict__ query, long ldq, int nq, const uint8_t *__restrict__ train,
                                                        long ldt, int nt, int r, const int32_t *__restrict__ qnorm,
                                                        const int32_t *__restrict__ tneg, int tiles_per_slice, int32_t *__restrict__ idx,
@@ -140,18 +116,12 @@ __global__ __launch_bounds__(UTH) void match_u8_kernel(const uint8_t *__restrict
     const float *gxy = nullptr;
     long gld = 0;
     double gt2 = 0.0;
-    if constexpr (GUIDED != 0) { grec = g.rec; gqrec = g.qrec; gxy = g.xy; gld = g.ldxy; gt2 = g.t2; }
+    if constexpr (GUIDED != kPlain) { grec = g.rec; gqrec = g.qrec; gxy = g.xy; gld = g.ldxy; gt2 = g.t2; }
     if constexpr (BATCH) {
         const int wg = (int)blockIdx.x;
         const int ei = batch_entry_of(ent, n_ent, wg, [](const match_batch::Entry &x) { return x.wg0; });
         const match_batch::Entry e = ent[ei];
-        if constexpr (GUIDED != 0) {
-            const match_batch::GuideOff o = g.off[ei];
-            const double *qr = g.rec + 4 * o.rec0, *tr = qr + 4 * (long)o.nqrec;
-            grec = GUIDED == 1 ? qr : tr;
-            gqrec = qr;
-            gxy = g.xy + (GUIDED == 1 ? e.t0 : e.q0) * g.ldxy;
-        }
+        if constexpr (GUIDED != kPlain) bind_entry_guide<GUIDED>(g, e, ei, grec, gqrec, gxy);
         const unsigned w = (unsigned)(wg - e.wg0);
         slice = w / (unsigned)e.qblocks;
         qblk = w - slice * (unsigned)e.qblocks;
@@ -163,8 +133,7 @@ __global__ __launch_bounds__(UTH) void match_u8_kernel(const uint8_t *__restrict
     }
     __shared__ __attribute__((aligned(16))) uint8_t Bs[2][UT * UP];            // the staged tile, flipped and masked when stored
     __shared__ __attribute__((aligned(16))) int32_t Tn[2][UT];                 // -|a_t|^2 of its rows, kEmpty beyond the slice
-    constexpr int CW = GUIDED >= 2 ? 4 : 2;                // doubles of geometry a train row brings: (x, y) or a record
-    constexpr int QW = GUIDED == 1 || GUIDED >= 3 ? 4 : 2; // and a query
+    constexpr int CW = train_geom_width(GUIDED), QW = query_geom_width(GUIDED);
     __shared__ __attribute__((aligned(16))) double Tg[GUIDED ? 2 : 1][GUIDED ? UT * CW : 1];   // GUIDED: the tile's geometry, staged with it,
     __shared__ __attribute__((aligned(16))) double Qg[GUIDED ? UQ * QW : 1];   // and the workgroup's queries': written once, before the loop
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
@@ -200,45 +169,22 @@ __global__ __launch_bounds__(UTH) void match_u8_kernel(const uint8_t *__restrict
         const long jn = jt + (tid & (UT - 1));
         const int tn = tneg[jn < jend ? jn : (long)jbeg];
         rtn = jn < jend ? tn : kEmpty;
-        if constexpr (GUIDED != 0) {                       // a row beyond the slice: the slice's first row's, never consulted
-            const long js = jn < jend ? jn : (long)jbeg;
-            if constexpr (GUIDED == 1) {
-                const float *p = gxy + js * gld;
-                rg[0] = (double)p[0]; rg[1] = (double)p[1];
-            } else {
-                const f64x2 a = *reinterpret_cast<const f64x2 *>(grec + 4 * js), b = *reinterpret_cast<const f64x2 *>(grec + 4 * js + 2);
-                rg[0] = a[0]; rg[1] = a[1]; rg[2] = b[0]; rg[3] = b[1];
-            }
-        }
+        geom_fetch<GUIDED>(rg, grec, gxy, gld, jn < jend ? jn : (long)jbeg);   // a row beyond the slice: the slice's first row's, never consulted
     };
     auto lstore = [&](int buf) {
 #pragma unroll
         for (int u = 0; u < UT / 32; u++) *reinterpret_cast<i32x4 *>(&Bs[buf][(lrow + 32 * u) * UP + 16 * lseg]) = rb[u];
         if (tid < UT) {
             Tn[buf][tid] = rtn;
-            if constexpr (GUIDED != 0) {
-#pragma unroll
-                for (int e = 0; e < CW; e += 2) *reinterpret_cast<f64x2 *>(&Tg[buf][tid * CW + e]) = f64x2{rg[e], rg[e + 1]};
-            }
+            if constexpr (GUIDED != kPlain) geom_store(&Tg[buf][tid * CW], rg);
         }
     };
-    // GUIDED: the geometry of one row, a record or (x, y) in v[0], v[1]; that of row `row` of the staged tile, and that of the
-    // lane's query of block qb.  The empty asm hides from the compiler that the queries' address does not change over the
-    // tile loop: hoisted out of it, the four records would sit in registers for the whole loop.
-    struct Geom { double v[4]; };
-    auto tgeom = [&](int buf, int row) {
-        Geom o{};
-#pragma unroll
-        for (int e = 0; e < CW; e += 2) {
-            const f64x2 t = *reinterpret_cast<const f64x2 *>(&Tg[buf][row * CW + e]);
-            o.v[e] = t[0]; o.v[e + 1] = t[1];
-        }
-        return o;
-    };
+    // GUIDED: the geometry of the lane's query of block qb.  The empty asm hides from the compiler that the queries' address
+    // does not change over the tile loop: hoisted out of it, the four records would sit in registers for the whole loop.
     auto qgeom = [&](int qb) {
-        Geom o{};
         int qoff = (wave * UWQ + 16 * qb + li) * QW;
         asm volatile("" : "+v"(qoff));
+        Geom o{};                                          // not geom_read: through it these reads compile to other LDS instructions
 #pragma unroll
         for (int e = 0; e < QW; e += 2) {
             const f64x2 t = *reinterpret_cast<const f64x2 *>(&Qg[qoff + e]);
@@ -246,29 +192,17 @@ __global__ __launch_bounds__(UTH) void match_u8_kernel(const uint8_t *__restrict
         }
         return o;
     };
-    // the verdict on a query and a train row, whichever of the two carries the record (1, 2) or is src (3, 4)
-    auto admits = [&](const Geom &q, const Geom &t) -> bool {
-        if constexpr (GUIDED == 1) return guided_rules::admits(guided_rules::Rec{q.v[0], q.v[1], q.v[2], q.v[3]}, t.v[0], t.v[1]);
-        else if constexpr (GUIDED == 2) return guided_rules::admits(guided_rules::Rec{t.v[0], t.v[1], t.v[2], t.v[3]}, q.v[0], q.v[1]);
-        else if constexpr (GUIDED == 3)
-            return guided_epipolar::admits(guided_epipolar::SrcRec{q.v[0], q.v[1], q.v[2], q.v[3]},
-                                           guided_epipolar::DstRec{t.v[0], t.v[1], t.v[2], t.v[3]}, gt2);
-        else if constexpr (GUIDED == 4)
-            return guided_epipolar::admits(guided_epipolar::SrcRec{t.v[0], t.v[1], t.v[2], t.v[3]},
-                                           guided_epipolar::DstRec{q.v[0], q.v[1], q.v[2], q.v[3]}, gt2);
-        else return true;
-    };
     // which of the sixteen entries of the 16-row block sub of the staged tile the rule admits: bit 4 qb + reg
     auto admit_mask = [&](int buf, int sub) -> unsigned {
         unsigned m = 0;
         Geom t[4];
 #pragma unroll
-        for (int reg = 0; reg < 4; reg++) t[reg] = tgeom(buf, 16 * sub + 4 * lg + reg);
+        for (int reg = 0; reg < 4; reg++) t[reg] = geom_read<CW>(&Tg[buf][(16 * sub + 4 * lg + reg) * CW]);
 #pragma unroll
         for (int qb = 0; qb < UQB; qb++) {
             const Geom q = qgeom(qb);
 #pragma unroll
-            for (int reg = 0; reg < 4; reg++) m |= (admits(q, t[reg]) ? 1u : 0u) << (4 * qb + reg);
+            for (int reg = 0; reg < 4; reg++) m |= (admits<GUIDED>(q, t[reg], gt2) ? 1u : 0u) << (4 * qb + reg);
         }
         return m;
     };
@@ -291,19 +225,10 @@ __global__ __launch_bounds__(UTH) void match_u8_kernel(const uint8_t *__restrict
     };
     if (!MULTI) bload(0);
 
-    // GUIDED: the geometry of the workgroup's queries, a record (1; 3, 4: from qrec) or (x, y) (2), a thread per query; the
+    // GUIDED: the geometry of the workgroup's queries, a record or (x, y) (query_geom_fill), a thread per query; the
     // barrier before the loop orders it
-    if constexpr (GUIDED != 0) {
-        const long row = (long)qblk * UQ + tid;
-        const long rs = row < nq ? row : 0;
-        if constexpr (QW == 4) {
-            const double *qr = GUIDED == 1 ? grec : gqrec;
-            *reinterpret_cast<f64x2 *>(&Qg[tid * 4]) = *reinterpret_cast<const f64x2 *>(qr + 4 * rs);
-            *reinterpret_cast<f64x2 *>(&Qg[tid * 4 + 2]) = *reinterpret_cast<const f64x2 *>(qr + 4 * rs + 2);
-        } else {
-            const float *p = gxy + rs * gld;
-            *reinterpret_cast<f64x2 *>(&Qg[tid * 2]) = f64x2{(double)p[0], (double)p[1]};
-        }
+    if constexpr (GUIDED != kPlain) {
+        query_geom_fill<GUIDED>(&Qg[tid * QW], grec, gqrec, gxy, gld, (long)qblk * UQ + tid, nq);
     }
     int qn[UQB];                                           // STORE: |a_q|^2 of the lane's query of every block
     if (STORE) {
@@ -330,10 +255,10 @@ __global__ __launch_bounds__(UTH) void match_u8_kernel(const uint8_t *__restrict
                 const int q = q0 + 16 * qb + li;
                 const long j = jrow0 + reg;
                 int d = qn[qb] - key;
-                if constexpr (GUIDED != 0) d = ((m >> reg) & 1u) != 0 ? d : INT_MAX;
+                if constexpr (GUIDED != kPlain) d = ((m >> reg) & 1u) != 0 ? d : INT_MAX;
                 if (q < nq && j < jend) out[(long)q * nt + j] = d;
             } else {
-                if constexpr (GUIDED != 0) key = ((m >> reg) & 1u) != 0 ? key : kEmpty;
+                if constexpr (GUIDED != kPlain) key = ((m >> reg) & 1u) != 0 ? key : kEmpty;
                 const int cnt = blk * 4 + reg;
                 const bool first = key > b1[qb], second = key > b2[qb];
                 c2[qb] = first ? c1[qb] : (second ? cnt : c2[qb]);
@@ -362,7 +287,7 @@ __global__ __launch_bounds__(UTH) void match_u8_kernel(const uint8_t *__restrict
                 const i32x4 tn = *reinterpret_cast<const i32x4 *>(&Tn[buf][16 * sub + 4 * lg]);
                 const long jrow0 = (long)jbeg + (long)tile * UT + 16 * sub + 4 * lg;
                 unsigned adm = 0;
-                if constexpr (GUIDED != 0) {
+                if constexpr (GUIDED != kPlain) {
                     if (!MULTI || kc == nch - 1) adm = admit_mask(buf, sub);
                 }
 #pragma unroll
@@ -382,75 +307,24 @@ __global__ __launch_bounds__(UTH) void match_u8_kernel(const uint8_t *__restrict
     // the four lane groups of a query hold disjoint train rows: butterfly under the key, every lane ends with the top two
 #pragma unroll
     for (int qb = 0; qb < UQB; qb++) {
-        Top2 me;
+        Top2<int> me;
         me.k1 = b1[qb]; me.k2 = b2[qb];
         me.j1 = c1[qb] < 0 ? -1 : jbeg + (c1[qb] >> 2) * 16 + 4 * lg + (c1[qb] & 3);
         me.j2 = c2[qb] < 0 ? -1 : jbeg + (c2[qb] >> 2) * 16 + 4 * lg + (c2[qb] & 3);
 #pragma unroll
-        for (int o = 16; o < 64; o <<= 1) {
-            Top2 other;
-            other.k1 = __shfl_xor(me.k1, o, 64); other.j1 = __shfl_xor(me.j1, o, 64);
-            other.k2 = __shfl_xor(me.k2, o, 64); other.j2 = __shfl_xor(me.j2, o, 64);
-            me = merge2(me, other);
-        }
+        for (int o = 16; o < 64; o <<= 1) me = merge2<ByteKey>(me, shfl_xor_top2(me, o));
         const int q = q0 + 16 * qb + li;
         if (lg == 0 && q < nq) {
-            if (part) {
-                part[(long)slice * nq + q] = i32x4{me.k1, me.j1, me.k2, me.j2};
-            } else {
-                const int n = qnorm[q];
-                idx[2 * (long)q] = me.j1; idx[2 * (long)q + 1] = me.j2;
-                sqdist[2 * (long)q] = me.j1 < 0 ? INT_MAX : n - me.k1;
-                sqdist[2 * (long)q + 1] = me.j2 < 0 ? INT_MAX : n - me.k2;
-            }
+            if (part) part[(long)slice * nq + q] = ByteKey::pack(me);
+            else ByteKey::write(me, q, q, qnorm, idx, sqdist);
         }
     }
-}
-
-// the merge of a batched launch: 256 rows of an entry with more than one slice per workgroup, numbered from its mwg0
-__global__ __launch_bounds__(256) void match_u8_merge_batch_kernel(const i32x4 *__restrict__ part, const match_batch::Entry *__restrict__ ent,
-                                                                   int n_ent, const int32_t *__restrict__ qnorm, int32_t *__restrict__ idx,
-                                                                   int32_t *__restrict__ sqdist)
-{
-    const int wg = (int)blockIdx.x;
-    const match_batch::Entry e = ent[batch_entry_of(ent, n_ent, wg, [](const match_batch::Entry &x) { return x.mwg0; })];
-    const int row = (wg - e.mwg0) * 256 + threadIdx.x;
-    if (row >= e.nq) return;
-    const i32x4 *pp = part + e.part0;
-    const i32x4 p0 = pp[row];
-    Top2 me{p0[0], p0[1], p0[2], p0[3]};
-    for (int s = 1; s < e.slices; s++) {
-        const i32x4 p = pp[(long)s * e.nq + row];
-        me = merge2(me, Top2{p[0], p[1], p[2], p[3]});
-    }
-    const int n = qnorm[e.q0 + row];
-    const long o = 2 * (e.out0 + row);
-    idx[o] = me.j1; idx[o + 1] = me.j2;
-    sqdist[o] = me.j1 < 0 ? INT_MAX : n - me.k1;
-    sqdist[o + 1] = me.j2 < 0 ? INT_MAX : n - me.k2;
-}
-
-__global__ __launch_bounds__(256) void match_u8_merge_kernel(const i32x4 *__restrict__ part, int slices, int nq, const int32_t *__restrict__ qnorm,
-                                                             int32_t *__restrict__ idx, int32_t *__restrict__ sqdist)
-{
-    const int row = blockIdx.x * 256 + threadIdx.x;
-    if (row >= nq) return;
-    const i32x4 p0 = part[row];
-    Top2 me{p0[0], p0[1], p0[2], p0[3]};
-    for (int s = 1; s < slices; s++) {
-        const i32x4 p = part[(long)s * nq + row];
-        me = merge2(me, Top2{p[0], p[1], p[2], p[3]});
-    }
-    const int n = qnorm[row];
-    idx[2 * (long)row] = me.j1; idx[2 * (long)row + 1] = me.j2;
-    sqdist[2 * (long)row] = me.j1 < 0 ? INT_MAX : n - me.k1;
-    sqdist[2 * (long)row + 1] = me.j2 < 0 ? INT_MAX : n - me.k2;
 }
 
 // what a launch passes for the guide: the geometry, or nothing at all for the plain forms
 template <int GUIDED> typename GuideArg<GUIDED>::type guide_arg(const MatchGuide &g)
 {
-    if constexpr (GUIDED != 0) return g; else return NoGuide{};
+    if constexpr (GUIDED != kPlain) return g; else return NoGuide{};
 }
 
 constexpr int NTH = 256;               // four rows per workgroup, one wave each
@@ -515,26 +389,19 @@ void match_u8_top2(const uint8_t *query, long ldq, int nq, const uint8_t *train,
     const int slices = match_slicing::slices(match_slicing::kU8, nt, tiles_per_slice);
     const dim3 grid((unsigned)((nq + UQ - 1) / UQ), (unsigned)slices);
     i32x4 *pp = (!out && slices > 1) ? static_cast<i32x4 *>(part) : nullptr;
-    const bool multi = r > UK;
     const MatchGuide g = guide ? *guide : MatchGuide{};
-#define DLCO_MATCH_U8_LAUNCH(ST, MU, GU)                                                                                              \
-    hipLaunchKernelGGL((match_u8_kernel<ST, MU, GU>), grid, dim3(UTH), 0, s, query, ldq, nq, train, ldt, nt, r, qnorm, tneg,          \
-                       tiles_per_slice, idx, sqdist, pp, out, nullptr, 0, guide_arg<GU>(g))
-#define DLCO_MATCH_U8_FORM(GU)                                                                                                        \
-    do {                                                                                                                              \
-        if (out) { if (multi) DLCO_MATCH_U8_LAUNCH(true, true, GU); else DLCO_MATCH_U8_LAUNCH(true, false, GU); }                     \
-        else     { if (multi) DLCO_MATCH_U8_LAUNCH(false, true, GU); else DLCO_MATCH_U8_LAUNCH(false, false, GU); }                   \
-    } while (0)
-    if (!guide) DLCO_MATCH_U8_FORM(0);
-    else if (g.model == kGuideHomography && g.side == 0) DLCO_MATCH_U8_FORM(1);
-    else if (g.model == kGuideHomography) DLCO_MATCH_U8_FORM(2);
-    else if (g.side == 0) DLCO_MATCH_U8_FORM(3);
-    else DLCO_MATCH_U8_FORM(4);
-#undef DLCO_MATCH_U8_FORM
-#undef DLCO_MATCH_U8_LAUNCH
+    dispatch_form(guided_form_of(guide), [&](auto form) {
+        dispatch_bool(out != nullptr, [&](auto store) {
+            dispatch_bool(r > UK, [&](auto multi) {
+                hipLaunchKernelGGL((match_u8_kernel<store.value, multi.value, form.value>), grid, dim3(UTH), 0, s, query, ldq, nq, train, ldt, nt, r,
+                                   qnorm, tneg, tiles_per_slice, idx, sqdist, pp, out, nullptr, 0, guide_arg<form.value>(g));
+            });
+        });
+    });
     DLCO_HIP(hipGetLastError());
     if (pp) {
-        hipLaunchKernelGGL(match_u8_merge_kernel, dim3((unsigned)((nq + 255) / 256)), dim3(256), 0, s, pp, slices, nq, qnorm, idx, sqdist);
+        hipLaunchKernelGGL((match_merge_kernel<ByteKey, false, const int32_t, int32_t, int32_t>), dim3((unsigned)((nq + 255) / 256)), dim3(256), 0, s, pp, slices, nq,
+                           qnorm, idx, sqdist);
         DLCO_HIP(hipGetLastError());
     }
 }
@@ -550,20 +417,16 @@ void match_u8_top2_batch(const uint8_t *table, long ld, int r, const int32_t *qn
     i32x4 *pp = static_cast<i32x4 *>(part);
     const dim3 grid((unsigned)wgs);
     const MatchGuide g = guide ? *guide : MatchGuide{};
-#define DLCO_MATCH_U8_BATCH_LAUNCH(MU, GU)                                                                                            \
-    hipLaunchKernelGGL((match_u8_kernel<false, MU, GU, true>), grid, dim3(UTH), 0, s, table, ld, 0, nullptr, 0L, 0, r, qnorm, tneg, 0, idx,  \
-                       sqdist, pp, nullptr, ent, n_ent, guide_arg<GU>(g))
-#define DLCO_MATCH_U8_BATCH_FORM(GU) do { if (r > UK) DLCO_MATCH_U8_BATCH_LAUNCH(true, GU); else DLCO_MATCH_U8_BATCH_LAUNCH(false, GU); } while (0)
-    if (!guide) DLCO_MATCH_U8_BATCH_FORM(0);
-    else if (g.model == kGuideHomography && g.side == 0) DLCO_MATCH_U8_BATCH_FORM(1);
-    else if (g.model == kGuideHomography) DLCO_MATCH_U8_BATCH_FORM(2);
-    else if (g.side == 0) DLCO_MATCH_U8_BATCH_FORM(3);
-    else DLCO_MATCH_U8_BATCH_FORM(4);
-#undef DLCO_MATCH_U8_BATCH_FORM
-#undef DLCO_MATCH_U8_BATCH_LAUNCH
+    dispatch_form(guided_form_of(guide), [&](auto form) {
+        dispatch_bool(r > UK, [&](auto multi) {
+            hipLaunchKernelGGL((match_u8_kernel<false, multi.value, form.value, true>), grid, dim3(UTH), 0, s, table, ld, 0, nullptr, 0L, 0, r, qnorm,
+                               tneg, 0, idx, sqdist, pp, nullptr, ent, n_ent, guide_arg<form.value>(g));
+        });
+    });
     DLCO_HIP(hipGetLastError());
     if (merge_wgs > 0) {
-        hipLaunchKernelGGL(match_u8_merge_batch_kernel, dim3((unsigned)merge_wgs), dim3(256), 0, s, pp, ent, n_ent, qnorm, idx, sqdist);
+        hipLaunchKernelGGL((match_merge_kernel<ByteKey, true, const int32_t, int32_t, int32_t>), dim3((unsigned)merge_wgs), dim3(256), 0, s, pp, ent, n_ent,
+                           qnorm, idx, sqdist);
         DLCO_HIP(hipGetLastError());
     }
 }
