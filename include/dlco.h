@@ -606,7 +606,9 @@ int dlco_desc_cross_sqdists(dlco_desc_ctx *ctx, const float *query_host, int64_t
  * table that is not 16-byte aligned.
  *   Out of scope: a batched distance matrix; seg / pairs in device memory.
  *   In scope since: a batched verify, dlco_desc_verify_pairs_* below; guided forms of the batch,
- * dlco_desc_match_pairs_guided* below. ---- */
+ * dlco_desc_match_pairs_guided* below.
+ *   In scope since: the step from idx / sqdist to the match list of dlco_desc_verify_pairs_* (ratio test, mutual check,
+ * compaction) on the device, dlco_desc_select_pairs* below. ---- */
 /* row0 [n_pairs + 1]; needs neither a context nor a device */
 int dlco_desc_match_pairs_rows(const int64_t *seg, int32_t n_img, const int32_t *pairs, int64_t n_pairs, int64_t *row0);
 /* the table on the host, [n_rows][r] dense; idx_host / sqdist_host [row0[n_pairs]][2].  The table is held in device memory
@@ -859,7 +861,9 @@ int dlco_desc_match_pairs_guided_epipolar_u8_device(dlco_desc_ctx *ctx, const ui
  * m >= 2^31, a threshold that is not finite or <= 0, n_hyp outside 1 .. 2^20, refine outside 0 .. 8.
  *   Out of scope of this call: a device-memory form (the match list is filtered on the host); a fundamental or essential matrix
  * (the fundamental matrix has calls of its own, dlco_desc_verify_fundamental below; an essential matrix has none);
- * symmetric transfer error; an adaptive hypothesis count. */
+ * symmetric transfer error; an adaptive hypothesis count.
+ *   In scope since: filtering the match list on the device, dlco_desc_select_pairs* below, which writes the lists of
+ * dlco_desc_verify_pairs_* from a batched answer in device memory (the verification itself still takes its lists on the host). */
 int  dlco_desc_verify_homography(dlco_desc_ctx *ctx, const float *src_xy_host, const float *dst_xy_host, int64_t m, float threshold,
                                  int32_t n_hyp, uint64_t seed, int32_t refine, double *H_out, uint8_t *inlier_host, int64_t *n_inliers,
                                  int32_t *best_hyp);
@@ -924,6 +928,55 @@ int  dlco_desc_verify_pairs_fundamental_hypotheses(dlco_desc_ctx *ctx, const flo
  * call, -1 for a pair that launches nothing (fewer matches than a sample); fundamental = 0: the homography, 1: the fundamental
  * matrix.  DLCO_ERR_INVALID as above, and for another value of fundamental.  For tests and tools */
 int  dlco_desc_verify_pairs_launches(const int64_t *moff, int64_t n_pairs, int32_t n_hyp, int32_t fundamental, int32_t *launch_of_pair);
+/* ---- Selecting matches: from the answer of a dlco_desc_match_pairs* call to the lists of a dlco_desc_verify_pairs_* call.  The
+ * link between the two: Lowe's ratio test, the mutual check and the compaction into (query, train) rows, on the device, so that
+ * a caller whose idx / sqdist live in HBM need not download them, restate the rule and gather coordinates.
+ * csrc/select_rules.hpp states the rule; it is the rule of the tools match and match-pairs (-ratio, -cross).
+ *   Input: seg, n_img, pairs, n_pairs as the match_pairs call took them; idx / sqdist [R][2], R = row0[n_pairs], exactly what that
+ * call wrote, plain or guided, float or byte line (the _u8 forms take the int32 distances).  seg, pairs, back_row0 and moff are
+ * host memory in every form.  Row i of pair p = (a, b), with j = idx[i][0] and nt_b the rows of image b:
+ *     never a match if j < 0 or j >= nt_b, decided before anything is read at j: no content of idx makes the call read outside
+ *   a buffer;
+ *     ratio != 0 (it must lie in (0, 1]; 0: no ratio test): kept iff idx[i][1] == -1 or
+ *   (double)sqdist[i][0] < (double)ratio * (double)ratio * (double)sqdist[i][1]; equality is dropped, and so is 0 < 0;
+ *     back_idx != NULL (NULL: no mutual check): back_idx [n_back_rows][2] holds the reverse answers, back_row0 [n_pairs] the
+ *   first row of pair p's, image b's rows matched against image a, or -1 for "no mutual check for this pair"; kept iff
+ *   back_idx[back_row0[p] + j][0] == i.  back_idx may be idx itself with back_row0[p] = row0[q], q the reversed pair of the same
+ *   batch (how match-pairs -cross batches them), or the answer of a second call (how the guided tools run side 1).
+ *     xy != NULL (NULL: no coordinates, and then src_xy and dst_xy must be NULL): the batch's coordinate table as
+ *   dlco_desc_match_pairs_guided* takes it, [seg[n_img]][2] on the host, pitch ldxy >= 2 floats on the device (4 takes the rows
+ *   dlco_desc_detect_device wrote).
+ *   Output: moff [n_pairs + 1]; matches [.][2] int32, (i, j) as rows of the pair's own two images; dist [.], sqdist[i][0], float
+ * or int32; src_xy, dst_xy [.][2] float, the (x, y) of row i of image a and row j of image b.  The caller provides R entries of
+ * each list; the first M = moff[n_pairs] are written, pairs in order and rows ascending inside a pair, the rest is not touched.
+ * moff, src_xy and dst_xy are the arguments of dlco_desc_verify_pairs_*.  Everything is an integer or a comparison: no result
+ * depends on the other pairs of the batch or on the run.  Empty images, pairs that keep nothing and M = 0 are normal.
+ *   The device forms are queued on the context's stream and synchronised on return.  Like the matcher, the calls use the context
+ * for its device, stream and scratch only.
+ *   DLCO_ERR_INVALID, before the handle is used and with no output touched: a null handle or required pointer (seg, pairs, idx,
+ * sqdist, moff, matches, dist), whatever dlco_desc_match_pairs rejects of seg / pairs, R >= 2^31, a ratio that is NaN, negative or
+ * above 1, back_idx without back_row0, a back_row0[p] below -1 or one whose nt_b rows end beyond n_back_rows, src_xy or dst_xy
+ * without xy or only one of the two, ldxy < 2 with xy.
+ *   Out of scope: a device-memory form of dlco_desc_verify_pairs_* (its refit runs on the host and needs the list there anyway);
+ * seg / pairs in device memory; the tools, which keep their host rule; single-pair entry points: a batch of one pair is the
+ * single call. ---- */
+int  dlco_desc_select_pairs(dlco_desc_ctx *ctx, const int64_t *seg, int32_t n_img, const int32_t *pairs, int64_t n_pairs,
+                            const int32_t *idx_host, const float *sqdist_host, float ratio, const int32_t *back_idx_host,
+                            const int64_t *back_row0, int64_t n_back_rows, const float *xy_host, int64_t *moff, int32_t *matches_host,
+                            float *dist_host, float *src_xy_host, float *dst_xy_host);
+int  dlco_desc_select_pairs_device(dlco_desc_ctx *ctx, const int64_t *seg, int32_t n_img, const int32_t *pairs, int64_t n_pairs,
+                                   const int32_t *idx_dev, const float *sqdist_dev, float ratio, const int32_t *back_idx_dev,
+                                   const int64_t *back_row0, int64_t n_back_rows, const float *xy_dev, int64_t ldxy, int64_t *moff,
+                                   int32_t *matches_dev, float *dist_dev, float *src_xy_dev, float *dst_xy_dev);
+/* the same on the answer of the byte line (dlco_desc_match_pairs_u8, dlco_desc_match_pairs_guided*_u8): int32 distances */
+int  dlco_desc_select_pairs_u8(dlco_desc_ctx *ctx, const int64_t *seg, int32_t n_img, const int32_t *pairs, int64_t n_pairs,
+                               const int32_t *idx_host, const int32_t *sqdist_host, float ratio, const int32_t *back_idx_host,
+                               const int64_t *back_row0, int64_t n_back_rows, const float *xy_host, int64_t *moff, int32_t *matches_host,
+                               int32_t *dist_host, float *src_xy_host, float *dst_xy_host);
+int  dlco_desc_select_pairs_u8_device(dlco_desc_ctx *ctx, const int64_t *seg, int32_t n_img, const int32_t *pairs, int64_t n_pairs,
+                                      const int32_t *idx_dev, const int32_t *sqdist_dev, float ratio, const int32_t *back_idx_dev,
+                                      const int64_t *back_row0, int64_t n_back_rows, const float *xy_dev, int64_t ldxy, int64_t *moff,
+                                      int32_t *matches_dev, int32_t *dist_dev, float *src_xy_dev, float *dst_xy_dev);
 /* HIP-event time of the kernels of the last compute / describe call (transform, pooling, projection, and the sampling
  * for the keypoint calls; extract_patches: the sampling alone); the pair_sqdists /
  * pair_stats calls add their distance kernel; after a match / cross_sqdists call, float or _u8, the time of its kernels
@@ -934,7 +987,8 @@ int  dlco_desc_verify_pairs_launches(const int64_t *moff, int64_t n_pairs, int32
  * verify call the verify kernels, of either model, as after a verify_pairs call of one pair, which is what a verify call
  * runs; after a verify_pairs call every kernel of the call (the hypotheses and the scoring of every launch; the model forms,
  * verify_homography, verify_fundamental, verify_pairs_homography and verify_pairs_fundamental, add the selection, the mask
- * of the best models and the mask launch of every lockstep refit round) */
+ * of the best models and the mask launch of every lockstep refit round); after a select_pairs call, float or _u8, its kernels
+ * (the flags, the scan of the block counts, the scatter, the match offsets; 0 when the batch has no row) */
 double dlco_desc_last_kernel_ms(const dlco_desc_ctx *ctx);
 
 #ifdef __cplusplus

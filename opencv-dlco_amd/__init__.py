@@ -225,6 +225,10 @@ def load():
     L.dlco_desc_match_pairs_u8.argtypes = [vp, u8p, i64p, C.c_int32, i32p, i64, C.c_int32, i32p, i32p]
     L.dlco_desc_match_pairs_u8_device.argtypes = [vp, vp, i64, i64p, C.c_int32, i32p, i64, C.c_int32, vp, vp]
     L.dlco_desc_match_pairs_slices.argtypes = [vp, i64p, C.c_int32, i32p, i64, C.c_int32, i32p]
+    L.dlco_desc_select_pairs.argtypes = [vp, i64p, C.c_int32, i32p, i64, i32p, f32p, C.c_float, i32p, i64p, i64, f32p, i64p, i32p, f32p, f32p, f32p]
+    L.dlco_desc_select_pairs_device.argtypes = [vp, i64p, C.c_int32, i32p, i64, vp, vp, C.c_float, vp, i64p, i64, vp, i64, i64p, vp, vp, vp, vp]
+    L.dlco_desc_select_pairs_u8.argtypes = [vp, i64p, C.c_int32, i32p, i64, i32p, i32p, C.c_float, i32p, i64p, i64, f32p, i64p, i32p, i32p, f32p, f32p]
+    L.dlco_desc_select_pairs_u8_device.argtypes = L.dlco_desc_select_pairs_device.argtypes
     L.dlco_desc_match_pairs_guided.argtypes = [vp, f32p, f32p, i64p, C.c_int32, i32p, i64, C.c_int32, f64p, C.c_float, C.c_int32, i32p, f32p]
     L.dlco_desc_match_pairs_guided_device.argtypes = [vp, vp, i64, vp, i64, i64p, C.c_int32, i32p, i64, C.c_int32, f64p, C.c_float, C.c_int32,
                                                       vp, vp]
@@ -1462,6 +1466,95 @@ class DescContext:
         """match_pairs_guided_epipolar_u8 on tables in device memory, pitches as match_pairs_guided_u8_device."""
         self._match_pairs_guided_device(self.L.dlco_desc_match_pairs_guided_epipolar_u8_device, table_ptr, xy_ptr, seg, pairs, r, F, idx_ptr,
                                         d_ptr, threshold, f_side, ld, ldxy)
+
+    # ---- selecting matches: from the answer of match_pairs to the lists of verify_pairs (csrc/select_rules.hpp states the rule) ----
+    @staticmethod
+    def _select_seg(answers, sizes_or_seg, q):
+        """seg [n_img + 1] from the row counts of the images [n_img] or from seg itself, whichever fits the answers: pair
+        (a, b)'s answer has as many rows as image a.  Row counts are tried first."""
+        s = np.ascontiguousarray(sizes_or_seg, np.int64)
+        assert s.ndim == 1 and s.size >= 1 and len(answers) == q.shape[0]
+        rows = np.array([len(a[0]) for a in answers], np.int64)
+        fits = lambda n: q.size > 0 and q.min() >= 0 and q.max() < n.size and np.array_equal(n[q[:, 0]], rows)
+        if fits(s):
+            return np.concatenate([[0], np.cumsum(s)]).astype(np.int64)
+        assert s.size >= 2 and s[0] == 0 and fits(np.diff(s)), "select_pairs: neither the row counts nor seg of these answers"
+        return s
+
+    def _select_pairs(self, call, answers, sizes_or_seg, pairs, ratio, back, xys, dist):
+        q = np.ascontiguousarray(pairs, np.int32)
+        assert q.ndim == 2 and q.shape[1] == 2
+        seg = self._select_seg(answers, sizes_or_seg, q)
+        P, dp = q.shape[0], C.POINTER(C.c_float if dist == np.float32 else C.c_int32)
+        stack = lambda ans, k, t: np.ascontiguousarray(np.concatenate([np.reshape(np.asarray(a[k], t), (-1, 2)) for a in ans] + [np.zeros((1, 2), t)]))
+        idx, d = stack(answers, 0, np.int32), stack(answers, 1, dist)       # a row of padding: an empty answer still has an address
+        row0 = match_pairs_rows(seg, q)
+        R = int(row0[-1])
+        bidx, brow0, nback = None, None, 0
+        if back is not None:
+            assert len(back) == P
+            if all(b is None or isinstance(b, (int, np.integer)) for b in back):    # the same batch: back[p] names the pair that reverses p
+                bidx, nback = idx, R
+                brow0 = np.array([-1 if b is None or b < 0 else row0[int(b)] for b in back], np.int64)
+            else:                                                           # a second answer list, None where a pair has none
+                n = [0 if b is None else len(b[0]) for b in back]
+                brow0 = np.concatenate([[0], np.cumsum(n)])[:-1].astype(np.int64)
+                brow0[[b is None for b in back]] = -1
+                bidx, nback = stack([b for b in back if b is not None], 0, np.int32), int(sum(n))
+        xy = src = dst = None
+        if xys is not None:
+            assert len(xys) == seg.size - 1 and all(np.shape(x) == (seg[k + 1] - seg[k], 2) for k, x in enumerate(xys))
+            xy = np.ascontiguousarray(np.concatenate([_f32(x).reshape(-1, 2) for x in xys] + [np.zeros((1, 2), np.float32)]))
+            src, dst = np.empty((R + 1, 2), np.float32), np.empty((R + 1, 2), np.float32)
+        moff, m, dd = np.empty(P + 1, np.int64), np.empty((R + 1, 2), np.int32), np.empty(R + 1, dist)
+        self._ck(call(self.h, _p(seg, i64p), seg.size - 1, _p(q, i32p), P, _p(idx, i32p), _p(d, dp), 0.0 if ratio is None else ratio,
+                      _p(bidx, i32p), _p(brow0, i64p), nback, _p(xy, f32p), _p(moff, i64p), _p(m, i32p), _p(dd, dp), _p(src, f32p), _p(dst, f32p)))
+        sel = [(m[moff[p]:moff[p + 1]], dd[moff[p]:moff[p + 1]]) for p in range(P)]
+        if xys is None:
+            return sel
+        return sel, [(src[moff[p]:moff[p + 1]], dst[moff[p]:moff[p + 1]]) for p in range(P)]
+
+    def select_pairs(self, answers, sizes_or_seg, pairs, ratio=None, back=None, xys=None):
+        """The matches of every pair of a match_pairs / match_pairs_guided* answer, selected on the device: answers is the list
+        those calls return, sizes_or_seg the row counts of the images [n_img] (or seg [n_img + 1]), pairs as they took them.
+        ratio (None: no ratio test, else in (0, 1]) is Lowe's test, idx2 == -1 or d1 < ratio^2 d2 in double; back asks for the
+        mutual check: either a list of pair indices, back[p] the pair of this batch that reverses p (None or -1: no check for p),
+        or a second answer list, back[p] the answer of (b, a) (None: no check for p).  Returns per pair (matches [m, 2] int32 of
+        (query row, train row), dist [m] float32), rows ascending.  With xys, the list of [n_s, 2] keypoint coordinates of the
+        images, returns (that list, lists), lists the per-pair (src [m, 2], dst [m, 2]) that verify_pairs_* take."""
+        return self._select_pairs(self.L.dlco_desc_select_pairs, answers, sizes_or_seg, pairs, ratio, back, xys, np.float32)
+
+    def select_pairs_u8(self, answers, sizes_or_seg, pairs, ratio=None, back=None, xys=None):
+        """select_pairs on the answers of the byte line (match_pairs_u8, match_pairs_guided*_u8): dist [m] int32."""
+        return self._select_pairs(self.L.dlco_desc_select_pairs_u8, answers, sizes_or_seg, pairs, ratio, back, xys, np.int32)
+
+    def _select_pairs_device(self, call, idx_ptr, d_ptr, seg, pairs, matches_ptr, dist_ptr, ratio, back_idx_ptr, back_row0, n_back_rows, xy_ptr, ldxy,
+                             src_ptr, dst_ptr):
+        s, q = _seg_pairs(seg, pairs)
+        b = None if back_row0 is None else np.ascontiguousarray(back_row0, np.int64)
+        assert b is None or b.shape == (q.shape[0],)
+        moff = np.empty(q.shape[0] + 1, np.int64)
+        ptr = lambda a: None if a is None else C.c_void_p(a)
+        self._ck(call(self.h, _p(s, i64p), s.size - 1, _p(q, i32p), q.shape[0], ptr(idx_ptr), ptr(d_ptr), 0.0 if ratio is None else ratio,
+                      ptr(back_idx_ptr), _p(b, i64p), n_back_rows, ptr(xy_ptr), ldxy, _p(moff, i64p), ptr(matches_ptr), ptr(dist_ptr), ptr(src_ptr),
+                      ptr(dst_ptr)))
+        return moff
+
+    def select_pairs_device(self, idx_ptr, d_ptr, seg, pairs, matches_ptr, dist_ptr, ratio=None, back_idx_ptr=None, back_row0=None, n_back_rows=0,
+                            xy_ptr=None, ldxy=2, src_ptr=None, dst_ptr=None):
+        """select_pairs on an answer in device memory, idx / sqdist [R, 2] as match_pairs_device wrote them for seg and pairs
+        (R = match_pairs_rows(seg, pairs)[-1]).  back_idx_ptr [n_back_rows, 2] holds the reverse answers and back_row0 [n_pairs]
+        the first row of every pair's (-1: no check); it may be idx_ptr itself.  xy_ptr is the coordinate table (pitch ldxy
+        floats).  The lists go to device memory of R entries each: matches [., 2] int32, dist [.] float32, and with xy_ptr src,
+        dst [., 2] float32.  Returns moff [n_pairs + 1] int64; the first moff[-1] entries are written."""
+        return self._select_pairs_device(self.L.dlco_desc_select_pairs_device, idx_ptr, d_ptr, seg, pairs, matches_ptr, dist_ptr, ratio, back_idx_ptr,
+                                         back_row0, n_back_rows, xy_ptr, ldxy, src_ptr, dst_ptr)
+
+    def select_pairs_u8_device(self, idx_ptr, d_ptr, seg, pairs, matches_ptr, dist_ptr, ratio=None, back_idx_ptr=None, back_row0=None, n_back_rows=0,
+                               xy_ptr=None, ldxy=2, src_ptr=None, dst_ptr=None):
+        """select_pairs_device on the answer of match_pairs_u8_device: int32 distances in and out."""
+        return self._select_pairs_device(self.L.dlco_desc_select_pairs_u8_device, idx_ptr, d_ptr, seg, pairs, matches_ptr, dist_ptr, ratio,
+                                         back_idx_ptr, back_row0, n_back_rows, xy_ptr, ldxy, src_ptr, dst_ptr)
 
     def match_pairs_slices(self, seg, pairs, u8=False):
         """The plan only: slices [n_pairs] int32 of train that each pair is cut into in such a call on this context's device

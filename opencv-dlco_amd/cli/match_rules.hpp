@@ -2,6 +2,8 @@
 // functions, no device, no I/O (tests/shim/match_rules_shim.cpp runs them on a machine without a GPU).
 #pragma once
 
+#include "../csrc/select_rules.hpp"
+
 #include <cstdint>
 #include <vector>
 
@@ -9,24 +11,17 @@ namespace match_rules {
 
 // Lowe's ratio test on L2 distances, stated on the squared ones: the nearest row is kept iff it is closer than f times
 // the second nearest, d1 < f^2 d2 in double (so d1 == f^2 d2 is dropped, and d1 = d2 = 0 is dropped).  A query without
-// a second neighbour (idx2 == -1, a train table of one row) has nothing to be compared with and is kept.
-inline bool ratio_keep(float d1, float d2, int32_t idx2, float f)
-{
-    if (idx2 == -1) return true;
-    return (double)d1 < (double)f * (double)f * (double)d2;
-}
-
-// The same test on the exact integer distances of byte tables (dlco_desc_match_u8): the same comparison in double, in which
-// an int32 and its product with f^2 of a float f are exact enough that d1 == f^2 d2 is still dropped.
-inline bool ratio_keep(int32_t d1, int32_t d2, int32_t idx2, float f)
-{
-    if (idx2 == -1) return true;
-    return (double)d1 < (double)f * (double)f * (double)d2;
-}
+// a second neighbour (idx2 == -1, a train table of one row) has nothing to be compared with and is kept.  On the exact
+// integer distances of byte tables (dlco_desc_match_u8) the same comparison in double, in which an int32 and its product
+// with f^2 of a float f are exact enough that d1 == f^2 d2 is still dropped.  csrc/select_rules.hpp states both, for these
+// filters and for the library's dlco_desc_select_pairs*:
+//   bool ratio_keep(float d1, float d2, int32_t idx2, float f);   bool ratio_keep(int32_t d1, int32_t d2, int32_t idx2, float f);
+using select_rules::ratio_keep;
 
 // The mutual rule: (i, j) is kept iff the nearest query of train row j is i.  back [nt][2] is the library's answer with
 // the tables swapped.
-inline bool cross_keep(int64_t i, int32_t j, const int32_t *back) { return back[2 * (int64_t)j] == (int32_t)i; }
+//   bool cross_keep(int64_t i, int32_t j, const int32_t *back);
+using select_rules::cross_keep;
 
 // The filtered list for nearest [nq][2] / sqdist [nq][2]: pairs (query, train) ascending in query and their squared
 // distances.  use_ratio / back (NULL: no mutual check) select the rules; both may be given; an empty list is a valid result.

@@ -6,7 +6,7 @@
 // quantisation of rows to bytes (quant_rules.hpp) and the match of byte tables in kernels_match_u8.hip, the detection of
 // keypoints (detect_rules.hpp) in kernels_detect.hip, their orientation (orient_rules.hpp) in kernels_orient.hip, the
 // verification of a match list against a homography (verify_rules.hpp) or a fundamental matrix (epipolar_rules.hpp) in
-// kernels_verify.hip.
+// kernels_verify.hip, the selection of matches from a batched answer (select_rules.hpp) in kernels_select.hip.
 // compute() serves every describe call: a PatchSource in, the rows a RowsOut names out.  The float and the byte matcher
 // share one host path (match_host, match_device) over a FloatLine / ByteLine.
 #include "../../include/dlco.h"
@@ -107,6 +107,14 @@ struct dlco_desc_ctx {
     DevBuf<int32_t> v_count, v_n;
     DevBuf<uint64_t> v_key;
     DevBuf<uint8_t> v_mask, v_plan;
+    // selecting matches (dlco_desc_select_pairs*, select_rules.hpp): the uploaded pairs, the kept rows as bits, the block
+    // counts, their exclusive sums and the match offsets; for the host forms the uploaded answer, reverse table and
+    // coordinates and the lists on their way down (distances of either line as 4-byte words); buffers of their own
+    DevBuf<select_rules::Pair> s_pairs;
+    DevBuf<uint64_t> s_word;
+    DevBuf<int32_t> s_count, s_idx, s_sqdist, s_back, s_matches, s_dist;
+    DevBuf<int64_t> s_off, s_moff;
+    DevBuf<float> s_xy, s_src, s_dst;
     double last_ms = 0.0;
 };
 
@@ -560,6 +568,118 @@ void match_pairs_host(dlco_desc_ctx *c, const typename L::Elem *table_host, cons
         DLCO_HIP(hipMemcpyAsync(sqdist_host, b.sqdist.p, (size_t)out_rows * 2 * sizeof(Dist), hipMemcpyDeviceToHost, c->stream));
     }
     sync(c);
+}
+
+// ---- selecting matches (dlco_desc_select_pairs*): from the answer of a match_pairs call to the segmented match list of a
+// verify_pairs call, by the rule of select_rules.hpp in kernels_select.hip.  One path over the distance type of the two lines;
+// the host forms are the device path between an upload and a download -----------------------------------------------------------
+struct SelectArgs {
+    const int64_t *seg; int32_t n_img;
+    const int32_t *pairs; int64_t n_pairs;
+    float ratio;
+    const int64_t *back_row0; int64_t n_back_rows;
+    int64_t *moff;
+};
+
+// xy: ldxy is looked at only with a coordinate table
+bool select_args_ok(const SelectArgs &a, const void *idx, const void *sqdist, const void *back, const void *xy, int64_t ldxy, const void *matches,
+                    const void *dist, const void *src, const void *dst)
+{
+    if (!idx || !sqdist || !a.moff || !matches || !dist || !match_pairs_args_ok(a.seg, a.n_img, a.pairs, a.n_pairs)) return false;
+    if (!select_rules::ratio_ok(a.ratio)) return false;
+    if (back && !select_rules::back_rows_ok(a.seg, a.pairs, a.n_pairs, a.back_row0, a.n_back_rows)) return false;
+    if (xy ? (!src || !dst || ldxy < 2) : (src || dst)) return false;
+    int64_t rows = 0;                                      // fewer than 2^31 pairs of fewer than 2^31 rows each: no overflow
+    for (int64_t p = 0; p < a.n_pairs; p++) rows += a.seg[a.pairs[2 * p] + 1] - a.seg[a.pairs[2 * p]];
+    return rows < ((int64_t)1 << 31);
+}
+
+// every table in device memory, moff on the host: the kernels, timed, and the download of the offsets behind them
+template <typename Dist>
+void select_on_device(dlco_desc_ctx *c, const std::vector<select_rules::Pair> &rec, int64_t R, const int32_t *idx, const Dist *sqdist, float f,
+                      const int32_t *back, const float *xy, int64_t ldxy, int64_t *moff, int32_t *matches, Dist *dist, float *src, float *dst)
+{
+    const int64_t P = (int64_t)rec.size();
+    if (R == 0) {                                          // every query image is empty: no row, no match, nothing to launch
+        std::fill(moff, moff + P + 1, (int64_t)0);
+        c->last_ms = 0.0;
+        return;
+    }
+    const int64_t nb = select_rules::blocks(R);
+    c->s_pairs.alloc((size_t)P);
+    c->s_word.alloc((size_t)nb * (select_rules::kBlockRows / 64));
+    c->s_count.alloc((size_t)nb);
+    c->s_off.alloc((size_t)nb + 1);
+    c->s_moff.alloc((size_t)P + 1);
+    DLCO_HIP(hipMemcpyAsync(c->s_pairs.p, rec.data(), (size_t)P * sizeof(select_rules::Pair), hipMemcpyHostToDevice, c->stream));
+    EventPair ev;
+    c->last_ms = timed_ms(c, ev, [&] {
+        select_flag(c->s_pairs.p, P, R, idx, sqdist, f, back, c->s_word.p, c->s_count.p, c->stream);
+        select_scan(c->s_count.p, nb, c->s_off.p, c->stream);
+        select_scatter(c->s_pairs.p, P, R, idx, sqdist, c->s_word.p, c->s_off.p, xy, ldxy, matches, dist, src, dst, c->stream);
+        select_offsets(c->s_pairs.p, P, R, c->s_word.p, c->s_off.p, c->s_moff.p, c->stream);
+    }, [&] { DLCO_HIP(hipMemcpyAsync(moff, c->s_moff.p, (size_t)(P + 1) * sizeof(int64_t), hipMemcpyDeviceToHost, c->stream)); });
+}
+
+template <typename Dist>
+int select_pairs_device_call(dlco_desc_ctx *c, const SelectArgs &a, const int32_t *idx_dev, const Dist *sqdist_dev, const int32_t *back_dev,
+                             const float *xy_dev, int64_t ldxy, int32_t *matches_dev, Dist *dist_dev, float *src_dev, float *dst_dev)
+{
+    if (!c || !select_args_ok(a, idx_dev, sqdist_dev, back_dev, xy_dev, ldxy, matches_dev, dist_dev, src_dev, dst_dev)) return DLCO_ERR_INVALID;
+    return guarded(c, [&] {
+        DLCO_HIP(hipSetDevice(c->device));
+        std::vector<select_rules::Pair> rec;
+        const int64_t R = select_rules::pair_records(a.seg, a.pairs, a.n_pairs, back_dev ? a.back_row0 : nullptr, rec);
+        select_on_device<Dist>(c, rec, R, idx_dev, sqdist_dev, a.ratio, back_dev, xy_dev, ldxy, a.moff, matches_dev, dist_dev, src_dev, dst_dev);
+    });
+}
+
+// the host form: the answer, the reverse table (unless it is the answer itself) and the coordinates go up once, the first
+// M entries of the lists come down
+template <typename Dist>
+int select_pairs_host_call(dlco_desc_ctx *c, const SelectArgs &a, const int32_t *idx_host, const Dist *sqdist_host, const int32_t *back_host,
+                           const float *xy_host, int32_t *matches_host, Dist *dist_host, float *src_host, float *dst_host)
+{
+    static_assert(sizeof(Dist) == sizeof(int32_t), "distances travel as 4-byte words");
+    if (!c || !select_args_ok(a, idx_host, sqdist_host, back_host, xy_host, 2, matches_host, dist_host, src_host, dst_host)) return DLCO_ERR_INVALID;
+    return guarded(c, [&] {
+        DLCO_HIP(hipSetDevice(c->device));
+        std::vector<select_rules::Pair> rec;
+        const int64_t R = select_rules::pair_records(a.seg, a.pairs, a.n_pairs, back_host ? a.back_row0 : nullptr, rec);
+        const int64_t n_rows = a.seg[a.n_img];
+        const bool back_is_idx = back_host == idx_host && a.n_back_rows <= R;
+        if (R > 0) {
+            try {
+                c->s_idx.alloc((size_t)R * 2);
+                c->s_sqdist.alloc((size_t)R * 2);
+                c->s_matches.alloc((size_t)R * 2);
+                c->s_dist.alloc((size_t)R);
+                if (back_host && !back_is_idx) c->s_back.alloc((size_t)a.n_back_rows * 2);
+                if (xy_host) { c->s_xy.alloc((size_t)n_rows * 2); c->s_src.alloc((size_t)R * 2); c->s_dst.alloc((size_t)R * 2); }
+            } catch (const Error &e) {
+                throw Error(DLCO_ERR_HIP, std::string("dlco_desc_select_pairs: the tables and the lists do not fit in device memory: ") + e.what());
+            }
+            DLCO_HIP(hipMemcpyAsync(c->s_idx.p, idx_host, (size_t)R * 2 * sizeof(int32_t), hipMemcpyHostToDevice, c->stream));
+            DLCO_HIP(hipMemcpyAsync(c->s_sqdist.p, sqdist_host, (size_t)R * 2 * sizeof(Dist), hipMemcpyHostToDevice, c->stream));
+            if (back_host && !back_is_idx && a.n_back_rows > 0)
+                DLCO_HIP(hipMemcpyAsync(c->s_back.p, back_host, (size_t)a.n_back_rows * 2 * sizeof(int32_t), hipMemcpyHostToDevice, c->stream));
+            if (xy_host) DLCO_HIP(hipMemcpyAsync(c->s_xy.p, xy_host, (size_t)n_rows * 2 * sizeof(float), hipMemcpyHostToDevice, c->stream));
+        }
+        const int32_t *back_dev = !back_host ? nullptr : back_is_idx ? c->s_idx.p : c->s_back.p;
+        Dist *dist_dev = reinterpret_cast<Dist *>(c->s_dist.p);
+        select_on_device<Dist>(c, rec, R, c->s_idx.p, reinterpret_cast<const Dist *>(c->s_sqdist.p), a.ratio, back_dev, xy_host ? c->s_xy.p : nullptr, 2,
+                               a.moff, c->s_matches.p, dist_dev, c->s_src.p, c->s_dst.p);
+        const int64_t M = a.moff[a.n_pairs];
+        if (M > 0) {
+            DLCO_HIP(hipMemcpyAsync(matches_host, c->s_matches.p, (size_t)M * 2 * sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
+            DLCO_HIP(hipMemcpyAsync(dist_host, dist_dev, (size_t)M * sizeof(Dist), hipMemcpyDeviceToHost, c->stream));
+            if (xy_host) {
+                DLCO_HIP(hipMemcpyAsync(src_host, c->s_src.p, (size_t)M * 2 * sizeof(float), hipMemcpyDeviceToHost, c->stream));
+                DLCO_HIP(hipMemcpyAsync(dst_host, c->s_dst.p, (size_t)M * 2 * sizeof(float), hipMemcpyDeviceToHost, c->stream));
+            }
+            sync(c);
+        }
+    });
 }
 
 // ---- verification: a homography (verify_rules.hpp) or a fundamental matrix (epipolar_rules.hpp) between the two sides of
@@ -1428,6 +1548,24 @@ int dlco_desc_match_pairs_slices(dlco_desc_ctx *c, const int64_t *seg, int32_t n
     });
 }
 
+// ---- selecting matches from a batched answer (select_rules.hpp): the float line; the byte line is with the other _u8 calls ----
+int dlco_desc_select_pairs(dlco_desc_ctx *c, const int64_t *seg, int32_t n_img, const int32_t *pairs, int64_t n_pairs, const int32_t *idx_host,
+                           const float *sqdist_host, float ratio, const int32_t *back_idx_host, const int64_t *back_row0, int64_t n_back_rows,
+                           const float *xy_host, int64_t *moff, int32_t *matches_host, float *dist_host, float *src_xy_host, float *dst_xy_host)
+{
+    return select_pairs_host_call<float>(c, SelectArgs{seg, n_img, pairs, n_pairs, ratio, back_row0, n_back_rows, moff}, idx_host, sqdist_host,
+                                         back_idx_host, xy_host, matches_host, dist_host, src_xy_host, dst_xy_host);
+}
+
+int dlco_desc_select_pairs_device(dlco_desc_ctx *c, const int64_t *seg, int32_t n_img, const int32_t *pairs, int64_t n_pairs, const int32_t *idx_dev,
+                                  const float *sqdist_dev, float ratio, const int32_t *back_idx_dev, const int64_t *back_row0, int64_t n_back_rows,
+                                  const float *xy_dev, int64_t ldxy, int64_t *moff, int32_t *matches_dev, float *dist_dev, float *src_xy_dev,
+                                  float *dst_xy_dev)
+{
+    return select_pairs_device_call<float>(c, SelectArgs{seg, n_img, pairs, n_pairs, ratio, back_row0, n_back_rows, moff}, idx_dev, sqdist_dev,
+                                           back_idx_dev, xy_dev, ldxy, matches_dev, dist_dev, src_xy_dev, dst_xy_dev);
+}
+
 // ---- guided matching: the nearest two among the rows a two-view model admits: a homography (guided_rules.hpp) or a
 // fundamental matrix (guided_epipolar_rules.hpp; records on both sides), the guided epilogue of the tile loop in
 // kernels_match.hip and kernels_match_u8.hip.  Either line's host path with a Geometry: the calls below are one body per
@@ -1860,6 +1998,23 @@ int dlco_desc_match_pairs_u8_device(dlco_desc_ctx *c, const uint8_t *table_dev, 
     return guarded(c, [&] { match_pairs_device<ByteLine>(c, table_dev, (long)ld, seg, n_img, pairs, n_pairs, r, idx_dev, sqdist_dev); });
 }
 
+int dlco_desc_select_pairs_u8(dlco_desc_ctx *c, const int64_t *seg, int32_t n_img, const int32_t *pairs, int64_t n_pairs, const int32_t *idx_host,
+                              const int32_t *sqdist_host, float ratio, const int32_t *back_idx_host, const int64_t *back_row0, int64_t n_back_rows,
+                              const float *xy_host, int64_t *moff, int32_t *matches_host, int32_t *dist_host, float *src_xy_host, float *dst_xy_host)
+{
+    return select_pairs_host_call<int32_t>(c, SelectArgs{seg, n_img, pairs, n_pairs, ratio, back_row0, n_back_rows, moff}, idx_host, sqdist_host,
+                                           back_idx_host, xy_host, matches_host, dist_host, src_xy_host, dst_xy_host);
+}
+
+int dlco_desc_select_pairs_u8_device(dlco_desc_ctx *c, const int64_t *seg, int32_t n_img, const int32_t *pairs, int64_t n_pairs,
+                                     const int32_t *idx_dev, const int32_t *sqdist_dev, float ratio, const int32_t *back_idx_dev,
+                                     const int64_t *back_row0, int64_t n_back_rows, const float *xy_dev, int64_t ldxy, int64_t *moff,
+                                     int32_t *matches_dev, int32_t *dist_dev, float *src_xy_dev, float *dst_xy_dev)
+{
+    return select_pairs_device_call<int32_t>(c, SelectArgs{seg, n_img, pairs, n_pairs, ratio, back_row0, n_back_rows, moff}, idx_dev, sqdist_dev,
+                                             back_idx_dev, xy_dev, ldxy, matches_dev, dist_dev, src_xy_dev, dst_xy_dev);
+}
+
 int dlco_desc_cross_sqdists_u8(dlco_desc_ctx *c, const uint8_t *query_u8, int64_t nq, const uint8_t *train_u8, int64_t nt, int32_t r,
                                int32_t *out_host)
 {
@@ -1876,7 +2031,7 @@ int dlco_desc_cross_sqdists_u8(dlco_desc_ctx *c, const uint8_t *query_u8, int64_
 // call formed it; after a detect call the detector's kernels (the integral image when the call
 // formed it, the octaves, the selection); after a verify or verify_pairs call every kernel of every launch of the call: for
 // the _hypotheses forms the hypotheses and the scoring, for the model forms these, the selection, the mask of the best models
-// and the mask launches of the lockstep refit rounds
+// and the mask launches of the lockstep refit rounds; after a select_pairs call its four kernels (flag, scan, scatter, offsets)
 double dlco_desc_last_kernel_ms(const dlco_desc_ctx *c) { return c ? c->last_ms : 0.0; }
 
 }  // extern "C"

@@ -5,6 +5,7 @@
 #include "../../include/dlco.h"
 #include "match_batch.hpp"
 #include "match_slices.hpp"
+#include "select_rules.hpp"
 #include "verify_batch.hpp"
 
 #include <hip/hip_runtime.h>
@@ -627,5 +628,20 @@ void verify_pairs_select(const int32_t *count, const double *M_all, int64_t n_en
 template <typename Model>
 void verify_pairs_mask(const float *src, const float *dst, const verify_batch::Entry *ent, const verify_batch::Active *active, int64_t n_active,
                        int64_t mask_wgs, const double *M_cur, double t2, uint8_t *mask, int32_t *n, hipStream_t s);
+
+// selecting matches (kernels_select.hip; the rule is select_rules.hpp): the steps of a dlco_desc_select_pairs* call over the
+// R >= 1 rows of a batched answer idx, sqdist [R][2], pairs [n_pairs] = select_rules::pair_records and every table in device
+// memory.  Dist is float or int32_t, the two that kernels_select.hip instantiates.  f == 0: no ratio test; back: the reverse
+// table or null; word [blocks][4] the kept rows as bits and count [blocks] theirs per block, blocks = select_rules::blocks(R);
+// off [blocks + 1] the exclusive sums, off [blocks] = M; the first M entries of matches [.][2], dist [.] and, when xy (pitch
+// ldxy floats) is not null, src, dst [.][2]; moff [n_pairs + 1]
+template <typename Dist>
+void select_flag(const select_rules::Pair *pairs, int64_t n_pairs, int64_t R, const int32_t *idx, const Dist *sqdist, float f, const int32_t *back,
+                 uint64_t *word, int32_t *count, hipStream_t s);
+void select_scan(const int32_t *count, int64_t blocks, int64_t *off, hipStream_t s);
+template <typename Dist>
+void select_scatter(const select_rules::Pair *pairs, int64_t n_pairs, int64_t R, const int32_t *idx, const Dist *sqdist, const uint64_t *word,
+                    const int64_t *off, const float *xy, int64_t ldxy, int32_t *matches, Dist *dist, float *src, float *dst, hipStream_t s);
+void select_offsets(const select_rules::Pair *pairs, int64_t n_pairs, int64_t R, const uint64_t *word, const int64_t *off, int64_t *moff, hipStream_t s);
 
 }  // namespace dlco
