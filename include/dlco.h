@@ -959,7 +959,10 @@ int  dlco_desc_verify_pairs_launches(const int64_t *moff, int64_t n_pairs, int32
  * without xy or only one of the two, ldxy < 2 with xy.
  *   Out of scope: a device-memory form of dlco_desc_verify_pairs_* (its refit runs on the host and needs the list there anyway);
  * seg / pairs in device memory; the tools, which keep their host rule; single-pair entry points: a batch of one pair is the
- * single call. ---- */
+ * single call.
+ *   In scope since: the tools.  match and match-pairs make their lists with the host forms of these calls (cli/match_tool.hpp),
+ * match as a batch of one pair with the reverse answer of its second call as back_idx; no host restatement of the rule is
+ * left in them. ---- */
 int  dlco_desc_select_pairs(dlco_desc_ctx *ctx, const int64_t *seg, int32_t n_img, const int32_t *pairs, int64_t n_pairs,
                             const int32_t *idx_host, const float *sqdist_host, float ratio, const int32_t *back_idx_host,
                             const int64_t *back_row0, int64_t n_back_rows, const float *xy_host, int64_t *moff, int32_t *matches_host,

@@ -7,6 +7,7 @@ This module is plumbing only: every computation happens in the HIP kernels of
 ``libdlco.so`` (sources under ``csrc/``).  There is no CPU fallback — a missing library or
 a missing gfx950 device raises.
 """
+import collections
 import ctypes as C
 import os
 import subprocess
@@ -90,6 +91,10 @@ def build(verbose=False):
 
 _lib = None
 f32p, i32p, u8p, i64p = C.POINTER(C.c_float), C.POINTER(C.c_int32), C.POINTER(C.c_uint8), C.POINTER(C.c_int64)
+f64p = C.POINTER(C.c_double)
+# the matcher's two lines: the tables' element type and pointer, the distances' type and pointer, the suffix of the C names
+_Line = collections.namedtuple("_Line", "dtype ptr dist dptr suffix")
+_FLOAT, _BYTE = _Line(np.float32, f32p, np.float32, f32p, ""), _Line(np.uint8, u8p, np.int32, i32p, "_u8")
 
 
 def load():
@@ -1046,16 +1051,68 @@ class DescContext:
         self._ck(self.L.dlco_desc_pair_stats(self.h, _p(p, u8p), p.shape[0], _p(q, i32p), q.shape[0], C.byref(dim), C.byref(f), C.byref(a)))
         return dim.value, f.value, a.value
 
-    # ---- matching two descriptor tables ----
+    # ---- matching two descriptor tables.  The matcher's call shapes, one helper each: `line` is _FLOAT or _BYTE, `name` the C
+    # function without dlco_desc_ and without the line's suffix; the public methods below forward to them ----
+    def _fn(self, line, name, device=False):
+        return getattr(self.L, "dlco_desc_" + name + line.suffix + ("_device" if device else ""))
+
+    @staticmethod
+    def _tables(line, query, train):
+        q, t = np.ascontiguousarray(query, line.dtype), np.ascontiguousarray(train, line.dtype)
+        assert q.ndim == 2 and t.ndim == 2 and q.shape[1] == t.shape[1]
+        return q, t
+
+    def _top2(self, line, name, query, train):
+        q, t = self._tables(line, query, train)
+        idx, d = np.empty((q.shape[0], 2), np.int32), np.empty((q.shape[0], 2), line.dist)
+        self._ck(self._fn(line, name)(self.h, _p(q, line.ptr), q.shape[0], _p(t, line.ptr), t.shape[0], q.shape[1], _p(idx, i32p), _p(d, line.dptr)))
+        return idx, d
+
+    def _matrix(self, line, name, query, train):
+        q, t = self._tables(line, query, train)
+        out = np.empty((q.shape[0], t.shape[0]), line.dist)
+        self._ck(self._fn(line, name)(self.h, _p(q, line.ptr), q.shape[0], _p(t, line.ptr), t.shape[0], q.shape[1], _p(out, line.dptr)))
+        return out
+
+    def _on_device(self, line, name, q_ptr, nq, t_ptr, nt, r, idx_ptr, d_ptr, ldq, ldt):
+        self._ck(self._fn(line, name, True)(self.h, C.c_void_p(q_ptr), ldq or r, nq, C.c_void_p(t_ptr), ldt or r, nt, r, C.c_void_p(idx_ptr),
+                                            C.c_void_p(d_ptr)))
+
+    def _guided_tables(self, line, query, query_xy, train, train_xy, M):
+        q, t = self._tables(line, query, train)
+        qxy, txy = _f32(query_xy), _f32(train_xy)
+        assert qxy.shape == (q.shape[0], 2) and txy.shape == (t.shape[0], 2)
+        return q, qxy, t, txy, self._model(M)
+
+    @staticmethod
+    def _model(M):
+        m = np.ascontiguousarray(M, np.float64)
+        assert m.size == 9
+        return m
+
+    def _top2_guided(self, line, name, query, query_xy, train, train_xy, M, radius, side):
+        q, qxy, t, txy, m = self._guided_tables(line, query, query_xy, train, train_xy, M)
+        idx, d = np.empty((q.shape[0], 2), np.int32), np.empty((q.shape[0], 2), line.dist)
+        self._ck(self._fn(line, name)(self.h, _p(q, line.ptr), _p(qxy, f32p), q.shape[0], _p(t, line.ptr), _p(txy, f32p), t.shape[0], q.shape[1],
+                                      _p(m, f64p), radius, side, _p(idx, i32p), _p(d, line.dptr)))
+        return idx, d
+
+    def _matrix_guided(self, line, name, query, query_xy, train, train_xy, M, radius, side):
+        q, qxy, t, txy, m = self._guided_tables(line, query, query_xy, train, train_xy, M)
+        out = np.empty((q.shape[0], t.shape[0]), line.dist)
+        self._ck(self._fn(line, name)(self.h, _p(q, line.ptr), _p(qxy, f32p), q.shape[0], _p(t, line.ptr), _p(txy, f32p), t.shape[0], q.shape[1],
+                                      _p(m, f64p), radius, side, _p(out, line.dptr)))
+        return out
+
+    def _on_device_guided(self, line, name, q_ptr, qxy_ptr, nq, t_ptr, txy_ptr, nt, r, M, idx_ptr, d_ptr, radius, side, ldq, ldt, ldxy_q, ldxy_t):
+        self._ck(self._fn(line, name, True)(self.h, C.c_void_p(q_ptr), ldq or r, C.c_void_p(qxy_ptr), ldxy_q, nq, C.c_void_p(t_ptr), ldt or r,
+                                            C.c_void_p(txy_ptr), ldxy_t, nt, r, _p(self._model(M), f64p), radius, side, C.c_void_p(idx_ptr),
+                                            C.c_void_p(d_ptr)))
+
     def match(self, query, train):
         """For every row of query [nq, r] the nearest and second-nearest row of train [nt, r]: (idx [nq,2] int32,
         sqdist [nq,2] float32), ordered by (distance, index); nt == 1 gives -1 / +inf in column 1."""
-        q, t = _f32(query), _f32(train)
-        assert q.ndim == 2 and t.ndim == 2 and q.shape[1] == t.shape[1]
-        idx = np.empty((q.shape[0], 2), np.int32)
-        d = np.empty((q.shape[0], 2), np.float32)
-        self._ck(self.L.dlco_desc_match(self.h, _p(q, f32p), q.shape[0], _p(t, f32p), t.shape[0], q.shape[1], _p(idx, i32p), _p(d, f32p)))
-        return idx, d
+        return self._top2(_FLOAT, "match", query, train)
 
     # ---- verifying a match list against a homography (csrc/verify_rules.hpp states the rule) ----
     @staticmethod
@@ -1154,57 +1211,30 @@ class DescContext:
 
     def match_device(self, q_ptr, nq, t_ptr, nt, r, idx_ptr, d_ptr, ldq=None, ldt=None):
         """match on tables in device memory (row pitches ldq, ldt: multiples of 4, default r); results to device memory."""
-        self._ck(self.L.dlco_desc_match_device(self.h, C.c_void_p(q_ptr), ldq or r, nq, C.c_void_p(t_ptr), ldt or r, nt, r,
-                                               C.c_void_p(idx_ptr), C.c_void_p(d_ptr)))
+        self._on_device(_FLOAT, "match", q_ptr, nq, t_ptr, nt, r, idx_ptr, d_ptr, ldq, ldt)
 
     def cross_sqdists(self, query, train):
         """The whole matrix [nq, nt] float32 of the distances match orders (nq * nt <= 2^28)."""
-        q, t = _f32(query), _f32(train)
-        assert q.ndim == 2 and t.ndim == 2 and q.shape[1] == t.shape[1]
-        out = np.empty((q.shape[0], t.shape[0]), np.float32)
-        self._ck(self.L.dlco_desc_cross_sqdists(self.h, _p(q, f32p), q.shape[0], _p(t, f32p), t.shape[0], q.shape[1], _p(out, f32p)))
-        return out
+        return self._matrix(_FLOAT, "cross_sqdists", query, train)
 
     # ---- guided matching: the nearest two among the rows a homography admits (csrc/guided_rules.hpp states the rule) ----
-    @staticmethod
-    def _guided_tables(query, query_xy, train, train_xy, H):
-        q, t, qxy, txy = _f32(query), _f32(train), _f32(query_xy), _f32(train_xy)
-        assert q.ndim == 2 and t.ndim == 2 and q.shape[1] == t.shape[1]
-        assert qxy.shape == (q.shape[0], 2) and txy.shape == (t.shape[0], 2)
-        h = np.ascontiguousarray(H, np.float64)
-        assert h.size == 9
-        return q, qxy, t, txy, h
-
     def match_guided(self, query, query_xy, train, train_xy, H, radius=6.0, h_side=0):
         """match among the rows of train the homography H [3,3] admits for a query: those whose keypoint train_xy [nt,2] lies
         within radius pixels of H applied to the query's query_xy [nq,2] (h_side=0: H maps the query image to the train
         image; h_side=1: H maps the train image to the query image, the call of a mutual check with the tables swapped).
         (idx [nq,2] int32, sqdist [nq,2] float32); fewer than two admitted rows leave -1 / +inf."""
-        q, qxy, t, txy, h = self._guided_tables(query, query_xy, train, train_xy, H)
-        idx = np.empty((q.shape[0], 2), np.int32)
-        d = np.empty((q.shape[0], 2), np.float32)
-        self._ck(self.L.dlco_desc_match_guided(self.h, _p(q, f32p), _p(qxy, f32p), q.shape[0], _p(t, f32p), _p(txy, f32p), t.shape[0],
-                                               q.shape[1], _p(h, C.POINTER(C.c_double)), radius, h_side, _p(idx, i32p), _p(d, f32p)))
-        return idx, d
+        return self._top2_guided(_FLOAT, "match_guided", query, query_xy, train, train_xy, H, radius, h_side)
 
     def match_guided_device(self, q_ptr, qxy_ptr, nq, t_ptr, txy_ptr, nt, r, H, idx_ptr, d_ptr, radius=6.0, h_side=0, ldq=None,
                             ldt=None, ldxy_q=2, ldxy_t=2):
         """match_guided on tables in device memory (row pitches ldq, ldt: multiples of 4, default r; coordinate pitches in
         floats, >= 2: 4 takes the keypoint rows detect_device wrote); results to device memory."""
-        h = np.ascontiguousarray(H, np.float64)
-        assert h.size == 9
-        self._ck(self.L.dlco_desc_match_guided_device(self.h, C.c_void_p(q_ptr), ldq or r, C.c_void_p(qxy_ptr), ldxy_q, nq,
-                                                      C.c_void_p(t_ptr), ldt or r, C.c_void_p(txy_ptr), ldxy_t, nt, r,
-                                                      _p(h, C.POINTER(C.c_double)), radius, h_side, C.c_void_p(idx_ptr), C.c_void_p(d_ptr)))
+        self._on_device_guided(_FLOAT, "match_guided", q_ptr, qxy_ptr, nq, t_ptr, txy_ptr, nt, r, H, idx_ptr, d_ptr, radius, h_side, ldq, ldt,
+                               ldxy_q, ldxy_t)
 
     def cross_sqdists_guided(self, query, query_xy, train, train_xy, H, radius=6.0, h_side=0):
         """cross_sqdists with +inf where H does not admit the pair: match_guided is the top two of its finite entries."""
-        q, qxy, t, txy, h = self._guided_tables(query, query_xy, train, train_xy, H)
-        out = np.empty((q.shape[0], t.shape[0]), np.float32)
-        self._ck(self.L.dlco_desc_cross_sqdists_guided(self.h, _p(q, f32p), _p(qxy, f32p), q.shape[0], _p(t, f32p), _p(txy, f32p),
-                                                       t.shape[0], q.shape[1], _p(h, C.POINTER(C.c_double)), radius, h_side,
-                                                       _p(out, f32p)))
-        return out
+        return self._matrix_guided(_FLOAT, "cross_sqdists_guided", query, query_xy, train, train_xy, H, radius, h_side)
 
     # ---- guided matching under a fundamental matrix (csrc/guided_epipolar_rules.hpp states the rule) ----
     def match_guided_epipolar(self, query, query_xy, train, train_xy, F, threshold=3.0, f_side=0):
@@ -1213,32 +1243,17 @@ class DescContext:
         is src, F as verify_fundamental(query keypoints, train keypoints) returns it; f_side=1: the train image is src, the
         call of a mutual check with the tables swapped).  (idx [nq,2] int32, sqdist [nq,2] float32); fewer than two admitted
         rows leave -1 / +inf."""
-        q, qxy, t, txy, f = self._guided_tables(query, query_xy, train, train_xy, F)
-        idx = np.empty((q.shape[0], 2), np.int32)
-        d = np.empty((q.shape[0], 2), np.float32)
-        self._ck(self.L.dlco_desc_match_guided_epipolar(self.h, _p(q, f32p), _p(qxy, f32p), q.shape[0], _p(t, f32p), _p(txy, f32p),
-                                                        t.shape[0], q.shape[1], _p(f, C.POINTER(C.c_double)), threshold, f_side,
-                                                        _p(idx, i32p), _p(d, f32p)))
-        return idx, d
+        return self._top2_guided(_FLOAT, "match_guided_epipolar", query, query_xy, train, train_xy, F, threshold, f_side)
 
     def match_guided_epipolar_device(self, q_ptr, qxy_ptr, nq, t_ptr, txy_ptr, nt, r, F, idx_ptr, d_ptr, threshold=3.0, f_side=0,
                                      ldq=None, ldt=None, ldxy_q=2, ldxy_t=2):
         """match_guided_epipolar on tables in device memory, pitches as match_guided_device; results to device memory."""
-        f = np.ascontiguousarray(F, np.float64)
-        assert f.size == 9
-        self._ck(self.L.dlco_desc_match_guided_epipolar_device(self.h, C.c_void_p(q_ptr), ldq or r, C.c_void_p(qxy_ptr), ldxy_q, nq,
-                                                               C.c_void_p(t_ptr), ldt or r, C.c_void_p(txy_ptr), ldxy_t, nt, r,
-                                                               _p(f, C.POINTER(C.c_double)), threshold, f_side, C.c_void_p(idx_ptr),
-                                                               C.c_void_p(d_ptr)))
+        self._on_device_guided(_FLOAT, "match_guided_epipolar", q_ptr, qxy_ptr, nq, t_ptr, txy_ptr, nt, r, F, idx_ptr, d_ptr, threshold, f_side,
+                               ldq, ldt, ldxy_q, ldxy_t)
 
     def cross_sqdists_guided_epipolar(self, query, query_xy, train, train_xy, F, threshold=3.0, f_side=0):
         """cross_sqdists with +inf where F does not admit the pair: match_guided_epipolar is the top two of its finite entries."""
-        q, qxy, t, txy, f = self._guided_tables(query, query_xy, train, train_xy, F)
-        out = np.empty((q.shape[0], t.shape[0]), np.float32)
-        self._ck(self.L.dlco_desc_cross_sqdists_guided_epipolar(self.h, _p(q, f32p), _p(qxy, f32p), q.shape[0], _p(t, f32p),
-                                                                _p(txy, f32p), t.shape[0], q.shape[1], _p(f, C.POINTER(C.c_double)),
-                                                                threshold, f_side, _p(out, f32p)))
-        return out
+        return self._matrix_guided(_FLOAT, "cross_sqdists_guided_epipolar", query, query_xy, train, train_xy, F, threshold, f_side)
 
     # ---- eight-bit descriptors: rows quantised on the device, byte tables matched with exact integer distances ----
     def set_quantizer(self, scale, offset=None, r=None):
@@ -1278,141 +1293,99 @@ class DescContext:
     def match_u8(self, query, train):
         """match on byte tables [nq, r] / [nt, r] uint8: (idx [nq,2] int32, sqdist [nq,2] int32), exact integer distances
         ordered by (distance, index); nt == 1 gives -1 / INT32_MAX in column 1."""
-        q, t = np.ascontiguousarray(query, np.uint8), np.ascontiguousarray(train, np.uint8)
-        assert q.ndim == 2 and t.ndim == 2 and q.shape[1] == t.shape[1]
-        idx = np.empty((q.shape[0], 2), np.int32)
-        d = np.empty((q.shape[0], 2), np.int32)
-        self._ck(self.L.dlco_desc_match_u8(self.h, _p(q, u8p), q.shape[0], _p(t, u8p), t.shape[0], q.shape[1], _p(idx, i32p), _p(d, i32p)))
-        return idx, d
+        return self._top2(_BYTE, "match", query, train)
 
     def match_u8_device(self, q_ptr, nq, t_ptr, nt, r, idx_ptr, d_ptr, ldq=None, ldt=None):
         """match_u8 on tables in device memory (row pitches ldq, ldt in bytes: multiples of 16); results to device memory."""
-        self._ck(self.L.dlco_desc_match_u8_device(self.h, C.c_void_p(q_ptr), ldq or r, nq, C.c_void_p(t_ptr), ldt or r, nt, r,
-                                                  C.c_void_p(idx_ptr), C.c_void_p(d_ptr)))
+        self._on_device(_BYTE, "match", q_ptr, nq, t_ptr, nt, r, idx_ptr, d_ptr, ldq, ldt)
 
     def cross_sqdists_u8(self, query, train):
         """The whole matrix [nq, nt] int32 of the distances match_u8 orders (nq * nt <= 2^28)."""
-        q, t = np.ascontiguousarray(query, np.uint8), np.ascontiguousarray(train, np.uint8)
-        assert q.ndim == 2 and t.ndim == 2 and q.shape[1] == t.shape[1]
-        out = np.empty((q.shape[0], t.shape[0]), np.int32)
-        self._ck(self.L.dlco_desc_cross_sqdists_u8(self.h, _p(q, u8p), q.shape[0], _p(t, u8p), t.shape[0], q.shape[1], _p(out, i32p)))
-        return out
+        return self._matrix(_BYTE, "cross_sqdists", query, train)
 
     # ---- guided matching on byte tables: the float guided calls argument for argument, integer distances ----
-    @staticmethod
-    def _guided_tables_u8(query, query_xy, train, train_xy, M):
-        q, t = np.ascontiguousarray(query, np.uint8), np.ascontiguousarray(train, np.uint8)
-        qxy, txy = _f32(query_xy), _f32(train_xy)
-        assert q.ndim == 2 and t.ndim == 2 and q.shape[1] == t.shape[1]
-        assert qxy.shape == (q.shape[0], 2) and txy.shape == (t.shape[0], 2)
-        m = np.ascontiguousarray(M, np.float64)
-        assert m.size == 9
-        return q, qxy, t, txy, m
-
-    def _match_guided_u8(self, call, query, query_xy, train, train_xy, M, radius, side):
-        q, qxy, t, txy, m = self._guided_tables_u8(query, query_xy, train, train_xy, M)
-        idx = np.empty((q.shape[0], 2), np.int32)
-        d = np.empty((q.shape[0], 2), np.int32)
-        self._ck(call(self.h, _p(q, u8p), _p(qxy, f32p), q.shape[0], _p(t, u8p), _p(txy, f32p), t.shape[0], q.shape[1],
-                      _p(m, C.POINTER(C.c_double)), radius, side, _p(idx, i32p), _p(d, i32p)))
-        return idx, d
-
-    def _cross_guided_u8(self, call, query, query_xy, train, train_xy, M, radius, side):
-        q, qxy, t, txy, m = self._guided_tables_u8(query, query_xy, train, train_xy, M)
-        out = np.empty((q.shape[0], t.shape[0]), np.int32)
-        self._ck(call(self.h, _p(q, u8p), _p(qxy, f32p), q.shape[0], _p(t, u8p), _p(txy, f32p), t.shape[0], q.shape[1],
-                      _p(m, C.POINTER(C.c_double)), radius, side, _p(out, i32p)))
-        return out
-
-    def _match_guided_u8_device(self, call, q_ptr, qxy_ptr, nq, t_ptr, txy_ptr, nt, r, M, idx_ptr, d_ptr, radius, side, ldq, ldt, ldxy_q,
-                                ldxy_t):
-        m = np.ascontiguousarray(M, np.float64)
-        assert m.size == 9
-        self._ck(call(self.h, C.c_void_p(q_ptr), ldq or r, C.c_void_p(qxy_ptr), ldxy_q, nq, C.c_void_p(t_ptr), ldt or r, C.c_void_p(txy_ptr),
-                      ldxy_t, nt, r, _p(m, C.POINTER(C.c_double)), radius, side, C.c_void_p(idx_ptr), C.c_void_p(d_ptr)))
-
     def match_guided_u8(self, query, query_xy, train, train_xy, H, radius=6.0, h_side=0):
         """match_guided on byte tables [n, r] uint8: the first two rows of match_u8's (d, index) order among those the homography
         admits.  (idx [nq,2] int32, sqdist [nq,2] int32); fewer than two admitted rows leave -1 / INT32_MAX."""
-        return self._match_guided_u8(self.L.dlco_desc_match_guided_u8, query, query_xy, train, train_xy, H, radius, h_side)
+        return self._top2_guided(_BYTE, "match_guided", query, query_xy, train, train_xy, H, radius, h_side)
 
     def match_guided_u8_device(self, q_ptr, qxy_ptr, nq, t_ptr, txy_ptr, nt, r, H, idx_ptr, d_ptr, radius=6.0, h_side=0, ldq=None,
                                ldt=None, ldxy_q=2, ldxy_t=2):
         """match_guided_u8 on tables in device memory (row pitches ldq, ldt in bytes: multiples of 16; coordinate pitches in
         floats, >= 2); results to device memory."""
-        self._match_guided_u8_device(self.L.dlco_desc_match_guided_u8_device, q_ptr, qxy_ptr, nq, t_ptr, txy_ptr, nt, r, H, idx_ptr, d_ptr,
-                                     radius, h_side, ldq, ldt, ldxy_q, ldxy_t)
+        self._on_device_guided(_BYTE, "match_guided", q_ptr, qxy_ptr, nq, t_ptr, txy_ptr, nt, r, H, idx_ptr, d_ptr, radius, h_side, ldq, ldt,
+                               ldxy_q, ldxy_t)
 
     def cross_sqdists_guided_u8(self, query, query_xy, train, train_xy, H, radius=6.0, h_side=0):
         """cross_sqdists_u8 with INT32_MAX where H does not admit the pair: match_guided_u8 is the top two of the entries below it."""
-        return self._cross_guided_u8(self.L.dlco_desc_cross_sqdists_guided_u8, query, query_xy, train, train_xy, H, radius, h_side)
+        return self._matrix_guided(_BYTE, "cross_sqdists_guided", query, query_xy, train, train_xy, H, radius, h_side)
 
     def match_guided_epipolar_u8(self, query, query_xy, train, train_xy, F, threshold=3.0, f_side=0):
         """match_guided_epipolar on byte tables: (idx [nq,2] int32, sqdist [nq,2] int32), -1 / INT32_MAX in free columns."""
-        return self._match_guided_u8(self.L.dlco_desc_match_guided_epipolar_u8, query, query_xy, train, train_xy, F, threshold, f_side)
+        return self._top2_guided(_BYTE, "match_guided_epipolar", query, query_xy, train, train_xy, F, threshold, f_side)
 
     def match_guided_epipolar_u8_device(self, q_ptr, qxy_ptr, nq, t_ptr, txy_ptr, nt, r, F, idx_ptr, d_ptr, threshold=3.0, f_side=0,
                                         ldq=None, ldt=None, ldxy_q=2, ldxy_t=2):
         """match_guided_epipolar_u8 on tables in device memory, pitches as match_guided_u8_device."""
-        self._match_guided_u8_device(self.L.dlco_desc_match_guided_epipolar_u8_device, q_ptr, qxy_ptr, nq, t_ptr, txy_ptr, nt, r, F, idx_ptr,
-                                     d_ptr, threshold, f_side, ldq, ldt, ldxy_q, ldxy_t)
+        self._on_device_guided(_BYTE, "match_guided_epipolar", q_ptr, qxy_ptr, nq, t_ptr, txy_ptr, nt, r, F, idx_ptr, d_ptr, threshold, f_side,
+                               ldq, ldt, ldxy_q, ldxy_t)
 
     def cross_sqdists_guided_epipolar_u8(self, query, query_xy, train, train_xy, F, threshold=3.0, f_side=0):
         """cross_sqdists_u8 with INT32_MAX where F does not admit the pair."""
-        return self._cross_guided_u8(self.L.dlco_desc_cross_sqdists_guided_epipolar_u8, query, query_xy, train, train_xy, F, threshold,
-                                     f_side)
+        return self._matrix_guided(_BYTE, "cross_sqdists_guided_epipolar", query, query_xy, train, train_xy, F, threshold, f_side)
 
     # ---- matching many pairs of images in one call (csrc/match_batch.hpp states the plan) ----
-    def _match_pairs(self, call, tables, pairs, dtype, ptr, dist):
-        tabs = [np.ascontiguousarray(t, dtype) for t in tables]
+    @staticmethod
+    def _batch(line, tables, pairs):
+        """the images as one table: (table, seg, pairs, row0) as the match_pairs calls take them"""
+        tabs = [np.ascontiguousarray(t, line.dtype) for t in tables]
         assert tabs and all(t.ndim == 2 and t.shape[1] == tabs[0].shape[1] for t in tabs)
         seg = np.concatenate([[0], np.cumsum([t.shape[0] for t in tabs])]).astype(np.int64)
         seg, q = _seg_pairs(seg, pairs)
-        table = np.ascontiguousarray(np.concatenate(tabs, axis=0))
-        row0 = match_pairs_rows(seg, q)
-        idx, d = np.empty((row0[-1], 2), np.int32), np.empty((row0[-1], 2), dist)
-        self._ck(call(self.h, _p(table, ptr), _p(seg, i64p), seg.size - 1, _p(q, i32p), q.shape[0], table.shape[1], _p(idx, i32p),
-                      _p(d, C.POINTER(C.c_float if dist == np.float32 else C.c_int32))))
+        return np.ascontiguousarray(np.concatenate(tabs, axis=0)), seg, q, match_pairs_rows(seg, q)
+
+    def _match_pairs(self, line, name, tables, pairs):
+        table, seg, q, row0 = self._batch(line, tables, pairs)
+        idx, d = np.empty((row0[-1], 2), np.int32), np.empty((row0[-1], 2), line.dist)
+        self._ck(self._fn(line, name)(self.h, _p(table, line.ptr), _p(seg, i64p), seg.size - 1, _p(q, i32p), q.shape[0], table.shape[1],
+                                      _p(idx, i32p), _p(d, line.dptr)))
         return [(idx[row0[p]:row0[p + 1]], d[row0[p]:row0[p + 1]]) for p in range(q.shape[0])]
+
+    def _match_pairs_device(self, line, name, table_ptr, seg, pairs, r, idx_ptr, d_ptr, ld):
+        s, q = _seg_pairs(seg, pairs)
+        self._ck(self._fn(line, name, True)(self.h, C.c_void_p(table_ptr), ld or r, _p(s, i64p), s.size - 1, _p(q, i32p), q.shape[0], r,
+                                            C.c_void_p(idx_ptr), C.c_void_p(d_ptr)))
 
     def match_pairs(self, tables, pairs):
         """Many pairs of images in one call: tables is a list of [n_s, r] arrays (an image may have no rows), pairs [n_pairs, 2]
         of (query image, train image).  Returns a list of (idx [n_a, 2] int32, sqdist [n_a, 2] float32), one per pair, each
         byte for byte what match(tables[a], tables[b]) returns; an empty train image gives -1 / +inf in both columns."""
-        return self._match_pairs(self.L.dlco_desc_match_pairs, tables, pairs, np.float32, f32p, np.float32)
+        return self._match_pairs(_FLOAT, "match_pairs", tables, pairs)
 
     def match_pairs_u8(self, tables, pairs):
         """match_pairs on byte tables: every pair is what match_u8 returns for it; an empty train image gives -1 / INT32_MAX."""
-        return self._match_pairs(self.L.dlco_desc_match_pairs_u8, tables, pairs, np.uint8, u8p, np.int32)
+        return self._match_pairs(_BYTE, "match_pairs", tables, pairs)
 
     def match_pairs_device(self, table_ptr, seg, pairs, r, idx_ptr, d_ptr, ld=None):
         """match_pairs on one table in device memory (row pitch ld floats, a multiple of 4, default r) whose segments seg
         [n_img + 1] are the images; results [match_pairs_rows(seg, pairs)[-1], 2] to device memory."""
-        s, q = _seg_pairs(seg, pairs)
-        self._ck(self.L.dlco_desc_match_pairs_device(self.h, C.c_void_p(table_ptr), ld or r, _p(s, i64p), s.size - 1, _p(q, i32p), q.shape[0], r,
-                                                     C.c_void_p(idx_ptr), C.c_void_p(d_ptr)))
+        self._match_pairs_device(_FLOAT, "match_pairs", table_ptr, seg, pairs, r, idx_ptr, d_ptr, ld)
 
     def match_pairs_u8_device(self, table_ptr, seg, pairs, r, idx_ptr, d_ptr, ld=None):
         """match_pairs_u8 on one table in device memory (row pitch ld bytes, a multiple of 16)."""
-        s, q = _seg_pairs(seg, pairs)
-        self._ck(self.L.dlco_desc_match_pairs_u8_device(self.h, C.c_void_p(table_ptr), ld or r, _p(s, i64p), s.size - 1, _p(q, i32p), q.shape[0],
-                                                        r, C.c_void_p(idx_ptr), C.c_void_p(d_ptr)))
+        self._match_pairs_device(_BYTE, "match_pairs", table_ptr, seg, pairs, r, idx_ptr, d_ptr, ld)
 
     # ---- guided matching of many pairs in one call: a matrix per pair (csrc/match_batch.hpp states the plan) ----
-    def _match_pairs_guided(self, call, tables, xys, pairs, M, radius, side, dtype=np.float32, ptr=f32p, dist=np.float32):
-        tabs, cs = [np.ascontiguousarray(t, dtype) for t in tables], [_f32(x) for x in xys]
-        assert tabs and len(cs) == len(tabs) and all(t.ndim == 2 and t.shape[1] == tabs[0].shape[1] for t in tabs)
-        assert all(x.shape == (t.shape[0], 2) for x, t in zip(cs, tabs))
-        seg = np.concatenate([[0], np.cumsum([t.shape[0] for t in tabs])]).astype(np.int64)
-        seg, q = _seg_pairs(seg, pairs)
+    def _match_pairs_guided(self, line, name, tables, xys, pairs, M, radius, side):
+        table, seg, q, row0 = self._batch(line, tables, pairs)
+        cs = [_f32(x) for x in xys]
+        assert len(cs) == seg.size - 1 and all(x.shape == (n, 2) for x, n in zip(cs, np.diff(seg)))
         m = np.ascontiguousarray(M, np.float64).reshape(-1, 9)
         assert m.shape[0] == q.shape[0]
-        table, xy = np.ascontiguousarray(np.concatenate(tabs, axis=0)), np.ascontiguousarray(np.concatenate(cs, axis=0))
-        row0 = match_pairs_rows(seg, q)
-        idx, d = np.empty((row0[-1], 2), np.int32), np.empty((row0[-1], 2), dist)
-        self._ck(call(self.h, _p(table, ptr), _p(xy, f32p), _p(seg, i64p), seg.size - 1, _p(q, i32p), q.shape[0], table.shape[1],
-                      _p(m, C.POINTER(C.c_double)), radius, side, _p(idx, i32p),
-                      _p(d, C.POINTER(C.c_float if dist == np.float32 else C.c_int32))))
+        xy = np.ascontiguousarray(np.concatenate(cs, axis=0))
+        idx, d = np.empty((row0[-1], 2), np.int32), np.empty((row0[-1], 2), line.dist)
+        self._ck(self._fn(line, name)(self.h, _p(table, line.ptr), _p(xy, f32p), _p(seg, i64p), seg.size - 1, _p(q, i32p), q.shape[0],
+                                      table.shape[1], _p(m, f64p), radius, side, _p(idx, i32p), _p(d, line.dptr)))
         return [(idx[row0[p]:row0[p + 1]], d[row0[p]:row0[p + 1]]) for p in range(q.shape[0])]
 
     def match_pairs_guided(self, tables, xys, pairs, H, radius=6.0, h_side=0):
@@ -1420,52 +1393,49 @@ class DescContext:
         coordinates, one per table, H [n_pairs, 3, 3] (or [n_pairs, 9]) as verify_pairs_homography returns it.  Returns a list of
         (idx, sqdist), one per pair, each byte for byte what match_guided(tables[a], xys[a], tables[b], xys[b], H[p], radius,
         h_side) returns; an all-zero H[p] ("no model") or an empty train image gives -1 / +inf in both columns."""
-        return self._match_pairs_guided(self.L.dlco_desc_match_pairs_guided, tables, xys, pairs, H, radius, h_side)
+        return self._match_pairs_guided(_FLOAT, "match_pairs_guided", tables, xys, pairs, H, radius, h_side)
 
     def match_pairs_guided_epipolar(self, tables, xys, pairs, F, threshold=3.0, f_side=0):
         """match_pairs under a fundamental matrix per pair: every pair is what match_guided_epipolar returns for it."""
-        return self._match_pairs_guided(self.L.dlco_desc_match_pairs_guided_epipolar, tables, xys, pairs, F, threshold, f_side)
+        return self._match_pairs_guided(_FLOAT, "match_pairs_guided_epipolar", tables, xys, pairs, F, threshold, f_side)
 
-    def _match_pairs_guided_device(self, call, table_ptr, xy_ptr, seg, pairs, r, M, idx_ptr, d_ptr, radius, side, ld, ldxy):
+    def _match_pairs_guided_device(self, line, name, table_ptr, xy_ptr, seg, pairs, r, M, idx_ptr, d_ptr, radius, side, ld, ldxy):
         s, q = _seg_pairs(seg, pairs)
         m = np.ascontiguousarray(M, np.float64).reshape(-1, 9)
         assert m.shape[0] == q.shape[0]
-        self._ck(call(self.h, C.c_void_p(table_ptr), ld or r, C.c_void_p(xy_ptr), ldxy, _p(s, i64p), s.size - 1, _p(q, i32p), q.shape[0], r,
-                      _p(m, C.POINTER(C.c_double)), radius, side, C.c_void_p(idx_ptr), C.c_void_p(d_ptr)))
+        self._ck(self._fn(line, name, True)(self.h, C.c_void_p(table_ptr), ld or r, C.c_void_p(xy_ptr), ldxy, _p(s, i64p), s.size - 1, _p(q, i32p),
+                                            q.shape[0], r, _p(m, f64p), radius, side, C.c_void_p(idx_ptr), C.c_void_p(d_ptr)))
 
     def match_pairs_guided_device(self, table_ptr, xy_ptr, seg, pairs, r, H, idx_ptr, d_ptr, radius=6.0, h_side=0, ld=None, ldxy=2):
         """match_pairs_guided on one table in device memory (row pitch ld floats, default r) and one coordinate table with the
         same rows (pitch ldxy floats >= 2: 4 takes the keypoint rows detect_device wrote); H on the host; results
         [match_pairs_rows(seg, pairs)[-1], 2] to device memory."""
-        self._match_pairs_guided_device(self.L.dlco_desc_match_pairs_guided_device, table_ptr, xy_ptr, seg, pairs, r, H, idx_ptr, d_ptr, radius,
-                                        h_side, ld, ldxy)
+        self._match_pairs_guided_device(_FLOAT, "match_pairs_guided", table_ptr, xy_ptr, seg, pairs, r, H, idx_ptr, d_ptr, radius, h_side, ld, ldxy)
 
     def match_pairs_guided_epipolar_device(self, table_ptr, xy_ptr, seg, pairs, r, F, idx_ptr, d_ptr, threshold=3.0, f_side=0, ld=None, ldxy=2):
         """match_pairs_guided_epipolar on tables in device memory, pitches as match_pairs_guided_device."""
-        self._match_pairs_guided_device(self.L.dlco_desc_match_pairs_guided_epipolar_device, table_ptr, xy_ptr, seg, pairs, r, F, idx_ptr, d_ptr,
-                                        threshold, f_side, ld, ldxy)
+        self._match_pairs_guided_device(_FLOAT, "match_pairs_guided_epipolar", table_ptr, xy_ptr, seg, pairs, r, F, idx_ptr, d_ptr, threshold, f_side,
+                                        ld, ldxy)
 
     def match_pairs_guided_u8(self, tables, xys, pairs, H, radius=6.0, h_side=0):
         """match_pairs_guided on byte tables: every pair is byte for byte what match_guided_u8 returns for it with H[p]; an
         all-zero H[p] or an empty train image gives -1 / INT32_MAX in both columns."""
-        return self._match_pairs_guided(self.L.dlco_desc_match_pairs_guided_u8, tables, xys, pairs, H, radius, h_side, np.uint8, u8p, np.int32)
+        return self._match_pairs_guided(_BYTE, "match_pairs_guided", tables, xys, pairs, H, radius, h_side)
 
     def match_pairs_guided_epipolar_u8(self, tables, xys, pairs, F, threshold=3.0, f_side=0):
         """match_pairs_guided_epipolar on byte tables: every pair is what match_guided_epipolar_u8 returns for it."""
-        return self._match_pairs_guided(self.L.dlco_desc_match_pairs_guided_epipolar_u8, tables, xys, pairs, F, threshold, f_side, np.uint8,
-                                        u8p, np.int32)
+        return self._match_pairs_guided(_BYTE, "match_pairs_guided_epipolar", tables, xys, pairs, F, threshold, f_side)
 
     def match_pairs_guided_u8_device(self, table_ptr, xy_ptr, seg, pairs, r, H, idx_ptr, d_ptr, radius=6.0, h_side=0, ld=None, ldxy=2):
         """match_pairs_guided_u8 on one table in device memory (row pitch ld bytes, a multiple of 16) and one coordinate table
         (pitch ldxy floats >= 2); H on the host; results to device memory."""
-        self._match_pairs_guided_device(self.L.dlco_desc_match_pairs_guided_u8_device, table_ptr, xy_ptr, seg, pairs, r, H, idx_ptr, d_ptr,
-                                        radius, h_side, ld, ldxy)
+        self._match_pairs_guided_device(_BYTE, "match_pairs_guided", table_ptr, xy_ptr, seg, pairs, r, H, idx_ptr, d_ptr, radius, h_side, ld, ldxy)
 
     def match_pairs_guided_epipolar_u8_device(self, table_ptr, xy_ptr, seg, pairs, r, F, idx_ptr, d_ptr, threshold=3.0, f_side=0, ld=None,
                                               ldxy=2):
         """match_pairs_guided_epipolar_u8 on tables in device memory, pitches as match_pairs_guided_u8_device."""
-        self._match_pairs_guided_device(self.L.dlco_desc_match_pairs_guided_epipolar_u8_device, table_ptr, xy_ptr, seg, pairs, r, F, idx_ptr,
-                                        d_ptr, threshold, f_side, ld, ldxy)
+        self._match_pairs_guided_device(_BYTE, "match_pairs_guided_epipolar", table_ptr, xy_ptr, seg, pairs, r, F, idx_ptr, d_ptr, threshold, f_side,
+                                        ld, ldxy)
 
     # ---- selecting matches: from the answer of match_pairs to the lists of verify_pairs (csrc/select_rules.hpp states the rule) ----
     @staticmethod
@@ -1481,11 +1451,11 @@ class DescContext:
         assert s.size >= 2 and s[0] == 0 and fits(np.diff(s)), "select_pairs: neither the row counts nor seg of these answers"
         return s
 
-    def _select_pairs(self, call, answers, sizes_or_seg, pairs, ratio, back, xys, dist):
+    def _select_pairs(self, line, answers, sizes_or_seg, pairs, ratio, back, xys):
         q = np.ascontiguousarray(pairs, np.int32)
         assert q.ndim == 2 and q.shape[1] == 2
         seg = self._select_seg(answers, sizes_or_seg, q)
-        P, dp = q.shape[0], C.POINTER(C.c_float if dist == np.float32 else C.c_int32)
+        P, dist, dp = q.shape[0], line.dist, line.dptr
         stack = lambda ans, k, t: np.ascontiguousarray(np.concatenate([np.reshape(np.asarray(a[k], t), (-1, 2)) for a in ans] + [np.zeros((1, 2), t)]))
         idx, d = stack(answers, 0, np.int32), stack(answers, 1, dist)       # a row of padding: an empty answer still has an address
         row0 = match_pairs_rows(seg, q)
@@ -1507,8 +1477,9 @@ class DescContext:
             xy = np.ascontiguousarray(np.concatenate([_f32(x).reshape(-1, 2) for x in xys] + [np.zeros((1, 2), np.float32)]))
             src, dst = np.empty((R + 1, 2), np.float32), np.empty((R + 1, 2), np.float32)
         moff, m, dd = np.empty(P + 1, np.int64), np.empty((R + 1, 2), np.int32), np.empty(R + 1, dist)
-        self._ck(call(self.h, _p(seg, i64p), seg.size - 1, _p(q, i32p), P, _p(idx, i32p), _p(d, dp), 0.0 if ratio is None else ratio,
-                      _p(bidx, i32p), _p(brow0, i64p), nback, _p(xy, f32p), _p(moff, i64p), _p(m, i32p), _p(dd, dp), _p(src, f32p), _p(dst, f32p)))
+        self._ck(self._fn(line, "select_pairs")(self.h, _p(seg, i64p), seg.size - 1, _p(q, i32p), P, _p(idx, i32p), _p(d, dp), 0.0 if ratio is None else ratio,
+                                                _p(bidx, i32p), _p(brow0, i64p), nback, _p(xy, f32p), _p(moff, i64p), _p(m, i32p), _p(dd, dp), _p(src, f32p),
+                                                _p(dst, f32p)))
         sel = [(m[moff[p]:moff[p + 1]], dd[moff[p]:moff[p + 1]]) for p in range(P)]
         if xys is None:
             return sel
@@ -1522,22 +1493,22 @@ class DescContext:
         or a second answer list, back[p] the answer of (b, a) (None: no check for p).  Returns per pair (matches [m, 2] int32 of
         (query row, train row), dist [m] float32), rows ascending.  With xys, the list of [n_s, 2] keypoint coordinates of the
         images, returns (that list, lists), lists the per-pair (src [m, 2], dst [m, 2]) that verify_pairs_* take."""
-        return self._select_pairs(self.L.dlco_desc_select_pairs, answers, sizes_or_seg, pairs, ratio, back, xys, np.float32)
+        return self._select_pairs(_FLOAT, answers, sizes_or_seg, pairs, ratio, back, xys)
 
     def select_pairs_u8(self, answers, sizes_or_seg, pairs, ratio=None, back=None, xys=None):
         """select_pairs on the answers of the byte line (match_pairs_u8, match_pairs_guided*_u8): dist [m] int32."""
-        return self._select_pairs(self.L.dlco_desc_select_pairs_u8, answers, sizes_or_seg, pairs, ratio, back, xys, np.int32)
+        return self._select_pairs(_BYTE, answers, sizes_or_seg, pairs, ratio, back, xys)
 
-    def _select_pairs_device(self, call, idx_ptr, d_ptr, seg, pairs, matches_ptr, dist_ptr, ratio, back_idx_ptr, back_row0, n_back_rows, xy_ptr, ldxy,
+    def _select_pairs_device(self, line, idx_ptr, d_ptr, seg, pairs, matches_ptr, dist_ptr, ratio, back_idx_ptr, back_row0, n_back_rows, xy_ptr, ldxy,
                              src_ptr, dst_ptr):
         s, q = _seg_pairs(seg, pairs)
         b = None if back_row0 is None else np.ascontiguousarray(back_row0, np.int64)
         assert b is None or b.shape == (q.shape[0],)
         moff = np.empty(q.shape[0] + 1, np.int64)
         ptr = lambda a: None if a is None else C.c_void_p(a)
-        self._ck(call(self.h, _p(s, i64p), s.size - 1, _p(q, i32p), q.shape[0], ptr(idx_ptr), ptr(d_ptr), 0.0 if ratio is None else ratio,
-                      ptr(back_idx_ptr), _p(b, i64p), n_back_rows, ptr(xy_ptr), ldxy, _p(moff, i64p), ptr(matches_ptr), ptr(dist_ptr), ptr(src_ptr),
-                      ptr(dst_ptr)))
+        self._ck(self._fn(line, "select_pairs", True)(self.h, _p(s, i64p), s.size - 1, _p(q, i32p), q.shape[0], ptr(idx_ptr), ptr(d_ptr),
+                                                      0.0 if ratio is None else ratio, ptr(back_idx_ptr), _p(b, i64p), n_back_rows, ptr(xy_ptr), ldxy,
+                                                      _p(moff, i64p), ptr(matches_ptr), ptr(dist_ptr), ptr(src_ptr), ptr(dst_ptr)))
         return moff
 
     def select_pairs_device(self, idx_ptr, d_ptr, seg, pairs, matches_ptr, dist_ptr, ratio=None, back_idx_ptr=None, back_row0=None, n_back_rows=0,
@@ -1547,13 +1518,13 @@ class DescContext:
         the first row of every pair's (-1: no check); it may be idx_ptr itself.  xy_ptr is the coordinate table (pitch ldxy
         floats).  The lists go to device memory of R entries each: matches [., 2] int32, dist [.] float32, and with xy_ptr src,
         dst [., 2] float32.  Returns moff [n_pairs + 1] int64; the first moff[-1] entries are written."""
-        return self._select_pairs_device(self.L.dlco_desc_select_pairs_device, idx_ptr, d_ptr, seg, pairs, matches_ptr, dist_ptr, ratio, back_idx_ptr,
+        return self._select_pairs_device(_FLOAT, idx_ptr, d_ptr, seg, pairs, matches_ptr, dist_ptr, ratio, back_idx_ptr,
                                          back_row0, n_back_rows, xy_ptr, ldxy, src_ptr, dst_ptr)
 
     def select_pairs_u8_device(self, idx_ptr, d_ptr, seg, pairs, matches_ptr, dist_ptr, ratio=None, back_idx_ptr=None, back_row0=None, n_back_rows=0,
                                xy_ptr=None, ldxy=2, src_ptr=None, dst_ptr=None):
         """select_pairs_device on the answer of match_pairs_u8_device: int32 distances in and out."""
-        return self._select_pairs_device(self.L.dlco_desc_select_pairs_u8_device, idx_ptr, d_ptr, seg, pairs, matches_ptr, dist_ptr, ratio,
+        return self._select_pairs_device(_BYTE, idx_ptr, d_ptr, seg, pairs, matches_ptr, dist_ptr, ratio,
                                          back_idx_ptr, back_row0, n_back_rows, xy_ptr, ldxy, src_ptr, dst_ptr)
 
     def match_pairs_slices(self, seg, pairs, u8=False):

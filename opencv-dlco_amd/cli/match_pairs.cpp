@@ -11,10 +11,11 @@
 //                                                          `match` writes for the pair's two files
 //     "MatchOffsets" [P+1] i64: pair p owns the rows MatchOffsets[p] .. MatchOffsets[p+1] - 1 of
 //     "Matches" [M,2] i32 = (query, train) as rows of the pair's own two tables, and "MatchSqDist" [M] f32   the filtered lists
-// The filters are `match`'s host rules (match_rules.hpp), applied per pair: -ratio f (0 < f <= 1) is Lowe's test, -cross the
-// mutual check, for which the reversed pairs are appended to the same batch instead of making second calls.
-//   With -u8 the files hold "DescriptorU8" [n, r] u8 instead, the call is dlco_desc_match_pairs_u8 and the distances are
-// i32.  Files that carry a quantiser ("QuantScale", "QuantOffset") must all carry the same one, bit for bit.
+// The filters are the library's, ONE dlco_desc_select_pairs call over the P pairs (include/dlco.h states the rule): -ratio f
+// (0 < f <= 1) is Lowe's test, -cross the mutual check, for which the reversed pairs are appended to the same batch instead of
+// making second calls.
+//   With -u8 the files hold "DescriptorU8" [n, r] u8 instead, the calls are dlco_desc_match_pairs_u8 and
+// dlco_desc_select_pairs_u8, and the distances are i32.  Files that carry a quantiser ("QuantScale", "QuantOffset") must all carry the same one, bit for bit.
 //   With -guided the call is dlco_desc_match_pairs_guided: every pair is matched again under its own model of a `verify-pairs`
 // output ("HomographyBits" [P,9], query image -> train image), among the train keypoints the model puts within -radius pixels
 // (default 6) of the query.  The output's "Pairs" must be the -pairs list, row for row; a pair without a model (an all-zero
@@ -24,37 +25,17 @@
 // "FundamentalBits" of a `verify-pairs -model fundamental` output (dlco_desc_match_pairs_guided_epipolar, -radius its
 // threshold).  The datasets written are the same; per pair they are what `match -guided` writes.  There is no guided -u8.
 // A path that does not end in .h5/.hdf5 is a directory of .npy files with the same dataset names (dlco_io.hpp).
-#include "../../include/dlco.h"
-#include "dlco_io.hpp"
-#include "match_rules.hpp"
+#include "match_tool.hpp"
 #include "quant_io.hpp"
 
 #include <chrono>
-#include <cmath>
 #include <cstdlib>
-#include <cstring>
-#include <iostream>
 
 using std::cout;
 using std::endl;
+using match_tool::Line;
 
 namespace {
-template <typename T> struct Line;
-template <> struct Line<float> {
-    using Dist = float;
-    static constexpr const char *dataset = "Descriptor";
-    static constexpr const char *tag = "";
-    static int call(dlco_desc_ctx *c, const float *t, const int64_t *seg, int32_t n_img, const int32_t *pairs, int64_t n_pairs, int32_t r,
-                    int32_t *idx, float *d) { return dlco_desc_match_pairs(c, t, seg, n_img, pairs, n_pairs, r, idx, d); }
-};
-template <> struct Line<uint8_t> {
-    using Dist = int32_t;
-    static constexpr const char *dataset = "DescriptorU8";
-    static constexpr const char *tag = " (u8)";
-    static int call(dlco_desc_ctx *c, const uint8_t *t, const int64_t *seg, int32_t n_img, const int32_t *pairs, int64_t n_pairs, int32_t r,
-                    int32_t *idx, int32_t *d) { return dlco_desc_match_pairs_u8(c, t, seg, n_img, pairs, n_pairs, r, idx, d); }
-};
-
 // -guided: the verify-pairs output, the keypoint files, the radius or threshold and the model
 struct Guided {
     const char *verify_out = nullptr;
@@ -75,16 +56,11 @@ void run(const char *pairs_file, const std::vector<const char *> &files, const c
     for (size_t f = 0; f < n_img; f++) {
         std::vector<size_t> shape;
         std::vector<T> rows;
-        dlco_io::read_dataset<T>(files[f], Line<T>::dataset, shape, rows);
-        if (shape.size() != 2 || shape[1] < 1) throw std::runtime_error(std::string(files[f]) + ": " + Line<T>::dataset + " must be an [n, r] table");
+        match_tool::load_table<T>(files[f], true, shape, rows);
         if (f == 0) r = shape[1];
         if (shape[1] != r)
             throw std::runtime_error("the descriptors differ in size: " + std::to_string(r) + " (" + files[0] + ") against " + std::to_string(shape[1]) +
                                      " (" + files[f] + ")");
-        if constexpr (std::is_same<T, float>::value) {
-            for (float v : rows)
-                if (!(v == v) || v > 3.0e38f || v < -3.0e38f) throw std::runtime_error(std::string(files[f]) + ": Descriptor contains NaN");
-        }
         seg[f + 1] = seg[f] + (int64_t)shape[0];
         table.insert(table.end(), rows.begin(), rows.end());
     }
@@ -117,16 +93,7 @@ void run(const char *pairs_file, const std::vector<const char *> &files, const c
     std::vector<double> models;
     if (guided) {
         xy.resize((size_t)seg[n_img] * 2);
-        for (size_t f = 0; f < n_img; f++) {
-            std::vector<size_t> shape;
-            std::vector<float> kp;
-            dlco_io::read_dataset<float>(guided->kp[f], "Keypoints", shape, kp);
-            if (shape.size() != 2 || shape[1] != 4) throw std::runtime_error(std::string(guided->kp[f]) + ": Keypoints must be an [n, 4] table");
-            if ((int64_t)shape[0] != seg[f + 1] - seg[f])
-                throw std::runtime_error(std::string(guided->kp[f]) + ": " + std::to_string(shape[0]) + " keypoints against " +
-                                         std::to_string(seg[f + 1] - seg[f]) + " descriptors in " + files[f]);
-            for (size_t i = 0; i < shape[0]; i++) { xy[2 * ((size_t)seg[f] + i)] = kp[4 * i]; xy[2 * ((size_t)seg[f] + i) + 1] = kp[4 * i + 1]; }
-        }
+        for (size_t f = 0; f < n_img; f++) match_tool::load_xy(guided->kp[f], (size_t)(seg[f + 1] - seg[f]), files[f], xy.data() + 2 * seg[f]);
         std::vector<size_t> vs, bs;
         std::vector<int32_t> vpairs;
         std::vector<int64_t> bits;
@@ -143,7 +110,7 @@ void run(const char *pairs_file, const std::vector<const char *> &files, const c
     }
     printf("Tables: %zu, %lld x %zu%s\n", n_img, (long long)seg[n_img], r, Line<T>::tag);
     printf("Pairs: %zu\n", P);
-    if (guided) printf(guided->fundamental ? "Guided: fundamental, radius %g\n" : "Guided: radius %g\n", guided->radius);
+    if (guided) match_tool::print_guided(guided->fundamental, guided->radius);
 
     // -cross: the reversed pairs ride in the same batch, pair P + p is pair p swapped
     std::vector<int32_t> batch(pairs);
@@ -159,34 +126,27 @@ void run(const char *pairs_file, const std::vector<const char *> &files, const c
     std::vector<int32_t> nearest((size_t)row0[B] * 2);
     std::vector<Dist> sqdist((size_t)row0[B] * 2);
     double kernel_ms = 0.0;
-    if constexpr (std::is_same<T, float>::value) {
-        if (guided) {
-            // the pairs under side 0, then (-cross) the reversed pairs under side 1 and the same matrices: two calls, one output
-            const auto call = guided->fundamental ? dlco_desc_match_pairs_guided_epipolar : dlco_desc_match_pairs_guided;
-            for (size_t k = 0; k < B / P; k++) {
-                if (call(ctx, table.data(), xy.data(), seg.data(), (int32_t)n_img, batch.data() + 2 * P * k, (int64_t)P, (int32_t)r, models.data(),
-                         guided->radius, (int32_t)k, nearest.data() + 2 * row0[P * k], sqdist.data() + 2 * row0[P * k]) != DLCO_OK)
-                    throw std::runtime_error(dlco_desc_last_error(ctx));
-                kernel_ms += dlco_desc_last_kernel_ms(ctx);
-            }
+    if (guided) {
+        // the pairs under side 0, then (-cross) the reversed pairs under side 1 and the same matrices: two calls, one output
+        const auto call = guided->fundamental ? Line<T>::pairs_guided_epipolar : Line<T>::pairs_guided;
+        for (size_t k = 0; k < B / P; k++) {
+            if (call(ctx, table.data(), xy.data(), seg.data(), (int32_t)n_img, batch.data() + 2 * P * k, (int64_t)P, (int32_t)r, models.data(),
+                     guided->radius, (int32_t)k, nearest.data() + 2 * row0[P * k], sqdist.data() + 2 * row0[P * k]) != DLCO_OK)
+                throw std::runtime_error(dlco_desc_last_error(ctx));
+            kernel_ms += dlco_desc_last_kernel_ms(ctx);
         }
-    }
-    if (!guided) {
-        if (Line<T>::call(ctx, table.data(), seg.data(), (int32_t)n_img, batch.data(), (int64_t)B, (int32_t)r, nearest.data(), sqdist.data()) != DLCO_OK)
+    } else {
+        if (Line<T>::match_pairs(ctx, table.data(), seg.data(), (int32_t)n_img, batch.data(), (int64_t)B, (int32_t)r, nearest.data(), sqdist.data()) != DLCO_OK)
             throw std::runtime_error(dlco_desc_last_error(ctx));
         kernel_ms = dlco_desc_last_kernel_ms(ctx);
     }
-    std::vector<int64_t> moff(P + 1, 0);
-    std::vector<int32_t> matches, mp;
-    std::vector<Dist> mdist, md;
-    for (size_t p = 0; p < P; p++) {
-        const int64_t nq = row0[p + 1] - row0[p];
-        match_rules::select(nq, nearest.data() + 2 * row0[p], sqdist.data() + 2 * row0[p], use_ratio, ratio,
-                            cross ? nearest.data() + 2 * row0[P + p] : nullptr, mp, md);
-        matches.insert(matches.end(), mp.begin(), mp.end());
-        mdist.insert(mdist.end(), md.begin(), md.end());
-        moff[p + 1] = (int64_t)mdist.size();
-    }
+    // the lists of the first P pairs; -cross: pair p's reverse answer is pair P + p's rows of the same buffer, whichever call wrote them
+    std::vector<int64_t> moff;
+    std::vector<int32_t> matches;
+    std::vector<Dist> mdist;
+    const std::vector<int64_t> back_row0(row0.begin() + (B - P), row0.begin() + B);
+    match_tool::select<T>(ctx, seg, batch.data(), P, (size_t)row0[P], nearest.data(), sqdist.data(), use_ratio ? ratio : 0.0f,
+                          cross ? nearest.data() : nullptr, back_row0, row0[B], moff, matches, mdist);
     {
         dlco_io::Writer wr(out);
         wr.write<int32_t>("Pairs", pairs.data(), P, 2);
@@ -238,15 +198,9 @@ int main(int argc, char **argv)
         }
     }
     if (!pairs_file || !out || files.empty()) help = true;
-    if (use_ratio && !(ratio > 0.0f && ratio <= 1.0f)) {
-        cout << "ERROR: -ratio must be in (0, 1]." << endl;
-        help = true;
-    }
+    if (!match_tool::ratio_ok(use_ratio, ratio)) help = true;
     guided.fundamental = model && std::strcmp(model, "fundamental") == 0;
-    if (model && !guided.fundamental && std::strcmp(model, "homography") != 0) {
-        cout << "ERROR: -model must be homography or fundamental." << endl;
-        help = true;
-    }
+    if (!match_tool::model_ok(model)) help = true;
     if ((model || kp_given) && !guided.verify_out) {
         cout << "ERROR: -kp and -model need -guided." << endl;
         help = true;
@@ -259,10 +213,7 @@ int main(int argc, char **argv)
         cout << "ERROR: -guided has no -u8 form." << endl;
         help = true;
     }
-    if (!(std::isfinite(guided.radius) && guided.radius > 0.0f)) {
-        cout << "ERROR: -radius must be finite and > 0." << endl;
-        help = true;
-    }
+    if (!match_tool::radius_ok(guided.radius)) help = true;
     if (help) {
         cout << endl;
         cout << "Usage: match-pairs -pairs pairs_file -out dst_h5_filename [-u8] [-ratio f] [-cross] [-device n] desc_file_0 desc_file_1 ..." << endl;

@@ -1,7 +1,8 @@
 // select_rules.hpp — which rows of a batched match answer become matches (dlco_desc_select_pairs*): Lowe's ratio test, the
 // mutual check and the order of the compacted list.  The rule stated once for the host path (dlco_desc_api.cpp), the kernels
-// (kernels_select.hip), the tools' filters (cli/match_rules.hpp forwards here) and the CPU tests
-// (tests/shim/select_rules_shim.cpp).  Plain C++: no HIP header, no device, no I/O.
+// (kernels_select.hip) and the CPU tests (tests/shim/select_rules_shim.cpp, and match_rules_shim.cpp / match_rules_u8_shim.cpp
+// on one pair).  The tools match and match-pairs hold no copy: they call dlco_desc_select_pairs*.  Plain C++: no HIP header, no
+// device, no I/O.
 //
 // The answer of a match_pairs call, plain or guided, is idx [R][2] / sqdist [R][2]: pair p = (a, b) owns the rows
 // [row0[p], row0[p + 1]) (match_batch.hpp), row i of it holds the nearest two rows of image b for row i of image a.  With

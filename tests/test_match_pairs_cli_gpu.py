@@ -1,12 +1,14 @@
 """The tool match-pairs on a GPU: four small descriptor files, with and without -ratio 0.8 -cross, float and -u8.  Every pair's
 Nearest, NearestSqDist, Matches and MatchSqDist are byte-equal to a run of the tool match on that pair's two files with the
-same flags."""
+same flags.  Two more cases put the lists of both tools against the numpy rule of test_match_cli_gpu.py where the select call
+behind them has more than one block of rows, and an image without rows."""
 import os
 import subprocess
 
 import numpy as np
 import pytest
 
+from test_match_cli_gpu import rules
 from test_match_gpu import make_tables
 from test_match_u8_gpu import byte_tables
 
@@ -68,3 +70,53 @@ def test_match_pairs_writes_what_match_writes_for_every_pair(files, tmp_path, u8
     assert "Pairs: %d" % len(PAIRS) in q.stdout and "Matches: %d / %d" % (total, row0[-1]) in q.stdout and "Total: " in q.stdout
     if flags[:1] == ["-ratio"]:
         assert 0 < total < row0[-1]                         # the filters did filter
+
+
+def run_tool(tool, args):
+    q = subprocess.run([os.path.join(CLI, tool)] + args, capture_output=True, text=True, timeout=600)
+    assert q.returncode == 0, q.stderr
+    return q.stdout
+
+
+def check_lists(u8, near, near_d, back, mat, mat_d):
+    """Matches / MatchSqDist of one pair against the numpy rule of test_match_cli_gpu.py on the tool's own Nearest, -ratio 0.8 -cross"""
+    want_p, _ = rules(near, near_d, 0.8, back)
+    assert mat.dtype == np.int32 and mat_d.dtype == (np.int32 if u8 else np.float32) and mat.shape == want_p.shape
+    assert np.array_equal(mat, want_p) and mat_d.tobytes() == near_d[want_p[:, 0], 0].tobytes()
+    return len(want_p)
+
+
+@pytest.mark.parametrize("u8", [False, True])
+def test_match_selects_among_more_queries_than_a_select_block(files, tmp_path, u8):
+    """match -ratio -cross with 300 queries: the select call behind it cuts them into two blocks of 256 rows."""
+    flags = ["-ratio", "0.8", "-cross"] + (["-u8"] if u8 else [])
+    fwd, rev = tmp_path / "fwd", tmp_path / "rev"
+    stdout = run_tool("match", [files[u8][1], files[u8][3], "-out", str(fwd)] + flags)
+    run_tool("match", [files[u8][3], files[u8][1], "-out", str(rev)] + flags[2:])
+    load = lambda d, name: np.load(os.path.join(str(d), name + ".npy"))
+    near, back = load(fwd, "Nearest"), load(rev, "Nearest")
+    assert near.shape == (300, 2) and back.shape == (129, 2)
+    m = check_lists(u8, near, load(fwd, "NearestSqDist"), back, load(fwd, "Matches"), load(fwd, "MatchSqDist"))
+    assert 0 < m < 300 and "Matches: %d / 300" % m in stdout
+
+
+@pytest.mark.parametrize("u8", [False, True])
+def test_match_pairs_selects_across_blocks_and_an_empty_image(files, tmp_path, u8):
+    """match-pairs -ratio -cross on pairs that own 881 rows, an image without rows among them on either side: every pair's
+    lists by the numpy rule, the reverse answer read from the pair that lists it the other way round."""
+    empty, pdir, out = tmp_path / "empty", tmp_path / "pairs", tmp_path / "batch"
+    empty.mkdir()
+    pdir.mkdir()
+    np.save(empty / ("DescriptorU8.npy" if u8 else "Descriptor.npy"), np.zeros((0, R), np.uint8 if u8 else np.float32))
+    pairs = [(0, 1), (1, 0), (0, 4), (4, 0), (3, 1), (1, 3)]                 # pair p ^ 1 is pair p reversed
+    np.save(pdir / "Pairs.npy", np.array(pairs, np.int32))
+    stdout = run_tool("match-pairs", ["-pairs", str(pdir), "-out", str(out), "-ratio", "0.8", "-cross"] + (["-u8"] if u8 else []) + files[u8] + [str(empty)])
+    load = lambda name: np.load(os.path.join(str(out), name + ".npy"))
+    row0, moff, near, near_d, mat, mat_d = (load(n) for n in ("RowOffsets", "MatchOffsets", "Nearest", "NearestSqDist", "Matches", "MatchSqDist"))
+    assert row0.tolist() == [0, 76, 376, 452, 452, 581, 881] and moff.shape == (7,) and moff[0] == 0 and mat.shape == (moff[-1], 2)
+    assert (near[376:452] == -1).all() and moff[2] == moff[3] == moff[4]     # an empty train image, an empty query image: no match
+    rows = lambda p: slice(row0[p], row0[p + 1])
+    for p in range(len(pairs)):
+        m = check_lists(u8, near[rows(p)], near_d[rows(p)], near[rows(p ^ 1)], mat[moff[p]:moff[p + 1]], mat_d[moff[p]:moff[p + 1]])
+        assert m == moff[p + 1] - moff[p] and (m > 0 or 4 in pairs[p])
+    assert "Tables: 5, 522 x 20" in stdout and "Matches: %d / 881" % moff[-1] in stdout

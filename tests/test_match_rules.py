@@ -1,5 +1,6 @@
-"""CPU tests of the match tool's filters (opencv-dlco_amd/cli/match_rules.hpp, through tests/shim/match_rules_shim.cpp): Lowe's
-ratio test stated on squared distances, the mutual (cross) check, both together.  Nothing here needs a GPU or libdlco.so."""
+"""CPU tests of the match tool's filters (the rule of opencv-dlco_amd/csrc/select_rules.hpp on one pair, through
+tests/shim/match_rules_shim.cpp): Lowe's ratio test stated on squared distances, the mutual (cross) check, both together.
+Nothing here needs a GPU or libdlco.so."""
 import ctypes as C
 import os
 import subprocess
@@ -19,7 +20,7 @@ def rules(tmp_path_factory):
                            os.path.join(ROOT, "tests", "shim", "match_rules_shim.cpp")])
     L = C.CDLL(str(out))
     L.shim_match_ratio_keep.argtypes = [C.c_float, C.c_float, C.c_int32, C.c_float]
-    L.shim_match_select.argtypes = [C.c_int64, i32p, f32p, C.c_int, C.c_float, i32p, i32p, f32p]
+    L.shim_match_select.argtypes = [C.c_int64, C.c_int32, i32p, f32p, C.c_int, C.c_float, i32p, i32p, f32p]
     L.shim_match_select.restype = C.c_int64
     return L
 
@@ -30,7 +31,8 @@ def select(L, nearest, sqdist, ratio=None, back=None):
     nq = len(nearest)
     pairs, dists = np.full((max(nq, 1), 2), -99, np.int32), np.full(max(nq, 1), -99, np.float32)
     b = None if back is None else np.ascontiguousarray(back, np.int32)
-    m = L.shim_match_select(nq, nearest.ctypes.data_as(i32p), sqdist.ctypes.data_as(f32p), 0 if ratio is None else 1,
+    nt = len(b) if b is not None else int(nearest.max(initial=0)) + 1      # the back table's rows, else above every index used
+    m = L.shim_match_select(nq, nt, nearest.ctypes.data_as(i32p), sqdist.ctypes.data_as(f32p), 0 if ratio is None else 1,
                             1.0 if ratio is None else ratio, None if b is None else b.ctypes.data_as(i32p),
                             pairs.ctypes.data_as(i32p), dists.ctypes.data_as(f32p))
     return pairs[:m], dists[:m]

@@ -1,5 +1,5 @@
 """CPU tests of the quantiser (opencv-dlco_amd/csrc/quant_rules.hpp, through tests/shim/quant_rules_shim.cpp) against its numpy
-float32 restatement, and of the integer twins of the match tool's filters (opencv-dlco_amd/cli/match_rules.hpp, through
+float32 restatement, and of the integer twins of the match tool's filters (opencv-dlco_amd/csrc/select_rules.hpp, through
 tests/shim/match_rules_u8_shim.cpp).  Nothing here needs a GPU or libdlco.so."""
 import ctypes as C
 import os
@@ -139,7 +139,7 @@ def test_fit_equals_the_restatement_and_its_own_sample_never_clamps(rules):
 def mrules(tmp_path_factory):
     L = _compile(tmp_path_factory, "libmatchu8shim.so", "match_rules_u8_shim.cpp")
     L.shim_match_ratio_keep_i32.argtypes = [C.c_int32, C.c_int32, C.c_int32, C.c_float]
-    L.shim_match_select_i32.argtypes = [C.c_int64, i32p, i32p, C.c_int, C.c_float, i32p, i32p, i32p]
+    L.shim_match_select_i32.argtypes = [C.c_int64, C.c_int32, i32p, i32p, C.c_int, C.c_float, i32p, i32p, i32p]
     L.shim_match_select_i32.restype = C.c_int64
     return L
 
@@ -169,7 +169,8 @@ def select(L, nearest, sqdist, ratio=None, back=None):
     nq = len(nearest)
     pairs, dists = np.full((max(nq, 1), 2), -99, np.int32), np.full(max(nq, 1), -99, np.int32)
     b = None if back is None else np.ascontiguousarray(back, np.int32)
-    m = L.shim_match_select_i32(nq, nearest.ctypes.data_as(i32p), sqdist.ctypes.data_as(i32p), 0 if ratio is None else 1,
+    nt = len(b) if b is not None else int(nearest.max(initial=0)) + 1      # the back table's rows, else above every index used
+    m = L.shim_match_select_i32(nq, nt, nearest.ctypes.data_as(i32p), sqdist.ctypes.data_as(i32p), 0 if ratio is None else 1,
                                 1.0 if ratio is None else ratio, None if b is None else b.ctypes.data_as(i32p),
                                 pairs.ctypes.data_as(i32p), dists.ctypes.data_as(i32p))
     return pairs[:m], dists[:m]

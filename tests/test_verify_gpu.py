@@ -145,7 +145,7 @@ def chain_model(c):
 
 
 def ratio_cross_ref(nearest, sqdist, back, f):
-    """match's two host rules restated (cli/match_rules.hpp): d1 < f^2 d2 in double, and the nearest query of train row j is i"""
+    """match's two rules restated (csrc/select_rules.hpp): d1 < f^2 d2 in double, and the nearest query of train row j is i"""
     f = float(np.float32(f))
     return np.array([(i, j) for i, ((j, j2), (d1, d2)) in enumerate(zip(nearest.tolist(), sqdist.astype(np.float64).tolist()))
                      if j >= 0 and (j2 == -1 or d1 < f * f * d2) and int(back[j][0]) == i], np.int32).reshape(-1, 2)
