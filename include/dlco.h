@@ -863,7 +863,7 @@ int dlco_desc_match_pairs_guided_epipolar_u8_device(dlco_desc_ctx *ctx, const ui
  * (the fundamental matrix has calls of its own, dlco_desc_verify_fundamental below; an essential matrix has none);
  * symmetric transfer error; an adaptive hypothesis count.
  *   In scope since: filtering the match list on the device, dlco_desc_select_pairs* below, which writes the lists of
- * dlco_desc_verify_pairs_* from a batched answer in device memory (the verification itself still takes its lists on the host). */
+ * dlco_desc_verify_pairs_* from a batched answer in device memory; dlco_desc_verify_pairs_*_device below take them there. */
 int  dlco_desc_verify_homography(dlco_desc_ctx *ctx, const float *src_xy_host, const float *dst_xy_host, int64_t m, float threshold,
                                  int32_t n_hyp, uint64_t seed, int32_t refine, double *H_out, uint8_t *inlier_host, int64_t *n_inliers,
                                  int32_t *best_hyp);
@@ -910,7 +910,8 @@ int  dlco_desc_verify_fundamental_hypotheses(dlco_desc_ctx *ctx, const float *sr
  *   DLCO_ERR_INVALID, before the handle is used and with no output touched: a null handle or required pointer, n_pairs < 1 or
  * n_pairs >= 2^31, moff[0] != 0, a decreasing moff, a pair of 2^31 matches or more, a threshold, n_hyp or refine outside the
  * single call's limits.
- *   Out of scope: a device-memory form; seeds or thresholds per pair; a choice between H and F. ---- */
+ *   Out of scope: a device-memory form; seeds or thresholds per pair; a choice between H and F.
+ *   In scope since: the device-memory form, dlco_desc_verify_pairs_*_device below, with its refit on the device. ---- */
 int  dlco_desc_verify_pairs_homography(dlco_desc_ctx *ctx, const float *src_xy_host, const float *dst_xy_host, const int64_t *moff,
                                        int64_t n_pairs, float threshold, int32_t n_hyp, uint64_t seed, int32_t refine, double *H_out,
                                        uint8_t *inlier_host, int64_t *n_inliers, int32_t *best_hyp);
@@ -928,6 +929,37 @@ int  dlco_desc_verify_pairs_fundamental_hypotheses(dlco_desc_ctx *ctx, const flo
  * call, -1 for a pair that launches nothing (fewer matches than a sample); fundamental = 0: the homography, 1: the fundamental
  * matrix.  DLCO_ERR_INVALID as above, and for another value of fundamental.  For tests and tools */
 int  dlco_desc_verify_pairs_launches(const int64_t *moff, int64_t n_pairs, int32_t n_hyp, int32_t fundamental, int32_t *launch_of_pair);
+/* ---- The batched verification on lists in device memory: the step behind dlco_desc_select_pairs_device, so that the chain
+ * match_pairs_device -> select_pairs_device -> verify_pairs_*_device -> match_pairs_guided*_device moves only moff, the matrices
+ * (72 bytes per pair) and the counts to the host.  src_xy_dev, dst_xy_dev [M][2] float in device memory, as
+ * dlco_desc_select_pairs_device wrote them, 8-byte aligned (the kernels read pairs of floats); moff [n_pairs + 1] host memory, as
+ * that call returns it.  A launch of the plan (csrc/verify_batch.hpp, unchanged) reads its range of the lists in place: nothing
+ * is copied.  The refit runs on the device: a kernel forms the round's matrices from the current masks (refit_pairs_kernel,
+ * csrc/kernels_verify.hip: the sums of the rule in ascending match index, one lane per sum; the rule headers' elimination or
+ * Jacobi), the mask kernel scores them, a third kernel is verify_rules::refit_step.  Per launch the hypotheses, the scoring, the
+ * selection, the first mask and the `refine` rounds are queued without a host sync; then one download of matrices, counts and
+ * keys, and one sync.
+ *   Output: M_out [n_pairs][9], n_inliers [n_pairs] and best_hyp [n_pairs] (may be NULL) in host memory; inlier_dev [M] (may be
+ * NULL) in device memory, written in place, the slices of pairs below the sample zeroed.  Pair p's matrix, mask slice, count
+ * and best hypothesis are, byte for byte, what dlco_desc_verify_pairs_homography (dlco_desc_verify_pairs_fundamental) returns for
+ * the same lists on the host: the refit kernel calls the rule headers' functions, and its double sqrt and division are the
+ * correctly rounded ones.
+ *   "No model", a pair below the sample, M = 0 and DLCO_ERR_INVALID are those of the host forms; a src_xy_dev or dst_xy_dev
+ * that is not 8-byte aligned is DLCO_ERR_INVALID as well.
+ *   Out of scope: the host forms and the tools on these rounds (they keep their host refit); moff in device memory. ---- */
+int  dlco_desc_verify_pairs_homography_device(dlco_desc_ctx *ctx, const float *src_xy_dev, const float *dst_xy_dev, const int64_t *moff,
+                                              int64_t n_pairs, float threshold, int32_t n_hyp, uint64_t seed, int32_t refine, double *H_out,
+                                              uint8_t *inlier_dev, int64_t *n_inliers, int32_t *best_hyp);
+int  dlco_desc_verify_pairs_fundamental_device(dlco_desc_ctx *ctx, const float *src_xy_dev, const float *dst_xy_dev, const int64_t *moff,
+                                               int64_t n_pairs, float threshold, int32_t n_hyp, uint64_t seed, int32_t refine, double *F_out,
+                                               uint8_t *inlier_dev, int64_t *n_inliers, int32_t *best_hyp);
+/* one round of the refit kernel on masks of the caller's, for tests and tools: lists and moff as dlco_desc_verify_pairs_* take
+ * them, mask_host [M] (0 / non-zero), fundamental = 0 or 1.  M_out [n_pairs][9] is the round's matrix, byte for byte
+ * verify_rules::refit_round's (epipolar_rules::refit_round's) on the pair's slice; ok [n_pairs] = 1.  A rejected round, and a
+ * pair below the sample, give ok = 0 and a zero matrix.  DLCO_ERR_INVALID as the _pairs forms, and for another value of
+ * fundamental */
+int  dlco_desc_verify_pairs_refit_round(dlco_desc_ctx *ctx, const float *src_xy_host, const float *dst_xy_host, const int64_t *moff,
+                                        int64_t n_pairs, const uint8_t *mask_host, int32_t fundamental, double *M_out, uint8_t *ok);
 /* ---- Selecting matches: from the answer of a dlco_desc_match_pairs* call to the lists of a dlco_desc_verify_pairs_* call.  The
  * link between the two: Lowe's ratio test, the mutual check and the compaction into (query, train) rows, on the device, so that
  * a caller whose idx / sqdist live in HBM need not download them, restate the rule and gather coordinates.
@@ -957,12 +989,12 @@ int  dlco_desc_verify_pairs_launches(const int64_t *moff, int64_t n_pairs, int32
  * sqdist, moff, matches, dist), whatever dlco_desc_match_pairs rejects of seg / pairs, R >= 2^31, a ratio that is NaN, negative or
  * above 1, back_idx without back_row0, a back_row0[p] below -1 or one whose nt_b rows end beyond n_back_rows, src_xy or dst_xy
  * without xy or only one of the two, ldxy < 2 with xy.
- *   Out of scope: a device-memory form of dlco_desc_verify_pairs_* (its refit runs on the host and needs the list there anyway);
- * seg / pairs in device memory; the tools, which keep their host rule; single-pair entry points: a batch of one pair is the
+ *   Out of scope: seg / pairs in device memory; the tools, which keep their host rule; single-pair entry points: a batch of one pair is the
  * single call.
  *   In scope since: the tools.  match and match-pairs make their lists with the host forms of these calls (cli/match_tool.hpp),
  * match as a batch of one pair with the reverse answer of its second call as back_idx; no host restatement of the rule is
- * left in them. ---- */
+ * left in them.  Also a device-memory form of dlco_desc_verify_pairs_*: dlco_desc_verify_pairs_*_device above take src_xy_dev
+ * and dst_xy_dev as these calls write them. ---- */
 int  dlco_desc_select_pairs(dlco_desc_ctx *ctx, const int64_t *seg, int32_t n_img, const int32_t *pairs, int64_t n_pairs,
                             const int32_t *idx_host, const float *sqdist_host, float ratio, const int32_t *back_idx_host,
                             const int64_t *back_row0, int64_t n_back_rows, const float *xy_host, int64_t *moff, int32_t *matches_host,
@@ -990,7 +1022,8 @@ int  dlco_desc_select_pairs_u8_device(dlco_desc_ctx *ctx, const int64_t *seg, in
  * verify call the verify kernels, of either model, as after a verify_pairs call of one pair, which is what a verify call
  * runs; after a verify_pairs call every kernel of the call (the hypotheses and the scoring of every launch; the model forms,
  * verify_homography, verify_fundamental, verify_pairs_homography and verify_pairs_fundamental, add the selection, the mask
- * of the best models and the mask launch of every lockstep refit round); after a select_pairs call, float or _u8, its kernels
+ * of the best models and the mask launch of every lockstep refit round; the _device forms all of that and, for every round,
+ * the refit and the step kernel; verify_pairs_refit_round its one refit launch per launch of the plan); after a select_pairs call, float or _u8, its kernels
  * (the flags, the scan of the block counts, the scatter, the match offsets; 0 when the batch has no row) */
 double dlco_desc_last_kernel_ms(const dlco_desc_ctx *ctx);
 

@@ -217,6 +217,9 @@ def load():
     L.dlco_desc_verify_pairs_fundamental.argtypes = L.dlco_desc_verify_pairs_homography.argtypes
     L.dlco_desc_verify_pairs_fundamental_hypotheses.argtypes = L.dlco_desc_verify_pairs_hypotheses.argtypes
     L.dlco_desc_verify_pairs_launches.argtypes = [i64p, i64, C.c_int32, C.c_int32, i32p]
+    L.dlco_desc_verify_pairs_homography_device.argtypes = [vp, vp, vp, i64p, i64, C.c_float, C.c_int32, C.c_uint64, C.c_int32, f64p, vp, i64p, i32p]
+    L.dlco_desc_verify_pairs_fundamental_device.argtypes = L.dlco_desc_verify_pairs_homography_device.argtypes
+    L.dlco_desc_verify_pairs_refit_round.argtypes = [vp, f32p, f32p, i64p, i64, u8p, C.c_int32, f64p, u8p]
     L.dlco_desc_match_guided.argtypes = [vp, f32p, f32p, i64, f32p, f32p, i64, C.c_int32, f64p, C.c_float, C.c_int32, i32p, f32p]
     L.dlco_desc_match_guided_device.argtypes = [vp, vp, i64, vp, i64, i64, vp, i64, vp, i64, i64, C.c_int32, f64p, C.c_float,
                                                 C.c_int32, vp, vp]
@@ -1208,6 +1211,39 @@ class DescContext:
     def verify_pairs_fundamental_hypotheses(self, lists, threshold=1.0, n_hyp=2048, seed=0):
         """Every hypothesis of verify_pairs_fundamental and its count, all zero for a pair of fewer than 8 matches."""
         return self._verify_pairs_hypotheses(self.L.dlco_desc_verify_pairs_fundamental_hypotheses, lists, threshold, n_hyp, seed)
+
+    def _verify_pairs_device(self, call, src_ptr, dst_ptr, moff, threshold, n_hyp, seed, refine, inlier_ptr):
+        o = np.ascontiguousarray(moff, np.int64)
+        assert o.ndim == 1 and o.size >= 2
+        P = o.size - 1
+        M, n, best = np.zeros((P, 3, 3), np.float64), np.zeros(P, np.int64), np.zeros(P, np.int32)
+        self._ck(call(self.h, C.c_void_p(src_ptr), C.c_void_p(dst_ptr), _p(o, i64p), P, threshold, n_hyp, seed, refine, _p(M, C.POINTER(C.c_double)),
+                      None if inlier_ptr is None else C.c_void_p(inlier_ptr), _p(n, i64p), _p(best, i32p)))
+        return M, n, best
+
+    def verify_pairs_homography_device(self, src_ptr, dst_ptr, moff, threshold=3.0, n_hyp=2048, seed=0, refine=2, inlier_ptr=None):
+        """verify_pairs_homography on lists in device memory, src / dst [moff[-1], 2] float32 (8-byte aligned) as
+        select_pairs_device wrote them and moff [n_pairs + 1] as it returned it, with the refit rounds on the device:
+        (H [n_pairs, 3, 3], n_inliers [n_pairs] int64, best_hyp [n_pairs] int32) on the host, the mask [moff[-1]] uint8 to the
+        device pointer inlier_ptr (None: no mask).  Every pair is byte for byte what verify_pairs_homography returns."""
+        return self._verify_pairs_device(self.L.dlco_desc_verify_pairs_homography_device, src_ptr, dst_ptr, moff, threshold, n_hyp, seed, refine, inlier_ptr)
+
+    def verify_pairs_fundamental_device(self, src_ptr, dst_ptr, moff, threshold=1.0, n_hyp=2048, seed=0, refine=2, inlier_ptr=None):
+        """verify_pairs_fundamental on lists in device memory, as verify_pairs_homography_device."""
+        return self._verify_pairs_device(self.L.dlco_desc_verify_pairs_fundamental_device, src_ptr, dst_ptr, moff, threshold, n_hyp, seed, refine, inlier_ptr)
+
+    def verify_pairs_refit_round(self, lists, masks, fundamental=False):
+        """One round of the refit kernel for a list of (src [m,2], dst [m,2]) under the caller's masks, a list of [m] bool:
+        (M [n_pairs, 3, 3] f64, ok [n_pairs] bool); a rejected round and a pair below the sample give ok = False and zeros.
+        For tests and tools."""
+        s, d, moff = self._match_lists(lists)
+        assert len(masks) == len(lists) and all(len(k) == len(l[0]) for k, l in zip(masks, lists))
+        mk = np.ascontiguousarray(np.concatenate([np.asarray(k, bool).astype(np.uint8) for k in masks] + [np.zeros(1, np.uint8)]))
+        P = moff.size - 1
+        M, ok = np.zeros((P, 3, 3), np.float64), np.zeros(P, np.uint8)
+        self._ck(self.L.dlco_desc_verify_pairs_refit_round(self.h, _p(s, f32p), _p(d, f32p), _p(moff, i64p), P, _p(mk, u8p), 1 if fundamental else 0,
+                                                           _p(M, C.POINTER(C.c_double)), _p(ok, u8p)))
+        return M, ok.astype(bool)
 
     def match_device(self, q_ptr, nq, t_ptr, nt, r, idx_ptr, d_ptr, ldq=None, ldt=None):
         """match on tables in device memory (row pitches ldq, ldt: multiples of 4, default r); results to device memory."""

@@ -101,12 +101,13 @@ struct dlco_desc_ctx {
     // verification (dlco_desc_verify_*, either model; a single call is a launch of one entry): one launch of
     // verify_batch.hpp's plan, a slot per entry.  The uploaded matches, every hypothesis and its count, the selection key,
     // v_cur, the matrix the mask kernel scores per entry, the trial mask and its count, and v_plan, the uploaded entries and
-    // behind them the active list; buffers of their own, like the matchers'
+    // behind them the active list; buffers of their own, like the matchers'.  The refit on the device (the _device forms,
+    // verify_pairs_refit_round) adds a round's matrices v_try, its trial mask and count, and the entries' live flags
     DevBuf<float> v_src, v_dst;
-    DevBuf<double> v_H, v_cur;
-    DevBuf<int32_t> v_count, v_n;
+    DevBuf<double> v_H, v_cur, v_try;
+    DevBuf<int32_t> v_count, v_n, v_ntry;
     DevBuf<uint64_t> v_key;
-    DevBuf<uint8_t> v_mask, v_plan;
+    DevBuf<uint8_t> v_mask, v_plan, v_trial, v_live;
     // selecting matches (dlco_desc_select_pairs*, select_rules.hpp): the uploaded pairs, the kept rows as bits, the block
     // counts, their exclusive sums and the match offsets; for the host forms the uploaded answer, reverse table and
     // coordinates and the lists on their way down (distances of either line as 4-byte words); buffers of their own
@@ -687,6 +688,7 @@ int select_pairs_host_call(dlco_desc_ctx *c, const SelectArgs &a, const int32_t 
 // epipolar_rules::Fundamental) and over the match lists of many pairs as one segmented list, by the plan of verify_batch.hpp.
 // A launch carries the workgroups of many pairs, the selection leaves the winning matrices on the device for the first mask,
 // and the refit runs in lockstep: the host forms a round's models, one mask launch scores those of every pair still refining.
+// The _device forms (verify_pairs_device_call) read their lists in device memory and run the lockstep rounds in kernels.
 // The single calls (dlco_desc_verify_homography and its kin) are this path with one pair, moff = {0, m}: a launch of one
 // entry.  Model::kSample matches make a sample -------------------------------------------------------------------------------
 using verify_rules::Homography;
@@ -808,7 +810,7 @@ int verify_pairs_model_call(dlco_desc_ctx *c, const float *src_xy_host, const fl
                 verify_pairs_hypotheses<Model>(c->v_src.p, c->v_dst.p, v.ent, v.n, seed, n_hyp, c->v_H.p, c->stream);
                 verify_pairs_score<Model>(c->v_src.p, c->v_dst.p, v.ent, v.n, la.score_wgs, c->v_H.p, n_hyp, t2, c->v_count.p, c->stream);
                 verify_pairs_select(c->v_count.p, c->v_H.p, v.n, n_hyp, c->v_key.p, c->v_cur.p, c->stream);
-                verify_pairs_mask<Model>(c->v_src.p, c->v_dst.p, v.ent, v.active, v.n, la.mask_wgs, c->v_cur.p, t2, c->v_mask.p, c->v_n.p, c->stream);
+                verify_pairs_mask<Model>(c->v_src.p, c->v_dst.p, v.ent, v.active, v.n, la.mask_wgs, c->v_cur.p, t2, c->v_mask.p, c->v_n.p, nullptr, c->stream);
             }, [&] {
                 DLCO_HIP(hipMemcpyAsync(key.data(), c->v_key.p, (size_t)v.n * sizeof(uint64_t), hipMemcpyDeviceToHost, c->stream));
                 DLCO_HIP(hipMemcpyAsync(M_try.data(), c->v_cur.p, (size_t)v.n * 9 * sizeof(double), hipMemcpyDeviceToHost, c->stream));
@@ -837,7 +839,7 @@ int verify_pairs_model_call(dlco_desc_ctx *c, const float *src_xy_host, const fl
                 DLCO_HIP(hipMemcpyAsync(v.active, act.data(), (size_t)n_act * sizeof(vb::Active), hipMemcpyHostToDevice, c->stream));
                 DLCO_HIP(hipMemsetAsync(c->v_n.p, 0, (size_t)v.n * sizeof(int32_t), c->stream));
                 ms += timed_ms(c, ev, [&] {
-                    verify_pairs_mask<Model>(c->v_src.p, c->v_dst.p, v.ent, v.active, n_act, wgs, c->v_cur.p, t2, c->v_mask.p, c->v_n.p, c->stream);
+                    verify_pairs_mask<Model>(c->v_src.p, c->v_dst.p, v.ent, v.active, n_act, wgs, c->v_cur.p, t2, c->v_mask.p, c->v_n.p, nullptr, c->stream);
                 }, [&] {
                     DLCO_HIP(hipMemcpyAsync(trial.data(), c->v_mask.p, (size_t)v.matches, hipMemcpyDeviceToHost, c->stream));
                     DLCO_HIP(hipMemcpyAsync(cnt.data(), c->v_n.p, (size_t)v.n * sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
@@ -857,6 +859,112 @@ int verify_pairs_model_call(dlco_desc_ctx *c, const float *src_xy_host, const fl
         }
         c->last_ms = ms;
     });
+}
+
+// The same call on lists in device memory, read in place (8-byte aligned: the kernels read pairs of floats), with the refit
+// on the device: per launch of the plan the hypotheses, the scoring, the selection and the first mask, then `refine` rounds of
+// refit, mask and step queued without a host sync (an entry that has left the refit only reads its live flag), one download
+// of matrices, counts and keys and one sync.  The current mask of an entry lives where it ends up: in inlier_dev, or in
+// scratch when that is NULL.
+template <typename Model>
+int verify_pairs_device_call(dlco_desc_ctx *c, const float *src_xy_dev, const float *dst_xy_dev, const int64_t *moff, int64_t n_pairs, float threshold,
+                             int32_t n_hyp, uint64_t seed, int32_t refine, double *M_out, uint8_t *inlier_dev, int64_t *n_inliers, int32_t *best_hyp)
+{
+    if (!c || !M_out || !n_inliers || refine < 0 || refine > verify_rules::kMaxRefine || (uintptr_t)src_xy_dev % 8 != 0 || (uintptr_t)dst_xy_dev % 8 != 0 ||
+        !verify_pairs_args_ok<Model>(src_xy_dev, dst_xy_dev, moff, n_pairs, threshold, n_hyp))
+        return DLCO_ERR_INVALID;
+    return guarded(c, [&] {
+        namespace vr = verify_rules;
+        DLCO_HIP(hipSetDevice(c->device));
+        const double t2 = vr::threshold_sq(threshold);
+        const vb::Plan pl = vb::plan(moff, n_pairs, n_hyp, Model::kSample);
+        std::memset(M_out, 0, (size_t)n_pairs * 9 * sizeof(double));
+        for (int64_t p = 0; p < n_pairs; p++) { n_inliers[p] = 0; if (best_hyp) best_hyp[p] = -1; }
+        if (inlier_dev && moff[n_pairs] > 0) DLCO_HIP(hipMemsetAsync(inlier_dev, 0, (size_t)moff[n_pairs], c->stream));
+        const size_t ne = (size_t)pl.max_entries;
+        std::vector<uint64_t> key(ne);
+        std::vector<double> M(ne * 9);
+        std::vector<int32_t> cnt(ne);
+        std::vector<vb::Active> act(ne);
+        EventPair ev;
+        double ms = 0.0;
+        for (const vb::Launch &la : pl.launches) {
+            const size_t n = (size_t)la.n, ent_bytes = n * sizeof(vb::Entry);
+            c->v_H.alloc((size_t)la.hyps * 9); c->v_count.alloc((size_t)la.hyps);
+            c->v_key.alloc(n); c->v_cur.alloc(n * 9); c->v_try.alloc(n * 9); c->v_n.alloc(n); c->v_ntry.alloc(n); c->v_live.alloc(n);
+            c->v_trial.alloc((size_t)la.matches);
+            if (!inlier_dev) c->v_mask.alloc((size_t)la.matches);
+            c->v_plan.alloc(ent_bytes + n * sizeof(vb::Active));
+            const vb::Entry *ent_host = pl.entries.data() + la.e0;
+            const vb::Entry *ent = reinterpret_cast<const vb::Entry *>(c->v_plan.p);
+            const vb::Active *active = reinterpret_cast<const vb::Active *>(c->v_plan.p + ent_bytes);
+            const float *src = src_xy_dev + 2 * la.match0, *dst = dst_xy_dev + 2 * la.match0;
+            uint8_t *mask = inlier_dev ? inlier_dev + la.match0 : c->v_mask.p;
+            for (int64_t e = 0; e < la.n; e++) act[(size_t)e] = vb::Active{(int32_t)e, ent_host[e].mwg0};
+            DLCO_HIP(hipMemcpyAsync(c->v_plan.p, ent_host, ent_bytes, hipMemcpyHostToDevice, c->stream));
+            DLCO_HIP(hipMemcpyAsync(c->v_plan.p + ent_bytes, act.data(), n * sizeof(vb::Active), hipMemcpyHostToDevice, c->stream));
+            DLCO_HIP(hipMemsetAsync(c->v_count.p, 0, (size_t)la.hyps * sizeof(int32_t), c->stream));
+            DLCO_HIP(hipMemsetAsync(c->v_n.p, 0, n * sizeof(int32_t), c->stream));
+            DLCO_HIP(hipMemsetAsync(c->v_ntry.p, 0, n * sizeof(int32_t), c->stream));
+            ms += timed_ms(c, ev, [&] {
+                verify_pairs_hypotheses<Model>(src, dst, ent, la.n, seed, n_hyp, c->v_H.p, c->stream);
+                verify_pairs_score<Model>(src, dst, ent, la.n, la.score_wgs, c->v_H.p, n_hyp, t2, c->v_count.p, c->stream);
+                verify_pairs_select(c->v_count.p, c->v_H.p, la.n, n_hyp, c->v_key.p, c->v_cur.p, c->stream);
+                verify_pairs_mask<Model>(src, dst, ent, active, la.n, la.mask_wgs, c->v_cur.p, t2, mask, c->v_n.p, nullptr, c->stream);
+                if (refine > 0) verify_pairs_live(c->v_key.p, la.n, c->v_live.p, c->stream);
+                for (int32_t k = 0; k < refine; k++) {
+                    verify_pairs_refit<Model>(src, dst, ent, la.n, mask, c->v_live.p, c->v_try.p, c->stream);
+                    verify_pairs_mask<Model>(src, dst, ent, active, la.n, la.mask_wgs, c->v_try.p, t2, c->v_trial.p, c->v_ntry.p, c->v_live.p, c->stream);
+                    verify_pairs_step(ent, la.n, c->v_try.p, c->v_trial.p, c->v_ntry.p, c->v_cur.p, mask, c->v_n.p, c->v_live.p, c->stream);
+                }
+            }, [&] {
+                DLCO_HIP(hipMemcpyAsync(key.data(), c->v_key.p, n * sizeof(uint64_t), hipMemcpyDeviceToHost, c->stream));
+                DLCO_HIP(hipMemcpyAsync(M.data(), c->v_cur.p, n * 9 * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+                DLCO_HIP(hipMemcpyAsync(cnt.data(), c->v_n.p, n * sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
+            });
+            for (int64_t e = 0; e < la.n; e++) {
+                if (vr::key_count(key[(size_t)e]) == 0) continue;
+                const size_t p = (size_t)ent_host[e].pair;
+                std::memcpy(M_out + 9 * p, M.data() + 9 * (size_t)e, 9 * sizeof(double));
+                n_inliers[p] = cnt[(size_t)e];
+                if (best_hyp) best_hyp[p] = vr::key_hyp(key[(size_t)e]);
+            }
+        }
+        if (pl.launches.empty()) sync(c);                   // the memset of the mask
+        c->last_ms = ms;
+    });
+}
+
+// one round of the refit kernel on masks of the caller's: for tests and tools
+template <typename Model>
+void verify_pairs_refit_round_call(dlco_desc_ctx *c, const float *src_host, const float *dst_host, const int64_t *moff, int64_t n_pairs,
+                                   const uint8_t *mask_host, double *M_out, uint8_t *ok)
+{
+    DLCO_HIP(hipSetDevice(c->device));
+    const vb::Plan pl = vb::plan(moff, n_pairs, 1, Model::kSample);
+    std::memset(M_out, 0, (size_t)n_pairs * 9 * sizeof(double));
+    std::memset(ok, 0, (size_t)n_pairs);
+    std::vector<double> M((size_t)pl.max_entries * 9);
+    std::vector<uint8_t> live((size_t)pl.max_entries);
+    EventPair ev;
+    double ms = 0.0;
+    for (const vb::Launch &la : pl.launches) {
+        const VerifyLaunch v = verify_pairs_upload(c, pl, la, src_host, dst_host, 1);
+        const size_t n = (size_t)la.n;
+        c->v_try.alloc(n * 9); c->v_live.alloc(n);
+        DLCO_HIP(hipMemcpyAsync(c->v_mask.p, mask_host + la.match0, (size_t)la.matches, hipMemcpyHostToDevice, c->stream));
+        DLCO_HIP(hipMemsetAsync(c->v_live.p, 1, n, c->stream));
+        ms += timed_ms(c, ev, [&] { verify_pairs_refit<Model>(c->v_src.p, c->v_dst.p, v.ent, v.n, c->v_mask.p, c->v_live.p, c->v_try.p, c->stream); }, [&] {
+            DLCO_HIP(hipMemcpyAsync(M.data(), c->v_try.p, n * 9 * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+            DLCO_HIP(hipMemcpyAsync(live.data(), c->v_live.p, n, hipMemcpyDeviceToHost, c->stream));
+        });
+        for (size_t e = 0; e < n; e++) {
+            const size_t p = (size_t)v.ent_host[e].pair;
+            ok[p] = live[e];
+            std::memcpy(M_out + 9 * p, M.data() + 9 * e, 9 * sizeof(double));
+        }
+    }
+    c->last_ms = ms;
 }
 }  // namespace
 
@@ -1886,6 +1994,36 @@ int dlco_desc_verify_pairs_fundamental_hypotheses(dlco_desc_ctx *c, const float 
                                                   int32_t *count_host)
 {
     return verify_pairs_hypotheses_call<Fundamental>(c, src_xy_host, dst_xy_host, moff, n_pairs, threshold, n_hyp, seed, F_all_host, count_host);
+}
+
+// the same on lists in device memory, as dlco_desc_select_pairs_device writes them, with the refit rounds on the device
+int dlco_desc_verify_pairs_homography_device(dlco_desc_ctx *c, const float *src_xy_dev, const float *dst_xy_dev, const int64_t *moff, int64_t n_pairs,
+                                             float threshold, int32_t n_hyp, uint64_t seed, int32_t refine, double *H_out, uint8_t *inlier_dev,
+                                             int64_t *n_inliers, int32_t *best_hyp)
+{
+    return verify_pairs_device_call<Homography>(c, src_xy_dev, dst_xy_dev, moff, n_pairs, threshold, n_hyp, seed, refine, H_out, inlier_dev, n_inliers,
+                                                best_hyp);
+}
+
+int dlco_desc_verify_pairs_fundamental_device(dlco_desc_ctx *c, const float *src_xy_dev, const float *dst_xy_dev, const int64_t *moff, int64_t n_pairs,
+                                              float threshold, int32_t n_hyp, uint64_t seed, int32_t refine, double *F_out, uint8_t *inlier_dev,
+                                              int64_t *n_inliers, int32_t *best_hyp)
+{
+    return verify_pairs_device_call<Fundamental>(c, src_xy_dev, dst_xy_dev, moff, n_pairs, threshold, n_hyp, seed, refine, F_out, inlier_dev, n_inliers,
+                                                 best_hyp);
+}
+
+// one round of the refit kernel on the caller's masks: M_out [n_pairs][9] and ok [n_pairs], zero where the round is rejected
+int dlco_desc_verify_pairs_refit_round(dlco_desc_ctx *c, const float *src_xy_host, const float *dst_xy_host, const int64_t *moff, int64_t n_pairs,
+                                       const uint8_t *mask_host, int32_t fundamental, double *M_out, uint8_t *ok)
+{
+    if (!c || !src_xy_host || !dst_xy_host || !mask_host || !M_out || !ok || !verify_batch::offsets_ok(moff, n_pairs) ||
+        (fundamental != 0 && fundamental != 1))
+        return DLCO_ERR_INVALID;
+    return guarded(c, [&] {
+        if (fundamental) verify_pairs_refit_round_call<Fundamental>(c, src_xy_host, dst_xy_host, moff, n_pairs, mask_host, M_out, ok);
+        else verify_pairs_refit_round_call<Homography>(c, src_xy_host, dst_xy_host, moff, n_pairs, mask_host, M_out, ok);
+    });
 }
 
 // the plan only: the launch of every pair, -1 for a pair that launches nothing; host only

@@ -627,7 +627,17 @@ void verify_pairs_score(const float *src, const float *dst, const verify_batch::
 void verify_pairs_select(const int32_t *count, const double *M_all, int64_t n_ent, int n_hyp, uint64_t *best, double *M_cur, hipStream_t s);
 template <typename Model>
 void verify_pairs_mask(const float *src, const float *dst, const verify_batch::Entry *ent, const verify_batch::Active *active, int64_t n_active,
-                       int64_t mask_wgs, const double *M_cur, double t2, uint8_t *mask, int32_t *n, hipStream_t s);
+                       int64_t mask_wgs, const double *M_cur, double t2, uint8_t *mask, int32_t *n, const uint8_t *live, hipStream_t s);
+// The refit on the device, live [n_ent] saying which entries still refine: live from the selection keys; a round's matrices
+// M_try [.][9] from the entries' matches under mask (a rejected round clears live [e]); the round against the model, which it
+// replaces when its count n_try [e] is no smaller (n_try [e] is zeroed, live [e] cleared when the entry's refit ends).  The
+// mask launch in between takes live as its last argument; the host forms pass NULL there
+void verify_pairs_live(const uint64_t *best, int64_t n_ent, uint8_t *live, hipStream_t s);
+template <typename Model>
+void verify_pairs_refit(const float *src, const float *dst, const verify_batch::Entry *ent, int64_t n_ent, const uint8_t *mask, uint8_t *live,
+                        double *M_try, hipStream_t s);
+void verify_pairs_step(const verify_batch::Entry *ent, int64_t n_ent, const double *M_try, const uint8_t *trial, int32_t *n_try, double *M_cur,
+                       uint8_t *mask, int32_t *count, uint8_t *live, hipStream_t s);
 
 // selecting matches (kernels_select.hip; the rule is select_rules.hpp): the steps of a dlco_desc_select_pairs* call over the
 // R >= 1 rows of a batched answer idx, sqdist [R][2], pairs [n_pairs] = select_rules::pair_records and every table in device

@@ -6,12 +6,13 @@
 // header, no device, no I/O.
 //
 // This is NOT cv::findFundamentalMat, which nothing here can run or pin, and no parity with it is claimed.  It is a rule of
-// this library: every step on the device path is IEEE double + - x /, one rounding each, no fused multiply-add, no sqrt and
-// no transcendental; counts are integers.  The refit on the host adds sqrt.  So the host, the kernels and a numpy
-// restatement agree in every bit.  The functions below switch contraction off themselves (VERIFY_RULES_NO_FMA).
+// this library: every step is IEEE double + - x /, one rounding each, no fused multiply-add and no transcendental; counts
+// are integers.  The refit adds sqrt, correctly rounded on the host and on the device alike.  So the host, the kernels and a
+// numpy restatement agree in every bit.  The functions below switch contraction off themselves (VERIFY_RULES_NO_FMA).
 //
-// Out of scope: a device-memory form; a seven-point solver; an essential matrix; a choice between a homography and F; an
+// Out of scope: a seven-point solver; an essential matrix; a choice between a homography and F; an
 // adaptive hypothesis count.  (The inlier test as the predicate of guided matching: guided_epipolar_rules.hpp.)
+// In scope since: a device-memory form, dlco_desc_verify_pairs_fundamental_device, whose refit rounds run in refit_pairs_kernel.
 //
 // Degeneracy, documented and not detected.  Matches related by a homography (a plane, a camera that only rotates, a shifted
 // image) satisfy a three-dimensional family of F.  The pivot floor below makes an exactly degenerate sample invalid; a nearly
@@ -52,8 +53,8 @@
 //
 // Selection.  verify_rules::select_key, unchanged; a best count of 0: no model.
 //
-// Refit, on the host only (refit_round; a round's acceptance is verify_rules::refit_step, the loop the library's lockstep one
-// and, in the CPU frame verify_host, verify_rules::refit_rounds).  At most `refine` rounds; a round runs on the
+// Refit (refit_round on the host, refit_pairs_kernel on the device from the same functions; a round's acceptance is
+// verify_rules::refit_step, the loop the library's lockstep one and, in the CPU frame verify_host, verify_rules::refit_rounds).  At most `refine` rounds; a round runs on the
 // inliers of the current model in ascending match index and is rejected when there are fewer than 8:
 //   verify_rules::hartley on each side; a normalised point is ((x - cx) s, (y - cy) s).
 //   N = sum a a^T, 9 x 9, a the row above of the normalised match, N[p][q] = N[p][q] + a[p] a[q] in index order.
@@ -298,10 +299,31 @@ VERIFY_RULES_HD inline bool inlier(const double F[9], double x, double y, double
     return S > 0.0 && e * e <= t2 * S;
 }
 
-// ---- the rule on the host: what the kernels must reproduce ---------------------------------------------------------------
+// ---- the pieces of a refit round that the host below and refit_pairs_kernel (kernels_verify.hip) share: everything but the
+// sums, which both walk over the inliers in ascending match index.  Whatever is indexed at run time comes through a pointer,
+// so that the kernel can keep it in LDS ---------------------------------------------------------------------------------------
+// the row a [9] of a normalised match (x, y) -> (u, v)
+VERIFY_RULES_HD inline void refit_row(double x, double y, double u, double v, double *a)
+{
+    VERIFY_RULES_NO_FMA
+    a[0] = u * x; a[1] = u * y; a[2] = u; a[3] = v * x; a[4] = v * y; a[5] = v; a[6] = x; a[7] = y; a[8] = 1.0;
+}
+
+// one term of N[p][q]: a = a[p], b = a[q]
+VERIFY_RULES_HD inline double refit_add(double acc, double a, double b)
+{
+    VERIFY_RULES_NO_FMA
+    return acc + a * b;
+}
+
+// the sums of a round as refit_pairs_kernel spreads them over lanes (verify_rules::Terms): l < 81 is N[l / 9][l % 9]
+constexpr int kRefitRow = 9, kRefitSums = 81;
+VERIFY_RULES_HD inline vr::Terms refit_terms(int l) { return l < kRefitSums ? vr::Terms{l / 9, l % 9, 0, 0} : vr::Terms{0, 0, 0, 0}; }
+VERIFY_RULES_HD inline double refit_add(double acc, const double *row, vr::Terms t) { return refit_add(acc, row[t.a], row[t.b]); }
+
 // cyclic Jacobi of the symmetric N [n][n] (row-major, n <= 9): N's diagonal becomes the eigenvalues, V [n][n] the eigenvectors
 // in its columns; returns the number of sweeps that rotated
-inline int jacobi(double *N, int n, double *V)
+VERIFY_RULES_HD inline int jacobi(double *N, int n, double *V)
 {
     VERIFY_RULES_NO_FMA
     for (int i = 0; i < n; i++)
@@ -315,9 +337,9 @@ inline int jacobi(double *N, int n, double *V)
                 if (a == 0.0) continue;
                 rotated++;
                 const double theta = (N[n * q + q] - N[n * p + p]) / (2.0 * a);
-                const double den = std::fabs(theta) + std::sqrt(theta * theta + 1.0);
+                const double den = __builtin_fabs(theta) + __builtin_sqrt(theta * theta + 1.0);
                 const double t = (theta < 0.0 ? -1.0 : 1.0) / den;
-                const double c = 1.0 / std::sqrt(t * t + 1.0), s = t * c;
+                const double c = 1.0 / __builtin_sqrt(t * t + 1.0), s = t * c;
                 N[n * p + p] = N[n * p + p] - t * a;
                 N[n * q + q] = N[n * q + q] + t * a;
                 N[n * p + q] = N[n * q + p] = 0.0;
@@ -338,10 +360,10 @@ inline int jacobi(double *N, int n, double *V)
     return sweeps;
 }
 
-// vec [n] = the eigenvector of the smallest eigenvalue of the symmetric N [n][n], which is overwritten (ties: lowest index)
-inline void smallest_eigenvector(double *N, int n, double *vec)
+// vec [n] = the eigenvector of the smallest eigenvalue of the symmetric N [n][n], which is overwritten (ties: lowest index);
+// V [n][n] is scratch
+VERIFY_RULES_HD inline void smallest_eigenvector(double *N, int n, double *V, double *vec)
 {
-    double V[81];
     jacobi(N, n, V);
     int best = 0;
     for (int i = 1; i < n; i++)
@@ -349,35 +371,60 @@ inline void smallest_eigenvector(double *N, int n, double *vec)
     for (int j = 0; j < n; j++) vec[j] = V[n * j + best];
 }
 
+constexpr int kRefitWork = 21;                             // doubles of refit_solve's w: Fn [9], G [9], v [3]
+
+// F' of the summed N [81], which is overwritten: the smallest eigenvector, the rank-2 step, finish; V [81] and w [kRefitWork]
+// are scratch; false: F' is not finite or is zero
+VERIFY_RULES_HD inline bool refit_solve(double *N, double *V, double *w, double cxs, double cys, double ss, double cxd, double cyd, double sd,
+                                        double F_out[9])
+{
+    VERIFY_RULES_NO_FMA
+    double *Fn = w, *G = w + 9, *v = w + 18;
+    double FnT[9], Fr[9];
+    smallest_eigenvector(N, 9, V, Fn);
+    EPIPOLAR_RULES_UNROLL
+    for (int i = 0; i < 3; i++) {
+        EPIPOLAR_RULES_UNROLL
+        for (int j = 0; j < 3; j++) FnT[3 * i + j] = Fn[3 * j + i];
+    }
+    EPIPOLAR_RULES_UNROLL
+    for (int i = 0; i < 9; i++) Fr[i] = Fn[i];
+    vr::mul3(FnT, Fr, G);
+    smallest_eigenvector(G, 3, V, v);
+    EPIPOLAR_RULES_UNROLL
+    for (int i = 0; i < 3; i++) {
+        const double d = (Fr[3 * i] * v[0] + Fr[3 * i + 1] * v[1]) + Fr[3 * i + 2] * v[2];
+        EPIPOLAR_RULES_UNROLL
+        for (int j = 0; j < 3; j++) Fr[3 * i + j] = Fr[3 * i + j] - d * v[j];
+    }
+    return finish(Fr, ss, -(ss * cxs), -(ss * cys), sd, -(sd * cxd), -(sd * cyd), F_out);
+}
+
+// ---- the rule on the host: what the kernels must reproduce ---------------------------------------------------------------
+inline void smallest_eigenvector(double *N, int n, double *vec)
+{
+    double V[81];
+    smallest_eigenvector(N, n, V, vec);
+}
+
 // one round of the refit on the inliers of mask: F' in F_out; false: rejected, F_out is undefined
 inline bool refit_round(const float *src, const float *dst, int64_t m, const uint8_t *mask, double F_out[9])
 {
-    VERIFY_RULES_NO_FMA
     int64_t n = 0;
     for (int64_t i = 0; i < m; i++) n += mask[i] ? 1 : 0;
     if (n < kSample) return false;
     double cxs, cys, ss, cxd, cyd, sd;
     if (!vr::hartley(src, mask, m, cxs, cys, ss) || !vr::hartley(dst, mask, m, cxd, cyd, sd)) return false;
-    double N[81] = {};
+    double N[81] = {}, V[81], w[kRefitWork];
     for (int64_t i = 0; i < m; i++) {
         if (!mask[i]) continue;
-        const double x = ((double)src[2 * i] - cxs) * ss, y = ((double)src[2 * i + 1] - cys) * ss;
-        const double u = ((double)dst[2 * i] - cxd) * sd, v = ((double)dst[2 * i + 1] - cyd) * sd;
-        const double a[9] = {u * x, u * y, u, v * x, v * y, v, x, y, 1.0};
+        double a[9];
+        refit_row(vr::normalised((double)src[2 * i], cxs, ss), vr::normalised((double)src[2 * i + 1], cys, ss), vr::normalised((double)dst[2 * i], cxd, sd),
+                  vr::normalised((double)dst[2 * i + 1], cyd, sd), a);
         for (int p = 0; p < 9; p++)
-            for (int q = 0; q < 9; q++) N[9 * p + q] = N[9 * p + q] + a[p] * a[q];
+            for (int q = 0; q < 9; q++) N[9 * p + q] = refit_add(N[9 * p + q], a[p], a[q]);
     }
-    double Fn[9], FnT[9], G[9], v[3];
-    smallest_eigenvector(N, 9, Fn);
-    for (int i = 0; i < 3; i++)
-        for (int j = 0; j < 3; j++) FnT[3 * i + j] = Fn[3 * j + i];
-    vr::mul3(FnT, Fn, G);
-    smallest_eigenvector(G, 3, v);
-    for (int i = 0; i < 3; i++) {
-        const double w = (Fn[3 * i] * v[0] + Fn[3 * i + 1] * v[1]) + Fn[3 * i + 2] * v[2];
-        for (int j = 0; j < 3; j++) Fn[3 * i + j] = Fn[3 * i + j] - w * v[j];
-    }
-    return finish(Fn, ss, -(ss * cxs), -(ss * cys), sd, -(sd * cxd), -(sd * cyd), F_out);
+    return refit_solve(N, V, w, cxs, cys, ss, cxd, cyd, sd, F_out);
 }
 
 // The fundamental matrix as the frame of verify_rules.hpp (all_hypotheses, count_inliers, verify_host) and the kernels
@@ -395,6 +442,17 @@ struct Fundamental {
     static bool refit_round(const float *src, const float *dst, int64_t m, const uint8_t *mask, double F_out[9])
     {
         return epipolar_rules::refit_round(src, dst, m, mask, F_out);
+    }
+    // the round as refit_pairs_kernel takes a model (verify_rules::Homography says what each is): work = N [81] summed, V [81], w
+    static constexpr int kRefitRow = epipolar_rules::kRefitRow, kRefitSums = epipolar_rules::kRefitSums, kRefitWork = 81 + 81 + epipolar_rules::kRefitWork;
+    VERIFY_RULES_HD static void refit_row(double x, double y, double u, double v, double *a) { epipolar_rules::refit_row(x, y, u, v, a); }
+    VERIFY_RULES_HD static vr::Terms refit_terms(int l) { return epipolar_rules::refit_terms(l); }
+    VERIFY_RULES_HD static double refit_add(double acc, const double *a, vr::Terms t) { return epipolar_rules::refit_add(acc, a, t); }
+    VERIFY_RULES_HD static bool refit_few(int n) { return n < kSample; }
+    VERIFY_RULES_HD static bool refit_solve(double *work, double cxs, double cys, double ss, double cxd, double cyd, double sd, double, double,
+                                            double F_out[9])
+    {
+        return epipolar_rules::refit_solve(work, work + 81, work + 162, cxs, cys, ss, cxd, cyd, sd, F_out);
     }
 };
 

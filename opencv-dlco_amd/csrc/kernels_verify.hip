@@ -131,10 +131,11 @@ __global__ __launch_bounds__(VSEL) void select_pairs_kernel(const int *count, co
 template <typename Model>
 __global__ __launch_bounds__(VTH) void mask_pairs_kernel(const float2 *src, const float2 *dst, const vb::Entry *__restrict__ ent,
                                                          const vb::Active *__restrict__ active, int n_active, const double *M_cur, double t2,
-                                                         uint8_t *mask, int *count)
+                                                         uint8_t *mask, int *count, const uint8_t *live)
 {
     const long wg = blockIdx.x;
     const vb::Active a = active[pairs_item_of(active, n_active, wg, [](const vb::Active &x) { return x.wg0; })];
+    if (live && !live[a.entry]) return;                     // the same for the whole workgroup
     const vb::Entry en = ent[a.entry];
     const long i = (wg - a.wg0) * VTH + threadIdx.x;
     double M[9];
@@ -147,6 +148,136 @@ __global__ __launch_bounds__(VTH) void mask_pairs_kernel(const float2 *src, cons
     }
     const int n = __popcll(__ballot(in));
     if ((threadIdx.x & 63) == 0 && n > 0) atomicAdd(&count[a.entry], n);
+}
+
+// ---- the refit round on the device ---------------------------------------------------------------------------------------------
+constexpr int kRefitLanes = vr::kRefitChunk;                // a lane stages one match of the chunk
+static_assert(kRefitLanes % 64 == 0, "whole waves");
+
+__global__ __launch_bounds__(VTH) void live_pairs_kernel(const unsigned long long *best, int n_ent, uint8_t *live)
+{
+    const int e = blockIdx.x * VTH + threadIdx.x;
+    if (e < n_ent) live[e] = vr::key_count(best[e]) > 0 ? 1 : 0;
+}
+
+template <typename Model>
+__global__ __launch_bounds__(kRefitLanes) void refit_pairs_kernel(const float2 *src, const float2 *dst, const vb::Entry *__restrict__ ent,
+                                                                  const uint8_t *mask, uint8_t *live, double *M_try)
+{
+    constexpr int C = vr::kRefitChunk;
+    static_assert(Model::kRefitSums <= kRefitLanes && Model::kRefitSums <= Model::kRefitWork, "a lane for every sum, and the sums are the head of work");
+    __shared__ double rows[C * Model::kRefitRow];                   // a chunk: (x, y, u, v), then the two distances, then the model's rows
+    __shared__ double work[Model::kRefitWork];
+    __shared__ double par[6];                               // cxs, cys, cxd, cyd, then the mean distances ds, dd
+    __shared__ uint8_t in[C];
+    const int e = blockIdx.x, l = threadIdx.x;
+    if (!live[e]) return;                                   // the same for the whole workgroup
+    const vb::Entry en = ent[e];
+    const float2 *s2 = src + en.m0, *d2 = dst + en.m0;
+    const uint8_t *mk = mask + en.m0;
+    // the coordinate sums: lane k < 4 owns sum_x, sum_y of src and of dst; every lane counts the inliers
+    int n = 0, first = -1;
+    double sum = 0.0;
+    for (int i0 = 0; i0 < en.m; i0 += C) {
+        const int cnt = min(C, en.m - i0);
+        if (l < cnt) {
+            const float2 s = s2[i0 + l], d = d2[i0 + l];
+            rows[4 * l] = (double)s.x; rows[4 * l + 1] = (double)s.y; rows[4 * l + 2] = (double)d.x; rows[4 * l + 3] = (double)d.y;
+            in[l] = mk[i0 + l];
+        }
+        __syncthreads();
+        for (int j = 0; j < cnt; j++) {
+            if (!in[j]) continue;
+            first = first < 0 ? i0 + j : first;
+            n++;
+            sum = sum + rows[4 * j + (l & 3)];
+        }
+        __syncthreads();
+    }
+    if (l < 4) par[l] = sum / (double)n;
+    __syncthreads();
+    const double cxs = par[0], cys = par[1], cxd = par[2], cyd = par[3];
+    // the distance sums: the workgroup forms the square roots of a chunk, lane k < 2 adds those of src or dst in order
+    sum = 0.0;
+    for (int i0 = 0; i0 < en.m; i0 += C) {
+        const int cnt = min(C, en.m - i0);
+        if (l < cnt) {
+            const float2 s = s2[i0 + l], d = d2[i0 + l];
+            rows[2 * l] = vr::centred_length((double)s.x, (double)s.y, cxs, cys);
+            rows[2 * l + 1] = vr::centred_length((double)d.x, (double)d.y, cxd, cyd);
+            in[l] = mk[i0 + l];
+        }
+        __syncthreads();
+        for (int j = 0; j < cnt; j++) {
+            if (!in[j]) continue;
+            sum = sum + rows[2 * j + (l & 1)];
+        }
+        __syncthreads();
+    }
+    if (l < 2) par[4 + l] = sum / (double)n;
+    __syncthreads();
+    double ss = 0.0, sd = 0.0;
+    bool ok = !Model::refit_few(n);
+    ok = vr::hartley_scale(par[4], ss) && ok;
+    ok = vr::hartley_scale(par[5], sd) && ok;
+    if (!ok) {                                              // uniform: every lane holds the same n and reads the same par
+        if (l == 0) live[e] = 0;
+        if (l < 9) M_try[9 * (long)e + l] = 0.0;
+        return;
+    }
+    // the sums of N (and r): the workgroup forms the rows of a chunk, lane l < kSums adds its products in order
+    const vr::Terms t = Model::refit_terms(l);
+    sum = 0.0;
+    for (int i0 = 0; i0 < en.m; i0 += C) {
+        const int cnt = min(C, en.m - i0);
+        if (l < cnt) {
+            const float2 s = s2[i0 + l], d = d2[i0 + l];
+            Model::refit_row(vr::normalised((double)s.x, cxs, ss), vr::normalised((double)s.y, cys, ss), vr::normalised((double)d.x, cxd, sd),
+                             vr::normalised((double)d.y, cyd, sd), rows + Model::kRefitRow * l);
+            in[l] = mk[i0 + l];
+        }
+        __syncthreads();
+        for (int j = 0; j < cnt; j++) {
+            if (!in[j]) continue;
+            sum = Model::refit_add(sum, rows + Model::kRefitRow * j, t);
+        }
+        __syncthreads();
+    }
+    if (l < Model::kRefitSums) work[l] = sum;
+    __syncthreads();
+    if (l == 0) {
+        const float2 f = s2[first];                         // n > 0 here: a mean distance above 0 has an inlier behind it
+        double M[9];
+        const bool good = Model::refit_solve(work, cxs, cys, ss, cxd, cyd, sd, (double)f.x, (double)f.y, M);
+        for (int i = 0; i < 9; i++) M_try[9 * (long)e + i] = good ? M[i] : 0.0;
+        if (!good) live[e] = 0;
+    }
+}
+
+// verify_rules::refit_step of every live entry: (M_try, trial, n_try) of the round against (M_cur, mask, count)
+__global__ __launch_bounds__(VTH) void step_pairs_kernel(const vb::Entry *__restrict__ ent, const double *M_try, const uint8_t *trial, int *n_try,
+                                                         double *M_cur, uint8_t *mask, int *count, uint8_t *live)
+{
+    const int e = blockIdx.x;
+    const bool alive = live[e] != 0;
+    const int c = n_try[e], have = count[e];
+    __syncthreads();                                        // every lane has read what lane 0 writes below
+    if (!alive) return;
+    if (threadIdx.x == 0) n_try[e] = 0;                     // the next round's mask launch adds into it
+    if (c < have) {
+        if (threadIdx.x == 0) live[e] = 0;
+        return;
+    }
+    const vb::Entry en = ent[e];
+    bool changed = false;
+    for (int i = threadIdx.x; i < en.m; i += VTH) {
+        const uint8_t b = trial[en.m0 + i];
+        changed = changed || b != mask[en.m0 + i];
+        mask[en.m0 + i] = b;
+    }
+    const int any = __syncthreads_or(changed ? 1 : 0);
+    if (threadIdx.x < 9) M_cur[9 * (long)e + threadIdx.x] = M_try[9 * (long)e + threadIdx.x];
+    if (threadIdx.x == 0) { count[e] = c; live[e] = any ? 1 : 0; }
 }
 
 }  // namespace
@@ -186,13 +317,41 @@ void verify_pairs_select(const int32_t *count, const double *M_all, int64_t n_en
 }
 
 // for the entries of active [n_active] (wgs workgroups in all): the mask of M_cur [entry] at the entry's matches and
-// n [entry] += its inliers; the caller zeroes n
+// n [entry] += its inliers; the caller zeroes n.  live (may be NULL: all) [n_ent]: an entry with live [entry] = 0 is left alone
 template <typename Model>
 void verify_pairs_mask(const float *src, const float *dst, const verify_batch::Entry *ent, const verify_batch::Active *active, int64_t n_active,
-                       int64_t wgs, const double *M_cur, double t2, uint8_t *mask, int32_t *n, hipStream_t s)
+                       int64_t wgs, const double *M_cur, double t2, uint8_t *mask, int32_t *n, const uint8_t *live, hipStream_t s)
 {
     hipLaunchKernelGGL(mask_pairs_kernel<Model>, dim3((unsigned)wgs), dim3(VTH), 0, s, reinterpret_cast<const float2 *>(src),
-                       reinterpret_cast<const float2 *>(dst), ent, active, (int)n_active, M_cur, t2, mask, n);
+                       reinterpret_cast<const float2 *>(dst), ent, active, (int)n_active, M_cur, t2, mask, n, live);
+    DLCO_HIP(hipGetLastError());
+}
+
+// live [n_ent] = the selection found a model for the entry (best [e] has a count above 0)
+void verify_pairs_live(const uint64_t *best, int64_t n_ent, uint8_t *live, hipStream_t s)
+{
+    hipLaunchKernelGGL(live_pairs_kernel, dim3((unsigned)((n_ent + VTH - 1) / VTH)), dim3(VTH), 0, s, reinterpret_cast<const unsigned long long *>(best),
+                       (int)n_ent, live);
+    DLCO_HIP(hipGetLastError());
+}
+
+// one round of the refit for the entries with live [e] != 0: M_try [e] = Model::refit_round of the entry's matches under
+// mask; a rejected round clears live [e] and zeroes M_try [e]
+template <typename Model>
+void verify_pairs_refit(const float *src, const float *dst, const verify_batch::Entry *ent, int64_t n_ent, const uint8_t *mask, uint8_t *live,
+                        double *M_try, hipStream_t s)
+{
+    hipLaunchKernelGGL(refit_pairs_kernel<Model>, dim3((unsigned)n_ent), dim3(kRefitLanes), 0, s, reinterpret_cast<const float2 *>(src),
+                       reinterpret_cast<const float2 *>(dst), ent, mask, live, M_try);
+    DLCO_HIP(hipGetLastError());
+}
+
+// verify_rules::refit_step for the live entries: the round (M_try, trial, n_try) meets the model (M_cur, mask, count); n_try
+// [e] is zeroed for the next round, live [e] cleared when the entry's refit ends
+void verify_pairs_step(const verify_batch::Entry *ent, int64_t n_ent, const double *M_try, const uint8_t *trial, int32_t *n_try, double *M_cur,
+                       uint8_t *mask, int32_t *count, uint8_t *live, hipStream_t s)
+{
+    hipLaunchKernelGGL(step_pairs_kernel, dim3((unsigned)n_ent), dim3(VTH), 0, s, ent, M_try, trial, n_try, M_cur, mask, count, live);
     DLCO_HIP(hipGetLastError());
 }
 
@@ -201,7 +360,9 @@ void verify_pairs_mask(const float *src, const float *dst, const verify_batch::E
     template void verify_pairs_score<Model>(const float *, const float *, const verify_batch::Entry *, int64_t, int64_t, const double *, int, double,      \
                                             int32_t *, hipStream_t);                                                                                       \
     template void verify_pairs_mask<Model>(const float *, const float *, const verify_batch::Entry *, const verify_batch::Active *, int64_t, int64_t,      \
-                                           const double *, double, uint8_t *, int32_t *, hipStream_t);
+                                           const double *, double, uint8_t *, int32_t *, const uint8_t *, hipStream_t);                                    \
+    template void verify_pairs_refit<Model>(const float *, const float *, const verify_batch::Entry *, int64_t, const uint8_t *, uint8_t *, double *,     \
+                                            hipStream_t);
 DLCO_VERIFY_MODEL(verify_rules::Homography)
 DLCO_VERIFY_MODEL(epipolar_rules::Fundamental)
 #undef DLCO_VERIFY_MODEL

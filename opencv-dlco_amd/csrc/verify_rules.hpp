@@ -4,13 +4,14 @@
 // (kernels_verify.hip) and the CPU tests (tests/shim/verify_rules_shim.cpp).  Plain C++: no HIP header, no device, no I/O.
 //
 // This is NOT cv::findHomography, which nothing here can run or pin, and no parity with it is claimed.  It is a rule of
-// this library: every step on the device path is IEEE double + - x, one rounding each, no fused multiply-add and no
-// division; counts are integers.  So the host, the kernels and a numpy restatement agree in every bit.  The scalar
+// this library: every step is IEEE double + - x, one rounding each, no fused multiply-add; counts are integers.  Up to
+// the first mask there is no division; the refit adds / and sqrt, correctly rounded on the host and on the device alike.  So the host, the kernels and a numpy restatement agree in every bit.  The scalar
 // functions below switch contraction off themselves (VERIFY_RULES_NO_FMA); a compiler that does not know the pragma
 // builds this header with -ffp-contract=off.
 //
-// Out of scope: a device-memory form (the match list is filtered on the host); an essential matrix (the fundamental matrix
+// Out of scope: an essential matrix (the fundamental matrix
 // is epipolar_rules.hpp); symmetric transfer error; an adaptive hypothesis count.
+// In scope since: a device-memory form, dlco_desc_verify_pairs_homography_device, whose refit rounds run in refit_pairs_kernel.
 //
 // Inputs.  src [m][2] and dst [m][2] float, widened to double; 4 <= m < 2^31.  Expected finite with |x|, |y| <= 2^20;
 // nothing is checked: a non-finite coordinate fails every comparison below, so its match is never an inlier and a sample
@@ -43,8 +44,9 @@
 // Selection.  count[h] = inliers of hypothesis h (0 for an invalid one: W = 0 everywhere).  The best has the largest count,
 // ties go to the smallest h: the maximum of the key (count << 32) | (0xFFFFFFFF - h).  A best count of 0: no model.
 //
-// Refit, on the host only (refit_round; a round's acceptance is refit_step, the loop the library's lockstep one and, in the
-// CPU frame verify_host, refit_rounds).  At most `refine` rounds; a round runs on the inliers of the current model in
+// Refit (refit_round on the host, refit_pairs_kernel on the device from the same functions; a round's acceptance is
+// refit_step, step_pairs_kernel on the device; the loop is the library's lockstep one and, in the CPU frame verify_host,
+// refit_rounds).  At most `refine` rounds; a round runs on the inliers of the current model in
 // ascending match index:
 //   Hartley normalisation of each side: centroid c = (sum x / n, sum y / n), d = (sum sqrt(dx dx + dy dy)) / n with
 //   dx = x - cx, s = sqrt(2) / d, sums in index order; a normalised point is ((x - cx) s, (y - cy) s).
@@ -79,6 +81,7 @@
 namespace verify_rules {
 
 constexpr int kScoreChunk = 256;               // matches a workgroup of the scoring kernel stages in LDS at a time
+constexpr int kRefitChunk = 128;               // matches a workgroup of the refit kernel stages in LDS at a time
 constexpr int kMaxDraws = 16;
 constexpr int32_t kMaxHyp = 1 << 20;
 constexpr int32_t kMaxRefine = 8;
@@ -253,23 +256,91 @@ inline uint64_t select(const int32_t *count, int32_t n_hyp)
     return best;
 }
 
-// Hartley normalisation of the masked points: centroid and scale; false: the mean distance is 0 or not finite
-inline bool hartley(const float *pts, const uint8_t *mask, int64_t m, double &cx, double &cy, double &s)
+// ---- the pieces of a refit round that the host below and refit_pairs_kernel (kernels_verify.hip) share: everything but the
+// sums, which both walk over the inliers in ascending match index -------------------------------------------------------------
+// the distance of (x, y) from the centroid
+VERIFY_RULES_HD inline double centred_length(double x, double y, double cx, double cy)
 {
     VERIFY_RULES_NO_FMA
-    double sum_x = 0.0, sum_y = 0.0, sum_d = 0.0;
-    int64_t n = 0;
-    for (int64_t i = 0; i < m; i++)
-        if (mask[i]) { sum_x += (double)pts[2 * i]; sum_y += (double)pts[2 * i + 1]; n++; }
-    cx = sum_x / (double)n; cy = sum_y / (double)n;
-    for (int64_t i = 0; i < m; i++)
-        if (mask[i]) {
-            const double dx = (double)pts[2 * i] - cx, dy = (double)pts[2 * i + 1] - cy;
-            sum_d += std::sqrt(dx * dx + dy * dy);
-        }
-    const double d = sum_d / (double)n;
+    const double dx = x - cx, dy = y - cy;
+    return __builtin_sqrt(dx * dx + dy * dy);
+}
+
+// Hartley's scale from the mean distance d; false: d is 0 or not finite
+VERIFY_RULES_HD inline bool hartley_scale(double d, double &s)
+{
+    VERIFY_RULES_NO_FMA
     if (!(d > 0.0) || !(d <= kLargestDouble)) return false;
     s = kSqrt2 / d;
+    return true;
+}
+
+// a coordinate of the normalised point
+VERIFY_RULES_HD inline double normalised(double p, double c, double s)
+{
+    VERIFY_RULES_NO_FMA
+    return (p - c) * s;
+}
+
+// what a normalised match (x, y) -> (u, v) adds to the DLT's normal equations: a [0, 8) = a1, a [8, 16) = a2, then u and v
+constexpr int kDltRow = 18;
+VERIFY_RULES_HD inline void dlt_rows(double x, double y, double u, double v, double *a)
+{
+    VERIFY_RULES_NO_FMA
+    a[0] = x; a[1] = y; a[2] = 1.0; a[3] = 0.0; a[4] = 0.0; a[5] = 0.0; a[6] = -(u * x); a[7] = -(u * y);
+    a[8] = 0.0; a[9] = 0.0; a[10] = 0.0; a[11] = x; a[12] = y; a[13] = 1.0; a[14] = -(v * x); a[15] = -(v * y);
+    a[16] = u; a[17] = v;
+}
+
+// one term of N[p][q] (a = a1[p], b = a1[q], c = a2[p], d = a2[q]) or of r[p] (b = u, d = v)
+VERIFY_RULES_HD inline double dlt_add(double acc, double a, double b, double c, double d)
+{
+    VERIFY_RULES_NO_FMA
+    return acc + (a * b + c * d);
+}
+
+// The sums of a round as refit_pairs_kernel spreads them over lanes: sum l adds, match after match, the product(s) of the
+// entries a, b (and c, d) of the match's row.  The homography: l < 64 is N[l / 8][l % 8], l < 72 is r[l - 64] (kDltSums);
+// beyond, a sum nobody reads
+struct Terms { int a, b, c, d; };
+constexpr int kDltSums = 72;
+VERIFY_RULES_HD inline Terms dlt_terms(int l)
+{
+    if (l < 64) return Terms{l >> 3, l & 7, 8 + (l >> 3), 8 + (l & 7)};
+    if (l < kDltSums) return Terms{l - 64, 16, 8 + (l - 64), 17};
+    return Terms{0, 0, 0, 0};
+}
+VERIFY_RULES_HD inline double dlt_add(double acc, const double *row, Terms t) { return dlt_add(acc, row[t.a], row[t.b], row[t.c], row[t.d]); }
+
+// h [8] of the summed normal equations N [8][8] (row-major), r [8], both overwritten: Gaussian elimination with partial
+// pivoting (largest magnitude, lowest row on ties), back-substitution; false: a pivot at or under 1e-12 max |N|
+VERIFY_RULES_HD inline bool dlt_solve(double *N, double *r, double *h)
+{
+    VERIFY_RULES_NO_FMA
+    double nmax = 0.0;
+    for (int i = 0; i < 64; i++) nmax = __builtin_fabs(N[i]) > nmax ? __builtin_fabs(N[i]) : nmax;
+    const double floor_pivot = 1e-12 * nmax;
+    for (int k = 0; k < 8; k++) {
+        int piv = k;
+        double best = __builtin_fabs(N[8 * k + k]);
+        for (int i = k + 1; i < 8; i++)
+            if (__builtin_fabs(N[8 * i + k]) > best) { best = __builtin_fabs(N[8 * i + k]); piv = i; }
+        if (!(best > floor_pivot)) return false;
+        if (piv != k) {
+            for (int q = 0; q < 8; q++) { const double t = N[8 * k + q]; N[8 * k + q] = N[8 * piv + q]; N[8 * piv + q] = t; }
+            const double t = r[k]; r[k] = r[piv]; r[piv] = t;
+        }
+        for (int i = k + 1; i < 8; i++) {
+            const double f = N[8 * i + k] / N[8 * k + k];
+            for (int q = k + 1; q < 8; q++) N[8 * i + q] = N[8 * i + q] - f * N[8 * k + q];
+            r[i] = r[i] - f * r[k];
+        }
+    }
+    for (int i = 7; i >= 0; i--) {
+        double acc = r[i];
+        for (int q = i + 1; q < 8; q++) acc = acc - N[8 * i + q] * h[q];
+        h[i] = acc / N[8 * i + i];
+    }
     return true;
 }
 
@@ -281,52 +352,10 @@ VERIFY_RULES_HD inline void mul3(const double A[9], const double B[9], double C[
         for (int j = 0; j < 3; j++) C[3 * i + j] = (A[3 * i] * B[j] + A[3 * i + 1] * B[3 + j]) + A[3 * i + 2] * B[6 + j];
 }
 
-// one round of the refit on the inliers of mask: H' in H_out; false: rejected, H_out is undefined
-inline bool refit_round(const float *src, const float *dst, int64_t m, const uint8_t *mask, double H_out[9])
+// H' = (Td^-1 Hn) Ts of the solution h [8] (h33 = 1), scaled; false: not finite or zero
+VERIFY_RULES_HD inline bool dlt_denormalise(const double *h, double cxs, double cys, double ss, double cxd, double cyd, double sd, double H_out[9])
 {
     VERIFY_RULES_NO_FMA
-    double cxs, cys, ss, cxd, cyd, sd;
-    if (!hartley(src, mask, m, cxs, cys, ss) || !hartley(dst, mask, m, cxd, cyd, sd)) return false;
-    double N[8][8] = {}, r[8] = {};
-    int64_t first = -1;
-    for (int64_t i = 0; i < m; i++) {
-        if (!mask[i]) continue;
-        if (first < 0) first = i;
-        const double x = ((double)src[2 * i] - cxs) * ss, y = ((double)src[2 * i + 1] - cys) * ss;
-        const double u = ((double)dst[2 * i] - cxd) * sd, v = ((double)dst[2 * i + 1] - cyd) * sd;
-        const double a1[8] = {x, y, 1.0, 0.0, 0.0, 0.0, -(u * x), -(u * y)};
-        const double a2[8] = {0.0, 0.0, 0.0, x, y, 1.0, -(v * x), -(v * y)};
-        for (int p = 0; p < 8; p++) {
-            for (int q = 0; q < 8; q++) N[p][q] = N[p][q] + (a1[p] * a1[q] + a2[p] * a2[q]);
-            r[p] = r[p] + (a1[p] * u + a2[p] * v);
-        }
-    }
-    double nmax = 0.0;
-    for (int p = 0; p < 8; p++)
-        for (int q = 0; q < 8; q++) nmax = std::fabs(N[p][q]) > nmax ? std::fabs(N[p][q]) : nmax;
-    const double floor_pivot = 1e-12 * nmax;
-    for (int k = 0; k < 8; k++) {
-        int piv = k;
-        double best = std::fabs(N[k][k]);
-        for (int i = k + 1; i < 8; i++)
-            if (std::fabs(N[i][k]) > best) { best = std::fabs(N[i][k]); piv = i; }
-        if (!(best > floor_pivot)) return false;
-        if (piv != k) {
-            for (int q = 0; q < 8; q++) { const double t = N[k][q]; N[k][q] = N[piv][q]; N[piv][q] = t; }
-            const double t = r[k]; r[k] = r[piv]; r[piv] = t;
-        }
-        for (int i = k + 1; i < 8; i++) {
-            const double f = N[i][k] / N[k][k];
-            for (int q = k + 1; q < 8; q++) N[i][q] = N[i][q] - f * N[k][q];
-            r[i] = r[i] - f * r[k];
-        }
-    }
-    double h[8];
-    for (int i = 7; i >= 0; i--) {
-        double acc = r[i];
-        for (int q = i + 1; q < 8; q++) acc = acc - N[i][q] * h[q];
-        h[i] = acc / N[i][i];
-    }
     const double Hn[9] = {h[0], h[1], h[2], h[3], h[4], h[5], h[6], h[7], 1.0};
     const double isd = 1.0 / sd;
     const double Tdi[9] = {isd, 0.0, cxd, 0.0, isd, cyd, 0.0, 0.0, 1.0};
@@ -334,12 +363,54 @@ inline bool refit_round(const float *src, const float *dst, int64_t m, const uin
     double T[9];
     mul3(Tdi, Hn, T);
     mul3(T, Ts, H_out);
-    if (!normalise(H_out)) return false;
-    const double W = w_at(H_out, (double)src[2 * first], (double)src[2 * first + 1]);
+    return normalise(H_out);
+}
+
+// the sign of H from W at the first inlier (x, y); false: W is 0
+VERIFY_RULES_HD inline bool dlt_sign(double H[9], double x, double y)
+{
+    const double W = w_at(H, x, y);
     if (W == 0.0) return false;
     if (W < 0.0)
-        for (int i = 0; i < 9; i++) H_out[i] = -H_out[i];
+        for (int i = 0; i < 9; i++) H[i] = -H[i];
     return true;
+}
+
+// Hartley normalisation of the masked points: centroid and scale; false: the mean distance is 0 or not finite
+inline bool hartley(const float *pts, const uint8_t *mask, int64_t m, double &cx, double &cy, double &s)
+{
+    VERIFY_RULES_NO_FMA
+    double sum_x = 0.0, sum_y = 0.0, sum_d = 0.0;
+    int64_t n = 0;
+    for (int64_t i = 0; i < m; i++)
+        if (mask[i]) { sum_x += (double)pts[2 * i]; sum_y += (double)pts[2 * i + 1]; n++; }
+    cx = sum_x / (double)n; cy = sum_y / (double)n;
+    for (int64_t i = 0; i < m; i++)
+        if (mask[i]) sum_d += centred_length((double)pts[2 * i], (double)pts[2 * i + 1], cx, cy);
+    return hartley_scale(sum_d / (double)n, s);
+}
+
+// one round of the refit on the inliers of mask: H' in H_out; false: rejected, H_out is undefined
+inline bool refit_round(const float *src, const float *dst, int64_t m, const uint8_t *mask, double H_out[9])
+{
+    double cxs, cys, ss, cxd, cyd, sd;
+    if (!hartley(src, mask, m, cxs, cys, ss) || !hartley(dst, mask, m, cxd, cyd, sd)) return false;
+    double N[64] = {}, r[8] = {}, h[8];
+    int64_t first = -1;
+    for (int64_t i = 0; i < m; i++) {
+        if (!mask[i]) continue;
+        if (first < 0) first = i;
+        double a[kDltRow];
+        dlt_rows(normalised((double)src[2 * i], cxs, ss), normalised((double)src[2 * i + 1], cys, ss), normalised((double)dst[2 * i], cxd, sd),
+                 normalised((double)dst[2 * i + 1], cyd, sd), a);
+        for (int p = 0; p < 8; p++) {
+            for (int q = 0; q < 8; q++) N[8 * p + q] = dlt_add(N[8 * p + q], a[p], a[q], a[8 + p], a[8 + q]);
+            r[p] = dlt_add(r[p], a[p], a[16], a[8 + p], a[17]);
+        }
+    }
+    if (!dlt_solve(N, r, h)) return false;
+    if (!dlt_denormalise(h, cxs, cys, ss, cxd, cyd, sd, H_out)) return false;
+    return dlt_sign(H_out, (double)src[2 * first], (double)src[2 * first + 1]);
 }
 
 // The acceptance rule of one round: the model M [9] with (mask [m], count) meets the round's Mn [9], scored as (trial [m], c).
@@ -391,6 +462,19 @@ struct Homography {
     static bool refit_round(const float *src, const float *dst, int64_t m, const uint8_t *mask, double H_out[9])
     {
         return verify_rules::refit_round(src, dst, m, mask, H_out);
+    }
+    // The round as refit_pairs_kernel takes a model (and its walk on the CPU, tests/shim/verify_refit_asan_main.cpp): the doubles
+    // of a staged match's row, the sums and their terms, the fewest inliers, and the solve on work = N [64], r [8] summed, h [8]
+    // with the centroids, the scales and the first inlier (fx, fy) of src
+    static constexpr int kRefitRow = kDltRow, kRefitSums = kDltSums, kRefitWork = 64 + 8 + 8;
+    VERIFY_RULES_HD static void refit_row(double x, double y, double u, double v, double *a) { dlt_rows(x, y, u, v, a); }
+    VERIFY_RULES_HD static Terms refit_terms(int l) { return dlt_terms(l); }
+    VERIFY_RULES_HD static double refit_add(double acc, const double *a, Terms t) { return dlt_add(acc, a, t); }
+    VERIFY_RULES_HD static bool refit_few(int) { return false; }
+    VERIFY_RULES_HD static bool refit_solve(double *work, double cxs, double cys, double ss, double cxd, double cyd, double sd, double fx, double fy,
+                                            double H_out[9])
+    {
+        return dlt_solve(work, work + 64, work + 72) && dlt_denormalise(work + 72, cxs, cys, ss, cxd, cyd, sd, H_out) && dlt_sign(H_out, fx, fy);
     }
 };
 

@@ -20,7 +20,16 @@ calls on the same lists in the same process: 72 pairs x 2 000 matches x 2 048 hy
 hypotheses, refine 2, the same planted scenes.  One warm-up each, then three rounds that alternate batch and loop; per side the
 best round and the range, for the kernels (last_kernel_ms, summed over the loop's calls) and for the wall clock around the
 Python call(s).  The answers of the two sides are compared for equality, and the run ends with an error when they differ; the
-last line says whether the batch's slowest wall time is below the loop's fastest on every workload."""
+last line says whether the batch's slowest wall time is below the loop's fastest on every workload.
+
+    verify_bench.py --pairs --device [--fundamental]
+times dlco_desc_verify_pairs_homography_device (_fundamental_device), whose refit rounds run on the device, on lists already in
+device memory against dlco_desc_verify_pairs_homography (_fundamental), whose refit is formed on the host, on the same lists in
+host memory: the two workloads above, refine 2.  Both sides are the library's C calls on arrays prepared beforehand, so neither
+wall time holds the packing of Python lists.  One warm-up each, then three rounds that alternate the two; per side the best round
+and the range, kernels (last_kernel_ms) and wall.  Matrices, masks (read back from device memory after the timing), counts and
+best hypotheses of the two sides must be the same bytes, or the run ends with an error; the last line says whether the device
+form's slowest wall time is below the host form's fastest on every workload."""
 import importlib, os, sys, time
 import numpy as np
 import torch                                                # before libdlco.so: one HIP runtime per process, torch's first
@@ -29,7 +38,8 @@ dlco = importlib.import_module("opencv-dlco_amd")
 
 FUNDAMENTAL = "--fundamental" in sys.argv[1:]
 PAIRS = "--pairs" in sys.argv[1:]
-args = [a for a in sys.argv[1:] if a not in ("--fundamental", "--pairs")]
+DEVICE = "--device" in sys.argv[1:]
+args = [a for a in sys.argv[1:] if a not in ("--fundamental", "--pairs", "--device")]
 reps = int(args[0]) if args else 15
 OPS_PER_PAIR, THRESHOLD = (33.0, 1.0) if FUNDAMENTAL else (19.0, 3.0)
 OPS_PER_SECOND = 256 * 64 * 2.4e9
@@ -137,8 +147,62 @@ def pairs_bench():
     ctx.close()
 
 
+def device_bench():
+    import ctypes as C
+    ctx = dlco.DescContext()
+    name = "fundamental" if FUNDAMENTAL else "homography"
+    host_call = getattr(ctx.L, f"dlco_desc_verify_pairs_{name}")
+    dev_call = getattr(ctx.L, f"dlco_desc_verify_pairs_{name}_device")
+    ptr = lambda a, t: a.ctypes.data_as(C.POINTER(t))
+    print(f"verify_pairs_{name}_device on lists in device memory against verify_pairs_{name} on the same lists in host memory: "
+          f"best of 3 alternating rounds (min .. max), threshold {THRESHOLD}, refine 2")
+    print("| pairs | m | n_hyp | device kernels | host kernels | device wall | host wall | wall ratio | inliers |")
+    print("|---|---|---|---|---|---|---|---|---|")
+    faster = True
+    for P, m, n_hyp in ((72, 2000, 2048), (1056, 500, 1024)):
+        rng = np.random.default_rng(P)
+        lists = [(two_cameras if FUNDAMENTAL else planted)(m, rng) for _ in range(P)]
+        src, dst = (np.ascontiguousarray(np.concatenate([l[k] for l in lists])) for k in (0, 1))
+        moff = (np.arange(P + 1) * m).astype(np.int64)
+        tsrc, tdst = torch.from_numpy(src).to("cuda"), torch.from_numpy(dst).to("cuda")
+        tmask = torch.zeros(P * m, dtype=torch.uint8, device="cuda")
+        torch.cuda.synchronize()
+        out = {side: (np.zeros((P, 9)), np.zeros(P * m, np.uint8), np.zeros(P, np.int64), np.zeros(P, np.int32)) for side in ("device", "host")}
+
+        def run(side):
+            M, mask, n, best = out[side]
+            a, b, k = (tsrc.data_ptr(), tdst.data_ptr(), tmask.data_ptr()) if side == "device" else (ptr(src, C.c_float), ptr(dst, C.c_float), ptr(mask, C.c_uint8))
+            t0 = time.perf_counter()
+            rc = (dev_call if side == "device" else host_call)(ctx.h, a, b, ptr(moff, C.c_int64), P, THRESHOLD, n_hyp, 0, 2, ptr(M, C.c_double), k,
+                                                               ptr(n, C.c_int64), ptr(best, C.c_int32))
+            wall = 1e3 * (time.perf_counter() - t0)
+            if rc != 0:
+                sys.exit(f"verify_bench: the {side} form failed: {ctx.L.dlco_desc_last_error(ctx.h).decode()}")
+            return wall, ctx.last_kernel_ms()
+
+        def compare():
+            (Md, _, nd, bd), (Mh, kh, nh, bh) = out["device"], out["host"]
+            if not (Md.tobytes() == Mh.tobytes() and tmask.cpu().numpy().tobytes() == kh.tobytes() and nd.tobytes() == nh.tobytes() and bd.tobytes() == bh.tobytes()):
+                sys.exit("verify_bench: the device form's answer differs from the host form's")
+
+        run("device"), run("host")                             # the warm-up of each side, and the comparison
+        compare()
+        d, h = [], []
+        for _ in range(3):
+            d.append(run("device"))
+            h.append(run("host"))
+        compare()
+        (dw, dk), (hw, hk) = (np.array(x).T for x in (d, h))
+        row = lambda a: f"{a.min():.3f} ms ({a.min():.3f} .. {a.max():.3f})"
+        print(f"| {P} | {m} | {n_hyp} | {row(dk)} | {row(hk)} | {row(dw)} | {row(hw)} | {hw.min() / dw.min():.1f}x | {int(out['host'][2].sum())} of {P * m} |")
+        faster = faster and dw.max() < hw.min()
+    print("the device form's slowest wall time is below the host form's fastest on every workload" if faster
+          else "the device form did NOT beat the host form by more than the spread")
+    ctx.close()
+
+
 if PAIRS:
-    pairs_bench()
+    device_bench() if DEVICE else pairs_bench()
     sys.exit(0)
 
 ctx = dlco.DescContext()
