@@ -1026,6 +1026,44 @@ int  dlco_desc_select_pairs_u8_device(dlco_desc_ctx *ctx, const int64_t *seg, in
  * the refit and the step kernel; verify_pairs_refit_round its one refit launch per launch of the plan); after a select_pairs call, float or _u8, its kernels
  * (the flags, the scan of the block counts, the scatter, the match offsets; 0 when the batch has no row) */
 double dlco_desc_last_kernel_ms(const dlco_desc_ctx *ctx);
+/* ---- Building tracks: from the match lists and inlier masks of many ordered pairs to the keypoints that are one scene point
+ * across all images, the step behind dlco_desc_select_pairs* and dlco_desc_verify_pairs_*, on the device, so that a caller whose
+ * lists live in HBM need not download them, run a union-find and upload the result.  csrc/track_rules.hpp states the rule.
+ *   Input: seg, n_img, pairs, n_pairs as the match_pairs call took them; moff [n_pairs + 1] and matches [M][2] int32,
+ * M = moff[n_pairs], as dlco_desc_select_pairs* wrote them; keep [M] (may be NULL: every match counts), 0 / non-zero, the inlier
+ * mask as dlco_desc_verify_pairs_* wrote it.  seg, pairs, moff, n_tracks and counts are host memory in every form.
+ *     Nodes: the rows of the batch's table, N = seg[n_img]; row i of image a is node seg[a] + i.
+ *     Edges: match m of pair p = (a, b) with matches[m] = (i, j) joins the nodes seg[a] + i and seg[b] + j.  It is skipped, not
+ *   an error, if keep != NULL && keep[m] == 0, or if i or j lies outside its image, decided before anything is indexed with it:
+ *   no content of matches makes the call read or write outside a buffer.  Duplicate edges, both directions of a pair and
+ *   edges with equal ends are harmless.
+ *     label[g] is the smallest node of g's connected component.  A track is a component of at least min_len nodes
+ *   (min_len >= 2) and, when unique != 0, without two nodes in one image; a conflicting component is dropped whole.
+ *   Output: counts[0] the components of at least 2 nodes, counts[1] those of fewer than min_len nodes, counts[2] those of at
+ * least min_len nodes dropped for a conflict; *n_tracks = counts[0] - counts[1] - counts[2].  Tracks ascend in label and,
+ * inside a track, nodes ascend in id, so images ascend as well: toff [n_tracks + 1] int64 with toff[0] = 0, obs [toff[n_tracks]]
+ * int32 node ids, track_of [N] int32 the node's track or -1, label [N] int32 (may be NULL).  The caller provides N / 2 + 1 entries
+ * of toff and N of obs; entries beyond those used are not touched.  Everything is an integer or a comparison: no result depends
+ * on the order of the matches, on scheduling or on the run.  M = 0, N = 0, empty images and pairs without a match are normal:
+ * *n_tracks = 0, toff[0] = 0, track_of all -1.
+ *   The device form reads matches_dev and keep_dev and writes toff_dev, obs_dev, track_of_dev and label_dev in device memory;
+ * it is queued on the context's stream and synchronised on return, and only n_tracks and counts cross to the host.  The host
+ * form uploads, runs the same kernels and downloads.  Like the matcher, the calls use the context for its device, stream and
+ * scratch only.  After either, dlco_desc_last_kernel_ms is the time of the call's kernels (the union-find, the labels, the
+ * sort of the nodes by label, the flags, the scan and the scatter; 0 when the batch has no node).
+ *   DLCO_ERR_INVALID, before the handle is used and with no output touched: a null handle or required pointer (seg, pairs,
+ * moff, matches, n_tracks, toff, obs, track_of, counts), whatever dlco_desc_match_pairs rejects of seg / pairs (but a table of
+ * no rows, seg all zero, is a batch here), moff[0] != 0 or a decreasing moff, M or N >= 2^31, min_len < 2, unique not 0 or 1.
+ *   Out of scope: seg / pairs / moff in device memory; splitting a conflicting component instead of dropping it; a min_len per
+ * pair; triangulation. ---- */
+int  dlco_desc_build_tracks(dlco_desc_ctx *ctx, const int64_t *seg, int32_t n_img, const int32_t *pairs, int64_t n_pairs,
+                            const int64_t *moff, const int32_t *matches_host, const uint8_t *keep_host, int32_t min_len, int32_t unique,
+                            int64_t *n_tracks, int64_t *toff_host, int32_t *obs_host, int32_t *track_of_host, int32_t *label_host,
+                            int64_t counts[3]);
+int  dlco_desc_build_tracks_device(dlco_desc_ctx *ctx, const int64_t *seg, int32_t n_img, const int32_t *pairs, int64_t n_pairs,
+                                   const int64_t *moff, const int32_t *matches_dev, const uint8_t *keep_dev, int32_t min_len,
+                                   int32_t unique, int64_t *n_tracks, int64_t *toff_dev, int32_t *obs_dev, int32_t *track_of_dev,
+                                   int32_t *label_dev, int64_t counts[3]);
 
 #ifdef __cplusplus
 }

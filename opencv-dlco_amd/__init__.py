@@ -95,6 +95,24 @@ f64p = C.POINTER(C.c_double)
 # the matcher's two lines: the tables' element type and pointer, the distances' type and pointer, the suffix of the C names
 _Line = collections.namedtuple("_Line", "dtype ptr dist dptr suffix")
 _FLOAT, _BYTE = _Line(np.float32, f32p, np.float32, f32p, ""), _Line(np.uint8, u8p, np.int32, i32p, "_u8")
+# what DescContext.build_tracks returns: toff [n_tracks + 1] int64, obs [toff[-1]] int32 node ids, track_of [N] int32, label [N]
+# int32, counts [3] int64 (csrc/track_rules.hpp), seg [n_img + 1] int64 the nodes' images; images() and rows() split obs
+class Tracks(collections.namedtuple("Tracks", "toff obs track_of label counts seg")):
+    __slots__ = ()
+
+    @property
+    def n_tracks(self):
+        return self.toff.size - 1
+
+    def images(self):
+        """the image of every observation, [len(obs)] int32"""
+        return (np.searchsorted(self.seg, self.obs, side="right") - 1).astype(np.int32)
+
+    def rows(self):
+        """the row of every observation inside its image, [len(obs)] int32"""
+        return (self.obs - self.seg[self.images()]).astype(np.int32)
+
+
 
 
 def load():
@@ -237,6 +255,8 @@ def load():
     L.dlco_desc_select_pairs_device.argtypes = [vp, i64p, C.c_int32, i32p, i64, vp, vp, C.c_float, vp, i64p, i64, vp, i64, i64p, vp, vp, vp, vp]
     L.dlco_desc_select_pairs_u8.argtypes = [vp, i64p, C.c_int32, i32p, i64, i32p, i32p, C.c_float, i32p, i64p, i64, f32p, i64p, i32p, i32p, f32p, f32p]
     L.dlco_desc_select_pairs_u8_device.argtypes = L.dlco_desc_select_pairs_device.argtypes
+    L.dlco_desc_build_tracks.argtypes = [vp, i64p, C.c_int32, i32p, i64, i64p, i32p, u8p, C.c_int32, C.c_int32, i64p, i64p, i32p, i32p, i32p, i64p]
+    L.dlco_desc_build_tracks_device.argtypes = [vp, i64p, C.c_int32, i32p, i64, i64p, vp, vp, C.c_int32, C.c_int32, i64p, vp, vp, vp, vp, i64p]
     L.dlco_desc_match_pairs_guided.argtypes = [vp, f32p, f32p, i64p, C.c_int32, i32p, i64, C.c_int32, f64p, C.c_float, C.c_int32, i32p, f32p]
     L.dlco_desc_match_pairs_guided_device.argtypes = [vp, vp, i64, vp, i64, i64p, C.c_int32, i32p, i64, C.c_int32, f64p, C.c_float, C.c_int32,
                                                       vp, vp]
@@ -1562,6 +1582,60 @@ class DescContext:
         """select_pairs_device on the answer of match_pairs_u8_device: int32 distances in and out."""
         return self._select_pairs_device(_BYTE, idx_ptr, d_ptr, seg, pairs, matches_ptr, dist_ptr, ratio,
                                          back_idx_ptr, back_row0, n_back_rows, xy_ptr, ldxy, src_ptr, dst_ptr)
+
+    # ---- building tracks: from the match lists and masks of many pairs to the keypoints that are one scene point (csrc/track_rules.hpp) ----
+    @staticmethod
+    def _tracks_seg(sizes_or_seg, q):
+        """seg [n_img + 1] from seg itself or from the row counts of the images [n_img]: the array is seg when it starts at 0,
+        never decreases and has an entry more than the images the pairs name need; pass seg where that could be in doubt."""
+        s = np.ascontiguousarray(sizes_or_seg, np.int64)
+        assert s.ndim == 1 and s.size >= 1
+        n_named = int(q.max()) + 1 if q.size else 1
+        if s.size >= n_named + 1 and s[0] == 0 and (np.diff(s) >= 0).all():
+            return s
+        return np.concatenate([[0], np.cumsum(s)]).astype(np.int64)
+
+    def build_tracks(self, matches, moff, sizes_or_seg, pairs, keep=None, min_len=2, unique=True):
+        """The tracks across the images of a batch: matches [M, 2] int32 of (query row, train row) and moff [n_pairs + 1] as
+        select_pairs_device wrote them (or the per-pair lists select_pairs returns, concatenated), sizes_or_seg the row counts of
+        the images [n_img] or seg [n_img + 1], pairs [n_pairs, 2], keep [M] the inlier mask of verify_pairs_* (None: every match
+        counts).  A node is a row of the batch's table, seg[a] + i; a track is a connected component of at least min_len nodes
+        and, with unique, without two nodes in one image.  Returns Tracks(toff, obs, track_of, label, counts, seg): tracks
+        ascend in their smallest node, nodes ascend inside a track."""
+        q = np.ascontiguousarray(pairs, np.int32)
+        assert q.ndim == 2 and q.shape[1] == 2
+        seg = self._tracks_seg(sizes_or_seg, q)
+        o = np.ascontiguousarray(moff, np.int64)
+        assert o.shape == (q.shape[0] + 1,)
+        M, N = int(o[-1]) if o.size else 0, int(seg[-1])
+        m = np.ascontiguousarray(np.concatenate([np.reshape(np.asarray(matches, np.int32), (-1, 2)), np.zeros((1, 2), np.int32)]))
+        assert m.shape[0] == M + 1, "build_tracks: matches and moff disagree"
+        k = None
+        if keep is not None:
+            k = np.ascontiguousarray(np.concatenate([np.reshape(np.asarray(keep), -1) != 0, [False]]).astype(np.uint8))
+            assert k.size == M + 1, "build_tracks: keep and moff disagree"
+        nt, counts = np.zeros(1, np.int64), np.zeros(3, np.int64)
+        toff, obs, track_of, label = np.empty(N // 2 + 1, np.int64), np.empty(N + 1, np.int32), np.full(N + 1, -1, np.int32), np.empty(N + 1, np.int32)
+        self._ck(self.L.dlco_desc_build_tracks(self.h, _p(seg, i64p), seg.size - 1, _p(q, i32p), q.shape[0], _p(o, i64p), _p(m, i32p), _p(k, u8p), min_len,
+                                               1 if unique else 0, _p(nt, i64p), _p(toff, i64p), _p(obs, i32p), _p(track_of, i32p), _p(label, i32p),
+                                               _p(counts, i64p)))
+        T = int(nt[0])
+        return Tracks(toff[:T + 1].copy(), obs[:toff[T]].copy(), track_of[:N], label[:N], counts, seg)
+
+    def build_tracks_device(self, matches_ptr, moff, seg, pairs, toff_ptr, obs_ptr, track_of_ptr, keep_ptr=None, label_ptr=None, min_len=2, unique=True):
+        """build_tracks on lists in device memory: matches [M, 2] int32 as select_pairs_device wrote them for seg and pairs, moff
+        [n_pairs + 1] as it returned it, keep [M] uint8 as verify_pairs_*_device wrote inlier_ptr (None: every match counts).
+        The outputs go to device memory: toff [N // 2 + 1] int64, obs [N] int32, track_of [N] int32 and, if asked for, label [N]
+        int32, N = seg[-1].  Returns (n_tracks, counts [3] int64); toff[:n_tracks + 1] and obs[:toff[n_tracks]] are written."""
+        s, q = _seg_pairs(seg, pairs)
+        o = np.ascontiguousarray(moff, np.int64)
+        assert o.shape == (q.shape[0] + 1,)
+        nt, counts = np.zeros(1, np.int64), np.zeros(3, np.int64)
+        ptr = lambda a: None if a is None else C.c_void_p(a)
+        self._ck(self.L.dlco_desc_build_tracks_device(self.h, _p(s, i64p), s.size - 1, _p(q, i32p), q.shape[0], _p(o, i64p), ptr(matches_ptr), ptr(keep_ptr),
+                                                      min_len, 1 if unique else 0, _p(nt, i64p), ptr(toff_ptr), ptr(obs_ptr), ptr(track_of_ptr),
+                                                      ptr(label_ptr), _p(counts, i64p)))
+        return int(nt[0]), counts
 
     def match_pairs_slices(self, seg, pairs, u8=False):
         """The plan only: slices [n_pairs] int32 of train that each pair is cut into in such a call on this context's device

@@ -184,6 +184,23 @@ void read_dataset(const std::string &path, const char *name, std::vector<size_t>
     }
 }
 
+// Is there a dataset `name` at `path`?  A file or directory that cannot be opened has none.
+inline bool has_dataset(const std::string &path, const char *name)
+{
+    if (is_h5(path)) {
+        H5 &L = h5();
+        if (!L.load()) throw std::runtime_error("HDF5 input requested but libhdf5 could not be loaded (set DLCO_HDF5_LIB, or pass a directory of .npy files)");
+        const H5::hid_t f = L.H5Fopen(path.c_str(), 0, 0);
+        if (f < 0) return false;
+        const bool there = L.H5Lexists(f, name, 0) > 0;
+        L.H5Fclose(f);
+        return there;
+    }
+    std::FILE *f = std::fopen((path + "/" + name + ".npy").c_str(), "rb");
+    if (f) std::fclose(f);
+    return f != nullptr;
+}
+
 struct Writer {
     std::string path;
     H5::hid_t f = -1;

@@ -6,7 +6,8 @@
 // quantisation of rows to bytes (quant_rules.hpp) and the match of byte tables in kernels_match_u8.hip, the detection of
 // keypoints (detect_rules.hpp) in kernels_detect.hip, their orientation (orient_rules.hpp) in kernels_orient.hip, the
 // verification of a match list against a homography (verify_rules.hpp) or a fundamental matrix (epipolar_rules.hpp) in
-// kernels_verify.hip, the selection of matches from a batched answer (select_rules.hpp) in kernels_select.hip.
+// kernels_verify.hip, the selection of matches from a batched answer (select_rules.hpp) in kernels_select.hip, the tracks
+// across the verified matches of many pairs (track_rules.hpp) in kernels_tracks.hip.
 // compute() serves every describe call: a PatchSource in, the rows a RowsOut names out.  The float and the byte matcher
 // share one host path (match_host, match_device) over a FloatLine / ByteLine.
 #include "../../include/dlco.h"
@@ -116,6 +117,15 @@ struct dlco_desc_ctx {
     DevBuf<int32_t> s_count, s_idx, s_sqdist, s_back, s_matches, s_dist;
     DevBuf<int64_t> s_off, s_moff;
     DevBuf<float> s_xy, s_src, s_dst;
+    // building tracks (dlco_desc_build_tracks*, track_rules.hpp): the uploaded pairs and seg, the union-find's parent, the
+    // labels when the caller wants none, the nodes and labels before and after the sort with its workspace, the components'
+    // sizes and conflicts, the kept nodes and heads as bits, the block counts, their exclusive sums and the five totals; for the
+    // host form the uploaded matches and mask and the outputs on their way down; buffers of their own
+    DevBuf<track_rules::Pair> t_pairs;
+    DevBuf<int64_t> t_seg, t_off, t_total, t_toff;
+    DevBuf<int32_t> t_parent, t_label, t_node, t_slabel, t_snode, t_size, t_count, t_matches, t_obs, t_track_of;
+    DevBuf<uint8_t> t_conf, t_tmp, t_keep;
+    DevBuf<uint64_t> t_word;
     double last_ms = 0.0;
 };
 
@@ -678,6 +688,130 @@ int select_pairs_host_call(dlco_desc_ctx *c, const SelectArgs &a, const int32_t 
                 DLCO_HIP(hipMemcpyAsync(src_host, c->s_src.p, (size_t)M * 2 * sizeof(float), hipMemcpyDeviceToHost, c->stream));
                 DLCO_HIP(hipMemcpyAsync(dst_host, c->s_dst.p, (size_t)M * 2 * sizeof(float), hipMemcpyDeviceToHost, c->stream));
             }
+            sync(c);
+        }
+    });
+}
+
+// ---- building tracks (dlco_desc_build_tracks*): from the match lists and masks of many pairs to the tracks across all images,
+// by the rule of track_rules.hpp in kernels_tracks.hip.  The host form is the device path between an upload and a download ---
+struct TracksArgs {
+    const int64_t *seg; int32_t n_img;
+    const int32_t *pairs; int64_t n_pairs;
+    const int64_t *moff;
+    int32_t min_len, unique;
+    int64_t *n_tracks, *counts;
+};
+
+// seg / pairs as dlco_desc_match_pairs checks them, except that a table of no rows is a batch like another here
+bool tracks_args_ok(const TracksArgs &a, const void *matches, const void *toff, const void *obs, const void *track_of)
+{
+    if (!a.seg || !a.pairs || !a.moff || !matches || !a.n_tracks || !a.counts || !toff || !obs || !track_of) return false;
+    if (a.n_img >= 1 && a.seg[0] == 0 && a.seg[a.n_img] == 0) {
+        for (int32_t i = 0; i < a.n_img; i++)
+            if (a.seg[i + 1] != 0) return false;
+        if (a.n_pairs < 1 || a.n_pairs >= ((int64_t)1 << 31)) return false;
+        for (int64_t p = 0; p < 2 * a.n_pairs; p++)
+            if (a.pairs[p] < 0 || a.pairs[p] >= a.n_img) return false;
+    } else if (!match_pairs_args_ok(a.seg, a.n_img, a.pairs, a.n_pairs)) {
+        return false;
+    }
+    return a.seg[a.n_img] < ((int64_t)1 << 31) && track_rules::moff_ok(a.moff, a.n_pairs) && track_rules::settings_ok(a.min_len, a.unique);
+}
+
+// every list in device memory: the kernels, timed, and the download of the five totals behind them
+void tracks_on_device(dlco_desc_ctx *c, const TracksArgs &a, const int32_t *matches, const uint8_t *keep, int64_t *toff, int32_t *obs,
+                      int32_t *track_of, int32_t *label)
+{
+    const int64_t N = a.seg[a.n_img], M = a.moff[a.n_pairs], P = a.n_pairs;
+    if (N == 0) {                                          // no node: no track, nothing to launch
+        DLCO_HIP(hipMemsetAsync(toff, 0, sizeof(int64_t), c->stream));
+        sync(c);
+        *a.n_tracks = 0;
+        a.counts[0] = a.counts[1] = a.counts[2] = 0;
+        c->last_ms = 0.0;
+        return;
+    }
+    std::vector<track_rules::Pair> rec;
+    track_rules::pair_records(a.seg, a.pairs, P, a.moff, rec);
+    const int64_t nb = track_rules::blocks(N);
+    const size_t tmp_bytes = tracks_sort_bytes(N);
+    c->t_pairs.alloc((size_t)P);
+    c->t_seg.alloc((size_t)a.n_img + 1);
+    c->t_parent.alloc((size_t)N);
+    if (!label) { c->t_label.alloc((size_t)N); label = c->t_label.p; }
+    c->t_node.alloc((size_t)N);
+    c->t_slabel.alloc((size_t)N);
+    c->t_snode.alloc((size_t)N);
+    c->t_size.alloc((size_t)N);
+    c->t_conf.alloc((size_t)N);
+    c->t_tmp.alloc(std::max<size_t>(tmp_bytes, 1));
+    c->t_word.alloc((size_t)nb * 2 * (track_rules::kBlockNodes / 64));
+    c->t_count.alloc((size_t)nb * track_rules::kCounted);
+    c->t_off.alloc((size_t)(nb + 1) * track_rules::kCounted);
+    c->t_total.alloc(track_rules::kCounted);
+    DLCO_HIP(hipMemcpyAsync(c->t_pairs.p, rec.data(), (size_t)P * sizeof(track_rules::Pair), hipMemcpyHostToDevice, c->stream));
+    DLCO_HIP(hipMemcpyAsync(c->t_seg.p, a.seg, ((size_t)a.n_img + 1) * sizeof(int64_t), hipMemcpyHostToDevice, c->stream));
+    int64_t total[track_rules::kCounted] = {0, 0, 0, 0, 0};
+    EventPair ev;
+    c->last_ms = timed_ms(c, ev, [&] {
+        tracks_labels(c->t_pairs.p, P, N, M, matches, keep, c->t_parent.p, c->t_node.p, c->t_conf.p, label, c->stream);
+        tracks_group(N, label, c->t_node.p, c->t_seg.p, a.n_img, a.min_len, a.unique, c->t_slabel.p, c->t_snode.p, c->t_size.p, c->t_conf.p, c->t_tmp.p,
+                     tmp_bytes, c->t_word.p, c->t_count.p, c->t_off.p, c->t_total.p, toff, obs, track_of, c->stream);
+    }, [&] { DLCO_HIP(hipMemcpyAsync(total, c->t_total.p, sizeof(total), hipMemcpyDeviceToHost, c->stream)); });
+    *a.n_tracks = total[1];
+    a.counts[0] = total[2];
+    a.counts[1] = total[3];
+    a.counts[2] = total[4];
+}
+
+int build_tracks_device_call(dlco_desc_ctx *c, const TracksArgs &a, const int32_t *matches_dev, const uint8_t *keep_dev, int64_t *toff_dev,
+                             int32_t *obs_dev, int32_t *track_of_dev, int32_t *label_dev)
+{
+    if (!c || !tracks_args_ok(a, matches_dev, toff_dev, obs_dev, track_of_dev)) return DLCO_ERR_INVALID;
+    return guarded(c, [&] {
+        DLCO_HIP(hipSetDevice(c->device));
+        tracks_on_device(c, a, matches_dev, keep_dev, toff_dev, obs_dev, track_of_dev, label_dev);
+    });
+}
+
+// the host form: matches and mask go up once; toff [n_tracks + 1], the observations, track_of and label come down
+int build_tracks_host_call(dlco_desc_ctx *c, const TracksArgs &a, const int32_t *matches_host, const uint8_t *keep_host, int64_t *toff_host,
+                           int32_t *obs_host, int32_t *track_of_host, int32_t *label_host)
+{
+    if (!c || !tracks_args_ok(a, matches_host, toff_host, obs_host, track_of_host)) return DLCO_ERR_INVALID;
+    return guarded(c, [&] {
+        DLCO_HIP(hipSetDevice(c->device));
+        const int64_t N = a.seg[a.n_img], M = a.moff[a.n_pairs];
+        if (N == 0) {
+            *a.n_tracks = 0;
+            a.counts[0] = a.counts[1] = a.counts[2] = 0;
+            toff_host[0] = 0;
+            c->last_ms = 0.0;
+            return;
+        }
+        try {
+            c->t_matches.alloc((size_t)std::max<int64_t>(M, 1) * 2);
+            if (keep_host) c->t_keep.alloc((size_t)std::max<int64_t>(M, 1));
+            c->t_toff.alloc((size_t)N / 2 + 1);
+            c->t_obs.alloc((size_t)N);
+            c->t_track_of.alloc((size_t)N);
+            if (label_host) c->t_label.alloc((size_t)N);
+        } catch (const Error &e) {
+            throw Error(DLCO_ERR_HIP, std::string("dlco_desc_build_tracks: the lists do not fit in device memory: ") + e.what());
+        }
+        if (M > 0) {
+            DLCO_HIP(hipMemcpyAsync(c->t_matches.p, matches_host, (size_t)M * 2 * sizeof(int32_t), hipMemcpyHostToDevice, c->stream));
+            if (keep_host) DLCO_HIP(hipMemcpyAsync(c->t_keep.p, keep_host, (size_t)M, hipMemcpyHostToDevice, c->stream));
+        }
+        tracks_on_device(c, a, c->t_matches.p, keep_host ? c->t_keep.p : nullptr, c->t_toff.p, c->t_obs.p, c->t_track_of.p, label_host ? c->t_label.p : nullptr);
+        const int64_t T = *a.n_tracks;
+        DLCO_HIP(hipMemcpyAsync(toff_host, c->t_toff.p, (size_t)(T + 1) * sizeof(int64_t), hipMemcpyDeviceToHost, c->stream));
+        DLCO_HIP(hipMemcpyAsync(track_of_host, c->t_track_of.p, (size_t)N * sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
+        if (label_host) DLCO_HIP(hipMemcpyAsync(label_host, c->t_label.p, (size_t)N * sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
+        sync(c);
+        if (toff_host[T] > 0) {
+            DLCO_HIP(hipMemcpyAsync(obs_host, c->t_obs.p, (size_t)toff_host[T] * sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
             sync(c);
         }
     });
@@ -2153,6 +2287,22 @@ int dlco_desc_select_pairs_u8_device(dlco_desc_ctx *c, const int64_t *seg, int32
                                              back_idx_dev, xy_dev, ldxy, matches_dev, dist_dev, src_xy_dev, dst_xy_dev);
 }
 
+int dlco_desc_build_tracks(dlco_desc_ctx *c, const int64_t *seg, int32_t n_img, const int32_t *pairs, int64_t n_pairs, const int64_t *moff,
+                           const int32_t *matches_host, const uint8_t *keep_host, int32_t min_len, int32_t unique, int64_t *n_tracks, int64_t *toff_host,
+                           int32_t *obs_host, int32_t *track_of_host, int32_t *label_host, int64_t counts[3])
+{
+    return build_tracks_host_call(c, TracksArgs{seg, n_img, pairs, n_pairs, moff, min_len, unique, n_tracks, counts}, matches_host, keep_host, toff_host,
+                                  obs_host, track_of_host, label_host);
+}
+
+int dlco_desc_build_tracks_device(dlco_desc_ctx *c, const int64_t *seg, int32_t n_img, const int32_t *pairs, int64_t n_pairs, const int64_t *moff,
+                                  const int32_t *matches_dev, const uint8_t *keep_dev, int32_t min_len, int32_t unique, int64_t *n_tracks,
+                                  int64_t *toff_dev, int32_t *obs_dev, int32_t *track_of_dev, int32_t *label_dev, int64_t counts[3])
+{
+    return build_tracks_device_call(c, TracksArgs{seg, n_img, pairs, n_pairs, moff, min_len, unique, n_tracks, counts}, matches_dev, keep_dev, toff_dev,
+                                    obs_dev, track_of_dev, label_dev);
+}
+
 int dlco_desc_cross_sqdists_u8(dlco_desc_ctx *c, const uint8_t *query_u8, int64_t nq, const uint8_t *train_u8, int64_t nt, int32_t r,
                                int32_t *out_host)
 {
@@ -2169,7 +2319,8 @@ int dlco_desc_cross_sqdists_u8(dlco_desc_ctx *c, const uint8_t *query_u8, int64_
 // call formed it; after a detect call the detector's kernels (the integral image when the call
 // formed it, the octaves, the selection); after a verify or verify_pairs call every kernel of every launch of the call: for
 // the _hypotheses forms the hypotheses and the scoring, for the model forms these, the selection, the mask of the best models
-// and the mask launches of the lockstep refit rounds; after a select_pairs call its four kernels (flag, scan, scatter, offsets)
+// and the mask launches of the lockstep refit rounds; after a select_pairs call its four kernels (flag, scan, scatter, offsets);
+// after a build_tracks call its kernels and the sort between them
 double dlco_desc_last_kernel_ms(const dlco_desc_ctx *c) { return c ? c->last_ms : 0.0; }
 
 }  // extern "C"

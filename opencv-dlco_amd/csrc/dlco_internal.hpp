@@ -6,6 +6,7 @@
 #include "match_batch.hpp"
 #include "match_slices.hpp"
 #include "select_rules.hpp"
+#include "track_rules.hpp"
 #include "verify_batch.hpp"
 
 #include <hip/hip_runtime.h>
@@ -653,5 +654,18 @@ template <typename Dist>
 void select_scatter(const select_rules::Pair *pairs, int64_t n_pairs, int64_t R, const int32_t *idx, const Dist *sqdist, const uint64_t *word,
                     const int64_t *off, const float *xy, int64_t ldxy, int32_t *matches, Dist *dist, float *src, float *dst, hipStream_t s);
 void select_offsets(const select_rules::Pair *pairs, int64_t n_pairs, int64_t R, const uint64_t *word, const int64_t *off, int64_t *moff, hipStream_t s);
+
+// building tracks (kernels_tracks.hip; the rule is track_rules.hpp): the two halves of a dlco_desc_build_tracks* call over the
+// N >= 1 nodes of a batch, every table in device memory.  tracks_labels: pairs [n_pairs] = track_rules::pair_records, matches
+// [M][2], keep [M] or null, M may be 0; parent, node, conf [N] are written (node = 0 .. N - 1, conf = 0) and label [N] is the
+// smallest node of every node's component.  tracks_group: from label and node to toff, obs, track_of; seg [n_img + 1] in device
+// memory, slabel, snode, size [N] scratch, tmp tracks_sort_bytes(N) bytes, word [2][blocks][4], count [5][blocks],
+// off [5][blocks + 1], blocks = track_rules::blocks(N); total [5] = observations, tracks, counts [0 .. 2]
+size_t tracks_sort_bytes(int64_t N);
+void tracks_labels(const track_rules::Pair *pairs, int64_t n_pairs, int64_t N, int64_t M, const int32_t *matches, const uint8_t *keep, int32_t *parent,
+                   int32_t *node, uint8_t *conf, int32_t *label, hipStream_t s);
+void tracks_group(int64_t N, const int32_t *label, const int32_t *node, const int64_t *seg, int32_t n_img, int32_t min_len, int32_t unique,
+                  int32_t *slabel, int32_t *snode, int32_t *size, uint8_t *conf, void *tmp, size_t tmp_bytes, uint64_t *word, int32_t *count,
+                  int64_t *off, int64_t *total, int64_t *toff, int32_t *obs, int32_t *track_of, hipStream_t s);
 
 }  // namespace dlco
